@@ -4,6 +4,8 @@ full D3Feat U-Net forward+backward on one fragment pair (~19k + 19k points, 32-d
 radius search + grid subsampling ON THE DEVICE, SGD step included.
 
     python bench.py --gpus 1 --steps 20 --warmup 5            # default: 4 graphs in flight x 3 stacked pairs per GPU
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     # + every leg reported next to `value` (see --full)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -285,6 +287,34 @@ def cpu_baseline(item, cfg, limits, budget_s=90.0):
                       "reference's mode, config.py:86)" % (n_warm, len(serial), mcol, best, mnet, workers)}
 
 
+DUMP_SAMPLE = 1 << 21    # positions of the flat parameter / gradient vectors written by --dump-outputs
+
+
+def dump_outputs(out_dir, outs, ts, lanes):
+    """--dump-outputs: what the last timed step computed, for comparing two builds output for output.  That step starts
+    from the initial parameters and momentum (see start_state in main), so its inputs are the same in every run.
+      pair_losses.npy   float64 [pairs of the step, 3]: descriptor loss, detector loss, accuracy of every pair, lane by lane
+      lane_loss.npy     float64 [lanes]: the loss each network graph back-propagated (the sum over its stacked pairs)
+      params_sample.npy float32 [DUMP_SAMPLE]: the flat parameter vector after the step's update, at a fixed seeded
+                        sample of positions (the whole vector is ~97 MB)
+      grad_sample.npy   float64 [DUMP_SAMPLE]: the gradient buffers the update read (every lane's, summed), same positions"""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    lane_loss = np.array([float(o[0].item()) for o in outs], np.float64)
+    pair_losses = np.concatenate([np.stack([o[i].detach().double().reshape(-1).cpu().numpy() for i in (1, 2, 3)], 1)
+                                  for o in outs], 0)
+    flat = ts.flat
+    n = int(flat.data.numel())
+    pos = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    pos = torch.from_numpy(pos).to(flat.data.device)
+    grads = [flat.lanes[0][0]] if lanes is None or lanes.split else [flat.lanes[k][0] for k in range(lanes.P)]
+    grad = sum(g[pos].double() for g in grads)
+    arrays = {"pair_losses": pair_losses, "lane_loss": lane_loss,
+              "params_sample": flat.data[pos].float().cpu().numpy(), "grad_sample": grad.cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,20 +331,34 @@ def main():
     ap.add_argument("--lanes", type=int, default=4,
                     help="network graphs in flight per GPU (train.PairLanes): each on streams and graphs of its own, one "
                          "optimizer step on the mean of all their pairs' gradients per step.  --lanes 1 --stack 1 = the "
-                         "reference's one pair per optimizer step (also measured and reported otherwise: "
-                         "one_pair_in_flight)")
+                         "reference's one pair per optimizer step (with --full also measured and reported "
+                         "otherwise: one_pair_in_flight)")
     ap.add_argument("--stack", type=int, default=3,
                     help="fragment pairs STACKED into one pyramid + one network graph per lane (TrainStep stack): a step "
                          "trains on lanes x stack pairs, one optimizer step on the mean of their gradients")
-    ap.add_argument("--quick", action="store_true", help="headline legs only (value, blocks, one_pair_in_flight): no "
-                                                         "trainer-path / evaluation / matching / roofline / CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg reported next to `value` after the timed region: extra timed blocks, the "
+                         "one-pair schedule, PCIe-inclusive and trainer-path legs, the exchange legs and replica check "
+                         "(N > 1), per-operator and roofline timing, matching, evaluation and the CPU baseline.  Without "
+                         "it the run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64): the per-pair losses and accuracy, and a fixed seeded sample of the updated "
+                         "parameters and of the gradient the update applied.  That step starts from the initial "
+                         "parameters and momentum, so that its inputs are the same in every run")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline legs only (value, blocks, "
+                                                         "one_pair_in_flight): no trainer-path / evaluation / matching / "
+                                                         "roofline / CPU legs")
     ap.add_argument("--cpu-budget", type=float, default=90.0)
-    ap.add_argument("--blocks", type=int, default=5, help="extra timed blocks of --steps steps after the contract region "
-                                                         "(median / min / max reported next to `value`)")
+    ap.add_argument("--blocks", type=int, default=5, help="with --full: extra timed blocks of --steps steps after the "
+                                                         "contract region (median / min / max reported next to `value`)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch / rendezvous check only (no GPU work): every rank joins the process group and rank 0 "
                          "prints {n_gpus, ranks}; what tests/test_dist_cpu.py runs on a GPU-less host")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extra = args.full and not args.quick     # the legs --quick leaves out
     # D3F_BENCH_WATCHDOG=<seconds>: dump every thread's Python stack and exit if the run is still going by then (a hung
     # capture / tuning pass on a rented GPU box costs the whole call's budget otherwise); D3F_BENCH_LOG=1: stage stamps
     # Default 30 minutes (a full default run takes ~2): a blind multi-GPU submission that stalls -- e.g. lane replays beside
@@ -420,6 +464,11 @@ def main():
 
     stage("items + limits ready")
     ts = TrainStep(cfg, limits, dev, world_size=world, seed=0)
+    # --dump-outputs: the state the dumped step starts from.  The backward passes accumulate with float atomics (pooling
+    # and detector scatters), so two runs agree step by step only to rounding and their training
+    # trajectories drift apart; the last timed step of a dumping run starts again from these initial parameters and
+    # momentum buffers, which every run with the same arguments shares.
+    start_state = (ts.flat.data.clone(), ts.opt.buf.clone()) if args.dump_outputs else None
     prof = ops.EventProfiler()
     n_total = args.warmup + args.steps
     use_graph = not args.no_graph
@@ -482,12 +531,15 @@ def main():
 
     def run(k):
         if lanes is None:
-            return run_one(k)
+            run.outs = [run_one(k)]
+            return run.outs[0]
         if frozen:
-            return lanes.step_graph([items[j % len(items)] for j in range(P)], TrainStep.NO_PREFETCH)[0]
+            run.outs = lanes.step_graph([items[j % len(items)] for j in range(P)], TrainStep.NO_PREFETCH)
+            return run.outs[0]
         cur = [items[(P * k + j) % len(items)] for j in range(P)]
         nxt = [items[(P * (k + 1) + j) % len(items)] for j in range(P)]
-        return lanes.step_graph(cur, nxt)[0]
+        run.outs = lanes.step_graph(cur, nxt)     # every lane's (loss, desc, det, accuracy) of the step
+        return run.outs[0]
 
     for w in range(args.warmup):
         run(w)
@@ -496,8 +548,28 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    def reset_state():
+        """Parameters and momentum back to start_state: after the previous step's update, before the next step reads
+        them.  In stream order on the stream the update ran on (no host synchronisation) where that is known."""
+        if lanes is not None:
+            s = lanes._exchange_stream() if lanes.split else lanes.engines[0].stream
+        elif world == 1:
+            s = torch.cuda.current_stream(dev)     # the one-pair engine steps on the current stream
+        else:
+            s = None
+            torch.cuda.synchronize()
+        with torch.cuda.stream(s if s is not None else torch.cuda.current_stream(dev)):
+            ts.flat.data.copy_(start_state[0])
+            ts.opt.buf.copy_(start_state[1])
+        if lanes is not None:
+            lanes._join['ev_step'].record(s)     # every lane's next step waits for this event
+        if s is None:
+            torch.cuda.synchronize()
+
     t0 = time.perf_counter()
     for k in range(args.steps):
+        if start_state is not None and k == args.steps - 1:
+            reset_state()
         out = run(args.warmup + k)
     t_enq = time.perf_counter()
     torch.cuda.synchronize()
@@ -509,9 +581,12 @@ def main():
     loss_val = float(out[0].item()) / Q      # (a stacked lane reports the sum over its stack)
     if use_graph:
         ts.check_status()
+    if args.dump_outputs and rank == 0:       # before any --full leg trains on
+        dump_outputs(args.dump_outputs, run.outs, ts, lanes)
+        stage("outputs written")
     # run-to-run spread: the same K steps a few more times (single shots of 90 ms differ by ~1 %)
     block_rates = []
-    if world == 1:
+    if world == 1 and args.full:
         for _ in range(max(0, args.blocks)):
             torch.cuda.synchronize()
             tb0 = time.perf_counter()
@@ -523,7 +598,7 @@ def main():
             ts.check_status()
     # the reference's schedule -- ONE pair per optimizer step -- on the same engine, same K steps
     one_in_flight = None
-    if lanes is not None:
+    if lanes is not None and args.full:
         torch.cuda.synchronize()
         for k in range(3):
             run_one(k)
@@ -548,7 +623,7 @@ def main():
     # pair uploaded from pageable NumPy memory inside the timed region (TrainStep.upload); reported next to `value`,
     # never as `value`.
     pcie = None
-    if world == 1 and not args.quick:
+    if world == 1 and extra:
         def run_host(k):
             if lanes is not None:     # P pairs per step, each uploaded inside the timed region
                 cur = run_host.cur if run_host.cur is not None else [
@@ -575,7 +650,7 @@ def main():
     # exact pairs, and a stream of pairs of different sizes through capacity classes (one graph engine per class,
     # the next pair's pyramid prefetched into its own class's sets).  Reported next to `value`, never as `value`.
     trainer_path = None
-    if world == 1 and use_graph and not args.quick:
+    if world == 1 and use_graph and extra:
         try:
             keep = (ts.flat.data.clone(), ts.opt.buf.clone(), ts.opt.state.clone())
             eng110 = ts.clone_for_capacities(TrainStep.capacities_for(sizes, slack=1.10), num_corr=int(items[0][4].shape[0]))
@@ -680,7 +755,7 @@ def main():
     # steps: (a) the timed region above; (b) the steps with the all-reduces left out (ranks drift apart: run LAST, after
     # the replica check below would be too late, so parameters are saved and restored); (c) the all-reduces alone.
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             keep = (ts.flat.data.clone(), ts.opt.buf.clone())
             ts_world = ts.world
@@ -762,7 +837,7 @@ def main():
             exchange = {"rccl_ranks": world, "error": "%s: %s" % (type(e).__name__, e)}
     # data-parallel sanity: after the timed steps every rank must hold bit-identical parameters
     replica_spread = None
-    if world > 1:
+    if world > 1 and args.full:
         chk = ts.flat.data.double().abs().sum().reshape(1)
         hi, lo = chk.clone(), chk.clone()
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
@@ -770,7 +845,7 @@ def main():
         replica_spread = float((hi - lo).item())
     # Per-operator HIP-event timing (events on the launch stream around every C-ABI call).  Events cannot be recorded
     # inside a replayed graph, so the same steps are run eagerly right after the timed region, same process and data.
-    if not args.quick:
+    if extra:
         ops.set_profiler(prof)
         ts._pending = None
         for k in range(3):
@@ -798,7 +873,7 @@ def main():
             else:
                 ts.step(items[k % len(items)])
     edges, widths = {}, {}
-    if not args.quick:   # TRUE edges of the transposed tables = valid entries of the forward tables
+    if extra:   # TRUE edges of the transposed tables = valid entries of the forward tables
         if roof_eng is not None:
             roof_eng._static_step(roof_items)
             torch.cuda.synchronize()
@@ -812,7 +887,7 @@ def main():
                     if r is not None:
                         edges[(r.Nq, r.Ns)] = int((t < r.Ns).sum())
                         widths[(r.Nq, r.Ns)] = int(r.width)
-    kt = {} if args.quick else timed_kernels(
+    kt = {} if not extra else timed_kernels(
         _native.lib(), _three_steps, {1: fwd_kernel_cost, 2: dx_kernel_cost, 3: gather_kernel_cost(edges, widths),
                                       4: atb_kernel_cost, 5: agg_fwd_kernel_cost, 6: agg_rev_kernel_cost(edges),
                                       7: atb_group_cost}, 3)
@@ -822,7 +897,7 @@ def main():
     # dense mutual-NN matching of the pair's descriptors (19k x 19k x 32, the distance matrix is
     # never materialised) -- the one MFMA-bound kernel of the path; timed with HIP events on the current stream.
     matching = None
-    if rank == 0 and not args.quick:
+    if rank == 0 and extra:
         n0m, n1m = int(items[0][0].shape[0]), int(items[0][1].shape[0])
         gen = torch.Generator(device=dev).manual_seed(0)
         da = torch.nn.functional.normalize(torch.randn(n0m, 32, device=dev, generator=gen), dim=1)
@@ -847,7 +922,7 @@ def main():
     # evaluation pass of one pair -- pyramid + eval-mode forward (descriptors, gated scores), top-k
     # keypoints by score, mutual-NN matching of the selected descriptors (build_correspondence); eager launches.
     evaluation = None
-    if rank == 0 and not args.quick:
+    if rank == 0 and extra:
         from d3feat_pytorch_amd.geometric_registration.common import build_correspondence, select_keypoints
         ts.model.eval()
         ev_item = items[0]
@@ -1082,7 +1157,7 @@ def main():
             "roofline": roofline,
             "matching": matching,
             "evaluation": evaluation,
-            "kernels": {k: {"avg_us": round(v["avg_ms"] * 1e3, 2), "calls": v["calls"],
+            "kernels": None if not args.full else {k: {"avg_us": round(v["avg_ms"] * 1e3, 2), "calls": v["calls"],
                             "total_ms": round(v["total_ms"], 3)} for k, v in
                         sorted(summary.items(), key=lambda kv: -kv[1]["total_ms"])[:12]},
         }
@@ -1098,7 +1173,7 @@ def main():
                     one_in_flight["value"] / world * fl_pair / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
                 "note": "SURVEY 8d algorithmic FLOPs (forward KPConv + Linear, x3) x pairs/s per GPU; `frac` above is the "
                         "dominant hand-written kernel running alone"}
-        if world == 1 and not args.no_cpu_baseline and not args.quick:
+        if world == 1 and not args.no_cpu_baseline and extra:
             res["cpu_baseline"] = cpu_baseline(host_items[0], cfg, limits, budget_s=args.cpu_budget)
         print(json.dumps(res))
     if world > 1:

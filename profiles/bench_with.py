@@ -1,5 +1,5 @@
 """bench.py with module constants of the package overridden first (the package reads no environment):
-    python profiles/bench_with.py ops._FUSED_LINEAR_MAX_CIN=256 train.PairLanes.JOIN_ON_HOST=True -- --quick --steps 20
+    python profiles/bench_with.py ops._FUSED_LINEAR_MAX_CIN=256 train.PairLanes.JOIN_ON_HOST=True -- --full --quick --steps 20
 Everything before `--` is `<module>.<attr>[.<attr>]=<python literal>` (or `tunables.<field>=<int>` for the library's
 d3f_tunables), everything after goes to bench.py."""
 import ast

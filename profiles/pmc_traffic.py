@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """HBM-side traffic per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) -> profiles/pmc_traffic.json.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d out_f -o f -- python bench.py --no-graph --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d out_w -o w -- python bench.py --no-graph --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d out_f -o f -- python bench.py --full --no-graph --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d out_w -o w -- python bench.py --full --no-graph --steps 3 --warmup 1 --no-cpu-baseline
     python profiles/pmc_traffic.py out_f/f_results.db out_w/w_results.db profiles/pmc_traffic.json
 
 The counters are memory-side request tallies (TCC_EA*), reported in KiB.  MI355X_MICROARCH.md notes that on gfx950

@@ -7,7 +7,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 out = sys.argv[1]
-sys.argv = [os.path.join(REPO, "bench.py"), "--no-tuned-gemm"] + (sys.argv[2:] or ["--quick", "--steps", "10"])
+sys.argv = [os.path.join(REPO, "bench.py"), "--no-tuned-gemm"] + (sys.argv[2:] or ["--full", "--quick", "--steps", "10"])
 import tempfile  # noqa: E402
 import torch  # noqa: E402
 torch.cuda.tunable.enable(True)

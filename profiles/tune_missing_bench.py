@@ -8,7 +8,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 out = sys.argv[1]
-sys.argv = [os.path.join(REPO, "bench.py")] + (sys.argv[2:] or ["--no-cpu-baseline", "--steps", "10"])
+sys.argv = [os.path.join(REPO, "bench.py")] + (sys.argv[2:] or ["--full", "--no-cpu-baseline", "--steps", "10"])
 import torch  # noqa: E402
 import bench  # noqa: E402
 

@@ -1172,7 +1172,7 @@ def test_two_rank_bench_control_flow_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     # launched PLAINLY: bench.py spawns its ranks through torch.distributed.run itself (and refuses to run 1 rank as 2)
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--pairs", "2", "--lanes", "2",
-           "--stack", "2", "--no-cpu-baseline"]
+           "--stack", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

@@ -15,6 +15,7 @@ from d3feat_pytorch_amd.kernels.kernel_points import base_disposition, load_kern
 from d3feat_pytorch_amd.models import blocks
 from d3feat_pytorch_amd.models.architectures import KPFCNN
 from d3feat_pytorch_amd.utils.loss import CircleLoss, DetLoss, LazyList
+from util import sha
 
 REF = "/root/reference"
 
@@ -112,47 +113,67 @@ def test_lazy_list_and_loss_signatures():
         CircleLoss(dist_type='chebyshev')                       # the reference's cdist rejects it too (loss.py:42-44)
 
 
-@pytest.mark.parametrize("metric", ["cosine", "arccosine", "sqeuclidean", "cityblock"])
-def test_losses_with_the_other_cdist_metrics(metric):
-    """CircleLoss / DetLoss with the metrics of the reference's cdist other than the configured 'euclidean'
-    (loss.py:8-44; CircleLoss' constructor default is 'cosine'): metric-agnostic tensor algebra, equal to the oracle
-    restatement -- and, where the reference tree is mounted, to the reference's own modules -- values and gradients."""
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-    from oracle import ops_ref
+def _ref_checks():
+    """tests/golden/ref_checks.npz: what the reference's own modules returned in the tests below
+    (make_golden_ref_checks.py), so that they run where the reference is not at hand."""
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_checks.npz'))
+
+
+def _loss_inputs():
     gen = torch.Generator().manual_seed(3)
     a0 = torch.nn.functional.normalize(torch.randn(48, 32, generator=gen), dim=1) * 0.98
     p0 = torch.nn.functional.normalize(a0 + 0.3 * torch.randn(48, 32, generator=gen), dim=1) * 0.98
     dk = torch.rand(48, 48, generator=gen) * 0.3
     sa, sp = torch.rand(48, 1, generator=gen), torch.rand(48, 1, generator=gen)
+    return a0, p0, dk, sa, sp
 
-    def run(circle_fn, det_fn):
-        a, p = a0.clone().requires_grad_(True), p0.clone().requires_grad_(True)
-        out = circle_fn(a, p, dk)
-        loss, dists = out[0], out[-1]
-        det = det_fn(dists, sa, sp)
-        (loss + det).backward()
-        return [loss.detach(), det.detach(), torch.as_tensor(float(out[1])), torch.as_tensor(list(out[2])),
-                torch.as_tensor(list(out[3])), a.grad, p.grad]
 
-    ours = run(CircleLoss(dist_type=metric, log_scale=10, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4), DetLoss())
-    orc = run(lambda a, p, d: ops_ref.circle_loss(a, p, d, metric=metric), ops_ref.det_loss)
-    for u, v in zip(ours, orc):
-        assert torch.allclose(u.float(), v.float(), rtol=1e-5, atol=1e-6)
-    if os.path.isdir(REF):
-        saved = {k: sys.modules.get(k) for k in list(sys.modules) if k == 'utils' or k.startswith('utils.')}
-        for k in saved:
+def run_losses(circle_fn, det_fn):
+    """Circle loss (+ its statistics) and detector loss of the fixed inputs, and the descriptor gradients."""
+    a0, p0, dk, sa, sp = _loss_inputs()
+    a, p = a0.clone().requires_grad_(True), p0.clone().requires_grad_(True)
+    out = circle_fn(a, p, dk)
+    loss, dists = out[0], out[-1]
+    det = det_fn(dists, sa, sp)
+    (loss + det).backward()
+    return [loss.detach(), det.detach(), torch.as_tensor(float(out[1])), torch.as_tensor(list(out[2])),
+            torch.as_tensor(list(out[3])), a.grad, p.grad]
+
+
+def reference_loss_outputs(ref_root, metric):
+    """run_losses on the reference's own utils/loss.py under ``ref_root``."""
+    saved = {k: sys.modules.get(k) for k in list(sys.modules) if k == 'utils' or k.startswith('utils.')}
+    for k in saved:
+        sys.modules.pop(k, None)
+    sys.path.insert(0, ref_root)
+    try:
+        import importlib
+        ref_loss = importlib.import_module('utils.loss')
+        return run_losses(ref_loss.CircleLoss(dist_type=metric, log_scale=10, safe_radius=0.1, pos_margin=0.1,
+                                              neg_margin=1.4), ref_loss.DetLoss())
+    finally:
+        sys.path.remove(ref_root)
+        for k in [k for k in sys.modules if k == 'utils' or k.startswith('utils.')]:
             sys.modules.pop(k, None)
-        sys.path.insert(0, REF)
-        try:
-            import importlib
-            ref_loss = importlib.import_module('utils.loss')
-            ref = run(ref_loss.CircleLoss(dist_type=metric, log_scale=10, safe_radius=0.1, pos_margin=0.1,
-                                          neg_margin=1.4), ref_loss.DetLoss())
-        finally:
-            sys.path.remove(REF)
-            for k in [k for k in sys.modules if k == 'utils' or k.startswith('utils.')]:
-                sys.modules.pop(k, None)
-            sys.modules.update({k: v for k, v in saved.items() if v is not None})
+        sys.modules.update({k: v for k, v in saved.items() if v is not None})
+
+
+@pytest.mark.parametrize("metric", ["cosine", "arccosine", "sqeuclidean", "cityblock"])
+def test_losses_with_the_other_cdist_metrics(metric):
+    """CircleLoss / DetLoss with the metrics of the reference's cdist other than the configured 'euclidean'
+    (loss.py:8-44; CircleLoss' constructor default is 'cosine'): metric-agnostic tensor algebra, equal to the oracle
+    restatement and to the reference's own modules (run where the reference tree is mounted, recorded otherwise) --
+    values and gradients."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+    from oracle import ops_ref
+    ours = run_losses(CircleLoss(dist_type=metric, log_scale=10, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4),
+                      DetLoss())
+    orc = run_losses(lambda a, p, d: ops_ref.circle_loss(a, p, d, metric=metric), ops_ref.det_loss)
+    rec = _ref_checks()
+    refs = [orc, [torch.from_numpy(rec['loss.%s.%d' % (metric, i)]) for i in range(len(ours))]]
+    if os.path.isdir(REF):
+        refs.append(reference_loss_outputs(REF, metric))
+    for ref in refs:
         for u, v in zip(ours, ref):
             assert torch.allclose(u.float(), v.float(), rtol=1e-5, atol=1e-6)
 
@@ -187,17 +208,17 @@ def test_unsupported_modes_raise():
         blocks.block_decider('nonsense', 0.1, 8, 8, 0, cfgmod.default_config())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_reference_architectures_runs_on_our_blocks_unchanged():
-    """Drop-in boundary: the reference's models/architectures.py imported as-is, with `models.blocks` resolved to
-    this package, builds the same network (same parameter names and shapes)."""
+def reference_architectures_state(ref_root):
+    """The reference's models/architectures.py under ``ref_root`` imported as-is, with `models.blocks` resolved to this
+    package: (its KPFCNN at first_features_dim=16 under seed 0, that network's first KPConv class)."""
     saved = {k: sys.modules.get(k) for k in list(sys.modules) if k == 'models' or k.startswith('models.')}
     for k in saved:
         sys.modules.pop(k, None)
     try:
         pkg.install_reference_aliases(['models', 'models.blocks'], overwrite=True)
         import importlib.util
-        spec = importlib.util.spec_from_file_location('ref_architectures', os.path.join(REF, 'models', 'architectures.py'))
+        spec = importlib.util.spec_from_file_location('ref_architectures',
+                                                      os.path.join(ref_root, 'models', 'architectures.py'))
         mod = importlib.util.module_from_spec(spec)
         import contextlib
         import io
@@ -206,20 +227,33 @@ def test_reference_architectures_runs_on_our_blocks_unchanged():
             np.random.seed(0)
             torch.manual_seed(0)
             ref_model = mod.KPFCNN(cfgmod.default_config(first_features_dim=16))
-        assert isinstance(ref_model.encoder_blocks[0].KPConv, blocks.KPConv)
-        np.random.seed(0)
-        torch.manual_seed(0)
-        ours = KPFCNN(cfgmod.default_config(first_features_dim=16))
-        a, b = ref_model.state_dict(), ours.state_dict()
-        assert list(a) == list(b)
-        for k in a:
-            assert torch.equal(a[k], b[k]), k
+        return ref_model.state_dict(), type(ref_model.encoder_blocks[0].KPConv)
     finally:
         for k in [k for k in sys.modules if k == 'models' or k.startswith('models.')]:
             sys.modules.pop(k, None)
         for k, v in saved.items():
             if v is not None:
                 sys.modules[k] = v
+
+
+def test_reference_architectures_runs_on_our_blocks_unchanged():
+    """Drop-in boundary: the reference's models/architectures.py imported as-is, with `models.blocks` resolved to
+    this package, builds the same network (same parameter names, shapes and initial values).  Run where the reference
+    tree is mounted; elsewhere against the names, shapes and SHA-256 of the values that run recorded."""
+    np.random.seed(0)
+    torch.manual_seed(0)
+    b = KPFCNN(cfgmod.default_config(first_features_dim=16)).state_dict()
+    rec = _ref_checks()
+    assert [str(k) for k in rec['arch.names']] == list(b)
+    for k, shape, digest in zip(rec['arch.names'], rec['arch.shapes'], rec['arch.sha']):
+        assert ','.join(str(d) for d in b[str(k)].shape) == str(shape), k
+        assert sha(b[str(k)].numpy()) == str(digest), k
+    if os.path.isdir(REF):
+        a, kpconv_class = reference_architectures_state(REF)
+        assert issubclass(kpconv_class, blocks.KPConv)
+        assert list(a) == list(b)
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
 
 
 def test_grad_holder_protocol():

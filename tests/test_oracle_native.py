@@ -2,12 +2,14 @@
 (oracle/_ref, present only where /root/reference is) and (b) the committed golden vectors, which were produced by that
 same reference build.  Parity bar: indices exact up to the order inside equal-d2 groups; barycentres and their ROW ORDER
 bit-exact."""
+import os
+
 import numpy as np
 import pytest
 
 import d3feat_pytorch_amd  # noqa: F401  (package must import without a GPU)
 from d3feat_pytorch_amd import config as cfgmod
-from util import assert_neighbors_equal_tie_aware, sha
+from util import assert_neighbors_equal_tie_aware, neighbor_d2, sha
 
 LEVELS = 5
 
@@ -88,22 +90,52 @@ def test_edge_cases(native):
     assert np.array_equal(cut[:7], full[:7]) and np.array_equal(cut[7:], full[fb[0]:fb[0] + 7])
 
 
-def test_oracle_vs_compiled_reference(native):
-    if not native.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+def _ref_checks():
+    """tests/golden/ref_checks.npz: what the reference's own C++ (oracle/_ref) returned on the inputs of the two tests
+    below (make_golden_ref_checks.py), so that they run where the reference is not at hand."""
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_checks.npz'))
+
+
+def oracle_vs_reference_cases():
+    """(key, points, lengths, dl) of test_oracle_vs_compiled_reference."""
     rng = np.random.default_rng(17)
     for trial in range(3):
         n = [2500, 1700]
         pts = (rng.random((sum(n), 3)) * np.array([2.0, 1.5, 0.6])).astype(np.float32)
         lens = np.array(n, np.int32)
         for dl in (0.05, 0.11):
-            a, ab = native.subsample_batch(pts, lens, sampleDl=dl)
-            b, bb = native.ref_subsample_batch(pts, lens, sampleDl=dl)
+            yield 'nb.%d.%g' % (trial, dl), pts, lens, dl
+
+
+def reference_grid_and_radius(native, pts, lens, dl):
+    """The reference's subsampling of a case and its radius search of the barycentres (radius 2.5 dl) in the cloud."""
+    b, bb = native.ref_subsample_batch(pts, lens, sampleDl=dl)
+    return b, bb, native.ref_batch_query(b, pts, bb, lens, radius=2.5 * dl)
+
+
+def canonical_neighbors(queries, supports, table):
+    """A radius-search table with every run of equal d2 in a row sorted by index: two uncapped tables (no tie group cut
+    by a column limit) agree in this form iff they agree as assert_neighbors_equal_tie_aware requires."""
+    d2 = neighbor_d2(queries, supports, table)
+    order = np.lexsort((table, d2), axis=-1)
+    return np.take_along_axis(np.asarray(table).astype(np.int32), order, 1)
+
+
+def test_oracle_vs_compiled_reference(native):
+    """Against the compiled reference where it is built, and against its recorded outputs everywhere (its subsampling
+    as such, its radius tables as the SHA-256 of their canonical form)."""
+    rec = _ref_checks()
+    for key, pts, lens, dl in oracle_vs_reference_cases():
+        a, ab = native.subsample_batch(pts, lens, sampleDl=dl)
+        ours = native.batch_query(a, pts, ab, lens, radius=2.5 * dl)
+        assert np.array_equal(ab, rec[key + '.lens']) and np.array_equal(a.view(np.uint32),
+                                                                          rec[key + '.pts'].view(np.uint32)), key
+        assert ours.shape == tuple(rec[key + '.nbr_shape']), key
+        assert sha(canonical_neighbors(a, pts, ours)) == str(rec[key + '.nbr_sha']), key
+        if native.have_ref():
+            b, bb, ref = reference_grid_and_radius(native, pts, lens, dl)
             assert np.array_equal(ab, bb) and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-            r = 2.5 * dl
-            ours = native.batch_query(a, pts, ab, lens, radius=r)
-            ref = native.ref_batch_query(a, pts, ab, lens, radius=r)
-            assert_neighbors_equal_tie_aware(a, pts, ours, ref, 'trial %d dl %g' % (trial, dl))
+            assert_neighbors_equal_tie_aware(a, pts, ours, ref, key)
 
 
 def _attr_case(rng, n, n_labels, ldim):
@@ -118,24 +150,41 @@ def test_subsample_features_and_labels_vs_compiled_reference(native):
     """Feature / label branches (grid_subsampling.h:42-73, .cpp:89-102): the restatement equals the reference's C++ bit
     for bit, including which label wins a tied vote (iteration order of the per-cell unordered_map<int,int>); big voxels
     with up to 40 distinct labels drive that map through its rehashes."""
-    if not native.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    rec = _ref_checks()
+    for key, pts, lens, feats, labels, dl, mp in attribute_cases():
+        f, l = (feats if mp != 'labels' else None), (labels if mp != 'features' else None)
+        a = native.subsample_batch_ex(pts, lens, f, l, sampleDl=dl, max_p=mp if isinstance(mp, int) else 0)
+        refs = [[rec['%s.%d' % (key, i)] for i in range(4)] if isinstance(mp, int) else [None, None, rec[key + '.2']]]
+        if native.have_ref():
+            refs.append(native.ref_subsample_batch_ex(pts, lens, f, l, sampleDl=dl,
+                                                      max_p=mp if isinstance(mp, int) else 0))
+        for b in refs:
+            if isinstance(mp, int):
+                assert len(a) == len(b) == 4
+                for x, y in zip(a, b):
+                    assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x.view(np.uint32),
+                                                                                        y.view(np.uint32))
+            else:
+                assert len(a) == 3 and np.array_equal(a[2], b[2])
+        if mp == 'labels':
+            assert a[2].shape[1] == labels.shape[1]
+
+
+def attribute_cases():
+    """(key, points, lengths, features, labels, dl, max_p | 'features' | 'labels') of the test above: the full call at
+    max_p 0 and 6, then the features-only and labels-only forms."""
     rng = np.random.default_rng(23)
-    for n, n_labels, ldim, dl in (([2500, 1700], 4, 1, 0.11), ([3000, 500], 40, 1, 0.45), ([4000], 40, 3, 0.5),
-                                  ([1500], 3, 2, 0.05)):
+    for c, (n, n_labels, ldim, dl) in enumerate((([2500, 1700], 4, 1, 0.11), ([3000, 500], 40, 1, 0.45),
+                                                 ([4000], 40, 3, 0.5), ([1500], 3, 2, 0.05))):
         pts, lens, feats, labels = _attr_case(rng, n, n_labels, ldim)
-        for mp in (0, 6):
-            a = native.subsample_batch_ex(pts, lens, feats, labels, sampleDl=dl, max_p=mp)
-            b = native.ref_subsample_batch_ex(pts, lens, feats, labels, sampleDl=dl, max_p=mp)
-            assert len(a) == len(b) == 4
-            for x, y in zip(a, b):
-                assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x.view(np.uint32), y.view(np.uint32))
-        fa = native.subsample_batch_ex(pts, lens, feats, None, sampleDl=dl)
-        fb = native.ref_subsample_batch_ex(pts, lens, feats, None, sampleDl=dl)
-        la = native.subsample_batch_ex(pts, lens, None, labels, sampleDl=dl)
-        lb = native.ref_subsample_batch_ex(pts, lens, None, labels, sampleDl=dl)
-        assert len(fa) == len(la) == 3 and np.array_equal(fa[2], fb[2]) and np.array_equal(la[2], lb[2])
-        assert la[2].shape[1] == ldim
+        for mp in (0, 6, 'features', 'labels'):
+            yield 'ex.%d.%s' % (c, mp), pts, lens, feats, labels, dl, mp
+
+
+def reference_attributes(native, pts, lens, feats, labels, dl, mp):
+    """The reference's subsampling of an attribute case, as the test calls it."""
+    f, l = (feats if mp != 'labels' else None), (labels if mp != 'features' else None)
+    return native.ref_subsample_batch_ex(pts, lens, f, l, sampleDl=dl, max_p=mp if isinstance(mp, int) else 0)
 
 
 def test_s1_pyramid_hashes(golden_s1, native):
