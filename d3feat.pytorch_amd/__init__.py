@@ -7,6 +7,7 @@ Layout mirrors the reference's module paths so its callers keep working:
   utils.loss               cdist, CircleLoss, DetLoss, ContrastiveLoss
   cpp_wrappers.cpp_neighbors.radius_neighbors.batch_query / cpp_wrappers.cpp_subsampling.grid_subsampling.subsample_batch
   geometric_registration.common.build_correspondence          geometric_registration.evaluate (test.py's protocol)
+  geometric_registration.registration   RANSAC pose per pair (ops.ransac_rigid), gt.info, 3DMatch registration recall
   datasets.ThreeDMatch     ThreeDMatchDataset / ThreeDMatchTestset          trainer.Trainer (trainer.py's epoch loop)
 ``install_reference_aliases()`` registers those names in ``sys.modules`` so the reference's own
 ``models/architectures.py`` (``from models.blocks import *``) runs on top of this package unchanged.

@@ -1,0 +1,202 @@
+"""Rigid registration of fragment pairs and the 3DMatch registration recall -- the step after the correspondences.
+
+The reference stops at the feature-match recall (``evaluate.register_one_scene``) and leaves pose estimation to Open3D
+on the CPU.  Here it runs on the device: top-k keypoints by score, mutual nearest neighbours (``ops.mutual_nn``), then
+RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid`` call (two launches).
+
+* ``estimate_transform``             one pair: keypoints / descriptors / scores -> (T, inliers, num_matches);
+* ``estimate_transforms_from_match`` the batched inference path: ``infer.InferStep.match(item, feats, scores,
+  num_points=k)`` output -> one transform per pair of the stacked item;
+* ``loadinfo`` / ``transformation_error`` / ``evaluate_registration``  the benchmark's ``gt.info`` files and its
+  registration recall / precision (error p <= 0.2^2 under the 6x6 information matrix, pairs with j - i > 1);
+* ``register_scene``                  every pair listed in ``gt.log`` from the dumped files, estimates written in the
+  ``gt.log`` format (``evaluate.writelog``).
+
+Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import evaluate as ev
+from .common import select_keypoints
+
+RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0)
+
+
+def _compact(mutual, src_pts, tgt_pts):
+    """[P,k] mutual flags + [P,k,3] source / matched target points -> stacked (src [P*k,3], tgt [P*k,3], seg [P,2]):
+    pair p's mutual rows first, in slot order, at offset p*k.  On the device, no host synchronisation."""
+    P, k = int(mutual.shape[0]), int(mutual.shape[1])
+    m = mutual.reshape(P, k).to(torch.int64)
+    n = m.sum(dim=1)
+    pos = torch.cumsum(m, dim=1) - 1 + torch.arange(P, device=m.device).view(P, 1) * k
+    dst = torch.where(m.bool(), pos, torch.full_like(pos, P * k)).reshape(-1)      # the others go to a spill row
+    src = torch.zeros((P * k + 1, 3), dtype=torch.float32, device=m.device)
+    tgt = torch.zeros((P * k + 1, 3), dtype=torch.float32, device=m.device)
+    src.index_put_((dst,), src_pts.reshape(-1, 3).float())
+    tgt.index_put_((dst,), tgt_pts.reshape(-1, 3).float())
+    seg = torch.stack([torch.arange(P, device=m.device) * k, n], dim=1).to(torch.int32).contiguous()
+    return src[:P * k].contiguous(), tgt[:P * k].contiguous(), seg, n
+
+
+def _ransac(src, tgt, seg, params):
+    p = dict(RANSAC_DEFAULTS)
+    p.update(params)
+    return ops.ransac_rigid(src, tgt, seg, **p)
+
+
+def _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score, num_points):
+    """[k] mutual flags and the [k,3] source keypoints with their matched target keypoints (match_pair's selection)."""
+    si = select_keypoints(source_score.reshape(-1), num_points)
+    ti = select_keypoints(target_score.reshape(-1), num_points)
+    sd = torch.nan_to_num(source_desc[si]).contiguous()
+    td = torch.nan_to_num(target_desc[ti]).contiguous()
+    row, _, mutual = ops.mutual_nn(sd, td)
+    return mutual, source_keypts[si], target_keypts[ti][row.long()]
+
+
+def estimate_transform(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
+                       num_points=5000, **ransac):
+    """One fragment pair (device tensors): top-k keypoints by score, mutual nearest neighbours, RANSAC.  Returns device
+    tensors ``(T [4,4] f64, inliers, num_matches)``; T maps the target into the source frame.  ``ransac``: keywords of
+    ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS)."""
+    mutual, sp, tp = _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
+                                  num_points)
+    src, tgt, seg, n = _compact(mutual.view(1, -1), sp.unsqueeze(0), tp.unsqueeze(0))
+    T, inl = _ransac(src, tgt, seg, ransac)[:2]
+    return T[0], inl[0], n[0]
+
+
+def estimate_transforms_from_match(points, seg, row, mutual, sel, **ransac):
+    """The batched path: ``row, mutual, sel = InferStep.match(item, feats, scores, num_points=k)`` with ``points`` the
+    item's stacked level-0 points [rows,3] and ``seg`` = ``InferStep.segments(item)`` [2P,2] (clouds 2p, 2p+1 are the
+    source and target of pair p).  The mutual rows of every pair are compacted on the device and ONE ``ransac_rigid``
+    call estimates all P transforms.  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
+    P, k = int(row.shape[0]), int(row.shape[1])
+    pts = points if points.dtype == torch.float32 else points.float()
+    off = seg[:, 0].long()
+    live = (sel >= 0)
+    n_live = live.sum(dim=1)                                                  # keypoints per cloud (the tail of sel)
+    src_rows = off[0::2].view(P, 1) + sel[0::2].clamp(min=0).long()           # [P,k] stacked rows of the sources
+    tslot = (k - n_live[1::2]).view(P, 1) + row.long().clamp(min=0)           # target slot of each source's match
+    tslot = tslot.clamp(max=k - 1)
+    tgt_rows = off[1::2].view(P, 1) + torch.gather(sel[1::2].long(), 1, tslot).clamp(min=0)
+    m = mutual.bool() & live[0::2]
+    src, tgt, sg, n = _compact(m, pts[src_rows.reshape(-1)].view(P, k, 3), pts[tgt_rows.reshape(-1)].view(P, k, 3))
+    T, inl = _ransac(src, tgt, sg, ransac)[:2]
+    return T, inl, n
+
+
+# ------------------------------------------------------------------------------------------------- gt.info, metric
+def loadinfo(gtpath):
+    """{'i_j': 6x6 float64} from ``<gtpath>/gt.info``: an ``i \\t j \\t n`` line, then 6 rows of 6 (like ``loadlog``)."""
+    with open(os.path.join(gtpath, 'gt.info')) as f:
+        rows = [ln.rstrip('\n') for ln in f if ln.strip()]
+    if len(rows) % 7:
+        raise ValueError("gt.info: %d non-empty lines, expected blocks of 7" % len(rows))
+    out = {}
+    for i in range(0, len(rows), 7):
+        head = rows[i].split()[0:2]
+        mat = np.array([[float(x) for x in rows[i + r].split()[0:6]] for r in range(1, 7)], dtype=np.float64)
+        out['%d_%d' % (int(head[0]), int(head[1]))] = mat
+    return out
+
+
+def _quaternion(R):
+    """Unit quaternion (w, x, y, z), w >= 0, of the active rotation R (R v = q v q*)."""
+    R = np.asarray(R, dtype=np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = 2.0 * np.sqrt(tr + 1.0)
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
+        q = np.array([(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s])
+    elif R[1, 1] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
+        q = np.array([(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s])
+    else:
+        s = 2.0 * np.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
+        q = np.array([(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s])
+    q /= np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
+def transformation_error(T_est, T_gt, info):
+    """The benchmark's error of an estimate: D = inv(T_gt) T_est, q = (w, x, y, z) the unit quaternion of D's rotation
+    with w >= 0, er = [D_t, -q_xyz], p = er^T info er / info[0,0].
+
+    Sign convention: q is the quaternion of D's rotation read as a direction-cosine matrix (what MATLAB's dcm2quat
+    returns, the evaluation code of the benchmark), i.e. the active-rotation quaternion of D_R^T -- so for a rotation
+    by +a about z, q_z = -sin(a/2) and er ends in +sin(a/2).  With the other sign the benchmark's own 3dmatch.log
+    trajectories score 5-16 recall points lower on every scene (tests/test_ransac_cpu.py)."""
+    D = np.linalg.inv(np.asarray(T_gt, dtype=np.float64)) @ np.asarray(T_est, dtype=np.float64)
+    q = _quaternion(D[:3, :3].T)
+    er = np.concatenate([D[:3, 3], -q[1:]])
+    info = np.asarray(info, dtype=np.float64)
+    return float(er @ info @ er / info[0, 0])
+
+
+def _far(key):
+    i, j = (int(x) for x in key.split('_'))
+    return j - i > 1
+
+
+def evaluate_registration(est, gt, info, err2=0.2 ** 2):
+    """Registration recall / precision of estimates ``est`` against ``gt`` (``{'i_j': 4x4}``; ``info``: ``loadinfo``).
+    Only pairs with j - i > 1 count (consecutive fragments overlap trivially).  A pair is good when it is listed in
+    ``gt`` and its ``transformation_error`` is <= err2.  Returns ``(recall = good / #gt pairs, precision = good /
+    #estimated pairs, {key: error})`` -- the error of every counted estimate that ``gt`` lists."""
+    gt_keys = [k for k in gt if _far(k)]
+    est_keys = [k for k in est if _far(k)]
+    errs = {k: transformation_error(est[k], gt[k], info[k]) for k in est_keys if k in gt}
+    good = sum(1 for e in errs.values() if e <= err2)
+    recall = good / len(gt_keys) if gt_keys else 0.0
+    precision = good / len(est_keys) if est_keys else 0.0
+    return recall, precision, errs
+
+
+def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, **ransac):
+    """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
+    scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
+    ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
+    ``evaluate_registration(...)`` when ``<gtpath>/gt.info`` exists, else None."""
+    gt = ev.loadlog(gtpath)
+    dpath, kpath, spath = ev._paths(save_path, scene)
+    if num_frag is None:
+        num_frag = len([f for f in os.listdir(kpath) if f.endswith('.npy')])
+    dev = torch.device(device)
+    cache = {}
+
+    def load(i):
+        if i not in cache:
+            name = 'cloud_bin_%d' % i
+            cache[i] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (
+                ev.get_keypts(kpath, name), ev.get_desc(dpath, name), ev.get_scores(spath, name).reshape(-1)))
+        return cache[i]
+    keys = sorted(gt, key=lambda k: tuple(int(x) for x in k.split('_')))
+    if not keys:
+        raise ValueError("no fragment pair is listed in %s" % os.path.join(gtpath, 'gt.log'))
+    k = int(num_points)
+    muts, sps, tps = [], [], []
+    for key in keys:
+        i, j = (int(x) for x in key.split('_'))
+        mutual, sp, tp = _pair_points(*load(i), *load(j), k)
+        pad = k - int(mutual.shape[0])          # fragments with fewer than k points: pad with non-mutual rows
+        if pad:
+            mutual = torch.cat([mutual, mutual.new_zeros(pad)])
+            sp = torch.cat([sp, sp.new_zeros((pad, 3))])
+            tp = torch.cat([tp, tp.new_zeros((pad, 3))])
+        muts.append(mutual)
+        sps.append(sp)
+        tps.append(tp)
+    src, tgt, seg, _ = _compact(torch.stack(muts), torch.stack(sps), torch.stack(tps))
+    T = _ransac(src, tgt, seg, ransac)[0].cpu().numpy()          # the scene's only read-back
+    est = {key: T[n] for n, key in enumerate(keys)}
+    ev.writelog(out_log or os.path.join(save_path, 'registration', scene), est, num_frag)
+    if not os.path.exists(os.path.join(gtpath, 'gt.info')):
+        return None
+    return evaluate_registration(est, gt, loadinfo(gtpath))

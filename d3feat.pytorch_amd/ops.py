@@ -2536,6 +2536,53 @@ def topk_scores(scores, seg, k):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# rigid registration (what the reference leaves to Open3D's RANSAC on the CPU)
+# ---------------------------------------------------------------------------------------------------------------
+RANSAC_MAX_HYPOTHESES = 1 << 24
+RANSAC_MAX_COUNT = 65536
+RANSAC_MAX_REFINE = 64
+RANSAC_ST_FEW, RANSAC_ST_NO_HYPOTHESIS, RANSAC_ST_SEGMENT = 1, 2, 4
+
+
+def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0,
+                 return_hypotheses=False, first_pair=0):
+    """RANSAC rigid registration of P correspondence sets in two launches (d3f_ransac_rigid).
+
+    ``src`` / ``tgt`` [rows,3] (row i of one matches row i of the other); ``seg`` int32 [P,2] on the device =
+    (offset, count) per pair.  Returns device tensors ``(T [P,4,4] f64, inliers [P], best_hypothesis [P],
+    best_count [P], status [P])``: T maps the TARGET onto the SOURCE (src ~ R tgt + t, the gt.log convention) and is the
+    identity where ``status`` is non-zero (RANSAC_ST_* bits).  ``return_hypotheses=True`` appends every hypothesis'
+    inlier count [P,H] int32 (-1 when invalid) and f32 (R row-major, t) [P,H,12].  ``first_pair``: the hash index of
+    pair 0 (a batch split over several calls draws what one call would)."""
+    s, t = _f32(src, "src"), _f32(tgt, "tgt")
+    if s.dim() != 2 or s.shape[1] != 3 or tuple(t.shape) != tuple(s.shape):
+        raise ValueError("src and tgt must be [rows,3] tensors of the same shape")
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 2
+            and seg.shape[1] == 2 and seg.shape[0] >= 1 and seg.is_contiguous()):
+        raise ValueError("seg must be a contiguous device int32 [P,2] tensor")
+    H, P = int(num_hypotheses), int(seg.shape[0])
+    if not 1 <= H <= RANSAC_MAX_HYPOTHESES:
+        raise ValueError("num_hypotheses must be in 1..%d" % RANSAC_MAX_HYPOTHESES)
+    if not 0 <= int(refine_iters) <= RANSAC_MAX_REFINE:
+        raise ValueError("refine_iters must be in 0..%d" % RANSAC_MAX_REFINE)
+    if not (0.0 <= float(edge_ratio) <= 1.0) or not (0.0 < float(distance_threshold) < float("inf")):
+        raise ValueError("edge_ratio must be in [0, 1] and distance_threshold positive")
+    dev = s.device
+    T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+    out = [torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4)]
+    hc = torch.empty((P, H), dtype=torch.int32, device=dev) if return_hypotheses else None
+    hr = torch.empty((P, H, 12), dtype=torch.float32, device=dev) if return_hypotheses else None
+    nbytes = _native.lib().d3f_ransac_rigid_ws_bytes(P, H)
+    ws = _ws(nbytes, dev)
+    _native.check(_native.lib().d3f_ransac_rigid(
+        _p(s), _p(t), int(s.shape[0]), _p(seg), P, int(first_pair), H, float(distance_threshold), float(edge_ratio),
+        int(refine_iters), int(seed) & 0xffffffffffffffff, _p(T), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
+        _p(hc), _p(hr), _p(ws), nbytes, _stream()), "d3f_ransac_rigid")
+    res = (T,) + tuple(out)
+    return res + (hc, hr) if return_hypotheses else res
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

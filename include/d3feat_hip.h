@@ -631,6 +631,44 @@ int d3f_mutual_nn_batched(const float* src_desc, int src_rows, const float* tgt_
 int d3f_topk_scores(const float* scores, int rows, const int32_t* seg, int P, int k, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rigid registration -- replaces Open3D's registration_ransac_based_on_correspondence (3 points per hypothesis,
+ * CorrespondenceCheckerBasedOnEdgeLength, inlier re-fits), which the reference leaves to Open3D on the CPU.
+ * P correspondence sets in one stacked buffer: src / tgt [rows,3] f32 (row i of src matches row i of tgt); seg [P,2]
+ * int32 ON THE DEVICE = (offset, count) per pair, like d3f_topk_scores.  Pair p is estimated from H hypotheses drawn by
+ * the counter-based hash of (seed, first_pair + p, h, k) written in csrc/rigid.hpp (a batch split into chunks draws
+ * what one call would when each chunk passes its first pair's index).  A hypothesis is invalid (never wins) when two
+ * of its 3 indices are equal, either triangle is degenerate (|cross| < 1e-6) or, with edge_ratio > 0, an edge fails
+ * min(la, lb) >= edge_ratio * max(la, lb).  Valid ones are fitted in f64 (Horn's quaternion form: always a proper
+ * rotation) and score the correspondences with |R tgt + t - src|^2 < distance_threshold^2 in f32.  The winner has the
+ * largest count, ties to the lowest h; it is refined refine_iters times (f64 least-squares fit over its inliers, fixed
+ * summation order, then a recount).  Deterministic: integer counts, fixed-order f64 sums.  Two launches, no host
+ * synchronisation (graph-capturable).
+ * Outputs per pair: T [P,4,4] f64 mapping TARGET onto SOURCE (src ~ R tgt + t: the gt.log convention), inliers [P]
+ * (final count), best_hypothesis [P] (winning h, -1 if none), best_count [P] (its count before refinement), status [P]
+ * (D3F_RANSAC_ST_* bits; any bit set: T is the identity).  Optional (NULL to skip), for tests: hyp_count [P,H] int32
+ * (-1 when invalid) and hyp_rt [P,H,12] f32 (R row-major, then t; zeros when invalid).
+ * Limits: 1 <= H <= D3F_RANSAC_MAX_HYPOTHESES, count <= D3F_RANSAC_MAX_COUNT (a longer or out-of-range segment sets
+ * D3F_RANSAC_ST_SEGMENT), 0 <= refine_iters <= D3F_RANSAC_MAX_REFINE, 0 <= edge_ratio <= 1, distance_threshold > 0,
+ * P <= 65535; src / tgt may be NULL when rows = 0 (every pair then has fewer than 3 correspondences).
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_RANSAC_MAX_HYPOTHESES (1 << 24)
+#define D3F_RANSAC_MAX_COUNT 65536
+#define D3F_RANSAC_MAX_REFINE 64
+#define D3F_RANSAC_ST_FEW 1           /* fewer than 3 correspondences */
+#define D3F_RANSAC_ST_NO_HYPOTHESIS 2 /* no valid hypothesis among the H drawn */
+#define D3F_RANSAC_ST_SEGMENT 4       /* segment outside [0, rows) or longer than D3F_RANSAC_MAX_COUNT */
+size_t d3f_ransac_rigid_ws_bytes(int P, int H);
+int d3f_ransac_rigid(const float* src, const float* tgt, int rows, const int32_t* seg, int P, int first_pair, int H,
+                     float distance_threshold, float edge_ratio, int refine_iters, uint64_t seed, double* T,
+                     int32_t* inliers, int32_t* best_hypothesis, int32_t* best_count, int32_t* status,
+                     int32_t* hyp_count, float* hyp_rt, void* ws, size_t ws_bytes, void* stream);
+/* Host-only twins of the device code (csrc/rigid.hpp), for checking the sampler and solver without a GPU:
+ * the 3 indices hypothesis h of pair p draws from count >= 1 correspondences; the least-squares rigid fit of n >= 1
+ * pairs given as [n,3] f64 (src ~ R tgt + t) as a row-major 4x4. */
+int d3f_ransac_sample_host(uint64_t seed, int p, int h, int count, int32_t* out_host);
+int d3f_rigid_fit_host(const double* src_host, const double* tgt_host, int n, double* out_host);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
