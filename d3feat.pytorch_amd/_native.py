@@ -16,6 +16,7 @@ SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_f
            "registration.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_d = C.c_double
 
 
 class Tunables(C.Structure):
@@ -129,6 +130,14 @@ SIGNATURES = {
     "d3f_select_normalize_forward_pairs": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_select_normalize_backward_pairs": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_circle_det_loss_stats_floats": (_sz, [_i]),
+    "d3f_contrastive_det_loss_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    "d3f_contrastive_det_loss_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp]),
+    "d3f_contrastive_det_loss_forward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _d, _f, _f, _f, _f, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp]),
+    "d3f_contrastive_det_loss_backward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp]),
     "d3f_circle_det_loss_ws_bytes": (_sz, [_i]),
     "d3f_circle_det_loss_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
                                          _vp]),
@@ -148,6 +157,7 @@ SIGNATURES = {
     "d3f_rigid_fit_host": (_i, [_vp, _vp, _i, _vp]),
     "d3f_sgd_guarded_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "d3f_sgd_guarded_step_lanes": (_i, [_vp, _i, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "d3f_adam_guarded_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "d3f_poison_gradient_if_status": (_i, [_vp, _vp, _vp, _vp]),
 }
 

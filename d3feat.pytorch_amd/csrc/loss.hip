@@ -472,6 +472,202 @@ __global__ __launch_bounds__(256) void loss_bwd_tile_kernel(const float* __restr
   }
 }
 
+// ---- batch-hard contrastive loss + detector loss (reference utils/loss.py:47-97 with metric 'euclidean', :149-158) ----
+// Rows are independent: one wave per row i of a pair computes the row of D with the circle kernels' expression, adds 10
+// where the keypoints are closer than safe_radius (reference :57-60, evaluated in f64 like its NumPy), and keeps the
+// row's furthest positive (the diagonal), closest negative (lowest index on ties, like torch.min) and sum.
+//   dists = D + 10*near,  near_ij = (dist_keypts_ij + (i == j ? 10 : 0)) < safe_radius
+//   desc  = mean_i [max(fp_i - pos_margin, 0) + max(neg_margin - cn_i, 0)],  det = mean_i (fp_i - cn_i)(sa_i + sp_i)
+// stats layout (floats, d3f_circle_det_loss_stats_floats(M) per pair): [0,M) D_ii  [M,2M) D_i,arg_i  [2M,3M) fp
+// [4M,5M) cn  [5M,6M) arg_i (int).  The backward reads only these, the descriptors and the scores.
+__global__ __launch_bounds__(256) void contrastive_fwd_kernel(const float* __restrict__ a, const float* __restrict__ p,
+                                                              int M, int C, const double* __restrict__ dk,
+                                                              double safe_radius, float* __restrict__ dists,
+                                                              float* __restrict__ fp_out,
+                                                              float* __restrict__ avgneg_out,
+                                                              float* __restrict__ stats) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= M) return;
+  {  // blockIdx.y = fragment pair of a stacked batch: its own M x M problem
+    const size_t pr = blockIdx.y;
+    a += pr * M * C; p += pr * M * C; dk += pr * M * M; dists += pr * M * M;
+    fp_out += pr * M; avgneg_out += pr * M; stats += pr * 6 * M;
+  }
+  const float* ai = a + (size_t)i * C;
+  float sd = 0.0f, cm = INFINITY, cmd = 0.0f, dii = 0.0f, fpv = 0.0f;
+  int ca = 0x7fffffff;
+  for (int j = lane; j < M; j += 64) {
+    const float* pj = p + (size_t)j * C;
+    float acc = 0.0f;
+    for (int c = 0; c < C; ++c) {
+      const float df = ai[c] - pj[c];
+      acc += df * df;
+    }
+    const float d = sqrtf(acc + 1e-12f);
+    const bool near = (dk[(size_t)i * M + j] + (i == j ? 10.0 : 0.0)) < safe_radius;
+    const float e = d + (near ? 10.0f : 0.0f);
+    dists[(size_t)i * M + j] = e;
+    sd += e;
+    if (j == i) {
+      dii = d;
+      fpv = e;
+    } else if (e < cm) {   // j ascending within the lane: the first minimum stays
+      cm = e;
+      ca = j;
+      cmd = d;
+    }
+  }
+  sd = d3f::wave_sum(sd);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {  // (value, index) lexicographic min -> first minimal index like torch.min
+    const float ov = __shfl_xor(cm, o, 64);
+    const int oa = __shfl_xor(ca, o, 64);
+    const float od = __shfl_xor(cmd, o, 64);
+    if (ov < cm || (ov == cm && oa < ca)) { cm = ov; ca = oa; cmd = od; }
+  }
+  if (ca >= M) {   // no ordered candidate (a row of NaN): NaN statistics, and an index the backward may read
+    ca = i == 0 ? 1 : 0;
+    cm = cmd = __builtin_nanf("");
+  }
+  const int owner = i & 63;   // the lane that met j == i
+  dii = __shfl(dii, owner, 64);
+  fpv = __shfl(fpv, owner, 64);
+  if (lane == 0) {
+    stats[i] = dii;
+    stats[M + i] = cmd;
+    stats[2 * M + i] = fpv;
+    stats[3 * M + i] = 0.0f;
+    stats[4 * M + i] = cm;
+    ((int*)stats)[5 * M + i] = ca;
+    fp_out[i] = fpv;
+    avgneg_out[i] = (sd - fpv) / (float)(M - 1);
+  }
+}
+
+// scalars of the contrastive + detector loss from the per-row statistics; pairs and total as loss_finalize_kernel
+__global__ __launch_bounds__(256) void contrastive_finalize_kernel(int M, const float* __restrict__ sa,
+                                                                   const float* __restrict__ sp, float pos_margin,
+                                                                   float neg_margin, const float* __restrict__ avgneg_out,
+                                                                   const float* __restrict__ stats,
+                                                                   float* __restrict__ scalars, int pairs, float w_desc,
+                                                                   float w_det, float* __restrict__ total) {
+  __shared__ float sh[16];
+  const int tid = threadIdx.x;
+  float tot = 0.0f;
+  for (int pr = 0; pr < pairs; ++pr, sa += M, sp += M, avgneg_out += M, stats += 6 * M, scalars += 6) {
+    float l = 0.0f, dt = 0.0f, ac = 0.0f, fps = 0.0f, ans = 0.0f;
+    for (int i = tid; i < M; i += blockDim.x) {
+      const float fp = stats[2 * M + i], cn = stats[4 * M + i];
+      l += fmaxf(fp - pos_margin, 0.0f) + fmaxf(neg_margin - cn, 0.0f);
+      const float diff = fp - cn;
+      dt += diff * (sa[i] + sp[i]);
+      ac += diff < 0.0f ? 1.0f : 0.0f;
+      fps += fp;
+      ans += avgneg_out[i];
+    }
+    l = block_sum(l, sh);
+    dt = block_sum(dt, sh);
+    ac = block_sum(ac, sh);
+    fps = block_sum(fps, sh);
+    ans = block_sum(ans, sh);
+    if (tid == 0) {
+      scalars[0] = l / (float)M;
+      scalars[1] = dt / (float)M;
+      scalars[2] = ac * 100.0f / (float)M;
+      scalars[3] = fps / (float)M;
+      scalars[4] = ans / (float)M;
+      scalars[5] = l / (float)M + dt / (float)M;
+    }
+    tot += w_desc * (l / (float)M) + w_det * (dt / (float)M);
+  }
+  if (tid == 0 && total) *total = tot;
+}
+
+// torch.max(x, 0) (elementwise, reference :93): the gradient is split in half where x == 0 exactly
+__device__ __forceinline__ float hinge_grad(float x) { return x > 0.0f ? 1.0f : (x == 0.0f ? 0.5f : 0.0f); }
+
+// d loss / d dists of row i, at (i, i) and at (i, arg_i): the only entries that reach the loss
+__device__ __forceinline__ void contrastive_row_grads(const float* __restrict__ stats, int M, int i, float pos_margin,
+                                                      float neg_margin, float gdM, float gtM, float s, float& g_fp,
+                                                      float& g_cn) {
+  const float fp = stats[2 * M + i], cn = stats[4 * M + i];
+  g_fp = gdM * hinge_grad(fp - pos_margin) + gtM * s;
+  g_cn = -gdM * hinge_grad(neg_margin - cn) - gtM * s;
+}
+
+// wave m2 < M: grad of anchor row i = m2 (+ both score gradients); wave m2 >= M: grad of positive row j = m2 - M, which
+// collects its diagonal term and, in ascending i, every row whose closest negative it is (a fixed order: no atomics)
+__global__ __launch_bounds__(256) void contrastive_bwd_kernel(const float* __restrict__ a, const float* __restrict__ p,
+                                                              int M, int C, const float* __restrict__ sa,
+                                                              const float* __restrict__ sp, float pos_margin,
+                                                              float neg_margin, const float* __restrict__ stats,
+                                                              const float* __restrict__ g_desc,
+                                                              const float* __restrict__ g_det, float w_desc, float w_det,
+                                                              float* __restrict__ ga, float* __restrict__ gp,
+                                                              float* __restrict__ gsa, float* __restrict__ gsp) {
+  const int lane = threadIdx.x & 63;
+  const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m2 >= 2 * M) return;
+  {
+    const size_t pr = blockIdx.y;
+    a += pr * M * C; p += pr * M * C; stats += pr * 6 * M;
+    sa += pr * M; sp += pr * M; ga += pr * M * C; gp += pr * M * C;
+    if (gsa) gsa += pr * M;
+    if (gsp) gsp += pr * M;
+  }
+  const float invM = 1.0f / (float)M;
+  const float gdM = (g_desc ? *g_desc : 0.0f) * w_desc * invM, gtM = (g_det ? *g_det : 0.0f) * w_det * invM;
+  const int* arg = (const int*)stats + 5 * M;
+  if (m2 < M) {
+    const int i = m2, k = arg[i];
+    float g_fp, g_cn;
+    contrastive_row_grads(stats, M, i, pos_margin, neg_margin, gdM, gtM, sa[i] + sp[i], g_fp, g_cn);
+    const float wd = g_fp / stats[i], wn = g_cn / stats[M + i];
+    for (int c = lane; c < C; c += 64) {
+      const float ac = a[(size_t)i * C + c];
+      ga[(size_t)i * C + c] = wd * (ac - p[(size_t)i * C + c]) + wn * (ac - p[(size_t)k * C + c]);
+    }
+    if (lane == 0) {
+      const float v = gtM * (stats[2 * M + i] - stats[4 * M + i]);
+      if (gsa) gsa[i] = v;
+      if (gsp) gsp[i] = v;
+    }
+    return;
+  }
+  const int j = m2 - M;
+  float acc[4];
+  const int nc = (C + 63) / 64;
+  {
+    float g_fp, g_cn;
+    contrastive_row_grads(stats, M, j, pos_margin, neg_margin, gdM, gtM, sa[j] + sp[j], g_fp, g_cn);
+    const float wd = g_fp / stats[j];
+    for (int q = 0; q < 4; ++q) {
+      const int c = lane + 64 * q;
+      acc[q] = (q < nc && c < C) ? wd * (p[(size_t)j * C + c] - a[(size_t)j * C + c]) : 0.0f;
+    }
+  }
+  for (int base = 0; base < M; base += 64) {
+    const int i0 = base + lane;
+    unsigned long long hit = __ballot(i0 < M && arg[i0] == j);
+    while (hit) {
+      const int i = base + __builtin_ctzll(hit);
+      hit &= hit - 1;
+      float g_fp, g_cn;
+      contrastive_row_grads(stats, M, i, pos_margin, neg_margin, gdM, gtM, sa[i] + sp[i], g_fp, g_cn);
+      const float wn = g_cn / stats[M + i];
+      for (int q = 0; q < 4; ++q) {
+        const int c = lane + 64 * q;
+        if (q < nc && c < C) acc[q] += wn * (p[(size_t)j * C + c] - a[(size_t)i * C + c]);
+      }
+    }
+  }
+  for (int q = 0; q < 4; ++q) {
+    const int c = lane + 64 * q;
+    if (q < nc && c < C) gp[(size_t)j * C + c] = acc[q];
+  }
+}
+
 // ---- keypoint selection + L2 normalisation of the selected descriptors -------------------------------------------
 // The reference normalises ALL N descriptors (architectures.py:318, F.normalize) and then indexes the M sampled
 // correspondences out of them and out of the scores (trainer.py:91-94): ~10 PyTorch launches forward and ~15 backward
@@ -645,6 +841,82 @@ int d3f_circle_det_loss_backward_pairs(const float* anchor, const float* positiv
       grad_positive, grad_anc_score, grad_pos_score, w_desc, w_det);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
+}
+
+static int contrastive_forward_impl(const float* anchor, const float* positive, int M, int C, int pairs,
+                                    const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                    double safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                    float* dists, float* furthest_positive, float* average_negative, float* out_scalars,
+                                    float* out_total, float* stats, void* stream) {
+  if (!anchor || !positive || !dist_keypts || !anc_score || !pos_score || !dists || !furthest_positive ||
+      !average_negative || !out_scalars || !stats || M < 2 || M > kMaxM || C < 1 || C > 256 || pairs < 1 || pairs > 32)
+    return D3F_EINVAL;
+  contrastive_fwd_kernel<<<dim3(d3f::cdiv(M, 4), pairs), 256, 0, (hipStream_t)stream>>>(
+      anchor, positive, M, C, dist_keypts, safe_radius, dists, furthest_positive, average_negative, stats);
+  D3F_LAUNCH_CHECK();
+  contrastive_finalize_kernel<<<1, 256, 0, (hipStream_t)stream>>>(M, anc_score, pos_score, pos_margin, neg_margin,
+                                                                  average_negative, stats, out_scalars, pairs, w_desc,
+                                                                  w_det, out_total);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C,
+                                     const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                     double safe_radius, float pos_margin, float neg_margin, float* dists,
+                                     float* furthest_positive, float* average_negative, float* out_scalars,
+                                     float* stats, void* stream) {
+  return contrastive_forward_impl(anchor, positive, M, C, 1, dist_keypts, anc_score, pos_score, safe_radius, pos_margin,
+                                  neg_margin, 1.0f, 1.0f, dists, furthest_positive, average_negative, out_scalars,
+                                  nullptr, stats, stream);
+}
+
+int d3f_contrastive_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
+                                           const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                           double safe_radius, float pos_margin, float neg_margin, float w_desc,
+                                           float w_det, float* dists, float* furthest_positive,
+                                           float* average_negative, float* out_scalars, float* out_total, float* stats,
+                                           void* stream) {
+  if (!out_total) return D3F_EINVAL;
+  return contrastive_forward_impl(anchor, positive, M, C, pairs, dist_keypts, anc_score, pos_score, safe_radius,
+                                  pos_margin, neg_margin, w_desc, w_det, dists, furthest_positive, average_negative,
+                                  out_scalars, out_total, stats, stream);
+}
+
+static int contrastive_backward_impl(const float* anchor, const float* positive, int M, int C, int pairs,
+                                     const float* anc_score, const float* pos_score, float pos_margin, float neg_margin,
+                                     const float* stats, const float* grad_desc, const float* grad_det, float w_desc,
+                                     float w_det, float* grad_anchor, float* grad_positive, float* grad_anc_score,
+                                     float* grad_pos_score, void* stream) {
+  if (!anchor || !positive || !anc_score || !pos_score || !stats || !grad_anchor || !grad_positive || M < 2 ||
+      M > kMaxM || C < 1 || C > 256 || pairs < 1 || pairs > 32)
+    return D3F_EINVAL;
+  contrastive_bwd_kernel<<<dim3(d3f::cdiv(2 * M, 4), pairs), 256, 0, (hipStream_t)stream>>>(
+      anchor, positive, M, C, anc_score, pos_score, pos_margin, neg_margin, stats, grad_desc, grad_det, w_desc, w_det,
+      grad_anchor, grad_positive, grad_anc_score, grad_pos_score);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, const float* anc_score,
+                                      const float* pos_score, float pos_margin, float neg_margin, const float* stats,
+                                      const float* grad_desc, const float* grad_det, float* grad_anchor,
+                                      float* grad_positive, float* grad_anc_score, float* grad_pos_score,
+                                      void* stream) {
+  return contrastive_backward_impl(anchor, positive, M, C, 1, anc_score, pos_score, pos_margin, neg_margin, stats,
+                                   grad_desc, grad_det, 1.0f, 1.0f, grad_anchor, grad_positive, grad_anc_score,
+                                   grad_pos_score, stream);
+}
+
+int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
+                                            const float* anc_score, const float* pos_score, float pos_margin,
+                                            float neg_margin, float w_desc, float w_det, const float* stats,
+                                            const float* grad_total, float* grad_anchor, float* grad_positive,
+                                            float* grad_anc_score, float* grad_pos_score, void* stream) {
+  if (!grad_total) return D3F_EINVAL;
+  return contrastive_backward_impl(anchor, positive, M, C, pairs, anc_score, pos_score, pos_margin, neg_margin, stats,
+                                   grad_total, grad_total, w_desc, w_det, grad_anchor, grad_positive, grad_anc_score,
+                                   grad_pos_score, stream);
 }
 
 /* Sampled-correspondence front end of the loss -- replaces F.normalize over all N descriptors

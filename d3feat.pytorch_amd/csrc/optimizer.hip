@@ -104,6 +104,68 @@ __global__ __launch_bounds__(256) void sgd_kernel(Lanes lanes, float* __restrict
   }
 }
 
+// Guarded Adam (reference training_3DMatch.py:69-75, torch.optim.Adam: amsgrad=False, maximize=False, L2 weight decay)
+// on the same flat buffers, after the same nonfinite_kernel.  torch's single-tensor order, unfused:
+//   g = (lane 0 + lane 1 + ...) * gs;  g = g + wd*p;  m = m + (1-b1)*(g - m);  v = v*b2 + (1-b2)*g*g
+//   p = p + (-step_size) * (m / (sqrt(v)/bc2 + eps)),  step_size = lr/(1 - b1^t), bc2 = sqrt(1 - b2^t)  (f64 -> f32)
+// with t = the device step counter + 1.  The counter itself is advanced by adam_tick_kernel, one thread launched after
+// the update: every block of the update has read the old value by then.  HBM-bound: 16 B read + 12 B written per
+// parameter and lane (4 B more per extra lane), 4 B per lane in the guard.
+__device__ __forceinline__ void adam1(float g, float& p, float& m, float& v, float gs, float wd, float omb1, float b2,
+                                      float omb2, float eps, float neg_ss, float bc2) {
+  g = g * gs;
+  g = g + wd * p;
+  m = m + omb1 * (g - m);
+  v = v * b2 + omb2 * g * g;
+  p = p + neg_ss * (m / (sqrtf(v) / bc2 + eps));
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(Lanes lanes, float* __restrict__ p, float* __restrict__ m,
+                                                   float* __restrict__ v, size_t n, const double* __restrict__ hyper,
+                                                   const float* __restrict__ step, const int* __restrict__ state) {
+  if (__builtin_nontemporal_load(state) != 0) return;   // skipped: p, m, v and the counter stay as they are
+  // device-resident f64 {lr, beta1, beta2, eps, weight_decay, grad_scale} (torch's Python floats; changeable under a
+  // captured graph): the scalars reach the arithmetic as torch hands them to its f32 kernels, 1 - beta in f64 first
+  const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2];
+  const float eps = (float)hyper[3], wd = (float)hyper[4], gs = (float)hyper[5];
+  const double t = (double)*step + 1.0;
+  const float neg_ss = (float)(-(lr / (1.0 - pow(b1, t))));
+  const float bc2 = (float)sqrt(1.0 - pow(b2, t));
+  const float omb1 = (float)(1.0 - b1), fb2 = (float)b2, omb2 = (float)(1.0 - b2);
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 gv = ((const float4*)lanes.g[0])[i];
+    for (int l = 1; l < lanes.n; ++l) {  // fixed order: lane 0 + lane 1 + ...
+      const float4 o = ((const float4*)lanes.g[l])[i];
+      gv.x += o.x;
+      gv.y += o.y;
+      gv.z += o.z;
+      gv.w += o.w;
+    }
+    float4 pv = ((float4*)p)[i], mv = ((float4*)m)[i], vv = ((float4*)v)[i];
+    adam1(gv.x, pv.x, mv.x, vv.x, gs, wd, omb1, fb2, omb2, eps, neg_ss, bc2);
+    adam1(gv.y, pv.y, mv.y, vv.y, gs, wd, omb1, fb2, omb2, eps, neg_ss, bc2);
+    adam1(gv.z, pv.z, mv.z, vv.z, gs, wd, omb1, fb2, omb2, eps, neg_ss, bc2);
+    adam1(gv.w, pv.w, mv.w, vv.w, gs, wd, omb1, fb2, omb2, eps, neg_ss, bc2);
+    ((float4*)p)[i] = pv;
+    ((float4*)m)[i] = mv;
+    ((float4*)v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t i = n4 * 4 + threadIdx.x;
+    float gv = lanes.g[0][i];
+    for (int l = 1; l < lanes.n; ++l) gv += lanes.g[l][i];
+    adam1(gv, p[i], m[i], v[i], gs, wd, omb1, fb2, omb2, eps, neg_ss, bc2);
+  }
+}
+
+// after the update: an applied step advances the counter, a skipped one is counted
+__global__ void adam_tick_kernel(float* __restrict__ step, int* __restrict__ state) {
+  if (threadIdx.x != 0) return;
+  if (state[0]) atomicAdd(state + 1, 1);
+  else *step += 1.0f;
+}
+
 __global__ void poison_kernel(float* __restrict__ g, const int32_t* __restrict__ pair_status, int* __restrict__ state) {
   if (threadIdx.x != 0) return;
   const int f = *pair_status;
@@ -155,6 +217,42 @@ int d3f_sgd_guarded_step(const float* grad, float* params, float* momentum_buf, 
                          void* stream) {
   return d3f_sgd_guarded_step_lanes(&grad, 1, params, momentum_buf, n, lr, momentum, weight_decay, hyper_device, state,
                                     pair_status, stream);
+}
+
+/* Guarded Adam on the same flat buffers and with the same guard, state and pair_status as d3f_sgd_guarded_step_lanes
+ * (replaces the reference's torch.optim.Adam(lr, betas=(0.9, 0.999), weight_decay) step, training_3DMatch.py:69-75,
+ * with the guard of trainer.py:104-111).  grads: a HOST array of n_grads (1..4) device gradient buffers, summed in
+ * order.  params, exp_avg, exp_avg_sq: [n] fp32, 16-byte aligned.  step: device float[1], the number of applied steps
+ * (torch's per-parameter `step`); an applied step advances it, a skipped one leaves params, moments and step untouched
+ * and increments state[1].  hyper_device: double[6] on the device = {lr, beta1, beta2, eps, weight_decay, grad_scale},
+ * read at execution time.  Three launches: guard, update, one-thread counter. */
+int d3f_adam_guarded_step(const float* const* grads, int n_grads, float* params, float* exp_avg, float* exp_avg_sq,
+                          float* step, size_t n, const double* hyper_device, int32_t* state, const int32_t* pair_status,
+                          void* stream) {
+  if (!grads || n_grads < 1 || n_grads > kMaxLanes || !params || !exp_avg || !exp_avg_sq || !step || !hyper_device ||
+      !state)
+    return D3F_EINVAL;
+  Lanes lanes = {};
+  lanes.n = n_grads;
+  uintptr_t bits = (uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq;
+  for (int l = 0; l < n_grads; ++l) {
+    if (!grads[l]) return D3F_EINVAL;
+    lanes.g[l] = grads[l];
+    bits |= (uintptr_t)grads[l];
+  }
+  if ((bits & 15) != 0) return D3F_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (d3f::zero_async(state, sizeof(int32_t), st) != hipSuccess) return D3F_ELAUNCH;
+  const int blocks = (int)std::min<size_t>(2048, (size_t)d3f::cdiv((long long)(n / 4 + 1), 256));
+  if (n > 0) {
+    nonfinite_kernel<<<blocks, 256, 0, st>>>(lanes, n, state, pair_status);
+    D3F_LAUNCH_CHECK();
+    adam_kernel<<<blocks, 256, 0, st>>>(lanes, params, exp_avg, exp_avg_sq, n, hyper_device, step, state);
+    D3F_LAUNCH_CHECK();
+  }
+  adam_tick_kernel<<<1, 64, 0, st>>>(step, state);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
 }
 
 /* Data-parallel form of the same gate: BEFORE the gradient exchange, a rank whose pair raised a status flag turns

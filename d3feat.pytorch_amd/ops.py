@@ -2481,6 +2481,201 @@ def train_loss_pairs(x, scores, corr, lens, dist_keypts=None, log_scale=10.0, sa
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# contrastive + detector loss (utils/loss.py:47-97 with metric 'euclidean', :149-158; desc_loss 'contrastive')
+# ---------------------------------------------------------------------------------------------------------------
+def _dk64(dist_keypts, shape, device):
+    dk = dist_keypts.to(device=device, dtype=torch.float64).contiguous()
+    if tuple(dk.shape) != tuple(shape):
+        raise ValueError("dist_keypts must be [%s], got %s" % (",".join(map(str, shape)), tuple(dk.shape)))
+    return dk
+
+
+def _contrastive_fwd(oa, op, sa, sp, dk, P, M, params, weights):
+    """Forward launches on selected rows oa/op [P*M,C]: (scalars [P,6], total or None, dists, fp, an, stats)."""
+    L = _native.lib()
+    C, dev = int(oa.shape[1]), oa.device
+    sr, pm, nm = params
+    dists = torch.empty((P, M, M), dtype=torch.float32, device=dev)
+    fp = torch.empty(P * M, dtype=torch.float32, device=dev)
+    an = torch.empty(P * M, dtype=torch.float32, device=dev)
+    scalars = torch.empty((P, 6), dtype=torch.float32, device=dev)
+    stats = torch.empty(P * L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
+    if weights is None:
+        total = None
+        _native.check(L.d3f_contrastive_det_loss_forward(_p(oa), _p(op), M, C, _p(dk), _p(sa), _p(sp), sr, pm, nm,
+                                                         _p(dists), _p(fp), _p(an), _p(scalars), _p(stats), _stream()),
+                      "d3f_contrastive_det_loss_forward")
+    else:
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        _native.check(L.d3f_contrastive_det_loss_forward_pairs(_p(oa), _p(op), M, C, P, _p(dk), _p(sa), _p(sp), sr, pm,
+                                                               nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
+                                                               _p(scalars), _p(total), _p(stats), _stream()),
+                      "d3f_contrastive_det_loss_forward_pairs")
+    return scalars, total, dists, fp, an, stats
+
+
+def _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs):
+    L = _native.lib()
+    C = int(oa.shape[1])
+    _, pm, nm = params
+    ga, gp = torch.empty_like(oa), torch.empty_like(op)
+    gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
+    if weights is None:
+        _native.check(L.d3f_contrastive_det_loss_backward(_p(oa), _p(op), M, C, _p(sa), _p(sp), pm, nm, _p(stats),
+                                                          g_ptrs[0], g_ptrs[1], _p(ga), _p(gp), _p(gsa), _p(gsp),
+                                                          _stream()), "d3f_contrastive_det_loss_backward")
+    else:
+        _native.check(L.d3f_contrastive_det_loss_backward_pairs(_p(oa), _p(op), M, C, P, _p(sa), _p(sp), pm, nm,
+                                                                weights[0], weights[1], _p(stats), g_ptrs[0], _p(ga),
+                                                                _p(gp), _p(gsa), _p(gsp), _stream()),
+                      "d3f_contrastive_det_loss_backward_pairs")
+    return ga, gp, gsa, gsp
+
+
+class _ContrastiveDetFn(torch.autograd.Function):
+    """Returns (scalars[6], dists[M,M], furthest_positive[M], average_negative[M]); scalars[0] = desc loss,
+    scalars[1] = det loss are differentiable wrt anchor / positive / scores."""
+
+    @staticmethod
+    def forward(ctx, anchor, positive, dk, anc_score, pos_score, params):
+        M = int(anchor.shape[0])
+        scalars, _, dists, fp, an, stats = _contrastive_fwd(anchor, positive, anc_score, pos_score, dk, 1, M, params, None)
+        scalars, dists = scalars.view(6), dists.view(M, M)
+        ctx.save_for_backward(anchor, positive, anc_score, pos_score, stats)
+        ctx.params = params
+        ctx.mark_non_differentiable(dists, fp, an)
+        ctx.set_materialize_grads(False)
+        return scalars, dists, fp, an
+
+    @staticmethod
+    def backward(ctx, g_scalars, g_dists, g_fp, g_an):
+        if g_scalars is None:
+            return (None,) * 6
+        anchor, positive, anc_score, pos_score, stats = ctx.saved_tensors
+        g = g_scalars.contiguous().float()
+        ga, gp, gsa, gsp = _contrastive_bwd(anchor, positive, anc_score, pos_score, stats, 1, int(anchor.shape[0]),
+                                            ctx.params, None, (g.data_ptr(), g.data_ptr() + 4))
+        return ga, gp, None, gsa, gsp, None
+
+
+def contrastive_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, safe_radius=0.1, pos_margin=0.1,
+                         neg_margin=1.4):
+    """The reference's ``ContrastiveLoss(pos_margin, neg_margin, 'euclidean', safe_radius)`` followed by ``DetLoss`` on
+    its ``dists``, in two launches (d3f_contrastive_det_loss_forward).  ``dist_keypts`` [M,M] is read as float64.
+    Returns (scalars[6] = desc, det, accuracy, mean furthest positive, mean average negative, desc + det;
+    dists [M,M] with the +10s; furthest_positive [M]; average_negative [M]); desc and det carry gradient."""
+    anchor, positive = _f32(anchor, "anchor"), _f32(positive, "positive")
+    M = int(anchor.shape[0])
+    if not 2 <= M <= 1024 or tuple(positive.shape) != tuple(anchor.shape) or not 1 <= int(anchor.shape[1]) <= 256:
+        raise ValueError("anchor / positive must both be [M,C] with 2 <= M <= 1024, C <= 256")
+    dk = _dk64(dist_keypts, (M, M), anchor.device)
+    sa = _f32(anc_score, "anc_score").reshape(-1)
+    sp = _f32(pos_score, "pos_score").reshape(-1)
+    return _ContrastiveDetFn.apply(anchor, positive, dk, sa, sp,
+                                   (float(safe_radius), float(pos_margin), float(neg_margin)))
+
+
+class _TrainContrastiveFn(torch.autograd.Function):
+    """_TrainLossFn / _TrainLossPairsFn with the contrastive loss: the select + normalise launches of the circle's
+    training forms, then the contrastive launches.  ``lens`` None: one pair (corr [M,2], p_offset); otherwise P stacked
+    pairs (corr [P*M,2] cloud-local, lens int32 [2P])."""
+
+    @staticmethod
+    def forward(ctx, x, scores, corr, p_offset, lens, dk, P, params, weights):
+        M = int(dk.shape[-1])
+        N, C = int(x.shape[0]), int(x.shape[1])
+        if lens is None:
+            ia, ip, stride = _corr_columns(corr[:, 0], corr[:, 1])
+            oa, op, sa, sp = _select_normalize_fwd(x, scores, ia, ip, stride, p_offset)
+            ctx.sel = (stride, p_offset is not None)
+            saved = (ia, ip, p_offset if p_offset is not None else ia.new_empty(0))
+        else:
+            T, dev = P * M, x.device
+            oa = torch.empty((T, C), dtype=torch.float32, device=dev)
+            op = torch.empty((T, C), dtype=torch.float32, device=dev)
+            sa = torch.empty(T, dtype=torch.float32, device=dev)
+            sp = torch.empty(T, dtype=torch.float32, device=dev)
+            _native.check(_native.lib().d3f_select_normalize_forward_pairs(_p(x), _p(scores), N, C, _p(corr), M, P,
+                                                                           _p(lens), _p(oa), _p(op), _p(sa), _p(sp),
+                                                                           _stream()),
+                          "d3f_select_normalize_forward_pairs")
+            ctx.sel = None
+            saved = (corr, lens, corr.new_empty(0))
+        scalars, total, dists, fp, an, stats = _contrastive_fwd(oa, op, sa, sp, dk, P, M, params, weights)
+        ctx.save_for_backward(x, *saved, oa, op, sa, sp, stats)
+        ctx.meta = (P, M, params, weights)
+        ctx.mark_non_differentiable(scalars, dists, fp, an)
+        ctx.set_materialize_grads(False)
+        return total, scalars, dists, fp, an
+
+    @staticmethod
+    def backward(ctx, g_total, g_scalars, g_dists, g_fp, g_an):
+        if g_total is None:
+            return (None,) * 9
+        x, s0, s1, s2, oa, op, sa, sp, stats = ctx.saved_tensors
+        P, M, params, weights = ctx.meta
+        g = g_total.contiguous().float().reshape(1)
+        ga, gp, gsa, gsp = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, (g.data_ptr(), None))
+        N, C = int(x.shape[0]), int(x.shape[1])
+        if ctx.sel is not None:
+            stride, has_off = ctx.sel
+            gx, gs = _select_normalize_bwd(x, s0, s1, stride, s2 if has_off else None, ga, gp, gsa, gsp)
+        else:
+            buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
+            gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+            _native.check(_native.lib().d3f_select_normalize_backward_pairs(_p(x), N, C, _p(s0), M, P, _p(s1), _p(ga),
+                                                                            _p(gp), _p(gsa), _p(gsp), _p(gx), _p(gs),
+                                                                            _stream()),
+                          "d3f_select_normalize_backward_pairs")
+        return gx, gs, None, None, None, None, None, None, None
+
+
+def train_contrastive_loss(x, scores, corr, p_offset, dist_keypts, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
+                           w_desc=1.0, w_det=1.0):
+    """``train_loss`` with the reference's desc_loss 'contrastive' (training_3DMatch.py:119-125):
+    ``w_desc * ContrastiveLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset], dist_keypts) + w_det *
+    DetLoss(dists, ...)``.  Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only
+    ``total`` carries gradient."""
+    x = _f32(x, "x")
+    sc = _f32(scores, "scores").reshape(-1, 1)
+    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
+        raise ValueError("corr must be an int64 [M,2] device tensor")
+    corr = corr.contiguous()
+    M = int(corr.shape[0])
+    if not 2 <= M <= 1024 or int(x.shape[1]) > 256:
+        raise ValueError("contrastive loss: 2 <= M <= 1024 correspondences, C <= 256 channels")
+    dk = _dk64(dist_keypts, (1, M, M), x.device) if dist_keypts.dim() == 3 else _dk64(dist_keypts, (M, M), x.device)
+    total, scalars, dists, fp, an = _TrainContrastiveFn.apply(
+        x, sc, corr, _p_offset(p_offset, x.device), None, dk, 1,
+        (float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)))
+    return total, scalars[0, 0], scalars[0, 1], scalars[0, 2], fp, an
+
+
+def train_contrastive_loss_pairs(x, scores, corr, lens, dist_keypts, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
+                                 w_desc=1.0, w_det=1.0):
+    """``train_loss_pairs`` with the contrastive loss: P stacked pairs, ``dist_keypts`` [P,M,M] (read as float64),
+    total = sum_p (w_desc desc_p + w_det det_p).
+    Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
+    x = _f32(x, "x")
+    sc = _f32(scores, "scores").reshape(-1, 1)
+    if dist_keypts.dim() != 3 or dist_keypts.shape[1] != dist_keypts.shape[2]:
+        raise ValueError("dist_keypts must be [P,M,M]")
+    P, M = int(dist_keypts.shape[0]), int(dist_keypts.shape[1])
+    dk = _dk64(dist_keypts, (P, M, M), x.device)
+    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
+        raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
+    corr = corr.contiguous().view(P * M, 2)
+    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
+        raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
+    if not 2 <= M <= 1024 or int(x.shape[1]) > 256 or P > 32:
+        raise ValueError("stacked contrastive loss: 2 <= M <= 1024, C <= 256 channels, P <= 32 pairs")
+    total, scalars, dists, fp, an = _TrainContrastiveFn.apply(
+        x, sc, corr, None, lens.contiguous(), dk, P, (float(safe_radius), float(pos_margin), float(neg_margin)),
+        (float(w_desc), float(w_det)))
+    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # dense mutual-NN matching (geometric_registration/common.py:5-21)
 # ---------------------------------------------------------------------------------------------------------------
 def mutual_nn(source_desc, target_desc):
@@ -2616,6 +2811,34 @@ def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, sta
                 ctypes.cast(ptrs, ctypes.c_void_p), len(lanes), _p(params), _p(momentum_buf), grad.numel(), float(lr),
                 float(momentum), float(weight_decay), _p(hyper) if hyper is not None else None, _p(state),
                 _p(pair_status), _stream()), "d3f_sgd_guarded_step_lanes")
+
+
+def adam_guarded_step(grad, params, exp_avg, exp_avg_sq, step, hyper, state, pair_status=None):
+    """In place, torch.optim.Adam's step (amsgrad off, L2 weight decay) on flat buffers unless a gradient holds a
+    non-finite value or ``pair_status`` is set (then nothing changes but state[1] += 1; see sgd_guarded_step).
+    ``grad``: one gradient buffer or a list of up to four (summed in order).  ``step``: device fp32[1], applied steps so
+    far (advanced by an applied step).  ``hyper``: device fp64[6] {lr, beta1, beta2, eps, weight_decay, grad_scale},
+    read when the kernels run."""
+    lanes = list(grad) if isinstance(grad, (list, tuple)) else [grad]
+    if not 1 <= len(lanes) <= 4:
+        raise ValueError("1..4 gradient buffers, got %d" % len(lanes))
+    n = lanes[0].numel()
+    for t, name in [(g, "grad") for g in lanes] + [(params, "params"), (exp_avg, "exp_avg"),
+                                                   (exp_avg_sq, "exp_avg_sq")]:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError("%s must be a contiguous fp32 device tensor of %d elements" % (name, n))
+    if not (step.is_cuda and step.dtype == torch.float32 and step.numel() == 1):
+        raise ValueError("step must be an fp32[1] device tensor")
+    if not (hyper.is_cuda and hyper.dtype == torch.float64 and hyper.numel() == 6 and hyper.is_contiguous()):
+        raise ValueError("hyper must be a contiguous fp64[6] device tensor")
+    if not (state.is_cuda and state.dtype == torch.int32 and state.numel() >= 4):
+        raise ValueError("state must be an int32[4] device tensor")
+    import ctypes
+    ptrs = (ctypes.c_void_p * len(lanes))(*[g.data_ptr() for g in lanes])
+    with _region("adam", (24 + 8 * len(lanes)) * n):
+        _native.check(_native.lib().d3f_adam_guarded_step(
+            ctypes.cast(ptrs, ctypes.c_void_p), len(lanes), _p(params), _p(exp_avg), _p(exp_avg_sq), _p(step), n,
+            _p(hyper), _p(state), _p(pair_status), _stream()), "d3f_adam_guarded_step")
 
 
 def poison_gradient_if_status(grad, pair_status, state):

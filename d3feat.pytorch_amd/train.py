@@ -203,6 +203,10 @@ class GuardedSGD:
                 raise ValueError("momentum buffer %s has shape %s, parameter has %s" % (key, tuple(mb.shape), tuple(p.shape)))
             self.buf[off:off + p.numel()].copy_(mb.reshape(-1))
 
+    def device_state(self):
+        """The tensors that make up the optimizer's state besides the parameters (a capture warm-up restores them)."""
+        return self.buf, self.state
+
     @property
     def skipped(self):
         return self.state[1]
@@ -240,6 +244,203 @@ class GuardedSGD:
         self.flat.data.sub_(torch.where(ok, new_buf, torch.zeros_like(new_buf)), alpha=self.lr)
         self.state[1] += (~ok).to(torch.int32)
         return ok
+
+
+class GuardedAdam:
+    """torch.optim.Adam (amsgrad off, L2 weight decay) on flat buffers -- the reference's optimizer 'ADAM'
+    (training_3DMatch.py:69-75) -- with GuardedSGD's interface and guard: a step whose gradient holds a non-finite value
+    or whose pair was flagged leaves parameters, moments and the step counter untouched (the reference does not call
+    optimizer.step() then, trainer.py:104-111).  On the GPU this is d3f_adam_guarded_step (three launches, no host
+    sync; the counter ``t`` lives on the device); the torch expression below is the same arithmetic for host tensors."""
+
+    def __init__(self, flat, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.flat = flat
+        dev = flat.data.device
+        self.m = torch.zeros_like(flat.data)
+        self.v = torch.zeros_like(flat.data)
+        self.t = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.state = torch.zeros(4, dtype=torch.int32, device=dev)   # as GuardedSGD.state
+        # {lr, beta1, beta2, eps, weight_decay, grad_scale} in f64 on the device (torch's Python floats), read by the
+        # kernels when they run: a schedule reaches an already captured graph
+        self._hyper = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 1.0]
+        self.hyper = torch.tensor(self._hyper, dtype=torch.float64, device=dev)
+        self.initial_lr = float(lr)
+
+    def _set(self, i, v):
+        self._hyper[i] = float(v)
+        self.hyper[i] = float(v)   # stream-ordered fill, no sync
+
+    lr = property(lambda self: self._hyper[0], lambda self, v: self._set(0, v))
+    betas = property(lambda self: (self._hyper[1], self._hyper[2]),
+                     lambda self, v: (self._set(1, v[0]), self._set(2, v[1])))
+    eps = property(lambda self: self._hyper[3], lambda self, v: self._set(3, v))
+    weight_decay = property(lambda self: self._hyper[4], lambda self, v: self._set(4, v))
+    grad_scale = property(lambda self: self._hyper[5], lambda self, v: self._set(5, v))
+
+    def use_grad_scale(self, v):
+        """See GuardedSGD.use_grad_scale."""
+        v = float(v)
+        if self._hyper[5] == v:
+            return
+        if self.hyper.is_cuda:
+            torch.cuda.synchronize(self.hyper.device)
+        self.grad_scale = v
+        if self.hyper.is_cuda:
+            torch.cuda.current_stream(self.hyper.device).synchronize()
+
+    def device_state(self):
+        """The tensors that make up the optimizer's state besides the parameters (a capture warm-up restores them)."""
+        return self.m, self.v, self.t, self.state
+
+    @property
+    def param_groups(self):
+        """Read-only view in torch.optim.Adam's shape."""
+        return [{'lr': self.lr, 'betas': self.betas, 'eps': self.eps, 'weight_decay': self.weight_decay,
+                 'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False,
+                 'fused': None, 'decoupled_weight_decay': False, 'initial_lr': self.initial_lr,
+                 'params': list(range(self.flat.n_module_params))}]
+
+    def state_dict(self):
+        """Same layout as ``torch.optim.Adam.state_dict()`` over ``model.parameters()``: per parameter ``step`` (a
+        scalar f32 tensor), ``exp_avg`` and ``exp_avg_sq``; nothing for a parameter before its first step."""
+        state, off = {}, 0
+        t = float(self.t.item())
+        for idx, p in zip(self.flat.module_index, self.flat.params):
+            if t > 0:
+                state[idx] = {'step': torch.tensor(t, dtype=torch.float32),
+                              'exp_avg': self.m[off:off + p.numel()].view_as(p).detach().clone(),
+                              'exp_avg_sq': self.v[off:off + p.numel()].view_as(p).detach().clone()}
+            off += p.numel()
+        return {'state': state, 'param_groups': self.param_groups}
+
+    def load_state_dict(self, sd):
+        groups = sd.get('param_groups') or [{}]
+        group = groups[0]
+        if len(groups) != 1 or 'betas' not in group or 'momentum' in group:
+            raise ValueError("GuardedAdam loads a single-group torch.optim.Adam state")
+        if group.get('amsgrad', False) or group.get('maximize', False) or group.get('decoupled_weight_decay', False):
+            raise ValueError("GuardedAdam is Adam with L2 weight decay: amsgrad, maximize and decoupled weight decay "
+                             "are not supported")
+        if len(group['params']) != self.flat.n_module_params:
+            raise ValueError("optimizer state covers %d parameters, the model has %d" % (
+                len(group['params']), self.flat.n_module_params))
+        slot, off = {}, 0
+        for idx, p in zip(self.flat.module_index, self.flat.params):
+            slot[idx] = (off, p)
+            off += p.numel()
+        steps, moments = set(), []
+        for key, st in sd['state'].items():
+            if 'exp_avg' not in st or 'exp_avg_sq' not in st or 'step' not in st or 'max_exp_avg_sq' in st:
+                raise ValueError("optimizer state for parameter %s is not torch.optim.Adam's" % key)
+            if int(key) not in slot:
+                raise ValueError("optimizer state for parameter %s, which is not trainable here" % key)
+            off, p = slot[int(key)]
+            for name in ('exp_avg', 'exp_avg_sq'):
+                if tuple(st[name].shape) != tuple(p.shape):
+                    raise ValueError("%s %s has shape %s, parameter has %s" % (name, key, tuple(st[name].shape),
+                                                                              tuple(p.shape)))
+            steps.add(float(st['step']))
+            moments.append((off, p, st))
+        if len(steps) > 1:
+            raise ValueError("per-parameter Adam steps differ (%s): the flat optimizer keeps one counter"
+                             % sorted(steps))
+        if moments and len(moments) != len(slot):
+            raise ValueError("optimizer state covers %d of the %d trainable parameters" % (len(moments), len(slot)))
+        self.lr, self.betas = group['lr'], tuple(group['betas'])
+        self.eps, self.weight_decay = group['eps'], group['weight_decay']
+        self.initial_lr = float(group.get('initial_lr', self.initial_lr))
+        self.m.zero_()
+        self.v.zero_()
+        for off, p, st in moments:
+            self.m[off:off + p.numel()].copy_(st['exp_avg'].reshape(-1))
+            self.v[off:off + p.numel()].copy_(st['exp_avg_sq'].reshape(-1))
+        self.t.fill_(steps.pop() if steps else 0.0)
+
+    @property
+    def skipped(self):
+        return self.state[1]
+
+    @torch.no_grad()
+    def step(self, want_ok=True, pair_status=None, grads=None):
+        """As GuardedSGD.step."""
+        g = self.flat.grad if grads is None else list(grads)
+        on_gpu = (g if grads is None else g[0]).is_cuda
+        if on_gpu:
+            before = self.state[1].clone() if want_ok else None
+            ops.adam_guarded_step(g, self.flat.data, self.m, self.v, self.t, self.hyper, self.state,
+                                  pair_status=pair_status)
+            return (self.state[1] == before) if want_ok else None
+        lanes = g if grads is not None else [g]
+        total = lanes[0].clone()
+        for other in lanes[1:]:
+            total += other
+        g = total
+        ok = torch.isfinite(g).all()
+        for lane in lanes:
+            ok = ok & torch.isfinite(lane).all()
+        if pair_status is not None:
+            bad = pair_status.reshape(-1)[0] != 0
+            self.state[2] |= pair_status.reshape(-1)[0].to(self.state.dtype)
+            self.state[3] += bad.to(self.state.dtype)
+            ok = ok & ~bad
+        lr, b1, b2, eps, wd, gs = self._hyper
+        p = self.flat.data
+        if gs != 1.0:
+            g = g * gs
+        g = g.add(p, alpha=wd)
+        t = float(self.t.item()) + 1.0
+        m = self.m.lerp(g, 1 - b1)
+        v = (self.v * b2).addcmul_(g, g, value=1 - b2)
+        step_size = lr / (1 - b1 ** t)
+        bc2 = (1 - b2 ** t) ** 0.5
+        new_p = p.addcdiv(m, (v.sqrt() / bc2).add_(eps), value=-step_size)
+        self.m.copy_(torch.where(ok, m, self.m))
+        self.v.copy_(torch.where(ok, v, self.v))
+        p.copy_(torch.where(ok, new_p, p))
+        self.t += ok.to(self.t.dtype)
+        self.state[1] += (~ok).to(torch.int32)
+        return ok
+
+
+OPTIMIZERS = ('SGD', 'ADAM')
+DESC_LOSSES = ('circle', 'contrastive')
+
+
+def make_optimizer(flat, config):
+    """The optimizer the configuration asks for (reference config.py:63, training_3DMatch.py:62-76): 'SGD' or 'ADAM',
+    or the ``torch.optim.SGD`` / ``torch.optim.Adam`` instance the reference's script hands its Trainer (its
+    ``param_groups[0]`` supplies the hyper-parameters).  Anything else raises ValueError."""
+    opt = getattr(config, 'optimizer', 'SGD')
+    opt = 'SGD' if opt is None else opt
+    if isinstance(opt, torch.optim.Adam):
+        g = opt.param_groups[0]
+        if g.get('amsgrad', False) or g.get('maximize', False) or g.get('decoupled_weight_decay', False):
+            raise ValueError("optimizer: Adam with amsgrad, maximize or decoupled weight decay is not supported")
+        return GuardedAdam(flat, lr=g['lr'], betas=tuple(g['betas']), eps=g['eps'], weight_decay=g['weight_decay'])
+    if isinstance(opt, torch.optim.SGD):
+        g = opt.param_groups[0]
+        if g.get('dampening', 0) != 0 or g.get('nesterov', False) or g.get('maximize', False):
+            raise ValueError("optimizer: SGD with dampening, nesterov or maximize is not supported")
+        return GuardedSGD(flat, lr=g['lr'], momentum=g['momentum'], weight_decay=g['weight_decay'])
+    if isinstance(opt, str) and opt == 'SGD':
+        return GuardedSGD(flat, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay)
+    if isinstance(opt, str) and opt == 'ADAM':
+        return GuardedAdam(flat, lr=config.lr, betas=(0.9, 0.999), weight_decay=config.weight_decay)
+    raise ValueError("optimizer must be one of %s or a torch.optim.SGD / Adam instance, got %r" % (OPTIMIZERS, opt))
+
+
+def desc_loss_of(config):
+    """'circle' or 'contrastive' (reference config.py:51); ValueError for anything else, and for a circle loss on a
+    metric other than 'euclidean' (the fused kernels compute that one; the reference's contrastive branch always uses
+    'euclidean', training_3DMatch.py:119-125)."""
+    kind = getattr(config, 'desc_loss', 'circle')
+    kind = 'circle' if kind is None else kind
+    if kind not in DESC_LOSSES:
+        raise ValueError("desc_loss must be one of %s, got %r" % (DESC_LOSSES, kind))
+    metric = getattr(config, 'dist_type', 'euclidean')
+    if kind == 'circle' and (metric or 'euclidean') != 'euclidean':
+        raise ValueError("desc_loss 'circle' trains with dist_type 'euclidean' only, got %r" % (metric,))
+    return kind
 
 
 KEEP_GRAPH_TEMPLATES = True
@@ -366,7 +567,8 @@ class TrainStep:
 
     def _init_training_state(self, config, world_size):
         self.flat = FlatParams(self.model)
-        self.opt = GuardedSGD(self.flat, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay)
+        self.desc_loss = desc_loss_of(config)
+        self.opt = make_optimizer(self.flat, config)
         self.opt.grad_scale = 1.0 / max(1, world_size)
         self.circle = CircleLoss(dist_type='euclidean', log_scale=config.log_scale, safe_radius=config.safe_radius,
                                  pos_margin=config.pos_margin, neg_margin=config.neg_margin)
@@ -439,6 +641,8 @@ class TrainStep:
         """Reference trainer.py:91-98 on the un-normalised descriptors: the 2M sampled rows are gathered and
         normalised by one launch (the other rows never enter the loss)."""
         c = self.circle
+        if getattr(self, 'desc_loss', 'circle') == 'contrastive':
+            return self._contrastive_from_raw(x, scores, batch)
         if batch.get('_pairs', 1) > 1:     # stacked pairs: every pair's own M x M problem, total = their sum
             total, desc, det, acc, fp, an = ops.train_loss_pairs(
                 x, scores, batch['corr'], batch['stack_lengths'][0], None, c.log_scale, c.safe_radius, c.pos_margin,
@@ -452,6 +656,24 @@ class TrainStep:
                                                       neg_mask=batch.get('neg_mask'))
         # per-row furthest-positive / average-negative distances [M] (trainer.py:99-100 averages them on the host);
         # kept on the device for whoever wants the statistics -- no extra launches in the step itself
+        self.last_distances = (fp, an)
+        return loss, desc, det, acc
+
+    def _contrastive_from_raw(self, x, scores, batch):
+        """_loss_from_raw for desc_loss 'contrastive' (training_3DMatch.py:119-125): the same select + normalise
+        launches, then the contrastive + detector kernels on the f64 keypoint distances (not the circle's mask)."""
+        c = self.circle
+        if batch.get('_pairs', 1) > 1:
+            total, desc, det, acc, fp, an = ops.train_contrastive_loss_pairs(
+                x, scores, batch['corr'], batch['stack_lengths'][0], batch['dist_keypts'], c.safe_radius, c.pos_margin,
+                c.neg_margin, self.w_desc, self.w_det)
+            self.last_distances = (fp, an)
+            self.last_pair_losses = (desc, det, acc)
+            return total, desc, det, acc
+        n0 = batch['n0'] if 'n0' in batch else batch['stack_lengths'][0][:1]
+        loss, desc, det, acc, fp, an = ops.train_contrastive_loss(x, scores, batch['corr'], n0, batch['dist_keypts'],
+                                                                  c.safe_radius, c.pos_margin, c.neg_margin,
+                                                                  self.w_desc, self.w_det)
         self.last_distances = (fp, an)
         return loss, desc, det, acc
 

@@ -282,7 +282,7 @@ class Trainer(object):
         eng = self.engine
         ds = self.train_loader.dataset
         self._engines = []
-        keep = (eng.flat.data.clone(), eng.opt.buf.clone(), eng.opt.state.clone())
+        keep = tuple(t.clone() for t in (eng.flat.data,) + tuple(eng.opt.device_state()))
         for caps, member in self._capacity_classes(ds, classes=int(_get(self.config, 'capacity_classes', 3))):
             caps = [self.stack * int(c) for c in caps]     # a stack holds `stack` pairs of the class
             if self.lanes > 1:        # several graphs in flight: the lanes of every class share streams and the join
@@ -301,7 +301,7 @@ class Trainer(object):
             if self.lanes > 1 and not self._engines:
                 self.lanes_overlap = e.probe_overlap()       # do the lanes' streams really run side by side?
             self._engines.append(e)
-        for dst, src in zip((eng.flat.data, eng.opt.buf, eng.opt.state), keep):
+        for dst, src in zip((eng.flat.data,) + tuple(eng.opt.device_state()), keep):
             dst.copy_(src)
         self._captured = True
 

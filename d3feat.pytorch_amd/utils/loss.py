@@ -141,7 +141,8 @@ class DetLoss(nn.Module):
 
 
 class ContrastiveLoss(nn.Module):
-    """Batch-hard contrastive loss (reference loss.py:47-97); not the default (config.py:51) -- plain PyTorch."""
+    """Batch-hard contrastive loss (reference loss.py:47-97); not the default (config.py:51) -- plain PyTorch, the
+    oracle of the fused kernels the training step runs for desc_loss 'contrastive' (ops.contrastive_det_loss)."""
 
     def __init__(self, pos_margin=0.1, neg_margin=1.4, metric='euclidean', safe_radius=0.25):
         super(ContrastiveLoss, self).__init__()
@@ -157,7 +158,8 @@ class ContrastiveLoss(nn.Module):
         closest_negative = torch.min(dists + 1e5 * eye, dim=1)[0]
         diff = furthest_positive - closest_negative
         accuracy = (diff < 0).sum() * 100.0 / diff.shape[0]
-        loss = torch.clamp(furthest_positive - self.pos_margin, min=0) + torch.clamp(self.neg_margin - closest_negative,
-                                                                                    min=0)
+        # torch.max(x, 0) as in the reference (loss.py:93): half the gradient where x == 0 exactly, unlike clamp
+        zeros = torch.zeros_like(diff)
+        loss = torch.max(furthest_positive - self.pos_margin, zeros) + torch.max(self.neg_margin - closest_negative, zeros)
         average_negative = (torch.sum(dists, dim=-1) - furthest_positive) / (M - 1)
         return torch.mean(loss), accuracy, LazyList(furthest_positive), LazyList(average_negative), 0, dists

@@ -574,6 +574,39 @@ int d3f_circle_det_loss_backward_pairs(const float* anchor, const float* positiv
                                        const float* grad_total, float* grad_anchor, float* grad_positive,
                                        float* grad_anc_score, float* grad_pos_score, void* stream);
 
+/* Batch-hard contrastive loss + detector loss -- replaces utils/loss.py: ContrastiveLoss.forward(:54-62) with
+ * metric 'euclidean' (what training_3DMatch.py:119-125 builds for desc_loss 'contrastive'), calculate_loss(:65-97) and
+ * DetLoss.forward(:149-158) on its dists.  Two launches forward (one wave per row, then the scalars), one backward.
+ *   dists = D + 10*near,  near_ij = (dist_keypts_ij + (i == j ? 10 : 0)) < safe_radius  (f64, like the reference's
+ *   NumPy); furthest_positive = dists_ii, closest negative cn_i = min_{j != i} dists_ij (lowest j on ties);
+ *   desc = mean_i [max(fp_i - pos_margin, 0) + max(neg_margin - cn_i, 0)], det = mean_i (fp_i - cn_i)(sa_i + sp_i).
+ * anchor/positive [M,C] (C <= 256), dist_keypts [M,M] float64, scores [M]; M in 2..1024.  Outputs and out_scalars as
+ * d3f_circle_det_loss_forward; stats [d3f_circle_det_loss_stats_floats(M)] hold what the backward reads.
+ * backward: gradients of grad_desc*desc + grad_det*det (device scalars; either may be NULL = 0) wrt anchor, positive
+ * and (optional) the scores, as torch autograd forms them: half the gradient where a hinge is exactly 0. */
+int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C,
+                                     const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                     double safe_radius, float pos_margin, float neg_margin, float* dists,
+                                     float* furthest_positive, float* average_negative, float* out_scalars,
+                                     float* stats, void* stream);
+int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, const float* anc_score,
+                                      const float* pos_score, float pos_margin, float neg_margin, const float* stats,
+                                      const float* grad_desc, const float* grad_det, float* grad_anchor,
+                                      float* grad_positive, float* grad_anc_score, float* grad_pos_score,
+                                      void* stream);
+/* stacked pairs, laid out as d3f_circle_det_loss_forward_pairs (dist_keypts [pairs,M,M] float64); pairs <= 32. */
+int d3f_contrastive_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
+                                           const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                           double safe_radius, float pos_margin, float neg_margin, float w_desc,
+                                           float w_det, float* dists, float* furthest_positive,
+                                           float* average_negative, float* out_scalars, float* out_total, float* stats,
+                                           void* stream);
+int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
+                                            const float* anc_score, const float* pos_score, float pos_margin,
+                                            float neg_margin, float w_desc, float w_det, const float* stats,
+                                            const float* grad_total, float* grad_anchor, float* grad_positive,
+                                            float* grad_anc_score, float* grad_pos_score, void* stream);
+
 /* Sampled-correspondence front end of the loss -- replaces F.normalize over all N descriptors
  * (models/architectures.py:318) + the four index selections of trainer.py:91-94 and their backward:
  *   out[m,:] = x[idx[m],:] / max(||x[idx[m],:]||, 1e-12),  s[m] = scores[idx[m]].
@@ -708,6 +741,19 @@ int d3f_sgd_guarded_step(const float* grad, float* params, float* momentum_buf, 
 int d3f_sgd_guarded_step_lanes(const float* const* grads, int n_grads, float* params, float* momentum_buf, size_t n,
                                float lr, float momentum, float weight_decay, const float* hyper_device, int32_t* state,
                                const int32_t* pair_status, void* stream);
+/* Guarded Adam -- replaces torch.optim.Adam(lr, betas=(0.9, 0.999), weight_decay) as training_3DMatch.py:69-75
+ * configures it for optimizer 'ADAM' (amsgrad off, L2 weight decay), with the same guard, state and pair_status as
+ * the SGD step, on the SUM of n_grads (1..4) gradient buffers (`grads`: a host array of device pointers):
+ *   g = sum * grad_scale + weight_decay*params;  exp_avg += (1-beta1)(g - exp_avg);
+ *   exp_avg_sq = beta2*exp_avg_sq + (1-beta2) g*g;  t = step + 1;
+ *   params -= lr/(1-beta1^t) * exp_avg / (sqrt(exp_avg_sq)/sqrt(1-beta2^t) + eps)
+ * step: device float[1] = applied steps so far (torch's per-parameter `step`), advanced after the update; a skipped
+ * step modifies none of params, moments, step and increments state[1].  hyper_device: double[6] on the device =
+ * {lr, beta1, beta2, eps, weight_decay, grad_scale}, read when the kernels execute (a captured graph follows the
+ * schedule).  Three launches: guard, update, a one-thread counter launch. */
+int d3f_adam_guarded_step(const float* const* grads, int n_grads, float* params, float* exp_avg, float* exp_avg_sq,
+                          float* step, size_t n, const double* hyper_device, int32_t* state, const int32_t* pair_status,
+                          void* stream);
 /* data-parallel form of the pair-status gate: poisons grad[0] with NaN before the exchange when the flag is set */
 int d3f_poison_gradient_if_status(float* grad, const int32_t* pair_status, int32_t* state, void* stream);
 
