@@ -132,6 +132,37 @@ struct PhaseClock {
 };
 unsigned long long* phase_clock_ptr();   // kpconv_fused.hip
 
+// x of lane (l ^ j) for the butterfly distances of a 64-lane wave WITHOUT the LDS crossbar: __shfl_xor compiles to
+// ds_bpermute_b32 (an LDS-pipe instruction with its address arithmetic and ~100 cycles of dependent latency) -- the
+// 64-key bitonic network of a query is 21 dependent exchanges of a 64-bit key = 42 of them.  Distances 1, 2, 8 are one
+// DPP move (quad_perm / row_ror), 4 is two (row_shl / row_shr under complementary bank masks), 16 and 32 are gfx950's
+// v_permlane16_swap / v_permlane32_swap (rows of the two operands exchanged; the lane's row bit picks the half).
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x, int j, int lane) {
+  switch (j) {
+    case 1: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
+    case 2: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
+    case 4: {
+      int r = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x104, 0xF, 0x5, false);                  // banks 0, 2 <- lane + 4
+      return (uint32_t)__builtin_amdgcn_update_dpp(r, (int)x, 0x114, 0xF, 0xA, false);              // banks 1, 3 <- lane - 4
+    }
+    case 8: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x128, 0xF, 0xF, false);   // row_ror:8
+    case 16: {
+      const auto p = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+      return (lane & 16) ? p[0] : p[1];
+    }
+    case 32: {
+      const auto p = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+      return (lane & 32) ? p[0] : p[1];
+    }
+    default: return __shfl_xor(x, j, 64);
+  }
+}
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t lo = lane_xor((uint32_t)v, m, lane), hi = lane_xor((uint32_t)(v >> 32), m, lane);
+  return ((uint64_t)hi << 32) | lo;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

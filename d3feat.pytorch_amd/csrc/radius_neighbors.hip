@@ -12,56 +12,15 @@
 // buckets, a wave prefix sum flattens their ranges so all 64 lanes test candidates, survivors are compacted
 // with ballot/popcount into LDS as (d2 bits << 32 | index) and ranked by a wave-wide bitonic network
 // (register shuffles for <= 64 candidates, LDS otherwise).
-#include "common.hpp"
+#include "cell_list.hpp"
 
 namespace {
 
-constexpr double kCellSlack = 1.0 + 1e-4;
+using namespace d3f::cells;   // cell_list.hpp: GridLayout, pack_key, bucket_of, cell_coord, grid_alloc_kernel
+using d3f::shfl_xor_u64;
+
 constexpr int kCand = 512;       // ranked candidates per query (overflow -> D3F_ST_CAND_OVERFLOW)
 constexpr int kQueryWaves = 4;   // queries per workgroup
-
-__host__ __device__ inline uint32_t table_size_for(int Ns) {
-  uint32_t m = 64;
-  while (m < 2u * (uint32_t)(Ns > 0 ? Ns : 1)) m <<= 1;
-  return m;
-}
-
-struct GridLayout {
-  uint32_t M;
-  int32_t* cnt;      // [M + 64]  per-bucket population; cnt[M] is the global range allocator
-  int32_t* start;    // [M]
-  int32_t* end;      // [M]       fill cursor during the scatter == range end afterwards
-  uint64_t* key_tmp; // [Ns]      cell key of support i (input order)
-  float4* pts;       // [Ns]      supports in bucket order: x, y, z, bit-cast global index
-  uint64_t* key;     // [Ns]      cell key per sorted support
-  size_t bytes;
-};
-
-GridLayout grid_layout(void* ws, int Ns) {
-  GridLayout g;
-  g.M = table_size_for(Ns);
-  d3f::Carver c(ws);
-  const size_t n = (size_t)(Ns > 0 ? Ns : 1);
-  g.cnt = c.take<int32_t>(g.M + 64);
-  g.start = c.take<int32_t>(g.M);
-  g.end = c.take<int32_t>(g.M);
-  g.key_tmp = c.take<uint64_t>(n);
-  g.pts = c.take<float4>(n);
-  g.key = c.take<uint64_t>(n);
-  g.bytes = d3f::align_up(c.off, 256);
-  return g;
-}
-
-__device__ __forceinline__ int cell_coord(float v, double inv_cell) { return (int)floor((double)v * inv_cell); }
-
-__device__ __forceinline__ uint64_t pack_key(int b, int cx, int cy, int cz) {
-  return ((uint64_t)(uint32_t)b << 48) | ((uint64_t)(uint32_t)(cx + 32768) << 32) |
-         ((uint64_t)(uint32_t)(cy + 32768) << 16) | (uint64_t)(uint32_t)(cz + 32768);
-}
-
-__device__ __forceinline__ uint32_t bucket_of(uint64_t key, uint32_t mask) {
-  return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
 
 __global__ void grid_count_kernel(const float* __restrict__ s, int Ns, const int32_t* __restrict__ s_len, int B,
                                   double inv_cell, uint32_t mask, int32_t* __restrict__ cnt,
@@ -77,36 +36,6 @@ __global__ void grid_count_kernel(const float* __restrict__ s, int Ns, const int
   const uint64_t key = pack_key(b, cx, cy, cz);
   key_tmp[i] = key;
   atomicAdd(&cnt[bucket_of(key, mask)], 1);
-}
-
-__global__ __launch_bounds__(1024) void grid_alloc_kernel(uint32_t M, int32_t* __restrict__ cnt,
-                                                          int32_t* __restrict__ start, int32_t* __restrict__ end) {
-  // ranges need to be disjoint, not ordered; the running total is ONE word, so a whole workgroup of 16 waves reserves
-  // its buckets together (wave scans, wave totals combined through LDS, one atomic) -- per-bucket atomics on that word
-  // serialise, per-wave ones still queued 2048 deep at level 0 (23 us)
-  __shared__ int wtot[16], wbase[16];
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = b < M ? cnt[b] : 0;
-  int incl = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int total = 0;
-    for (int w = 0; w < 16; ++w) { wbase[w] = total; total += wtot[w]; }
-    const int base = total > 0 ? atomicAdd(&cnt[M], total) : 0;
-    for (int w = 0; w < 16; ++w) wbase[w] += base;
-  }
-  __syncthreads();
-  if (b >= M) return;
-  const int s = c ? wbase[wave] + incl - c : 0;
-  start[b] = s;
-  end[b] = s;
 }
 
 __global__ void grid_scatter_kernel(const float* __restrict__ s, int Ns, const int32_t* __restrict__ s_len, int B,
@@ -128,37 +57,6 @@ struct WaveScratch {
   int pre[32];
   int st[32];
 };
-
-// x of lane (l ^ j) for the butterfly distances of a 64-lane wave WITHOUT the LDS crossbar: __shfl_xor compiles to
-// ds_bpermute_b32 (an LDS-pipe instruction with its address arithmetic and ~100 cycles of dependent latency) -- the
-// 64-key bitonic network of a query is 21 dependent exchanges of a 64-bit key = 42 of them.  Distances 1, 2, 8 are one
-// DPP move (quad_perm / row_ror), 4 is two (row_shl / row_shr under complementary bank masks), 16 and 32 are gfx950's
-// v_permlane16_swap / v_permlane32_swap (rows of the two operands exchanged; the lane's row bit picks the half).
-__device__ __forceinline__ uint32_t lane_xor(uint32_t x, int j, int lane) {
-  switch (j) {
-    case 1: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
-    case 2: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
-    case 4: {
-      int r = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x104, 0xF, 0x5, false);                  // banks 0, 2 <- lane + 4
-      return (uint32_t)__builtin_amdgcn_update_dpp(r, (int)x, 0x114, 0xF, 0xA, false);              // banks 1, 3 <- lane - 4
-    }
-    case 8: return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x128, 0xF, 0xF, false);   // row_ror:8
-    case 16: {
-      const auto p = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-      return (lane & 16) ? p[0] : p[1];
-    }
-    case 32: {
-      const auto p = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-      return (lane & 32) ? p[0] : p[1];
-    }
-    default: return __shfl_xor(x, j, 64);
-  }
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t lo = lane_xor((uint32_t)v, m, lane), hi = lane_xor((uint32_t)(v >> 32), m, lane);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     const float* __restrict__ q, int Nq, const int32_t* __restrict__ q_len, const int32_t* __restrict__ s_len, int B,

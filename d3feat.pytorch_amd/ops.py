@@ -2778,6 +2778,118 @@ def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, e
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# nearest neighbour over a list of cloud pairs (mining of the 3DMatch training pickles, datasets/preprocess.py)
+# ---------------------------------------------------------------------------------------------------------------
+MAX_CLOUDS = 65535   # the cell key keeps the cloud index in 16 bits
+
+
+def _cloud_start(s_len):
+    """int32 [B+1] device prefix of the cloud lengths."""
+    start = torch.zeros(int(s_len.numel()) + 1, dtype=torch.int32, device=s_len.device)
+    start[1:] = torch.cumsum(s_len, 0)
+    return start
+
+
+class CloudGrid:
+    """One cell list over MANY stacked clouds (up to ``MAX_CLOUDS``; ``RadiusGrid`` takes 64) for ``nearest_pairs``:
+    d3f_cloud_grid_build finds a point's cloud in a prefix of the lengths and keeps every cloud's buckets and points
+    contiguous, which the radius search's queries do not read -- hence a class of its own."""
+
+    def __init__(self, points, lens, radius, status=None):
+        self.supports = _f32(points, "points")
+        if self.supports.dim() != 2 or self.supports.shape[1] != 3:
+            raise RuntimeError("Wrong dimensions : points.shape is not (N, 3)")
+        dev = self.supports.device
+        self.s_len = _lens(lens, dev, "lens")
+        # lengths that came from the host stay known there: nearest_pairs then sizes its output without a read-back
+        self.lens_host = None if isinstance(lens, torch.Tensor) and lens.is_cuda else \
+            np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64).reshape(-1)
+        if self.lens_host is not None and (self.lens_host.min(initial=0) < 0 or
+                                           int(self.lens_host.sum()) > int(self.supports.shape[0])):
+            raise ValueError("lens must be non-negative and sum to at most the %d stacked points"
+                             % int(self.supports.shape[0]))
+        if not 1 <= int(self.s_len.numel()) <= MAX_CLOUDS:
+            raise ValueError("1..%d clouds per cell list, got %d" % (MAX_CLOUDS, int(self.s_len.numel())))
+        self.radius = float(radius)
+        self.status = status if status is not None else DeviceStatus(dev)
+        self.cloud_start = _cloud_start(self.s_len)
+        L = _native.lib()
+        self.Ns = int(self.supports.shape[0])
+        nbytes = L.d3f_radius_grid_ws_bytes(self.Ns)
+        self.ws = _ws(nbytes, dev)
+        with _region("cloud_grid_build[Ns=%d]" % self.Ns, 12 * self.Ns + 24 * self.Ns):
+            _native.check(L.d3f_cloud_grid_build(_p(self.supports), self.Ns, _p(self.cloud_start),
+                                                 int(self.s_len.numel()), self.radius, _p(self.ws), nbytes,
+                                                 _p(self.status.word), _stream()), "d3f_cloud_grid_build")
+
+
+def nearest_pairs_bytes(rows, found=None):
+    """Algorithmic bytes of ``rows`` queries: the source point (12), the (start, end) headers of 27 buckets (216), the
+    stored point and cell key of every candidate the accepted cells hold (24 each; ``found`` of them, by default one
+    per query, the least a matched row reads) and the index written (4)."""
+    rows = int(rows)
+    return rows * (12 + 27 * 8 + 4) + 24 * (rows if found is None else int(found))
+
+
+def nearest_pairs(grid_or_points, lens, pairs, transforms, radius, lanes=0):
+    """Nearest neighbour within ``radius`` for every point of the source cloud of every pair (d3f_nearest_pairs).
+
+    ``grid_or_points``: a ``RadiusGrid`` / ``CloudGrid`` over the stacked clouds (several chunks of pairs then share one
+    cell list; ``lens`` may be None), or the stacked points [N,3] themselves, each cloud in its own frame, with ``lens``
+    their lengths.  ``pairs`` int [P,2] = (source cloud, target cloud), ``transforms`` f64 [P,3,4] or [P,4,4] mapping
+    source points into the target's frame.  Returns ``(nn int32 [rows], count int32 [P], row_start int64 [P+1])``:
+    rows ``row_start[p] .. row_start[p+1]`` are the points of pair p's source in order, ``nn`` the index inside the target
+    cloud (-1: none within the radius), ``count[p]`` the rows of pair p with a neighbour.  Arithmetic and tie rule:
+    include/d3feat_hip.h.  ``lanes``: lanes per query (measurements; the result does not depend on it)."""
+    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
+        grid = grid_or_points
+        if float(radius) > grid.radius:
+            raise RuntimeError("search radius %g exceeds the cell list's %g" % (float(radius), grid.radius))
+    else:
+        if lens is None:
+            raise ValueError("lens is required with stacked points")
+        grid = CloudGrid(grid_or_points, lens, radius)
+    dev = grid.supports.device
+    B = int(grid.s_len.numel())
+    cloud_start = getattr(grid, "cloud_start", None)
+    if cloud_start is None:
+        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
+    host = None
+    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
+    else:
+        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if host.size and (host.min() < 0 or host.max() >= B):
+            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
+        pr = torch.as_tensor(host.astype(np.int32), device=dev)
+    P = int(pr.shape[0])
+    tf = torch.as_tensor(transforms, dtype=torch.float64).to(dev)
+    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4), (P, 12)):
+        raise ValueError("transforms must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (P, tuple(tf.shape)))
+    tf = tf.reshape(P, 16 if tuple(tf.shape[1:]) == (4, 4) else 12)[:, :12].contiguous()
+    lens_host = getattr(grid, "lens_host", None)
+    if host is not None and lens_host is not None:
+        rs = np.zeros(P + 1, dtype=np.int64)
+        rs[1:] = np.cumsum(lens_host[host[:, 0]])
+        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
+    else:
+        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        if P:
+            row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long()], 0)
+        rows = int(row_start[-1].item()) if P else 0   # sizes the output: the one read-back of this form
+    nn = torch.empty(rows, dtype=torch.int32, device=dev)
+    count = torch.zeros(P, dtype=torch.int32, device=dev)
+    if rows == 0:
+        return nn, count, row_start
+    with _region("nearest_pairs[P=%d,rows=%d]" % (P, rows), nearest_pairs_bytes(rows)):
+        _native.check(_native.lib().d3f_nearest_pairs_lanes(
+            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(radius), _p(pr), _p(tf),
+            _p(row_start), P, rows, _p(nn), _p(count), _p(grid.status.word), int(lanes), _stream()),
+            "d3f_nearest_pairs")
+    return nn, count, row_start
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

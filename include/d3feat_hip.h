@@ -702,6 +702,40 @@ int d3f_ransac_sample_host(uint64_t seed, int p, int h, int count, int32_t* out_
 int d3f_rigid_fit_host(const double* src_host, const double* tgt_host, int n, double* out_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nearest neighbour within a radius over a list of cloud pairs -- the mining step of the 3DMatch training pickles
+ * (datasets/preprocess.py; the reference ships the finished files and has no counterpart).
+ * `points` [Ns,3] f32 are B clouds stacked, each in its OWN frame; cloud_start [B+1] int32 ON THE DEVICE is the prefix
+ * of their lengths (cloud_start[0] = 0, cloud_start[B] live rows <= Ns).  d3f_cloud_grid_build makes ONE cell list over
+ * all of them (workspace: d3f_radius_grid_ws_bytes(Ns)) with the cloud index as the batch element of the cell key,
+ * B <= 65535.  It keeps the buckets and the stored points of every cloud contiguous (the searches against one target
+ * stay inside ~40 B per target point), so it serves d3f_nearest_pairs only; d3f_nearest_pairs also takes a list that
+ * d3f_radius_grid_build made over the same stack (B <= 64) -- the list records which of the two it is.
+ * d3f_nearest_pairs: pair p = (pairs[2p] source cloud, pairs[2p+1] target cloud; equal is legal) with transforms[12p..]
+ * a row-major 3x4 f64 matrix that maps source points into the target's frame.  Query row row_start[p] + i is point i of
+ * the source cloud; row_start [P+1] int64 on the device is the prefix of the source lengths.  `rows` is the capacity of
+ * out_nn (the launch is sized by it); rows beyond row_start[P] are left untouched.
+ *   q  = f32(((T0 x + T1 y) + T2 z) + T3) per component, evaluated in f64 without contraction;
+ *   d2 = ((dx dx) + (dy dy)) + (dz dz) in f32 without FMA, accepted when d2 < radius * radius (f32 product, strict);
+ *   out_nn[row] = index INSIDE the target cloud of the accepted point with the least d2, the lowest index among equal
+ *   d2, or -1; out_count[p] (caller-cleared) += rows of pair p that found one.
+ * radius <= grid_radius (the radius the list was built with).  A query whose cell falls outside the addressable grid
+ * sets D3F_ST_CELL_RANGE and yields -1; a pair that names a cloud outside [0, B), or a row beyond its source cloud,
+ * yields -1.  One launch on `stream`, no host synchronisation, no allocation; integer results, identical from run to
+ * run.  d3f_nearest_pairs_lanes is the same with the lanes that share one query chosen by the caller (4, 8, 16, 32;
+ * 0 = the default, 8) -- for measurements; the result does not depend on it.
+ * ---------------------------------------------------------------------------------------------- */
+int d3f_cloud_grid_build(const float* points, int Ns, const int32_t* cloud_start, int B, float radius, void* grid_ws,
+                         size_t grid_ws_bytes, int32_t* status, void* stream);
+int d3f_nearest_pairs(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                      float grid_radius, float radius, const int32_t* pairs, const double* transforms,
+                      const int64_t* row_start, int P, int64_t rows, int32_t* out_nn, int32_t* out_count,
+                      int32_t* status, void* stream);
+int d3f_nearest_pairs_lanes(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                            float grid_radius, float radius, const int32_t* pairs, const double* transforms,
+                            const int64_t* row_start, int P, int64_t rows, int32_t* out_nn, int32_t* out_count,
+                            int32_t* status, int lanes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
