@@ -87,6 +87,10 @@ def _f32(t, name):
     return t.contiguous()
 
 
+def _opt_f32(t, name):
+    return _f32(t, name) if t is not None else None
+
+
 def _i32(t, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("%s must be a CUDA/HIP tensor (d3feat_pytorch_amd has no CPU path)" % name)
@@ -501,6 +505,35 @@ def _grad_slot(param):
     return getattr(param, "_d3f_grad_slot", None)
 
 
+def _grad_target(slot, param):
+    """The tensor a weight gradient is written to: the reserved slot, else a fresh tensor shaped like ``param``."""
+    return slot if slot is not None else torch.empty_like(param)
+
+
+def _bias_grad_buffer(want1, want2, Cout, device):
+    """(gbuf, nb): one row [Cout] per bias that wants a gradient.  The node's forward launch clears the rows on the side
+    (no fill launch in backward), and two bias parameters get separate rows (autograd would clone a shared one)."""
+    nb = int(bool(want1)) + int(bool(want2))
+    return (torch.empty((nb, Cout), dtype=torch.float32, device=device) if nb else None), nb
+
+
+def _bias_grad_rows(ctx, want1, want2, Cout, device):
+    """(g1, g2, first, second, pre): the bias-gradient rows of ``ctx.gbuf`` for the biases that want one, ``first`` /
+    ``second`` = the same rows in the order the kernels fill them, ``pre`` = 1 when the forward cleared them."""
+    g1 = g2 = None
+    pre = 0
+    if want1 or want2:
+        gbuf, pre = ctx.gbuf, 1
+        ctx.gbuf = None
+        if gbuf is None:  # a second backward through the same node: fresh, not pre-cleared accumulators
+            gbuf, pre = _bias_grad_buffer(want1, want2, Cout, device)[0], 0
+        rows = list(gbuf.unbind(0))
+        g1 = rows.pop(0) if want1 else None
+        g2 = rows.pop(0) if want2 else None
+    first, second = (g1, g2) if g1 is not None else (g2, None)
+    return g1, g2, first, second, pre
+
+
 # False: the backward pass recomputes the neighbor aggregation instead of reading it back (saves K*Cin*4 B/query)
 SAVE_WEIGHTED_FEATURES = True
 # below this many rows a weight gradient is a plain GEMM for the library; above, the reduction-parallel kernel
@@ -519,7 +552,6 @@ _GEMM_DX_AGG_MIN_COUT = 64
 
 _DW_LIBRARY_MIN_OUT = 1920 * 128
 _DW_LIBRARY_MAX_ROWS = 16384
-_DW_LIBRARY = True
 
 
 def _takes_gemm_path(Nq, Cin):
@@ -529,10 +561,7 @@ def _takes_gemm_path(Nq, Cin):
 def _kpconv_gw(gon, weights, Nq, K, Cin, Cout):
     """gW [Nq, K Cin] = (g / nn) [Nq, Cout] @ W^T, W viewed [K Cin, Cout]: the per-query gradient of the weighted features
     the scatter-form grad-input kernel distributes (few-point layers)."""
-    w2 = weights.view(K * Cin, Cout)
-    if _own_gemm("kpconv_gw", gon, w2, GEMM_NT, Nq, Cout, K * Cin):
-        return gemm_epilogue(gon, w2, GEMM_NT, Nq, Cout, K * Cin)
-    return torch.mm(gon, w2.t())
+    return torch.mm(gon, weights.view(K * Cin, Cout).t())
 
 
 class _KPConvFn(torch.autograd.Function):
@@ -594,7 +623,7 @@ class _KPConvFn(torch.autograd.Function):
             pre = 1 if gx is not None else 0
             if gx is None:
                 gx = torch.empty_like(x)
-        gw = (ctx.gw_slot if ctx.gw_slot is not None else torch.empty_like(weights)) if need_w else None
+        gw = _grad_target(ctx.gw_slot, weights) if need_w else None
         go = grad_out.contiguous().float() if (need_x or need_w) else None
         gw_native, gx_native = gw, gx
         gon = None
@@ -621,15 +650,14 @@ class _KPConvFn(torch.autograd.Function):
             gx_native = None
         if big_dw:
             # x := g / nn [Nq, Cout], grad_out := wf [Nq, K Cin]: grad_W [K Cin, Cout] = wf^T (g / nn)
-            _grad_weight_atb(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), None, 0, None, None, "kpconv_dw_atb")
+            _weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), True, label="kpconv_dw_atb")
             gw_native = None
         if need_w and wf is not None and Nq < _SPLITK_MIN_ROWS and wf.shape[1] == K * Cin:
             # few points, wide layers (bottom of the U-Net): grad_W = wf^T (g/nn) is an ordinary GEMM with a short
             # reduction -- a library call; the reduction-parallel kernel is for the tall-skinny upper levels
             gon = go / nn.unsqueeze(1)
-            if not _queue_small_weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout)):
-                with _region("kpconv_dw_gemm[Nq=%d,Cin=%d,Cout=%d]" % (Nq, Cin, Cout), 4 * Nq * (K * Cin + Cout)):
-                    torch.mm(wf.t(), gon, out=gw.view(K * Cin, Cout))
+            _weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), False,
+                         gemm_label="kpconv_dw_gemm[Nq=%d,Cin=%d,Cout=%d]" % (Nq, Cin, Cout))
             gw_native = None
         if gx_native is not None and 0 < Nq < _GEMM_DX_MAX_ROWS and L.d3f_kpconv_grad_input_supported(Cin, K, H, Ns):
             # same layers: gW = (g/nn) W^T over all queries is one library GEMM; the kernel only scatters
@@ -653,7 +681,7 @@ class _KPConvFn(torch.autograd.Function):
                                                     _p(go), _p(wf), _p(keep), pre, _p(gx_native), _p(gw_native),
                                                     _p(ws), nbytes, _stream()),
                               "d3f_kpconv_backward")
-        return None, None, None, gx, None, (_adoptable(gw, ctx.gw_slot) if gw is not None else None), None, None, None
+        return None, None, None, gx, None, _adoptable(gw, ctx.gw_slot), None, None, None
 
 
 # The transposed-aggregation grad-input contracts with the permuted weights W'[k, o, c] = W[k, c, o].  One
@@ -661,8 +689,7 @@ class _KPConvFn(torch.autograd.Function):
 # such layer queues its weights, the first grad-input that needs a permuted matrix launches d3f_permute_kpconv_weights
 # for the whole queue.  The queue is process-wide, not per thread: a forward on the calling thread is followed by its
 # backward on autograd's device thread (or, for a lane, on the lane's capture thread); steps are recorded / run one at a
-# time, the lock only keeps the two dictionaries consistent.  False: one launch per layer.
-BATCH_WEIGHT_PERMUTES = True
+# time, the lock only keeps the two dictionaries consistent.  A shape the launch does not serve is permuted on its own.
 _WPERM = {'queue': {}, 'ready': {}}
 _WPERM_LOCK = threading.Lock()
 
@@ -689,7 +716,7 @@ def _permuted_weights(weights):
     with _WPERM_LOCK:
         wp = st['ready'].pop(key, None)
         jobs = []
-        if wp is None and BATCH_WEIGHT_PERMUTES and key in st['queue']:
+        if wp is None and key in st['queue']:
             jobs = [w for w in st['queue'].values()
                     if w.shape[1] % 32 == 0 and w.shape[2] % 32 == 0 and w.is_contiguous() and w.device == weights.device]
             st['queue'].clear()
@@ -753,8 +780,8 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
                           "d3f_kpconv_aggregate")
         ctx.keep, ctx.gx_buf = keep, gx_buf
         want_b = bias is not None and ctx.needs_input_grad[6]
-        gbuf = torch.empty((1, Cout), dtype=torch.float32, device=dev) if want_b else None
-        if _own_gemm("kpconv_fwd", wf, weights, GEMM_NN, Nq, K * Cin, Cout, 0, None, None, bias):
+        gbuf, _ = _bias_grad_buffer(want_b, False, Cout, dev)
+        if _own_gemm(wf, weights, Nq, K * Cin, Cout, bias):
             # contraction + / nn + bias + LeakyReLU in one launch (csrc/gemm_epilogue.hip)
             out = gemm_epilogue(wf, weights, GEMM_NN, Nq, K * Cin, Cout, row_div=nn, bias1=bias, slope=slope,
                                 zero_init=gbuf if want_b else None)
@@ -767,7 +794,7 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
         ctx.save_for_backward(q_pts, s_pts, idx, x, kernel_points, weights, nn, wf, out)
         ctx.gbuf, ctx.extent, ctx.slope, ctx.want_b = gbuf, float(extent), float(slope), want_b
         ctx.gw_slot = _grad_slot(weights)
-        if BATCH_WEIGHT_PERMUTES and ctx.needs_input_grad[3] and rev is not None and rev.rel is not None and \
+        if ctx.needs_input_grad[3] and rev is not None and rev.rel is not None and \
                 Cout >= _GEMM_DX_AGG_MIN_COUT and L.d3f_kpconv_aggregate_transposed_supported(Cout, K):
             _queue_weight_permute(weights)      # (its grad-input contracts with W': one launch for all such layers)
         return out
@@ -779,30 +806,21 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
         K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
         go = grad_out.contiguous()
-        gb, pre = None, 0
-        if ctx.want_b:
-            gb, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gb is None:
-                gb, pre = torch.empty((1, Cout), dtype=torch.float32, device=go.device), 0
+        gb, _, _, _, pre = _bias_grad_rows(ctx, ctx.want_b, False, Cout, go.device)
         gon = torch.empty_like(go)  # masked gradient / nn
         # many rows: the reduction over the points is what has to be spread over the chip (csrc/linear.hip); a large
         # output over a few thousand rows (1920 x 128 and up) is an ordinary GEMM again: 36 against 58 us at 6159 rows
-        # (profiles/r04_dw_library_vs_atb.txt; D3F_DW_LIBRARY=0: never, round 5's kernel re-measures it)
+        # (profiles/r04_dw_library_vs_atb.txt)
         atb = (ctx.needs_input_grad[5] and Nq >= _SPLITK_MIN_ROWS
                and bool(L.d3f_linear_grad_weight_supported(Nq, Cout, K * Cin))
-               and not (_DW_LIBRARY and K * Cin * Cout >= _DW_LIBRARY_MIN_OUT and Nq <= _DW_LIBRARY_MAX_ROWS))
-        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, Nq, Cout, gon, gb, None, pre, nn,
-                                                    _FOLD_BIAS_SUM and atb)
+               and not (K * Cin * Cout >= _DW_LIBRARY_MIN_OUT and Nq <= _DW_LIBRARY_MAX_ROWS))
+        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, Nq, Cout, gon, gb, None, pre, nn, atb)
         gx = gw = None
         if ctx.needs_input_grad[5]:
-            gw = ctx.gw_slot if ctx.gw_slot is not None else torch.empty_like(weights)
-            if atb:
-                # x := g / nn [Nq, Cout], grad_out := wf [Nq, K Cin]: grad_W [K Cin, Cout] = wf^T (g / nn)
-                _grad_weight_atb(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), bias_part, bias_blocks, gb, None,
-                                 "kpconv_dw_atb")
-            elif not _queue_small_weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout)):
-                torch.mm(wf.t(), gon, out=gw.view(K * Cin, Cout))
+            gw = _grad_target(ctx.gw_slot, weights)
+            # x := g / nn [Nq, Cout], grad_out := wf [Nq, K Cin]: grad_W [K Cin, Cout] = wf^T (g / nn)
+            _weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), atb, bias_part, bias_blocks, gb, None,
+                         label="kpconv_dw_atb")
         rev = ctx.rev
         if ctx.needs_input_grad[3] and rev is not None and rev.rel is not None and Cout >= _GEMM_DX_AGG_MIN_COUT \
                 and L.d3f_kpconv_aggregate_transposed_supported(Cout, K):
@@ -813,11 +831,7 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
                 _native.check(L.d3f_kpconv_aggregate_transposed(_p(rev.rel), rev.width, Ns, Nq, _p(kernel_points), K,
                                                                 ctx.extent, None, _p(gon), Cout, _p(agg), _stream()),
                               "d3f_kpconv_aggregate_transposed")
-            if _own_gemm("kpconv_dx", agg, weights, GEMM_NT, Ns, K * Cout, Cin, Cout):
-                # W' read in place from W [K, Cin, Cout] (block form of the reduction): no permuted copy of the weights
-                gx = gemm_epilogue(agg, weights, GEMM_NT, Ns, K * Cout, Cin, kblock=Cout)
-            else:
-                gx = torch.mm(agg, _permuted_weights(weights))
+            gx = torch.mm(agg, _permuted_weights(weights))
         elif ctx.needs_input_grad[3] and rev is not None:
             # gather form: one launch instead of the gW GEMM + atomic scatter (gon is already / nn)
             gx = torch.empty_like(x)
@@ -842,8 +856,7 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
                 _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
                                                       _p(kernel_points), K, ctx.extent, _p(gwf), _p(ctx.keep), pre,
                                                       _p(gx), _p(ws), nbytes, _stream()), "d3f_kpconv_grad_input")
-        return (None, None, None, gx, None, (_adoptable(gw, ctx.gw_slot) if gw is not None else None),
-                (gb.view(-1) if gb is not None else None), None, None, None, None)
+        return None, None, None, gx, None, _adoptable(gw, ctx.gw_slot), gb, None, None, None, None
 
 
 def _ready_supports(x, s_pts):
@@ -869,7 +882,7 @@ def kpconv_bias_act(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent
         if x.shape[0] != s_pts.shape[0] or x.shape[1] != w.shape[1] or idx.shape[0] != q_pts.shape[0]:
             raise RuntimeError("KPConv: inconsistent shapes q%s s%s idx%s x%s W%s" % (
                 tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape)))
-        b = _f32(bias, "bias") if bias is not None else None
+        b = _opt_f32(bias, "bias")
         rev = reverse_table_of(neighb_inds, Nq, H, int(s_pts.shape[0]), rev) if x.requires_grad else None
         return _KPConvGemmBiasActFn.apply(q_pts, s_pts, idx, x, kp, w, b, float(extent), float(slope), rev,
                                           _ready_supports(x, s_pts))
@@ -1070,11 +1083,6 @@ def grad_tap(x, holder):
 def _add_deposited(holder, go, weight):
     """grad_x = go @ weight (+ the sibling branch's deposited gradient, accumulated by the GEMM itself)."""
     c = holder.collect() if holder is not None else None
-    N, Cout, Cin = int(go.shape[0]), int(go.shape[1]), int(weight.shape[1])
-    if go.is_contiguous() and weight.is_contiguous() and \
-            (c is None or (c.is_contiguous() and c.dtype == go.dtype and c.shape == (N, Cin))) and \
-            _own_gemm("unary_dx", go, weight, GEMM_NN, N, Cout, Cin, 0, None, None, c):
-        return gemm_epilogue(go, weight, GEMM_NN, N, Cout, Cin, add=c)      # (out of place: safe beside queued operands)
     if c is None:
         return torch.mm(go, weight)
     if c.is_contiguous() and c.dtype == go.dtype and c.shape == (go.shape[0], weight.shape[1]):
@@ -1101,8 +1109,6 @@ def _add_deposited(holder, go, weight):
 # (:481-541) with bias + residual + LeakyReLU, and their grad-input products
 # ---------------------------------------------------------------------------------------------------------------
 GEMM_NT, GEMM_NN = 0, 1
-# False: every such product is a library GEMM followed by its epilogue launch (rounds 1-5; A/B measurements)
-OWN_GEMM = True
 
 
 def _al16(*ts):
@@ -1111,7 +1117,7 @@ def _al16(*ts):
 
 def gemm_epilogue_ok(x, w, mode, R, K, N, kblock=0, ldx=None, ldw=None, *others):
     """True when d3f_gemm_epilogue serves this product (shape, alignment, leading dimensions)."""
-    if not OWN_GEMM or R < 1:
+    if R < 1:
         return False
     ldx = K if ldx is None else ldx
     ldw = (K if mode == GEMM_NT else N) if ldw is None else ldw
@@ -1143,31 +1149,22 @@ def gemm_epilogue(x, w, mode, R, K, N, kblock=0, ldx=None, ldw=None, row_div=Non
     return out
 
 
-# which products go to the own kernel (the others stay library GEMMs).  Measured per shape against the library GEMM + its
-# epilogue launch (profiles/gemm_epilogue_bench.py -> profiles/r06_gemm_epilogue_bench.txt) and per kind inside the 4 x 3
-# step (profiles/calls/r06_gemm_kinds_ab.sh): the own kernel wins where the library's pick is poor or the fused epilogue
-# is a large share -- KPConv contractions of the bottom levels (<= 1024 rows x 3840 / 7680: split reduction) and of the
+# Which products go to the own kernel: KPConv's forward contraction only (every other product is a library GEMM).
+# Measured per shape against the library GEMM + its epilogue launch (profiles/gemm_epilogue_bench.py ->
+# profiles/r06_gemm_epilogue_bench.txt) and per kind of product inside the 4 x 3 step
+# (profiles/calls/r06_gemm_kinds_ab.sh): the own kernel wins where the library's pick is poor or the fused epilogue is
+# a large share -- KPConv contractions of the bottom levels (<= 1024 rows x 3840 / 7680: split reduction) and of the
 # many-row levels -- and loses on the mid-size square-ish products of levels 2-3 and the decoder, where the library's
-# shared-panel tiles reach 0.65-0.75 of the matrix rate.  Inside the step only the KPConv kind pays (+1.0 %); the unary
-# kinds ("unary_fwd", "unary_dx": >= 16k rows by rule), "kpconv_dx", "kpconv_gw" and "decoder" measured 0 ... -1.4 %
-# and stay library GEMMs (the kernel serves them all: tests/test_gpu_ops.py::test_gemm_epilogue_matches_float64).
-OWN_GEMM_KINDS = {"kpconv_fwd"}
-OWN_GEMM_RULES = True     # False: every product of an enabled kind (A/B measurements)
-OWN_GEMM_TALL_ROWS = 1 << 30
-
-
-def _own_gemm(kind, x, w, mode, R, K, N, kblock=0, ldx=None, ldw=None, *others):
-    """Policy + capability: True when the product `kind` of this shape runs on d3f_gemm_epilogue."""
-    if kind not in OWN_GEMM_KINDS:
-        return False
-    if OWN_GEMM_RULES:
-        if kind == "kpconv_fwd" and not (R <= 1024 or 4096 <= R < 16384 or R >= OWN_GEMM_TALL_ROWS):
-            return False       # (levels 1 and 3 of a 3-pair stack: 43 vs 33 + 5 us and 45 vs 38 + 5 us inside the step)
-        if kind in ("unary_fwd", "unary_dx") and R < 16384:
-            return False
-        if kind == "kpconv_dx" and R > 1024:
-            return False
-    return gemm_epilogue_ok(x, w, mode, R, K, N, kblock, ldx, ldw, *others)
+# shared-panel tiles reach 0.65-0.75 of the matrix rate.  Inside the step only the KPConv forward pays (+1.0 %); the
+# unary blocks' forward and grad-input (from 16k rows), KPConv's grad-input products (transposed-aggregation GEMM up to
+# 1024 rows, gW = (g/nn) W^T) and the decoder's four products measured 0 ... -1.4 % (profiles/r06_ab_log.txt) and are
+# library GEMMs at their call sites.  The kernel serves them all (GEMM_NT / GEMM_NN, the ``kblock`` form, leading
+# dimensions: tests/test_gpu_ops.py::test_gemm_epilogue_matches_float64), so taking one up again is a call-site edit.
+def _own_gemm(x, w, R, K, N, *others):
+    """Policy + capability: True when KPConv's forward contraction wf [R, K] @ W [K, N] runs on d3f_gemm_epilogue."""
+    if not (R <= 1024 or 4096 <= R < 16384):
+        return False       # (levels 1 and 3 of a 3-pair stack: 43 vs 33 + 5 us and 45 vs 38 + 5 us inside the step)
+    return gemm_epilogue_ok(x, w, GEMM_NN, R, K, N, 0, None, None, *others)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1191,17 +1188,11 @@ class _LinearFn(torch.autograd.Function):
             gx = None
         gw = None
         if ctx.needs_input_grad[1]:
-            L = _native.lib()
             N, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
-            slot = ctx.gw_slot
-            if N >= _SPLITK_MIN_ROWS and L.d3f_linear_grad_weight_supported(N, Cin, Cout):
-                gw = slot if slot is not None else torch.empty_like(weight)
-                _grad_weight_atb(x, go, N, Cin, Cout, gw, None, 0, None, None, "linear_dw")
-            else:
-                gw = slot if slot is not None else torch.empty_like(weight)
-                if not _queue_small_weight_grad(x, go, N, Cin, Cout, gw):
-                    torch.mm(go.t(), x, out=gw)
-        return gx, (_adoptable(gw, ctx.gw_slot) if gw is not None else None), None, None
+            atb = N >= _SPLITK_MIN_ROWS and bool(_native.lib().d3f_linear_grad_weight_supported(N, Cin, Cout))
+            gw = _grad_target(ctx.gw_slot, weight)
+            _weight_grad(x, go, N, Cin, Cout, gw, atb)
+        return gx, _adoptable(gw, ctx.gw_slot), None, None
 
 
 class _LinearBiasActFn(torch.autograd.Function):
@@ -1215,8 +1206,8 @@ class _LinearBiasActFn(torch.autograd.Function):
         ctx.holder, ctx.dep = holder, deposit
         N, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
         out = torch.empty((N, Cout), dtype=torch.float32, device=x.device)
-        nb = int(b1 is not None and ctx.needs_input_grad[2]) + int(b2 is not None and ctx.needs_input_grad[4])
-        gbuf = torch.empty((nb, Cout), dtype=torch.float32, device=x.device) if nb else None
+        gbuf, nb = _bias_grad_buffer(b1 is not None and ctx.needs_input_grad[2],
+                                     b2 is not None and ctx.needs_input_grad[4], Cout, x.device)
         with _region("linear_fused_fwd[N=%d,Cin=%d,Cout=%d]" % (N, Cin, Cout), 4 * N * (Cin + Cout) + 4 * Cin * Cout):
             _native.check(L.d3f_linear_bias_act_forward(_p(x), _p(weight), N, Cin, Cout, _p(b1), _p(add), _p(b2),
                                                         float(slope), _p(out), _p(gbuf), nb * Cout, _stream()),
@@ -1236,17 +1227,7 @@ class _LinearBiasActFn(torch.autograd.Function):
         go = grad_out.contiguous()
         want1 = ctx.has[0] and ctx.needs_input_grad[2]
         want2 = ctx.has[2] and ctx.needs_input_grad[4]
-        g1 = g2 = None
-        pre = 0
-        if want1 or want2:
-            gbuf, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gbuf is None:
-                gbuf, pre = torch.empty((int(want1) + int(want2), Cout), dtype=torch.float32, device=go.device), 0
-            rows = list(gbuf.unbind(0))
-            g1 = rows.pop(0) if want1 else None
-            g2 = rows.pop(0) if want2 else None
-        first, second = (g1, g2) if g1 is not None else (g2, None)
+        g1, g2, first, second, pre = _bias_grad_rows(ctx, want1, want2, Cout, go.device)
         atb = ctx.needs_input_grad[1] and bool(L.d3f_linear_grad_weight_supported(N, Cin, Cout))
         bias_part, bias_blocks = None, 0
         if ctx.slope == 1.0 and not (want1 or want2):
@@ -1254,7 +1235,7 @@ class _LinearBiasActFn(torch.autograd.Function):
         else:
             gm = go if ctx.slope == 1.0 else torch.empty_like(go)
             bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, gm if ctx.slope != 1.0 else None,
-                                                        first, second, pre, None, _FOLD_BIAS_SUM and atb)
+                                                        first, second, pre, None, atb)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
@@ -1267,20 +1248,10 @@ class _LinearBiasActFn(torch.autograd.Function):
             if ctx.dep is not None and ctx.dep.deposit(gx):
                 gx = None
         if ctx.needs_input_grad[1]:
-            slot = ctx.gw_slot
-            if atb:
-                gw = slot if slot is not None else torch.empty_like(weight)
-                _grad_weight_atb(x, gm, N, Cin, Cout, gw, bias_part, bias_blocks, first, second, "linear_dw")
-                bias_part = None
-            else:
-                gw = slot if slot is not None else torch.empty_like(weight)
-                if not _queue_small_weight_grad(x, gm, N, Cin, Cout, gw):
-                    torch.mm(gm.t(), x, out=gw)
-        if bias_part is not None:      # (not reached: the fold implies the A^T B path)
-            _native.check(L.d3f_bias_sum(_p(bias_part), bias_blocks, Cout, _p(first), _p(second), _stream()),
-                          "d3f_bias_sum")
-        return (gx, (_adoptable(gw, ctx.gw_slot) if gw is not None else None), g1,
-                gm if ctx.has[1] and ctx.needs_input_grad[3] else None, g2, None, None, None)
+            gw = _grad_target(ctx.gw_slot, weight)
+            _weight_grad(x, gm, N, Cin, Cout, gw, atb, bias_part, bias_blocks, first, second)
+        return (gx, _adoptable(gw, ctx.gw_slot), g1, gm if ctx.has[1] and ctx.needs_input_grad[3] else None, g2,
+                None, None, None)
 
 
 class _LinearPairBiasActFn(torch.autograd.Function):
@@ -1296,8 +1267,8 @@ class _LinearPairBiasActFn(torch.autograd.Function):
         N, C1, C2, Cout = int(x1.shape[0]), int(x1.shape[1]), int(x2.shape[1]), int(w1.shape[0])
         out = torch.empty((N, Cout), dtype=torch.float32, device=x1.device)
         ctx.want = tuple(b is not None and ctx.needs_input_grad[i] for b, i in ((b1a, 2), (b1b, 3), (b2a, 6), (b2b, 7)))
-        nb = 2 if any(ctx.want) else 0
-        gbuf = torch.empty((nb, Cout), dtype=torch.float32, device=x1.device) if nb else None
+        # (two rows whenever any of the four biases wants a gradient: the epilogue pass fills both)
+        gbuf, nb = _bias_grad_buffer(any(ctx.want), any(ctx.want), Cout, x1.device)
         with _region("linear_pair_fwd[N=%d,Cin=%d|%d,Cout=%d]" % (N, C1, C2, Cout),
                      4 * N * (C1 + C2 + Cout) + 4 * (C1 + C2) * Cout):
             _native.check(L.d3f_linear_pair_bias_act_forward(_p(x1), _p(w1), C1, _p(x2), _p(w2), C2, N, Cout, _p(b1a),
@@ -1314,18 +1285,12 @@ class _LinearPairBiasActFn(torch.autograd.Function):
         L = _native.lib()
         N, C1, C2, Cout = int(x1.shape[0]), int(x1.shape[1]), int(x2.shape[1]), int(w1.shape[0])
         go = grad_out.contiguous()
-        first = second = None
-        pre = 0
-        if any(ctx.want):
-            gbuf, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gbuf is None:
-                gbuf, pre = torch.empty((2, Cout), dtype=torch.float32, device=go.device), 0
-            first, second = gbuf.unbind(0)
+        first, second, _, _, pre = _bias_grad_rows(ctx, any(ctx.want), any(ctx.want), Cout, go.device)
+        # Both weight gradients run on the A^T B kernel: it serves every row count >= 1 with channel counts that are
+        # multiples of 16 (atb_supported, csrc/linear.hip), which the pairs the forward launch accepts all are
+        # (rowgemm_pair_supported: >= 4096 rows, 32 | 64 -> 128 or 16 | 32 -> 64 channels)
         need_w1, need_w2 = ctx.needs_input_grad[1], ctx.needs_input_grad[5]
-        atb1 = need_w1 and bool(L.d3f_linear_grad_weight_supported(N, C1, Cout))
-        atb2 = need_w2 and bool(L.d3f_linear_grad_weight_supported(N, C2, Cout))
-        fold = _FOLD_BIAS_SUM and atb1 and atb2 and _WG_GROUP is not None
+        fold = need_w1 and need_w2 and _WG_GROUP is not None
         gm = torch.empty_like(go) if ctx.slope != 1.0 else go
         bias_part, bias_blocks = None, 0
         if ctx.slope != 1.0 or first is not None:
@@ -1347,40 +1312,24 @@ class _LinearPairBiasActFn(torch.autograd.Function):
                 gx2 = None
         gw1 = gw2 = None
         if need_w1:
-            gw1 = ctx.slots[0] if ctx.slots[0] is not None else torch.empty_like(w1)
-            if atb1:
-                _grad_weight_atb(x1, gm, N, C1, Cout, gw1, bias_part, bias_blocks, first, second, "linear_dw")
-            else:
-                torch.mm(gm.t(), x1, out=gw1)
+            gw1 = _grad_target(ctx.slots[0], w1)
+            _weight_grad(x1, gm, N, C1, Cout, gw1, True, bias_part, bias_blocks, first, second)
         if need_w2:
-            gw2 = ctx.slots[1] if ctx.slots[1] is not None else torch.empty_like(w2)
-            if atb2:
-                # (the second problem finishes the same bias partials into the shortcut's two bias gradients)
-                _grad_weight_atb(x2, gm, N, C2, Cout, gw2, bias_part, bias_blocks, third, fourth, "linear_dw")
-            else:
-                torch.mm(gm.t(), x2, out=gw2)
+            gw2 = _grad_target(ctx.slots[1], w2)
+            # (the second problem finishes the same bias partials into the shortcut's two bias gradients)
+            _weight_grad(x2, gm, N, C2, Cout, gw2, True, bias_part, bias_blocks, third, fourth)
         if first is not None and bias_part is None:     # (no fold: the epilogue pass finished first / second itself)
-            third.copy_(first)
-            fourth.copy_(first)
-        elif first is not None and not (atb1 and atb2):  # (fold implies both problems are queued: not reached)
-            _native.check(L.d3f_bias_sum(_p(bias_part), bias_blocks, Cout, _p(first), _p(second), _stream()), "d3f_bias_sum")
             third.copy_(first)
             fourth.copy_(first)
         g = [first if ctx.want[0] else None, second if ctx.want[1] else None, third if ctx.want[2] else None,
              fourth if ctx.want[3] else None]
-        return (gx1, (_adoptable(gw1, ctx.slots[0]) if gw1 is not None else None), g[0], g[1],
-                gx2, (_adoptable(gw2, ctx.slots[1]) if gw2 is not None else None), g[2], g[3], None, None)
-
-
-# False: unary2 and the shortcut unary of a bottleneck stay two launches (A/B measurements)
-FUSE_UNARY_PAIR = True
+        return (gx1, _adoptable(gw1, ctx.slots[0]), g[0], g[1], gx2, _adoptable(gw2, ctx.slots[1]), g[2], g[3],
+                None, None)
 
 
 def linear_pair_supported(N, C1, C2, Cout, *tensors):
     """Whether linear_pair_bias_act serves a pair of these dimensions (the level-0 bottleneck's: (32 | 64) -> 128 from 4096
     rows); ``tensors``: operands already at hand, checked for device / dtype / layout."""
-    if not FUSE_UNARY_PAIR:
-        return False
     for t in tensors:
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
             return False
@@ -1394,7 +1343,7 @@ def linear_pair_bias_act(x1, w1, b1a, b1b, x2, w2, b2a, b2b, slope=0.1, grad_dep
     """act(x1 @ w1^T + b1a + b1b + x2 @ w2^T + b2a + b2b): unary2(x1) + unary_shortcut(x2) + LeakyReLU of a bottleneck
     block in one launch (reference blocks.py:658-686).  grad_deposit2: x2's gradient is handed to a sibling branch
     (GradHolder) instead of being returned."""
-    f = lambda t, n: _f32(t, n) if t is not None else None
+    f = _opt_f32
     if not linear_pair_supported(x1.shape[0], x1.shape[1], x2.shape[1], w1.shape[0], x1, x2, w1, w2):
         raise RuntimeError("linear_pair_bias_act: unsupported operands x1%s x2%s w1%s w2%s" % (
             tuple(x1.shape), tuple(x2.shape), tuple(w1.shape), tuple(w2.shape)))
@@ -1404,10 +1353,7 @@ def linear_pair_bias_act(x1, w1, b1a, b1b, x2, w2, b2a, b2b, slope=0.1, grad_dep
 
 # The bias gradient's second pass rides in the weight gradient's second-stage launch (csrc/linear.hip,
 # atb_reduce_bias_kernel) whenever both are two-pass forms: N >= 4096 rows for the epilogue's backward and the A^T B
-# kernel for grad_W.  False: two launches as before (experiments).
-_FOLD_BIAS_SUM = True
-
-
+# kernel for grad_W -- the nodes pass ``fold`` = "this node's weight gradient takes the A^T B path".
 def _epilogue_backward(go, out, slope, N, C, gm, first, second, pre, row_div, fold):
     """grad through act(. + biases): masked gradient into ``gm`` (None: not wanted) and the bias gradient(s).  With
     ``fold`` only the first pass runs; returns (partials, blocks) for d3f_linear_grad_weight_bias, else (None, 0)."""
@@ -1510,16 +1456,12 @@ def _queue_small_weight_grad(x, gm, N, Cin, Cout, gw):
     GEMMs when launched where autograd reaches them; inside a weight_grad_group they join the stage's grouped launch
     (undivided reduction, one task per 64 x 64 output block, written straight to the target).  True when queued."""
     g = _WG_GROUP
-    if g is None or not GROUP_SMALL_ROW_GRADS or N < 1 or Cin % 16 or Cout % 16:
+    if g is None or N < 1 or Cin % 16 or Cout % 16:
         return False
     if x.data_ptr() % 16 or gm.data_ptr() % 16 or not x.is_contiguous() or not gm.is_contiguous():
         return False
     g.add(x, gm, N, Cin, Cout, gw, None, 0, None, None)
     return True
-
-
-# False: weight gradients below _SPLITK_MIN_ROWS rows stay library GEMMs even inside a group (A/B measurements)
-GROUP_SMALL_ROW_GRADS = True
 
 
 def _grad_weight_atb(x, gm, N, Cin, Cout, gw, bias_part, bias_blocks, first, second, label):
@@ -1547,6 +1489,18 @@ def _grad_weight_atb(x, gm, N, Cin, Cout, gw, bias_part, bias_blocks, first, sec
                           "d3f_linear_grad_weight")
 
 
+def _weight_grad(x, gm, N, Cin, Cout, gw, use_atb, bias_part=None, bias_blocks=0, first=None, second=None,
+                 label="linear_dw", gemm_label=None):
+    """grad_W = gm^T x into ``gw`` [Cout, Cin] the way every node does it: the reduction-parallel kernels when the node
+    decided ``use_atb`` (they also finish the bias partials, see _grad_weight_atb), else as one of the stage's grouped
+    small problems, else a library GEMM (under the profiler region ``gemm_label`` when given)."""
+    if use_atb:
+        _grad_weight_atb(x, gm, N, Cin, Cout, gw, bias_part, bias_blocks, first, second, label)
+    elif not _queue_small_weight_grad(x, gm, N, Cin, Cout, gw):
+        with _Region(_PROFILER if gemm_label else None, gemm_label, 4 * N * (Cin + Cout)):
+            torch.mm(gm.t(), x, out=gw)
+
+
 class _LinearLibBiasActFn(torch.autograd.Function):
     """act(x W^T + b1 + add + b2) as library GEMM + one epilogue launch, as ONE autograd node (round 5; it used to be
     _LinearFn followed by _BiasActFn): the backward runs the epilogue's backward, grad_x = g W (library; a sibling
@@ -1558,18 +1512,11 @@ class _LinearLibBiasActFn(torch.autograd.Function):
         L = _native.lib()
         ctx.holder, ctx.dep = holder, deposit
         N, C = int(x.shape[0]), int(weight.shape[0])
-        nb = int(b1 is not None and ctx.needs_input_grad[2]) + int(b2 is not None and ctx.needs_input_grad[4])
-        gbuf = torch.empty((nb, C), dtype=torch.float32, device=x.device) if nb else None
+        gbuf, nb = _bias_grad_buffer(b1 is not None and ctx.needs_input_grad[2],
+                                     b2 is not None and ctx.needs_input_grad[4], C, x.device)
         ctx.gbuf, ctx.slope = gbuf, float(slope)
         ctx.has = (b1 is not None, add is not None, b2 is not None)
         ctx.gw_slot = _grad_slot(weight)
-        Cin = int(x.shape[1])
-        if pack is None and x.is_contiguous() and weight.is_contiguous() and (add is None or add.is_contiguous()) and \
-                _own_gemm("unary_fwd", x, weight, GEMM_NT, N, Cin, C, 0, None, None, b1, add, b2):
-            # x W^T + both biases + residual + LeakyReLU in one launch (csrc/gemm_epilogue.hip)
-            out = gemm_epilogue(x, weight, GEMM_NT, N, Cin, C, bias1=b1, add=add, bias2=b2, slope=slope, zero_init=gbuf)
-            ctx.save_for_backward(x, weight, out)
-            return out
         raw = torch.mm(x, weight.t())
         out = torch.empty_like(raw)
         if pack is not None:
@@ -1601,17 +1548,7 @@ class _LinearLibBiasActFn(torch.autograd.Function):
         go = grad_out.contiguous()
         want1 = ctx.has[0] and ctx.needs_input_grad[2]
         want2 = ctx.has[2] and ctx.needs_input_grad[4]
-        g1 = g2 = None
-        pre = 0
-        if want1 or want2:
-            gbuf, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gbuf is None:
-                gbuf, pre = torch.empty((int(want1) + int(want2), Cout), dtype=torch.float32, device=go.device), 0
-            rows = list(gbuf.unbind(0))
-            g1 = rows.pop(0) if want1 else None
-            g2 = rows.pop(0) if want2 else None
-        first, second = (g1, g2) if g1 is not None else (g2, None)
+        g1, g2, first, second, pre = _bias_grad_rows(ctx, want1, want2, Cout, go.device)
         need_w = ctx.needs_input_grad[1]
         atb = need_w and N >= _SPLITK_MIN_ROWS and bool(L.d3f_linear_grad_weight_supported(N, Cin, Cout))
         bias_part, bias_blocks = None, 0
@@ -1621,26 +1558,16 @@ class _LinearLibBiasActFn(torch.autograd.Function):
         else:
             gm = go if identity else torch.empty_like(go)
             bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, None if identity else gm, first,
-                                                        second, pre, None, _FOLD_BIAS_SUM and atb)
+                                                        second, pre, None, atb)
         gx = _add_deposited(ctx.holder, gm, weight) if ctx.needs_input_grad[0] else None
         if gx is not None and ctx.dep is not None and ctx.dep.deposit(gx):
             gx = None
         gw = None
         if need_w:
-            slot = ctx.gw_slot
-            if atb:
-                gw = slot if slot is not None else torch.empty_like(weight)
-                _grad_weight_atb(x, gm, N, Cin, Cout, gw, bias_part, bias_blocks, first, second, "linear_dw")
-                bias_part = None
-            else:
-                gw = slot if slot is not None else torch.empty_like(weight)
-                if not _queue_small_weight_grad(x, gm, N, Cin, Cout, gw):
-                    torch.mm(gm.t(), x, out=gw)
-        if bias_part is not None:      # (not reached: fold implies the A^T B path)
-            _native.check(L.d3f_bias_sum(_p(bias_part), bias_blocks, Cout, _p(first), _p(second), _stream()),
-                          "d3f_bias_sum")
-        return (gx, (_adoptable(gw, ctx.gw_slot) if gw is not None else None), g1,
-                gm if ctx.has[1] and ctx.needs_input_grad[3] else None, g2, None, None, None, None)
+            gw = _grad_target(ctx.gw_slot, weight)
+            _weight_grad(x, gm, N, Cin, Cout, gw, atb, bias_part, bias_blocks, first, second)
+        return (gx, _adoptable(gw, ctx.gw_slot), g1, gm if ctx.has[1] and ctx.needs_input_grad[3] else None, g2,
+                None, None, None, None)
 
 
 class _UpsampleLinearFn(torch.autograd.Function):
@@ -1658,15 +1585,8 @@ class _UpsampleLinearFn(torch.autograd.Function):
         N, Cs = int(skip.shape[0]), int(skip.shape[1])
         Cout, H = int(weight.shape[0]), int(idx.shape[1])
         w1, w2 = weight[:, :Cc], weight[:, Cc:]
-        ldw = int(weight.stride(0))
-        if xc.is_contiguous() and _own_gemm("decoder", xc, w1, GEMM_NT, Nc, Cc, Cout, 0, None, ldw):
-            t = gemm_epilogue(xc, w1, GEMM_NT, Nc, Cc, Cout, ldw=ldw)
-        else:
-            t = torch.mm(xc, w1.t())                  # [Nc, Cout] on the coarse rows
-        if skip.is_contiguous() and _own_gemm("decoder", skip, w2, GEMM_NT, N, Cs, Cout, 0, None, ldw):
-            y = gemm_epilogue(skip, w2, GEMM_NT, N, Cs, Cout, ldw=ldw)
-        else:
-            y = torch.mm(skip, w2.t())                # [N, Cout]
+        t = torch.mm(xc, w1.t())                  # [Nc, Cout] on the coarse rows
+        y = torch.mm(skip, w2.t())                # [N, Cout]
         out = torch.empty_like(y)
         nb = int(b1 is not None and ctx.needs_input_grad[4]) + int(b2 is not None and ctx.needs_input_grad[5])
         # backward targets, cleared by the forward launch on the side: bias-gradient rows + the pooled gradient [Nc, Cout]
@@ -1691,22 +1611,11 @@ class _UpsampleLinearFn(torch.autograd.Function):
         go = grad_out.contiguous()
         want1 = ctx.has[0] and ctx.needs_input_grad[4]
         want2 = ctx.has[1] and ctx.needs_input_grad[5]
-        g1 = g2 = None
-        pre = 0
-        if want1 or want2:
-            gbuf, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gbuf is None:
-                gbuf, pre = torch.empty((int(want1) + int(want2), Cout), dtype=torch.float32, device=go.device), 0
-            rows = list(gbuf.unbind(0))
-            g1 = rows.pop(0) if want1 else None
-            g2 = rows.pop(0) if want2 else None
+        g1, g2, first, second, pre = _bias_grad_rows(ctx, want1, want2, Cout, go.device)
         gm = torch.empty_like(go)
-        first, second = (g1, g2) if g1 is not None else (g2, None)
         atb = (ctx.needs_input_grad[3] and N >= _SPLITK_MIN_ROWS
                and bool(L.d3f_linear_grad_weight_supported(N, Cs, Cout)))
-        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, gm, first, second, pre, None,
-                                                    _FOLD_BIAS_SUM and atb)
+        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, gm, first, second, pre, None, atb)
         # pooled gradient of the coarse product: g_t[m] = sum_{n: idx[n,0] = m} gm[n]
         gt, ctx.gt_buf = ctx.gt_buf, None
         pre_t = 1 if gt is not None else 0
@@ -1715,32 +1624,18 @@ class _UpsampleLinearFn(torch.autograd.Function):
         _native.check(L.d3f_closest_pool_backward(_p(gm), Cout, _p(idx), N, H, Cout, Nc, _p(gt), pre_t, _stream()),
                       "d3f_closest_pool_backward")
         w1, w2 = weight[:, :Cc], weight[:, Cc:]
-        ldw = int(weight.stride(0))
-        gxc = gskip = None
-        if ctx.needs_input_grad[0]:
-            if _own_gemm("decoder", gt, w1, GEMM_NN, Nc, Cout, Cc, 0, None, ldw):
-                gxc = gemm_epilogue(gt, w1, GEMM_NN, Nc, Cout, Cc, ldw=ldw)
-            else:
-                gxc = torch.mm(gt, w1)
-        if ctx.needs_input_grad[2]:
-            if _own_gemm("decoder", gm, w2, GEMM_NN, N, Cout, Cs, 0, None, ldw):
-                gskip = gemm_epilogue(gm, w2, GEMM_NN, N, Cout, Cs, ldw=ldw)
-            else:
-                gskip = torch.mm(gm, w2)
+        gxc = torch.mm(gt, w1) if ctx.needs_input_grad[0] else None
+        gskip = torch.mm(gm, w2) if ctx.needs_input_grad[2] else None
         if gskip is not None and ctx.skip_dep is not None and ctx.skip_dep.deposit(gskip):
             gskip = None    # handed to the encoder block that consumes the same skip tensor (GradHolder)
         gw = None
         if ctx.needs_input_grad[3]:
-            slot = ctx.gw_slot
-            gw = slot if slot is not None else torch.empty_like(weight)
-            if not _queue_small_weight_grad(xc, gt, Nc, Cc, Cout, gw[:, :Cc]):
-                torch.mm(gt.t(), xc, out=gw[:, :Cc])  # the GEMMs write their column block of W's gradient in place
-            if atb:   # (the grouped second stage writes the column block of W's gradient in place: row stride Cc + Cs)
-                _grad_weight_atb(skip, gm, N, Cs, Cout, gw[:, Cc:], bias_part, bias_blocks, first, second, "linear_dw")
-            elif not _queue_small_weight_grad(skip, gm, N, Cs, Cout, gw[:, Cc:]):
-                torch.mm(gm.t(), skip, out=gw[:, Cc:])
-            gw = _adoptable(gw, slot)
-        return gxc, None, gskip, gw, g1, g2, None, None
+            gw = _grad_target(ctx.gw_slot, weight)
+            # the GEMMs and the grouped second stage write their column block of W's gradient in place (row stride
+            # Cc + Cs); the coarse half (few rows) never takes the A^T B path
+            _weight_grad(xc, gt, Nc, Cc, Cout, gw[:, :Cc], False)
+            _weight_grad(skip, gm, N, Cs, Cout, gw[:, Cc:], atb, bias_part, bias_blocks, first, second)
+        return gxc, None, gskip, _adoptable(gw, ctx.gw_slot), g1, g2, None, None
 
 
 def upsample_linear_bias_act(x_coarse, inds, skip, weight, bias1=None, bias2=None, slope=0.1, skip_grad_deposit=None):
@@ -1752,16 +1647,13 @@ def upsample_linear_bias_act(x_coarse, inds, skip, weight, bias1=None, bias2=Non
     if w.shape[1] != xc.shape[1] + sk.shape[1] or idx.shape[0] != sk.shape[0]:
         raise RuntimeError("upsample_linear: shapes x_c%s skip%s W%s idx%s" % (
             tuple(xc.shape), tuple(sk.shape), tuple(w.shape), tuple(idx.shape)))
-    b1 = _f32(bias1, "bias1") if bias1 is not None else None
-    b2 = _f32(bias2, "bias2") if bias2 is not None else None
-    return _UpsampleLinearFn.apply(xc, idx, sk, w, b1, b2, float(slope), skip_grad_deposit)
+    return _UpsampleLinearFn.apply(xc, idx, sk, w, _opt_f32(bias1, "bias1"), _opt_f32(bias2, "bias2"), float(slope),
+                                   skip_grad_deposit)
 
 
 # rows from which the unary blocks use the fused row-streaming kernels instead of library GEMM + epilogue launch
 _FUSED_LINEAR_MIN_ROWS = 4096
 _FUSED_LINEAR_MAX_CIN = 64     # (wider inputs: the library GEMM's deeper tiling + an epilogue launch wins, re-measured in round 6)
-# library GEMM + epilogue as ONE autograd node (_LinearLibBiasActFn); D3F_MERGED_UNARY=0: the two nodes of rounds 1-4
-_MERGED_UNARY = True
 
 
 def linear_bias_act(x, weight, bias1=None, add=None, bias2=None, slope=0.1, grad_holder=None, grad_deposit=None,
@@ -1774,15 +1666,13 @@ def linear_bias_act(x, weight, bias1=None, add=None, bias2=None, slope=0.1, grad
     N, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
     # measured (profiles/unary_gemm_microbench.py): the fused kernel beats library GEMM + epilogue launch for
     # Cin <= 64 (7-21 us vs 10-27 us at 38k rows), not for Cin >= 128 where the library's deeper tiling wins
-    if N >= _FUSED_LINEAR_MIN_ROWS and Cin <= _FUSED_LINEAR_MAX_CIN and _native.lib().d3f_linear_fused_supported(N, Cin, Cout):
-        b1 = _f32(bias1, "bias1") if bias1 is not None else None
-        b2 = _f32(bias2, "bias2") if bias2 is not None else None
-        a = _f32(add, "add") if add is not None else None
-        return _LinearBiasActFn.apply(x, weight, b1, a, b2, float(slope), grad_holder, grad_deposit)
-    if _MERGED_UNARY and x.dim() == 2 and x.is_cuda and (add is None or add.shape == (N, Cout)):
-        b1 = _f32(bias1, "bias1") if bias1 is not None else None
-        b2 = _f32(bias2, "bias2") if bias2 is not None else None
-        a = _f32(add, "add") if add is not None else None
+    fused = N >= _FUSED_LINEAR_MIN_ROWS and Cin <= _FUSED_LINEAR_MAX_CIN and \
+        _native.lib().d3f_linear_fused_supported(N, Cin, Cout)
+    if fused or (x.dim() == 2 and x.is_cuda and (add is None or add.shape == (N, Cout))):
+        b1, b2, a = _opt_f32(bias1, "bias1"), _opt_f32(bias2, "bias2"), _opt_f32(add, "add")
+        if fused:
+            return _LinearBiasActFn.apply(x, weight, b1, a, b2, float(slope), grad_holder, grad_deposit)
+        # library GEMM + epilogue as ONE autograd node
         if pack_for is not None and N > 0 and _native.lib().d3f_bias_act_packs(Cout) and N * Cout < 2 ** 32 and \
                 int(pack_for[0].shape[0]) == N:
             s_pts = _f32(pack_for[0], "s_pts")
@@ -1915,7 +1805,7 @@ def closest_pool(x, inds, skip=None):
     idx = _i32(inds, "inds")
     if idx.dim() == 1:
         idx = idx.view(-1, 1)
-    sk = _f32(skip, "skip") if skip is not None else None
+    sk = _opt_f32(skip, "skip")
     if sk is not None and (sk.dim() != 2 or sk.shape[0] != idx.shape[0]):
         raise RuntimeError("closest_pool: skip %s does not match %d query rows" % (tuple(sk.shape), idx.shape[0]))
     return _ClosestPoolFn.apply(_f32(x, "x"), idx, sk)
@@ -1934,18 +1824,20 @@ class _BiasActFn(torch.autograd.Function):
     def forward(ctx, x, b1, add, b2, slope, pack=None):
         N, C = int(x.shape[0]), int(x.shape[1])
         out = torch.empty_like(x)
+        # the backward's bias-gradient accumulators [2, C] are cleared by the forward kernel on the side: no fill
+        # launch in backward, and the two bias parameters get separate buffers (autograd would clone a shared one)
+        gbuf, nb = _bias_grad_buffer(b1 is not None and ctx.needs_input_grad[1],
+                                     b2 is not None and ctx.needs_input_grad[3], C, x.device)
+        ctx.gbuf, ctx.slope = gbuf, float(slope)
+        ctx.has = (b1 is not None, add is not None, b2 is not None)
         if pack is not None:
             s_pts, want_clear = pack
-            nb = int(b1 is not None and ctx.needs_input_grad[1]) + int(b2 is not None and ctx.needs_input_grad[3])
-            gbuf = torch.empty((nb, C), dtype=torch.float32, device=x.device) if nb else None
             spack = torch.empty(16 * N, dtype=torch.uint8, device=x.device)
             gx_clear = torch.empty_like(x) if want_clear else None
             _native.check(_native.lib().d3f_bias_act_forward_pack(
                 _p(x), _p(b1), _p(add), _p(b2), float(slope), N, C, _p(out), _p(gbuf), nb * C, None, None, 0, 0,
                 _p(s_pts), _p(spack), _p(gx_clear), _stream()), "d3f_bias_act_forward_pack")
             ctx.save_for_backward(out)
-            ctx.gbuf, ctx.slope = gbuf, float(slope)
-            ctx.has = (b1 is not None, add is not None, b2 is not None)
             ctx.mark_non_differentiable(spack)
             if gx_clear is not None:
                 ctx.mark_non_differentiable(gx_clear)
@@ -1953,17 +1845,10 @@ class _BiasActFn(torch.autograd.Function):
             # per packed layer and step, visible in the step timeline as FillFunctor pairs)
             ctx.set_materialize_grads(False)
             return out, spack, gx_clear
-        # the backward's bias-gradient accumulators [2, C] are cleared by the forward kernel on the side: no fill
-        # launch in backward, and the two bias parameters get separate buffers (autograd would clone a shared one)
-        nb = int(b1 is not None and ctx.needs_input_grad[1]) + int(b2 is not None and ctx.needs_input_grad[3])
-        gbuf = torch.empty((nb, C), dtype=torch.float32, device=x.device) if nb else None
         _native.check(_native.lib().d3f_bias_act_forward(_p(x), _p(b1), _p(add), _p(b2), float(slope), N, C, _p(out),
                                                          _p(gbuf), nb * C, None, None, 0, 0, _stream()),
                       "d3f_bias_act_forward")
         ctx.save_for_backward(out)
-        ctx.gbuf = gbuf
-        ctx.slope = float(slope)
-        ctx.has = (b1 is not None, add is not None, b2 is not None)
         return out
 
     @staticmethod
@@ -1977,21 +1862,13 @@ class _BiasActFn(torch.autograd.Function):
         want1 = ctx.has[0] and ctx.needs_input_grad[1]
         want2 = ctx.has[2] and ctx.needs_input_grad[3]
         identity = ctx.slope == 1.0
-        gx = g1 = g2 = None
-        if want1 or want2:
-            gbuf, pre = ctx.gbuf, 1
-            ctx.gbuf = None
-            if gbuf is None:  # a second backward through the same node: fresh, not pre-cleared accumulators
-                gbuf, pre = torch.empty((int(want1) + int(want2), C), dtype=torch.float32, device=go.device), 0
-            rows = list(gbuf.unbind(0))
-            g1 = rows.pop(0) if want1 else None
-            g2 = rows.pop(0) if want2 else None
+        gx = None
+        g1, g2, first, second, pre = _bias_grad_rows(ctx, want1, want2, C, go.device)
         if identity and not (want1 or want2):
             gx = go
         elif need_gx or want1 or want2:
             if need_gx and not identity:
                 gx = torch.empty_like(go)
-            first, second = (g1, g2) if g1 is not None else (g2, None)
             wsb, nws = _bias_bwd_ws(N, C, go.device) if first is not None else (None, 0)
             _native.check(_native.lib().d3f_bias_act_backward(_p(go), _p(out), ctx.slope, N, C, _p(gx), _p(first),
                                                               _p(second), pre if first is not None else 0, None,
@@ -2010,9 +1887,7 @@ def bias_act(x, bias1=None, add=None, bias2=None, slope=0.1, pack_for=None):
     x = _f32(x, "x")
     if x.dim() != 2:
         raise RuntimeError("bias_act expects [N, C]")
-    b1 = _f32(bias1, "bias1") if bias1 is not None else None
-    b2 = _f32(bias2, "bias2") if bias2 is not None else None
-    a = _f32(add, "add") if add is not None else None
+    b1, b2, a = _opt_f32(bias1, "bias1"), _opt_f32(bias2, "bias2"), _opt_f32(add, "add")
     if a is not None and a.shape != x.shape:
         raise RuntimeError("bias_act: residual shape %s != %s" % (tuple(a.shape), tuple(x.shape)))
     if pack_for is not None and x.shape[0] > 0 and _native.lib().d3f_bias_act_packs(int(x.shape[1])) and \
@@ -2081,8 +1956,7 @@ def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.
         raise RuntimeError("batch_norm in eval mode needs running statistics")
     if momentum is None:
         raise RuntimeError("batch_norm: cumulative-average momentum (None) is not supported")
-    w = _f32(weight, "weight") if weight is not None else None
-    b = _f32(bias, "bias") if bias is not None else None
+    w, b = _opt_f32(weight, "weight"), _opt_f32(bias, "bias")
     return _BatchNormFn.apply(x, w, b, running_mean, running_var, bool(training), float(momentum), float(eps),
                               float(slope), n_live)[0]
 
@@ -2174,6 +2048,56 @@ def detection_scores(features, neighbors, training=True, lens=None, width=None, 
 # ---------------------------------------------------------------------------------------------------------------
 # circle + detector loss (utils/loss.py:8-44,111-141,149-158)
 # ---------------------------------------------------------------------------------------------------------------
+def _circle_fwd(oa, op, sa, sp, neg_mask, P, M, params, weights):
+    """Forward launches on selected rows oa/op [P*M,C]: (scalars, total or None, dists, fp, an, stats).  ``weights``
+    None: the single-pair kernel (scalars [6], dists [M,M]; scalars[5] = desc + det); otherwise P stacked pairs in two
+    launches (strips of all pairs, finalize), scalars [P,6], dists [P,M,M], total = sum_p (w_desc desc_p + w_det det_p)."""
+    L = _native.lib()
+    C, dev = int(oa.shape[1]), oa.device
+    s, sr, pm, nm = params
+    lead = () if weights is None else (P,)
+    dists = torch.empty(lead + (M, M), dtype=torch.float32, device=dev)
+    fp = torch.empty(P * M, dtype=torch.float32, device=dev)
+    an = torch.empty(P * M, dtype=torch.float32, device=dev)
+    scalars = torch.empty(lead + (6,), dtype=torch.float32, device=dev)
+    stats = torch.empty(P * L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
+    if weights is None:
+        total = None
+        _native.check(L.d3f_circle_det_loss_forward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
+                                                    _p(dists), _p(fp), _p(an), _p(scalars), _p(stats), _stream()),
+                      "d3f_circle_det_loss_forward")
+    else:
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        _native.check(L.d3f_circle_det_loss_forward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
+                                                          pm, nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
+                                                          _p(scalars), _p(total), _p(stats), _stream()),
+                      "d3f_circle_det_loss_forward_pairs")
+    return scalars, total, dists, fp, an, stats
+
+
+def _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, weights, g_ptrs):
+    """(ga, gp, gsa, gsp) of _circle_fwd.  ``g_ptrs``: device addresses of d / d desc and d / d det (single pair), or of
+    d / d total alone (stacked pairs: the kernel applies ``weights``)."""
+    L = _native.lib()
+    C = int(oa.shape[1])
+    s, sr, pm, nm = params
+    ga, gp = torch.empty_like(oa), torch.empty_like(op)
+    gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
+    if weights is None:
+        nbytes = L.d3f_circle_det_loss_ws_bytes(M)
+        ws = _ws(nbytes, oa.device)
+        _native.check(L.d3f_circle_det_loss_backward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
+                                                     _p(dists), _p(stats), g_ptrs[0], g_ptrs[1], _p(ga), _p(gp),
+                                                     _p(gsa), _p(gsp), _p(ws), nbytes, _stream()),
+                      "d3f_circle_det_loss_backward")
+    else:
+        _native.check(L.d3f_circle_det_loss_backward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
+                                                           pm, nm, weights[0], weights[1], _p(dists), _p(stats),
+                                                           g_ptrs[0], _p(ga), _p(gp), _p(gsa), _p(gsp), _stream()),
+                      "d3f_circle_det_loss_backward_pairs")
+    return ga, gp, gsa, gsp
+
+
 class _CircleDetFn(torch.autograd.Function):
     """Returns (scalars[6], dists[M,M], furthest_positive[M], average_negative[M]); scalars[0] = desc loss,
     scalars[1] = det loss are differentiable wrt anchor / positive / scores."""
@@ -2181,20 +2105,10 @@ class _CircleDetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, positive, neg_mask, anc_score, pos_score, log_scale, safe_radius, pos_margin,
                 neg_margin):
-        L = _native.lib()
-        M, C = int(anchor.shape[0]), int(anchor.shape[1])
-        dev = anchor.device
-        dists = torch.empty((M, M), dtype=torch.float32, device=dev)
-        fp = torch.empty(M, dtype=torch.float32, device=dev)
-        an = torch.empty(M, dtype=torch.float32, device=dev)
-        scalars = torch.empty(6, dtype=torch.float32, device=dev)
-        stats = torch.empty(L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
-        _native.check(L.d3f_circle_det_loss_forward(_p(anchor), _p(positive), M, C, _p(neg_mask), _p(anc_score),
-                                                    _p(pos_score), float(log_scale), float(safe_radius),
-                                                    float(pos_margin), float(neg_margin), _p(dists), _p(fp), _p(an),
-                                                    _p(scalars), _p(stats), _stream()), "d3f_circle_det_loss_forward")
-        ctx.save_for_backward(anchor, positive, neg_mask, anc_score, pos_score, dists, stats)
         ctx.params = (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin))
+        scalars, _, dists, fp, an, stats = _circle_fwd(anchor, positive, anc_score, pos_score, neg_mask, 1,
+                                                       int(anchor.shape[0]), ctx.params, None)
+        ctx.save_for_backward(anchor, positive, neg_mask, anc_score, pos_score, dists, stats)
         ctx.mark_non_differentiable(dists, fp, an)
         ctx.set_materialize_grads(False)
         return scalars, dists, fp, an
@@ -2204,27 +2118,22 @@ class _CircleDetFn(torch.autograd.Function):
         if g_scalars is None:
             return (None,) * 9
         anchor, positive, neg_mask, anc_score, pos_score, dists, stats = ctx.saved_tensors
-        L = _native.lib()
-        M, C = int(anchor.shape[0]), int(anchor.shape[1])
         g = g_scalars.contiguous().float()
-        ga, gp = torch.empty_like(anchor), torch.empty_like(positive)
-        gsa, gsp = torch.empty_like(anc_score), torch.empty_like(pos_score)
-        nbytes = L.d3f_circle_det_loss_ws_bytes(M)
-        ws = _ws(nbytes, anchor.device)
-        s, sr, pm, nm = ctx.params
-        _native.check(L.d3f_circle_det_loss_backward(_p(anchor), _p(positive), M, C, _p(neg_mask), _p(anc_score),
-                                                     _p(pos_score), s, sr, pm, nm, _p(dists), _p(stats),
-                                                     g.data_ptr(), g.data_ptr() + 4, _p(ga), _p(gp), _p(gsa), _p(gsp),
-                                                     _p(ws), nbytes, _stream()), "d3f_circle_det_loss_backward")
+        ga, gp, gsa, gsp = _circle_bwd(anchor, positive, anc_score, pos_score, neg_mask, dists, stats, 1,
+                                       int(anchor.shape[0]), ctx.params, None, (g.data_ptr(), g.data_ptr() + 4))
         return ga, gp, None, gsa, gsp, None, None, None, None
+
+
+def _neg_mask_of(dist_keypts, safe_radius):
+    if dist_keypts is None or not dist_keypts.is_cuda:
+        raise RuntimeError("dist_keypts must be a CUDA/HIP tensor")
+    return (dist_keypts > safe_radius).to(torch.uint8).contiguous()  # evaluated in the caller's dtype (f64)
 
 
 def circle_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, log_scale=10.0, safe_radius=0.1,
                     pos_margin=0.1, neg_margin=1.4):
     anchor, positive = _f32(anchor, "anchor"), _f32(positive, "positive")
-    if not dist_keypts.is_cuda:
-        raise RuntimeError("dist_keypts must be a CUDA/HIP tensor")
-    neg_mask = (dist_keypts > safe_radius).to(torch.uint8).contiguous()  # evaluated in the caller's dtype (f64)
+    neg_mask = _neg_mask_of(dist_keypts, safe_radius)
     sa = _f32(anc_score, "anc_score").reshape(-1)
     sp = _f32(pos_score, "pos_score").reshape(-1)
     return _CircleDetFn.apply(anchor, positive, neg_mask, sa, sp, log_scale, safe_radius, pos_margin, neg_margin)
@@ -2296,188 +2205,6 @@ def select_normalize(x, scores, idx_a, idx_p, p_offset=None):
     sc = _f32(scores, "scores").reshape(-1, 1)
     ia, ip, stride = _corr_columns(idx_a, idx_p)
     return _SelectNormalizeFn.apply(x, sc, ia, ip, _p_offset(p_offset, x.device), stride)
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# the whole loss of one training step (trainer.py:91-98) as ONE autograd node
-# ---------------------------------------------------------------------------------------------------------------
-class _TrainLossFn(torch.autograd.Function):
-    """x [N,C] raw descriptors, scores [N,1], corr [M,2] -> (total, scalars[6], dists, furthest_positive,
-    average_negative) with total = w_desc * desc + w_det * det.  Same three kernels as select_normalize +
-    circle_det_loss; what disappears is the autograd glue between them (index selects and their zero-filled
-    backward, the weighted sum and its backward: ~12 sub-5-us launches per step)."""
-
-    @staticmethod
-    def forward(ctx, x, scores, corr, p_offset, neg_mask, params, weights, gw):
-        L = _native.lib()
-        ia, ip, stride = _corr_columns(corr[:, 0], corr[:, 1])
-        oa, op, sa, sp = _select_normalize_fwd(x, scores, ia, ip, stride, p_offset)
-        M, C = int(oa.shape[0]), int(oa.shape[1])
-        dev = x.device
-        dists = torch.empty((M, M), dtype=torch.float32, device=dev)
-        fp = torch.empty(M, dtype=torch.float32, device=dev)
-        an = torch.empty(M, dtype=torch.float32, device=dev)
-        scalars = torch.empty(6, dtype=torch.float32, device=dev)
-        stats = torch.empty(L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
-        s, sr, pm, nm = params
-        _native.check(L.d3f_circle_det_loss_forward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
-                                                    _p(dists), _p(fp), _p(an), _p(scalars), _p(stats), _stream()),
-                      "d3f_circle_det_loss_forward")
-        # unit weights (config.py:58-59): the kernel's own desc + det (scalars[5]); no launch for the sum
-        total = scalars[5] if weights == (1.0, 1.0) else torch.dot(scalars[:2], gw)
-        ctx.save_for_backward(x, ia, ip, p_offset if p_offset is not None else ia.new_empty(0), neg_mask, oa, op, sa,
-                              sp, dists, stats, gw)
-        ctx.meta = (stride, p_offset is not None, params, weights == (1.0, 1.0))
-        ctx.mark_non_differentiable(scalars, dists, fp, an)
-        ctx.set_materialize_grads(False)   # (else four zero-fill launches per step for the by-products' gradients)
-        return total, scalars, dists, fp, an
-
-    @staticmethod
-    def backward(ctx, g_total, g_scalars, g_dists, g_fp, g_an):
-        if g_total is None:
-            return (None,) * 8
-        x, ia, ip, p_off, neg_mask, oa, op, sa, sp, dists, stats, gw = ctx.saved_tensors
-        stride, has_off, (s, sr, pm, nm), unit = ctx.meta
-        L = _native.lib()
-        M, C = int(oa.shape[0]), int(oa.shape[1])
-        if unit:   # d total / d desc = d total / d det = g_total: both pointers read the same scalar
-            g = g_total.contiguous().float().reshape(1)
-            p_desc = p_det = g.data_ptr()
-        else:
-            g = (gw * g_total).contiguous()
-            p_desc, p_det = g.data_ptr(), g.data_ptr() + 4
-        ga, gp = torch.empty_like(oa), torch.empty_like(op)
-        gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
-        nbytes = L.d3f_circle_det_loss_ws_bytes(M)
-        ws = _ws(nbytes, x.device)
-        _native.check(L.d3f_circle_det_loss_backward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
-                                                     _p(dists), _p(stats), p_desc, p_det, _p(ga),
-                                                     _p(gp), _p(gsa), _p(gsp), _p(ws), nbytes, _stream()),
-                      "d3f_circle_det_loss_backward")
-        gx, gs = _select_normalize_bwd(x, ia, ip, stride, p_off if has_off else None, ga, gp, gsa, gsp)
-        return gx, gs, None, None, None, None, None, None
-
-
-def train_loss(x, scores, corr, p_offset, dist_keypts, log_scale=10.0, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
-               w_desc=1.0, w_det=1.0, neg_mask=None, _gw_cache={}):
-    """Loss of one training step on the un-normalised network output (trainer.py:91-98):
-    ``w_desc * CircleLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset]) + w_det * DetLoss(...)``.
-    Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only ``total`` carries
-    gradient.  ``neg_mask``: ``dist_keypts > safe_radius`` as uint8 when the caller already has it (the pipelined step
-    evaluates it with the pair's upload, off the training stream)."""
-    x = _f32(x, "x")
-    sc = _f32(scores, "scores").reshape(-1, 1)
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
-        raise ValueError("corr must be an int64 [M,2] device tensor")
-    corr = corr.contiguous()
-    if neg_mask is None:
-        if not dist_keypts.is_cuda:
-            raise RuntimeError("dist_keypts must be a CUDA/HIP tensor")
-        neg_mask = (dist_keypts > safe_radius).to(torch.uint8).contiguous()  # evaluated in the caller's dtype (f64)
-    elif not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous()
-              and tuple(neg_mask.shape) == (corr.shape[0], corr.shape[0])):
-        raise ValueError("neg_mask must be a contiguous uint8 [M,M] device tensor (dist_keypts > safe_radius)")
-    key = (x.device, float(w_desc), float(w_det))
-    if key not in _gw_cache:
-        _gw_cache[key] = torch.tensor([float(w_desc), float(w_det)], dtype=torch.float32, device=x.device)
-    total, scalars, dists, fp, an = _TrainLossFn.apply(
-        x, sc, corr, _p_offset(p_offset, x.device), neg_mask,
-        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)),
-        _gw_cache[key])
-    return total, scalars[0], scalars[1], scalars[2], fp, an
-
-
-class _TrainLossPairsFn(torch.autograd.Function):
-    """_TrainLossFn for P fragment pairs stacked into one batch: x [N,C], scores [N,1], corr [P*M,2] (every pair's own
-    cloud-local table), lens int32 [2P] (level-0 stack lengths on the device), neg_mask [P,M,M] -> (total, scalars
-    [P,6], dists [P,M,M], furthest_positive [P*M], average_negative [P*M]) with total = sum_p (w_desc desc_p + w_det
-    det_p).  Three launches forward (select + normalise, strips of all pairs, finalize), two backward."""
-
-    @staticmethod
-    def forward(ctx, x, scores, corr, lens, neg_mask, params, weights):
-        L = _native.lib()
-        P, M = int(neg_mask.shape[0]), int(neg_mask.shape[1])
-        N, C = int(x.shape[0]), int(x.shape[1])
-        dev = x.device
-        T = P * M
-        oa = torch.empty((T, C), dtype=torch.float32, device=dev)
-        op = torch.empty((T, C), dtype=torch.float32, device=dev)
-        sa = torch.empty(T, dtype=torch.float32, device=dev)
-        sp = torch.empty(T, dtype=torch.float32, device=dev)
-        _native.check(L.d3f_select_normalize_forward_pairs(_p(x), _p(scores), N, C, _p(corr), M, P, _p(lens), _p(oa),
-                                                           _p(op), _p(sa), _p(sp), _stream()),
-                      "d3f_select_normalize_forward_pairs")
-        dists = torch.empty((P, M, M), dtype=torch.float32, device=dev)
-        fp = torch.empty(T, dtype=torch.float32, device=dev)
-        an = torch.empty(T, dtype=torch.float32, device=dev)
-        scalars = torch.empty((P, 6), dtype=torch.float32, device=dev)
-        total = torch.empty((), dtype=torch.float32, device=dev)
-        stats = torch.empty(P * L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
-        s, sr, pm, nm = params
-        _native.check(L.d3f_circle_det_loss_forward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
-                                                          pm, nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
-                                                          _p(scalars), _p(total), _p(stats), _stream()),
-                      "d3f_circle_det_loss_forward_pairs")
-        ctx.save_for_backward(x, corr, lens, neg_mask, oa, op, sa, sp, dists, stats)
-        ctx.meta = (params, weights)
-        ctx.mark_non_differentiable(scalars, dists, fp, an)
-        ctx.set_materialize_grads(False)
-        return total, scalars, dists, fp, an
-
-    @staticmethod
-    def backward(ctx, g_total, g_scalars, g_dists, g_fp, g_an):
-        if g_total is None:
-            return (None,) * 7
-        x, corr, lens, neg_mask, oa, op, sa, sp, dists, stats = ctx.saved_tensors
-        (s, sr, pm, nm), weights = ctx.meta
-        L = _native.lib()
-        P, M = int(neg_mask.shape[0]), int(neg_mask.shape[1])
-        N, C = int(x.shape[0]), int(x.shape[1])
-        g = g_total.contiguous().float().reshape(1)
-        ga, gp = torch.empty_like(oa), torch.empty_like(op)
-        gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
-        _native.check(L.d3f_circle_det_loss_backward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
-                                                           pm, nm, weights[0], weights[1], _p(dists), _p(stats), _p(g),
-                                                           _p(ga), _p(gp), _p(gsa), _p(gsp), _stream()),
-                      "d3f_circle_det_loss_backward_pairs")
-        buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
-        gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
-        _native.check(L.d3f_select_normalize_backward_pairs(_p(x), N, C, _p(corr), M, P, _p(lens), _p(ga), _p(gp),
-                                                            _p(gsa), _p(gsp), _p(gx), _p(gs), _stream()),
-                      "d3f_select_normalize_backward_pairs")
-        return gx, gs, None, None, None, None, None
-
-
-def train_loss_pairs(x, scores, corr, lens, dist_keypts=None, log_scale=10.0, safe_radius=0.1, pos_margin=0.1,
-                     neg_margin=1.4, w_desc=1.0, w_det=1.0, neg_mask=None):
-    """Loss of one training step on P fragment pairs STACKED into one batch (clouds 2p, 2p+1 = pair p): per pair the
-    reference's ``CircleLoss`` + ``DetLoss`` on its own M sampled correspondences (trainer.py:91-98; the reference
-    trains one pair per step, dataloader.py:73), ``total`` = their sum -- its gradient is the sum of the pairs'
-    gradients, the optimizer's gradient scale makes the mean.  ``corr`` int64 [P,M,2] / [P*M,2] cloud-local rows as the
-    dataset yields them, ``lens`` device int32 [2P] (level-0 stack lengths), ``dist_keypts`` [P,M,M] or ``neg_mask``
-    uint8 [P,M,M] = dist_keypts > safe_radius.
-    Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
-    x = _f32(x, "x")
-    sc = _f32(scores, "scores").reshape(-1, 1)
-    if neg_mask is None:
-        if dist_keypts is None or not dist_keypts.is_cuda:
-            raise RuntimeError("dist_keypts must be a CUDA/HIP tensor")
-        neg_mask = (dist_keypts > safe_radius).to(torch.uint8).contiguous()   # evaluated in the caller's dtype (f64)
-    if not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous() and neg_mask.dim() == 3
-            and neg_mask.shape[1] == neg_mask.shape[2]):
-        raise ValueError("neg_mask must be a contiguous uint8 [P,M,M] device tensor (dist_keypts > safe_radius)")
-    P, M = int(neg_mask.shape[0]), int(neg_mask.shape[1])
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
-        raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
-    corr = corr.contiguous().view(P * M, 2)
-    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
-        raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
-    if M > 128 or int(x.shape[1]) > 64 or P > 32:
-        raise ValueError("stacked loss: M <= 128 correspondences, C <= 64 channels, P <= 32 pairs")
-    total, scalars, dists, fp, an = _TrainLossPairsFn.apply(
-        x, sc, corr, lens.contiguous(), neg_mask,
-        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)))
-    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -2575,59 +2302,161 @@ def contrastive_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, sa
                                    (float(safe_radius), float(pos_margin), float(neg_margin)))
 
 
-class _TrainContrastiveFn(torch.autograd.Function):
-    """_TrainLossFn / _TrainLossPairsFn with the contrastive loss: the select + normalise launches of the circle's
-    training forms, then the contrastive launches.  ``lens`` None: one pair (corr [M,2], p_offset); otherwise P stacked
-    pairs (corr [P*M,2] cloud-local, lens int32 [2P])."""
+# ---------------------------------------------------------------------------------------------------------------
+# the whole loss of one training step (trainer.py:91-98) as ONE autograd node
+# ---------------------------------------------------------------------------------------------------------------
+def _select_rows_fwd(x, scores, corr, p_offset, lens, P, M):
+    """The 2 P M sampled rows, gathered and normalised by one launch: (oa, op, sa, sp, saved, stride).  ``lens`` None:
+    one pair (corr [M,2], its columns read in place; p_offset); otherwise P stacked pairs (corr [P*M,2] cloud-local,
+    lens int32 [2P]).  ``saved`` (three tensors or None) and ``stride`` (None: stacked) are what _select_rows_bwd needs."""
+    if lens is None:
+        ia, ip, stride = _corr_columns(corr[:, 0], corr[:, 1])
+        return _select_normalize_fwd(x, scores, ia, ip, stride, p_offset) + ((ia, ip, p_offset), stride)
+    N, C, T, dev = int(x.shape[0]), int(x.shape[1]), P * M, x.device
+    oa = torch.empty((T, C), dtype=torch.float32, device=dev)
+    op = torch.empty((T, C), dtype=torch.float32, device=dev)
+    sa = torch.empty(T, dtype=torch.float32, device=dev)
+    sp = torch.empty(T, dtype=torch.float32, device=dev)
+    _native.check(_native.lib().d3f_select_normalize_forward_pairs(_p(x), _p(scores), N, C, _p(corr), M, P, _p(lens),
+                                                                   _p(oa), _p(op), _p(sa), _p(sp), _stream()),
+                  "d3f_select_normalize_forward_pairs")
+    return oa, op, sa, sp, (corr, lens, None), None
+
+
+def _select_rows_bwd(x, saved, stride, P, M, ga, gp, gsa, gsp):
+    """(grad_x [N,C], grad_scores [N,1]) of _select_rows_fwd."""
+    s0, s1, s2 = saved
+    if stride is not None:
+        return _select_normalize_bwd(x, s0, s1, stride, s2, ga, gp, gsa, gsp)
+    N, C = int(x.shape[0]), int(x.shape[1])
+    buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
+    gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+    _native.check(_native.lib().d3f_select_normalize_backward_pairs(_p(x), N, C, _p(s0), M, P, _p(s1), _p(ga), _p(gp),
+                                                                    _p(gsa), _p(gsp), _p(gx), _p(gs), _stream()),
+                  "d3f_select_normalize_backward_pairs")
+    return gx, gs
+
+
+class _TrainLossFn(torch.autograd.Function):
+    """x [N,C] raw descriptors, scores [N,1], corr -> (total, scalars, dists, furthest_positive, average_negative)
+    with total = sum over the pairs of w_desc * desc + w_det * det.  Same kernels as select_normalize + circle_det_loss /
+    contrastive_det_loss; what disappears is the autograd glue between them (index selects and their zero-filled
+    backward, the weighted sum and its backward: ~12 sub-5-us launches per step).
+    ``lens`` None: one pair (corr [M,2], p_offset), scalars [6] (circle) / [1,6] (contrastive); otherwise P pairs
+    stacked into one batch (corr [P*M,2], every pair's own cloud-local table; lens int32 [2P], the level-0 stack lengths
+    on the device), scalars [P,6], dists [P,M,M].  ``aux``: the circle loss's neg_mask (uint8) or the contrastive loss's
+    keypoint distances (f64), [M,M] / [P,M,M]; ``params`` = the loss's scalars, led by log_scale for the circle loss.
+    ``gw``: (w_desc, w_det) on the device, for the one form whose kernel does not apply the weights itself."""
 
     @staticmethod
-    def forward(ctx, x, scores, corr, p_offset, lens, dk, P, params, weights):
-        M = int(dk.shape[-1])
-        N, C = int(x.shape[0]), int(x.shape[1])
-        if lens is None:
-            ia, ip, stride = _corr_columns(corr[:, 0], corr[:, 1])
-            oa, op, sa, sp = _select_normalize_fwd(x, scores, ia, ip, stride, p_offset)
-            ctx.sel = (stride, p_offset is not None)
-            saved = (ia, ip, p_offset if p_offset is not None else ia.new_empty(0))
+    def forward(ctx, x, scores, corr, p_offset, lens, aux, circle, P, params, weights, gw):
+        M = int(aux.shape[-1])
+        oa, op, sa, sp, saved, stride = _select_rows_fwd(x, scores, corr, p_offset, lens, P, M)
+        # the single-pair circle kernel knows no weights: unit weights (config.py:58-59) take its own desc + det
+        # (scalars[5]; no launch for the sum), others go through ``gw``; every other form weights inside the kernel
+        plain = circle and lens is None
+        if circle:
+            scalars, total, dists, fp, an, stats = _circle_fwd(oa, op, sa, sp, aux, P, M, params,
+                                                               None if plain else weights)
         else:
-            T, dev = P * M, x.device
-            oa = torch.empty((T, C), dtype=torch.float32, device=dev)
-            op = torch.empty((T, C), dtype=torch.float32, device=dev)
-            sa = torch.empty(T, dtype=torch.float32, device=dev)
-            sp = torch.empty(T, dtype=torch.float32, device=dev)
-            _native.check(_native.lib().d3f_select_normalize_forward_pairs(_p(x), _p(scores), N, C, _p(corr), M, P,
-                                                                           _p(lens), _p(oa), _p(op), _p(sa), _p(sp),
-                                                                           _stream()),
-                          "d3f_select_normalize_forward_pairs")
-            ctx.sel = None
-            saved = (corr, lens, corr.new_empty(0))
-        scalars, total, dists, fp, an, stats = _contrastive_fwd(oa, op, sa, sp, dk, P, M, params, weights)
-        ctx.save_for_backward(x, *saved, oa, op, sa, sp, stats)
-        ctx.meta = (P, M, params, weights)
+            scalars, total, dists, fp, an, stats = _contrastive_fwd(oa, op, sa, sp, aux, P, M, params, weights)
+        if plain:
+            total = scalars[5] if weights == (1.0, 1.0) else torch.dot(scalars[:2], gw)
+        ctx.save_for_backward(x, *saved, oa, op, sa, sp, stats, *((aux, dists, gw) if circle else ()))
+        ctx.meta = (stride, circle, plain, P, M, params, weights)
         ctx.mark_non_differentiable(scalars, dists, fp, an)
-        ctx.set_materialize_grads(False)
+        ctx.set_materialize_grads(False)   # (else four zero-fill launches per step for the by-products' gradients)
         return total, scalars, dists, fp, an
 
     @staticmethod
     def backward(ctx, g_total, g_scalars, g_dists, g_fp, g_an):
         if g_total is None:
-            return (None,) * 9
-        x, s0, s1, s2, oa, op, sa, sp, stats = ctx.saved_tensors
-        P, M, params, weights = ctx.meta
-        g = g_total.contiguous().float().reshape(1)
-        ga, gp, gsa, gsp = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, (g.data_ptr(), None))
-        N, C = int(x.shape[0]), int(x.shape[1])
-        if ctx.sel is not None:
-            stride, has_off = ctx.sel
-            gx, gs = _select_normalize_bwd(x, s0, s1, stride, s2 if has_off else None, ga, gp, gsa, gsp)
+            return (None,) * 11
+        x, s0, s1, s2, oa, op, sa, sp, stats = ctx.saved_tensors[:9]
+        stride, circle, plain, P, M, params, weights = ctx.meta
+        if plain and weights != (1.0, 1.0):
+            g = (ctx.saved_tensors[11] * g_total).contiguous()
+            g_ptrs = (g.data_ptr(), g.data_ptr() + 4)
+        else:      # d total / d desc = d total / d det = g_total: both pointers read the same scalar
+            g = g_total.contiguous().float().reshape(1)
+            g_ptrs = (g.data_ptr(), g.data_ptr())
+        if circle:
+            neg_mask, dists = ctx.saved_tensors[9:11]
+            grads = _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, None if plain else weights, g_ptrs)
         else:
-            buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
-            gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
-            _native.check(_native.lib().d3f_select_normalize_backward_pairs(_p(x), N, C, _p(s0), M, P, _p(s1), _p(ga),
-                                                                            _p(gp), _p(gsa), _p(gsp), _p(gx), _p(gs),
-                                                                            _stream()),
-                          "d3f_select_normalize_backward_pairs")
-        return gx, gs, None, None, None, None, None, None, None
+            grads = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs)
+        gx, gs = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads)
+        return (gx, gs) + (None,) * 9
+
+
+def _loss_inputs(x, scores):
+    return _f32(x, "x"), _f32(scores, "scores").reshape(-1, 1)
+
+
+def _check_corr(corr):
+    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
+        raise ValueError("corr must be an int64 [M,2] device tensor")
+    return corr.contiguous()
+
+
+def _check_corr_pairs(corr, lens, P, M):
+    """(corr [P*M,2], lens) of a stacked batch of P pairs with M correspondences each."""
+    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
+        raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
+    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
+        raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
+    return corr.contiguous().view(P * M, 2), lens.contiguous()
+
+
+def train_loss(x, scores, corr, p_offset, dist_keypts, log_scale=10.0, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
+               w_desc=1.0, w_det=1.0, neg_mask=None, _gw_cache={}):
+    """Loss of one training step on the un-normalised network output (trainer.py:91-98):
+    ``w_desc * CircleLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset]) + w_det * DetLoss(...)``.
+    Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only ``total`` carries
+    gradient.  ``neg_mask``: ``dist_keypts > safe_radius`` as uint8 when the caller already has it (the pipelined step
+    evaluates it with the pair's upload, off the training stream)."""
+    x, sc = _loss_inputs(x, scores)
+    corr = _check_corr(corr)
+    if neg_mask is None:
+        neg_mask = _neg_mask_of(dist_keypts, safe_radius)
+    elif not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous()
+              and tuple(neg_mask.shape) == (corr.shape[0], corr.shape[0])):
+        raise ValueError("neg_mask must be a contiguous uint8 [M,M] device tensor (dist_keypts > safe_radius)")
+    key = (x.device, float(w_desc), float(w_det))
+    if key not in _gw_cache:
+        _gw_cache[key] = torch.tensor([float(w_desc), float(w_det)], dtype=torch.float32, device=x.device)
+    total, scalars, dists, fp, an = _TrainLossFn.apply(
+        x, sc, corr, _p_offset(p_offset, x.device), None, neg_mask, True, 1,
+        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)),
+        _gw_cache[key])
+    return total, scalars[0], scalars[1], scalars[2], fp, an
+
+
+def train_loss_pairs(x, scores, corr, lens, dist_keypts=None, log_scale=10.0, safe_radius=0.1, pos_margin=0.1,
+                     neg_margin=1.4, w_desc=1.0, w_det=1.0, neg_mask=None):
+    """Loss of one training step on P fragment pairs STACKED into one batch (clouds 2p, 2p+1 = pair p): per pair the
+    reference's ``CircleLoss`` + ``DetLoss`` on its own M sampled correspondences (trainer.py:91-98; the reference
+    trains one pair per step, dataloader.py:73), ``total`` = their sum -- its gradient is the sum of the pairs'
+    gradients, the optimizer's gradient scale makes the mean.  ``corr`` int64 [P,M,2] / [P*M,2] cloud-local rows as the
+    dataset yields them, ``lens`` device int32 [2P] (level-0 stack lengths), ``dist_keypts`` [P,M,M] or ``neg_mask``
+    uint8 [P,M,M] = dist_keypts > safe_radius.  Three launches forward (select + normalise, strips of all pairs,
+    finalize), two backward.
+    Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
+    x, sc = _loss_inputs(x, scores)
+    if neg_mask is None:
+        neg_mask = _neg_mask_of(dist_keypts, safe_radius)
+    if not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous() and neg_mask.dim() == 3
+            and neg_mask.shape[1] == neg_mask.shape[2]):
+        raise ValueError("neg_mask must be a contiguous uint8 [P,M,M] device tensor (dist_keypts > safe_radius)")
+    P, M = int(neg_mask.shape[0]), int(neg_mask.shape[1])
+    corr, lens = _check_corr_pairs(corr, lens, P, M)
+    if M > 128 or int(x.shape[1]) > 64 or P > 32:
+        raise ValueError("stacked loss: M <= 128 correspondences, C <= 64 channels, P <= 32 pairs")
+    total, scalars, dists, fp, an = _TrainLossFn.apply(
+        x, sc, corr, None, lens, neg_mask, True, P,
+        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)),
+        None)
+    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
 
 
 def train_contrastive_loss(x, scores, corr, p_offset, dist_keypts, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
@@ -2636,18 +2465,15 @@ def train_contrastive_loss(x, scores, corr, p_offset, dist_keypts, safe_radius=0
     ``w_desc * ContrastiveLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset], dist_keypts) + w_det *
     DetLoss(dists, ...)``.  Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only
     ``total`` carries gradient."""
-    x = _f32(x, "x")
-    sc = _f32(scores, "scores").reshape(-1, 1)
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
-        raise ValueError("corr must be an int64 [M,2] device tensor")
-    corr = corr.contiguous()
+    x, sc = _loss_inputs(x, scores)
+    corr = _check_corr(corr)
     M = int(corr.shape[0])
     if not 2 <= M <= 1024 or int(x.shape[1]) > 256:
         raise ValueError("contrastive loss: 2 <= M <= 1024 correspondences, C <= 256 channels")
     dk = _dk64(dist_keypts, (1, M, M), x.device) if dist_keypts.dim() == 3 else _dk64(dist_keypts, (M, M), x.device)
-    total, scalars, dists, fp, an = _TrainContrastiveFn.apply(
-        x, sc, corr, _p_offset(p_offset, x.device), None, dk, 1,
-        (float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)))
+    total, scalars, dists, fp, an = _TrainLossFn.apply(
+        x, sc, corr, _p_offset(p_offset, x.device), None, dk, False, 1,
+        (float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)), None)
     return total, scalars[0, 0], scalars[0, 1], scalars[0, 2], fp, an
 
 
@@ -2656,22 +2482,17 @@ def train_contrastive_loss_pairs(x, scores, corr, lens, dist_keypts, safe_radius
     """``train_loss_pairs`` with the contrastive loss: P stacked pairs, ``dist_keypts`` [P,M,M] (read as float64),
     total = sum_p (w_desc desc_p + w_det det_p).
     Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
-    x = _f32(x, "x")
-    sc = _f32(scores, "scores").reshape(-1, 1)
+    x, sc = _loss_inputs(x, scores)
     if dist_keypts.dim() != 3 or dist_keypts.shape[1] != dist_keypts.shape[2]:
         raise ValueError("dist_keypts must be [P,M,M]")
     P, M = int(dist_keypts.shape[0]), int(dist_keypts.shape[1])
     dk = _dk64(dist_keypts, (P, M, M), x.device)
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
-        raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
-    corr = corr.contiguous().view(P * M, 2)
-    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
-        raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
+    corr, lens = _check_corr_pairs(corr, lens, P, M)
     if not 2 <= M <= 1024 or int(x.shape[1]) > 256 or P > 32:
         raise ValueError("stacked contrastive loss: 2 <= M <= 1024, C <= 256 channels, P <= 32 pairs")
-    total, scalars, dists, fp, an = _TrainContrastiveFn.apply(
-        x, sc, corr, None, lens.contiguous(), dk, P, (float(safe_radius), float(pos_margin), float(neg_margin)),
-        (float(w_desc), float(w_det)))
+    total, scalars, dists, fp, an = _TrainLossFn.apply(
+        x, sc, corr, None, lens, dk, False, P, (float(safe_radius), float(pos_margin), float(neg_margin)),
+        (float(w_desc), float(w_det)), None)
     return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
 
 

@@ -120,32 +120,29 @@ def allreduce_mean_(flat, world_size, n_buckets=4, group=None, average=True):
     return flat
 
 
-class GuardedSGD:
-    """SGD with momentum + weight decay on flat buffers; the update is skipped (momentum untouched) when the
-    gradient holds a non-finite value -- the reference's guard (trainer.py:104-111) evaluated on the device.
-    On the GPU this is d3f_sgd_guarded_step (two launches, no host sync); the torch expression below is the same
-    arithmetic for host tensors (the gloo tests of the data-parallel logic)."""
+class _GuardedOptimizer:
+    """What GuardedSGD and GuardedAdam share: the hyper-parameters on the device with their host mirror, the gradient
+    scale, the skipped-step counters, the map from ``model.parameters()`` positions to the flat buffers and, for host
+    tensors (the gloo tests of the data-parallel logic), the lane sum and the guard."""
 
-    def __init__(self, flat, lr=0.01, momentum=0.98, weight_decay=1e-6):
-        self.flat = flat
-        self.buf = torch.zeros_like(flat.data)
+    _SCALE = None       # index of grad_scale in the hyper vector
+
+    def _init_state(self, hyper, dtype):
+        dev = self.flat.data.device
         # {scratch, skipped steps, OR of pair-status flags that caused a skip, number of those skips}
-        self.state = torch.zeros(4, dtype=torch.int32, device=flat.data.device)
-        # {lr, momentum, weight_decay} live on the device: the kernel reads them when it runs, so a schedule changes the
-        # step size of an already captured graph (a scalar argument would be frozen at capture)
-        self.hyper = torch.tensor([lr, momentum, weight_decay, 1.0], dtype=torch.float32, device=flat.data.device)
-        self._hyper = [float(lr), float(momentum), float(weight_decay), 1.0]
-        self.initial_lr = float(lr)
+        self.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        # the hyper-parameters live on the device: the kernels read them when they run, so a schedule changes the step
+        # size of an already captured graph (a scalar argument would be frozen at capture)
+        self._hyper = [float(v) for v in hyper]
+        self.hyper = torch.tensor(self._hyper, dtype=dtype, device=dev)
+        self.initial_lr = self._hyper[0]
 
     def _set(self, i, v):
         self._hyper[i] = float(v)
         self.hyper[i] = float(v)   # stream-ordered fill, no sync
 
-    lr = property(lambda self: self._hyper[0], lambda self, v: self._set(0, v))
-    momentum = property(lambda self: self._hyper[1], lambda self, v: self._set(1, v))
-    weight_decay = property(lambda self: self._hyper[2], lambda self, v: self._set(2, v))
     # the gradient is multiplied by this first: 1/world_size makes the mean out of an all-reduced SUM inside the step
-    grad_scale = property(lambda self: self._hyper[3], lambda self, v: self._set(3, v))
+    grad_scale = property(lambda self: self._hyper[self._SCALE], lambda self, v: self._set(self._SCALE, v))
 
     def use_grad_scale(self, v):
         """Make ``v`` the gradient scale of the steps launched from here on: 1 / (pairs whose gradients are summed into
@@ -155,13 +152,62 @@ class GuardedSGD:
         the device (an update still in flight on another stream must see the old value) -- rare, engines alternate only
         when a pair leaves the graph path."""
         v = float(v)
-        if self._hyper[3] == v:
+        if self._hyper[self._SCALE] == v:
             return
         if self.hyper.is_cuda:
             torch.cuda.synchronize(self.hyper.device)
         self.grad_scale = v
         if self.hyper.is_cuda:
             torch.cuda.current_stream(self.hyper.device).synchronize()
+
+    @property
+    def skipped(self):
+        return self.state[1]
+
+    def _slots(self):
+        """{position in ``model.parameters()``: (offset into the flat buffers, parameter)}, in flat order."""
+        slot, off = {}, 0
+        for idx, p in zip(self.flat.module_index, self.flat.params):
+            slot[idx] = (off, p)
+            off += p.numel()
+        return slot
+
+    def _check_param_count(self, group):
+        if len(group['params']) != self.flat.n_module_params:
+            raise ValueError("optimizer state covers %d parameters, the model has %d" % (
+                len(group['params']), self.flat.n_module_params))
+
+    def _host_gradient(self, grads, pair_status):
+        """Host tensors: (the fixed-order sum of the gradient lanes, 0-dim bool "apply the update").  A non-finite lane
+        makes the sum non-finite, so the sum alone is tested."""
+        lanes = [self.flat.grad] if grads is None else list(grads)
+        g = lanes[0].clone()
+        for other in lanes[1:]:
+            g += other
+        ok = torch.isfinite(g).all()
+        if pair_status is not None:
+            bad = pair_status.reshape(-1)[0] != 0
+            self.state[2] |= pair_status.reshape(-1)[0].to(self.state.dtype)
+            self.state[3] += bad.to(self.state.dtype)
+            ok = ok & ~bad
+        return g, ok
+
+
+class GuardedSGD(_GuardedOptimizer):
+    """SGD with momentum + weight decay on flat buffers; the update is skipped (momentum untouched) when the
+    gradient holds a non-finite value -- the reference's guard (trainer.py:104-111) evaluated on the device.
+    On the GPU this is d3f_sgd_guarded_step (two launches, no host sync); the torch expression below is the same
+    arithmetic for host tensors (the gloo tests of the data-parallel logic)."""
+
+    def __init__(self, flat, lr=0.01, momentum=0.98, weight_decay=1e-6):
+        self.flat = flat
+        self.buf = torch.zeros_like(flat.data)
+        self._init_state([lr, momentum, weight_decay, 1.0], torch.float32)   # {lr, momentum, weight_decay, grad_scale}
+
+    _SCALE = 3
+    lr = property(lambda self: self._hyper[0], lambda self, v: self._set(0, v))
+    momentum = property(lambda self: self._hyper[1], lambda self, v: self._set(1, v))
+    weight_decay = property(lambda self: self._hyper[2], lambda self, v: self._set(2, v))
 
     @property
     def param_groups(self):
@@ -172,25 +218,18 @@ class GuardedSGD:
     def state_dict(self):
         """Same layout as ``torch.optim.SGD.state_dict()`` over ``model.parameters()`` (what the reference snapshots,
         trainer.py:196): momentum buffers keyed by the parameter's position in ``model.parameters()``."""
-        state, off = {}, 0
-        for idx, p in zip(self.flat.module_index, self.flat.params):
-            state[idx] = {'momentum_buffer': self.buf[off:off + p.numel()].view_as(p).detach().clone()}
-            off += p.numel()
+        state = {idx: {'momentum_buffer': self.buf[off:off + p.numel()].view_as(p).detach().clone()}
+                 for idx, (off, p) in self._slots().items()}
         return {'state': state, 'param_groups': self.param_groups}
 
     def load_state_dict(self, sd):
         group = sd['param_groups'][0]
         if len(sd['param_groups']) != 1 or group.get('dampening', 0) != 0 or group.get('nesterov', False):
             raise ValueError("GuardedSGD loads a single-group torch.optim.SGD state without dampening / nesterov")
-        if len(group['params']) != self.flat.n_module_params:
-            raise ValueError("optimizer state covers %d parameters, the model has %d" % (
-                len(group['params']), self.flat.n_module_params))
+        self._check_param_count(group)
         self.lr, self.momentum, self.weight_decay = group['lr'], group['momentum'], group['weight_decay']
         self.initial_lr = float(group.get('initial_lr', self.initial_lr))
-        slot, off = {}, 0
-        for idx, p in zip(self.flat.module_index, self.flat.params):
-            slot[idx] = (off, p)
-            off += p.numel()
+        slot = self._slots()
         self.buf.zero_()   # a parameter without state has not been stepped yet: first step sets buf = d = 0*m + d
         for key, st in sd['state'].items():
             mb = st.get('momentum_buffer')
@@ -207,10 +246,6 @@ class GuardedSGD:
         """The tensors that make up the optimizer's state besides the parameters (a capture warm-up restores them)."""
         return self.buf, self.state
 
-    @property
-    def skipped(self):
-        return self.state[1]
-
     @torch.no_grad()
     def step(self, want_ok=True, pair_status=None, grads=None):
         """Returns a 0-dim bool tensor: True when the update was applied (None with want_ok=False: the training
@@ -219,23 +254,12 @@ class GuardedSGD:
         gradient came from; when it is set the update is skipped like for a non-finite gradient (a pyramid that
         outgrew a graph capacity, say, never reaches the parameters) and the flags are kept in ``state[2:4]``."""
         g = self.flat.grad if grads is None else list(grads)
-        on_gpu = (g if grads is None else g[0]).is_cuda
-        if grads is not None and not on_gpu:    # host tensors (gloo tests): the same fixed-order sum
-            total = g[0].clone()
-            for other in g[1:]:
-                total += other
-            g = total
-        if on_gpu:
+        if (g if grads is None else g[0]).is_cuda:
             before = self.state[1].clone() if want_ok else None
             ops.sgd_guarded_step(g, self.flat.data, self.buf, self.lr, self.momentum, self.weight_decay, self.state,
                                  hyper=self.hyper, pair_status=pair_status)
             return (self.state[1] == before) if want_ok else None
-        ok = torch.isfinite(g).all()
-        if pair_status is not None:
-            bad = pair_status.reshape(-1)[0] != 0
-            self.state[2] |= pair_status.reshape(-1)[0].to(self.state.dtype)
-            self.state[3] += bad.to(self.state.dtype)
-            ok = ok & ~bad
+        g, ok = self._host_gradient(grads, pair_status)
         if self.grad_scale != 1.0:
             g = g * self.grad_scale
         d = torch.add(g, self.flat.data, alpha=self.weight_decay)       # g + wd * p
@@ -246,7 +270,7 @@ class GuardedSGD:
         return ok
 
 
-class GuardedAdam:
+class GuardedAdam(_GuardedOptimizer):
     """torch.optim.Adam (amsgrad off, L2 weight decay) on flat buffers -- the reference's optimizer 'ADAM'
     (training_3DMatch.py:69-75) -- with GuardedSGD's interface and guard: a step whose gradient holds a non-finite value
     or whose pair was flagged leaves parameters, moments and the step counter untouched (the reference does not call
@@ -255,38 +279,18 @@ class GuardedAdam:
 
     def __init__(self, flat, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.flat = flat
-        dev = flat.data.device
         self.m = torch.zeros_like(flat.data)
         self.v = torch.zeros_like(flat.data)
-        self.t = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.state = torch.zeros(4, dtype=torch.int32, device=dev)   # as GuardedSGD.state
-        # {lr, beta1, beta2, eps, weight_decay, grad_scale} in f64 on the device (torch's Python floats), read by the
-        # kernels when they run: a schedule reaches an already captured graph
-        self._hyper = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 1.0]
-        self.hyper = torch.tensor(self._hyper, dtype=torch.float64, device=dev)
-        self.initial_lr = float(lr)
+        self.t = torch.zeros(1, dtype=torch.float32, device=flat.data.device)
+        # {lr, beta1, beta2, eps, weight_decay, grad_scale} in f64 (torch's Python floats)
+        self._init_state([lr, betas[0], betas[1], eps, weight_decay, 1.0], torch.float64)
 
-    def _set(self, i, v):
-        self._hyper[i] = float(v)
-        self.hyper[i] = float(v)   # stream-ordered fill, no sync
-
+    _SCALE = 5
     lr = property(lambda self: self._hyper[0], lambda self, v: self._set(0, v))
     betas = property(lambda self: (self._hyper[1], self._hyper[2]),
                      lambda self, v: (self._set(1, v[0]), self._set(2, v[1])))
     eps = property(lambda self: self._hyper[3], lambda self, v: self._set(3, v))
     weight_decay = property(lambda self: self._hyper[4], lambda self, v: self._set(4, v))
-    grad_scale = property(lambda self: self._hyper[5], lambda self, v: self._set(5, v))
-
-    def use_grad_scale(self, v):
-        """See GuardedSGD.use_grad_scale."""
-        v = float(v)
-        if self._hyper[5] == v:
-            return
-        if self.hyper.is_cuda:
-            torch.cuda.synchronize(self.hyper.device)
-        self.grad_scale = v
-        if self.hyper.is_cuda:
-            torch.cuda.current_stream(self.hyper.device).synchronize()
 
     def device_state(self):
         """The tensors that make up the optimizer's state besides the parameters (a capture warm-up restores them)."""
@@ -303,14 +307,13 @@ class GuardedAdam:
     def state_dict(self):
         """Same layout as ``torch.optim.Adam.state_dict()`` over ``model.parameters()``: per parameter ``step`` (a
         scalar f32 tensor), ``exp_avg`` and ``exp_avg_sq``; nothing for a parameter before its first step."""
-        state, off = {}, 0
+        state = {}
         t = float(self.t.item())
-        for idx, p in zip(self.flat.module_index, self.flat.params):
-            if t > 0:
+        if t > 0:
+            for idx, (off, p) in self._slots().items():
                 state[idx] = {'step': torch.tensor(t, dtype=torch.float32),
                               'exp_avg': self.m[off:off + p.numel()].view_as(p).detach().clone(),
                               'exp_avg_sq': self.v[off:off + p.numel()].view_as(p).detach().clone()}
-            off += p.numel()
         return {'state': state, 'param_groups': self.param_groups}
 
     def load_state_dict(self, sd):
@@ -321,13 +324,8 @@ class GuardedAdam:
         if group.get('amsgrad', False) or group.get('maximize', False) or group.get('decoupled_weight_decay', False):
             raise ValueError("GuardedAdam is Adam with L2 weight decay: amsgrad, maximize and decoupled weight decay "
                              "are not supported")
-        if len(group['params']) != self.flat.n_module_params:
-            raise ValueError("optimizer state covers %d parameters, the model has %d" % (
-                len(group['params']), self.flat.n_module_params))
-        slot, off = {}, 0
-        for idx, p in zip(self.flat.module_index, self.flat.params):
-            slot[idx] = (off, p)
-            off += p.numel()
+        self._check_param_count(group)
+        slot = self._slots()
         steps, moments = set(), []
         for key, st in sd['state'].items():
             if 'exp_avg' not in st or 'exp_avg_sq' not in st or 'step' not in st or 'max_exp_avg_sq' in st:
@@ -356,33 +354,16 @@ class GuardedAdam:
             self.v[off:off + p.numel()].copy_(st['exp_avg_sq'].reshape(-1))
         self.t.fill_(steps.pop() if steps else 0.0)
 
-    @property
-    def skipped(self):
-        return self.state[1]
-
     @torch.no_grad()
     def step(self, want_ok=True, pair_status=None, grads=None):
         """As GuardedSGD.step."""
         g = self.flat.grad if grads is None else list(grads)
-        on_gpu = (g if grads is None else g[0]).is_cuda
-        if on_gpu:
+        if (g if grads is None else g[0]).is_cuda:
             before = self.state[1].clone() if want_ok else None
             ops.adam_guarded_step(g, self.flat.data, self.m, self.v, self.t, self.hyper, self.state,
                                   pair_status=pair_status)
             return (self.state[1] == before) if want_ok else None
-        lanes = g if grads is not None else [g]
-        total = lanes[0].clone()
-        for other in lanes[1:]:
-            total += other
-        g = total
-        ok = torch.isfinite(g).all()
-        for lane in lanes:
-            ok = ok & torch.isfinite(lane).all()
-        if pair_status is not None:
-            bad = pair_status.reshape(-1)[0] != 0
-            self.state[2] |= pair_status.reshape(-1)[0].to(self.state.dtype)
-            self.state[3] += bad.to(self.state.dtype)
-            ok = ok & ~bad
+        g, ok = self._host_gradient(grads, pair_status)
         lr, b1, b2, eps, wd, gs = self._hyper
         p = self.flat.data
         if gs != 1.0:
@@ -639,43 +620,32 @@ class TrainStep:
 
     def _loss_from_raw(self, x, scores, batch):
         """Reference trainer.py:91-98 on the un-normalised descriptors: the 2M sampled rows are gathered and
-        normalised by one launch (the other rows never enter the loss)."""
+        normalised by one launch (the other rows never enter the loss).  desc_loss 'contrastive'
+        (training_3DMatch.py:119-125): the same select + normalise launches, then the contrastive + detector kernels on
+        the f64 keypoint distances (not the circle's mask)."""
         c = self.circle
-        if getattr(self, 'desc_loss', 'circle') == 'contrastive':
-            return self._contrastive_from_raw(x, scores, batch)
+        margins = (c.safe_radius, c.pos_margin, c.neg_margin, self.w_desc, self.w_det)
+        contrastive = getattr(self, 'desc_loss', 'circle') == 'contrastive'
         if batch.get('_pairs', 1) > 1:     # stacked pairs: every pair's own M x M problem, total = their sum
-            total, desc, det, acc, fp, an = ops.train_loss_pairs(
-                x, scores, batch['corr'], batch['stack_lengths'][0], None, c.log_scale, c.safe_radius, c.pos_margin,
-                c.neg_margin, self.w_desc, self.w_det, neg_mask=batch['neg_mask'])
-            self.last_distances = (fp, an)                     # [Q, M] each
-            self.last_pair_losses = (desc, det, acc)           # [Q] each
-            return total, desc, det, acc
-        n0 = batch['n0'] if 'n0' in batch else batch['stack_lengths'][0][:1]  # host int, or a device scalar (no sync)
-        loss, desc, det, acc, fp, an = ops.train_loss(x, scores, batch['corr'], n0, batch['dist_keypts'], c.log_scale,
-                                                      c.safe_radius, c.pos_margin, c.neg_margin, self.w_desc, self.w_det,
-                                                      neg_mask=batch.get('neg_mask'))
-        # per-row furthest-positive / average-negative distances [M] (trainer.py:99-100 averages them on the host);
-        # kept on the device for whoever wants the statistics -- no extra launches in the step itself
-        self.last_distances = (fp, an)
-        return loss, desc, det, acc
-
-    def _contrastive_from_raw(self, x, scores, batch):
-        """_loss_from_raw for desc_loss 'contrastive' (training_3DMatch.py:119-125): the same select + normalise
-        launches, then the contrastive + detector kernels on the f64 keypoint distances (not the circle's mask)."""
-        c = self.circle
-        if batch.get('_pairs', 1) > 1:
-            total, desc, det, acc, fp, an = ops.train_contrastive_loss_pairs(
-                x, scores, batch['corr'], batch['stack_lengths'][0], batch['dist_keypts'], c.safe_radius, c.pos_margin,
-                c.neg_margin, self.w_desc, self.w_det)
-            self.last_distances = (fp, an)
-            self.last_pair_losses = (desc, det, acc)
-            return total, desc, det, acc
-        n0 = batch['n0'] if 'n0' in batch else batch['stack_lengths'][0][:1]
-        loss, desc, det, acc, fp, an = ops.train_contrastive_loss(x, scores, batch['corr'], n0, batch['dist_keypts'],
-                                                                  c.safe_radius, c.pos_margin, c.neg_margin,
-                                                                  self.w_desc, self.w_det)
-        self.last_distances = (fp, an)
-        return loss, desc, det, acc
+            lens = batch['stack_lengths'][0]
+            if contrastive:
+                res = ops.train_contrastive_loss_pairs(x, scores, batch['corr'], lens, batch['dist_keypts'], *margins)
+            else:
+                res = ops.train_loss_pairs(x, scores, batch['corr'], lens, None, c.log_scale, *margins,
+                                           neg_mask=batch['neg_mask'])
+            self.last_pair_losses = res[1:4]                   # (desc, det, acc), [Q] each
+        else:
+            n0 = batch['n0'] if 'n0' in batch else batch['stack_lengths'][0][:1]  # host int, or a device scalar (no sync)
+            if contrastive:
+                res = ops.train_contrastive_loss(x, scores, batch['corr'], n0, batch['dist_keypts'], *margins)
+            else:
+                res = ops.train_loss(x, scores, batch['corr'], n0, batch['dist_keypts'], c.log_scale, *margins,
+                                     neg_mask=batch.get('neg_mask'))
+        # per-row furthest-positive / average-negative distances ([M]; [Q, M] for stacked pairs; trainer.py:99-100
+        # averages them on the host); kept on the device for whoever wants the statistics -- no extra launches in the
+        # step itself
+        self.last_distances = res[4:6]
+        return res[:4]
 
     @torch.no_grad()
     def evaluate(self, item):
