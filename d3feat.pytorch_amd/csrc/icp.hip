@@ -1,0 +1,358 @@
+// Batched point-to-point ICP over a LIST of cloud pairs of one cell list -- the refinement after RANSAC
+// (geometric_registration/registration.py; the reference leaves it to Open3D on the CPU).  All P pairs advance together,
+// without host synchronisation and with a launch sequence that does not depend on the data: one setup launch, then per
+// iteration a search launch and a fit launch.
+//
+// CONVENTION (easy to get backwards).  Pair p = (MOVING cloud a, FIXED cloud b) and T_p maps points of a into b's frame
+// -- exactly the (source, target, transform) of d3f_nearest_pairs.  For a gt.log key i_j, whose matrix maps fragment j
+// into fragment i (what d3f_ransac_rigid returns: "target onto source"), the moving cloud is j and the fixed cloud is i:
+// a RANSAC result is a valid T_init as it stands with pairs = (j, i).
+//
+// The search of iteration k is nearest_pairs.hip's, word for word (pair_search.hpp: one statement of q, d2, the
+// acceptance and the tie rule serves both kernels).  That kernel is bound by the cache lines it asks the L2 for, not by
+// its lanes, so the sums the fit needs ride in the same pass: the lane whose candidate wins its group's minimum still
+// holds that candidate's coordinates and adds, in f64, n, sum x', sum y', sum x' y'^T and sum d2 to its own 17
+// accumulators (x' = x - px, y' = y - py; the pivots px, py are row 0 of the moving / fixed cloud -- nothing promises
+// clouds near the origin, and the raw second moment of clouds at (300, -200, 50) costs 1e-8 in t).  No index is written.
+//
+// Determinism and batch independence.  There is no floating-point atomic.  A workgroup serves kRows consecutive rows of
+// ONE pair (block blk belongs to the pair p with first(p) <= blk < first(p + 1), first(p) = row_start[p] / kRows + p:
+// a prefix that needs no scan and leaves every pair at least the cdiv(len, kRows) blocks it needs); a lane adds its rows
+// in slice order, the wave is reduced by a fixed butterfly (DPP / permlane swaps, common.hpp), the 8 waves in wave order
+// through LDS, and the pair's workgroups are added by one wave in the order lane = block mod 64, blocks ascending, then
+// the same butterfly.  Every order depends on the pair's length alone, so a pair's sums -- and with them its whole
+// trajectory -- are bit-identical alone, inside any batch, and from run to run.
+#include "pair_search.hpp"
+#include "rigid.hpp"
+
+namespace {
+
+using namespace d3f::cells;
+
+constexpr int kBlock = 512;
+constexpr int kG = 8;                                // lanes per query, nearest_pairs.hip's default
+constexpr int kRows = D3F_ICP_BLOCK_ROWS;            // rows per workgroup
+constexpr int kRowsPerSlice = (kBlock / 64) * (64 / kG);
+constexpr int kSlices = kRows / kRowsPerSlice;
+constexpr int kSums = 17;
+constexpr int kMaxClouds = 65535;
+static_assert(kRows % kRowsPerSlice == 0, "a workgroup serves whole slices");
+
+struct IcpArgs {
+  const float* points;
+  const int32_t* cloud_start;
+  const int32_t* pairs;
+  const int64_t* row_start;
+  const int32_t* placement;   // cell_list.hpp: 0 = one hashed table, 1 = per-cloud tables
+  CellSearch S;               // pair_search.hpp
+  const double* T_init;       // [P,12]
+  double* T_cur;              // [P,12] ws: T_k
+  double* prev;               // [P,2]  ws: fitness_{k-1}, rmse_{k-1}
+  int32_t* done;              // [P]    ws: the pair has stopped
+  double* partial;            // [blocks,17] ws
+  double* T;
+  int32_t* count;
+  double* rmse;
+  int32_t* iterations;
+  int32_t* status;
+  double* trace;
+  double rel_fitness, rel_rmse;
+  long long rows;
+  int B, P, Ns, max_iters;
+};
+
+__device__ __forceinline__ long long first_block(const IcpArgs& A, int p) { return A.row_start[p] / kRows + p; }
+
+// rows of pair p that are searched: its segment of row_start, at most the moving cloud's length (a valid pair only)
+__device__ __forceinline__ long long pair_rows(const IcpArgs& A, int p, int a) {
+  const long long seg = A.row_start[p + 1] - A.row_start[p], len = A.cloud_start[a + 1] - A.cloud_start[a];
+  const long long m = seg < len ? seg : len;
+  return m > 0 ? m : 0;
+}
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+  return __longlong_as_double((long long)d3f::shfl_xor_u64((uint64_t)__double_as_longlong(v), m));
+}
+
+__device__ __forceinline__ void wave_sum17(double v[kSums]) {
+#pragma unroll
+  for (int k = 0; k < kSums; ++k)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v[k] += shfl_xor_f64(v[k], o);
+}
+
+__device__ __forceinline__ void write_pose(double* __restrict__ o, const double* __restrict__ rt) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) o[k] = rt[k];
+  o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
+}
+
+__global__ void icp_setup_kernel(const IcpArgs A) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (A.trace) {
+    const long long n = 2ll * A.P * (A.max_iters + 1);
+    for (long long k = i; k < n; k += (long long)gridDim.x * blockDim.x) A.trace[k] = __longlong_as_double(0x7ff8000000000000ll);
+  }
+  if (i >= A.P) return;
+  const int p = (int)i;
+  const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
+  int st = 0;
+  if (!((unsigned)a < (unsigned)A.B && (unsigned)b < (unsigned)A.B) || A.row_start[p] < 0 ||
+      A.row_start[p + 1] < A.row_start[p] || A.row_start[p + 1] > A.rows)
+    st |= D3F_ICP_ST_PAIR;
+  bool finite = true;
+  for (int k = 0; k < 12; ++k) {
+    const double v = A.T_init[12 * (size_t)p + k];
+    A.T_cur[12 * (size_t)p + k] = v;
+    finite = finite && isfinite(v);
+  }
+  if (!finite) st |= D3F_ICP_ST_NONFINITE;
+  A.prev[2 * p] = 0.0;
+  A.prev[2 * p + 1] = 0.0;
+  A.done[p] = st != 0;
+  A.status[p] = st;
+  A.iterations[p] = 0;
+  if (st) {   // never searched: the result is T_init
+    write_pose(A.T + 16 * (size_t)p, A.T_init + 12 * (size_t)p);
+    A.count[p] = 0;
+    A.rmse[p] = 0.0;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
+  const int lane = threadIdx.x & 63, sub = lane & (kG - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // the pair of this workgroup: the largest p with first_block(p) <= blockIdx.x (first_block(0) = 0)
+  const long long blk = blockIdx.x;
+  int p = 0, hi = A.P;
+  while (hi - p > 1) {
+    const int mid = p + ((hi - p) >> 1);
+    if (first_block(A, mid) <= blk) p = mid; else hi = mid;
+  }
+  if (A.done[p]) return;   // (everything up to the barrier below is uniform over the workgroup)
+  const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];   // in [0, B): the setup launch stopped the others
+  const long long m = pair_rows(A, p, a), row0 = (blk - first_block(A, p)) * kRows;
+  if (row0 < 0 || row0 >= m) return;   // a block of the prefix's slack
+  const int sa = A.cloud_start[a], tgt0 = A.cloud_start[b], tgt_n = A.cloud_start[b + 1] - tgt0;
+  const bool per_cloud = *A.placement != 0;
+  const double cell = 1.0 / A.S.inv_cell, reach = (double)A.S.prune_r * (1.0 + 1e-4);
+  const double* T = A.T_cur + 12 * (size_t)p;
+  const bool pivots = tgt_n > 0 && (long long)sa < (long long)A.Ns && (long long)tgt0 < (long long)A.Ns;
+  double px[3] = {0.0, 0.0, 0.0}, py[3] = {0.0, 0.0, 0.0};
+  if (pivots) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      px[k] = (double)A.points[3 * (size_t)sa + k];
+      py[k] = (double)A.points[3 * (size_t)tgt0 + k];
+    }
+  }
+
+  double acc[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
+  for (int it = 0; it < kSlices; ++it) {
+    const long long i = row0 + it * kRowsPerSlice + wave * (64 / kG) + lane / kG;
+    bool ok = pivots && i < m && sa + i < (long long)A.Ns;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (ok) {
+      const size_t src = (size_t)(sa + i);
+      x = (double)A.points[3 * src + 0];
+      y = (double)A.points[3 * src + 1];
+      z = (double)A.points[3 * src + 2];
+    }
+    uint64_t mine;
+    float4 win;
+    const uint64_t best =
+        nearest_in_cloud<kG>(A.S, ok, x, y, z, T, b, tgt0, tgt_n, per_cloud, cell, reach, sub, A.status + p, mine, win);
+    if (ok && best != ~0ull && mine == best) {   // the one lane of the group that holds the winner
+      const double xd[3] = {x - px[0], y - px[1], z - px[2]};
+      const double yd[3] = {(double)win.x - py[0], (double)win.y - py[1], (double)win.z - py[2]};
+      acc[0] += 1.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        acc[1 + k] += xd[k];
+        acc[4 + k] += yd[k];
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[7 + 3 * r + c] += xd[r] * yd[c];
+      acc[16] += (double)__uint_as_float((uint32_t)(best >> 32));
+    }
+  }
+  wave_sum17(acc);
+  __shared__ double red[kBlock / 64][kSums];
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    double s = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
+    A.partial[(size_t)blk * kSums + threadIdx.x] = s;
+  }
+}
+
+// one wave per pair: the pair's block sums in a fixed order, the stopping rule, the fit
+__global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  if (A.done[p]) return;
+  const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
+  const long long m = pair_rows(A, p, a), nblk = (m + kRows - 1) / kRows, first = first_block(A, p);
+  double v[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+  for (long long j = lane; j < nblk; j += 64) {
+    const double* part = A.partial + (size_t)(first + j) * kSums;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) v[k] += part[k];
+  }
+  wave_sum17(v);
+  if (lane != 0) return;
+  const int sa = A.cloud_start[a], len_a = A.cloud_start[a + 1] - sa, tgt0 = A.cloud_start[b];
+  const double n = v[0], sd2 = v[16];
+  const double fitness = len_a > 0 ? n / (double)len_a : 0.0, rmse = n > 0.0 ? sqrt(sd2 / n) : 0.0;
+  if (A.trace) {
+    double* tr = A.trace + 2 * ((size_t)p * (A.max_iters + 1) + k_iter);
+    tr[0] = n;
+    tr[1] = sd2;
+  }
+  double* T = A.T_cur + 12 * (size_t)p;
+  bool stop = false;
+  if (n < 3.0) {
+    atomicOr(A.status + p, D3F_ICP_ST_FEW);
+    stop = true;
+  } else if (k_iter >= 1 && fabs(fitness - A.prev[2 * p]) < A.rel_fitness && fabs(rmse - A.prev[2 * p + 1]) < A.rel_rmse) {
+    stop = true;
+  } else if (k_iter >= A.max_iters) {
+    stop = true;
+  }
+  if (stop) {
+    write_pose(A.T + 16 * (size_t)p, T);
+    A.count[p] = (int)n;
+    A.rmse[p] = rmse;
+    A.done[p] = 1;
+    return;
+  }
+  double px[3], py[3], R[9], t[3];   // (n >= 3: both clouds have a row 0 inside the stack, the search read it)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    px[k] = (double)A.points[3 * (size_t)sa + k];
+    py[k] = (double)A.points[3 * (size_t)tgt0 + k];
+  }
+  d3f::rigid::fit_from_sums(v, px, py, R, t);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    T[4 * r] = R[3 * r];
+    T[4 * r + 1] = R[3 * r + 1];
+    T[4 * r + 2] = R[3 * r + 2];
+    T[4 * r + 3] = t[r];
+  }
+  A.prev[2 * p] = fitness;
+  A.prev[2 * p + 1] = rmse;
+  A.iterations[p] = k_iter + 1;
+}
+
+struct IcpLayout {
+  double* T_cur;
+  double* prev;
+  int32_t* done;
+  double* partial;
+  long long blocks;
+  size_t bytes;
+};
+
+IcpLayout icp_layout(void* ws, int P, long long rows) {
+  IcpLayout l;
+  const size_t n = (size_t)(P > 0 ? P : 1);
+  l.blocks = (rows > 0 ? rows : 0) / kRows + (long long)n + 1;
+  d3f::Carver c(ws);
+  l.T_cur = c.take<double>(12 * n);
+  l.prev = c.take<double>(2 * n);
+  l.done = c.take<int32_t>(n);
+  l.partial = c.take<double>((size_t)l.blocks * kSums);
+  l.bytes = d3f::align_up(c.off, 256);
+  return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t d3f_icp_rigid_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows).bytes; }
+
+int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                  float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                  int64_t rows, const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T,
+                  int32_t* count, double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws,
+                  size_t ws_bytes, void* stream_) {
+  if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
+      rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) || max_iters < 0 ||
+      max_iters > D3F_ICP_MAX_ITERS || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0) ||
+      (P > 0 && (!pairs || !T_init || !T || !count || !rmse || !iterations || !status || !ws)))
+    return D3F_EINVAL;
+  if (P == 0) return D3F_OK;
+  if (ws_bytes < d3f_icp_rigid_ws_bytes(P, rows)) return D3F_EWORKSPACE;
+  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
+  IcpLayout l = icp_layout(ws, P, rows);
+  IcpArgs a;
+  a.points = points;
+  a.cloud_start = cloud_start;
+  a.pairs = pairs;
+  a.row_start = row_start;
+  a.placement = g.cnt + g.M + kPlacementWord;
+  a.S.start = g.start;
+  a.S.end = g.end;
+  a.S.pts = g.pts;
+  a.S.key = g.key;
+  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
+  a.S.r2 = max_distance * max_distance;                      // float32 product, like d3f_nearest_pairs
+  a.S.prune_r = max_distance;
+  a.S.mask = g.M - 1;
+  a.T_init = T_init;
+  a.T_cur = l.T_cur;
+  a.prev = l.prev;
+  a.done = l.done;
+  a.partial = l.partial;
+  a.T = T;
+  a.count = count;
+  a.rmse = rmse;
+  a.iterations = iterations;
+  a.status = status;
+  a.trace = trace;
+  a.rel_fitness = rel_fitness;
+  a.rel_rmse = rel_rmse;
+  a.rows = rows;
+  a.B = B;
+  a.P = P;
+  a.Ns = Ns;
+  a.max_iters = max_iters;
+  hipStream_t stream = (hipStream_t)stream_;
+  const long long fill = trace ? 2ll * P * (max_iters + 1) : P;
+  long long setup_blocks = ((fill > P ? fill : P) + 255) / 256;
+  if (setup_blocks > 4096) setup_blocks = 4096;
+  if (setup_blocks < (P + 255) / 256) setup_blocks = (P + 255) / 256;
+  icp_setup_kernel<<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
+  D3F_LAUNCH_CHECK();
+  for (int k = 0; k <= max_iters; ++k) {
+    icp_search_kernel<<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
+    icp_fit_kernel<<<(unsigned)P, 64, 0, stream>>>(a, k);
+  }
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_icp_fit_host(const double* sums_host, const double* px_host, const double* py_host, double* out_host) {
+  if (!sums_host || !px_host || !py_host || !out_host || !(sums_host[0] >= 1.0)) return D3F_EINVAL;
+  double R[9], t[3];
+  d3f::rigid::fit_from_sums(sums_host, px_host, py_host, R, t);
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) out_host[4 * a + b] = R[3 * a + b];
+    out_host[4 * a + 3] = t[a];
+  }
+  out_host[12] = 0.0; out_host[13] = 0.0; out_host[14] = 0.0; out_host[15] = 1.0;
+  return D3F_OK;
+}
+
+}  // extern "C"

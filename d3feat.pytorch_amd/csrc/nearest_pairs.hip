@@ -22,7 +22,7 @@
 // 60-fragment scene (profiles/nearest_pairs_bench.txt): 4, 8 and 16 lanes are within 4 % of each other (15.0 / 15.2 /
 // 15.5 ms for 42 M queries), 32 lanes 13 % behind -- the kernel is bound by the number of cache lines it asks the L2
 // for (two 4-byte headers per cell out of two arrays, 24 B per candidate out of two more), not by its lanes.
-#include "cell_list.hpp"
+#include "pair_search.hpp"
 
 namespace {
 
@@ -32,26 +32,7 @@ using d3f::shfl_xor_u64;
 constexpr int kBlock = 512;   // 8 waves share one add to out_count
 constexpr int kMaxClouds = 65535;   // the cell key keeps the cloud index in 16 bits
 
-// largest p in [lo, n - 1] with pre[p] <= r, for a non-decreasing prefix pre[0..n] with pre[lo] <= r < pre[n]
-template <typename T>
-__device__ __forceinline__ int prefix_find(const T* __restrict__ pre, int lo, int n, long long r) {
-  int hi = n;
-  while (hi - lo > 1) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if ((long long)pre[mid] <= r) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 constexpr uint64_t kNoKey = ~0ull;   // no cell key has the cloud field 65535 (B <= kMaxClouds)
-
-// cell coordinate as cell_coord computes it, or false when it (or a neighbour cell) cannot be keyed
-__device__ __forceinline__ bool query_cell(float v, double inv_cell, int& c) {
-  const double f = floor((double)v * inv_cell);
-  const bool ok = f >= -32767.0 && f <= 32766.0;   // false for NaN too
-  c = ok ? (int)f : 0;
-  return ok;
-}
 
 __global__ void cloud_count_kernel(const float* __restrict__ s, int Ns, const int32_t* __restrict__ cloud_start, int B,
                                    double inv_cell, uint32_t mask, int32_t* __restrict__ cnt,
@@ -96,30 +77,23 @@ struct PairArgs {
   const int32_t* pairs;
   const double* transforms;
   const int64_t* row_start;
-  const int32_t* start;
-  const int32_t* end;
   const int32_t* placement;   // cell_list.hpp: 0 = one hashed table, 1 = per-cloud tables
-  const float4* pts;
-  const uint64_t* key;
   int32_t* out_nn;
   int32_t* out_count;
   int32_t* status;
-  double inv_cell;
+  CellSearch S;   // pair_search.hpp
   long long rows;
   int B, P, Ns, iters;
-  float r2, prune_r;
-  uint32_t mask;
 };
 
 template <int G>
 __global__ __launch_bounds__(kBlock) void nearest_pairs_kernel(const PairArgs A) {
-  constexpr int kCells = (27 + G - 1) / G;   // cells per lane
   constexpr int kRowsPerWave = 64 / G, kRowsPerBlock = (kBlock / 64) * kRowsPerWave;
   const int lane = threadIdx.x & 63, sub = lane & (G - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long total = A.row_start[A.P] < A.rows ? A.row_start[A.P] : A.rows;   // rows is out_nn's capacity
   const bool per_cloud = *A.placement != 0;
-  const double cell = 1.0 / A.inv_cell, reach = (double)A.prune_r * (1.0 + 1e-4);
+  const double cell = 1.0 / A.S.inv_cell, reach = (double)A.S.prune_r * (1.0 + 1e-4);
   // a workgroup serves A.iters consecutive slices of kRowsPerBlock rows: the pair of a wave's first row is searched for
   // once and then followed, and the hits of a pair are added to out_count once per wave and pair, not once per slice
   // (thousands of waves adding to ONE word each slice serialise on it: 12 of 17 ms of a scene went there)
@@ -149,75 +123,16 @@ __global__ __launch_bounds__(kBlock) void nearest_pairs_kernel(const PairArgs A)
       tgt_n = A.cloud_start[b + 1] - tgt0;
     }
 
-    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-    int cx = 0, cy = 0, cz = 0;
+    double x = 0.0, y = 0.0, z = 0.0;
     if (ok) {
-      const double x = (double)A.points[3 * (size_t)src + 0], y = (double)A.points[3 * (size_t)src + 1],
-                   z = (double)A.points[3 * (size_t)src + 2];
-      const double* T = A.transforms + 12 * (size_t)p;
-      qx = (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);   // (-ffp-contract=off: no FMA)
-      qy = (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]);
-      qz = (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]);
-      const bool in_x = query_cell(qx, A.inv_cell, cx), in_y = query_cell(qy, A.inv_cell, cy),
-                 in_z = query_cell(qz, A.inv_cell, cz);
-      if (!(in_x && in_y && in_z)) {
-        if (sub == 0) atomicOr(A.status, D3F_ST_CELL_RANGE);
-        ok = false;
-      }
+      x = (double)A.points[3 * (size_t)src + 0];
+      y = (double)A.points[3 * (size_t)src + 1];
+      z = (double)A.points[3 * (size_t)src + 2];
     }
-
-    // bucket headers of this lane's cells first (independent loads).  A cell whose box is farther from the query than
-    // the radius holds no accepted point and is skipped (same margin as radius_query_kernel).
-    uint64_t nk[kCells];
-    int st[kCells], len[kCells];
-    int longest = 0;
-#pragma unroll
-    for (int c = 0; c < kCells; ++c) {
-      const int k = sub + c * G;
-      st[c] = len[c] = 0;
-      nk[c] = 0;
-      if (ok && tgt_n > 0 && k < 27) {
-        const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-        auto gap = [&](float v, int cc) -> double {
-          const double lo = (double)cc * cell, hi = lo + cell, xx = (double)v;
-          return xx < lo ? lo - xx : (xx > hi ? xx - hi : 0.0);
-        };
-        const double gx = gap(qx, cx + dx), gy = gap(qy, cy + dy), gz = gap(qz, cz + dz);
-        if (gx * gx + gy * gy + gz * gz <= reach * reach) {
-          nk[c] = pack_key(b, cx + dx, cy + dy, cz + dz);
-          const uint32_t bk = per_cloud ? bucket_of_cloud(nk[c], 2u * tgt0, 2u * tgt_n) : bucket_of(nk[c], A.mask);
-          st[c] = A.start[bk];
-          len[c] = A.end[bk] - st[c];
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < kCells; ++c) longest = len[c] > longest ? len[c] : longest;
-    // the lane's buckets side by side: entry t of each of them is loaded before any is looked at, so a step costs one
-    // memory latency, not one per cell (an exhausted bucket re-reads entry 0 of the list, which its key check discards)
-    uint64_t best = ~0ull;
-    for (int t = 0; t < longest; ++t) {
-      uint64_t kk[kCells];
-      float4 sp[kCells];
-#pragma unroll
-      for (int c = 0; c < kCells; ++c) {
-        const int pos = t < len[c] ? st[c] + t : 0;
-        kk[c] = A.key[pos];
-        sp[c] = A.pts[pos];
-      }
-#pragma unroll
-      for (int c = 0; c < kCells; ++c) {
-        const float d2 = d3f::sqdist_exact(qx, qy, qz, sp[c].x, sp[c].y, sp[c].z);
-        const uint64_t packed = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(sp[c].w);
-        // (kk == nk: not another cell hashed into the same bucket)
-        if (t < len[c] && kk[c] == nk[c] && d2 < A.r2 && packed < best) best = packed;
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) {
-      const uint64_t other = shfl_xor_u64(best, o);
-      best = other < best ? other : best;
-    }
+    uint64_t mine;
+    float4 win;   // (the winner's coordinates: the ICP kernel's sums want them, nothing here does)
+    const uint64_t best = nearest_in_cloud<G>(A.S, ok, x, y, z, A.transforms + 12 * (size_t)p, b, tgt0, tgt_n, per_cloud,
+                                              cell, reach, sub, A.status, mine, win);
     const bool found = live && sub == 0 && best != ~0ull;
     if (live && sub == 0) A.out_nn[r] = found ? (int32_t)(uint32_t)best - tgt0 : -1;
 
@@ -321,22 +236,22 @@ int d3f_nearest_pairs_lanes(const void* grid_ws, const float* points, int Ns, co
   a.pairs = pairs;
   a.transforms = transforms;
   a.row_start = row_start;
-  a.start = g.start;
-  a.end = g.end;
+  a.S.start = g.start;
+  a.S.end = g.end;
   a.placement = g.cnt + g.M + kPlacementWord;
-  a.pts = g.pts;
-  a.key = g.key;
+  a.S.pts = g.pts;
+  a.S.key = g.key;
   a.out_nn = out_nn;
   a.out_count = out_count;
   a.status = status;
-  a.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
+  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
   a.rows = rows;
   a.B = B;
   a.P = P;
   a.Ns = Ns;
-  a.r2 = radius * radius;   // float32 product, like the radius search
-  a.prune_r = radius;
-  a.mask = g.M - 1;
+  a.S.r2 = radius * radius;   // float32 product, like the radius search
+  a.S.prune_r = radius;
+  a.S.mask = g.M - 1;
   hipStream_t stream = (hipStream_t)stream_;
   switch (lanes) {
     case 4: launch_pairs<4>(a, stream); break;

@@ -129,6 +129,34 @@ D3F_HD inline void fit(const double* src, const double* tgt, int n, double R[9],
   translation(R, cs, ct, t);
 }
 
+// The ICP step's fit from sums over the accepted correspondences (icp.hip; d3f_icp_fit_host): y ~ R x + t for moving
+// points x and fixed points y, given about pivots px, py as
+//   sums[17] = { n, sum x' (3), sum y' (3), sum x'_a y'_b (9, row-major in a), sum d2 }   x' = x - px, y' = y - py.
+// Centroids cx = sum x' / n, cy = sum y' / n; S[3a+b] = sum x'_a y'_b - n cx_a cy_b is the cross-covariance of the
+// centred points, handed to rotation_from_covariance with the moving cloud in its "target" role and the fixed cloud in
+// its "source" role; t = (cy + py) - R (cx + px).  n >= 1.
+D3F_HD inline void fit_from_sums(const double sums[17], const double px[3], const double py[3], double R[9],
+                                 double t[3]) {
+  const double n = sums[0];
+  double cx[3], cy[3], S[9], cs[3], ct[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    cx[a] = sums[1 + a] / n;
+    cy[a] = sums[4 + a] / n;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) S[3 * a + b] = sums[7 + 3 * a + b] - n * cx[a] * cy[b];
+  rotation_from_covariance(S, R);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    cs[a] = cy[a] + py[a];
+    ct[a] = cx[a] + px[a];
+  }
+  translation(R, cs, ct, t);
+}
+
 // Minimal-set checks of a drawn triple (points as doubles, exact images of the f32 inputs):
 //   distinct indices; both triangles non-degenerate: |(b - a) x (c - a)|^2 >= kMinCross2;
 //   edge_ratio > 0: for each of the 3 edges, with squared lengths la2 (source) and lb2 (target),

@@ -10,9 +10,14 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``loadinfo`` / ``transformation_error`` / ``evaluate_registration``  the benchmark's ``gt.info`` files and its
   registration recall / precision (error p <= 0.2^2 under the 6x6 information matrix, pairs with j - i > 1);
 * ``register_scene``                  every pair listed in ``gt.log`` from the dumped files, estimates written in the
-  ``gt.log`` format (``evaluate.writelog``).
+  ``gt.log`` format (``evaluate.writelog``);
+* ``refine_transforms`` / ``icp_numpy``  point-to-point ICP over the whole fragments after RANSAC (``ops.icp_rigid``, all
+  pairs of a scene in one call) and its NumPy restatement -- ``estimate_transform`` / ``register_scene`` run it when
+  given ``icp=dict(max_distance=...)``.
 
-Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.
+Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
+target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
+``pairs = (j, i)`` with the ``gt.log`` matrix as it stands.
 """
 import os
 
@@ -24,6 +29,7 @@ from . import evaluate as ev
 from .common import select_keypoints
 
 RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0)
+ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8      # ops.ICP_ST_*
 
 
 def _compact(mutual, src_pts, tgt_pts):
@@ -59,14 +65,18 @@ def _pair_points(source_keypts, source_desc, source_score, target_keypts, target
 
 
 def estimate_transform(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
-                       num_points=5000, **ransac):
+                       num_points=5000, icp=None, **ransac):
     """One fragment pair (device tensors): top-k keypoints by score, mutual nearest neighbours, RANSAC.  Returns device
     tensors ``(T [4,4] f64, inliers, num_matches)``; T maps the target into the source frame.  ``ransac``: keywords of
-    ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS)."""
+    ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS).  ``icp``: None, or a dict of ``refine_transforms`` keywords (at
+    least ``max_distance``): the RANSAC pose is then refined by ICP over ALL points of the two fragments."""
     mutual, sp, tp = _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
                                   num_points)
     src, tgt, seg, n = _compact(mutual.view(1, -1), sp.unsqueeze(0), tp.unsqueeze(0))
     T, inl = _ransac(src, tgt, seg, ransac)[:2]
+    if icp is not None:
+        T = refine_transforms([source_keypts, target_keypts], [(0, 1)], T, device=source_keypts.device,
+                              **_icp_keywords(icp))[0]
     return T[0], inl[0], n[0]
 
 
@@ -88,6 +98,118 @@ def estimate_transforms_from_match(points, seg, row, mutual, sel, **ransac):
     src, tgt, sg, n = _compact(m, pts[src_rows.reshape(-1)].view(P, k, 3), pts[tgt_rows.reshape(-1)].view(P, k, 3))
     T, inl = _ransac(src, tgt, sg, ransac)[:2]
     return T, inl, n
+
+
+# ------------------------------------------------------------------------------------------------- ICP refinement
+def _pose44(T, P):
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape not in ((P, 4, 4), (P, 3, 4)):
+        raise ValueError("T must be [P,4,4] or [P,3,4] for the %d pairs, got %s" % (P, T.shape))
+    out = np.tile(np.eye(4), (P, 1, 1))
+    out[:, :3, :] = T[:, :3, :]
+    return out
+
+
+def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6, return_trace=False):
+    """The contract of ``ops.icp_rigid`` in NumPy f64 (include/d3feat_hip.h): the ``device='cpu'`` path of
+    ``refine_transforms`` and the oracle of the GPU tests.  ``clouds``: list of [n,3] f32 arrays; pair p = (moving cloud
+    a, fixed cloud b), ``T_init[p]`` maps a into b's frame.  The search is ``preprocess.transform_points`` /
+    ``nearest_within``; the fit is the SVD solution of the same least-squares problem the kernel solves with Horn's
+    quaternions.  Returns ``(T [P,4,4], count int32 [P], rmse [P], iterations int32 [P], status int32 [P])`` and, with
+    ``return_trace``, ``trace [P, max_iters+1, 2]`` = (n_k, sum d2_k), NaN beyond the stop."""
+    from ..datasets.preprocess import nearest_within, transform_points
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    P, K = pairs.shape[0], int(max_iters)
+    if K < 0:
+        raise ValueError("max_iters must be >= 0")
+    T = _pose44(T_init, P)
+    count, iters, status = (np.zeros(P, dtype=np.int32) for _ in range(3))
+    rmse = np.zeros(P, dtype=np.float64)
+    trace = np.full((P, K + 1, 2), np.nan)
+    for p, (a, b) in enumerate(pairs):
+        if not (0 <= a < len(clouds) and 0 <= b < len(clouds)):
+            status[p] |= ICP_ST_PAIR
+        if not np.isfinite(T[p, :3]).all():
+            status[p] |= ICP_ST_NONFINITE
+        if status[p]:
+            continue
+        x = np.ascontiguousarray(clouds[a], dtype=np.float32).reshape(-1, 3)
+        y = np.ascontiguousarray(clouds[b], dtype=np.float32).reshape(-1, 3)
+        prev = (0.0, 0.0)
+        for k in range(K + 1):
+            q = transform_points(x, T[p])
+            nn = nearest_within(q, y, max_distance)
+            sel = nn >= 0
+            n = int(sel.sum())
+            ym = y[nn[sel]]
+            d = q[sel] - ym                                              # f32, the kernel's d2
+            d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            sd2 = float(d2.astype(np.float64).sum())
+            fitness = n / x.shape[0] if x.shape[0] else 0.0
+            r = float(np.sqrt(sd2 / n)) if n else 0.0
+            trace[p, k] = (n, sd2)
+            count[p], rmse[p] = n, r
+            if n < 3:
+                status[p] |= ICP_ST_FEW
+                break
+            if k >= 1 and abs(fitness - prev[0]) < rel_fitness and abs(r - prev[1]) < rel_rmse:
+                break
+            if k == K:
+                break
+            px, py = x[0].astype(np.float64), y[0].astype(np.float64)    # pivots: row 0 of either cloud
+            xs, ys = x[sel].astype(np.float64) - px, ym.astype(np.float64) - py
+            cx, cy = xs.mean(0), ys.mean(0)
+            U, _, Vt = np.linalg.svd((xs - cx).T @ (ys - cy))            # S[a,b] = sum moving'_a fixed'_b
+            D = np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T)) or 1.0])
+            R = Vt.T @ D @ U.T                                           # y ~ R x + t
+            T[p, :3, :3] = R
+            T[p, :3, 3] = (cy + py) - R @ (cx + px)
+            prev = (fitness, r)
+            iters[p] = k + 1
+    res = (T, count, rmse, iters, status)
+    return res + (trace,) if return_trace else res
+
+
+def _icp_keywords(icp):
+    if not isinstance(icp, dict) or 'max_distance' not in icp:
+        raise ValueError("icp must be None or a dict of refine_transforms keywords with at least max_distance")
+    return dict(icp)
+
+
+def _pair_list(keys_or_pairs):
+    out = []
+    for k in keys_or_pairs:
+        i, j = (k.split('_') if isinstance(k, str) else k)
+        out.append((int(i), int(j)))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 2)
+
+
+def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', **icp):
+    """Point-to-point ICP refinement of fragment-pair poses, all pairs in ONE ``ops.icp_rigid`` call over one
+    ``ops.CloudGrid`` of the fragments.  ``clouds``: list of [n,3] arrays / tensors, fragment k at index k;
+    ``keys_or_pairs``: ``gt.log`` keys ``'i_j'`` or (i, j) tuples with ``T[p]`` ([P,4,4] / [P,3,4]; array or tensor)
+    mapping fragment j into fragment i -- j is the moving cloud, i the fixed one.  ``icp``: ``max_iters``,
+    ``rel_fitness``, ``rel_rmse`` of ``ops.icp_rigid``.  Returns ``(T [P,4,4] f64, fitness [P] = matched share of j's
+    points under the returned T, rmse [P], iterations [P])``: device tensors, or NumPy arrays from ``device='cpu'``
+    (``icp_numpy``).  A pair that ends with fewer than 3 matches keeps the pose it had then."""
+    ij = _pair_list(keys_or_pairs)
+    ji = ij[:, ::-1].copy()
+    if ij.size and (ij.min() < 0 or ij.max() >= len(clouds)):
+        raise ValueError("pairs name fragments outside 0..%d" % (len(clouds) - 1))
+    lens = np.asarray([int(c.shape[0]) for c in clouds], dtype=np.int64)
+    if str(device).startswith('cpu'):
+        arrs = [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
+                for c in clouds]
+        Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
+        Tr, count, rmse, iters, _ = icp_numpy(arrs, ji, Tn, max_distance, **icp)
+        return Tr, count / np.maximum(lens[ji[:, 0]], 1), rmse, iters
+    dev = torch.device(device)
+    pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
+    grid = ops.CloudGrid(pts, lens, float(max_distance))
+    Tr, count, rmse, iters, _ = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
+                                              max_distance, **icp)
+    fitness = count.double() / torch.as_tensor(np.maximum(lens[ji[:, 0]], 1), dtype=torch.float64, device=dev)
+    return Tr, fitness, rmse, iters
 
 
 # ------------------------------------------------------------------------------------------------- gt.info, metric
@@ -159,11 +281,14 @@ def evaluate_registration(est, gt, info, err2=0.2 ** 2):
     return recall, precision, errs
 
 
-def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, **ransac):
+def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
+                   **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
-    ``evaluate_registration(...)`` when ``<gtpath>/gt.info`` exists, else None."""
+    ``evaluate_registration(...)`` when ``<gtpath>/gt.info`` exists, else None.  ``icp``: None, or a dict of
+    ``refine_transforms`` keywords (at least ``max_distance``): every pose is refined by ICP over the dumped keypoint
+    files (they hold the whole subsampled fragment), all pairs in one call, before it is written and scored."""
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -194,7 +319,13 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
         sps.append(sp)
         tps.append(tp)
     src, tgt, seg, _ = _compact(torch.stack(muts), torch.stack(sps), torch.stack(tps))
-    T = _ransac(src, tgt, seg, ransac)[0].cpu().numpy()          # the scene's only read-back
+    T = _ransac(src, tgt, seg, ransac)[0]
+    if icp is not None:
+        frags = sorted(cache)
+        slot = {f: n for n, f in enumerate(frags)}
+        ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]
+        T = refine_transforms([cache[f][0] for f in frags], ij, T, device=dev, **_icp_keywords(icp))[0]
+    T = T.cpu().numpy()                                          # the scene's only read-back
     est = {key: T[n] for n, key in enumerate(keys)}
     ev.writelog(out_log or os.path.join(save_path, 'registration', scene), est, num_frag)
     if not os.path.exists(os.path.join(gtpath, 'gt.info')):

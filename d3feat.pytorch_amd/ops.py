@@ -2711,6 +2711,95 @@ def nearest_pairs(grid_or_points, lens, pairs, transforms, radius, lanes=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# point-to-point ICP over a list of cloud pairs (the refinement after RANSAC; Open3D's registration_icp)
+# ---------------------------------------------------------------------------------------------------------------
+ICP_MAX_ITERS = 1024
+ICP_BLOCK_ROWS = 512
+ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8
+
+
+def icp_rigid_bytes(rows, found=None):
+    """Algorithmic bytes of ONE search of ``rows`` rows: ``nearest_pairs_bytes`` without the 4-byte index, plus the 136
+    bytes of sums a workgroup of ``ICP_BLOCK_ROWS`` rows writes and the fit reads back."""
+    rows = int(rows)
+    return nearest_pairs_bytes(rows, found) - 4 * rows + 2 * 136 * (-(-rows // ICP_BLOCK_ROWS))
+
+
+def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
+              return_trace=False, rows=None):
+    """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).
+
+    ``grid_or_points``, ``lens``, ``pairs``: as in ``nearest_pairs`` -- pair p = (MOVING cloud a, FIXED cloud b) and
+    ``T_init`` f64 [P,4,4] or [P,3,4] maps points of a into b's frame.  (For a ``gt.log`` key i_j, whose matrix maps j
+    into i -- what ``ransac_rigid`` returns -- the pair is (j, i) and the matrix is a valid ``T_init`` as it stands.)
+    Each iteration matches every moving point to its nearest fixed point closer than ``max_distance`` (arithmetic and tie
+    rule of ``nearest_pairs``) and fits the rigid motion to the matches in f64; a pair stops when fitness and RMSE both
+    change by less than ``rel_fitness`` / ``rel_rmse`` (absolute differences, Open3D's ICPConvergenceCriteria), after
+    ``max_iters`` fits, or with fewer than 3 matches (``ICP_ST_FEW``).  Returns device tensors ``(T [P,4,4] f64, count
+    [P] int32, rmse [P] f64, iterations [P] int32, status [P] int32)``: ``count`` / ``rmse`` are those of the returned
+    ``T``; ``return_trace=True`` appends ``trace [P, max_iters+1, 2]`` f64 = (n_k, sum d2_k) per search (NaN beyond the
+    stop).  Bit-identical from run to run and for a pair alone or inside any batch.  No read-back when the lengths and
+    pairs are known on the host, or when ``rows`` -- a host bound on the moving rows of all pairs together -- comes with
+    device ``pairs`` (the form a captured graph takes; a pair reaching beyond it gets ``ICP_ST_PAIR``)."""
+    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
+        grid = grid_or_points
+        if float(max_distance) > grid.radius:
+            raise RuntimeError("max_distance %g exceeds the cell list's %g" % (float(max_distance), grid.radius))
+    else:
+        if lens is None:
+            raise ValueError("lens is required with stacked points")
+        grid = CloudGrid(grid_or_points, lens, max_distance)
+    if not 0 <= int(max_iters) <= ICP_MAX_ITERS:
+        raise ValueError("max_iters must be in 0..%d" % ICP_MAX_ITERS)
+    if not (0.0 < float(max_distance) < float("inf")) or not float(rel_fitness) >= 0.0 or not float(rel_rmse) >= 0.0:
+        raise ValueError("max_distance must be positive and finite, rel_fitness and rel_rmse non-negative")
+    dev = grid.supports.device
+    B = int(grid.s_len.numel())
+    cloud_start = getattr(grid, "cloud_start", None)
+    if cloud_start is None:
+        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
+    host = None
+    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
+    else:
+        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if host.size and (host.min() < 0 or host.max() >= B):
+            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
+        pr = torch.as_tensor(host.astype(np.int32), device=dev)
+    P = int(pr.shape[0])
+    if not 1 <= P <= MAX_CLOUDS:
+        raise ValueError("1..%d pairs per call, got %d" % (MAX_CLOUDS, P))
+    tf = torch.as_tensor(T_init, dtype=torch.float64).to(dev)
+    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4)):
+        raise ValueError("T_init must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (P, tuple(tf.shape)))
+    tf = tf[:, :3, :].contiguous()
+    lens_host = getattr(grid, "lens_host", None)
+    if host is not None and lens_host is not None:
+        rs = np.zeros(P + 1, dtype=np.int64)
+        rs[1:] = np.cumsum(lens_host[host[:, 0]])
+        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
+    else:
+        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long().clamp(0, B - 1)], 0)
+        rows = int(rows) if rows is not None else int(row_start[-1].item())   # (the one read-back of this form)
+    K = int(max_iters)
+    T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+    count, iterations, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    rmse = torch.empty(P, dtype=torch.float64, device=dev)
+    trace = torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev) if return_trace else None
+    L = _native.lib()
+    nbytes = L.d3f_icp_rigid_ws_bytes(P, rows)
+    ws = _ws(nbytes, dev)
+    with _region("icp_rigid[P=%d,rows=%d,iters<=%d]" % (P, rows, K), (K + 1) * icp_rigid_bytes(rows)):
+        _native.check(L.d3f_icp_rigid(
+            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
+            _p(row_start), P, rows, _p(tf), K, float(rel_fitness), float(rel_rmse), _p(T), _p(count), _p(rmse),
+            _p(iterations), _p(status), _p(trace), _p(ws), nbytes, _stream()), "d3f_icp_rigid")
+    res = (T, count, rmse, iterations, status)
+    return res + (trace,) if return_trace else res
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

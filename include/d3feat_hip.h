@@ -736,6 +736,53 @@ int d3f_nearest_pairs_lanes(const void* grid_ws, const float* points, int Ns, co
                             int32_t* status, int lanes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-to-point ICP over a list of cloud pairs -- the refinement every 3DMatch registration pipeline runs after RANSAC
+ * (Open3D's registration_icp; the reference leaves it to Open3D on the CPU).  The clouds, the cell list (grid_ws,
+ * grid_radius), cloud_start, pairs and row_start are those of d3f_nearest_pairs: pair p = (pairs[2p] MOVING cloud a,
+ * pairs[2p+1] FIXED cloud b) and its transform maps points of a into b's frame.  For a gt.log key i_j, whose matrix
+ * maps fragment j into fragment i (what d3f_ransac_rigid returns: "target onto source"), the moving cloud is j and the
+ * fixed cloud is i: a RANSAC result is a valid T_init as it stands with pairs = (j, i).
+ * T_init [P,12] f64: row-major 3x4 per pair.  All P pairs advance together; iteration k = 0, 1, ... of pair p:
+ *   1. search under T_k with the arithmetic, acceptance (d2 < max_distance * max_distance, f32) and tie rule of
+ *      d3f_nearest_pairs, and over the accepted rows, in f64: n, sum x', sum y', sum x' y'^T, sum d2 (the f32 d2
+ *      widened); x' = x - px with x the ORIGINAL moving point and px row 0 of the moving cloud, y' = y - py with y the
+ *      matched fixed point and py row 0 of the fixed cloud.  No index table is written.
+ *   2. fitness_k = n / len(a), rmse_k = sqrt(sum d2 / n) (0 when n = 0).
+ *      n < 3: stop, status D3F_ICP_ST_FEW.
+ *      k >= 1 and |fitness_k - fitness_{k-1}| < rel_fitness and |rmse_k - rmse_{k-1}| < rel_rmse: stop (Open3D's
+ *      ICPConvergenceCriteria, which compares absolute differences despite the names).
+ *      k == max_iters: stop.
+ *      else T_{k+1} = the least-squares fit y ~ R x + t from the sums (csrc/rigid.hpp fit_from_sums), next iteration.
+ *   A stopped pair's result is T_k; max_iters = 0 only evaluates T_init.  At most max_iters + 1 searches.
+ * Outputs per pair: T [P,4,4] f64; count [P] int32 and rmse [P] f64 of the RETURNED T (n_k, rmse_k of the stopping
+ * iteration); iterations [P] int32 (fits applied); status [P] int32 (D3F_ICP_ST_* bits).  A pair that names a cloud
+ * outside [0, B), or whose rows reach beyond `rows`, gets D3F_ICP_ST_PAIR; a non-finite T_init D3F_ICP_ST_NONFINITE;
+ * both return T_init, count 0, rmse 0, iterations 0.  Optional (NULL to skip), for tests: trace [P, max_iters+1, 2] f64
+ * = (n_k, sum d2_k) per search, NaN beyond the stop.
+ * Deterministic and batch-independent: a workgroup serves D3F_ICP_BLOCK_ROWS consecutive rows of ONE pair, sums them
+ * in a fixed tree, and the pair's workgroups are added in a fixed order that depends on the pair's length alone -- no
+ * floating-point atomics -- so a pair's result is bit-identical alone or inside any batch and from run to run.
+ * `rows` >= row_start[P] sizes the launches and the workspace (d3f_icp_rigid_ws_bytes(P, rows)); P <= 65535,
+ * 0 <= max_iters <= D3F_ICP_MAX_ITERS, max_distance <= grid_radius.  1 + 2 (max_iters + 1) launches on `stream`
+ * whatever the data, no host synchronisation, no allocation (graph-capturable).
+ * d3f_icp_fit_host: host-only twin of step 2's fit: sums[17] = {n, sum x' (3), sum y' (3), sum x'_a y'_b (9), sum d2},
+ * pivots px, py -> row-major 4x4; n >= 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_ICP_MAX_ITERS 1024
+#define D3F_ICP_BLOCK_ROWS 512
+#define D3F_ICP_ST_FEW 1        /* fewer than 3 accepted rows at the stopping iteration */
+#define D3F_ICP_ST_CELL_RANGE 2 /* a moved point fell outside the addressable cell grid (= D3F_ST_CELL_RANGE) */
+#define D3F_ICP_ST_PAIR 4       /* the pair names a cloud outside [0, B) or rows beyond `rows` */
+#define D3F_ICP_ST_NONFINITE 8  /* T_init holds a non-finite value */
+size_t d3f_icp_rigid_ws_bytes(int P, int64_t rows);
+int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                  float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                  int64_t rows, const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T,
+                  int32_t* count, double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws,
+                  size_t ws_bytes, void* stream);
+int d3f_icp_fit_host(const double* sums_host, const double* px_host, const double* py_host, double* out_host);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
