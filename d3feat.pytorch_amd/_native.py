@@ -123,6 +123,16 @@ SIGNATURES = {
     "d3f_detection_scores_ws_bytes": (_sz, [_i, _i]),
     "d3f_detection_scores_backward": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_detection_scores_backward_groups": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "d3f_detection_rows_supported": (_i, [_i, _i]),
+    "d3f_detection_rows_ws_bytes": (_sz, [_i]),
+    "d3f_detection_rows_forward": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "d3f_detection_rows_forward_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                              _vp]),
+    "d3f_detection_rows_backward": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _sz, _vp]),
+    "d3f_detection_rows_backward_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                               _vp, _sz, _vp]),
     "d3f_circle_det_loss_forward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp]),
     "d3f_circle_det_loss_backward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp,

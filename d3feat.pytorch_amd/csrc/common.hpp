@@ -82,6 +82,28 @@ __device__ __forceinline__ int group_of_row(const RowGroups& rg, int row) {
   return b / rg.group;
 }
 
+// The 2M sampled rows of a training step (loss.hip: select + normalise; detection.hip: the detector on those rows):
+// m2 in [0, M) are the anchors, [M, 2M) the positives.  idx_a / idx_p int64, element m at idx[m * idx_stride]; idx_p is
+// offset by *p_offset when given.  pair_len (stacked pairs): the rows of pair m / M_pair are local to its own two clouds
+// (2p, 2p + 1 of the stack).
+struct SampledRows {
+  const int64_t* idx_a;
+  const int64_t* idx_p;
+  int idx_stride;
+  int M;
+  const int32_t* p_offset;
+  const int32_t* pair_len;
+  int M_pair;
+};
+__device__ __forceinline__ long sampled_row(const SampledRows& sr, int m2, int N) {
+  const bool pos = m2 >= sr.M;
+  const int m = pos ? m2 - sr.M : m2;
+  long row = pos ? sr.idx_p[(size_t)m * sr.idx_stride] + (sr.p_offset ? (long)*sr.p_offset : 0)
+                 : sr.idx_a[(size_t)m * sr.idx_stride];
+  if (sr.pair_len) row += batch_offset(sr.pair_len, 2 * (m / sr.M_pair) + (pos ? 1 : 0));
+  return row < 0 ? 0 : (row >= N ? N - 1 : row);
+}
+
 // squared distance with the reference's float32 evaluation order and NO fused multiply-add:
 // d2 = dx*dx; d2 += dy*dy; d2 += dz*dz   (nanoflann.hpp:433-441).  NOTE: on AMD the __f*_rn intrinsics are plain
 // operators, so this is only exact because the library is compiled with -ffp-contract=off (see _native.build).

@@ -142,16 +142,14 @@ __global__ __launch_bounds__(256) void det_bwd_kernel(const float* __restrict__ 
 // ---- 16-byte gathers: lane = (4 channels, neighbor group); LP = C/4 lanes serve one neighbor row, 64/LP rows per step.
 // Training additionally leaves 8 scalars per point behind (aux) so that the backward pass needs no feature gather:
 //   {f*, alpha*, beta*, u*, dmax, num, c* (int bits), c' (int bits)}   (* = winning channel, ' = channel of max_c f)
+// The score of point n, computed by one wave (the same value in every lane); `a` (optional): the point's aux record.
+// Shared by the dense kernel (one wave per point of the batch) and the rows form (one wave per sampled row).
 template <int LP>
-__global__ __launch_bounds__(256) void det_fwd_v4_kernel(const float* __restrict__ feat, int N,
-                                                         const int32_t* __restrict__ idx, int H,
-                                                         const float* __restrict__ fmax, int training,
-                                                         float* __restrict__ scores, float* __restrict__ aux,
-                                                         const int32_t* __restrict__ width, d3f::RowGroups rg) {
+__device__ __forceinline__ float det_point_v4(const float* __restrict__ feat, int N, const int32_t* __restrict__ idx,
+                                              int H, const float* __restrict__ fmax, int training,
+                                              const int32_t* __restrict__ width, const d3f::RowGroups& rg, int n,
+                                              int lane, float* __restrict__ a) {
   constexpr int C = 4 * LP, G = 64 / LP;
-  const int lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (n >= N) return;
   const int c4 = lane % LP, g = lane / LP;
   const int gi = d3f::group_of_row(rg, n);   // see det_fwd_kernel
   fmax += gi;
@@ -222,8 +220,7 @@ __global__ __launch_bounds__(256) void det_fwd_v4_kernel(const float* __restrict
     for (int k = 0; k < 4; ++k) is = fmaxf(is, fs[k] == lm[k] ? 1.0f : 0.0f);
     score *= group_max<LP>(is);
   }
-  if (lane == 0) scores[n] = score;
-  if (aux) {
+  if (a) {
     // first channel attaining the max (torch.max returns the first maximal index), and first channel of max_c f
     int cs = 0x7fffffff, cp = 0x7fffffff;
 #pragma unroll
@@ -239,10 +236,45 @@ __global__ __launch_bounds__(256) void det_fwd_v4_kernel(const float* __restrict
     // the lane that owns channel c* publishes its values
     if (g == 0 && (cs >> 2) == c4) {
       const int k = cs & 3;
-      float* a = aux + (size_t)n * 8;
       a[0] = fs[k]; a[1] = al[k]; a[2] = be[k]; a[3] = u[k];
       a[4] = dmax; a[5] = num; a[6] = __int_as_float(cs); a[7] = __int_as_float(cp);
     }
+  }
+  return score;
+}
+
+template <int LP>
+__global__ __launch_bounds__(256) void det_fwd_v4_kernel(const float* __restrict__ feat, int N,
+                                                         const int32_t* __restrict__ idx, int H,
+                                                         const float* __restrict__ fmax, int training,
+                                                         float* __restrict__ scores, float* __restrict__ aux,
+                                                         const int32_t* __restrict__ width, d3f::RowGroups rg) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float score = det_point_v4<LP>(feat, N, idx, H, fmax, training, width, rg, n, lane,
+                                       aux ? aux + (size_t)n * 8 : nullptr);
+  if (lane == 0) scores[n] = score;
+}
+
+// ---- rows form: the training loss reads the scores of the 2M sampled correspondences only (reference trainer.py:90-97
+// indexes scores[corr] before det_loss), so one wave per SAMPLED row runs the same body and leaves a compact aux [2M, 8].
+template <int LP>
+__global__ __launch_bounds__(256) void det_rows_fwd_kernel(const float* __restrict__ feat, int N,
+                                                           const int32_t* __restrict__ idx, int H,
+                                                           const float* __restrict__ fmax, int training,
+                                                           const int32_t* __restrict__ width, d3f::RowGroups rg,
+                                                           d3f::SampledRows sr, float* __restrict__ sa,
+                                                           float* __restrict__ sp, float* __restrict__ aux) {
+  const int lane = threadIdx.x & 63;
+  const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);  // 0..2M-1: anchors then positives
+  if (m2 >= 2 * sr.M) return;
+  const int n = (int)d3f::sampled_row(sr, m2, N);
+  const float score = det_point_v4<LP>(feat, N, idx, H, fmax, training, width, rg, n, lane,
+                                       aux ? aux + (size_t)m2 * 8 : nullptr);
+  if (lane == 0) {
+    if (m2 >= sr.M) sp[m2 - sr.M] = score;
+    else sa[m2] = score;
   }
 }
 
@@ -405,6 +437,135 @@ __global__ void det_finalize_kernel(const float* __restrict__ feat, int cap_rows
   }
 }
 
+// ---- backward of the rows form -------------------------------------------------------------------------------------
+// One wave per sampled row, lanes over the H neighbor slots: the three kinds of contribution of det_bwd_aux_kernel (the
+// row's c* term, its c' term, -du/num on c* of every live neighbor), already divided by the group's denom, go with float
+// atomics straight into the ONE dense [N, C] gradient of x that select_normalize_bwd_kernel wrote its rows into.  The
+// normaliser's gradient needs S = sum df * f over the group: every sampled row leaves its own partial (part[m2], with the
+// row's group in pgroup[m2]); det_rows_tie_apply_kernel adds a group's partials up in a fixed order (no float atomics: the
+// tie term has the same bits on every replay).
+constexpr int DET_TIE_CAP = 32;   // arg-max positions listed per group; more (all features <= 0, say): the dense scan
+
+__global__ __launch_bounds__(256) void det_rows_bwd_kernel(const float* __restrict__ feat, int N, int C,
+                                                           const int32_t* __restrict__ idx, int H,
+                                                           const float* __restrict__ fmax, d3f::RowGroups rg,
+                                                           d3f::SampledRows sr, const float* __restrict__ aux,
+                                                           const float* __restrict__ g_sa, const float* __restrict__ g_sp,
+                                                           float* __restrict__ grad, float* __restrict__ part,
+                                                           int32_t* __restrict__ pgroup, int32_t* __restrict__ tie_count,
+                                                           int G) {
+  // the tie scan that follows on the stream counts from zero (a fill launch of its own would cost more than this store)
+  if (blockIdx.x == 0 && (int)threadIdx.x < G) tie_count[threadIdx.x] = 0;
+  const int lane = threadIdx.x & 63;
+  const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m2 >= 2 * sr.M) return;
+  const bool pos = m2 >= sr.M;
+  const int n = (int)d3f::sampled_row(sr, m2, N);
+  const int gi = d3f::group_of_row(rg, n);
+  const float denom = fmaxf(fmax[gi], 0.0f) + 1e-6f;
+  const float* gs = pos ? g_sp : g_sa;
+  const float ds = gs ? gs[pos ? m2 - sr.M : m2] : 0.0f;
+  float s = 0.0f;
+  if (ds != 0.0f) {   // (a row without gradient adds nothing, as in det_bwd_aux_kernel)
+    const float4 a0 = *(const float4*)(aux + (size_t)m2 * 8);      // f*, alpha*, beta*, u*
+    const float4 a1 = *(const float4*)(aux + (size_t)m2 * 8 + 4);  // dmax, num, c*, c'
+    const int cstar = __float_as_int(a1.z), cprime = __float_as_int(a1.w);
+    const float sig = a0.w > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-a0.w));
+    const float du = ds * a0.z * sig;
+    // (a row of NaN features has no winning channel and left no record: nothing to address)
+    const bool ok = (unsigned)cstar < (unsigned)C && (unsigned)cprime < (unsigned)C;
+    if (ok && lane < H) {
+      const int m = idx[(size_t)n * H + lane];
+      if (m >= 0 && m < N) {
+        const float gn = -du / a1.y;
+        atomicAdd(&grad[(size_t)m * C + cstar], gn / denom);
+        s = gn * (feat[(size_t)m * C + cstar] / denom);
+      }
+    }
+    if (ok && lane == 0) {
+      const float inv = 1.0f / (1e-6f + a1.x);
+      const float v1 = du + ds * a0.y * inv, v2 = -ds * a0.y * a0.x * inv * inv;
+      atomicAdd(&grad[(size_t)n * C + cstar], v1 / denom);
+      atomicAdd(&grad[(size_t)n * C + cprime], v2 / denom);
+      s += v1 * a0.x + v2 * a1.x;   // f[n, c*] = f*, f[n, c'] = dmax
+    }
+  }
+  s = d3f::wave_sum(s);
+  if (lane == 0) {
+    part[m2] = s;
+    pgroup[m2] = gi;
+  }
+}
+
+// Arg-max positions of every group, found by reading feat only: counted under an integer counter, the first DET_TIE_CAP
+// of them listed (in any order: they all receive the same term).
+__global__ __launch_bounds__(256) void det_rows_tie_scan_kernel(const float* __restrict__ feat, int cap_rows, int C,
+                                                                const float* __restrict__ fmax, d3f::RowGroups rg,
+                                                                int32_t* __restrict__ tie_count,
+                                                                unsigned long long* __restrict__ tie_list) {
+  size_t beg, end;
+  group_range(rg, cap_rows, C, beg, end);
+  const float mx = fmaxf(fmax[blockIdx.y], 0.0f);
+  int32_t* cnt = tie_count + blockIdx.y;
+  unsigned long long* list = tie_list + (size_t)blockIdx.y * DET_TIE_CAP;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+  if ((((uintptr_t)feat) & 15) == 0 && (beg & 3) == 0 && (end & 3) == 0) {   // (C is a multiple of 16 here)
+    for (size_t i = beg + 4 * tid; i < end; i += 4 * nth) {
+      const float4 v = *(const float4*)(feat + i);
+      if (v.x == mx || v.y == mx || v.z == mx || v.w == mx) {
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (e[k] == mx) {
+            const int at = atomicAdd(cnt, 1);
+            if (at < DET_TIE_CAP) list[at] = i + k;
+          }
+      }
+    }
+  } else {
+    for (size_t i = beg + tid; i < end; i += nth)
+      if (feat[i] == mx) {
+        const int at = atomicAdd(cnt, 1);
+        if (at < DET_TIE_CAP) list[at] = i;
+      }
+  }
+}
+
+// grad += [feat == mx] * (-S / denom) / ties  (mx = max(fmax, 0); the zero shadow row is one more tie when mx == 0), as
+// det_reduce_kernel + det_finalize_kernel.  One workgroup per group (blockIdx.y) walks the group's list; only when the list
+// overflowed does it scan the group's feat again itself (rare -- a group without a positive feature and many exact zeros --
+// and then slow rather than wrong).
+__global__ __launch_bounds__(256) void det_rows_tie_apply_kernel(const float* __restrict__ feat, int cap_rows, int C,
+                                                                 const float* __restrict__ fmax, d3f::RowGroups rg,
+                                                                 const float* __restrict__ part,
+                                                                 const int32_t* __restrict__ pgroup, int rows,
+                                                                 const int32_t* __restrict__ tie_count,
+                                                                 const unsigned long long* __restrict__ tie_list,
+                                                                 float* __restrict__ grad) {
+  const int g = blockIdx.y;
+  const int cnt = tie_count[g];
+  __shared__ float S;
+  if (threadIdx.x < 64) {   // the group's partials: lane l takes rows l, l + 64, ... in ascending order, then the butterfly
+    float s = 0.0f;
+    for (int m2 = threadIdx.x; m2 < rows; m2 += 64)
+      if (pgroup[m2] == g) s += part[m2];
+    s = d3f::wave_sum(s);
+    if (threadIdx.x == 0) S = s;
+  }
+  __syncthreads();
+  const float mx = fmaxf(fmax[g], 0.0f), denom = mx + 1e-6f;
+  const float ties = (float)cnt + (mx == 0.0f ? 1.0f : 0.0f);
+  const float tie_term = (-S / denom) / fmaxf(ties, 1.0f);
+  if (cnt <= DET_TIE_CAP) {
+    for (int t = threadIdx.x; t < cnt; t += blockDim.x) atomicAdd(&grad[tie_list[(size_t)g * DET_TIE_CAP + t]], tie_term);
+    return;
+  }
+  size_t beg, end;
+  group_range(rg, cap_rows, C, beg, end);
+  for (size_t i = beg + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (size_t)gridDim.x * blockDim.x)
+    if (feat[i] == mx) atomicAdd(&grad[i], tie_term);
+}
+
 }  // namespace
 
 extern "C" {
@@ -519,6 +680,106 @@ int d3f_detection_scores_backward_groups(const float* feat, int N, int C, const 
   if (!len) return D3F_EINVAL;
   return det_backward_impl(feat, N, C, idx, H, feat_max, grad_scores, aux, grad_feat, len, B, group, ws, ws_bytes,
                            stream_);
+}
+
+/* ---- the detector on the sampled rows of a training step ---- */
+int d3f_detection_rows_supported(int C, int H) {
+  return (C == 16 || C == 32 || C == 64) && H >= 1 && H <= 64;
+}
+
+size_t d3f_detection_rows_ws_bytes(int rows) {
+  if (rows < 1) rows = 1;
+  // part [rows] f32, pgroup [rows] i32, tie_count [D3F_MAX_BATCH] i32, tie_list [D3F_MAX_BATCH * DET_TIE_CAP] u64; each
+  // carved at a 256-byte boundary
+  return d3f::align_up(8 * (size_t)rows, 256) * 2 + 256 + 8 * (size_t)D3F_MAX_BATCH * DET_TIE_CAP + 256;
+}
+
+static bool det_rows_args_ok(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                             const int32_t* len, int B, int group, const d3f::SampledRows& sr) {
+  if (!feat || !idx || !feat_max || !sr.idx_a || !sr.idx_p || N < 1 || sr.M < 1 || sr.idx_stride < 1 || sr.M_pair < 1)
+    return false;
+  if (!d3f_detection_rows_supported(C, H)) return false;
+  if (len && (B < 1 || B > D3F_MAX_BATCH || group < 0)) return false;   // group 0: one normaliser for the whole batch
+  if (sr.M > (1 << 24)) return false;
+  return true;
+}
+
+static int det_rows_forward_impl(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                 int training, const int32_t* width, const int32_t* len, int B, int group,
+                                 const d3f::SampledRows& sr, float* sa, float* sp, float* aux, void* stream_) {
+  if (!det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, sr) || !sa || !sp || (aux && !training))
+    return D3F_EINVAL;
+  const d3f::RowGroups rg = {group > 0 ? len : nullptr, B, group};
+  hipStream_t stream = (hipStream_t)stream_;
+  const int grid = d3f::cdiv(2 * sr.M, 4);
+  if (C == 16) det_rows_fwd_kernel<4><<<grid, 256, 0, stream>>>(feat, N, idx, H, feat_max, training, width, rg, sr, sa, sp, aux);
+  else if (C == 32) det_rows_fwd_kernel<8><<<grid, 256, 0, stream>>>(feat, N, idx, H, feat_max, training, width, rg, sr, sa, sp, aux);
+  else det_rows_fwd_kernel<16><<<grid, 256, 0, stream>>>(feat, N, idx, H, feat_max, training, width, rg, sr, sa, sp, aux);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_detection_rows_forward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                               int training, const int32_t* width, const int32_t* len, int B, int group,
+                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M,
+                               const int32_t* p_offset, float* sa, float* sp, float* aux, void* stream) {
+  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
+  return det_rows_forward_impl(feat, N, C, idx, H, feat_max, training, width, len, B, group, sr, sa, sp, aux, stream);
+}
+
+int d3f_detection_rows_forward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                     int training, const int32_t* width, const int32_t* len, int B, int group,
+                                     const int64_t* corr, int M, int pairs, float* sa, float* sp, float* aux,
+                                     void* stream) {
+  if (!corr || !len || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH || B != 2 * pairs) return D3F_EINVAL;
+  const d3f::SampledRows sr = {corr, corr + 1, 2, pairs * M, nullptr, len, M};
+  return det_rows_forward_impl(feat, N, C, idx, H, feat_max, training, width, len, B, group, sr, sa, sp, aux, stream);
+}
+
+static int det_rows_backward_impl(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                  const int32_t* len, int B, int group, const d3f::SampledRows& sr, const float* aux,
+                                  const float* g_sa, const float* g_sp, float* grad_x, void* ws, size_t ws_bytes,
+                                  void* stream_) {
+  if (!det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, sr) || !aux || !grad_x || !ws) return D3F_EINVAL;
+  const int rows = 2 * sr.M;
+  if (ws_bytes < d3f_detection_rows_ws_bytes(rows)) return D3F_EWORKSPACE;
+  const d3f::RowGroups rg = {group > 0 ? len : nullptr, B, group};
+  const int G = rg.len ? d3f::cdiv(B, group) : 1;
+  hipStream_t stream = (hipStream_t)stream_;
+  d3f::Carver cv(ws);
+  float* part = cv.take<float>(rows);
+  int32_t* pgroup = cv.take<int32_t>(rows);
+  int32_t* tie_count = cv.take<int32_t>(D3F_MAX_BATCH);
+  unsigned long long* tie_list = cv.take<unsigned long long>((size_t)D3F_MAX_BATCH * DET_TIE_CAP);
+  det_rows_bwd_kernel<<<d3f::cdiv(rows, 4), 256, 0, stream>>>(feat, N, C, idx, H, feat_max, rg, sr, aux, g_sa, g_sp,
+                                                                grad_x, part, pgroup, tie_count, G);
+  int blocks = d3f::cdiv((long long)N * C, 256 * 16 * (long long)G);
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  det_rows_tie_scan_kernel<<<dim3(blocks, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, tie_count, tie_list);
+  det_rows_tie_apply_kernel<<<dim3(1, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, part, pgroup, rows, tie_count,
+                                                             tie_list, grad_x);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
+                                int idx_stride, int M, const int32_t* p_offset, const float* aux, const float* g_sa,
+                                const float* g_sp, float* grad_x, void* ws, size_t ws_bytes, void* stream) {
+  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
+  return det_rows_backward_impl(feat, N, C, idx, H, feat_max, len, B, group, sr, aux, g_sa, g_sp, grad_x, ws, ws_bytes,
+                                stream);
+}
+
+int d3f_detection_rows_backward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                      const int32_t* len, int B, int group, const int64_t* corr, int M, int pairs,
+                                      const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  if (!corr || !len || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH || B != 2 * pairs) return D3F_EINVAL;
+  const d3f::SampledRows sr = {corr, corr + 1, 2, pairs * M, nullptr, len, M};
+  return det_rows_backward_impl(feat, N, C, idx, H, feat_max, len, B, group, sr, aux, g_sa, g_sp, grad_x, ws, ws_bytes,
+                                stream);
 }
 
 }  // extern "C"

@@ -676,24 +676,15 @@ __global__ __launch_bounds__(256) void contrastive_bwd_kernel(const float* __res
 //   out[m,:] = x[idx[m],:] / max(||x[idx[m],:]||, 1e-12)          (torch F.normalize semantics)
 __global__ __launch_bounds__(256) void select_normalize_fwd_kernel(const float* __restrict__ x,
                                                                    const float* __restrict__ scores, int N, int C,
-                                                                   const int64_t* __restrict__ idx_a,
-                                                                   const int64_t* __restrict__ idx_p, int M,
-                                                                   const int32_t* __restrict__ p_offset,
-                                                                   float* __restrict__ out_a, float* __restrict__ out_p,
-                                                                   float* __restrict__ sa, float* __restrict__ sp,
-                                                                   int idx_stride, const int32_t* __restrict__ pair_len,
-                                                                   int M_pair) {
+                                                                   d3f::SampledRows sr, float* __restrict__ out_a,
+                                                                   float* __restrict__ out_p, float* __restrict__ sa,
+                                                                   float* __restrict__ sp) {
   const int lane = threadIdx.x & 63;
   const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);  // 0..2M-1: anchors then positives
-  if (m2 >= 2 * M) return;
-  const bool pos = m2 >= M;
-  const int m = pos ? m2 - M : m2;
-  long row = pos ? idx_p[(size_t)m * idx_stride] + (p_offset ? (long)*p_offset : 0) : idx_a[(size_t)m * idx_stride];
-  if (pair_len) {  // stacked pairs: rows of pair m / M_pair are local to its own two clouds (2p, 2p + 1 of the stack)
-    const int pr = m / M_pair;
-    row += d3f::batch_offset(pair_len, 2 * pr + (pos ? 1 : 0));
-  }
-  row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+  if (m2 >= 2 * sr.M) return;
+  const bool pos = m2 >= sr.M;
+  const int m = pos ? m2 - sr.M : m2;
+  const long row = d3f::sampled_row(sr, m2, N);
   float ss = 0.0f;
   for (int c = lane; c < C; c += 64) {
     const float v = x[row * C + c];
@@ -703,32 +694,23 @@ __global__ __launch_bounds__(256) void select_normalize_fwd_kernel(const float* 
   const float denom = fmaxf(sqrtf(ss), 1e-12f);
   float* o = (pos ? out_p : out_a) + (size_t)m * C;
   for (int c = lane; c < C; c += 64) o[c] = x[row * C + c] / denom;
-  if (lane == 0) (pos ? sp : sa)[m] = scores[row];
+  if (lane == 0 && scores) (pos ? sp : sa)[m] = scores[row];   // no scores: the detector runs on the sampled rows itself
 }
 
 // grad_x[row,:] += g/n - y (y.g)/n  with y = x/n the normalised row (n > eps); grad_scores[row] += g_s
 __global__ __launch_bounds__(256) void select_normalize_bwd_kernel(const float* __restrict__ x, int N, int C,
-                                                                   const int64_t* __restrict__ idx_a,
-                                                                   const int64_t* __restrict__ idx_p, int M,
-                                                                   const int32_t* __restrict__ p_offset,
-                                                                   const float* __restrict__ g_a,
+                                                                   d3f::SampledRows sr, const float* __restrict__ g_a,
                                                                    const float* __restrict__ g_p,
                                                                    const float* __restrict__ g_sa,
                                                                    const float* __restrict__ g_sp,
                                                                    float* __restrict__ grad_x,
-                                                                   float* __restrict__ grad_s, int idx_stride,
-                                                                   const int32_t* __restrict__ pair_len, int M_pair) {
+                                                                   float* __restrict__ grad_s) {
   const int lane = threadIdx.x & 63;
   const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m2 >= 2 * M) return;
-  const bool pos = m2 >= M;
-  const int m = pos ? m2 - M : m2;
-  long row = pos ? idx_p[(size_t)m * idx_stride] + (p_offset ? (long)*p_offset : 0) : idx_a[(size_t)m * idx_stride];
-  if (pair_len) {  // stacked pairs: rows of pair m / M_pair are local to its own two clouds (2p, 2p + 1 of the stack)
-    const int pr = m / M_pair;
-    row += d3f::batch_offset(pair_len, 2 * pr + (pos ? 1 : 0));
-  }
-  row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+  if (m2 >= 2 * sr.M) return;
+  const bool pos = m2 >= sr.M;
+  const int m = pos ? m2 - sr.M : m2;
+  const long row = d3f::sampled_row(sr, m2, N);
   const float* g = (pos ? g_p : g_a) + (size_t)m * C;
   float ss = 0.0f, dot = 0.0f;
   for (int c = lane; c < C; c += 64) {
@@ -927,29 +909,31 @@ int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* po
 int d3f_select_normalize_forward(const float* x, const float* scores, int N, int C, const int64_t* idx_a,
                                  const int64_t* idx_p, int idx_stride, int M, const int32_t* p_offset, float* out_a,
                                  float* out_p, float* sa, float* sp, void* stream) {
-  if (!x || !scores || !idx_a || !idx_p || !out_a || !out_p || !sa || !sp || N < 1 || C < 1 || M < 1 || idx_stride < 1)
+  if (!x || !idx_a || !idx_p || !out_a || !out_p || (scores && (!sa || !sp)) || N < 1 || C < 1 || M < 1 ||
+      idx_stride < 1)
     return D3F_EINVAL;
-  select_normalize_fwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, idx_a, idx_p, M,
-                                                                                      p_offset, out_a, out_p, sa, sp,
-                                                                                      idx_stride, nullptr, 1);
+  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
+  select_normalize_fwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, sr, out_a, out_p,
+                                                                                      sa, sp);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
 
 /* grad_x [N,C] and grad_scores [N] must be ONE allocation of N*(C+1) floats starting at grad_x (cleared here with a
- * single fill); g_* may be NULL for outputs that received no gradient. */
+ * single fill); g_* may be NULL for outputs that received no gradient.  grad_scores NULL: only grad_x [N,C] is cleared
+ * and written (the detector's rows form adds its own part to it, d3f_detection_rows_backward). */
 int d3f_select_normalize_backward(const float* x, int N, int C, const int64_t* idx_a, const int64_t* idx_p,
                                   int idx_stride, int M, const int32_t* p_offset, const float* g_a, const float* g_p,
                                   const float* g_sa, const float* g_sp, float* grad_x, float* grad_scores,
                                   void* stream) {
-  if (!x || !idx_a || !idx_p || !grad_x || !grad_scores || N < 1 || C < 1 || M < 1 || idx_stride < 1 ||
-      grad_scores != grad_x + (size_t)N * C)
+  if (!x || !idx_a || !idx_p || !grad_x || N < 1 || C < 1 || M < 1 || idx_stride < 1 ||
+      (grad_scores && grad_scores != grad_x + (size_t)N * C))
     return D3F_EINVAL;
-  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + 1), (hipStream_t)stream) != hipSuccess)
+  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + (grad_scores ? 1 : 0)), (hipStream_t)stream) != hipSuccess)
     return D3F_ELAUNCH;
-  select_normalize_bwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, idx_a, idx_p, M, p_offset,
-                                                                                      g_a, g_p, g_sa, g_sp, grad_x,
-                                                                                      grad_scores, idx_stride, nullptr, 1);
+  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
+  select_normalize_bwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, sr, g_a, g_p, g_sa, g_sp,
+                                                                                      grad_x, grad_scores);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
@@ -960,13 +944,13 @@ int d3f_select_normalize_backward(const float* x, int N, int C, const int64_t* i
 int d3f_select_normalize_forward_pairs(const float* x, const float* scores, int N, int C, const int64_t* corr, int M,
                                        int pairs, const int32_t* len, float* out_a, float* out_p, float* sa, float* sp,
                                        void* stream) {
-  if (!x || !scores || !corr || !len || !out_a || !out_p || !sa || !sp || N < 1 || C < 1 || M < 1 || pairs < 1 ||
+  if (!x || !corr || !len || !out_a || !out_p || (scores && (!sa || !sp)) || N < 1 || C < 1 || M < 1 || pairs < 1 ||
       2 * pairs > D3F_MAX_BATCH)
     return D3F_EINVAL;
   const int T = pairs * M;
-  select_normalize_fwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, corr, corr + 1, T,
-                                                                                      nullptr, out_a, out_p, sa, sp, 2,
-                                                                                      len, M);
+  const d3f::SampledRows sr = {corr, corr + 1, 2, T, nullptr, len, M};
+  select_normalize_fwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, sr, out_a, out_p,
+                                                                                      sa, sp);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
@@ -974,15 +958,15 @@ int d3f_select_normalize_forward_pairs(const float* x, const float* scores, int 
 int d3f_select_normalize_backward_pairs(const float* x, int N, int C, const int64_t* corr, int M, int pairs,
                                         const int32_t* len, const float* g_a, const float* g_p, const float* g_sa,
                                         const float* g_sp, float* grad_x, float* grad_scores, void* stream) {
-  if (!x || !corr || !len || !grad_x || !grad_scores || N < 1 || C < 1 || M < 1 || pairs < 1 ||
-      2 * pairs > D3F_MAX_BATCH || grad_scores != grad_x + (size_t)N * C)
+  if (!x || !corr || !len || !grad_x || N < 1 || C < 1 || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH ||
+      (grad_scores && grad_scores != grad_x + (size_t)N * C))
     return D3F_EINVAL;
-  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + 1), (hipStream_t)stream) != hipSuccess)
+  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + (grad_scores ? 1 : 0)), (hipStream_t)stream) != hipSuccess)
     return D3F_ELAUNCH;
   const int T = pairs * M;
-  select_normalize_bwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, corr, corr + 1, T, nullptr,
-                                                                                      g_a, g_p, g_sa, g_sp, grad_x,
-                                                                                      grad_scores, 2, len, M);
+  const d3f::SampledRows sr = {corr, corr + 1, 2, T, nullptr, len, M};
+  select_normalize_bwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, sr, g_a, g_p, g_sa, g_sp,
+                                                                                      grad_x, grad_scores);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }

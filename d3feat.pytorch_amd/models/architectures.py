@@ -94,15 +94,20 @@ class KPFCNN(nn.Module):
 
     def forward_raw(self, batch):
         """(un-normalised descriptors [N,C], scores [N,1]) -- `forward` without the final F.normalize, for callers
-        that only need a few normalised rows (the training step: ops.select_normalize)."""
+        that only need a few normalised rows (ops.select_normalize)."""
+        x = self.forward_descriptors(batch)
+        return x, self.detection_scores(batch, x)
+
+    def forward_descriptors(self, batch):
+        """The un-normalised descriptors [N,C] alone: the training step scores only its sampled rows
+        (`detector_rows`, ops.train_loss)."""
         x = batch['features'].detach()   # (the reference clones, architectures.py:301; nothing writes into it here)
         skips = []
         for i, op in enumerate(self.encoder_blocks):
             if i in self.encoder_skips:
                 skips.append(self.mark_skip(x, op))
             x = op(x, batch)
-        x = self._decode(x, skips, batch)
-        return x, self.detection_scores(batch, x)
+        return self._decode(x, skips, batch)
 
     @staticmethod
     def mark_skip(x, op):
@@ -153,10 +158,17 @@ class KPFCNN(nn.Module):
         x, scores = self.forward_raw(batch)
         return F.normalize(x, p=2, dim=-1), scores
 
+    def _detector_args(self, inputs):
+        lens = inputs['stack_lengths'][0] if inputs.get('_static', False) else None  # capacity-shaped batch
+        widths = inputs.get('neighbors_width')   # full-limit tables: the level-0 table's max count, on the device
+        return dict(training=self.training, lens=lens, width=widths[0] if widths else None,
+                    group=inputs.get('_group', 0) if lens is not None else 0)
+
     def detection_scores(self, inputs, features):
         """Saliency score of every point [N,1] (reference architectures.py:322-368); eval mode adds the
         local-maximum gate."""
-        lens = inputs['stack_lengths'][0] if inputs.get('_static', False) else None  # capacity-shaped batch
-        widths = inputs.get('neighbors_width')   # full-limit tables: the level-0 table's max count, on the device
-        return ops.detection_scores(features, inputs['neighbors'][0], training=self.training, lens=lens,
-                                    width=widths[0] if widths else None, group=inputs.get('_group', 0) if lens is not None else 0)
+        return ops.detection_scores(features, inputs['neighbors'][0], **self._detector_args(inputs))
+
+    def detector_rows(self, inputs):
+        """`detection_scores` deferred to the loss: what ops.train_loss needs to score its sampled rows itself."""
+        return ops.DetectorRows(inputs['neighbors'][0], **self._detector_args(inputs))

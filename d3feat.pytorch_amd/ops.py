@@ -2045,6 +2045,25 @@ def detection_scores(features, neighbors, training=True, lens=None, width=None, 
                              int(group))
 
 
+class DetectorRows(object):
+    """The arguments of ``detection_scores`` without the features: handed to ``train_loss`` and its siblings in place
+    of a ``scores`` tensor, it makes the loss node score the 2 P M sampled rows itself (d3f_detection_rows_forward: the
+    dense kernel's own body, one wave per sampled row) -- the reference's loss reads no other score (trainer.py:90-97).
+    The node is then differentiable with respect to ``x`` alone and returns the one merged gradient."""
+
+    def __init__(self, neighbors, training=True, lens=None, width=None, group=0):
+        _check_groups(width, (lens, group) if group else None, "DetectorRows")
+        if group and lens is None:
+            raise RuntimeError("DetectorRows: the grouped form needs the stack lengths")
+        self.neighbors = _i32(neighbors, "neighbors")
+        self.training, self.lens, self.width, self.group = bool(training), lens, width, int(group)
+
+    @staticmethod
+    def supported(C, H):
+        """The rows form's domain (the aux path's own: C in {16, 32, 64}, H <= 64); others keep the dense detector."""
+        return bool(_native.lib().d3f_detection_rows_supported(int(C), int(H)))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # circle + detector loss (utils/loss.py:8-44,111-141,149-158)
 # ---------------------------------------------------------------------------------------------------------------
@@ -2165,10 +2184,18 @@ def _select_normalize_fwd(x, scores, ia, ip, stride, off):
     return oa, op, sa, sp
 
 
-def _select_normalize_bwd(x, ia, ip, stride, off, g_a, g_p, g_sa, g_sp):
-    N, C, M = int(x.shape[0]), int(x.shape[1]), int(ia.shape[0])
+def _grad_rows_buffer(x, with_scores):
+    """(grad_x [N,C], grad_scores [N,1] or None): one allocation, cleared by one fill."""
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if not with_scores:
+        return torch.empty((N, C), dtype=torch.float32, device=x.device), None
     buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
-    gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+    return buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+
+
+def _select_normalize_bwd(x, ia, ip, stride, off, g_a, g_p, g_sa, g_sp, with_scores=True):
+    N, C, M = int(x.shape[0]), int(x.shape[1]), int(ia.shape[0])
+    gx, gs = _grad_rows_buffer(x, with_scores)
     cont = [g.contiguous() if g is not None else None for g in (g_a, g_p, g_sa, g_sp)]
     _native.check(_native.lib().d3f_select_normalize_backward(_p(x), N, C, _p(ia), _p(ip), stride, M, _p(off),
                                                               _p(cont[0]), _p(cont[1]), _p(cont[2]), _p(cont[3]),
@@ -2306,7 +2333,8 @@ def contrastive_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, sa
 # the whole loss of one training step (trainer.py:91-98) as ONE autograd node
 # ---------------------------------------------------------------------------------------------------------------
 def _select_rows_fwd(x, scores, corr, p_offset, lens, P, M):
-    """The 2 P M sampled rows, gathered and normalised by one launch: (oa, op, sa, sp, saved, stride).  ``lens`` None:
+    """The 2 P M sampled rows, gathered and normalised by one launch: (oa, op, sa, sp, saved, stride).  ``scores``
+    None: sa / sp are left for the detector's rows form to fill (_det_rows_fwd).  ``lens`` None:
     one pair (corr [M,2], its columns read in place; p_offset); otherwise P stacked pairs (corr [P*M,2] cloud-local,
     lens int32 [2P]).  ``saved`` (three tensors or None) and ``stride`` (None: stacked) are what _select_rows_bwd needs."""
     if lens is None:
@@ -2323,18 +2351,71 @@ def _select_rows_fwd(x, scores, corr, p_offset, lens, P, M):
     return oa, op, sa, sp, (corr, lens, None), None
 
 
-def _select_rows_bwd(x, saved, stride, P, M, ga, gp, gsa, gsp):
-    """(grad_x [N,C], grad_scores [N,1]) of _select_rows_fwd."""
+def _select_rows_bwd(x, saved, stride, P, M, ga, gp, gsa, gsp, with_scores=True):
+    """(grad_x [N,C], grad_scores [N,1]) of _select_rows_fwd; ``with_scores`` False: (grad_x, None), the score
+    gradients go through _det_rows_bwd instead."""
     s0, s1, s2 = saved
+    if not with_scores:
+        gsa = gsp = None
     if stride is not None:
-        return _select_normalize_bwd(x, s0, s1, stride, s2, ga, gp, gsa, gsp)
+        return _select_normalize_bwd(x, s0, s1, stride, s2, ga, gp, gsa, gsp, with_scores)
     N, C = int(x.shape[0]), int(x.shape[1])
-    buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
-    gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+    gx, gs = _grad_rows_buffer(x, with_scores)
     _native.check(_native.lib().d3f_select_normalize_backward_pairs(_p(x), N, C, _p(s0), M, P, _p(s1), _p(ga), _p(gp),
                                                                     _p(gsa), _p(gsp), _p(gx), _p(gs), _stream()),
                   "d3f_select_normalize_backward_pairs")
     return gx, gs
+
+
+def _det_rows_args(x, det, fmax, pair_lens):
+    """Leading arguments of the d3f_detection_rows_* entries and their (len, B, group); the stacked forms hand the
+    pairs' own lengths (group 0: one normaliser for all of them, as the dense form without groups)."""
+    N, C, H = int(x.shape[0]), int(x.shape[1]), int(det.neighbors.shape[1])
+    if int(det.neighbors.shape[0]) != N:
+        raise ValueError("DetectorRows: the neighbor table must have one row per descriptor")
+    lens = pair_lens if pair_lens is not None else (det.lens if det.group else None)
+    if pair_lens is not None and det.group and (det.lens is None or det.lens.numel() != pair_lens.numel()):
+        raise ValueError("DetectorRows: lens must be the stacked pairs' own level-0 lengths")
+    if int(fmax.numel()) != (-(-int(lens.numel()) // det.group) if det.group else 1):
+        raise ValueError("DetectorRows: one normaliser per group of clouds expected")
+    return ((_p(x), N, C, _p(det.neighbors), H, _p(fmax)),
+            (_p(lens), int(lens.numel()) if lens is not None else 0, det.group))
+
+
+def _det_rows_fwd(x, det, fmax, saved, stride, P, M, sa, sp, want_aux):
+    """Scores of the sampled rows into sa / sp; returns the compact aux [2 P M, 8] (None when no backward follows)."""
+    L = _native.lib()
+    head, groups = _det_rows_args(x, det, fmax, None if stride is not None else saved[1])
+    aux = torch.empty((2 * P * M, 8), dtype=torch.float32, device=x.device) if want_aux else None
+    s0, s1, s2 = saved
+    with _region("detection_rows_fwd[T=%d]" % (P * M)):
+        if stride is not None:
+            _native.check(L.d3f_detection_rows_forward(*head, 1 if det.training else 0, _p(det.width), *groups, _p(s0),
+                                                       _p(s1), stride, M, _p(s2), _p(sa), _p(sp), _p(aux), _stream()),
+                          "d3f_detection_rows_forward")
+        else:
+            _native.check(L.d3f_detection_rows_forward_pairs(*head, 1 if det.training else 0, _p(det.width), *groups,
+                                                             _p(s0), M, P, _p(sa), _p(sp), _p(aux), _stream()),
+                          "d3f_detection_rows_forward_pairs")
+    return aux
+
+
+def _det_rows_bwd(x, det, fmax, saved, stride, P, M, aux, gsa, gsp, gx):
+    """Adds the detector's gradient of the sampled rows (and the normaliser's arg-max term) to ``gx``."""
+    L = _native.lib()
+    head, groups = _det_rows_args(x, det, fmax, None if stride is not None else saved[1])
+    nws = int(L.d3f_detection_rows_ws_bytes(2 * P * M))
+    ws = _ws(nws, x.device)
+    s0, s1, s2 = saved
+    with _region("detection_rows_bwd[T=%d]" % (P * M)):
+        if stride is not None:
+            _native.check(L.d3f_detection_rows_backward(*head, *groups, _p(s0), _p(s1), stride, M, _p(s2), _p(aux),
+                                                        _p(gsa), _p(gsp), _p(gx), _p(ws), nws, _stream()),
+                          "d3f_detection_rows_backward")
+        else:
+            _native.check(L.d3f_detection_rows_backward_pairs(*head, *groups, _p(s0), M, P, _p(aux), _p(gsa), _p(gsp),
+                                                              _p(gx), _p(ws), nws, _stream()),
+                          "d3f_detection_rows_backward_pairs")
 
 
 class _TrainLossFn(torch.autograd.Function):
@@ -2346,12 +2427,21 @@ class _TrainLossFn(torch.autograd.Function):
     stacked into one batch (corr [P*M,2], every pair's own cloud-local table; lens int32 [2P], the level-0 stack lengths
     on the device), scalars [P,6], dists [P,M,M].  ``aux``: the circle loss's neg_mask (uint8) or the contrastive loss's
     keypoint distances (f64), [M,M] / [P,M,M]; ``params`` = the loss's scalars, led by log_scale for the circle loss.
-    ``gw``: (w_desc, w_det) on the device, for the one form whose kernel does not apply the weights itself."""
+    ``gw``: (w_desc, w_det) on the device, for the one form whose kernel does not apply the weights itself.
+    ``scores`` may be a ``DetectorRows`` instead of a tensor: the node then scores the sampled rows itself, is
+    differentiable with respect to x only and returns the single merged grad_x (one fill, no dense score gradient)."""
 
     @staticmethod
     def forward(ctx, x, scores, corr, p_offset, lens, aux, circle, P, params, weights, gw):
         M = int(aux.shape[-1])
-        oa, op, sa, sp, saved, stride = _select_rows_fwd(x, scores, corr, p_offset, lens, P, M)
+        det = scores if isinstance(scores, DetectorRows) else None
+        oa, op, sa, sp, saved, stride = _select_rows_fwd(x, None if det else scores, corr, p_offset, lens, P, M)
+        if det is not None:
+            fmax = global_max(x, det.lens, det.group)
+            ctx.det = (det, fmax, _det_rows_fwd(x, det, fmax, saved, stride, P, M, sa, sp,
+                                                det.training and ctx.needs_input_grad[0]))
+        else:
+            ctx.det = None
         # the single-pair circle kernel knows no weights: unit weights (config.py:58-59) take its own desc + det
         # (scalars[5]; no launch for the sum), others go through ``gw``; every other form weights inside the kernel
         plain = circle and lens is None
@@ -2385,12 +2475,25 @@ class _TrainLossFn(torch.autograd.Function):
             grads = _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, None if plain else weights, g_ptrs)
         else:
             grads = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs)
-        gx, gs = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads)
-        return (gx, gs) + (None,) * 9
+        if ctx.det is None:
+            gx, gs = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads)
+            return (gx, gs) + (None,) * 9
+        det, fmax, aux8 = ctx.det
+        if aux8 is None:
+            raise RuntimeError("train loss: the detector's backward is defined for training mode only")
+        gx, _ = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads, with_scores=False)
+        _det_rows_bwd(x, det, fmax, (s0, s1, s2), stride, P, M, aux8, grads[2], grads[3], gx)
+        return (gx,) + (None,) * 10
 
 
 def _loss_inputs(x, scores):
-    return _f32(x, "x"), _f32(scores, "scores").reshape(-1, 1)
+    """(x, scores [N,1]); a ``DetectorRows`` outside the rows form's domain becomes the dense scores here."""
+    x = _f32(x, "x")
+    if isinstance(scores, DetectorRows):
+        if DetectorRows.supported(x.shape[1], scores.neighbors.shape[1]):
+            return x, scores
+        scores = detection_scores(x, scores.neighbors, scores.training, scores.lens, scores.width, scores.group)
+    return x, _f32(scores, "scores").reshape(-1, 1)
 
 
 def _check_corr(corr):
@@ -2414,7 +2517,8 @@ def train_loss(x, scores, corr, p_offset, dist_keypts, log_scale=10.0, safe_radi
     ``w_desc * CircleLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset]) + w_det * DetLoss(...)``.
     Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only ``total`` carries
     gradient.  ``neg_mask``: ``dist_keypts > safe_radius`` as uint8 when the caller already has it (the pipelined step
-    evaluates it with the pair's upload, off the training stream)."""
+    evaluates it with the pair's upload, off the training stream).  ``scores``: the [N,1] scores, or a ``DetectorRows``
+    (here and in the three sibling forms): the detector then runs on the 2M sampled rows only, inside this node."""
     x, sc = _loss_inputs(x, scores)
     corr = _check_corr(corr)
     if neg_mask is None:

@@ -601,6 +601,9 @@ class TrainStep:
     SPLIT_BACKWARD_ON_ONE_RANK = False
     # one launch for a step's input loads (ops.copy_buffers); False: one copy_() per tensor (A/B experiments)
     FUSED_INPUT_LOAD = True
+    # the detector scores only the 2 P M sampled rows of the loss, inside the loss node (ops.DetectorRows); False
+    # (or D3FEAT_DENSE_DETECTOR=1 in the environment): all N scores and their dense backward, as before (A/B experiments)
+    SPARSE_DETECTOR = os.environ.get('D3FEAT_DENSE_DETECTOR', '0') in ('', '0')
 
     def build_batch(self, item):
         batch = dl.collate_fn_descriptor([item], self.config, self.limits, device=self.device, exact_width=False,
@@ -668,9 +671,17 @@ class TrainStep:
             self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
         return self._one
 
+    def _scores_for_loss(self, batch, x):
+        """What the loss takes as ``scores``: the deferred detector (ops.train_loss falls back to the dense scores
+        outside the rows form's domain), or all N scores with the switch off."""
+        m = self.model
+        if self.SPARSE_DETECTOR and x.is_cuda:
+            return m.detector_rows(batch)
+        return m.detection_scores(batch, x)
+
     def forward_loss(self, batch):
-        x, scores = self.model.forward_raw(batch)
-        return self._loss_from_raw(x, scores, batch)
+        x = self.model.forward_descriptors(batch)
+        return self._loss_from_raw(x, self._scores_for_loss(batch, x), batch)
 
     def _forward_loss_cut(self, batch):
         """forward_loss with the autograd graph cut at the input of encoder block CUT: everything downstream (coarse
@@ -690,8 +701,7 @@ class TrainStep:
                 skips.append(m.mark_skip(x, op))
             x = op(x, batch)
         x = m._decode(x, skips, batch)
-        scores = m.detection_scores(batch, x)
-        return self._loss_from_raw(x, scores, batch), cuts
+        return self._loss_from_raw(x, self._scores_for_loss(batch, x), batch), cuts
 
     def _lane_stages(self, st):
         """(stage 1, stage 2) of a LANE's split step on the set's pair(s): gradients into the lane's own buffer, no

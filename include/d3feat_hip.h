@@ -530,6 +530,39 @@ int d3f_detection_scores_backward_groups(const float* feat, int N, int C, const 
                                          size_t ws_bytes, void* stream);
 size_t d3f_detection_scores_ws_bytes(int N, int C);
 
+/* The detector on the SAMPLED rows of a training step: the loss reads the scores of the 2M correspondences only
+ * (trainer.py:90-97 and :158-165 index scores[corr] before det_loss), so one wave per sampled row runs the body of
+ * d3f_detection_scores_forward (the same device function: the scores are bit-identical to the dense ones) and leaves
+ * sa [M], sp [M] and a compact aux [2M, 8] (anchors, then positives; NULL when no backward follows or training == 0).
+ * Rows are resolved as by d3f_select_normalize_forward[_pairs]; feat_max / width / len + group as for
+ * d3f_detection_scores_forward (group 0: one normaliser for the whole batch; the _pairs forms take len [B = 2 pairs] for
+ * both the pairs' clouds and the groups).  C in {16, 32, 64} and H <= 64 (d3f_detection_rows_supported); anything else
+ * is D3F_EINVAL: the caller keeps the dense path.
+ * backward: g_sa / g_sp [M] (either may be NULL = 0) are d loss / d sa, sp.  The gradient of x -- the three per-row terms
+ * of d3f_detection_scores_backward and the normaliser's arg-max term -- is ADDED to grad_x [N,C] with float atomics:
+ * grad_x is the buffer d3f_select_normalize_backward[_pairs] (grad_scores NULL) has just cleared and written its rows
+ * into, so one fill serves both.  The arg-max positions are found by reading feat only; the normaliser's term is summed
+ * from one partial per sampled row in a fixed order (the same bits on every replay).
+ * ws >= d3f_detection_rows_ws_bytes(2M). */
+int d3f_detection_rows_supported(int C, int H);
+size_t d3f_detection_rows_ws_bytes(int rows);
+int d3f_detection_rows_forward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                               int training, const int32_t* width, const int32_t* len, int B, int group,
+                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M,
+                               const int32_t* p_offset, float* sa, float* sp, float* aux, void* stream);
+int d3f_detection_rows_forward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                     int training, const int32_t* width, const int32_t* len, int B, int group,
+                                     const int64_t* corr, int M, int pairs, float* sa, float* sp, float* aux,
+                                     void* stream);
+int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
+                                int idx_stride, int M, const int32_t* p_offset, const float* aux, const float* g_sa,
+                                const float* g_sp, float* grad_x, void* ws, size_t ws_bytes, void* stream);
+int d3f_detection_rows_backward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                      const int32_t* len, int B, int group, const int64_t* corr, int M, int pairs,
+                                      const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
+                                      size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Descriptor loss -- replaces utils/loss.py: cdist(:8-44, 'euclidean'), CircleLoss.forward(:111-141),
  * DetLoss.forward(:149-158), fused into one single-workgroup launch (M <= 1024 sampled correspondences).
@@ -613,7 +646,9 @@ int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* po
  * idx_a / idx_p int64, element m at idx[m * idx_stride] (2 = the columns of the [M,2] correspondence table, read in
  * place); idx_p is offset by *p_offset (device int32: rows of the first cloud) when given.
  * backward: grad_x [N,C] and grad_scores [N] are ONE allocation of N*(C+1) floats (grad_scores == grad_x + N*C),
- * overwritten; g_* may be NULL. */
+ * overwritten; g_* may be NULL.
+ * scores NULL (forward; sa / sp are then not written) and grad_scores NULL (backward; only grad_x [N,C] is cleared and
+ * written): the detector runs on the sampled rows itself (d3f_detection_rows_forward / _backward). */
 int d3f_select_normalize_forward(const float* x, const float* scores, int N, int C, const int64_t* idx_a,
                                  const int64_t* idx_p, int idx_stride, int M, const int32_t* p_offset, float* out_a,
                                  float* out_p, float* sa, float* sp, void* stream);
