@@ -22,7 +22,14 @@
 // through LDS, and the pair's workgroups are added by one wave in the order lane = block mod 64, blocks ascending, then
 // the same butterfly.  Every order depends on the pair's length alone, so a pair's sums -- and with them its whole
 // trajectory -- are bit-identical alone, inside any batch, and from run to run.
+//
+// Point-to-plane form (d3f_icp_rigid_plane; kernels instantiated with kPlane).  Same setup, search, prefix, reduction
+// orders and stopping rule; only what the winning lane adds and what the fit solves differ.  The lane reads the normal
+// of the matched fixed point through the index the stored point carries and adds the 21 + 6 entries of the 6x6 normal
+// equations of the linearised point-to-plane residual (plane.hpp), 29 sums with n and sum d2; the fit is a Cholesky
+// solve by one lane.  Point-to-point ICP removes the error ALONG a plane only slowly; this form does not penalise it.
 #include "pair_search.hpp"
+#include "plane.hpp"
 #include "rigid.hpp"
 
 namespace {
@@ -34,12 +41,14 @@ constexpr int kG = 8;                                // lanes per query, nearest
 constexpr int kRows = D3F_ICP_BLOCK_ROWS;            // rows per workgroup
 constexpr int kRowsPerSlice = (kBlock / 64) * (64 / kG);
 constexpr int kSlices = kRows / kRowsPerSlice;
-constexpr int kSums = 17;
+constexpr int kPoint = 0, kPlane = 1;   // what the fit minimises
+constexpr int sums_of(int kind) { return kind == kPlane ? d3f::plane::kPlaneSums : 17; }
 constexpr int kMaxClouds = 65535;
 static_assert(kRows % kRowsPerSlice == 0, "a workgroup serves whole slices");
 
 struct IcpArgs {
   const float* points;
+  const float* normals;       // [Ns,3], input row order (kPlane)
   const int32_t* cloud_start;
   const int32_t* pairs;
   const int64_t* row_start;
@@ -49,7 +58,7 @@ struct IcpArgs {
   double* T_cur;              // [P,12] ws: T_k
   double* prev;               // [P,2]  ws: fitness_{k-1}, rmse_{k-1}
   int32_t* done;              // [P]    ws: the pair has stopped
-  double* partial;            // [blocks,17] ws
+  double* partial;            // [blocks, sums_of(kind)] ws
   double* T;
   int32_t* count;
   double* rmse;
@@ -74,7 +83,8 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int m) {
   return __longlong_as_double((long long)d3f::shfl_xor_u64((uint64_t)__double_as_longlong(v), m));
 }
 
-__device__ __forceinline__ void wave_sum17(double v[kSums]) {
+template <int kSums>
+__device__ __forceinline__ void wave_sum(double (&v)[kSums]) {
 #pragma unroll
   for (int k = 0; k < kSums; ++k)
 #pragma unroll
@@ -119,7 +129,9 @@ __global__ void icp_setup_kernel(const IcpArgs A) {
   }
 }
 
+template <int kKind>
 __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
+  constexpr int kSums = sums_of(kKind);
   const int lane = threadIdx.x & 63, sub = lane & (kG - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // the pair of this workgroup: the largest p with first_block(p) <= blockIdx.x (first_block(0) = 0)
@@ -164,7 +176,30 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
     float4 win;
     const uint64_t best =
         nearest_in_cloud<kG>(A.S, ok, x, y, z, T, b, tgt0, tgt_n, per_cloud, cell, reach, sub, A.status + p, mine, win);
-    if (ok && best != ~0ull && mine == best) {   // the one lane of the group that holds the winner
+    const bool winner = ok && best != ~0ull && mine == best;   // the one lane of the group that holds the winner
+    if constexpr (kKind == kPlane) {
+      if (winner) {
+        // a = T_k x - py in f64 (NOT the f32-rounded query: at coordinates of 300 that rounding is 3e-5 of residual
+        // noise), c = y - py, nrm the matched point's normal; J = [a x nrm, nrm], r = (a - c) . nrm
+        const size_t w = (size_t)(uint32_t)__float_as_int(win.w);
+        const double nrm[3] = {(double)A.normals[3 * w + 0], (double)A.normals[3 * w + 1], (double)A.normals[3 * w + 2]};
+        const double a[3] = {(((T[0] * x + T[1] * y) + T[2] * z) + T[3]) - py[0],
+                             (((T[4] * x + T[5] * y) + T[6] * z) + T[7]) - py[1],
+                             (((T[8] * x + T[9] * y) + T[10] * z) + T[11]) - py[2]};
+        const double c[3] = {(double)win.x - py[0], (double)win.y - py[1], (double)win.z - py[2]};
+        const double J[6] = {a[1] * nrm[2] - a[2] * nrm[1], a[2] * nrm[0] - a[0] * nrm[2], a[0] * nrm[1] - a[1] * nrm[0],
+                             nrm[0], nrm[1], nrm[2]};
+        const double r = ((a[0] - c[0]) * nrm[0] + (a[1] - c[1]) * nrm[1]) + (a[2] - c[2]) * nrm[2];
+        acc[0] += 1.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+#pragma unroll
+          for (int j = i; j < 6; ++j) acc[1 + d3f::plane::upper6(i, j)] += J[i] * J[j];
+          acc[22 + i] += J[i] * r;
+        }
+        acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
+      }
+    } else if (winner) {
       const double xd[3] = {x - px[0], y - px[1], z - px[2]};
       const double yd[3] = {(double)win.x - py[0], (double)win.y - py[1], (double)win.z - py[2]};
       acc[0] += 1.0;
@@ -177,10 +212,10 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
       for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[7 + 3 * r + c] += xd[r] * yd[c];
-      acc[16] += (double)__uint_as_float((uint32_t)(best >> 32));
+      acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
     }
   }
-  wave_sum17(acc);
+  wave_sum(acc);
   __shared__ double red[kBlock / 64][kSums];
   if (lane == 0) {
 #pragma unroll
@@ -195,7 +230,9 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
 }
 
 // one wave per pair: the pair's block sums in a fixed order, the stopping rule, the fit
+template <int kKind>
 __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter) {
+  constexpr int kSums = sums_of(kKind);
   const int p = blockIdx.x, lane = threadIdx.x;
   if (A.done[p]) return;
   const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
@@ -208,10 +245,10 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
 #pragma unroll
     for (int k = 0; k < kSums; ++k) v[k] += part[k];
   }
-  wave_sum17(v);
+  wave_sum(v);
   if (lane != 0) return;
   const int sa = A.cloud_start[a], len_a = A.cloud_start[a + 1] - sa, tgt0 = A.cloud_start[b];
-  const double n = v[0], sd2 = v[16];
+  const double n = v[0], sd2 = v[kSums - 1];
   const double fitness = len_a > 0 ? n / (double)len_a : 0.0, rmse = n > 0.0 ? sqrt(sd2 / n) : 0.0;
   if (A.trace) {
     double* tr = A.trace + 2 * ((size_t)p * (A.max_iters + 1) + k_iter);
@@ -235,19 +272,36 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
     A.done[p] = 1;
     return;
   }
-  double px[3], py[3], R[9], t[3];   // (n >= 3: both clouds have a row 0 inside the stack, the search read it)
+  double px[3], py[3];   // (n >= 3: both clouds have a row 0 inside the stack, the search read it)
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     px[k] = (double)A.points[3 * (size_t)sa + k];
     py[k] = (double)A.points[3 * (size_t)tgt0 + k];
   }
-  d3f::rigid::fit_from_sums(v, px, py, R, t);
+  if constexpr (kKind == kPlane) {
+    double Tk[12], Tn[12];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    T[4 * r] = R[3 * r];
-    T[4 * r + 1] = R[3 * r + 1];
-    T[4 * r + 2] = R[3 * r + 2];
-    T[4 * r + 3] = t[r];
+    for (int k = 0; k < 12; ++k) Tk[k] = T[k];
+    if (!d3f::plane::plane_step(v, py, Tk, Tn)) {   // the free slide of a single plane, or an overlap of zero normals
+      atomicOr(A.status + p, D3F_ICP_ST_SINGULAR);
+      write_pose(A.T + 16 * (size_t)p, T);
+      A.count[p] = (int)n;
+      A.rmse[p] = rmse;
+      A.done[p] = 1;
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tn[k];
+  } else {
+    double R[9], t[3];
+    d3f::rigid::fit_from_sums(v, px, py, R, t);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      T[4 * r] = R[3 * r];
+      T[4 * r + 1] = R[3 * r + 1];
+      T[4 * r + 2] = R[3 * r + 2];
+      T[4 * r + 3] = t[r];
+    }
   }
   A.prev[2 * p] = fitness;
   A.prev[2 * p + 1] = rmse;
@@ -263,7 +317,7 @@ struct IcpLayout {
   size_t bytes;
 };
 
-IcpLayout icp_layout(void* ws, int P, long long rows) {
+IcpLayout icp_layout(void* ws, int P, long long rows, int kind) {
   IcpLayout l;
   const size_t n = (size_t)(P > 0 ? P : 1);
   l.blocks = (rows > 0 ? rows : 0) / kRows + (long long)n + 1;
@@ -271,33 +325,29 @@ IcpLayout icp_layout(void* ws, int P, long long rows) {
   l.T_cur = c.take<double>(12 * n);
   l.prev = c.take<double>(2 * n);
   l.done = c.take<int32_t>(n);
-  l.partial = c.take<double>((size_t)l.blocks * kSums);
+  l.partial = c.take<double>((size_t)l.blocks * sums_of(kind));
   l.bytes = d3f::align_up(c.off, 256);
   return l;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t d3f_icp_rigid_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows).bytes; }
-
-int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
-                  float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
-                  int64_t rows, const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T,
-                  int32_t* count, double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws,
-                  size_t ws_bytes, void* stream_) {
+template <int kKind>
+int icp_run(const void* grid_ws, const float* points, const float* normals, int Ns, const int32_t* cloud_start, int B,
+            float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P, int64_t rows,
+            const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T, int32_t* count,
+            double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes,
+            void* stream_) {
   if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
       rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) || max_iters < 0 ||
       max_iters > D3F_ICP_MAX_ITERS || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0) ||
       (P > 0 && (!pairs || !T_init || !T || !count || !rmse || !iterations || !status || !ws)))
     return D3F_EINVAL;
   if (P == 0) return D3F_OK;
-  if (ws_bytes < d3f_icp_rigid_ws_bytes(P, rows)) return D3F_EWORKSPACE;
+  if (ws_bytes < icp_layout(nullptr, P, rows, kKind).bytes) return D3F_EWORKSPACE;
   GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
-  IcpLayout l = icp_layout(ws, P, rows);
+  IcpLayout l = icp_layout(ws, P, rows, kKind);
   IcpArgs a;
   a.points = points;
+  a.normals = normals;
   a.cloud_start = cloud_start;
   a.pairs = pairs;
   a.row_start = row_start;
@@ -336,11 +386,39 @@ int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_
   icp_setup_kernel<<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
   D3F_LAUNCH_CHECK();
   for (int k = 0; k <= max_iters; ++k) {
-    icp_search_kernel<<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
-    icp_fit_kernel<<<(unsigned)P, 64, 0, stream>>>(a, k);
+    icp_search_kernel<kKind><<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
+    icp_fit_kernel<kKind><<<(unsigned)P, 64, 0, stream>>>(a, k);
   }
   D3F_LAUNCH_CHECK();
   return D3F_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t d3f_icp_rigid_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kPoint).bytes; }
+size_t d3f_icp_rigid_plane_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kPlane).bytes; }
+
+int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                  float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                  int64_t rows, const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T,
+                  int32_t* count, double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws,
+                  size_t ws_bytes, void* stream_) {
+  return icp_run<kPoint>(grid_ws, points, nullptr, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+                         rows, T_init, max_iters, rel_fitness, rel_rmse, T, count, rmse, iterations, status, trace, ws,
+                         ws_bytes, stream_);
+}
+
+int d3f_icp_rigid_plane(const void* grid_ws, const float* points, const float* normals, int Ns,
+                        const int32_t* cloud_start, int B, float grid_radius, float max_distance, const int32_t* pairs,
+                        const int64_t* row_start, int P, int64_t rows, const double* T_init, int max_iters,
+                        double rel_fitness, double rel_rmse, double* T, int32_t* count, double* rmse,
+                        int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes, void* stream_) {
+  if (!normals) return D3F_EINVAL;
+  return icp_run<kPlane>(grid_ws, points, normals, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+                         rows, T_init, max_iters, rel_fitness, rel_rmse, T, count, rmse, iterations, status, trace, ws,
+                         ws_bytes, stream_);
 }
 
 int d3f_icp_fit_host(const double* sums_host, const double* px_host, const double* py_host, double* out_host) {
@@ -352,6 +430,14 @@ int d3f_icp_fit_host(const double* sums_host, const double* px_host, const doubl
     out_host[4 * a + 3] = t[a];
   }
   out_host[12] = 0.0; out_host[13] = 0.0; out_host[14] = 0.0; out_host[15] = 1.0;
+  return D3F_OK;
+}
+
+int d3f_icp_plane_fit_host(const double* sums_host, const double* py_host, const double* T_k_host, double* T_next_host,
+                           int* singular_host) {
+  if (!sums_host || !py_host || !T_k_host || !T_next_host || !singular_host) return D3F_EINVAL;
+  *singular_host = d3f::plane::plane_step(sums_host, py_host, T_k_host, T_next_host) ? 0 : 1;
+  T_next_host[12] = 0.0; T_next_host[13] = 0.0; T_next_host[14] = 0.0; T_next_host[15] = 1.0;
   return D3F_OK;
 }
 

@@ -42,6 +42,38 @@ struct CellSearch {
   uint32_t mask;
 };
 
+// Bucket headers of the cells lane `sub` of a group of G walks for the query point (qx, qy, qz) in cell (cx, cy, cz) of
+// cloud b (first stored row tgt0, tgt_n rows): per cell the key nk, the first entry st and the length len (0 for a
+// cell it skips).  The 27 cells are dealt round robin to the lanes; the loads are independent.  A cell whose box is
+// farther from the query than the radius holds no accepted point and is skipped (same margin as radius_query_kernel).
+template <int G>
+__device__ __forceinline__ void cell_headers(const CellSearch& S, bool ok, float qx, float qy, float qz, int cx, int cy,
+                                             int cz, int b, int tgt0, int tgt_n, bool per_cloud, double cell,
+                                             double reach, int sub, uint64_t (&nk)[(27 + G - 1) / G],
+                                             int (&st)[(27 + G - 1) / G], int (&len)[(27 + G - 1) / G]) {
+  constexpr int kCells = (27 + G - 1) / G;
+#pragma unroll
+  for (int c = 0; c < kCells; ++c) {
+    const int k = sub + c * G;
+    st[c] = len[c] = 0;
+    nk[c] = 0;
+    if (ok && tgt_n > 0 && k < 27) {
+      const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
+      auto gap = [&](float v, int cc) -> double {
+        const double lo = (double)cc * cell, hi = lo + cell, xx = (double)v;
+        return xx < lo ? lo - xx : (xx > hi ? xx - hi : 0.0);
+      };
+      const double gx = gap(qx, cx + dx), gy = gap(qy, cy + dy), gz = gap(qz, cz + dz);
+      if (gx * gx + gy * gy + gz * gz <= reach * reach) {
+        nk[c] = pack_key(b, cx + dx, cy + dy, cz + dz);
+        const uint32_t bk = per_cloud ? bucket_of_cloud(nk[c], 2u * tgt0, 2u * tgt_n) : bucket_of(nk[c], S.mask);
+        st[c] = S.start[bk];
+        len[c] = S.end[bk] - st[c];
+      }
+    }
+  }
+}
+
 // The query (x, y, z) of target cloud b (first stored row tgt0, tgt_n rows) under the row-major 3x4 transform T, by the
 // G lanes of its group (sub = lane & (G - 1)).  Returns the group's least packed key (d2 bits << 32 | global index of
 // the stored point), ~0 when none is accepted; `mine` is this LANE's least key and `win` the stored point that gave it,
@@ -67,31 +99,10 @@ __device__ __forceinline__ uint64_t nearest_in_cloud(const CellSearch& S, bool& 
     }
   }
 
-  // bucket headers of this lane's cells first (independent loads).  A cell whose box is farther from the query than
-  // the radius holds no accepted point and is skipped (same margin as radius_query_kernel).
   uint64_t nk[kCells];
   int st[kCells], len[kCells];
   int longest = 0;
-#pragma unroll
-  for (int c = 0; c < kCells; ++c) {
-    const int k = sub + c * G;
-    st[c] = len[c] = 0;
-    nk[c] = 0;
-    if (ok && tgt_n > 0 && k < 27) {
-      const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-      auto gap = [&](float v, int cc) -> double {
-        const double lo = (double)cc * cell, hi = lo + cell, xx = (double)v;
-        return xx < lo ? lo - xx : (xx > hi ? xx - hi : 0.0);
-      };
-      const double gx = gap(qx, cx + dx), gy = gap(qy, cy + dy), gz = gap(qz, cz + dz);
-      if (gx * gx + gy * gy + gz * gz <= reach * reach) {
-        nk[c] = pack_key(b, cx + dx, cy + dy, cz + dz);
-        const uint32_t bk = per_cloud ? bucket_of_cloud(nk[c], 2u * tgt0, 2u * tgt_n) : bucket_of(nk[c], S.mask);
-        st[c] = S.start[bk];
-        len[c] = S.end[bk] - st[c];
-      }
-    }
-  }
+  cell_headers<G>(S, ok, qx, qy, qz, cx, cy, cz, b, tgt0, tgt_n, per_cloud, cell, reach, sub, nk, st, len);
 #pragma unroll
   for (int c = 0; c < kCells; ++c) longest = len[c] > longest ? len[c] : longest;
   // the lane's buckets side by side: entry t of each of them is loaded before any is looked at, so a step costs one

@@ -13,7 +13,8 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
   ``gt.log`` format (``evaluate.writelog``);
 * ``refine_transforms`` / ``icp_numpy``  point-to-point ICP over the whole fragments after RANSAC (``ops.icp_rigid``, all
   pairs of a scene in one call) and its NumPy restatement -- ``estimate_transform`` / ``register_scene`` run it when
-  given ``icp=dict(max_distance=...)``.
+  given ``icp=dict(max_distance=...)``; ``estimation='point_to_plane'`` in that dict takes the point-to-plane form with
+  normals from ``ops.estimate_normals`` (NumPy restatement: ``estimate_normals_numpy``).
 
 Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
 target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
@@ -29,7 +30,8 @@ from . import evaluate as ev
 from .common import select_keypoints
 
 RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0)
-ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8      # ops.ICP_ST_*
+ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 1, 2, 4, 8, 16      # ops.ICP_ST_*
+PLANE_PIVOT = 1e-10            # csrc/plane.hpp kPlanePivot
 
 
 def _compact(mutual, src_pts, tgt_pts):
@@ -110,18 +112,121 @@ def _pose44(T, P):
     return out
 
 
-def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6, return_trace=False):
+def normals_scale(radius):
+    """Q = 2^floor(log2(2^20 / radius)) for the f32 ``radius``, in double (frexp is exact)."""
+    return 2.0 ** (np.frexp(2.0 ** 20 / float(np.float32(radius)))[1] - 1)
+
+
+def estimate_normals_numpy(clouds, radius, min_neighbors=3, viewpoint=None, return_moments=False, block=1 << 21):
+    """The contract of ``ops.estimate_normals`` in NumPy (include/d3feat_hip.h): ``clouds`` a list of [n,3] f32 arrays,
+    each searched on its own.  Returns ``(normals f32 [N,3], count int32 [N])`` over the stacked rows and, with
+    ``return_moments``, ``moments int64 [N,10]`` -- the same integers the kernel adds, so counts and moments are equal
+    to the device's bit for bit; the eigenvectors come from ``numpy.linalg.eigh`` in f64 and agree with the kernel's
+    Jacobi solver to rounding.  Brute force within a window of the rows sorted by x: exact, and fast enough for
+    fragments."""
+    r32 = np.float32(radius)
+    if not (0.0 < float(r32) < np.inf) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    r2, Q = r32 * r32, normals_scale(radius)
+    view = np.zeros(3) if viewpoint is None else np.asarray(viewpoint, dtype=np.float32).astype(np.float64).reshape(3)
+    normals, counts, moments = [], [], []
+    for cloud in clouds:
+        p = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        order = np.argsort(p[:, 0], kind='stable')
+        ps = p[order]
+        m = np.zeros((n, 10), dtype=np.int64)
+        reach = float(r32) * 1.001 + 1e-6
+        step = max(1, int(block) // max(n, 1))
+        for s in range(0, n, step):
+            q = ps[s:s + step]
+            lo = np.searchsorted(ps[:, 0], float(q[0, 0]) - reach, 'left')
+            hi = np.searchsorted(ps[:, 0], float(q[-1, 0]) + reach, 'right')
+            t = ps[lo:hi]
+            d = t[None, :, :] - q[:, None, :]                          # p_j - p_i: one f32 subtraction
+            e = q[:, None, :] - t[None, :, :]                          # the search's p_i - p_j
+            d2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+            inside = d2 < r2
+            u = np.where(inside[..., None], np.rint(d.astype(np.float64) * Q).astype(np.int64), 0)
+            ux, uy, uz = u[..., 0], u[..., 1], u[..., 2]
+            m[s:s + step] = np.stack([inside.sum(1), ux.sum(1), uy.sum(1), uz.sum(1), (ux * ux).sum(1),
+                                      (ux * uy).sum(1), (ux * uz).sum(1), (uy * uy).sum(1), (uy * uz).sum(1),
+                                      (uz * uz).sum(1)], 1)
+        back = np.empty(n, dtype=np.int64)
+        back[order] = np.arange(n)
+        m = m[back]
+        nrm = np.zeros((n, 3), dtype=np.float32)
+        live = np.nonzero(m[:, 0] >= int(min_neighbors))[0]
+        if live.size:
+            k = m[live, 0].astype(np.float64)
+            sm = m[live, 1:4].astype(np.float64)
+            S = m[live][:, [4, 5, 6, 5, 7, 8, 6, 8, 9]].astype(np.float64).reshape(-1, 3, 3)
+            C = (S - sm[:, :, None] * sm[:, None, :] / k[:, None, None]) / k[:, None, None] / (Q * Q)
+            w, V = np.linalg.eigh(C)
+            v = V[:, :, 0]
+            dot = (v * (view - p[live].astype(np.float64))).sum(1)
+            first = np.take_along_axis(v, np.argmax(v != 0.0, axis=1)[:, None], 1)[:, 0]
+            v = np.where(((dot < 0) | ((dot == 0) & (first < 0)))[:, None], -v, v)
+            nrm[live] = np.where((w[:, 2] > 0)[:, None], v, 0.0).astype(np.float32)
+        normals.append(nrm)
+        counts.append(m[:, 0].astype(np.int32))
+        moments.append(m)
+    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dtype=dt)
+    res = (cat(normals, (0, 3), np.float32), cat(counts, (0,), np.int32))
+    return res + (cat(moments, (0, 10), np.int64),) if return_moments else res
+
+
+def _plane_step(x, ym, nrm, T, py):
+    """One point-to-plane fit (include/d3feat_hip.h): moving points x matched to fixed points ym with normals nrm under
+    the 4x4 T, about the pivot py -> (T_next, singular).  The pivot test is the kernel's (Cholesky of the normal
+    equations); the solution is a least-squares solve of the stacked system."""
+    R, t = T[:3, :3], T[:3, 3]
+    x = x.astype(np.float64)
+    a = np.stack([((R[r, 0] * x[:, 0] + R[r, 1] * x[:, 1]) + R[r, 2] * x[:, 2]) + t[r] for r in range(3)], 1) - py
+    c = ym.astype(np.float64) - py
+    n = nrm.astype(np.float64)
+    J = np.concatenate([np.cross(a, n), n], 1)
+    r = ((a - c) * n).sum(1)
+    A = J.T @ J
+    floor, U = PLANE_PIVOT * A.diagonal().max(), np.zeros((6, 6))
+    for i in range(6):
+        d = A[i, i] - (U[:i, i] ** 2).sum()
+        if not d > floor:
+            return T, True
+        U[i, i] = np.sqrt(d)
+        U[i, i + 1:] = (A[i, i + 1:] - U[:i, i] @ U[:i, i + 1:]) / U[i, i]
+    v = np.linalg.lstsq(J, -r, rcond=None)[0]
+    ca, sa, cb, sb, cg, sg = np.cos(v[0]), np.sin(v[0]), np.cos(v[1]), np.sin(v[1]), np.cos(v[2]), np.sin(v[2])
+    D = np.array([[cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa],
+                  [sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa],
+                  [-sb, cb * sa, cb * ca]])                            # Rz(gamma) Ry(beta) Rx(alpha)
+    out = np.eye(4)
+    out[:3, :3] = D @ R
+    out[:3, 3] = D @ (t - py) + py + v[3:]
+    return out, False
+
+
+def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6, return_trace=False,
+              normals=None):
     """The contract of ``ops.icp_rigid`` in NumPy f64 (include/d3feat_hip.h): the ``device='cpu'`` path of
     ``refine_transforms`` and the oracle of the GPU tests.  ``clouds``: list of [n,3] f32 arrays; pair p = (moving cloud
     a, fixed cloud b), ``T_init[p]`` maps a into b's frame.  The search is ``preprocess.transform_points`` /
     ``nearest_within``; the fit is the SVD solution of the same least-squares problem the kernel solves with Horn's
     quaternions.  Returns ``(T [P,4,4], count int32 [P], rmse [P], iterations int32 [P], status int32 [P])`` and, with
-    ``return_trace``, ``trace [P, max_iters+1, 2]`` = (n_k, sum d2_k), NaN beyond the stop."""
+    ``return_trace``, ``trace [P, max_iters+1, 2]`` = (n_k, sum d2_k), NaN beyond the stop.  ``normals``: None, or
+    the f32 normals of the stacked clouds [N,3] (or one array per cloud): the point-to-plane form, whose fit follows
+    ``_plane_step`` and which may end with ``ICP_ST_SINGULAR``."""
     from ..datasets.preprocess import nearest_within, transform_points
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     P, K = pairs.shape[0], int(max_iters)
     if K < 0:
         raise ValueError("max_iters must be >= 0")
+    if normals is not None and not isinstance(normals, (list, tuple)):
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        ends = np.cumsum([len(c) for c in clouds])
+        if normals.shape[0] != (ends[-1] if len(ends) else 0):
+            raise ValueError("normals must hold one row per stacked point")
+        normals = [normals[e - len(c):e] for e, c in zip(ends, clouds)]
     T = _pose44(T_init, P)
     count, iters, status = (np.zeros(P, dtype=np.int32) for _ in range(3))
     rmse = np.zeros(P, dtype=np.float64)
@@ -157,6 +262,14 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
             if k == K:
                 break
             px, py = x[0].astype(np.float64), y[0].astype(np.float64)    # pivots: row 0 of either cloud
+            if normals is not None:
+                T[p], singular = _plane_step(x[sel], ym, normals[b][nn[sel]], T[p], py)
+                if singular:
+                    status[p] |= ICP_ST_SINGULAR
+                    break
+                prev = (fitness, r)
+                iters[p] = k + 1
+                continue
             xs, ys = x[sel].astype(np.float64) - px, ym.astype(np.float64) - py
             cx, cy = xs.mean(0), ys.mean(0)
             U, _, Vt = np.linalg.svd((xs - cx).T @ (ys - cy))            # S[a,b] = sum moving'_a fixed'_b
@@ -184,14 +297,25 @@ def _pair_list(keys_or_pairs):
     return np.asarray(out, dtype=np.int64).reshape(-1, 2)
 
 
-def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', **icp):
-    """Point-to-point ICP refinement of fragment-pair poses, all pairs in ONE ``ops.icp_rigid`` call over one
-    ``ops.CloudGrid`` of the fragments.  ``clouds``: list of [n,3] arrays / tensors, fragment k at index k;
+def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', estimation='point_to_point',
+                      normal_radius=None, **icp):
+    """ICP refinement of fragment-pair poses, all pairs in ONE ``ops.icp_rigid`` call over one ``ops.CloudGrid`` of the
+    fragments.  ``estimation``: ``'point_to_point'``, or ``'point_to_plane'`` -- the cell list is then built at
+    ``max(normal_radius, max_distance)`` (``normal_radius`` defaults to ``2 * max_distance``), the normals of all
+    fragments are estimated once (``ops.estimate_normals``, viewpoint at each fragment's origin) and the fit minimises
+    the point-to-plane residual: a handful of iterations from a good RANSAC pose, but it can stall on a low overlap that
+    is mostly one plane and diverge from a poor start -- an option, not the default.
+    ``clouds``: list of [n,3] arrays / tensors, fragment k at index k;
     ``keys_or_pairs``: ``gt.log`` keys ``'i_j'`` or (i, j) tuples with ``T[p]`` ([P,4,4] / [P,3,4]; array or tensor)
     mapping fragment j into fragment i -- j is the moving cloud, i the fixed one.  ``icp``: ``max_iters``,
     ``rel_fitness``, ``rel_rmse`` of ``ops.icp_rigid``.  Returns ``(T [P,4,4] f64, fitness [P] = matched share of j's
     points under the returned T, rmse [P], iterations [P])``: device tensors, or NumPy arrays from ``device='cpu'``
     (``icp_numpy``).  A pair that ends with fewer than 3 matches keeps the pose it had then."""
+    if estimation not in ('point_to_point', 'point_to_plane'):
+        raise ValueError("estimation must be 'point_to_point' or 'point_to_plane', got %r" % (estimation,))
+    plane = estimation == 'point_to_plane'
+    if normal_radius is None:
+        normal_radius = 2.0 * float(max_distance)
     ij = _pair_list(keys_or_pairs)
     ji = ij[:, ::-1].copy()
     if ij.size and (ij.min() < 0 or ij.max() >= len(clouds)):
@@ -201,11 +325,15 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', **i
         arrs = [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
                 for c in clouds]
         Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
+        if plane:
+            icp = dict(icp, normals=estimate_normals_numpy(arrs, normal_radius)[0])
         Tr, count, rmse, iters, _ = icp_numpy(arrs, ji, Tn, max_distance, **icp)
         return Tr, count / np.maximum(lens[ji[:, 0]], 1), rmse, iters
     dev = torch.device(device)
     pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
-    grid = ops.CloudGrid(pts, lens, float(max_distance))
+    grid = ops.CloudGrid(pts, lens, max(float(normal_radius), float(max_distance)) if plane else float(max_distance))
+    if plane:
+        icp = dict(icp, normals=ops.estimate_normals(grid, None, normal_radius)[0])
     Tr, count, rmse, iters, _ = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
                                               max_distance, **icp)
     fitness = count.double() / torch.as_tensor(np.maximum(lens[ji[:, 0]], 1), dtype=torch.float64, device=dev)

@@ -2820,6 +2820,7 @@ def nearest_pairs(grid_or_points, lens, pairs, transforms, radius, lanes=0):
 ICP_MAX_ITERS = 1024
 ICP_BLOCK_ROWS = 512
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8
+ICP_ST_SINGULAR = 16   # point-to-plane: singular normal equations (one plane's free slide, zero normals)
 
 
 def icp_rigid_bytes(rows, found=None):
@@ -2829,8 +2830,68 @@ def icp_rigid_bytes(rows, found=None):
     return nearest_pairs_bytes(rows, found) - 4 * rows + 2 * 136 * (-(-rows // ICP_BLOCK_ROWS))
 
 
+def icp_plane_bytes(rows, found=None):
+    """Algorithmic bytes of ONE point-to-plane search of ``rows`` rows: ``icp_rigid_bytes`` with 232 bytes of sums (29
+    f64) per workgroup in place of 136, plus the 12-byte normal of every matched row (``found`` of them, by default one
+    per row)."""
+    rows = int(rows)
+    return (icp_rigid_bytes(rows, found) + 2 * (232 - 136) * (-(-rows // ICP_BLOCK_ROWS))
+            + 12 * (rows if found is None else int(found)))
+
+
+def estimate_normals_bytes(n, neighbors=None):
+    """Algorithmic bytes of the normals of ``n`` points: the point (12), the (start, end) headers of 27 buckets (216),
+    the stored point and cell key of every candidate the accepted cells hold (24 each; ``neighbors`` of them in all, by
+    default the point itself), the normal (12) and the count (4)."""
+    n = int(n)
+    return n * (12 + 27 * 8 + 12 + 4) + 24 * (n if neighbors is None else int(neighbors))
+
+
+def estimate_normals(grid_or_points, lens, radius, min_neighbors=3, viewpoint=None, return_moments=False):
+    """Surface normal of every point of the stacked clouds (d3f_estimate_normals): the eigenvector of the smallest
+    eigenvalue of the covariance of the point's neighbours within ``radius`` IN ITS OWN CLOUD (itself included), turned
+    towards ``viewpoint`` (3 numbers, the same point in every cloud's own frame; default the origin).
+
+    ``grid_or_points``, ``lens``: as in ``nearest_pairs`` -- a ``RadiusGrid`` / ``CloudGrid`` with ``radius`` at most
+    its own, or the stacked points with their lengths.  Returns device tensors ``(normals [N,3] f32, count [N] int32)``
+    in input row order and, with ``return_moments``, ``moments [N,10] int64``.  A point with fewer than
+    ``min_neighbors`` neighbours, or whose neighbours coincide, gets the normal (0, 0, 0).  The moments are integer sums
+    (include/d3feat_hip.h), so the result does not depend on the order in which the cell list holds the points: it is
+    bit-identical from run to run, for a cloud alone or stacked among others, and for any cell size."""
+    if not (0.0 < float(radius) < float("inf")) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
+        grid = grid_or_points
+        if float(radius) > grid.radius:
+            raise RuntimeError("radius %g exceeds the cell list's %g" % (float(radius), grid.radius))
+    else:
+        if lens is None:
+            raise ValueError("lens is required with stacked points")
+        grid = CloudGrid(grid_or_points, lens, radius)
+    dev = grid.supports.device
+    cloud_start = getattr(grid, "cloud_start", None)
+    if cloud_start is None:
+        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
+    view = None
+    if viewpoint is not None:
+        view = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float32).reshape(-1))
+        if view.shape != (3,) or not np.isfinite(view).all():
+            raise ValueError("viewpoint must be 3 finite numbers")
+    N = grid.Ns
+    normals = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    moments = torch.empty((N, 10), dtype=torch.int64, device=dev) if return_moments else None
+    if N:
+        with _region("estimate_normals[N=%d]" % N, estimate_normals_bytes(N)):
+            _native.check(_native.lib().d3f_estimate_normals(
+                _p(grid.ws), _p(grid.supports), N, _p(cloud_start), int(grid.s_len.numel()), grid.radius, float(radius),
+                int(min_neighbors), view.ctypes.data if view is not None else None, _p(normals), _p(count),
+                _p(moments), _p(grid.status.word), _stream()), "d3f_estimate_normals")
+    return (normals, count, moments) if return_moments else (normals, count)
+
+
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
-              return_trace=False, rows=None):
+              return_trace=False, rows=None, normals=None):
     """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).
 
     ``grid_or_points``, ``lens``, ``pairs``: as in ``nearest_pairs`` -- pair p = (MOVING cloud a, FIXED cloud b) and
@@ -2844,7 +2905,14 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     ``T``; ``return_trace=True`` appends ``trace [P, max_iters+1, 2]`` f64 = (n_k, sum d2_k) per search (NaN beyond the
     stop).  Bit-identical from run to run and for a pair alone or inside any batch.  No read-back when the lengths and
     pairs are known on the host, or when ``rows`` -- a host bound on the moving rows of all pairs together -- comes with
-    device ``pairs`` (the form a captured graph takes; a pair reaching beyond it gets ``ICP_ST_PAIR``)."""
+    device ``pairs`` (the form a captured graph takes; a pair reaching beyond it gets ``ICP_ST_PAIR``).
+
+    ``normals``: None, or the f32 [N,3] normals of the stacked points (``estimate_normals``) -- the fit then minimises
+    the POINT-TO-PLANE residual against the fixed cloud's normals (d3f_icp_rigid_plane; Open3D's
+    TransformationEstimationPointToPlane).  Search, count, rmse, stopping rule and trace keep their meaning; a pair
+    whose 6x6 normal equations are singular (the overlap is one plane, or has only zero normals) stops at its current
+    pose with ``ICP_ST_SINGULAR``.  It converges in a handful of iterations from a good pose and can stall or diverge
+    where point-to-point does not -- on a low overlap that is mostly one plane, or from a poor start."""
     if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
         grid = grid_or_points
         if float(max_distance) > grid.radius:
@@ -2892,13 +2960,22 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     rmse = torch.empty(P, dtype=torch.float64, device=dev)
     trace = torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev) if return_trace else None
     L = _native.lib()
-    nbytes = L.d3f_icp_rigid_ws_bytes(P, rows)
+    nrm = None
+    if normals is not None:
+        nrm = _f32(normals, "normals")
+        if tuple(nrm.shape) != (grid.Ns, 3) or nrm.device != dev:
+            raise ValueError("normals must be [%d,3] on the points' device, got %s" % (grid.Ns, tuple(nrm.shape)))
+    plane = nrm is not None
+    name = "d3f_icp_rigid_plane" if plane else "d3f_icp_rigid"
+    nbytes = getattr(L, name + "_ws_bytes")(P, rows)
     ws = _ws(nbytes, dev)
-    with _region("icp_rigid[P=%d,rows=%d,iters<=%d]" % (P, rows, K), (K + 1) * icp_rigid_bytes(rows)):
-        _native.check(L.d3f_icp_rigid(
-            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
+    head = (_p(grid.ws), _p(grid.supports)) + ((_p(nrm),) if plane else ())
+    with _region("%s[P=%d,rows=%d,iters<=%d]" % (name[4:], P, rows, K),
+                 (K + 1) * (icp_plane_bytes if plane else icp_rigid_bytes)(rows)):
+        _native.check(getattr(L, name)(
+            *head, grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
             _p(row_start), P, rows, _p(tf), K, float(rel_fitness), float(rel_rmse), _p(T), _p(count), _p(rmse),
-            _p(iterations), _p(status), _p(trace), _p(ws), nbytes, _stream()), "d3f_icp_rigid")
+            _p(iterations), _p(status), _p(trace), _p(ws), nbytes, _stream()), name)
     res = (T, count, rmse, iterations, status)
     return res + (trace,) if return_trace else res
 

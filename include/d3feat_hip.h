@@ -818,6 +818,60 @@ int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_
 int d3f_icp_fit_host(const double* sums_host, const double* px_host, const double* py_host, double* out_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Surface normals of every point of the stacked clouds of a cell list, and point-to-plane ICP with them.  The reference
+ * leaves both to Open3D on the CPU (estimate_normals, TransformationEstimationPointToPlane).
+ *
+ * d3f_estimate_normals.  The cell list (grid_ws, grid_radius), points, Ns, cloud_start and B are those of
+ * d3f_nearest_pairs; radius <= grid_radius; min_neighbors >= 1; viewpoint_host: 3 floats ON THE HOST, the same point in
+ * every cloud's own frame, NULL for the origin.  The fill order of a bucket is decided by atomics, so the result is made
+ * independent of the order in which neighbours are met BY CONSTRUCTION:
+ *   neighbours of point i: the points j of the SAME cloud, i itself included, with
+ *        d2 = ((dx dx) + (dy dy)) + (dz dz) < radius * radius   (f32 without FMA, f32 product, strict: the rule of the
+ *        other searches; the cell key carries the cloud index, so clouds that overlap in coordinates never mix);
+ *   Q  = 2^floor(log2(2^20 / radius)), computed on the host in double;
+ *   u  = (int64) rint((double)(p_j - p_i) Q) per component, p_j - p_i ONE f32 subtraction, ties to even; |u| <= 2^20;
+ *   moments (int64): n, sum u_x, sum u_y, sum u_z, sum u_x u_x, u_x u_y, u_x u_z, u_y u_y, u_y u_z, u_z u_z -- integer
+ *        addition commutes, so lanes, groups and bucket order cannot change them (products < 2^40: 2^22 neighbours fit);
+ *   C  = (S - s s^T / n) / n in f64; the normal is the unit eigenvector of C's smallest eigenvalue in f64 (cyclic
+ *        Jacobi, a fixed number of sweeps; csrc/plane.hpp), rounded to f32;
+ *   sign: n . (viewpoint - p_i) >= 0 (f64); when that is exactly 0 the first non-zero component is positive;
+ *   n < min_neighbors, or a largest eigenvalue that is not positive: the normal is (0, 0, 0).
+ * Outputs in input row order: normals [Ns,3] f32, count [Ns] int32 (= n), optional (NULL to skip) moments [Ns,10] int64.
+ * Rows beyond cloud_start[B] get zeros.  A point outside the addressable cell grid is in no cell list: it has count 0
+ * and sets D3F_ST_CELL_RANGE in *status.  One launch on `stream`, no host synchronisation, no allocation.
+ * d3f_normal_from_moments_host: host-only twin of everything after the moments (the same inline code): m[10], Q and
+ * to_view = viewpoint - p_i -> out[3]; n < 1 gives zeros (min_neighbors is the caller's test).
+ *
+ * d3f_icp_rigid_plane: d3f_icp_rigid with `normals` [Ns,3] f32 in input row order (the normals of the FIXED cloud are
+ * used).  Setup, search, n_k, sum d2, fitness, rmse (Open3D's inlier_rmse is the point distance under every estimation
+ * method), the stopping rule, count, rmse, trace and the reduction orders are those of d3f_icp_rigid.  Per accepted
+ * row, in f64, with nrm the normal of the matched fixed point y and py row 0 of the fixed cloud:
+ *   a = (((T0 x + T1 y) + T2 z) + T3) - py per component (T_k x in f64, NOT the f32 query), c = y - py,
+ *   J = [a x nrm, nrm] (6), r = (a - c) . nrm;
+ *   sums[29] = { n, the 21 upper entries of sum J J^T row by row, sum J r (6), sum d2 }.
+ * Fit: Cholesky of the 6x6 in f64.  A pivot <= 1e-10 max_i A_ii stops the pair at its current pose with
+ * D3F_ICP_ST_SINGULAR (the free slide of a single plane, or an overlap of zero normals).  Otherwise
+ *   v = -A^-1 sum J r = (alpha, beta, gamma, t_d); R_d = Rz(gamma) Ry(beta) Rx(alpha) (Open3D's
+ *   TransformVector6dToMatrix4d); R_{k+1} = R_d R_k; t_{k+1} = R_d (t_k - py) + py + t_d.
+ * A zero normal contributes zeros to the fit and still counts in n_k.  Workspace: d3f_icp_rigid_plane_ws_bytes(P, rows).
+ * d3f_icp_plane_fit_host: host-only twin of the fit: sums[29], py[3], T_k [12] (row-major 3x4) -> T_next [16]
+ * (row-major 4x4; T_k when singular), *singular = 0 / 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_ICP_ST_SINGULAR 16  /* point-to-plane: the 6x6 normal equations are singular at the stopping iteration */
+int d3f_estimate_normals(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                         float grid_radius, float radius, int min_neighbors, const float* viewpoint_host,
+                         float* normals, int32_t* count, int64_t* moments, int32_t* status, void* stream);
+int d3f_normal_from_moments_host(const int64_t* m_host, double Q, const double* to_view_host, float* out_host);
+size_t d3f_icp_rigid_plane_ws_bytes(int P, int64_t rows);
+int d3f_icp_rigid_plane(const void* grid_ws, const float* points, const float* normals, int Ns,
+                        const int32_t* cloud_start, int B, float grid_radius, float max_distance, const int32_t* pairs,
+                        const int64_t* row_start, int P, int64_t rows, const double* T_init, int max_iters,
+                        double rel_fitness, double rel_rmse, double* T, int32_t* count, double* rmse,
+                        int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes, void* stream);
+int d3f_icp_plane_fit_host(const double* sums_host, const double* py_host, const double* T_k_host, double* T_next_host,
+                           int* singular_host);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.

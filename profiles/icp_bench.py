@@ -1,6 +1,6 @@
 """Times ops.icp_rigid (d3f_icp_rigid) on one 3DMatch-sized scene against what the package offered before it:
 
-    python profiles/icp_bench.py [--fragments 60] [--out FILE]
+    python profiles/icp_bench.py [--fragments 60] [--no-composed] [--out FILE]
 
 Scene and pairs: those of profiles/nearest_pairs_bench.py (F fragments of ~25 k points at 0.03 m, every overlapping
 pair, one cell list over the scene); every pair starts from its ground truth perturbed by 1 degree / 0.02 m and is
@@ -13,8 +13,12 @@ refined at max_distance = 1.25 voxels, the radius of the search floor.
 * search floor -- one d3f_nearest_pairs launch over the same rows and radius; against it ONE fused iteration (search
   launch + fit launch), taken from runs whose tolerances are 0 so that no pair stops early: (t(K = 8) - t(K = 0)) / 8.
 
+* point-to-plane -- one d3f_estimate_normals launch over the scene (cell list and radius of 2 max_distance), and ONE
+  point-to-plane iteration (d3f_icp_rigid_plane, the same K = 8 / K = 0 difference) next to the point-to-point one on
+  the same cell list, rows and poses.
+
 Device times are events around back-to-back calls after a warm-up, medians over the repetitions, the arms of a
-comparison taking turns in one process.
+comparison taking turns in one process.  ``--no-composed`` leaves the composed baseline out (it takes most of the run).
 """
 import argparse
 import json
@@ -128,6 +132,7 @@ def main():
     ap.add_argument('--fragments', type=int, default=60)
     ap.add_argument('--raw', type=int, default=1200000)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--no-composed', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     dev = torch.device('cuda')
@@ -166,42 +171,42 @@ def main():
 
     # ---- the same answers first
     fused = ops.icp_rigid(grid, None, pr, Ti, RADIUS, **kw)
-    comp = composed_icp(grid, lens_dev, pr, Ti, RADIUS, 30, 1e-6, 1e-6)
     torch.cuda.synchronize()
     grid.status.raise_if_set()
-    it_f, it_c = fused[3].cpu().numpy(), comp[3].cpu().numpy()
-    same = it_f == it_c
-    dT = (fused[0] - comp[0]).abs().amax(dim=(1, 2)).cpu().numpy()
-    say("fused against composed: %d of %d pairs stop after the same number of fits; max |T - T_composed| over those "
-        "%.2e; fits per pair %d..%d (mean %.1f), status != 0 on %d pairs" % (
-            same.sum(), len(same), dT[same].max() if same.any() else float('nan'), it_f.min(), it_f.max(), it_f.mean(),
-            int((fused[4] != 0).sum())))
-    searches = int((it_f + 1).sum())
+    it_f = fused[3].cpu().numpy()
     found = int(fused[1].sum())
-    say("searched rows over the run (pairs that stopped leave): %.1f M in %d pair-searches" % (
-        float(((it_f + 1) * lens[pairs[:, 0]]).sum()) / 1e6, searches))
-
-    # ---- per scene: fused against composed
+    say("fits per pair %d..%d (mean %.1f), status != 0 on %d pairs; searched rows over the run (pairs that stopped "
+        "leave): %.1f M in %d pair-searches" % (it_f.min(), it_f.max(), it_f.mean(), int((fused[4] != 0).sum()),
+                                                float(((it_f + 1) * lens[pairs[:, 0]]).sum()) / 1e6,
+                                                int((it_f + 1).sum())))
     ms, spread = medians({"fused": lambda: ops.icp_rigid(grid, None, pr, Ti, RADIUS, **kw)}, a.reps)
-    wall = []
-    for _ in range(max(2, a.reps // 2)):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        composed_icp(grid, lens_dev, pr, Ti, RADIUS, 30, 1e-6, 1e-6)
-        torch.cuda.synchronize()
-        wall.append(1e3 * (time.perf_counter() - t0))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     ops.icp_rigid(grid, None, pr, Ti, RADIUS, **kw)
     torch.cuda.synchronize()
     fused_wall = 1e3 * (time.perf_counter() - t0)
-    comp_ms, fused_ms = float(np.median(wall)), max(ms["fused"], fused_wall)
+    fused_ms, comp_ms = max(ms["fused"], fused_wall), None
     say("per scene, defaults (30 / 1e-6 / 1e-6):")
     say("  fused     %9.3f ms  (device events, median of %d, %.3f..%.3f; host wall of one call %.3f ms)" % (
         ms["fused"], a.reps, spread["fused"][0], spread["fused"][1], fused_wall))
-    say("  composed  %9.3f ms  (host wall incl. synchronise, median of %d, %.3f..%.3f)" % (
-        comp_ms, len(wall), min(wall), max(wall)))
-    say("  ratio composed / fused = %.2f  (fused taken at the larger of its two figures)" % (comp_ms / fused_ms))
+    if not a.no_composed:
+        comp = composed_icp(grid, lens_dev, pr, Ti, RADIUS, 30, 1e-6, 1e-6)
+        it_c = comp[3].cpu().numpy()
+        same = it_f == it_c
+        dT = (fused[0] - comp[0]).abs().amax(dim=(1, 2)).cpu().numpy()
+        say("fused against composed: %d of %d pairs stop after the same number of fits; max |T - T_composed| over "
+            "those %.2e" % (same.sum(), len(same), dT[same].max() if same.any() else float('nan')))
+        wall = []
+        for _ in range(max(2, a.reps // 2)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            composed_icp(grid, lens_dev, pr, Ti, RADIUS, 30, 1e-6, 1e-6)
+            torch.cuda.synchronize()
+            wall.append(1e3 * (time.perf_counter() - t0))
+        comp_ms = float(np.median(wall))
+        say("  composed  %9.3f ms  (host wall incl. synchronise, median of %d, %.3f..%.3f)" % (
+            comp_ms, len(wall), min(wall), max(wall)))
+        say("  ratio composed / fused = %.2f  (fused taken at the larger of its two figures)" % (comp_ms / fused_ms))
 
     # ---- one fused iteration against the search floor (launches only, buffers made beforehand)
     L, stream, p_ = _native.lib(), torch.cuda.current_stream().cuda_stream, ops._p
@@ -240,9 +245,59 @@ def main():
     say("algorithmic bytes per search at the final poses' %d matched rows: nearest_pairs %.1f MB, icp_rigid %.1f MB "
         "(no 4-byte index, 2 x 136 B of sums per %d rows); %.2f TB/s at the fused iteration's time" % (
             found, nb_floor / 1e6, nb_icp / 1e6, ops.ICP_BLOCK_ROWS, nb_icp / (one * 1e-3) / 1e12))
+
+    # ---- point-to-plane: the normals launch, and one iteration next to the point-to-point one on the same cell list
+    r_n = 2.0 * RADIUS
+    grid_n = ops.CloudGrid(pts, lens, r_n)
+    normals = torch.empty((grid_n.Ns, 3), dtype=torch.float32, device=dev)
+    n_cnt = torch.empty(grid_n.Ns, dtype=torch.int32, device=dev)
+    nbytes_p = L.d3f_icp_rigid_plane_ws_bytes(P, rows)
+    ws_p = torch.empty(nbytes_p, dtype=torch.uint8, device=dev)
+
+    def estimate():
+        _native.check(L.d3f_estimate_normals(p_(grid_n.ws), p_(pts), grid_n.Ns, p_(grid_n.cloud_start), B, grid_n.radius,
+                                             r_n, 3, None, p_(normals), p_(n_cnt), None, p_(grid_n.status.word),
+                                             stream), "d3f_estimate_normals")
+
+    def icp_on(K, plane):
+        if plane:
+            _native.check(L.d3f_icp_rigid_plane(
+                p_(grid_n.ws), p_(pts), p_(normals), grid_n.Ns, p_(grid_n.cloud_start), B, grid_n.radius, RADIUS, p_(pr),
+                p_(rs), P, rows, p_(tf12), K, 0.0, 0.0, p_(To), p_(oc), p_(orm), p_(oi), p_(os_), None, p_(ws_p),
+                nbytes_p, stream), "d3f_icp_rigid_plane")
+        else:
+            _native.check(L.d3f_icp_rigid(
+                p_(grid_n.ws), p_(pts), grid_n.Ns, p_(grid_n.cloud_start), B, grid_n.radius, RADIUS, p_(pr), p_(rs), P,
+                rows, p_(tf12), K, 0.0, 0.0, p_(To), p_(oc), p_(orm), p_(oi), p_(os_), None, p_(ws), nbytes, stream),
+                "d3f_icp_rigid")
+
+    estimate()
+    torch.cuda.synchronize()
+    neighbours = int(n_cnt.long().sum())
+    msp, spreadp = medians({"normals": estimate, "point K=0": lambda: icp_on(0, False),
+                            "point K=8": lambda: icp_on(8, False), "plane K=0": lambda: icp_on(0, True),
+                            "plane K=8": lambda: icp_on(8, True)}, max(a.reps, 7))
+    grid_n.status.raise_if_set()
+    one_point, one_plane = (msp["point K=8"] - msp["point K=0"]) / 8, (msp["plane K=8"] - msp["plane K=0"]) / 8
+    plane_run = ops.icp_rigid(grid_n, None, pr, Ti, RADIUS, normals=normals, **kw)
+    it_p = plane_run[3].cpu().numpy()
+    say("point-to-plane, cell list and normals at %.4f m (%d points, %.1f neighbours per point):" % (
+        r_n, grid_n.Ns, neighbours / max(grid_n.Ns, 1)))
+    say("  d3f_estimate_normals, one launch          %8.3f ms  (%.3f..%.3f); %.1f MB algorithmic = %.2f TB/s" % (
+        msp["normals"], spreadp["normals"][0], spreadp["normals"][1],
+        ops.estimate_normals_bytes(grid_n.Ns, neighbours) / 1e6,
+        ops.estimate_normals_bytes(grid_n.Ns, neighbours) / (msp["normals"] * 1e-3) / 1e12))
+    say("  one point-to-point iteration on this list %8.3f ms  (K = 0: %.3f, K = 8: %.3f)" % (
+        one_point, msp["point K=0"], msp["point K=8"]))
+    say("  one point-to-plane iteration              %8.3f ms  (K = 0: %.3f, K = 8: %.3f) = %.3f x point-to-point" % (
+        one_plane, msp["plane K=0"], msp["plane K=8"], one_plane / one_point))
+    say("  defaults (30 / 1e-6 / 1e-6): point-to-plane fits per pair %d..%d (mean %.1f) against %d..%d (mean %.1f); "
+        "status != 0 on %d pairs" % (it_p.min(), it_p.max(), it_p.mean(), it_f.min(), it_f.max(), it_f.mean(),
+                                     int((plane_run[4] != 0).sum())))
     say(json.dumps({"fragments": a.fragments, "pairs": P, "rows": rows, "fused_ms": fused_ms,
                     "composed_ms": comp_ms, "floor_ms": ms["floor"], "fused_iteration_ms": one,
-                    "iteration_over_floor": one / ms["floor"]}))
+                    "iteration_over_floor": one / ms["floor"], "normals_ms": msp["normals"],
+                    "point_iteration_ms": one_point, "plane_iteration_ms": one_plane}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, 'w') as f:
