@@ -37,7 +37,8 @@ struct RevTest {
 };
 
 // Feature gathers + MFMAs of one prepared chunk: lane l holds entry l of the (compacted) list -- its query index n_c
-// (Nq = none), that query's position and 1/nn (0 = none); `NSTEPS` 16-entry MFMA steps cover the live prefix.
+// (Nq = none), that query's position RELATIVE TO THE ROW'S SUPPORT (q - s, exact; the centres are then -kp) and 1/nn
+// (0 = none); `NSTEPS` 16-entry MFMA steps cover the live prefix.
 template <int CV, int NSTEPS>
 __device__ __forceinline__ void dxg_core(int n_c, float qx, float qy, float qz, float inn, __amdgpu_buffer_rsrc_t rs_g,
                                          unsigned row_bytes, unsigned col_off, float cx, float cy, float cz,
@@ -94,7 +95,7 @@ __device__ __forceinline__ void dxg_table_chunk(int n, float qx, float qy, float
   if (cnt == 0) return;
   const int rank = __popcll(m & ((1ull << lane) - 1ull));
   if (member) {
-    scr4[rank] = make_float4(qx, qy, qz, __int_as_float(n));
+    scr4[rank] = make_float4(qx - rt.sx, qy - rt.sy, qz - rt.sz, __int_as_float(n));
     scr1[rank] = has_nn ? 1.0f / nnv : 1.0f;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
   const int li = lane & 15, lg = lane >> 4;
   const int s0 = blockIdx.x * 16;
   const bool klive = li < K;
-  // centre of kernel point li as seen from the row's point s: |(s - q) - kp| = |q - (s - kp)|
+  // kernel point li as seen from the row's point s: |(s - q) - kp| = |(q - s) - (-kp)|
   const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
               kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
   const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(q_pts, (unsigned)Nq * 12u);
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         for (int r = 0; r < CV; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (s < Ns) {
           const float sx = s_pts[3 * (size_t)s + 0], sy = s_pts[3 * (size_t)s + 1], sz = s_pts[3 * (size_t)s + 2];
-          const float cx = sx - kx, cy = sy - ky, cz = sz - kz;
+          const float cx = -kx, cy = -ky, cz = -kz;
           const RevTest rt = {last_key, sx, sy, sz, (unsigned)s, rev_r2};
           int32_t* st = ch == 0 ? status : nullptr;
           const uint64_t lk_i = ((uint64_t)(unsigned)lkhi[0] << 32) | (unsigned)lklo[0];
@@ -296,7 +297,6 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         const int beg = __builtin_amdgcn_readfirstlane(rev_ptr[s]);
         const int end = __builtin_amdgcn_readfirstlane(rev_ptr[s + 1]);
         const float sx = s_pts[3 * (size_t)s + 0], sy = s_pts[3 * (size_t)s + 1], sz = s_pts[3 * (size_t)s + 2];
-        const float cx = sx - kx, cy = sy - ky, cz = sz - kz;
         for (int c0 = beg; c0 < end; c0 += 64) {
           const int rem = min(end - c0, 64);
           const int n = lane < rem ? min(max(rev_ent[(size_t)c0 + lane], 0), Nq) : Nq;
@@ -306,7 +306,8 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
           const float qz = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)n * 12u + 8u, 0, 0));
           const float nnv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)n * 4u, 0, 0));
           const float inn = (lane < rem && n < Nq) ? (nn ? 1.0f / nnv : 1.0f) : 0.0f;
-          dxg_core_n<CV>((rem + 15) >> 4, n, qx, qy, qz, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
+          dxg_core_n<CV>((rem + 15) >> 4, n, qx - sx, qy - sy, qz - sz, inn, rs_g, row_bytes, col_off, -kx, -ky, -kz,
+                         inv_extent, lg, acc);
         }
       }
       store_wf_tile<CV>(tile + (wave * 4 + i) * RS, li, lg, acc);

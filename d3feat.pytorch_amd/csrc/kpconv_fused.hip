@@ -361,18 +361,16 @@ __global__ __launch_bounds__(256) void kpconv_bwd_dx_kernel(
     const int q = q0 + ql;
     if (q >= Nq || (dbg & 32)) continue;
     const float qx = q_pts[3 * (size_t)q + 0], qy = q_pts[3 * (size_t)q + 1], qz = q_pts[3 * (size_t)q + 2];
-    float cx[4], cy[4], cz[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { cx[s] = qx + kpx[s]; cy[s] = qy + kpy[s]; cz[s] = qz + kpz[s]; }
     const int32_t* row = idx + (size_t)q * H;
     const float* gq = gw + ql * RS;
     for (int h0 = 16 * ih; h0 < H; h0 += 16 * hsplit) {
       const int h = h0 + li;
       const int n = (int)min((unsigned)(h < H ? row[h] : Ns), (unsigned)Ns);
-      const float4 sp = buf_load_f4(rs_sp, (unsigned)n * 16u);
+      float4 sp = buf_load_f4(rs_sp, (unsigned)n * 16u);
+      sp.x -= qx; sp.y -= qy; sp.z -= qz;   // relative to the query first (exact), then to the kernel points
       float wk[4];
 #pragma unroll
-      for (int s = 0; s < 4; ++s) wk[s] = n < Ns ? kp_influence(sp, cx[s], cy[s], cz[s], inv_extent) : 0.0f;
+      for (int s = 0; s < 4; ++s) wk[s] = n < Ns ? kp_influence(sp, kpx[s], kpy[s], kpz[s], inv_extent) : 0.0f;
       int nrow[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) nrow[r] = __shfl(n, 4 * lg + r, 64);

@@ -40,19 +40,20 @@ struct SmallAgg {
       rowsum += xo[c];
     }
     nn = fmaxf((float)__popcll(__ballot(rowsum > 0.0f)), 1.0f);   // (#neighbors with a positive feature sum, blocks.py:377)
-    rec[lane] = make_float4(sx, sy, sz, xo[0]);
+    // (relative to the query, which is exact for neighbouring points; the kernel point is subtracted from that)
+    const float qx = q_pts[3 * (size_t)q + 0], qy = q_pts[3 * (size_t)q + 1], qz = q_pts[3 * (size_t)q + 2];
+    rec[lane] = make_float4(sx - qx, sy - qy, sz - qz, xo[0]);
 #pragma unroll
     for (int c = 1; c < CIN; ++c) recx[(c - 1) * 64 + lane] = xo[c];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const float cx = q_pts[3 * (size_t)q + 0] + kx, cy = q_pts[3 * (size_t)q + 1] + ky, cz = q_pts[3 * (size_t)q + 2] + kz;
 #pragma unroll
     for (int c = 0; c < CIN; ++c) wf[c] = 0.0f;
     const int ng = (H + 3) >> 2;
     for (int g = 0; g < ng; ++g) {
       const int src = 4 * g + lg;  // < 64
       const float4 sp = rec[src];
-      const float w = kp_influence(sp, cx, cy, cz, inv_extent);
+      const float w = kp_influence(sp, kx, ky, kz, inv_extent);
       wf[0] = fmaf(w, sp.w, wf[0]);
 #pragma unroll
       for (int c = 1; c < CIN; ++c) wf[c] = fmaf(w, recx[(c - 1) * 64 + src], wf[c]);

@@ -61,8 +61,11 @@ __device__ __forceinline__ float4 buf_load_vec<4>(__amdgpu_buffer_rsrc_t r, unsi
 // clamps to exactly 0 without a select in the inner loop.
 constexpr float kFarKernelPoint = 1e18f;
 
-// influence of the kernel point on a neighbor at sp; (cx,cy,cz) = query + kernel point (blocks.py:283-336):
-//   w = max(0, 1 - sqrt(|sp - q - kp|^2)/extent)
+// influence of the kernel point at (cx,cy,cz) on a neighbor whose position RELATIVE TO THE QUERY is sp
+// (blocks.py:283-336):   w = max(0, 1 - sqrt(|(s - q) - kp|^2)/extent)
+// The caller subtracts the query first, as the reference does: s - q of two neighbouring float32 points is exact
+// wherever the scene lies, while q + kp rounds the kernel point to the spacing of the coordinates (3e-5 at 300 m
+// against an extent of centimetres: 1e-4 of a weight).
 // The correctly rounded sqrtf and division expand to ~10 VALU instructions EACH on gfx950 and made the aggregation
 // VALU-bound; the hardware v_sqrt_f32 (1 ulp) and a reciprocal multiply differ from the reference by <= 2 ulp of a
 // weight in [0,1] (tests bound the effect at 2e-5 of the output range).
@@ -93,10 +96,11 @@ struct QueryGather {
 };
 
 template <int CV, int NSTEPS, typename Flush>
-__device__ __forceinline__ void aggregate_wave_n(const int (&nall)[4], const float (&cqx)[4], const float (&cqy)[4],
-                                                 const float (&cqz)[4], __amdgpu_buffer_rsrc_t rs_sp,
-                                                 __amdgpu_buffer_rsrc_t rs_x, unsigned row_bytes, unsigned col_off,
-                                                 float inv_extent, int lg, int lane, float* nn_lds, Flush&& flush) {
+__device__ __forceinline__ void aggregate_wave_n(const int (&nall)[4], const float (&qx)[4], const float (&qy)[4],
+                                                 const float (&qz)[4], float kx, float ky, float kz,
+                                                 __amdgpu_buffer_rsrc_t rs_sp, __amdgpu_buffer_rsrc_t rs_x,
+                                                 unsigned row_bytes, unsigned col_off, float inv_extent, int lg, int lane,
+                                                 float* nn_lds, Flush&& flush) {
   constexpr int NG = 4 * NSTEPS;
   QueryGather<CV, NG> qg[1];  // (a second register set for cross-query prefetch cost an occupancy step: slower)
   auto gather = [&](QueryGather<CV, NG>& d, int nrow) {
@@ -115,16 +119,18 @@ __device__ __forceinline__ void aggregate_wave_n(const int (&nall)[4], const flo
       const float f = wave_sum(c.sp.w);
       if (lane == 0) nn_lds[i] = fmaxf(f, 1.0f);
     }
+    // the lane's own neighbor relative to the query, once per query (a shadow lane holds -q: its features are zeros)
+    const float rx = c.sp.x - qx[i], ry = c.sp.y - qy[i], rz = c.sp.z - qz[i];
     f32x4 acc[CV];
 #pragma unroll
     for (int r = 0; r < CV; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       float4 sp;
-      sp.x = __shfl(c.sp.x, 4 * g + lg, 64);
-      sp.y = __shfl(c.sp.y, 4 * g + lg, 64);
-      sp.z = __shfl(c.sp.z, 4 * g + lg, 64);
-      const float w = kp_influence(sp, cqx[i], cqy[i], cqz[i], inv_extent);
+      sp.x = __shfl(rx, 4 * g + lg, 64);
+      sp.y = __shfl(ry, 4 * g + lg, 64);
+      sp.z = __shfl(rz, 4 * g + lg, 64);
+      const float w = kp_influence(sp, kx, ky, kz, inv_extent);
 #pragma unroll
       for (int r = 0; r < CV; ++r)
         acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, vget<CV>(c.xv[g], r), acc[r], 0, 0, 0);
@@ -133,12 +139,11 @@ __device__ __forceinline__ void aggregate_wave_n(const int (&nall)[4], const flo
   }
 }
 
-// (query + kernel point, clamped index row) of the wave's four queries
+// (query position, clamped index row) of the wave's four queries
 template <int DUMMY = 0>
 __device__ __forceinline__ void load_wave_queries(const float* __restrict__ q_pts, const int32_t* __restrict__ idx,
-                                                  int q_first, int Nq, int H, int Ns, float kx, float ky, float kz,
-                                                  int lane, int (&nall)[4], float (&cqx)[4], float (&cqy)[4],
-                                                  float (&cqz)[4]) {
+                                                  int q_first, int Nq, int H, int Ns, int lane, int (&nall)[4],
+                                                  float (&qx)[4], float (&qy)[4], float (&qz)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int q = q_first + i;
@@ -146,9 +151,9 @@ __device__ __forceinline__ void load_wave_queries(const float* __restrict__ q_pt
     const int n = (live && lane < H) ? idx[(size_t)q * H + lane] : Ns;
     nall[i] = (int)min((unsigned)n, (unsigned)Ns);  // negative / oversized entries behave like the shadow index
     const int qs = live ? q : 0;
-    cqx[i] = q_pts[3 * (size_t)qs + 0] + kx;
-    cqy[i] = q_pts[3 * (size_t)qs + 1] + ky;
-    cqz[i] = q_pts[3 * (size_t)qs + 2] + kz;
+    qx[i] = q_pts[3 * (size_t)qs + 0];
+    qy[i] = q_pts[3 * (size_t)qs + 1];
+    qz[i] = q_pts[3 * (size_t)qs + 2];
   }
 }
 
@@ -161,18 +166,22 @@ __device__ __forceinline__ void aggregate_wave(const float* __restrict__ q_pts, 
   const unsigned row_bytes = (unsigned)Cin * 4u;
   const unsigned col_off = (unsigned)(cbase + li * CV) * 4u;
   int nall[4];
-  float cqx[4], cqy[4], cqz[4];  // query + kernel point, per query
-  load_wave_queries(q_pts, idx, q_first, Nq, H, Ns, kx, ky, kz, lane, nall, cqx, cqy, cqz);
+  float qx[4], qy[4], qz[4];
+  load_wave_queries(q_pts, idx, q_first, Nq, H, Ns, lane, nall, qx, qy, qz);
   // straight-line bodies per step count (H <= 64 -> 1..4 steps of 16 neighbors)
   const int nsteps = (H + 15) >> 4;
   if (nsteps == 3)
-    aggregate_wave_n<CV, 3>(nall, cqx, cqy, cqz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds, flush);
+    aggregate_wave_n<CV, 3>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds,
+                            flush);
   else if (nsteps == 2)
-    aggregate_wave_n<CV, 2>(nall, cqx, cqy, cqz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds, flush);
+    aggregate_wave_n<CV, 2>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds,
+                            flush);
   else if (nsteps == 4)
-    aggregate_wave_n<CV, 4>(nall, cqx, cqy, cqz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds, flush);
+    aggregate_wave_n<CV, 4>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds,
+                            flush);
   else
-    aggregate_wave_n<CV, 1>(nall, cqx, cqy, cqz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds, flush);
+    aggregate_wave_n<CV, 1>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, row_bytes, col_off, inv_extent, lg, lane, nn_lds,
+                            flush);
 }
 
 // the same with the step count fixed at compile time (the launcher picks the instantiation from H): the registers of
@@ -184,10 +193,10 @@ __device__ __forceinline__ void aggregate_wave_steps(const float* __restrict__ q
                                                      float kz, float inv_extent, int lane, float* nn_lds, Flush&& flush) {
   const int li = lane & 15, lg = lane >> 4;
   int nall[4];
-  float cqx[4], cqy[4], cqz[4];
-  load_wave_queries(q_pts, idx, q_first, Nq, H, Ns, kx, ky, kz, lane, nall, cqx, cqy, cqz);
-  aggregate_wave_n<CV, NSTEPS>(nall, cqx, cqy, cqz, rs_sp, rs_x, (unsigned)Cin * 4u, (unsigned)(cbase + li * CV) * 4u,
-                               inv_extent, lg, lane, nn_lds, flush);
+  float qx[4], qy[4], qz[4];
+  load_wave_queries(q_pts, idx, q_first, Nq, H, Ns, lane, nall, qx, qy, qz);
+  aggregate_wave_n<CV, NSTEPS>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, (unsigned)Cin * 4u,
+                               (unsigned)(cbase + li * CV) * 4u, inv_extent, lg, lane, nn_lds, flush);
 }
 
 // store one query's D tile (rows k = 4*lg + i, column li -> channels li*CV + r) into a [16][CC] LDS row block.

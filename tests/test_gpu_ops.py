@@ -2,6 +2,8 @@
 the CPU oracle on the same seeded inputs (bit-exact for indices / barycentres, tolerance stated for fp32).
 Tolerance: the north star asks descriptors/scores within 1e-4 (fp32); operator outputs are compared at
 <= 2e-5 relative to the tensor's max magnitude, gradients at <= 2e-4 (atomic accumulation order)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -12,6 +14,8 @@ from d3feat_pytorch_amd import _native, ops, synthetic
 from d3feat_pytorch_amd.datasets import dataloader as dl
 from d3feat_pytorch_amd.geometric_registration.common import build_correspondence
 from oracle import ops_ref
+import kpconv_cases as kc
+from kpconv_cases import _kpconv_case
 from util import assert_neighbors_equal_tie_aware, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -282,31 +286,100 @@ def test_radius_query_prefix_rows_are_the_leading_part_of_the_full_rows(native, 
 
 
 # ------------------------------------------------------------------------------------------------ KPConv
-def _kpconv_case(rng, nq, ns, h, cin, cout, shadow_frac=0.15, k=15):
-    q, s = _cloud(rng, nq, (1, 1, 1)), _cloud(rng, ns, (1, 1, 1))
-    idx = rng.integers(0, ns, size=(nq, h))
-    # make geometry meaningful: neighbors near the query so influence weights are non-trivial
-    s_near = q[rng.integers(0, nq, size=ns)] + rng.normal(scale=0.03, size=(ns, 3)).astype(np.float32)
-    s = s_near.astype(np.float32)
-    shadow = rng.random((nq, h)) < shadow_frac
-    idx[shadow] = ns
-    idx.sort(axis=1)  # shadows (== ns) at the row end like real tables (not required by the kernel)
-    x = rng.normal(size=(ns, cin)).astype(np.float32)
-    x[rng.random(ns) < 0.1] = 0.0  # rows with zero feature sum exercise the neighbor_num rule
-    kp = (rng.normal(size=(k, 3)) * 0.03).astype(np.float32)
-    kp[0] = 0
-    w = (rng.normal(size=(k, cin, cout)) / np.sqrt(cin * k)).astype(np.float32)
-    return q, s, idx.astype(np.int64), x, kp, w
+# Two kinds of input (tests/kpconv_cases.py): "sparse", the table of random supports these tests started with (next to no
+# influence weight is non-zero, a row's sum has one term at most), against the float32 oracle; and "dense", rows of a
+# radius search (every sum a sum, every support hit by many rows), against the same oracle in float64, at the same
+# FWD_TOL / BWD_TOL.  Every dense case prints its errors (worst per path: DESIGN.md, section 2).
+def _with_geometry(shapes):
+    """(nq, ns, h, cin, cout, geometry) parameters: every shape on the sparse table (under the id it always had), then
+    its dense twin."""
+    name = lambda s: "-".join(str(v) for v in s)
+    return [pytest.param(*s, 'sparse', id=name(s)) for s in shapes] + \
+           [pytest.param(*kc.DENSE_TWIN.get(s, s), 'dense', id=name(kc.DENSE_TWIN.get(s, s)) + "-dense") for s in shapes]
 
 
-@pytest.mark.parametrize("nq,ns,h,cin,cout", [(700, 900, 42, 1, 64), (1000, 1000, 42, 32, 32), (333, 1000, 37, 64, 64),
-                                              (257, 300, 45, 128, 128), (97, 154, 23, 512, 512), (500, 500, 9, 16, 8),
-                                              (200, 260, 42, 24, 40), (300, 400, 42, 16, 16), (300, 400, 40, 32, 64),
-                                              (150, 160, 42, 256, 128), (2100, 2100, 42, 64, 32), (571, 2053, 42, 128, 128),
-                                              (900, 900, 42, 1, 32), (400, 500, 30, 2, 100), (300, 300, 42, 4, 64), (300, 300, 17, 3, 8)])
+@functools.lru_cache(maxsize=None)
+def _dense_inputs(nq, ns, h, cin, cout, k, shift, h_fill):
+    q, s, idx, x, kp, w, ext = kc.dense_case(kc.dense_rng(nq, ns, h, k), nq, ns, h, cin, cout, k=k, shift=shift,
+                                             h_fill=h_fill)
+    rng = np.random.default_rng([nq, cout, 1])
+    go = rng.normal(size=(nq, cout)).astype(np.float32)
+    bias = rng.normal(size=cout).astype(np.float32)
+    return q, s, idx, x, kp, w, ext, go, bias
+
+
+@functools.lru_cache(maxsize=None)
+def _dense(nq, ns, h, cin, cout, k=15, shift=(0, 0, 0), h_fill=None, with_bias=False):
+    """One dense case and its float64 reference, computed once: ((q, s, idx, x, kp, w, extent, grad_out, bias),
+    (out, grad_x, grad_w, grad_bias)); with_bias: the reference is LeakyReLU(KPConv + bias, 0.1).  Read only."""
+    case = _dense_inputs(nq, ns, h, cin, cout, k, shift, h_fill)
+    q, s, idx, x, kp, w, ext, go, bias = case
+    return case, kc.oracle64(q, s, idx, x, kp, w, ext, grad_out=go, bias=bias if with_bias else None, slope=0.1)
+
+
+def _small_kernels_take(cin, cout, h):
+    """The library's own answer: the input-layer kernels save rows of 16 slots (or nothing), every other path
+    K * Cin floats -- asked at K = 1, where the two cannot coincide (their choice does not depend on K)."""
+    return _native.lib().d3f_kpconv_saves_wf(cin, cout, 1, h) != cin
+
+
+def _kpconv_paths(nq, ns, h, cin, cout, k=15, rev=None, block=False):
+    """(forward path, grad-input path) ops.kpconv -- block: ops.kpconv_bias_act -- takes for a shape under the current
+    switches of ops: 'small' / 'fused' / 'general' / 'aggregate+GEMM', and those or 'scatter' / 'gather'.  The forward
+    label comes from the library's predicates alone (d3f_kpconv_saves_wf, d3f_kpconv_packs_supports), the grad-input
+    label from the switches of ops and the predicates ops itself asks; it names the row of DESIGN.md's table a case
+    reports under, the kernels are held to the float64 oracle whichever label they run under."""
+    L = _native.lib()
+    if rev is not None and not (ns >= ops.DX_GATHER_MIN_ROWS and L.d3f_kpconv_grad_input_gather_supported(cin, cout, k)):
+        rev = None
+    tiles = bool(L.d3f_kpconv_grad_input_supported(cin, k, h, ns))
+    if block and ops._takes_gemm_path(nq, cin) and tiles:
+        if rev is not None and rev.rel is not None and cout >= ops._GEMM_DX_AGG_MIN_COUT and \
+                L.d3f_kpconv_aggregate_transposed_supported(cout, k):
+            return 'aggregate+GEMM', 'aggregate+GEMM'
+        return 'aggregate+GEMM', ('gather' if rev is not None else 'scatter')
+    fwd = 'small' if _small_kernels_take(cin, cout, h) else \
+        ('fused' if L.d3f_kpconv_packs_supports(cin, cout, k, h, ns) else 'general')
+    if rev is not None:
+        return fwd, 'gather'
+    if 0 < nq < ops._GEMM_DX_MAX_ROWS and tiles:
+        return fwd, 'scatter'
+    return fwd, ('fused' if fwd == 'fused' else 'general')
+
+
+def _report_dense(what, shape, paths, out=None, gx=None, gw=None):
+    fmt = lambda e: "-" if e is None else "%.2e" % e
+    print("\nKPCONV-DENSE %s %s fwd=%s dx=%s out=%s grad_x=%s grad_w=%s" % (
+        what, "x".join(str(v) for v in shape), paths[0], paths[1], fmt(out), fmt(gx), fmt(gw)))
+
+
+def _dense_forward_backward(what, nq, ns, h, cin, cout, k=15, rev=None, **kw):
+    """ops.kpconv forward + backward on a dense case against float64; returns (case, ref, out, grad_x, grad_w)."""
+    case, ref = _dense(nq, ns, h, cin, cout, k=k, **kw)
+    q, s, idx, x, kp, w, ext, go = case[:8]
+    paths = _kpconv_paths(nq, ns, h, cin, cout, k, rev)
+    gx, gw = cu(x).requires_grad_(True), cu(w).requires_grad_(True)
+    out = ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), gw, ext, rev=rev)
+    out.backward(cu(go))
+    errs = (rel_err(out.detach().cpu().numpy(), ref[0]), rel_err(gx.grad.cpu().numpy(), ref[1]),
+            rel_err(gw.grad.cpu().numpy(), ref[2]))
+    _report_dense(what, (nq, ns, h, cin, cout, k), paths, *errs)
+    assert errs[0] < FWD_TOL
+    assert errs[1] < BWD_TOL
+    assert errs[2] < BWD_TOL
+    return case, ref, out.detach(), gx.grad, gw.grad
+
+
+@pytest.mark.parametrize("nq,ns,h,cin,cout,geometry", _with_geometry(kc.FWD_BWD_SHAPES))
 @pytest.mark.parametrize("gemm_dx_rows", [0, 1 << 30])  # grad_x: fused gW tile / library GEMM + scatter kernel
-def test_kpconv_forward_backward(nq, ns, h, cin, cout, gemm_dx_rows, monkeypatch):
+def test_kpconv_forward_backward(nq, ns, h, cin, cout, geometry, gemm_dx_rows, monkeypatch):
     monkeypatch.setattr(ops, "_GEMM_DX_MAX_ROWS", gemm_dx_rows)
+    if geometry == "dense":
+        case, _, out, _, _ = _dense_forward_backward("forward_backward", nq, ns, h, cin, cout)
+        q, s, idx, x, kp, w, ext = case[:7]
+        out32 = ops.kpconv(cu(q), cu(s), cu(idx, torch.int32), cu(x), cu(kp), cu(w), ext)
+        assert rel_err(out32.cpu().numpy(), out.cpu().numpy()) < 1e-6
+        return
     rng = np.random.default_rng(nq + cin)
     q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
     ext = 0.05
@@ -447,14 +520,51 @@ def test_search_form_transpose_equals_the_csr_transpose(n0, n1, r, lim):
         assert torch.equal(gx.grad, grads[2])
 
 
-@pytest.mark.parametrize("nq,ns,h,cin,cout", [(1000, 1000, 42, 32, 32), (333, 1000, 37, 64, 64), (4500, 4500, 42, 64, 64),
-                                              (257, 300, 45, 128, 128), (97, 154, 23, 512, 512), (300, 400, 42, 16, 16),
-                                              (300, 400, 40, 32, 64), (150, 160, 42, 256, 128), (2100, 2100, 42, 64, 32),
-                                              (571, 2053, 42, 128, 128), (5000, 900, 64, 32, 32)])
-def test_kpconv_grad_input_as_a_gather_over_the_reverse_table(nq, ns, h, cin, cout, monkeypatch):
+def _dense_gather_case(nq, ns, h, cin, cout):
+    """The gather-form test on a dense table (rows of the reverse table hold some twenty live edges), against float64."""
+    case, ref = _dense(nq, ns, h, cin, cout)
+    q, s, idx, x, kp, w, ext, go, bias = case
+    tab = cu(idx, torch.int32)
+    rev = ops.build_reverse_table(tab, ns)
+    paths = _kpconv_paths(nq, ns, h, cin, cout, rev=rev)
+    grads = []
+    for _ in range(2):
+        gx, gw = cu(x).requires_grad_(True), cu(w).requires_grad_(True)
+        out = ops.kpconv(cu(q), cu(s), tab, gx, cu(kp), gw, ext)          # finds the table's transpose on the table
+        out.backward(cu(go))
+        grads.append(gx.grad.clone())
+    errs = (rel_err(out.detach().cpu().numpy(), ref[0]), rel_err(grads[0].cpu().numpy(), ref[1]),
+            rel_err(gw.grad.cpu().numpy(), ref[2]))
+    _report_dense("gather", (nq, ns, h, cin, cout, 15), paths, *errs)
+    assert errs[0] < FWD_TOL
+    assert errs[1] < BWD_TOL
+    assert errs[2] < BWD_TOL
+    assert torch.equal(grads[0], grads[1])
+    # block form (KPConv + bias + LeakyReLU), explicit rev argument, int64 table as the reference hands it
+    _, ref2 = _dense(nq, ns, h, cin, cout, with_bias=True)
+    paths = _kpconv_paths(nq, ns, h, cin, cout, rev=rev, block=True)
+    gx, gw, gb = cu(x).requires_grad_(True), cu(w).requires_grad_(True), cu(bias).requires_grad_(True)
+    y = ops.kpconv_bias_act(cu(q), cu(s), cu(idx), gx, cu(kp), gw, ext, gb, slope=0.1, rev=rev)
+    y.backward(cu(go))
+    errs = (rel_err(y.detach().cpu().numpy(), ref2[0]), rel_err(gx.grad.cpu().numpy(), ref2[1]),
+            rel_err(gw.grad.cpu().numpy(), ref2[2]))
+    _report_dense("gather_block", (nq, ns, h, cin, cout, 15), paths, *errs)
+    assert errs[0] < FWD_TOL
+    assert errs[1] < BWD_TOL
+    assert errs[2] < BWD_TOL
+    assert rel_err(gb.grad.cpu().numpy(), ref2[3]) < BWD_TOL
+    with pytest.raises(RuntimeError):   # a transpose of another table is refused
+        ops.kpconv(cu(q)[:-1], cu(s), tab[:-1], cu(x).requires_grad_(True), cu(kp), cu(w), ext, rev=rev)
+
+
+@pytest.mark.parametrize("nq,ns,h,cin,cout,geometry", _with_geometry(kc.GATHER_SHAPES))
+def test_kpconv_grad_input_as_a_gather_over_the_reverse_table(nq, ns, h, cin, cout, geometry, monkeypatch):
     """grad_x = sum_k (sum_{q in rev(s)} w gn[q]) W[k]^T  ==  the oracle's autograd gradient; bit-identical run to run
     (no atomics), on the fused path and on the aggregate + GEMM path of the few-point layers."""
     monkeypatch.setattr(ops, "DX_GATHER_MIN_ROWS", 0)   # (the training step uses it from 4096 support rows)
+    if geometry == "dense":
+        _dense_gather_case(nq, ns, h, cin, cout)
+        return
     rng = np.random.default_rng(nq + cin)
     q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
     ext = 0.05
@@ -545,30 +655,42 @@ def test_kpconv_as_aggregation_kernels_plus_gemms(n0, n1, r, lim, cin, cout, mon
     g_coarse.status.raise_if_set()
 
 
-@pytest.mark.parametrize("nq,ns,h,cin,cout", [(1000, 1000, 42, 32, 32), (97, 154, 23, 512, 512), (300, 400, 42, 16, 16),
-                                              (150, 160, 42, 256, 128), (200, 260, 42, 24, 40)])
+@pytest.mark.parametrize("nq,ns,h,cin,cout,geometry", _with_geometry(kc.SAVED_WF_SHAPES))
 @pytest.mark.parametrize("min_rows", [1, 1 << 30])  # reduction-parallel kernel / library GEMM for grad_W
-def test_kpconv_backward_saved_vs_recomputed_aggregation(nq, ns, h, cin, cout, min_rows, monkeypatch):
+def test_kpconv_backward_saved_vs_recomputed_aggregation(nq, ns, h, cin, cout, geometry, min_rows, monkeypatch):
     """grad_W from the weighted features the forward leaves behind == grad_W with the aggregation recomputed."""
     monkeypatch.setattr(ops, "_SPLITK_MIN_ROWS", min_rows)
-    rng = np.random.default_rng(nq * 7 + cin)
-    q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
-    go = cu(rng.normal(size=(nq, cout)).astype(np.float32))
+    if geometry == "dense":
+        (q, s, idx, x, kp, w, ext, go_np, _), ref = _dense(nq, ns, h, cin, cout)
+        go = cu(go_np)
+    else:
+        rng = np.random.default_rng(nq * 7 + cin)
+        q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
+        go = cu(rng.normal(size=(nq, cout)).astype(np.float32))
+        ext, ref = 0.05, None
     grads = []
     for save in (True, False):
         monkeypatch.setattr(ops, "SAVE_WEIGHTED_FEATURES", save)
         gx, gw = cu(x).requires_grad_(True), cu(w).requires_grad_(True)
-        ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), gw, 0.05).backward(go)
+        out = ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), gw, ext)
+        out.backward(go)
         grads.append((gx.grad.cpu().numpy(), gw.grad.cpu().numpy()))
+        if ref is not None:   # dense: each of the two against float64 as well
+            errs = (rel_err(out.detach().cpu().numpy(), ref[0]), rel_err(grads[-1][0], ref[1]), rel_err(grads[-1][1], ref[2]))
+            _report_dense("saved_wf" if save else "recomputed_wf", (nq, ns, h, cin, cout, 15),
+                          _kpconv_paths(nq, ns, h, cin, cout), *errs)
+            assert errs[0] < FWD_TOL
+            assert errs[1] < BWD_TOL
+            assert errs[2] < BWD_TOL
     assert rel_err(grads[0][0], grads[1][0]) < 1e-5
     assert rel_err(grads[0][1], grads[1][1]) < 1e-5
     # weight gradient alone (frozen features) and feature gradient alone (frozen weights)
     monkeypatch.setattr(ops, "SAVE_WEIGHTED_FEATURES", True)
     gw = cu(w).requires_grad_(True)
-    ops.kpconv(cu(q), cu(s), cu(idx), cu(x), cu(kp), gw, 0.05).backward(go)
+    ops.kpconv(cu(q), cu(s), cu(idx), cu(x), cu(kp), gw, ext).backward(go)
     assert rel_err(gw.grad.cpu().numpy(), grads[0][1]) < 1e-6
     gx = cu(x).requires_grad_(True)
-    ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), cu(w), 0.05).backward(go)
+    ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), cu(w), ext).backward(go)
     assert rel_err(gx.grad.cpu().numpy(), grads[0][0]) < 1e-5
 
 
@@ -948,25 +1070,36 @@ def test_fused_unary_block_matches_unfused(n, cin, cout, with_add, slope, monkey
             assert rel_err(a, b) < 2e-5
 
 
-@pytest.mark.parametrize("nq,ns,h,cin,cout", [(97, 154, 23, 512, 512), (150, 160, 42, 256, 128), (300, 400, 42, 16, 16),
-                                              (257, 300, 45, 128, 128), (571, 2053, 42, 64, 256)])
-def test_kpconv_bias_act_gemm_path_matches_fused_path(nq, ns, h, cin, cout, monkeypatch):
+@pytest.mark.parametrize("nq,ns,h,cin,cout,geometry", _with_geometry(kc.BIAS_ACT_SHAPES))
+def test_kpconv_bias_act_gemm_path_matches_fused_path(nq, ns, h, cin, cout, geometry, monkeypatch):
     """LeakyReLU(KPConv(x) + b): aggregation kernel + library GEMMs + row-divided epilogue (few-point layers) ==
     fused KPConv kernel + epilogue, values and all three gradients."""
-    rng = np.random.default_rng(nq + cout)
-    q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
-    b = rng.normal(size=cout).astype(np.float32)
-    go = rng.normal(size=(nq, cout)).astype(np.float32)
+    if geometry == "dense":
+        (q, s, idx, x, kp, w, ext, go, b), ref64 = _dense(nq, ns, h, cin, cout, with_bias=True)
+    else:
+        rng = np.random.default_rng(nq + cout)
+        q, s, idx, x, kp, w = _kpconv_case(rng, nq, ns, h, cin, cout)
+        b = rng.normal(size=cout).astype(np.float32)
+        go = rng.normal(size=(nq, cout)).astype(np.float32)
+        ext = 0.05
     res = []
     for rows in (1 << 30, 0):
         monkeypatch.setattr(ops, "_GEMM_DX_MAX_ROWS", rows)
         tx, tw, tb = cu(x).requires_grad_(True), cu(w).requires_grad_(True), cu(b).requires_grad_(True)
-        y = ops.kpconv_bias_act(cu(q), cu(s), cu(idx), tx, cu(kp), tw, 0.05, tb, slope=0.1)
+        y = ops.kpconv_bias_act(cu(q), cu(s), cu(idx), tx, cu(kp), tw, ext, tb, slope=0.1)
         y.backward(cu(go))
         res.append([t.detach().cpu().numpy() for t in (y, tx.grad, tw.grad, tb.grad)])
-    ref = ops_ref.kpconv(*[torch.from_numpy(a) for a in (q, s, idx, x, kp, w)], 0.05).numpy() + b
-    ref = np.where(ref > 0, ref, 0.1 * ref)
-    assert rel_err(res[0][0], ref) < FWD_TOL
+        if geometry == "dense":   # both paths against float64 (bias + LeakyReLU in float64 too), gradients included
+            errs = [rel_err(a, c) for a, c in zip(res[-1], ref64)]
+            _report_dense("bias_act", (nq, ns, h, cin, cout, 15), _kpconv_paths(nq, ns, h, cin, cout, block=True), *errs[:3])
+            assert errs[0] < FWD_TOL
+            assert errs[1] < BWD_TOL
+            assert errs[2] < BWD_TOL
+            assert errs[3] < BWD_TOL
+    if geometry == "sparse":
+        ref = ops_ref.kpconv(*[torch.from_numpy(a) for a in (q, s, idx, x, kp, w)], 0.05).numpy() + b
+        ref = np.where(ref > 0, ref, 0.1 * ref)
+        assert rel_err(res[0][0], ref) < FWD_TOL
     for a, c in zip(res[0], res[1]):
         assert rel_err(a, c) < 2e-5
 
@@ -1004,6 +1137,126 @@ def test_kpconv_all_shadow_rows_and_empty():
     assert np.all(out[:5] == 0)
     ref = ops_ref.kpconv(*[torch.from_numpy(a) for a in (q, s, idx, x, kp, w)], 0.05).numpy()
     assert rel_err(out, ref) < FWD_TOL
+
+
+def test_kpconv_all_shadow_rows_on_a_dense_table():
+    """Five all-shadow rows are exactly zero, five rows keep exactly one live entry, the rest are full sums: all of it
+    against float64, forward and backward."""
+    nq, ns, h, cin, cout = kc.DENSE_TWIN[kc.SHADOW_ROWS_SHAPE]
+    q, s, idx, x, kp, w, ext = kc.dense_case(kc.dense_rng(nq, ns, h), nq, ns, h, cin, cout)
+    idx[:5] = ns
+    idx[5:10, 1:] = ns
+    assert ((idx[5:10] < ns).sum(axis=1) == 1).all() and (idx[10:] < ns).sum(axis=1).min() > 1
+    go = np.random.default_rng(nq).normal(size=(nq, cout)).astype(np.float32)
+    ref = kc.oracle64(q, s, idx, x, kp, w, ext, grad_out=go)
+    gx, gw = cu(x).requires_grad_(True), cu(w).requires_grad_(True)
+    out = ops.kpconv(cu(q), cu(s), cu(idx), gx, cu(kp), gw, ext)
+    out.backward(cu(go))
+    out = out.detach().cpu().numpy()
+    assert np.all(out[:5] == 0) and np.abs(out[5:]).max(axis=1).min() > 0
+    errs = (rel_err(out, ref[0]), rel_err(gx.grad.cpu().numpy(), ref[1]), rel_err(gw.grad.cpu().numpy(), ref[2]))
+    _report_dense("shadow_rows", (nq, ns, h, cin, cout, 15), _kpconv_paths(nq, ns, h, cin, cout), *errs)
+    assert errs[0] < FWD_TOL
+    assert errs[1] < BWD_TOL
+    assert errs[2] < BWD_TOL
+
+
+# ---- dense tables only: shapes between the ones above -----------------------------------------------------------------
+@pytest.mark.parametrize("nq,ns,h,cin,cout,k", kc.K_CASES)
+def test_kpconv_kernel_point_counts(nq, ns, h, cin, cout, k):
+    """K = 1 (the centre point alone), 7 and 16 (no spare slot in the 16-slot rows the input-layer kernels save) on the
+    fused, the input-layer (saved wf / own weight-gradient kernel) and the general path."""
+    _dense_forward_backward("K", nq, ns, h, cin, cout, k=k)
+
+
+@pytest.mark.parametrize("nq,ns,h,cin,cout", kc.H_CASES)
+def test_kpconv_table_widths_around_the_tile_limit(nq, ns, h, cin, cout):
+    """H = 64 is the last width the fused and the input-layer kernels take, 65 the first of the general path; H = 1."""
+    L = _native.lib()
+    tiled = h <= 64
+    if cin == 1:     # input-layer kernels: rows of 16 slots saved / general path: K * Cin floats
+        assert L.d3f_kpconv_saves_wf(cin, cout, 15, h) == (16 if tiled else 15)
+        assert L.d3f_kpconv_packs_supports(cin, cout, 15, h, ns) == 0
+    else:
+        assert L.d3f_kpconv_packs_supports(cin, cout, 15, h, ns) == (1 if tiled else 0)
+    assert _kpconv_paths(nq, ns, h, cin, cout)[0] == (('small' if cin == 1 else 'fused') if tiled else 'general')
+    _dense_forward_backward("H", nq, ns, h, cin, cout, h_fill=kc.H_FILL if h == 1 else None)
+
+
+@pytest.mark.parametrize("nq,ns,h,cin,cout", kc.WIDE_SHAPES)
+@pytest.mark.parametrize("gemm_dx_rows", [0, 1 << 30])
+def test_kpconv_general_path_with_many_channels_per_lane(nq, ns, h, cin, cout, gemm_dx_rows, monkeypatch):
+    """The wave-per-query aggregation and scatter kernels with 4 and 8 channels per lane (Cin of 129..512 the tile
+    kernels do not take, or a Cout they do not), then the own MFMA GEMMs."""
+    monkeypatch.setattr(ops, "_GEMM_DX_MAX_ROWS", gemm_dx_rows)
+    assert _native.lib().d3f_kpconv_packs_supports(cin, cout, 15, h, ns) == 0
+    _dense_forward_backward("wide", nq, ns, h, cin, cout)
+
+
+@pytest.mark.parametrize("nq,ns,h,cin,cout", kc.SMALL_EDGE_SHAPES)
+def test_kpconv_input_layer_kernels_and_their_boundary(nq, ns, h, cin, cout):
+    """Cin * ceil(Cout / 64) <= 4 is what the input-layer kernels take: both sides of it, two outputs per lane, and a
+    Cout that leaves the weight gradient to their own kernel."""
+    small = cin * ((cout + 63) // 64) <= 4
+    saves = _native.lib().d3f_kpconv_saves_wf(cin, cout, 15, h)
+    assert saves == ((16 * cin if cout % 16 == 0 else 0) if small else 15 * cin)
+    assert _kpconv_paths(nq, ns, h, cin, cout)[0] == ('small' if small else 'general')
+    _dense_forward_backward("small_edge", nq, ns, h, cin, cout)
+
+
+def _exact_reverse_table(idx, nq, ns, q, s):
+    """Exact-form reverse table of any table: its CSR transpose (ops.build_reverse_table) laid out as search-form rows
+    whose every entry is a member (last_key = the largest key), then ops.filter_reverse_table."""
+    csr = ops.build_reverse_table(cu(idx, torch.int32), ns)
+    ptr, ent = csr.ptr.cpu().numpy().astype(np.int64), csr.ent.cpu().numpy()
+    width = int(np.diff(ptr).max())
+    rows = np.full((ns, width), nq, np.int32)
+    for i in range(ns):
+        rows[i, :ptr[i + 1] - ptr[i]] = ent[ptr[i]:ptr[i + 1]]
+    last_key = torch.full((nq,), -1, dtype=torch.int64, device=DEV)   # (all bits set: the largest unsigned key)
+    h = int(idx.shape[1])
+    return ops.filter_reverse_table(ops.ReverseTable(cu(rows), nq, h, ns, last_key=last_key), q, s)
+
+
+@pytest.mark.parametrize("path", ["fused", "scatter", "small", "general", "gather", "aggregate_gemm"])
+def test_kpconv_far_from_the_origin(path, monkeypatch):
+    """Every path on a scene moved by (300, -200, 50) after its table was built.  s - q of neighbouring float32 points
+    is exact, so the float64 oracle on the moved float32 coordinates is matched at the SAME bounds; a path that expands
+    |s - q - kp|^2 or packs positions with fewer bits is not."""
+    nq, ns, h, cin, cout = kc.SHIFT_SHAPES['fused' if path == 'scatter' else path]
+    monkeypatch.setattr(ops, "_GEMM_DX_MAX_ROWS", 1 << 30 if path == "scatter" else 0)
+    if path in ("gather", "aggregate_gemm"):
+        monkeypatch.setattr(ops, "DX_GATHER_MIN_ROWS", 0)
+    if path != "aggregate_gemm":
+        rev = None
+        if path == "gather":
+            idx = _dense(nq, ns, h, cin, cout, shift=kc.SHIFT)[0][2]
+            rev = ops.build_reverse_table(cu(idx, torch.int32), ns)
+        assert _kpconv_paths(nq, ns, h, cin, cout, rev=rev) == {
+            'fused': ('fused', 'fused'), 'scatter': ('fused', 'scatter'), 'small': ('small', 'general'),
+            'general': ('general', 'general'), 'gather': ('fused', 'gather')}[path]
+        _dense_forward_backward("shift", nq, ns, h, cin, cout, rev=rev, shift=kc.SHIFT)
+        return
+    monkeypatch.setattr(ops, "_GEMM_PATH_MIN_CIN", 16)
+    (q, s, idx, x, kp, w, ext, go, bias), ref = _dense(nq, ns, h, cin, cout, shift=kc.SHIFT, with_bias=True)
+    rev = _exact_reverse_table(idx, nq, ns, cu(q), cu(s))
+    assert rev.rel is not None
+    paths = _kpconv_paths(nq, ns, h, cin, cout, rev=rev, block=True)
+    assert paths == ('aggregate+GEMM', 'aggregate+GEMM')
+    res = []
+    for _ in range(2):
+        gx, gw, gb = cu(x).requires_grad_(True), cu(w).requires_grad_(True), cu(bias).requires_grad_(True)
+        y = ops.kpconv_bias_act(cu(q), cu(s), cu(idx, torch.int32), gx, cu(kp), gw, ext, gb, slope=0.1, rev=rev)
+        y.backward(cu(go))
+        res.append(gx.grad.clone())
+    errs = (rel_err(y.detach().cpu().numpy(), ref[0]), rel_err(gx.grad.cpu().numpy(), ref[1]),
+            rel_err(gw.grad.cpu().numpy(), ref[2]))
+    _report_dense("shift", (nq, ns, h, cin, cout, 15), paths, *errs)
+    assert errs[0] < FWD_TOL
+    assert errs[1] < BWD_TOL
+    assert errs[2] < BWD_TOL
+    assert rel_err(gb.grad.cpu().numpy(), ref[3]) < BWD_TOL
+    assert torch.equal(res[0], res[1])      # no atomics in the transposed aggregation
 
 
 # ------------------------------------------------------------------------------------------------ pools
