@@ -6,7 +6,9 @@
 //   1. nonfinite_kernel : state[0] |= any(!isfinite(g))  (or the pair's device status word is set: a pyramid that
 //                         overflowed a capacity must not reach the parameters -- state[2] |= flags, ++state[3])
 //   2. sgd_kernel       : if (!state[0]) { buf = momentum*buf + (g + wd*p); p -= lr*buf; } else ++state[1]
-// The operation order is torch.optim.SGD's (d = g + wd*p; buf = buf*momentum + d; p = p + (-lr)*buf), unfused.
+// The operation order is torch.optim.SGD's (d = g + wd*p; buf = buf*momentum + d; p = p + (-lr)*buf), every product
+// rounded on its own.  torch's kernels may fuse some of them; SGD is linear in g, so such a last-bit difference in d
+// moves p by lr times that bit and stays there (unlike Adam's decay below, which is fused for the reason given there).
 // HBM-bound: 4 B/param read in (1), 12 B read + 8 B written in (2).
 // Several pairs in flight on one GPU (train.PairLanes) leave one gradient buffer each: both kernels take up to four of
 // them and the update uses their SUM (4 B/param more per extra lane and kernel, no pass of its own for the addition).
@@ -105,8 +107,8 @@ __global__ __launch_bounds__(256) void sgd_kernel(Lanes lanes, float* __restrict
 }
 
 // Guarded Adam (reference training_3DMatch.py:69-75, torch.optim.Adam: amsgrad=False, maximize=False, L2 weight decay)
-// on the same flat buffers, after the same nonfinite_kernel.  torch's single-tensor order, unfused:
-//   g = (lane 0 + lane 1 + ...) * gs;  g = g + wd*p;  m = m + (1-b1)*(g - m);  v = v*b2 + (1-b2)*g*g
+// on the same flat buffers, after the same nonfinite_kernel.  torch's single-tensor order, unfused but for the decay:
+//   g = (lane 0 + lane 1 + ...) * gs;  g = fma(wd, p, g);  m = m + (1-b1)*(g - m);  v = v*b2 + (1-b2)*g*g
 //   p = p + (-step_size) * (m / (sqrt(v)/bc2 + eps)),  step_size = lr/(1 - b1^t), bc2 = sqrt(1 - b2^t)  (f64 -> f32)
 // with t = the device step counter + 1.  The counter itself is advanced by adam_tick_kernel, one thread launched after
 // the update: every block of the update has read the old value by then.  HBM-bound: 16 B read + 12 B written per
@@ -114,7 +116,11 @@ __global__ __launch_bounds__(256) void sgd_kernel(Lanes lanes, float* __restrict
 __device__ __forceinline__ void adam1(float g, float& p, float& m, float& v, float gs, float wd, float omb1, float b2,
                                       float omb2, float eps, float neg_ss, float bc2) {
   g = g * gs;
-  g = g + wd * p;
+  // One fused multiply-add, as torch's grad.add(param, alpha=wd) behaves on the device: where g + wd*p cancels to
+  // |g| <= eps the first step lr g/(|g| + eps) has slope lr/eps = 1e6, and rounding wd*p on its own moved p by 2.1e-6
+  // away from torch.optim.Adam at n = 9.4 M, lr 0.01, wd 1e-4; fused, the same comparison agrees to 1e-6.  That
+  // agreement is the evidence for torch's fusion (its add functor is a plain `a + alpha * b`, which hipcc contracts unless told not to).
+  g = fmaf(wd, p, g);
   m = m + omb1 * (g - m);
   v = v * b2 + omb2 * g * g;
   p = p + neg_ss * (m / (sqrtf(v) / bc2 + eps));

@@ -275,7 +275,9 @@ class GuardedAdam(_GuardedOptimizer):
     (training_3DMatch.py:69-75) -- with GuardedSGD's interface and guard: a step whose gradient holds a non-finite value
     or whose pair was flagged leaves parameters, moments and the step counter untouched (the reference does not call
     optimizer.step() then, trainer.py:104-111).  On the GPU this is d3f_adam_guarded_step (three launches, no host
-    sync; the counter ``t`` lives on the device); the torch expression below is the same arithmetic for host tensors."""
+    sync; the counter ``t`` lives on the device); for host tensors the expression below is torch.optim.Adam's own
+    sequence of calls, which the kernel follows term by term (its decay ``g + wd p`` as one fused multiply-add, like
+    ``add(alpha=)`` on the device; the other terms with separate roundings, within a last bit of torch's)."""
 
     def __init__(self, flat, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.flat = flat
