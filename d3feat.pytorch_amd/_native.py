@@ -179,6 +179,9 @@ SIGNATURES = {
     "d3f_icp_rigid_plane": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _i, _d, _d, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_icp_plane_fit_host": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "d3f_pair_information_ws_bytes": (_sz, [_i, C.c_int64]),
+    "d3f_pair_information": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _sz,
+                                  _vp]),
     "d3f_sgd_guarded_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "d3f_sgd_guarded_step_lanes": (_i, [_vp, _i, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "d3f_adam_guarded_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),

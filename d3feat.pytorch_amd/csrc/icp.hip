@@ -28,6 +28,14 @@
 // of the matched fixed point through the index the stored point carries and adds the 21 + 6 entries of the 6x6 normal
 // equations of the linearised point-to-plane residual (plane.hpp), 29 sums with n and sum d2; the fit is a Cholesky
 // solve by one lane.  Point-to-point ICP removes the error ALONG a plane only slowly; this form does not penalise it.
+//
+// Information matrices (d3f_pair_information; the search kernel instantiated with kInfo).  The 6x6 information matrix
+// of a pair -- what gt.info holds and what a pose graph takes per edge -- is a handful of sums over exactly the accepted
+// rows of ONE search under a given T, so it is a third kind of the same kernel: the winning lane adds n, sum x,
+// sum x x^T (upper triangle) of the moving point, the same of the matched fixed point y, and sum d2: 20 RAW moments, no
+// pivots (a product of two f32 values is exact in f64 and nothing is subtracted afterwards, so there is no cancellation
+// to protect).  Setup, prefix, reduction orders and flags are ICP's; a finishing launch adds the pair's block sums in
+// the fit kernel's order and writes them.  Three launches whatever the data.
 #include "pair_search.hpp"
 #include "plane.hpp"
 #include "rigid.hpp"
@@ -42,7 +50,8 @@ constexpr int kRows = D3F_ICP_BLOCK_ROWS;            // rows per workgroup
 constexpr int kRowsPerSlice = (kBlock / 64) * (64 / kG);
 constexpr int kSlices = kRows / kRowsPerSlice;
 constexpr int kPoint = 0, kPlane = 1;   // what the fit minimises
-constexpr int sums_of(int kind) { return kind == kPlane ? d3f::plane::kPlaneSums : 17; }
+constexpr int kInfo = 2;                // no fit: the raw moments of the accepted rows (d3f_pair_information)
+constexpr int sums_of(int kind) { return kind == kPlane ? d3f::plane::kPlaneSums : kind == kInfo ? D3F_INFO_MOMENTS : 17; }
 constexpr int kMaxClouds = 65535;
 static_assert(kRows % kRowsPerSlice == 0, "a workgroup serves whole slices");
 
@@ -68,6 +77,7 @@ struct IcpArgs {
   double rel_fitness, rel_rmse;
   long long rows;
   int B, P, Ns, max_iters;
+  double* moments;            // [P, D3F_INFO_MOMENTS] (kInfo)
 };
 
 __device__ __forceinline__ long long first_block(const IcpArgs& A, int p) { return A.row_start[p] / kRows + p; }
@@ -151,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
   const double* T = A.T_cur + 12 * (size_t)p;
   const bool pivots = tgt_n > 0 && (long long)sa < (long long)A.Ns && (long long)tgt0 < (long long)A.Ns;
   double px[3] = {0.0, 0.0, 0.0}, py[3] = {0.0, 0.0, 0.0};
-  if (pivots) {
+  if (kKind != kInfo && pivots) {   // (kInfo adds raw moments: `pivots` only says that both clouds have a row 0)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       px[k] = (double)A.points[3 * (size_t)sa + k];
@@ -196,6 +206,22 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
 #pragma unroll
           for (int j = i; j < 6; ++j) acc[1 + d3f::plane::upper6(i, j)] += J[i] * J[j];
           acc[22 + i] += J[i] * r;
+        }
+        acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
+      }
+    } else if constexpr (kKind == kInfo) {
+      if (winner) {
+        const double xs[3] = {x, y, z}, ys[3] = {(double)win.x, (double)win.y, (double)win.z};
+        acc[0] += 1.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          acc[1 + r] += xs[r];
+          acc[10 + r] += ys[r];
+#pragma unroll
+          for (int c = r; c < 3; ++c) {   // upper triangle row by row: xx, xy, xz, yy, yz, zz
+            acc[4 + (r * (7 - r)) / 2 + (c - r)] += xs[r] * xs[c];
+            acc[13 + (r * (7 - r)) / 2 + (c - r)] += ys[r] * ys[c];
+          }
         }
         acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
       }
@@ -308,6 +334,49 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
   A.iterations[p] = k_iter + 1;
 }
 
+// d3f_pair_information's setup: icp_setup_kernel's flags and copy of T, nothing else
+__global__ void info_setup_kernel(const IcpArgs A) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= A.P) return;
+  const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
+  int st = 0;
+  if (!((unsigned)a < (unsigned)A.B && (unsigned)b < (unsigned)A.B) || A.row_start[p] < 0 ||
+      A.row_start[p + 1] < A.row_start[p] || A.row_start[p + 1] > A.rows)
+    st |= D3F_ICP_ST_PAIR;
+  bool finite = true;
+  for (int k = 0; k < 12; ++k) {
+    const double v = A.T_init[12 * (size_t)p + k];
+    A.T_cur[12 * (size_t)p + k] = v;
+    finite = finite && isfinite(v);
+  }
+  if (!finite) st |= D3F_ICP_ST_NONFINITE;
+  A.done[p] = st != 0;   // never searched: zero moments
+  A.status[p] = st;
+}
+
+// one wave per pair: the pair's block sums in icp_fit_kernel's order, written as they are
+__global__ __launch_bounds__(64) void info_finish_kernel(const IcpArgs A) {
+  constexpr int kSums = sums_of(kInfo);
+  const int p = blockIdx.x, lane = threadIdx.x;
+  double v[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+  if (!A.done[p]) {   // (uniform over the wave)
+    const int a = A.pairs[2 * p];
+    const long long m = pair_rows(A, p, a), nblk = (m + kRows - 1) / kRows, first = first_block(A, p);
+    for (long long j = lane; j < nblk; j += 64) {
+      const double* part = A.partial + (size_t)(first + j) * kSums;
+#pragma unroll
+      for (int k = 0; k < kSums; ++k) v[k] += part[k];
+    }
+    wave_sum(v);
+  }
+  if (lane != 0) return;
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) A.moments[(size_t)p * kSums + k] = v[k];
+  A.count[p] = (int)v[0];
+}
+
 struct IcpLayout {
   double* T_cur;
   double* prev;
@@ -346,6 +415,7 @@ int icp_run(const void* grid_ws, const float* points, const float* normals, int 
   GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
   IcpLayout l = icp_layout(ws, P, rows, kKind);
   IcpArgs a;
+  a.moments = nullptr;
   a.points = points;
   a.normals = normals;
   a.cloud_start = cloud_start;
@@ -393,9 +463,65 @@ int icp_run(const void* grid_ws, const float* points, const float* normals, int 
   return D3F_OK;
 }
 
+int info_run(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B, float grid_radius,
+             float max_distance, const int32_t* pairs, const int64_t* row_start, int P, int64_t rows, const double* T,
+             double* moments, int32_t* count, int32_t* status, void* ws, size_t ws_bytes, void* stream_) {
+  if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
+      rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) ||
+      (P > 0 && (!pairs || !T || !moments || !count || !status || !ws)))
+    return D3F_EINVAL;
+  if (P == 0) return D3F_OK;
+  if (ws_bytes < icp_layout(nullptr, P, rows, kInfo).bytes) return D3F_EWORKSPACE;
+  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
+  IcpLayout l = icp_layout(ws, P, rows, kInfo);
+  IcpArgs a = {};
+  a.points = points;
+  a.cloud_start = cloud_start;
+  a.pairs = pairs;
+  a.row_start = row_start;
+  a.placement = g.cnt + g.M + kPlacementWord;
+  a.S.start = g.start;
+  a.S.end = g.end;
+  a.S.pts = g.pts;
+  a.S.key = g.key;
+  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);
+  a.S.r2 = max_distance * max_distance;
+  a.S.prune_r = max_distance;
+  a.S.mask = g.M - 1;
+  a.T_init = T;
+  a.T_cur = l.T_cur;
+  a.prev = l.prev;
+  a.done = l.done;
+  a.partial = l.partial;
+  a.moments = moments;
+  a.count = count;
+  a.status = status;
+  a.rows = rows;
+  a.B = B;
+  a.P = P;
+  a.Ns = Ns;
+  hipStream_t stream = (hipStream_t)stream_;
+  info_setup_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(a);
+  D3F_LAUNCH_CHECK();
+  icp_search_kernel<kInfo><<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
+  info_finish_kernel<<<(unsigned)P, 64, 0, stream>>>(a);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t d3f_pair_information_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kInfo).bytes; }
+
+int d3f_pair_information(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                         float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                         int64_t rows, const double* T, double* moments, int32_t* count, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream_) {
+  return info_run(grid_ws, points, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P, rows, T, moments,
+                  count, status, ws, ws_bytes, stream_);
+}
 
 size_t d3f_icp_rigid_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kPoint).bytes; }
 size_t d3f_icp_rigid_plane_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kPlane).bytes; }

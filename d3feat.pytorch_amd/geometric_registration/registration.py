@@ -14,7 +14,12 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``refine_transforms`` / ``icp_numpy``  point-to-point ICP over the whole fragments after RANSAC (``ops.icp_rigid``, all
   pairs of a scene in one call) and its NumPy restatement -- ``estimate_transform`` / ``register_scene`` run it when
   given ``icp=dict(max_distance=...)``; ``estimation='point_to_plane'`` in that dict takes the point-to-plane form with
-  normals from ``ops.estimate_normals`` (NumPy restatement: ``estimate_normals_numpy``).
+  normals from ``ops.estimate_normals`` (NumPy restatement: ``estimate_normals_numpy``);
+* ``information_matrices`` / ``information_from_moments`` / ``information_numpy`` / ``writeinfo``  the 6x6 information
+  matrix of fragment pairs under given poses (``ops.pair_information``: one search, 20 raw moments per pair) -- the
+  matrix ``gt.info`` holds and a pose graph takes per edge -- and the writer of ``gt.info``;
+* ``build_benchmark`` / ``build_benchmark_files``  ``gt.log`` and ``gt.info`` of a scene from raw fragments with poses:
+  what ``register_scene`` and ``evaluate_registration`` need to score registration recall on scenes of one's own.
 
 Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
 target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
@@ -298,7 +303,7 @@ def _pair_list(keys_or_pairs):
 
 
 def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', estimation='point_to_point',
-                      normal_radius=None, **icp):
+                      normal_radius=None, return_information=False, **icp):
     """ICP refinement of fragment-pair poses, all pairs in ONE ``ops.icp_rigid`` call over one ``ops.CloudGrid`` of the
     fragments.  ``estimation``: ``'point_to_point'``, or ``'point_to_plane'`` -- the cell list is then built at
     ``max(normal_radius, max_distance)`` (``normal_radius`` defaults to ``2 * max_distance``), the normals of all
@@ -310,7 +315,9 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
     mapping fragment j into fragment i -- j is the moving cloud, i the fixed one.  ``icp``: ``max_iters``,
     ``rel_fitness``, ``rel_rmse`` of ``ops.icp_rigid``.  Returns ``(T [P,4,4] f64, fitness [P] = matched share of j's
     points under the returned T, rmse [P], iterations [P])``: device tensors, or NumPy arrays from ``device='cpu'``
-    (``icp_numpy``).  A pair that ends with fewer than 3 matches keeps the pose it had then."""
+    (``icp_numpy``).  A pair that ends with fewer than 3 matches keeps the pose it had then.
+    ``return_information=True`` appends ``info [P,6,6]``, the benchmark-form information matrices of the RETURNED poses
+    at ``max_distance`` (``information_matrices``): one more call on the cell list that is already built."""
     if estimation not in ('point_to_point', 'point_to_plane'):
         raise ValueError("estimation must be 'point_to_point' or 'point_to_plane', got %r" % (estimation,))
     plane = estimation == 'point_to_plane'
@@ -328,7 +335,9 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
         if plane:
             icp = dict(icp, normals=estimate_normals_numpy(arrs, normal_radius)[0])
         Tr, count, rmse, iters, _ = icp_numpy(arrs, ji, Tn, max_distance, **icp)
-        return Tr, count / np.maximum(lens[ji[:, 0]], 1), rmse, iters
+        res = (Tr, count / np.maximum(lens[ji[:, 0]], 1), rmse, iters)
+        return res + (information_from_moments(information_numpy(arrs, ji, Tr, max_distance)[0]),) \
+            if return_information else res
     dev = torch.device(device)
     pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
     grid = ops.CloudGrid(pts, lens, max(float(normal_radius), float(max_distance)) if plane else float(max_distance))
@@ -337,7 +346,105 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
     Tr, count, rmse, iters, _ = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
                                               max_distance, **icp)
     fitness = count.double() / torch.as_tensor(np.maximum(lens[ji[:, 0]], 1), dtype=torch.float64, device=dev)
+    if return_information:
+        return Tr, fitness, rmse, iters, information_from_moments(ops.pair_information(grid, None, ji, Tr,
+                                                                                        max_distance)[0])
     return Tr, fitness, rmse, iters
+
+
+# ------------------------------------------------------------------------------------------------- information matrices
+INFO_MOMENTS = 20              # ops.INFO_MOMENTS: n, sum x (3), sum x x^T (6), sum y (3), sum y y^T (6), sum d2
+
+
+def information_from_moments(moments, frame='moving', order='translation_first'):
+    """[P,6,6] f64 information matrices from the ``[P,20]`` raw moments of ``ops.pair_information`` /
+    ``information_numpy`` (NumPy array or tensor; the result is of the same kind): sum of ``G^T G`` over the accepted
+    rows with ``G = [I | -[p]x]``, i.e. ``[[n I, -[s]x], [[s]x, sum (|p|^2 I - p p^T)]]``, ``s = sum p``.
+    ``frame='moving'`` takes p = x, the moving point in its own frame -- the frame ``transformation_error``'s
+    ``D = inv(T_gt) T_est`` acts in, and with ``order='translation_first'`` the form of the benchmark's ``gt.info``
+    (the defaults).  ``frame='fixed'`` takes p = y, the matched fixed point, and ``order='rotation_first'`` puts the
+    rotation block first: together the form of Open3D's ``get_information_matrix_from_point_clouds`` -- stated from its
+    formula and tested against a brute-force sum of it; Open3D itself was not available to compare with.  A pair with
+    n = 0 gives zeros."""
+    if frame not in ('moving', 'fixed') or order not in ('translation_first', 'rotation_first'):
+        raise ValueError("frame must be 'moving' or 'fixed', order 'translation_first' or 'rotation_first'")
+    tensor = isinstance(moments, torch.Tensor)
+    m = moments.double() if tensor else np.asarray(moments, dtype=np.float64)
+    if m.shape[-1] != INFO_MOMENTS:
+        raise ValueError("moments must be [P,%d], got %s" % (INFO_MOMENTS, tuple(m.shape)))
+    m = m.reshape(-1, INFO_MOMENTS)
+    o = 1 if frame == 'moving' else 10
+    n, sx, sy, sz = m[:, 0], m[:, o], m[:, o + 1], m[:, o + 2]
+    xx, xy, xz, yy, yz, zz = (m[:, o + 3 + k] for k in range(6))
+    z = torch.zeros_like(n) if tensor else np.zeros_like(n)
+    rows = [[n, z, z, z, sz, -sy], [z, n, z, -sz, z, sx], [z, z, n, sy, -sx, z],
+            [z, -sz, sy, yy + zz, -xy, -xz], [sz, z, -sx, -xy, xx + zz, -yz], [-sy, sx, z, -xz, -yz, xx + yy]]
+    stack = torch.stack if tensor else np.stack
+    info = stack([stack(r, -1) for r in rows], -2)
+    if order == 'rotation_first':
+        perm = [3, 4, 5, 0, 1, 2]
+        info = info[:, perm][:, :, perm]
+    return info
+
+
+def information_numpy(clouds, pairs, T, max_distance):
+    """The contract of ``ops.pair_information`` in NumPy (include/d3feat_hip.h): the search of
+    ``preprocess.nearest_pairs_numpy`` and f64 sums over its accepted rows.  ``clouds``: list of [n,3] f32 arrays; pair
+    p = (moving cloud a, fixed cloud b), ``T[p]`` maps a into b's frame.  Returns ``(moments f64 [P,20], count int32
+    [P])``."""
+    from ..datasets.preprocess import nearest_pairs_numpy, transform_points
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    T = _pose44(T, pairs.shape[0])
+    arrs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds]
+    nn, count, row_start = nearest_pairs_numpy(arrs, pairs, T, max_distance)
+    moments = np.zeros((pairs.shape[0], INFO_MOMENTS), dtype=np.float64)
+    iu = np.triu_indices(3)
+    for p, (a, b) in enumerate(pairs):
+        res = nn[row_start[p]:row_start[p + 1]]
+        sel = res >= 0
+        x32, y32 = arrs[a][sel], arrs[b][res[sel]]
+        d = transform_points(x32, T[p]) - y32                                # f32, the kernel's d2
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        x, y = x32.astype(np.float64), y32.astype(np.float64)
+        moments[p, 0] = x.shape[0]
+        moments[p, 1:4], moments[p, 10:13] = x.sum(0), y.sum(0)
+        moments[p, 4:10] = (x[:, iu[0]] * x[:, iu[1]]).sum(0)
+        moments[p, 13:19] = (y[:, iu[0]] * y[:, iu[1]]).sum(0)
+        moments[p, 19] = d2.astype(np.float64).sum()
+    return moments, count
+
+
+def _rmse_from_moments(moments):
+    n, sd2 = moments[:, 0], moments[:, INFO_MOMENTS - 1]
+    if isinstance(moments, torch.Tensor):
+        return torch.where(n > 0, torch.sqrt(sd2 / n.clamp(min=1.0)), torch.zeros_like(n))
+    return np.where(n > 0, np.sqrt(sd2 / np.maximum(n, 1.0)), 0.0)
+
+
+def information_matrices(clouds, keys_or_pairs, T, max_distance, device='cuda', frame='moving',
+                         order='translation_first'):
+    """Information matrices of fragment pairs under the poses ``T``, all pairs in ONE ``ops.pair_information`` call
+    over one ``ops.CloudGrid`` of the fragments.  ``clouds``, ``keys_or_pairs``, ``T``: as in ``refine_transforms`` --
+    keys ``'i_j'`` or (i, j) tuples with ``T[p]`` mapping fragment j into fragment i; j is the moving cloud.  A moving
+    point counts when its nearest point of i under ``T[p]`` is closer than ``max_distance``.  ``frame``, ``order``:
+    ``information_from_moments`` (the defaults are the benchmark's ``gt.info`` form).  Returns ``(info [P,6,6] f64,
+    count [P], rmse [P])``: device tensors, or NumPy arrays from ``device='cpu'`` (``information_numpy``)."""
+    ij = _pair_list(keys_or_pairs)
+    ji = ij[:, ::-1].copy()
+    if ij.size and (ij.min() < 0 or ij.max() >= len(clouds)):
+        raise ValueError("pairs name fragments outside 0..%d" % (len(clouds) - 1))
+    if str(device).startswith('cpu'):
+        arrs = [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
+                for c in clouds]
+        Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
+        moments, count = information_numpy(arrs, ji, Tn, max_distance)
+    else:
+        dev = torch.device(device)
+        pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
+        grid = ops.CloudGrid(pts, np.asarray([int(c.shape[0]) for c in clouds], dtype=np.int64), float(max_distance))
+        moments, count, _ = ops.pair_information(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
+                                                 max_distance)
+    return information_from_moments(moments, frame, order), count, _rmse_from_moments(moments)
 
 
 # ------------------------------------------------------------------------------------------------- gt.info, metric
@@ -353,6 +460,21 @@ def loadinfo(gtpath):
         mat = np.array([[float(x) for x in rows[i + r].split()[0:6]] for r in range(1, 7)], dtype=np.float64)
         out['%d_%d' % (int(head[0]), int(head[1]))] = mat
     return out
+
+
+def writeinfo(gtpath, info, num_frag):
+    """Inverse of :func:`loadinfo`: ``{'i_j': 6x6}`` to ``<gtpath>/gt.info`` in the layout of the benchmark's files --
+    per key, ordered by (i, j), an ``i \\t j \\t num_frag`` line and six rows in ``%.8e``."""
+    os.makedirs(gtpath, exist_ok=True)
+    with open(os.path.join(gtpath, 'gt.info'), 'w') as f:
+        for key in sorted(info, key=lambda k: tuple(int(x) for x in k.split('_'))):
+            a, b = key.split('_')
+            mat = np.asarray(info[key], dtype=np.float64)
+            if mat.shape != (6, 6):
+                raise ValueError("info[%r] must be 6x6, got %s" % (key, mat.shape))
+            f.write('%d\t %d\t %d\t\n' % (int(a), int(b), num_frag))
+            for row in mat:
+                f.write(''.join(' % .8e\t ' % v for v in row).rstrip(' ') + '\n')
 
 
 def _quaternion(R):
@@ -459,3 +581,137 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     if not os.path.exists(os.path.join(gtpath, 'gt.info')):
         return None
     return evaluate_registration(est, gt, loadinfo(gtpath))
+
+
+# ------------------------------------------------------------------------------------------------- gt.log / gt.info
+MAX_PAIRS = 65535              # pairs per ops.pair_information call
+
+
+def _job_chunks(units, rows_of, max_rows):
+    """``preprocess._chunks`` with the call's pair cap on top: consecutive groups of units of at most ``max_rows``
+    moving rows and ``MAX_PAIRS`` jobs, one unit at least."""
+    from ..datasets.preprocess import _chunks
+    out = []
+    for chunk in _chunks(units, rows_of, max_rows):
+        cur, n = [], 0
+        for u in chunk:
+            if cur and n + len(u) > MAX_PAIRS:
+                out.append(cur)
+                cur, n = [], 0
+            cur.append(u)
+            n += len(u)
+        out.append(cur)
+    return out
+
+
+def build_benchmark(fragments, poses, out_dir, voxel, radius=None, min_overlap=0.3, info_distance=None,
+                    symmetric=False, device='cuda', max_rows=1 << 23, subsample=None):
+    """Writes ``gt.log`` and ``gt.info`` of ONE scene into ``out_dir`` from raw fragments with poses -- the two files
+    ``register_scene(save_path, scene, gtpath=out_dir)`` and ``evaluate_registration`` score registration recall with.
+
+    The benchmark ships these files for its eight test scenes only and no code that makes them, so the rule is stated
+    here rather than copied, as ``datasets/preprocess.py`` states the rule of the training pickles: ``fragments`` (a
+    list of [N,3] arrays in their own frames) are voxel-subsampled at ``voxel`` (``preprocess.subsample_fragments``;
+    ``voxel=None`` takes them as they are), ``poses`` [F,4,4] f64 map fragment to world.  Candidates are the pairs
+    i < j of ``preprocess.candidate_pairs``.  For the key ``i_j``, ``T = inv(P_i) @ P_j`` maps j into i: j is the
+    MOVING cloud, i the fixed one.  The OVERLAP of ``i_j`` is the share of j's points whose nearest point of i under T
+    is closer than ``radius`` (default ``1.25 * voxel``, the training pickles' rule); with ``symmetric=True`` the
+    direction i into j is searched too and the larger share decides.  Pairs whose overlap exceeds ``min_overlap`` (and
+    that have a correspondence in the direction j into i) are kept.  The information matrix of a kept pair is the
+    benchmark's form (``information_from_moments`` defaults) over the correspondences at ``info_distance`` (default
+    ``radius``: one ``ops.pair_information`` call then serves both the overlap and the matrices).  Calls hold at most
+    ``max_rows`` moving rows and 65535 pairs; a pair's result does not depend on the chunking.  ``device='cpu'`` is the
+    NumPy path (``information_numpy``).
+
+    Files made here follow THIS rule; they are not claimed to equal the benchmark's download, whose fragments are not
+    available to compare against (its blocks hold at most 5000 points each, whatever sampling produced that).
+
+    Returns ``(gt {'i_j': 4x4}, info {'i_j': 6x6}, overlap {'i_j': share})``; ``overlap`` lists every candidate."""
+    from ..datasets.preprocess import candidate_pairs, subsample_fragments
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if poses.shape[0] != len(fragments):
+        raise ValueError("%d poses for %d fragments" % (poses.shape[0], len(fragments)))
+    if radius is None:
+        if voxel is None:
+            raise ValueError("radius is required when voxel is None")
+        radius = 1.25 * voxel
+    radius = float(radius)
+    info_distance = radius if info_distance is None else float(info_distance)
+    clouds = subsample_fragments(fragments, voxel, subsample, device)
+    lens = np.array([c.shape[0] for c in clouds], dtype=np.int64)
+    ij, T_ij = candidate_pairs(clouds, poses, max(radius, info_distance))     # T_ij maps i into j
+    # jobs (moving, fixed, T): j into i for every candidate and, when symmetric, i into j right behind it
+    job_pairs, job_T, units = [], [], []
+    for p in range(ij.shape[0]):
+        unit = [len(job_pairs)]
+        job_pairs.append(ij[p, ::-1])
+        job_T.append(np.linalg.inv(poses[ij[p, 0]]) @ poses[ij[p, 1]])
+        if symmetric:
+            unit.append(len(job_pairs))
+            job_pairs.append(ij[p])
+            job_T.append(T_ij[p])
+        units.append(unit)
+    job_pairs = np.asarray(job_pairs, dtype=np.int64).reshape(-1, 2)
+    job_T = np.asarray(job_T, dtype=np.float64).reshape(-1, 4, 4)
+    rows_of = lens[job_pairs[:, 0]] if len(job_pairs) else np.zeros(0, np.int64)
+    on_cpu = str(device).startswith('cpu')
+    grid = None
+    if not on_cpu and len(job_pairs):
+        dev = torch.device(device)
+        grid = ops.CloudGrid(torch.as_tensor(np.concatenate(clouds, 0)).to(dev), lens, max(radius, info_distance))
+
+    def search(jobs, distance):
+        """(moments [len(jobs),20], count) of the listed jobs, in chunks."""
+        moments = np.zeros((len(jobs), INFO_MOMENTS))
+        count = np.zeros(len(jobs), dtype=np.int64)
+        at = {j: k for k, j in enumerate(jobs)}
+        # jobs of one fixed cloud next to each other: workgroups in flight together read the same part of the cell list
+        order = sorted(([j] for j in jobs), key=lambda u: (int(job_pairs[u[0], 1]), u[0]))
+        for chunk in _job_chunks(order, rows_of, int(max_rows)):
+            js = [u[0] for u in chunk]
+            if on_cpu:
+                m, c = information_numpy(clouds, job_pairs[js], job_T[js], distance)
+            else:
+                m, c, st = (t.cpu().numpy() for t in ops.pair_information(grid, None, job_pairs[js], job_T[js],
+                                                                          distance))
+                if st.any():
+                    raise RuntimeError("pair_information flagged pairs %s with status %s"
+                                       % (job_pairs[js][st != 0].tolist(), st[st != 0].tolist()))
+            where = [at[j] for j in js]
+            moments[where], count[where] = m, c
+        return moments, count
+
+    moments, count = search(list(range(len(job_pairs))), radius)
+    share = count / np.maximum(rows_of, 1)
+    gt, overlap, kept = {}, {}, []
+    for u in units:
+        j, i = (int(v) for v in job_pairs[u[0]])
+        key = '%d_%d' % (i, j)
+        overlap[key] = float(max(share[k] for k in u))
+        if overlap[key] > min_overlap and count[u[0]] > 0:
+            gt[key] = job_T[u[0]]
+            kept.append(u[0])
+    if info_distance != radius and kept:
+        moments_kept = search(kept, info_distance)[0]
+    else:
+        moments_kept = moments[kept]
+    if grid is not None:
+        grid.status.raise_if_set()
+    mats = information_from_moments(moments_kept.reshape(-1, INFO_MOMENTS))
+    info = {'%d_%d' % (int(job_pairs[k, 1]), int(job_pairs[k, 0])): mats[n] for n, k in enumerate(kept)}
+    ev.writelog(out_dir, gt, len(fragments))
+    writeinfo(out_dir, info, len(fragments))
+    return gt, info, overlap
+
+
+def build_benchmark_files(root, scene, out_dir, voxel, **kw):
+    """``build_benchmark`` over ``<root>/fragments/<scene>`` (``preprocess.read_scene``: ``cloud_bin_<i>.ply`` with
+    ``poses.npy`` or ``cloud_bin_<i>.info.txt``).  The keys of the files are fragment numbers, so the folder must hold
+    ``cloud_bin_0 .. cloud_bin_<F-1>`` without a gap.  The files follow ``build_benchmark``'s rule and are not claimed
+    to equal the benchmark's download."""
+    from ..datasets.preprocess import read_scene
+    ids, points, poses = read_scene(root, scene)
+    numbers = [int(i.rsplit('_', 1)[1]) for i in ids]
+    if numbers != list(range(len(ids))):
+        raise ValueError("%s: the fragments must be numbered 0..%d without a gap" % (scene, len(ids) - 1))
+    return build_benchmark(points, poses, out_dir, voxel, **kw)

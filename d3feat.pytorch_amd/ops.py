@@ -2839,6 +2839,13 @@ def icp_plane_bytes(rows, found=None):
             + 12 * (rows if found is None else int(found)))
 
 
+def pair_information_bytes(rows, found=None):
+    """Algorithmic bytes of the ONE search of ``pair_information``: ``icp_rigid_bytes`` with 160 bytes of sums (20 f64)
+    per workgroup in place of 136."""
+    rows = int(rows)
+    return icp_rigid_bytes(rows, found) + 2 * (160 - 136) * (-(-rows // ICP_BLOCK_ROWS))
+
+
 def estimate_normals_bytes(n, neighbors=None):
     """Algorithmic bytes of the normals of ``n`` points: the point (12), the (start, end) headers of 27 buckets (216),
     the stored point and cell key of every candidate the accepted cells hold (24 each; ``neighbors`` of them in all, by
@@ -2890,6 +2897,51 @@ def estimate_normals(grid_or_points, lens, radius, min_neighbors=3, viewpoint=No
     return (normals, count, moments) if return_moments else (normals, count)
 
 
+def _icp_arguments(grid_or_points, lens, pairs, T, max_distance, rows, name):
+    """The argument forms ``icp_rigid`` and ``pair_information`` share -> (grid, device, B, cloud_start, pairs int32
+    [P,2], P, T f64 [P,3,4], row_start int64 [P+1], rows)."""
+    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
+        grid = grid_or_points
+        if float(max_distance) > grid.radius:
+            raise RuntimeError("max_distance %g exceeds the cell list's %g" % (float(max_distance), grid.radius))
+    else:
+        if lens is None:
+            raise ValueError("lens is required with stacked points")
+        grid = CloudGrid(grid_or_points, lens, max_distance)
+    if not (0.0 < float(max_distance) < float("inf")):
+        raise ValueError("max_distance must be positive and finite")
+    dev = grid.supports.device
+    B = int(grid.s_len.numel())
+    cloud_start = getattr(grid, "cloud_start", None)
+    if cloud_start is None:
+        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
+    host = None
+    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
+    else:
+        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if host.size and (host.min() < 0 or host.max() >= B):
+            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
+        pr = torch.as_tensor(host.astype(np.int32), device=dev)
+    P = int(pr.shape[0])
+    if not 1 <= P <= MAX_CLOUDS:
+        raise ValueError("1..%d pairs per call, got %d" % (MAX_CLOUDS, P))
+    tf = torch.as_tensor(T, dtype=torch.float64).to(dev)
+    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4)):
+        raise ValueError("%s must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (name, P, tuple(tf.shape)))
+    tf = tf[:, :3, :].contiguous()
+    lens_host = getattr(grid, "lens_host", None)
+    if host is not None and lens_host is not None:
+        rs = np.zeros(P + 1, dtype=np.int64)
+        rs[1:] = np.cumsum(lens_host[host[:, 0]])
+        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
+    else:
+        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long().clamp(0, B - 1)], 0)
+        rows = int(rows) if rows is not None else int(row_start[-1].item())   # (the one read-back of this form)
+    return grid, dev, B, cloud_start, pr, P, tf, row_start, rows
+
+
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
               return_trace=False, rows=None, normals=None):
     """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).
@@ -2913,47 +2965,12 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     whose 6x6 normal equations are singular (the overlap is one plane, or has only zero normals) stops at its current
     pose with ``ICP_ST_SINGULAR``.  It converges in a handful of iterations from a good pose and can stall or diverge
     where point-to-point does not -- on a low overlap that is mostly one plane, or from a poor start."""
-    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
-        grid = grid_or_points
-        if float(max_distance) > grid.radius:
-            raise RuntimeError("max_distance %g exceeds the cell list's %g" % (float(max_distance), grid.radius))
-    else:
-        if lens is None:
-            raise ValueError("lens is required with stacked points")
-        grid = CloudGrid(grid_or_points, lens, max_distance)
     if not 0 <= int(max_iters) <= ICP_MAX_ITERS:
         raise ValueError("max_iters must be in 0..%d" % ICP_MAX_ITERS)
-    if not (0.0 < float(max_distance) < float("inf")) or not float(rel_fitness) >= 0.0 or not float(rel_rmse) >= 0.0:
-        raise ValueError("max_distance must be positive and finite, rel_fitness and rel_rmse non-negative")
-    dev = grid.supports.device
-    B = int(grid.s_len.numel())
-    cloud_start = getattr(grid, "cloud_start", None)
-    if cloud_start is None:
-        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
-    host = None
-    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
-        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
-    else:
-        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-        if host.size and (host.min() < 0 or host.max() >= B):
-            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
-        pr = torch.as_tensor(host.astype(np.int32), device=dev)
-    P = int(pr.shape[0])
-    if not 1 <= P <= MAX_CLOUDS:
-        raise ValueError("1..%d pairs per call, got %d" % (MAX_CLOUDS, P))
-    tf = torch.as_tensor(T_init, dtype=torch.float64).to(dev)
-    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4)):
-        raise ValueError("T_init must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (P, tuple(tf.shape)))
-    tf = tf[:, :3, :].contiguous()
-    lens_host = getattr(grid, "lens_host", None)
-    if host is not None and lens_host is not None:
-        rs = np.zeros(P + 1, dtype=np.int64)
-        rs[1:] = np.cumsum(lens_host[host[:, 0]])
-        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
-    else:
-        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
-        row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long().clamp(0, B - 1)], 0)
-        rows = int(rows) if rows is not None else int(row_start[-1].item())   # (the one read-back of this form)
+    if not float(rel_fitness) >= 0.0 or not float(rel_rmse) >= 0.0:
+        raise ValueError("rel_fitness and rel_rmse must be non-negative")
+    grid, dev, B, cloud_start, pr, P, tf, row_start, rows = _icp_arguments(grid_or_points, lens, pairs, T_init,
+                                                                           max_distance, rows, "T_init")
     K = int(max_iters)
     T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
     count, iterations, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
@@ -2978,6 +2995,36 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
             _p(iterations), _p(status), _p(trace), _p(ws), nbytes, _stream()), name)
     res = (T, count, rmse, iterations, status)
     return res + (trace,) if return_trace else res
+
+
+INFO_MOMENTS = 20   # n, sum x (3), sum x x^T (6), sum y (3), sum y y^T (6), sum d2
+
+
+def pair_information(grid_or_points, lens, pairs, T, max_distance, rows=None):
+    """Raw moments of the correspondences of P cloud pairs under the GIVEN poses (d3f_pair_information) -- what the 6x6
+    information matrix of a pair is made of (``registration.information_from_moments``; the benchmark's ``gt.info``).
+
+    Arguments as in ``icp_rigid``: pair p = (MOVING cloud a, FIXED cloud b), ``T`` f64 [P,4,4] or [P,3,4] maps points
+    of a into b's frame; host or device ``pairs``; ``rows`` for the captured form.  ONE search -- ``icp_rigid``'s
+    iteration 0, bit for bit -- and over its accepted rows, in f64, ``moments [P,20]`` = n, sum x (3), the upper
+    triangle of sum x x^T (xx, xy, xz, yy, yz, zz), sum y (3), the upper triangle of sum y y^T (6), sum d2: x the moving
+    point in its OWN frame, y the matched fixed point, raw (no pivots).  Returns device tensors ``(moments, count [P]
+    int32, status [P] int32)``; a pair flagged ``ICP_ST_PAIR`` / ``ICP_ST_NONFINITE`` has zero moments.  Three
+    launches, bit-identical from run to run and for a pair alone or inside any batch; no read-back when the lengths and
+    pairs are known on the host, or when ``rows`` comes with device ``pairs``."""
+    grid, dev, B, cloud_start, pr, P, tf, row_start, rows = _icp_arguments(grid_or_points, lens, pairs, T,
+                                                                           max_distance, rows, "T")
+    moments = torch.empty((P, INFO_MOMENTS), dtype=torch.float64, device=dev)
+    count, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
+    L = _native.lib()
+    nbytes = L.d3f_pair_information_ws_bytes(P, rows)
+    ws = _ws(nbytes, dev)
+    with _region("pair_information[P=%d,rows=%d]" % (P, rows), pair_information_bytes(rows)):
+        _native.check(L.d3f_pair_information(
+            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
+            _p(row_start), P, rows, _p(tf), _p(moments), _p(count), _p(status), _p(ws), nbytes, _stream()),
+            "d3f_pair_information")
+    return moments, count, status
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -872,6 +872,41 @@ int d3f_icp_plane_fit_host(const double* sums_host, const double* py_host, const
                            int* singular_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Raw moments of the accepted correspondences of cloud pairs under GIVEN poses -- what the 6x6 information matrix of a
+ * pair is made of (the benchmark's gt.info, which registration recall is scored under, and the weight of an edge of a
+ * pose graph; Open3D's get_information_matrix_from_point_clouds).  The clouds, the cell list (grid_ws, grid_radius),
+ * cloud_start, pairs and row_start are those of d3f_icp_rigid: pair p = (pairs[2p] MOVING cloud a, pairs[2p+1] FIXED
+ * cloud b) and T [P,12] f64 (row-major 3x4 per pair) maps points of a into b's frame.  For a gt.log key i_j the pair is
+ * (j, i) with the gt.log matrix as it stands.
+ *   1. ONE search under T with the arithmetic, acceptance (d2 < max_distance * max_distance, f32) and tie rule of
+ *      d3f_nearest_pairs -- iteration 0 of d3f_icp_rigid.
+ *   2. Over the accepted rows, in f64, with x the moving point's OWN f32 coordinates (not moved by T) and y the matched
+ *      fixed point:
+ *        moments[20] = { n, sum x (3), sum x x^T (xx, xy, xz, yy, yz, zz), sum y (3), sum y y^T (6), sum d2 }
+ *      (the f32 d2 widened, as in ICP).  RAW moments, no pivots: a product of two f32 values is exact in f64 and nothing
+ *      is subtracted afterwards.  With G = [I | -[p]x] the information matrix sum G^T G is
+ *      [[n I, -[s]x], [[s]x, sum (|p|^2 I - p p^T)]], s = sum p: the benchmark's form takes p = x (the error
+ *      D = inv(T_gt) T_est acts in the moving cloud's frame), Open3D's takes p = y and puts the rotation block first.
+ * Outputs per pair: moments [P,20] f64; count [P] int32 (= n); status [P] int32 (D3F_ICP_ST_* bits).  A pair that names
+ * a cloud outside [0, B), or whose rows reach beyond `rows`, gets D3F_ICP_ST_PAIR; a non-finite T D3F_ICP_ST_NONFINITE;
+ * both give zero moments and count 0.  D3F_ICP_ST_CELL_RANGE as in d3f_icp_rigid.  A pair without an accepted row has
+ * zero moments and status 0.
+ * Deterministic and batch-independent by d3f_icp_rigid's orders: a workgroup serves D3F_ICP_BLOCK_ROWS consecutive rows
+ * of ONE pair, lanes add in slice order, waves by the fixed butterfly and then in wave order, and a finishing launch
+ * adds the pair's workgroups in the fit's order -- no floating-point atomics -- so a pair's moments are bit-identical
+ * alone or inside any batch and from run to run.
+ * `rows` >= row_start[P] sizes the launches and the workspace (d3f_pair_information_ws_bytes(P, rows)); P <= 65535,
+ * max_distance <= grid_radius.  3 launches on `stream` whatever the data, no host synchronisation, no allocation
+ * (graph-capturable).
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_INFO_MOMENTS 20
+size_t d3f_pair_information_ws_bytes(int P, int64_t rows);
+int d3f_pair_information(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                         float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                         int64_t rows, const double* T, double* moments, int32_t* count, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
