@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libd3feat_hip.so")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
-           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip"]
+           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -31,6 +31,14 @@ class AtbProblem(C.Structure):
     _fields_ = [("x", _vp), ("grad_out", _vp), ("grad_w", _vp), ("N", C.c_int32), ("Cin", C.c_int32),
                 ("Cout", C.c_int32), ("ldw", C.c_int32), ("bias_part", _vp), ("bias_blocks", C.c_int32),
                 ("bias_cols", C.c_int32), ("grad_bias", _vp), ("grad_bias2", _vp)]
+
+
+class AugmentJob(C.Structure):
+    """d3f_augment_job of include/d3feat_hip.h: one training item of the resident 3DMatch split."""
+    _fields_ = [("src_off", C.c_int64), ("tgt_off", C.c_int64), ("corr_off", C.c_int64), ("src_len", C.c_int32),
+                ("tgt_len", C.c_int32), ("corr_len", C.c_int32), ("reserved", C.c_int32), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("key", C.c_uint64), ("out_src", _vp), ("out_tgt", _vp), ("out_corr", _vp),
+                ("out_dist", _vp)]
 
 
 # name -> (restype, argtypes); mirrors include/d3feat_hip.h one to one
@@ -165,6 +173,10 @@ SIGNATURES = {
                               _vp, _sz, _vp]),
     "d3f_ransac_sample_host": (_i, [C.c_uint64, _i, _i, _i, _vp]),
     "d3f_rigid_fit_host": (_i, [_vp, _vp, _i, _vp]),
+    "d3f_augment_pairs_ws_bytes": (_sz, [_i, _i]),
+    "d3f_augment_pairs": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(AugmentJob), _i, _i, _d, _vp, _sz, _vp]),
+    "d3f_augment_item_host": (_i, [_vp, _vp, C.POINTER(AugmentJob), _i, _d]),
+    "d3f_augment_key_host": (C.c_uint64, [C.c_uint64, _i, C.c_uint32]),
     "d3f_cloud_grid_build": (_i, [_vp, _i, _vp, _i, _f, _vp, _sz, _vp, _vp]),
     "d3f_nearest_pairs": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp]),
     "d3f_nearest_pairs_lanes": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _i,

@@ -2,6 +2,7 @@
 has it).  Every function here launches hand-written HIP kernels from ``libd3feat_hip.so``; none has a PyTorch or
 CPU fallback.  Reference locations are cited per operator.
 """
+import collections
 import numpy as np
 import ctypes
 import threading
@@ -2700,6 +2701,58 @@ def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, e
         _p(hc), _p(hr), _p(ws), nbytes, _stream()), "d3f_ransac_rigid")
     res = (T,) + tuple(out)
     return res + (hc, hr) if return_hypotheses else res
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# training items from a device-resident split (datasets.ThreeDMatch.ThreeDMatchResident)
+# ---------------------------------------------------------------------------------------------------------------
+AUGMENT_MAX_JOBS = 16
+AUGMENT_MAX_NODE = 1024
+# one item: rows of its clouds in the packed point store, rows of its table in the packed correspondence store, the
+# target's rigid transform (R [3,3], t [3]; float64) and the 64-bit item key
+AugmentJob = collections.namedtuple('AugmentJob', 'src_off src_len tgt_off tgt_len corr_off corr_len R t key')
+
+
+def augment_pairs(points, corr, jobs, num_node, noise):
+    """Up to 16 training items in one call of two launches (d3f_augment_pairs; arithmetic in csrc/augment.hpp).
+
+    ``points`` f32 [sumN,3] and ``corr`` int32 [sumM,2] are the packed device stores, ``jobs`` a sequence of
+    ``AugmentJob``.  Returns one ``(pts0 f32 [n0,3], pts1 f32 [n1,3], sel_corr int64 [m,2], dist_keypts f64 [m,m])`` per
+    job, m = min(corr_len, num_node), launched on the current stream (no copy, no host synchronisation)."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2
+            and points.shape[1] == 3 and points.is_contiguous()):
+        raise RuntimeError("points must be a contiguous CUDA/HIP float32 [sumN,3] tensor (no CPU path)")
+    if not (isinstance(corr, torch.Tensor) and corr.is_cuda and corr.dtype == torch.int32 and corr.dim() == 2
+            and corr.shape[1] == 2 and corr.is_contiguous()):
+        raise RuntimeError("corr must be a contiguous CUDA/HIP int32 [sumM,2] tensor (no CPU path)")
+    B, k = len(jobs), int(num_node)
+    if not 1 <= B <= AUGMENT_MAX_JOBS:
+        raise ValueError("1..%d jobs per call" % AUGMENT_MAX_JOBS)
+    if not 1 <= k <= AUGMENT_MAX_NODE:
+        raise ValueError("num_node must be in 1..%d" % AUGMENT_MAX_NODE)
+    dev = points.device
+    arr = (_native.AugmentJob * B)()
+    out = []
+    for q, j in zip(arr, jobs):
+        if int(j.corr_len) < 1:
+            raise ValueError("a pair without correspondences cannot be sampled")
+        m = min(int(j.corr_len), k)
+        o = (torch.empty((int(j.src_len), 3), dtype=torch.float32, device=dev),
+             torch.empty((int(j.tgt_len), 3), dtype=torch.float32, device=dev),
+             torch.empty((m, 2), dtype=torch.int64, device=dev), torch.empty((m, m), dtype=torch.float64, device=dev))
+        q.src_off, q.src_len, q.tgt_off, q.tgt_len = int(j.src_off), int(j.src_len), int(j.tgt_off), int(j.tgt_len)
+        q.corr_off, q.corr_len, q.key = int(j.corr_off), int(j.corr_len), int(j.key) & 0xffffffffffffffff
+        q.R[:] = [float(v) for v in np.asarray(j.R, dtype=np.float64).reshape(9)]
+        q.t[:] = [float(v) for v in np.asarray(j.t, dtype=np.float64).reshape(3)]
+        q.out_src, q.out_tgt, q.out_corr, q.out_dist = (t.data_ptr() for t in o)
+        out.append(o)
+    L = _native.lib()
+    nbytes = L.d3f_augment_pairs_ws_bytes(B, k)
+    ws = _ws(nbytes, dev) if nbytes else None
+    with _region("augment_pairs"):
+        _native.check(L.d3f_augment_pairs(_p(points), int(points.shape[0]), _p(corr), int(corr.shape[0]), arr, B, k,
+                                          float(noise), _p(ws), nbytes, _stream()), "d3f_augment_pairs")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------

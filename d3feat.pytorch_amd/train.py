@@ -577,6 +577,12 @@ class TrainStep:
         side stream, which does not wait for the training stream (step_graph), and a copy queued on the training
         stream would sit behind a whole network step.  ~0.6 MB per pair."""
         if all(isinstance(t, torch.Tensor) and t.device == self.device for t in item):
+            if self.device.type == 'cuda':   # device items (ThreeDMatchResident) were written on their maker's stream
+                if getattr(self, '_side', None) is None:
+                    self._side = torch.cuda.Stream(device=self.device)
+                for t in item:
+                    t.record_stream(torch.cuda.current_stream(self.device))
+                    t.record_stream(self._side)
             return item
         if self.device.type != 'cuda':
             return tuple(torch.as_tensor(t).to(dtype=k) for t, k in zip(item, self.ITEM_DTYPES))

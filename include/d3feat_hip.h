@@ -737,6 +737,50 @@ int d3f_ransac_sample_host(uint64_t seed, int p, int h, int count, int32_t* out_
 int d3f_rigid_fit_host(const double* src_host, const double* tgt_host, int n, double* out_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training items from a device-resident 3DMatch split -- replaces the per-item host work of the reference's
+ * ThreeDMatchDataset.__getitem__ (ThreeDMatch.py:93-149: float64 copies, rotation, two noise draws, a choice over the
+ * correspondences, cdist) and the upload that follows it.  The split is stored once on the device as `points`
+ * [sumN,3] f32 (all fragments packed) and `corr` [sumM,2] int32 (all pairs' tables packed, rows = fragment-local
+ * (source, target) indices).  A job names one item: where its two clouds and its table sit in the stores, the rigid
+ * transform of the target (R row-major 3x3, t; f64), a 64-bit item key and its four output buffers ON THE DEVICE:
+ *   out_src [src_len,3] f32, out_tgt [tgt_len,3] f32, out_corr [m,2] int64, out_dist [m,m] f64,  m = min(corr_len, k).
+ * All randomness is the counter-based hash of (key, stream, index) written in csrc/augment.hpp, which also fixes the
+ * f64 operation order of the points and of out_dist; a job's outputs are the same bits alone or in any batch.
+ * out_corr: corr_len > k: the k rows j with the smallest z(7, j), in ascending z (keys are distinct: no tie rule);
+ * otherwise all rows in table order.  out_dist: distances between the augmented f32 source points of out_corr's rows.
+ * d3f_augment_pairs: 1 <= B <= D3F_AUGMENT_MAX_JOBS jobs given as a HOST array that travels in the kernel argument;
+ * two launches, no copy, no host synchronisation (graph-capturable).  The selection runs in one workgroup per job:
+ * radix histograms of the recomputed keys in LDS narrow the k-th smallest down to at most D3F_AUGMENT_CANDIDATES
+ * candidates, which are sorted in LDS; exact for every corr_len < 2^31, no global atomics.  It needs no global
+ * workspace today: d3f_augment_pairs_ws_bytes(B, k) is 0 and ws may be NULL (callers still ask, so a later version can
+ * take scratch).  1 <= k <= D3F_AUGMENT_MAX_NODE, noise >= 0 and finite, every corr_len >= 1, segments inside the
+ * stores; a source index outside its cloud is clamped for the distance matrix (validate tables once on the host).
+ * d3f_augment_item_host: the same for ONE job on HOST pointers (stores and outputs), from the same functions of
+ * csrc/augment.hpp; returns m, or -1.  d3f_augment_key_host: z(stream, index) of item key `key`
+ * (d3f_augment_key_host(0, 0, 0) = splitmix64(0) = 0xE220A8397B1DCDAF).
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_AUGMENT_MAX_JOBS 16
+#define D3F_AUGMENT_MAX_NODE 1024
+#define D3F_AUGMENT_CANDIDATES 1024
+typedef struct d3f_augment_job {
+  int64_t src_off, tgt_off; /* first row of the source / target cloud in `points` */
+  int64_t corr_off;         /* first row of the pair's table in `corr` */
+  int32_t src_len, tgt_len, corr_len, reserved;
+  double R[9], t[3];
+  uint64_t key;
+  float* out_src;
+  float* out_tgt;
+  int64_t* out_corr;
+  double* out_dist;
+} d3f_augment_job;
+size_t d3f_augment_pairs_ws_bytes(int B, int k);
+int d3f_augment_pairs(const float* points, int64_t sum_n, const int32_t* corr, int64_t sum_m, const d3f_augment_job* jobs,
+                      int B, int k, double noise, void* ws, size_t ws_bytes, void* stream);
+int d3f_augment_item_host(const float* points_host, const int32_t* corr_host, const d3f_augment_job* job, int k,
+                          double noise);
+uint64_t d3f_augment_key_host(uint64_t key, int stream, uint32_t index);
+
+/* ------------------------------------------------------------------------------------------------
  * Nearest neighbour within a radius over a list of cloud pairs -- the mining step of the 3DMatch training pickles
  * (datasets/preprocess.py; the reference ships the finished files and has no counterpart).
  * `points` [Ns,3] f32 are B clouds stacked, each in its OWN frame; cloud_start [B+1] int32 ON THE DEVICE is the prefix
