@@ -48,6 +48,8 @@ inline GridLayout grid_layout(void* ws, int Ns) {
 
 __device__ __forceinline__ int cell_coord(float v, double inv_cell) { return (int)floor((double)v * inv_cell); }
 
+// the key keeps the cloud (batch element) in its top 16 bits; 65535 itself stays free for "no key" marks
+constexpr int kMaxClouds = 65535;
 __device__ __forceinline__ uint64_t pack_key(int b, int cx, int cy, int cz) {
   return ((uint64_t)(uint32_t)b << 48) | ((uint64_t)(uint32_t)(cx + 32768) << 32) |
          ((uint64_t)(uint32_t)(cy + 32768) << 16) | (uint64_t)(uint32_t)(cz + 32768);

@@ -34,8 +34,8 @@
 // rows of ONE search under a given T, so it is a third kind of the same kernel: the winning lane adds n, sum x,
 // sum x x^T (upper triangle) of the moving point, the same of the matched fixed point y, and sum d2: 20 RAW moments, no
 // pivots (a product of two f32 values is exact in f64 and nothing is subtracted afterwards, so there is no cancellation
-// to protect).  Setup, prefix, reduction orders and flags are ICP's; a finishing launch adds the pair's block sums in
-// the fit kernel's order and writes them.  Three launches whatever the data.
+// to protect).  Setup, prefix, reduction orders and flags are ICP's (the same code: icp_setup_kernel, pair_sums); a
+// finishing launch adds the pair's block sums and writes them.  Three launches whatever the data.
 #include "pair_search.hpp"
 #include "plane.hpp"
 #include "rigid.hpp"
@@ -52,7 +52,6 @@ constexpr int kSlices = kRows / kRowsPerSlice;
 constexpr int kPoint = 0, kPlane = 1;   // what the fit minimises
 constexpr int kInfo = 2;                // no fit: the raw moments of the accepted rows (d3f_pair_information)
 constexpr int sums_of(int kind) { return kind == kPlane ? d3f::plane::kPlaneSums : kind == kInfo ? D3F_INFO_MOMENTS : 17; }
-constexpr int kMaxClouds = 65535;
 static_assert(kRows % kRowsPerSlice == 0, "a workgroup serves whole slices");
 
 struct IcpArgs {
@@ -107,6 +106,8 @@ __device__ __forceinline__ void write_pose(double* __restrict__ o, const double*
   o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
 }
 
+// kFit: the pair is iterated (kPoint, kPlane); without it (kInfo) the flags, the copy of T and `done` are all there is
+template <bool kFit>
 __global__ void icp_setup_kernel(const IcpArgs A) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (A.trace) {
@@ -127,16 +128,33 @@ __global__ void icp_setup_kernel(const IcpArgs A) {
     finite = finite && isfinite(v);
   }
   if (!finite) st |= D3F_ICP_ST_NONFINITE;
-  A.prev[2 * p] = 0.0;
-  A.prev[2 * p + 1] = 0.0;
-  A.done[p] = st != 0;
+  A.done[p] = st != 0;   // never searched
   A.status[p] = st;
-  A.iterations[p] = 0;
-  if (st) {   // never searched: the result is T_init
-    write_pose(A.T + 16 * (size_t)p, A.T_init + 12 * (size_t)p);
-    A.count[p] = 0;
-    A.rmse[p] = 0.0;
+  if constexpr (kFit) {
+    A.prev[2 * p] = 0.0;
+    A.prev[2 * p + 1] = 0.0;
+    A.iterations[p] = 0;
+    if (st) {   // the result is T_init (kInfo: zero moments, written by the finishing launch)
+      write_pose(A.T + 16 * (size_t)p, A.T_init + 12 * (size_t)p);
+      A.count[p] = 0;
+      A.rmse[p] = 0.0;
+    }
   }
+}
+
+// Pair p's block sums in the fixed order of the header: lane = block mod 64, blocks ascending, then the butterfly.  One
+// wave; a = the pair's moving cloud.
+template <int kSums>
+__device__ __forceinline__ void pair_sums(const IcpArgs& A, int p, int a, int lane, double (&v)[kSums]) {
+  const long long m = pair_rows(A, p, a), nblk = (m + kRows - 1) / kRows, first = first_block(A, p);
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+  for (long long j = lane; j < nblk; j += 64) {
+    const double* part = A.partial + (size_t)(first + j) * kSums;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) v[k] += part[k];
+  }
+  wave_sum(v);
 }
 
 template <int kKind>
@@ -262,16 +280,8 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
   const int p = blockIdx.x, lane = threadIdx.x;
   if (A.done[p]) return;
   const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
-  const long long m = pair_rows(A, p, a), nblk = (m + kRows - 1) / kRows, first = first_block(A, p);
   double v[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-  for (long long j = lane; j < nblk; j += 64) {
-    const double* part = A.partial + (size_t)(first + j) * kSums;
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) v[k] += part[k];
-  }
-  wave_sum(v);
+  pair_sums(A, p, a, lane, v);
   if (lane != 0) return;
   const int sa = A.cloud_start[a], len_a = A.cloud_start[a + 1] - sa, tgt0 = A.cloud_start[b];
   const double n = v[0], sd2 = v[kSums - 1];
@@ -334,43 +344,12 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
   A.iterations[p] = k_iter + 1;
 }
 
-// d3f_pair_information's setup: icp_setup_kernel's flags and copy of T, nothing else
-__global__ void info_setup_kernel(const IcpArgs A) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= A.P) return;
-  const int a = A.pairs[2 * p], b = A.pairs[2 * p + 1];
-  int st = 0;
-  if (!((unsigned)a < (unsigned)A.B && (unsigned)b < (unsigned)A.B) || A.row_start[p] < 0 ||
-      A.row_start[p + 1] < A.row_start[p] || A.row_start[p + 1] > A.rows)
-    st |= D3F_ICP_ST_PAIR;
-  bool finite = true;
-  for (int k = 0; k < 12; ++k) {
-    const double v = A.T_init[12 * (size_t)p + k];
-    A.T_cur[12 * (size_t)p + k] = v;
-    finite = finite && isfinite(v);
-  }
-  if (!finite) st |= D3F_ICP_ST_NONFINITE;
-  A.done[p] = st != 0;   // never searched: zero moments
-  A.status[p] = st;
-}
-
-// one wave per pair: the pair's block sums in icp_fit_kernel's order, written as they are
+// one wave per pair: the pair's block sums, written as they are (zeros for a pair the setup launch stopped)
 __global__ __launch_bounds__(64) void info_finish_kernel(const IcpArgs A) {
   constexpr int kSums = sums_of(kInfo);
   const int p = blockIdx.x, lane = threadIdx.x;
-  double v[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-  if (!A.done[p]) {   // (uniform over the wave)
-    const int a = A.pairs[2 * p];
-    const long long m = pair_rows(A, p, a), nblk = (m + kRows - 1) / kRows, first = first_block(A, p);
-    for (long long j = lane; j < nblk; j += 64) {
-      const double* part = A.partial + (size_t)(first + j) * kSums;
-#pragma unroll
-      for (int k = 0; k < kSums; ++k) v[k] += part[k];
-    }
-    wave_sum(v);
-  }
+  double v[kSums] = {};
+  if (!A.done[p]) pair_sums(A, p, A.pairs[2 * p], lane, v);   // (uniform over the wave)
   if (lane != 0) return;
 #pragma unroll
   for (int k = 0; k < kSums; ++k) A.moments[(size_t)p * kSums + k] = v[k];
@@ -399,64 +378,70 @@ IcpLayout icp_layout(void* ws, int P, long long rows, int kind) {
   return l;
 }
 
+// What the three kinds share on the host: the checks of the common arguments and the common part of IcpArgs.  D3F_OK
+// with P == 0 means there is nothing to launch.
+int icp_prepare(int kind, const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P,
+                int64_t rows, const double* T_init, int32_t* count, int32_t* status, void* ws, size_t ws_bytes,
+                IcpArgs& a, long long& blocks) {
+  if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
+      rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) ||
+      (P > 0 && (!pairs || !T_init || !count || !status || !ws)))
+    return D3F_EINVAL;
+  if (P == 0) return D3F_OK;
+  if (ws_bytes < icp_layout(nullptr, P, rows, kind).bytes) return D3F_EWORKSPACE;
+  const IcpLayout l = icp_layout(ws, P, rows, kind);
+  a.points = points;
+  a.cloud_start = cloud_start;
+  a.pairs = pairs;
+  a.row_start = row_start;
+  a.S = cell_search(grid_ws, Ns, grid_radius, max_distance, &a.placement);
+  a.T_init = T_init;
+  a.T_cur = l.T_cur;
+  a.prev = l.prev;
+  a.done = l.done;
+  a.partial = l.partial;
+  a.count = count;
+  a.status = status;
+  a.rows = rows;
+  a.B = B;
+  a.P = P;
+  a.Ns = Ns;
+  blocks = l.blocks;
+  return D3F_OK;
+}
+
 template <int kKind>
 int icp_run(const void* grid_ws, const float* points, const float* normals, int Ns, const int32_t* cloud_start, int B,
             float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P, int64_t rows,
             const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T, int32_t* count,
             double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes,
             void* stream_) {
-  if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
-      rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) || max_iters < 0 ||
-      max_iters > D3F_ICP_MAX_ITERS || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0) ||
-      (P > 0 && (!pairs || !T_init || !T || !count || !rmse || !iterations || !status || !ws)))
+  if (max_iters < 0 || max_iters > D3F_ICP_MAX_ITERS || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0) ||
+      (P > 0 && (!T || !rmse || !iterations)))
     return D3F_EINVAL;
-  if (P == 0) return D3F_OK;
-  if (ws_bytes < icp_layout(nullptr, P, rows, kKind).bytes) return D3F_EWORKSPACE;
-  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
-  IcpLayout l = icp_layout(ws, P, rows, kKind);
-  IcpArgs a;
-  a.moments = nullptr;
-  a.points = points;
+  IcpArgs a = {};
+  long long blocks = 0;
+  const int rc = icp_prepare(kKind, grid_ws, points, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+                             rows, T_init, count, status, ws, ws_bytes, a, blocks);
+  if (rc != D3F_OK || P == 0) return rc;
   a.normals = normals;
-  a.cloud_start = cloud_start;
-  a.pairs = pairs;
-  a.row_start = row_start;
-  a.placement = g.cnt + g.M + kPlacementWord;
-  a.S.start = g.start;
-  a.S.end = g.end;
-  a.S.pts = g.pts;
-  a.S.key = g.key;
-  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
-  a.S.r2 = max_distance * max_distance;                      // float32 product, like d3f_nearest_pairs
-  a.S.prune_r = max_distance;
-  a.S.mask = g.M - 1;
-  a.T_init = T_init;
-  a.T_cur = l.T_cur;
-  a.prev = l.prev;
-  a.done = l.done;
-  a.partial = l.partial;
   a.T = T;
-  a.count = count;
   a.rmse = rmse;
   a.iterations = iterations;
-  a.status = status;
   a.trace = trace;
   a.rel_fitness = rel_fitness;
   a.rel_rmse = rel_rmse;
-  a.rows = rows;
-  a.B = B;
-  a.P = P;
-  a.Ns = Ns;
   a.max_iters = max_iters;
   hipStream_t stream = (hipStream_t)stream_;
   const long long fill = trace ? 2ll * P * (max_iters + 1) : P;
   long long setup_blocks = ((fill > P ? fill : P) + 255) / 256;
   if (setup_blocks > 4096) setup_blocks = 4096;
   if (setup_blocks < (P + 255) / 256) setup_blocks = (P + 255) / 256;
-  icp_setup_kernel<<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
+  icp_setup_kernel<true><<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
   D3F_LAUNCH_CHECK();
   for (int k = 0; k <= max_iters; ++k) {
-    icp_search_kernel<kKind><<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
+    icp_search_kernel<kKind><<<(unsigned)blocks, kBlock, 0, stream>>>(a);
     icp_fit_kernel<kKind><<<(unsigned)P, 64, 0, stream>>>(a, k);
   }
   D3F_LAUNCH_CHECK();
@@ -466,44 +451,17 @@ int icp_run(const void* grid_ws, const float* points, const float* normals, int 
 int info_run(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B, float grid_radius,
              float max_distance, const int32_t* pairs, const int64_t* row_start, int P, int64_t rows, const double* T,
              double* moments, int32_t* count, int32_t* status, void* ws, size_t ws_bytes, void* stream_) {
-  if (!grid_ws || !points || !cloud_start || !row_start || Ns < 0 || B < 1 || B > kMaxClouds || P < 0 || P > 65535 ||
-      rows < 0 || rows > 0x7fffffffll || !(max_distance > 0.0f) || !(grid_radius >= max_distance) ||
-      (P > 0 && (!pairs || !T || !moments || !count || !status || !ws)))
-    return D3F_EINVAL;
-  if (P == 0) return D3F_OK;
-  if (ws_bytes < icp_layout(nullptr, P, rows, kInfo).bytes) return D3F_EWORKSPACE;
-  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
-  IcpLayout l = icp_layout(ws, P, rows, kInfo);
+  if (P > 0 && !moments) return D3F_EINVAL;
   IcpArgs a = {};
-  a.points = points;
-  a.cloud_start = cloud_start;
-  a.pairs = pairs;
-  a.row_start = row_start;
-  a.placement = g.cnt + g.M + kPlacementWord;
-  a.S.start = g.start;
-  a.S.end = g.end;
-  a.S.pts = g.pts;
-  a.S.key = g.key;
-  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);
-  a.S.r2 = max_distance * max_distance;
-  a.S.prune_r = max_distance;
-  a.S.mask = g.M - 1;
-  a.T_init = T;
-  a.T_cur = l.T_cur;
-  a.prev = l.prev;
-  a.done = l.done;
-  a.partial = l.partial;
+  long long blocks = 0;
+  const int rc = icp_prepare(kInfo, grid_ws, points, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+                             rows, T, count, status, ws, ws_bytes, a, blocks);
+  if (rc != D3F_OK || P == 0) return rc;
   a.moments = moments;
-  a.count = count;
-  a.status = status;
-  a.rows = rows;
-  a.B = B;
-  a.P = P;
-  a.Ns = Ns;
   hipStream_t stream = (hipStream_t)stream_;
-  info_setup_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(a);
+  icp_setup_kernel<false><<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(a);
   D3F_LAUNCH_CHECK();
-  icp_search_kernel<kInfo><<<(unsigned)l.blocks, kBlock, 0, stream>>>(a);
+  icp_search_kernel<kInfo><<<(unsigned)blocks, kBlock, 0, stream>>>(a);
   info_finish_kernel<<<(unsigned)P, 64, 0, stream>>>(a);
   D3F_LAUNCH_CHECK();
   return D3F_OK;

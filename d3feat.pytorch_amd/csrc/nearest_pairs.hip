@@ -30,7 +30,6 @@ using namespace d3f::cells;
 using d3f::shfl_xor_u64;
 
 constexpr int kBlock = 512;   // 8 waves share one add to out_count
-constexpr int kMaxClouds = 65535;   // the cell key keeps the cloud index in 16 bits
 
 constexpr uint64_t kNoKey = ~0ull;   // no cell key has the cloud field 65535 (B <= kMaxClouds)
 
@@ -229,29 +228,20 @@ int d3f_nearest_pairs_lanes(const void* grid_ws, const float* points, int Ns, co
     return D3F_EINVAL;
   if (lanes != 0 && lanes != 4 && lanes != 8 && lanes != 16 && lanes != 32) return D3F_EINVAL;
   if (P == 0 || rows == 0) return D3F_OK;
-  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
   PairArgs a;
   a.points = points;
   a.cloud_start = cloud_start;
   a.pairs = pairs;
   a.transforms = transforms;
   a.row_start = row_start;
-  a.S.start = g.start;
-  a.S.end = g.end;
-  a.placement = g.cnt + g.M + kPlacementWord;
-  a.S.pts = g.pts;
-  a.S.key = g.key;
+  a.S = cell_search(grid_ws, Ns, grid_radius, radius, &a.placement);
   a.out_nn = out_nn;
   a.out_count = out_count;
   a.status = status;
-  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
   a.rows = rows;
   a.B = B;
   a.P = P;
   a.Ns = Ns;
-  a.S.r2 = radius * radius;   // float32 product, like the radius search
-  a.S.prune_r = radius;
-  a.S.mask = g.M - 1;
   hipStream_t stream = (hipStream_t)stream_;
   switch (lanes) {
     case 4: launch_pairs<4>(a, stream); break;

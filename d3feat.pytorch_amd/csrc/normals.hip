@@ -28,7 +28,6 @@ using namespace d3f::cells;
 constexpr int kBlock = 256;
 constexpr int kG = 8;
 constexpr int kMoments = 10;
-constexpr int kMaxClouds = 65535;
 
 struct NormalArgs {
   const float* points;
@@ -152,19 +151,10 @@ int d3f_estimate_normals(const void* grid_ws, const float* points, int Ns, const
       !isfinite(radius) || !(grid_radius >= radius) || min_neighbors < 1 || (Ns > 0 && (!normals || !count)))
     return D3F_EINVAL;
   if (Ns == 0) return D3F_OK;
-  GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
   NormalArgs a;
   a.points = points;
   a.cloud_start = cloud_start;
-  a.placement = g.cnt + g.M + kPlacementWord;
-  a.S.start = g.start;
-  a.S.end = g.end;
-  a.S.pts = g.pts;
-  a.S.key = g.key;
-  a.S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
-  a.S.r2 = radius * radius;                                  // float32 product, like the other searches
-  a.S.prune_r = radius;
-  a.S.mask = g.M - 1;
+  a.S = cell_search(grid_ws, Ns, grid_radius, radius, &a.placement);
   a.normals = normals;
   a.count = count;
   a.moments = moments;

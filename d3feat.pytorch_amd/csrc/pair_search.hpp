@@ -42,6 +42,23 @@ struct CellSearch {
   uint32_t mask;
 };
 
+// The CellSearch of one launch at `radius` over the list in grid_ws (d3f_cloud_grid_build / d3f_radius_grid_build over
+// Ns rows at grid_radius >= radius); *placement is the list's placement word (cell_list.hpp).
+inline CellSearch cell_search(const void* grid_ws, int Ns, float grid_radius, float radius, const int32_t** placement) {
+  const GridLayout g = grid_layout(const_cast<void*>(grid_ws), Ns);
+  CellSearch S;
+  S.start = g.start;
+  S.end = g.end;
+  S.pts = g.pts;
+  S.key = g.key;
+  S.inv_cell = 1.0 / ((double)grid_radius * kCellSlack);   // cells of the list the grid was built with
+  S.r2 = radius * radius;                                  // float32 product, like the radius search
+  S.prune_r = radius;
+  S.mask = g.M - 1;
+  *placement = g.cnt + g.M + kPlacementWord;
+  return S;
+}
+
 // Bucket headers of the cells lane `sub` of a group of G walks for the query point (qx, qy, qz) in cell (cx, cy, cz) of
 // cloud b (first stored row tgt0, tgt_n rows): per cell the key nk, the first entry st and the length len (0 for a
 // cell it skips).  The 27 cells are dealt round robin to the lanes; the loads are independent.  A cell whose box is

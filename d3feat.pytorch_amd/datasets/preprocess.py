@@ -135,6 +135,31 @@ def _chunks(units, rows_of, max_rows):
     return out
 
 
+def _directed_jobs(pairs, T, lens, symmetric, T_back=None):
+    """The searches of a list of pairs: job (moving, fixed, T) = pair p with ``T[p]`` and, when ``symmetric``, the
+    reverse direction right behind it with ``T_back[p]`` (default ``inv(T[p])``).  Returns ``(job_pairs int64 [J,2],
+    job_T f64 [J,4,4], units, rows_of)``: ``units[p]`` lists the job numbers of pair p, forward first, and
+    ``rows_of[j]`` is the length of job j's moving cloud."""
+    job_pairs, job_T, units = [], [], []
+    for p in range(len(pairs)):
+        unit = [len(job_pairs)]
+        job_pairs.append(pairs[p])
+        job_T.append(T[p])
+        if symmetric:
+            unit.append(len(job_pairs))
+            job_pairs.append(pairs[p, ::-1])
+            job_T.append(np.linalg.inv(T[p]) if T_back is None else T_back[p])
+        units.append(unit)
+    job_pairs = np.asarray(job_pairs, dtype=np.int64).reshape(-1, 2)
+    return job_pairs, np.asarray(job_T, dtype=np.float64).reshape(-1, 4, 4), units, lens[job_pairs[:, 0]]
+
+
+def _by_fixed_cloud(units, job_pairs):
+    """The units ordered by the fixed cloud of their first job: searches of one fixed cloud next to each other, so that
+    the workgroups in flight together read the same part of the cell list."""
+    return sorted(units, key=lambda u: (int(job_pairs[u[0], 1]), u[0]))
+
+
 def _mine(clouds, pairs, transforms, radius, min_overlap, symmetric, device, max_rows):
     """{(i, j): int64 [M,2]} and {(i, j): overlap} for the explicit ``pairs`` with ``transforms`` source -> target."""
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -146,21 +171,8 @@ def _mine(clouds, pairs, transforms, radius, min_overlap, symmetric, device, max
     if len(set(map(tuple, pairs.tolist()))) != pairs.shape[0]:
         raise ValueError("a pair is listed twice")
     lens = np.array([c.shape[0] for c in clouds], dtype=np.int64)
-    # jobs: the forward direction of every pair and, when symmetric, the reverse one right behind it
-    job_pairs, job_T, units = [], [], []
-    for p in range(pairs.shape[0]):
-        unit = [len(job_pairs)]
-        job_pairs.append(pairs[p])
-        job_T.append(T[p])
-        if symmetric:
-            unit.append(len(job_pairs))
-            job_pairs.append(pairs[p, ::-1])
-            job_T.append(np.linalg.inv(T[p]))
-        units.append(unit)
-    job_pairs = np.asarray(job_pairs, dtype=np.int64).reshape(-1, 2)
-    rows_of = lens[job_pairs[:, 0]] if len(job_pairs) else np.zeros(0, np.int64)
-    # pairs of one target next to each other: the workgroups in flight together then read the same part of the cell list
-    units.sort(key=lambda u: (int(job_pairs[u[0], 1]), u[0]))
+    job_pairs, job_T, units, rows_of = _directed_jobs(pairs, T, lens, symmetric)
+    units = _by_fixed_cloud(units, job_pairs)
     corr, overlap = {}, {}
     on_cpu = str(device).startswith('cpu')
     if not on_cpu and pairs.shape[0]:
@@ -171,7 +183,7 @@ def _mine(clouds, pairs, transforms, radius, min_overlap, symmetric, device, max
                              .to(dev), lens.astype(np.int32), radius)
     for chunk in _chunks(units, rows_of, int(max_rows)):
         jobs = [j for u in chunk for j in u]
-        jp, jt = job_pairs[jobs], np.stack([job_T[j] for j in jobs])
+        jp, jt = job_pairs[jobs], job_T[jobs]
         if on_cpu:
             nn, count, row_start = nearest_pairs_numpy(clouds, jp, jt, radius)
         else:

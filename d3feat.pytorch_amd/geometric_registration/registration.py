@@ -294,12 +294,29 @@ def _icp_keywords(icp):
     return dict(icp)
 
 
-def _pair_list(keys_or_pairs):
+def _moving_fixed_pairs(keys_or_pairs, num_clouds):
+    """``gt.log`` keys ``'i_j'`` or (i, j) tuples -> int64 [P,2] rows (j, i) = (moving, fixed), what the ``ops`` entries
+    take."""
     out = []
     for k in keys_or_pairs:
         i, j = (k.split('_') if isinstance(k, str) else k)
         out.append((int(i), int(j)))
-    return np.asarray(out, dtype=np.int64).reshape(-1, 2)
+    ij = np.asarray(out, dtype=np.int64).reshape(-1, 2)
+    if ij.size and (ij.min() < 0 or ij.max() >= num_clouds):
+        raise ValueError("pairs name fragments outside 0..%d" % (num_clouds - 1))
+    return ij[:, ::-1].copy()
+
+
+def _host_arrays(clouds):
+    """The clouds (arrays or tensors) as contiguous f32 NumPy arrays."""
+    return [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
+            for c in clouds]
+
+
+def _cloud_grid(clouds, radius, dev):
+    """One ``ops.CloudGrid`` at ``radius`` over the clouds stacked on ``dev``; the lengths stay known on the host."""
+    pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
+    return ops.CloudGrid(pts, np.asarray([int(c.shape[0]) for c in clouds], dtype=np.int64), float(radius))
 
 
 def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', estimation='point_to_point',
@@ -323,14 +340,10 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
     plane = estimation == 'point_to_plane'
     if normal_radius is None:
         normal_radius = 2.0 * float(max_distance)
-    ij = _pair_list(keys_or_pairs)
-    ji = ij[:, ::-1].copy()
-    if ij.size and (ij.min() < 0 or ij.max() >= len(clouds)):
-        raise ValueError("pairs name fragments outside 0..%d" % (len(clouds) - 1))
+    ji = _moving_fixed_pairs(keys_or_pairs, len(clouds))
     lens = np.asarray([int(c.shape[0]) for c in clouds], dtype=np.int64)
     if str(device).startswith('cpu'):
-        arrs = [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
-                for c in clouds]
+        arrs = _host_arrays(clouds)
         Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
         if plane:
             icp = dict(icp, normals=estimate_normals_numpy(arrs, normal_radius)[0])
@@ -339,8 +352,7 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
         return res + (information_from_moments(information_numpy(arrs, ji, Tr, max_distance)[0]),) \
             if return_information else res
     dev = torch.device(device)
-    pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
-    grid = ops.CloudGrid(pts, lens, max(float(normal_radius), float(max_distance)) if plane else float(max_distance))
+    grid = _cloud_grid(clouds, max(float(normal_radius), float(max_distance)) if plane else max_distance, dev)
     if plane:
         icp = dict(icp, normals=ops.estimate_normals(grid, None, normal_radius)[0])
     Tr, count, rmse, iters, _ = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
@@ -429,21 +441,14 @@ def information_matrices(clouds, keys_or_pairs, T, max_distance, device='cuda', 
     point counts when its nearest point of i under ``T[p]`` is closer than ``max_distance``.  ``frame``, ``order``:
     ``information_from_moments`` (the defaults are the benchmark's ``gt.info`` form).  Returns ``(info [P,6,6] f64,
     count [P], rmse [P])``: device tensors, or NumPy arrays from ``device='cpu'`` (``information_numpy``)."""
-    ij = _pair_list(keys_or_pairs)
-    ji = ij[:, ::-1].copy()
-    if ij.size and (ij.min() < 0 or ij.max() >= len(clouds)):
-        raise ValueError("pairs name fragments outside 0..%d" % (len(clouds) - 1))
+    ji = _moving_fixed_pairs(keys_or_pairs, len(clouds))
     if str(device).startswith('cpu'):
-        arrs = [np.ascontiguousarray(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float32)
-                for c in clouds]
         Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
-        moments, count = information_numpy(arrs, ji, Tn, max_distance)
+        moments, count = information_numpy(_host_arrays(clouds), ji, Tn, max_distance)
     else:
         dev = torch.device(device)
-        pts = torch.cat([torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3).to(dev) for c in clouds])
-        grid = ops.CloudGrid(pts, np.asarray([int(c.shape[0]) for c in clouds], dtype=np.int64), float(max_distance))
-        moments, count, _ = ops.pair_information(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
-                                                 max_distance)
+        moments, count, _ = ops.pair_information(_cloud_grid(clouds, max_distance, dev), None, ji,
+                                                 torch.as_tensor(T, dtype=torch.float64).to(dev), max_distance)
     return information_from_moments(moments, frame, order), count, _rmse_from_moments(moments)
 
 
@@ -627,7 +632,7 @@ def build_benchmark(fragments, poses, out_dir, voxel, radius=None, min_overlap=0
     available to compare against (its blocks hold at most 5000 points each, whatever sampling produced that).
 
     Returns ``(gt {'i_j': 4x4}, info {'i_j': 6x6}, overlap {'i_j': share})``; ``overlap`` lists every candidate."""
-    from ..datasets.preprocess import candidate_pairs, subsample_fragments
+    from ..datasets.preprocess import _by_fixed_cloud, _directed_jobs, candidate_pairs, subsample_fragments
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     if poses.shape[0] != len(fragments):
         raise ValueError("%d poses for %d fragments" % (poses.shape[0], len(fragments)))
@@ -641,33 +646,19 @@ def build_benchmark(fragments, poses, out_dir, voxel, radius=None, min_overlap=0
     lens = np.array([c.shape[0] for c in clouds], dtype=np.int64)
     ij, T_ij = candidate_pairs(clouds, poses, max(radius, info_distance))     # T_ij maps i into j
     # jobs (moving, fixed, T): j into i for every candidate and, when symmetric, i into j right behind it
-    job_pairs, job_T, units = [], [], []
-    for p in range(ij.shape[0]):
-        unit = [len(job_pairs)]
-        job_pairs.append(ij[p, ::-1])
-        job_T.append(np.linalg.inv(poses[ij[p, 0]]) @ poses[ij[p, 1]])
-        if symmetric:
-            unit.append(len(job_pairs))
-            job_pairs.append(ij[p])
-            job_T.append(T_ij[p])
-        units.append(unit)
-    job_pairs = np.asarray(job_pairs, dtype=np.int64).reshape(-1, 2)
-    job_T = np.asarray(job_T, dtype=np.float64).reshape(-1, 4, 4)
-    rows_of = lens[job_pairs[:, 0]] if len(job_pairs) else np.zeros(0, np.int64)
+    T_ji = [np.linalg.inv(poses[i]) @ poses[j] for i, j in ij]
+    job_pairs, job_T, units, rows_of = _directed_jobs(ij[:, ::-1], T_ji, lens, symmetric, T_back=T_ij)
     on_cpu = str(device).startswith('cpu')
     grid = None
     if not on_cpu and len(job_pairs):
-        dev = torch.device(device)
-        grid = ops.CloudGrid(torch.as_tensor(np.concatenate(clouds, 0)).to(dev), lens, max(radius, info_distance))
+        grid = _cloud_grid(clouds, max(radius, info_distance), torch.device(device))
 
     def search(jobs, distance):
         """(moments [len(jobs),20], count) of the listed jobs, in chunks."""
         moments = np.zeros((len(jobs), INFO_MOMENTS))
         count = np.zeros(len(jobs), dtype=np.int64)
         at = {j: k for k, j in enumerate(jobs)}
-        # jobs of one fixed cloud next to each other: workgroups in flight together read the same part of the cell list
-        order = sorted(([j] for j in jobs), key=lambda u: (int(job_pairs[u[0], 1]), u[0]))
-        for chunk in _job_chunks(order, rows_of, int(max_rows)):
+        for chunk in _job_chunks(_by_fixed_cloud([[j] for j in jobs], job_pairs), rows_of, int(max_rows)):
             js = [u[0] for u in chunk]
             if on_cpu:
                 m, c = information_numpy(clouds, job_pairs[js], job_T[js], distance)

@@ -2801,6 +2801,60 @@ class CloudGrid:
                                                  _p(self.status.word), _stream()), "d3f_cloud_grid_build")
 
 
+def _resolve_grid(grid_or_points, lens, radius, what):
+    """The cell list of the geometry entries: ``grid_or_points`` itself when it is a ``RadiusGrid`` / ``CloudGrid`` (its
+    radius must cover ``radius``; a ``RadiusGrid`` gets its ``cloud_start`` prefix on first use), else a ``CloudGrid``
+    built over the stacked points with their ``lens``.  ``what`` names the radius in the error."""
+    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
+        grid = grid_or_points
+        if float(radius) > grid.radius:
+            raise RuntimeError("%s %g exceeds the cell list's %g" % (what, float(radius), grid.radius))
+        if getattr(grid, "cloud_start", None) is None:
+            grid.cloud_start = _cloud_start(grid.s_len)
+        return grid
+    if lens is None:
+        raise ValueError("lens is required with stacked points")
+    return CloudGrid(grid_or_points, lens, radius)
+
+
+def _pair_list(grid, pairs, T, name, rows=None, max_pairs=None):
+    """The pair list of ``nearest_pairs`` / ``icp_rigid`` / ``pair_information`` -> ``(pairs int32 [P,2], P, T f64
+    [P,12], row_start int64 [P+1], rows)``.  ``pairs``: host values (checked against the grid's clouds) or a device
+    tensor (not read: the kernels answer a pair that names no cloud, and ``row_start`` takes the length of the clamped
+    cloud).  ``T`` (``name`` in the error): [P,3,4], [P,4,4] or [P,12].  ``row_start`` is the prefix of the moving clouds'
+    lengths; it and ``rows`` come from the host when pairs and lengths are known there, else ``rows`` is the caller's
+    bound or the one read-back of this form.  ``max_pairs``: None for any number of pairs, none included, else
+    1..max_pairs."""
+    dev = grid.supports.device
+    B = int(grid.s_len.numel())
+    host = None
+    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
+    else:
+        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if host.size and (host.min() < 0 or host.max() >= B):
+            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
+        pr = torch.as_tensor(host.astype(np.int32), device=dev)
+    P = int(pr.shape[0])
+    if max_pairs is not None and not 1 <= P <= max_pairs:
+        raise ValueError("1..%d pairs per call, got %d" % (max_pairs, P))
+    tf = torch.as_tensor(T, dtype=torch.float64).to(dev)
+    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4), (P, 12)):
+        raise ValueError("%s must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (name, P, tuple(tf.shape)))
+    tf = tf.reshape(P, 16 if tuple(tf.shape[1:]) == (4, 4) else 12)[:, :12].contiguous()
+    lens_host = getattr(grid, "lens_host", None)
+    if host is not None and lens_host is not None:
+        rs = np.zeros(P + 1, dtype=np.int64)
+        rs[1:] = np.cumsum(lens_host[host[:, 0]])
+        return pr, P, tf, torch.as_tensor(rs, device=dev), int(rs[-1])
+    row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    if P:
+        row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long().clamp(0, B - 1)], 0)
+    if rows is None:
+        rows = row_start[-1].item() if P else 0   # sizes the output: the one read-back of this form
+    return pr, P, tf, row_start, int(rows)
+
+
 def nearest_pairs_bytes(rows, found=None):
     """Algorithmic bytes of ``rows`` queries: the source point (12), the (start, end) headers of 27 buckets (216), the
     stored point and cell key of every candidate the accepted cells hold (24 each; ``found`` of them, by default one
@@ -2818,51 +2872,21 @@ def nearest_pairs(grid_or_points, lens, pairs, transforms, radius, lanes=0):
     source points into the target's frame.  Returns ``(nn int32 [rows], count int32 [P], row_start int64 [P+1])``:
     rows ``row_start[p] .. row_start[p+1]`` are the points of pair p's source in order, ``nn`` the index inside the target
     cloud (-1: none within the radius), ``count[p]`` the rows of pair p with a neighbour.  Arithmetic and tie rule:
-    include/d3feat_hip.h.  ``lanes``: lanes per query (measurements; the result does not depend on it)."""
-    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
-        grid = grid_or_points
-        if float(radius) > grid.radius:
-            raise RuntimeError("search radius %g exceeds the cell list's %g" % (float(radius), grid.radius))
-    else:
-        if lens is None:
-            raise ValueError("lens is required with stacked points")
-        grid = CloudGrid(grid_or_points, lens, radius)
+    include/d3feat_hip.h.  Host ``pairs`` are checked against the clouds; a device tensor is not read, and a pair of it
+    that names a cloud that is not there gets -1 rows and count 0 (its rows: those of the clamped source cloud).
+    ``lanes``: lanes per query (measurements; the result does not depend on it)."""
+    grid = _resolve_grid(grid_or_points, lens, radius, "search radius")
     dev = grid.supports.device
-    B = int(grid.s_len.numel())
-    cloud_start = getattr(grid, "cloud_start", None)
-    if cloud_start is None:
-        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
-    host = None
-    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
-        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
-    else:
-        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-        if host.size and (host.min() < 0 or host.max() >= B):
-            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
-        pr = torch.as_tensor(host.astype(np.int32), device=dev)
-    P = int(pr.shape[0])
-    tf = torch.as_tensor(transforms, dtype=torch.float64).to(dev)
-    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4), (P, 12)):
-        raise ValueError("transforms must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (P, tuple(tf.shape)))
-    tf = tf.reshape(P, 16 if tuple(tf.shape[1:]) == (4, 4) else 12)[:, :12].contiguous()
-    lens_host = getattr(grid, "lens_host", None)
-    if host is not None and lens_host is not None:
-        rs = np.zeros(P + 1, dtype=np.int64)
-        rs[1:] = np.cumsum(lens_host[host[:, 0]])
-        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
-    else:
-        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
-        if P:
-            row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long()], 0)
-        rows = int(row_start[-1].item()) if P else 0   # sizes the output: the one read-back of this form
+    pr, P, tf, row_start, rows = _pair_list(grid, pairs, transforms, "transforms")
     nn = torch.empty(rows, dtype=torch.int32, device=dev)
     count = torch.zeros(P, dtype=torch.int32, device=dev)
     if rows == 0:
         return nn, count, row_start
     with _region("nearest_pairs[P=%d,rows=%d]" % (P, rows), nearest_pairs_bytes(rows)):
         _native.check(_native.lib().d3f_nearest_pairs_lanes(
-            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(radius), _p(pr), _p(tf),
-            _p(row_start), P, rows, _p(nn), _p(count), _p(grid.status.word), int(lanes), _stream()),
+            _p(grid.ws), _p(grid.supports), grid.Ns, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+            float(radius), _p(pr), _p(tf), _p(row_start), P, rows, _p(nn), _p(count), _p(grid.status.word), int(lanes),
+            _stream()),
             "d3f_nearest_pairs")
     return nn, count, row_start
 
@@ -2920,18 +2944,8 @@ def estimate_normals(grid_or_points, lens, radius, min_neighbors=3, viewpoint=No
     bit-identical from run to run, for a cloud alone or stacked among others, and for any cell size."""
     if not (0.0 < float(radius) < float("inf")) or int(min_neighbors) < 1:
         raise ValueError("radius must be positive and finite, min_neighbors at least 1")
-    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
-        grid = grid_or_points
-        if float(radius) > grid.radius:
-            raise RuntimeError("radius %g exceeds the cell list's %g" % (float(radius), grid.radius))
-    else:
-        if lens is None:
-            raise ValueError("lens is required with stacked points")
-        grid = CloudGrid(grid_or_points, lens, radius)
+    grid = _resolve_grid(grid_or_points, lens, radius, "radius")
     dev = grid.supports.device
-    cloud_start = getattr(grid, "cloud_start", None)
-    if cloud_start is None:
-        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
     view = None
     if viewpoint is not None:
         view = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float32).reshape(-1))
@@ -2944,55 +2958,10 @@ def estimate_normals(grid_or_points, lens, radius, min_neighbors=3, viewpoint=No
     if N:
         with _region("estimate_normals[N=%d]" % N, estimate_normals_bytes(N)):
             _native.check(_native.lib().d3f_estimate_normals(
-                _p(grid.ws), _p(grid.supports), N, _p(cloud_start), int(grid.s_len.numel()), grid.radius, float(radius),
-                int(min_neighbors), view.ctypes.data if view is not None else None, _p(normals), _p(count),
-                _p(moments), _p(grid.status.word), _stream()), "d3f_estimate_normals")
+                _p(grid.ws), _p(grid.supports), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(radius), int(min_neighbors), view.ctypes.data if view is not None else None, _p(normals),
+                _p(count), _p(moments), _p(grid.status.word), _stream()), "d3f_estimate_normals")
     return (normals, count, moments) if return_moments else (normals, count)
-
-
-def _icp_arguments(grid_or_points, lens, pairs, T, max_distance, rows, name):
-    """The argument forms ``icp_rigid`` and ``pair_information`` share -> (grid, device, B, cloud_start, pairs int32
-    [P,2], P, T f64 [P,3,4], row_start int64 [P+1], rows)."""
-    if isinstance(grid_or_points, (RadiusGrid, CloudGrid)):
-        grid = grid_or_points
-        if float(max_distance) > grid.radius:
-            raise RuntimeError("max_distance %g exceeds the cell list's %g" % (float(max_distance), grid.radius))
-    else:
-        if lens is None:
-            raise ValueError("lens is required with stacked points")
-        grid = CloudGrid(grid_or_points, lens, max_distance)
-    if not (0.0 < float(max_distance) < float("inf")):
-        raise ValueError("max_distance must be positive and finite")
-    dev = grid.supports.device
-    B = int(grid.s_len.numel())
-    cloud_start = getattr(grid, "cloud_start", None)
-    if cloud_start is None:
-        cloud_start = grid.cloud_start = _cloud_start(grid.s_len)
-    host = None
-    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
-        pr = pairs.to(torch.int32).contiguous().view(-1, 2)
-    else:
-        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-        if host.size and (host.min() < 0 or host.max() >= B):
-            raise ValueError("pairs name clouds outside 0..%d" % (B - 1))
-        pr = torch.as_tensor(host.astype(np.int32), device=dev)
-    P = int(pr.shape[0])
-    if not 1 <= P <= MAX_CLOUDS:
-        raise ValueError("1..%d pairs per call, got %d" % (MAX_CLOUDS, P))
-    tf = torch.as_tensor(T, dtype=torch.float64).to(dev)
-    if tuple(tf.shape) not in ((P, 3, 4), (P, 4, 4)):
-        raise ValueError("%s must be [P,3,4] or [P,4,4] for the %d pairs, got %s" % (name, P, tuple(tf.shape)))
-    tf = tf[:, :3, :].contiguous()
-    lens_host = getattr(grid, "lens_host", None)
-    if host is not None and lens_host is not None:
-        rs = np.zeros(P + 1, dtype=np.int64)
-        rs[1:] = np.cumsum(lens_host[host[:, 0]])
-        row_start, rows = torch.as_tensor(rs, device=dev), int(rs[-1])
-    else:
-        row_start = torch.zeros(P + 1, dtype=torch.int64, device=dev)
-        row_start[1:] = torch.cumsum(grid.s_len.long()[pr[:, 0].long().clamp(0, B - 1)], 0)
-        rows = int(rows) if rows is not None else int(row_start[-1].item())   # (the one read-back of this form)
-    return grid, dev, B, cloud_start, pr, P, tf, row_start, rows
 
 
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
@@ -3022,8 +2991,11 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
         raise ValueError("max_iters must be in 0..%d" % ICP_MAX_ITERS)
     if not float(rel_fitness) >= 0.0 or not float(rel_rmse) >= 0.0:
         raise ValueError("rel_fitness and rel_rmse must be non-negative")
-    grid, dev, B, cloud_start, pr, P, tf, row_start, rows = _icp_arguments(grid_or_points, lens, pairs, T_init,
-                                                                           max_distance, rows, "T_init")
+    grid = _resolve_grid(grid_or_points, lens, max_distance, "max_distance")
+    if not (0.0 < float(max_distance) < float("inf")):
+        raise ValueError("max_distance must be positive and finite")
+    dev = grid.supports.device
+    pr, P, tf, row_start, rows = _pair_list(grid, pairs, T_init, "T_init", rows, MAX_CLOUDS)
     K = int(max_iters)
     T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
     count, iterations, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
@@ -3043,7 +3015,7 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     with _region("%s[P=%d,rows=%d,iters<=%d]" % (name[4:], P, rows, K),
                  (K + 1) * (icp_plane_bytes if plane else icp_rigid_bytes)(rows)):
         _native.check(getattr(L, name)(
-            *head, grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
+            *head, grid.Ns, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius, float(max_distance), _p(pr),
             _p(row_start), P, rows, _p(tf), K, float(rel_fitness), float(rel_rmse), _p(T), _p(count), _p(rmse),
             _p(iterations), _p(status), _p(trace), _p(ws), nbytes, _stream()), name)
     res = (T, count, rmse, iterations, status)
@@ -3065,8 +3037,11 @@ def pair_information(grid_or_points, lens, pairs, T, max_distance, rows=None):
     int32, status [P] int32)``; a pair flagged ``ICP_ST_PAIR`` / ``ICP_ST_NONFINITE`` has zero moments.  Three
     launches, bit-identical from run to run and for a pair alone or inside any batch; no read-back when the lengths and
     pairs are known on the host, or when ``rows`` comes with device ``pairs``."""
-    grid, dev, B, cloud_start, pr, P, tf, row_start, rows = _icp_arguments(grid_or_points, lens, pairs, T,
-                                                                           max_distance, rows, "T")
+    grid = _resolve_grid(grid_or_points, lens, max_distance, "max_distance")
+    if not (0.0 < float(max_distance) < float("inf")):
+        raise ValueError("max_distance must be positive and finite")
+    dev = grid.supports.device
+    pr, P, tf, row_start, rows = _pair_list(grid, pairs, T, "T", rows, MAX_CLOUDS)
     moments = torch.empty((P, INFO_MOMENTS), dtype=torch.float64, device=dev)
     count, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
     L = _native.lib()
@@ -3074,9 +3049,9 @@ def pair_information(grid_or_points, lens, pairs, T, max_distance, rows=None):
     ws = _ws(nbytes, dev)
     with _region("pair_information[P=%d,rows=%d]" % (P, rows), pair_information_bytes(rows)):
         _native.check(L.d3f_pair_information(
-            _p(grid.ws), _p(grid.supports), grid.Ns, _p(cloud_start), B, grid.radius, float(max_distance), _p(pr),
-            _p(row_start), P, rows, _p(tf), _p(moments), _p(count), _p(status), _p(ws), nbytes, _stream()),
-            "d3f_pair_information")
+            _p(grid.ws), _p(grid.supports), grid.Ns, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+            float(max_distance), _p(pr), _p(row_start), P, rows, _p(tf), _p(moments), _p(count), _p(status), _p(ws),
+            nbytes, _stream()), "d3f_pair_information")
     return moments, count, status
 
 

@@ -237,8 +237,9 @@ def main():
     one = (ms["K=8"] - ms["K=0"]) / 8
     say("one iteration against the search floor (tolerances 0: all %d pairs searched every time):" % P)
     say("  d3f_nearest_pairs, one launch      %8.3f ms  (%.3f..%.3f)" % ((ms["floor"],) + spread["floor"]))
-    say("  d3f_icp_rigid, max_iters = 0       %8.3f ms  (setup + one search + one stopping launch)" % ms["K=0"])
-    say("  d3f_icp_rigid, max_iters = 8       %8.3f ms" % ms["K=8"])
+    say("  d3f_icp_rigid, max_iters = 0       %8.3f ms  (%.3f..%.3f; setup + one search + one stopping launch)" % (
+        (ms["K=0"],) + spread["K=0"]))
+    say("  d3f_icp_rigid, max_iters = 8       %8.3f ms  (%.3f..%.3f)" % ((ms["K=8"],) + spread["K=8"]))
     say("  one fused iteration (search + fit) %8.3f ms  = %.3f x the search floor (target 1.15)" % (
         one, one / ms["floor"]))
     nb_floor, nb_icp = ops.nearest_pairs_bytes(rows, found), ops.icp_rigid_bytes(rows, found)
@@ -291,6 +292,7 @@ def main():
         one_point, msp["point K=0"], msp["point K=8"]))
     say("  one point-to-plane iteration              %8.3f ms  (K = 0: %.3f, K = 8: %.3f) = %.3f x point-to-point" % (
         one_plane, msp["plane K=0"], msp["plane K=8"], one_plane / one_point))
+    say("  ranges: " + "; ".join("%s %.3f..%.3f" % ((k,) + spreadp[k]) for k in msp if k != "normals"))
     say("  defaults (30 / 1e-6 / 1e-6): point-to-plane fits per pair %d..%d (mean %.1f) against %d..%d (mean %.1f); "
         "status != 0 on %d pairs" % (it_p.min(), it_p.max(), it_p.mean(), it_f.min(), it_f.max(), it_f.mean(),
                                      int((plane_run[4] != 0).sum())))

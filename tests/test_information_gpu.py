@@ -116,6 +116,33 @@ def test_edges_of_the_launch_geometry_in_one_call(scene):
 
 
 @pytest.mark.gpu
+def test_a_pair_of_more_than_64_blocks(scene):
+    """One pair of 64 * 512 + 1 moving rows: 65 block sums, so lane 0 of the wave that adds them (pair_sums in
+    csrc/icp.hip, shared by the fit kernels and the information kernel) takes a second trip -- no other test has a
+    fragment beyond 16 blocks.  The moving cloud repeats points of the fixed one under the identity: every row matches
+    its own point at d2 == 0.  Moments within 1e-11 of the pair's largest against information_numpy (2^15 exact
+    products per sum, added in f64 in two different orders); both fit kinds reduce the same count and sum of d2."""
+    base = scene[0][0]
+    moving = np.tile(base[:4097], (8, 1))[:32769]
+    assert len(base) >= 4097 and len(moving) == 64 * ops.ICP_BLOCK_ROWS + 1
+    stack, pairs, T = [moving, base], [(0, 1)], np.eye(4)[None]
+    grid = device_grid(stack, 2 * R)
+    moments, count, status = ops.pair_information(grid, None, pairs, T, R)
+    m = moments.cpu().numpy()[0]
+    assert count.tolist() == [32769] and status.tolist() == [0]
+    assert m[19] == 0 and np.array_equal(m[1:10], m[10:19])
+    want, cn = reg.information_numpy(stack, pairs, T, R)
+    err = np.abs(m - want[0]).max() / np.abs(want[0]).max()
+    print("n = %d, largest moment %.3e, rel. diff %.2e" % (cn[0], np.abs(want[0]).max(), err))
+    assert cn.tolist() == [32769] and err <= 1e-11
+    normals = ops.estimate_normals(grid, None, 2 * R)[0]
+    for kw in ({}, {'normals': normals}):
+        icp = ops.icp_rigid(grid, None, pairs, T, R, max_iters=0, return_trace=True, **kw)
+        assert torch.equal(icp[1], count) and icp[4].tolist() == [0]
+        assert torch.equal(icp[5][:, 0, 0], moments[:, 0]) and torch.equal(icp[5][:, 0, 1], moments[:, 19])
+
+
+@pytest.mark.gpu
 def test_batch_independent_and_deterministic(scene, gpu_run):
     clouds, pairs, T0 = scene
     grid, outs = gpu_run

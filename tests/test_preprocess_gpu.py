@@ -157,6 +157,25 @@ def test_edge_cases(scene12):
         ops.RadiusGrid(*_stack(small), RADIUS)
 
 
+def test_device_pair_that_names_no_cloud(scene12):
+    """Device pairs are not read on the host: a pair that names a cloud that is not there gets -1 rows (those of the
+    clamped source cloud) and count 0 -- the kernel's own answer -- while its neighbours in the list are what the same
+    pairs give from the host, and the grid's status word stays clear."""
+    clouds, poses = scene12
+    a, b, one = clouds[0], clouds[1], clouds[0][:1].copy()
+    grid = ops.CloudGrid(*_stack([a, b, one]), RADIUS)
+    T01 = np.linalg.inv(poses[1]) @ poses[0]
+    T = np.stack([T01, np.eye(4), np.linalg.inv(T01)])
+    pairs = torch.tensor([[0, 1], [9, 0], [1, 0]], dtype=torch.int32, device=DEV)
+    nn, count, row_start = (t.cpu().numpy() for t in ops.nearest_pairs(grid, None, pairs, T, RADIUS))
+    want_nn, want_count, want_start = _device(None, [(0, 1), (1, 0)], T[[0, 2]], RADIUS, grid=grid)
+    assert row_start.tolist() == [0, len(a), len(a) + 1, len(a) + 1 + len(b)] and want_start[1] == len(a)
+    assert np.array_equal(nn[:len(a)], want_nn[:len(a)]) and np.array_equal(nn[len(a) + 1:], want_nn[len(a):])
+    assert count.tolist() == [want_count[0], 0, want_count[1]] and want_count.min() > 0
+    assert nn[len(a)] == -1
+    assert int(grid.status.word.item()) == 0
+
+
 def _equal_dicts(x, y):
     return list(x) == list(y) and all(np.array_equal(x[k], y[k]) and x[k].dtype == y[k].dtype for k in x)
 
