@@ -19,7 +19,11 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
   matrix of fragment pairs under given poses (``ops.pair_information``: one search, 20 raw moments per pair) -- the
   matrix ``gt.info`` holds and a pose graph takes per edge -- and the writer of ``gt.info``;
 * ``build_benchmark`` / ``build_benchmark_files``  ``gt.log`` and ``gt.info`` of a scene from raw fragments with poses:
-  what ``register_scene`` and ``evaluate_registration`` need to score registration recall on scenes of one's own.
+  what ``register_scene`` and ``evaluate_registration`` need to score registration recall on scenes of one's own;
+* ``multiway_registration`` / ``spanning_tree_poses`` / ``pose_graph_numpy``  one consistent pose per fragment from the
+  pair poses and their information matrices: robust pose-graph optimisation (``ops.pose_graph_optimize``, one launch)
+  that prunes false loop closures, and its NumPy restatement -- ``register_scene`` runs it when given
+  ``pose_graph=dict(max_distance=...)``.
 
 Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
 target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
@@ -36,6 +40,8 @@ from .common import select_keypoints
 
 RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0)
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 1, 2, 4, 8, 16      # ops.ICP_ST_*
+PG_ST_ITER_CAP, PG_ST_NONFINITE, PG_ST_GRAPH, PG_ST_INDEFINITE = 1, 2, 4, 8                         # ops.PG_ST_*
+PG_LAMBDA0, PG_LAMBDA_MIN, PG_LAMBDA_MAX = 1e-4, 1e-12, 1e8    # csrc/posegraph.hpp kLambda0 / kLambdaMin / kLambdaMax
 PLANE_PIVOT = 1e-10            # csrc/plane.hpp kPlanePivot
 
 
@@ -537,13 +543,18 @@ def evaluate_registration(est, gt, info, err2=0.2 ** 2):
 
 
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
-                   **ransac):
+                   pose_graph=None, **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
     ``evaluate_registration(...)`` when ``<gtpath>/gt.info`` exists, else None.  ``icp``: None, or a dict of
     ``refine_transforms`` keywords (at least ``max_distance``): every pose is refined by ICP over the dumped keypoint
-    files (they hold the whole subsampled fragment), all pairs in one call, before it is written and scored."""
+    files (they hold the whole subsampled fragment), all pairs in one call, before it is written and scored.
+    ``pose_graph``: None, or a dict of ``multiway_registration`` keywords (at least ``max_distance``): the information
+    matrices of the estimated poses are taken (from the ICP call when ``icp`` is given, else from one
+    ``information_matrices`` call over the keypoint files), ``multiway_registration`` gives one pose per fragment, and
+    the log holds ``inv(P_i) P_j`` for every pair it kept -- the pairs it pruned are left out.  The return value is then
+    ``(the usual result, poses [num_frag,4,4])``.  Still one read-back per scene."""
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -575,17 +586,342 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
         tps.append(tp)
     src, tgt, seg, _ = _compact(torch.stack(muts), torch.stack(sps), torch.stack(tps))
     T = _ransac(src, tgt, seg, ransac)[0]
+    frags = sorted(cache)
+    slot = {f: n for n, f in enumerate(frags)}
+    ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]
+    info = None
     if icp is not None:
-        frags = sorted(cache)
-        slot = {f: n for n, f in enumerate(frags)}
-        ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]
-        T = refine_transforms([cache[f][0] for f in frags], ij, T, device=dev, **_icp_keywords(icp))[0]
-    T = T.cpu().numpy()                                          # the scene's only read-back
-    est = {key: T[n] for n, key in enumerate(keys)}
+        res = refine_transforms([cache[f][0] for f in frags], ij, T, device=dev,
+                                return_information=pose_graph is not None, **_icp_keywords(icp))
+        T, info = res[0], (res[4] if pose_graph is not None else None)
+    if pose_graph is None:
+        T = T.cpu().numpy()                                      # the scene's only read-back
+        est = {key: T[n] for n, key in enumerate(keys)}
+        poses = None
+    else:
+        if not isinstance(pose_graph, dict) or 'max_distance' not in pose_graph:
+            raise ValueError("pose_graph must be None or a dict of multiway_registration keywords with at least "
+                             "max_distance")
+        if info is None:
+            info = information_matrices([cache[f][0] for f in frags], ij, T, pose_graph['max_distance'], device=dev)[0]
+        P, kept = multiway_registration(keys, T, info, num_frag, device=dev, **pose_graph)[:2]
+        i, j = (torch.as_tensor([int(k.split('_')[c]) for k in keys], device=dev) for c in (0, 1))
+        rel = torch.matmul(_rigid_inverse(P[i]), P[j])
+        flat = torch.cat([rel.reshape(-1), kept.double().reshape(-1), P.reshape(-1)]).cpu().numpy()   # the only read-back
+        n = len(keys)
+        rel, kept, poses = flat[:16 * n].reshape(n, 4, 4), flat[16 * n:17 * n] != 0, flat[17 * n:].reshape(-1, 4, 4)
+        est = {key: rel[m] for m, key in enumerate(keys) if kept[m]}
     ev.writelog(out_log or os.path.join(save_path, 'registration', scene), est, num_frag)
-    if not os.path.exists(os.path.join(gtpath, 'gt.info')):
-        return None
-    return evaluate_registration(est, gt, loadinfo(gtpath))
+    result = None
+    if os.path.exists(os.path.join(gtpath, 'gt.info')):
+        result = evaluate_registration(est, gt, loadinfo(gtpath))
+    return result if pose_graph is None else (result, poses)
+
+
+# ------------------------------------------------------------------------------------------------- multiway registration
+def _edge_list(keys_or_pairs, num_nodes):
+    """``gt.log`` keys ``'i_j'`` or (i, j) tuples -> int64 [E,2] rows (i, j), checked against ``num_nodes``."""
+    out = []
+    for k in keys_or_pairs:
+        i, j = (k.split('_') if isinstance(k, str) else k)
+        out.append((int(i), int(j)))
+    ij = np.asarray(out, dtype=np.int64).reshape(-1, 2)
+    if ij.size and (ij.min() < 0 or ij.max() >= num_nodes or (ij[:, 0] == ij[:, 1]).any()):
+        raise ValueError("edges must join two different nodes in 0..%d" % (num_nodes - 1))
+    return ij
+
+
+def _rigid_inverse(T):
+    """[..., 4, 4] rigid matrices (tensor or array) -> their inverses ``[R^T, -R^T t]``."""
+    Rt = T[..., :3, :3].transpose(-1, -2) if isinstance(T, torch.Tensor) else np.swapaxes(T[..., :3, :3], -1, -2)
+    out = T.clone() if isinstance(T, torch.Tensor) else np.array(T, dtype=np.float64)
+    out[..., :3, :3] = Rt
+    out[..., :3, 3] = -(Rt @ T[..., :3, 3:4])[..., 0]
+    return out
+
+
+def spanning_tree(num_nodes, edges, uncertain=None):
+    """The tree ``spanning_tree_poses`` composes along, decided on the host: for every component, from its lowest node,
+    a breadth-first search over the CERTAIN edges (a node's edges in list order); when it runs dry, the first
+    uncertain edge of the list that joins a reached node to an unreached one is taken and the search goes on from
+    there.  Returns ``(parent [N] (-1 for a root), edge [N] (the edge to the parent), depth [N], root [N])``."""
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    unc = np.zeros(len(edges), dtype=bool) if uncertain is None else np.asarray(uncertain).astype(bool).reshape(-1)
+    adj = [[] for _ in range(num_nodes)]
+    for e, (i, j) in enumerate(edges):
+        if not unc[e]:
+            adj[i].append((e, j))
+            adj[j].append((e, i))
+    parent, via, depth, root = (np.full(num_nodes, -1, dtype=np.int64) for _ in range(4))
+    loops = [e for e in range(len(edges)) if unc[e]]
+    for r in range(num_nodes):
+        if root[r] >= 0:
+            continue
+        root[r], depth[r] = r, 0
+        queue = [r]
+        while True:
+            while queue:
+                k = queue.pop(0)
+                for e, m in adj[k]:
+                    if root[m] < 0:
+                        root[m], parent[m], via[m], depth[m] = r, k, e, depth[k] + 1
+                        queue.append(m)
+            for e in loops:
+                i, j = edges[e]
+                if (root[i] == r) != (root[j] == r) and min(root[i], root[j]) < 0:
+                    k, m = (i, j) if root[i] == r else (j, i)
+                    root[m], parent[m], via[m], depth[m] = r, k, e, depth[k] + 1
+                    queue.append(m)
+                    break
+            if not queue:
+                break
+    return parent, via, depth, root
+
+
+def spanning_tree_poses(num_nodes, keys_or_edges, T, uncertain=None):
+    """Initial poses of a pose graph by composing the pair poses along ``spanning_tree``: the root (lowest node) of
+    every component gets the identity and ``P_j = P_i T_ij`` (``P_i = P_j inv(T_ij)`` against the edge's direction).
+    ``T`` [E,4,4]: a NumPy array gives a NumPy result; a tensor is composed in f64 on its device, one batched product
+    per tree level, without a read-back (the tree itself depends on the key list alone)."""
+    edges = _edge_list(keys_or_edges, num_nodes)
+    parent, via, depth, _ = spanning_tree(num_nodes, edges, uncertain)
+    tensor = isinstance(T, torch.Tensor)
+    Z = T.double() if tensor else torch.as_tensor(np.asarray(T, dtype=np.float64))
+    if tuple(Z.shape) != (len(edges), 4, 4):
+        raise ValueError("T must be [E,4,4] for the %d edges, got %s" % (len(edges), tuple(Z.shape)))
+    P = torch.eye(4, dtype=torch.float64, device=Z.device).repeat(num_nodes, 1, 1)
+    if len(edges):
+        step = torch.stack([Z, _rigid_inverse(Z)])                       # [2,E,4,4]: along / against the edge
+        for level in range(1, int(depth.max()) + 1):
+            kids = np.nonzero(depth == level)[0]
+            against = (edges[via[kids], 0] == kids).astype(np.int64)     # the child is the edge's i
+            idx = lambda a: torch.as_tensor(a, device=Z.device)
+            P[idx(kids)] = torch.matmul(P[idx(parent[kids])], step[idx(against), idx(via[kids])])
+    return P if tensor else P.numpy()
+
+
+def _so3_log_numpy(R):
+    """Rotation vector of R by the angle-axis formulas (not the kernel's quaternion route)."""
+    c = min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))
+    theta = np.arccos(c)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    if theta < 1e-7:
+        return v / 2.0
+    if theta < np.pi - 1e-3:
+        return v * (theta / (2.0 * np.sin(theta)))
+    B = (R + np.eye(3)) / 2.0                                            # ~ a a^T near pi
+    a = B[:, np.argmax(np.diag(B))].copy()
+    a /= np.linalg.norm(a)
+    if a @ v < 0:
+        a = -a
+    return a * theta
+
+
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _exp_numpy(d):
+    """Exp([v, w]) = [[R(w), v], [0, 1]] by Rodrigues' formula."""
+    w = d[3:]
+    theta = np.linalg.norm(w)
+    K = _hat(w)
+    if theta < 1e-6:
+        R = np.eye(3) + K + K @ K / 2.0
+    else:
+        R = np.eye(3) + np.sin(theta) / theta * K + (1.0 - np.cos(theta)) / theta ** 2 * K @ K
+    out = np.eye(4)
+    out[:3, :3], out[:3, 3] = R, d[:3]
+    return out
+
+
+def pose_graph_edge_numpy(Pi, Pj, Z, L):
+    """One edge of the pose graph in NumPy: ``(r [6], cost, Ji [6,6], Jj [6,6])`` -- ``D = inv(Z) inv(Pi) Pj``,
+    ``r = [D_t ; log(D_R)]``, ``Jj = diag(D_R, Jr^-1(phi))``, ``Ji = -Jj Ad(inv(M))`` with ``M = inv(Pi) Pj``
+    (include/d3feat_hip.h)."""
+    M = _rigid_inverse(np.asarray(Pi, dtype=np.float64)) @ Pj
+    D = _rigid_inverse(np.asarray(Z, dtype=np.float64)) @ M
+    phi = _so3_log_numpy(D[:3, :3])
+    r = np.concatenate([D[:3, 3], phi])
+    theta = np.linalg.norm(phi)
+    K = _hat(phi)
+    C = 1.0 / 12.0 + theta ** 2 / 720.0 if theta < 1e-3 else (1.0 - 0.5 * theta / np.tan(0.5 * theta)) / theta ** 2
+    Jj = np.zeros((6, 6))
+    Jj[:3, :3], Jj[3:, 3:] = D[:3, :3], np.eye(3) + 0.5 * K + C * K @ K
+    Ad = np.zeros((6, 6))
+    Ad[:3, :3] = Ad[3:, 3:] = M[:3, :3].T
+    Ad[:3, 3:] = -M[:3, :3].T @ _hat(M[:3, 3])
+    return r, float(r @ L @ r), -Jj @ Ad, Jj
+
+
+def _components_numpy(N, edges, active):
+    label = np.arange(N)
+
+    def find(k):
+        while label[k] != k:
+            label[k] = label[label[k]]
+            k = label[k]
+        return k
+    for e in np.nonzero(active)[0]:
+        a, b = find(edges[e, 0]), find(edges[e, 1])
+        if a != b:
+            label[max(a, b)] = min(a, b)
+    return np.array([find(k) for k in range(N)], dtype=np.int32)
+
+
+def _pose_graph_one(P, edges, Z, L, unc, max_distance, preference, prune_threshold, max_iters, step_tol, rel_cost):
+    """One graph of ``pose_graph_numpy``."""
+    N, E = len(P), len(edges)
+    P = P.copy()
+    weight, pruned = np.zeros(E), np.zeros(E, dtype=np.int32)
+    iterations, cost, status = np.zeros(2, dtype=np.int32), np.zeros(3), 0
+    component = np.arange(N, dtype=np.int32)
+    bad = 0
+    if not np.isfinite(P[:, :3]).all() or not np.isfinite(Z[:, :3]).all():
+        bad |= PG_ST_NONFINITE
+    if E and (edges.min() < 0 or edges.max() >= N or (edges[:, 0] == edges[:, 1]).any()):
+        bad |= PG_ST_GRAPH
+    active = np.array([np.isfinite(L[e]).all() and L[e, 0, 0] > 0 for e in range(E)], dtype=bool)
+    pruned[~active] = 1
+    if bad:
+        return P, weight, pruned, component, iterations, cost, bad
+
+    def energy_of(Q, mu):
+        total, costs = 0.0, np.zeros(E)
+        for e in np.nonzero(active)[0]:
+            D = _rigid_inverse(Z[e]) @ _rigid_inverse(Q[edges[e, 0]]) @ Q[edges[e, 1]]
+            r = np.concatenate([D[:3, 3], _so3_log_numpy(D[:3, :3])])
+            costs[e] = r @ L[e] @ r
+            total += mu * costs[e] / (mu + costs[e]) if unc[e] else costs[e]
+        return total, costs
+
+    for p in range(2):
+        component = _components_numpy(N, edges, active)
+        fixed = component == np.arange(N)
+        live = np.nonzero(active)[0]
+        mu = preference * max_distance ** 2 * L[live, 0, 0].mean() if live.size else 0.0
+        energy, costs = energy_of(P, mu)
+        if p == 0:
+            cost[0] = energy
+        lam, it, ended, system = PG_LAMBDA0, 0, live.size == 0, None
+        while not ended and it < max_iters:
+            if system is None:
+                H, g = np.zeros((6 * N, 6 * N)), np.zeros(6 * N)
+                for e in live:
+                    i, j = edges[e]
+                    r, c, Ji, Jj = pose_graph_edge_numpy(P[i], P[j], Z[e], L[e])
+                    l = (mu / (mu + c)) ** 2 if unc[e] else 1.0
+                    J = np.zeros((6, 6 * N))
+                    J[:, 6 * i:6 * i + 6], J[:, 6 * j:6 * j + 6] = Ji, Jj
+                    H += l * J.T @ L[e] @ J
+                    g += l * J.T @ L[e] @ r
+                for k in np.nonzero(fixed)[0]:
+                    H[6 * k:6 * k + 6, :] = 0.0
+                    H[:, 6 * k:6 * k + 6] = 0.0
+                    H[6 * k:6 * k + 6, 6 * k:6 * k + 6] = np.eye(6)
+                    g[6 * k:6 * k + 6] = 0.0
+                system = (H, g)
+            H, g = system
+            it += 1
+            A = H + lam * np.diag(np.diag(H))
+            try:
+                np.linalg.cholesky(A)
+            except np.linalg.LinAlgError:
+                lam *= 10.0
+                if lam > PG_LAMBDA_MAX:
+                    status |= PG_ST_INDEFINITE
+                    ended = True
+                continue
+            d = -np.linalg.solve(A, g)
+            maxd = np.abs(d).max()
+            Q = P.copy()
+            for k in np.nonzero(~fixed)[0]:
+                Q[k] = P[k] @ _exp_numpy(d[6 * k:6 * k + 6])
+            trial, trial_costs = energy_of(Q, mu)
+            if trial < energy:
+                P, costs, system = Q, trial_costs, None
+                if maxd <= step_tol or energy - trial <= rel_cost * energy:
+                    ended = True
+                energy = trial
+                lam = max(lam / 10.0, PG_LAMBDA_MIN)
+            else:
+                if maxd <= step_tol:
+                    ended = True
+                lam *= 10.0
+                if lam > PG_LAMBDA_MAX:
+                    ended = True
+        if not ended:
+            status |= PG_ST_ITER_CAP
+        for e in live:
+            weight[e] = (mu / (mu + costs[e])) ** 2 if unc[e] else 1.0
+            if p == 0 and unc[e] and weight[e] < prune_threshold:
+                active[e], pruned[e] = False, 1
+        iterations[p], cost[1 + p] = it, energy
+    return P, weight, pruned, component, iterations, cost, status
+
+
+def pose_graph_numpy(poses, edges, T, info, uncertain, max_distance, node_start=None, edge_start=None,
+                     preference_loop_closure=2.0, prune_threshold=0.25, max_iters=100, step_tol=1e-9, rel_cost=1e-9):
+    """The contract of ``ops.pose_graph_optimize`` in NumPy f64 (include/d3feat_hip.h): the ``device='cpu'`` path of
+    ``multiway_registration`` and the oracle of the tests.  It shares no code with the kernel: union-find components, a
+    Python loop over the edges, dense ``numpy.linalg`` factorisation and solve, the rotation logarithm by the
+    angle-axis formulas.  Arguments and the returned tuple ``(poses, weight, pruned, component, iterations, cost,
+    status)`` are those of ``ops.pose_graph_optimize``, as NumPy arrays."""
+    P = np.array(poses, dtype=np.float64).reshape(-1, 4, 4)
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    Z = np.asarray(T, dtype=np.float64).reshape(-1, 4, 4)
+    L = np.asarray(info, dtype=np.float64).reshape(-1, 6, 6)
+    unc = np.asarray(uncertain).astype(bool).reshape(-1)
+    ns = np.asarray([0, len(P)] if node_start is None else node_start, dtype=np.int64)
+    es = np.asarray([0, len(edges)] if edge_start is None else edge_start, dtype=np.int64)
+    outs = [_pose_graph_one(P[ns[g]:ns[g + 1]], edges[es[g]:es[g + 1]], Z[es[g]:es[g + 1]], L[es[g]:es[g + 1]],
+                            unc[es[g]:es[g + 1]], float(max_distance), float(preference_loop_closure),
+                            float(prune_threshold), int(max_iters), float(step_tol), float(rel_cost))
+            for g in range(len(ns) - 1)]
+    cat = lambda k, shape, dt: np.concatenate([o[k] for o in outs]) if outs else np.zeros(shape, dtype=dt)
+    return (cat(0, (0, 4, 4), np.float64), cat(1, (0,), np.float64), cat(2, (0,), np.int32), cat(3, (0,), np.int32),
+            np.stack([o[4] for o in outs]).astype(np.int32) if outs else np.zeros((0, 2), dtype=np.int32),
+            np.stack([o[5] for o in outs]) if outs else np.zeros((0, 3)),
+            np.array([o[6] for o in outs], dtype=np.int32))
+
+
+def multiway_registration(keys_or_pairs, T, info, num_nodes, max_distance, uncertain=None, init=None, device='cuda',
+                          **options):
+    """One consistent pose per fragment from the pair poses of a scene: robust pose-graph optimisation
+    (``ops.pose_graph_optimize``, ONE launch; ``device='cpu'``: ``pose_graph_numpy``) that switches off and prunes the
+    false loop closures.
+
+    ``keys_or_pairs``: ``gt.log`` keys ``'i_j'`` or (i, j) tuples; ``T`` [E,4,4] maps fragment j into fragment i (what
+    ``ransac_rigid`` / ``refine_transforms`` return); ``info`` [E,6,6] their information matrices in the default form
+    of ``information_from_moments`` (``refine_transforms(..., return_information=True)``), computed at
+    ``max_distance``; ``num_nodes`` fragments.  ``uncertain`` [E]: the edges the line process may switch off; None
+    takes ``|j - i| > 1``, the benchmark's rule for "not consecutive".  ``init`` [N,4,4]: initial poses; None takes
+    ``spanning_tree_poses``.  ``options``: ``preference_loop_closure``, ``prune_threshold``, ``max_iters``,
+    ``step_tol``, ``rel_cost`` of ``ops.pose_graph_optimize``.
+
+    Returns ``(poses [N,4,4] f64 -- fragment k into the frame of the lowest fragment of its component --, kept [E]
+    bool, weight [E], component [N], status)``: device tensors (``status`` [1]), or NumPy arrays from ``device='cpu'``.
+    ``inv(poses[i]) @ poses[j]`` is the consistent pose of a kept pair.  A false edge that is the ONLY link between two
+    parts of the graph (a bridge) contradicts nothing and cannot be detected: it is kept."""
+    edges = _edge_list(keys_or_pairs, num_nodes)
+    unc = np.abs(edges[:, 1] - edges[:, 0]) > 1 if uncertain is None else np.asarray(
+        uncertain.cpu() if isinstance(uncertain, torch.Tensor) else uncertain).astype(bool).reshape(-1)
+    if unc.shape[0] != edges.shape[0]:
+        raise ValueError("uncertain must hold one flag per edge")
+    if str(device).startswith('cpu'):
+        Tn, Ln = (np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+                  for a in (T, info))
+        P0 = spanning_tree_poses(num_nodes, edges, Tn, unc) if init is None else np.asarray(
+            init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+        P, weight, pruned, component, _, _, status = pose_graph_numpy(P0, edges, Tn, Ln, unc, max_distance, **options)
+        return P, pruned == 0, weight, component, status
+    dev = torch.device(device)
+    Td, Ld = (torch.as_tensor(a, dtype=torch.float64).to(dev) for a in (T, info))
+    P0 = spanning_tree_poses(num_nodes, edges, Td, unc) if init is None else torch.as_tensor(
+        init, dtype=torch.float64).to(dev)
+    P, weight, pruned, component, _, _, status = ops.pose_graph_optimize(P0, edges, Td, Ld, unc, max_distance,
+                                                                         **options)
+    return P, pruned == 0, weight, component, status
 
 
 # ------------------------------------------------------------------------------------------------- gt.log / gt.info

@@ -2898,6 +2898,9 @@ ICP_MAX_ITERS = 1024
 ICP_BLOCK_ROWS = 512
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8
 ICP_ST_SINGULAR = 16   # point-to-plane: singular normal equations (one plane's free slide, zero normals)
+PG_ST_ITER_CAP, PG_ST_NONFINITE, PG_ST_GRAPH, PG_ST_INDEFINITE = 1, 2, 4, 8   # pose_graph_optimize (D3F_PG_ST_*)
+PG_MAX_NODES = 128     # nodes of one graph (D3F_PG_MAX_NODES)
+PG_MAX_ITERS = 1024
 
 
 def icp_rigid_bytes(rows, found=None):
@@ -3053,6 +3056,146 @@ def pair_information(grid_or_points, lens, pairs, T, max_distance, rows=None):
             float(max_distance), _p(pr), _p(row_start), P, rows, _p(tf), _p(moments), _p(count), _p(status), _p(ws),
             nbytes, _stream()), "d3f_pair_information")
     return moments, count, status
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# multiway registration: robust pose-graph optimisation over the fragments of a scene (Open3D's global_optimization)
+# ---------------------------------------------------------------------------------------------------------------
+def _graph_starts(start, count, device, name):
+    """``node_start`` / ``edge_start`` -> (int32 device tensor [G+1], host array or None).  None: one graph."""
+    if isinstance(start, torch.Tensor) and start.is_cuda:
+        return start.to(torch.int32).contiguous().view(-1), None
+    host = np.asarray([0, count] if start is None else (start.cpu() if isinstance(start, torch.Tensor) else start),
+                      dtype=np.int64).reshape(-1)
+    if host.size < 2 or host[0] != 0 or host[-1] != count or (np.diff(host) < 0).any():
+        raise ValueError("%s must rise from 0 to %d, got %s" % (name, count, host.tolist()))
+    return torch.as_tensor(host.astype(np.int32), device=device), host
+
+
+def _pose_graph_inputs(poses, edges, T, info, uncertain, node_start, edge_start, max_nodes, max_edges, device):
+    """The arguments of d3f_pose_graph_optimize on ``device`` (a torch device; the host twin takes 'cpu')."""
+    ps = torch.as_tensor(poses, dtype=torch.float64).to(device).contiguous()
+    if ps.dim() != 3 or tuple(ps.shape[1:]) != (4, 4):
+        raise ValueError("poses must be [N,4,4], got %s" % (tuple(ps.shape),))
+    N = int(ps.shape[0])
+    on_device = isinstance(edges, torch.Tensor) and edges.is_cuda
+    if on_device:
+        ed = edges.to(torch.int32).contiguous().view(-1, 2)
+    else:
+        host = np.asarray(edges.cpu() if isinstance(edges, torch.Tensor) else edges, dtype=np.int64).reshape(-1, 2)
+        ed = torch.as_tensor(host.astype(np.int32)).to(device)
+    E = int(ed.shape[0])
+    Z = torch.as_tensor(T, dtype=torch.float64).to(device).contiguous()
+    L = torch.as_tensor(info, dtype=torch.float64).to(device).contiguous()
+    if tuple(Z.shape) != (E, 4, 4) or tuple(L.shape) != (E, 6, 6):
+        raise ValueError("T must be [E,4,4] and info [E,6,6] for the %d edges, got %s and %s"
+                         % (E, tuple(Z.shape), tuple(L.shape)))
+    un = torch.as_tensor(uncertain).to(device).to(torch.int32).contiguous().view(-1)
+    if int(un.numel()) != E:
+        raise ValueError("uncertain must hold one flag per edge")
+    ns, ns_host = _graph_starts(node_start, N, device, "node_start")
+    es, es_host = _graph_starts(edge_start, E, device, "edge_start")
+    G = int(ns.numel()) - 1
+    if int(es.numel()) - 1 != G:
+        raise ValueError("node_start and edge_start must delimit the same number of graphs")
+    if max_nodes is None:
+        if ns_host is None:
+            raise ValueError("max_nodes is required with a device node_start")
+        max_nodes = int(np.diff(ns_host).max())
+    if max_edges is None:
+        if es_host is None:
+            raise ValueError("max_edges is required with a device edge_start")
+        max_edges = int(np.diff(es_host).max())
+    if int(max_nodes) > PG_MAX_NODES:
+        raise ValueError("a graph holds at most %d nodes, got %d" % (PG_MAX_NODES, int(max_nodes)))
+    if not on_device and ns_host is not None and es_host is not None:    # host edges are checked here
+        for g in range(G):
+            e = host[es_host[g]:es_host[g + 1]]
+            n = int(ns_host[g + 1] - ns_host[g])
+            if e.size and (e.min() < 0 or e.max() >= n or (e[:, 0] == e[:, 1]).any()):
+                raise ValueError("graph %d: edges must join two different nodes in 0..%d" % (g, n - 1))
+    return ps, ed, Z, L, un, ns, es, G, N, E, int(max_nodes), int(max_edges)
+
+
+def _pose_graph_call(fn, name, device, stream, poses, edges, T, info, uncertain, max_distance, node_start, edge_start,
+                     preference_loop_closure, prune_threshold, max_iters, step_tol, rel_cost, max_nodes, max_edges):
+    if not (0.0 < float(max_distance) < float("inf")):
+        raise ValueError("max_distance must be positive and finite")
+    if not 0 <= int(max_iters) <= PG_MAX_ITERS:
+        raise ValueError("max_iters must be in 0..%d" % PG_MAX_ITERS)
+    if not (0.0 < float(preference_loop_closure) < float("inf")) or not 0.0 <= float(prune_threshold) <= 1.0:
+        raise ValueError("preference_loop_closure must be positive and finite, prune_threshold in 0..1")
+    if not float(step_tol) >= 0.0 or not float(rel_cost) >= 0.0:
+        raise ValueError("step_tol and rel_cost must be non-negative")
+    ps, ed, Z, L, un, ns, es, G, N, E, max_nodes, max_edges = _pose_graph_inputs(
+        poses, edges, T, info, uncertain, node_start, edge_start, max_nodes, max_edges, device)
+    out = torch.empty_like(ps)
+    weight = torch.empty(E, dtype=torch.float64, device=device)
+    pruned = torch.empty(E, dtype=torch.int32, device=device)
+    component = torch.empty(N, dtype=torch.int32, device=device)
+    iterations = torch.empty((G, 2), dtype=torch.int32, device=device)
+    cost = torch.empty((G, 3), dtype=torch.float64, device=device)
+    status = torch.empty(G, dtype=torch.int32, device=device)
+    nbytes = _native.lib().d3f_pose_graph_optimize_ws_bytes(G, max_nodes, max_edges)
+    ws = _ws(nbytes, device)
+    with _region("%s[G=%d,N=%d,E=%d]" % (name[4:], G, N, E)):
+        _native.check(fn(_p(ns), _p(es), G, N, E, max_nodes, max_edges, _p(ps), _p(ed), _p(Z), _p(L), _p(un),
+                         float(max_distance), float(preference_loop_closure), float(prune_threshold), int(max_iters),
+                         float(step_tol), float(rel_cost), _p(out), _p(weight), _p(pruned), _p(component),
+                         _p(iterations), _p(cost), _p(status), _p(ws), nbytes, stream), name)
+    return out, weight, pruned, component, iterations, cost, status
+
+
+def pose_graph_optimize(poses, edges, T, info, uncertain, max_distance, node_start=None, edge_start=None,
+                        preference_loop_closure=2.0, prune_threshold=0.25, max_iters=100, step_tol=1e-9, rel_cost=1e-9,
+                        max_nodes=None, max_edges=None):
+    """Robust pose-graph optimisation of G stacked fragment graphs, each carried by one workgroup
+    (d3f_pose_graph_optimize): one consistent pose per fragment from the pair poses of a scene, with the false loop
+    closures switched off by a line process and pruned.
+
+    ``poses`` f64 [N,4,4]: initial pose of every node (fragment k into the frame of its component's reference node);
+    ``edges`` [E,2] = (i, j) LOCAL to their graph -- host values (checked here) or a device int32 tensor (checked by
+    the kernel: ``PG_ST_GRAPH``); ``T`` f64 [E,4,4] maps fragment j into fragment i (a ``gt.log`` key i_j, what
+    ``ransac_rigid`` / ``icp_rigid`` with pairs (j, i) return); ``info`` f64 [E,6,6] in the project's default form
+    (``registration.information_from_moments``); ``uncertain`` [E] flags the edges under the line process;
+    ``max_distance``: the distance the information was computed at.  ``node_start`` / ``edge_start`` [G+1] delimit the
+    graphs (None: one graph); as device tensors they come with the host bounds ``max_nodes`` / ``max_edges`` on one
+    graph's size -- with device ``edges`` too that is the form a captured graph takes.  At most ``PG_MAX_NODES`` nodes
+    per graph.
+
+    Residual ``[D_t ; log(D_R)]`` of ``D = inv(T) inv(P_i) P_j`` under ``info``; uncertain edges weigh
+    ``(mu / (mu + c))^2`` with ``mu = preference_loop_closure * max_distance^2 * mean info[0,0]``; Levenberg-Marquardt,
+    then every uncertain edge below ``prune_threshold`` is pruned, the components are taken again and a second pass
+    runs -- all in ONE launch (include/d3feat_hip.h has the damping schedule and the stopping rules ``step_tol``,
+    ``rel_cost``, ``max_iters``).  The lowest node of every component of the active edges is fixed.
+
+    Returns device tensors ``(poses [N,4,4] f64, weight [E] f64, pruned [E] int32, component [N] int32, iterations
+    [G,2] int32, cost [G,3] f64 (initial, after pass 1, final), status [G] int32 (PG_ST_* bits))``.  An edge without
+    correspondences (``info[0,0] <= 0``) or with a non-finite matrix is reported pruned.  Bit-identical from run to run
+    and for a graph alone or inside any batch; no read-back, no floating-point atomics."""
+    dev = poses.device if isinstance(poses, torch.Tensor) and poses.is_cuda else torch.device("cuda")
+    if not torch.cuda.is_available():
+        raise RuntimeError("pose_graph_optimize needs the GPU (d3feat_pytorch_amd has no CPU path; the host twin is "
+                           "pose_graph_optimize_host)")
+    return _pose_graph_call(_native.lib().d3f_pose_graph_optimize, "d3f_pose_graph_optimize", dev, _stream(), poses,
+                            edges, T, info, uncertain, max_distance, node_start, edge_start, preference_loop_closure,
+                            prune_threshold, max_iters, step_tol, rel_cost, max_nodes, max_edges)
+
+
+def pose_graph_optimize_host(poses, edges, T, info, uncertain, max_distance, node_start=None, edge_start=None,
+                             preference_loop_closure=2.0, prune_threshold=0.25, max_iters=100, step_tol=1e-9,
+                             rel_cost=1e-9, max_nodes=None, max_edges=None):
+    """The host twin of ``pose_graph_optimize`` (d3f_pose_graph_optimize_host): the same text as the kernel run by one
+    worker on the CPU, for tests -- host arrays / CPU tensors in, CPU tensors out, no GPU call."""
+    global _PROFILER
+    prof, _PROFILER = _PROFILER, None      # a region records device events
+    try:
+        return _pose_graph_call(_native.lib().d3f_pose_graph_optimize_host, "d3f_pose_graph_optimize_host",
+                                torch.device("cpu"), None, poses, edges, T, info, uncertain, max_distance, node_start,
+                                edge_start, preference_loop_closure, prune_threshold, max_iters, step_tol, rel_cost,
+                                max_nodes, max_edges)
+    finally:
+        _PROFILER = prof
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -951,6 +951,89 @@ int d3f_pair_information(const void* grid_ws, const float* points, int Ns, const
                          size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multiway registration: robust pose-graph optimisation of the fragments of a scene -- the step the 3DMatch / Open3D
+ * reconstruction pipeline ends with (Levenberg-Marquardt on SE(3) with the line process of Choi, Zhou, Koltun 2015 on
+ * the uncertain edges, pruning, a second pass).  The reference has no counterpart.  csrc/posegraph.hpp holds the text
+ * the kernel and the host twin both run.
+ *
+ * A batch of G graphs is stacked: node_start [G+1] / edge_start [G+1] int32 delimit the graphs inside poses [N,16] and
+ * the edge arrays [E,...]; edges [E,2] int32 = (i, j), indices LOCAL to the graph, i != j; (j, i) with j > i and
+ * duplicates are legal.  All matrices f64 row-major.
+ *   node k:  pose P_k (4x4, rigid) maps fragment k into the frame of its component's reference node;
+ *   edge e:  Z_e (4x4) maps fragment j into fragment i (gt.log's key i_j, what d3f_ransac_rigid returns, inv(P_i) P_j);
+ *            L_e (6x6, symmetric) in the moving frame with the translation block first (the gt.info form, the frame
+ *            D = inv(T_gt) T_est acts in); uncertain[e] != 0 puts the edge under the line process.
+ *   inv() is the rigid inverse [R^T, -R^T t].
+ *   D_e = inv(Z_e) inv(P_i) P_j;  r_e = [D_t ; log(D_R)] (rotation vector);  c_e = r_e^T L_e r_e -- to first order the
+ *   sum of squared displacements of the pair's correspondences, so mu below is in squared metres times a count.
+ *   energy = sum over certain active edges of c_e + sum over uncertain active edges of mu c_e / (mu + c_e);
+ *   weight l_e = (mu / (mu + c_e))^2 (uncertain), 1 (certain);
+ *   mu = preference_loop_closure * max_distance^2 * mean over the graph's ACTIVE edges of L_e[0,0] (the number of
+ *   correspondences), taken anew for each pass.
+ *   update P_k <- P_k Exp(d_k), Exp([v, w]) = [[R(w), v], [0, 1]].
+ * An edge whose L_e holds a non-finite value or has L_e[0,0] <= 0 is inactive from the start and reported pruned.
+ * Components are taken over the active edges (min-label propagation); the lowest-numbered node of every component is
+ * FIXED and its returned pose is bit-equal to the given one; an isolated node is its own component.
+ * One call makes two passes: optimise; mark pruned (and deactivate) every uncertain edge with l_e < prune_threshold
+ * (0.25 is c_e > mu); recompute the components; optimise the remaining edges again.
+ * A pass is Levenberg-Marquardt on the weighted normal equations, weights frozen within an iteration, Jacobians exact
+ * (csrc/posegraph.hpp), damping relative to the diagonal:
+ *   lambda = 1e-4 at the start of a pass; ITERATION (at most max_iters per pass):
+ *     factor H + lambda diag(H) (dense f64 Cholesky, rows and columns of the fixed nodes identity); a pivot that is
+ *       not > 0: lambda *= 10 and, beyond 1e8, the pass ends with D3F_PG_ST_INDEFINITE;
+ *     d = -(H + lambda diag(H))^-1 g, trial poses, their energy E';
+ *     E' < E: accepted, lambda = max(lambda / 10, 1e-12); the pass ends when max|d| <= step_tol or
+ *       E - E' <= rel_cost * E;
+ *     otherwise rejected: the pass ends when max|d| <= step_tol; lambda *= 10 and, beyond 1e8, the pass ends.
+ *   A pass that used max_iters iterations without ending sets D3F_PG_ST_ITER_CAP.  The Python layer's defaults:
+ *   preference_loop_closure 2, prune_threshold 0.25, max_iters 100, step_tol 1e-9, rel_cost 1e-9.
+ * Outputs: out_poses [N,16]; weight [E] = l_e at the end of the last pass in which the edge was active (0 for an edge
+ * inactive from the start); pruned [E] int32; component [N] int32 = the lowest node (local index) of the node's
+ * component after pruning; iterations [G,2] per pass; cost [G,3] = energy at the start, after pass 1 (under pass 1's
+ * mu), at the end (under pass 2's mu); status [G] = D3F_PG_ST_* bits.  A graph with a non-finite pose or measurement
+ * (D3F_PG_ST_NONFINITE), or with an edge index outside the graph, i == j, or more nodes / edges than max_nodes /
+ * max_edges (D3F_PG_ST_GRAPH) returns its poses as given, zero weights and iterations and every node its own component.
+ * max_nodes / max_edges are host bounds on ONE graph's size; they size the workspace
+ * (d3f_pose_graph_optimize_ws_bytes(G, max_nodes, max_edges): two dense [6 max_nodes]^2 matrices and 1 KB per edge,
+ * per graph).  max_nodes <= D3F_PG_MAX_NODES = 128 (D3F_EINVAL beyond): the 6-row panel of the factorisation
+ * (6 x 6 max_nodes f64) and the step vector live in LDS, 43 KB at the cap, and the matrices of a larger graph would
+ * leave L2.  G <= 65535, max_edges <= 2^20, max_iters <= 1024.
+ * One workgroup per graph carries both passes: ONE launch on `stream`, no host synchronisation, no allocation
+ * (graph-capturable).  Every entry of H and g has one owner that adds the node's edges in ascending edge order and
+ * every energy is summed in one fixed shape -- no floating-point atomics -- so a graph's result is bit-identical from
+ * run to run, alone or inside any batch.
+ * d3f_pose_graph_optimize_host: the host twin -- the same arguments as host pointers, the same text run by one
+ * worker, no GPU call (`stream` is ignored).  It differs from the device only where sin / cos / atan2 / sqrt do.
+ * d3f_pose_graph_edge_host: one edge: r [6], *cost = c_e, Ji / Jj [36] row-major (row = residual component,
+ * column = component of d_i / d_j).
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_PG_MAX_NODES 128
+#define D3F_PG_MAX_EDGES (1 << 20)
+#define D3F_PG_MAX_GRAPHS 65535
+#define D3F_PG_MAX_ITERS 1024
+#define D3F_PG_ST_ITER_CAP 1    /* a pass used max_iters iterations without meeting a stopping rule */
+#define D3F_PG_ST_NONFINITE 2   /* a pose or a measurement holds a non-finite value: poses returned as given */
+#define D3F_PG_ST_GRAPH 4       /* an edge index out of range, i == j, or a graph beyond max_nodes / max_edges */
+#define D3F_PG_ST_INDEFINITE 8  /* the normal equations stayed indefinite at the largest damping */
+size_t d3f_pose_graph_optimize_ws_bytes(int G, int max_nodes, int max_edges);
+int d3f_pose_graph_optimize(const int32_t* node_start, const int32_t* edge_start, int G, int N, int E, int max_nodes,
+                            int max_edges, const double* poses, const int32_t* edges, const double* Z,
+                            const double* info, const int32_t* uncertain, double max_distance,
+                            double preference_loop_closure, double prune_threshold, int max_iters, double step_tol,
+                            double rel_cost, double* out_poses, double* weight, int32_t* pruned, int32_t* component,
+                            int32_t* iterations, double* cost, int32_t* status, void* ws, size_t ws_bytes,
+                            void* stream);
+int d3f_pose_graph_optimize_host(const int32_t* node_start, const int32_t* edge_start, int G, int N, int E,
+                                 int max_nodes, int max_edges, const double* poses, const int32_t* edges,
+                                 const double* Z, const double* info, const int32_t* uncertain, double max_distance,
+                                 double preference_loop_closure, double prune_threshold, int max_iters,
+                                 double step_tol, double rel_cost, double* out_poses, double* weight, int32_t* pruned,
+                                 int32_t* component, int32_t* iterations, double* cost, int32_t* status, void* ws,
+                                 size_t ws_bytes, void* stream);
+int d3f_pose_graph_edge_host(const double* Pi_host, const double* Pj_host, const double* Z_host, const double* L_host,
+                             double* r_host, double* cost_host, double* Ji_host, double* Jj_host);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
