@@ -1,0 +1,243 @@
+"""Fragments and scenes from an RGB-D sequence: TSDF fusion of depth frames on the device (csrc/tsdf.hpp has the rule).
+
+The upstream end of the 3DMatch pipeline -- a fragment is the fusion of ``frames_per_fragment`` (50) consecutive depth
+frames, expressed in the frame of its first camera, whose pose is the fragment's ``.info.txt`` -- and its downstream
+end: the fused scene, the same integration over all frames with the fragment poses of ``multiway_registration``
+composed in.  The reference ships no code for either step (its fragments are the authors' download), so files made here
+follow the rule of csrc/tsdf.hpp and are not claimed to equal that download.
+
+``device='cuda'`` runs the HIP kernels (``ops.tsdf_bounds`` / ``tsdf_integrate`` / ``tsdf_extract``); ``device='cpu'``
+runs their NumPy restatement, which gives the same clouds bit for bit.  Normals and colour are not part of this
+(``ops.estimate_normals`` works on the result).
+"""
+import os
+import re
+from os.path import exists, join
+
+import numpy as np
+
+DEFAULT_MAX_BYTES = 1 << 33      # D and w of the volumes integrated in one launch (8 bytes per voxel)
+DEFAULT_DEPTH_MAX = 6.0          # metres (ops.TSDF_DEPTH_MAX)
+
+
+def rigid_inverse(P):
+    """f64 inverse [R^T, -R^T t] of the rigid 4x4 ``P``."""
+    P = np.asarray(P, dtype=np.float64)
+    out = np.eye(4)
+    out[:3, :3] = P[:3, :3].T
+    out[:3, 3] = -(P[:3, :3].T @ P[:3, 3])
+    return out
+
+
+def _is_cpu(device):
+    return str(device).startswith('cpu')
+
+
+def _frames(depth, intrinsics, poses):
+    if hasattr(depth, 'detach'):
+        from .. import ops
+        depth = ops._tsdf_depth_array(depth)
+    depth = np.asarray(depth)
+    if depth.ndim != 3:
+        raise ValueError("depth must be [F,H,W], got %s" % (depth.shape,))
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if poses.shape[0] != depth.shape[0]:
+        raise ValueError("%d poses for %d depth frames" % (poses.shape[0], depth.shape[0]))
+    K = np.asarray(intrinsics, dtype=np.float64)
+    if K.shape == (3, 3):
+        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    K = np.broadcast_to(K.reshape(-1, 4), (depth.shape[0], 4)).astype(np.float32)
+    return depth, K, poses
+
+
+def place_volumes(bounds, voxel):
+    """``(origin f32 [V,3], dims int64 [V,3])`` from the [V,6] bounds of ``tsdf_bounds``: ``origin = voxel * (floor(min
+    / voxel) - 1)`` and the lattice reaches one plane past the maximum.  A volume without a valid pixel gets one voxel."""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 6)
+    origin = np.zeros((b.shape[0], 3), dtype=np.float32)
+    dims = np.ones((b.shape[0], 3), dtype=np.int64)
+    for v in range(b.shape[0]):
+        if not np.isfinite(b[v]).all():
+            continue
+        origin[v] = (voxel * (np.floor(b[v, :3] / voxel) - 1.0)).astype(np.float32)
+        dims[v] = np.ceil((b[v, 3:] - origin[v].astype(np.float64)) / voxel).astype(np.int64) + 2
+    return origin, dims
+
+
+def _check_fits(dims, voxel, max_bytes, what):
+    for v, n in enumerate(dims):
+        nbytes = 8 * int(n[0]) * int(n[1]) * int(n[2])
+        if nbytes > max_bytes:
+            raise ValueError("%s %d: a volume of %d x %d x %d voxels of %g m (extent %.2f x %.2f x %.2f m) takes %d "
+                             "bytes, more than max_bytes = %d: raise max_bytes or the voxel size"
+                             % (what, v, n[0], n[1], n[2], voxel, n[0] * voxel, n[1] * voxel, n[2] * voxel, nbytes,
+                                max_bytes))
+
+
+def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what):
+    """Clouds (list of f32 [N,3]) of the volumes that own the frame ranges ``frame_start`` of (depth, K, M, C)."""
+    from .. import ops
+    cpu = _is_cpu(device)
+    frame_start = np.asarray(frame_start, dtype=np.int64)
+    V = frame_start.size - 1
+    if V == 0:
+        return []
+    # the bounds in groups of volumes whose frames fit max_bytes too (one volume's frames at least): the depth frames
+    # of a call are on the device next to its volumes
+    frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
+    bounds, v = [], 0
+    while v < V:
+        e = v + 1
+        while e < V and int(frame_start[e + 1] - frame_start[v]) * frame_bytes <= int(max_bytes):
+            e += 1
+        lo, hi = int(frame_start[v]), int(frame_start[e])
+        args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], C[lo:hi], depth_scale, depth_max)
+        bounds.append(ops.tsdf_bounds_numpy(*args) if cpu else ops.tsdf_bounds(*args).cpu().numpy())
+        v = e
+    bounds = np.concatenate(bounds, 0)
+    origin, dims = place_volumes(bounds, voxel)
+    _check_fits(dims, voxel, int(max_bytes), what)        # before anything is launched
+    sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
+    clouds, v = [], 0
+    while v < V:
+        e, used = v, 0
+        while e < V and (e == v or used + int(sizes[e]) <= int(max_bytes)):
+            used += int(sizes[e])
+            e += 1
+        lo, hi = int(frame_start[v]), int(frame_start[e])
+        args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi], origin[v:e], dims[v:e], voxel, trunc,
+                depth_scale, depth_max)
+        if cpu:
+            D, w, vs = ops.tsdf_numpy(*args)
+            pts, ps = ops.tsdf_extract_numpy(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
+        else:
+            D, w, vs = ops.tsdf_integrate(*args)
+            pts, ps = ops.tsdf_extract(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
+            pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
+            del D, w
+        clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
+        v = e
+    return clouds
+
+
+def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
+                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+    """``(clouds, fragment_poses)``: the fragments of a depth sequence, the 3DMatch way.
+
+    ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or floating-point metres; ``intrinsics`` [4] =
+    fx, fy, cx, cy, a 3x3 camera matrix, or [F,4]; ``poses`` [F,4,4] f64 camera-to-world.  Fragment g takes the frames
+    ``[g k, (g + 1) k)`` (the last group may be shorter); its frame is its first camera's and its pose that camera's
+    pose.  Frame f enters with ``M_f = inv(pose_f) @ pose_first`` (f64, rigid inverse, rounded to f32 once).  Every
+    volume is placed from the back-projected extent of its frames (``place_volumes``); ``trunc`` defaults to ``5 *
+    voxel``; a voxel counts with ``w >= min_weight``.  Fragments are integrated in batches whose volumes fit
+    ``max_bytes``; one that does not fit alone raises ``ValueError`` before anything is launched.  The depth frames of
+    a batch are uploaded with it (for the bounds, in groups that fit ``max_bytes`` as well): the device holds the
+    volumes of one batch plus its frames, never the whole sequence.
+    ``clouds``: list of f32 [N_g,3] in the fragments' own frames; ``fragment_poses`` f64 [G,4,4]."""
+    depth, K, poses = _frames(depth, intrinsics, poses)
+    k = int(frames_per_fragment)
+    if k < 1:
+        raise ValueError("frames_per_fragment must be at least 1")
+    F = depth.shape[0]
+    frame_start = np.asarray(list(range(0, F, k)) + [F], dtype=np.int64) if F else np.zeros(1, dtype=np.int64)
+    first = np.repeat(frame_start[:-1], np.diff(frame_start))
+    M = np.stack([rigid_inverse(poses[f]) @ poses[first[f]] for f in range(F)]) if F else np.zeros((0, 4, 4))
+    C = np.stack([rigid_inverse(poses[first[f]]) @ poses[f] for f in range(F)]) if F else np.zeros((0, 4, 4))
+    trunc = 5.0 * voxel if trunc is None else trunc
+    clouds = _fuse(depth, K, M, C, frame_start, float(voxel), float(trunc), depth_scale, depth_max, float(min_weight),
+                   device, max_bytes, "fragment")
+    return clouds, poses[frame_start[:-1]].copy()
+
+
+def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
+               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+    """One cloud f32 [N,3] in the scene frame: all frames fused into ONE volume, frame f of fragment g entering with the
+    camera-to-scene pose ``fragment_poses[g] @ inv(poses[first_g]) @ poses[f]``.  ``fragment_poses`` [G',4,4] is what
+    ``multiway_registration`` returns; the frames of a fragment whose pose is not finite, or that has none (g >= G'),
+    are left out.  The one volume takes all kept frames in one launch, so they are on the device together with it.
+    The other arguments are those of ``fuse_fragments``."""
+    depth, K, poses = _frames(depth, intrinsics, poses)
+    k = int(frames_per_fragment)
+    if k < 1:
+        raise ValueError("frames_per_fragment must be at least 1")
+    fp = np.asarray(fragment_poses, dtype=np.float64).reshape(-1, 4, 4)
+    keep, S = [], []
+    for f in range(depth.shape[0]):
+        g = f // k
+        if g >= fp.shape[0] or not np.isfinite(fp[g]).all():
+            continue
+        keep.append(f)
+        S.append(fp[g] @ rigid_inverse(poses[g * k]) @ poses[f])
+    if not keep:
+        return np.zeros((0, 3), dtype=np.float32)
+    S = np.stack(S)
+    M = np.stack([rigid_inverse(s) for s in S])
+    trunc = 5.0 * voxel if trunc is None else trunc
+    return _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
+                 depth_scale, depth_max, float(min_weight), device, max_bytes, "scene")[0]
+
+
+# ------------------------------------------------------------------------------------------------------ files
+def write_ply_points(filename, points):
+    """Binary little-endian PLY with the three float properties x, y, z."""
+    p = np.ascontiguousarray(points, dtype='<f4').reshape(-1, 3)
+    with open(filename, 'wb') as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+                 "property float z\nend_header\n" % p.shape[0]).encode('ascii'))
+        f.write(p.tobytes())
+
+
+def write_fragments(root, scene, clouds, poses, frames_per_fragment, seq='seq-01', num_frames=None):
+    """``<root>/fragments/<scene>/cloud_bin_<i>.ply`` and ``cloud_bin_<i>.info.txt`` (header ``<scene>\\t<seq>\\t<first
+    frame>\\t<last frame>``, then the 4x4 fragment-to-world pose with 17 significant digits), the layout
+    ``preprocess.read_scene`` reads.  ``num_frames``: the length of the sequence, so that a shorter last fragment names
+    its true last frame (None: every fragment is taken to be full).  Returns the folder."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if poses.shape[0] != len(clouds):
+        raise ValueError("%d poses for %d clouds" % (poses.shape[0], len(clouds)))
+    path = join(root, 'fragments', scene)
+    os.makedirs(path, exist_ok=True)
+    k = int(frames_per_fragment)
+    for i, (c, P) in enumerate(zip(clouds, poses)):
+        write_ply_points(join(path, 'cloud_bin_%d.ply' % i), c)
+        with open(join(path, 'cloud_bin_%d.info.txt' % i), 'w') as f:
+            last = (i + 1) * k if num_frames is None else min((i + 1) * k, int(num_frames))
+            f.write("%s\t%s\t%d\t%d\n" % (scene, seq, i * k, last - 1))
+            for row in P:
+                f.write("\t".join("%.17g" % x for x in row) + "\n")
+    return path
+
+
+def read_sequence(folder):
+    """``(depth uint16 [F,H,W], intrinsics f64 [4] = fx, fy, cx, cy, poses f64 [F,4,4])`` of a 3DMatch raw sequence
+    folder: ``frame-%06d.depth.png`` (16-bit), ``frame-%06d.pose.txt`` (camera-to-world), and ``camera-intrinsics.txt``
+    (3x3) in the folder or in its parent."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("read_sequence needs Pillow to read the 16-bit depth PNGs (import PIL failed: %s)" % e)
+    names = sorted(n for n in os.listdir(folder) if re.fullmatch(r'frame-\d+\.depth\.png', n))
+    if not names:
+        raise ValueError("%s: no frame-*.depth.png" % folder)
+    for where in (folder, os.path.dirname(os.path.abspath(folder))):
+        if exists(join(where, 'camera-intrinsics.txt')):
+            Kmat = np.loadtxt(join(where, 'camera-intrinsics.txt'), dtype=np.float64)
+            break
+    else:
+        raise ValueError("%s: no camera-intrinsics.txt here or one folder up" % folder)
+    if Kmat.shape != (3, 3):
+        raise ValueError("camera-intrinsics.txt: expected a 3x3 matrix, got %s" % (Kmat.shape,))
+    depth, poses = [], []
+    for n in names:
+        with Image.open(join(folder, n)) as im:
+            a = np.array(im)
+        if a.ndim != 2 or a.min() < 0 or a.max() > 65535:
+            raise ValueError("%s: not a single-channel 16-bit image" % n)
+        depth.append(a.astype(np.uint16))
+        P = np.loadtxt(join(folder, n.replace('.depth.png', '.pose.txt')), dtype=np.float64)
+        if P.shape != (4, 4):
+            raise ValueError("%s: expected a 4x4 pose" % n.replace('.depth.png', '.pose.txt'))
+        poses.append(P)
+    if len({d.shape for d in depth}) != 1:
+        raise ValueError("%s: the depth images differ in size" % folder)
+    return np.stack(depth), np.array([Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]]), np.stack(poses)

@@ -3199,6 +3199,352 @@ def pose_graph_optimize_host(poses, edges, T, info, uncertain, max_distance, nod
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# TSDF fusion of depth frames into dense volumes, and their zero crossings as point clouds (csrc/tsdf.hpp)
+# ---------------------------------------------------------------------------------------------------------------
+TSDF_DEPTH_MAX = 6.0          # default depth_max in metres: farther pixels are not fused
+TSDF_ST_OVERFLOW = 1          # D3F_TSDF_ST_OVERFLOW
+TSDF_MAX_VOLUMES = 65535
+
+
+def _tsdf_depth_array(depth):
+    """Depth frames as a host array [F,H,W], uint16 raw units or f32 metres (other floats become f32)."""
+    if isinstance(depth, torch.Tensor):
+        t = depth.detach().cpu()
+        depth = t.view(torch.int16).numpy().view(np.uint16) if t.dtype in (torch.int16, torch.uint16) else t.numpy()
+    a = np.asarray(depth)
+    if a.dtype != np.uint16:
+        if a.dtype.kind != 'f':
+            raise ValueError("depth must be uint16 raw units or floating-point metres, got %s" % a.dtype)
+        a = a.astype(np.float32, copy=False)
+    if a.ndim != 3:
+        raise ValueError("depth must be [F,H,W], got %s" % (a.shape,))
+    return np.ascontiguousarray(a)
+
+
+def _tsdf_frames(depth, frame_start, intrinsics, matrices):
+    """Host form of the frame arguments: (depth [F,H,W], frame_start int32 [V+1], K f32 [F,4], matrices f32 [F,12])."""
+    d = _tsdf_depth_array(depth)
+    F = d.shape[0]
+    fs = np.asarray(frame_start, dtype=np.int64).reshape(-1)
+    if fs.size < 2 or fs[0] < 0 or fs[-1] > F or (np.diff(fs) < 0).any():
+        raise ValueError("frame_start must rise within 0..%d, got %s" % (F, fs.tolist()))
+    if fs.size - 1 > TSDF_MAX_VOLUMES:
+        raise ValueError("at most %d volumes per call" % TSDF_MAX_VOLUMES)
+    K = np.asarray(intrinsics.cpu() if isinstance(intrinsics, torch.Tensor) else intrinsics, dtype=np.float32)
+    K = np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 4), (F, 4)))
+    m = np.asarray(matrices.cpu() if isinstance(matrices, torch.Tensor) else matrices)
+    if m.ndim == 3 and m.shape[1:] in ((4, 4), (3, 4)):
+        m = m[:, :3, :]
+    m = np.ascontiguousarray(m.astype(np.float32).reshape(-1, 12))        # rounded to f32 once, here
+    if m.shape[0] != F:
+        raise ValueError("%d frame matrices for %d frames" % (m.shape[0], F))
+    return d, fs.astype(np.int32), K, m
+
+
+def _tsdf_volumes(origin, dims, voxel, V, trunc=None):
+    """Host form of the volume arguments: (origin f32 [V,3], dims int32 [V,3], voxel f32 [V], trunc f32 [V] or None,
+    vol_start int64 [V+1])."""
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    o = np.ascontiguousarray(np.asarray(host(origin), dtype=np.float32).reshape(-1, 3))
+    n = np.ascontiguousarray(np.asarray(host(dims), dtype=np.int64).reshape(-1, 3))
+    if o.shape[0] != V or n.shape[0] != V:
+        raise ValueError("origin and dims must hold one row per volume (%d)" % V)
+    if (n < 1).any() or (n > 0x7fffffff).any():
+        raise ValueError("every lattice dimension must be at least 1, got %s" % n.tolist())
+    vx = np.ascontiguousarray(np.broadcast_to(np.asarray(host(voxel), dtype=np.float32).reshape(-1), (V,)))
+    if not (vx > 0).all():
+        raise ValueError("voxel sizes must be positive")
+    tr = None
+    if trunc is not None:
+        tr = np.ascontiguousarray(np.broadcast_to(np.asarray(host(trunc), dtype=np.float32).reshape(-1), (V,)))
+        if not (tr > 0).all():
+            raise ValueError("truncation distances must be positive")
+    vol_start = np.zeros(V + 1, dtype=np.int64)
+    vol_start[1:] = np.cumsum([int(a) * int(b) * int(c) for a, b, c in n])
+    return o, n.astype(np.int32), vx, tr, vol_start
+
+
+def _on(device, *arrays):
+    out = []
+    for a in arrays:
+        a = a if a.flags.writeable else a.copy()
+        t = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
+        out.append(t.to(device).contiguous())
+    return out
+
+
+def _tsdf_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("the TSDF kernels need the GPU (d3feat_pytorch_amd has no CPU path; the host twins are "
+                           "tsdf_*_host, the NumPy restatement tsdf_numpy)")
+    return torch.device("cuda")
+
+
+def _tsdf_bounds(fn, name, device, stream, depth, frame_start, intrinsics, camera_to_volume, depth_scale, depth_max):
+    d, fs, K, C = _tsdf_frames(depth, frame_start, intrinsics, camera_to_volume)
+    V = fs.size - 1
+    if d.shape[0] > 65535:
+        raise ValueError("at most 65535 frames per call")
+    td, tfs, tK, tC = _on(device, d, fs, K, C)
+    bounds = torch.empty((V, 6), dtype=torch.float32, device=device)
+    _native.check(fn(_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tC),
+                     float(depth_scale), float(depth_max), _p(bounds), stream), name)
+    return bounds
+
+
+def tsdf_bounds(depth, frame_start, intrinsics, camera_to_volume, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """f32 [V,6] on the device: per volume the minimum (3) and maximum (3), in the volume's frame, of the back-projected
+    valid pixels of its frames (d3f_tsdf_bounds; +inf / -inf for a volume without one).  ``camera_to_volume`` [F,3,4] /
+    [F,4,4]: the inverses of ``tsdf_integrate``'s matrices, rounded to f32 here.  Exact (integer-ordered min / max)."""
+    dev = _tsdf_device()
+    with _region("tsdf_bounds"):
+        return _tsdf_bounds(_native.lib().d3f_tsdf_bounds, "d3f_tsdf_bounds", dev, _stream(), depth, frame_start,
+                            intrinsics, camera_to_volume, depth_scale, depth_max)
+
+
+def tsdf_bounds_host(depth, frame_start, intrinsics, camera_to_volume, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """The host twin of ``tsdf_bounds`` (d3f_tsdf_bounds_host): CPU tensor out, no GPU call."""
+    return _tsdf_bounds(_native.lib().d3f_tsdf_bounds_host, "d3f_tsdf_bounds_host", torch.device("cpu"), None, depth,
+                        frame_start, intrinsics, camera_to_volume, depth_scale, depth_max)
+
+
+def _tsdf_integrate(fn, name, device, stream, depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel,
+                    trunc, depth_scale, depth_max):
+    d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
+    V = fs.size - 1
+    o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
+    total = int(vol_start[-1])
+    td, tfs, tK, tM, to, tn, tvx, ttr, tvs = _on(device, d, fs, K, M, o, n, vx, tr, vol_start)
+    D = torch.empty(total, dtype=torch.float32, device=device)
+    w = torch.empty(total, dtype=torch.float32, device=device)
+    _native.check(fn(_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), _p(tvs), V, total,
+                     int(np.diff(vol_start).max()), _p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr), float(depth_scale),
+                     float(depth_max), _p(D), _p(w), stream), name)
+    return D, w, tvs
+
+
+def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
+                   depth_max=TSDF_DEPTH_MAX):
+    """Fuse depth frames into V dense volumes in ONE launch (d3f_tsdf_integrate; the rule is csrc/tsdf.hpp).
+
+    ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres; ``frame_start`` [V+1]: volume v
+    owns the frames ``[frame_start[v], frame_start[v+1])``; ``intrinsics`` [4] or [F,4] = fx, fy, cx, cy;
+    ``volume_to_camera`` [F,3,4] / [F,4,4] (f64 is rounded to f32 once, here); ``origin`` [V,3], ``dims`` [V,3] = nx,
+    ny, nz (host values), ``voxel`` and ``trunc`` a number or [V].  Returns device tensors ``(D f32 [total], w f32
+    [total], vol_start int64 [V+1])``: volume v is ``D[vol_start[v]:vol_start[v+1]].view(nz, ny, nx)``.  One thread owns
+    a voxel for all frames: written once, no atomics, bit-identical from run to run and to the host twin."""
+    dev = _tsdf_device()
+    with _region("tsdf_integrate"):
+        return _tsdf_integrate(_native.lib().d3f_tsdf_integrate, "d3f_tsdf_integrate", dev, _stream(), depth,
+                               frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
+                               depth_max)
+
+
+def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc,
+                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host): CPU tensors out, no GPU call."""
+    return _tsdf_integrate(_native.lib().d3f_tsdf_integrate_host, "d3f_tsdf_integrate_host", torch.device("cpu"), None,
+                           depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
+                           depth_max)
+
+
+def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
+    D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else
+            torch.as_tensor(a, dtype=torch.float32) for a in (D, w))
+    D, w = D.to(device).contiguous().view(-1), w.to(device).contiguous().view(-1)
+    V = int(np.asarray(dims.cpu() if isinstance(dims, torch.Tensor) else dims).reshape(-1, 3).shape[0])
+    o, n, vx, _, vol_start = _tsdf_volumes(origin, dims, voxel, V)
+    total = int(vol_start[-1])
+    if int(D.numel()) != total or int(w.numel()) != total:
+        raise ValueError("D and w must hold the %d voxels of dims, got %d and %d" % (total, D.numel(), w.numel()))
+    if total == 0 or V > TSDF_MAX_VOLUMES:
+        raise ValueError("between 1 and %d volumes per call" % TSDF_MAX_VOLUMES)
+    return (D, w, V, total) + tuple(_on(device, o, n, vx, vol_start))
+
+
+def _check_vol_start(vol_start, expected):
+    """A host ``vol_start`` is compared with the prefix of dims; a device one is not read back."""
+    if vol_start is None or (isinstance(vol_start, torch.Tensor) and vol_start.is_cuda):
+        return
+    if not np.array_equal(np.asarray(vol_start, dtype=np.int64).reshape(-1), expected.cpu().numpy()):
+        raise ValueError("vol_start is not the voxel prefix of dims")
+
+
+def tsdf_extract(D, w, vol_start, origin, dims, voxel, min_weight=1.0, capacity=None, return_status=False):
+    """The zero crossings of V volumes as one stacked cloud (d3f_tsdf_extract): ``(points f32 [M,3], point_start int64
+    [V+1])`` on the device, in the order volume, lattice index of the lower voxel, axis -- a pure function of the
+    volumes.  ``D``, ``w``, ``vol_start`` as ``tsdf_integrate`` returns them (a device ``vol_start`` is taken to be the
+    prefix of ``dims``, which are host values).  A voxel counts when ``w >= min_weight`` and ``|D| < 1``.
+
+    ONE read-back: the count pass and the scan run first, the number of points is read from the device, exactly that
+    many rows are allocated and the emit pass fills them.  With ``capacity`` given nothing is read back: the three steps
+    run back to back into ``capacity`` rows, points beyond it are dropped and TSDF_ST_OVERFLOW is set in the status word
+    (``return_status=True`` appends it as a device int32 [1] tensor; ``point_start`` is complete either way)."""
+    dev = _tsdf_device()
+    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, dev)
+    _check_vol_start(vol_start, tvs)
+    L = _native.lib()
+    nbytes = L.d3f_tsdf_extract_ws_bytes(total)
+    ws = _ws(nbytes, dev)
+    point_start = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counted = 0
+    with _region("tsdf_extract"):
+        if capacity is None:
+            _native.check(L.d3f_tsdf_extract_count(_p(D), _p(w), _p(tvs), _p(tn), V, total, float(min_weight),
+                                                   _p(point_start), _p(ws), nbytes, _stream()),
+                          "d3f_tsdf_extract_count")
+            capacity = int(point_start[V].item())          # the one read-back: the size of the result
+            counted = 1
+        points = torch.empty((int(capacity), 3), dtype=torch.float32, device=dev)
+        _native.check(L.d3f_tsdf_extract(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight),
+                                         counted, int(capacity), _p(points) if capacity else None, _p(point_start),
+                                         _p(status), _p(ws), nbytes, _stream()), "d3f_tsdf_extract")
+    return (points, point_start, status) if return_status else (points, point_start)
+
+
+def tsdf_extract_host(D, w, vol_start, origin, dims, voxel, min_weight=1.0, capacity=None, return_status=False):
+    """The host twin of ``tsdf_extract`` (d3f_tsdf_extract_host): CPU tensors out, no GPU call."""
+    cpu = torch.device("cpu")
+    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, cpu)
+    _check_vol_start(vol_start, tvs)
+    fn = _native.lib().d3f_tsdf_extract_host
+    point_start = torch.zeros(V + 1, dtype=torch.int64)
+    status = torch.zeros(1, dtype=torch.int32)
+    if capacity is None:
+        scratch = torch.zeros(1, dtype=torch.int32)
+        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), 0, None,
+                         _p(point_start), _p(scratch)), "d3f_tsdf_extract_host")
+        capacity = int(point_start[V])
+    points = torch.empty((int(capacity), 3), dtype=torch.float32)
+    _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), int(capacity),
+                     _p(points) if capacity else None, _p(point_start), _p(status)), "d3f_tsdf_extract_host")
+    return (points, point_start, status) if return_status else (points, point_start)
+
+
+def _lattice_axes(local, n, o, vx):
+    """f32 lattice coordinates (x, y, z) and integer (ix, iy, iz) of the local voxel indices ``local`` of a lattice."""
+    nx, ny = int(n[0]), int(n[1])
+    ix, row = local % nx, local // nx
+    iy, iz = row % ny, row // ny
+    xyz = tuple(np.float32(o[a]) + np.float32(vx) * i.astype(np.float32) for a, i in enumerate((ix, iy, iz)))
+    return xyz, (ix, iy, iz)
+
+
+def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
+               depth_max=TSDF_DEPTH_MAX, chunk=1 << 21):
+    """The contract of ``tsdf_integrate`` in NumPy: ``(D f32 [total], w f32 [total], vol_start int64 [V+1])``.  Every
+    product and sum is spelled out in f32 in the order of csrc/tsdf.hpp (no ``@``), so the result equals the kernel's
+    bit for bit.  ``chunk`` voxels are swept at a time."""
+    d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
+    V = fs.size - 1
+    o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
+    H, W = d.shape[1:]
+    f32 = np.float32
+    D_all = np.zeros(int(vol_start[-1]), dtype=f32)
+    w_all = np.zeros(int(vol_start[-1]), dtype=f32)
+    scale, dmax, half, one = f32(depth_scale), f32(depth_max), f32(0.5), f32(1.0)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            first, last = int(vol_start[v]), int(vol_start[v + 1])
+            for s in range(first, last, int(chunk)):
+                e = min(s + int(chunk), last)
+                (x, y, z), _ = _lattice_axes(np.arange(s, e, dtype=np.int64) - vol_start[v], n[v], o[v], vx[v])
+                D = np.zeros(e - s, dtype=f32)
+                w = np.zeros(e - s, dtype=f32)
+                for f in range(int(fs[v]), int(fs[v + 1])):
+                    m = M[f]
+                    px = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
+                    py = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
+                    pz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+                    ok = pz > 0
+                    u = np.floor(((K[f, 0] * px) / pz + K[f, 2]) + half)
+                    r = np.floor(((K[f, 1] * py) / pz + K[f, 3]) + half)
+                    ok &= (u >= 0) & (u < f32(W)) & (r >= 0) & (r < f32(H))
+                    raw = d[f][np.where(ok, r, 0).astype(np.int64), np.where(ok, u, 0).astype(np.int64)]
+                    dm = raw.astype(f32) / scale if raw.dtype == np.uint16 else raw
+                    ok &= (dm > 0) & ~(dm > dmax)
+                    sdf = dm - pz
+                    ok &= ~(sdf < -tr[v])
+                    t = np.minimum(one, sdf / tr[v])
+                    D = np.where(ok, (D * w + t) / (w + one), D)
+                    w = np.where(ok, w + one, w)
+                D_all[s:e], w_all[s:e] = D, w
+    return D_all, w_all, vol_start
+
+
+def _order_keys(a):
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+
+
+def _order_values(k):
+    k = np.asarray(k, dtype=np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7fffffff), ~k).astype(np.uint32).view(np.float32)
+
+
+def tsdf_bounds_numpy(depth, frame_start, intrinsics, camera_to_volume, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """The contract of ``tsdf_bounds`` in NumPy: f32 [V,6], equal to the kernel's bit for bit."""
+    d, fs, K, C = _tsdf_frames(depth, frame_start, intrinsics, camera_to_volume)
+    V = fs.size - 1
+    H, W = d.shape[1:]
+    f32 = np.float32
+    rows, cols = np.meshgrid(np.arange(H, dtype=f32), np.arange(W, dtype=f32), indexing='ij')
+    lo = np.full((V, 3), 0xff800000, dtype=np.uint32)
+    hi = np.full((V, 3), 0x007fffff, dtype=np.uint32)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            for f in range(int(fs[v]), int(fs[v + 1])):
+                dm = d[f].astype(f32) / f32(depth_scale) if d.dtype == np.uint16 else d[f]
+                ok = (dm > 0) & ~(dm > f32(depth_max))
+                if not ok.any():
+                    continue
+                X = ((cols - K[f, 2]) * dm) / K[f, 0]
+                Y = ((rows - K[f, 3]) * dm) / K[f, 1]
+                c = C[f]
+                for r in range(3):
+                    q = ((c[4 * r] * X + c[4 * r + 1] * Y) + c[4 * r + 2] * dm) + c[4 * r + 3]
+                    keys = _order_keys(q[ok])
+                    lo[v, r] = min(lo[v, r], keys.min())
+                    hi[v, r] = max(hi[v, r], keys.max())
+    return np.concatenate([_order_values(lo), _order_values(hi)], axis=1)
+
+
+def tsdf_extract_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
+    """The contract of ``tsdf_extract`` in NumPy: ``(points f32 [M,3], point_start int64 [V+1])``, equal to the
+    kernel's bit for bit and in order."""
+    D = np.ascontiguousarray(D, dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    V = int(np.asarray(dims).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    if D.size != int(vs[-1]) or w.size != D.size:
+        raise ValueError("D and w must hold the %d voxels of dims" % int(vs[-1]))
+    out, point_start = [], np.zeros(V + 1, dtype=np.int64)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            nx, ny, nz = (int(a) for a in n[v])
+            Dv = D[vs[v]:vs[v + 1]].reshape(nz, ny, nx)
+            ok = (w[vs[v]:vs[v + 1]].reshape(nz, ny, nx) >= np.float32(min_weight)) & (np.abs(Dv) < np.float32(1.0))
+            neg = Dv < 0
+            emit = np.zeros((nz, ny, nx, 3), dtype=bool)
+            frac = np.zeros((nz, ny, nx, 3), dtype=np.float32)
+            for a, (low, high) in enumerate(((np.s_[:, :, :-1], np.s_[:, :, 1:]), (np.s_[:, :-1, :], np.s_[:, 1:, :]),
+                                             (np.s_[:-1, :, :], np.s_[1:, :, :]))):
+                emit[low + (a,)] = ok[low] & ok[high] & (neg[low] != neg[high])
+                a0, a1 = np.abs(Dv[low]), np.abs(Dv[high])
+                frac[low + (a,)] = a0 / (a0 + a1)
+            local, axis = np.nonzero(emit.reshape(-1, 3))          # row-major: lattice index, then axis
+            xyz, _ = _lattice_axes(local.astype(np.int64), n[v], o[v], vx[v])
+            pts = np.stack(xyz, axis=1).astype(np.float32)
+            rows = np.arange(local.size)
+            pts[rows, axis] = pts[rows, axis] + vx[v] * frac.reshape(-1, 3)[local, axis]
+            out.append(pts)
+            point_start[v + 1] = point_start[v] + local.size
+    return (np.concatenate(out, 0) if out else np.zeros((0, 3), np.float32)), point_start
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

@@ -1034,6 +1034,63 @@ int d3f_pose_graph_edge_host(const double* Pi_host, const double* Pj_host, const
                              double* r_host, double* cost_host, double* Ji_host, double* Jj_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * TSDF fusion of depth frames into a batch of V dense volumes, and the extraction of their zero crossings as point
+ * clouds (csrc/tsdf.hpp states the rule in full; the reference has no such step).
+ * Volume v: lattice dims[v] = (nx, ny, nz), ix fastest; origin[v][3], voxel[v], trunc[v]; its voxels are
+ * [vol_start[v], vol_start[v+1]) of D / w (vol_start int64 [V+1] from 0 to total_voxels; every dim >= 1); it owns the
+ * frames [frame_start[v], frame_start[v+1]) (an empty range leaves the volume at D = 0, w = 0).
+ * Frames: depth [F, H, W] uint16 raw units (metres = raw / depth_scale) or f32 metres (depth_is_f32), intrinsics
+ * [F, 4] = fx, fy, cx, cy, volume_to_camera / camera_to_volume [F, 12] row-major 3x4 f32.  A pixel is valid when
+ * d > 0 and not d > depth_max.  All arithmetic f32 in the order of tsdf.hpp; device, host twin and the NumPy
+ * restatement agree bit for bit.
+ * d3f_tsdf_bounds: bounds [V, 6] = per volume the minimum (3) and maximum (3) of the back-projected valid pixels of
+ *   its frames in the volume's frame; +inf / -inf where there is none.  Integer-ordered min / max atomics: exact.
+ *   F <= 65535.
+ * d3f_tsdf_integrate: D, w f32 [total_voxels], written once by the thread that owns the voxel for all frames: no
+ *   atomics, nothing read back, bit-identical from run to run and for a volume alone or inside any batch.
+ *   max_volume_voxels: a host bound on the voxels of one volume (the launch is blocks of the largest volume x V, the
+ *   volume being the grid's second index: uniform, so its frames' matrices come through scalar loads); voxels of a
+ *   volume beyond it are not written.
+ * d3f_tsdf_extract: count per block of voxels, exclusive scan, emit at block offset + in-block rank: points
+ *   [capacity, 3] in the order volume, lattice index of the lower voxel, axis; point_start int64 [V+1].  A point at
+ *   or beyond `capacity` is not written and ORs D3F_TSDF_ST_OVERFLOW into *status (int32, zeroed by the caller);
+ *   point_start is complete either way.  d3f_tsdf_extract_count runs the first two steps alone and writes
+ *   point_start[V] (the number of points); a following d3f_tsdf_extract on the same volumes and workspace with
+ *   counted = 1 skips them.  vol_start is taken to be the prefix of dims; where they disagree the result is
+ *   unspecified, but nothing outside a volume's own voxel range is read.
+ * The _host twins take host pointers and make no GPU call.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_TSDF_MAX_VOLUMES 65535
+#define D3F_TSDF_ST_OVERFLOW 1
+int d3f_tsdf_bounds(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
+                    const float* intrinsics, const float* camera_to_volume, float depth_scale, float depth_max,
+                    float* bounds, void* stream);
+int d3f_tsdf_bounds_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
+                         const float* intrinsics, const float* camera_to_volume, float depth_scale, float depth_max,
+                         float* bounds, void* stream);
+int d3f_tsdf_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                       const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+                       const float* intrinsics, const float* volume_to_camera, const float* origin,
+                       const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max,
+                       float* D, float* w, void* stream);
+int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                            const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+                            const float* intrinsics, const float* volume_to_camera, const float* origin,
+                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
+                            float depth_max, float* D, float* w, void* stream);
+size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels);
+int d3f_tsdf_extract_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
+                           int64_t total_voxels, float min_weight, int64_t* point_start, void* ws, size_t ws_bytes,
+                           void* stream);
+int d3f_tsdf_extract(const float* D, const float* w, const int64_t* vol_start, const float* origin,
+                     const int32_t* dims, const float* voxel, int V, int64_t total_voxels, float min_weight,
+                     int counted, int64_t capacity, float* points, int64_t* point_start, int32_t* status, void* ws,
+                     size_t ws_bytes, void* stream);
+int d3f_tsdf_extract_host(const float* D, const float* w, const int64_t* vol_start, const float* origin,
+                          const int32_t* dims, const float* voxel, int V, int64_t total_voxels, float min_weight,
+                          int64_t capacity, float* points, int64_t* point_start, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
