@@ -13,16 +13,13 @@
 //              group offset + block offset + in-block rank (ballots + a prefix over the four waves).  No atomic
 //              decides a position.
 // The host twins run the same tsdf.hpp text on the CPU and make no GPU call.
-#include "common.hpp"
-#include "tsdf.hpp"
+#include "tsdf_batch.hpp"   // the batch, locate(), the argument checks, the two-level scan
 
 namespace {
 
 using namespace d3f::tsdf;
 
-constexpr int kThreads = 256;
 constexpr int kBoundsPixels = 8;          // pixels per thread of the bounds kernel
-constexpr int kScanThreads = 1024;       // block counts per group of the two-level scan
 
 // ---------------------------------------------------------------------------------------------------------- bounds
 __global__ void __launch_bounds__(kThreads) bounds_init_kernel(uint32_t* keys, int V) {
@@ -102,27 +99,6 @@ void bounds_host(const DepthT* images, int F, int H, int W, const int32_t* frame
 }
 
 // ------------------------------------------------------------------------------------------------------- integrate
-struct Volumes {            // the batch: device pointers on the device side, host pointers in the twins
-  const int64_t* vol_start;   // [V + 1] voxel prefix
-  const float* origin;        // [V, 3]
-  const int32_t* dims;        // [V, 3] = nx, ny, nz
-  const float* voxel;         // [V]
-  int V;
-  int64_t total;
-};
-
-// (ix, iy, iz) of local voxel index `local` of volume v
-__host__ __device__ inline void locate(const Volumes& b, int v, int64_t local, int& ix, int& iy, int& iz, int& nx,
-                                       int& ny, int& nz) {
-  nx = b.dims[3 * v] > 0 ? b.dims[3 * v] : 1;
-  ny = b.dims[3 * v + 1] > 0 ? b.dims[3 * v + 1] : 1;
-  nz = b.dims[3 * v + 2];
-  ix = (int)(local % nx);
-  const int64_t row = local / nx;
-  iy = (int)(row % ny);
-  iz = (int)(row / ny);
-}
-
 struct Frames {
   const void* images;           // [F, H, W] uint16 or f32
   const int32_t* frame_start;   // [V + 1]
@@ -162,20 +138,11 @@ __global__ void __launch_bounds__(kThreads) integrate_kernel(Volumes b, Frames f
 }
 
 // ------------------------------------------------------------------------------------------------------- extract
-struct ExtractWs {
-  int64_t* block_offset;   // [blocks] exclusive prefix of the counts inside the block's group
-  int64_t* group_total;    // [groups]
-  int64_t* group_offset;   // [groups] exclusive prefix of the group totals
-  int32_t* block_count;    // [blocks]
-  int64_t groups;
+struct ExtractWs : BlockScan {
   size_t bytes;
   ExtractWs(void* ws, int64_t blocks) {
     d3f::Carver c(ws);
-    groups = (blocks + kScanThreads - 1) / kScanThreads;
-    block_offset = c.take<int64_t>((size_t)blocks);
-    group_total = c.take<int64_t>((size_t)groups);
-    group_offset = c.take<int64_t>((size_t)groups);
-    block_count = c.take<int32_t>((size_t)blocks);
+    carve(c, blocks);
     bytes = d3f::align_up(c.off, 256);
   }
 };
@@ -210,54 +177,6 @@ __global__ void __launch_bounds__(kThreads) extract_count_kernel(Volumes b, cons
     for (int k = 0; k < kThreads / D3F_WAVE; ++k) s += wave_total[k];
     block_count[blockIdx.x] = s;
   }
-}
-
-// exclusive scan of one value per thread over the kScanThreads threads of a workgroup; returns the thread's prefix and
-// the sum of all in `total`
-__device__ inline int64_t workgroup_exclusive_scan(int64_t value, int64_t* lds, int64_t& total) {
-  const int t = (int)threadIdx.x;
-  lds[t] = value;
-  __syncthreads();
-  for (int off = 1; off < kScanThreads; off <<= 1) {
-    const int64_t add = t >= off ? lds[t - off] : 0;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  const int64_t inclusive = lds[t];
-  total = lds[kScanThreads - 1];
-  __syncthreads();
-  return inclusive - value;
-}
-
-// level 1: one workgroup per group of 1024 block counts (coalesced): offsets inside the group, and the group's total
-__global__ void __launch_bounds__(kScanThreads) extract_scan_groups_kernel(const int32_t* __restrict__ block_count,
-                                                                           int64_t blocks,
-                                                                           int64_t* __restrict__ block_offset,
-                                                                           int64_t* __restrict__ group_total) {
-  __shared__ int64_t lds[kScanThreads];
-  const int64_t i = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
-  int64_t total;
-  const int64_t prefix = workgroup_exclusive_scan(i < blocks ? (int64_t)block_count[i] : 0, lds, total);
-  if (i < blocks) block_offset[i] = prefix;
-  if (threadIdx.x == 0) group_total[blockIdx.x] = total;
-}
-
-// level 2: ONE workgroup scans the group totals, 1024 at a time with a carry.  *point_total = the number of points.
-__global__ void __launch_bounds__(kScanThreads) extract_scan_totals_kernel(const int64_t* __restrict__ group_total,
-                                                                           int64_t groups,
-                                                                           int64_t* __restrict__ group_offset,
-                                                                           int64_t* point_total) {
-  __shared__ int64_t lds[kScanThreads];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < groups; base += kScanThreads) {
-    const int64_t i = base + threadIdx.x;
-    int64_t total;
-    const int64_t prefix = workgroup_exclusive_scan(i < groups ? group_total[i] : 0, lds, total);
-    if (i < groups) group_offset[i] = carry + prefix;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *point_total = carry;
 }
 
 __global__ void __launch_bounds__(kThreads) extract_emit_kernel(Volumes b, const float* __restrict__ D,
@@ -303,10 +222,6 @@ __global__ void __launch_bounds__(kThreads) extract_emit_kernel(Volumes b, const
 }
 
 // -------------------------------------------------------------------------------------------------- argument checks
-bool batch_ok(int V, int64_t total) { return V >= 1 && V <= D3F_TSDF_MAX_VOLUMES && total >= 0; }
-
-int64_t extract_blocks(int64_t total) { return (total + kThreads - 1) / kThreads; }
-
 int frames_ok(const void* depth, int F, int H, int W, const int32_t* frame_start, const float* K, const float* X,
               float depth_scale, float depth_max) {
   if (F < 0 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30 || !frame_start || !(depth_scale > 0.0f) ||
@@ -315,27 +230,11 @@ int frames_ok(const void* depth, int F, int H, int W, const int32_t* frame_start
   return F == 0 || (depth && K && X);
 }
 
-// host pointers only: vol_start is the prefix of dims, from 0 to total
-bool host_layout_ok(const int64_t* vol_start, const int32_t* dims, int V, int64_t total) {
-  if (vol_start[0] != 0 || vol_start[V] != total) return false;
-  for (int v = 0; v < V; ++v)
-    if (dims[3 * v] < 1 || dims[3 * v + 1] < 1 || dims[3 * v + 2] < 1 ||
-        (int64_t)dims[3 * v] * dims[3 * v + 1] * dims[3 * v + 2] != vol_start[v + 1] - vol_start[v])
-      return false;
-  return true;
-}
-
 int run_extract_count(const Volumes& b, const float* D, const float* w, float min_weight, int64_t* point_start,
                       const ExtractWs& x, int64_t blocks, hipStream_t stream) {
   extract_count_kernel<<<(unsigned)blocks, kThreads, 0, stream>>>(b, D, w, min_weight, x.block_count);
   D3F_LAUNCH_CHECK();
-  extract_scan_groups_kernel<<<(unsigned)x.groups, kScanThreads, 0, stream>>>(x.block_count, blocks, x.block_offset,
-                                                                              x.group_total);
-  D3F_LAUNCH_CHECK();
-  extract_scan_totals_kernel<<<1, kScanThreads, 0, stream>>>(x.group_total, x.groups, x.group_offset,
-                                                             point_start + b.V);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
+  return run_block_scan(x, blocks, point_start + b.V, stream);
 }
 
 }  // namespace
@@ -393,7 +292,7 @@ int d3f_tsdf_integrate(const void* depth, int depth_is_f32, int F, int H, int W,
       !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
     return D3F_EINVAL;
   if (total_voxels == 0 || max_volume_voxels == 0) return D3F_OK;
-  const int64_t blocks = extract_blocks(max_volume_voxels);
+  const int64_t blocks = voxel_blocks(max_volume_voxels);
   if (!D || !w || blocks > 0x7fffffff) return D3F_EINVAL;
   const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
   const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
@@ -432,13 +331,13 @@ int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, i
 
 size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels) {
   if (total_voxels < 0) return 0;
-  return ExtractWs(nullptr, extract_blocks(total_voxels)).bytes + 256;
+  return ExtractWs(nullptr, voxel_blocks(total_voxels)).bytes + 256;
 }
 
 int d3f_tsdf_extract_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
                            int64_t total_voxels, float min_weight, int64_t* point_start, void* ws, size_t ws_bytes,
                            void* stream) {
-  const int64_t blocks = extract_blocks(total_voxels);
+  const int64_t blocks = voxel_blocks(total_voxels);
   if (!batch_ok(V, total_voxels) || total_voxels == 0 || blocks > 0x7fffffff || !D || !w || !vol_start || !dims ||
       !point_start || !ws)
     return D3F_EINVAL;
@@ -452,7 +351,7 @@ int d3f_tsdf_extract(const float* D, const float* w, const int64_t* vol_start, c
                      const int32_t* dims, const float* voxel, int V, int64_t total_voxels, float min_weight,
                      int counted, int64_t capacity, float* points, int64_t* point_start, int32_t* status, void* ws,
                      size_t ws_bytes, void* stream) {
-  const int64_t blocks = extract_blocks(total_voxels);
+  const int64_t blocks = voxel_blocks(total_voxels);
   if (!batch_ok(V, total_voxels) || total_voxels == 0 || blocks > 0x7fffffff || !D || !w || !vol_start || !origin ||
       !dims || !voxel || !point_start || !status || !ws || capacity < 0 || (capacity > 0 && !points))
     return D3F_EINVAL;

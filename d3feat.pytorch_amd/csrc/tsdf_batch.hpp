@@ -1,0 +1,126 @@
+// What tsdf.hip and tsdf_mesh.hip share beyond the rule of tsdf.hpp: the batch of volumes, the position of a voxel in
+// its lattice, the argument checks, and the two-level exclusive scan of per-block counts (count per block of 256
+// voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by .hip files only.
+#pragma once
+#include "common.hpp"
+#include "tsdf.hpp"
+
+namespace d3f {
+namespace tsdf {
+
+constexpr int kThreads = 256;
+constexpr int kScanThreads = 1024;       // block counts per group of the two-level scan
+
+struct Volumes {            // the batch: device pointers on the device side, host pointers in the twins
+  const int64_t* vol_start;   // [V + 1] voxel prefix
+  const float* origin;        // [V, 3]
+  const int32_t* dims;        // [V, 3] = nx, ny, nz
+  const float* voxel;         // [V]
+  int V;
+  int64_t total;
+};
+
+// (ix, iy, iz) of local voxel index `local` of volume v
+__host__ __device__ inline void locate(const Volumes& b, int v, int64_t local, int& ix, int& iy, int& iz, int& nx,
+                                       int& ny, int& nz) {
+  nx = b.dims[3 * v] > 0 ? b.dims[3 * v] : 1;
+  ny = b.dims[3 * v + 1] > 0 ? b.dims[3 * v + 1] : 1;
+  nz = b.dims[3 * v + 2];
+  ix = (int)(local % nx);
+  const int64_t row = local / nx;
+  iy = (int)(row % ny);
+  iz = (int)(row / ny);
+}
+
+// -------------------------------------------------------------------------------------------------- argument checks
+static inline bool batch_ok(int V, int64_t total) { return V >= 1 && V <= D3F_TSDF_MAX_VOLUMES && total >= 0; }
+
+static inline int64_t voxel_blocks(int64_t total) { return (total + kThreads - 1) / kThreads; }
+
+// host pointers only: vol_start is the prefix of dims, from 0 to total
+static inline bool host_layout_ok(const int64_t* vol_start, const int32_t* dims, int V, int64_t total) {
+  if (vol_start[0] != 0 || vol_start[V] != total) return false;
+  for (int v = 0; v < V; ++v)
+    if (dims[3 * v] < 1 || dims[3 * v + 1] < 1 || dims[3 * v + 2] < 1 ||
+        (int64_t)dims[3 * v] * dims[3 * v + 1] * dims[3 * v + 2] != vol_start[v + 1] - vol_start[v])
+      return false;
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------ scan
+// one exclusive scan of `blocks` int32 counts: its arrays in a workspace
+struct BlockScan {
+  int64_t* block_offset;   // [blocks] exclusive prefix of the counts inside the block's group
+  int64_t* group_total;    // [groups]
+  int64_t* group_offset;   // [groups] exclusive prefix of the group totals
+  int32_t* block_count;    // [blocks]
+  int64_t groups;
+  void carve(d3f::Carver& c, int64_t blocks) {
+    groups = (blocks + kScanThreads - 1) / kScanThreads;
+    block_offset = c.take<int64_t>((size_t)blocks);
+    group_total = c.take<int64_t>((size_t)groups);
+    group_offset = c.take<int64_t>((size_t)groups);
+    block_count = c.take<int32_t>((size_t)blocks);
+  }
+};
+
+// exclusive scan of one value per thread over the kScanThreads threads of a workgroup; returns the thread's prefix and
+// the sum of all in `total`
+__device__ inline int64_t workgroup_exclusive_scan(int64_t value, int64_t* lds, int64_t& total) {
+  const int t = (int)threadIdx.x;
+  lds[t] = value;
+  __syncthreads();
+  for (int off = 1; off < kScanThreads; off <<= 1) {
+    const int64_t add = t >= off ? lds[t - off] : 0;
+    __syncthreads();
+    lds[t] += add;
+    __syncthreads();
+  }
+  const int64_t inclusive = lds[t];
+  total = lds[kScanThreads - 1];
+  __syncthreads();
+  return inclusive - value;
+}
+
+// level 1: one workgroup per group of 1024 block counts (coalesced): offsets inside the group, and the group's total
+__global__ static void __launch_bounds__(kScanThreads) scan_groups_kernel(const int32_t* __restrict__ block_count,
+                                                                          int64_t blocks,
+                                                                          int64_t* __restrict__ block_offset,
+                                                                          int64_t* __restrict__ group_total) {
+  __shared__ int64_t lds[kScanThreads];
+  const int64_t i = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
+  int64_t total;
+  const int64_t prefix = workgroup_exclusive_scan(i < blocks ? (int64_t)block_count[i] : 0, lds, total);
+  if (i < blocks) block_offset[i] = prefix;
+  if (threadIdx.x == 0) group_total[blockIdx.x] = total;
+}
+
+// level 2: ONE workgroup scans the group totals, 1024 at a time with a carry.  *grand_total = the sum of all counts.
+__global__ static void __launch_bounds__(kScanThreads) scan_totals_kernel(const int64_t* __restrict__ group_total,
+                                                                          int64_t groups,
+                                                                          int64_t* __restrict__ group_offset,
+                                                                          int64_t* grand_total) {
+  __shared__ int64_t lds[kScanThreads];
+  int64_t carry = 0;
+  for (int64_t base = 0; base < groups; base += kScanThreads) {
+    const int64_t i = base + threadIdx.x;
+    int64_t total;
+    const int64_t prefix = workgroup_exclusive_scan(i < groups ? group_total[i] : 0, lds, total);
+    if (i < groups) group_offset[i] = carry + prefix;
+    carry += total;
+  }
+  if (threadIdx.x == 0) *grand_total = carry;
+}
+
+// both levels over s.block_count; *grand_total (device) receives the sum
+static inline int run_block_scan(const BlockScan& s, int64_t blocks, int64_t* grand_total, hipStream_t stream) {
+  scan_groups_kernel<<<(unsigned)s.groups, kScanThreads, 0, stream>>>(s.block_count, blocks, s.block_offset,
+                                                                      s.group_total);
+  D3F_LAUNCH_CHECK();
+  scan_totals_kernel<<<1, kScanThreads, 0, stream>>>(s.group_total, s.groups, s.group_offset, grand_total);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+}  // namespace tsdf
+}  // namespace d3f

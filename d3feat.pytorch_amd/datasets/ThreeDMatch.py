@@ -321,7 +321,8 @@ _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short':
 
 def read_ply_points(filename):
     """[N,3] float64 vertex positions of an ascii / binary PLY file (only the ``vertex`` element is read, which must
-    come first -- true for the 3DMatch fragments; list properties inside it are not supported)."""
+    come first -- true for the 3DMatch fragments; list properties inside it are not supported; a ``face`` element
+    after it, as ``fragments.write_ply_mesh`` writes, is skipped)."""
     with open(filename, 'rb') as f:
         if f.readline().strip() != b'ply':
             raise ValueError("%s: not a PLY file" % filename)

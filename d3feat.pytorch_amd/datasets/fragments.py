@@ -7,8 +7,8 @@ composed in.  The reference ships no code for either step (its fragments are the
 follow the rule of csrc/tsdf.hpp and are not claimed to equal that download.
 
 ``device='cuda'`` runs the HIP kernels (``ops.tsdf_bounds`` / ``tsdf_integrate`` / ``tsdf_extract``); ``device='cpu'``
-runs their NumPy restatement, which gives the same clouds bit for bit.  Normals and colour are not part of this
-(``ops.estimate_normals`` works on the result).
+runs their NumPy restatement, which gives the same clouds bit for bit.  ``mesh=True`` also gives the triangle mesh of
+each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has the rule).  Colour is not part of this.
 """
 import os
 import re
@@ -74,14 +74,17 @@ def _check_fits(dims, voxel, max_bytes, what):
                                 max_bytes))
 
 
-def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what):
-    """Clouds (list of f32 [N,3]) of the volumes that own the frame ranges ``frame_start`` of (depth, K, M, C)."""
+def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what,
+          mesh=False):
+    """Clouds (list of f32 [N,3]) of the volumes that own the frame ranges ``frame_start`` of (depth, K, M, C); with
+    ``mesh`` also their meshes, a list of (vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3]), from the same
+    integrated volumes."""
     from .. import ops
     cpu = _is_cpu(device)
     frame_start = np.asarray(frame_start, dtype=np.int64)
     V = frame_start.size - 1
     if V == 0:
-        return []
+        return ([], []) if mesh else []
     # the bounds in groups of volumes whose frames fit max_bytes too (one volume's frames at least): the depth frames
     # of a call are on the device next to its volumes
     frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
@@ -98,7 +101,7 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
     origin, dims = place_volumes(bounds, voxel)
     _check_fits(dims, voxel, int(max_bytes), what)        # before anything is launched
     sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
-    clouds, v = [], 0
+    clouds, meshes, v = [], [], 0
     while v < V:
         e, used = v, 0
         while e < V and (e == v or used + int(sizes[e]) <= int(max_bytes)):
@@ -110,18 +113,26 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
         if cpu:
             D, w, vs = ops.tsdf_numpy(*args)
             pts, ps = ops.tsdf_extract_numpy(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
+            m = ops.tsdf_mesh_numpy(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight) if mesh else None
         else:
             D, w, vs = ops.tsdf_integrate(*args)
             pts, ps = ops.tsdf_extract(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
             pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
+            m = ([t.cpu().numpy() for t in ops.tsdf_mesh(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)]
+                 if mesh else None)
             del D, w
         clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
+        if mesh:
+            vert, norm, face, vstart, fstart = m
+            meshes.extend((np.ascontiguousarray(vert[vstart[k]:vstart[k + 1]]),
+                           np.ascontiguousarray(norm[vstart[k]:vstart[k + 1]]),
+                           np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])) for k in range(e - v))
         v = e
-    return clouds
+    return (clouds, meshes) if mesh else clouds
 
 
 def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
-                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False):
     """``(clouds, fragment_poses)``: the fragments of a depth sequence, the 3DMatch way.
 
     ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or floating-point metres; ``intrinsics`` [4] =
@@ -133,7 +144,10 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     ``max_bytes``; one that does not fit alone raises ``ValueError`` before anything is launched.  The depth frames of
     a batch are uploaded with it (for the bounds, in groups that fit ``max_bytes`` as well): the device holds the
     volumes of one batch plus its frames, never the whole sequence.
-    ``clouds``: list of f32 [N_g,3] in the fragments' own frames; ``fragment_poses`` f64 [G,4,4]."""
+    ``clouds``: list of f32 [N_g,3] in the fragments' own frames; ``fragment_poses`` f64 [G,4,4].  ``mesh=True``
+    returns ``(clouds, fragment_poses, meshes)``: per fragment ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32
+    [Nf,3])`` in the fragment's frame, from the same integrated volume (``ops.tsdf_mesh``); the clouds and poses are
+    those of ``mesh=False``."""
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -144,18 +158,20 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     M = np.stack([rigid_inverse(poses[f]) @ poses[first[f]] for f in range(F)]) if F else np.zeros((0, 4, 4))
     C = np.stack([rigid_inverse(poses[first[f]]) @ poses[f] for f in range(F)]) if F else np.zeros((0, 4, 4))
     trunc = 5.0 * voxel if trunc is None else trunc
-    clouds = _fuse(depth, K, M, C, frame_start, float(voxel), float(trunc), depth_scale, depth_max, float(min_weight),
-                   device, max_bytes, "fragment")
-    return clouds, poses[frame_start[:-1]].copy()
+    fused = _fuse(depth, K, M, C, frame_start, float(voxel), float(trunc), depth_scale, depth_max, float(min_weight),
+                  device, max_bytes, "fragment", mesh)
+    fragment_poses = poses[frame_start[:-1]].copy()
+    return (fused[0], fragment_poses, fused[1]) if mesh else (fused, fragment_poses)
 
 
 def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
-               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False):
     """One cloud f32 [N,3] in the scene frame: all frames fused into ONE volume, frame f of fragment g entering with the
     camera-to-scene pose ``fragment_poses[g] @ inv(poses[first_g]) @ poses[f]``.  ``fragment_poses`` [G',4,4] is what
     ``multiway_registration`` returns; the frames of a fragment whose pose is not finite, or that has none (g >= G'),
     are left out.  The one volume takes all kept frames in one launch, so they are on the device together with it.
-    The other arguments are those of ``fuse_fragments``."""
+    The other arguments are those of ``fuse_fragments``.  ``mesh=True`` returns ``(cloud, (vertices, normals, faces))``,
+    the mesh of the same volume (empty arrays when no frame is kept)."""
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -169,12 +185,14 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
         keep.append(f)
         S.append(fp[g] @ rigid_inverse(poses[g * k]) @ poses[f])
     if not keep:
-        return np.zeros((0, 3), dtype=np.float32)
+        none = np.zeros((0, 3), dtype=np.float32)
+        return (none, (none.copy(), none.copy(), np.zeros((0, 3), dtype=np.int32))) if mesh else none
     S = np.stack(S)
     M = np.stack([rigid_inverse(s) for s in S])
     trunc = 5.0 * voxel if trunc is None else trunc
-    return _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
-                 depth_scale, depth_max, float(min_weight), device, max_bytes, "scene")[0]
+    fused = _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
+                  depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh)
+    return (fused[0][0], fused[1][0]) if mesh else fused[0]
 
 
 # ------------------------------------------------------------------------------------------------------ files
@@ -185,6 +203,30 @@ def write_ply_points(filename, points):
         f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
                  "property float z\nend_header\n" % p.shape[0]).encode('ascii'))
         f.write(p.tobytes())
+
+
+def write_ply_mesh(filename, vertices, faces, normals=None):
+    """Binary little-endian PLY of a triangle mesh: ``vertex`` with the float properties x, y, z (and nx, ny, nz when
+    ``normals`` is given) and ``face`` with ``list uchar int vertex_indices``.  ``read_ply_points`` of
+    ``datasets/ThreeDMatch.py`` reads the vertices of such a file as a cloud."""
+    cols = [np.ascontiguousarray(vertices, dtype='<f4').reshape(-1, 3)]
+    names = ['x', 'y', 'z']
+    if normals is not None:
+        cols.append(np.ascontiguousarray(normals, dtype='<f4').reshape(-1, 3))
+        names += ['nx', 'ny', 'nz']
+        if cols[1].shape != cols[0].shape:
+            raise ValueError("%d normals for %d vertices" % (cols[1].shape[0], cols[0].shape[0]))
+    f3 = np.asarray(faces).reshape(-1, 3)
+    if f3.size and (f3.min() < 0 or f3.max() >= cols[0].shape[0]):
+        raise ValueError("face entries must be vertex indices in 0..%d" % (cols[0].shape[0] - 1))
+    rows = np.zeros(f3.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    rows['n'], rows['i'] = 3, f3
+    with open(filename, 'wb') as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\n"
+                 "property list uchar int vertex_indices\nend_header\n"
+                 % (cols[0].shape[0], "".join("property float %s\n" % n for n in names), f3.shape[0])).encode('ascii'))
+        f.write(np.ascontiguousarray(np.concatenate(cols, axis=1)).tobytes())
+        f.write(rows.tobytes())
 
 
 def write_fragments(root, scene, clouds, poses, frames_per_fragment, seq='seq-01', num_frames=None):

@@ -3545,6 +3545,194 @@ def tsdf_extract_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# triangle meshes with normals from the TSDF volumes: dual contouring of the lattice (csrc/tsdf_mesh.hpp)
+# ---------------------------------------------------------------------------------------------------------------
+TSDF_ST_FACE_OVERFLOW = 2     # D3F_TSDF_ST_FACE_OVERFLOW
+
+
+def tsdf_mesh_bytes(total_voxels, vertices, faces):
+    """The bytes ``tsdf_mesh`` must move: D and w read by the count pass and again by the emit pass (8 bytes per voxel
+    each), the ballot word of every wave written once, and the rows written (vertices and normals 12 bytes each, a
+    triangle 12).  The neighbourhood reads are taken to come from cache and the scans are left out."""
+    return 16 * int(total_voxels) + (int(total_voxels) + 63) // 64 * 8 + 24 * int(vertices) + 12 * int(faces)
+
+
+def tsdf_mesh(D, w, vol_start, origin, dims, voxel, min_weight=1.0, vertex_capacity=None, face_capacity=None,
+              return_status=False):
+    """Triangle meshes of V volumes by dual contouring of the lattice (d3f_tsdf_mesh; the rule is csrc/tsdf_mesh.hpp):
+    ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3], vertex_start int64 [V+1], face_start int64 [V+1])``
+    on the device.  A cell whose 8 corners are valid (``w >= min_weight`` and ``|D| < 1``) and that has a crossing edge
+    owns one vertex, the mean of the points ``tsdf_extract`` emits for its crossing edges; its normal is the normalised
+    gradient of D over the cell and points to positive D (free space).  A crossing lattice edge whose four cells are
+    complete gives two triangles, counter-clockwise seen from outside.  Vertices come in the order volume, cell index;
+    faces in the order volume, lattice index of the edge's lower voxel, axis; face entries are vertex indices LOCAL to
+    their volume (global row = entry + ``vertex_start[v]``).  A pure function of the volumes, bit-identical from run to
+    run and to the host twin.  The arguments are those of ``tsdf_extract``.
+
+    ONE read-back: the count pass and the scans run first, the two totals are read from the device, exactly that many
+    rows are allocated and the emit pass fills them.  With BOTH capacities given nothing is read back; rows beyond a
+    capacity are dropped and TSDF_ST_OVERFLOW (vertices) / TSDF_ST_FACE_OVERFLOW (faces) is set in the status word
+    (``return_status=True`` appends it as a device int32 [1] tensor; both starts are complete either way)."""
+    dev = _tsdf_device()
+    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, dev)
+    _check_vol_start(vol_start, tvs)
+    L = _native.lib()
+    nbytes = L.d3f_tsdf_mesh_ws_bytes(total)
+    ws = _ws(nbytes, dev)
+    starts = torch.zeros((2, V + 1), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counted = 0
+    with _region("tsdf_mesh"):
+        if vertex_capacity is None or face_capacity is None:
+            _native.check(L.d3f_tsdf_mesh_count(_p(D), _p(w), _p(tvs), _p(tn), V, total, float(min_weight),
+                                                _p(starts[0]), _p(starts[1]), _p(ws), nbytes, _stream()),
+                          "d3f_tsdf_mesh_count")
+            nv, nf = starts[:, V].tolist()                 # the one read-back: the sizes of the result
+            vertex_capacity = nv if vertex_capacity is None else vertex_capacity
+            face_capacity = nf if face_capacity is None else face_capacity
+            counted = 1
+        nv, nf = int(vertex_capacity), int(face_capacity)
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        _native.check(L.d3f_tsdf_mesh(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight),
+                                      counted, nv, nf, _p(vertices) if nv else None, _p(normals) if nv else None,
+                                      _p(faces) if nf else None, _p(starts[0]), _p(starts[1]), _p(status), _p(ws),
+                                      nbytes, _stream()), "d3f_tsdf_mesh")
+    out = (vertices, normals, faces, starts[0], starts[1])
+    return out + (status,) if return_status else out
+
+
+def tsdf_mesh_host(D, w, vol_start, origin, dims, voxel, min_weight=1.0, vertex_capacity=None, face_capacity=None,
+                   return_status=False):
+    """The host twin of ``tsdf_mesh`` (d3f_tsdf_mesh_host): CPU tensors out, no GPU call."""
+    cpu = torch.device("cpu")
+    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, cpu)
+    _check_vol_start(vol_start, tvs)
+    fn = _native.lib().d3f_tsdf_mesh_host
+    vertex_start = torch.zeros(V + 1, dtype=torch.int64)
+    face_start = torch.zeros(V + 1, dtype=torch.int64)
+    status = torch.zeros(1, dtype=torch.int32)
+
+    def run(nv, nf, vertices, normals, faces, status):
+        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), nv, nf,
+                         _p(vertices) if nv else None, _p(normals) if nv else None, _p(faces) if nf else None,
+                         _p(vertex_start), _p(face_start), _p(status)), "d3f_tsdf_mesh_host")
+    if vertex_capacity is None or face_capacity is None:
+        run(0, 0, None, None, None, torch.zeros(1, dtype=torch.int32))          # the totals
+        vertex_capacity = int(vertex_start[V]) if vertex_capacity is None else vertex_capacity
+        face_capacity = int(face_start[V]) if face_capacity is None else face_capacity
+    nv, nf = int(vertex_capacity), int(face_capacity)
+    vertices = torch.empty((nv, 3), dtype=torch.float32)
+    normals = torch.empty((nv, 3), dtype=torch.float32)
+    faces = torch.empty((nf, 3), dtype=torch.int32)
+    run(nv, nf, vertices, normals, faces, status)
+    out = (vertices, normals, faces, vertex_start, face_start)
+    return out + (status,) if return_status else out
+
+
+_MESH_QUAD = ((-1, -1), (0, -1), (0, 0), (-1, 0))       # the cells q0..q3 around an edge, offsets on the axes (b, c)
+
+
+def tsdf_mesh_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
+    """The contract of ``tsdf_mesh`` in NumPy: ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3],
+    vertex_start int64 [V+1], face_start int64 [V+1])``, equal to the kernel's bit for bit and in order.  Every sum is
+    spelled out in f32 in the order of csrc/tsdf_mesh.hpp."""
+    f32 = np.float32
+    D = np.ascontiguousarray(D, dtype=f32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=f32).reshape(-1)
+    V = int(np.asarray(dims).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    if D.size != int(vs[-1]) or w.size != D.size:
+        raise ValueError("D and w must hold the %d voxels of dims" % int(vs[-1]))
+    if vol_start is not None and not np.array_equal(np.asarray(vol_start, dtype=np.int64).reshape(-1), vs):
+        raise ValueError("vol_start is not the voxel prefix of dims")
+    verts, norms, faces = [], [], []
+    vertex_start, face_start = np.zeros(V + 1, dtype=np.int64), np.zeros(V + 1, dtype=np.int64)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            nx, ny, nz = (int(a) for a in n[v])
+            Dv = D[vs[v]:vs[v + 1]].reshape(nz, ny, nx)
+            ok = (w[vs[v]:vs[v + 1]].reshape(nz, ny, nx) >= f32(min_weight)) & (np.abs(Dv) < f32(1.0))
+            neg = Dv < 0
+            lat3 = [np.broadcast_to((f32(o[v][a]) + f32(vx[v]) * np.arange(m).astype(f32)).reshape(shape), (nz, ny, nx))
+                    for a, (m, shape) in enumerate(((nx, (1, 1, -1)), (ny, (1, -1, 1)), (nz, (-1, 1, 1))))]
+
+            def corner(A, c):           # A at the corner c (bits 0..2 = offsets on x, y, z) of every cell
+                dx, dy, dz = c & 1, (c >> 1) & 1, (c >> 2) & 1
+                return A[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+            cells = (max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0))
+            complete = np.ones(cells, dtype=bool)
+            for c in range(8):
+                complete &= corner(ok, c)
+            k = np.zeros(cells, dtype=np.int64)
+            s = [np.zeros(cells, dtype=f32) for _ in range(3)]
+            g = []
+            for a in range(3):
+                a1, a2 = (1 if a == 0 else 0), (1 if a == 2 else 2)
+                total = None
+                for j in range(4):
+                    c0 = ((j & 1) << a1) | (((j >> 1) & 1) << a2)
+                    c1 = c0 | (1 << a)
+                    d0, d1 = corner(Dv, c0), corner(Dv, c1)
+                    diff = d1 - d0
+                    total = diff if total is None else total + diff
+                    cross = corner(neg, c0) != corner(neg, c1)
+                    a0, a1_ = np.abs(d0), np.abs(d1)
+                    p = [corner(lat3[r], c0) for r in range(3)]
+                    p[a] = p[a] + f32(vx[v]) * (a0 / (a0 + a1_))
+                    for r in range(3):
+                        s[r] = np.where(cross, np.where(k == 0, p[r], s[r] + p[r]), s[r])
+                    k = k + cross
+                g.append(total)
+            active = complete & (k > 0)
+            length = np.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            good = (length > 0) & np.isfinite(length)
+            sel = np.nonzero(active)                                  # row-major: the cell index
+            kf = k[sel].astype(f32)
+            verts.append(np.stack([s[r][sel] / kf for r in range(3)], axis=1).astype(f32).reshape(-1, 3))
+            norms.append(np.stack([np.where(good[sel], g[r][sel] / length[sel], f32(0.0)) for r in range(3)],
+                                  axis=1).astype(f32).reshape(-1, 3))
+            vertex_start[v + 1] = vertex_start[v] + sel[0].size
+            # faces: the complete cells and their vertex indices on the whole lattice, then the quads of every edge
+            C = np.zeros((nz, ny, nx), dtype=bool)
+            C[:cells[0], :cells[1], :cells[2]] = complete
+            index = np.full((nz, ny, nx), -1, dtype=np.int64)
+            act = np.zeros((nz, ny, nx), dtype=bool)
+            act[:cells[0], :cells[1], :cells[2]] = active
+            index[act] = np.arange(int(act.sum()))
+            local = np.arange(nz * ny * nx, dtype=np.int64).reshape(nz, ny, nx)
+            keys, tris = [], []
+            for a in range(3):
+                b, c = (a + 1) % 3, (a + 2) % 3
+                n_abc = (nx, ny, nz)
+                rng = [slice(0, None)] * 3                            # the voxels e that can have all four cells
+                rng[b], rng[c] = slice(1, None), slice(1, None)
+                rng[a] = slice(0, n_abc[a] - 1)
+                e = (rng[2], rng[1], rng[0])                          # arrays are [z, y, x]
+
+                def shifted(A, db, dc):
+                    r = list(rng)
+                    r[b] = slice(1 + db, n_abc[b] + db)
+                    r[c] = slice(1 + dc, n_abc[c] + dc)
+                    return A[r[2], r[1], r[0]]
+                up = list(rng)
+                up[a] = slice(1, n_abc[a])
+                quad = neg[e] != neg[up[2], up[1], up[0]]
+                for db, dc in _MESH_QUAD:
+                    quad = quad & shifted(C, db, dc)
+                q = np.stack([shifted(index, db, dc)[quad] for db, dc in _MESH_QUAD], axis=1)      # [m, 4]
+                inside = neg[e][quad][:, None]
+                tris.append(np.where(inside, q[:, [0, 1, 2, 0, 2, 3]], q[:, [3, 2, 1, 3, 1, 0]]))
+                keys.append(local[e][quad] * 3 + a)
+            order = np.argsort(np.concatenate(keys), kind='stable')          # lattice index of e, then axis
+            faces.append(np.concatenate(tris, 0)[order].reshape(-1, 3).astype(np.int32))
+            face_start[v + 1] = face_start[v] + faces[-1].shape[0]
+    cat = np.concatenate
+    return cat(verts, 0), cat(norms, 0), cat(faces, 0), vertex_start, face_start
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

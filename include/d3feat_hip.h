@@ -1091,6 +1091,42 @@ int d3f_tsdf_extract_host(const float* D, const float* w, const int64_t* vol_sta
                           int64_t capacity, float* points, int64_t* point_start, int32_t* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * Triangle meshes with normals from the same batch of TSDF volumes: dual contouring of the lattice ("naive surface
+ * nets"; csrc/tsdf_mesh.hpp states the rule in full, in the terms of csrc/tsdf.hpp; the reference has no such step).
+ * The arguments D, w, vol_start, origin, dims, voxel, V, total_voxels and min_weight are those of d3f_tsdf_extract.
+ * A cell (the cube above a voxel) whose 8 corners are valid and that has a crossing edge owns one vertex: the mean of
+ * the points d3f_tsdf_extract emits for its crossing edges, with the normalised gradient of D over the cell as its
+ * normal (towards positive D: free space).  A crossing lattice edge whose four cells are complete emits a quad as two
+ * triangles, counter-clockwise seen from positive D.  All arithmetic f32 in the order of tsdf_mesh.hpp; device, host
+ * twin and the NumPy restatement agree bit for bit.
+ * d3f_tsdf_mesh: count per block of voxels (vertices and triangles in one pass, keeping one bit per voxel), exclusive
+ *   scans, emit at block offset + in-block rank: vertices and normals f32 [vertex_capacity, 3] in the order volume, cell
+ *   index; faces int32 [face_capacity, 3] in the order volume, lattice index of the edge's lower voxel, axis, a quad's
+ *   two triangles consecutive, their entries vertex indices LOCAL to the volume (global row = entry +
+ *   vertex_start[v]); vertex_start, face_start int64 [V+1].  A vertex at or beyond vertex_capacity is not written and
+ *   ORs D3F_TSDF_ST_OVERFLOW into *status (int32, zeroed by the caller), a triangle at or beyond face_capacity is not
+ *   written and ORs D3F_TSDF_ST_FACE_OVERFLOW; both starts are complete either way.  A volume with more than 2^31 - 1
+ *   vertices sets D3F_TSDF_ST_OVERFLOW instead of writing a wrapped index.  d3f_tsdf_mesh_count runs the count and the
+ *   scans alone and writes vertex_start[V] and face_start[V] (the totals); a following d3f_tsdf_mesh on the same
+ *   volumes and workspace with counted = 1 skips them.  Nothing outside a volume's own voxel range is read.
+ * d3f_tsdf_mesh_host takes host pointers and makes no GPU call.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_TSDF_ST_FACE_OVERFLOW 2
+size_t d3f_tsdf_mesh_ws_bytes(int64_t total_voxels);
+int d3f_tsdf_mesh_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
+                        int64_t total_voxels, float min_weight, int64_t* vertex_start, int64_t* face_start, void* ws,
+                        size_t ws_bytes, void* stream);
+int d3f_tsdf_mesh(const float* D, const float* w, const int64_t* vol_start, const float* origin, const int32_t* dims,
+                  const float* voxel, int V, int64_t total_voxels, float min_weight, int counted,
+                  int64_t vertex_capacity, int64_t face_capacity, float* vertices, float* normals, int32_t* faces,
+                  int64_t* vertex_start, int64_t* face_start, int32_t* status, void* ws, size_t ws_bytes,
+                  void* stream);
+int d3f_tsdf_mesh_host(const float* D, const float* w, const int64_t* vol_start, const float* origin,
+                       const int32_t* dims, const float* voxel, int V, int64_t total_voxels, float min_weight,
+                       int64_t vertex_capacity, int64_t face_capacity, float* vertices, float* normals, int32_t* faces,
+                       int64_t* vertex_start, int64_t* face_start, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
