@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libd3feat_hip.so")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
-           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip"]
+           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -211,6 +211,24 @@ SIGNATURES = {
     "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
                               _vp]),
     "d3f_tsdf_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, _vp, _vp, _vp]),
+    "d3f_tsdf_sparse_mark": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _vp,
+                                  _vp]),
+    "d3f_tsdf_sparse_mark_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f,
+                                       _vp]),
+    "d3f_tsdf_sparse_index_ws_bytes": (_sz, [C.c_int64]),
+    "d3f_tsdf_sparse_index": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_tsdf_sparse_index_host": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
+    "d3f_tsdf_sparse_integrate": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f,
+                                       _f, _vp, _vp, _vp]),
+    "d3f_tsdf_sparse_integrate_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
+                                            _f, _f, _vp, _vp]),
+    "d3f_tsdf_sparse_extract_ws_bytes": (_sz, [C.c_int64]),
+    "d3f_tsdf_sparse_extract_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _sz,
+                                           _vp]),
+    "d3f_tsdf_sparse_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
+                                     C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_tsdf_sparse_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
+                                          C.c_int64, _vp, _vp, _vp]),
     "d3f_tsdf_mesh_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_mesh_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,

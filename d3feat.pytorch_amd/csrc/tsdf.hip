@@ -13,7 +13,7 @@
 //              group offset + block offset + in-block rank (ballots + a prefix over the four waves).  No atomic
 //              decides a position.
 // The host twins run the same tsdf.hpp text on the CPU and make no GPU call.
-#include "tsdf_batch.hpp"   // the batch, locate(), the argument checks, the two-level scan
+#include "tsdf_batch.hpp"   // the batch, the frames, locate(), the argument checks, the two-level scan
 
 namespace {
 
@@ -99,16 +99,6 @@ void bounds_host(const DepthT* images, int F, int H, int W, const int32_t* frame
 }
 
 // ------------------------------------------------------------------------------------------------------- integrate
-struct Frames {
-  const void* images;           // [F, H, W] uint16 or f32
-  const int32_t* frame_start;   // [V + 1]
-  const float* K;               // [F, 4]
-  const float* M;               // [F, 12] volume -> camera
-  const float* trunc;           // [V]
-  int F, H, W;
-  float depth_scale, depth_max;
-};
-
 template <typename DepthT>
 __host__ __device__ inline void fuse_voxel(const Volumes& b, const Frames& fr, int v, int64_t local, float& D,
                                            float& w) {
@@ -222,14 +212,6 @@ __global__ void __launch_bounds__(kThreads) extract_emit_kernel(Volumes b, const
 }
 
 // -------------------------------------------------------------------------------------------------- argument checks
-int frames_ok(const void* depth, int F, int H, int W, const int32_t* frame_start, const float* K, const float* X,
-              float depth_scale, float depth_max) {
-  if (F < 0 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30 || !frame_start || !(depth_scale > 0.0f) ||
-      !(depth_max > 0.0f))
-    return 0;
-  return F == 0 || (depth && K && X);
-}
-
 int run_extract_count(const Volumes& b, const float* D, const float* w, float min_weight, int64_t* point_start,
                       const ExtractWs& x, int64_t blocks, hipStream_t stream) {
   extract_count_kernel<<<(unsigned)blocks, kThreads, 0, stream>>>(b, D, w, min_weight, x.block_count);

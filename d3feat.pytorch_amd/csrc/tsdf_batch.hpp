@@ -1,6 +1,7 @@
-// What tsdf.hip and tsdf_mesh.hip share beyond the rule of tsdf.hpp: the batch of volumes, the position of a voxel in
-// its lattice, the argument checks, and the two-level exclusive scan of per-block counts (count per block of 256
-// voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by .hip files only.
+// What tsdf.hip, tsdf_mesh.hip and tsdf_sparse.hip share beyond the rule of tsdf.hpp: the batch of volumes and its
+// frames, the position of a voxel in its lattice, the argument checks, and the two-level exclusive scan of per-block
+// counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by
+// .hip files only.
 #pragma once
 #include "common.hpp"
 #include "tsdf.hpp"
@@ -20,6 +21,16 @@ struct Volumes {            // the batch: device pointers on the device side, ho
   int64_t total;
 };
 
+struct Frames {             // the depth frames of a batch
+  const void* images;           // [F, H, W] uint16 or f32
+  const int32_t* frame_start;   // [V + 1]
+  const float* K;               // [F, 4]
+  const float* M;               // [F, 12] volume -> camera (camera -> volume where a kernel back-projects)
+  const float* trunc;           // [V]
+  int F, H, W;
+  float depth_scale, depth_max;
+};
+
 // (ix, iy, iz) of local voxel index `local` of volume v
 __host__ __device__ inline void locate(const Volumes& b, int v, int64_t local, int& ix, int& iy, int& iz, int& nx,
                                        int& ny, int& nz) {
@@ -34,6 +45,14 @@ __host__ __device__ inline void locate(const Volumes& b, int v, int64_t local, i
 
 // -------------------------------------------------------------------------------------------------- argument checks
 static inline bool batch_ok(int V, int64_t total) { return V >= 1 && V <= D3F_TSDF_MAX_VOLUMES && total >= 0; }
+
+static inline int frames_ok(const void* depth, int F, int H, int W, const int32_t* frame_start, const float* K,
+                            const float* X, float depth_scale, float depth_max) {
+  if (F < 0 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30 || !frame_start || !(depth_scale > 0.0f) ||
+      !(depth_max > 0.0f))
+    return 0;
+  return F == 0 || (depth && K && X);
+}
 
 static inline int64_t voxel_blocks(int64_t total) { return (total + kThreads - 1) / kThreads; }
 

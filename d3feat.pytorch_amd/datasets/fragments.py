@@ -8,7 +8,10 @@ follow the rule of csrc/tsdf.hpp and are not claimed to equal that download.
 
 ``device='cuda'`` runs the HIP kernels (``ops.tsdf_bounds`` / ``tsdf_integrate`` / ``tsdf_extract``); ``device='cpu'``
 runs their NumPy restatement, which gives the same clouds bit for bit.  ``mesh=True`` also gives the triangle mesh of
-each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has the rule).  Colour is not part of this.
+each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has the rule).  ``sparse=True`` keeps D and w
+only for the bricks of 8 x 8 x 8 voxels near a surface (``ops.tsdf_allocate`` / ``tsdf_integrate_sparse`` /
+``tsdf_extract_sparse``; csrc/tsdf_sparse.hpp has the rule): the same points, in the sparse order, from a fraction of
+the memory.  Colour is not part of this.
 """
 import os
 import re
@@ -64,6 +67,11 @@ def place_volumes(bounds, voxel):
     return origin, dims
 
 
+def _check_sparse(sparse, mesh):
+    if sparse and mesh:
+        raise ValueError("sparse=True gives no mesh: fuse with sparse=False, or ops.tsdf_densify a volume that fits")
+
+
 def _check_fits(dims, voxel, max_bytes, what):
     for v, n in enumerate(dims):
         nbytes = 8 * int(n[0]) * int(n[1]) * int(n[2])
@@ -74,11 +82,76 @@ def _check_fits(dims, voxel, max_bytes, what):
                                 max_bytes))
 
 
+def _frame_groups(frame_start, frame_bytes, max_bytes):
+    """(v, e) ranges of volumes whose frames fit ``max_bytes`` together (one volume's frames at least)."""
+    V, v = frame_start.size - 1, 0
+    while v < V:
+        e = v + 1
+        while e < V and int(frame_start[e + 1] - frame_start[v]) * frame_bytes <= int(max_bytes):
+            e += 1
+        yield v, e
+        v = e
+
+
+def _size_batches(sizes, max_bytes):
+    """(v, e) ranges of volumes whose ``sizes`` fit ``max_bytes`` together (one volume at least)."""
+    V, v = len(sizes), 0
+    while v < V:
+        e, used = v, 0
+        while e < V and (e == v or used + int(sizes[e]) <= int(max_bytes)):
+            used += int(sizes[e])
+            e += 1
+        yield v, e
+        v = e
+
+
+def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight, cpu,
+                 max_bytes, what):
+    """``_fuse`` on sparse volumes: the bricks of every volume first (in the frame groups of the bounds), so that a
+    volume whose pool and tables exceed ``max_bytes`` raises before any integration; then batches by the sparse
+    sizes."""
+    from .. import ops
+    V = frame_start.size - 1
+    allocate = ops.tsdf_allocate_numpy if cpu else ops.tsdf_allocate
+    frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
+
+    def tables(v, e):
+        lo, hi = int(frame_start[v]), int(frame_start[e])
+        return allocate(depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], C[lo:hi], origin[v:e], dims[v:e], voxel,
+                        trunc, depth_scale, depth_max)
+    sizes, kept = np.zeros(V, dtype=np.int64), {}
+    for v, e in _frame_groups(frame_start, frame_bytes, max_bytes):
+        sv = kept[(v, e)] = tables(v, e)                  # the tables are small: kept for a batch of the same volumes
+        for k in range(v, e):
+            sizes[k] = ops.tsdf_sparse_bytes(sv, k - v)
+            if sizes[k] > max_bytes:
+                n, start = dims[k], ops._host_array(sv.brick_start)
+                raise ValueError("%s %d: the %d allocated bricks (of %d) of a volume of %d x %d x %d voxels of %g m "
+                                 "take %d bytes, more than max_bytes = %d: raise max_bytes or the voxel size"
+                                 % (what, k, start[k - v + 1] - start[k - v], np.diff(sv.lattice_start)[k - v], n[0],
+                                    n[1], n[2], voxel, sizes[k], max_bytes))
+    clouds = []
+    for v, e in _size_batches(sizes, max_bytes):
+        lo, hi = int(frame_start[v]), int(frame_start[e])
+        frames = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi])
+        sv = kept.pop((v, e), None) or tables(v, e)
+        if cpu:
+            D, w = ops.tsdf_sparse_numpy(*frames, sv, trunc, depth_scale, depth_max)
+            pts, ps = ops.tsdf_extract_sparse_numpy(D, w, sv, min_weight)
+        else:
+            D, w = ops.tsdf_integrate_sparse(*frames, sv, trunc, depth_scale, depth_max)
+            pts, ps = ops.tsdf_extract_sparse(D, w, sv, min_weight)
+            pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
+            del D, w
+        clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
+    return clouds
+
+
 def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what,
-          mesh=False):
+          mesh=False, sparse=False):
     """Clouds (list of f32 [N,3]) of the volumes that own the frame ranges ``frame_start`` of (depth, K, M, C); with
     ``mesh`` also their meshes, a list of (vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3]), from the same
-    integrated volumes."""
+    integrated volumes; with ``sparse`` from sparse volumes (``_fuse_sparse``)."""
     from .. import ops
     cpu = _is_cpu(device)
     frame_start = np.asarray(frame_start, dtype=np.int64)
@@ -88,25 +161,20 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
     # the bounds in groups of volumes whose frames fit max_bytes too (one volume's frames at least): the depth frames
     # of a call are on the device next to its volumes
     frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
-    bounds, v = [], 0
-    while v < V:
-        e = v + 1
-        while e < V and int(frame_start[e + 1] - frame_start[v]) * frame_bytes <= int(max_bytes):
-            e += 1
+    bounds = []
+    for v, e in _frame_groups(frame_start, frame_bytes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
         args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], C[lo:hi], depth_scale, depth_max)
         bounds.append(ops.tsdf_bounds_numpy(*args) if cpu else ops.tsdf_bounds(*args).cpu().numpy())
-        v = e
     bounds = np.concatenate(bounds, 0)
     origin, dims = place_volumes(bounds, voxel)
+    if sparse:
+        return _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight,
+                            cpu, int(max_bytes), what)
     _check_fits(dims, voxel, int(max_bytes), what)        # before anything is launched
     sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
-    clouds, meshes, v = [], [], 0
-    while v < V:
-        e, used = v, 0
-        while e < V and (e == v or used + int(sizes[e]) <= int(max_bytes)):
-            used += int(sizes[e])
-            e += 1
+    clouds, meshes = [], []
+    for v, e in _size_batches(sizes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
         args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi], origin[v:e], dims[v:e], voxel, trunc,
                 depth_scale, depth_max)
@@ -127,12 +195,12 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
             meshes.extend((np.ascontiguousarray(vert[vstart[k]:vstart[k + 1]]),
                            np.ascontiguousarray(norm[vstart[k]:vstart[k + 1]]),
                            np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])) for k in range(e - v))
-        v = e
     return (clouds, meshes) if mesh else clouds
 
 
 def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
-                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False):
+                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False,
+                   sparse=False):
     """``(clouds, fragment_poses)``: the fragments of a depth sequence, the 3DMatch way.
 
     ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or floating-point metres; ``intrinsics`` [4] =
@@ -147,7 +215,11 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     ``clouds``: list of f32 [N_g,3] in the fragments' own frames; ``fragment_poses`` f64 [G,4,4].  ``mesh=True``
     returns ``(clouds, fragment_poses, meshes)``: per fragment ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32
     [Nf,3])`` in the fragment's frame, from the same integrated volume (``ops.tsdf_mesh``); the clouds and poses are
-    those of ``mesh=False``."""
+    those of ``mesh=False``.  ``sparse=True`` fuses into sparse volumes (csrc/tsdf_sparse.hpp): every volume's bricks
+    are allocated first, ``max_bytes`` bounds the pools and tables of a batch (``ops.tsdf_sparse_bytes``) instead of the
+    dense volumes, and each cloud holds the rows of ``sparse=False`` bit for bit in the sparse order (brick in lattice
+    order, slot, axis).  There is no sparse mesh: ``sparse=True`` with ``mesh=True`` raises ``ValueError``."""
+    _check_sparse(sparse, mesh)
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -159,19 +231,22 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     C = np.stack([rigid_inverse(poses[first[f]]) @ poses[f] for f in range(F)]) if F else np.zeros((0, 4, 4))
     trunc = 5.0 * voxel if trunc is None else trunc
     fused = _fuse(depth, K, M, C, frame_start, float(voxel), float(trunc), depth_scale, depth_max, float(min_weight),
-                  device, max_bytes, "fragment", mesh)
+                  device, max_bytes, "fragment", mesh, sparse)
     fragment_poses = poses[frame_start[:-1]].copy()
     return (fused[0], fragment_poses, fused[1]) if mesh else (fused, fragment_poses)
 
 
 def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
-               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False):
+               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False,
+               sparse=False):
     """One cloud f32 [N,3] in the scene frame: all frames fused into ONE volume, frame f of fragment g entering with the
     camera-to-scene pose ``fragment_poses[g] @ inv(poses[first_g]) @ poses[f]``.  ``fragment_poses`` [G',4,4] is what
     ``multiway_registration`` returns; the frames of a fragment whose pose is not finite, or that has none (g >= G'),
     are left out.  The one volume takes all kept frames in one launch, so they are on the device together with it.
     The other arguments are those of ``fuse_fragments``.  ``mesh=True`` returns ``(cloud, (vertices, normals, faces))``,
-    the mesh of the same volume (empty arrays when no frame is kept)."""
+    the mesh of the same volume (empty arrays when no frame is kept).  ``sparse=True`` as for ``fuse_fragments``: the
+    one volume is sparse, so a scene whose dense volume exceeds ``max_bytes`` fits when its allocated bricks do."""
+    _check_sparse(sparse, mesh)
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -191,7 +266,7 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
     M = np.stack([rigid_inverse(s) for s in S])
     trunc = 5.0 * voxel if trunc is None else trunc
     fused = _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
-                  depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh)
+                  depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh, sparse)
     return (fused[0][0], fused[1][0]) if mesh else fused[0]
 
 

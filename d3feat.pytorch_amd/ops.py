@@ -3432,6 +3432,35 @@ def _lattice_axes(local, n, o, vx):
     return xyz, (ix, iy, iz)
 
 
+def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max):
+    """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1)."""
+    x, y, z = xyz
+    H, W = d.shape[1:]
+    f32 = np.float32
+    scale, dmax, half, one = f32(depth_scale), f32(depth_max), f32(0.5), f32(1.0)
+    D = np.zeros(x.shape, dtype=f32)
+    w = np.zeros(x.shape, dtype=f32)
+    with np.errstate(all='ignore'):
+        for f in range(f0, f1):
+            m = M[f]
+            px = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
+            py = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
+            pz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+            ok = pz > 0
+            u = np.floor(((K[f, 0] * px) / pz + K[f, 2]) + half)
+            r = np.floor(((K[f, 1] * py) / pz + K[f, 3]) + half)
+            ok &= (u >= 0) & (u < f32(W)) & (r >= 0) & (r < f32(H))
+            raw = d[f][np.where(ok, r, 0).astype(np.int64), np.where(ok, u, 0).astype(np.int64)]
+            dm = raw.astype(f32) / scale if raw.dtype == np.uint16 else raw
+            ok &= (dm > 0) & ~(dm > dmax)
+            sdf = dm - pz
+            ok &= ~(sdf < -trunc)
+            t = np.minimum(one, sdf / trunc)
+            D = np.where(ok, (D * w + t) / (w + one), D)
+            w = np.where(ok, w + one, w)
+    return D, w
+
+
 def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
                depth_max=TSDF_DEPTH_MAX, chunk=1 << 21):
     """The contract of ``tsdf_integrate`` in NumPy: ``(D f32 [total], w f32 [total], vol_start int64 [V+1])``.  Every
@@ -3440,37 +3469,15 @@ def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, v
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
-    H, W = d.shape[1:]
-    f32 = np.float32
-    D_all = np.zeros(int(vol_start[-1]), dtype=f32)
-    w_all = np.zeros(int(vol_start[-1]), dtype=f32)
-    scale, dmax, half, one = f32(depth_scale), f32(depth_max), f32(0.5), f32(1.0)
-    with np.errstate(all='ignore'):
-        for v in range(V):
-            first, last = int(vol_start[v]), int(vol_start[v + 1])
-            for s in range(first, last, int(chunk)):
-                e = min(s + int(chunk), last)
-                (x, y, z), _ = _lattice_axes(np.arange(s, e, dtype=np.int64) - vol_start[v], n[v], o[v], vx[v])
-                D = np.zeros(e - s, dtype=f32)
-                w = np.zeros(e - s, dtype=f32)
-                for f in range(int(fs[v]), int(fs[v + 1])):
-                    m = M[f]
-                    px = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
-                    py = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
-                    pz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
-                    ok = pz > 0
-                    u = np.floor(((K[f, 0] * px) / pz + K[f, 2]) + half)
-                    r = np.floor(((K[f, 1] * py) / pz + K[f, 3]) + half)
-                    ok &= (u >= 0) & (u < f32(W)) & (r >= 0) & (r < f32(H))
-                    raw = d[f][np.where(ok, r, 0).astype(np.int64), np.where(ok, u, 0).astype(np.int64)]
-                    dm = raw.astype(f32) / scale if raw.dtype == np.uint16 else raw
-                    ok &= (dm > 0) & ~(dm > dmax)
-                    sdf = dm - pz
-                    ok &= ~(sdf < -tr[v])
-                    t = np.minimum(one, sdf / tr[v])
-                    D = np.where(ok, (D * w + t) / (w + one), D)
-                    w = np.where(ok, w + one, w)
-                D_all[s:e], w_all[s:e] = D, w
+    D_all = np.zeros(int(vol_start[-1]), dtype=np.float32)
+    w_all = np.zeros(int(vol_start[-1]), dtype=np.float32)
+    for v in range(V):
+        first, last = int(vol_start[v]), int(vol_start[v + 1])
+        for s in range(first, last, int(chunk)):
+            e = min(s + int(chunk), last)
+            xyz, _ = _lattice_axes(np.arange(s, e, dtype=np.int64) - vol_start[v], n[v], o[v], vx[v])
+            D_all[s:e], w_all[s:e] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v], depth_scale,
+                                                      depth_max)
     return D_all, w_all, vol_start
 
 
@@ -3541,6 +3548,399 @@ def tsdf_extract_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
             pts[rows, axis] = pts[rows, axis] + vx[v] * frac.reshape(-1, 3)[local, axis]
             out.append(pts)
             point_start[v + 1] = point_start[v] + local.size
+    return (np.concatenate(out, 0) if out else np.zeros((0, 3), np.float32)), point_start
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# sparse TSDF volumes: bricks of 8 x 8 x 8 voxels allocated only near a surface (csrc/tsdf_sparse.hpp)
+# ---------------------------------------------------------------------------------------------------------------
+TSDF_BRICK = 8                # voxels along a brick's edge
+TSDF_BRICK_VOXELS = 512
+
+
+class SparseVolumes(object):
+    """The tables of a batch of sparse volumes, as ``tsdf_allocate`` returns them: ``brick_index`` int32 [L] (per lattice
+    brick, bx fastest, volume after volume: its rank among the allocated bricks of its volume, or -1), ``brick_coord``
+    int32 [B,3] = (bx, by, bz) of the allocated bricks in pool order, ``brick_start`` int64 [V+1] (the prefix of the
+    allocated bricks over the volumes) -- device tensors from ``tsdf_allocate``, CPU tensors from the host twin, arrays
+    from the restatement -- and the host arrays ``origin`` f32 [V,3], ``dims`` int32 [V,3], ``voxel`` f32 [V].  The pool
+    row of lattice brick l of volume v is ``brick_start[v] + brick_index[lattice_start[v] + l]``."""
+    __slots__ = ('brick_index', 'brick_coord', 'brick_start', 'origin', 'dims', 'voxel')
+
+    def __init__(self, brick_index, brick_coord, brick_start, origin, dims, voxel):
+        self.brick_index, self.brick_coord, self.brick_start = brick_index, brick_coord, brick_start
+        self.origin, self.dims, self.voxel = origin, dims, voxel
+
+    @property
+    def volumes(self):
+        return int(self.dims.shape[0])
+
+    @property
+    def bricks(self):
+        return int(self.brick_coord.shape[0])
+
+    @property
+    def lattice_start(self):
+        """int64 [V+1] (host): the prefix of the volumes' brick lattices ceil(n / 8)^3."""
+        return _lattice_start(self.dims)
+
+
+def _lattice_start(dims):
+    nb = (np.asarray(dims, dtype=np.int64) + (TSDF_BRICK - 1)) // TSDF_BRICK
+    out = np.zeros(nb.shape[0] + 1, dtype=np.int64)
+    out[1:] = np.cumsum(nb[:, 0] * nb[:, 1] * nb[:, 2])
+    return out
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def tsdf_sparse_bytes(sv, volume=None):
+    """The bytes of a batch of sparse volumes: the pool (D and w, 8 bytes per slot of an allocated brick) plus the
+    tables (``brick_index``, ``brick_coord``, ``brick_start``).  ``volume``: of that volume alone."""
+    lattice, bricks, V = int(sv.lattice_start[-1]), sv.bricks, sv.volumes
+    if volume is not None:
+        lattice = int(np.diff(sv.lattice_start)[volume])
+        bricks, V = int(np.diff(_host_array(sv.brick_start))[volume]), 1
+    return 2 * 4 * TSDF_BRICK_VOXELS * bricks + 4 * lattice + 12 * bricks + 8 * (V + 1)
+
+
+def _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
+                   depth_scale, depth_max):
+    d, fs, K, C = _tsdf_frames(depth, frame_start, intrinsics, camera_to_volume)
+    V = fs.size - 1
+    o, n, vx, tr, _ = _tsdf_volumes(origin, dims, voxel, V, trunc)
+    ls = _lattice_start(n)
+    lattice = int(ls[-1])
+    if lattice > 0x7fffffff:
+        raise ValueError("the brick lattices of a call hold %d bricks, more than 2^31 - 1" % lattice)
+    if not host and d.shape[0] > 65535:
+        raise ValueError("at most 65535 frames per call")
+    td, tfs, tK, tC, to, tn, tvx, ttr, tls = _on(device, d, fs, K, C, o, n, vx, tr, ls)
+    flags = torch.empty(lattice, dtype=torch.int32, device=device)
+    brick_index = torch.empty(lattice, dtype=torch.int32, device=device)
+    coord = torch.empty((lattice, 3), dtype=torch.int32, device=device)
+    brick_start = torch.zeros(V + 1, dtype=torch.int64, device=device)
+    L = _native.lib()
+    frames = (_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tC),
+              _p(to), _p(tn), _p(tvx), _p(ttr), _p(tls), lattice, float(depth_scale), float(depth_max), _p(flags))
+    if host:
+        _native.check(L.d3f_tsdf_sparse_mark_host(*frames), "d3f_tsdf_sparse_mark_host")
+        _native.check(L.d3f_tsdf_sparse_index_host(_p(flags), _p(tls), _p(tn), V, lattice, _p(brick_index), _p(coord),
+                                                   _p(brick_start)), "d3f_tsdf_sparse_index_host")
+    else:
+        nbytes = L.d3f_tsdf_sparse_index_ws_bytes(lattice)
+        ws = _ws(nbytes, device)
+        _native.check(L.d3f_tsdf_sparse_mark(*(frames + (stream,))), "d3f_tsdf_sparse_mark")
+        _native.check(L.d3f_tsdf_sparse_index(_p(flags), _p(tls), _p(tn), V, lattice, _p(brick_index), _p(coord),
+                                              _p(brick_start), _p(ws), nbytes, stream), "d3f_tsdf_sparse_index")
+    bricks = int(brick_start[V].item())                    # the one read-back: the number of allocated bricks
+    return SparseVolumes(brick_index, coord[:bricks].clone(), brick_start, o, n, vx)
+
+
+def tsdf_allocate(depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc, depth_scale=1000.0,
+                  depth_max=TSDF_DEPTH_MAX):
+    """The bricks of V sparse volumes (d3f_tsdf_sparse_mark, d3f_tsdf_sparse_index; the rule is csrc/tsdf_sparse.hpp): a
+    ``SparseVolumes`` with device tables.  Every valid pixel of a volume's frames flags the bricks of 8 x 8 x 8 voxels
+    that the box of its footprint over ``[max(d - trunc, 0), d + trunc]``, widened by one voxel, touches; the flags are
+    scanned in lattice order.  The frame arguments are those of ``tsdf_bounds``, the volume arguments those of
+    ``tsdf_integrate``.  ONE read-back: the number of allocated bricks."""
+    dev = _tsdf_device()
+    with _region("tsdf_allocate"):
+        return _tsdf_allocate(False, dev, _stream(), depth, frame_start, intrinsics, camera_to_volume, origin, dims,
+                              voxel, trunc, depth_scale, depth_max)
+
+
+def tsdf_allocate_host(depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
+                       depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """The host twin of ``tsdf_allocate`` (d3f_tsdf_sparse_mark_host, d3f_tsdf_sparse_index_host): CPU tensors, no GPU
+    call."""
+    return _tsdf_allocate(True, torch.device("cpu"), None, depth, frame_start, intrinsics, camera_to_volume, origin,
+                          dims, voxel, trunc, depth_scale, depth_max)
+
+
+def _sparse_tables(sv, device):
+    """(lattice_start, brick_start, brick_index, brick_coord, origin, dims, voxel) of ``sv`` as tensors on ``device``."""
+    def tensor(a, dtype):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device=device, dtype=dtype).contiguous()
+    tls, to, tn, tvx = _on(device, sv.lattice_start, sv.origin, sv.dims, sv.voxel)
+    bi, bc, bs = tensor(sv.brick_index, torch.int32), tensor(sv.brick_coord, torch.int32), tensor(sv.brick_start,
+                                                                                                  torch.int64)
+    if (int(bi.numel()) != int(sv.lattice_start[-1]) or tuple(bc.shape) != (sv.bricks, 3) or
+            int(bs.numel()) != sv.volumes + 1):
+        raise ValueError("the tables of the sparse volumes do not fit their dims")
+    return tls, bs, bi, bc, to, tn, tvx
+
+
+def _tsdf_integrate_sparse(host, device, stream, depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
+                           depth_scale, depth_max):
+    d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
+    V = fs.size - 1
+    if V != sv.volumes:
+        raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
+    tr = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)[3]
+    td, tfs, tK, tM, ttr = _on(device, d, fs, K, M, tr)
+    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, device)
+    B = sv.bricks
+    D = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+    w = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+    args = (_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tM), _p(to),
+            _p(tn), _p(tvx), _p(ttr), _p(bs), _p(bc) if B else None, B, float(depth_scale), float(depth_max),
+            _p(D) if B else None, _p(w) if B else None)
+    L = _native.lib()
+    if host:
+        _native.check(L.d3f_tsdf_sparse_integrate_host(*args), "d3f_tsdf_sparse_integrate_host")
+    else:
+        _native.check(L.d3f_tsdf_sparse_integrate(*(args + (stream,))), "d3f_tsdf_sparse_integrate")
+    return D, w
+
+
+def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
+                          depth_max=TSDF_DEPTH_MAX):
+    """Fuse depth frames into the allocated bricks of ``sv`` in ONE launch (d3f_tsdf_sparse_integrate): device tensors
+    ``(D f32 [B,512], w f32 [B,512])``, row b the brick ``sv.brick_coord[b]``, voxel (ix, iy, iz) at slot ``(ix & 7) + 8
+    (iy & 7) + 64 (iz & 7)``.  Every slot inside the lattice holds what ``tsdf_integrate`` gives that voxel, bit for
+    bit; a slot beyond ``dims`` holds 0.  The frame arguments and ``trunc`` are those of ``tsdf_integrate``."""
+    dev = _tsdf_device()
+    with _region("tsdf_integrate_sparse"):
+        return _tsdf_integrate_sparse(False, dev, _stream(), depth, frame_start, intrinsics, volume_to_camera, sv,
+                                      trunc, depth_scale, depth_max)
+
+
+def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
+                               depth_max=TSDF_DEPTH_MAX):
+    """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host): CPU tensors out, no GPU call."""
+    return _tsdf_integrate_sparse(True, torch.device("cpu"), None, depth, frame_start, intrinsics, volume_to_camera,
+                                  sv, trunc, depth_scale, depth_max)
+
+
+def _sparse_pool(D, w, sv, device):
+    D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else
+            torch.as_tensor(a, dtype=torch.float32) for a in (D, w))
+    D, w = D.to(device).contiguous().view(-1), w.to(device).contiguous().view(-1)
+    if int(D.numel()) != sv.bricks * TSDF_BRICK_VOXELS or int(w.numel()) != int(D.numel()):
+        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks, got %d and %d"
+                         % (sv.bricks, D.numel(), w.numel()))
+    return D, w
+
+
+def tsdf_extract_sparse(D, w, sv, min_weight=1.0, capacity=None, return_status=False):
+    """The zero crossings of sparse volumes as one stacked cloud (d3f_tsdf_sparse_extract): ``(points f32 [M,3],
+    point_start int64 [V+1])`` on the device, in the order volume, brick in lattice order, slot, axis.  As a set of rows
+    they are ``tsdf_extract``'s points of the dense volumes, bit for bit.  ``D``, ``w`` as ``tsdf_integrate_sparse``
+    returns them; ``capacity``, ``return_status`` and the one read-back as for ``tsdf_extract``."""
+    dev = _tsdf_device()
+    D, w = _sparse_pool(D, w, sv, dev)
+    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, dev)
+    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
+    point_start = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:                                                 # nothing allocated: no kernel has anything to do
+        points = torch.empty((int(capacity or 0), 3), dtype=torch.float32, device=dev)
+        return (points, point_start, status) if return_status else (points, point_start)
+    L = _native.lib()
+    nbytes = L.d3f_tsdf_sparse_extract_ws_bytes(B)
+    ws = _ws(nbytes, dev)
+    counted = 0
+    with _region("tsdf_extract_sparse"):
+        if capacity is None:
+            _native.check(L.d3f_tsdf_sparse_extract_count(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(tn), V,
+                                                          lattice, B, float(min_weight), _p(point_start), _p(ws),
+                                                          nbytes, _stream()), "d3f_tsdf_sparse_extract_count")
+            capacity = int(point_start[V].item())          # the one read-back: the size of the result
+            counted = 1
+        points = torch.empty((int(capacity), 3), dtype=torch.float32, device=dev)
+        _native.check(L.d3f_tsdf_sparse_extract(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(to), _p(tn), _p(tvx),
+                                                V, lattice, B, float(min_weight), counted, int(capacity),
+                                                _p(points) if capacity else None, _p(point_start), _p(status), _p(ws),
+                                                nbytes, _stream()), "d3f_tsdf_sparse_extract")
+    return (points, point_start, status) if return_status else (points, point_start)
+
+
+def tsdf_extract_sparse_host(D, w, sv, min_weight=1.0, capacity=None, return_status=False):
+    """The host twin of ``tsdf_extract_sparse`` (d3f_tsdf_sparse_extract_host): CPU tensors out, no GPU call."""
+    cpu = torch.device("cpu")
+    D, w = _sparse_pool(D, w, sv, cpu)
+    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, cpu)
+    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
+    fn = _native.lib().d3f_tsdf_sparse_extract_host
+    point_start = torch.zeros(V + 1, dtype=torch.int64)
+    status = torch.zeros(1, dtype=torch.int32)
+    pool = (_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(bc) if B else None, _p(to), _p(tn),
+            _p(tvx), V, lattice, B, float(min_weight))
+    if capacity is None:
+        scratch = torch.zeros(1, dtype=torch.int32)
+        _native.check(fn(*(pool + (0, None, _p(point_start), _p(scratch)))), "d3f_tsdf_sparse_extract_host")
+        capacity = int(point_start[V])
+    points = torch.empty((int(capacity), 3), dtype=torch.float32)
+    _native.check(fn(*(pool + (int(capacity), _p(points) if capacity else None, _p(point_start), _p(status)))),
+                  "d3f_tsdf_sparse_extract_host")
+    return (points, point_start, status) if return_status else (points, point_start)
+
+
+def _slot_voxels(coord):
+    """int64 [B,512] x 3: the voxel (ix, iy, iz) of every slot of the bricks ``coord`` [B,3]."""
+    s = np.arange(TSDF_BRICK_VOXELS, dtype=np.int64)
+    inside = (s & 7, (s >> 3) & 7, s >> 6)
+    return tuple(coord[:, a, None].astype(np.int64) * TSDF_BRICK + inside[a][None, :] for a in range(3))
+
+
+def tsdf_densify(D, w, sv):
+    """A pool scattered into the dense layout of ``tsdf_integrate``: ``(D f32 [total], w f32 [total], vol_start int64
+    [V+1])``, zero outside the allocated bricks, by plain indexing (tensors in, tensors on the same device out; arrays
+    in, arrays out).  For tests, and for ``tsdf_mesh`` on a volume that fits."""
+    arrays = isinstance(D, np.ndarray)
+    dev = torch.device("cpu") if arrays else D.device
+    Dp, wp = _sparse_pool(D, w, sv, dev)
+    n = np.asarray(sv.dims, dtype=np.int64)
+    vol_start = np.zeros(sv.volumes + 1, dtype=np.int64)
+    vol_start[1:] = np.cumsum(n[:, 0] * n[:, 1] * n[:, 2])
+    coord, bs = _host_array(sv.brick_coord), _host_array(sv.brick_start)
+    vol = np.repeat(np.arange(sv.volumes), np.diff(bs))
+    ix, iy, iz = _slot_voxels(coord)
+    nv = n[vol]
+    exists = (ix < nv[:, 0, None]) & (iy < nv[:, 1, None]) & (iz < nv[:, 2, None])
+    at = vol_start[vol][:, None] + (iz * nv[:, 1, None] + iy) * nv[:, 0, None] + ix
+    src = torch.from_numpy(np.flatnonzero(exists.reshape(-1))).to(dev)
+    dst = torch.from_numpy(at[exists]).to(dev)
+    out = []
+    for pool in (Dp, wp):
+        dense = torch.zeros(int(vol_start[-1]), dtype=torch.float32, device=dev)
+        dense[dst] = pool[src]
+        out.append(dense.numpy() if arrays else dense)
+    return out[0], out[1], (vol_start if arrays else torch.from_numpy(vol_start).to(dev))
+
+
+def tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
+                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
+    """The contract of ``tsdf_allocate`` in NumPy: a ``SparseVolumes`` of arrays, equal to the kernels' tables.  Every
+    product and sum is spelled out in f32 in the order of csrc/tsdf_sparse.hpp."""
+    d, fs, K, C = _tsdf_frames(depth, frame_start, intrinsics, camera_to_volume)
+    V = fs.size - 1
+    o, n, vx, tr, _ = _tsdf_volumes(origin, dims, voxel, V, trunc)
+    H, W = d.shape[1:]
+    f32 = np.float32
+    half, one, zero = f32(0.5), f32(1.0), f32(0.0)
+    rows, cols = np.meshgrid(np.arange(H, dtype=f32), np.arange(W, dtype=f32), indexing='ij')
+    index, coords, brick_start = [], [], np.zeros(V + 1, dtype=np.int64)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            nb = (n[v].astype(np.int64) + (TSDF_BRICK - 1)) // TSDF_BRICK
+            flags = np.zeros((int(nb[2]), int(nb[1]), int(nb[0])), dtype=bool)
+            for f in range(int(fs[v]), int(fs[v + 1])):
+                dm = d[f].astype(f32) / f32(depth_scale) if d.dtype == np.uint16 else d[f]
+                ok = (dm > 0) & ~(dm > f32(depth_max))
+                near = dm - tr[v]
+                z = (np.where(near > 0, near, zero), dm + tr[v])
+                su = ((cols - half) - K[f, 2], (cols + half) - K[f, 2])
+                sv = ((rows - half) - K[f, 3], (rows + half) - K[f, 3])
+                c, lo, hi = C[f], None, None
+                for corner in range(8):
+                    zz = z[corner >> 2]
+                    X = (su[corner & 1] * zz) / K[f, 0]
+                    Y = (sv[(corner >> 1) & 1] * zz) / K[f, 1]
+                    q = [((c[4 * r] * X + c[4 * r + 1] * Y) + c[4 * r + 2] * zz) + c[4 * r + 3] for r in range(3)]
+                    lo = q if lo is None else [np.where(q[r] < lo[r], q[r], lo[r]) for r in range(3)]
+                    hi = q if hi is None else [np.where(q[r] > hi[r], q[r], hi[r]) for r in range(3)]
+                box = []
+                for r in range(3):
+                    last = f32(int(n[v, r]) - 1)
+                    flo = np.floor((lo[r] - o[v, r]) / vx[v]) - one
+                    fhi = np.floor((hi[r] - o[v, r]) / vx[v]) + one
+                    ok &= (fhi >= 0) & (flo <= last)
+                    box += [np.where(flo <= 0, zero, np.where(flo >= last, last, flo)),
+                            np.where(fhi <= 0, zero, np.where(fhi >= last, last, fhi))]
+                if not ok.any():
+                    continue
+                box = np.stack([b[ok] for b in box], axis=1).astype(np.int64)
+                box = np.minimum(box, n[v].astype(np.int64).repeat(2)[None, :] - 1) >> 3    # f32(n - 1) may round up
+                for x0, x1, y0, y1, z0, z1 in np.unique(box, axis=0):
+                    flags[z0:z1 + 1, y0:y1 + 1, x0:x1 + 1] = True
+            flat = flags.reshape(-1)
+            index.append(np.where(flat, np.cumsum(flat) - 1, -1).astype(np.int32))
+            bz, by, bx = np.nonzero(flags)                          # row-major: lattice order
+            coords.append(np.stack([bx, by, bz], axis=1).astype(np.int32))
+            brick_start[v + 1] = brick_start[v] + bx.size
+    return SparseVolumes(np.concatenate(index), np.concatenate(coords, 0).reshape(-1, 3), brick_start, o, n, vx)
+
+
+def tsdf_sparse_numpy(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
+                      depth_max=TSDF_DEPTH_MAX, chunk=1 << 12):
+    """The contract of ``tsdf_integrate_sparse`` in NumPy: ``(D f32 [B,512], w f32 [B,512])``, equal to the kernel's bit
+    for bit: ``tsdf_numpy``'s arithmetic on the slots of the allocated bricks, ``chunk`` bricks at a time."""
+    d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
+    V = fs.size - 1
+    if V != sv.volumes:
+        raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
+    o, n, vx, tr, _ = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)
+    coord, bs = _host_array(sv.brick_coord), _host_array(sv.brick_start)
+    D = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    w = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    for v in range(V):
+        for s in range(int(bs[v]), int(bs[v + 1]), int(chunk)):
+            e = min(s + int(chunk), int(bs[v + 1]))
+            i = _slot_voxels(coord[s:e])
+            exists = (i[0] < n[v, 0]) & (i[1] < n[v, 1]) & (i[2] < n[v, 2])
+            xyz = tuple(np.float32(o[v, a]) + np.float32(vx[v]) * i[a][exists].astype(np.float32) for a in range(3))
+            D[s:e][exists], w[s:e][exists] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v],
+                                                               depth_scale, depth_max)
+    return D, w
+
+
+def tsdf_extract_sparse_numpy(D, w, sv, min_weight=1.0):
+    """The contract of ``tsdf_extract_sparse`` in NumPy: ``(points f32 [M,3], point_start int64 [V+1])``, equal to the
+    kernel's bit for bit and in order."""
+    B, V = sv.bricks, sv.volumes
+    D = np.ascontiguousarray(_host_array(D), dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(_host_array(w), dtype=np.float32).reshape(-1)
+    if D.size != B * TSDF_BRICK_VOXELS or w.size != D.size:
+        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks" % B)
+    o, n, vx, _, _ = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V)
+    index, coord, bs = (_host_array(a) for a in (sv.brick_index, sv.brick_coord, sv.brick_start))
+    ls = sv.lattice_start
+    out, point_start = [], np.zeros(V + 1, dtype=np.int64)
+    face = (np.s_[:, :, :, 7], np.s_[:, :, 7, :], np.s_[:, 7, :, :]), (np.s_[:, :, :, 0], np.s_[:, :, 0, :],
+                                                                       np.s_[:, 0, :, :])
+    inner = ((np.s_[:, :, :, :-1], np.s_[:, :, :, 1:]), (np.s_[:, :, :-1, :], np.s_[:, :, 1:, :]),
+             (np.s_[:, :-1, :, :], np.s_[:, 1:, :, :]))
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            rows = slice(int(bs[v]), int(bs[v + 1]))
+            Bv = rows.stop - rows.start
+            c = coord[rows].astype(np.int64)
+            nb = (n[v].astype(np.int64) + (TSDF_BRICK - 1)) // TSDF_BRICK
+            i = _slot_voxels(c)
+            exists = ((i[0] < n[v, 0]) & (i[1] < n[v, 1]) & (i[2] < n[v, 2])).reshape(Bv, 8, 8, 8)
+            Dv = D[rows.start * TSDF_BRICK_VOXELS:rows.stop * TSDF_BRICK_VOXELS].reshape(Bv, 8, 8, 8)   # [b, iz, iy, ix]
+            wv = w[rows.start * TSDF_BRICK_VOXELS:rows.stop * TSDF_BRICK_VOXELS].reshape(Bv, 8, 8, 8)
+            ok = exists & (wv >= np.float32(min_weight)) & (np.abs(Dv) < np.float32(1.0))
+            emit = np.zeros((Bv, 8, 8, 8, 3), dtype=bool)
+            frac = np.zeros((Bv, 8, 8, 8, 3), dtype=np.float32)
+            for a in range(3):
+                D1, ok1 = np.zeros_like(Dv), np.zeros_like(ok)     # the +1 neighbour on axis a, and whether it is valid
+                low, high = inner[a]
+                D1[low], ok1[low] = Dv[high], ok[high]
+                beyond = c.copy()                                  # across the face: the brick that brick_index names
+                beyond[:, a] += 1
+                inside = beyond[:, a] < nb[a]
+                at = ls[v] + (beyond[:, 2] * nb[1] + beyond[:, 1]) * nb[0] + beyond[:, 0]
+                rank = np.where(inside, index[np.where(inside, at, 0)], -1)
+                has = np.flatnonzero(rank >= 0)
+                D1[face[0][a]][has] = Dv[face[1][a]][rank[has]]
+                ok1[face[0][a]][has] = ok[face[1][a]][rank[has]]
+                emit[..., a] = ok & ok1 & ((Dv < 0) != (D1 < 0))
+                a0, a1 = np.abs(Dv), np.abs(D1)
+                frac[..., a] = a0 / (a0 + a1)
+            slot, axis = np.nonzero(emit.reshape(-1, 3))           # row-major: brick, slot, then axis
+            xyz = tuple(np.float32(o[v, a]) + np.float32(vx[v]) * i[a].reshape(-1)[slot].astype(np.float32)
+                        for a in range(3))
+            pts = np.stack(xyz, axis=1).astype(np.float32)
+            r = np.arange(slot.size)
+            pts[r, axis] = pts[r, axis] + vx[v] * frac.reshape(-1, 3)[slot, axis]
+            out.append(pts)
+            point_start[v + 1] = point_start[v] + slot.size
     return (np.concatenate(out, 0) if out else np.zeros((0, 3), np.float32)), point_start
 
 

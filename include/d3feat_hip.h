@@ -1091,6 +1091,75 @@ int d3f_tsdf_extract_host(const float* D, const float* w, const int64_t* vol_sta
                           int64_t capacity, float* points, int64_t* point_start, int32_t* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sparse TSDF volumes: the same batch of V volumes, frames and rule, but D and w are kept only for the bricks of
+ * 8 x 8 x 8 voxels that a depth pixel can reach within trunc (csrc/tsdf_sparse.hpp states the rule in full, with the
+ * argument that no voxel the dense volume can emit a point from is left out; the reference has no such step).
+ * Volume v has a brick lattice of ceil(n / 8) bricks per axis, bx fastest: the lattice bricks of the batch are
+ * [lattice_start[v], lattice_start[v+1]) of flags / brick_index (lattice_start int64 [V+1] from 0 to lattice_bricks,
+ * the prefix of the volumes' brick lattices; lattice_bricks <= 2^31 - 1).  Its allocated bricks are the pool rows
+ * [brick_start[v], brick_start[v+1]) (int64 [V+1] from 0 to `bricks`), in lattice order; brick_coord [bricks, 3] =
+ * (bx, by, bz) of a row; brick_index [lattice_bricks] = the rank of a lattice brick among the allocated bricks of its
+ * volume, or -1.  The pool D, w is f32 [bricks, 512]: voxel (ix, iy, iz) at slot (ix & 7) + 8 (iy & 7) + 64 (iz & 7)
+ * of its brick's row; a slot beyond dims holds D = 0, w = 0.  The other arguments are those of the dense entry points.
+ * d3f_tsdf_sparse_mark: flags int32 [lattice_bricks], zeroed here, then 1 for every brick in the box of a valid pixel
+ *   (plain idempotent stores: the result is a set, no atomic decides anything).  F <= 65535.
+ * d3f_tsdf_sparse_index: exclusive scan of the flags (as mark wrote them, 0 / 1) -> brick_index, brick_start
+ *   (brick_start[V] = the number of allocated bricks, the one value a caller reads back) and brick_coord, which must
+ *   hold lattice_bricks rows (the bound known before the read-back); the rows from brick_start[V] on are not written.
+ * d3f_tsdf_sparse_integrate: one workgroup per pool row, written once by the threads that own its slots for all frames
+ *   of the row's volume: no atomics, nothing read back; every slot is d3f_tsdf_integrate's voxel bit for bit.
+ * d3f_tsdf_sparse_extract: count per block of 256 slots, exclusive scan, emit, as d3f_tsdf_extract; the +1 neighbour
+ *   across a brick face is found through brick_index, an absent brick being an invalid neighbour.  points
+ *   [capacity, 3] in the order volume, brick in lattice order, slot, axis: d3f_tsdf_extract's rows bit for bit, as a
+ *   set.  capacity, status, counted, d3f_tsdf_sparse_extract_count and point_start as for d3f_tsdf_extract; bricks >= 1.
+ *   Indices read from brick_index / brick_coord / brick_start are bounded before use: tables that disagree with each
+ *   other give an unspecified result, but nothing outside brick_index and the pool is read.
+ * The _host twins take host pointers and make no GPU call.
+ * ---------------------------------------------------------------------------------------------- */
+int d3f_tsdf_sparse_mark(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
+                         const float* intrinsics, const float* camera_to_volume, const float* origin,
+                         const int32_t* dims, const float* voxel, const float* trunc, const int64_t* lattice_start,
+                         int64_t lattice_bricks, float depth_scale, float depth_max, int32_t* flags, void* stream);
+int d3f_tsdf_sparse_mark_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                              int V, const float* intrinsics, const float* camera_to_volume, const float* origin,
+                              const int32_t* dims, const float* voxel, const float* trunc,
+                              const int64_t* lattice_start, int64_t lattice_bricks, float depth_scale, float depth_max,
+                              int32_t* flags);
+size_t d3f_tsdf_sparse_index_ws_bytes(int64_t lattice_bricks);
+int d3f_tsdf_sparse_index(const int32_t* flags, const int64_t* lattice_start, const int32_t* dims, int V,
+                          int64_t lattice_bricks, int32_t* brick_index, int32_t* brick_coord, int64_t* brick_start,
+                          void* ws, size_t ws_bytes, void* stream);
+int d3f_tsdf_sparse_index_host(const int32_t* flags, const int64_t* lattice_start, const int32_t* dims, int V,
+                               int64_t lattice_bricks, int32_t* brick_index, int32_t* brick_coord,
+                               int64_t* brick_start);
+int d3f_tsdf_sparse_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                              int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
+                              const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
+                              float* w, void* stream);
+int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W,
+                                   const int32_t* frame_start, int V, const float* intrinsics,
+                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                   const float* voxel, const float* trunc, const int64_t* brick_start,
+                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                   float* D, float* w);
+size_t d3f_tsdf_sparse_extract_ws_bytes(int64_t bricks);
+int d3f_tsdf_sparse_extract_count(const float* D, const float* w, const int64_t* lattice_start,
+                                  const int64_t* brick_start, const int32_t* brick_index, const int32_t* brick_coord,
+                                  const int32_t* dims, int V, int64_t lattice_bricks, int64_t bricks, float min_weight,
+                                  int64_t* point_start, void* ws, size_t ws_bytes, void* stream);
+int d3f_tsdf_sparse_extract(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
+                            const int32_t* brick_index, const int32_t* brick_coord, const float* origin,
+                            const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                            float min_weight, int counted, int64_t capacity, float* points, int64_t* point_start,
+                            int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int d3f_tsdf_sparse_extract_host(const float* D, const float* w, const int64_t* lattice_start,
+                                 const int64_t* brick_start, const int32_t* brick_index, const int32_t* brick_coord,
+                                 const float* origin, const int32_t* dims, const float* voxel, int V,
+                                 int64_t lattice_bricks, int64_t bricks, float min_weight, int64_t capacity,
+                                 float* points, int64_t* point_start, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------------
  * Triangle meshes with normals from the same batch of TSDF volumes: dual contouring of the lattice ("naive surface
  * nets"; csrc/tsdf_mesh.hpp states the rule in full, in the terms of csrc/tsdf.hpp; the reference has no such step).
  * The arguments D, w, vol_start, origin, dims, voxel, V, total_voxels and min_weight are those of d3f_tsdf_extract.
