@@ -185,6 +185,18 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+  return __longlong_as_double((long long)shfl_xor_u64((uint64_t)__double_as_longlong(v), m));
+}
+// every entry of v summed over the wave, in every lane: the fixed butterfly the deterministic f64 reductions share
+template <int kN>
+__device__ __forceinline__ void wave_sum_f64(double (&v)[kN]) {
+#pragma unroll
+  for (int k = 0; k < kN; ++k)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v[k] += shfl_xor_f64(v[k], o);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -88,18 +88,6 @@ __device__ __forceinline__ long long pair_rows(const IcpArgs& A, int p, int a) {
   return m > 0 ? m : 0;
 }
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-  return __longlong_as_double((long long)d3f::shfl_xor_u64((uint64_t)__double_as_longlong(v), m));
-}
-
-template <int kSums>
-__device__ __forceinline__ void wave_sum(double (&v)[kSums]) {
-#pragma unroll
-  for (int k = 0; k < kSums; ++k)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v[k] += shfl_xor_f64(v[k], o);
-}
-
 __device__ __forceinline__ void write_pose(double* __restrict__ o, const double* __restrict__ rt) {
 #pragma unroll
   for (int k = 0; k < 12; ++k) o[k] = rt[k];
@@ -154,7 +142,7 @@ __device__ __forceinline__ void pair_sums(const IcpArgs& A, int p, int a, int la
 #pragma unroll
     for (int k = 0; k < kSums; ++k) v[k] += part[k];
   }
-  wave_sum(v);
+  d3f::wave_sum_f64(v);
 }
 
 template <int kKind>
@@ -259,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
       acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
     }
   }
-  wave_sum(acc);
+  d3f::wave_sum_f64(acc);
   __shared__ double red[kBlock / 64][kSums];
   if (lane == 0) {
 #pragma unroll

@@ -12,6 +12,9 @@ each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has t
 only for the bricks of 8 x 8 x 8 voxels near a surface (``ops.tsdf_allocate`` / ``tsdf_integrate_sparse`` /
 ``tsdf_extract_sparse``; csrc/tsdf_sparse.hpp has the rule): the same points, in the sparse order, from a fraction of
 the memory.  Colour is not part of this.
+
+``track_sequence`` gives the camera poses of a sequence that comes without them: frame-to-frame depth odometry
+(``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence.
 """
 import os
 import re
@@ -270,6 +273,64 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
     return (fused[0][0], fused[1][0]) if mesh else fused[0]
 
 
+# --------------------------------------------------------------------------------------------------- tracking
+DEFAULT_TRACK_BYTES = 1 << 30    # the depth pyramid of the frames tracked in one call (4 bytes per pixel, about 4/3 H W)
+
+
+def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT_TRACK_BYTES, depth_scale=1000.0,
+                   depth_max=DEFAULT_DEPTH_MAX, depth_diff=0.05, **odometry):
+    """``(poses f64 [F,4,4], status int32 [F-1])``: camera poses of a depth sequence by frame-to-frame depth odometry
+    (``ops.depth_odometry``: projective point-to-plane ICP over a depth pyramid, every pair from the identity).
+
+    ``depth`` [F,H,W] and ``intrinsics`` as for ``fuse_fragments``.  ``stride`` takes every stride-th frame (F counts the
+    frames taken).  ``poses[0] = I``; the pairs are ``(f+1, f)``, T_f maps camera f+1 into camera f, and
+    ``poses[f+1] = poses[f] @ T_f``: camera-to-"world" poses in the frame of the first camera.  ``status[f]`` is the
+    odometry's status of pair f (``ops.ODO_ST_*``); a pair whose status is not 0 keeps T_f = I -- reported, never
+    repaired.  ``**odometry``: ``iterations`` (their number is the number of pyramid levels), ``max_distance``.
+    Sequences whose pyramid exceeds ``max_bytes`` are tracked in chunks that overlap by one frame (two frames at
+    least); a pair's result does not depend on its chunk.  ``device='cuda'`` runs the HIP kernels, ``device='cpu'``
+    the NumPy restatement (equal to rounding).
+
+    ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it; drift
+    accumulates from frame to frame and nothing closes a loop."""
+    from .. import ops
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be at least 1")
+    depth = ops._tsdf_depth_array(depth)[::stride]
+    F = depth.shape[0]
+    if F < 1:
+        raise ValueError("depth holds no frame")
+    K = np.asarray(intrinsics, dtype=np.float64)
+    if K.shape == (3, 3):
+        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    K = K.reshape(-1, 4)
+    K = (K[::stride] if K.shape[0] > 1 else np.broadcast_to(K, (F, 4))).astype(np.float32)
+    if K.shape[0] != F:
+        raise ValueError("%d intrinsics rows for %d frames" % (K.shape[0], F))
+    iterations = odometry.pop('iterations', ops.ODO_ITERATIONS)
+    levels = len(ops._odo_iterations(iterations))
+    cpu = _is_cpu(device)
+    frame_bytes = 4 * ops.depth_pyramid_pixels(depth.shape[1], depth.shape[2], levels)
+    per_chunk = max(2, int(max_bytes) // max(frame_bytes, 1))
+    T = np.broadcast_to(np.eye(4), (max(F - 1, 0), 4, 4)).copy()
+    status = np.zeros(max(F - 1, 0), dtype=np.int32)
+    for lo in range(0, F - 1, per_chunk - 1):
+        hi = min(lo + per_chunk, F)                       # frames [lo, hi): the pairs (lo+1, lo) .. (hi-1, hi-2)
+        pairs = np.stack([np.arange(1, hi - lo), np.arange(0, hi - lo - 1)], axis=1)
+        args = (depth[lo:hi], K[lo:hi], levels, depth_scale, depth_max, depth_diff)
+        if cpu:
+            res = ops.depth_odometry_numpy(ops.depth_pyramid_numpy(*args), pairs, None, iterations, **odometry)
+        else:
+            res = [t.cpu().numpy() for t in ops.depth_odometry(ops.depth_pyramid(*args), pairs, None, iterations,
+                                                               **odometry)]
+        T[lo:hi - 1], status[lo:hi - 1] = res[0], res[3]
+    poses = np.broadcast_to(np.eye(4), (F, 4, 4)).copy()
+    for f in range(F - 1):
+        poses[f + 1] = poses[f] @ (T[f] if status[f] == 0 else np.eye(4))
+    return poses, status
+
+
 # ------------------------------------------------------------------------------------------------------ files
 def write_ply_points(filename, points):
     """Binary little-endian PLY with the three float properties x, y, z."""
@@ -325,10 +386,11 @@ def write_fragments(root, scene, clouds, poses, frames_per_fragment, seq='seq-01
     return path
 
 
-def read_sequence(folder):
+def read_sequence(folder, require_poses=True):
     """``(depth uint16 [F,H,W], intrinsics f64 [4] = fx, fy, cx, cy, poses f64 [F,4,4])`` of a 3DMatch raw sequence
     folder: ``frame-%06d.depth.png`` (16-bit), ``frame-%06d.pose.txt`` (camera-to-world), and ``camera-intrinsics.txt``
-    (3x3) in the folder or in its parent."""
+    (3x3) in the folder or in its parent.  ``require_poses=False``: a sequence in which a pose file is missing gives
+    ``poses = None`` (``track_sequence`` makes them) instead of an error."""
     try:
         from PIL import Image
     except ImportError as e:
@@ -345,16 +407,20 @@ def read_sequence(folder):
     if Kmat.shape != (3, 3):
         raise ValueError("camera-intrinsics.txt: expected a 3x3 matrix, got %s" % (Kmat.shape,))
     depth, poses = [], []
+    tracked = require_poses or all(exists(join(folder, n.replace('.depth.png', '.pose.txt'))) for n in names)
     for n in names:
         with Image.open(join(folder, n)) as im:
             a = np.array(im)
         if a.ndim != 2 or a.min() < 0 or a.max() > 65535:
             raise ValueError("%s: not a single-channel 16-bit image" % n)
         depth.append(a.astype(np.uint16))
+        if not tracked:
+            continue
         P = np.loadtxt(join(folder, n.replace('.depth.png', '.pose.txt')), dtype=np.float64)
         if P.shape != (4, 4):
             raise ValueError("%s: expected a 4x4 pose" % n.replace('.depth.png', '.pose.txt'))
         poses.append(P)
     if len({d.shape for d in depth}) != 1:
         raise ValueError("%s: the depth images differ in size" % folder)
-    return np.stack(depth), np.array([Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]]), np.stack(poses)
+    return (np.stack(depth), np.array([Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]]),
+            np.stack(poses) if tracked else None)

@@ -4133,6 +4133,526 @@ def tsdf_mesh_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Depth odometry: camera poses of a depth sequence by projective point-to-plane ICP over a depth pyramid
+# (csrc/odometry.hpp has the rule; csrc/odometry.hip the kernels)
+# ---------------------------------------------------------------------------------------------------------------
+ODO_ST_FEW = 1           # D3F_ODO_ST_FEW: the final association has fewer than 6 accepted pixels
+ODO_ST_PAIR = 4          # D3F_ODO_ST_PAIR: a frame index outside [0, F)
+ODO_ST_NONFINITE = 8     # D3F_ODO_ST_NONFINITE: T_init holds a non-finite value
+ODO_ST_SINGULAR = 16     # D3F_ODO_ST_SINGULAR: the last fit at level 0 was singular (e.g. a view of a single plane)
+ODO_MAX_LEVELS = 8
+ODO_MAX_ITERS = 1024
+ODO_MAX_PAIRS = 65535
+ODO_SUMS = 29            # n, the 21 upper entries of sum J J^T, sum J r (6), sum d2
+ODO_MIN_PIXELS = 6
+ODO_ITERATIONS = (10, 5, 4)
+ODO_MAX_DISTANCE = 0.1
+ODO_DEPTH_DIFF = 0.05
+
+
+def depth_pyramid_pixels(H, W, levels):
+    """Pixels of one frame's packed pyramid: the sum of ``(H >> l) * (W >> l)`` over the levels."""
+    return sum((int(H) >> l) * (int(W) >> l) for l in range(int(levels)))
+
+
+class DepthPyramid(object):
+    """The packed depth pyramid of F frames and its level table (``depth_pyramid``).  ``data`` f32 [F, pixels]: the
+    levels of a frame one after another, level l being ``(H >> l) x (W >> l)`` pixels in raster order (metres, 0 where
+    invalid); ``K`` f32 [F, levels, 4] the intrinsics of every level; ``table`` int64 [levels, 3] = rows, columns and
+    pixel offset of a level inside a frame (host values); ``depth_diff`` what the levels were built with (the normals
+    use it again).  ``data`` and ``K`` are device tensors, CPU tensors (host twin) or NumPy arrays (restatement)."""
+
+    def __init__(self, data, K, H, W, levels, depth_diff):
+        self.data, self.K, self.H, self.W, self.levels = data, K, int(H), int(W), int(levels)
+        self.depth_diff = float(depth_diff)
+        self.frames = int(data.shape[0])
+        off = np.cumsum([0] + [(self.H >> l) * (self.W >> l) for l in range(self.levels)])
+        self.table = np.array([[self.H >> l, self.W >> l, off[l]] for l in range(self.levels)], dtype=np.int64)
+
+    def level(self, l):
+        """Level ``l`` of all frames as a view [F, H_l, W_l]."""
+        h, w, off = (int(x) for x in self.table[l])
+        return self.data[:, off:off + h * w].reshape(self.frames, h, w)
+
+
+def _odo_check_levels(H, W, levels):
+    levels = int(levels)
+    if not 1 <= levels <= ODO_MAX_LEVELS or (H >> (levels - 1)) < 1 or (W >> (levels - 1)) < 1:
+        raise ValueError("levels must be in 1..%d and leave every level of a %d x %d image a pixel, got %d"
+                         % (ODO_MAX_LEVELS, W, H, levels))
+    return levels
+
+
+def _odo_frames(depth, intrinsics):
+    """Host form of the frames: (depth [F,H,W] uint16 / f32, K f32 [F,4])."""
+    d = _tsdf_depth_array(depth)
+    if d.shape[0] < 1:
+        raise ValueError("depth holds no frame")
+    K = np.asarray(intrinsics.cpu() if isinstance(intrinsics, torch.Tensor) else intrinsics, dtype=np.float32)
+    return d, np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 4), (d.shape[0], 4)))
+
+
+def _depth_pyramid(host, device, depth, intrinsics, levels, depth_scale, depth_max, depth_diff):
+    d, K = _odo_frames(depth, intrinsics)
+    F, H, W = d.shape
+    levels = _odo_check_levels(H, W, levels)
+    td, tK = _on(device, d, K)
+    data = torch.empty((F, depth_pyramid_pixels(H, W, levels)), dtype=torch.float32, device=device)
+    KL = torch.empty((F, levels, 4), dtype=torch.float32, device=device)
+    L = _native.lib()
+    args = (_p(td), int(d.dtype != np.uint16), F, H, W, _p(tK), levels, float(depth_scale), float(depth_max),
+            float(depth_diff), _p(data), _p(KL))
+    if host:
+        _native.check(L.d3f_depth_pyramid_host(*args), "d3f_depth_pyramid_host")
+    else:
+        _native.check(L.d3f_depth_pyramid(*(args + (_stream(),))), "d3f_depth_pyramid")
+    return DepthPyramid(data, KL, H, W, levels, depth_diff)
+
+
+def depth_pyramid(depth, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, depth_diff=ODO_DEPTH_DIFF):
+    """The depth pyramid of F frames on the device (d3f_depth_pyramid; the rule is csrc/odometry.hpp): a
+    ``DepthPyramid`` -- the packed pyramid ``.data`` f32 [F, pixels], the level table ``.table`` and the intrinsics of
+    every level ``.K``.  ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres;
+    ``intrinsics`` [4] or [F,4] = fx, fy, cx, cy.  Level 0 is the depth in metres, 0 where invalid (not ``d > 0``, or
+    ``d > depth_max``: a NaN and an infinity too); level l+1 halves level l (an odd last row or column is dropped),
+    a pixel being the mean of the valid pixels of its 2x2 block and 0 when there is none or when they span more than
+    ``depth_diff``.  Equal to the host twin and ``depth_pyramid_numpy`` bit for bit."""
+    dev = _tsdf_device()
+    with _region("depth_pyramid"):
+        return _depth_pyramid(False, dev, depth, intrinsics, levels, depth_scale, depth_max, depth_diff)
+
+
+def depth_pyramid_host(depth, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                       depth_diff=ODO_DEPTH_DIFF):
+    """The host twin of ``depth_pyramid`` (d3f_depth_pyramid_host): CPU tensors, no GPU call."""
+    return _depth_pyramid(True, torch.device("cpu"), depth, intrinsics, levels, depth_scale, depth_max, depth_diff)
+
+
+def _odo_pairs(pairs, T, name):
+    """Host form of a pair list: (pairs int32 [P,2], T f64 [P,12]); ``T`` None gives identities."""
+    pr = np.ascontiguousarray(np.asarray(_host_array(pairs), dtype=np.int64).reshape(-1, 2))
+    P = pr.shape[0]
+    if P > ODO_MAX_PAIRS:
+        raise ValueError("at most %d pairs per call, got %d" % (ODO_MAX_PAIRS, P))
+    if (np.abs(pr) > 0x7fffffff).any():
+        raise ValueError("%s: frame indices must fit an int32" % name)
+    if T is None:
+        T = np.broadcast_to(np.eye(4), (P, 4, 4))
+    t = np.asarray(_host_array(T), dtype=np.float64)
+    if t.ndim == 2 and P == 1:
+        t = t[None]
+    if t.ndim != 3 or t.shape[0] != P or t.shape[1:] not in ((4, 4), (3, 4)):
+        raise ValueError("%s: T must be [%d,4,4] or [%d,3,4], got %s" % (name, P, P, t.shape))
+    return pr.astype(np.int32), np.ascontiguousarray(t[:, :3, :].reshape(P, 12))
+
+
+def _odo_check_distance(max_distance):
+    if not float(max_distance) > 0.0:
+        raise ValueError("max_distance must be positive")
+    return float(max_distance)
+
+
+def _odo_step(host, pyr, pairs, T, level, max_distance, return_index):
+    device = pyr.data.device
+    pr, t = _odo_pairs(pairs, T, "depth_odometry_step")
+    level, P = int(level), pr.shape[0]
+    if not 0 <= level < pyr.levels:
+        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    h, w = int(pyr.table[level, 0]), int(pyr.table[level, 1])
+    sums = torch.zeros((P, ODO_SUMS), dtype=torch.float64, device=device)
+    index = torch.full((P, h, w), -1, dtype=torch.int32, device=device) if return_index else None
+    if P:
+        tp, tt = _on(device, pr, t)
+        L = _native.lib()
+        args = (_p(pyr.data), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt), level,
+                _odo_check_distance(max_distance), pyr.depth_diff, _p(sums), _p(index))
+        if host:
+            _native.check(L.d3f_depth_odometry_step_host(*args), "d3f_depth_odometry_step_host")
+        else:
+            nbytes = L.d3f_depth_odometry_ws_bytes(P, pyr.H, pyr.W)
+            ws = _ws(nbytes, device)
+            _native.check(L.d3f_depth_odometry_step(*(args + (_p(ws), nbytes, _stream()))), "d3f_depth_odometry_step")
+    return (sums, index) if return_index else sums
+
+
+def _odo_device_pyramid(pyr, what):
+    if not isinstance(pyr, DepthPyramid) or not isinstance(pyr.data, torch.Tensor) or not pyr.data.is_cuda:
+        raise RuntimeError("%s takes the DepthPyramid of ops.depth_pyramid (on the device); the host twin is %s_host, "
+                           "the NumPy restatement %s_numpy" % (what, what, what))
+    return pyr
+
+
+def _odo_host_pyramid(pyr, what):
+    if not isinstance(pyr, DepthPyramid) or not isinstance(pyr.data, torch.Tensor) or pyr.data.is_cuda:
+        raise RuntimeError("%s takes the DepthPyramid of ops.depth_pyramid_host (CPU tensors)" % what)
+    return pyr
+
+
+def depth_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False):
+    """ONE association of P frame pairs at ``level`` under ``T`` (d3f_depth_odometry_step): ``sums`` f64 [P,29] on the
+    device -- n, the 21 upper entries of sum J J^T row by row, sum J r (6), sum d2 of the accepted pixels, with
+    ``J = [a x n, n]`` and ``r = (a - y) . n``.  ``pairs`` [P,2] = (moving frame a, fixed frame b), ``T`` [P,4,4] maps
+    a's camera frame into b's.  ``return_index=True`` appends int32 [P, H_l, W_l]: per moving pixel the raster index of
+    the accepted fixed pixel, or -1.  A pair that names a frame outside the pyramid, or whose T is not finite, gives
+    zero sums and -1 everywhere."""
+    _odo_device_pyramid(pyr, "depth_odometry_step")
+    with _region("depth_odometry_step"):
+        return _odo_step(False, pyr, pairs, T, level, max_distance, return_index)
+
+
+def depth_odometry_step_host(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False):
+    """The host twin of ``depth_odometry_step`` (d3f_depth_odometry_step_host): the same rule pixel by pixel in raster
+    order, CPU tensors, no GPU call."""
+    return _odo_step(True, _odo_host_pyramid(pyr, "depth_odometry_step_host"), pairs, T, level, max_distance,
+                     return_index)
+
+
+def _odo_iterations(iterations, levels=None):
+    it = [int(k) for k in np.asarray(iterations).reshape(-1)]
+    if not it or len(it) > ODO_MAX_LEVELS or min(it) < 0 or max(it) > ODO_MAX_ITERS:
+        raise ValueError("iterations must hold 1..%d counts in 0..%d (finest level first), got %s"
+                         % (ODO_MAX_LEVELS, ODO_MAX_ITERS, it))
+    if levels is not None and len(it) != levels:
+        raise ValueError("%d iteration counts for a pyramid of %d levels" % (len(it), levels))
+    return it
+
+
+def _odometry(host, pyr, pairs, T_init, iterations, max_distance, return_information):
+    device = pyr.data.device
+    pr, t = _odo_pairs(pairs, T_init, "depth_odometry")
+    it = _odo_iterations(iterations, pyr.levels)
+    P = pr.shape[0]
+    T = torch.zeros((P, 4, 4), dtype=torch.float64, device=device)
+    count = torch.zeros(P, dtype=torch.int32, device=device)
+    rmse = torch.zeros(P, dtype=torch.float64, device=device)
+    status = torch.zeros(P, dtype=torch.int32, device=device)
+    info = torch.zeros((P, 6, 6), dtype=torch.float64, device=device) if return_information else None
+    if P:
+        tp, tt = _on(device, pr, t)
+        L = _native.lib()
+        counts = (ctypes.c_int32 * len(it))(*it)
+        args = (_p(pyr.data), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
+                ctypes.cast(counts, ctypes.c_void_p), _odo_check_distance(max_distance), pyr.depth_diff, _p(T),
+                _p(count), _p(rmse), _p(status), _p(info))
+        if host:
+            _native.check(L.d3f_depth_odometry_host(*args), "d3f_depth_odometry_host")
+        else:
+            nbytes = L.d3f_depth_odometry_ws_bytes(P, pyr.H, pyr.W)
+            ws = _ws(nbytes, device)
+            _native.check(L.d3f_depth_odometry(*(args + (_p(ws), nbytes, _stream()))), "d3f_depth_odometry")
+    res = (T, count, rmse, status)
+    return res + (info,) if return_information else res
+
+
+def depth_odometry(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                   return_information=False, intrinsics=None, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                   depth_diff=ODO_DEPTH_DIFF):
+    """Relative poses of P frame pairs by projective point-to-plane ICP over the depth pyramid, all pairs in one launch
+    sequence (d3f_depth_odometry; the rule is csrc/odometry.hpp -- KinectFusion's tracker, frame to frame).
+
+    ``pyr_or_depth``: the ``DepthPyramid`` of ``depth_pyramid``, or depth frames [F,H,W] with ``intrinsics`` (the
+    pyramid of ``len(iterations)`` levels is then built here with ``depth_scale``, ``depth_max``, ``depth_diff``).
+    ``pairs`` [P,2] = (moving frame a, fixed frame b) and T maps a's camera frame into b's -- the (source, target,
+    transform) convention of ``icp_rigid``; with camera-to-world poses, ``T = inv(pose_b) @ pose_a``.  ``T_init``
+    [P,4,4] f64 (None: identities).  ``iterations[l]`` fits at level l (0 the finest), coarsest level first, fixed
+    counts: no host synchronisation, nothing read back.  An iteration projects every valid pixel of a into b, takes
+    b's pixel there with the normal computed from b's depth, accepts within ``max_distance`` and solves the 6x6
+    point-to-plane system; fewer than 6 accepted pixels or a singular system leave T as it is.
+
+    Returns device tensors ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P])``: count and rmse of one
+    more association at level 0 under the final T.  ``status``: ODO_ST_FEW (that association has fewer than 6 pixels),
+    ODO_ST_SINGULAR (the last fit at level 0 was singular: a view of a single plane), ODO_ST_PAIR (a frame outside the
+    pyramid), ODO_ST_NONFINITE (a non-finite T_init); each leaves T = T_init and gives count 0.
+    ``return_information=True`` appends f64 [P,6,6] = sum J J^T of that association, ``J = [a x n, n]``: ROTATION
+    FIRST, in the FIXED frame b, point-to-plane -- not the point-to-point form of
+    ``registration.information_from_moments``, whose default is translation first in the moving frame; its
+    ``frame='fixed', order='rotation_first'`` has the same layout.  A pair's result is bit-identical alone, in any
+    batch, and from run to run."""
+    if isinstance(pyr_or_depth, DepthPyramid):
+        pyr = _odo_device_pyramid(pyr_or_depth, "depth_odometry")
+    else:
+        if intrinsics is None:
+            raise ValueError("depth frames need intrinsics")
+        pyr = depth_pyramid(pyr_or_depth, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max,
+                            depth_diff)
+    with _region("depth_odometry"):
+        return _odometry(False, pyr, pairs, T_init, iterations, max_distance, return_information)
+
+
+def depth_odometry_host(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                        return_information=False, intrinsics=None, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                        depth_diff=ODO_DEPTH_DIFF):
+    """The host twin of ``depth_odometry`` (d3f_depth_odometry_host): CPU tensors, no GPU call.  It sums in raster
+    order, so T agrees with the device's to rounding (1e-6), not bit for bit."""
+    if isinstance(pyr_or_depth, DepthPyramid):
+        pyr = _odo_host_pyramid(pyr_or_depth, "depth_odometry_host")
+    else:
+        if intrinsics is None:
+            raise ValueError("depth frames need intrinsics")
+        pyr = depth_pyramid_host(pyr_or_depth, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max,
+                                 depth_diff)
+    return _odometry(True, pyr, pairs, T_init, iterations, max_distance, return_information)
+
+
+# ------------------------------------------------------------------------------------------- NumPy restatement
+def depth_pyramid_numpy(depth, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                        depth_diff=ODO_DEPTH_DIFF):
+    """The contract of ``depth_pyramid`` in NumPy: a ``DepthPyramid`` of NumPy arrays, equal to the kernel's bit for
+    bit (every f32 operation in the order of csrc/odometry.hpp)."""
+    d, K = _odo_frames(depth, intrinsics)
+    F, H, W = d.shape
+    levels = _odo_check_levels(H, W, levels)
+    f32 = np.float32
+    dd = f32(depth_diff)
+    data = np.zeros((F, depth_pyramid_pixels(H, W, levels)), dtype=f32)
+    with np.errstate(all='ignore'):
+        dm = d.astype(f32) / f32(depth_scale) if d.dtype == np.uint16 else d
+        cur = np.where((dm > 0) & ~(dm > f32(depth_max)), dm, f32(0.0)).astype(f32)
+        off = 0
+        for l in range(levels):
+            h, w = cur.shape[1:]
+            data[:, off:off + h * w] = cur.reshape(F, -1)
+            off += h * w
+            if l + 1 == levels:
+                break
+            hn, wn = h >> 1, w >> 1
+            total = np.zeros((F, hn, wn), dtype=f32)
+            k = np.zeros((F, hn, wn), dtype=np.int32)
+            lo = np.full((F, hn, wn), np.inf, dtype=f32)
+            hi = np.full((F, hn, wn), -np.inf, dtype=f32)
+            for dy in range(2):
+                for dx in range(2):
+                    b = cur[:, dy:2 * hn:2, dx:2 * wn:2]
+                    ok = b > 0
+                    total = np.where(ok, total + b, total)
+                    lo = np.where(ok, np.minimum(lo, b), lo)
+                    hi = np.where(ok, np.maximum(hi, b), hi)
+                    k += ok
+            cur = np.where((k == 0) | (hi - lo > dd), f32(0.0), total / k.astype(f32)).astype(f32)
+    KL = np.zeros((F, levels, 4), dtype=f32)
+    KL[:, 0] = K
+    for l in range(1, levels):
+        KL[:, l, 0] = KL[:, l - 1, 0] / f32(2.0)
+        KL[:, l, 1] = KL[:, l - 1, 1] / f32(2.0)
+        KL[:, l, 2] = (KL[:, l - 1, 2] - f32(0.5)) / f32(2.0)
+        KL[:, l, 3] = (KL[:, l - 1, 3] - f32(0.5)) / f32(2.0)
+    return DepthPyramid(data, KL, H, W, levels, depth_diff)
+
+
+def _odo_numpy_pyramid(pyr):
+    if not isinstance(pyr, DepthPyramid):
+        raise ValueError("expected a DepthPyramid")
+    if isinstance(pyr.data, np.ndarray):
+        return pyr
+    return DepthPyramid(_host_array(pyr.data), _host_array(pyr.K), pyr.H, pyr.W, pyr.levels, pyr.depth_diff)
+
+
+def _odo_vertices(img, K):
+    """(X, Y, Z) f32 [H,W] of a level image: vertex() of csrc/odometry.hpp for every pixel."""
+    h, w = img.shape
+    u = np.arange(w, dtype=np.float32)[None, :]
+    v = np.arange(h, dtype=np.float32)[:, None]
+    return ((u - K[2]) * img) / K[0], ((v - K[3]) * img) / K[1], img
+
+
+def _odo_normals(img, K, depth_diff):
+    """normal_at() of csrc/odometry.hpp for every pixel of a level image: (has bool [H,W], n f32 [3,H,W], V f32
+    [3,H,W])."""
+    f32 = np.float32
+    h, w = img.shape
+    V = np.stack(_odo_vertices(img, K)).astype(f32)
+    has = np.zeros((h, w), dtype=bool)
+    n = np.zeros((3, h, w), dtype=f32)
+    if h < 3 or w < 3:
+        return has, n, V
+    dd = f32(depth_diff)
+    c, le, ri, up, dn = img[1:-1, 1:-1], img[1:-1, :-2], img[1:-1, 2:], img[:-2, 1:-1], img[2:, 1:-1]
+    ok = (c > 0) & (le > 0) & (ri > 0) & (up > 0) & (dn > 0)
+    for nb in (le, ri, up, dn):
+        ok &= np.abs(nb - c) <= dd
+    e1 = [A[1:-1, 2:] - A[1:-1, :-2] for A in V]
+    e2 = [A[2:, 1:-1] - A[:-2, 1:-1] for A in V]
+    c0 = e1[1] * e2[2] - e1[2] * e2[1]
+    c1 = e1[2] * e2[0] - e1[0] * e2[2]
+    c2 = e1[0] * e2[1] - e1[1] * e2[0]
+    ln = np.sqrt((c0 * c0 + c1 * c1) + c2 * c2)
+    ok &= (ln > 0) & np.isfinite(ln)
+    nn = [c0 / ln, c1 / ln, c2 / ln]
+    Vc = V[:, 1:-1, 1:-1]
+    flip = (nn[0] * Vc[0] + nn[1] * Vc[1]) + nn[2] * Vc[2] > 0
+    for r in range(3):
+        n[r, 1:-1, 1:-1] = np.where(ok, np.where(flip, -nn[r], nn[r]), f32(0.0))
+    has[1:-1, 1:-1] = ok
+    return has, n, V
+
+
+def _odo_associate_numpy(A_img, Ka, fixed, Kb, T12, max_distance):
+    """associate() of csrc/odometry.hpp for every pixel of the moving level image: (index int32 [H,W], a, y, n f32
+    [3,m] of the accepted pixels in raster order).  ``fixed`` = ``_odo_normals`` of the fixed image."""
+    f32 = np.float32
+    has, nb, Vb = fixed
+    h, w = A_img.shape
+    M = np.asarray(T12, dtype=np.float64).reshape(12).astype(f32)
+    md = f32(max_distance)
+    X, Y, Z = _odo_vertices(A_img, Ka)
+    ok = A_img > 0
+    a = [((M[4 * r] * X + M[4 * r + 1] * Y) + M[4 * r + 2] * Z) + M[4 * r + 3] for r in range(3)]
+    ok &= a[2] > 0
+    up = np.floor(((Kb[0] * a[0]) / a[2] + Kb[2]) + f32(0.5))
+    vp = np.floor(((Kb[1] * a[1]) / a[2] + Kb[3]) + f32(0.5))
+    ok &= (up >= 0) & (up < f32(w)) & (vp >= 0) & (vp < f32(h))
+    ui = np.where(ok, up, 0).astype(np.int64)
+    vi = np.where(ok, vp, 0).astype(np.int64)
+    ok &= has[vi, ui]
+    y = [Vb[r][vi, ui] for r in range(3)]
+    e = [a[r] - y[r] for r in range(3)]
+    ok &= (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2] <= md * md
+    index = np.where(ok, vi * w + ui, -1).astype(np.int32)
+    pick = lambda rows: np.stack([np.asarray(x, dtype=f32)[ok] for x in rows])
+    return index, pick(a), pick(y), np.stack([nb[r][vi, ui][ok] for r in range(3)])
+
+
+_ODO_UPPER = [(i, j) for i in range(6) for j in range(i, 6)]
+
+
+def _odo_terms(a, y, n):
+    """add_pixel() of csrc/odometry.hpp: f64 [m,29], what every accepted pixel adds to the sums."""
+    a, y, n = (x.astype(np.float64) for x in (a, y, n))
+    e = a - y
+    J = [a[1] * n[2] - a[2] * n[1], a[2] * n[0] - a[0] * n[2], a[0] * n[1] - a[1] * n[0], n[0], n[1], n[2]]
+    r = (e[0] * n[0] + e[1] * n[1]) + e[2] * n[2]
+    cols = [np.ones_like(r)] + [J[i] * J[j] for i, j in _ODO_UPPER] + [J[i] * r for i in range(6)]
+    cols.append((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+    return np.stack(cols, axis=1) if r.size else np.zeros((0, ODO_SUMS))
+
+
+def _odo_pair_ok(pr, t, F):
+    return 0 <= pr[0] < F and 0 <= pr[1] < F and bool(np.isfinite(t).all())
+
+
+def depth_odometry_step_numpy(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False,
+                              return_terms=False):
+    """The contract of ``depth_odometry_step`` in NumPy: ``sums`` f64 [P,29] (NumPy's own summation order: equal to
+    the kernel's within the summation bound, not bit for bit) and, with ``return_index``, the index int32 [P,H_l,W_l],
+    which is equal.  ``return_terms=True`` appends the list of the f64 [m_p,29] terms the sums are made of."""
+    pyr = _odo_numpy_pyramid(pyr)
+    pr, t = _odo_pairs(pairs, T, "depth_odometry_step_numpy")
+    level = int(level)
+    if not 0 <= level < pyr.levels:
+        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    imgs = pyr.level(level)
+    h, w = imgs.shape[1:]
+    sums = np.zeros((pr.shape[0], ODO_SUMS))
+    index = np.full((pr.shape[0], h, w), -1, dtype=np.int32)
+    terms = []
+    with np.errstate(all='ignore'):
+        for p in range(pr.shape[0]):
+            terms.append(np.zeros((0, ODO_SUMS)))
+            if not _odo_pair_ok(pr[p], t[p], pyr.frames):
+                continue
+            a, b = int(pr[p, 0]), int(pr[p, 1])
+            fixed = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
+            index[p], av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], fixed, pyr.K[b, level], t[p],
+                                                        _odo_check_distance(max_distance))
+            terms[-1] = _odo_terms(av, yv, nv)
+            sums[p] = terms[-1].sum(axis=0)
+    res = (sums,) + ((index,) if return_index else ()) + ((terms,) if return_terms else ())
+    return res if len(res) > 1 else sums
+
+
+_ODO_PLANE_PIVOT = 1e-10      # kPlanePivot of csrc/plane.hpp
+
+
+def _odo_plane_step(sums, T12):
+    """fit() of csrc/odometry.hpp (plane_step of csrc/plane.hpp with a zero pivot) -> (T_next [12], moved, singular):
+    the pivot test is the kernel's Cholesky; the solution is NumPy's solve of the same system."""
+    if sums[0] < ODO_MIN_PIXELS:
+        return T12, False, False
+    A = np.zeros((6, 6))
+    for k, (i, j) in enumerate(_ODO_UPPER):
+        A[i, j] = A[j, i] = sums[1 + k]
+    floor, U = _ODO_PLANE_PIVOT * A.diagonal().max(), np.zeros((6, 6))
+    for i in range(6):
+        d = A[i, i] - (U[:i, i] ** 2).sum()
+        if not d > floor:
+            return T12, False, True
+        U[i, i] = np.sqrt(d)
+        U[i, i + 1:] = (A[i, i + 1:] - U[:i, i] @ U[:i, i + 1:]) / U[i, i]
+    v = np.linalg.solve(A, -sums[22:28])
+    ca, sa, cb, sb, cg, sg = np.cos(v[0]), np.sin(v[0]), np.cos(v[1]), np.sin(v[1]), np.cos(v[2]), np.sin(v[2])
+    D = np.array([[cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa],
+                  [sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa],
+                  [-sb, cb * sa, cb * ca]])                            # Rz(gamma) Ry(beta) Rx(alpha)
+    Tk = T12.reshape(3, 4)
+    out = np.empty((3, 4))
+    out[:, :3] = D @ Tk[:, :3]
+    out[:, 3] = D @ Tk[:, 3] + v[3:]
+    return out.reshape(12), True, False
+
+
+def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                         return_information=False, intrinsics=None, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                         depth_diff=ODO_DEPTH_DIFF):
+    """The contract of ``depth_odometry`` in NumPy: ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P])``
+    (and the information matrices [P,6,6]); T agrees with the kernel's to rounding, not bit for bit."""
+    it = _odo_iterations(iterations)
+    if isinstance(pyr_or_depth, DepthPyramid):
+        pyr = _odo_numpy_pyramid(pyr_or_depth)
+        _odo_iterations(iterations, pyr.levels)
+    else:
+        if intrinsics is None:
+            raise ValueError("depth frames need intrinsics")
+        pyr = depth_pyramid_numpy(pyr_or_depth, intrinsics, len(it), depth_scale, depth_max, depth_diff)
+    pr, t0 = _odo_pairs(pairs, T_init, "depth_odometry_numpy")
+    md = _odo_check_distance(max_distance)
+    P = pr.shape[0]
+    T = np.zeros((P, 4, 4))
+    T[:, 3, 3] = 1.0
+    T[:, :3, :] = t0.reshape(P, 3, 4)
+    count = np.zeros(P, dtype=np.int32)
+    rmse = np.zeros(P)
+    status = np.zeros(P, dtype=np.int32)
+    info = np.zeros((P, 6, 6))
+    normals = {}
+
+    def sums_at(p, level, t):
+        a, b = int(pr[p, 0]), int(pr[p, 1])
+        imgs = pyr.level(level)
+        if (b, level) not in normals:
+            normals[(b, level)] = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
+        _, av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], normals[(b, level)], pyr.K[b, level], t, md)
+        return _odo_terms(av, yv, nv).sum(axis=0)
+
+    with np.errstate(all='ignore'):
+        for p in range(P):
+            if not (0 <= pr[p, 0] < pyr.frames and 0 <= pr[p, 1] < pyr.frames):
+                status[p] |= ODO_ST_PAIR
+            if not np.isfinite(t0[p]).all():
+                status[p] |= ODO_ST_NONFINITE
+            if status[p]:
+                continue
+            t, singular = t0[p].copy(), False
+            for level in range(pyr.levels - 1, -1, -1):
+                for _ in range(it[level]):
+                    t, _moved, s = _odo_plane_step(sums_at(p, level, t), t)
+                    if level == 0:
+                        singular = s
+            sums = sums_at(p, 0, t)
+            if sums[0] < ODO_MIN_PIXELS:
+                status[p] = ODO_ST_FEW
+            elif singular:
+                status[p] = ODO_ST_SINGULAR
+            else:
+                T[p, :3, :] = t.reshape(3, 4)
+                count[p] = int(sums[0])
+                rmse[p] = np.sqrt(sums[28] / sums[0])
+                for k, (i, j) in enumerate(_ODO_UPPER):
+                    info[p, i, j] = info[p, j, i] = sums[1 + k]
+    res = (T, count, rmse, status)
+    return res + (info,) if return_information else res
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

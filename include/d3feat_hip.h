@@ -1196,6 +1196,72 @@ int d3f_tsdf_mesh_host(const float* D, const float* w, const int64_t* vol_start,
                        int64_t* vertex_start, int64_t* face_start, int32_t* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth odometry: the camera poses of a depth sequence by frame-to-frame projective point-to-plane ICP over a depth
+ * pyramid (KinectFusion's tracker; csrc/odometry.hpp states the rule in full, in the terms of csrc/tsdf.hpp and
+ * csrc/plane.hpp; the reference has no such step).  Frames as for d3f_tsdf_integrate: depth [F, H, W] uint16 raw units
+ * or f32 metres, intrinsics [F, 4]; a pixel is valid when d > 0 and not d > depth_max.
+ * The packed pyramid is f32 [F, d3f_depth_pyramid_pixels(H, W, levels)]: the levels of a frame one after another,
+ * level l being (H >> l) x (W >> l) pixels in raster order (depth in metres, 0 where invalid; a 2x2 block of the finer
+ * level averaged over its valid pixels, 0 when they span more than depth_diff).  level_intrinsics is f32
+ * [F, levels, 4].  1 <= levels <= D3F_ODO_MAX_LEVELS and every level has at least one pixel; H W <= 2^30.
+ * Pair p = pairs[2p], pairs[2p+1] = (moving frame a, fixed frame b); T [12] row-major 3x4 f64 maps a's camera frame
+ * into b's (d3f_icp_rigid's convention).  An association at level l under T (rounded to f32) projects every valid
+ * pixel of a into b, takes b's pixel there with the normal computed from b's depth, and accepts it within
+ * max_distance; the accepted pixels give the D3F_ODO_SUMS = 29 sums of the point-to-plane normal equations
+ * { n, the 21 upper entries of sum J J^T row by row, sum J r (6), sum d2 }, J = [a x n, n] (rotation first, in frame
+ * b), in f64.  depth_diff is the pyramid's (the normals use it again).
+ * d3f_depth_pyramid: one launch per level, one thread per output pixel, and a launch for the intrinsics.  Device,
+ *   host twin and the NumPy restatement agree bit for bit.
+ * d3f_depth_odometry_step: ONE association at `level` under T [P, 12]: sums [P, 29] and, when index is given, int32
+ *   [P, (H >> level) (W >> level)] = per moving pixel the raster index of the accepted fixed pixel or -1.  A pair that
+ *   names a frame outside [0, F) or whose T is not finite gives zero sums and -1 everywhere.
+ * d3f_depth_odometry: from T_init [P, 12], iterations_host[l] (a HOST array of `levels` counts, each in
+ *   0..D3F_ODO_MAX_ITERS) iterations of associate + fit (plane_step of csrc/plane.hpp, pivot 0) at level l, coarsest
+ *   level first; an iteration with fewer than 6 accepted pixels or a singular system leaves T unchanged.  One more
+ *   association at level 0 under the final T gives count [P] int32, rmse [P] f64 = sqrt(sum d2 / count) and, when
+ *   information is given, [P, 36] f64 = sum J J^T as a full 6x6.  T [P, 16] f64 (4x4).  status [P] int32:
+ *   D3F_ODO_ST_FEW (the final association has fewer than 6 accepted pixels), D3F_ODO_ST_SINGULAR (the last fit at
+ *   level 0 was singular), D3F_ODO_ST_PAIR (a frame outside [0, F)), D3F_ODO_ST_NONFINITE (a non-finite T_init); each
+ *   of them leaves T = T_init and gives count 0, rmse 0 and a zero information matrix.  The launch sequence depends on
+ *   levels and iterations_host alone: no host synchronisation, nothing read back, capturable into a graph.  P <= 65535.
+ * Deterministic and batch-independent: a workgroup serves D3F_ODO_CHUNK consecutive raster pixels of ONE pair's moving
+ *   image, sums them in a fixed order (lane, wave butterfly, waves in order), and one wave adds the pair's chunks in
+ *   ascending order; no floating-point atomic.  A pair's result is bit-identical alone, in any batch, from run to run.
+ * ws: d3f_depth_odometry_ws_bytes(P, H, W) bytes, for both device entry points.
+ * The _host twins take host pointers, sum in raster order and make no GPU call.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_ODO_MAX_LEVELS 8
+#define D3F_ODO_MAX_ITERS 1024
+#define D3F_ODO_CHUNK 1024
+#define D3F_ODO_SUMS 29
+#define D3F_ODO_ST_FEW 1        /* = D3F_ICP_ST_FEW */
+#define D3F_ODO_ST_PAIR 4       /* = D3F_ICP_ST_PAIR */
+#define D3F_ODO_ST_NONFINITE 8  /* = D3F_ICP_ST_NONFINITE */
+#define D3F_ODO_ST_SINGULAR 16  /* = D3F_ICP_ST_SINGULAR */
+int64_t d3f_depth_pyramid_pixels(int H, int W, int levels);   /* pixels of one frame's pyramid; 0 for a bad shape */
+int d3f_depth_pyramid(const void* depth, int depth_is_f32, int F, int H, int W, const float* intrinsics, int levels,
+                      float depth_scale, float depth_max, float depth_diff, float* pyramid, float* level_intrinsics,
+                      void* stream);
+int d3f_depth_pyramid_host(const void* depth, int depth_is_f32, int F, int H, int W, const float* intrinsics,
+                           int levels, float depth_scale, float depth_max, float depth_diff, float* pyramid,
+                           float* level_intrinsics);
+size_t d3f_depth_odometry_ws_bytes(int P, int H, int W);
+int d3f_depth_odometry_step(const float* pyramid, const float* level_intrinsics, int F, int H, int W, int levels,
+                            const int32_t* pairs, int P, const double* T, int level, float max_distance,
+                            float depth_diff, double* sums, int32_t* index, void* ws, size_t ws_bytes, void* stream);
+int d3f_depth_odometry_step_host(const float* pyramid, const float* level_intrinsics, int F, int H, int W, int levels,
+                                 const int32_t* pairs, int P, const double* T, int level, float max_distance,
+                                 float depth_diff, double* sums, int32_t* index);
+int d3f_depth_odometry(const float* pyramid, const float* level_intrinsics, int F, int H, int W, int levels,
+                       const int32_t* pairs, int P, const double* T_init, const int32_t* iterations_host,
+                       float max_distance, float depth_diff, double* T, int32_t* count, double* rmse, int32_t* status,
+                       double* information, void* ws, size_t ws_bytes, void* stream);
+int d3f_depth_odometry_host(const float* pyramid, const float* level_intrinsics, int F, int H, int W, int levels,
+                            const int32_t* pairs, int P, const double* T_init, const int32_t* iterations_host,
+                            float max_distance, float depth_diff, double* T, int32_t* count, double* rmse,
+                            int32_t* status, double* information);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
