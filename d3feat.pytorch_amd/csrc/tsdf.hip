@@ -8,6 +8,8 @@
 //              blockIdx.y, uniform by construction: its frame range, the frame loop, the frame matrices and the
 //              intrinsics live in scalar registers and come through scalar loads; the depth images are gathered
 //              (neighbouring ix project to neighbouring pixels; 50 frames of 640 x 480 uint16 are 30 MB).
+//              d3f_tsdf_integrate_into is the same kernel with one difference: the thread first reads the (D, w) its
+//              voxel holds and continues the running mean from it; a volume that owns no frame is left alone.
 //   extract    count per block of 256 voxels -> exclusive scan of the block counts in two levels (groups of 1024
 //              counts, coalesced, then the group totals) -> emit, which recomputes the crossings and writes at
 //              group offset + block offset + in-block rank (ballots + a prefix over the four waves).  No atomic
@@ -99,7 +101,8 @@ void bounds_host(const DepthT* images, int F, int H, int W, const int32_t* frame
 }
 
 // ------------------------------------------------------------------------------------------------------- integrate
-template <typename DepthT>
+// kInto: D and w come in holding the voxel's stored value and the frames continue from it (d3f_tsdf_integrate_into)
+template <typename DepthT, bool kInto = false>
 __host__ __device__ inline void fuse_voxel(const Volumes& b, const Frames& fr, int v, int64_t local, float& D,
                                            float& w) {
   int ix, iy, iz, nx, ny, nz;
@@ -108,13 +111,20 @@ __host__ __device__ inline void fuse_voxel(const Volumes& b, const Frames& fr, i
   if (f0 < 0) f0 = 0;
   if (f1 > fr.F) f1 = fr.F;
   const float voxel = b.voxel[v];
-  integrate_voxel(lattice(b.origin[3 * v], voxel, ix), lattice(b.origin[3 * v + 1], voxel, iy),
-                  lattice(b.origin[3 * v + 2], voxel, iz), f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W,
-                  fr.depth_scale, fr.depth_max, fr.trunc[v], D, w);
+  const float x = lattice(b.origin[3 * v], voxel, ix), y = lattice(b.origin[3 * v + 1], voxel, iy);
+  const float z = lattice(b.origin[3 * v + 2], voxel, iz);
+  if (kInto)
+    integrate_voxel_into(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale,
+                         fr.depth_max, fr.trunc[v], D, w);
+  else
+    integrate_voxel(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale, fr.depth_max,
+                    fr.trunc[v], D, w);
 }
 
 // grid (blocks of the largest volume, V): the volume is blockIdx.y, so everything indexed by it is uniform
-template <typename DepthT>
+// kInto: the voxel's thread reads its stored (D, w) first and continues from it; a volume that owns no frame in the
+// call is left alone
+template <typename DepthT, bool kInto = false>
 __global__ void __launch_bounds__(kThreads) integrate_kernel(Volumes b, Frames fr, float* __restrict__ D_out,
                                                              float* __restrict__ w_out) {
   const int v = (int)blockIdx.y;
@@ -122,9 +132,62 @@ __global__ void __launch_bounds__(kThreads) integrate_kernel(Volumes b, Frames f
   const int64_t local = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (local >= count || start < 0 || start + local >= b.total) return;
   float D, w;
-  fuse_voxel<DepthT>(b, fr, v, local, D, w);
+  if (kInto) {
+    if (fr.frame_start[v + 1] <= fr.frame_start[v]) return;
+    D = D_out[start + local];
+    w = w_out[start + local];
+  }
+  fuse_voxel<DepthT, kInto>(b, fr, v, local, D, w);
   D_out[start + local] = D;
   w_out[start + local] = w;
+}
+
+template <bool kInto>
+int run_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                  const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+                  const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
+                  const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
+                  void* stream) {
+  if (!batch_ok(V, total_voxels) || max_volume_voxels < 0 || max_volume_voxels > total_voxels || !vol_start ||
+      !origin || !dims || !voxel || !trunc ||
+      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
+    return D3F_EINVAL;
+  if (total_voxels == 0 || max_volume_voxels == 0) return D3F_OK;
+  const int64_t blocks = voxel_blocks(max_volume_voxels);
+  if (!D || !w || blocks > 0x7fffffff) return D3F_EINVAL;
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  const dim3 grid((unsigned)blocks, (unsigned)V);
+  if (depth_is_f32)
+    integrate_kernel<float, kInto><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, fr, D, w);
+  else
+    integrate_kernel<uint16_t, kInto><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, fr, D, w);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+template <bool kInto>
+int run_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                       const int64_t* vol_start, int V, int64_t total_voxels, const float* intrinsics,
+                       const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel,
+                       const float* trunc, float depth_scale, float depth_max, float* D, float* w) {
+  if (!batch_ok(V, total_voxels) || !vol_start || !origin || !dims || !voxel || !trunc ||
+      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
+    return D3F_EINVAL;
+  if (total_voxels == 0) return D3F_OK;
+  if (!D || !w || !host_layout_ok(vol_start, dims, V, total_voxels)) return D3F_EINVAL;
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  for (int v = 0; v < V; ++v) {
+    if (kInto && frame_start[v + 1] <= frame_start[v]) continue;
+    for (int64_t g = vol_start[v]; g < vol_start[v + 1]; ++g) {
+      if (depth_is_f32)
+        fuse_voxel<float, kInto>(b, fr, v, g - vol_start[v], D[g], w[g]);
+      else
+        fuse_voxel<uint16_t, kInto>(b, fr, v, g - vol_start[v], D[g], w[g]);
+    }
+  }
+  return D3F_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------- extract
@@ -265,50 +328,39 @@ int d3f_tsdf_bounds_host(const void* depth, int depth_is_f32, int F, int H, int 
 }
 
 int d3f_tsdf_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                       const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                       const float* intrinsics, const float* volume_to_camera, const float* origin,
-                       const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max,
-                       float* D, float* w, void* stream) {
-  if (!batch_ok(V, total_voxels) || max_volume_voxels < 0 || max_volume_voxels > total_voxels || !vol_start ||
-      !origin || !dims || !voxel || !trunc ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (total_voxels == 0 || max_volume_voxels == 0) return D3F_OK;
-  const int64_t blocks = voxel_blocks(max_volume_voxels);
-  if (!D || !w || blocks > 0x7fffffff) return D3F_EINVAL;
-  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const dim3 grid((unsigned)blocks, (unsigned)V);
-  if (depth_is_f32)
-    integrate_kernel<float><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, fr, D, w);
-  else
-    integrate_kernel<uint16_t><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, fr, D, w);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
+    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
+    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+    float depth_scale, float depth_max, float* D, float* w, void* stream) {
+  return run_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
+                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream);
 }
 
 int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                            const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                            const float* intrinsics, const float* volume_to_camera, const float* origin,
-                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
-                            float depth_max, float* D, float* w, void* stream) {
+    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
+    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+    float depth_scale, float depth_max, float* D, float* w, void* stream) {
   (void)stream;
   (void)max_volume_voxels;
-  if (!batch_ok(V, total_voxels) || !vol_start || !origin || !dims || !voxel || !trunc ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (total_voxels == 0) return D3F_OK;
-  if (!D || !w || !host_layout_ok(vol_start, dims, V, total_voxels)) return D3F_EINVAL;
-  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  for (int v = 0; v < V; ++v)
-    for (int64_t g = vol_start[v]; g < vol_start[v + 1]; ++g) {
-      if (depth_is_f32)
-        fuse_voxel<float>(b, fr, v, g - vol_start[v], D[g], w[g]);
-      else
-        fuse_voxel<uint16_t>(b, fr, v, g - vol_start[v], D[g], w[g]);
-    }
-  return D3F_OK;
+  return run_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
+                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w);
+}
+
+int d3f_tsdf_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
+    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+    float depth_scale, float depth_max, float* D, float* w, void* stream) {
+  return run_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
+                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream);
+}
+
+int d3f_tsdf_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
+    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+    float depth_scale, float depth_max, float* D, float* w, void* stream) {
+  (void)stream;
+  (void)max_volume_voxels;
+  return run_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
+                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w);
 }
 
 size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels) {

@@ -67,17 +67,27 @@ D3F_HD inline void integrate_frame(float x, float y, float z, const float* M, co
   w = w + 1.0f;
 }
 
-// all frames [f0, f1) of a volume into the voxel at (x, y, z); images [F, H, W], M [F, 12], K [F, 4]
+// the frames [f0, f1) of a volume into the voxel at (x, y, z), continuing from the (D, w) given; images [F, H, W],
+// M [F, 12], K [F, 4].  The running mean is sequential over the frames, so the frames [f0, k) from (0, 0) and then
+// [k, f1) from their result give exactly what [f0, f1) gives from (0, 0) (d3f_tsdf_integrate_into).
+template <typename DepthT>
+D3F_HD inline void integrate_voxel_into(float x, float y, float z, int f0, int f1, const float* M, const float* K,
+                                        const DepthT* images, int H, int W, float depth_scale, float depth_max,
+                                        float trunc, float& D, float& w) {
+  const size_t pixels = (size_t)H * (size_t)W;
+  for (int f = f0; f < f1; ++f)
+    integrate_frame(x, y, z, M + 12 * (size_t)f, K + 4 * (size_t)f, images + pixels * (size_t)f, H, W, depth_scale,
+                    depth_max, trunc, D, w);
+}
+
+// all frames [f0, f1) of a volume into the voxel at (x, y, z), from D = 0, w = 0
 template <typename DepthT>
 D3F_HD inline void integrate_voxel(float x, float y, float z, int f0, int f1, const float* M, const float* K,
                                    const DepthT* images, int H, int W, float depth_scale, float depth_max,
                                    float trunc, float& D, float& w) {
   D = 0.0f;
   w = 0.0f;
-  const size_t pixels = (size_t)H * (size_t)W;
-  for (int f = f0; f < f1; ++f)
-    integrate_frame(x, y, z, M + 12 * (size_t)f, K + 4 * (size_t)f, images + pixels * (size_t)f, H, W, depth_scale,
-                    depth_max, trunc, D, w);
+  integrate_voxel_into(x, y, z, f0, f1, M, K, images, H, W, depth_scale, depth_max, trunc, D, w);
 }
 
 // the volume of global voxel g / of frame f: the last v with start[v] <= i (start rises; empty ranges are skipped)

@@ -14,7 +14,9 @@ only for the bricks of 8 x 8 x 8 voxels near a surface (``ops.tsdf_allocate`` / 
 the memory.  Colour is not part of this.
 
 ``track_sequence`` gives the camera poses of a sequence that comes without them: frame-to-frame depth odometry
-(``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence.
+(``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence; with
+``model=`` every frame is tracked against a ray-cast of its fragment's TSDF volume as well (``ops.tsdf_raycast``;
+csrc/tsdf_raycast.hpp has the rule).  ``render_views`` ray-casts volumes from 4x4 poses.
 """
 import os
 import re
@@ -277,8 +279,131 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
 DEFAULT_TRACK_BYTES = 1 << 30    # the depth pyramid of the frames tracked in one call (4 bytes per pixel, about 4/3 H W)
 
 
+DEFAULT_MODEL = dict(frames_per_fragment=50, voxel=0.01, trunc=None, margin=None, step=None,
+                     max_bytes=DEFAULT_MAX_BYTES)
+
+
+def render_views(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume=None,
+                 device='cuda', **raycast):
+    """Depth images f32 [R,H,W] in metres (0: no surface) of dense TSDF volumes seen from the camera-to-volume 4x4
+    ``poses`` [R,4,4]: ``ops.tsdf_raycast`` (csrc/tsdf_raycast.hpp has the rule) on the device, where D and w are device
+    tensors and so is the result; ``device='cpu'`` runs ``ops.tsdf_raycast_numpy`` on arrays.  ``view_volume`` [R] names
+    every view's volume (None: one view per volume).  ``**raycast``: ``step``, ``depth_min``, ``depth_max``,
+    ``min_weight``, ``normals`` (then ``(depth, normals f32 [R,H,W,3])``), ``clip``."""
+    from .. import ops
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    cast = ops.tsdf_raycast_numpy if _is_cpu(device) else ops.tsdf_raycast
+    return cast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume, **raycast)
+
+
+def _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, odometry):
+    """``(T f64 [F-1,4,4], status int32 [F-1])`` of the consecutive pairs (f+1, f), every pair from the identity, in
+    chunks whose pyramid fits ``max_bytes``."""
+    from .. import ops
+    F = depth.shape[0]
+    frame_bytes = 4 * ops.depth_pyramid_pixels(depth.shape[1], depth.shape[2], levels)
+    per_chunk = max(2, int(max_bytes) // max(frame_bytes, 1))
+    T = np.broadcast_to(np.eye(4), (max(F - 1, 0), 4, 4)).copy()
+    status = np.zeros(max(F - 1, 0), dtype=np.int32)
+    for lo in range(0, F - 1, per_chunk - 1):
+        hi = min(lo + per_chunk, F)                       # frames [lo, hi): the pairs (lo+1, lo) .. (hi-1, hi-2)
+        pairs = np.stack([np.arange(1, hi - lo), np.arange(0, hi - lo - 1)], axis=1)
+        args = (depth[lo:hi], K[lo:hi], levels, depth_scale, depth_max, depth_diff)
+        if cpu:
+            res = ops.depth_odometry_numpy(ops.depth_pyramid_numpy(*args), pairs, None, iterations, **odometry)
+        else:
+            res = [t.cpu().numpy() for t in ops.depth_odometry(ops.depth_pyramid(*args), pairs, None, iterations,
+                                                               **odometry)]
+        T[lo:hi - 1], status[lo:hi - 1] = res[0], res[3]
+    return T, status
+
+
+def _metres(frames, depth_scale):
+    """f32 metres of depth frames, the conversion of csrc/tsdf.hpp's depth_value."""
+    return frames.astype(np.float32) / np.float32(depth_scale) if frames.dtype == np.uint16 else frames
+
+
+def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, depth_max, depth_diff, odometry):
+    """The frame-to-model pass of ``track_sequence``: ``(T f64 [F-1,4,4], model_status int32 [F-1])``.  ``T_ff`` are the
+    frame-to-frame poses actually used (the identity where that pass failed)."""
+    from .. import ops
+    unknown = set(model) - set(DEFAULT_MODEL)
+    if unknown:
+        raise ValueError("model: unknown keys %s (known: %s)" % (sorted(unknown), sorted(DEFAULT_MODEL)))
+    m = dict(DEFAULT_MODEL)
+    m.update(model)
+    k, voxel = int(m['frames_per_fragment']), float(m['voxel'])
+    if k < 1:
+        raise ValueError("model: frames_per_fragment must be at least 1")
+    trunc = 5.0 * voxel if m['trunc'] is None else float(m['trunc'])
+    margin = trunc if m['margin'] is None else float(m['margin'])
+    max_bytes = int(m['max_bytes'])
+    F, H, W = depth.shape
+    frame_start = np.asarray(list(range(0, F, k)) + [F], dtype=np.int64)
+    G = frame_start.size - 1
+    T = T_ff.copy()
+    model_status = np.zeros(max(F - 1, 0), dtype=np.int32)
+    model_status[frame_start[1:-1] - 1] = -1              # the pairs that cross a fragment boundary
+    # every camera in the frame of its fragment's first camera, chained frame to frame: where the volumes go
+    L = np.broadcast_to(np.eye(4), (F, 4, 4)).copy()
+    for g in range(G):
+        for f in range(int(frame_start[g]) + 1, int(frame_start[g + 1])):
+            L[f] = L[f - 1] @ T_ff[f - 1]
+    frame_bytes = int(depth[0].nbytes)
+    bounds = []
+    for v, e in _frame_groups(frame_start, frame_bytes, max_bytes):
+        lo, hi = int(frame_start[v]), int(frame_start[e])
+        args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], L[lo:hi], depth_scale, depth_max)
+        bounds.append(ops.tsdf_bounds_numpy(*args) if cpu else ops.tsdf_bounds(*args).cpu().numpy())
+    bounds = np.concatenate(bounds, 0).astype(np.float64)
+    bounds[:, :3] -= margin
+    bounds[:, 3:] += margin
+    origin, dims = place_volumes(bounds, voxel)
+    _check_fits(dims, voxel, max_bytes, "model of fragment")  # before anything is launched
+    sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
+    integrate = ops.tsdf_numpy if cpu else ops.tsdf_integrate
+    eye = np.eye(4)
+    for v, e in _size_batches(sizes, max_bytes):
+        n = e - v
+        first, count = frame_start[v:e], np.diff(frame_start[v:e + 1])
+        vol = (origin[v:e], dims[v:e], voxel, trunc, depth_scale, depth_max)
+        # step 0: the first frame of every fragment of the group, at the identity
+        D, w, vs = integrate(depth[first], np.arange(n + 1), K[first], np.broadcast_to(eye, (n, 4, 4)), *vol)[:3]
+        for s in range(1, int(count.max())):
+            live = np.nonzero(count > s)[0]                # the fragments that have a frame s
+            f = first[live] + s
+            A = live.size
+            view = (D, w, vs, origin[v:e], dims[v:e], voxel, trunc, K[f - 1], L[f - 1], H, W, live)
+            frames = _metres(depth[f], depth_scale)
+            pairs = np.stack([np.arange(A), A + np.arange(A)], axis=1)      # (frame s, the render of frame s - 1)
+            if cpu:
+                both = np.concatenate([frames, ops.tsdf_raycast_numpy(*view, step=m['step'], depth_max=depth_max)])
+                pyr = ops.depth_pyramid_numpy(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
+                                              depth_diff)
+                res = ops.depth_odometry_numpy(pyr, pairs, T_ff[f - 1], iterations, **odometry)
+            else:
+                import torch
+                render = ops.tsdf_raycast(*view, step=m['step'], depth_max=depth_max)
+                both = torch.cat([torch.from_numpy(np.ascontiguousarray(frames)).to(render.device), render])
+                pyr = ops.depth_pyramid(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
+                                        depth_diff)
+                res = ops.depth_odometry(pyr, pairs, T_ff[f - 1], iterations, **odometry)
+                res = (res[0].cpu().numpy(), None, None, res[3].cpu().numpy())   # the one read-back of the step
+            for i in range(A):
+                model_status[f[i] - 1] = res[3][i]
+                if res[3][i] == 0:
+                    T[f[i] - 1] = res[0][i]
+                L[f[i]] = L[f[i] - 1] @ T[f[i] - 1]
+            # frame s of every live fragment into its volume under inv(L): the others own no frame and keep theirs
+            owns = np.zeros(n + 1, dtype=np.int64)
+            owns[live + 1] = 1
+            integrate(depth[f], np.cumsum(owns), K[f], np.stack([rigid_inverse(L[j]) for j in f]), *vol, into=(D, w))
+        del D, w
+    return T, model_status
+
+
 def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT_TRACK_BYTES, depth_scale=1000.0,
-                   depth_max=DEFAULT_DEPTH_MAX, depth_diff=0.05, **odometry):
+                   depth_max=DEFAULT_DEPTH_MAX, depth_diff=0.05, model=None, **odometry):
     """``(poses f64 [F,4,4], status int32 [F-1])``: camera poses of a depth sequence by frame-to-frame depth odometry
     (``ops.depth_odometry``: projective point-to-plane ICP over a depth pyramid, every pair from the identity).
 
@@ -291,8 +416,23 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     least); a pair's result does not depend on its chunk.  ``device='cuda'`` runs the HIP kernels, ``device='cpu'``
     the NumPy restatement (equal to rounding).
 
-    ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it; drift
-    accumulates from frame to frame and nothing closes a loop."""
+    ``model=dict(frames_per_fragment=50, voxel=0.01, trunc=None, margin=None, step=None)`` (any subset; also
+    ``max_bytes`` for the volumes of one group, as in ``fuse_fragments``) adds a frame-to-MODEL pass, KinectFusion's, and
+    returns ``(poses, status, model_status)``.  Every fragment gets a dense volume in the frame of its first camera,
+    placed from the frame-to-frame poses (``place_volumes``, widened by ``margin``, default ``trunc``, itself ``5 *
+    voxel`` by default).  The first frame is integrated at the identity; then, frame by frame and for all fragments of a
+    group at once, the volume is ray-cast from the refined pose of the previous frame (``ops.tsdf_raycast``, ``step``
+    default ``trunc / 2``), the frame is tracked against that render by the same odometry, started from its
+    frame-to-frame pose, and integrated into the volume under the result (``ops.tsdf_integrate(..., into=)``).  A pair
+    tracked against the model with status 0 takes the model's pose; any other keeps its frame-to-frame pose.
+    ``status`` is then the status of the pose actually used; ``model_status`` int32 [F-1] holds 0 where the model's pose
+    was used, the tracker's ``ODO_ST_*`` where it failed against the render, and -1 for the pairs that cross a fragment
+    boundary, which chain by their frame-to-frame pose: the model restarts with every fragment.  One read-back of poses
+    and statuses per step.  Use it where the depth is noisy (the README has the figures): on clean depth the model's
+    voxel quantisation costs more than the drift it removes.
+
+    ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it.  Without
+    ``model`` drift accumulates from frame to frame; with it, from fragment to fragment; nothing closes a loop."""
     from .. import ops
     stride = int(stride)
     if stride < 1:
@@ -311,24 +451,19 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     iterations = odometry.pop('iterations', ops.ODO_ITERATIONS)
     levels = len(ops._odo_iterations(iterations))
     cpu = _is_cpu(device)
-    frame_bytes = 4 * ops.depth_pyramid_pixels(depth.shape[1], depth.shape[2], levels)
-    per_chunk = max(2, int(max_bytes) // max(frame_bytes, 1))
-    T = np.broadcast_to(np.eye(4), (max(F - 1, 0), 4, 4)).copy()
-    status = np.zeros(max(F - 1, 0), dtype=np.int32)
-    for lo in range(0, F - 1, per_chunk - 1):
-        hi = min(lo + per_chunk, F)                       # frames [lo, hi): the pairs (lo+1, lo) .. (hi-1, hi-2)
-        pairs = np.stack([np.arange(1, hi - lo), np.arange(0, hi - lo - 1)], axis=1)
-        args = (depth[lo:hi], K[lo:hi], levels, depth_scale, depth_max, depth_diff)
-        if cpu:
-            res = ops.depth_odometry_numpy(ops.depth_pyramid_numpy(*args), pairs, None, iterations, **odometry)
-        else:
-            res = [t.cpu().numpy() for t in ops.depth_odometry(ops.depth_pyramid(*args), pairs, None, iterations,
-                                                               **odometry)]
-        T[lo:hi - 1], status[lo:hi - 1] = res[0], res[3]
+    T, status = _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, odometry)
+    for f in range(F - 1):
+        if status[f] != 0:
+            T[f] = np.eye(4)
+    model_status = None
+    if model is not None:
+        T, model_status = _track_model(np.ascontiguousarray(depth), K, T, dict(model), levels, iterations, cpu,
+                                       depth_scale, depth_max, depth_diff, odometry)
+        status = np.where(model_status == 0, 0, status).astype(np.int32)
     poses = np.broadcast_to(np.eye(4), (F, 4, 4)).copy()
     for f in range(F - 1):
-        poses[f + 1] = poses[f] @ (T[f] if status[f] == 0 else np.eye(4))
-    return poses, status
+        poses[f + 1] = poses[f] @ T[f]
+    return (poses, status) if model is None else (poses, status, model_status)
 
 
 # ------------------------------------------------------------------------------------------------------ files

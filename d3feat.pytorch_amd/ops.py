@@ -3206,8 +3206,14 @@ TSDF_ST_OVERFLOW = 1          # D3F_TSDF_ST_OVERFLOW
 TSDF_MAX_VOLUMES = 65535
 
 
-def _tsdf_depth_array(depth):
-    """Depth frames as a host array [F,H,W], uint16 raw units or f32 metres (other floats become f32)."""
+def _tsdf_depth_array(depth, device_ok=False):
+    """Depth frames as a host array [F,H,W], uint16 raw units or f32 metres (other floats become f32).  With
+    ``device_ok`` a device f32 tensor [F,H,W] is passed through as it is (no copy to the host): what ``tsdf_raycast``
+    returns goes straight into ``depth_pyramid``."""
+    if device_ok and isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32:
+        if depth.dim() != 3:
+            raise ValueError("depth must be [F,H,W], got %s" % (tuple(depth.shape),))
+        return depth.detach().contiguous()
     if isinstance(depth, torch.Tensor):
         t = depth.detach().cpu()
         depth = t.view(torch.int16).numpy().view(np.uint16) if t.dtype in (torch.int16, torch.uint16) else t.numpy()
@@ -3309,15 +3315,34 @@ def tsdf_bounds_host(depth, frame_start, intrinsics, camera_to_volume, depth_sca
                         frame_start, intrinsics, camera_to_volume, depth_scale, depth_max)
 
 
+def _tsdf_into(into, total, device):
+    """The (D, w) of ``into=``: f32 tensors of ``total`` voxels on ``device``, contiguous -- they are written in place."""
+    if not isinstance(into, (tuple, list)) or len(into) != 2:
+        raise ValueError("into must be the pair (D, w) of an earlier integration")
+    for name, t in zip("Dw", into):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("into: %s must be a contiguous float32 tensor" % name)
+        if t.device.type != torch.device(device).type:
+            raise ValueError("into: %s is on %s, the call runs on %s" % (name, t.device, device))
+        if int(t.numel()) != total:
+            raise ValueError("into: %s holds %d voxels, dims give %d" % (name, t.numel(), total))
+    return into[0].view(-1), into[1].view(-1)
+
+
 def _tsdf_integrate(fn, name, device, stream, depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel,
-                    trunc, depth_scale, depth_max):
+                    trunc, depth_scale, depth_max, into=None):
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
     total = int(vol_start[-1])
     td, tfs, tK, tM, to, tn, tvx, ttr, tvs = _on(device, d, fs, K, M, o, n, vx, tr, vol_start)
-    D = torch.empty(total, dtype=torch.float32, device=device)
-    w = torch.empty(total, dtype=torch.float32, device=device)
+    if into is None:
+        D = torch.empty(total, dtype=torch.float32, device=device)
+        w = torch.empty(total, dtype=torch.float32, device=device)
+    else:
+        D, w = _tsdf_into(into, total, device)
+        name = name.replace("integrate", "integrate_into")          # d3f_tsdf_integrate_into[_host]
+        fn = getattr(_native.lib(), name)
     _native.check(fn(_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), _p(tvs), V, total,
                      int(np.diff(vol_start).max()), _p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr), float(depth_scale),
                      float(depth_max), _p(D), _p(w), stream), name)
@@ -3325,7 +3350,7 @@ def _tsdf_integrate(fn, name, device, stream, depth, frame_start, intrinsics, vo
 
 
 def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
-                   depth_max=TSDF_DEPTH_MAX):
+                   depth_max=TSDF_DEPTH_MAX, into=None):
     """Fuse depth frames into V dense volumes in ONE launch (d3f_tsdf_integrate; the rule is csrc/tsdf.hpp).
 
     ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres; ``frame_start`` [V+1]: volume v
@@ -3333,20 +3358,26 @@ def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dim
     ``volume_to_camera`` [F,3,4] / [F,4,4] (f64 is rounded to f32 once, here); ``origin`` [V,3], ``dims`` [V,3] = nx,
     ny, nz (host values), ``voxel`` and ``trunc`` a number or [V].  Returns device tensors ``(D f32 [total], w f32
     [total], vol_start int64 [V+1])``: volume v is ``D[vol_start[v]:vol_start[v+1]].view(nz, ny, nx)``.  One thread owns
-    a voxel for all frames: written once, no atomics, bit-identical from run to run and to the host twin."""
+    a voxel for all frames: written once, no atomics, bit-identical from run to run and to the host twin.
+
+    ``into=(D, w)``: device tensors of an earlier call over the same ``origin`` / ``dims`` / ``voxel`` / ``trunc``; the
+    frames are integrated into them IN PLACE (d3f_tsdf_integrate_into) and the same tensors are returned.  The running
+    mean is sequential over frames, so the frames [0, k) and then [k, F) ``into`` the result give the volume of one call
+    over [0, F) bit for bit.  A volume that owns no frame in the call keeps its values."""
     dev = _tsdf_device()
     with _region("tsdf_integrate"):
         return _tsdf_integrate(_native.lib().d3f_tsdf_integrate, "d3f_tsdf_integrate", dev, _stream(), depth,
                                frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                               depth_max)
+                               depth_max, into)
 
 
 def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc,
-                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX):
-    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host): CPU tensors out, no GPU call."""
+                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, into=None):
+    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host / d3f_tsdf_integrate_into_host): CPU tensors out
+    (``into``: CPU tensors, written in place), no GPU call."""
     return _tsdf_integrate(_native.lib().d3f_tsdf_integrate_host, "d3f_tsdf_integrate_host", torch.device("cpu"), None,
                            depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                           depth_max)
+                           depth_max, into)
 
 
 def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
@@ -3432,14 +3463,18 @@ def _lattice_axes(local, n, o, vx):
     return xyz, (ix, iy, iz)
 
 
-def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max):
-    """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1)."""
+def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max, start=None):
+    """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1);
+    ``start = (D, w)``: integrate_voxel_into, continuing from these values."""
     x, y, z = xyz
     H, W = d.shape[1:]
     f32 = np.float32
     scale, dmax, half, one = f32(depth_scale), f32(depth_max), f32(0.5), f32(1.0)
-    D = np.zeros(x.shape, dtype=f32)
-    w = np.zeros(x.shape, dtype=f32)
+    if start is None:
+        D = np.zeros(x.shape, dtype=f32)
+        w = np.zeros(x.shape, dtype=f32)
+    else:
+        D, w = start
     with np.errstate(all='ignore'):
         for f in range(f0, f1):
             m = M[f]
@@ -3462,22 +3497,36 @@ def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max):
 
 
 def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
-               depth_max=TSDF_DEPTH_MAX, chunk=1 << 21):
+               depth_max=TSDF_DEPTH_MAX, chunk=1 << 21, into=None):
     """The contract of ``tsdf_integrate`` in NumPy: ``(D f32 [total], w f32 [total], vol_start int64 [V+1])``.  Every
     product and sum is spelled out in f32 in the order of csrc/tsdf.hpp (no ``@``), so the result equals the kernel's
-    bit for bit.  ``chunk`` voxels are swept at a time."""
+    bit for bit.  ``chunk`` voxels are swept at a time.  ``into=(D, w)``: contiguous f32 arrays of an earlier call,
+    written in place and returned, as ``tsdf_integrate`` does with its tensors."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
-    D_all = np.zeros(int(vol_start[-1]), dtype=np.float32)
-    w_all = np.zeros(int(vol_start[-1]), dtype=np.float32)
+    total = int(vol_start[-1])
+    if into is None:
+        D_all = np.zeros(total, dtype=np.float32)
+        w_all = np.zeros(total, dtype=np.float32)
+    else:
+        if not isinstance(into, (tuple, list)) or len(into) != 2:
+            raise ValueError("into must be the pair (D, w) of an earlier integration")
+        for name, a in zip("Dw", into):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or \
+                    not a.flags.writeable or a.size != total:
+                raise ValueError("into: %s must be a writeable contiguous float32 array of %d voxels" % (name, total))
+        D_all, w_all = into[0].reshape(-1), into[1].reshape(-1)
     for v in range(V):
+        if into is not None and fs[v + 1] <= fs[v]:
+            continue
         first, last = int(vol_start[v]), int(vol_start[v + 1])
         for s in range(first, last, int(chunk)):
             e = min(s + int(chunk), last)
             xyz, _ = _lattice_axes(np.arange(s, e, dtype=np.int64) - vol_start[v], n[v], o[v], vx[v])
+            start = None if into is None else (D_all[s:e].copy(), w_all[s:e].copy())
             D_all[s:e], w_all[s:e] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v], depth_scale,
-                                                      depth_max)
+                                                      depth_max, start)
     return D_all, w_all, vol_start
 
 
@@ -4133,6 +4182,261 @@ def tsdf_mesh_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Ray-casting dense TSDF volumes: a volume plus a camera pose gives a depth image (csrc/tsdf_raycast.hpp has the rule;
+# csrc/tsdf_raycast.hip the kernel)
+# ---------------------------------------------------------------------------------------------------------------
+RAYCAST_MAX_SAMPLES = 65536   # D3F_RAYCAST_MAX_SAMPLES: samples of one ray at most
+RAYCAST_DEPTH_MIN = 0.1       # default depth_min in metres: where every ray starts
+RAYCAST_MAX_VIEWS = 65535
+
+
+def _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step, depth_min, depth_max):
+    """Host form of the view arguments: (view_volume int32 [R], K f32 [R,4], C f32 [R,12], step f32 [V])."""
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    H, W = int(height), int(width)
+    if H < 1 or W < 1 or H * W > 1 << 30:
+        raise ValueError("height and width must be positive and hold at most 2^30 pixels, got %d x %d" % (H, W))
+    vv = np.arange(V, dtype=np.int64) if view_volume is None else np.asarray(host(view_volume), dtype=np.int64).reshape(-1)
+    R = vv.size
+    if R > RAYCAST_MAX_VIEWS:
+        raise ValueError("at most %d views per call, got %d" % (RAYCAST_MAX_VIEWS, R))
+    if R and (vv.min() < 0 or vv.max() >= V):
+        raise ValueError("view_volume must name volumes in 0..%d, got %s" % (V - 1, vv.tolist()))
+    K = np.asarray(host(intrinsics), dtype=np.float32)
+    K = np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 4), (R, 4)))
+    c = np.asarray(host(camera_to_volume))
+    if c.ndim == 2 and c.shape in ((4, 4), (3, 4)) and R == 1:
+        c = c[None]
+    if c.ndim == 3 and c.shape[1:] in ((4, 4), (3, 4)):
+        c = c[:, :3, :]
+    c = np.ascontiguousarray(c.astype(np.float32).reshape(-1, 12))        # rounded to f32 once, here
+    if c.shape[0] != R:
+        raise ValueError("%d camera_to_volume matrices for %d views" % (c.shape[0], R))
+    dmin, dmax = np.float32(depth_min), np.float32(depth_max)
+    if not (dmin >= 0 and dmax >= dmin and np.isfinite(dmax)):
+        raise ValueError("0 <= depth_min <= depth_max (finite) is required, got %g and %g" % (depth_min, depth_max))
+    if step is None:
+        if trunc is None:
+            raise ValueError("step=None takes trunc / 2: give trunc or step")
+        st = np.broadcast_to(np.asarray(host(trunc), dtype=np.float32).reshape(-1), (V,)) / np.float32(2.0)
+    else:
+        st = np.broadcast_to(np.asarray(host(step), dtype=np.float32).reshape(-1), (V,))
+    st = np.ascontiguousarray(st, dtype=np.float32)
+    if not (st > 0).all() or not ((dmax - dmin) / st <= np.float32(RAYCAST_MAX_SAMPLES)).all():
+        raise ValueError("every step must be positive and give at most %d samples between depth_min and depth_max, "
+                         "got %s" % (RAYCAST_MAX_SAMPLES, st.tolist()))
+    return vv.astype(np.int32), K, c, st, H, W
+
+
+def _tsdf_raycast(host, device, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height,
+                  width, view_volume, step, depth_min, depth_max, min_weight, normals, clip):
+    if host:
+        D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (D, w))
+    for name, t in zip("Dw", (D, w)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
+            raise ValueError("%s must be a float32 tensor on %s: the volume stays where it is" % (name, device))
+    D, w = D.contiguous().view(-1), w.contiguous().view(-1)
+    V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    total = int(vs[-1])
+    if int(D.numel()) != total or int(w.numel()) != total:
+        raise ValueError("D and w must hold the %d voxels of dims, got %d and %d" % (total, D.numel(), w.numel()))
+    if V > TSDF_MAX_VOLUMES:
+        raise ValueError("at most %d volumes per call" % TSDF_MAX_VOLUMES)
+    vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                                        depth_min, depth_max)
+    R = vv.size
+    depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
+    nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
+    if R:
+        to, tn, tvx, tvs, tvv, tK, tC, tst = _on(device, o, n, vx, vs, vv, K, C, st)
+        _check_vol_start(vol_start, tvs)
+        L = _native.lib()
+        fn, name = ((L.d3f_tsdf_raycast_host, "d3f_tsdf_raycast_host") if host else
+                    (L.d3f_tsdf_raycast, "d3f_tsdf_raycast"))
+        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, _p(tvv), R, H, W, _p(tK), _p(tC),
+                         _p(tst), float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), _p(depth),
+                         _p(nrm), None if host else _stream()), name)
+    return (depth, nrm) if normals else depth
+
+
+def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
+                 view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0,
+                 normals=False, clip=True):
+    """Ray-cast R views of V dense TSDF volumes in ONE launch (d3f_tsdf_raycast; the rule is csrc/tsdf_raycast.hpp):
+    ``depth`` f32 [R,H,W] on the device, the camera z-depth in metres of the surface along every pixel's ray, 0 where
+    the ray meets none -- what ``depth_pyramid`` takes as f32 metres.  ``normals=True`` returns ``(depth, normals f32
+    [R,H,W,3])``: unit normals in the camera frame, towards positive D (out of the surface, facing the camera: the sign
+    of ``tsdf_mesh``'s normals and of the odometry's), zeros where there is no hit or the gradient is not defined.
+
+    ``D``, ``w``, ``vol_start``, ``origin``, ``dims``, ``voxel`` as ``tsdf_integrate`` returns and takes them; D and w
+    are device tensors and stay where they are.  ``intrinsics`` [4] or [R,4] = fx, fy, cx, cy; ``camera_to_volume``
+    [R,3,4] / [R,4,4] maps a view's camera into the frame of its volume (f64 is rounded to f32 once, here);
+    ``view_volume`` [R]: the volume of every view, in any order, a volume any number of times (None: R = V, one view per
+    volume).  A ray samples the trilinear D at ``depth_min + step k <= depth_max``; ``step`` (a number or [V]) defaults
+    to ``trunc / 2``.  A sample counts when all 8 corners of its cell have ``w >= min_weight``; |D| < 1 is not asked
+    for.  A positive sample followed by a non-positive one is a hit at the interpolated zero; a ray that first meets a
+    surface from behind (a negative sample not preceded by a positive one) ends without a hit.  ``clip=False`` turns
+    off the clipping of every ray's sample range to the volume's box, which changes the time and no bit.
+
+    One thread per ray, a wave per 8 x 8 pixels; no atomics, nothing read back: a view's image is bit-identical alone,
+    in any batch, from run to run, and to ``tsdf_raycast_host`` and ``tsdf_raycast_numpy``.  R = 0 returns empty
+    tensors without a launch."""
+    dev = _tsdf_device()
+    with _region("tsdf_raycast"):
+        return _tsdf_raycast(False, dev, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume,
+                             height, width, view_volume, step, depth_min, depth_max, min_weight, normals, clip)
+
+
+def tsdf_raycast_host(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
+                      view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX,
+                      min_weight=1.0, normals=False, clip=True):
+    """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host): CPU tensors (or arrays) in, CPU tensors out, no GPU
+    call."""
+    return _tsdf_raycast(True, torch.device("cpu"), D, w, vol_start, origin, dims, voxel, trunc, intrinsics,
+                         camera_to_volume, height, width, view_volume, step, depth_min, depth_max, min_weight, normals,
+                         clip)
+
+
+def _raycast_lerp(a, b, t):
+    return a + t * (b - a)
+
+
+def _raycast_sample_numpy(Dv, wv, n, o, vx, qx, qy, qz, min_weight):
+    """sample() of csrc/tsdf_raycast.hpp for the f32 points (qx, qy, qz): (valid bool, value f32)."""
+    f32 = np.float32
+    nx, ny, nz = (int(a) for a in n)
+    one = f32(1.0)
+    gx, gy, gz = (qx - o[0]) / vx, (qy - o[1]) / vx, (qz - o[2]) / vx
+    ix, iy, iz = np.floor(gx), np.floor(gy), np.floor(gz)
+    inside = ((ix >= 0) & (ix + one < f32(nx)) & (iy >= 0) & (iy + one < f32(ny)) & (iz >= 0) & (iz + one < f32(nz)))
+    zero = f32(0.0)
+    i = (np.where(inside, ix, zero).astype(np.int64) + nx * np.where(inside, iy, zero).astype(np.int64)
+         + nx * ny * np.where(inside, iz, zero).astype(np.int64))
+    if nx < 2 or ny < 2 or nz < 2:                    # no cell: nothing is inside, and nothing is read
+        return np.zeros(i.shape, dtype=bool), np.zeros(i.shape, dtype=f32)
+    sy, sz = nx, nx * ny
+    corners = (0, 1, sy, sy + 1, sz, sz + 1, sz + sy, sz + sy + 1)
+    d000, d100, d010, d110, d001, d101, d011, d111 = (Dv[i + c] for c in corners)
+    weighted = np.ones(i.shape, dtype=bool)
+    for c in corners:
+        weighted &= wv[i + c] >= min_weight
+    fx, fy, fz = gx - ix, gy - iy, gz - iz
+    e00, e10 = _raycast_lerp(d000, d100, fx), _raycast_lerp(d010, d110, fx)
+    e01, e11 = _raycast_lerp(d001, d101, fx), _raycast_lerp(d011, d111, fx)
+    value = _raycast_lerp(_raycast_lerp(e00, e10, fy), _raycast_lerp(e01, e11, fy), fz)
+    return inside & weighted, value.astype(f32)
+
+
+def _raycast_point_numpy(C, x, y, z):
+    """ray_point() of csrc/tsdf_raycast.hpp."""
+    X, Y = x * z, y * z
+    return tuple(((C[4 * r] * X + C[4 * r + 1] * Y) + C[4 * r + 2] * z) + C[4 * r + 3] for r in range(3))
+
+
+def _raycast_clip_numpy(n, o, vx, C, x, y, step, dmin, dmax):
+    """clip_range() of csrc/tsdf_raycast.hpp: (k0, k1) int64 per ray."""
+    f32 = np.float32
+    zin = np.full(x.shape, dmin, dtype=f32)
+    zout = np.full(x.shape, dmax, dtype=f32)
+    empty = np.zeros(x.shape, dtype=bool)
+    for a in range(3):
+        d = (C[4 * a] * x + C[4 * a + 1] * y) + C[4 * a + 2]
+        oa = C[4 * a + 3]
+        lo, hi = o[a] - vx, o[a] + vx * f32(n[a])
+        still = d == 0
+        empty |= still & ((oa < lo) | (oa > hi))
+        ta, tb = (lo - oa) / d, (hi - oa) / d
+        zin = np.where(still, zin, np.fmax(zin, np.fmin(ta, tb)))      # fmin / fmax drop a NaN, as fminf / fmaxf do
+        zout = np.where(still, zout, np.fmin(zout, np.fmax(ta, tb)))
+    lo = np.floor((zin - dmin) / step) - f32(1.0)
+    hi = np.ceil((zout - dmin) / step) + f32(1.0)
+    lo = np.fmin(np.fmax(lo, f32(0.0)), f32(RAYCAST_MAX_SAMPLES + 1))
+    hi = np.fmax(np.fmin(hi, f32(RAYCAST_MAX_SAMPLES)), f32(-1.0))
+    return lo.astype(np.int64), np.where(empty, -1, hi.astype(np.int64))
+
+
+def _raycast_view_numpy(Dv, wv, n, o, vx, K, C, H, W, step, dmin, dmax, min_weight, clip, normals):
+    """cast_ray() of csrc/tsdf_raycast.hpp for every pixel of one view: (depth f32 [H,W], normals f32 [H,W,3] | None)."""
+    f32 = np.float32
+    P = H * W
+    depth = np.zeros(P, dtype=f32)
+    nrm = np.zeros((P, 3), dtype=f32) if normals else None
+    u = np.broadcast_to(np.arange(W, dtype=f32)[None, :], (H, W)).reshape(-1)
+    v = np.broadcast_to(np.arange(H, dtype=f32)[:, None], (H, W)).reshape(-1)
+    x, y = (u - K[2]) / K[0], (v - K[3]) / K[1]
+    if clip:
+        k0, k1 = _raycast_clip_numpy(n, o, vx, C, x, y, step, dmin, dmax)
+    else:
+        k0, k1 = np.zeros(P, dtype=np.int64), np.full(P, RAYCAST_MAX_SAMPLES, dtype=np.int64)
+    positive = np.zeros(P, dtype=bool)
+    t0 = np.zeros(P, dtype=f32)
+    done = k1 < k0
+    for k in range(int(k0.min()) if P else 0, (int(k1.max()) if P else -1) + 1):
+        z = dmin + step * f32(k)
+        if not z <= dmax or done.all():
+            break
+        idx = np.nonzero(~done & (k0 <= k) & (k <= k1))[0]
+        if idx.size == 0:
+            continue
+        q = _raycast_point_numpy(C, x[idx], y[idx], z)
+        valid, t1 = _raycast_sample_numpy(Dv, wv, n, o, vx, q[0], q[1], q[2], min_weight)
+        hit = valid & positive[idx] & ~(t1 > 0)
+        a0, a1 = t0[idx][hit], t1[hit]
+        depth[idx[hit]] = (z - step) + step * (a0 / (a0 - a1))
+        end = valid & ~hit & (t1 < 0)
+        done[idx[hit | end]] = True
+        positive[idx] = valid & (t1 > 0)
+        t0[idx] = np.where(valid, t1, t0[idx])
+    depth = np.where((depth > 0) & (depth <= dmax), depth, f32(0.0)).astype(f32)
+    if normals:
+        idx = np.nonzero(depth > 0)[0]
+        q = _raycast_point_numpy(C, x[idx], y[idx], depth[idx])
+        ok = np.ones(idx.size, dtype=bool)
+        g = []
+        for a in range(3):
+            p, m = list(q), list(q)
+            p[a], m[a] = q[a] + vx, q[a] - vx
+            okp, vp = _raycast_sample_numpy(Dv, wv, n, o, vx, p[0], p[1], p[2], min_weight)
+            okm, vm = _raycast_sample_numpy(Dv, wv, n, o, vx, m[0], m[1], m[2], min_weight)
+            ok &= okp & okm
+            g.append(vp - vm)
+        nc = [(C[j] * g[0] + C[4 + j] * g[1]) + C[8 + j] * g[2] for j in range(3)]
+        ln = np.sqrt((nc[0] * nc[0] + nc[1] * nc[1]) + nc[2] * nc[2])
+        ok &= (ln > 0) & (ln <= np.finfo(f32).max)
+        for j in range(3):
+            nrm[idx, j] = np.where(ok, nc[j] / ln, f32(0.0))
+    return depth.reshape(H, W), (nrm.reshape(H, W, 3) if normals else None)
+
+
+def tsdf_raycast_numpy(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
+                       view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX,
+                       min_weight=1.0, normals=False, clip=True):
+    """The contract of ``tsdf_raycast`` in NumPy: ``depth`` f32 [R,H,W] (and ``normals`` f32 [R,H,W,3]), every f32
+    operation in the order of csrc/tsdf_raycast.hpp, so the result equals the kernel's bit for bit."""
+    D = np.ascontiguousarray(_host_array(D), dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(_host_array(w), dtype=np.float32).reshape(-1)
+    V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    if D.size != int(vs[-1]) or w.size != int(vs[-1]):
+        raise ValueError("D and w must hold the %d voxels of dims, got %d and %d" % (vs[-1], D.size, w.size))
+    vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                                        depth_min, depth_max)
+    f32 = np.float32
+    depth = np.zeros((vv.size, H, W), dtype=f32)
+    nrm = np.zeros((vv.size, H, W, 3), dtype=f32) if normals else None
+    with np.errstate(all='ignore'):
+        for r, vol in enumerate(vv):
+            a, b = int(vs[vol]), int(vs[vol + 1])
+            depth[r], nr = _raycast_view_numpy(D[a:b], w[a:b], n[vol], o[vol], vx[vol], K[r], C[r], H, W, st[vol],
+                                               f32(depth_min), f32(depth_max), f32(min_weight), clip, normals)
+            if normals:
+                nrm[r] = nr
+    return (depth, nrm) if normals else depth
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Depth odometry: camera poses of a depth sequence by projective point-to-plane ICP over a depth pyramid
 # (csrc/odometry.hpp has the rule; csrc/odometry.hip the kernels)
 # ---------------------------------------------------------------------------------------------------------------
@@ -4183,9 +4487,10 @@ def _odo_check_levels(H, W, levels):
     return levels
 
 
-def _odo_frames(depth, intrinsics):
-    """Host form of the frames: (depth [F,H,W] uint16 / f32, K f32 [F,4])."""
-    d = _tsdf_depth_array(depth)
+def _odo_frames(depth, intrinsics, device_ok=False):
+    """Host form of the frames: (depth [F,H,W] uint16 / f32, K f32 [F,4]); with ``device_ok`` a device f32 tensor stays
+    one."""
+    d = _tsdf_depth_array(depth, device_ok)
     if d.shape[0] < 1:
         raise ValueError("depth holds no frame")
     K = np.asarray(intrinsics.cpu() if isinstance(intrinsics, torch.Tensor) else intrinsics, dtype=np.float32)
@@ -4193,14 +4498,19 @@ def _odo_frames(depth, intrinsics):
 
 
 def _depth_pyramid(host, device, depth, intrinsics, levels, depth_scale, depth_max, depth_diff):
-    d, K = _odo_frames(depth, intrinsics)
-    F, H, W = d.shape
+    d, K = _odo_frames(depth, intrinsics, device_ok=not host)
+    F, H, W = (int(k) for k in d.shape)
     levels = _odo_check_levels(H, W, levels)
-    td, tK = _on(device, d, K)
+    if isinstance(d, torch.Tensor):                   # f32 metres already on the device: no round trip
+        td, is_f32 = d, 1
+        tK, = _on(device, K)
+    else:
+        td, tK = _on(device, d, K)
+        is_f32 = int(d.dtype != np.uint16)
     data = torch.empty((F, depth_pyramid_pixels(H, W, levels)), dtype=torch.float32, device=device)
     KL = torch.empty((F, levels, 4), dtype=torch.float32, device=device)
     L = _native.lib()
-    args = (_p(td), int(d.dtype != np.uint16), F, H, W, _p(tK), levels, float(depth_scale), float(depth_max),
+    args = (_p(td), is_f32, F, H, W, _p(tK), levels, float(depth_scale), float(depth_max),
             float(depth_diff), _p(data), _p(KL))
     if host:
         _native.check(L.d3f_depth_pyramid_host(*args), "d3f_depth_pyramid_host")
@@ -4212,7 +4522,8 @@ def _depth_pyramid(host, device, depth, intrinsics, levels, depth_scale, depth_m
 def depth_pyramid(depth, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, depth_diff=ODO_DEPTH_DIFF):
     """The depth pyramid of F frames on the device (d3f_depth_pyramid; the rule is csrc/odometry.hpp): a
     ``DepthPyramid`` -- the packed pyramid ``.data`` f32 [F, pixels], the level table ``.table`` and the intrinsics of
-    every level ``.K``.  ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres;
+    every level ``.K``.  ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres (a device
+    f32 tensor, such as ``tsdf_raycast``'s, is taken where it is);
     ``intrinsics`` [4] or [F,4] = fx, fy, cx, cy.  Level 0 is the depth in metres, 0 where invalid (not ``d > 0``, or
     ``d > depth_max``: a NaN and an infinity too); level l+1 halves level l (an odd last row or column is dropped),
     a pixel being the mean of the valid pixels of its 2x2 block and 0 when there is none or when they span more than

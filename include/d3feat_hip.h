@@ -1078,6 +1078,20 @@ int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, i
                             const float* intrinsics, const float* volume_to_camera, const float* origin,
                             const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
                             float depth_max, float* D, float* w, void* stream);
+/* d3f_tsdf_integrate_into: the same kernel body, but every voxel's thread first reads the (D, w) stored in the volume
+ *   and continues the running mean from it (tsdf.hpp: integrate_voxel_into).  The mean is sequential over frames, so
+ *   integrating the frames [0, k) and then [k, F) into the result gives the volume of one call over [0, F) bit for
+ *   bit.  A volume that owns no frame in the call keeps its values. */
+int d3f_tsdf_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                            const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+                            const float* intrinsics, const float* volume_to_camera, const float* origin,
+                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
+                            float depth_max, float* D, float* w, void* stream);
+int d3f_tsdf_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                                 const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+                                 const float* intrinsics, const float* volume_to_camera, const float* origin,
+                                 const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
+                                 float depth_max, float* D, float* w, void* stream);
 size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels);
 int d3f_tsdf_extract_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
                            int64_t total_voxels, float min_weight, int64_t* point_start, void* ws, size_t ws_bytes,
@@ -1194,6 +1208,34 @@ int d3f_tsdf_mesh_host(const float* D, const float* w, const int64_t* vol_start,
                        const int32_t* dims, const float* voxel, int V, int64_t total_voxels, float min_weight,
                        int64_t vertex_capacity, int64_t face_capacity, float* vertices, float* normals, int32_t* faces,
                        int64_t* vertex_start, int64_t* face_start, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ray-casting dense TSDF volumes: a volume plus a camera pose gives a depth image and, when asked, a normal image
+ * (csrc/tsdf_raycast.hpp states the rule in full; the reference has no such step).  The batch of V volumes is that of
+ * d3f_tsdf_integrate (D, w, vol_start, origin, dims, voxel).  View r looks at volume view_volume[r] (int32 [R], any
+ * order, a volume any number of times; a value outside [0, V) gives an image of zeros) through intrinsics[r] = fx, fy,
+ * cx, cy and camera_to_volume[r] [12] row-major 3x4 f32; step is f32 [V], the sample spacing of a volume's views along
+ * the camera z-depth.  Every ray samples the trilinear D at z_k = depth_min + step k <= depth_max, a sample being valid
+ * when all 8 corners of its cell have w >= min_weight; a valid positive sample followed by a valid non-positive one is
+ * a hit at the interpolated zero, a valid negative sample not preceded by a valid positive one ends the ray without
+ * one.  depth f32 [R, H, W] in metres, 0 without a hit; normals (may be null) f32 [R, H, W, 3] in the camera frame,
+ * towards positive D, zeros where there is no hit or a gradient sample is invalid.  clip != 0 cuts every ray's sample
+ * range to the lattice's box (widened: the result is the same bit for bit; clip = 0 is the switch that proves it).
+ * A step that is not > 0 or gives more than D3F_RAYCAST_MAX_SAMPLES samples casts nothing.  0 <= R <= 65535, H W <=
+ * 2^30, 0 <= depth_min <= depth_max.  One thread per ray, a wave per 8 x 8 pixels, all views in one launch; no atomics,
+ * nothing read back, a view's image bit-identical alone, in any batch and from run to run, and to the host twin.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_RAYCAST_MAX_SAMPLES 65536
+int d3f_tsdf_raycast(const float* D, const float* w, const int64_t* vol_start, const float* origin,
+                     const int32_t* dims, const float* voxel, int V, int64_t total_voxels, const int32_t* view_volume,
+                     int R, int H, int W, const float* intrinsics, const float* camera_to_volume, const float* step,
+                     float depth_min, float depth_max, float min_weight, int clip, float* depth, float* normals,
+                     void* stream);
+int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_start, const float* origin,
+                          const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+                          const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                          const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                          float min_weight, int clip, float* depth, float* normals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth odometry: the camera poses of a depth sequence by frame-to-frame projective point-to-plane ICP over a depth
