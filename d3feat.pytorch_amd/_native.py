@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(_PKG_DIR, "libd3feat_hip.so")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
-           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip"]
+           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
+           "tsdf_raycast_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -214,6 +215,10 @@ SIGNATURES = {
                               _vp, _vp, _vp]),
     "d3f_tsdf_raycast_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f,
                                    _i, _vp, _vp, _vp]),
+    "d3f_tsdf_raycast_sparse": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _i, _i, _i,
+                                     _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
+    "d3f_tsdf_raycast_sparse_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _i, _i,
+                                          _i, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
     "d3f_tsdf_extract_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_extract_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
@@ -230,6 +235,10 @@ SIGNATURES = {
                                        _f, _vp, _vp, _vp]),
     "d3f_tsdf_sparse_integrate_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
                                             _f, _f, _vp, _vp]),
+    "d3f_tsdf_sparse_integrate_into": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
+                                            _f, _f, _vp, _vp, _vp]),
+    "d3f_tsdf_sparse_integrate_into_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 C.c_int64, _f, _f, _vp, _vp]),
     "d3f_tsdf_sparse_extract_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_sparse_extract_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _sz,
                                            _vp]),

@@ -38,6 +38,12 @@
 // box is widened by a voxel and the k range by a sample on either side, and the inside test above still decides: the
 // clip changes no bit (samples left out are invalid ones before the first or after the last valid one, which neither
 // start, end nor hit anything).
+//
+// The sampler.  clip_range and cast_ray are templates over the type that stands for the volume: they read its members
+// ox, oy, oz, voxel, nx, ny, nz and call two overloaded functions on it, sample() (the trilinear D at a point) and
+// march() (the same for sample k of the marching loop, which may also name the last of the samples after k that are
+// certainly invalid too: the loop goes on behind it).  Here the sampler is the dense Lattice, whose march() is its
+// sample() and names nothing; tsdf_raycast_sparse.hpp adds the sampler of a sparse volume.
 #pragma once
 #include "tsdf.hpp"
 
@@ -81,6 +87,14 @@ D3F_HD inline bool sample(const Lattice& L, float qx, float qy, float qz, float 
   return weighted;
 }
 
+// sample k of the marching loop at q = the ray's point of z_k; `last` comes in as k.  A dense lattice knows nothing
+// about the samples after an invalid one.
+D3F_HD inline bool march(const Lattice& L, const float* C, float x, float y, float step, float depth_min, int k,
+                         const float q[3], float min_weight, float& value, int& last) {
+  (void)C, (void)x, (void)y, (void)step, (void)depth_min, (void)k, (void)last;
+  return sample(L, q[0], q[1], q[2], min_weight, value);
+}
+
 // the point of camera z-depth z on the ray (x, y), in the volume's frame
 D3F_HD inline void ray_point(const float* C, float x, float y, float z, float q[3]) {
   const float X = x * z, Y = y * z;
@@ -103,7 +117,8 @@ D3F_HD inline void clip_axis(float dir, float o, float origin, float voxel, int 
 }
 
 // the k range [k0, k1] of the ray (x, y) that can be inside the lattice (empty: k1 < k0); conservative, see above
-D3F_HD inline void clip_range(const Lattice& L, const float* C, float x, float y, float step, float depth_min,
+template <typename Sampler>
+D3F_HD inline void clip_range(const Sampler& L, const float* C, float x, float y, float step, float depth_min,
                               float depth_max, int& k0, int& k1) {
   float zin = depth_min, zout = depth_max;
   bool empty = false;
@@ -118,7 +133,8 @@ D3F_HD inline void clip_range(const Lattice& L, const float* C, float x, float y
 }
 
 // the depth of pixel (u, v), 0 without a hit; normal[3] receives the camera-frame normal when `want_normal`, else zeros
-D3F_HD inline float cast_ray(const Lattice& L, const float* K, const float* C, int u, int v, float step,
+template <typename Sampler>
+D3F_HD inline float cast_ray(const Sampler& L, const float* K, const float* C, int u, int v, float step,
                              float depth_min, float depth_max, float min_weight, bool clip, bool want_normal,
                              float normal[3]) {
   normal[0] = normal[1] = normal[2] = 0.0f;
@@ -133,8 +149,10 @@ D3F_HD inline float cast_ray(const Lattice& L, const float* K, const float* C, i
     if (!(z <= depth_max)) break;
     float q[3], t1;
     ray_point(C, x, y, z, q);
-    if (!sample(L, q[0], q[1], q[2], min_weight, t1)) {
+    int last = k;              // the last sample known to be invalid when this one is
+    if (!march(L, C, x, y, step, depth_min, k, q, min_weight, t1, last)) {
       positive = false;
+      k = last;
       continue;
     }
     if (positive && !(t1 > 0.0f)) {

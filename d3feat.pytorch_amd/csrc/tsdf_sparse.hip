@@ -10,6 +10,8 @@
 //   integrate  one workgroup per allocated brick, so the volume, its frame range and the frame matrices are uniform as
 //              in tsdf.hip's integrate_kernel; lanes along ix (a wave is one z plane of the brick), each thread owns
 //              slots t and t + 256 for ALL frames: the pool is read never and written once, contiguously, no atomics.
+//              d3f_tsdf_sparse_integrate_into is the same kernel with one difference: the thread first reads the (D, w)
+//              its slots hold and continues the running mean from them; a volume without a frame is left alone.
 //   extract    tsdf.hip's count -> scan -> emit over blocks of 256 pool slots (two per brick); the +1 neighbour across
 //              a brick face is found through brick_index.  No atomic decides a position.
 // The host twins run the same tsdf_sparse.hpp text on the CPU and make no GPU call.
@@ -99,35 +101,49 @@ __global__ void __launch_bounds__(kThreads) sparse_index_kernel(const int32_t* _
 }
 
 // ------------------------------------------------------------------------------------------------------- integrate
-// D and w of slot s of pool row b
-template <typename DepthT>
+// D and w of slot s of pool row b.  kInto: D and w come in holding the slot's stored values and the frames continue
+// from them (d3f_tsdf_sparse_integrate_into); a slot beyond dims is left as it is
+template <typename DepthT, bool kInto = false>
 __host__ __device__ inline void fuse_slot(const Bricks& k, const Frames& fr, int v, int64_t b, int s, float& D,
                                           float& w) {
   int i[3];
-  D = 0.0f;
-  w = 0.0f;
+  if (!kInto) {
+    D = 0.0f;
+    w = 0.0f;
+  }
   if (!slot_voxel(k.dims + 3 * (size_t)v, k.brick_coord + 3 * (size_t)b, s, i)) return;
   int f0 = fr.frame_start[v], f1 = fr.frame_start[v + 1];
   if (f0 < 0) f0 = 0;
   if (f1 > fr.F) f1 = fr.F;
   const float voxel = k.voxel[v];
-  integrate_voxel(lattice(k.origin[3 * v], voxel, i[0]), lattice(k.origin[3 * v + 1], voxel, i[1]),
-                  lattice(k.origin[3 * v + 2], voxel, i[2]), f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W,
-                  fr.depth_scale, fr.depth_max, fr.trunc[v], D, w);
+  const float x = lattice(k.origin[3 * v], voxel, i[0]), y = lattice(k.origin[3 * v + 1], voxel, i[1]);
+  const float z = lattice(k.origin[3 * v + 2], voxel, i[2]);
+  if (kInto)
+    integrate_voxel_into(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale,
+                         fr.depth_max, fr.trunc[v], D, w);
+  else
+    integrate_voxel(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale, fr.depth_max,
+                    fr.trunc[v], D, w);
 }
 
-// grid (B): the brick is blockIdx.x, so its volume and everything indexed by it are uniform
-template <typename DepthT>
+// grid (B): the brick is blockIdx.x, so its volume and everything indexed by it are uniform.  kInto: the slot's thread
+// reads its stored (D, w) first and continues from it; the rows of a volume that owns no frame in the call are left alone
+template <typename DepthT, bool kInto = false>
 __global__ void __launch_bounds__(kThreads) sparse_integrate_kernel(Bricks k, Frames fr, float* __restrict__ D_out,
                                                                     float* __restrict__ w_out) {
   const int64_t b = (int64_t)blockIdx.x;
   if (b >= k.B) return;
   const int v = owner(k.brick_start, k.V, b);
+  if (kInto && fr.frame_start[v + 1] <= fr.frame_start[v]) return;
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     const int s = half * kThreads + (int)threadIdx.x;
     float D, w;
-    fuse_slot<DepthT>(k, fr, v, b, s, D, w);
+    if (kInto) {
+      D = D_out[b * kBrickVoxels + s];
+      w = w_out[b * kBrickVoxels + s];
+    }
+    fuse_slot<DepthT, kInto>(k, fr, v, b, s, D, w);
     D_out[b * kBrickVoxels + s] = D;
     w_out[b * kBrickVoxels + s] = w;
   }
@@ -273,6 +289,55 @@ void mark_host(const Frames& fr, const Bricks& k, int32_t* flags) {
   }
 }
 
+template <bool kInto>
+int run_sparse_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
+                         const float* intrinsics, const float* volume_to_camera, const float* origin,
+                         const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+                         const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
+                         float* w, void* stream) {
+  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
+      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
+    return D3F_EINVAL;
+  if (bricks == 0) return D3F_OK;
+  if (!D || !w || !brick_coord) return D3F_EINVAL;
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
+  if (depth_is_f32)
+    sparse_integrate_kernel<float, kInto><<<(unsigned)bricks, kThreads, 0, (hipStream_t)stream>>>(k, fr, D, w);
+  else
+    sparse_integrate_kernel<uint16_t, kInto><<<(unsigned)bricks, kThreads, 0, (hipStream_t)stream>>>(k, fr, D, w);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+template <bool kInto>
+int run_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
+                              int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
+                              const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
+                              float* w) {
+  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
+      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
+    return D3F_EINVAL;
+  if (bricks == 0) return D3F_OK;
+  if (!D || !w || !brick_coord || brick_start[0] != 0 || brick_start[V] != bricks) return D3F_EINVAL;
+  for (int v = 0; v < V; ++v)
+    if (brick_start[v + 1] < brick_start[v]) return D3F_EINVAL;
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
+  for (int v = 0; v < V; ++v) {
+    if (kInto && frame_start[v + 1] <= frame_start[v]) continue;      // a volume without a frame keeps its rows
+    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
+      for (int s = 0; s < kBrickVoxels; ++s) {
+        if (depth_is_f32)
+          fuse_slot<float, kInto>(k, fr, v, b, s, D[b * kBrickVoxels + s], w[b * kBrickVoxels + s]);
+        else
+          fuse_slot<uint16_t, kInto>(k, fr, v, b, s, D[b * kBrickVoxels + s], w[b * kBrickVoxels + s]);
+      }
+  }
+  return D3F_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,19 +434,9 @@ int d3f_tsdf_sparse_integrate(const void* depth, int depth_is_f32, int F, int H,
                               const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
                               const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
                               float* w, void* stream) {
-  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (bricks == 0) return D3F_OK;
-  if (!D || !w || !brick_coord) return D3F_EINVAL;
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
-  if (depth_is_f32)
-    sparse_integrate_kernel<float><<<(unsigned)bricks, kThreads, 0, (hipStream_t)stream>>>(k, fr, D, w);
-  else
-    sparse_integrate_kernel<uint16_t><<<(unsigned)bricks, kThreads, 0, (hipStream_t)stream>>>(k, fr, D, w);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
+  return run_sparse_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
+                                     dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
+                                     stream);
 }
 
 int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W,
@@ -390,24 +445,31 @@ int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, i
                                    const float* voxel, const float* trunc, const int64_t* brick_start,
                                    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
                                    float* D, float* w) {
-  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (bricks == 0) return D3F_OK;
-  if (!D || !w || !brick_coord || brick_start[0] != 0 || brick_start[V] != bricks) return D3F_EINVAL;
-  for (int v = 0; v < V; ++v)
-    if (brick_start[v + 1] < brick_start[v]) return D3F_EINVAL;
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
-  for (int v = 0; v < V; ++v)
-    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
-      for (int s = 0; s < kBrickVoxels; ++s) {
-        if (depth_is_f32)
-          fuse_slot<float>(k, fr, v, b, s, D[b * kBrickVoxels + s], w[b * kBrickVoxels + s]);
-        else
-          fuse_slot<uint16_t>(k, fr, v, b, s, D[b * kBrickVoxels + s], w[b * kBrickVoxels + s]);
-      }
-  return D3F_OK;
+  return run_sparse_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
+                                          origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
+                                          depth_max, D, w);
+}
+
+int d3f_tsdf_sparse_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W,
+                                   const int32_t* frame_start, int V, const float* intrinsics,
+                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                   const float* voxel, const float* trunc, const int64_t* brick_start,
+                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                   float* D, float* w, void* stream) {
+  return run_sparse_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
+                                    dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
+                                    stream);
+}
+
+int d3f_tsdf_sparse_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W,
+                                        const int32_t* frame_start, int V, const float* intrinsics,
+                                        const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                        const float* voxel, const float* trunc, const int64_t* brick_start,
+                                        const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                        float* D, float* w) {
+  return run_sparse_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
+                                         origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
+                                         depth_max, D, w);
 }
 
 size_t d3f_tsdf_sparse_extract_ws_bytes(int64_t bricks) {

@@ -16,7 +16,8 @@ the memory.  Colour is not part of this.
 ``track_sequence`` gives the camera poses of a sequence that comes without them: frame-to-frame depth odometry
 (``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence; with
 ``model=`` every frame is tracked against a ray-cast of its fragment's TSDF volume as well (``ops.tsdf_raycast``;
-csrc/tsdf_raycast.hpp has the rule).  ``render_views`` ray-casts volumes from 4x4 poses.
+csrc/tsdf_raycast.hpp has the rule), which ``sparse=True`` keeps in bricks (``ops.tsdf_raycast_sparse`` / ``tsdf_extend``;
+csrc/tsdf_raycast_sparse.hpp).  ``render_views`` ray-casts volumes, dense or sparse, from 4x4 poses.
 """
 import os
 import re
@@ -280,18 +281,25 @@ DEFAULT_TRACK_BYTES = 1 << 30    # the depth pyramid of the frames tracked in on
 
 
 DEFAULT_MODEL = dict(frames_per_fragment=50, voxel=0.01, trunc=None, margin=None, step=None,
-                     max_bytes=DEFAULT_MAX_BYTES)
+                     max_bytes=DEFAULT_MAX_BYTES, sparse=False)
 
 
 def render_views(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume=None,
-                 device='cuda', **raycast):
+                 device='cuda', sv=None, **raycast):
     """Depth images f32 [R,H,W] in metres (0: no surface) of dense TSDF volumes seen from the camera-to-volume 4x4
     ``poses`` [R,4,4]: ``ops.tsdf_raycast`` (csrc/tsdf_raycast.hpp has the rule) on the device, where D and w are device
     tensors and so is the result; ``device='cpu'`` runs ``ops.tsdf_raycast_numpy`` on arrays.  ``view_volume`` [R] names
     every view's volume (None: one view per volume).  ``**raycast``: ``step``, ``depth_min``, ``depth_max``,
-    ``min_weight``, ``normals`` (then ``(depth, normals f32 [R,H,W,3])``), ``clip``."""
+    ``min_weight``, ``normals`` (then ``(depth, normals f32 [R,H,W,3])``), ``clip``.
+
+    ``sv=``: the ``ops.SparseVolumes`` of a sparse pool ``D``, ``w`` [B,512] (``ops.tsdf_raycast_sparse``;
+    csrc/tsdf_raycast_sparse.hpp has the rule: the render of the densified pool, bit for bit).  ``vol_start``,
+    ``origin``, ``dims`` and ``voxel`` are then taken from ``sv`` and may be None; ``**raycast`` also takes ``skip``."""
     from .. import ops
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if sv is not None:
+        cast = ops.tsdf_raycast_sparse_numpy if _is_cpu(device) else ops.tsdf_raycast_sparse
+        return cast(D, w, sv, trunc, intrinsics, poses, height, width, view_volume, **raycast)
     cast = ops.tsdf_raycast_numpy if _is_cpu(device) else ops.tsdf_raycast
     return cast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume, **raycast)
 
@@ -359,31 +367,62 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
     bounds[:, :3] -= margin
     bounds[:, 3:] += margin
     origin, dims = place_volumes(bounds, voxel)
-    _check_fits(dims, voxel, max_bytes, "model of fragment")  # before anything is launched
-    sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
-    integrate = ops.tsdf_numpy if cpu else ops.tsdf_integrate
+    sparse = bool(m['sparse'])
     eye = np.eye(4)
+    if sparse:
+        allocate = ops.tsdf_allocate_numpy if cpu else ops.tsdf_allocate
+        extend = ops.tsdf_extend_numpy if cpu else ops.tsdf_extend
+        integrate = ops.tsdf_sparse_numpy if cpu else ops.tsdf_integrate_sparse
+        raycast = ops.tsdf_raycast_sparse_numpy if cpu else ops.tsdf_raycast_sparse
+
+        def check_bytes(sv, v, e):
+            nbytes = ops.tsdf_sparse_bytes(sv)
+            if nbytes > max_bytes:
+                raise ValueError("model of fragments %d..%d: the %d allocated bricks (of %d) take %d bytes, more than "
+                                 "max_bytes = %d: raise max_bytes or the voxel size"
+                                 % (v, e - 1, sv.bricks, int(sv.lattice_start[-1]), nbytes, max_bytes))
+        # the bricks of every fragment's first frame at the identity: the sizes the groups are made from
+        first_all = frame_start[:-1]
+        sizes = np.zeros(G, dtype=np.int64)
+        for v, e in _frame_groups(np.arange(G + 1), frame_bytes, max_bytes):
+            sv = allocate(depth[first_all[v:e]], np.arange(e - v + 1), K[first_all[v:e]],
+                          np.broadcast_to(eye, (e - v, 4, 4)), origin[v:e], dims[v:e], voxel, trunc, depth_scale,
+                          depth_max)
+            for j in range(v, e):
+                sizes[j] = ops.tsdf_sparse_bytes(sv, j - v)
+    else:
+        _check_fits(dims, voxel, max_bytes, "model of fragment")  # before anything is launched
+        sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
+        integrate = ops.tsdf_numpy if cpu else ops.tsdf_integrate
+        raycast = ops.tsdf_raycast_numpy if cpu else ops.tsdf_raycast
     for v, e in _size_batches(sizes, max_bytes):
         n = e - v
         first, count = frame_start[v:e], np.diff(frame_start[v:e + 1])
         vol = (origin[v:e], dims[v:e], voxel, trunc, depth_scale, depth_max)
         # step 0: the first frame of every fragment of the group, at the identity
-        D, w, vs = integrate(depth[first], np.arange(n + 1), K[first], np.broadcast_to(eye, (n, 4, 4)), *vol)[:3]
+        frames0 = (depth[first], np.arange(n + 1), K[first], np.broadcast_to(eye, (n, 4, 4)))
+        if sparse:
+            sv = allocate(*frames0, *vol)
+            check_bytes(sv, v, e)
+            D, w = integrate(*frames0, sv, trunc, depth_scale, depth_max)
+        else:
+            D, w, vs = integrate(*frames0, *vol)[:3]
         for s in range(1, int(count.max())):
             live = np.nonzero(count > s)[0]                # the fragments that have a frame s
             f = first[live] + s
             A = live.size
-            view = (D, w, vs, origin[v:e], dims[v:e], voxel, trunc, K[f - 1], L[f - 1], H, W, live)
+            views = (trunc, K[f - 1], L[f - 1], H, W, live)
+            view = (D, w, sv) + views if sparse else (D, w, vs, origin[v:e], dims[v:e], voxel) + views
             frames = _metres(depth[f], depth_scale)
             pairs = np.stack([np.arange(A), A + np.arange(A)], axis=1)      # (frame s, the render of frame s - 1)
             if cpu:
-                both = np.concatenate([frames, ops.tsdf_raycast_numpy(*view, step=m['step'], depth_max=depth_max)])
+                both = np.concatenate([frames, raycast(*view, step=m['step'], depth_max=depth_max)])
                 pyr = ops.depth_pyramid_numpy(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
                                               depth_diff)
                 res = ops.depth_odometry_numpy(pyr, pairs, T_ff[f - 1], iterations, **odometry)
             else:
                 import torch
-                render = ops.tsdf_raycast(*view, step=m['step'], depth_max=depth_max)
+                render = raycast(*view, step=m['step'], depth_max=depth_max)
                 both = torch.cat([torch.from_numpy(np.ascontiguousarray(frames)).to(render.device), render])
                 pyr = ops.depth_pyramid(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
                                         depth_diff)
@@ -397,7 +436,14 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
             # frame s of every live fragment into its volume under inv(L): the others own no frame and keep theirs
             owns = np.zeros(n + 1, dtype=np.int64)
             owns[live + 1] = 1
-            integrate(depth[f], np.cumsum(owns), K[f], np.stack([rigid_inverse(L[j]) for j in f]), *vol, into=(D, w))
+            M = np.stack([rigid_inverse(L[j]) for j in f])
+            if sparse:
+                # the bricks the frame reaches under its refined pose first, then the frame into the grown pool
+                sv, D, w = extend(sv, D, w, depth[f], np.cumsum(owns), K[f], L[f], trunc, depth_scale, depth_max)
+                check_bytes(sv, v, e)
+                integrate(depth[f], np.cumsum(owns), K[f], M, sv, trunc, depth_scale, depth_max, into=(D, w))
+            else:
+                integrate(depth[f], np.cumsum(owns), K[f], M, *vol, into=(D, w))
         del D, w
     return T, model_status
 
@@ -430,6 +476,14 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     boundary, which chain by their frame-to-frame pose: the model restarts with every fragment.  One read-back of poses
     and statuses per step.  Use it where the depth is noisy (the README has the figures): on clean depth the model's
     voxel quantisation costs more than the drift it removes.
+
+    ``model=dict(sparse=True, ...)`` keeps the model in sparse volumes (csrc/tsdf_raycast_sparse.hpp): every fragment's
+    bricks are allocated from its first frame at the identity; per step the pools are ray-cast directly
+    (``ops.tsdf_raycast_sparse``), and after tracking every live fragment's bricks are grown by its new frame under the
+    refined pose (``ops.tsdf_extend``) before the frame is integrated ``into`` the pool.  ``max_bytes`` then bounds
+    ``ops.tsdf_sparse_bytes`` of a group instead of 8 bytes per voxel; it is checked after every growth and a group that
+    outgrows it raises ``ValueError``.  A brick allocated late misses the free-space votes of the earlier frames, so the
+    sparse model is not the dense one bit for bit; the README has the figures of both.
 
     ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it.  Without
     ``model`` drift accumulates from frame to frame; with it, from fragment to fragment; nothing closes a loop."""

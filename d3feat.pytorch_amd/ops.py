@@ -3656,7 +3656,9 @@ def tsdf_sparse_bytes(sv, volume=None):
 
 
 def _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
-                   depth_scale, depth_max):
+                   depth_scale, depth_max, existing=None):
+    """``existing``: an int32 [L] ``brick_index`` on ``device`` whose bricks (entries >= 0) are flagged too, between the
+    mark and the index launches (``tsdf_extend``)."""
     d, fs, K, C = _tsdf_frames(depth, frame_start, intrinsics, camera_to_volume)
     V = fs.size - 1
     o, n, vx, tr, _ = _tsdf_volumes(origin, dims, voxel, V, trunc)
@@ -3676,12 +3678,16 @@ def _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_
               _p(to), _p(tn), _p(tvx), _p(ttr), _p(tls), lattice, float(depth_scale), float(depth_max), _p(flags))
     if host:
         _native.check(L.d3f_tsdf_sparse_mark_host(*frames), "d3f_tsdf_sparse_mark_host")
+        if existing is not None:
+            flags.copy_(torch.maximum(flags, (existing >= 0).to(torch.int32)))
         _native.check(L.d3f_tsdf_sparse_index_host(_p(flags), _p(tls), _p(tn), V, lattice, _p(brick_index), _p(coord),
                                                    _p(brick_start)), "d3f_tsdf_sparse_index_host")
     else:
         nbytes = L.d3f_tsdf_sparse_index_ws_bytes(lattice)
         ws = _ws(nbytes, device)
         _native.check(L.d3f_tsdf_sparse_mark(*(frames + (stream,))), "d3f_tsdf_sparse_mark")
+        if existing is not None:
+            flags.copy_(torch.maximum(flags, (existing >= 0).to(torch.int32)))      # in place: same stream, no sync
         _native.check(L.d3f_tsdf_sparse_index(_p(flags), _p(tls), _p(tn), V, lattice, _p(brick_index), _p(coord),
                                               _p(brick_start), _p(ws), nbytes, stream), "d3f_tsdf_sparse_index")
     bricks = int(brick_start[V].item())                    # the one read-back: the number of allocated bricks
@@ -3723,8 +3729,23 @@ def _sparse_tables(sv, device):
     return tls, bs, bi, bc, to, tn, tvx
 
 
+def _sparse_into(into, B, device):
+    """The (D, w) of a sparse ``into=``: contiguous f32 tensors of B x 512 slots on ``device``, written in place."""
+    if not isinstance(into, (tuple, list)) or len(into) != 2:
+        raise ValueError("into must be the pair (D, w) of an earlier sparse integration")
+    for name, t in zip("Dw", into):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("into: %s must be a contiguous float32 tensor" % name)
+        if t.device.type != torch.device(device).type:
+            raise ValueError("into: %s is on %s, the call runs on %s" % (name, t.device, device))
+        if int(t.numel()) != B * TSDF_BRICK_VOXELS:
+            raise ValueError("into: %s holds %d slots, the %d allocated bricks give %d"
+                             % (name, t.numel(), B, B * TSDF_BRICK_VOXELS))
+    return into[0], into[1]
+
+
 def _tsdf_integrate_sparse(host, device, stream, depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
-                           depth_scale, depth_max):
+                           depth_scale, depth_max, into=None):
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     if V != sv.volumes:
@@ -3733,36 +3754,47 @@ def _tsdf_integrate_sparse(host, device, stream, depth, frame_start, intrinsics,
     td, tfs, tK, tM, ttr = _on(device, d, fs, K, M, tr)
     tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, device)
     B = sv.bricks
-    D = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
-    w = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+    name = "d3f_tsdf_sparse_integrate"
+    if into is None:
+        D = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+        w = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+    else:
+        D, w = _sparse_into(into, B, device)
+        name += "_into"                                            # d3f_tsdf_sparse_integrate_into[_host]
     args = (_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tM), _p(to),
             _p(tn), _p(tvx), _p(ttr), _p(bs), _p(bc) if B else None, B, float(depth_scale), float(depth_max),
             _p(D) if B else None, _p(w) if B else None)
     L = _native.lib()
     if host:
-        _native.check(L.d3f_tsdf_sparse_integrate_host(*args), "d3f_tsdf_sparse_integrate_host")
+        _native.check(getattr(L, name + "_host")(*args), name + "_host")
     else:
-        _native.check(L.d3f_tsdf_sparse_integrate(*(args + (stream,))), "d3f_tsdf_sparse_integrate")
+        _native.check(getattr(L, name)(*(args + (stream,))), name)
     return D, w
 
 
 def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                          depth_max=TSDF_DEPTH_MAX):
+                          depth_max=TSDF_DEPTH_MAX, into=None):
     """Fuse depth frames into the allocated bricks of ``sv`` in ONE launch (d3f_tsdf_sparse_integrate): device tensors
     ``(D f32 [B,512], w f32 [B,512])``, row b the brick ``sv.brick_coord[b]``, voxel (ix, iy, iz) at slot ``(ix & 7) + 8
     (iy & 7) + 64 (iz & 7)``.  Every slot inside the lattice holds what ``tsdf_integrate`` gives that voxel, bit for
-    bit; a slot beyond ``dims`` holds 0.  The frame arguments and ``trunc`` are those of ``tsdf_integrate``."""
+    bit; a slot beyond ``dims`` holds 0.  The frame arguments and ``trunc`` are those of ``tsdf_integrate``.
+
+    ``into=(D, w)``: the device pool of an earlier call over the same ``sv`` and ``trunc``; the frames are integrated
+    into it IN PLACE (d3f_tsdf_sparse_integrate_into; csrc/tsdf_raycast_sparse.hpp) and the same tensors are returned.
+    The frames [0, k) and then [k, F) ``into`` the result give the pool of one call over [0, F) bit for bit; the rows of
+    a volume that owns no frame in the call keep their values."""
     dev = _tsdf_device()
     with _region("tsdf_integrate_sparse"):
         return _tsdf_integrate_sparse(False, dev, _stream(), depth, frame_start, intrinsics, volume_to_camera, sv,
-                                      trunc, depth_scale, depth_max)
+                                      trunc, depth_scale, depth_max, into)
 
 
 def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                               depth_max=TSDF_DEPTH_MAX):
-    """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host): CPU tensors out, no GPU call."""
+                               depth_max=TSDF_DEPTH_MAX, into=None):
+    """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host / d3f_tsdf_sparse_integrate_into_host):
+    CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
     return _tsdf_integrate_sparse(True, torch.device("cpu"), None, depth, frame_start, intrinsics, volume_to_camera,
-                                  sv, trunc, depth_scale, depth_max)
+                                  sv, trunc, depth_scale, depth_max, into)
 
 
 def _sparse_pool(D, w, sv, device):
@@ -3916,26 +3948,40 @@ def tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, origin
 
 
 def tsdf_sparse_numpy(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                      depth_max=TSDF_DEPTH_MAX, chunk=1 << 12):
+                      depth_max=TSDF_DEPTH_MAX, chunk=1 << 12, into=None):
     """The contract of ``tsdf_integrate_sparse`` in NumPy: ``(D f32 [B,512], w f32 [B,512])``, equal to the kernel's bit
-    for bit: ``tsdf_numpy``'s arithmetic on the slots of the allocated bricks, ``chunk`` bricks at a time."""
+    for bit: ``tsdf_numpy``'s arithmetic on the slots of the allocated bricks, ``chunk`` bricks at a time.
+    ``into=(D, w)``: writeable contiguous f32 arrays [B,512] of an earlier call, continued in place and returned."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     if V != sv.volumes:
         raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
     o, n, vx, tr, _ = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)
     coord, bs = _host_array(sv.brick_coord), _host_array(sv.brick_start)
-    D = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
-    w = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    if into is None:
+        D = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+        w = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    else:
+        if not isinstance(into, (tuple, list)) or len(into) != 2:
+            raise ValueError("into must be the pair (D, w) of an earlier sparse integration")
+        for name, a in zip("Dw", into):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or \
+                    not a.flags.writeable or a.size != sv.bricks * TSDF_BRICK_VOXELS:
+                raise ValueError("into: %s must be a writeable contiguous float32 array of %d x 512 slots"
+                                 % (name, sv.bricks))
+        D, w = (a.reshape(sv.bricks, TSDF_BRICK_VOXELS) for a in into)
     for v in range(V):
+        if into is not None and fs[v + 1] <= fs[v]:
+            continue
         for s in range(int(bs[v]), int(bs[v + 1]), int(chunk)):
             e = min(s + int(chunk), int(bs[v + 1]))
             i = _slot_voxels(coord[s:e])
             exists = (i[0] < n[v, 0]) & (i[1] < n[v, 1]) & (i[2] < n[v, 2])
             xyz = tuple(np.float32(o[v, a]) + np.float32(vx[v]) * i[a][exists].astype(np.float32) for a in range(3))
+            start = None if into is None else (D[s:e][exists], w[s:e][exists])
             D[s:e][exists], w[s:e][exists] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v],
-                                                               depth_scale, depth_max)
-    return D, w
+                                                               depth_scale, depth_max, start)
+    return (D, w) if into is None else (into[0], into[1])
 
 
 def tsdf_extract_sparse_numpy(D, w, sv, min_weight=1.0):
@@ -4434,6 +4480,184 @@ def tsdf_raycast_numpy(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, 
             if normals:
                 nrm[r] = nr
     return (depth, nrm) if normals else depth
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Ray-casting, growing and continuing SPARSE TSDF volumes (csrc/tsdf_raycast_sparse.hpp has the rule;
+# csrc/tsdf_raycast_sparse.hip the kernel)
+# ---------------------------------------------------------------------------------------------------------------
+def _tsdf_raycast_sparse(host, device, D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                         depth_min, depth_max, min_weight, normals, clip, skip):
+    if host:
+        D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (D, w))
+    for name, t in zip("Dw", (D, w)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
+            raise ValueError("%s must be a float32 tensor on %s: the pool stays where it is" % (name, device))
+    D, w = D.contiguous().view(-1), w.contiguous().view(-1)
+    V, B, lattice = sv.volumes, sv.bricks, int(sv.lattice_start[-1])
+    if int(D.numel()) != B * TSDF_BRICK_VOXELS or int(w.numel()) != int(D.numel()):
+        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks, got %d and %d"
+                         % (B, D.numel(), w.numel()))
+    if V > TSDF_MAX_VOLUMES:
+        raise ValueError("at most %d volumes per call" % TSDF_MAX_VOLUMES)
+    vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                                        depth_min, depth_max)
+    R = vv.size
+    depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
+    nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
+    if R:
+        tls, bs, bi, _, to, tn, tvx = _sparse_tables(sv, device)
+        tvv, tK, tC, tst = _on(device, vv, K, C, st)
+        L = _native.lib()
+        fn, name = ((L.d3f_tsdf_raycast_sparse_host, "d3f_tsdf_raycast_sparse_host") if host else
+                    (L.d3f_tsdf_raycast_sparse, "d3f_tsdf_raycast_sparse"))
+        _native.check(fn(_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx),
+                         V, lattice, B, _p(tvv), R, H, W, _p(tK), _p(tC), _p(tst), float(depth_min), float(depth_max),
+                         float(min_weight), int(bool(clip)), int(bool(skip)), _p(depth), _p(nrm),
+                         None if host else _stream()), name)
+    return (depth, nrm) if normals else depth
+
+
+def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
+                        depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
+                        clip=True, skip=True):
+    """Ray-cast R views of V SPARSE TSDF volumes in ONE launch (d3f_tsdf_raycast_sparse; the rule is
+    csrc/tsdf_raycast_sparse.hpp): ``depth`` f32 [R,H,W] on the device, and ``(depth, normals f32 [R,H,W,3])`` with
+    ``normals=True`` -- the outputs, conventions and view arguments of ``tsdf_raycast``.  ``D``, ``w``: the pool [B,512]
+    of ``tsdf_integrate_sparse``, device tensors that stay where they are; ``sv`` their ``SparseVolumes``.
+
+    The rule is ``tsdf_raycast``'s with one thing replaced: a corner voxel's D and w come from its brick's pool row, and
+    a voxel of an absent brick is D = 0, w = 0.  The render is therefore ``tsdf_raycast`` of ``tsdf_densify(D, w, sv)``
+    bit for bit, depth and normals, without the dense volume ever existing.  ``skip=False`` turns off the skipping of the
+    samples that stay inside an absent brick (used only when ``min_weight > 0``), which, like ``clip=False``, changes
+    the time and no bit (at the default step of 2.5 voxels ``skip=False`` was measured the faster of the two:
+    profiles/tsdf_raycast_sparse_bench.txt).  One thread per ray, no atomics, nothing read back: a view's image is
+    bit-identical alone, in any batch, from run to run, and to ``tsdf_raycast_sparse_host`` and
+    ``tsdf_raycast_sparse_numpy``.  R = 0 returns empty tensors without a launch; B = 0 gives images of zeros."""
+    dev = _tsdf_device()
+    with _region("tsdf_raycast_sparse"):
+        return _tsdf_raycast_sparse(False, dev, D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
+                                    view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip)
+
+
+def tsdf_raycast_sparse_host(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
+                             depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
+                             clip=True, skip=True):
+    """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host): CPU tensors (or arrays) in, CPU tensors
+    out, no GPU call."""
+    return _tsdf_raycast_sparse(True, torch.device("cpu"), D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
+                                view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip)
+
+
+def tsdf_raycast_sparse_numpy(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None,
+                              step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0,
+                              normals=False, clip=True, skip=True):
+    """The contract of ``tsdf_raycast_sparse`` in NumPy, and the statement of its rule: ``tsdf_raycast_numpy`` of the
+    densified pool.  ``skip`` changes no bit and is not restated."""
+    Dd, wd, vs = tsdf_densify(np.ascontiguousarray(_host_array(D), dtype=np.float32),
+                              np.ascontiguousarray(_host_array(w), dtype=np.float32), sv)
+    return tsdf_raycast_numpy(Dd, wd, vs, sv.origin, sv.dims, sv.voxel, trunc, intrinsics, camera_to_volume, height,
+                              width, view_volume, step, depth_min, depth_max, min_weight, normals, clip)
+
+
+def _extend_rows(sv, sv2, D, w, device):
+    """The pool of ``sv2`` (a superset of ``sv``'s bricks over the same lattices) holding the rows of (D, w): every old
+    row at its new place, zeros elsewhere.  Plain tensor indexing on ``device``; nothing is read back."""
+    B, B2 = sv.bricks, sv2.bricks
+    D, w = _sparse_pool(D, w, sv, device)
+    out = [torch.zeros((B2, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device) for _ in range(2)]
+    if B:
+        def tensor(a, dtype):
+            a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+            return a.to(device=device, dtype=dtype)
+        nb = (np.asarray(sv.dims, dtype=np.int64) + (TSDF_BRICK - 1)) // TSDF_BRICK
+        tls, tnb = _on(device, sv.lattice_start, nb)
+        bs, bs2 = tensor(sv.brick_start, torch.int64), tensor(sv2.brick_start, torch.int64)
+        bc, bi2 = tensor(sv.brick_coord, torch.int64), tensor(sv2.brick_index, torch.int64)
+        rows = torch.arange(B, dtype=torch.int64, device=device)
+        vol = torch.searchsorted(bs[1:].contiguous(), rows, right=True).clamp_(max=sv.volumes - 1)   # the row's volume
+        l = tls[vol] + (bc[:, 2] * tnb[vol, 1] + bc[:, 1]) * tnb[vol, 0] + bc[:, 0]
+        dst = bs2[vol] + bi2[l]
+        out[0][dst] = D.view(B, TSDF_BRICK_VOXELS)
+        out[1][dst] = w.view(B, TSDF_BRICK_VOXELS)
+    return out[0], out[1]
+
+
+def _tsdf_extend(host, device, stream, sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale,
+                 depth_max):
+    fs = np.asarray(frame_start).reshape(-1)
+    if fs.size - 1 != sv.volumes:
+        raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (fs.size - 1, sv.volumes))
+    bi = sv.brick_index if isinstance(sv.brick_index, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(sv.brick_index))
+    bi = bi.to(device=device, dtype=torch.int32)
+    if int(bi.numel()) != int(sv.lattice_start[-1]):
+        raise ValueError("the tables of the sparse volumes do not fit their dims")
+    sv2 = _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_to_volume, sv.origin, sv.dims,
+                         sv.voxel, trunc, depth_scale, depth_max, existing=bi)
+    D2, w2 = _extend_rows(sv, sv2, D, w, device)
+    return sv2, D2, w2
+
+
+def tsdf_extend(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
+                depth_max=TSDF_DEPTH_MAX):
+    """Grow the sparse volumes ``sv`` with pool ``(D, w)`` by the bricks that further frames flag: ``(sv2, D2, w2)`` on
+    the device (csrc/tsdf_raycast_sparse.hpp).  ``sv2`` holds the bricks of ``sv`` united with those the frames flag
+    under ``tsdf_allocate``'s rule -- origin, dims and voxel unchanged, tables in lattice order, so ``sv2`` equals
+    ``tsdf_allocate`` over all the frames seen so far, table for table.  Rows that existed are copied to their new place
+    bit for bit; new rows hold D = 0, w = 0.  The frame arguments are those of ``tsdf_allocate``; a volume may own no
+    frame.  The mark and index launches of ``tsdf_allocate`` do the work, with the flags OR-ed with ``brick_index >= 0``
+    between them; the rows move by plain tensor indexing.  ONE read-back: the number of bricks.
+
+    A brick allocated late holds only the frames integrated after it appeared: where earlier frames saw that space as
+    free, it is not what the dense volume holds."""
+    dev = _tsdf_device()
+    with _region("tsdf_extend"):
+        return _tsdf_extend(False, dev, _stream(), sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc,
+                            depth_scale, depth_max)
+
+
+def tsdf_extend_host(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
+                     depth_max=TSDF_DEPTH_MAX):
+    """The host twin of ``tsdf_extend`` (d3f_tsdf_sparse_mark_host, d3f_tsdf_sparse_index_host): CPU tensors, no GPU
+    call."""
+    return _tsdf_extend(True, torch.device("cpu"), None, sv, D, w, depth, frame_start, intrinsics, camera_to_volume,
+                        trunc, depth_scale, depth_max)
+
+
+def tsdf_extend_numpy(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
+                      depth_max=TSDF_DEPTH_MAX):
+    """The contract of ``tsdf_extend`` in NumPy: ``(sv2, D2, w2)`` of arrays, equal to the device's tables and pool."""
+    new = tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, sv.origin, sv.dims, sv.voxel, trunc,
+                              depth_scale, depth_max)
+    old_index, old_start = _host_array(sv.brick_index), _host_array(sv.brick_start).astype(np.int64)
+    ls = sv.lattice_start
+    n = np.asarray(sv.dims, dtype=np.int64)
+    index, coords, brick_start = [], [], np.zeros(sv.volumes + 1, dtype=np.int64)
+    for v in range(sv.volumes):
+        flat = (old_index[ls[v]:ls[v + 1]] >= 0) | (new.brick_index[ls[v]:ls[v + 1]] >= 0)
+        nb = (n[v] + (TSDF_BRICK - 1)) // TSDF_BRICK
+        index.append(np.where(flat, np.cumsum(flat) - 1, -1).astype(np.int32))
+        local = np.flatnonzero(flat)                                # lattice order
+        coords.append(np.stack([local % nb[0], (local // nb[0]) % nb[1], local // (nb[0] * nb[1])],
+                               axis=1).astype(np.int32))
+        brick_start[v + 1] = brick_start[v] + local.size
+    sv2 = SparseVolumes(np.concatenate(index), np.concatenate(coords, 0).reshape(-1, 3), brick_start, sv.origin,
+                        sv.dims, sv.voxel)
+    B = sv.bricks
+    D = np.ascontiguousarray(_host_array(D), dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(_host_array(w), dtype=np.float32).reshape(-1)
+    if D.size != B * TSDF_BRICK_VOXELS or w.size != D.size:
+        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks" % B)
+    D2 = np.zeros((sv2.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    w2 = np.zeros((sv2.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    for v in range(sv.volumes):
+        kept = np.flatnonzero(old_index[ls[v]:ls[v + 1]] >= 0)
+        src = old_start[v] + old_index[ls[v]:ls[v + 1]][kept]
+        dst = brick_start[v] + sv2.brick_index[ls[v]:ls[v + 1]][kept]
+        D2[dst] = D.reshape(B, TSDF_BRICK_VOXELS)[src]
+        w2[dst] = w.reshape(B, TSDF_BRICK_VOXELS)[src]
+    return sv2, D2, w2
 
 
 # ---------------------------------------------------------------------------------------------------------------

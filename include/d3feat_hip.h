@@ -1157,6 +1157,22 @@ int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, i
                                    const float* voxel, const float* trunc, const int64_t* brick_start,
                                    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
                                    float* D, float* w);
+/* d3f_tsdf_sparse_integrate_into: the same kernel body, but every slot's thread first reads the (D, w) stored in the
+ *   pool and continues the running mean from it (csrc/tsdf_raycast_sparse.hpp).  For fixed tables the frames [0, k) and
+ *   then [k, F) into the result give the pool of one call over [0, F) bit for bit.  The rows of a volume that owns no
+ *   frame in the call, and the slots beyond dims, keep their values. */
+int d3f_tsdf_sparse_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W,
+                                   const int32_t* frame_start, int V, const float* intrinsics,
+                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                   const float* voxel, const float* trunc, const int64_t* brick_start,
+                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                   float* D, float* w, void* stream);
+int d3f_tsdf_sparse_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W,
+                                        const int32_t* frame_start, int V, const float* intrinsics,
+                                        const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                        const float* voxel, const float* trunc, const int64_t* brick_start,
+                                        const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                        float* D, float* w);
 size_t d3f_tsdf_sparse_extract_ws_bytes(int64_t bricks);
 int d3f_tsdf_sparse_extract_count(const float* D, const float* w, const int64_t* lattice_start,
                                   const int64_t* brick_start, const int32_t* brick_index, const int32_t* brick_coord,
@@ -1236,6 +1252,26 @@ int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_sta
                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
                           float min_weight, int clip, float* depth, float* normals, void* stream);
+/* d3f_tsdf_raycast_sparse: the same render of V SPARSE volumes (the tables and the pool of the sparse section above;
+ *   csrc/tsdf_raycast_sparse.hpp states the rule): cast_ray unchanged, a corner voxel's D and w read from its brick's
+ *   pool row, D = 0, w = 0 where the brick is absent -- by definition d3f_tsdf_raycast of the densified pool, bit for
+ *   bit, depth and normals.  D, w f32 [bricks, 512] (may be null when bricks == 0: every image is then 0 unless
+ *   min_weight <= 0).  skip != 0 steps over the samples that stay inside an absent brick (only when min_weight > 0; the
+ *   result is the same bit for bit, skip = 0 is the switch that proves it).  Every index read from the tables is
+ *   bounded before use: tables that do not fit give an unspecified image, and nothing outside brick_index
+ *   [lattice_bricks] and the pool is read.  The other arguments, limits and guarantees are d3f_tsdf_raycast's. */
+int d3f_tsdf_raycast_sparse(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
+                            const int32_t* brick_index, const float* origin, const int32_t* dims, const float* voxel,
+                            int V, int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H,
+                            int W, const float* intrinsics, const float* camera_to_volume, const float* step,
+                            float depth_min, float depth_max, float min_weight, int clip, int skip, float* depth,
+                            float* normals, void* stream);
+int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* lattice_start,
+                                 const int64_t* brick_start, const int32_t* brick_index, const float* origin,
+                                 const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                                 const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                                 const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                                 float min_weight, int clip, int skip, float* depth, float* normals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth odometry: the camera poses of a depth sequence by frame-to-frame projective point-to-plane ICP over a depth
