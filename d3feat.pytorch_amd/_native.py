@@ -14,7 +14,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_raycast_sparse.hip"]
+           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -252,6 +252,13 @@ SIGNATURES = {
                            _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
                                 _vp, _vp]),
+    "d3f_tsdf_sparse_mesh_ws_bytes": (_sz, [C.c_int64]),
+    "d3f_tsdf_sparse_mesh_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _vp,
+                                        _sz, _vp]),
+    "d3f_tsdf_sparse_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
+                                  C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
+                                       C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
     "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),

@@ -62,6 +62,24 @@ D3F_HD inline Hood hood(const float* Dv, const float* wv, int64_t local, int64_t
   return h;
 }
 
+// the same neighbourhood from a sampler instead of a dense pointer (tsdf_mesh_sparse.hpp): sample(dx, dy, dz) gives
+// bit 0 = the voxel e + (dx, dy, dz) is VALID, bit 1 = it is VALID and its D < 0
+template <typename Sample>
+D3F_HD inline Hood hood_from(Sample sample) {
+  Hood h = {0u, 0u};
+  if (!(sample(0, 0, 0) & 1)) return h;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int f = sample(dx, dy, dz);
+        if (!(f & 1)) continue;
+        const uint32_t bit = 1u << hood_bit(dx, dy, dz);
+        h.ok |= bit;
+        if (f & 2) h.neg |= bit;
+      }
+  return h;
+}
+
 // the cell whose lowest voxel is bit `lowest` of the neighbourhood (an offset in {-1, 0}^3): exists and is COMPLETE
 D3F_HD inline bool cell_complete(const Hood& h, int lowest) {
   const uint32_t m = kCellCorners << lowest;
@@ -121,13 +139,11 @@ D3F_HD inline void quad_triangles(const int32_t q[4], bool inside, int32_t* out)
   }
 }
 
-// vertex[3] and normal[3] of the ACTIVE cell at `local` = (ix, iy, iz), whose crossing edges are `edges`
-// (cell_crossings(): every corner is then inside the volume's voxel range)
-D3F_HD inline void cell_vertex(const float* Dv, int64_t local, int ix, int iy, int iz, int nx, int ny, int edges,
-                               const float* origin, float voxel, float* vertex, float* normal) {
-  const int64_t step[3] = {1, (int64_t)nx, (int64_t)nx * (int64_t)ny};
-  float d[8];
-  for (int c = 0; c < 8; ++c) d[c] = Dv[local + (c & 1) * step[0] + ((c >> 1) & 1) * step[1] + ((c >> 2) & 1) * step[2]];
+// vertex[3] and normal[3] of the ACTIVE cell of voxel (ix, iy, iz) from the D of its 8 corners (d[c], bits 0..2 of c =
+// the offsets on x, y, z), whose crossing edges are `edges` (cell_crossings()).  The point of an edge is
+// crossing_point()'s, in its arithmetic: the lower corner's lattice point moved by voxel * (|D0| / (|D0| + |D1|)).
+D3F_HD inline void cell_vertex(const float d[8], int ix, int iy, int iz, int edges, const float* origin, float voxel,
+                               float* vertex, float* normal) {
   float s[3] = {0.0f, 0.0f, 0.0f}, g[3];
   int k = 0;
   for (int a = 0; a < 3; ++a) {
@@ -138,10 +154,10 @@ D3F_HD inline void cell_vertex(const float* Dv, int64_t local, int ix, int iy, i
       const float diff = d[c1] - d[c0];
       sum = j == 0 ? diff : sum + diff;
       if (!((edges >> (4 * a + j)) & 1)) continue;
-      const int ox = c0 & 1, oy = (c0 >> 1) & 1, oz = (c0 >> 2) & 1;
-      float p[3];
-      crossing_point(Dv, local + ox * step[0] + oy * step[1] + oz * step[2], ix + ox, iy + oy, iz + oz, nx, ny, a,
-                     origin, voxel, p);
+      const float a0 = fabsf(d[c0]), a1 = fabsf(d[c1]);
+      float p[3] = {lattice(origin[0], voxel, ix + (c0 & 1)), lattice(origin[1], voxel, iy + ((c0 >> 1) & 1)),
+                    lattice(origin[2], voxel, iz + ((c0 >> 2) & 1))};
+      p[a] = p[a] + voxel * (a0 / (a0 + a1));
       for (int r = 0; r < 3; ++r) s[r] = k == 0 ? p[r] : s[r] + p[r];
       ++k;
     }
@@ -153,6 +169,16 @@ D3F_HD inline void cell_vertex(const float* Dv, int64_t local, int ix, int iy, i
     vertex[r] = s[r] / (float)k;
     normal[r] = ok ? g[r] / len : 0.0f;
   }
+}
+
+// the same for the ACTIVE cell at `local` = (ix, iy, iz) of a dense lattice (every corner is then inside the volume's
+// voxel range): the 8 corners are read and the form above does the rest
+D3F_HD inline void cell_vertex(const float* Dv, int64_t local, int ix, int iy, int iz, int nx, int ny, int edges,
+                               const float* origin, float voxel, float* vertex, float* normal) {
+  const int64_t step[3] = {1, (int64_t)nx, (int64_t)nx * (int64_t)ny};
+  float d[8];
+  for (int c = 0; c < 8; ++c) d[c] = Dv[local + (c & 1) * step[0] + ((c >> 1) & 1) * step[1] + ((c >> 2) & 1) * step[2]];
+  cell_vertex(d, ix, iy, iz, edges, origin, voxel, vertex, normal);
 }
 
 }  // namespace tsdf

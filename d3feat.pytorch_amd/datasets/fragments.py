@@ -11,7 +11,8 @@ runs their NumPy restatement, which gives the same clouds bit for bit.  ``mesh=T
 each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has the rule).  ``sparse=True`` keeps D and w
 only for the bricks of 8 x 8 x 8 voxels near a surface (``ops.tsdf_allocate`` / ``tsdf_integrate_sparse`` /
 ``tsdf_extract_sparse``; csrc/tsdf_sparse.hpp has the rule): the same points, in the sparse order, from a fraction of
-the memory.  Colour is not part of this.
+the memory; ``mesh_fragments`` / ``mesh_scene`` give their meshes straight from the pools (``ops.tsdf_mesh_sparse``;
+csrc/tsdf_mesh_sparse.hpp has the rule).  Colour is not part of this.
 
 ``track_sequence`` gives the camera poses of a sequence that comes without them: frame-to-frame depth odometry
 (``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence; with
@@ -75,7 +76,8 @@ def place_volumes(bounds, voxel):
 
 def _check_sparse(sparse, mesh):
     if sparse and mesh:
-        raise ValueError("sparse=True gives no mesh: fuse with sparse=False, or ops.tsdf_densify a volume that fits")
+        raise ValueError("sparse=True gives no mesh here: mesh_fragments / mesh_scene fuse into sparse volumes and mesh "
+                         "them (ops.tsdf_mesh_sparse)")
 
 
 def _check_fits(dims, voxel, max_bytes, what):
@@ -111,11 +113,18 @@ def _size_batches(sizes, max_bytes):
         v = e
 
 
+def _split_meshes(m, count):
+    """The per-volume (vertices, normals, faces) of a stacked mesh ``m`` of ``count`` volumes."""
+    vert, norm, face, vstart, fstart = m
+    return [(np.ascontiguousarray(vert[vstart[k]:vstart[k + 1]]), np.ascontiguousarray(norm[vstart[k]:vstart[k + 1]]),
+             np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])) for k in range(count)]
+
+
 def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight, cpu,
-                 max_bytes, what):
+                 max_bytes, what, mesh=False):
     """``_fuse`` on sparse volumes: the bricks of every volume first (in the frame groups of the bounds), so that a
     volume whose pool and tables exceed ``max_bytes`` raises before any integration; then batches by the sparse
-    sizes."""
+    sizes.  ``mesh``: also the meshes of the same pools (``ops.tsdf_mesh_sparse``), as ``_fuse`` returns them."""
     from .. import ops
     V = frame_start.size - 1
     allocate = ops.tsdf_allocate_numpy if cpu else ops.tsdf_allocate
@@ -136,7 +145,7 @@ def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_
                                  "take %d bytes, more than max_bytes = %d: raise max_bytes or the voxel size"
                                  % (what, k, start[k - v + 1] - start[k - v], np.diff(sv.lattice_start)[k - v], n[0],
                                     n[1], n[2], voxel, sizes[k], max_bytes))
-    clouds = []
+    clouds, meshes = [], []
     for v, e in _size_batches(sizes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
         frames = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi])
@@ -144,13 +153,17 @@ def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_
         if cpu:
             D, w = ops.tsdf_sparse_numpy(*frames, sv, trunc, depth_scale, depth_max)
             pts, ps = ops.tsdf_extract_sparse_numpy(D, w, sv, min_weight)
+            m = ops.tsdf_mesh_sparse_numpy(D, w, sv, min_weight) if mesh else None
         else:
             D, w = ops.tsdf_integrate_sparse(*frames, sv, trunc, depth_scale, depth_max)
             pts, ps = ops.tsdf_extract_sparse(D, w, sv, min_weight)
             pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
+            m = [t.cpu().numpy() for t in ops.tsdf_mesh_sparse(D, w, sv, min_weight)] if mesh else None
             del D, w
         clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
-    return clouds
+        if mesh:
+            meshes.extend(_split_meshes(m, e - v))
+    return (clouds, meshes) if mesh else clouds
 
 
 def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what,
@@ -176,7 +189,7 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
     origin, dims = place_volumes(bounds, voxel)
     if sparse:
         return _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight,
-                            cpu, int(max_bytes), what)
+                            cpu, int(max_bytes), what, mesh)
     _check_fits(dims, voxel, int(max_bytes), what)        # before anything is launched
     sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
     clouds, meshes = [], []
@@ -197,10 +210,7 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
             del D, w
         clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
         if mesh:
-            vert, norm, face, vstart, fstart = m
-            meshes.extend((np.ascontiguousarray(vert[vstart[k]:vstart[k + 1]]),
-                           np.ascontiguousarray(norm[vstart[k]:vstart[k + 1]]),
-                           np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])) for k in range(e - v))
+            meshes.extend(_split_meshes(m, e - v))
     return (clouds, meshes) if mesh else clouds
 
 
@@ -224,8 +234,15 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     those of ``mesh=False``.  ``sparse=True`` fuses into sparse volumes (csrc/tsdf_sparse.hpp): every volume's bricks
     are allocated first, ``max_bytes`` bounds the pools and tables of a batch (``ops.tsdf_sparse_bytes``) instead of the
     dense volumes, and each cloud holds the rows of ``sparse=False`` bit for bit in the sparse order (brick in lattice
-    order, slot, axis).  There is no sparse mesh: ``sparse=True`` with ``mesh=True`` raises ``ValueError``."""
+    order, slot, axis).  ``sparse=True`` with ``mesh=True`` raises ``ValueError``: the mesh of sparse volumes comes
+    from ``mesh_fragments``."""
     _check_sparse(sparse, mesh)
+    return _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight,
+                      device, max_bytes, mesh, sparse)
+
+
+def _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight, device,
+               max_bytes, mesh, sparse):
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -251,8 +268,15 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
     are left out.  The one volume takes all kept frames in one launch, so they are on the device together with it.
     The other arguments are those of ``fuse_fragments``.  ``mesh=True`` returns ``(cloud, (vertices, normals, faces))``,
     the mesh of the same volume (empty arrays when no frame is kept).  ``sparse=True`` as for ``fuse_fragments``: the
-    one volume is sparse, so a scene whose dense volume exceeds ``max_bytes`` fits when its allocated bricks do."""
+    one volume is sparse, so a scene whose dense volume exceeds ``max_bytes`` fits when its allocated bricks do; its
+    mesh comes from ``mesh_scene``."""
     _check_sparse(sparse, mesh)
+    return _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
+                  min_weight, device, max_bytes, mesh, sparse)
+
+
+def _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
+           min_weight, device, max_bytes, mesh, sparse):
     depth, K, poses = _frames(depth, intrinsics, poses)
     k = int(frames_per_fragment)
     if k < 1:
@@ -274,6 +298,27 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
     fused = _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
                   depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh, sparse)
     return (fused[0][0], fused[1][0]) if mesh else fused[0]
+
+
+def mesh_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
+                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+    """``(clouds, fragment_poses, meshes)`` as ``fuse_fragments(mesh=True)`` returns them, fused into SPARSE volumes and
+    meshed straight from their pools (``ops.tsdf_mesh_sparse``; csrc/tsdf_mesh_sparse.hpp has the rule): no dense volume
+    is built, ``max_bytes`` bounds the pools and tables of a batch as for ``fuse_fragments(sparse=True)``, whose clouds
+    these are.  Every mesh holds the vertices, normals and triangles of ``fuse_fragments(mesh=True)`` bit for bit, in
+    the sparse order (pool row, slot, axis) and so with another vertex numbering.  ``device='cpu'`` runs the NumPy
+    restatements, which work on the pools too."""
+    return _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight,
+                      device, max_bytes, True, True)
+
+
+def mesh_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
+               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+    """``(cloud, (vertices, normals, faces))`` as ``fuse_scene(mesh=True)`` returns them, from ONE sparse volume meshed
+    straight from its pool (``ops.tsdf_mesh_sparse``): a scene whose dense volume exceeds ``max_bytes`` has a mesh when
+    its allocated bricks fit.  The cloud is that of ``fuse_scene(sparse=True)``; empty arrays when no frame is kept."""
+    return _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
+                  min_weight, device, max_bytes, True, True)
 
 
 # --------------------------------------------------------------------------------------------------- tracking

@@ -4228,6 +4228,264 @@ def tsdf_mesh_numpy(D, w, vol_start, origin, dims, voxel, min_weight=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# triangle meshes straight from a sparse pool (csrc/tsdf_mesh_sparse.hpp has the rule; csrc/tsdf_mesh_sparse.hip the
+# kernels)
+# ---------------------------------------------------------------------------------------------------------------
+def tsdf_mesh_sparse_bytes(bricks, vertices, faces, lattice_bricks=0):
+    """The bytes ``tsdf_mesh_sparse`` must move: the pool's D and w read by the count pass and again by the emit pass
+    (8 bytes per slot each), ``brick_index`` read once per pass, the 8 ballot words of every row written once, and the
+    rows written (vertices and normals 12 bytes each, a triangle 12).  The halo voxels a row takes from its neighbours
+    (488 of 1000) are taken to come from cache, and the scans are left out."""
+    return (16 * TSDF_BRICK_VOXELS * int(bricks) + 8 * int(lattice_bricks) + 64 * int(bricks) + 24 * int(vertices) +
+            12 * int(faces))
+
+
+def tsdf_mesh_sparse(D, w, sv, min_weight=1.0, vertex_capacity=None, face_capacity=None, return_status=False):
+    """Triangle meshes of sparse volumes straight from the pool (d3f_tsdf_sparse_mesh; the rule is
+    csrc/tsdf_mesh_sparse.hpp): ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3], vertex_start int64
+    [V+1], face_start int64 [V+1])`` on the device, and no dense array on the way.  The rule is ``tsdf_mesh``'s with a
+    voxel's D and w taken from its brick's pool row; a voxel of an absent brick is never valid.  The result is
+    ``tsdf_mesh`` of ``tsdf_densify(D, w, sv)`` -- the same vertices, normals and faces bit for bit -- in another order:
+    vertices by volume, pool row (brick in lattice order) and slot of the cell's lowest voxel; faces by volume, pool row
+    and slot of the edge's lower voxel, then axis; face entries are vertex indices LOCAL to their volume.  For a pool
+    allocated and integrated over the same frames in one go that is the mesh of the densely integrated volume; bricks
+    added late by ``tsdf_extend`` hold only the later frames.  ``D``, ``w`` as ``tsdf_integrate_sparse`` returns them;
+    the capacities, ``return_status`` and the one read-back as for ``tsdf_mesh``."""
+    dev = _tsdf_device()
+    D, w = _sparse_pool(D, w, sv, dev)
+    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, dev)
+    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
+    starts = torch.zeros((2, V + 1), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:                                                 # nothing allocated: no kernel has anything to do
+        nv, nf = int(vertex_capacity or 0), int(face_capacity or 0)
+        out = (torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nv, 3), dtype=torch.float32, device=dev),
+               torch.empty((nf, 3), dtype=torch.int32, device=dev), starts[0], starts[1])
+        return out + (status,) if return_status else out
+    L = _native.lib()
+    nbytes = L.d3f_tsdf_sparse_mesh_ws_bytes(B)
+    ws = _ws(nbytes, dev)
+    counted = 0
+    with _region("tsdf_mesh_sparse"):
+        if vertex_capacity is None or face_capacity is None:
+            _native.check(L.d3f_tsdf_sparse_mesh_count(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(tn), V, lattice,
+                                                       B, float(min_weight), _p(starts[0]), _p(starts[1]), _p(ws),
+                                                       nbytes, _stream()), "d3f_tsdf_sparse_mesh_count")
+            nv, nf = starts[:, V].tolist()                 # the one read-back: the sizes of the result
+            vertex_capacity = nv if vertex_capacity is None else vertex_capacity
+            face_capacity = nf if face_capacity is None else face_capacity
+            counted = 1
+        nv, nf = int(vertex_capacity), int(face_capacity)
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        _native.check(L.d3f_tsdf_sparse_mesh(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(to), _p(tn), _p(tvx), V,
+                                             lattice, B, float(min_weight), counted, nv, nf,
+                                             _p(vertices) if nv else None, _p(normals) if nv else None,
+                                             _p(faces) if nf else None, _p(starts[0]), _p(starts[1]), _p(status),
+                                             _p(ws), nbytes, _stream()), "d3f_tsdf_sparse_mesh")
+    out = (vertices, normals, faces, starts[0], starts[1])
+    return out + (status,) if return_status else out
+
+
+def tsdf_mesh_sparse_host(D, w, sv, min_weight=1.0, vertex_capacity=None, face_capacity=None, return_status=False):
+    """The host twin of ``tsdf_mesh_sparse`` (d3f_tsdf_sparse_mesh_host): CPU tensors out, no GPU call."""
+    cpu = torch.device("cpu")
+    D, w = _sparse_pool(D, w, sv, cpu)
+    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, cpu)
+    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
+    fn = _native.lib().d3f_tsdf_sparse_mesh_host
+    vertex_start = torch.zeros(V + 1, dtype=torch.int64)
+    face_start = torch.zeros(V + 1, dtype=torch.int64)
+    status = torch.zeros(1, dtype=torch.int32)
+
+    def run(nv, nf, vertices, normals, faces, status):
+        _native.check(fn(_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(bc) if B else None,
+                         _p(to), _p(tn), _p(tvx), V, lattice, B, float(min_weight), nv, nf,
+                         _p(vertices) if nv else None, _p(normals) if nv else None, _p(faces) if nf else None,
+                         _p(vertex_start), _p(face_start), _p(status)), "d3f_tsdf_sparse_mesh_host")
+    if vertex_capacity is None or face_capacity is None:
+        run(0, 0, None, None, None, torch.zeros(1, dtype=torch.int32))          # the totals
+        vertex_capacity = int(vertex_start[V]) if vertex_capacity is None else vertex_capacity
+        face_capacity = int(face_start[V]) if face_capacity is None else face_capacity
+    nv, nf = int(vertex_capacity), int(face_capacity)
+    vertices = torch.empty((nv, 3), dtype=torch.float32)
+    normals = torch.empty((nv, 3), dtype=torch.float32)
+    faces = torch.empty((nf, 3), dtype=torch.int32)
+    run(nv, nf, vertices, normals, faces, status)
+    out = (vertices, normals, faces, vertex_start, face_start)
+    return out + (status,) if return_status else out
+
+
+def _brick_rows27(sv, v, index, coord, bs):
+    """int64 [Bv,27]: the pool rows of the 27 bricks around every row of volume v, entry ``(dx + 1) + 3 (dy + 1) + 9
+    (dz + 1)``, -1 where the brick is absent or outside the lattice (brick_neighbour() of csrc/tsdf_mesh_sparse.hpp)."""
+    lo, hi = int(bs[v]), int(bs[v + 1])
+    c = coord[lo:hi].astype(np.int64)
+    nb = (np.asarray(sv.dims[v], dtype=np.int64) + (TSDF_BRICK - 1)) // TSDF_BRICK
+    ls, L, B = sv.lattice_start, int(index.size), int(coord.shape[0])
+    rows = np.full((hi - lo, 27), -1, dtype=np.int64)
+    for j in range(27):
+        off = np.array([j % 3 - 1, (j // 3) % 3 - 1, j // 9 - 1], dtype=np.int64)
+        if j == 13:
+            rows[:, j] = np.arange(lo, hi)
+            continue
+        n = c + off[None, :]
+        inside = ((n >= 0) & (n < nb[None, :])).all(axis=1)
+        at = int(ls[v]) + (n[:, 2] * nb[1] + n[:, 1]) * nb[0] + n[:, 0]
+        inside &= (at >= 0) & (at < L)
+        rank = np.where(inside, index[np.where(inside, at, 0)], -1).astype(np.int64)
+        row = lo + rank
+        rows[:, j] = np.where((rank >= 0) & (row >= 0) & (row < B), row, -1)
+    return rows
+
+
+def _brick_halo(A, rows27, lo, hi, fill):
+    """``A`` [B,8,8,8] (any dtype, [row, z, y, x]) gathered around the n rows of ``rows27`` [n,27] into [n, m, m, m], m = hi - lo
+    + 1: the in-brick coordinates lo..hi (lo in (-1, 0), hi in (7, 8)) per axis, with ``fill`` where a neighbour
+    brick is missing."""
+    n, m = rows27.shape[0], hi - lo + 1
+    out = np.full((n, m, m, m), fill, dtype=A.dtype)
+    parts = [(d, dst, src) for d, dst, src in ((-1, slice(0, 1), slice(7, 8)), (0, slice(-lo, 8 - lo), slice(0, 8)),
+                                               (1, slice(8 - lo, 9 - lo), slice(0, 1)))
+             if (d != -1 or lo < 0) and (d != 1 or hi > 7)]
+    for dz, tz, sz in parts:
+        for dy, ty, sy in parts:
+            for dx, tx, sx in parts:
+                row = rows27[:, (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1)]
+                has = np.flatnonzero(row >= 0)
+                if has.size:
+                    out[has, tz, ty, tx] = A[row[has], sz, sy, sx]
+    return out
+
+
+def tsdf_mesh_sparse_numpy(D, w, sv, min_weight=1.0, chunk=1 << 10):
+    """The contract of ``tsdf_mesh_sparse`` in NumPy: ``(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3],
+    vertex_start int64 [V+1], face_start int64 [V+1])``, equal to the kernel's bit for bit and in order.  It works on
+    the pool, ``chunk`` bricks at a time: every brick gathers its 10 x 10 x 10 halo from the rows around it, and no
+    dense volume is built.  Every sum is spelled out in f32 in the order of csrc/tsdf_mesh.hpp."""
+    f32 = np.float32
+    B, V = sv.bricks, sv.volumes
+    D = np.ascontiguousarray(_host_array(D), dtype=f32).reshape(-1)
+    w = np.ascontiguousarray(_host_array(w), dtype=f32).reshape(-1)
+    if D.size != B * TSDF_BRICK_VOXELS or w.size != D.size:
+        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks" % B)
+    o, n, vx, _, _ = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V)
+    index, coord, bs = (_host_array(a) for a in (sv.brick_index, sv.brick_coord, sv.brick_start))
+    coord = coord.reshape(-1, 3)
+    Dp = D.reshape(B, 8, 8, 8)                                       # [row, iz, iy, ix]
+    vol = np.repeat(np.arange(V), np.diff(bs))
+    i = _slot_voxels(coord)
+    nv_ = n[vol].astype(np.int64)
+    exists = ((i[0] < nv_[:, 0, None]) & (i[1] < nv_[:, 1, None]) & (i[2] < nv_[:, 2, None])).reshape(B, 8, 8, 8)
+    ok = exists & (w.reshape(B, 8, 8, 8) >= f32(min_weight)) & (np.abs(Dp) < f32(1.0))
+    neg = ok & (Dp < 0)
+    rows27 = (np.concatenate([_brick_rows27(sv, v, index, coord, bs) for v in range(V)], 0) if B
+              else np.zeros((0, 27), dtype=np.int64))
+
+    def corner(A, c, lo=0):     # A [n, m, m, m] over the in-brick coordinates lo..: A at corner c of the cells lo..7
+        dx, dy, dz = c & 1, (c >> 1) & 1, (c >> 2) & 1
+        m = 8 - lo
+        return A[:, dz:m + dz, dy:m + dy, dx:m + dx]
+    # pass 1: the ACTIVE cells of every row, hence every cell's vertex index in its volume
+    active = np.zeros((B, 8, 8, 8), dtype=bool)
+    for s in range(0, B, int(chunk)):
+        e = min(s + int(chunk), B)
+        hok = _brick_halo(ok, rows27[s:e], 0, 8, False)
+        hneg = _brick_halo(neg, rows27[s:e], 0, 8, False)
+        complete = np.ones((e - s, 8, 8, 8), dtype=bool)
+        crossing = np.zeros((e - s, 8, 8, 8), dtype=bool)
+        for c in range(8):
+            complete &= corner(hok, c)
+            crossing |= corner(hneg, c) != corner(hneg, 0)
+        active[s:e] = complete & crossing
+    order = np.cumsum(active.reshape(-1)) - 1
+    vertex_start = np.zeros(V + 1, dtype=np.int64)
+    for v in range(V):
+        vertex_start[v + 1] = int(active[:int(bs[v + 1])].sum())
+    vindex = np.where(active, order.reshape(B, 8, 8, 8) - vertex_start[vol][:, None, None, None], -1).astype(np.int64)
+    # pass 2: vertices, normals and faces, in the order row, slot (, axis)
+    verts, norms, faces = [], [], []
+    face_start = np.zeros(V + 1, dtype=np.int64)
+    face_rows = np.zeros(B, dtype=np.int64)
+    with np.errstate(all='ignore'):
+        for s in range(0, B, int(chunk)):
+            e = min(s + int(chunk), B)
+            r27 = rows27[s:e]
+            hD = _brick_halo(Dp, r27, 0, 8, f32(0.0))
+            hneg = _brick_halo(neg, r27, 0, 8, False)
+            vox = f32(vx[vol[s:e]])[:, None, None, None]
+            org = o[vol[s:e]].astype(f32)
+            lat = [(org[:, a, None] + f32(vx[vol[s:e]])[:, None] *
+                    (coord[s:e, a, None].astype(np.int64) * 8 + np.arange(9)[None, :]).astype(f32)).astype(f32)
+                   for a in range(3)]
+            lat3 = [np.broadcast_to(lat[0][:, None, None, :], (e - s, 9, 9, 9)),
+                    np.broadcast_to(lat[1][:, None, :, None], (e - s, 9, 9, 9)),
+                    np.broadcast_to(lat[2][:, :, None, None], (e - s, 9, 9, 9))]
+            cells = (e - s, 8, 8, 8)
+            k = np.zeros(cells, dtype=np.int64)
+            sums = [np.zeros(cells, dtype=f32) for _ in range(3)]
+            g = []
+            for a in range(3):
+                a1, a2 = (1 if a == 0 else 0), (1 if a == 2 else 2)
+                total = None
+                for j in range(4):
+                    c0 = ((j & 1) << a1) | (((j >> 1) & 1) << a2)
+                    c1 = c0 | (1 << a)
+                    d0, d1 = corner(hD, c0), corner(hD, c1)
+                    diff = d1 - d0
+                    total = diff if total is None else total + diff
+                    cross = corner(hneg, c0) != corner(hneg, c1)
+                    b0, b1 = np.abs(d0), np.abs(d1)
+                    p = [corner(lat3[r], c0) for r in range(3)]
+                    p[a] = p[a] + vox * (b0 / (b0 + b1))
+                    for r in range(3):
+                        sums[r] = np.where(cross, np.where(k == 0, p[r], sums[r] + p[r]), sums[r])
+                    k = k + cross
+                g.append(total)
+            length = np.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            good = (length > 0) & np.isfinite(length)
+            sel = np.nonzero(active[s:e])                              # row-major: row, slot
+            kf = k[sel].astype(f32)
+            verts.append(np.stack([sums[r][sel] / kf for r in range(3)], axis=1).astype(f32).reshape(-1, 3))
+            norms.append(np.stack([np.where(good[sel], g[r][sel] / length[sel], f32(0.0)) for r in range(3)],
+                                  axis=1).astype(f32).reshape(-1, 3))
+            # faces: the COMPLETE cells and the vertex indices of the cells -1..7 around every row
+            hok = _brick_halo(ok, r27, -1, 8, False)
+            hneg = _brick_halo(neg, r27, -1, 8, False)
+            hidx = _brick_halo(vindex, r27, -1, 7, -1)
+            C = np.ones((e - s, 9, 9, 9), dtype=bool)                  # the cells of the voxels -1..7
+            for c in range(8):
+                C &= corner(hok, c, -1)
+            quad = np.zeros(cells + (3,), dtype=bool)
+            tri = np.zeros(cells + (3, 6), dtype=np.int64)
+            here = hneg[:, 1:9, 1:9, 1:9]
+            for a in range(3):
+                b, c = (a + 1) % 3, (a + 2) % 3
+
+                def shifted(A, db, dc):                                # A over -1..7 at e + (db, dc) on the axes (b, c)
+                    r = [slice(1, 9)] * 3
+                    r[b], r[c] = slice(1 + db, 9 + db), slice(1 + dc, 9 + dc)
+                    return A[:, r[2], r[1], r[0]]
+                up = [slice(1, 9)] * 3
+                up[a] = slice(2, 10)
+                q = hok[:, 1:9, 1:9, 1:9] & hok[:, up[2], up[1], up[0]] & (here != hneg[:, up[2], up[1], up[0]])
+                for db, dc in _MESH_QUAD:
+                    q = q & shifted(C, db, dc)
+                quad[..., a] = q
+                idx = np.stack([shifted(hidx, db, dc) for db, dc in _MESH_QUAD], axis=-1)      # [.., 4]
+                tri[..., a, :] = np.where(here[..., None], idx[..., [0, 1, 2, 0, 2, 3]], idx[..., [3, 2, 1, 3, 1, 0]])
+            faces.append(tri[quad].reshape(-1, 3).astype(np.int32))    # row-major: row, slot, axis
+            face_rows[s:e] = 2 * quad.reshape(e - s, -1).sum(axis=1)
+    for v in range(V):
+        face_start[v + 1] = int(face_rows[:int(bs[v + 1])].sum())
+    cat = np.concatenate
+    none = np.zeros((0, 3), dtype=f32)
+    return (cat(verts, 0) if verts else none, cat(norms, 0) if norms else none.copy(),
+            cat(faces, 0) if faces else np.zeros((0, 3), dtype=np.int32), vertex_start, face_start)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Ray-casting dense TSDF volumes: a volume plus a camera pose gives a depth image (csrc/tsdf_raycast.hpp has the rule;
 # csrc/tsdf_raycast.hip the kernel)
 # ---------------------------------------------------------------------------------------------------------------

@@ -1226,6 +1226,48 @@ int d3f_tsdf_mesh_host(const float* D, const float* w, const int64_t* vol_start,
                        int64_t* vertex_start, int64_t* face_start, int32_t* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * Triangle meshes with normals straight from a sparse pool (csrc/tsdf_mesh_sparse.hpp states the rule in full, in the
+ * terms of csrc/tsdf_mesh.hpp and csrc/tsdf_sparse.hpp; the reference has no such step).  The rule is d3f_tsdf_mesh's
+ * with one thing replaced: a voxel's D and w come from its brick's pool row, and a voxel of an absent brick, a slot
+ * beyond dims and a voxel outside the lattice are never valid.  The result is d3f_tsdf_mesh of the densified pool
+ * (min_weight > 0): the same vertices, normals and faces bit for bit, in another order.  No dense array is built.
+ * The arguments D, w [bricks, 512], lattice_start, brick_start, brick_index, brick_coord, origin, dims, voxel, V,
+ * lattice_bricks, bricks and min_weight are those of d3f_tsdf_sparse_extract; the outputs, the capacities, status and
+ * counted are those of d3f_tsdf_mesh.
+ * d3f_tsdf_sparse_mesh: one workgroup per pool row, which looks up the up to 27 bricks around its own once and stages
+ *   the 10 x 10 x 10 voxels around the brick in LDS; count per row (keeping one bit per slot), exclusive scans, emit at
+ *   row offset + rank inside the row: vertices and normals f32 [vertex_capacity, 3] in the order volume, pool row
+ *   (brick in lattice order), slot of the cell's lowest voxel; faces int32 [face_capacity, 3] in the order volume, pool
+ *   row and slot of the edge's lower voxel, axis, a quad's two triangles consecutive, their entries vertex indices
+ *   LOCAL to the volume; vertex_start, face_start int64 [V+1], a volume without bricks owning an empty range.  A
+ *   vertex at or beyond vertex_capacity is not written and ORs D3F_TSDF_ST_OVERFLOW into *status (int32, zeroed by the
+ *   caller), a triangle at or beyond face_capacity is not written and ORs D3F_TSDF_ST_FACE_OVERFLOW; both starts are
+ *   complete either way.  A volume with more than 2^31 - 1 vertices sets D3F_TSDF_ST_OVERFLOW instead of writing a
+ *   wrapped index.  d3f_tsdf_sparse_mesh_count runs the count and the scans alone and writes both starts in full; a
+ *   following d3f_tsdf_sparse_mesh on the same pool and workspace with counted = 1 skips them.  bricks >= 1.  Indices
+ *   read from the tables are bounded before use: tables that disagree with each other give an unspecified result,
+ *   but nothing outside brick_index, the tables and the pool is read.
+ * d3f_tsdf_sparse_mesh_host takes host pointers, makes no GPU call and accepts bricks = 0.
+ * ---------------------------------------------------------------------------------------------- */
+size_t d3f_tsdf_sparse_mesh_ws_bytes(int64_t bricks);
+int d3f_tsdf_sparse_mesh_count(const float* D, const float* w, const int64_t* lattice_start,
+                               const int64_t* brick_start, const int32_t* brick_index, const int32_t* brick_coord,
+                               const int32_t* dims, int V, int64_t lattice_bricks, int64_t bricks, float min_weight,
+                               int64_t* vertex_start, int64_t* face_start, void* ws, size_t ws_bytes, void* stream);
+int d3f_tsdf_sparse_mesh(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
+                         const int32_t* brick_index, const int32_t* brick_coord, const float* origin,
+                         const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                         float min_weight, int counted, int64_t vertex_capacity, int64_t face_capacity, float* vertices,
+                         float* normals, int32_t* faces, int64_t* vertex_start, int64_t* face_start, int32_t* status,
+                         void* ws, size_t ws_bytes, void* stream);
+int d3f_tsdf_sparse_mesh_host(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
+                              const int32_t* brick_index, const int32_t* brick_coord, const float* origin,
+                              const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                              float min_weight, int64_t vertex_capacity, int64_t face_capacity, float* vertices,
+                              float* normals, int32_t* faces, int64_t* vertex_start, int64_t* face_start,
+                              int32_t* status);
+
+/* ------------------------------------------------------------------------------------------------
  * Ray-casting dense TSDF volumes: a volume plus a camera pose gives a depth image and, when asked, a normal image
  * (csrc/tsdf_raycast.hpp states the rule in full; the reference has no such step).  The batch of V volumes is that of
  * d3f_tsdf_integrate (D, w, vol_start, origin, dims, voxel).  View r looks at volume view_volume[r] (int32 [R], any
