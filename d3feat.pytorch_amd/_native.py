@@ -14,7 +14,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip"]
+           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip", "rgbd_odometry.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -268,6 +268,16 @@ SIGNATURES = {
     "d3f_depth_odometry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                 _vp]),
     "d3f_depth_odometry_host": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_rgbd_pyramid": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "d3f_rgbd_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
+    "d3f_rgbd_odometry_ws_bytes": (_sz, [_i, _i, _i]),
+    "d3f_rgbd_odometry_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _sz,
+                                    _vp]),
+    "d3f_rgbd_odometry_step_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
+    "d3f_rgbd_odometry": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _sz, _vp]),
+    "d3f_rgbd_odometry_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
     "d3f_sgd_guarded_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "d3f_sgd_guarded_step_lanes": (_i, [_vp, _i, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "d3f_adam_guarded_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),

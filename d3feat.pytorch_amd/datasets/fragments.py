@@ -18,7 +18,9 @@ csrc/tsdf_mesh_sparse.hpp has the rule).  Colour is not part of this.
 (``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence; with
 ``model=`` every frame is tracked against a ray-cast of its fragment's TSDF volume as well (``ops.tsdf_raycast``;
 csrc/tsdf_raycast.hpp has the rule), which ``sparse=True`` keeps in bricks (``ops.tsdf_raycast_sparse`` / ``tsdf_extend``;
-csrc/tsdf_raycast_sparse.hpp).  ``render_views`` ray-casts volumes, dense or sparse, from 4x4 poses.
+csrc/tsdf_raycast_sparse.hpp).  With ``color=`` the frame-to-frame pass is the RGB-D odometry (``ops.rgbd_odometry``;
+csrc/rgbd_odometry.hpp), which also tracks views of a single plane; ``read_sequence(color=True)`` reads the colour
+images.  ``render_views`` ray-casts volumes, dense or sparse, from 4x4 poses.
 """
 import os
 import re
@@ -349,12 +351,14 @@ def render_views(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses,
     return cast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume, **raycast)
 
 
-def _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, odometry):
+def _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, odometry,
+                 color=None):
     """``(T f64 [F-1,4,4], status int32 [F-1])`` of the consecutive pairs (f+1, f), every pair from the identity, in
-    chunks whose pyramid fits ``max_bytes``."""
+    chunks whose pyramid fits ``max_bytes``; with ``color`` by ``ops.rgbd_odometry``, whose intensity pyramid counts
+    too."""
     from .. import ops
     F = depth.shape[0]
-    frame_bytes = 4 * ops.depth_pyramid_pixels(depth.shape[1], depth.shape[2], levels)
+    frame_bytes = (4 if color is None else 8) * ops.depth_pyramid_pixels(depth.shape[1], depth.shape[2], levels)
     per_chunk = max(2, int(max_bytes) // max(frame_bytes, 1))
     T = np.broadcast_to(np.eye(4), (max(F - 1, 0), 4, 4)).copy()
     status = np.zeros(max(F - 1, 0), dtype=np.int32)
@@ -362,7 +366,14 @@ def _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, dept
         hi = min(lo + per_chunk, F)                       # frames [lo, hi): the pairs (lo+1, lo) .. (hi-1, hi-2)
         pairs = np.stack([np.arange(1, hi - lo), np.arange(0, hi - lo - 1)], axis=1)
         args = (depth[lo:hi], K[lo:hi], levels, depth_scale, depth_max, depth_diff)
-        if cpu:
+        if color is not None:
+            args = (args[0], color[lo:hi]) + args[1:]
+            if cpu:
+                res = ops.rgbd_odometry_numpy(ops.rgbd_pyramid_numpy(*args), pairs, None, iterations, **odometry)
+            else:
+                res = [t.cpu().numpy() for t in ops.rgbd_odometry(ops.rgbd_pyramid(*args), pairs, None, iterations,
+                                                                  **odometry)]
+        elif cpu:
             res = ops.depth_odometry_numpy(ops.depth_pyramid_numpy(*args), pairs, None, iterations, **odometry)
         else:
             res = [t.cpu().numpy() for t in ops.depth_odometry(ops.depth_pyramid(*args), pairs, None, iterations,
@@ -494,7 +505,8 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
 
 
 def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT_TRACK_BYTES, depth_scale=1000.0,
-                   depth_max=DEFAULT_DEPTH_MAX, depth_diff=0.05, model=None, **odometry):
+                   depth_max=DEFAULT_DEPTH_MAX, depth_diff=0.05, model=None, color=None, photo_weight=None,
+                   **odometry):
     """``(poses f64 [F,4,4], status int32 [F-1])``: camera poses of a depth sequence by frame-to-frame depth odometry
     (``ops.depth_odometry``: projective point-to-plane ICP over a depth pyramid, every pair from the identity).
 
@@ -530,6 +542,14 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     outgrows it raises ``ValueError``.  A brick allocated late misses the free-space votes of the earlier frames, so the
     sparse model is not the dense one bit for bit; the README has the figures of both.
 
+    ``color=`` uint8 [F,H,W,3] (``read_sequence(..., color=True)``), uint8 [F,H,W] or f32 [F,H,W], registered to the
+    depth pixel by pixel: the frame-to-frame pass runs ``ops.rgbd_odometry`` instead (csrc/rgbd_odometry.hpp: a
+    photometric row beside the point-to-plane row, scaled by ``photo_weight``, default ``ops.ODO_PHOTO_WEIGHT``), which
+    tracks a view of a single plane where the depth-only pass reports ``ODO_ST_SINGULAR``; ``device='cpu'`` runs its
+    NumPy restatement, and ``max_bytes`` counts the intensity pyramid too.  With ``model=`` the model pass stays
+    depth-only, because a render has no colour; it then starts from the better frame-to-frame pose.  The colour is not
+    fused into the volumes.
+
     ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it.  Without
     ``model`` drift accumulates from frame to frame; with it, from fragment to fragment; nothing closes a loop."""
     from .. import ops
@@ -550,7 +570,14 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     iterations = odometry.pop('iterations', ops.ODO_ITERATIONS)
     levels = len(ops._odo_iterations(iterations))
     cpu = _is_cpu(device)
-    T, status = _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, odometry)
+    first = dict(odometry)
+    if color is not None:
+        color = ops._rgbd_color(np.asarray(ops._host_array(color))[::stride], depth.shape)[0]
+        first['photo_weight'] = ops.ODO_PHOTO_WEIGHT if photo_weight is None else ops._rgbd_check_weight(photo_weight)
+    elif photo_weight is not None:
+        raise ValueError("photo_weight needs color")
+    T, status = _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, depth_max, depth_diff, first,
+                             color)
     for f in range(F - 1):
         if status[f] != 0:
             T[f] = np.eye(4)
@@ -620,11 +647,13 @@ def write_fragments(root, scene, clouds, poses, frames_per_fragment, seq='seq-01
     return path
 
 
-def read_sequence(folder, require_poses=True):
+def read_sequence(folder, require_poses=True, color=False):
     """``(depth uint16 [F,H,W], intrinsics f64 [4] = fx, fy, cx, cy, poses f64 [F,4,4])`` of a 3DMatch raw sequence
     folder: ``frame-%06d.depth.png`` (16-bit), ``frame-%06d.pose.txt`` (camera-to-world), and ``camera-intrinsics.txt``
     (3x3) in the folder or in its parent.  ``require_poses=False``: a sequence in which a pose file is missing gives
-    ``poses = None`` (``track_sequence`` makes them) instead of an error."""
+    ``poses = None`` (``track_sequence`` makes them) instead of an error.  ``color=True`` appends uint8 [F,H,W,3]
+    (R, G, B) from ``frame-%06d.color.png`` next to every depth image (``track_sequence(color=)`` takes it); a missing
+    colour file, or one whose size is not the depth's, raises ``ValueError``."""
     try:
         from PIL import Image
     except ImportError as e:
@@ -640,7 +669,7 @@ def read_sequence(folder, require_poses=True):
         raise ValueError("%s: no camera-intrinsics.txt here or one folder up" % folder)
     if Kmat.shape != (3, 3):
         raise ValueError("camera-intrinsics.txt: expected a 3x3 matrix, got %s" % (Kmat.shape,))
-    depth, poses = [], []
+    depth, poses, rgb = [], [], []
     tracked = require_poses or all(exists(join(folder, n.replace('.depth.png', '.pose.txt'))) for n in names)
     for n in names:
         with Image.open(join(folder, n)) as im:
@@ -648,6 +677,16 @@ def read_sequence(folder, require_poses=True):
         if a.ndim != 2 or a.min() < 0 or a.max() > 65535:
             raise ValueError("%s: not a single-channel 16-bit image" % n)
         depth.append(a.astype(np.uint16))
+        if color:
+            cn = n.replace('.depth.png', '.color.png')
+            if not exists(join(folder, cn)):
+                raise ValueError("%s: no %s next to %s" % (folder, cn, n))
+            with Image.open(join(folder, cn)) as im:
+                c = np.array(im.convert('RGB'))
+            if c.shape[:2] != a.shape:
+                raise ValueError("%s is %d x %d, its depth image %d x %d: the colour must be registered to the depth"
+                                 % (cn, c.shape[1], c.shape[0], a.shape[1], a.shape[0]))
+            rgb.append(c.astype(np.uint8))
         if not tracked:
             continue
         P = np.loadtxt(join(folder, n.replace('.depth.png', '.pose.txt')), dtype=np.float64)
@@ -656,5 +695,6 @@ def read_sequence(folder, require_poses=True):
         poses.append(P)
     if len({d.shape for d in depth}) != 1:
         raise ValueError("%s: the depth images differ in size" % folder)
-    return (np.stack(depth), np.array([Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]]),
-            np.stack(poses) if tracked else None)
+    res = (np.stack(depth), np.array([Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]]),
+           np.stack(poses) if tracked else None)
+    return res + (np.stack(rgb),) if color else res

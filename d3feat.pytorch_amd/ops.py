@@ -5446,6 +5446,428 @@ def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERAT
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# RGB-D odometry: the depth odometry with a photometric term (csrc/rgbd_odometry.hpp has the rule;
+# csrc/rgbd_odometry.hip the kernels)
+# ---------------------------------------------------------------------------------------------------------------
+RGBD_SUMS = 31           # the 29 of the depth odometry (both kinds of rows in sum J J^T and sum J r), n_photo, sum r_I^2
+ODO_PHOTO_WEIGHT = 0.3   # profiles/rgbd_odometry_weight_sweep.txt: the largest of the swept weights that meets both
+#                          conditions of the sweep (the planar slide recovered, the textured room no worse than twice
+#                          the depth tracker's worst pair)
+_RGBD_KINDS = {'rgb8': 0, 'grey8': 1, 'f32': 2}      # D3F_RGBD_COLOR_*
+
+
+class RgbdPyramid(DepthPyramid):
+    """A ``DepthPyramid`` with the intensity pyramid beside it (``rgbd_pyramid``): ``intensity`` f32 [F, pixels] has
+    the layout of ``data`` (``intensity_level(l)`` is the view [F, H_l, W_l]).  ``data``, ``K`` and ``table`` are
+    ``depth_pyramid``'s bit for bit, so every ``depth_*`` function takes this object as it is."""
+
+    def __init__(self, data, K, H, W, levels, depth_diff, intensity):
+        DepthPyramid.__init__(self, data, K, H, W, levels, depth_diff)
+        self.intensity = intensity
+
+    def intensity_level(self, l):
+        h, w, off = (int(x) for x in self.table[l])
+        return self.intensity[:, off:off + h * w].reshape(self.frames, h, w)
+
+
+def _rgbd_color(color, shape, device_ok=False):
+    """Host form of the colour frames of depth frames of ``shape`` [F,H,W]: (array, kind) with kind 'rgb8' (uint8
+    [F,H,W,3]), 'grey8' (uint8 [F,H,W]) or 'f32' (f32 [F,H,W]; with ``device_ok`` a device f32 tensor stays one)."""
+    if isinstance(color, torch.Tensor):
+        if device_ok and color.is_cuda and color.dtype == torch.float32:
+            c = color.contiguous()
+        else:
+            c = color.detach().cpu().numpy()
+    else:
+        c = np.asarray(color)
+    if isinstance(c, torch.Tensor) or c.dtype == np.float32:
+        kind = 'f32'
+    elif c.dtype == np.uint8:
+        kind = 'rgb8' if c.ndim == 4 else 'grey8'
+    else:
+        raise ValueError("color must be uint8 [F,H,W,3] (R, G, B), uint8 [F,H,W] or float32 [F,H,W], got %s"
+                         % (c.dtype,))
+    want = tuple(shape) + ((3,) if kind == 'rgb8' else ())
+    if tuple(c.shape) != want:
+        raise ValueError("color of shape %s for depth frames of shape %s: expected %s"
+                         % (tuple(c.shape), tuple(shape), want))
+    return (c if isinstance(c, torch.Tensor) else np.ascontiguousarray(c)), kind
+
+
+def _rgbd_check_weight(photo_weight):
+    w = float(photo_weight)
+    if not 0.0 <= w <= float(np.finfo(np.float32).max):       # (a NaN fails; the kernels take it as f32)
+        raise ValueError("photo_weight must be a finite number >= 0, got %r" % (photo_weight,))
+    return w
+
+
+def _rgbd_pyramid(host, device, depth, color, intrinsics, levels, depth_scale, depth_max, depth_diff):
+    d = _tsdf_depth_array(depth, not host)
+    c, kind = _rgbd_color(color, d.shape, device_ok=not host)
+    base = _depth_pyramid(host, device, depth, intrinsics, levels, depth_scale, depth_max, depth_diff)
+    tc = c if isinstance(c, torch.Tensor) else _on(device, c)[0]
+    inten = torch.empty_like(base.data)
+    L = _native.lib()
+    args = (_p(tc), _RGBD_KINDS[kind], base.frames, base.H, base.W, base.levels, _p(inten))
+    if host:
+        _native.check(L.d3f_rgbd_pyramid_host(*args), "d3f_rgbd_pyramid_host")
+    else:
+        _native.check(L.d3f_rgbd_pyramid(*(args + (_stream(),))), "d3f_rgbd_pyramid")
+    return RgbdPyramid(base.data, base.K, base.H, base.W, base.levels, base.depth_diff, inten)
+
+
+def rgbd_pyramid(depth, color, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                 depth_diff=ODO_DEPTH_DIFF):
+    """The depth and intensity pyramids of F frames on the device (d3f_depth_pyramid and d3f_rgbd_pyramid; the rule is
+    csrc/rgbd_odometry.hpp): an ``RgbdPyramid`` whose ``data``, ``table`` and ``K`` are ``depth_pyramid``'s bit for
+    bit, with ``.intensity`` f32 [F, pixels] in the same layout.  ``color``: uint8 [F,H,W,3] (R, G, B;
+    I = ((0.299 R + 0.587 G) + 0.114 B) / 255 in f32), uint8 [F,H,W] (I = v / 255) or f32 [F,H,W] (as it is; a device
+    tensor is taken where it is), H and W the depth's, registered to the depth pixel by pixel.  A coarser pixel is the
+    f32 sum of its 2x2 block in raster order divided by 4; an odd last row or column is dropped.  Intensity has no
+    validity: a non-finite f32 value propagates into the coarser pixels above it and is excluded where the tracker
+    reads it.  Equal to the host twin and ``rgbd_pyramid_numpy`` bit for bit."""
+    dev = _tsdf_device()
+    with _region("rgbd_pyramid"):
+        return _rgbd_pyramid(False, dev, depth, color, intrinsics, levels, depth_scale, depth_max, depth_diff)
+
+
+def rgbd_pyramid_host(depth, color, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                      depth_diff=ODO_DEPTH_DIFF):
+    """The host twin of ``rgbd_pyramid`` (d3f_depth_pyramid_host, d3f_rgbd_pyramid_host): CPU tensors, no GPU call."""
+    return _rgbd_pyramid(True, torch.device("cpu"), depth, color, intrinsics, levels, depth_scale, depth_max,
+                         depth_diff)
+
+
+def _rgbd_device_pyramid(pyr, what):
+    if not isinstance(pyr, RgbdPyramid) or not isinstance(pyr.data, torch.Tensor) or not pyr.data.is_cuda:
+        raise RuntimeError("%s takes the RgbdPyramid of ops.rgbd_pyramid (on the device); the host twin is %s_host, "
+                           "the NumPy restatement %s_numpy" % (what, what, what))
+    return pyr
+
+
+def _rgbd_host_pyramid(pyr, what):
+    if not isinstance(pyr, RgbdPyramid) or not isinstance(pyr.data, torch.Tensor) or pyr.data.is_cuda:
+        raise RuntimeError("%s takes the RgbdPyramid of ops.rgbd_pyramid_host (CPU tensors)" % what)
+    return pyr
+
+
+def _rgbd_step(host, pyr, pairs, T, level, max_distance, photo_weight, return_index):
+    device = pyr.data.device
+    pr, t = _odo_pairs(pairs, T, "rgbd_odometry_step")
+    level, P = int(level), pr.shape[0]
+    if not 0 <= level < pyr.levels:
+        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    w = _rgbd_check_weight(photo_weight)
+    h, wd = int(pyr.table[level, 0]), int(pyr.table[level, 1])
+    sums = torch.zeros((P, RGBD_SUMS), dtype=torch.float64, device=device)
+    index = torch.full((P, h, wd), -1, dtype=torch.int32, device=device) if return_index else None
+    if P:
+        tp, tt = _on(device, pr, t)
+        L = _native.lib()
+        args = (_p(pyr.data), _p(pyr.intensity), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
+                level, _odo_check_distance(max_distance), pyr.depth_diff, w, _p(sums), _p(index))
+        if host:
+            _native.check(L.d3f_rgbd_odometry_step_host(*args), "d3f_rgbd_odometry_step_host")
+        else:
+            nbytes = L.d3f_rgbd_odometry_ws_bytes(P, pyr.H, pyr.W)
+            ws = _ws(nbytes, device)
+            _native.check(L.d3f_rgbd_odometry_step(*(args + (_p(ws), nbytes, _stream()))), "d3f_rgbd_odometry_step")
+    return (sums, index) if return_index else sums
+
+
+def rgbd_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, photo_weight=ODO_PHOTO_WEIGHT,
+                       return_index=False):
+    """ONE association of P frame pairs at ``level`` under ``T`` with both terms (d3f_rgbd_odometry_step): ``sums`` f64
+    [P,31] on the device.  The first 29 are ``depth_odometry_step``'s, where sum J J^T and sum J r also hold the
+    photometric rows ``photo_weight * [a x q, q]`` and ``photo_weight * r_I`` (n and sum d2 stay geometric); then
+    n_photo and sum r_I^2 (unweighted).  The association, and with it the index of ``return_index=True``, is
+    ``depth_odometry_step``'s.  An accepted pixel has a photometric row when the 2x2 bilinear footprint of its
+    unrounded projection and the central differences at it lie inside the fixed image and every intensity read is
+    finite.  ``photo_weight=0`` skips the term (n_photo = 0)."""
+    _rgbd_device_pyramid(pyr, "rgbd_odometry_step")
+    with _region("rgbd_odometry_step"):
+        return _rgbd_step(False, pyr, pairs, T, level, max_distance, photo_weight, return_index)
+
+
+def rgbd_odometry_step_host(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, photo_weight=ODO_PHOTO_WEIGHT,
+                            return_index=False):
+    """The host twin of ``rgbd_odometry_step`` (d3f_rgbd_odometry_step_host): the same rule pixel by pixel in raster
+    order, CPU tensors, no GPU call."""
+    return _rgbd_step(True, _rgbd_host_pyramid(pyr, "rgbd_odometry_step_host"), pairs, T, level, max_distance,
+                      photo_weight, return_index)
+
+
+def _rgbd_odometry(host, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information):
+    device = pyr.data.device
+    pr, t = _odo_pairs(pairs, T_init, "rgbd_odometry")
+    it = _odo_iterations(iterations, pyr.levels)
+    w = _rgbd_check_weight(photo_weight)
+    P = pr.shape[0]
+    T = torch.zeros((P, 4, 4), dtype=torch.float64, device=device)
+    count = torch.zeros(P, dtype=torch.int32, device=device)
+    rmse = torch.zeros(P, dtype=torch.float64, device=device)
+    status = torch.zeros(P, dtype=torch.int32, device=device)
+    n_photo = torch.zeros(P, dtype=torch.int32, device=device)
+    info = torch.zeros((P, 6, 6), dtype=torch.float64, device=device) if return_information else None
+    if P:
+        tp, tt = _on(device, pr, t)
+        L = _native.lib()
+        counts = (ctypes.c_int32 * len(it))(*it)
+        args = (_p(pyr.data), _p(pyr.intensity), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
+                ctypes.cast(counts, ctypes.c_void_p), _odo_check_distance(max_distance), pyr.depth_diff, w, _p(T),
+                _p(count), _p(rmse), _p(status), _p(n_photo), _p(info))
+        if host:
+            _native.check(L.d3f_rgbd_odometry_host(*args), "d3f_rgbd_odometry_host")
+        else:
+            nbytes = L.d3f_rgbd_odometry_ws_bytes(P, pyr.H, pyr.W)
+            ws = _ws(nbytes, device)
+            _native.check(L.d3f_rgbd_odometry(*(args + (_p(ws), nbytes, _stream()))), "d3f_rgbd_odometry")
+    res = (T, count, rmse, status)
+    return res + ((info,) if return_information else ()) + (n_photo,)
+
+
+def _rgbd_frames(pyr_or_frames, intrinsics):
+    if intrinsics is None:
+        raise ValueError("(depth, color) frames need intrinsics")
+    if not isinstance(pyr_or_frames, (tuple, list)) or len(pyr_or_frames) != 2:
+        raise ValueError("expected an RgbdPyramid or the pair (depth, color) of frames")
+    return pyr_or_frames
+
+
+def rgbd_odometry(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                  photo_weight=ODO_PHOTO_WEIGHT, return_information=False, intrinsics=None, depth_scale=1000.0,
+                  depth_max=TSDF_DEPTH_MAX, depth_diff=ODO_DEPTH_DIFF):
+    """Relative poses of P frame pairs from depth AND intensity, all pairs in one launch sequence (d3f_rgbd_odometry;
+    the rule is csrc/rgbd_odometry.hpp): ``depth_odometry`` with a photometric row per pixel beside the point-to-plane
+    row -- the hybrid objective of Park, Zhou, Koltun 2017 after Steinbruecker et al. 2011, what Open3D's
+    ``compute_rgbd_odometry`` minimises.  The intensity residual ``r_I = I_b(projection of a) - I_a(pixel)`` constrains
+    the three motions a view of one plane leaves free, so such a pair is tracked where ``depth_odometry`` reports
+    ``ODO_ST_SINGULAR``.
+
+    ``pyr_or_frames``: the ``RgbdPyramid`` of ``rgbd_pyramid``, or ``(depth, color)`` frames with ``intrinsics``.
+    Everything else is ``depth_odometry``'s: pairs, T, iterations, ``max_distance``, the statuses (``ODO_ST_FEW`` by
+    the geometric count, ``ODO_ST_SINGULAR`` by the combined system), count and rmse (geometric).  ``photo_weight``
+    is a plain scale between the two residuals: intensity is in [0, 1], the geometric residual in metres, and the
+    photometric row and residual are multiplied by it (its square weighs the squared term).  The default
+    ``ODO_PHOTO_WEIGHT`` comes from profiles/rgbd_odometry_weight_sweep.txt.  ``photo_weight=0`` gives
+    ``depth_odometry``'s results bit for bit.  The colour must be registered to the depth and keep a surface's
+    brightness from frame to frame (no auto-exposure).
+
+    Returns device tensors ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P], n_photo int32 [P])``;
+    ``return_information=True`` inserts f64 [P,6,6] = the combined sum J J^T of the final association (rotation first,
+    fixed frame) before ``n_photo``, which is the number of photometric rows of that association.  A pair's result is
+    bit-identical alone, in any batch, and from run to run."""
+    if isinstance(pyr_or_frames, DepthPyramid):
+        pyr = _rgbd_device_pyramid(pyr_or_frames, "rgbd_odometry")
+    else:
+        d, c = _rgbd_frames(pyr_or_frames, intrinsics)
+        pyr = rgbd_pyramid(d, c, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max, depth_diff)
+    with _region("rgbd_odometry"):
+        return _rgbd_odometry(False, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
+
+
+def rgbd_odometry_host(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                       photo_weight=ODO_PHOTO_WEIGHT, return_information=False, intrinsics=None, depth_scale=1000.0,
+                       depth_max=TSDF_DEPTH_MAX, depth_diff=ODO_DEPTH_DIFF):
+    """The host twin of ``rgbd_odometry`` (d3f_rgbd_odometry_host): CPU tensors, no GPU call.  It sums in raster
+    order, so T agrees with the device's to rounding (1e-6), not bit for bit."""
+    if isinstance(pyr_or_frames, DepthPyramid):
+        pyr = _rgbd_host_pyramid(pyr_or_frames, "rgbd_odometry_host")
+    else:
+        d, c = _rgbd_frames(pyr_or_frames, intrinsics)
+        pyr = rgbd_pyramid_host(d, c, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max, depth_diff)
+    return _rgbd_odometry(True, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
+
+
+# ------------------------------------------------------------------------------------------- NumPy restatement
+def rgbd_pyramid_numpy(depth, color, intrinsics, levels=3, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                       depth_diff=ODO_DEPTH_DIFF):
+    """The contract of ``rgbd_pyramid`` in NumPy: an ``RgbdPyramid`` of NumPy arrays, equal to the kernels' bit for bit
+    (every f32 operation in the order of csrc/rgbd_odometry.hpp)."""
+    f32 = np.float32
+    base = depth_pyramid_numpy(depth, intrinsics, levels, depth_scale, depth_max, depth_diff)
+    c, kind = _rgbd_color(color, (base.frames, base.H, base.W))
+    with np.errstate(all='ignore'):
+        if kind == 'rgb8':
+            c = c.astype(f32)
+            cur = ((f32(0.299) * c[..., 0] + f32(0.587) * c[..., 1]) + f32(0.114) * c[..., 2]) / f32(255.0)
+        elif kind == 'grey8':
+            cur = c.astype(f32) / f32(255.0)
+        else:
+            cur = c
+        inten = np.zeros_like(base.data)
+        for l in range(base.levels):
+            h, w, off = (int(x) for x in base.table[l])
+            inten[:, off:off + h * w] = cur.reshape(base.frames, -1)
+            hn, wn = h >> 1, w >> 1
+            blk = lambda dy, dx: cur[:, dy:2 * hn:2, dx:2 * wn:2]
+            cur = (((blk(0, 0) + blk(0, 1)) + blk(1, 0)) + blk(1, 1)) / f32(4.0)
+    return RgbdPyramid(base.data, base.K, base.H, base.W, base.levels, base.depth_diff, inten)
+
+
+def _rgbd_numpy_pyramid(pyr):
+    if not isinstance(pyr, RgbdPyramid):
+        raise ValueError("expected an RgbdPyramid")
+    if isinstance(pyr.data, np.ndarray):
+        return pyr
+    return RgbdPyramid(_host_array(pyr.data), _host_array(pyr.K), pyr.H, pyr.W, pyr.levels, pyr.depth_diff,
+                       _host_array(pyr.intensity))
+
+
+def _rgbd_photometric_numpy(index, a, IA, IB, Kb):
+    """photometric() of csrc/rgbd_odometry.hpp for the accepted pixels of one association (``index`` int32 [H,W] and
+    ``a`` f32 [3,m] of ``_odo_associate_numpy``): (has bool [m], r f32 [m], q f32 [3,m])."""
+    f32 = np.float32
+    h, w = IA.shape
+    Ia = IA[index >= 0]
+    m = Ia.shape[0]
+    if m == 0 or h < 4 or w < 4:
+        return np.zeros(m, dtype=bool), np.zeros(m, dtype=f32), np.zeros((3, m), dtype=f32)
+    two = f32(2.0)
+    px = (Kb[0] * a[0]) / a[2] + Kb[2]
+    py = (Kb[1] * a[1]) / a[2] + Kb[3]
+    x0f, y0f = np.floor(px), np.floor(py)
+    has = (x0f >= 1) & (x0f <= f32(w - 3)) & (y0f >= 1) & (y0f <= f32(h - 3))
+    x0 = np.where(has, x0f, 1).astype(np.int64)
+    y0 = np.where(has, y0f, 1).astype(np.int64)
+    wx, wy = px - x0f, py - y0f
+    at = lambda dx, dy: IB[y0 + dy, x0 + dx]
+    u0, u1 = at(0, -1), at(1, -1)
+    m0, m1, m2, m3 = at(-1, 0), at(0, 0), at(1, 0), at(2, 0)
+    n0, n1, n2, n3 = at(-1, 1), at(0, 1), at(1, 1), at(2, 1)
+    d0, d1 = at(0, 2), at(1, 2)
+    for x in (Ia, u0, u1, m0, m1, m2, m3, n0, n1, n2, n3, d0, d1):
+        has &= np.isfinite(x)
+
+    def bilinear(c00, c10, c01, c11):
+        t = c00 + wx * (c10 - c00)
+        b = c01 + wx * (c11 - c01)
+        return t + wy * (b - t)
+
+    Ib = bilinear(m1, m2, n1, n2)
+    gx = bilinear((m2 - m0) / two, (m3 - m1) / two, (n2 - n0) / two, (n3 - n1) / two)
+    gy = bilinear((n1 - u0) / two, (n2 - u1) / two, (d0 - m1) / two, (d1 - m2) / two)
+    g0, g1 = gx * Kb[0], gy * Kb[1]
+    q = np.stack([g0 / a[2], g1 / a[2], -((g0 * a[0] + g1 * a[1]) / (a[2] * a[2]))]).astype(f32)
+    has &= np.isfinite(q).all(axis=0)
+    return has, (Ib - Ia).astype(f32), q
+
+
+def _rgbd_terms(a, q, r, w):
+    """add_photometric() of csrc/rgbd_odometry.hpp: f64 [m,31], what every photometric row adds to the sums."""
+    a, q, r = a.astype(np.float64), q.astype(np.float64), r.astype(np.float64)
+    J = [w * (a[1] * q[2] - a[2] * q[1]), w * (a[2] * q[0] - a[0] * q[2]), w * (a[0] * q[1] - a[1] * q[0]),
+         w * q[0], w * q[1], w * q[2]]
+    rw = w * r
+    zero = np.zeros_like(r)
+    cols = [zero] + [J[i] * J[j] for i, j in _ODO_UPPER] + [J[i] * rw for i in range(6)] + [zero, np.ones_like(r), r * r]
+    return np.stack(cols, axis=1) if r.size else np.zeros((0, RGBD_SUMS))
+
+
+def _rgbd_pair_terms(pyr, level, a, b, t, md, w, normals=None):
+    """(index int32 [H_l,W_l], terms f64 [m + m_photo, 31]) of one association of the pair (a, b): the geometric rows
+    (zero in the last two columns), then the photometric rows, each in raster order."""
+    imgs, inten = pyr.level(level), pyr.intensity_level(level)
+    key = (b, level)
+    fixed = normals.get(key) if normals is not None else None
+    if fixed is None:
+        fixed = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
+        if normals is not None:
+            normals[key] = fixed
+    index, av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], fixed, pyr.K[b, level], t, md)
+    geo = np.concatenate([_odo_terms(av, yv, nv), np.zeros((av.shape[1], 2))], axis=1)
+    if w == 0.0:
+        return index, geo
+    has, r, q = _rgbd_photometric_numpy(index, av, inten[a], inten[b], pyr.K[b, level])
+    return index, np.concatenate([geo, _rgbd_terms(av[:, has], q[:, has], r[has], w)], axis=0)
+
+
+def rgbd_odometry_step_numpy(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, photo_weight=ODO_PHOTO_WEIGHT,
+                             return_index=False, return_terms=False):
+    """The contract of ``rgbd_odometry_step`` in NumPy: ``sums`` f64 [P,31] (NumPy's own summation order: equal to the
+    kernel's within the summation bound, not bit for bit) and, with ``return_index``, the index int32 [P,H_l,W_l],
+    which is equal.  ``return_terms=True`` appends the list of the f64 [m_p + m_photo_p, 31] rows the sums are made
+    of: the geometric terms, then the photometric ones."""
+    pyr = _rgbd_numpy_pyramid(pyr)
+    pr, t = _odo_pairs(pairs, T, "rgbd_odometry_step_numpy")
+    level = int(level)
+    if not 0 <= level < pyr.levels:
+        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    w = float(np.float32(_rgbd_check_weight(photo_weight)))
+    md = _odo_check_distance(max_distance)
+    h, wd = int(pyr.table[level, 0]), int(pyr.table[level, 1])
+    sums = np.zeros((pr.shape[0], RGBD_SUMS))
+    index = np.full((pr.shape[0], h, wd), -1, dtype=np.int32)
+    terms = []
+    with np.errstate(all='ignore'):
+        for p in range(pr.shape[0]):
+            terms.append(np.zeros((0, RGBD_SUMS)))
+            if not _odo_pair_ok(pr[p], t[p], pyr.frames):
+                continue
+            index[p], terms[-1] = _rgbd_pair_terms(pyr, level, int(pr[p, 0]), int(pr[p, 1]), t[p], md, w)
+            sums[p] = terms[-1].sum(axis=0)
+    res = (sums,) + ((index,) if return_index else ()) + ((terms,) if return_terms else ())
+    return res if len(res) > 1 else sums
+
+
+def rgbd_odometry_numpy(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                        photo_weight=ODO_PHOTO_WEIGHT, return_information=False, intrinsics=None, depth_scale=1000.0,
+                        depth_max=TSDF_DEPTH_MAX, depth_diff=ODO_DEPTH_DIFF):
+    """The contract of ``rgbd_odometry`` in NumPy: ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P],
+    [information f64 [P,6,6],] n_photo int32 [P])``; T agrees with the kernel's to rounding, not bit for bit."""
+    it = _odo_iterations(iterations)
+    if isinstance(pyr_or_frames, DepthPyramid):
+        pyr = _rgbd_numpy_pyramid(pyr_or_frames)
+        _odo_iterations(iterations, pyr.levels)
+    else:
+        d, c = _rgbd_frames(pyr_or_frames, intrinsics)
+        pyr = rgbd_pyramid_numpy(d, c, intrinsics, len(it), depth_scale, depth_max, depth_diff)
+    pr, t0 = _odo_pairs(pairs, T_init, "rgbd_odometry_numpy")
+    md = _odo_check_distance(max_distance)
+    w = float(np.float32(_rgbd_check_weight(photo_weight)))
+    P = pr.shape[0]
+    T = np.zeros((P, 4, 4))
+    T[:, 3, 3] = 1.0
+    T[:, :3, :] = t0.reshape(P, 3, 4)
+    count = np.zeros(P, dtype=np.int32)
+    rmse = np.zeros(P)
+    status = np.zeros(P, dtype=np.int32)
+    n_photo = np.zeros(P, dtype=np.int32)
+    info = np.zeros((P, 6, 6))
+    normals = {}
+    sums_at = lambda p, level, t: _rgbd_pair_terms(pyr, level, int(pr[p, 0]), int(pr[p, 1]), t, md, w,
+                                                   normals)[1].sum(axis=0)
+    with np.errstate(all='ignore'):
+        for p in range(P):
+            if not (0 <= pr[p, 0] < pyr.frames and 0 <= pr[p, 1] < pyr.frames):
+                status[p] |= ODO_ST_PAIR
+            if not np.isfinite(t0[p]).all():
+                status[p] |= ODO_ST_NONFINITE
+            if status[p]:
+                continue
+            t, singular = t0[p].copy(), False
+            for level in range(pyr.levels - 1, -1, -1):
+                for _ in range(it[level]):
+                    t, _moved, s = _odo_plane_step(sums_at(p, level, t), t)
+                    if level == 0:
+                        singular = s
+            sums = sums_at(p, 0, t)
+            if sums[0] < ODO_MIN_PIXELS:
+                status[p] = ODO_ST_FEW
+            elif singular:
+                status[p] = ODO_ST_SINGULAR
+            else:
+                T[p, :3, :] = t.reshape(3, 4)
+                count[p] = int(sums[0])
+                rmse[p] = np.sqrt(sums[28] / sums[0])
+                n_photo[p] = int(sums[29])
+                for k, (i, j) in enumerate(_ODO_UPPER):
+                    info[p, i, j] = info[p, j, i] = sums[1 + k]
+    res = (T, count, rmse, status)
+    return res + ((info,) if return_information else ()) + (n_photo,)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # guarded SGD step on flat buffers (trainer.py:104-111 + training_3DMatch.py:62-76)
 # ---------------------------------------------------------------------------------------------------------------
 def sgd_guarded_step(grad, params, momentum_buf, lr, momentum, weight_decay, state, hyper=None, pair_status=None):

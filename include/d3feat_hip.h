@@ -1382,6 +1382,58 @@ int d3f_depth_odometry_host(const float* pyramid, const float* level_intrinsics,
                             int32_t* status, double* information);
 
 /* ------------------------------------------------------------------------------------------------
+ * RGB-D odometry: the depth odometry above with a photometric term, so that a view of a single plane, which leaves
+ * the depth-only system singular, is tracked by its texture (the hybrid objective of Park, Zhou, Koltun 2017 after
+ * Steinbruecker et al. 2011; it stands in for Open3D's compute_rgbd_odometry, which the reference's fragment maker
+ * calls; csrc/rgbd_odometry.hpp states the rule in full, on top of csrc/odometry.hpp).
+ * The intensity pyramid is a second packed f32 array [F, d3f_depth_pyramid_pixels(H, W, levels)] with the depth
+ * pyramid's level table.  Level 0 from `color`: D3F_RGBD_COLOR_RGB8 uint8 [F, H, W, 3],
+ * I = ((0.299 R + 0.587 G) + 0.114 B) / 255 in f32; D3F_RGBD_COLOR_GREY8 uint8 [F, H, W], I = v / 255;
+ * D3F_RGBD_COLOR_F32 f32 [F, H, W] as it is.  A coarser pixel is the f32 sum of its 2x2 block in raster order divided
+ * by 4.  There is no validity: a non-finite value propagates upwards and is excluded where it is read.
+ * An association is d3f_depth_odometry_step's: the same accepted pixels and index.  An accepted pixel whose unrounded
+ * projection has its 2x2 bilinear footprint and the central differences at it inside the fixed image, with every
+ * intensity read finite, adds a second row J_I = [a x q, q], r_I = I_b(projection) - I_a(pixel), q the derivative of
+ * the sampled intensity with respect to the point, both scaled by photo_weight (>= 0, finite; intensity in [0, 1]
+ * against metres).  D3F_RGBD_SUMS = 31 sums per pair: the 29 above, with sum J J^T and sum J r over both kinds of rows
+ * and n, sum d2 geometric as before, then n_photo and sum r_I^2 (unweighted).  photo_weight = 0 skips the term:
+ * n_photo = 0 and everything else equals the depth odometry's bit for bit.
+ * d3f_rgbd_pyramid: the intensity pyramid alone (the depth pyramid and the intrinsics are d3f_depth_pyramid's); one
+ *   launch per level, one thread per output pixel.  Device, host twin and the NumPy restatement agree bit for bit.
+ * d3f_rgbd_odometry_step: ONE association at `level` under T [P, 12]: sums [P, 31] and the index as above.
+ * d3f_rgbd_odometry: d3f_depth_odometry's schedule, outputs and statuses (D3F_ODO_ST_FEW by the geometric count,
+ *   D3F_ODO_ST_SINGULAR by the combined system), information = the combined sum J J^T, and n_photo [P] int32 of the
+ *   final association (0 with a status).  Same determinism and batch independence; no host synchronisation.
+ * ws: d3f_rgbd_odometry_ws_bytes(P, H, W) bytes, for both device entry points.
+ * The _host twins take host pointers, sum in raster order and make no GPU call.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_RGBD_SUMS 31
+#define D3F_RGBD_COLOR_RGB8 0
+#define D3F_RGBD_COLOR_GREY8 1
+#define D3F_RGBD_COLOR_F32 2
+int d3f_rgbd_pyramid(const void* color, int color_kind, int F, int H, int W, int levels, float* intensity,
+                     void* stream);
+int d3f_rgbd_pyramid_host(const void* color, int color_kind, int F, int H, int W, int levels, float* intensity);
+size_t d3f_rgbd_odometry_ws_bytes(int P, int H, int W);
+int d3f_rgbd_odometry_step(const float* pyramid, const float* intensity, const float* level_intrinsics, int F, int H,
+                           int W, int levels, const int32_t* pairs, int P, const double* T, int level,
+                           float max_distance, float depth_diff, float photo_weight, double* sums, int32_t* index,
+                           void* ws, size_t ws_bytes, void* stream);
+int d3f_rgbd_odometry_step_host(const float* pyramid, const float* intensity, const float* level_intrinsics, int F,
+                                int H, int W, int levels, const int32_t* pairs, int P, const double* T, int level,
+                                float max_distance, float depth_diff, float photo_weight, double* sums,
+                                int32_t* index);
+int d3f_rgbd_odometry(const float* pyramid, const float* intensity, const float* level_intrinsics, int F, int H, int W,
+                      int levels, const int32_t* pairs, int P, const double* T_init, const int32_t* iterations_host,
+                      float max_distance, float depth_diff, float photo_weight, double* T, int32_t* count, double* rmse,
+                      int32_t* status, int32_t* n_photo, double* information, void* ws, size_t ws_bytes, void* stream);
+int d3f_rgbd_odometry_host(const float* pyramid, const float* intensity, const float* level_intrinsics, int F, int H,
+                           int W, int levels, const int32_t* pairs, int P, const double* T_init,
+                           const int32_t* iterations_host, float max_distance, float depth_diff, float photo_weight,
+                           double* T, int32_t* count, double* rmse, int32_t* status, int32_t* n_photo,
+                           double* information);
+
+/* ------------------------------------------------------------------------------------------------
  * KPConv with the non-default influence / aggregation modes -- models/blocks.py:327-352 (KP_influence 'constant' /
  * 'gaussian', aggregation_mode 'closest'; the D3Feat configuration uses 'linear' / 'sum', config.py:39,41, which the
  * fused entry points above implement).  mode = influence (0 linear, 1 constant, 2 gaussian) | 4 for 'closest'.
