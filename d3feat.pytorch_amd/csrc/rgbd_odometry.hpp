@@ -1,5 +1,5 @@
 // RGB-D odometry: depth odometry (odometry.hpp) with a photometric term, the "hybrid" objective of Park, Zhou, Koltun
-// 2017 after Steinbruecker et al. 2011 (rgbd_odometry.hip; d3f_rgbd_pyramid, d3f_rgbd_odometry_step, d3f_rgbd_odometry
+// 2017 after Steinbruecker et al. 2011 (odometry.hip; d3f_rgbd_pyramid, d3f_rgbd_odometry_step, d3f_rgbd_odometry
 // and their host twins).  Everything here is __host__ __device__ and reads no state: the kernels and the host twins run
 // this text, and ops.rgbd_pyramid_numpy / rgbd_odometry_step_numpy / rgbd_odometry_numpy restate it.  f32 arithmetic
 // runs in exactly the order written (-ffp-contract=off; f32 division is correctly rounded on both sides); f64 is used

@@ -362,23 +362,17 @@ def _track_pairs(depth, K, levels, iterations, cpu, max_bytes, depth_scale, dept
     per_chunk = max(2, int(max_bytes) // max(frame_bytes, 1))
     T = np.broadcast_to(np.eye(4), (max(F - 1, 0), 4, 4)).copy()
     status = np.zeros(max(F - 1, 0), dtype=np.int32)
+    pyramid, track = {(False, False): (ops.depth_pyramid, ops.depth_odometry),
+                      (False, True): (ops.depth_pyramid_numpy, ops.depth_odometry_numpy),
+                      (True, False): (ops.rgbd_pyramid, ops.rgbd_odometry),
+                      (True, True): (ops.rgbd_pyramid_numpy, ops.rgbd_odometry_numpy)}[color is not None, bool(cpu)]
     for lo in range(0, F - 1, per_chunk - 1):
         hi = min(lo + per_chunk, F)                       # frames [lo, hi): the pairs (lo+1, lo) .. (hi-1, hi-2)
         pairs = np.stack([np.arange(1, hi - lo), np.arange(0, hi - lo - 1)], axis=1)
-        args = (depth[lo:hi], K[lo:hi], levels, depth_scale, depth_max, depth_diff)
-        if color is not None:
-            args = (args[0], color[lo:hi]) + args[1:]
-            if cpu:
-                res = ops.rgbd_odometry_numpy(ops.rgbd_pyramid_numpy(*args), pairs, None, iterations, **odometry)
-            else:
-                res = [t.cpu().numpy() for t in ops.rgbd_odometry(ops.rgbd_pyramid(*args), pairs, None, iterations,
-                                                                  **odometry)]
-        elif cpu:
-            res = ops.depth_odometry_numpy(ops.depth_pyramid_numpy(*args), pairs, None, iterations, **odometry)
-        else:
-            res = [t.cpu().numpy() for t in ops.depth_odometry(ops.depth_pyramid(*args), pairs, None, iterations,
-                                                               **odometry)]
-        T[lo:hi - 1], status[lo:hi - 1] = res[0], res[3]
+        frames = (depth[lo:hi],) if color is None else (depth[lo:hi], color[lo:hi])
+        pyr = pyramid(*(frames + (K[lo:hi], levels, depth_scale, depth_max, depth_diff)))
+        res = track(pyr, pairs, None, iterations, **odometry)
+        T[lo:hi - 1], status[lo:hi - 1] = ops._host_array(res[0]), ops._host_array(res[3])
     return T, status
 
 

@@ -4920,7 +4920,7 @@ def tsdf_extend_numpy(sv, D, w, depth, frame_start, intrinsics, camera_to_volume
 
 # ---------------------------------------------------------------------------------------------------------------
 # Depth odometry: camera poses of a depth sequence by projective point-to-plane ICP over a depth pyramid
-# (csrc/odometry.hpp has the rule; csrc/odometry.hip the kernels)
+# (csrc/odometry.hpp has the rule; csrc/odometry.hip the kernels, of this section and the next)
 # ---------------------------------------------------------------------------------------------------------------
 ODO_ST_FEW = 1           # D3F_ODO_ST_FEW: the final association has fewer than 6 accepted pixels
 ODO_ST_PAIR = 4          # D3F_ODO_ST_PAIR: a frame index outside [0, F)
@@ -5045,40 +5045,56 @@ def _odo_check_distance(max_distance):
     return float(max_distance)
 
 
-def _odo_step(host, pyr, pairs, T, level, max_distance, return_index):
+def _odo_check_level(level, pyr):
+    if not 0 <= int(level) < pyr.levels:
+        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, int(level)))
+    return int(level)
+
+
+def _odo_call(stem, what, host, pyr, pr, t, rest):
+    """Calls d3f_<stem>_odometry<what> (with its workspace, on the stream) or its ``_host`` twin: the pyramid, the
+    pairs and their poses, then ``rest``.  ``stem`` 'rgbd' passes the intensity too."""
     device = pyr.data.device
-    pr, t = _odo_pairs(pairs, T, "depth_odometry_step")
-    level, P = int(level), pr.shape[0]
-    if not 0 <= level < pyr.levels:
-        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    tp, tt = _on(device, pr, t)
+    L = _native.lib()
+    P = pr.shape[0]
+    name = "d3f_%s_odometry%s" % (stem, what)
+    args = ((_p(pyr.data),) + ((_p(pyr.intensity),) if stem == "rgbd" else ())
+            + (_p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt)) + rest)
+    if host:
+        _native.check(getattr(L, name + "_host")(*args), name + "_host")
+    else:
+        nbytes = getattr(L, "d3f_%s_odometry_ws_bytes" % stem)(P, pyr.H, pyr.W)
+        ws = _ws(nbytes, device)
+        _native.check(getattr(L, name)(*(args + (_p(ws), nbytes, _stream()))), name)
+
+
+def _odo_step(host, pyr, pairs, T, level, max_distance, photo_weight, return_index):
+    """One association on the host or the device; ``photo_weight`` None: the depth entry points, else the RGB-D
+    ones."""
+    stem = "depth" if photo_weight is None else "rgbd"
+    device = pyr.data.device
+    pr, t = _odo_pairs(pairs, T, stem + "_odometry_step")
+    level, P = _odo_check_level(level, pyr), pr.shape[0]
+    weight = () if photo_weight is None else (_rgbd_check_weight(photo_weight),)
     h, w = int(pyr.table[level, 0]), int(pyr.table[level, 1])
-    sums = torch.zeros((P, ODO_SUMS), dtype=torch.float64, device=device)
+    sums = torch.zeros((P, RGBD_SUMS if weight else ODO_SUMS), dtype=torch.float64, device=device)
     index = torch.full((P, h, w), -1, dtype=torch.int32, device=device) if return_index else None
     if P:
-        tp, tt = _on(device, pr, t)
-        L = _native.lib()
-        args = (_p(pyr.data), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt), level,
-                _odo_check_distance(max_distance), pyr.depth_diff, _p(sums), _p(index))
-        if host:
-            _native.check(L.d3f_depth_odometry_step_host(*args), "d3f_depth_odometry_step_host")
-        else:
-            nbytes = L.d3f_depth_odometry_ws_bytes(P, pyr.H, pyr.W)
-            ws = _ws(nbytes, device)
-            _native.check(L.d3f_depth_odometry_step(*(args + (_p(ws), nbytes, _stream()))), "d3f_depth_odometry_step")
+        _odo_call(stem, "_step", host, pyr, pr, t, (level, _odo_check_distance(max_distance), pyr.depth_diff) + weight
+                  + (_p(sums), _p(index)))
     return (sums, index) if return_index else sums
 
 
-def _odo_device_pyramid(pyr, what):
-    if not isinstance(pyr, DepthPyramid) or not isinstance(pyr.data, torch.Tensor) or not pyr.data.is_cuda:
-        raise RuntimeError("%s takes the DepthPyramid of ops.depth_pyramid (on the device); the host twin is %s_host, "
-                           "the NumPy restatement %s_numpy" % (what, what, what))
-    return pyr
-
-
-def _odo_host_pyramid(pyr, what):
-    if not isinstance(pyr, DepthPyramid) or not isinstance(pyr.data, torch.Tensor) or pyr.data.is_cuda:
-        raise RuntimeError("%s takes the DepthPyramid of ops.depth_pyramid_host (CPU tensors)" % what)
-    return pyr
+def _odo_checked_pyramid(pyr, what, cls, host):
+    """``pyr`` when it is a ``cls`` (DepthPyramid or RgbdPyramid) of CPU tensors (``host``) or of device tensors."""
+    if isinstance(pyr, cls) and isinstance(pyr.data, torch.Tensor) and pyr.data.is_cuda != host:
+        return pyr
+    made_by = "ops.rgbd_pyramid" if cls is RgbdPyramid else "ops.depth_pyramid"
+    if host:
+        raise RuntimeError("%s takes the %s of %s_host (CPU tensors)" % (what, cls.__name__, made_by))
+    raise RuntimeError("%s takes the %s of %s (on the device); the host twin is %s_host, "
+                       "the NumPy restatement %s_numpy" % (what, cls.__name__, made_by, what, what))
 
 
 def depth_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False):
@@ -5088,16 +5104,16 @@ def depth_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, ret
     a's camera frame into b's.  ``return_index=True`` appends int32 [P, H_l, W_l]: per moving pixel the raster index of
     the accepted fixed pixel, or -1.  A pair that names a frame outside the pyramid, or whose T is not finite, gives
     zero sums and -1 everywhere."""
-    _odo_device_pyramid(pyr, "depth_odometry_step")
+    _odo_checked_pyramid(pyr, "depth_odometry_step", DepthPyramid, False)
     with _region("depth_odometry_step"):
-        return _odo_step(False, pyr, pairs, T, level, max_distance, return_index)
+        return _odo_step(False, pyr, pairs, T, level, max_distance, None, return_index)
 
 
 def depth_odometry_step_host(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False):
     """The host twin of ``depth_odometry_step`` (d3f_depth_odometry_step_host): the same rule pixel by pixel in raster
     order, CPU tensors, no GPU call."""
-    return _odo_step(True, _odo_host_pyramid(pyr, "depth_odometry_step_host"), pairs, T, level, max_distance,
-                     return_index)
+    return _odo_step(True, _odo_checked_pyramid(pyr, "depth_odometry_step_host", DepthPyramid, True), pairs, T, level,
+                     max_distance, None, return_index)
 
 
 def _odo_iterations(iterations, levels=None):
@@ -5110,31 +5126,27 @@ def _odo_iterations(iterations, levels=None):
     return it
 
 
-def _odometry(host, pyr, pairs, T_init, iterations, max_distance, return_information):
+def _odometry(host, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information):
+    """The whole odometry on the host or the device; ``photo_weight`` None: the depth entry points, else the RGB-D
+    ones, whose ``n_photo`` ends the result."""
+    stem = "depth" if photo_weight is None else "rgbd"
     device = pyr.data.device
-    pr, t = _odo_pairs(pairs, T_init, "depth_odometry")
+    pr, t = _odo_pairs(pairs, T_init, stem + "_odometry")
     it = _odo_iterations(iterations, pyr.levels)
+    weight = () if photo_weight is None else (_rgbd_check_weight(photo_weight),)
     P = pr.shape[0]
     T = torch.zeros((P, 4, 4), dtype=torch.float64, device=device)
     count = torch.zeros(P, dtype=torch.int32, device=device)
     rmse = torch.zeros(P, dtype=torch.float64, device=device)
     status = torch.zeros(P, dtype=torch.int32, device=device)
+    n_photo = (torch.zeros(P, dtype=torch.int32, device=device),) if weight else ()
     info = torch.zeros((P, 6, 6), dtype=torch.float64, device=device) if return_information else None
     if P:
-        tp, tt = _on(device, pr, t)
-        L = _native.lib()
         counts = (ctypes.c_int32 * len(it))(*it)
-        args = (_p(pyr.data), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
-                ctypes.cast(counts, ctypes.c_void_p), _odo_check_distance(max_distance), pyr.depth_diff, _p(T),
-                _p(count), _p(rmse), _p(status), _p(info))
-        if host:
-            _native.check(L.d3f_depth_odometry_host(*args), "d3f_depth_odometry_host")
-        else:
-            nbytes = L.d3f_depth_odometry_ws_bytes(P, pyr.H, pyr.W)
-            ws = _ws(nbytes, device)
-            _native.check(L.d3f_depth_odometry(*(args + (_p(ws), nbytes, _stream()))), "d3f_depth_odometry")
-    res = (T, count, rmse, status)
-    return res + (info,) if return_information else res
+        _odo_call(stem, "", host, pyr, pr, t,
+                  (ctypes.cast(counts, ctypes.c_void_p), _odo_check_distance(max_distance), pyr.depth_diff) + weight
+                  + (_p(T), _p(count), _p(rmse), _p(status)) + tuple(_p(n) for n in n_photo) + (_p(info),))
+    return (T, count, rmse, status) + ((info,) if return_information else ()) + n_photo
 
 
 def depth_odometry(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
@@ -5162,14 +5174,14 @@ def depth_odometry(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, 
     ``frame='fixed', order='rotation_first'`` has the same layout.  A pair's result is bit-identical alone, in any
     batch, and from run to run."""
     if isinstance(pyr_or_depth, DepthPyramid):
-        pyr = _odo_device_pyramid(pyr_or_depth, "depth_odometry")
+        pyr = _odo_checked_pyramid(pyr_or_depth, "depth_odometry", DepthPyramid, False)
     else:
         if intrinsics is None:
             raise ValueError("depth frames need intrinsics")
         pyr = depth_pyramid(pyr_or_depth, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max,
                             depth_diff)
     with _region("depth_odometry"):
-        return _odometry(False, pyr, pairs, T_init, iterations, max_distance, return_information)
+        return _odometry(False, pyr, pairs, T_init, iterations, max_distance, None, return_information)
 
 
 def depth_odometry_host(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
@@ -5178,13 +5190,13 @@ def depth_odometry_host(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATI
     """The host twin of ``depth_odometry`` (d3f_depth_odometry_host): CPU tensors, no GPU call.  It sums in raster
     order, so T agrees with the device's to rounding (1e-6), not bit for bit."""
     if isinstance(pyr_or_depth, DepthPyramid):
-        pyr = _odo_host_pyramid(pyr_or_depth, "depth_odometry_host")
+        pyr = _odo_checked_pyramid(pyr_or_depth, "depth_odometry_host", DepthPyramid, True)
     else:
         if intrinsics is None:
             raise ValueError("depth frames need intrinsics")
         pyr = depth_pyramid_host(pyr_or_depth, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max,
                                  depth_diff)
-    return _odometry(True, pyr, pairs, T_init, iterations, max_distance, return_information)
+    return _odometry(True, pyr, pairs, T_init, iterations, max_distance, None, return_information)
 
 
 # ------------------------------------------------------------------------------------------- NumPy restatement
@@ -5323,6 +5335,38 @@ def _odo_pair_ok(pr, t, F):
     return 0 <= pr[0] < F and 0 <= pr[1] < F and bool(np.isfinite(t).all())
 
 
+def _odo_pair_terms(pyr, level, a, b, t, md, normals=None):
+    """(index int32 [H_l,W_l], a f32 [3,m], terms f64 [m,29]) of one association of the pair (a, b), the accepted
+    pixels in raster order.  ``normals``: a cache of ``_odo_normals`` by (fixed frame, level)."""
+    imgs = pyr.level(level)
+    key = (b, level)
+    fixed = normals.get(key) if normals is not None else None
+    if fixed is None:
+        fixed = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
+        if normals is not None:
+            normals[key] = fixed
+    index, av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], fixed, pyr.K[b, level], t, md)
+    return index, av, _odo_terms(av, yv, nv)
+
+
+def _odo_step_numpy(pyr, pr, t, level, n_sums, pair_terms, return_index, return_terms):
+    """The per-pair loop of the ``*_odometry_step_numpy`` functions: ``pair_terms(a, b, t)`` gives the index and the
+    f64 [rows, n_sums] terms of one valid pair."""
+    h, w = int(pyr.table[level, 0]), int(pyr.table[level, 1])
+    sums = np.zeros((pr.shape[0], n_sums))
+    index = np.full((pr.shape[0], h, w), -1, dtype=np.int32)
+    terms = []
+    with np.errstate(all='ignore'):
+        for p in range(pr.shape[0]):
+            terms.append(np.zeros((0, n_sums)))
+            if not _odo_pair_ok(pr[p], t[p], pyr.frames):
+                continue
+            index[p], terms[-1] = pair_terms(int(pr[p, 0]), int(pr[p, 1]), t[p])
+            sums[p] = terms[-1].sum(axis=0)
+    res = (sums,) + ((index,) if return_index else ()) + ((terms,) if return_terms else ())
+    return res if len(res) > 1 else sums
+
+
 def depth_odometry_step_numpy(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, return_index=False,
                               return_terms=False):
     """The contract of ``depth_odometry_step`` in NumPy: ``sums`` f64 [P,29] (NumPy's own summation order: equal to
@@ -5330,27 +5374,13 @@ def depth_odometry_step_numpy(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANC
     which is equal.  ``return_terms=True`` appends the list of the f64 [m_p,29] terms the sums are made of."""
     pyr = _odo_numpy_pyramid(pyr)
     pr, t = _odo_pairs(pairs, T, "depth_odometry_step_numpy")
-    level = int(level)
-    if not 0 <= level < pyr.levels:
-        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
-    imgs = pyr.level(level)
-    h, w = imgs.shape[1:]
-    sums = np.zeros((pr.shape[0], ODO_SUMS))
-    index = np.full((pr.shape[0], h, w), -1, dtype=np.int32)
-    terms = []
-    with np.errstate(all='ignore'):
-        for p in range(pr.shape[0]):
-            terms.append(np.zeros((0, ODO_SUMS)))
-            if not _odo_pair_ok(pr[p], t[p], pyr.frames):
-                continue
-            a, b = int(pr[p, 0]), int(pr[p, 1])
-            fixed = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
-            index[p], av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], fixed, pyr.K[b, level], t[p],
-                                                        _odo_check_distance(max_distance))
-            terms[-1] = _odo_terms(av, yv, nv)
-            sums[p] = terms[-1].sum(axis=0)
-    res = (sums,) + ((index,) if return_index else ()) + ((terms,) if return_terms else ())
-    return res if len(res) > 1 else sums
+    level = _odo_check_level(level, pyr)
+
+    def pair_terms(a, b, tp):
+        index, _, terms = _odo_pair_terms(pyr, level, a, b, tp, _odo_check_distance(max_distance))
+        return index, terms
+
+    return _odo_step_numpy(pyr, pr, t, level, ODO_SUMS, pair_terms, return_index, return_terms)
 
 
 _ODO_PLANE_PIVOT = 1e-10      # kPlanePivot of csrc/plane.hpp
@@ -5383,21 +5413,10 @@ def _odo_plane_step(sums, T12):
     return out.reshape(12), True, False
 
 
-def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
-                         return_information=False, intrinsics=None, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
-                         depth_diff=ODO_DEPTH_DIFF):
-    """The contract of ``depth_odometry`` in NumPy: ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P])``
-    (and the information matrices [P,6,6]); T agrees with the kernel's to rounding, not bit for bit."""
-    it = _odo_iterations(iterations)
-    if isinstance(pyr_or_depth, DepthPyramid):
-        pyr = _odo_numpy_pyramid(pyr_or_depth)
-        _odo_iterations(iterations, pyr.levels)
-    else:
-        if intrinsics is None:
-            raise ValueError("depth frames need intrinsics")
-        pyr = depth_pyramid_numpy(pyr_or_depth, intrinsics, len(it), depth_scale, depth_max, depth_diff)
-    pr, t0 = _odo_pairs(pairs, T_init, "depth_odometry_numpy")
-    md = _odo_check_distance(max_distance)
+def _odo_march_numpy(pyr, pr, t0, it, sums_at, return_information, photo=False):
+    """The coarse-to-fine march of the ``*_odometry_numpy`` functions over P pairs from the poses ``t0`` [P,12]:
+    ``sums_at(p, level, t)`` gives the sums of one association of pair p: 29 of them, or with ``photo`` 31, and
+    ``n_photo`` then ends the result."""
     P = pr.shape[0]
     T = np.zeros((P, 4, 4))
     T[:, 3, 3] = 1.0
@@ -5405,17 +5424,8 @@ def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERAT
     count = np.zeros(P, dtype=np.int32)
     rmse = np.zeros(P)
     status = np.zeros(P, dtype=np.int32)
+    n_photo = np.zeros(P, dtype=np.int32)
     info = np.zeros((P, 6, 6))
-    normals = {}
-
-    def sums_at(p, level, t):
-        a, b = int(pr[p, 0]), int(pr[p, 1])
-        imgs = pyr.level(level)
-        if (b, level) not in normals:
-            normals[(b, level)] = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
-        _, av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], normals[(b, level)], pyr.K[b, level], t, md)
-        return _odo_terms(av, yv, nv).sum(axis=0)
-
     with np.errstate(all='ignore'):
         for p in range(P):
             if not (0 <= pr[p, 0] < pyr.frames and 0 <= pr[p, 1] < pyr.frames):
@@ -5439,15 +5449,37 @@ def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERAT
                 T[p, :3, :] = t.reshape(3, 4)
                 count[p] = int(sums[0])
                 rmse[p] = np.sqrt(sums[28] / sums[0])
+                if photo:
+                    n_photo[p] = int(sums[29])
                 for k, (i, j) in enumerate(_ODO_UPPER):
                     info[p, i, j] = info[p, j, i] = sums[1 + k]
-    res = (T, count, rmse, status)
-    return res + (info,) if return_information else res
+    return (T, count, rmse, status) + ((info,) if return_information else ()) + ((n_photo,) if photo else ())
+
+
+def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
+                         return_information=False, intrinsics=None, depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX,
+                         depth_diff=ODO_DEPTH_DIFF):
+    """The contract of ``depth_odometry`` in NumPy: ``(T f64 [P,4,4], count int32 [P], rmse f64 [P], status int32 [P])``
+    (and the information matrices [P,6,6]); T agrees with the kernel's to rounding, not bit for bit."""
+    it = _odo_iterations(iterations)
+    if isinstance(pyr_or_depth, DepthPyramid):
+        pyr = _odo_numpy_pyramid(pyr_or_depth)
+        _odo_iterations(iterations, pyr.levels)
+    else:
+        if intrinsics is None:
+            raise ValueError("depth frames need intrinsics")
+        pyr = depth_pyramid_numpy(pyr_or_depth, intrinsics, len(it), depth_scale, depth_max, depth_diff)
+    pr, t0 = _odo_pairs(pairs, T_init, "depth_odometry_numpy")
+    md = _odo_check_distance(max_distance)
+    normals = {}
+    sums_at = lambda p, level, t: _odo_pair_terms(pyr, level, int(pr[p, 0]), int(pr[p, 1]), t, md,
+                                                  normals)[2].sum(axis=0)
+    return _odo_march_numpy(pyr, pr, t0, it, sums_at, return_information)
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# RGB-D odometry: the depth odometry with a photometric term (csrc/rgbd_odometry.hpp has the rule;
-# csrc/rgbd_odometry.hip the kernels)
+# RGB-D odometry: the depth odometry with a photometric term (csrc/rgbd_odometry.hpp has the rule; the kernels and
+# the helpers that take ``photo_weight`` are the depth odometry's)
 # ---------------------------------------------------------------------------------------------------------------
 RGBD_SUMS = 31           # the 29 of the depth odometry (both kinds of rows in sum J J^T and sum J r), n_photo, sum r_I^2
 ODO_PHOTO_WEIGHT = 0.3   # profiles/rgbd_odometry_weight_sweep.txt: the largest of the swept weights that meets both
@@ -5538,43 +5570,6 @@ def rgbd_pyramid_host(depth, color, intrinsics, levels=3, depth_scale=1000.0, de
                          depth_diff)
 
 
-def _rgbd_device_pyramid(pyr, what):
-    if not isinstance(pyr, RgbdPyramid) or not isinstance(pyr.data, torch.Tensor) or not pyr.data.is_cuda:
-        raise RuntimeError("%s takes the RgbdPyramid of ops.rgbd_pyramid (on the device); the host twin is %s_host, "
-                           "the NumPy restatement %s_numpy" % (what, what, what))
-    return pyr
-
-
-def _rgbd_host_pyramid(pyr, what):
-    if not isinstance(pyr, RgbdPyramid) or not isinstance(pyr.data, torch.Tensor) or pyr.data.is_cuda:
-        raise RuntimeError("%s takes the RgbdPyramid of ops.rgbd_pyramid_host (CPU tensors)" % what)
-    return pyr
-
-
-def _rgbd_step(host, pyr, pairs, T, level, max_distance, photo_weight, return_index):
-    device = pyr.data.device
-    pr, t = _odo_pairs(pairs, T, "rgbd_odometry_step")
-    level, P = int(level), pr.shape[0]
-    if not 0 <= level < pyr.levels:
-        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
-    w = _rgbd_check_weight(photo_weight)
-    h, wd = int(pyr.table[level, 0]), int(pyr.table[level, 1])
-    sums = torch.zeros((P, RGBD_SUMS), dtype=torch.float64, device=device)
-    index = torch.full((P, h, wd), -1, dtype=torch.int32, device=device) if return_index else None
-    if P:
-        tp, tt = _on(device, pr, t)
-        L = _native.lib()
-        args = (_p(pyr.data), _p(pyr.intensity), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
-                level, _odo_check_distance(max_distance), pyr.depth_diff, w, _p(sums), _p(index))
-        if host:
-            _native.check(L.d3f_rgbd_odometry_step_host(*args), "d3f_rgbd_odometry_step_host")
-        else:
-            nbytes = L.d3f_rgbd_odometry_ws_bytes(P, pyr.H, pyr.W)
-            ws = _ws(nbytes, device)
-            _native.check(L.d3f_rgbd_odometry_step(*(args + (_p(ws), nbytes, _stream()))), "d3f_rgbd_odometry_step")
-    return (sums, index) if return_index else sums
-
-
 def rgbd_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, photo_weight=ODO_PHOTO_WEIGHT,
                        return_index=False):
     """ONE association of P frame pairs at ``level`` under ``T`` with both terms (d3f_rgbd_odometry_step): ``sums`` f64
@@ -5584,46 +5579,17 @@ def rgbd_odometry_step(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, phot
     ``depth_odometry_step``'s.  An accepted pixel has a photometric row when the 2x2 bilinear footprint of its
     unrounded projection and the central differences at it lie inside the fixed image and every intensity read is
     finite.  ``photo_weight=0`` skips the term (n_photo = 0)."""
-    _rgbd_device_pyramid(pyr, "rgbd_odometry_step")
+    _odo_checked_pyramid(pyr, "rgbd_odometry_step", RgbdPyramid, False)
     with _region("rgbd_odometry_step"):
-        return _rgbd_step(False, pyr, pairs, T, level, max_distance, photo_weight, return_index)
+        return _odo_step(False, pyr, pairs, T, level, max_distance, photo_weight, return_index)
 
 
 def rgbd_odometry_step_host(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE, photo_weight=ODO_PHOTO_WEIGHT,
                             return_index=False):
     """The host twin of ``rgbd_odometry_step`` (d3f_rgbd_odometry_step_host): the same rule pixel by pixel in raster
     order, CPU tensors, no GPU call."""
-    return _rgbd_step(True, _rgbd_host_pyramid(pyr, "rgbd_odometry_step_host"), pairs, T, level, max_distance,
-                      photo_weight, return_index)
-
-
-def _rgbd_odometry(host, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information):
-    device = pyr.data.device
-    pr, t = _odo_pairs(pairs, T_init, "rgbd_odometry")
-    it = _odo_iterations(iterations, pyr.levels)
-    w = _rgbd_check_weight(photo_weight)
-    P = pr.shape[0]
-    T = torch.zeros((P, 4, 4), dtype=torch.float64, device=device)
-    count = torch.zeros(P, dtype=torch.int32, device=device)
-    rmse = torch.zeros(P, dtype=torch.float64, device=device)
-    status = torch.zeros(P, dtype=torch.int32, device=device)
-    n_photo = torch.zeros(P, dtype=torch.int32, device=device)
-    info = torch.zeros((P, 6, 6), dtype=torch.float64, device=device) if return_information else None
-    if P:
-        tp, tt = _on(device, pr, t)
-        L = _native.lib()
-        counts = (ctypes.c_int32 * len(it))(*it)
-        args = (_p(pyr.data), _p(pyr.intensity), _p(pyr.K), pyr.frames, pyr.H, pyr.W, pyr.levels, _p(tp), P, _p(tt),
-                ctypes.cast(counts, ctypes.c_void_p), _odo_check_distance(max_distance), pyr.depth_diff, w, _p(T),
-                _p(count), _p(rmse), _p(status), _p(n_photo), _p(info))
-        if host:
-            _native.check(L.d3f_rgbd_odometry_host(*args), "d3f_rgbd_odometry_host")
-        else:
-            nbytes = L.d3f_rgbd_odometry_ws_bytes(P, pyr.H, pyr.W)
-            ws = _ws(nbytes, device)
-            _native.check(L.d3f_rgbd_odometry(*(args + (_p(ws), nbytes, _stream()))), "d3f_rgbd_odometry")
-    res = (T, count, rmse, status)
-    return res + ((info,) if return_information else ()) + (n_photo,)
+    return _odo_step(True, _odo_checked_pyramid(pyr, "rgbd_odometry_step_host", RgbdPyramid, True), pairs, T, level,
+                     max_distance, photo_weight, return_index)
 
 
 def _rgbd_frames(pyr_or_frames, intrinsics):
@@ -5658,12 +5624,12 @@ def rgbd_odometry(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, 
     fixed frame) before ``n_photo``, which is the number of photometric rows of that association.  A pair's result is
     bit-identical alone, in any batch, and from run to run."""
     if isinstance(pyr_or_frames, DepthPyramid):
-        pyr = _rgbd_device_pyramid(pyr_or_frames, "rgbd_odometry")
+        pyr = _odo_checked_pyramid(pyr_or_frames, "rgbd_odometry", RgbdPyramid, False)
     else:
         d, c = _rgbd_frames(pyr_or_frames, intrinsics)
         pyr = rgbd_pyramid(d, c, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max, depth_diff)
     with _region("rgbd_odometry"):
-        return _rgbd_odometry(False, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
+        return _odometry(False, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
 
 
 def rgbd_odometry_host(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
@@ -5672,11 +5638,11 @@ def rgbd_odometry_host(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATI
     """The host twin of ``rgbd_odometry`` (d3f_rgbd_odometry_host): CPU tensors, no GPU call.  It sums in raster
     order, so T agrees with the device's to rounding (1e-6), not bit for bit."""
     if isinstance(pyr_or_frames, DepthPyramid):
-        pyr = _rgbd_host_pyramid(pyr_or_frames, "rgbd_odometry_host")
+        pyr = _odo_checked_pyramid(pyr_or_frames, "rgbd_odometry_host", RgbdPyramid, True)
     else:
         d, c = _rgbd_frames(pyr_or_frames, intrinsics)
         pyr = rgbd_pyramid_host(d, c, intrinsics, len(_odo_iterations(iterations)), depth_scale, depth_max, depth_diff)
-    return _rgbd_odometry(True, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
+    return _odometry(True, pyr, pairs, T_init, iterations, max_distance, photo_weight, return_information)
 
 
 # ------------------------------------------------------------------------------------------- NumPy restatement
@@ -5767,17 +5733,11 @@ def _rgbd_terms(a, q, r, w):
 def _rgbd_pair_terms(pyr, level, a, b, t, md, w, normals=None):
     """(index int32 [H_l,W_l], terms f64 [m + m_photo, 31]) of one association of the pair (a, b): the geometric rows
     (zero in the last two columns), then the photometric rows, each in raster order."""
-    imgs, inten = pyr.level(level), pyr.intensity_level(level)
-    key = (b, level)
-    fixed = normals.get(key) if normals is not None else None
-    if fixed is None:
-        fixed = _odo_normals(imgs[b], pyr.K[b, level], pyr.depth_diff)
-        if normals is not None:
-            normals[key] = fixed
-    index, av, yv, nv = _odo_associate_numpy(imgs[a], pyr.K[a, level], fixed, pyr.K[b, level], t, md)
-    geo = np.concatenate([_odo_terms(av, yv, nv), np.zeros((av.shape[1], 2))], axis=1)
+    index, av, geo = _odo_pair_terms(pyr, level, a, b, t, md, normals)
+    geo = np.concatenate([geo, np.zeros((av.shape[1], 2))], axis=1)
     if w == 0.0:
         return index, geo
+    inten = pyr.intensity_level(level)
     has, r, q = _rgbd_photometric_numpy(index, av, inten[a], inten[b], pyr.K[b, level])
     return index, np.concatenate([geo, _rgbd_terms(av[:, has], q[:, has], r[has], w)], axis=0)
 
@@ -5790,24 +5750,11 @@ def rgbd_odometry_step_numpy(pyr, pairs, T, level, max_distance=ODO_MAX_DISTANCE
     of: the geometric terms, then the photometric ones."""
     pyr = _rgbd_numpy_pyramid(pyr)
     pr, t = _odo_pairs(pairs, T, "rgbd_odometry_step_numpy")
-    level = int(level)
-    if not 0 <= level < pyr.levels:
-        raise ValueError("level must be in 0..%d, got %d" % (pyr.levels - 1, level))
+    level = _odo_check_level(level, pyr)
     w = float(np.float32(_rgbd_check_weight(photo_weight)))
     md = _odo_check_distance(max_distance)
-    h, wd = int(pyr.table[level, 0]), int(pyr.table[level, 1])
-    sums = np.zeros((pr.shape[0], RGBD_SUMS))
-    index = np.full((pr.shape[0], h, wd), -1, dtype=np.int32)
-    terms = []
-    with np.errstate(all='ignore'):
-        for p in range(pr.shape[0]):
-            terms.append(np.zeros((0, RGBD_SUMS)))
-            if not _odo_pair_ok(pr[p], t[p], pyr.frames):
-                continue
-            index[p], terms[-1] = _rgbd_pair_terms(pyr, level, int(pr[p, 0]), int(pr[p, 1]), t[p], md, w)
-            sums[p] = terms[-1].sum(axis=0)
-    res = (sums,) + ((index,) if return_index else ()) + ((terms,) if return_terms else ())
-    return res if len(res) > 1 else sums
+    pair_terms = lambda a, b, tp: _rgbd_pair_terms(pyr, level, a, b, tp, md, w)
+    return _odo_step_numpy(pyr, pr, t, level, RGBD_SUMS, pair_terms, return_index, return_terms)
 
 
 def rgbd_odometry_numpy(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERATIONS, max_distance=ODO_MAX_DISTANCE,
@@ -5825,46 +5772,10 @@ def rgbd_odometry_numpy(pyr_or_frames, pairs, T_init=None, iterations=ODO_ITERAT
     pr, t0 = _odo_pairs(pairs, T_init, "rgbd_odometry_numpy")
     md = _odo_check_distance(max_distance)
     w = float(np.float32(_rgbd_check_weight(photo_weight)))
-    P = pr.shape[0]
-    T = np.zeros((P, 4, 4))
-    T[:, 3, 3] = 1.0
-    T[:, :3, :] = t0.reshape(P, 3, 4)
-    count = np.zeros(P, dtype=np.int32)
-    rmse = np.zeros(P)
-    status = np.zeros(P, dtype=np.int32)
-    n_photo = np.zeros(P, dtype=np.int32)
-    info = np.zeros((P, 6, 6))
     normals = {}
     sums_at = lambda p, level, t: _rgbd_pair_terms(pyr, level, int(pr[p, 0]), int(pr[p, 1]), t, md, w,
                                                    normals)[1].sum(axis=0)
-    with np.errstate(all='ignore'):
-        for p in range(P):
-            if not (0 <= pr[p, 0] < pyr.frames and 0 <= pr[p, 1] < pyr.frames):
-                status[p] |= ODO_ST_PAIR
-            if not np.isfinite(t0[p]).all():
-                status[p] |= ODO_ST_NONFINITE
-            if status[p]:
-                continue
-            t, singular = t0[p].copy(), False
-            for level in range(pyr.levels - 1, -1, -1):
-                for _ in range(it[level]):
-                    t, _moved, s = _odo_plane_step(sums_at(p, level, t), t)
-                    if level == 0:
-                        singular = s
-            sums = sums_at(p, 0, t)
-            if sums[0] < ODO_MIN_PIXELS:
-                status[p] = ODO_ST_FEW
-            elif singular:
-                status[p] = ODO_ST_SINGULAR
-            else:
-                T[p, :3, :] = t.reshape(3, 4)
-                count[p] = int(sums[0])
-                rmse[p] = np.sqrt(sums[28] / sums[0])
-                n_photo[p] = int(sums[29])
-                for k, (i, j) in enumerate(_ODO_UPPER):
-                    info[p, i, j] = info[p, j, i] = sums[1 + k]
-    res = (T, count, rmse, status)
-    return res + ((info,) if return_information else ()) + (n_photo,)
+    return _odo_march_numpy(pyr, pr, t0, it, sums_at, return_information, photo=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------

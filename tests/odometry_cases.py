@@ -1,6 +1,7 @@
 """Inputs shared by the depth-odometry tests: the analytic room of ``tsdf_scene`` (12 frames of 80 x 60 with analytic
 poses), its small images of 37 x 23 (odd dimensions: levels of 18 x 11 and 9 x 5, the 1024-pixel chunk not filled), a
-5 x 5 image whose coarsest level is 1 x 1, and a constant-depth pair whose normal equations are exactly singular."""
+5 x 5 image whose coarsest level is 1 x 1, a constant-depth pair whose normal equations are exactly singular, and two
+views of the room at 272 x 244, whose level 0 has more chunks than a wave has lanes."""
 import functools
 
 import numpy as np
@@ -59,6 +60,31 @@ def constant_pair():
                 levels=LEVELS)
 
 
+WIDE_W, WIDE_H = 272, 244
+WIDE_K = np.array([204.0, 204.0, 135.5, 121.5])
+WIDE_PAIRS = np.array([(1, 0), (0, 1)])
+CHUNK = 1024             # D3F_ODO_CHUNK: the consecutive raster pixels one workgroup sums
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """(depth uint16 [2,244,272], K [4], T_true [2,4,4] of ``WIDE_PAIRS``): the room from its cameras 0 and 1 at
+    272 x 244.  Level 0 has 66368 pixels = 64 chunks of 1024 and one of 832: a pair has more chunks than the 64 lanes
+    that add them, and the last chunk is partly filled.  Shared, do not modify."""
+    poses = [S.camera(0), S.camera(1)]
+    depth = np.stack([S.to_raw(S.render(P, WIDE_W, WIDE_H, WIDE_K)) for P in poses])
+    depth.setflags(write=False)
+    return depth, WIDE_K.copy(), np.stack([relative(poses, a, b) for a, b in WIDE_PAIRS])
+
+
+def chunk_counts(index):
+    """int [P, chunks]: the accepted pixels (index >= 0) of every chunk of ``CHUNK`` raster pixels of an association
+    index [P,H,W]."""
+    ok = np.asarray(index).reshape(len(index), -1) >= 0
+    pad = -ok.shape[1] % CHUNK
+    return np.pad(ok, ((0, 0), (0, pad))).reshape(len(index), -1, CHUNK).sum(axis=2)
+
+
 def step_cases():
     """(name, pyramid arguments, pairs, list of T [P,4,4]) for the association tests: at the identity and at a second
     pose, for every level."""
@@ -69,6 +95,8 @@ def step_cases():
     yield 'room', dict(depth=depth, intrinsics=K, levels=LEVELS), pairs, [np.stack([np.eye(4)] * 2), Tt]
     for name, args in small_inputs().items():
         yield name, args, np.array([(1, 0)]), [np.eye(4)[None], small_pose()[None]]
+    wd, wK, wT = wide()
+    yield 'wide', dict(depth=wd, intrinsics=wK, levels=LEVELS), WIDE_PAIRS, [np.stack([np.eye(4)] * 2), wT]
 
 
 def sum_bound(terms):

@@ -1,7 +1,7 @@
 """Inputs shared by the RGB-D odometry tests: a smooth analytic texture of world coordinates; the room of
 ``tsdf_scene`` painted with it (as f32 intensity and as uint8 RGB); the planar slide -- two 64 x 48 views of the
-fronto-parallel plane z = 1, whose depth-only normal equations are singular -- and the small odd images of
-``odometry_cases``, each with a deterministic intensity."""
+fronto-parallel plane z = 1, whose depth-only normal equations are singular -- the small odd images of
+``odometry_cases``, each with a deterministic intensity, and its two wide views of the room, painted."""
 import functools
 
 import numpy as np
@@ -54,6 +54,16 @@ def room():
     inten.setflags(write=False)
     rgb.setflags(write=False)
     return depth, K, poses, inten, rgb
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """(depth uint16 [2,244,272], K [4], T_true [2,4,4], intensity f32 [2,244,272]): ``odometry_cases.wide`` painted
+    with ``tex``; shared, do not modify."""
+    depth, K, T_true = OC.wide()
+    inten = paint(depth, K, [S.camera(0), S.camera(1)])
+    inten.setflags(write=False)
+    return depth, K, T_true, inten
 
 
 def _rigid(angle_deg, t):
@@ -128,6 +138,9 @@ def step_cases():
     yield 'room', dict(depth=depth, intrinsics=K, levels=LEVELS), inten, pairs, [np.stack([np.eye(4)] * 2), Tt]
     for name, (args, color) in small_inputs().items():
         yield name, args, color, np.array([(1, 0)]), [np.eye(4)[None], OC.small_pose()[None]]
+    wd, wK, wT, wi = wide()
+    yield ('wide', dict(depth=wd, intrinsics=wK, levels=LEVELS), wi, OC.WIDE_PAIRS,
+           [np.stack([np.eye(4)] * 2), wT])
 
 
 # ---------------------------------------------------------------------------------------------------------- checks

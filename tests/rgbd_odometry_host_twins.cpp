@@ -3,8 +3,7 @@
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined d3feat.pytorch_amd/csrc/odometry.hip \
-//         d3feat.pytorch_amd/csrc/rgbd_odometry.hip tests/rgbd_odometry_host_twins.cpp \
-//         -o /tmp/rgbd_odometry_host_twins && /tmp/rgbd_odometry_host_twins
+//         tests/rgbd_odometry_host_twins.cpp -o /tmp/rgbd_odometry_host_twins && /tmp/rgbd_odometry_host_twins
 //
 // It calls d3f_rgbd_pyramid_host (8-bit colour, 8-bit grey and f32), d3f_rgbd_odometry_step_host and
 // d3f_rgbd_odometry_host on small images of odd size (37 x 23: levels of 18 x 11 and 9 x 5) with holes in the depth, a

@@ -113,6 +113,19 @@ def test_step_twin_equals_restatement(case):
     assert accepted > 0
 
 
+def test_wide_case_fills_every_chunk_of_more_than_a_wave_of_chunks():
+    """What the 'wide' case is for: at the identity both pairs have 65 chunks of 1024 raster pixels at level 0 (one
+    more than the 64 lanes that add a pair's chunks, the last one of 832 pixels), and by the restatement's index every
+    chunk holds accepted pixels, so no partial sum is trivially zero."""
+    depth, K, _ = OC.wide()
+    assert depth.shape[1] * depth.shape[2] == 64 * OC.CHUNK + 832
+    _, idx = ops.depth_odometry_step_numpy(ops.depth_pyramid_numpy(depth, K, OC.LEVELS), OC.WIDE_PAIRS, None, 0,
+                                           return_index=True)
+    counts = OC.chunk_counts(idx)
+    print("accepted per pair %s, fewest in a chunk %d" % (counts.sum(axis=1).tolist(), counts.min()))
+    assert counts.shape == (2, 65) and counts.min() >= 1
+
+
 def test_step_index_names_a_pixel_with_a_normal(room):
     """The index is a raster index of the fixed image, interior (a normal needs four neighbours), and the identity
     associates a static interior pixel of frame 0 with itself."""

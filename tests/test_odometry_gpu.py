@@ -1,7 +1,7 @@
 """GPU: the depth-odometry kernels (csrc/odometry.hip) against their host twins -- the pyramid bit for bit, the
 association index for index and its sums within the summation bound, the poses to 1e-6 -- a pair alone against the same
 pair in a batch, in a reversed batch and from run to run bit for bit, the statuses, and ``track_sequence`` into
-``fuse_fragments`` on the device.  Images of 80 x 60 and smaller."""
+``fuse_fragments`` on the device.  Images of 80 x 60 and smaller, and two of 272 x 244 (65 chunks)."""
 import numpy as np
 import pytest
 import torch
@@ -80,9 +80,7 @@ def test_step_equals_host_twin(case):
             assert same_f64(ops.depth_odometry_step(pd, pairs, T, level), sd)     # without the index: the same sums
 
 
-def test_a_pair_alone_in_a_batch_reversed_and_again(room, room_batch):
-    pd, _ = room
-    pairs, batch = room_batch
+def check_alone_in_a_batch_reversed_and_again(pd, pairs, batch):
     again = [arr(t) for t in ops.depth_odometry(pd, pairs)]
     back = [arr(t)[::-1] for t in ops.depth_odometry(pd, pairs[::-1].copy())]
     for other in (again, back):
@@ -92,7 +90,19 @@ def test_a_pair_alone_in_a_batch_reversed_and_again(room, room_batch):
         alone = [arr(t) for t in ops.depth_odometry(pd, pairs[p:p + 1])]
         assert same_f64(alone[0][0], batch[0][p]) and same_f64(alone[2], batch[2][p:p + 1])
         assert alone[1][0] == batch[1][p] and alone[3][0] == batch[3][p] == 0
+
+
+def test_a_pair_alone_in_a_batch_reversed_and_again(room, room_batch):
+    pd, _ = room
+    pairs, batch = room_batch
+    check_alone_in_a_batch_reversed_and_again(pd, pairs, batch)
     assert batch[1].min() > 3500
+    # the wide views: 65 chunks per pair at level 0, one more than the lanes of the wave that adds them
+    depth, K, _ = OC.wide()
+    wide = ops.depth_pyramid(depth, K, OC.LEVELS)
+    batch = [arr(t) for t in ops.depth_odometry(wide, OC.WIDE_PAIRS)]
+    check_alone_in_a_batch_reversed_and_again(wide, OC.WIDE_PAIRS, batch)
+    assert batch[1].min() > 55000
 
 
 def test_odometry_equals_host_twin(room, room_batch):

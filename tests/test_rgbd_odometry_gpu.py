@@ -1,8 +1,8 @@
-"""GPU: the RGB-D odometry kernels (csrc/rgbd_odometry.hip) -- the planar slide and the textured room on the device;
+"""GPU: the RGB-D odometry kernels (csrc/odometry.hip) -- the planar slide and the textured room on the device;
 the intensity pyramid against the host twin and the restatement bit for bit; the association step against both within
 the summation bound; ``photo_weight=0`` against ``ops.depth_odometry`` bit for bit; a pair alone against the same pair
 in a batch, in a reversed batch and from run to run bit for bit; the information matrix; ``track_sequence(color=)`` on
-the device against ``device='cpu'``.  Images of 80 x 60 and smaller."""
+the device against ``device='cpu'``.  Images of 80 x 60 and smaller, and two of 272 x 244 (65 chunks)."""
 import numpy as np
 import pytest
 import torch
@@ -104,8 +104,7 @@ def test_weight_zero_is_the_depth_tracker_bit_for_bit(room):
     assert status.tolist() == [ops.ODO_ST_SINGULAR] * 2
 
 
-def test_a_pair_alone_in_a_batch_reversed_and_again_is_bit_identical(room):
-    pyr, pairs, batch = room
+def check_alone_in_a_batch_reversed_and_again(pyr, pairs, batch, alone_pairs):
     again = [arr(t) for t in ops.rgbd_odometry(pyr, pairs, return_information=True)]
     back = [arr(t)[::-1] for t in ops.rgbd_odometry(pyr, pairs[::-1].copy(), return_information=True)]
     for a, b, c in zip(batch, again, back):
@@ -113,13 +112,27 @@ def test_a_pair_alone_in_a_batch_reversed_and_again_is_bit_identical(room):
             assert RC.same_bits(a, b, np.float64) and RC.same_bits(a, c, np.float64)
         else:
             assert np.array_equal(a, b) and np.array_equal(a, c)
-    for p in (0, 4, 10):
+    for p in alone_pairs:
         alone = [arr(t)[0] for t in ops.rgbd_odometry(pyr, pairs[p:p + 1], return_information=True)]
         for a, b in zip(alone, batch):
             assert RC.same_bits(a, b[p], np.float64) if b.dtype == np.float64 else a == b[p]
+
+
+def test_a_pair_alone_in_a_batch_reversed_and_again_is_bit_identical(room):
+    pyr, pairs, batch = room
+    check_alone_in_a_batch_reversed_and_again(pyr, pairs, batch, (0, 4, 10))
     s_all = arr(ops.rgbd_odometry_step(pyr, pairs, batch[0], 0))
     s_one = arr(ops.rgbd_odometry_step(pyr, pairs[3:4], batch[0][3:4], 0))
     assert RC.same_bits(s_all[3], s_one[0], np.float64)
+    # the wide views: 65 chunks per pair at level 0, one more than the lanes of the wave that adds them
+    depth, K, _, inten = RC.wide()
+    wide = ops.rgbd_pyramid(depth, inten, K, RC.LEVELS)
+    batch = [arr(t) for t in ops.rgbd_odometry(wide, OC.WIDE_PAIRS, return_information=True)]
+    check_alone_in_a_batch_reversed_and_again(wide, OC.WIDE_PAIRS, batch, (0, 1))
+    assert not batch[3].any() and batch[1].min() > 55000 and batch[5].min() > 55000
+    s_all = arr(ops.rgbd_odometry_step(wide, OC.WIDE_PAIRS, batch[0], 0))
+    s_one = arr(ops.rgbd_odometry_step(wide, OC.WIDE_PAIRS[1:], batch[0][1:], 0))
+    assert RC.same_bits(s_all[1], s_one[0], np.float64)
 
 
 def test_information_is_the_combined_sum_and_has_full_rank_on_the_slide():
