@@ -14,7 +14,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip"]
+           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip", "tsdf_color.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -41,6 +41,19 @@ class AugmentJob(C.Structure):
                 ("t", C.c_double * 3), ("key", C.c_uint64), ("out_src", _vp), ("out_tgt", _vp), ("out_corr", _vp),
                 ("out_dist", _vp)]
 
+
+# the colour entry points (csrc/tsdf_color.hpp): a form and its host twin share one argument list
+_i64 = C.c_int64
+_TSDF_COLOR_INTEGRATE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
+                         _vp, _vp, _vp, _vp]
+_TSDF_COLOR_SPARSE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _vp,
+                      _vp, _vp]
+_TSDF_COLOR_RAYCAST = [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i,
+                       _vp, _vp, _vp, _vp]
+_TSDF_COLOR_RAYCAST_SPARSE = [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _i, _i, _vp,
+                              _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp]
+_TSDF_COLOR_SAMPLE = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _f, _vp, _vp]
+_TSDF_COLOR_SAMPLE_SPARSE = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _f, _vp, _vp]
 
 # name -> (restype, argtypes); mirrors include/d3feat_hip.h one to one
 SIGNATURES = {
@@ -259,6 +272,22 @@ SIGNATURES = {
                                   C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
                                        C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_tsdf_integrate_color": (_i, _TSDF_COLOR_INTEGRATE),
+    "d3f_tsdf_integrate_color_host": (_i, _TSDF_COLOR_INTEGRATE),
+    "d3f_tsdf_integrate_color_into": (_i, _TSDF_COLOR_INTEGRATE),
+    "d3f_tsdf_integrate_color_into_host": (_i, _TSDF_COLOR_INTEGRATE),
+    "d3f_tsdf_sparse_integrate_color": (_i, _TSDF_COLOR_SPARSE + [_vp]),
+    "d3f_tsdf_sparse_integrate_color_host": (_i, _TSDF_COLOR_SPARSE),
+    "d3f_tsdf_sparse_integrate_color_into": (_i, _TSDF_COLOR_SPARSE + [_vp]),
+    "d3f_tsdf_sparse_integrate_color_into_host": (_i, _TSDF_COLOR_SPARSE),
+    "d3f_tsdf_raycast_color": (_i, _TSDF_COLOR_RAYCAST),
+    "d3f_tsdf_raycast_color_host": (_i, _TSDF_COLOR_RAYCAST),
+    "d3f_tsdf_raycast_sparse_color": (_i, _TSDF_COLOR_RAYCAST_SPARSE),
+    "d3f_tsdf_raycast_sparse_color_host": (_i, _TSDF_COLOR_RAYCAST_SPARSE),
+    "d3f_tsdf_sample_color": (_i, _TSDF_COLOR_SAMPLE),
+    "d3f_tsdf_sample_color_host": (_i, _TSDF_COLOR_SAMPLE),
+    "d3f_tsdf_sample_color_sparse": (_i, _TSDF_COLOR_SAMPLE_SPARSE),
+    "d3f_tsdf_sample_color_sparse_host": (_i, _TSDF_COLOR_SAMPLE_SPARSE),
     "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
     "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),

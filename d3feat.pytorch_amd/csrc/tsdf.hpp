@@ -47,22 +47,34 @@ D3F_HD inline float depth_value(const float* image, size_t i, float) { return im
 
 D3F_HD inline float lattice(float origin, float voxel, int i) { return origin + voxel * (float)i; }
 
+// what one frame observes at one voxel: false when the frame skips it; else t, and (uf, vf), the voxel's projection
+// whose rounding names the depth pixel that was read (tsdf_color.hpp reads the colour there)
+template <typename DepthT>
+D3F_HD inline bool observe_frame(float x, float y, float z, const float* M, const float* K, const DepthT* image, int H,
+                                 int W, float depth_scale, float depth_max, float trunc, float& t, float& uf, float& vf) {
+  const float px = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
+  const float py = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
+  const float pz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+  if (!(pz > 0.0f)) return false;
+  uf = (K[0] * px) / pz + K[2];
+  vf = (K[1] * py) / pz + K[3];
+  const float u = floorf(uf + 0.5f);
+  const float v = floorf(vf + 0.5f);
+  if (!(u >= 0.0f && u < (float)W && v >= 0.0f && v < (float)H)) return false;
+  const float d = depth_value(image, (size_t)(int)v * (size_t)W + (size_t)(int)u, depth_scale);
+  if (!(d > 0.0f) || d > depth_max) return false;
+  const float sdf = d - pz;
+  if (sdf < -trunc) return false;
+  t = fminf(1.0f, sdf / trunc);
+  return true;
+}
+
 // one frame into one voxel
 template <typename DepthT>
 D3F_HD inline void integrate_frame(float x, float y, float z, const float* M, const float* K, const DepthT* image,
                                    int H, int W, float depth_scale, float depth_max, float trunc, float& D, float& w) {
-  const float px = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-  const float py = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-  const float pz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
-  if (!(pz > 0.0f)) return;
-  const float u = floorf(((K[0] * px) / pz + K[2]) + 0.5f);
-  const float v = floorf(((K[1] * py) / pz + K[3]) + 0.5f);
-  if (!(u >= 0.0f && u < (float)W && v >= 0.0f && v < (float)H)) return;
-  const float d = depth_value(image, (size_t)(int)v * (size_t)W + (size_t)(int)u, depth_scale);
-  if (!(d > 0.0f) || d > depth_max) return;
-  const float sdf = d - pz;
-  if (sdf < -trunc) return;
-  const float t = fminf(1.0f, sdf / trunc);
+  float t, uf, vf;
+  if (!observe_frame(x, y, z, M, K, image, H, W, depth_scale, depth_max, trunc, t, uf, vf)) return;
   D = (D * w + t) / (w + 1.0f);
   w = w + 1.0f;
 }

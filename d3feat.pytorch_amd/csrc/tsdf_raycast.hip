@@ -7,7 +7,7 @@
 //   the rule keeps it to the stretch of the ray that crosses the lattice.  Every pixel is written once, by its thread.
 // The host twin runs the same tsdf_raycast.hpp text on the CPU and makes no GPU call.
 #include "tsdf_batch.hpp"
-#include "tsdf_raycast.hpp"
+#include "tsdf_color.hpp"     // includes tsdf_raycast.hpp; the colour behind a hit
 
 namespace {
 
@@ -83,6 +83,41 @@ __global__ void __launch_bounds__(kThreads) raycast_kernel(Volumes b, Views vw, 
   cast_pixel(b, vw, D, w, r, u, v, depth, normals);
 }
 
+// cast_pixel, and behind it the colour of the hit (tsdf_color.hpp): Cv [total, kCc] beside D and w, colour [R, H, W, kCc]
+template <int kCc>
+__host__ __device__ inline void cast_pixel_color(const Volumes& b, const Views& vw, const float* D, const float* w,
+                                                 const float* Cv, int r, int u, int v, float* depth, float* normals,
+                                                 float* colour) {
+  cast_pixel(b, vw, D, w, r, u, v, depth, normals);
+  const size_t at = ((size_t)r * (size_t)vw.H + (size_t)v) * (size_t)vw.W + (size_t)u;
+  rc::Lattice L;
+  int vol;
+  float c[kCc];
+  if (view_lattice(b, vw, D, w, r, L, vol))
+    rc::hit_color<kCc>(L, Cv + b.vol_start[vol] * kCc, vw.K + 4 * (size_t)r, vw.C + 12 * (size_t)r, u, v, depth[at],
+                       vw.min_weight, c);
+  else
+    rc::color_none<kCc>(c);
+#pragma unroll
+  for (int ch = 0; ch < kCc; ++ch) colour[at * kCc + ch] = c[ch];
+}
+
+template <int kCc>
+__global__ void __launch_bounds__(kThreads) raycast_color_kernel(Volumes b, Views vw, const float* __restrict__ D,
+                                                                 const float* __restrict__ w,
+                                                                 const float* __restrict__ Cv, int blocks_x,
+                                                                 float* __restrict__ depth,
+                                                                 float* __restrict__ normals,
+                                                                 float* __restrict__ colour) {
+  const int r = (int)blockIdx.y;
+  const int lane = d3f::lane_id(), wave = (int)threadIdx.x / D3F_WAVE;
+  const int bx = (int)blockIdx.x % blocks_x, by = (int)blockIdx.x / blocks_x;
+  const int u = bx * kBlockEdge + (wave % kBlockTiles) * kTile + (lane % kTile);
+  const int v = by * kBlockEdge + (wave / kBlockTiles) * kTile + (lane / kTile);
+  if (u >= vw.W || v >= vw.H) return;
+  cast_pixel_color<kCc>(b, vw, D, w, Cv, r, u, v, depth, normals, colour);
+}
+
 bool args_ok(const float* D, const float* w, const int64_t* vol_start, const float* origin, const int32_t* dims,
              const float* voxel, int V, int64_t total_voxels, const int32_t* view_volume, int R, int H, int W,
              const float* intrinsics, const float* camera_to_volume, const float* step, float depth_min,
@@ -133,6 +168,57 @@ int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_sta
   for (int r = 0; r < R; ++r)
     for (int v = 0; v < H; ++v)
       for (int u = 0; u < W; ++u) cast_pixel(b, vw, D, w, r, u, v, depth, normals);
+  return D3F_OK;
+}
+
+int d3f_tsdf_raycast_color(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                           const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                           float min_weight, int clip, float* depth, float* normals, float* color, void* stream) {
+  if (!args_ok(D, w, vol_start, origin, dims, voxel, V, total_voxels, view_volume, R, H, W, intrinsics,
+               camera_to_volume, step, depth_min, depth_max, depth) ||
+      (channels != 1 && channels != 3))
+    return D3F_EINVAL;
+  if (R == 0) return D3F_OK;
+  const int blocks_x = d3f::cdiv(W, kBlockEdge), blocks_y = d3f::cdiv(H, kBlockEdge);
+  if ((int64_t)blocks_x * blocks_y > 0x7fffffff || !color || (total_voxels > 0 && !Cv)) return D3F_EINVAL;
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip};
+  const dim3 grid((unsigned)(blocks_x * blocks_y), (unsigned)R);
+  if (channels == 1)
+    raycast_color_kernel<1><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, vw, D, w, Cv, blocks_x, depth, normals,
+                                                                        color);
+  else
+    raycast_color_kernel<3><<<grid, kThreads, 0, (hipStream_t)stream>>>(b, vw, D, w, Cv, blocks_x, depth, normals,
+                                                                        color);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_tsdf_raycast_color_host(const float* D, const float* w, const float* Cv, int channels,
+                                const int64_t* vol_start, const float* origin, const int32_t* dims, const float* voxel,
+                                int V, int64_t total_voxels, const int32_t* view_volume, int R, int H, int W,
+                                const float* intrinsics, const float* camera_to_volume, const float* step,
+                                float depth_min, float depth_max, float min_weight, int clip, float* depth,
+                                float* normals, float* color, void* stream) {
+  (void)stream;
+  if (!args_ok(D, w, vol_start, origin, dims, voxel, V, total_voxels, view_volume, R, H, W, intrinsics,
+               camera_to_volume, step, depth_min, depth_max, depth) ||
+      (channels != 1 && channels != 3) || !host_layout_ok(vol_start, dims, V, total_voxels))
+    return D3F_EINVAL;
+  if (R == 0) return D3F_OK;
+  if (!color || (total_voxels > 0 && !Cv)) return D3F_EINVAL;
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip};
+  for (int r = 0; r < R; ++r)
+    for (int v = 0; v < H; ++v)
+      for (int u = 0; u < W; ++u) {
+        if (channels == 1)
+          cast_pixel_color<1>(b, vw, D, w, Cv, r, u, v, depth, normals, color);
+        else
+          cast_pixel_color<3>(b, vw, D, w, Cv, r, u, v, depth, normals, color);
+      }
   return D3F_OK;
 }
 

@@ -9,7 +9,7 @@
 //   the samples that stay inside it are skipped.  No LDS, no atomics, nothing read back; every pixel is written once.
 // The host twin runs the same text on the CPU and makes no GPU call.
 #include "tsdf_batch.hpp"
-#include "tsdf_raycast_sparse.hpp"
+#include "tsdf_color.hpp"     // includes tsdf_raycast_sparse.hpp; the colour behind a hit
 
 namespace {
 
@@ -92,6 +92,42 @@ __global__ void __launch_bounds__(kThreads) raycast_sparse_kernel(Bricks k, View
   cast_pixel(k, vw, D, w, r, u, v, depth, normals);
 }
 
+// cast_pixel, and behind it the colour of the hit (tsdf_color.hpp): Cp [B, 512, kCc] beside the pool, colour
+// [R, H, W, kCc]
+template <int kCc>
+__host__ __device__ inline void cast_pixel_color(const Bricks& k, const Views& vw, const float* D, const float* w,
+                                                 const float* Cp, int r, int u, int v, float* depth, float* normals,
+                                                 float* colour) {
+  cast_pixel(k, vw, D, w, r, u, v, depth, normals);
+  const size_t at = ((size_t)r * (size_t)vw.H + (size_t)v) * (size_t)vw.W + (size_t)u;
+  rc::SparseLattice L;
+  int vol;
+  float c[kCc];
+  if (view_lattice(k, vw, D, w, r, L, vol))
+    rc::hit_color<kCc>(L, Cp, vw.K + 4 * (size_t)r, vw.C + 12 * (size_t)r, u, v, depth[at], vw.min_weight, c);
+  else
+    rc::color_none<kCc>(c);
+#pragma unroll
+  for (int ch = 0; ch < kCc; ++ch) colour[at * kCc + ch] = c[ch];
+}
+
+template <int kCc>
+__global__ void __launch_bounds__(kThreads) raycast_sparse_color_kernel(Bricks k, Views vw,
+                                                                        const float* __restrict__ D,
+                                                                        const float* __restrict__ w,
+                                                                        const float* __restrict__ Cp, int blocks_x,
+                                                                        float* __restrict__ depth,
+                                                                        float* __restrict__ normals,
+                                                                        float* __restrict__ colour) {
+  const int r = (int)blockIdx.y;
+  const int lane = d3f::lane_id(), wave = (int)threadIdx.x / D3F_WAVE;
+  const int bx = (int)blockIdx.x % blocks_x, by = (int)blockIdx.x / blocks_x;
+  const int u = bx * kBlockEdge + (wave % kBlockTiles) * kTile + (lane % kTile);
+  const int v = by * kBlockEdge + (wave / kBlockTiles) * kTile + (lane / kTile);
+  if (u >= vw.W || v >= vw.H) return;
+  cast_pixel_color<kCc>(k, vw, D, w, Cp, r, u, v, depth, normals, colour);
+}
+
 bool args_ok(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
              const int32_t* brick_index, const float* origin, const int32_t* dims, const float* voxel, int V,
              int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H, int W,
@@ -160,6 +196,64 @@ int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* 
   for (int r = 0; r < R; ++r)
     for (int v = 0; v < H; ++v)
       for (int u = 0; u < W; ++u) cast_pixel(k, vw, D, w, r, u, v, depth, normals);
+  return D3F_OK;
+}
+
+int d3f_tsdf_raycast_sparse_color(const float* D, const float* w, const float* Cp, int channels,
+                                  const int64_t* lattice_start, const int64_t* brick_start,
+                                  const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                  const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                                  float min_weight, int clip, int skip, float* depth, float* normals, float* color,
+                                  void* stream) {
+  if (!args_ok(D, w, lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks,
+               view_volume, R, H, W, intrinsics, camera_to_volume, step, depth_min, depth_max, depth) ||
+      (channels != 1 && channels != 3))
+    return D3F_EINVAL;
+  if (R == 0) return D3F_OK;
+  const int blocks_x = d3f::cdiv(W, kBlockEdge), blocks_y = d3f::cdiv(H, kBlockEdge);
+  if ((int64_t)blocks_x * blocks_y > 0x7fffffff || !color || (bricks > 0 && !Cp)) return D3F_EINVAL;
+  const Bricks k = {lattice_start, brick_start, brick_index, nullptr, origin, dims, voxel, V, lattice_bricks, bricks};
+  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
+                    skip};
+  const dim3 grid((unsigned)(blocks_x * blocks_y), (unsigned)R);
+  if (channels == 1)
+    raycast_sparse_color_kernel<1><<<grid, kThreads, 0, (hipStream_t)stream>>>(k, vw, D, w, Cp, blocks_x, depth,
+                                                                               normals, color);
+  else
+    raycast_sparse_color_kernel<3><<<grid, kThreads, 0, (hipStream_t)stream>>>(k, vw, D, w, Cp, blocks_x, depth,
+                                                                               normals, color);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_tsdf_raycast_sparse_color_host(const float* D, const float* w, const float* Cp, int channels,
+                                       const int64_t* lattice_start, const int64_t* brick_start,
+                                       const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                       const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                                       const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                                       const float* camera_to_volume, const float* step, float depth_min,
+                                       float depth_max, float min_weight, int clip, int skip, float* depth,
+                                       float* normals, float* color, void* stream) {
+  (void)stream;
+  if (!args_ok(D, w, lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks,
+               view_volume, R, H, W, intrinsics, camera_to_volume, step, depth_min, depth_max, depth) ||
+      (channels != 1 && channels != 3) || !host_tables_ok(lattice_start, brick_start, dims, V, lattice_bricks, bricks))
+    return D3F_EINVAL;
+  if (R == 0) return D3F_OK;
+  if (!color || (bricks > 0 && !Cp)) return D3F_EINVAL;
+  const Bricks k = {lattice_start, brick_start, brick_index, nullptr, origin, dims, voxel, V, lattice_bricks, bricks};
+  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
+                    skip};
+  for (int r = 0; r < R; ++r)
+    for (int v = 0; v < H; ++v)
+      for (int u = 0; u < W; ++u) {
+        if (channels == 1)
+          cast_pixel_color<1>(k, vw, D, w, Cp, r, u, v, depth, normals, color);
+        else
+          cast_pixel_color<3>(k, vw, D, w, Cp, r, u, v, depth, normals, color);
+      }
   return D3F_OK;
 }
 

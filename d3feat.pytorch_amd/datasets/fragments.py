@@ -12,7 +12,9 @@ each volume with its vertex normals (``ops.tsdf_mesh``; csrc/tsdf_mesh.hpp has t
 only for the bricks of 8 x 8 x 8 voxels near a surface (``ops.tsdf_allocate`` / ``tsdf_integrate_sparse`` /
 ``tsdf_extract_sparse``; csrc/tsdf_sparse.hpp has the rule): the same points, in the sparse order, from a fraction of
 the memory; ``mesh_fragments`` / ``mesh_scene`` give their meshes straight from the pools (``ops.tsdf_mesh_sparse``;
-csrc/tsdf_mesh_sparse.hpp has the rule).  Colour is not part of this.
+csrc/tsdf_mesh_sparse.hpp has the rule).  ``color=`` fuses the colour images beside D and w (csrc/tsdf_color.hpp has
+the rule: one weight, ``c = (c w + c_pixel) / (w + 1)`` on the frames that update D) and returns the colour of every
+point and mesh vertex, sampled from the colour volume (``ops.tsdf_sample_color``).
 
 ``track_sequence`` gives the camera poses of a sequence that comes without them: frame-to-frame depth odometry
 (``ops.depth_odometry``; csrc/odometry.hpp has the rule), all frame pairs of a chunk in one launch sequence; with
@@ -20,7 +22,9 @@ csrc/tsdf_mesh_sparse.hpp has the rule).  Colour is not part of this.
 csrc/tsdf_raycast.hpp has the rule), which ``sparse=True`` keeps in bricks (``ops.tsdf_raycast_sparse`` / ``tsdf_extend``;
 csrc/tsdf_raycast_sparse.hpp).  With ``color=`` the frame-to-frame pass is the RGB-D odometry (``ops.rgbd_odometry``;
 csrc/rgbd_odometry.hpp), which also tracks views of a single plane; ``read_sequence(color=True)`` reads the colour
-images.  ``render_views`` ray-casts volumes, dense or sparse, from 4x4 poses.
+images, and with ``color=`` and ``model=`` together the model carries one intensity channel, every step renders depth
+and intensity, and the model pass is RGB-D too.  ``render_views`` ray-casts volumes, dense or sparse, from 4x4 poses,
+with ``color=`` their colour as well.
 """
 import os
 import re
@@ -28,7 +32,8 @@ from os.path import exists, join
 
 import numpy as np
 
-DEFAULT_MAX_BYTES = 1 << 33      # D and w of the volumes integrated in one launch (8 bytes per voxel)
+DEFAULT_MAX_BYTES = 1 << 33      # D and w of the volumes integrated in one launch (8 bytes per voxel, 4 more per
+                                 # colour channel)
 DEFAULT_DEPTH_MAX = 6.0          # metres (ops.TSDF_DEPTH_MAX)
 
 
@@ -82,9 +87,9 @@ def _check_sparse(sparse, mesh):
                          "them (ops.tsdf_mesh_sparse)")
 
 
-def _check_fits(dims, voxel, max_bytes, what):
+def _check_fits(dims, voxel, max_bytes, what, voxel_bytes=8):
     for v, n in enumerate(dims):
-        nbytes = 8 * int(n[0]) * int(n[1]) * int(n[2])
+        nbytes = int(voxel_bytes) * int(n[0]) * int(n[1]) * int(n[2])
         if nbytes > max_bytes:
             raise ValueError("%s %d: a volume of %d x %d x %d voxels of %g m (extent %.2f x %.2f x %.2f m) takes %d "
                              "bytes, more than max_bytes = %d: raise max_bytes or the voxel size"
@@ -115,22 +120,28 @@ def _size_batches(sizes, max_bytes):
         v = e
 
 
-def _split_meshes(m, count):
-    """The per-volume (vertices, normals, faces) of a stacked mesh ``m`` of ``count`` volumes."""
+def _split_meshes(m, count, colors=None):
+    """The per-volume (vertices, normals, faces) of a stacked mesh ``m`` of ``count`` volumes; with the stacked vertex
+    ``colors`` a fourth entry, the volume's vertex colours."""
     vert, norm, face, vstart, fstart = m
-    return [(np.ascontiguousarray(vert[vstart[k]:vstart[k + 1]]), np.ascontiguousarray(norm[vstart[k]:vstart[k + 1]]),
-             np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])) for k in range(count)]
+    parts = (vert, norm) if colors is None else (vert, norm, colors)
+    out = []
+    for k in range(count):
+        rows = [np.ascontiguousarray(a[vstart[k]:vstart[k + 1]]) for a in parts]
+        out.append(tuple(rows[:2] + [np.ascontiguousarray(face[fstart[k]:fstart[k + 1]])] + rows[2:]))
+    return out
 
 
 def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight, cpu,
-                 max_bytes, what, mesh=False):
+                 max_bytes, what, mesh=False, color=None):
     """``_fuse`` on sparse volumes: the bricks of every volume first (in the frame groups of the bounds), so that a
     volume whose pool and tables exceed ``max_bytes`` raises before any integration; then batches by the sparse
     sizes.  ``mesh``: also the meshes of the same pools (``ops.tsdf_mesh_sparse``), as ``_fuse`` returns them."""
     from .. import ops
     V = frame_start.size - 1
     allocate = ops.tsdf_allocate_numpy if cpu else ops.tsdf_allocate
-    frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
+    Cc = 0 if color is None else color.shape[-1]
+    frame_bytes = (int(depth[0].nbytes) + (int(color[0].nbytes) if Cc else 0)) if depth.shape[0] else 0
 
     def tables(v, e):
         lo, hi = int(frame_start[v]), int(frame_start[e])
@@ -140,48 +151,58 @@ def _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_
     for v, e in _frame_groups(frame_start, frame_bytes, max_bytes):
         sv = kept[(v, e)] = tables(v, e)                  # the tables are small: kept for a batch of the same volumes
         for k in range(v, e):
-            sizes[k] = ops.tsdf_sparse_bytes(sv, k - v)
+            sizes[k] = ops.tsdf_sparse_bytes(sv, k - v, Cc)
             if sizes[k] > max_bytes:
                 n, start = dims[k], ops._host_array(sv.brick_start)
                 raise ValueError("%s %d: the %d allocated bricks (of %d) of a volume of %d x %d x %d voxels of %g m "
                                  "take %d bytes, more than max_bytes = %d: raise max_bytes or the voxel size"
                                  % (what, k, start[k - v + 1] - start[k - v], np.diff(sv.lattice_start)[k - v], n[0],
                                     n[1], n[2], voxel, sizes[k], max_bytes))
-    clouds, meshes = [], []
+    clouds, meshes, colors = [], [], []
+    host = ops._host_array
     for v, e in _size_batches(sizes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
         frames = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi])
         sv = kept.pop((v, e), None) or tables(v, e)
-        if cpu:
-            D, w = ops.tsdf_sparse_numpy(*frames, sv, trunc, depth_scale, depth_max)
-            pts, ps = ops.tsdf_extract_sparse_numpy(D, w, sv, min_weight)
-            m = ops.tsdf_mesh_sparse_numpy(D, w, sv, min_weight) if mesh else None
-        else:
-            D, w = ops.tsdf_integrate_sparse(*frames, sv, trunc, depth_scale, depth_max)
-            pts, ps = ops.tsdf_extract_sparse(D, w, sv, min_weight)
-            pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
-            m = [t.cpu().numpy() for t in ops.tsdf_mesh_sparse(D, w, sv, min_weight)] if mesh else None
-            del D, w
+        paint = dict(color=color[lo:hi]) if Cc else {}
+        integrate, extract, mesher, sample = (
+            (ops.tsdf_sparse_numpy, ops.tsdf_extract_sparse_numpy, ops.tsdf_mesh_sparse_numpy,
+             ops.tsdf_sample_color_sparse_numpy) if cpu else
+            (ops.tsdf_integrate_sparse, ops.tsdf_extract_sparse, ops.tsdf_mesh_sparse, ops.tsdf_sample_color_sparse))
+        pool = integrate(*frames, sv, trunc, depth_scale, depth_max, **paint)
+        D, w = pool[:2]
+        pts, ps = extract(D, w, sv, min_weight)
+        m = mesher(D, w, sv, min_weight) if mesh else None
+        cols = host(sample(pool[2], w, sv, pts, ps, min_weight)) if Cc else None
+        vcols = host(sample(pool[2], w, sv, m[0], m[3], min_weight)) if Cc and mesh else None
+        pts, ps = host(pts), host(ps)
+        m = [host(t) for t in m] if mesh else None
+        del D, w, pool
         clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
+        if Cc:
+            colors.extend(np.ascontiguousarray(cols[ps[k]:ps[k + 1]]) for k in range(e - v))
         if mesh:
-            meshes.extend(_split_meshes(m, e - v))
-    return (clouds, meshes) if mesh else clouds
+            meshes.extend(_split_meshes(m, e - v, vcols))
+    return (clouds,) + ((meshes,) if mesh else ()) + ((colors,) if Cc else ())
 
 
 def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min_weight, device, max_bytes, what,
-          mesh=False, sparse=False):
-    """Clouds (list of f32 [N,3]) of the volumes that own the frame ranges ``frame_start`` of (depth, K, M, C); with
-    ``mesh`` also their meshes, a list of (vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3]), from the same
-    integrated volumes; with ``sparse`` from sparse volumes (``_fuse_sparse``)."""
+          mesh=False, sparse=False, color=None):
+    """A tuple ``(clouds[, meshes][, colors])``: the clouds (list of f32 [N,3]) of the volumes that own the frame ranges
+    ``frame_start`` of (depth, K, M, C); with ``mesh`` also their meshes, a list of (vertices f32 [Nv,3], normals f32
+    [Nv,3], faces int32 [Nf,3]), from the same integrated volumes; with ``sparse`` from sparse volumes
+    (``_fuse_sparse``).  ``color`` f32 [F,H,W,Cc] (``ops.tsdf_color_frames``): the colour is fused beside D and w, every
+    mesh gains its vertex colours f32 [Nv,Cc] as a fourth entry and ``colors`` lists the clouds' colours f32 [N,Cc]."""
     from .. import ops
     cpu = _is_cpu(device)
     frame_start = np.asarray(frame_start, dtype=np.int64)
     V = frame_start.size - 1
+    Cc = 0 if color is None else color.shape[-1]
     if V == 0:
-        return ([], []) if mesh else []
+        return ([],) + (([],) if mesh else ()) + (([],) if Cc else ())
     # the bounds in groups of volumes whose frames fit max_bytes too (one volume's frames at least): the depth frames
-    # of a call are on the device next to its volumes
-    frame_bytes = int(depth[0].nbytes) if depth.shape[0] else 0
+    # of a call (and its colour frames) are on the device next to its volumes
+    frame_bytes = (int(depth[0].nbytes) + (int(color[0].nbytes) if Cc else 0)) if depth.shape[0] else 0
     bounds = []
     for v, e in _frame_groups(frame_start, frame_bytes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
@@ -191,34 +212,39 @@ def _fuse(depth, K, M, C, frame_start, voxel, trunc, depth_scale, depth_max, min
     origin, dims = place_volumes(bounds, voxel)
     if sparse:
         return _fuse_sparse(depth, K, M, C, frame_start, origin, dims, voxel, trunc, depth_scale, depth_max, min_weight,
-                            cpu, int(max_bytes), what, mesh)
-    _check_fits(dims, voxel, int(max_bytes), what)        # before anything is launched
-    sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
-    clouds, meshes = [], []
+                            cpu, int(max_bytes), what, mesh, color)
+    _check_fits(dims, voxel, int(max_bytes), what, 8 + 4 * Cc)        # before anything is launched
+    sizes = (8 + 4 * Cc) * dims[:, 0] * dims[:, 1] * dims[:, 2]
+    clouds, meshes, colors = [], [], []
+    host = ops._host_array
+    integrate, extract, mesher, sample = (
+        (ops.tsdf_numpy, ops.tsdf_extract_numpy, ops.tsdf_mesh_numpy, ops.tsdf_sample_color_numpy) if cpu else
+        (ops.tsdf_integrate, ops.tsdf_extract, ops.tsdf_mesh, ops.tsdf_sample_color))
     for v, e in _size_batches(sizes, max_bytes):
         lo, hi = int(frame_start[v]), int(frame_start[e])
         args = (depth[lo:hi], frame_start[v:e + 1] - lo, K[lo:hi], M[lo:hi], origin[v:e], dims[v:e], voxel, trunc,
                 depth_scale, depth_max)
-        if cpu:
-            D, w, vs = ops.tsdf_numpy(*args)
-            pts, ps = ops.tsdf_extract_numpy(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
-            m = ops.tsdf_mesh_numpy(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight) if mesh else None
-        else:
-            D, w, vs = ops.tsdf_integrate(*args)
-            pts, ps = ops.tsdf_extract(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)
-            pts, ps = pts.cpu().numpy(), ps.cpu().numpy()
-            m = ([t.cpu().numpy() for t in ops.tsdf_mesh(D, w, vs, origin[v:e], dims[v:e], voxel, min_weight)]
-                 if mesh else None)
-            del D, w
+        lattice = (origin[v:e], dims[v:e], voxel)
+        fused = integrate(*args, **(dict(color=color[lo:hi]) if Cc else {}))
+        D, w, vs = fused[:3]
+        pts, ps = extract(D, w, vs, *lattice, min_weight)
+        m = mesher(D, w, vs, *lattice, min_weight) if mesh else None
+        cols = host(sample(fused[3], w, vs, *lattice, pts, ps, min_weight)) if Cc else None
+        vcols = host(sample(fused[3], w, vs, *lattice, m[0], m[3], min_weight)) if Cc and mesh else None
+        pts, ps = host(pts), host(ps)
+        m = [host(t) for t in m] if mesh else None
+        del D, w, fused
         clouds.extend(np.ascontiguousarray(pts[ps[k]:ps[k + 1]]) for k in range(e - v))
+        if Cc:
+            colors.extend(np.ascontiguousarray(cols[ps[k]:ps[k + 1]]) for k in range(e - v))
         if mesh:
-            meshes.extend(_split_meshes(m, e - v))
-    return (clouds, meshes) if mesh else clouds
+            meshes.extend(_split_meshes(m, e - v, vcols))
+    return (clouds,) + ((meshes,) if mesh else ()) + ((colors,) if Cc else ())
 
 
 def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
                    depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False,
-                   sparse=False):
+                   sparse=False, color=None):
     """``(clouds, fragment_poses)``: the fragments of a depth sequence, the 3DMatch way.
 
     ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or floating-point metres; ``intrinsics`` [4] =
@@ -237,15 +263,30 @@ def fuse_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006
     are allocated first, ``max_bytes`` bounds the pools and tables of a batch (``ops.tsdf_sparse_bytes``) instead of the
     dense volumes, and each cloud holds the rows of ``sparse=False`` bit for bit in the sparse order (brick in lattice
     order, slot, axis).  ``sparse=True`` with ``mesh=True`` raises ``ValueError``: the mesh of sparse volumes comes
-    from ``mesh_fragments``."""
+    from ``mesh_fragments``.
+
+    ``color=`` uint8 [F,H,W,3] (R, G, B: three channels), uint8 [F,H,W] or floating point [F,H,W] (one), registered to
+    the depth pixel by pixel (``ops.tsdf_color_frames``): the colour is fused beside D and w (csrc/tsdf_color.hpp: one
+    weight, ``c = (c w + c_pixel) / (w + 1)`` on the frames that update D) and ``colors``, a list of f32 [N_g, Cc] with
+    the colour of every point of every cloud in [0, 1], is appended last to what is returned; with ``mesh=True`` every
+    mesh also gains its vertex colours f32 [Nv, Cc] as a fourth entry.  The colours are sampled from the colour volume
+    at the points (``ops.tsdf_sample_color``: trilinear over the cell's corners that have weight).  ``max_bytes`` then
+    counts ``8 + 4 Cc`` bytes per voxel (``ops.tsdf_sparse_bytes(..., channels=Cc)`` when sparse) and the colour frames
+    beside the depth frames.  Without ``color`` nothing changes."""
     _check_sparse(sparse, mesh)
     return _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight,
-                      device, max_bytes, mesh, sparse)
+                      device, max_bytes, mesh, sparse, color)
+
+
+def _color_frames(color, depth):
+    from .. import ops
+    return None if color is None else ops.tsdf_color_frames(color, depth.shape)
 
 
 def _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight, device,
-               max_bytes, mesh, sparse):
+               max_bytes, mesh, sparse, color=None):
     depth, K, poses = _frames(depth, intrinsics, poses)
+    color = _color_frames(color, depth)
     k = int(frames_per_fragment)
     if k < 1:
         raise ValueError("frames_per_fragment must be at least 1")
@@ -256,14 +297,14 @@ def _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, dept
     C = np.stack([rigid_inverse(poses[first[f]]) @ poses[f] for f in range(F)]) if F else np.zeros((0, 4, 4))
     trunc = 5.0 * voxel if trunc is None else trunc
     fused = _fuse(depth, K, M, C, frame_start, float(voxel), float(trunc), depth_scale, depth_max, float(min_weight),
-                  device, max_bytes, "fragment", mesh, sparse)
+                  device, max_bytes, "fragment", mesh, sparse, color)
     fragment_poses = poses[frame_start[:-1]].copy()
-    return (fused[0], fragment_poses, fused[1]) if mesh else (fused, fragment_poses)
+    return (fused[0], fragment_poses) + tuple(fused[1:])
 
 
 def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
                depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, mesh=False,
-               sparse=False):
+               sparse=False, color=None):
     """One cloud f32 [N,3] in the scene frame: all frames fused into ONE volume, frame f of fragment g entering with the
     camera-to-scene pose ``fragment_poses[g] @ inv(poses[first_g]) @ poses[f]``.  ``fragment_poses`` [G',4,4] is what
     ``multiway_registration`` returns; the frames of a fragment whose pose is not finite, or that has none (g >= G'),
@@ -271,15 +312,18 @@ def fuse_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, vo
     The other arguments are those of ``fuse_fragments``.  ``mesh=True`` returns ``(cloud, (vertices, normals, faces))``,
     the mesh of the same volume (empty arrays when no frame is kept).  ``sparse=True`` as for ``fuse_fragments``: the
     one volume is sparse, so a scene whose dense volume exceeds ``max_bytes`` fits when its allocated bricks do; its
-    mesh comes from ``mesh_scene``."""
+    mesh comes from ``mesh_scene``.  ``color=`` as for ``fuse_fragments``: the cloud's colours f32 [N, Cc] are appended
+    last -- ``(cloud, colors)``, or ``(cloud, (vertices, normals, faces, vertex_colors), colors)`` with a mesh."""
     _check_sparse(sparse, mesh)
     return _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
-                  min_weight, device, max_bytes, mesh, sparse)
+                  min_weight, device, max_bytes, mesh, sparse, color)
 
 
 def _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
-           min_weight, device, max_bytes, mesh, sparse):
+           min_weight, device, max_bytes, mesh, sparse, color=None):
     depth, K, poses = _frames(depth, intrinsics, poses)
+    color = _color_frames(color, depth)
+    Cc = 0 if color is None else color.shape[-1]
     k = int(frames_per_fragment)
     if k < 1:
         raise ValueError("frames_per_fragment must be at least 1")
@@ -293,34 +337,41 @@ def _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel,
         S.append(fp[g] @ rigid_inverse(poses[g * k]) @ poses[f])
     if not keep:
         none = np.zeros((0, 3), dtype=np.float32)
-        return (none, (none.copy(), none.copy(), np.zeros((0, 3), dtype=np.int32))) if mesh else none
+        nocol = (np.zeros((0, Cc), dtype=np.float32),) if Cc else ()
+        empty = (none.copy(), none.copy(), np.zeros((0, 3), dtype=np.int32)) + nocol
+        out = (none,) + ((empty,) if mesh else ()) + nocol
+        return out if len(out) > 1 else none
     S = np.stack(S)
     M = np.stack([rigid_inverse(s) for s in S])
     trunc = 5.0 * voxel if trunc is None else trunc
     fused = _fuse(np.ascontiguousarray(depth[keep]), K[keep], M, S, [0, len(keep)], float(voxel), float(trunc),
-                  depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh, sparse)
-    return (fused[0][0], fused[1][0]) if mesh else fused[0]
+                  depth_scale, depth_max, float(min_weight), device, max_bytes, "scene", mesh, sparse,
+                  None if color is None else np.ascontiguousarray(color[keep]))
+    out = tuple(part[0] for part in fused)
+    return out if len(out) > 1 else out[0]
 
 
 def mesh_fragments(depth, intrinsics, poses, frames_per_fragment=50, voxel=0.006, trunc=None, depth_scale=1000.0,
-                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+                   depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, color=None):
     """``(clouds, fragment_poses, meshes)`` as ``fuse_fragments(mesh=True)`` returns them, fused into SPARSE volumes and
     meshed straight from their pools (``ops.tsdf_mesh_sparse``; csrc/tsdf_mesh_sparse.hpp has the rule): no dense volume
     is built, ``max_bytes`` bounds the pools and tables of a batch as for ``fuse_fragments(sparse=True)``, whose clouds
     these are.  Every mesh holds the vertices, normals and triangles of ``fuse_fragments(mesh=True)`` bit for bit, in
     the sparse order (pool row, slot, axis) and so with another vertex numbering.  ``device='cpu'`` runs the NumPy
-    restatements, which work on the pools too."""
+    restatements, which work on the pools too.  ``color=`` as for ``fuse_fragments``: vertex colours as every mesh's
+    fourth entry and ``colors`` appended last (``ops.tsdf_sample_color_sparse``)."""
     return _fragments(depth, intrinsics, poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max, min_weight,
-                      device, max_bytes, True, True)
+                      device, max_bytes, True, True, color)
 
 
 def mesh_scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc=None, depth_scale=1000.0,
-               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES):
+               depth_max=DEFAULT_DEPTH_MAX, min_weight=1, device='cuda', max_bytes=DEFAULT_MAX_BYTES, color=None):
     """``(cloud, (vertices, normals, faces))`` as ``fuse_scene(mesh=True)`` returns them, from ONE sparse volume meshed
     straight from its pool (``ops.tsdf_mesh_sparse``): a scene whose dense volume exceeds ``max_bytes`` has a mesh when
-    its allocated bricks fit.  The cloud is that of ``fuse_scene(sparse=True)``; empty arrays when no frame is kept."""
+    its allocated bricks fit.  The cloud is that of ``fuse_scene(sparse=True)``; empty arrays when no frame is kept.
+    ``color=`` as for ``fuse_scene``."""
     return _scene(depth, intrinsics, poses, fragment_poses, frames_per_fragment, voxel, trunc, depth_scale, depth_max,
-                  min_weight, device, max_bytes, True, True)
+                  min_weight, device, max_bytes, True, True, color)
 
 
 # --------------------------------------------------------------------------------------------------- tracking
@@ -328,7 +379,7 @@ DEFAULT_TRACK_BYTES = 1 << 30    # the depth pyramid of the frames tracked in on
 
 
 DEFAULT_MODEL = dict(frames_per_fragment=50, voxel=0.01, trunc=None, margin=None, step=None,
-                     max_bytes=DEFAULT_MAX_BYTES, sparse=False)
+                     max_bytes=DEFAULT_MAX_BYTES, sparse=False, color=True)
 
 
 def render_views(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses, height, width, view_volume=None,
@@ -337,7 +388,9 @@ def render_views(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, poses,
     ``poses`` [R,4,4]: ``ops.tsdf_raycast`` (csrc/tsdf_raycast.hpp has the rule) on the device, where D and w are device
     tensors and so is the result; ``device='cpu'`` runs ``ops.tsdf_raycast_numpy`` on arrays.  ``view_volume`` [R] names
     every view's volume (None: one view per volume).  ``**raycast``: ``step``, ``depth_min``, ``depth_max``,
-    ``min_weight``, ``normals`` (then ``(depth, normals f32 [R,H,W,3])``), ``clip``.
+    ``min_weight``, ``normals`` (then ``(depth, normals f32 [R,H,W,3])``), ``clip``, and ``color=Cv`` (the colour volume
+    of ``ops.tsdf_integrate(color=)``, or the colour pool with ``sv=``), which appends the colour render f32 [R,H,W,Cc]:
+    NaN where the depth is 0.
 
     ``sv=``: the ``ops.SparseVolumes`` of a sparse pool ``D``, ``w`` [B,512] (``ops.tsdf_raycast_sparse``;
     csrc/tsdf_raycast_sparse.hpp has the rule: the render of the densified pool, bit for bit).  ``vol_start``,
@@ -381,9 +434,11 @@ def _metres(frames, depth_scale):
     return frames.astype(np.float32) / np.float32(depth_scale) if frames.dtype == np.uint16 else frames
 
 
-def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, depth_max, depth_diff, odometry):
+def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, depth_max, depth_diff, odometry,
+                 inten=None, photo_weight=None):
     """The frame-to-model pass of ``track_sequence``: ``(T f64 [F-1,4,4], model_status int32 [F-1])``.  ``T_ff`` are the
-    frame-to-frame poses actually used (the identity where that pass failed)."""
+    frame-to-frame poses actually used (the identity where that pass failed).  ``inten`` f32 [F,H,W]: the frames'
+    intensity; unless ``model['color']`` is false the model carries it as one colour channel and the pass is RGB-D."""
     from .. import ops
     unknown = set(model) - set(DEFAULT_MODEL)
     if unknown:
@@ -418,6 +473,9 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
     bounds[:, 3:] += margin
     origin, dims = place_volumes(bounds, voxel)
     sparse = bool(m['sparse'])
+    if inten is None or not m['color']:
+        inten = None
+    Cc = 0 if inten is None else 1
     eye = np.eye(4)
     if sparse:
         allocate = ops.tsdf_allocate_numpy if cpu else ops.tsdf_allocate
@@ -426,7 +484,7 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
         raycast = ops.tsdf_raycast_sparse_numpy if cpu else ops.tsdf_raycast_sparse
 
         def check_bytes(sv, v, e):
-            nbytes = ops.tsdf_sparse_bytes(sv)
+            nbytes = ops.tsdf_sparse_bytes(sv, channels=Cc)
             if nbytes > max_bytes:
                 raise ValueError("model of fragments %d..%d: the %d allocated bricks (of %d) take %d bytes, more than "
                                  "max_bytes = %d: raise max_bytes or the voxel size"
@@ -439,10 +497,10 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
                           np.broadcast_to(eye, (e - v, 4, 4)), origin[v:e], dims[v:e], voxel, trunc, depth_scale,
                           depth_max)
             for j in range(v, e):
-                sizes[j] = ops.tsdf_sparse_bytes(sv, j - v)
+                sizes[j] = ops.tsdf_sparse_bytes(sv, j - v, Cc)
     else:
-        _check_fits(dims, voxel, max_bytes, "model of fragment")  # before anything is launched
-        sizes = 8 * dims[:, 0] * dims[:, 1] * dims[:, 2]
+        _check_fits(dims, voxel, max_bytes, "model of fragment", 8 + 4 * Cc)  # before anything is launched
+        sizes = (8 + 4 * Cc) * dims[:, 0] * dims[:, 1] * dims[:, 2]
         integrate = ops.tsdf_numpy if cpu else ops.tsdf_integrate
         raycast = ops.tsdf_raycast_numpy if cpu else ops.tsdf_raycast
     for v, e in _size_batches(sizes, max_bytes):
@@ -451,12 +509,14 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
         vol = (origin[v:e], dims[v:e], voxel, trunc, depth_scale, depth_max)
         # step 0: the first frame of every fragment of the group, at the identity
         frames0 = (depth[first], np.arange(n + 1), K[first], np.broadcast_to(eye, (n, 4, 4)))
+        paint = dict(color=inten[first]) if Cc else {}
+        Cm = None                                              # the model's intensity: Cv, or the pool Cp
         if sparse:
             sv = allocate(*frames0, *vol)
             check_bytes(sv, v, e)
-            D, w = integrate(*frames0, sv, trunc, depth_scale, depth_max)
+            D, w, Cm = (tuple(integrate(*frames0, sv, trunc, depth_scale, depth_max, **paint)) + (None,))[:3]
         else:
-            D, w, vs = integrate(*frames0, *vol)[:3]
+            D, w, vs, Cm = (tuple(integrate(*frames0, *vol, **paint)) + (None,))[:4]
         for s in range(1, int(count.max())):
             live = np.nonzero(count > s)[0]                # the fragments that have a frame s
             f = first[live] + s
@@ -465,17 +525,33 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
             view = (D, w, sv) + views if sparse else (D, w, vs, origin[v:e], dims[v:e], voxel) + views
             frames = _metres(depth[f], depth_scale)
             pairs = np.stack([np.arange(A), A + np.arange(A)], axis=1)      # (frame s, the render of frame s - 1)
-            if cpu:
+            K2 = np.concatenate([K[f], K[f - 1]])
+            if Cc:
+                # depth and intensity of the model in one launch; one RGB-D pyramid over the frames and the renders.  A
+                # render's intensity is NaN where it has no depth: the tracker's finiteness test drops those pixels
+                render, shade = raycast(*view, step=m['step'], depth_max=depth_max, color=Cm)
+                rgbd = dict(odometry, photo_weight=photo_weight)
+                if cpu:
+                    pyr = ops.rgbd_pyramid_numpy(np.concatenate([frames, render]),
+                                                 np.concatenate([inten[f], shade[..., 0]]), K2, levels, depth_scale,
+                                                 depth_max, depth_diff)
+                    res = ops.rgbd_odometry_numpy(pyr, pairs, T_ff[f - 1], iterations, **rgbd)
+                else:
+                    import torch
+                    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(render.device)
+                    pyr = ops.rgbd_pyramid(torch.cat([up(frames), render]), torch.cat([up(inten[f]), shade[..., 0]]),
+                                           K2, levels, depth_scale, depth_max, depth_diff)
+                    res = ops.rgbd_odometry(pyr, pairs, T_ff[f - 1], iterations, **rgbd)
+                    res = (res[0].cpu().numpy(), None, None, res[3].cpu().numpy())   # the one read-back of the step
+            elif cpu:
                 both = np.concatenate([frames, raycast(*view, step=m['step'], depth_max=depth_max)])
-                pyr = ops.depth_pyramid_numpy(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
-                                              depth_diff)
+                pyr = ops.depth_pyramid_numpy(both, K2, levels, depth_scale, depth_max, depth_diff)
                 res = ops.depth_odometry_numpy(pyr, pairs, T_ff[f - 1], iterations, **odometry)
             else:
                 import torch
                 render = raycast(*view, step=m['step'], depth_max=depth_max)
                 both = torch.cat([torch.from_numpy(np.ascontiguousarray(frames)).to(render.device), render])
-                pyr = ops.depth_pyramid(both, np.concatenate([K[f], K[f - 1]]), levels, depth_scale, depth_max,
-                                        depth_diff)
+                pyr = ops.depth_pyramid(both, K2, levels, depth_scale, depth_max, depth_diff)
                 res = ops.depth_odometry(pyr, pairs, T_ff[f - 1], iterations, **odometry)
                 res = (res[0].cpu().numpy(), None, None, res[3].cpu().numpy())   # the one read-back of the step
             for i in range(A):
@@ -487,14 +563,19 @@ def _track_model(depth, K, T_ff, model, levels, iterations, cpu, depth_scale, de
             owns = np.zeros(n + 1, dtype=np.int64)
             owns[live + 1] = 1
             M = np.stack([rigid_inverse(L[j]) for j in f])
+            paint = dict(color=inten[f]) if Cc else {}
+            into = (D, w, Cm) if Cc else (D, w)
             if sparse:
                 # the bricks the frame reaches under its refined pose first, then the frame into the grown pool
-                sv, D, w = extend(sv, D, w, depth[f], np.cumsum(owns), K[f], L[f], trunc, depth_scale, depth_max)
+                grown = extend(sv, D, w, depth[f], np.cumsum(owns), K[f], L[f], trunc, depth_scale, depth_max,
+                               **(dict(color=Cm) if Cc else {}))
+                sv, into = grown[0], tuple(grown[1:])
+                D, w, Cm = (into + (None,))[:3]
                 check_bytes(sv, v, e)
-                integrate(depth[f], np.cumsum(owns), K[f], M, sv, trunc, depth_scale, depth_max, into=(D, w))
+                integrate(depth[f], np.cumsum(owns), K[f], M, sv, trunc, depth_scale, depth_max, into=into, **paint)
             else:
-                integrate(depth[f], np.cumsum(owns), K[f], M, *vol, into=(D, w))
-        del D, w
+                integrate(depth[f], np.cumsum(owns), K[f], M, *vol, into=into, **paint)
+        del D, w, Cm
     return T, model_status
 
 
@@ -540,9 +621,13 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
     depth pixel by pixel: the frame-to-frame pass runs ``ops.rgbd_odometry`` instead (csrc/rgbd_odometry.hpp: a
     photometric row beside the point-to-plane row, scaled by ``photo_weight``, default ``ops.ODO_PHOTO_WEIGHT``), which
     tracks a view of a single plane where the depth-only pass reports ``ODO_ST_SINGULAR``; ``device='cpu'`` runs its
-    NumPy restatement, and ``max_bytes`` counts the intensity pyramid too.  With ``model=`` the model pass stays
-    depth-only, because a render has no colour; it then starts from the better frame-to-frame pose.  The colour is not
-    fused into the volumes.
+    NumPy restatement, and ``max_bytes`` counts the intensity pyramid too.  With ``model=`` the model of every
+    fragment then carries ONE intensity channel beside D and w (csrc/tsdf_color.hpp; 12 bytes per voxel instead of 8):
+    every step ray-casts depth AND intensity (``ops.tsdf_raycast(color=)``; the intensity is NaN where the render has
+    no depth, which the tracker's finiteness test drops), builds one ``rgbd_pyramid`` over the frames and the renders,
+    runs ``ops.rgbd_odometry`` against the render from the frame-to-frame pose, and integrates the frame with its
+    intensity ``into`` the model -- dense or sparse, still one read-back per step.  The model pass therefore also holds
+    on views that depth cannot (a pan along a wall).  ``model=dict(color=False, ...)`` keeps the depth-only model pass.
 
     ``fuse_fragments`` needs only the relative poses inside a fragment, so the result goes straight into it.  Without
     ``model`` drift accumulates from frame to frame; with it, from fragment to fragment; nothing closes a loop."""
@@ -577,8 +662,10 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
             T[f] = np.eye(4)
     model_status = None
     if model is not None:
+        inten = None if color is None else ops.tsdf_color_frames(color, depth.shape, channels=1)[..., 0]
         T, model_status = _track_model(np.ascontiguousarray(depth), K, T, dict(model), levels, iterations, cpu,
-                                       depth_scale, depth_max, depth_diff, odometry)
+                                       depth_scale, depth_max, depth_diff, odometry, inten,
+                                       first.get('photo_weight'))
         status = np.where(model_status == 0, 0, status).astype(np.int32)
     poses = np.broadcast_to(np.eye(4), (F, 4, 4)).copy()
     for f in range(F - 1):
@@ -587,19 +674,48 @@ def track_sequence(depth, intrinsics, stride=1, device='cuda', max_bytes=DEFAULT
 
 
 # ------------------------------------------------------------------------------------------------------ files
-def write_ply_points(filename, points):
-    """Binary little-endian PLY with the three float properties x, y, z."""
+def _ply_colors(colors, count):
+    """uint8 [count,3] red, green, blue of colours f32 [count, 1 or 3] in [0, 1] (one channel is grey; a value outside
+    [0, 1] is clipped, a NaN is 0)."""
+    c = np.asarray(colors, dtype=np.float64).reshape(count, -1) if count else np.zeros((0, 3))
+    if c.shape[1] not in (1, 3):
+        raise ValueError("colors must hold 1 or 3 channels per vertex, got %d" % c.shape[1])
+    c = np.broadcast_to(c, (count, 3)) if c.shape[1] == 1 else c
+    return np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def _ply_vertex_rows(cols, names, colors):
+    """(the packed vertex rows, their header lines): float columns ``cols`` named ``names``, then uchar red, green, blue
+    when ``colors`` is given."""
+    data = np.ascontiguousarray(np.concatenate(cols, axis=1))
+    fields = [(n, '<f4') for n in names]
+    header = "".join("property float %s\n" % n for n in names)
+    if colors is None:
+        return data.tobytes(), header
+    rgb = _ply_colors(colors, data.shape[0])
+    rows = np.zeros(data.shape[0], dtype=fields + [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
+    for i, n in enumerate(names):
+        rows[n] = data[:, i]
+    rows['red'], rows['green'], rows['blue'] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    return rows.tobytes(), header + "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+
+
+def write_ply_points(filename, points, colors=None):
+    """Binary little-endian PLY with the three float properties x, y, z; with ``colors`` f32 [N, 1 or 3] in [0, 1] (what
+    ``fuse_fragments(color=)`` returns) also uchar red, green, blue.  ``read_ply_points`` reads either as a cloud."""
     p = np.ascontiguousarray(points, dtype='<f4').reshape(-1, 3)
+    rows, header = _ply_vertex_rows([p], ['x', 'y', 'z'], colors)
     with open(filename, 'wb') as f:
-        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-                 "property float z\nend_header\n" % p.shape[0]).encode('ascii'))
-        f.write(p.tobytes())
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%send_header\n"
+                 % (p.shape[0], header)).encode('ascii'))
+        f.write(rows)
 
 
-def write_ply_mesh(filename, vertices, faces, normals=None):
+def write_ply_mesh(filename, vertices, faces, normals=None, colors=None):
     """Binary little-endian PLY of a triangle mesh: ``vertex`` with the float properties x, y, z (and nx, ny, nz when
-    ``normals`` is given) and ``face`` with ``list uchar int vertex_indices``.  ``read_ply_points`` of
-    ``datasets/ThreeDMatch.py`` reads the vertices of such a file as a cloud."""
+    ``normals`` is given, and uchar red, green, blue when ``colors`` f32 [Nv, 1 or 3] in [0, 1] is) and ``face`` with
+    ``list uchar int vertex_indices``.  ``read_ply_points`` of ``datasets/ThreeDMatch.py`` reads the vertices of such a
+    file as a cloud."""
     cols = [np.ascontiguousarray(vertices, dtype='<f4').reshape(-1, 3)]
     names = ['x', 'y', 'z']
     if normals is not None:
@@ -612,11 +728,12 @@ def write_ply_mesh(filename, vertices, faces, normals=None):
         raise ValueError("face entries must be vertex indices in 0..%d" % (cols[0].shape[0] - 1))
     rows = np.zeros(f3.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     rows['n'], rows['i'] = 3, f3
+    vertex_rows, header = _ply_vertex_rows(cols, names, colors)
     with open(filename, 'wb') as f:
         f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\n"
                  "property list uchar int vertex_indices\nend_header\n"
-                 % (cols[0].shape[0], "".join("property float %s\n" % n for n in names), f3.shape[0])).encode('ascii'))
-        f.write(np.ascontiguousarray(np.concatenate(cols, axis=1)).tobytes())
+                 % (cols[0].shape[0], header, f3.shape[0])).encode('ascii'))
+        f.write(vertex_rows)
         f.write(rows.tobytes())
 
 

@@ -3315,42 +3315,84 @@ def tsdf_bounds_host(depth, frame_start, intrinsics, camera_to_volume, depth_sca
                         frame_start, intrinsics, camera_to_volume, depth_scale, depth_max)
 
 
-def _tsdf_into(into, total, device):
-    """The (D, w) of ``into=``: f32 tensors of ``total`` voxels on ``device``, contiguous -- they are written in place."""
-    if not isinstance(into, (tuple, list)) or len(into) != 2:
+def tsdf_color_frames(color, shape, channels=None):
+    """The colour frames of depth frames of ``shape`` [F,H,W] as the TSDF kernels read them (csrc/tsdf_color.hpp): a host
+    f32 array [F,H,W,Cc].  ``color``: uint8 [F,H,W,3] (R, G, B) gives Cc = 3, ``f32(c) / 255`` per channel, or with
+    ``channels=1`` the intensity ``((0.299 R + 0.587 G) + 0.114 B) / 255``; uint8 [F,H,W] gives ``v / 255``, Cc = 1;
+    floating point [F,H,W], [F,H,W,1] or [F,H,W,3] is taken as it is (f32).  The Cc = 1 forms are level 0 of
+    ``rgbd_pyramid(...).intensity`` bit for bit: a model fused from them holds what the tracker compares."""
+    c = color.detach().cpu().numpy() if isinstance(color, torch.Tensor) else np.asarray(color)
+    shape = tuple(int(a) for a in shape)
+    f32 = np.float32
+    if c.dtype == np.uint8 and c.shape == shape + (3,):
+        c = c.astype(f32)
+        if channels == 1:
+            c = (((f32(0.299) * c[..., 0] + f32(0.587) * c[..., 1]) + f32(0.114) * c[..., 2]) / f32(255.0))[..., None]
+        else:
+            c = c / f32(255.0)
+    elif c.dtype == np.uint8 and c.shape == shape:
+        c = (c.astype(f32) / f32(255.0))[..., None]
+    elif c.dtype.kind == 'f' and c.shape == shape:
+        c = c.astype(f32, copy=False)[..., None]
+    elif c.dtype.kind == 'f' and c.shape in (shape + (1,), shape + (3,)):
+        c = c.astype(f32, copy=False)
+    else:
+        raise ValueError("color must be uint8 [F,H,W,3] (R, G, B), uint8 [F,H,W] or floating point [F,H,W], [F,H,W,1] "
+                         "or [F,H,W,3] for depth frames of shape %s, got %s of shape %s" % (shape, c.dtype, c.shape))
+    if channels is not None and c.shape[-1] != int(channels):
+        raise ValueError("the colour frames give %d channels, %d were asked for" % (c.shape[-1], int(channels)))
+    return np.ascontiguousarray(c)
+
+
+def _tsdf_into(into, total, device, channels=0, what="voxels"):
+    """The (D, w) of ``into=``: f32 tensors of ``total`` voxels on ``device``, contiguous -- they are written in place.
+    ``channels`` > 0: the triple (D, w, Cv), Cv holding ``channels`` values per voxel."""
+    if channels:
+        if not isinstance(into, (tuple, list)) or len(into) != 3:
+            raise ValueError("into must be the triple (D, w, Cv) of an earlier integration with color=")
+    elif not isinstance(into, (tuple, list)) or len(into) != 2:
         raise ValueError("into must be the pair (D, w) of an earlier integration")
-    for name, t in zip("Dw", into):
+    for name, t, per in zip(("D", "w", "Cv"), into, (1, 1, channels)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("into: %s must be a contiguous float32 tensor" % name)
         if t.device.type != torch.device(device).type:
             raise ValueError("into: %s is on %s, the call runs on %s" % (name, t.device, device))
-        if int(t.numel()) != total:
-            raise ValueError("into: %s holds %d voxels, dims give %d" % (name, t.numel(), total))
-    return into[0].view(-1), into[1].view(-1)
+        if int(t.numel()) != total * per:
+            raise ValueError("into: %s holds %d values, the %d %s give %d" % (name, t.numel(), total, what, total * per))
+    return tuple(into)
 
 
 def _tsdf_integrate(fn, name, device, stream, depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel,
-                    trunc, depth_scale, depth_max, into=None):
+                    trunc, depth_scale, depth_max, into=None, color=None):
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
     total = int(vol_start[-1])
+    c = None if color is None else tsdf_color_frames(color, d.shape)
+    Cc = 0 if c is None else c.shape[-1]
     td, tfs, tK, tM, to, tn, tvx, ttr, tvs = _on(device, d, fs, K, M, o, n, vx, tr, vol_start)
     if into is None:
         D = torch.empty(total, dtype=torch.float32, device=device)
         w = torch.empty(total, dtype=torch.float32, device=device)
+        Cv = torch.empty((total, Cc), dtype=torch.float32, device=device) if Cc else None
     else:
-        D, w = _tsdf_into(into, total, device)
-        name = name.replace("integrate", "integrate_into")          # d3f_tsdf_integrate_into[_host]
+        D, w, Cv = (_tsdf_into(into, total, device, Cc) + (None,))[:3]
+    if Cc or into is not None:       # d3f_tsdf_integrate[_color][_into][_host]
+        name = name.replace("integrate", "integrate" + ("_color" if Cc else "") + ("" if into is None else "_into"))
         fn = getattr(_native.lib(), name)
-    _native.check(fn(_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), _p(tvs), V, total,
-                     int(np.diff(vol_start).max()), _p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr), float(depth_scale),
-                     float(depth_max), _p(D), _p(w), stream), name)
+    rest = (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), _p(tvs), V, total,
+            int(np.diff(vol_start).max()), _p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr), float(depth_scale),
+            float(depth_max), _p(D), _p(w))
+    if Cc:
+        tc = _on(device, c)[0]
+        _native.check(fn(*((_p(td), _p(tc), Cc) + rest + (_p(Cv), stream))), name)
+        return D, w, tvs, Cv
+    _native.check(fn(*((_p(td),) + rest + (stream,))), name)
     return D, w, tvs
 
 
 def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
-                   depth_max=TSDF_DEPTH_MAX, into=None):
+                   depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """Fuse depth frames into V dense volumes in ONE launch (d3f_tsdf_integrate; the rule is csrc/tsdf.hpp).
 
     ``depth`` [F,H,W] uint16 raw units (metres = raw / ``depth_scale``) or f32 metres; ``frame_start`` [V+1]: volume v
@@ -3363,21 +3405,28 @@ def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dim
     ``into=(D, w)``: device tensors of an earlier call over the same ``origin`` / ``dims`` / ``voxel`` / ``trunc``; the
     frames are integrated into them IN PLACE (d3f_tsdf_integrate_into) and the same tensors are returned.  The running
     mean is sequential over frames, so the frames [0, k) and then [k, F) ``into`` the result give the volume of one call
-    over [0, F) bit for bit.  A volume that owns no frame in the call keeps its values."""
+    over [0, F) bit for bit.  A volume that owns no frame in the call keeps its values.
+
+    ``color=frames`` (what ``tsdf_color_frames`` takes: uint8 RGB gives 3 channels, uint8 grey or f32 [F,H,W] one)
+    fuses the colour beside D and w (d3f_tsdf_integrate_color; the rule is csrc/tsdf_color.hpp) and returns ``(D, w,
+    vol_start, Cv f32 [total, Cc])``.  There is ONE weight: on exactly the frames that update a voxel's D and w, with
+    the w from before the increment, ``c = (c w + c_pixel) / (w + 1)`` per channel, ``c_pixel`` read bilinearly over the
+    2 x 2 pixels around the voxel's projection (the depth is read at the nearest of them); D and w are the colourless
+    call's bit for bit.  A non-finite colour value propagates into the voxels that have it among their four.  ``into=(D, w, Cv)`` continues all three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate"):
         return _tsdf_integrate(_native.lib().d3f_tsdf_integrate, "d3f_tsdf_integrate", dev, _stream(), depth,
                                frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                               depth_max, into)
+                               depth_max, into, color)
 
 
 def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc,
-                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, into=None):
-    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host / d3f_tsdf_integrate_into_host): CPU tensors out
-    (``into``: CPU tensors, written in place), no GPU call."""
+                        depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, into=None, color=None):
+    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host / d3f_tsdf_integrate_into_host and their _color
+    forms): CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
     return _tsdf_integrate(_native.lib().d3f_tsdf_integrate_host, "d3f_tsdf_integrate_host", torch.device("cpu"), None,
                            depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                           depth_max, into)
+                           depth_max, into, color)
 
 
 def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
@@ -3463,16 +3512,22 @@ def _lattice_axes(local, n, o, vx):
     return xyz, (ix, iy, iz)
 
 
-def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max, start=None):
+def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max, start=None, colour=None):
     """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1);
-    ``start = (D, w)``: integrate_voxel_into, continuing from these values."""
+    ``start = (D, w)``: integrate_voxel_into, continuing from these values.  ``colour`` f32 [F,H,W,Cc]:
+    integrate_voxel_color of csrc/tsdf_color.hpp, ``start = (D, w, c)``, and (D, w, c [n,Cc]) is returned."""
     x, y, z = xyz
     H, W = d.shape[1:]
     f32 = np.float32
     scale, dmax, half, one = f32(depth_scale), f32(depth_max), f32(0.5), f32(1.0)
+    c = None
     if start is None:
         D = np.zeros(x.shape, dtype=f32)
         w = np.zeros(x.shape, dtype=f32)
+        if colour is not None:
+            c = np.zeros(x.shape + (colour.shape[-1],), dtype=f32)
+    elif colour is not None:
+        D, w, c = start
     else:
         D, w = start
     with np.errstate(all='ignore'):
@@ -3485,38 +3540,49 @@ def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max, start=
             u = np.floor(((K[f, 0] * px) / pz + K[f, 2]) + half)
             r = np.floor(((K[f, 1] * py) / pz + K[f, 3]) + half)
             ok &= (u >= 0) & (u < f32(W)) & (r >= 0) & (r < f32(H))
-            raw = d[f][np.where(ok, r, 0).astype(np.int64), np.where(ok, u, 0).astype(np.int64)]
+            rr, uu = np.where(ok, r, 0).astype(np.int64), np.where(ok, u, 0).astype(np.int64)
+            raw = d[f][rr, uu]
             dm = raw.astype(f32) / scale if raw.dtype == np.uint16 else raw
             ok &= (dm > 0) & ~(dm > dmax)
             sdf = dm - pz
             ok &= ~(sdf < -trunc)
             t = np.minimum(one, sdf / trunc)
+            if c is not None:       # with the w from before the increment; bilinear at the unrounded projection
+                uf = np.where(ok, (K[f, 0] * px) / pz + K[f, 2], 0).astype(f32)
+                vf = np.where(ok, (K[f, 1] * py) / pz + K[f, 3], 0).astype(f32)
+                u0, v0 = np.floor(uf), np.floor(vf)
+                a, b = (uf - u0)[..., None], (vf - v0)[..., None]
+                iu, iv = u0.astype(np.int64), v0.astype(np.int64)
+                c0, c1 = np.maximum(iu, 0), np.minimum(iu + 1, W - 1)
+                r0, r1 = np.maximum(iv, 0), np.minimum(iv + 1, H - 1)
+                im = colour[f]
+                cp = ((im[r0, c0] * (one - a) + im[r0, c1] * a) * (one - b)
+                      + (im[r1, c0] * (one - a) + im[r1, c1] * a) * b)
+                c = np.where(ok[..., None], (c * w[..., None] + cp) / (w + one)[..., None], c)
             D = np.where(ok, (D * w + t) / (w + one), D)
             w = np.where(ok, w + one, w)
-    return D, w
+    return (D, w) if c is None else (D, w, c.astype(f32, copy=False))
 
 
 def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
-               depth_max=TSDF_DEPTH_MAX, chunk=1 << 21, into=None):
+               depth_max=TSDF_DEPTH_MAX, chunk=1 << 21, into=None, color=None):
     """The contract of ``tsdf_integrate`` in NumPy: ``(D f32 [total], w f32 [total], vol_start int64 [V+1])``.  Every
     product and sum is spelled out in f32 in the order of csrc/tsdf.hpp (no ``@``), so the result equals the kernel's
     bit for bit.  ``chunk`` voxels are swept at a time.  ``into=(D, w)``: contiguous f32 arrays of an earlier call,
-    written in place and returned, as ``tsdf_integrate`` does with its tensors."""
+    written in place and returned, as ``tsdf_integrate`` does with its tensors.  ``color=``: the colour of
+    csrc/tsdf_color.hpp beside them, ``(D, w, vol_start, Cv f32 [total, Cc])``; ``into=(D, w, Cv)``."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
     total = int(vol_start[-1])
+    c = None if color is None else tsdf_color_frames(color, d.shape)
+    Cc = 0 if c is None else c.shape[-1]
     if into is None:
-        D_all = np.zeros(total, dtype=np.float32)
-        w_all = np.zeros(total, dtype=np.float32)
+        arrays = [np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.float32)]
+        if Cc:
+            arrays.append(np.zeros((total, Cc), dtype=np.float32))
     else:
-        if not isinstance(into, (tuple, list)) or len(into) != 2:
-            raise ValueError("into must be the pair (D, w) of an earlier integration")
-        for name, a in zip("Dw", into):
-            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or \
-                    not a.flags.writeable or a.size != total:
-                raise ValueError("into: %s must be a writeable contiguous float32 array of %d voxels" % (name, total))
-        D_all, w_all = into[0].reshape(-1), into[1].reshape(-1)
+        arrays = _numpy_into(into, total, Cc, "voxels")
     for v in range(V):
         if into is not None and fs[v + 1] <= fs[v]:
             continue
@@ -3524,10 +3590,29 @@ def tsdf_numpy(depth, frame_start, intrinsics, volume_to_camera, origin, dims, v
         for s in range(first, last, int(chunk)):
             e = min(s + int(chunk), last)
             xyz, _ = _lattice_axes(np.arange(s, e, dtype=np.int64) - vol_start[v], n[v], o[v], vx[v])
-            start = None if into is None else (D_all[s:e].copy(), w_all[s:e].copy())
-            D_all[s:e], w_all[s:e] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v], depth_scale,
-                                                      depth_max, start)
-    return D_all, w_all, vol_start
+            start = None if into is None else tuple(a[s:e].copy() for a in arrays)
+            out = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v], depth_scale, depth_max, start, c)
+            for a, b in zip(arrays, out):
+                a[s:e] = b
+    return (arrays[0], arrays[1], vol_start) + ((arrays[2],) if Cc else ())
+
+
+def _numpy_into(into, total, channels, what):
+    """The arrays of a NumPy ``into=``, flat views [total] (and [total, channels]) of (D, w) or (D, w, Cv)."""
+    if channels:
+        if not isinstance(into, (tuple, list)) or len(into) != 3:
+            raise ValueError("into must be the triple (D, w, Cv) of an earlier integration with color=")
+    elif not isinstance(into, (tuple, list)) or len(into) != 2:
+        raise ValueError("into must be the pair (D, w) of an earlier integration")
+    for name, a, per in zip(("D", "w", "Cv"), into, (1, 1, channels)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or \
+                not a.flags.writeable or a.size != total * per:
+            raise ValueError("into: %s must be a writeable contiguous float32 array of %d values (%d %s)"
+                             % (name, total * per, total, what))
+    out = [into[0].reshape(-1), into[1].reshape(-1)]
+    if channels:
+        out.append(into[2].reshape(total, channels))
+    return out
 
 
 def _order_keys(a):
@@ -3645,14 +3730,15 @@ def _host_array(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def tsdf_sparse_bytes(sv, volume=None):
-    """The bytes of a batch of sparse volumes: the pool (D and w, 8 bytes per slot of an allocated brick) plus the
-    tables (``brick_index``, ``brick_coord``, ``brick_start``).  ``volume``: of that volume alone."""
+def tsdf_sparse_bytes(sv, volume=None, channels=0):
+    """The bytes of a batch of sparse volumes: the pool (D and w, 8 bytes per slot of an allocated brick, and 4 more per
+    colour channel with ``channels``) plus the tables (``brick_index``, ``brick_coord``, ``brick_start``).  ``volume``:
+    of that volume alone."""
     lattice, bricks, V = int(sv.lattice_start[-1]), sv.bricks, sv.volumes
     if volume is not None:
         lattice = int(np.diff(sv.lattice_start)[volume])
         bricks, V = int(np.diff(_host_array(sv.brick_start))[volume]), 1
-    return 2 * 4 * TSDF_BRICK_VOXELS * bricks + 4 * lattice + 12 * bricks + 8 * (V + 1)
+    return (2 + int(channels)) * 4 * TSDF_BRICK_VOXELS * bricks + 4 * lattice + 12 * bricks + 8 * (V + 1)
 
 
 def _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
@@ -3729,51 +3815,44 @@ def _sparse_tables(sv, device):
     return tls, bs, bi, bc, to, tn, tvx
 
 
-def _sparse_into(into, B, device):
-    """The (D, w) of a sparse ``into=``: contiguous f32 tensors of B x 512 slots on ``device``, written in place."""
-    if not isinstance(into, (tuple, list)) or len(into) != 2:
-        raise ValueError("into must be the pair (D, w) of an earlier sparse integration")
-    for name, t in zip("Dw", into):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("into: %s must be a contiguous float32 tensor" % name)
-        if t.device.type != torch.device(device).type:
-            raise ValueError("into: %s is on %s, the call runs on %s" % (name, t.device, device))
-        if int(t.numel()) != B * TSDF_BRICK_VOXELS:
-            raise ValueError("into: %s holds %d slots, the %d allocated bricks give %d"
-                             % (name, t.numel(), B, B * TSDF_BRICK_VOXELS))
-    return into[0], into[1]
-
-
 def _tsdf_integrate_sparse(host, device, stream, depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
-                           depth_scale, depth_max, into=None):
+                           depth_scale, depth_max, into=None, color=None):
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     if V != sv.volumes:
         raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
     tr = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)[3]
+    c = None if color is None else tsdf_color_frames(color, d.shape)
+    Cc = 0 if c is None else c.shape[-1]
     td, tfs, tK, tM, ttr = _on(device, d, fs, K, M, tr)
     tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, device)
     B = sv.bricks
-    name = "d3f_tsdf_sparse_integrate"
+    name = "d3f_tsdf_sparse_integrate" + ("_color" if Cc else "")
     if into is None:
         D = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
         w = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
+        Cp = torch.empty((B, TSDF_BRICK_VOXELS, Cc), dtype=torch.float32, device=device) if Cc else None
     else:
-        D, w = _sparse_into(into, B, device)
-        name += "_into"                                            # d3f_tsdf_sparse_integrate_into[_host]
-    args = (_p(td), int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tM), _p(to),
+        D, w, Cp = (_tsdf_into(into, B * TSDF_BRICK_VOXELS, device, Cc, "slots of the allocated bricks") + (None,))[:3]
+        name += "_into"                                            # d3f_tsdf_sparse_integrate[_color]_into[_host]
+    args = (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tM), _p(to),
             _p(tn), _p(tvx), _p(ttr), _p(bs), _p(bc) if B else None, B, float(depth_scale), float(depth_max),
             _p(D) if B else None, _p(w) if B else None)
+    if Cc:
+        tc = _on(device, c)[0]
+        args = (_p(td), _p(tc), Cc) + args + (_p(Cp) if B else None,)
+    else:
+        args = (_p(td),) + args
     L = _native.lib()
     if host:
         _native.check(getattr(L, name + "_host")(*args), name + "_host")
     else:
         _native.check(getattr(L, name)(*(args + (stream,))), name)
-    return D, w
+    return (D, w, Cp) if Cc else (D, w)
 
 
 def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                          depth_max=TSDF_DEPTH_MAX, into=None):
+                          depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """Fuse depth frames into the allocated bricks of ``sv`` in ONE launch (d3f_tsdf_sparse_integrate): device tensors
     ``(D f32 [B,512], w f32 [B,512])``, row b the brick ``sv.brick_coord[b]``, voxel (ix, iy, iz) at slot ``(ix & 7) + 8
     (iy & 7) + 64 (iz & 7)``.  Every slot inside the lattice holds what ``tsdf_integrate`` gives that voxel, bit for
@@ -3782,19 +3861,23 @@ def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, 
     ``into=(D, w)``: the device pool of an earlier call over the same ``sv`` and ``trunc``; the frames are integrated
     into it IN PLACE (d3f_tsdf_sparse_integrate_into; csrc/tsdf_raycast_sparse.hpp) and the same tensors are returned.
     The frames [0, k) and then [k, F) ``into`` the result give the pool of one call over [0, F) bit for bit; the rows of
-    a volume that owns no frame in the call keep their values."""
+    a volume that owns no frame in the call keep their values.
+
+    ``color=frames`` as for ``tsdf_integrate``: the colour pool ``Cp f32 [B,512,Cc]`` is fused beside D and w
+    (d3f_tsdf_sparse_integrate_color; csrc/tsdf_color.hpp) and ``(D, w, Cp)`` is returned; every slot inside the lattice
+    holds the dense ``Cv`` of that voxel bit for bit, every other slot 0.  ``into=(D, w, Cp)`` continues all three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate_sparse"):
         return _tsdf_integrate_sparse(False, dev, _stream(), depth, frame_start, intrinsics, volume_to_camera, sv,
-                                      trunc, depth_scale, depth_max, into)
+                                      trunc, depth_scale, depth_max, into, color)
 
 
 def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                               depth_max=TSDF_DEPTH_MAX, into=None):
+                               depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host / d3f_tsdf_sparse_integrate_into_host):
     CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
     return _tsdf_integrate_sparse(True, torch.device("cpu"), None, depth, frame_start, intrinsics, volume_to_camera,
-                                  sv, trunc, depth_scale, depth_max, into)
+                                  sv, trunc, depth_scale, depth_max, into, color)
 
 
 def _sparse_pool(D, w, sv, device):
@@ -3868,10 +3951,11 @@ def _slot_voxels(coord):
     return tuple(coord[:, a, None].astype(np.int64) * TSDF_BRICK + inside[a][None, :] for a in range(3))
 
 
-def tsdf_densify(D, w, sv):
+def tsdf_densify(D, w, sv, color=None):
     """A pool scattered into the dense layout of ``tsdf_integrate``: ``(D f32 [total], w f32 [total], vol_start int64
     [V+1])``, zero outside the allocated bricks, by plain indexing (tensors in, tensors on the same device out; arrays
-    in, arrays out).  For tests, and for ``tsdf_mesh`` on a volume that fits."""
+    in, arrays out).  For tests, and for ``tsdf_mesh`` on a volume that fits.  ``color=Cp`` [B,512,Cc]: the dense colour
+    ``Cv`` [total, Cc] is returned too, last."""
     arrays = isinstance(D, np.ndarray)
     dev = torch.device("cpu") if arrays else D.device
     Dp, wp = _sparse_pool(D, w, sv, dev)
@@ -3891,7 +3975,25 @@ def tsdf_densify(D, w, sv):
         dense = torch.zeros(int(vol_start[-1]), dtype=torch.float32, device=dev)
         dense[dst] = pool[src]
         out.append(dense.numpy() if arrays else dense)
-    return out[0], out[1], (vol_start if arrays else torch.from_numpy(vol_start).to(dev))
+    res = (out[0], out[1], (vol_start if arrays else torch.from_numpy(vol_start).to(dev)))
+    if color is not None:
+        Cp = _sparse_color_pool(color, sv, dev)
+        dense = torch.zeros((int(vol_start[-1]), Cp.shape[-1]), dtype=torch.float32, device=dev)
+        dense[dst] = Cp.view(-1, Cp.shape[-1])[src]
+        res += (dense.numpy() if arrays else dense,)
+    return res
+
+
+def _sparse_color_pool(Cp, sv, device):
+    """A colour pool as a contiguous f32 tensor [B, 512, Cc] on ``device`` ([B,512] is one channel)."""
+    Cp = torch.from_numpy(np.array(Cp, dtype=np.float32)) if isinstance(Cp, np.ndarray) else \
+        torch.as_tensor(Cp, dtype=torch.float32)
+    Cp = Cp.to(device).contiguous()
+    slots = sv.bricks * TSDF_BRICK_VOXELS
+    Cc = Cp.shape[-1] if Cp.dim() == 3 else 1
+    if Cc not in (1, 3) or int(Cp.numel()) != slots * Cc:
+        raise ValueError("the colour pool must be [%d, 512, 1 or 3], got %s" % (sv.bricks, tuple(Cp.shape)))
+    return Cp.view(sv.bricks, TSDF_BRICK_VOXELS, Cc)
 
 
 def tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, origin, dims, voxel, trunc,
@@ -3948,28 +4050,27 @@ def tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, origin
 
 
 def tsdf_sparse_numpy(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
-                      depth_max=TSDF_DEPTH_MAX, chunk=1 << 12, into=None):
+                      depth_max=TSDF_DEPTH_MAX, chunk=1 << 12, into=None, color=None):
     """The contract of ``tsdf_integrate_sparse`` in NumPy: ``(D f32 [B,512], w f32 [B,512])``, equal to the kernel's bit
     for bit: ``tsdf_numpy``'s arithmetic on the slots of the allocated bricks, ``chunk`` bricks at a time.
-    ``into=(D, w)``: writeable contiguous f32 arrays [B,512] of an earlier call, continued in place and returned."""
+    ``into=(D, w)``: writeable contiguous f32 arrays [B,512] of an earlier call, continued in place and returned.
+    ``color=``: ``(D, w, Cp f32 [B,512,Cc])`` (csrc/tsdf_color.hpp); ``into=(D, w, Cp)``."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     if V != sv.volumes:
         raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
     o, n, vx, tr, _ = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)
     coord, bs = _host_array(sv.brick_coord), _host_array(sv.brick_start)
+    c = None if color is None else tsdf_color_frames(color, d.shape)
+    Cc = 0 if c is None else c.shape[-1]
+    B = sv.bricks
     if into is None:
-        D = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
-        w = np.zeros((sv.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+        pools = [np.zeros((B, TSDF_BRICK_VOXELS), dtype=np.float32), np.zeros((B, TSDF_BRICK_VOXELS), dtype=np.float32)]
+        if Cc:
+            pools.append(np.zeros((B, TSDF_BRICK_VOXELS, Cc), dtype=np.float32))
     else:
-        if not isinstance(into, (tuple, list)) or len(into) != 2:
-            raise ValueError("into must be the pair (D, w) of an earlier sparse integration")
-        for name, a in zip("Dw", into):
-            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or \
-                    not a.flags.writeable or a.size != sv.bricks * TSDF_BRICK_VOXELS:
-                raise ValueError("into: %s must be a writeable contiguous float32 array of %d x 512 slots"
-                                 % (name, sv.bricks))
-        D, w = (a.reshape(sv.bricks, TSDF_BRICK_VOXELS) for a in into)
+        pools = _numpy_into(into, B * TSDF_BRICK_VOXELS, Cc, "slots of the allocated bricks")
+        pools = [a.reshape((B, TSDF_BRICK_VOXELS) + a.shape[1:]) for a in pools]
     for v in range(V):
         if into is not None and fs[v + 1] <= fs[v]:
             continue
@@ -3978,10 +4079,11 @@ def tsdf_sparse_numpy(depth, frame_start, intrinsics, volume_to_camera, sv, trun
             i = _slot_voxels(coord[s:e])
             exists = (i[0] < n[v, 0]) & (i[1] < n[v, 1]) & (i[2] < n[v, 2])
             xyz = tuple(np.float32(o[v, a]) + np.float32(vx[v]) * i[a][exists].astype(np.float32) for a in range(3))
-            start = None if into is None else (D[s:e][exists], w[s:e][exists])
-            D[s:e][exists], w[s:e][exists] = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v],
-                                                               depth_scale, depth_max, start)
-    return (D, w) if into is None else (into[0], into[1])
+            start = None if into is None else tuple(a[s:e][exists] for a in pools)
+            out = _tsdf_fuse_numpy(xyz, d, K, M, int(fs[v]), int(fs[v + 1]), tr[v], depth_scale, depth_max, start, c)
+            for a, b in zip(pools, out):
+                a[s:e][exists] = b
+    return tuple(pools) if into is None else tuple(into)
 
 
 def tsdf_extract_sparse_numpy(D, w, sv, min_weight=1.0):
@@ -4533,11 +4635,22 @@ def _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_v
     return vv.astype(np.int32), K, c, st, H, W
 
 
+def _color_volume(Cv, total, what):
+    """A colour volume / pool as a contiguous tensor [total, Cc] ([total] is one channel)."""
+    Cc = int(Cv.shape[-1]) if Cv.dim() >= 2 else 1
+    if Cc not in (1, 3) or int(Cv.numel()) != total * Cc:
+        raise ValueError("color must hold 1 or 3 channels for each of the %d %s, got %s" % (total, what, tuple(Cv.shape)))
+    return Cv.contiguous().view(total, Cc), Cc
+
+
 def _tsdf_raycast(host, device, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height,
-                  width, view_volume, step, depth_min, depth_max, min_weight, normals, clip):
+                  width, view_volume, step, depth_min, depth_max, min_weight, normals, clip, color=None):
     if host:
-        D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (D, w))
-    for name, t in zip("Dw", (D, w)):
+        D, w, color = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
+                       for a in (D, w, color))
+    for name, t in zip(("D", "w", "color"), (D, w, color)):
+        if name == "color" and t is None:
+            continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
             raise ValueError("%s must be a float32 tensor on %s: the volume stays where it is" % (name, device))
     D, w = D.contiguous().view(-1), w.contiguous().view(-1)
@@ -4551,23 +4664,25 @@ def _tsdf_raycast(host, device, D, w, vol_start, origin, dims, voxel, trunc, int
     vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
                                         depth_min, depth_max)
     R = vv.size
+    Cv, Cc = (None, 0) if color is None else _color_volume(color, total, "voxels")
     depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
     nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
+    col = torch.empty((R, H, W, Cc), dtype=torch.float32, device=device) if Cc else None
     if R:
         to, tn, tvx, tvs, tvv, tK, tC, tst = _on(device, o, n, vx, vs, vv, K, C, st)
         _check_vol_start(vol_start, tvs)
-        L = _native.lib()
-        fn, name = ((L.d3f_tsdf_raycast_host, "d3f_tsdf_raycast_host") if host else
-                    (L.d3f_tsdf_raycast, "d3f_tsdf_raycast"))
-        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, _p(tvv), R, H, W, _p(tK), _p(tC),
-                         _p(tst), float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), _p(depth),
-                         _p(nrm), None if host else _stream()), name)
-    return (depth, nrm) if normals else depth
+        name = "d3f_tsdf_raycast" + ("_color" if Cc else "") + ("_host" if host else "")
+        args = (_p(tvs), _p(to), _p(tn), _p(tvx), V, total, _p(tvv), R, H, W, _p(tK), _p(tC), _p(tst),
+                float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), _p(depth), _p(nrm))
+        args = (_p(D), _p(w)) + ((_p(Cv), Cc) if Cc else ()) + args + ((_p(col),) if Cc else ())
+        _native.check(getattr(_native.lib(), name)(*(args + (None if host else _stream(),))), name)
+    out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cc else ())
+    return out if len(out) > 1 else depth
 
 
 def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
                  view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0,
-                 normals=False, clip=True):
+                 normals=False, clip=True, color=None):
     """Ray-cast R views of V dense TSDF volumes in ONE launch (d3f_tsdf_raycast; the rule is csrc/tsdf_raycast.hpp):
     ``depth`` f32 [R,H,W] on the device, the camera z-depth in metres of the surface along every pixel's ray, 0 where
     the ray meets none -- what ``depth_pyramid`` takes as f32 metres.  ``normals=True`` returns ``(depth, normals f32
@@ -4586,21 +4701,28 @@ def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera
 
     One thread per ray, a wave per 8 x 8 pixels; no atomics, nothing read back: a view's image is bit-identical alone,
     in any batch, from run to run, and to ``tsdf_raycast_host`` and ``tsdf_raycast_numpy``.  R = 0 returns empty
-    tensors without a launch."""
+    tensors without a launch.
+
+    ``color=Cv`` (the colour volume [total, Cc] of ``tsdf_integrate(color=)``, a device tensor) appends the colour
+    image f32 [R,H,W,Cc] to whatever is returned (d3f_tsdf_raycast_color; csrc/tsdf_color.hpp): at a hit the
+    trilinear mean of the colours of the hit cell's corners with ``w >= min_weight``, renormalised over those corners
+    (so a hit in a partly observed cell still has a colour); NaN in every channel where depth is 0 -- NaN, not 0, so
+    the render goes into ``rgbd_pyramid`` as f32 intensity and the tracker's finiteness test drops those pixels.
+    Depth and normals are untouched, bit for bit."""
     dev = _tsdf_device()
     with _region("tsdf_raycast"):
         return _tsdf_raycast(False, dev, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume,
-                             height, width, view_volume, step, depth_min, depth_max, min_weight, normals, clip)
+                             height, width, view_volume, step, depth_min, depth_max, min_weight, normals, clip, color)
 
 
 def tsdf_raycast_host(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
                       view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX,
-                      min_weight=1.0, normals=False, clip=True):
-    """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host): CPU tensors (or arrays) in, CPU tensors out, no GPU
-    call."""
+                      min_weight=1.0, normals=False, clip=True, color=None):
+    """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host / d3f_tsdf_raycast_color_host): CPU tensors (or arrays)
+    in, CPU tensors out, no GPU call."""
     return _tsdf_raycast(True, torch.device("cpu"), D, w, vol_start, origin, dims, voxel, trunc, intrinsics,
                          camera_to_volume, height, width, view_volume, step, depth_min, depth_max, min_weight, normals,
-                         clip)
+                         clip, color)
 
 
 def _raycast_lerp(a, b, t):
@@ -4633,6 +4755,39 @@ def _raycast_sample_numpy(Dv, wv, n, o, vx, qx, qy, qz, min_weight):
     return inside & weighted, value.astype(f32)
 
 
+def _color_at_numpy(Cv, wv, n, o, vx, q, min_weight):
+    """color_at() of csrc/tsdf_color.hpp for the f32 points q = (qx, qy, qz) in a dense lattice with colours Cv
+    [count, Cc] and weights wv [count]: f32 [N, Cc], NaN where the rule gives none."""
+    f32 = np.float32
+    Cc = Cv.shape[1]
+    N = q[0].shape[0]
+    out = np.full((N, Cc), np.nan, dtype=f32)
+    nn = [int(a) for a in n]
+    if min(nn) < 2 or N == 0:
+        return out
+    one, zero = f32(1.0), f32(0.0)
+    g = [(q[a] - o[a]) / vx for a in range(3)]
+    inside = np.ones(N, dtype=bool)
+    for a in range(3):
+        inside &= (g[a] >= zero) & (g[a] <= f32(nn[a] - 1))
+    base = [np.minimum(np.floor(np.where(inside, g[a], zero)), f32(nn[a] - 2)) for a in range(3)]
+    f = [np.where(inside, g[a], zero) - base[a] for a in range(3)]
+    i = [b.astype(np.int64) for b in base]
+    sy, sz = nn[0], nn[0] * nn[1]
+    at = i[0] + sy * i[1] + sz * i[2]
+    tx, ty, tz = (one - f[0], f[0]), (one - f[1], f[1]), (one - f[2], f[2])
+    s = np.zeros(N, dtype=f32)
+    acc = np.zeros((N, Cc), dtype=f32)
+    for c in range(8):
+        t = (tx[c & 1] * ty[(c >> 1) & 1]) * tz[c >> 2]
+        j = at + (c & 1) + sy * ((c >> 1) & 1) + sz * (c >> 2)
+        weighted = wv[j] >= min_weight
+        s = np.where(weighted, s + t, s)
+        acc = np.where(weighted[:, None], acc + t[:, None] * Cv[j], acc)
+    ok = inside & (s > zero)
+    return np.where(ok[:, None], acc / s[:, None], f32(np.nan)).astype(f32)
+
+
 def _raycast_point_numpy(C, x, y, z):
     """ray_point() of csrc/tsdf_raycast.hpp."""
     X, Y = x * z, y * z
@@ -4661,8 +4816,9 @@ def _raycast_clip_numpy(n, o, vx, C, x, y, step, dmin, dmax):
     return lo.astype(np.int64), np.where(empty, -1, hi.astype(np.int64))
 
 
-def _raycast_view_numpy(Dv, wv, n, o, vx, K, C, H, W, step, dmin, dmax, min_weight, clip, normals):
-    """cast_ray() of csrc/tsdf_raycast.hpp for every pixel of one view: (depth f32 [H,W], normals f32 [H,W,3] | None)."""
+def _raycast_view_numpy(Dv, wv, n, o, vx, K, C, H, W, step, dmin, dmax, min_weight, clip, normals, Cv=None):
+    """cast_ray() of csrc/tsdf_raycast.hpp for every pixel of one view: (depth f32 [H,W], normals f32 [H,W,3] | None);
+    with the volume's colours ``Cv`` [count, Cc] also hit_color() of csrc/tsdf_color.hpp, f32 [H,W,Cc], third."""
     f32 = np.float32
     P = H * W
     depth = np.zeros(P, dtype=f32)
@@ -4711,14 +4867,21 @@ def _raycast_view_numpy(Dv, wv, n, o, vx, K, C, H, W, step, dmin, dmax, min_weig
         ok &= (ln > 0) & (ln <= np.finfo(f32).max)
         for j in range(3):
             nrm[idx, j] = np.where(ok, nc[j] / ln, f32(0.0))
+    if Cv is not None:
+        col = np.full((P, Cv.shape[1]), np.nan, dtype=f32)
+        idx = np.nonzero(depth > 0)[0]
+        q = _raycast_point_numpy(C, x[idx], y[idx], depth[idx])
+        col[idx] = _color_at_numpy(Cv, wv, n, o, vx, q, min_weight)
+        return depth.reshape(H, W), (nrm.reshape(H, W, 3) if normals else None), col.reshape(H, W, -1)
     return depth.reshape(H, W), (nrm.reshape(H, W, 3) if normals else None)
 
 
 def tsdf_raycast_numpy(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
                        view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX,
-                       min_weight=1.0, normals=False, clip=True):
-    """The contract of ``tsdf_raycast`` in NumPy: ``depth`` f32 [R,H,W] (and ``normals`` f32 [R,H,W,3]), every f32
-    operation in the order of csrc/tsdf_raycast.hpp, so the result equals the kernel's bit for bit."""
+                       min_weight=1.0, normals=False, clip=True, color=None):
+    """The contract of ``tsdf_raycast`` in NumPy: ``depth`` f32 [R,H,W] (and ``normals`` f32 [R,H,W,3], and with
+    ``color=Cv`` the colour image f32 [R,H,W,Cc]), every f32 operation in the order of csrc/tsdf_raycast.hpp and
+    csrc/tsdf_color.hpp, so the result equals the kernel's bit for bit."""
     D = np.ascontiguousarray(_host_array(D), dtype=np.float32).reshape(-1)
     w = np.ascontiguousarray(_host_array(w), dtype=np.float32).reshape(-1)
     V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
@@ -4728,16 +4891,120 @@ def tsdf_raycast_numpy(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, 
     vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
                                         depth_min, depth_max)
     f32 = np.float32
+    Cv = None
+    if color is not None:
+        Cv = np.ascontiguousarray(_host_array(color), dtype=f32)
+        Cv = Cv.reshape(D.size, -1)
+        if Cv.shape[1] not in (1, 3):
+            raise ValueError("color must hold 1 or 3 channels for each of the %d voxels" % D.size)
     depth = np.zeros((vv.size, H, W), dtype=f32)
     nrm = np.zeros((vv.size, H, W, 3), dtype=f32) if normals else None
+    col = np.zeros((vv.size, H, W, Cv.shape[1]), dtype=f32) if Cv is not None else None
     with np.errstate(all='ignore'):
         for r, vol in enumerate(vv):
             a, b = int(vs[vol]), int(vs[vol + 1])
-            depth[r], nr = _raycast_view_numpy(D[a:b], w[a:b], n[vol], o[vol], vx[vol], K[r], C[r], H, W, st[vol],
-                                               f32(depth_min), f32(depth_max), f32(min_weight), clip, normals)
+            res = _raycast_view_numpy(D[a:b], w[a:b], n[vol], o[vol], vx[vol], K[r], C[r], H, W, st[vol],
+                                      f32(depth_min), f32(depth_max), f32(min_weight), clip, normals,
+                                      None if Cv is None else Cv[a:b])
+            depth[r] = res[0]
             if normals:
-                nrm[r] = nr
-    return (depth, nrm) if normals else depth
+                nrm[r] = res[1]
+            if Cv is not None:
+                col[r] = res[2]
+    out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cv is not None else ())
+    return out if len(out) > 1 else depth
+
+
+def _sample_points(points, point_start, V):
+    """Host form of the points of ``tsdf_sample_color``: (f32 [N,3], int64 [V+1])."""
+    pts = np.ascontiguousarray(_host_array(points), dtype=np.float32).reshape(-1, 3)
+    ps = np.ascontiguousarray(_host_array(point_start), dtype=np.int64).reshape(-1)
+    if ps.size != V + 1 or ps[0] < 0 or ps[-1] > pts.shape[0] or (np.diff(ps) < 0).any():
+        raise ValueError("point_start must be the rising prefix [V+1] of the %d points over %d volumes, got %s"
+                         % (pts.shape[0], V, ps.tolist()))
+    return pts, ps
+
+
+def _sample_inputs(points, point_start, V, device):
+    """(points f32 [N,3], point_start int64 [V+1]) on ``device``; device tensors stay where they are (nothing is read
+    back), host values are checked."""
+    if isinstance(points, torch.Tensor) and isinstance(point_start, torch.Tensor) and points.is_cuda and \
+            device.type == "cuda":
+        tp = points.to(torch.float32).contiguous().view(-1, 3)
+        tps = point_start.to(device=device, dtype=torch.int64).contiguous().view(-1)
+        if int(tps.numel()) != V + 1:
+            raise ValueError("point_start must hold %d entries, got %d" % (V + 1, tps.numel()))
+        return tp, tps
+    pts, ps = _sample_points(points, point_start, V)
+    return tuple(_on(device, pts, ps))
+
+
+def _tsdf_sample_color(host, device, Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight):
+    if host:
+        Cv, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (Cv, w))
+    for name, t in zip(("Cv", "w"), (Cv, w)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
+            raise ValueError("%s must be a float32 tensor on %s: the volume stays where it is" % (name, device))
+    V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    total = int(vs[-1])
+    w = w.contiguous().view(-1)
+    if int(w.numel()) != total or V > TSDF_MAX_VOLUMES:
+        raise ValueError("w must hold the %d voxels of dims (at most %d volumes), got %d"
+                         % (total, TSDF_MAX_VOLUMES, w.numel()))
+    Cv, Cc = _color_volume(Cv, total, "voxels")
+    tp, tps = _sample_inputs(points, point_start, V, device)
+    N = int(tp.shape[0])
+    out = torch.empty((N, Cc), dtype=torch.float32, device=device)
+    if N:
+        to, tn, tvx, tvs = _on(device, o, n, vx, vs)
+        _check_vol_start(vol_start, tvs)
+        name = "d3f_tsdf_sample_color" + ("_host" if host else "")
+        _native.check(getattr(_native.lib(), name)(_p(Cv), _p(w), Cc, _p(tvs), _p(to), _p(tn), _p(tvx), V, total,
+                                                   _p(tp), _p(tps), N, float(min_weight), _p(out),
+                                                   None if host else _stream()), name)
+    return out
+
+
+def tsdf_sample_color(Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight=1.0):
+    """The colour of dense colour volumes at arbitrary points (d3f_tsdf_sample_color; ``color_at`` of
+    csrc/tsdf_color.hpp): f32 [N, Cc] on the device.  ``Cv`` [total, Cc], ``w``, ``vol_start``, ``origin``, ``dims``,
+    ``voxel`` as ``tsdf_integrate(color=)`` returns and takes them; ``points`` f32 [N,3] in the frame of their volume
+    and ``point_start`` [V+1] as ``tsdf_extract`` / ``tsdf_mesh`` (its vertex_start) return them -- device tensors are
+    used where they are.  A point's colour is the trilinear mean of its cell's corners with ``w >= min_weight``,
+    renormalised over those corners; a point on the last lattice plane is inside; NaN in every channel where the point
+    is outside the lattice (a NaN coordinate is), where some dimension is 1, or where no corner has weight.  One thread
+    per point; equal to the host twin and ``tsdf_sample_color_numpy`` bit for bit."""
+    dev = _tsdf_device()
+    with _region("tsdf_sample_color"):
+        return _tsdf_sample_color(False, dev, Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight)
+
+
+def tsdf_sample_color_host(Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight=1.0):
+    """The host twin of ``tsdf_sample_color`` (d3f_tsdf_sample_color_host): CPU tensors (or arrays) in, a CPU tensor
+    out, no GPU call."""
+    return _tsdf_sample_color(True, torch.device("cpu"), Cv, w, vol_start, origin, dims, voxel, points, point_start,
+                              min_weight)
+
+
+def tsdf_sample_color_numpy(Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight=1.0):
+    """The contract of ``tsdf_sample_color`` in NumPy: f32 [N, Cc], every f32 operation in the order of
+    csrc/tsdf_color.hpp."""
+    f32 = np.float32
+    w = np.ascontiguousarray(_host_array(w), dtype=f32).reshape(-1)
+    V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
+    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
+    Cv = np.ascontiguousarray(_host_array(Cv), dtype=f32).reshape(w.size, -1)
+    if w.size != int(vs[-1]) or Cv.shape[1] not in (1, 3):
+        raise ValueError("w and Cv must hold the %d voxels of dims, Cv with 1 or 3 channels" % int(vs[-1]))
+    pts, ps = _sample_points(points, point_start, V)
+    out = np.full((pts.shape[0], Cv.shape[1]), np.nan, dtype=f32)
+    with np.errstate(all='ignore'):
+        for v in range(V):
+            a, b, p0, p1 = int(vs[v]), int(vs[v + 1]), int(ps[v]), int(ps[v + 1])
+            q = tuple(pts[p0:p1, k] for k in range(3))
+            out[p0:p1] = _color_at_numpy(Cv[a:b], w[a:b], n[v], o[v], vx[v], q, f32(min_weight))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -4745,10 +5012,13 @@ def tsdf_raycast_numpy(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, 
 # csrc/tsdf_raycast_sparse.hip the kernel)
 # ---------------------------------------------------------------------------------------------------------------
 def _tsdf_raycast_sparse(host, device, D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
-                         depth_min, depth_max, min_weight, normals, clip, skip):
+                         depth_min, depth_max, min_weight, normals, clip, skip, color=None):
     if host:
-        D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (D, w))
-    for name, t in zip("Dw", (D, w)):
+        D, w, color = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
+                       for a in (D, w, color))
+    for name, t in zip(("D", "w", "color"), (D, w, color)):
+        if name == "color" and t is None:
+            continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
             raise ValueError("%s must be a float32 tensor on %s: the pool stays where it is" % (name, device))
     D, w = D.contiguous().view(-1), w.contiguous().view(-1)
@@ -4761,24 +5031,28 @@ def _tsdf_raycast_sparse(host, device, D, w, sv, trunc, intrinsics, camera_to_vo
     vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
                                         depth_min, depth_max)
     R = vv.size
+    Cp = None if color is None else _sparse_color_pool(color, sv, device)
+    Cc = 0 if Cp is None else int(Cp.shape[-1])
     depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
     nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
+    col = torch.empty((R, H, W, Cc), dtype=torch.float32, device=device) if Cc else None
     if R:
         tls, bs, bi, _, to, tn, tvx = _sparse_tables(sv, device)
         tvv, tK, tC, tst = _on(device, vv, K, C, st)
-        L = _native.lib()
-        fn, name = ((L.d3f_tsdf_raycast_sparse_host, "d3f_tsdf_raycast_sparse_host") if host else
-                    (L.d3f_tsdf_raycast_sparse, "d3f_tsdf_raycast_sparse"))
-        _native.check(fn(_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx),
-                         V, lattice, B, _p(tvv), R, H, W, _p(tK), _p(tC), _p(tst), float(depth_min), float(depth_max),
-                         float(min_weight), int(bool(clip)), int(bool(skip)), _p(depth), _p(nrm),
-                         None if host else _stream()), name)
-    return (depth, nrm) if normals else depth
+        name = "d3f_tsdf_raycast_sparse" + ("_color" if Cc else "") + ("_host" if host else "")
+        args = (_p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx), V, lattice, B, _p(tvv), R, H, W, _p(tK), _p(tC),
+                _p(tst), float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), int(bool(skip)),
+                _p(depth), _p(nrm))
+        args = ((_p(D) if B else None, _p(w) if B else None) + ((_p(Cp) if B else None, Cc) if Cc else ()) + args +
+                ((_p(col),) if Cc else ()))
+        _native.check(getattr(_native.lib(), name)(*(args + (None if host else _stream(),))), name)
+    out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cc else ())
+    return out if len(out) > 1 else depth
 
 
 def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
                         depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
-                        clip=True, skip=True):
+                        clip=True, skip=True, color=None):
     """Ray-cast R views of V SPARSE TSDF volumes in ONE launch (d3f_tsdf_raycast_sparse; the rule is
     csrc/tsdf_raycast_sparse.hpp): ``depth`` f32 [R,H,W] on the device, and ``(depth, normals f32 [R,H,W,3])`` with
     ``normals=True`` -- the outputs, conventions and view arguments of ``tsdf_raycast``.  ``D``, ``w``: the pool [B,512]
@@ -4791,39 +5065,96 @@ def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, w
     the time and no bit (at the default step of 2.5 voxels ``skip=False`` was measured the faster of the two:
     profiles/tsdf_raycast_sparse_bench.txt).  One thread per ray, no atomics, nothing read back: a view's image is
     bit-identical alone, in any batch, from run to run, and to ``tsdf_raycast_sparse_host`` and
-    ``tsdf_raycast_sparse_numpy``.  R = 0 returns empty tensors without a launch; B = 0 gives images of zeros."""
+    ``tsdf_raycast_sparse_numpy``.  R = 0 returns empty tensors without a launch; B = 0 gives images of zeros.
+
+    ``color=Cp`` (the colour pool [B,512,Cc] of ``tsdf_integrate_sparse(color=)``) appends the colour image f32
+    [R,H,W,Cc] (d3f_tsdf_raycast_sparse_color), NaN where depth is 0: ``tsdf_raycast(color=)`` of the densified pool bit
+    for bit, a corner in an absent brick being w = 0 with colour 0."""
     dev = _tsdf_device()
     with _region("tsdf_raycast_sparse"):
         return _tsdf_raycast_sparse(False, dev, D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
-                                    view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip)
+                                    view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip, color)
 
 
 def tsdf_raycast_sparse_host(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
                              depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
-                             clip=True, skip=True):
-    """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host): CPU tensors (or arrays) in, CPU tensors
-    out, no GPU call."""
+                             clip=True, skip=True, color=None):
+    """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host / _color_host): CPU tensors (or arrays)
+    in, CPU tensors out, no GPU call."""
     return _tsdf_raycast_sparse(True, torch.device("cpu"), D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
-                                view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip)
+                                view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip, color)
 
 
 def tsdf_raycast_sparse_numpy(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None,
                               step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0,
-                              normals=False, clip=True, skip=True):
+                              normals=False, clip=True, skip=True, color=None):
     """The contract of ``tsdf_raycast_sparse`` in NumPy, and the statement of its rule: ``tsdf_raycast_numpy`` of the
-    densified pool.  ``skip`` changes no bit and is not restated."""
-    Dd, wd, vs = tsdf_densify(np.ascontiguousarray(_host_array(D), dtype=np.float32),
-                              np.ascontiguousarray(_host_array(w), dtype=np.float32), sv)
-    return tsdf_raycast_numpy(Dd, wd, vs, sv.origin, sv.dims, sv.voxel, trunc, intrinsics, camera_to_volume, height,
-                              width, view_volume, step, depth_min, depth_max, min_weight, normals, clip)
+    densified pool (colour pool included).  ``skip`` changes no bit and is not restated."""
+    dense = tsdf_densify(np.ascontiguousarray(_host_array(D), dtype=np.float32),
+                         np.ascontiguousarray(_host_array(w), dtype=np.float32), sv,
+                         None if color is None else np.ascontiguousarray(_host_array(color), dtype=np.float32))
+    return tsdf_raycast_numpy(dense[0], dense[1], dense[2], sv.origin, sv.dims, sv.voxel, trunc, intrinsics,
+                              camera_to_volume, height, width, view_volume, step, depth_min, depth_max, min_weight,
+                              normals, clip, dense[3] if color is not None else None)
 
 
-def _extend_rows(sv, sv2, D, w, device):
-    """The pool of ``sv2`` (a superset of ``sv``'s bricks over the same lattices) holding the rows of (D, w): every old
-    row at its new place, zeros elsewhere.  Plain tensor indexing on ``device``; nothing is read back."""
+def _tsdf_sample_color_sparse(host, device, Cp, w, sv, points, point_start, min_weight):
+    if host:
+        Cp, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (Cp, w))
+    for name, t in zip(("Cp", "w"), (Cp, w)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
+            raise ValueError("%s must be a float32 tensor on %s: the pool stays where it is" % (name, device))
+    V, B, lattice = sv.volumes, sv.bricks, int(sv.lattice_start[-1])
+    w = w.contiguous().view(-1)
+    if int(w.numel()) != B * TSDF_BRICK_VOXELS or V > TSDF_MAX_VOLUMES:
+        raise ValueError("w must hold the %d x 512 slots of the allocated bricks, got %d" % (B, w.numel()))
+    Cp = _sparse_color_pool(Cp, sv, device)
+    Cc = int(Cp.shape[-1])
+    tp, tps = _sample_inputs(points, point_start, V, device)
+    N = int(tp.shape[0])
+    out = torch.empty((N, Cc), dtype=torch.float32, device=device)
+    if N:
+        tls, bs, bi, _, to, tn, tvx = _sparse_tables(sv, device)
+        name = "d3f_tsdf_sample_color_sparse" + ("_host" if host else "")
+        _native.check(getattr(_native.lib(), name)(_p(Cp) if B else None, _p(w) if B else None, Cc, _p(tls), _p(bs),
+                                                   _p(bi), _p(to), _p(tn), _p(tvx), V, lattice, B, _p(tp), _p(tps), N,
+                                                   float(min_weight), _p(out), None if host else _stream()), name)
+    return out
+
+
+def tsdf_sample_color_sparse(Cp, w, sv, points, point_start, min_weight=1.0):
+    """``tsdf_sample_color`` for sparse volumes (d3f_tsdf_sample_color_sparse): ``Cp`` [B,512,Cc] and ``w`` [B,512] the
+    pool of ``tsdf_integrate_sparse(color=)``, ``sv`` its ``SparseVolumes``; ``points`` / ``point_start`` as
+    ``tsdf_extract_sparse`` / ``tsdf_mesh_sparse`` return them.  A corner in an absent brick is w = 0 with colour 0, so
+    the result is ``tsdf_sample_color`` of the densified pool bit for bit."""
+    dev = _tsdf_device()
+    with _region("tsdf_sample_color_sparse"):
+        return _tsdf_sample_color_sparse(False, dev, Cp, w, sv, points, point_start, min_weight)
+
+
+def tsdf_sample_color_sparse_host(Cp, w, sv, points, point_start, min_weight=1.0):
+    """The host twin of ``tsdf_sample_color_sparse`` (d3f_tsdf_sample_color_sparse_host): no GPU call."""
+    return _tsdf_sample_color_sparse(True, torch.device("cpu"), Cp, w, sv, points, point_start, min_weight)
+
+
+def tsdf_sample_color_sparse_numpy(Cp, w, sv, points, point_start, min_weight=1.0):
+    """The contract of ``tsdf_sample_color_sparse`` in NumPy, and the statement of its rule:
+    ``tsdf_sample_color_numpy`` of the densified pool."""
+    w = np.ascontiguousarray(_host_array(w), dtype=np.float32)
+    _, wd, vs, Cv = tsdf_densify(w, w, sv, np.ascontiguousarray(_host_array(Cp), dtype=np.float32))
+    return tsdf_sample_color_numpy(Cv, wd, vs, sv.origin, sv.dims, sv.voxel, points, point_start, min_weight)
+
+
+def _extend_rows(sv, sv2, D, w, device, color=None):
+    """The pool of ``sv2`` (a superset of ``sv``'s bricks over the same lattices) holding the rows of (D, w) -- and of
+    the colour pool, when given: every old row at its new place, zeros elsewhere.  Plain tensor indexing on ``device``;
+    nothing is read back."""
     B, B2 = sv.bricks, sv2.bricks
     D, w = _sparse_pool(D, w, sv, device)
     out = [torch.zeros((B2, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device) for _ in range(2)]
+    if color is not None:
+        Cp = _sparse_color_pool(color, sv, device)
+        out.append(torch.zeros((B2, TSDF_BRICK_VOXELS, Cp.shape[-1]), dtype=torch.float32, device=device))
     if B:
         def tensor(a, dtype):
             a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
@@ -4838,11 +5169,13 @@ def _extend_rows(sv, sv2, D, w, device):
         dst = bs2[vol] + bi2[l]
         out[0][dst] = D.view(B, TSDF_BRICK_VOXELS)
         out[1][dst] = w.view(B, TSDF_BRICK_VOXELS)
-    return out[0], out[1]
+        if color is not None:
+            out[2][dst] = Cp
+    return tuple(out)
 
 
 def _tsdf_extend(host, device, stream, sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale,
-                 depth_max):
+                 depth_max, color=None):
     fs = np.asarray(frame_start).reshape(-1)
     if fs.size - 1 != sv.volumes:
         raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (fs.size - 1, sv.volumes))
@@ -4853,12 +5186,11 @@ def _tsdf_extend(host, device, stream, sv, D, w, depth, frame_start, intrinsics,
         raise ValueError("the tables of the sparse volumes do not fit their dims")
     sv2 = _tsdf_allocate(host, device, stream, depth, frame_start, intrinsics, camera_to_volume, sv.origin, sv.dims,
                          sv.voxel, trunc, depth_scale, depth_max, existing=bi)
-    D2, w2 = _extend_rows(sv, sv2, D, w, device)
-    return sv2, D2, w2
+    return (sv2,) + _extend_rows(sv, sv2, D, w, device, color)
 
 
 def tsdf_extend(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
-                depth_max=TSDF_DEPTH_MAX):
+                depth_max=TSDF_DEPTH_MAX, color=None):
     """Grow the sparse volumes ``sv`` with pool ``(D, w)`` by the bricks that further frames flag: ``(sv2, D2, w2)`` on
     the device (csrc/tsdf_raycast_sparse.hpp).  ``sv2`` holds the bricks of ``sv`` united with those the frames flag
     under ``tsdf_allocate``'s rule -- origin, dims and voxel unchanged, tables in lattice order, so ``sv2`` equals
@@ -4868,23 +5200,25 @@ def tsdf_extend(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trun
     between them; the rows move by plain tensor indexing.  ONE read-back: the number of bricks.
 
     A brick allocated late holds only the frames integrated after it appeared: where earlier frames saw that space as
-    free, it is not what the dense volume holds."""
+    free, it is not what the dense volume holds.  ``color=Cp``: the colour pool moves with its rows, new rows hold
+    colour 0, and ``(sv2, D2, w2, Cp2)`` is returned; a late brick's colour, like its D, holds only the frames
+    integrated after it appeared."""
     dev = _tsdf_device()
     with _region("tsdf_extend"):
         return _tsdf_extend(False, dev, _stream(), sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc,
-                            depth_scale, depth_max)
+                            depth_scale, depth_max, color)
 
 
 def tsdf_extend_host(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
-                     depth_max=TSDF_DEPTH_MAX):
+                     depth_max=TSDF_DEPTH_MAX, color=None):
     """The host twin of ``tsdf_extend`` (d3f_tsdf_sparse_mark_host, d3f_tsdf_sparse_index_host): CPU tensors, no GPU
     call."""
     return _tsdf_extend(True, torch.device("cpu"), None, sv, D, w, depth, frame_start, intrinsics, camera_to_volume,
-                        trunc, depth_scale, depth_max)
+                        trunc, depth_scale, depth_max, color)
 
 
 def tsdf_extend_numpy(sv, D, w, depth, frame_start, intrinsics, camera_to_volume, trunc, depth_scale=1000.0,
-                      depth_max=TSDF_DEPTH_MAX):
+                      depth_max=TSDF_DEPTH_MAX, color=None):
     """The contract of ``tsdf_extend`` in NumPy: ``(sv2, D2, w2)`` of arrays, equal to the device's tables and pool."""
     new = tsdf_allocate_numpy(depth, frame_start, intrinsics, camera_to_volume, sv.origin, sv.dims, sv.voxel, trunc,
                               depth_scale, depth_max)
@@ -4909,13 +5243,19 @@ def tsdf_extend_numpy(sv, D, w, depth, frame_start, intrinsics, camera_to_volume
         raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks" % B)
     D2 = np.zeros((sv2.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
     w2 = np.zeros((sv2.bricks, TSDF_BRICK_VOXELS), dtype=np.float32)
+    Cp = Cp2 = None
+    if color is not None:
+        Cp = np.ascontiguousarray(_host_array(color), dtype=np.float32).reshape(B, TSDF_BRICK_VOXELS, -1)
+        Cp2 = np.zeros((sv2.bricks, TSDF_BRICK_VOXELS, Cp.shape[-1]), dtype=np.float32)
     for v in range(sv.volumes):
         kept = np.flatnonzero(old_index[ls[v]:ls[v + 1]] >= 0)
         src = old_start[v] + old_index[ls[v]:ls[v + 1]][kept]
         dst = brick_start[v] + sv2.brick_index[ls[v]:ls[v + 1]][kept]
         D2[dst] = D.reshape(B, TSDF_BRICK_VOXELS)[src]
         w2[dst] = w.reshape(B, TSDF_BRICK_VOXELS)[src]
-    return sv2, D2, w2
+        if Cp is not None:
+            Cp2[dst] = Cp[src]
+    return (sv2, D2, w2) + ((Cp2,) if Cp is not None else ())
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -1316,6 +1316,113 @@ int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* 
                                  float min_weight, int clip, int skip, float* depth, float* normals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Colour in TSDF volumes (csrc/tsdf_color.hpp states the rule in full, in the terms of csrc/tsdf.hpp,
+ * csrc/tsdf_sparse.hpp and csrc/tsdf_raycast.hpp; the reference has no such step).  A colour volume Cv is f32
+ * [total_voxels, channels], channel last, beside D and w; a sparse pool Cp is f32 [bricks, 512, channels]; channels is
+ * 1 (intensity) or 3 (R, G, B), anything else is D3F_EINVAL.  Colour frames are f32 [F, H, W, channels], registered to
+ * the depth pixel by pixel.  There is one weight: on exactly the frames that update D and w, with the w from before
+ * the increment, c = (c w + c_pixel) / (w + 1) per channel, c_pixel read bilinearly over the 2 x 2 pixels around the
+ * voxel's projection (indices clamped into the image); D and w are the colourless call's bit for bit.
+ *
+ * d3f_tsdf_integrate_color / _into extend d3f_tsdf_integrate / d3f_tsdf_integrate_into: the same arguments and launch
+ * shape plus `color`, `channels` and `Cv` (written once by the voxel's thread; _into continues from the stored rows). */
+int d3f_tsdf_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
+    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
+    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
+    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
+    void* stream);
+int d3f_tsdf_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+    int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
+    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
+    float* Cv, void* stream);
+int d3f_tsdf_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+    int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
+    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
+    float* Cv, void* stream);
+int d3f_tsdf_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32, int F,
+    int H, int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
+    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
+    float* Cv, void* stream);
+/* d3f_tsdf_sparse_integrate_color / _into extend d3f_tsdf_sparse_integrate / d3f_tsdf_sparse_integrate_into: one
+ * workgroup per brick as there; a slot that does not exist holds colour 0 beside D = 0, w = 0. */
+int d3f_tsdf_sparse_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F,
+    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
+    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
+    void* stream);
+int d3f_tsdf_sparse_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F,
+    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
+    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp);
+int d3f_tsdf_sparse_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F,
+    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
+    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
+    void* stream);
+int d3f_tsdf_sparse_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32,
+    int F, int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
+    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
+    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp);
+/* d3f_tsdf_raycast_color / d3f_tsdf_raycast_sparse_color extend d3f_tsdf_raycast / d3f_tsdf_raycast_sparse: depth and
+ * normals are theirs bit for bit; color f32 [R, H, W, channels] holds, at a hit, color_at of the hit point -- the
+ * trilinear mean of the cell's corners with w >= min_weight, renormalised over those corners -- and NaN in every
+ * channel without a hit (NaN, not 0: the render goes into the intensity pyramid as it is and the RGB-D tracker's
+ * finiteness test drops those pixels). */
+int d3f_tsdf_raycast_color(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                           const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                           float min_weight, int clip, float* depth, float* normals, float* color, void* stream);
+int d3f_tsdf_raycast_color_host(const float* D, const float* w, const float* Cv, int channels,
+                                const int64_t* vol_start, const float* origin, const int32_t* dims, const float* voxel,
+                                int V, int64_t total_voxels, const int32_t* view_volume, int R, int H, int W,
+                                const float* intrinsics, const float* camera_to_volume, const float* step,
+                                float depth_min, float depth_max, float min_weight, int clip, float* depth,
+                                float* normals, float* color, void* stream);
+int d3f_tsdf_raycast_sparse_color(const float* D, const float* w, const float* Cp, int channels,
+                                  const int64_t* lattice_start, const int64_t* brick_start,
+                                  const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                  const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                                  float min_weight, int clip, int skip, float* depth, float* normals, float* color,
+                                  void* stream);
+int d3f_tsdf_raycast_sparse_color_host(const float* D, const float* w, const float* Cp, int channels,
+                                       const int64_t* lattice_start, const int64_t* brick_start,
+                                       const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                       const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                                       const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                                       const float* camera_to_volume, const float* step, float depth_min,
+                                       float depth_max, float min_weight, int clip, int skip, float* depth,
+                                       float* normals, float* color, void* stream);
+/* d3f_tsdf_sample_color / d3f_tsdf_sample_color_sparse: color_at at N arbitrary points, one thread per point -- what
+ * colours the clouds of d3f_tsdf_extract / d3f_tsdf_sparse_extract and the vertices of d3f_tsdf_mesh /
+ * d3f_tsdf_sparse_mesh, whose kernels and output orders they leave alone.  points f32 [N, 3] in the frame of the
+ * point's volume; point_start int64 [V + 1] as those calls return it (point i belongs to the last volume v with
+ * point_start[v] <= i; a point no volume owns gets NaN).  out f32 [N, channels]: NaN in every channel where the point
+ * lies outside the lattice (a NaN coordinate does) or its cell has no corner with w >= min_weight. */
+int d3f_tsdf_sample_color(const float* Cv, const float* w, int channels, const int64_t* vol_start, const float* origin,
+                          const int32_t* dims, const float* voxel, int V, int64_t total_voxels, const float* points,
+                          const int64_t* point_start, int64_t N, float min_weight, float* out, void* stream);
+int d3f_tsdf_sample_color_host(const float* Cv, const float* w, int channels, const int64_t* vol_start,
+                               const float* origin, const int32_t* dims, const float* voxel, int V,
+                               int64_t total_voxels, const float* points, const int64_t* point_start, int64_t N,
+                               float min_weight, float* out, void* stream);
+int d3f_tsdf_sample_color_sparse(const float* Cp, const float* w, int channels, const int64_t* lattice_start,
+                                 const int64_t* brick_start, const int32_t* brick_index, const float* origin,
+                                 const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks,
+                                 int64_t bricks, const float* points, const int64_t* point_start, int64_t N,
+                                 float min_weight, float* out, void* stream);
+int d3f_tsdf_sample_color_sparse_host(const float* Cp, const float* w, int channels, const int64_t* lattice_start,
+                                      const int64_t* brick_start, const int32_t* brick_index, const float* origin,
+                                      const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks,
+                                      int64_t bricks, const float* points, const int64_t* point_start, int64_t N,
+                                      float min_weight, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Depth odometry: the camera poses of a depth sequence by frame-to-frame projective point-to-plane ICP over a depth
  * pyramid (KinectFusion's tracker; csrc/odometry.hpp states the rule in full, in the terms of csrc/tsdf.hpp and
  * csrc/plane.hpp; the reference has no such step).  Frames as for d3f_tsdf_integrate: depth [F, H, W] uint16 raw units

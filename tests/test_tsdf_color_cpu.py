@@ -1,0 +1,151 @@
+"""CPU: colour in TSDF volumes (csrc/tsdf_color.hpp) through the host twins -- integration, ``into=``, the sparse pool,
+``color_at`` at hand-placed points, the ray-cast colour, the accuracy against the analytic texture, the coloured
+products of ``datasets/fragments.py`` and the RGB-D model tracker on ``device='cpu'`` -- every one against the NumPy
+restatement bit for bit.  tests/tsdf_color_cases.py has the inputs and the checks; tests/test_tsdf_color_gpu.py asks
+the same of the kernels."""
+import numpy as np
+import pytest
+
+from d3feat_pytorch_amd import ops
+import raycast_cases as RCC
+import tsdf_color_cases as CC
+
+HOST, NUMPY = CC.HOST, CC.NUMPY
+RENDER_MEDIAN, RENDER_MAX, CLOUD_MEDIAN, CLOUD_MAX = CC.RENDER_MEDIAN, CC.RENDER_MAX, CC.CLOUD_MEDIAN, CC.CLOUD_MAX
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=['uint16', 'f32'])
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("name", CC.INTEGRATION_CASES)
+def test_integration_equals_restatement_and_leaves_D_and_w_alone(name, channels, f32):
+    CC.check_integration(HOST, name, channels, f32)
+
+
+def test_small_cases_fuse_colour_somewhere():
+    assert CC.check_integration(HOST, 'dims_13x9x7', 3, False) > 100
+    assert CC.check_integration(HOST, 'zero_frames', 1, False) == 0
+
+
+def test_planted_nan_and_infinity_poison_exactly_the_voxels_that_read_them():
+    assert CC.check_poison(HOST) > 0
+
+
+@pytest.mark.parametrize("name,channels", [('dims_13x9x7', 1), ('partly_outside', 3), ('room', 1), ('room', 3)])
+def test_into_continues_colour_bit_for_bit(name, channels):
+    CC.check_into(HOST, name, channels)
+    CC.check_into(NUMPY, name, channels)
+
+
+def test_into_rejects_a_wrong_colour_volume():
+    CC.check_into_errors(HOST)
+    CC.check_into_errors(NUMPY)
+
+
+@pytest.mark.parametrize("name,channels", [(n, 1 + 2 * (i % 2)) for i, n in enumerate(CC.INTEGRATION_CASES)])
+def test_sparse_pool_holds_the_dense_colour(name, channels):
+    CC.check_sparse(HOST, name, channels)
+
+
+def test_sparse_restatement_equals_twin():
+    for name in ('dims_13x9x7', 'partly_outside'):
+        sv, D, w, Cp = CC.check_sparse(HOST, name, 3)
+        args = CC.case_args(name)
+        frames, _, rest = CC.sparse_args(args)
+        n = NUMPY.sparse(*frames, args['volume_to_camera'], CC.host_tables(sv), *rest, color=CC.case_color(name, 3))
+        assert CC.same(n[2], Cp) and CC.same(n[0], D)
+
+
+@pytest.mark.parametrize("be", [HOST, NUMPY], ids=['host', 'numpy'])
+def test_extend_moves_colour_rows_and_zero_fills_new_ones(be):
+    old, new = CC.check_extend(be, 'room', 1)
+    assert new > old > 0
+    CC.check_extend(be, 'partly_outside', 3)
+
+
+def test_sparse_bytes_count_the_colour_rows():
+    sv = CC.brick_case()[0]
+    base = ops.tsdf_sparse_bytes(sv)
+    assert ops.tsdf_sparse_bytes(sv, channels=0) == base
+    assert ops.tsdf_sparse_bytes(sv, channels=3) - base == 3 * 4 * 512 * sv.bricks
+    assert ops.tsdf_sparse_bytes(sv, 0, 1) - ops.tsdf_sparse_bytes(sv, 0) == 4 * 512 * sv.bricks
+
+
+@pytest.mark.parametrize("channels", [1, 3])
+def test_color_at_edge_cases(channels):
+    CC.check_color_at(HOST, channels)
+    CC.check_color_at_sparse(HOST, channels)
+
+
+@pytest.mark.parametrize("name", sorted(RCC.cases()))
+def test_raycast_colour(name):
+    depth, colour = CC.check_raycast(HOST, name)
+    if name in RCC.ALL_ZERO:
+        assert not depth.any() and np.isnan(colour).all()
+    else:
+        assert np.isfinite(colour).any() == bool(depth.any())
+
+
+def test_a_view_is_identical_alone_in_a_batch_reversed_and_rerun():
+    CC.check_view_alone_batch_reversed_rerun(HOST)
+
+
+def test_rendered_intensity_against_the_analytic_texture():
+    """The room's three views, intensity model: |render - tex| at the hit pixels whose depth is within one voxel of the
+    analytic depth (1.66 % of the hits are not: the silhouettes).  The NumPy restatement gives median 0.00247 and
+    maximum 0.1606 (the maximum sits at the sphere's rim, where a cell mixes sphere and wall); the twin must stay within
+    1.5 x of both, a margin for a future change of summation order only: today the results are bit-equal."""
+    median, worst, excluded = CC.check_render_accuracy(NUMPY, RENDER_MEDIAN, RENDER_MAX)
+    assert abs(median - RENDER_MEDIAN) < 5e-6 and abs(worst - RENDER_MAX) < 5e-5 and excluded < 0.03
+    CC.check_render_accuracy(HOST, RENDER_MEDIAN, RENDER_MAX)
+
+
+def test_cloud_colour_against_the_analytic_texture():
+    """``tsdf_sample_color`` at the 9266 extracted points of the room against ``tex`` at the points: the restatement
+    gives median 0.00313 and maximum 0.2235 (at the sphere's rim, where the four pixels a voxel's colour is taken
+    from lie on both sides of the silhouette); the twin within 1.5 x."""
+    median, worst = CC.check_cloud_accuracy(NUMPY, CLOUD_MEDIAN, CLOUD_MAX)
+    assert abs(median - CLOUD_MEDIAN) < 5e-6 and abs(worst - CLOUD_MAX) < 5e-5
+    CC.check_cloud_accuracy(HOST, CLOUD_MEDIAN, CLOUD_MAX)
+
+
+def test_products_carry_colours_and_max_bytes_counts_them(tmp_path):
+    clouds, colors, meshes = CC.check_products('cpu')
+    CC.check_max_bytes('cpu')
+    CC.check_ply(tmp_path, clouds, colors, meshes)
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=['dense', 'sparse'])
+def test_slide_model_pass_is_singular_without_colour_and_tracks_with_it(sparse):
+    """Six views sliding along the textured plane z = 1: the depth-only model pass (``model=dict(color=False)``) reports
+    ODO_ST_SINGULAR on every pair and keeps the frame-to-frame pose; with the intensity in the model every pair is
+    tracked against the render."""
+    poses, status, model_status = CC.track_slide('cpu', sparse, False)
+    assert model_status.tolist() == [ops.ODO_ST_SINGULAR] * 5 and not status.any()
+    assert np.array_equal(poses, CC.track_slide_pairs('cpu')[0])
+    poses, status, model_status = CC.track_slide('cpu', sparse, True)
+    assert model_status.tolist() == [0] * 5 and not status.any()
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=['dense', 'sparse'])
+def test_slide_colour_model_within_twice_the_frame_to_frame_error(sparse):
+    """The last frame's pose error under the colour model against twice that of the frame-to-frame RGB-D pass.
+    Measured: colour model 0.0089 deg / 0.136 mm (dense and sparse alike), frame-to-frame RGB-D 0.0071 deg / 0.114 mm
+    on this noise-free sequence.  This is the test of the bilinear colour read of csrc/tsdf_color.hpp: with the colour
+    of the nearest pixel instead the model ends 0.031 deg / 2.08 mm off here, because at z = 1 pixels are 16.7 mm
+    apart and voxels 20 mm, a voxel's pixel coordinate advances by 1.2 per voxel, the rounding offsets repeat every 5
+    voxels as (+0.1, -0.1, -0.3, +-0.5, +0.3) pixels and their mean, 0.1 pixel = 1.67 mm, is an offset the tracker
+    then finds between the frame and the render."""
+    model, pairs = CC.slide_errors('cpu', sparse)
+    assert model[0] <= 2.0 * pairs[0] and model[1] <= 2.0 * pairs[1]
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=['dense', 'sparse'])
+def test_noisy_room_colour_model_ends_closer_in_rotation(sparse):
+    """The painted room with 5 mm depth noise, one fragment of 12 frames: every pair is tracked against the colour model
+    and frame 11 ends closer to the truth than frame-to-frame RGB-D in degrees (0.1821 against 0.2467).  In millimetres
+    it does not (3.678 against 2.788), as the README says of the depth model's voxel quantisation; verified on this
+    restatement first, so only the rotation is asserted and both figures are printed."""
+    poses, status, model_status = CC.track_noisy_room('cpu', sparse)
+    assert model_status.tolist() == [0] * 11 and not status.any()
+    model, pairs = CC.room_errors('cpu', sparse)
+    assert model[0] < pairs[0]
