@@ -14,7 +14,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_raycast_sparse.hip", "tsdf_mesh_sparse.hip", "tsdf_color.hip"]
+           "tsdf_mesh_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -42,18 +42,33 @@ class AugmentJob(C.Structure):
                 ("out_dist", _vp)]
 
 
-# the colour entry points (csrc/tsdf_color.hpp): a form and its host twin share one argument list
+# the colour integration entry points (csrc/tsdf_color.hpp): a form and its host twin share one argument list
 _i64 = C.c_int64
 _TSDF_COLOR_INTEGRATE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
                          _vp, _vp, _vp, _vp]
 _TSDF_COLOR_SPARSE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _vp,
                       _vp, _vp]
-_TSDF_COLOR_RAYCAST = [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i,
-                       _vp, _vp, _vp, _vp]
-_TSDF_COLOR_RAYCAST_SPARSE = [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _i, _i, _vp,
-                              _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp]
-_TSDF_COLOR_SAMPLE = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _f, _vp, _vp]
-_TSDF_COLOR_SAMPLE_SPARSE = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _f, _vp, _vp]
+
+
+def _tsdf_reader_signatures():
+    """The twelve entry points that read a fused model (csrc/tsdf_raycast.hip), each from the same pieces: D and w (the
+    colour forms: Cv and the channels too), the model's tables, the views or the points with their outputs, the colour
+    image, the stream."""
+    dense = [_vp, _vp, _vp, _vp, _i, _i64]                     # vol_start, origin, dims, voxel, V, total_voxels
+    bricks = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64]    # lattice_start, brick_start, brick_index, origin, dims,
+    #                                                            voxel, V, lattice_bricks, bricks
+    views = [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i]   # view_volume, R, H, W, K, C, step, depth_min, depth_max,
+    #                                                            min_weight, clip
+    points = [_vp, _vp, _i64, _f, _vp]                         # points, point_start, N, min_weight, out
+    sigs = {}
+    for stem, model, skip in (("", dense, []), ("_sparse", bricks, [_i])):
+        cast = model + views + skip + [_vp, _vp]               # ..., depth, normals
+        for host in ("", "_host"):
+            sigs["d3f_tsdf_raycast" + stem + host] = (_i, [_vp, _vp] + cast + [_vp])
+            sigs["d3f_tsdf_raycast" + stem + "_color" + host] = (_i, [_vp, _vp, _vp, _i] + cast + [_vp, _vp])
+            sigs["d3f_tsdf_sample_color" + stem + host] = (_i, [_vp, _vp, _i] + model + points + [_vp])
+    return sigs
+
 
 # name -> (restype, argtypes); mirrors include/d3feat_hip.h one to one
 SIGNATURES = {
@@ -224,14 +239,6 @@ SIGNATURES = {
                                      _f, _f, _vp, _vp, _vp]),
     "d3f_tsdf_integrate_into_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _f, _f, _vp, _vp, _vp]),
-    "d3f_tsdf_raycast": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i,
-                              _vp, _vp, _vp]),
-    "d3f_tsdf_raycast_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f,
-                                   _i, _vp, _vp, _vp]),
-    "d3f_tsdf_raycast_sparse": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _i, _i, _i,
-                                     _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
-    "d3f_tsdf_raycast_sparse_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _i, _i,
-                                          _i, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
     "d3f_tsdf_extract_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_extract_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
@@ -280,14 +287,6 @@ SIGNATURES = {
     "d3f_tsdf_sparse_integrate_color_host": (_i, _TSDF_COLOR_SPARSE),
     "d3f_tsdf_sparse_integrate_color_into": (_i, _TSDF_COLOR_SPARSE + [_vp]),
     "d3f_tsdf_sparse_integrate_color_into_host": (_i, _TSDF_COLOR_SPARSE),
-    "d3f_tsdf_raycast_color": (_i, _TSDF_COLOR_RAYCAST),
-    "d3f_tsdf_raycast_color_host": (_i, _TSDF_COLOR_RAYCAST),
-    "d3f_tsdf_raycast_sparse_color": (_i, _TSDF_COLOR_RAYCAST_SPARSE),
-    "d3f_tsdf_raycast_sparse_color_host": (_i, _TSDF_COLOR_RAYCAST_SPARSE),
-    "d3f_tsdf_sample_color": (_i, _TSDF_COLOR_SAMPLE),
-    "d3f_tsdf_sample_color_host": (_i, _TSDF_COLOR_SAMPLE),
-    "d3f_tsdf_sample_color_sparse": (_i, _TSDF_COLOR_SAMPLE_SPARSE),
-    "d3f_tsdf_sample_color_sparse_host": (_i, _TSDF_COLOR_SAMPLE_SPARSE),
     "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
     "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
@@ -312,6 +311,8 @@ SIGNATURES = {
     "d3f_adam_guarded_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "d3f_poison_gradient_if_status": (_i, [_vp, _vp, _vp, _vp]),
 }
+
+SIGNATURES.update(_tsdf_reader_signatures())
 
 ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failure"}
 STATUS_BITS = {1: "a query has more in-radius candidates than the kernel can rank (512)",

@@ -1,10 +1,11 @@
-// What tsdf.hip, tsdf_mesh.hip and tsdf_sparse.hip share beyond the rule of tsdf.hpp: the batch of volumes and its
-// frames, the position of a voxel in its lattice, the argument checks, and the two-level exclusive scan of per-block
-// counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by
-// .hip files only.
+// What the tsdf*.hip files share beyond the rules of tsdf.hpp and tsdf_sparse.hpp: the batch of volumes and its
+// frames, the position of a voxel in its lattice, the argument checks (dense and sparse), and the two-level exclusive
+// scan of per-block counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block
+// rank).  Included by .hip files only.
 #pragma once
 #include "common.hpp"
 #include "tsdf.hpp"
+#include "tsdf_sparse.hpp"   // Bricks, brick_count
 
 namespace d3f {
 namespace tsdf {
@@ -63,6 +64,44 @@ static inline bool host_layout_ok(const int64_t* vol_start, const int32_t* dims,
     if (dims[3 * v] < 1 || dims[3 * v + 1] < 1 || dims[3 * v + 2] < 1 ||
         (int64_t)dims[3 * v] * dims[3 * v + 1] * dims[3 * v + 2] != vol_start[v + 1] - vol_start[v])
       return false;
+  return true;
+}
+
+// the sparse batch.  The lattice: at least one brick per volume, all of them indexable by int32
+static inline bool lattice_ok(int V, int64_t L) { return batch_ok(V, L) && L >= V && L <= 0x7fffffff; }
+
+static inline bool pool_ok(int V, int64_t L, int64_t B) { return lattice_ok(V, L) && B >= 0 && B <= L; }
+
+// host pointers only: lattice_start is the prefix of the brick lattices of dims, from 0 to L
+static inline bool host_lattice_ok(const int64_t* lattice_start, const int32_t* dims, int V, int64_t L) {
+  if (lattice_start[0] != 0 || lattice_start[V] != L) return false;
+  for (int v = 0; v < V; ++v) {
+    if (dims[3 * v] < 1 || dims[3 * v + 1] < 1 || dims[3 * v + 2] < 1) return false;
+    const int64_t n = (int64_t)brick_count(dims[3 * v]) * brick_count(dims[3 * v + 1]) * brick_count(dims[3 * v + 2]);
+    if (n != lattice_start[v + 1] - lattice_start[v]) return false;
+  }
+  return true;
+}
+
+// host pointers only: host_lattice_ok, and brick_start rises from 0 to B (so every row of every volume lies in the pool)
+static inline bool host_tables_ok(const int64_t* lattice_start, const int64_t* brick_start, const int32_t* dims, int V,
+                                  int64_t L, int64_t B) {
+  if (!host_lattice_ok(lattice_start, dims, V, L) || brick_start[0] != 0 || brick_start[V] != B) return false;
+  for (int v = 0; v < V; ++v)
+    if (brick_start[v + 1] < brick_start[v]) return false;
+  return true;
+}
+
+// host pointers only, after host_tables_ok: a volume holds no more bricks than its lattice, and every row's
+// coordinates lie in its volume's lattice (what the extract and mesh twins ask on top: they read brick_coord)
+static inline bool host_coords_ok(const int64_t* lattice_start, const int64_t* brick_start, const int32_t* brick_coord,
+                                  const int32_t* dims, int V) {
+  for (int v = 0; v < V; ++v) {
+    if (brick_start[v + 1] - brick_start[v] > lattice_start[v + 1] - lattice_start[v]) return false;
+    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
+      for (int a = 0; a < 3; ++a)
+        if (brick_coord[3 * b + a] < 0 || brick_coord[3 * b + a] >= brick_count(dims[3 * v + a])) return false;
+  }
   return true;
 }
 

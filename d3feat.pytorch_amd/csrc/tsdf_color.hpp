@@ -1,6 +1,5 @@
 // Colour in TSDF volumes: fused beside D and w, sampled at points and carried by the ray-caster (tsdf.hip,
-// tsdf_sparse.hip, tsdf_raycast.hip, tsdf_raycast_sparse.hip, tsdf_color.hip; the d3f_tsdf_*_color entry points and
-// their host twins).  Stated in the terms of tsdf.hpp, tsdf_sparse.hpp and tsdf_raycast.hpp, which it includes:
+// tsdf_sparse.hip, tsdf_raycast.hip; the d3f_tsdf_*_color entry points and their host twins).  Stated in the terms of tsdf.hpp, tsdf_sparse.hpp and tsdf_raycast.hpp, which it includes:
 // everything here is __host__ __device__ and reads no state, all arithmetic is f32 in exactly the order written
 // (-ffp-contract=off, correctly rounded division), and ops.tsdf_numpy(color=) / tsdf_sample_color_numpy /
 // tsdf_raycast_numpy(color=) restate it, so device, host twin and NumPy agree bit for bit.  A NaN is a NaN: which of

@@ -274,9 +274,6 @@ int run_count(const Bricks& k, const float* D, const float* w, float min_weight,
   return D3F_OK;
 }
 
-// the lattice holds at least one brick per volume, all of them indexable by int32; the pool no more than the lattice
-bool pool_ok(int V, int64_t L, int64_t B) { return batch_ok(V, L) && L >= V && L <= 0x7fffffff && B >= 0 && B <= L; }
-
 bool tables_ok(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
                const int32_t* brick_index, const int32_t* brick_coord, const int32_t* dims,
                const int64_t* vertex_start, const int64_t* face_start) {
@@ -286,23 +283,6 @@ bool tables_ok(const float* D, const float* w, const int64_t* lattice_start, con
 bool out_ok(const float* origin, const float* voxel, const MeshOut& out) {
   return origin && voxel && out.status && out.vertex_capacity >= 0 && out.face_capacity >= 0 &&
          (out.vertex_capacity == 0 || (out.vertices && out.normals)) && (out.face_capacity == 0 || out.faces);
-}
-
-// host pointers only: the prefixes are those of dims and of the pool, every row's coordinates lie in its volume's lattice
-bool host_tables_ok(const int64_t* lattice_start, const int64_t* brick_start, const int32_t* brick_coord,
-                    const int32_t* dims, int V, int64_t L, int64_t B) {
-  if (lattice_start[0] != 0 || lattice_start[V] != L || brick_start[0] != 0 || brick_start[V] != B) return false;
-  for (int v = 0; v < V; ++v) {
-    const int32_t* n = dims + 3 * (size_t)v;
-    if (n[0] < 1 || n[1] < 1 || n[2] < 1) return false;
-    const int64_t lattice = (int64_t)brick_count(n[0]) * brick_count(n[1]) * brick_count(n[2]);
-    const int64_t rows = brick_start[v + 1] - brick_start[v];
-    if (lattice != lattice_start[v + 1] - lattice_start[v] || rows < 0 || rows > lattice) return false;
-    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
-      for (int a = 0; a < 3; ++a)
-        if (brick_coord[3 * b + a] < 0 || brick_coord[3 * b + a] >= brick_count(n[a])) return false;
-  }
-  return true;
 }
 
 }  // namespace
@@ -362,7 +342,8 @@ int d3f_tsdf_sparse_mesh_host(const float* D, const float* w, const int64_t* lat
   const MeshOut out = {vertices, normals, faces, status, vertex_capacity, face_capacity};
   if (!pool_ok(V, lattice_bricks, bricks) || !lattice_start || !brick_start || !brick_index || !dims || !vertex_start ||
       !face_start || !out_ok(origin, voxel, out) || (bricks > 0 && (!D || !w || !brick_coord)) ||
-      !host_tables_ok(lattice_start, brick_start, brick_coord, dims, V, lattice_bricks, bricks))
+      !host_tables_ok(lattice_start, brick_start, dims, V, lattice_bricks, bricks) ||
+      !host_coords_ok(lattice_start, brick_start, brick_coord, dims, V))
     return D3F_EINVAL;
   const Bricks k = {lattice_start, brick_start, brick_index, brick_coord, origin, dims, voxel, V, lattice_bricks,
                     bricks};

@@ -271,38 +271,7 @@ __global__ void __launch_bounds__(kThreads) sparse_emit_kernel(Bricks k, const f
   if (overflow) atomicOr(status, D3F_TSDF_ST_OVERFLOW);
 }
 
-// -------------------------------------------------------------------------------------------------- argument checks
-// the lattice: at least one brick per volume, all of them indexable by int32
-bool lattice_ok(int V, int64_t L) { return batch_ok(V, L) && L >= V && L <= 0x7fffffff; }
-
-bool pool_ok(int V, int64_t L, int64_t B) { return lattice_ok(V, L) && B >= 0 && B <= L; }
-
-// host pointers only: lattice_start is the prefix of the brick lattices of dims, from 0 to L
-bool host_lattice_ok(const int64_t* lattice_start, const int32_t* dims, int V, int64_t L) {
-  if (lattice_start[0] != 0 || lattice_start[V] != L) return false;
-  for (int v = 0; v < V; ++v) {
-    if (dims[3 * v] < 1 || dims[3 * v + 1] < 1 || dims[3 * v + 2] < 1) return false;
-    const int64_t n = (int64_t)brick_count(dims[3 * v]) * brick_count(dims[3 * v + 1]) * brick_count(dims[3 * v + 2]);
-    if (n != lattice_start[v + 1] - lattice_start[v]) return false;
-  }
-  return true;
-}
-
-// host pointers only: brick_start rises from 0 to B, a volume holds no more bricks than its lattice, every row's
-// coordinates lie in its volume's lattice
-bool host_pool_ok(const int64_t* lattice_start, const int64_t* brick_start, const int32_t* brick_coord,
-                  const int32_t* dims, int V, int64_t B) {
-  if (brick_start[0] != 0 || brick_start[V] != B || (B > 0 && !brick_coord)) return false;
-  for (int v = 0; v < V; ++v) {
-    const int64_t n = brick_start[v + 1] - brick_start[v];
-    if (n < 0 || n > lattice_start[v + 1] - lattice_start[v]) return false;
-    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
-      for (int a = 0; a < 3; ++a)
-        if (brick_coord[3 * b + a] < 0 || brick_coord[3 * b + a] >= brick_count(dims[3 * v + a])) return false;
-  }
-  return true;
-}
-
+// ---------------------------------------------------------------- launches (the argument checks are tsdf_batch.hpp's)
 int64_t extract_blocks(int64_t B) { return B * kBlocksPerBrick; }
 
 int run_sparse_count(const Bricks& k, const float* D, const float* w, float min_weight, int64_t* point_start,
@@ -637,8 +606,9 @@ int d3f_tsdf_sparse_extract_host(const float* D, const float* w, const int64_t* 
                                  float* points, int64_t* point_start, int32_t* status) {
   if (!pool_ok(V, lattice_bricks, bricks) || !lattice_start || !brick_start || !brick_index || !origin || !dims ||
       !voxel || !point_start || !status || capacity < 0 || (capacity > 0 && !points) ||
-      (bricks > 0 && (!D || !w)) || !host_lattice_ok(lattice_start, dims, V, lattice_bricks) ||
-      !host_pool_ok(lattice_start, brick_start, brick_coord, dims, V, bricks))
+      (bricks > 0 && (!D || !w || !brick_coord)) ||
+      !host_tables_ok(lattice_start, brick_start, dims, V, lattice_bricks, bricks) ||
+      !host_coords_ok(lattice_start, brick_start, brick_coord, dims, V))
     return D3F_EINVAL;
   const Bricks k = {lattice_start, brick_start, brick_index, brick_coord, origin, dims, voxel, V, lattice_bricks,
                     bricks};

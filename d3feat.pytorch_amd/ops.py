@@ -4588,8 +4588,8 @@ def tsdf_mesh_sparse_numpy(D, w, sv, min_weight=1.0, chunk=1 << 10):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Ray-casting dense TSDF volumes: a volume plus a camera pose gives a depth image (csrc/tsdf_raycast.hpp has the rule;
-# csrc/tsdf_raycast.hip the kernel)
+# Ray-casting TSDF volumes, dense and sparse: a volume plus a camera pose gives a depth image (csrc/tsdf_raycast.hpp has
+# the rule; csrc/tsdf_raycast.hip the kernel, for both kinds of model)
 # ---------------------------------------------------------------------------------------------------------------
 RAYCAST_MAX_SAMPLES = 65536   # D3F_RAYCAST_MAX_SAMPLES: samples of one ray at most
 RAYCAST_DEPTH_MIN = 0.1       # default depth_min in metres: where every ray starts
@@ -4643,38 +4643,85 @@ def _color_volume(Cv, total, what):
     return Cv.contiguous().view(total, Cc), Cc
 
 
-def _tsdf_raycast(host, device, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height,
-                  width, view_volume, step, depth_min, depth_max, min_weight, normals, clip, color=None):
-    if host:
-        D, w, color = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
-                       for a in (D, w, color))
-    for name, t in zip(("D", "w", "color"), (D, w, color)):
+# A fused TSDF model as the entry points of csrc/tsdf_raycast.hip read it, dense or sparse: ``tensors`` (D, w and the
+# colour as given, checked to be float32 on the device), ``stem`` of the entry points' names, ``V``, ``cells`` (the voxels
+# or slots that D, w and the colours must hold), ``stored`` (False: an empty pool, whose pointers go in as NULL), the
+# words of the error messages (``holds``, ``limit``), ``color(c)`` -> (the checked colour tensor, Cc) and ``tables()`` ->
+# (the C arguments between the colour and the views / points, the tensors behind them).
+_FusedModel = collections.namedtuple("_FusedModel", "tensors stem V cells stored holds limit color tables")
+
+
+def _model_tensors(host, device, kind, named):
+    """``named`` = ((name, float32 tensor or None), ...) of a ``kind`` ("volume" / "pool"): the tensors, checked to be
+    on ``device`` (a host twin takes arrays too)."""
+    out = [torch.from_numpy(np.array(t, dtype=np.float32)) if host and isinstance(t, np.ndarray) else t
+           for _, t in named]
+    for (name, _), t in zip(named, out):
         if name == "color" and t is None:
             continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
-            raise ValueError("%s must be a float32 tensor on %s: the volume stays where it is" % (name, device))
-    D, w = D.contiguous().view(-1), w.contiguous().view(-1)
+            raise ValueError("%s must be a float32 tensor on %s: the %s stays where it is" % (name, device, kind))
+    return out
+
+
+def _dense_model(host, device, named, vol_start, origin, dims, voxel):
+    tensors = _model_tensors(host, device, "volume", named)
     V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
     o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
     total = int(vs[-1])
-    if int(D.numel()) != total or int(w.numel()) != total:
-        raise ValueError("D and w must hold the %d voxels of dims, got %d and %d" % (total, D.numel(), w.numel()))
-    if V > TSDF_MAX_VOLUMES:
+
+    def tables():
+        held = _on(device, vs, o, n, vx)
+        _check_vol_start(vol_start, held[0])
+        return tuple(_p(t) for t in held) + (V, total), held
+
+    return _FusedModel(tensors=tensors, stem="", V=V, cells=total, stored=True, holds="the %d voxels of dims" % total,
+                       limit=" (at most %d volumes)" % TSDF_MAX_VOLUMES,
+                       color=lambda c: _color_volume(c, total, "voxels"), tables=tables)
+
+
+def _sparse_model(host, device, named, sv):
+    tensors = _model_tensors(host, device, "pool", named)
+    B = sv.bricks
+
+    def color(c):
+        Cp = _sparse_color_pool(c, sv, device)
+        return Cp, int(Cp.shape[-1])
+
+    def tables():
+        tls, bs, bi, _, to, tn, tvx = held = _sparse_tables(sv, device)
+        return (_p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx), sv.volumes, int(sv.lattice_start[-1]), B), held
+
+    return _FusedModel(tensors=tensors, stem="_sparse", V=sv.volumes, cells=B * TSDF_BRICK_VOXELS, stored=bool(B),
+                       holds="the %d x 512 slots of the allocated bricks" % B, limit="", color=color, tables=tables)
+
+
+def _tsdf_raycast(host, device, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step, depth_min,
+                  depth_max, min_weight, normals, clip, skip=None):
+    """Every ray-cast form.  ``model``: ``_dense_model`` / ``_sparse_model`` of (D, w, color); ``skip``: None for the
+    dense entry points, which take none."""
+    D, w, color = model.tensors
+    D, w = D.contiguous().view(-1), w.contiguous().view(-1)
+    if int(D.numel()) != model.cells or int(w.numel()) != model.cells:
+        raise ValueError("D and w must hold %s, got %d and %d" % (model.holds, D.numel(), w.numel()))
+    if model.V > TSDF_MAX_VOLUMES:
         raise ValueError("at most %d volumes per call" % TSDF_MAX_VOLUMES)
-    vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+    vv, K, C, st, H, W = _raycast_views(model.V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
                                         depth_min, depth_max)
     R = vv.size
-    Cv, Cc = (None, 0) if color is None else _color_volume(color, total, "voxels")
+    Cv, Cc = (None, 0) if color is None else model.color(color)
     depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
     nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
     col = torch.empty((R, H, W, Cc), dtype=torch.float32, device=device) if Cc else None
     if R:
-        to, tn, tvx, tvs, tvv, tK, tC, tst = _on(device, o, n, vx, vs, vv, K, C, st)
-        _check_vol_start(vol_start, tvs)
-        name = "d3f_tsdf_raycast" + ("_color" if Cc else "") + ("_host" if host else "")
-        args = (_p(tvs), _p(to), _p(tn), _p(tvx), V, total, _p(tvv), R, H, W, _p(tK), _p(tC), _p(tst),
-                float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), _p(depth), _p(nrm))
-        args = (_p(D), _p(w)) + ((_p(Cv), Cc) if Cc else ()) + args + ((_p(col),) if Cc else ())
+        tables, _held = model.tables()
+        tvv, tK, tC, tst = _on(device, vv, K, C, st)
+        ptr = _p if model.stored else (lambda t: None)
+        name = "d3f_tsdf_raycast" + model.stem + ("_color" if Cc else "") + ("_host" if host else "")
+        args = ((ptr(D), ptr(w)) + ((ptr(Cv), Cc) if Cc else ()) + tables +
+                (_p(tvv), R, H, W, _p(tK), _p(tC), _p(tst), float(depth_min), float(depth_max), float(min_weight),
+                 int(bool(clip))) + (() if skip is None else (int(bool(skip)),)) + (_p(depth), _p(nrm)) +
+                ((_p(col),) if Cc else ()))
         _native.check(getattr(_native.lib(), name)(*(args + (None if host else _stream(),))), name)
     out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cc else ())
     return out if len(out) > 1 else depth
@@ -4711,8 +4758,9 @@ def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera
     Depth and normals are untouched, bit for bit."""
     dev = _tsdf_device()
     with _region("tsdf_raycast"):
-        return _tsdf_raycast(False, dev, D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume,
-                             height, width, view_volume, step, depth_min, depth_max, min_weight, normals, clip, color)
+        model = _dense_model(False, dev, (("D", D), ("w", w), ("color", color)), vol_start, origin, dims, voxel)
+        return _tsdf_raycast(False, dev, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                             depth_min, depth_max, min_weight, normals, clip)
 
 
 def tsdf_raycast_host(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
@@ -4720,9 +4768,10 @@ def tsdf_raycast_host(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, c
                       min_weight=1.0, normals=False, clip=True, color=None):
     """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host / d3f_tsdf_raycast_color_host): CPU tensors (or arrays)
     in, CPU tensors out, no GPU call."""
-    return _tsdf_raycast(True, torch.device("cpu"), D, w, vol_start, origin, dims, voxel, trunc, intrinsics,
-                         camera_to_volume, height, width, view_volume, step, depth_min, depth_max, min_weight, normals,
-                         clip, color)
+    cpu = torch.device("cpu")
+    model = _dense_model(True, cpu, (("D", D), ("w", w), ("color", color)), vol_start, origin, dims, voxel)
+    return _tsdf_raycast(True, cpu, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                         depth_min, depth_max, min_weight, normals, clip)
 
 
 def _raycast_lerp(a, b, t):
@@ -4939,30 +4988,22 @@ def _sample_inputs(points, point_start, V, device):
     return tuple(_on(device, pts, ps))
 
 
-def _tsdf_sample_color(host, device, Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight):
-    if host:
-        Cv, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (Cv, w))
-    for name, t in zip(("Cv", "w"), (Cv, w)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
-            raise ValueError("%s must be a float32 tensor on %s: the volume stays where it is" % (name, device))
-    V = int(np.asarray(_host_array(dims)).reshape(-1, 3).shape[0])
-    o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
-    total = int(vs[-1])
+def _tsdf_sample_color(host, device, model, points, point_start, min_weight):
+    """Every point-sampling form.  ``model``: ``_dense_model`` / ``_sparse_model`` of (the colours, w)."""
+    Cv, w = model.tensors
     w = w.contiguous().view(-1)
-    if int(w.numel()) != total or V > TSDF_MAX_VOLUMES:
-        raise ValueError("w must hold the %d voxels of dims (at most %d volumes), got %d"
-                         % (total, TSDF_MAX_VOLUMES, w.numel()))
-    Cv, Cc = _color_volume(Cv, total, "voxels")
-    tp, tps = _sample_inputs(points, point_start, V, device)
+    if int(w.numel()) != model.cells or model.V > TSDF_MAX_VOLUMES:
+        raise ValueError("w must hold %s%s, got %d" % (model.holds, model.limit, w.numel()))
+    Cv, Cc = model.color(Cv)
+    tp, tps = _sample_inputs(points, point_start, model.V, device)
     N = int(tp.shape[0])
     out = torch.empty((N, Cc), dtype=torch.float32, device=device)
     if N:
-        to, tn, tvx, tvs = _on(device, o, n, vx, vs)
-        _check_vol_start(vol_start, tvs)
-        name = "d3f_tsdf_sample_color" + ("_host" if host else "")
-        _native.check(getattr(_native.lib(), name)(_p(Cv), _p(w), Cc, _p(tvs), _p(to), _p(tn), _p(tvx), V, total,
-                                                   _p(tp), _p(tps), N, float(min_weight), _p(out),
-                                                   None if host else _stream()), name)
+        tables, _held = model.tables()
+        ptr = _p if model.stored else (lambda t: None)
+        name = "d3f_tsdf_sample_color" + model.stem + ("_host" if host else "")
+        _native.check(getattr(_native.lib(), name)(*((ptr(Cv), ptr(w), Cc) + tables + (
+            _p(tp), _p(tps), N, float(min_weight), _p(out), None if host else _stream()))), name)
     return out
 
 
@@ -4977,14 +5018,16 @@ def tsdf_sample_color(Cv, w, vol_start, origin, dims, voxel, points, point_start
     per point; equal to the host twin and ``tsdf_sample_color_numpy`` bit for bit."""
     dev = _tsdf_device()
     with _region("tsdf_sample_color"):
-        return _tsdf_sample_color(False, dev, Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight)
+        model = _dense_model(False, dev, (("Cv", Cv), ("w", w)), vol_start, origin, dims, voxel)
+        return _tsdf_sample_color(False, dev, model, points, point_start, min_weight)
 
 
 def tsdf_sample_color_host(Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight=1.0):
     """The host twin of ``tsdf_sample_color`` (d3f_tsdf_sample_color_host): CPU tensors (or arrays) in, a CPU tensor
     out, no GPU call."""
-    return _tsdf_sample_color(True, torch.device("cpu"), Cv, w, vol_start, origin, dims, voxel, points, point_start,
-                              min_weight)
+    cpu = torch.device("cpu")
+    model = _dense_model(True, cpu, (("Cv", Cv), ("w", w)), vol_start, origin, dims, voxel)
+    return _tsdf_sample_color(True, cpu, model, points, point_start, min_weight)
 
 
 def tsdf_sample_color_numpy(Cv, w, vol_start, origin, dims, voxel, points, point_start, min_weight=1.0):
@@ -5009,47 +5052,8 @@ def tsdf_sample_color_numpy(Cv, w, vol_start, origin, dims, voxel, points, point
 
 # ---------------------------------------------------------------------------------------------------------------
 # Ray-casting, growing and continuing SPARSE TSDF volumes (csrc/tsdf_raycast_sparse.hpp has the rule;
-# csrc/tsdf_raycast_sparse.hip the kernel)
+# csrc/tsdf_raycast.hip the kernel: _tsdf_raycast and _tsdf_sample_color above, with a _sparse_model)
 # ---------------------------------------------------------------------------------------------------------------
-def _tsdf_raycast_sparse(host, device, D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
-                         depth_min, depth_max, min_weight, normals, clip, skip, color=None):
-    if host:
-        D, w, color = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
-                       for a in (D, w, color))
-    for name, t in zip(("D", "w", "color"), (D, w, color)):
-        if name == "color" and t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
-            raise ValueError("%s must be a float32 tensor on %s: the pool stays where it is" % (name, device))
-    D, w = D.contiguous().view(-1), w.contiguous().view(-1)
-    V, B, lattice = sv.volumes, sv.bricks, int(sv.lattice_start[-1])
-    if int(D.numel()) != B * TSDF_BRICK_VOXELS or int(w.numel()) != int(D.numel()):
-        raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks, got %d and %d"
-                         % (B, D.numel(), w.numel()))
-    if V > TSDF_MAX_VOLUMES:
-        raise ValueError("at most %d volumes per call" % TSDF_MAX_VOLUMES)
-    vv, K, C, st, H, W = _raycast_views(V, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
-                                        depth_min, depth_max)
-    R = vv.size
-    Cp = None if color is None else _sparse_color_pool(color, sv, device)
-    Cc = 0 if Cp is None else int(Cp.shape[-1])
-    depth = torch.empty((R, H, W), dtype=torch.float32, device=device)
-    nrm = torch.empty((R, H, W, 3), dtype=torch.float32, device=device) if normals else None
-    col = torch.empty((R, H, W, Cc), dtype=torch.float32, device=device) if Cc else None
-    if R:
-        tls, bs, bi, _, to, tn, tvx = _sparse_tables(sv, device)
-        tvv, tK, tC, tst = _on(device, vv, K, C, st)
-        name = "d3f_tsdf_raycast_sparse" + ("_color" if Cc else "") + ("_host" if host else "")
-        args = (_p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx), V, lattice, B, _p(tvv), R, H, W, _p(tK), _p(tC),
-                _p(tst), float(depth_min), float(depth_max), float(min_weight), int(bool(clip)), int(bool(skip)),
-                _p(depth), _p(nrm))
-        args = ((_p(D) if B else None, _p(w) if B else None) + ((_p(Cp) if B else None, Cc) if Cc else ()) + args +
-                ((_p(col),) if Cc else ()))
-        _native.check(getattr(_native.lib(), name)(*(args + (None if host else _stream(),))), name)
-    out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cc else ())
-    return out if len(out) > 1 else depth
-
-
 def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
                         depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
                         clip=True, skip=True, color=None):
@@ -5072,8 +5076,9 @@ def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, w
     for bit, a corner in an absent brick being w = 0 with colour 0."""
     dev = _tsdf_device()
     with _region("tsdf_raycast_sparse"):
-        return _tsdf_raycast_sparse(False, dev, D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
-                                    view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip, color)
+        model = _sparse_model(False, dev, (("D", D), ("w", w), ("color", color)), sv)
+        return _tsdf_raycast(False, dev, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                             depth_min, depth_max, min_weight, normals, clip, bool(skip))
 
 
 def tsdf_raycast_sparse_host(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
@@ -5081,8 +5086,10 @@ def tsdf_raycast_sparse_host(D, w, sv, trunc, intrinsics, camera_to_volume, heig
                              clip=True, skip=True, color=None):
     """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host / _color_host): CPU tensors (or arrays)
     in, CPU tensors out, no GPU call."""
-    return _tsdf_raycast_sparse(True, torch.device("cpu"), D, w, sv, trunc, intrinsics, camera_to_volume, height, width,
-                                view_volume, step, depth_min, depth_max, min_weight, normals, clip, skip, color)
+    cpu = torch.device("cpu")
+    model = _sparse_model(True, cpu, (("D", D), ("w", w), ("color", color)), sv)
+    return _tsdf_raycast(True, cpu, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step,
+                         depth_min, depth_max, min_weight, normals, clip, bool(skip))
 
 
 def tsdf_raycast_sparse_numpy(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None,
@@ -5098,30 +5105,6 @@ def tsdf_raycast_sparse_numpy(D, w, sv, trunc, intrinsics, camera_to_volume, hei
                               normals, clip, dense[3] if color is not None else None)
 
 
-def _tsdf_sample_color_sparse(host, device, Cp, w, sv, points, point_start, min_weight):
-    if host:
-        Cp, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a for a in (Cp, w))
-    for name, t in zip(("Cp", "w"), (Cp, w)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != device.type:
-            raise ValueError("%s must be a float32 tensor on %s: the pool stays where it is" % (name, device))
-    V, B, lattice = sv.volumes, sv.bricks, int(sv.lattice_start[-1])
-    w = w.contiguous().view(-1)
-    if int(w.numel()) != B * TSDF_BRICK_VOXELS or V > TSDF_MAX_VOLUMES:
-        raise ValueError("w must hold the %d x 512 slots of the allocated bricks, got %d" % (B, w.numel()))
-    Cp = _sparse_color_pool(Cp, sv, device)
-    Cc = int(Cp.shape[-1])
-    tp, tps = _sample_inputs(points, point_start, V, device)
-    N = int(tp.shape[0])
-    out = torch.empty((N, Cc), dtype=torch.float32, device=device)
-    if N:
-        tls, bs, bi, _, to, tn, tvx = _sparse_tables(sv, device)
-        name = "d3f_tsdf_sample_color_sparse" + ("_host" if host else "")
-        _native.check(getattr(_native.lib(), name)(_p(Cp) if B else None, _p(w) if B else None, Cc, _p(tls), _p(bs),
-                                                   _p(bi), _p(to), _p(tn), _p(tvx), V, lattice, B, _p(tp), _p(tps), N,
-                                                   float(min_weight), _p(out), None if host else _stream()), name)
-    return out
-
-
 def tsdf_sample_color_sparse(Cp, w, sv, points, point_start, min_weight=1.0):
     """``tsdf_sample_color`` for sparse volumes (d3f_tsdf_sample_color_sparse): ``Cp`` [B,512,Cc] and ``w`` [B,512] the
     pool of ``tsdf_integrate_sparse(color=)``, ``sv`` its ``SparseVolumes``; ``points`` / ``point_start`` as
@@ -5129,12 +5112,15 @@ def tsdf_sample_color_sparse(Cp, w, sv, points, point_start, min_weight=1.0):
     the result is ``tsdf_sample_color`` of the densified pool bit for bit."""
     dev = _tsdf_device()
     with _region("tsdf_sample_color_sparse"):
-        return _tsdf_sample_color_sparse(False, dev, Cp, w, sv, points, point_start, min_weight)
+        return _tsdf_sample_color(False, dev, _sparse_model(False, dev, (("Cp", Cp), ("w", w)), sv), points,
+                                  point_start, min_weight)
 
 
 def tsdf_sample_color_sparse_host(Cp, w, sv, points, point_start, min_weight=1.0):
     """The host twin of ``tsdf_sample_color_sparse`` (d3f_tsdf_sample_color_sparse_host): no GPU call."""
-    return _tsdf_sample_color_sparse(True, torch.device("cpu"), Cp, w, sv, points, point_start, min_weight)
+    cpu = torch.device("cpu")
+    return _tsdf_sample_color(True, cpu, _sparse_model(True, cpu, (("Cp", Cp), ("w", w)), sv), points, point_start,
+                              min_weight)
 
 
 def tsdf_sample_color_sparse_numpy(Cp, w, sv, points, point_start, min_weight=1.0):

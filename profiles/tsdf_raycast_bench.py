@@ -45,7 +45,7 @@ MODEL = dict(frames_per_fragment=50, voxel=0.01)
 
 
 def kernel_resources():
-    """The compiler's report for raycast_kernel, or None when there is no hipcc."""
+    """The compiler's report for raycast_kernel<Volumes, 0>, or None when there is no hipcc."""
     src = os.path.join(_native.CSRC, "tsdf_raycast.hip")
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-pass-failed", "-fPIC",
@@ -56,7 +56,7 @@ def kernel_resources():
                                   universal_newlines=True).stdout
         except (OSError, subprocess.CalledProcessError):
             return None
-    block = text[text.find("raycast_kernel"):]
+    block = text[text.find("raycast_kernelIN3d3f4tsdf7VolumesELi0E"):]       # raycast_kernel<Volumes, 0>, mangled
     out = {}
     for key in ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill",
                 "LDS Size [bytes/block]"):
@@ -176,7 +176,7 @@ def main():
     # ------------------------------------------------------------------------------------------------ the kernel
     res = kernel_resources()
     say()
-    say("raycast_kernel as compiled for gfx950: %s" % (", ".join("%s %d" % kv for kv in res.items()) if res else
+    say("raycast_kernel<Volumes, 0> as compiled for gfx950: %s" % (", ".join("%s %d" % kv for kv in res.items()) if res else
                                                         "not measured (no hipcc here)"))
     text = "\n".join(out) + "\n"
     dest = os.environ.get("TSDF_RAYCAST_BENCH_OUT", os.path.join(HERE, "tsdf_raycast_bench.txt"))

@@ -1,4 +1,4 @@
-"""Times the sparse ray-caster (ops.tsdf_raycast_sparse, csrc/tsdf_raycast_sparse.hip) against the dense one and against
+"""Times the sparse ray-caster (ops.tsdf_raycast_sparse, csrc/tsdf_raycast.hip) against the dense one and against
 the only route there was before it, and the frame-to-model pass of track_sequence with a sparse model:
 
     python profiles/tsdf_raycast_sparse_bench.py            ->  profiles/tsdf_raycast_sparse_bench.txt
@@ -45,9 +45,10 @@ BATCH = 16
 MODEL = dict(frames_per_fragment=50, voxel=0.01)
 
 
-def kernel_resources(source, kernel):
-    """The compiler's report for ``kernel`` of csrc/``source``, or None when there is no hipcc."""
-    src = os.path.join(_native.CSRC, source)
+def kernel_resources(kernel):
+    """The compiler's report for the kernel of csrc/tsdf_raycast.hip whose mangled name holds ``kernel``, or None when
+    there is no hipcc."""
+    src = os.path.join(_native.CSRC, "tsdf_raycast.hip")
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-pass-failed", "-fPIC",
                "-I" + os.path.join(REPO, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
@@ -274,11 +275,11 @@ def main():
     # ------------------------------------------------------------------------------------------------ the kernels
     say()
     no_scratch = None
-    for source, kernel in (("tsdf_raycast_sparse.hip", "raycast_sparse_kernel"), ("tsdf_raycast.hip", "raycast_kernel")):
-        res = kernel_resources(source, kernel)
-        say("%s as compiled for gfx950: %s" % (kernel, ", ".join("%s %d" % kv for kv in res.items()) if res else
-                                                "not measured (no hipcc here)"))
-        if res and kernel == "raycast_sparse_kernel":
+    for model in ("Bricks", "Volumes"):             # raycast_kernel<Bricks, 0> and raycast_kernel<Volumes, 0>, mangled
+        res = kernel_resources("raycast_kernelIN3d3f4tsdf%d%sELi0E" % (len(model), model))
+        say("raycast_kernel<%s, 0> as compiled for gfx950: %s"
+            % (model, ", ".join("%s %d" % kv for kv in res.items()) if res else "not measured (no hipcc here)"))
+        if res and model == "Bricks":
             no_scratch = res.get("ScratchSize [bytes/lane]") == 0 and res.get("VGPRs Spill") == 0
     say("requirement (the sparse kernel uses no scratch): %s" % ("not measured" if no_scratch is None else
                                                                  "met" if no_scratch else "MISSED"))

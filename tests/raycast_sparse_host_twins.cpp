@@ -4,8 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined d3feat.pytorch_amd/csrc/tsdf.hip \
 //         d3feat.pytorch_amd/csrc/tsdf_sparse.hip d3feat.pytorch_amd/csrc/tsdf_raycast.hip \
-//         d3feat.pytorch_amd/csrc/tsdf_raycast_sparse.hip tests/raycast_sparse_host_twins.cpp \
-//         -o /tmp/raycast_sparse_host_twins && /tmp/raycast_sparse_host_twins
+//         tests/raycast_sparse_host_twins.cpp -o /tmp/raycast_sparse_host_twins && /tmp/raycast_sparse_host_twins
 //
 // Two volumes of different dims (13 x 9 x 7: 2 x 2 x 1 lattice bricks with borders at index 7 | 8 on two axes, and
 // 5 x 1 x 4, without a cell along y) go through d3f_tsdf_sparse_mark_host, _index_host and _integrate_host over two

@@ -74,15 +74,19 @@ def test_sparse_bytes_count_the_colour_rows():
 def test_color_at_edge_cases(channels):
     CC.check_color_at(HOST, channels)
     CC.check_color_at_sparse(HOST, channels)
+    CC.check_fold_points(HOST, channels)
 
 
-@pytest.mark.parametrize("name", sorted(RCC.cases()))
+@pytest.mark.parametrize("name", sorted(RCC.cases()) + list(CC.FOLD_CASES))
 def test_raycast_colour(name):
     depth, colour = CC.check_raycast(HOST, name)
     if name in RCC.ALL_ZERO:
         assert not depth.any() and np.isnan(colour).all()
     else:
         assert np.isfinite(colour).any() == bool(depth.any())
+    if name in CC.FOLD_CASES:       # the middle view hits in each of its four blocks of 16 x 16; its neighbours see no cell
+        halves = (slice(0, 16), slice(16, None))
+        assert all(depth[1, v, u].any() for v in halves for u in halves) and not depth[0].any() and not depth[2].any()
 
 
 def test_a_view_is_identical_alone_in_a_batch_reversed_and_rerun():

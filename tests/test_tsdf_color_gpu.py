@@ -59,15 +59,20 @@ def test_extend_moves_colour_rows_and_zero_fills_new_ones():
 def test_color_at_edge_cases(channels):
     assert CC.same(CC.check_color_at(DEVICE, channels), CC.check_color_at(CC.HOST, channels))
     assert CC.same(CC.check_color_at_sparse(DEVICE, channels), CC.check_color_at_sparse(CC.HOST, channels))
+    for device, host in zip(CC.check_fold_points(DEVICE, channels), CC.check_fold_points(CC.HOST, channels)):
+        assert CC.same(device, host)
 
 
-@pytest.mark.parametrize("name", sorted(RCC.cases()))
+@pytest.mark.parametrize("name", sorted(RCC.cases()) + list(CC.FOLD_CASES))
 def test_raycast_colour(name):
     depth, colour = CC.check_raycast(DEVICE, name)
     if name in RCC.ALL_ZERO:
         assert not depth.any() and np.isnan(colour).all()
     else:
         assert np.isfinite(colour).any() == bool(depth.any())
+    if name in CC.FOLD_CASES:       # the middle view hits in each of its four blocks of 16 x 16; its neighbours see no cell
+        halves = (slice(0, 16), slice(16, None))
+        assert all(depth[1, v, u].any() for v in halves for u in halves) and not depth[0].any() and not depth[2].any()
 
 
 def test_a_view_is_identical_alone_in_a_batch_reversed_and_rerun():

@@ -394,7 +394,77 @@ def painted_volume(key, channels):
     return dict(Cv=RCC.freeze(Cv.numpy())[0], sv=sv, Dp=Dp, wp=wp, Cp=Cp)
 
 
+def drop_brick(sv, row, *pools):
+    """Host tables ``sv`` and their pools without pool row ``row``: the brick is absent, as if it had never been
+    allocated."""
+    index, coord, start = (np.array(arr(a)) for a in (sv.brick_index, sv.brick_coord, sv.brick_start))
+    v = int(np.searchsorted(start, row, side='right')) - 1
+    part = index[sv.lattice_start[v]:sv.lattice_start[v + 1]]           # a view: the volume's part of the table
+    rank = row - start[v]
+    part[part == rank] = -1
+    part[part > rank] -= 1
+    start[v + 1:] -= 1
+    return (ops.SparseVolumes(index, np.delete(coord, row, axis=0), start, sv.origin, sv.dims, sv.voxel),) + \
+        tuple(np.delete(arr(a), row, axis=0) for a in pools)
+
+
+FOLD_CASES = ('fold_1', 'fold_3')          # names of fold_case(channels) among the ray-cast cases
+
+
+@functools.lru_cache(maxsize=None)
+def fold_case(channels):
+    """The one case that drives every instantiation of the single ray-cast body and the single sampling body of
+    csrc/tsdf_raycast.hip (dense and sparse; no colour, one channel, three) through the places a shared pixel prologue
+    can go wrong.  Two volumes, 13 x 9 x 7 (2 x 2 x 1 bricks, their borders at index 7 | 8 on two axes) and 5 x 1 x 4
+    (no cell along y), fused with colour by the host twins from the two small frames each; three views in the order
+    1, 0, 1 of 19 x 21 pixels: two blocks of 16 x 16 each way, with partial 8 x 8 tiles in both; the sparse form with
+    one allocated brick of the first volume taken out of the tables.  Returns (ray-cast arguments, dict(Cv, sv, Dp, wp,
+    Cp), channels, points f32 [40,3], point_start): 32 points of the first volume, one of them outside its lattice
+    and one NaN, and 8 of the second."""
+    small = S.small_cases()['dims_13x9x7']
+    twice = lambda a: np.concatenate([np.asarray(a)] * 2)
+    a = dict(small, depth=twice(small['depth']), frame_start=[0, 2, 4], volume_to_camera=twice(small['volume_to_camera']),
+             camera_to_volume=twice(small['camera_to_volume']),
+             origin=np.array([[-0.3, -0.2, 0.9], [-0.1, 0.0, 0.95]], dtype=np.float32), dims=np.array([[13, 9, 7], [5, 1, 4]]))
+    inten = RC.small_intensity(a['depth'].shape)
+    color = inten if channels == 1 else RC.to_rgb8(inten)
+    D, w, vs, Cv = (arr(t) for t in ops.tsdf_integrate_host(color=color, **S.integrate_args(a)))
+    frames, lattice, rest = sparse_args(a)
+    sv = host_tables(ops.tsdf_allocate_host(*frames, a['camera_to_volume'], *lattice))
+    pools = ops.tsdf_integrate_sparse_host(*frames, a['volume_to_camera'], sv, *rest, color=color)
+    assert int(arr(sv.brick_start)[1]) == 4, "the four lattice bricks of the first volume are allocated"
+    sv, Dp, wp, Cp = drop_brick(sv, 3, *pools)        # brick (1, 1, 0): the voxels with ix >= 8 and iy = 8
+    C = np.asarray(small['camera_to_volume'])
+    case = dict(D=D, w=w, vol_start=vs, origin=a['origin'], dims=a['dims'], voxel=a['voxel'], trunc=a['trunc'],
+                intrinsics=np.array([30.0, 30.0, 9.0, 15.0]), camera_to_volume=np.stack([C[0], C[1], C[0]]), height=21,
+                width=19, view_volume=[1, 0, 1])
+    rng = np.random.default_rng(5)
+    g = np.concatenate([rng.uniform(0.0, 1.0, (29, 3)) * [12.0, 8.0, 6.0], [[10.5, 7.5, 3.5]], [[12.5, 4.0, 3.0], [np.nan, 1.0, 1.0]],
+                        rng.uniform(0.0, 1.0, (8, 3)) * [4.0, 0.0, 3.0]])
+    own = np.repeat([0, 1], [32, 8])
+    pts = (a['origin'][own] + np.float32(a['voxel']) * g.astype(np.float32)).astype(np.float32)
+    RCC.freeze(D, w, Cv, Dp, wp, Cp, pts)
+    return case, dict(Cv=Cv, sv=sv, Dp=Dp, wp=wp, Cp=Cp), channels, pts, [0, 32, 40]
+
+
+def check_fold_points(be, channels):
+    """The points of ``fold_case`` through the dense and the sparse sampler: each equals the restatement."""
+    case, vol, _, pts, ps = fold_case(channels)
+    lattice = {k: case[k] for k in ('vol_start', 'origin', 'dims', 'voxel')}
+    dense = arr(be.sample(be.put(vol['Cv']), be.put(case['w']), points=pts, point_start=ps, **lattice))
+    sparse = arr(be.sample_sparse(be.put(vol['Cp']), be.put(vol['wp']), vol['sv'], pts, ps))
+    assert dense.shape == sparse.shape == (40, channels)
+    assert same(dense, ops.tsdf_sample_color_numpy(vol['Cv'], case['w'], points=pts, point_start=ps, **lattice))
+    assert same(sparse, ops.tsdf_sample_color_sparse_numpy(vol['Cp'], vol['wp'], vol['sv'], pts, ps))
+    assert np.isnan(dense[30:]).all() and np.isnan(sparse[30:]).all()      # outside, NaN, and the volume without a cell
+    assert np.isfinite(dense[:30]).all(1).any() and np.isfinite(sparse[:30]).all(1).any()
+    assert not same(dense, sparse), "the dropped brick holds none of the points"
+    return dense, sparse
+
+
 def raycast_case(name):
+    if name in FOLD_CASES:
+        return fold_case(int(name[-1]))[:3]
     channels = 3 if name in THREE_CHANNELS else 1
     key = VOLUME_OF.get(name) or name[len('small_'):]
     return RCC.cases()[name], painted_volume(key, channels), channels
