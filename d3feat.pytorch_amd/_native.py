@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libd3feat_hip.so")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
-           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
+           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
            "tsdf_mesh_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -42,12 +42,25 @@ class AugmentJob(C.Structure):
                 ("out_dist", _vp)]
 
 
-# the colour integration entry points (csrc/tsdf_color.hpp): a form and its host twin share one argument list
 _i64 = C.c_int64
-_TSDF_COLOR_INTEGRATE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
-                         _vp, _vp, _vp, _vp]
-_TSDF_COLOR_SPARSE = [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _vp,
-                      _vp, _vp]
+
+
+def _tsdf_integrate_signatures():
+    """The sixteen entry points that write a fused model (csrc/tsdf_integrate.hip), each from the same pieces: the depth
+    (the colour forms: the colour frames and the channels too), the frames, the model's tables around K, M, origin,
+    dims, voxel and trunc, the depth range, D and w (the colour forms: the colour volume too), the stream."""
+    frames = [_i, _i, _i, _i, _vp]                             # depth_is_f32, F, H, W, frame_start
+    common = [_vp, _vp, _vp, _vp, _vp, _vp]                    # K, M, origin, dims, voxel, trunc
+    dense = frames + [_vp, _i, _i64, _i64] + common            # vol_start, V, total_voxels, max_volume_voxels
+    bricks = frames + [_i] + common + [_vp, _vp, _i64]         # V; brick_start, brick_coord, bricks
+    sigs = {}
+    for stem, model, host_stream in (("", dense, [_vp]), ("_sparse", bricks, [])):     # the sparse twins take no stream
+        for into in ("", "_into"):
+            for host, stream in (("", [_vp]), ("_host", host_stream)):
+                name = "d3f_tsdf" + stem + "_integrate%s" + into + host
+                sigs[name % ""] = (_i, [_vp] + model + [_f, _f, _vp, _vp] + stream)
+                sigs[name % "_color"] = (_i, [_vp, _vp, _i] + model + [_f, _f, _vp, _vp, _vp] + stream)
+    return sigs
 
 
 def _tsdf_reader_signatures():
@@ -231,14 +244,6 @@ SIGNATURES = {
     "d3f_pose_graph_edge_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_tsdf_bounds": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
     "d3f_tsdf_bounds_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
-    "d3f_tsdf_integrate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _f,
-                                _f, _vp, _vp, _vp]),
-    "d3f_tsdf_integrate_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _f, _f, _vp, _vp, _vp]),
-    "d3f_tsdf_integrate_into": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _f, _f, _vp, _vp, _vp]),
-    "d3f_tsdf_integrate_into_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _f, _f, _vp, _vp, _vp]),
     "d3f_tsdf_extract_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_extract_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
@@ -251,14 +256,6 @@ SIGNATURES = {
     "d3f_tsdf_sparse_index_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_sparse_index": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_sparse_index_host": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
-    "d3f_tsdf_sparse_integrate": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f,
-                                       _f, _vp, _vp, _vp]),
-    "d3f_tsdf_sparse_integrate_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
-                                            _f, _f, _vp, _vp]),
-    "d3f_tsdf_sparse_integrate_into": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
-                                            _f, _f, _vp, _vp, _vp]),
-    "d3f_tsdf_sparse_integrate_into_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                 C.c_int64, _f, _f, _vp, _vp]),
     "d3f_tsdf_sparse_extract_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_sparse_extract_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _sz,
                                            _vp]),
@@ -279,14 +276,6 @@ SIGNATURES = {
                                   C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
                                        C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_tsdf_integrate_color": (_i, _TSDF_COLOR_INTEGRATE),
-    "d3f_tsdf_integrate_color_host": (_i, _TSDF_COLOR_INTEGRATE),
-    "d3f_tsdf_integrate_color_into": (_i, _TSDF_COLOR_INTEGRATE),
-    "d3f_tsdf_integrate_color_into_host": (_i, _TSDF_COLOR_INTEGRATE),
-    "d3f_tsdf_sparse_integrate_color": (_i, _TSDF_COLOR_SPARSE + [_vp]),
-    "d3f_tsdf_sparse_integrate_color_host": (_i, _TSDF_COLOR_SPARSE),
-    "d3f_tsdf_sparse_integrate_color_into": (_i, _TSDF_COLOR_SPARSE + [_vp]),
-    "d3f_tsdf_sparse_integrate_color_into_host": (_i, _TSDF_COLOR_SPARSE),
     "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
     "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
@@ -312,6 +301,7 @@ SIGNATURES = {
     "d3f_poison_gradient_if_status": (_i, [_vp, _vp, _vp, _vp]),
 }
 
+SIGNATURES.update(_tsdf_integrate_signatures())
 SIGNATURES.update(_tsdf_reader_signatures())
 
 ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failure"}

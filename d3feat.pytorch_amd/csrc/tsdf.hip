@@ -1,22 +1,15 @@
-// TSDF fusion of depth frames into a batch of dense volumes and the extraction of their zero crossings
-// (include/d3feat_hip.h: d3f_tsdf_bounds, d3f_tsdf_integrate, d3f_tsdf_extract; the rule is csrc/tsdf.hpp).
+// The bounds of the depth frames of a batch of dense TSDF volumes and the extraction of the volumes' zero crossings
+// (include/d3feat_hip.h: d3f_tsdf_bounds, d3f_tsdf_extract; the rule is csrc/tsdf.hpp).  The integration between the
+// two, d3f_tsdf_integrate, is csrc/tsdf_integrate.hip.
 //   bounds     one workgroup per 2048 pixels of one frame: the frame and its volume are workgroup-uniform, a wave folds
 //              its keys by shuffles and one lane issues six integer min / max atomics on the ordered keys (exact, so
 //              the order of arrival cannot matter).
-//   integrate  one thread owns one voxel for ALL frames of its volume, lanes along ix: the volume is read never and
-//              written once with coalesced stores, no atomics, deterministic by construction.  The volume is
-//              blockIdx.y, uniform by construction: its frame range, the frame loop, the frame matrices and the
-//              intrinsics live in scalar registers and come through scalar loads; the depth images are gathered
-//              (neighbouring ix project to neighbouring pixels; 50 frames of 640 x 480 uint16 are 30 MB).
-//              d3f_tsdf_integrate_into is the same kernel with one difference: the thread first reads the (D, w) its
-//              voxel holds and continues the running mean from it; a volume that owns no frame is left alone.
 //   extract    count per block of 256 voxels -> exclusive scan of the block counts in two levels (groups of 1024
 //              counts, coalesced, then the group totals) -> emit, which recomputes the crossings and writes at
 //              group offset + block offset + in-block rank (ballots + a prefix over the four waves).  No atomic
 //              decides a position.
 // The host twins run the same tsdf.hpp text on the CPU and make no GPU call.
 #include "tsdf_batch.hpp"   // the batch, the frames, locate(), the argument checks, the two-level scan
-#include "tsdf_color.hpp"   // the colour fused beside D and w
 
 namespace {
 
@@ -99,163 +92,6 @@ void bounds_host(const DepthT* images, int F, int H, int W, const int32_t* frame
       bounds[6 * (size_t)v + 3 + r] = order_value(hi[r]);
     }
   }
-}
-
-// ------------------------------------------------------------------------------------------------------- integrate
-// kInto: D and w come in holding the voxel's stored value and the frames continue from it (d3f_tsdf_integrate_into).
-// kCc > 0: c [kCc] is the voxel's colour, fused beside D and w from the colour frames (tsdf_color.hpp)
-template <typename DepthT, bool kInto = false, int kCc = 0>
-__host__ __device__ inline void fuse_voxel(const Volumes& b, const Frames& fr, int v, int64_t local, float& D,
-                                           float& w, const float* colours = nullptr, float* c = nullptr) {
-  int ix, iy, iz, nx, ny, nz;
-  locate(b, v, local, ix, iy, iz, nx, ny, nz);
-  int f0 = fr.frame_start[v], f1 = fr.frame_start[v + 1];
-  if (f0 < 0) f0 = 0;
-  if (f1 > fr.F) f1 = fr.F;
-  const float voxel = b.voxel[v];
-  const float x = lattice(b.origin[3 * v], voxel, ix), y = lattice(b.origin[3 * v + 1], voxel, iy);
-  const float z = lattice(b.origin[3 * v + 2], voxel, iz);
-  if constexpr (kCc > 0) {
-    if (kInto)
-      integrate_voxel_color_into<kCc>(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, colours, fr.H, fr.W,
-                                      fr.depth_scale, fr.depth_max, fr.trunc[v], D, w, c);
-    else
-      integrate_voxel_color<kCc>(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, colours, fr.H, fr.W,
-                                 fr.depth_scale, fr.depth_max, fr.trunc[v], D, w, c);
-  } else if (kInto) {
-    integrate_voxel_into(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale,
-                         fr.depth_max, fr.trunc[v], D, w);
-  } else {
-    integrate_voxel(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale, fr.depth_max,
-                    fr.trunc[v], D, w);
-  }
-}
-
-// grid (blocks of the largest volume, V): the volume is blockIdx.y, so everything indexed by it is uniform
-// kInto: the voxel's thread reads its stored (D, w) first and continues from it; a volume that owns no frame in the
-// call is left alone
-template <typename DepthT, bool kInto = false>
-__global__ void __launch_bounds__(kThreads) integrate_kernel(Volumes b, Frames fr, float* __restrict__ D_out,
-                                                             float* __restrict__ w_out) {
-  const int v = (int)blockIdx.y;
-  const int64_t start = b.vol_start[v], count = b.vol_start[v + 1] - start;
-  const int64_t local = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (local >= count || start < 0 || start + local >= b.total) return;
-  float D, w;
-  if (kInto) {
-    if (fr.frame_start[v + 1] <= fr.frame_start[v]) return;
-    D = D_out[start + local];
-    w = w_out[start + local];
-  }
-  fuse_voxel<DepthT, kInto>(b, fr, v, local, D, w);
-  D_out[start + local] = D;
-  w_out[start + local] = w;
-}
-
-// the same launch with kCc colour channels: the thread also owns its voxel's row of C_out [total, kCc] (a wave writes
-// 64 kCc consecutive floats) and gathers the colour of the 2 x 2 pixels around its projection
-template <typename DepthT, bool kInto, int kCc>
-__global__ void __launch_bounds__(kThreads) integrate_color_kernel(Volumes b, Frames fr,
-                                                                   const float* __restrict__ colours,
-                                                                   float* __restrict__ D_out,
-                                                                   float* __restrict__ w_out,
-                                                                   float* __restrict__ C_out) {
-  const int v = (int)blockIdx.y;
-  const int64_t start = b.vol_start[v], count = b.vol_start[v + 1] - start;
-  const int64_t local = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (local >= count || start < 0 || start + local >= b.total) return;
-  float D, w, c[kCc];
-  if (kInto) {
-    if (fr.frame_start[v + 1] <= fr.frame_start[v]) return;
-    D = D_out[start + local];
-    w = w_out[start + local];
-#pragma unroll
-    for (int ch = 0; ch < kCc; ++ch) c[ch] = C_out[(start + local) * kCc + ch];
-  }
-  fuse_voxel<DepthT, kInto, kCc>(b, fr, v, local, D, w, colours, c);
-  D_out[start + local] = D;
-  w_out[start + local] = w;
-#pragma unroll
-  for (int ch = 0; ch < kCc; ++ch) C_out[(start + local) * kCc + ch] = c[ch];
-}
-
-template <typename DepthT, bool kInto>
-void launch_integrate(const dim3& grid, const Volumes& b, const Frames& fr, int channels, const float* colours,
-                      float* D, float* w, float* Cv, hipStream_t s) {
-  if (channels == 1)
-    integrate_color_kernel<DepthT, kInto, 1><<<grid, kThreads, 0, s>>>(b, fr, colours, D, w, Cv);
-  else if (channels == 3)
-    integrate_color_kernel<DepthT, kInto, 3><<<grid, kThreads, 0, s>>>(b, fr, colours, D, w, Cv);
-  else
-    integrate_kernel<DepthT, kInto><<<grid, kThreads, 0, s>>>(b, fr, D, w);
-}
-
-// channels 0: no colour; 1 or 3: colours [F, H, W, channels] and Cv [total, channels] are needed
-bool colour_ok(int channels, int F, const float* colours, const float* Cv) {
-  if (channels == 0) return true;
-  return (channels == 1 || channels == 3) && (F == 0 || colours) && Cv;
-}
-
-template <bool kInto>
-int run_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                  const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                  const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-                  const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
-                  void* stream, int channels = 0, const float* colours = nullptr, float* Cv = nullptr) {
-  if (!batch_ok(V, total_voxels) || max_volume_voxels < 0 || max_volume_voxels > total_voxels || !vol_start ||
-      !origin || !dims || !voxel || !trunc ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (total_voxels == 0 || max_volume_voxels == 0) return D3F_OK;
-  const int64_t blocks = voxel_blocks(max_volume_voxels);
-  if (!D || !w || blocks > 0x7fffffff || !colour_ok(channels, F, colours, Cv)) return D3F_EINVAL;
-  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const dim3 grid((unsigned)blocks, (unsigned)V);
-  if (depth_is_f32)
-    launch_integrate<float, kInto>(grid, b, fr, channels, colours, D, w, Cv, (hipStream_t)stream);
-  else
-    launch_integrate<uint16_t, kInto>(grid, b, fr, channels, colours, D, w, Cv, (hipStream_t)stream);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
-}
-
-template <typename DepthT, bool kInto>
-void fuse_voxel_host(const Volumes& b, const Frames& fr, int v, int64_t g, int channels, const float* colours, float* D,
-                     float* w, float* Cv) {
-  const int64_t local = g - b.vol_start[v];
-  if (channels == 1)
-    fuse_voxel<DepthT, kInto, 1>(b, fr, v, local, D[g], w[g], colours, Cv + g);
-  else if (channels == 3)
-    fuse_voxel<DepthT, kInto, 3>(b, fr, v, local, D[g], w[g], colours, Cv + 3 * g);
-  else
-    fuse_voxel<DepthT, kInto>(b, fr, v, local, D[g], w[g]);
-}
-
-template <bool kInto>
-int run_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                       const int64_t* vol_start, int V, int64_t total_voxels, const float* intrinsics,
-                       const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel,
-                       const float* trunc, float depth_scale, float depth_max, float* D, float* w, int channels = 0,
-                       const float* colours = nullptr, float* Cv = nullptr) {
-  if (!batch_ok(V, total_voxels) || !vol_start || !origin || !dims || !voxel || !trunc ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (total_voxels == 0) return D3F_OK;
-  if (!D || !w || !host_layout_ok(vol_start, dims, V, total_voxels) || !colour_ok(channels, F, colours, Cv))
-    return D3F_EINVAL;
-  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  for (int v = 0; v < V; ++v) {
-    if (kInto && frame_start[v + 1] <= frame_start[v]) continue;
-    for (int64_t g = vol_start[v]; g < vol_start[v + 1]; ++g) {
-      if (depth_is_f32)
-        fuse_voxel_host<float, kInto>(b, fr, v, g, channels, colours, D, w, Cv);
-      else
-        fuse_voxel_host<uint16_t, kInto>(b, fr, v, g, channels, colours, D, w, Cv);
-    }
-  }
-  return D3F_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------- extract
@@ -393,90 +229,6 @@ int d3f_tsdf_bounds_host(const void* depth, int depth_is_f32, int F, int H, int 
     bounds_host((const uint16_t*)depth, F, H, W, frame_start, V, intrinsics, camera_to_volume, depth_scale, depth_max,
                 bounds);
   return D3F_OK;
-}
-
-int d3f_tsdf_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
-    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
-    float depth_scale, float depth_max, float* D, float* w, void* stream) {
-  return run_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
-                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream);
-}
-
-int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
-    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
-    float depth_scale, float depth_max, float* D, float* w, void* stream) {
-  (void)stream;
-  (void)max_volume_voxels;
-  return run_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
-                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w);
-}
-
-int d3f_tsdf_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
-    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
-    float depth_scale, float depth_max, float* D, float* w, void* stream) {
-  return run_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
-                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream);
-}
-
-int d3f_tsdf_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-    const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels, const float* intrinsics,
-    const float* volume_to_camera, const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
-    float depth_scale, float depth_max, float* D, float* w, void* stream) {
-  (void)stream;
-  (void)max_volume_voxels;
-  return run_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
-                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w);
-}
-
-int d3f_tsdf_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
-    void* stream) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
-                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream,
-                       channels, color, Cv);
-}
-
-int d3f_tsdf_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
-    void* stream) {
-  (void)stream;
-  (void)max_volume_voxels;
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
-                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, channels, color,
-                            Cv);
-}
-
-int d3f_tsdf_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
-    void* stream) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels,
-                       intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, stream,
-                       channels, color, Cv);
-}
-
-int d3f_tsdf_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
-    void* stream) {
-  (void)stream;
-  (void)max_volume_voxels;
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, intrinsics,
-                            volume_to_camera, origin, dims, voxel, trunc, depth_scale, depth_max, D, w, channels, color,
-                            Cv);
 }
 
 size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels) {

@@ -1,15 +1,16 @@
-// TSDF fusion of depth frames into dense volumes and the extraction of their zero crossings (tsdf.hip; d3f_tsdf_bounds,
-// d3f_tsdf_integrate, d3f_tsdf_extract and their host twins).  Everything here is __host__ __device__ and reads no
-// state: the kernels and the host twins run this text, and ops.tsdf_numpy / tsdf_extract_numpy restate it.  All
-// arithmetic is f32 in exactly the order written; the library is built with -ffp-contract=off and f32 division is
-// correctly rounded on both sides, so device, host twin and NumPy agree bit for bit.
+// TSDF fusion of depth frames into dense volumes and the extraction of their zero crossings (tsdf.hip: d3f_tsdf_bounds,
+// d3f_tsdf_extract; tsdf_integrate.hip: d3f_tsdf_integrate, dense and sparse; and their host twins).  Everything here
+// is __host__ __device__ and reads no state: the kernels and the host twins run this text, and ops.tsdf_numpy /
+// tsdf_extract_numpy restate it.  All arithmetic is f32 in exactly the order written; the library is built with
+// -ffp-contract=off and f32 division is correctly rounded on both sides, so device, host twin and NumPy agree bit for
+// bit.
 //
 // Volume v: a lattice nx x ny x nz (ix fastest in memory) with origin[3] and a voxel size, in some frame; lattice point
 // (ix, iy, iz) = origin_a + voxel * f32(i_a).  It owns the frames [frame_start[v], frame_start[v + 1]).
 // Frame f: a depth image H x W (uint16 raw units or f32 metres), intrinsics K = (fx, fy, cx, cy), M [3x4 row-major]
 // mapping the volume's frame into the camera, C [3x4] its inverse (camera into the volume's frame; the bounds only).
 //
-// Integration, per voxel (x, y, z), frames in order, from D = 0, w = 0:
+// Integration, per voxel (x, y, z), frames in order, from D = 0, w = 0 or from the stored values (the _into forms):
 //   p_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3]                      r = 0, 1, 2
 //   skip unless p_z > 0
 //   u = floorf(((fx p_x) / p_z + cx) + 0.5f), v likewise with fy, p_y, cy;  skip unless 0 <= u < W and 0 <= v < H
@@ -17,6 +18,10 @@
 //   d = f32(raw) / depth_scale (uint16) | raw (f32);  skip unless d > 0;  skip if d > depth_max
 //   sdf = d - p_z;  skip if sdf < -trunc;  t = fminf(1, sdf / trunc)
 //   D = (D w + t) / (w + 1);  w = w + 1
+// With colour (kCc = 1 or 3; tsdf_color.hpp), before D and w and with the w from before the increment, per channel
+//   c = (c w + c_pixel) / (w + 1),  c_pixel = colour_pixel() at the unrounded projection
+// integrate_frame<kCc> is the one frame body and integrate_voxel<kCc> the one frame loop of every form: dense and
+// sparse, from zero and continued, with colour and without (kCc = 0 reads and computes nothing of the colour).
 //
 // Bounds, per valid pixel (u, v) (d > 0 and not d > depth_max) of a volume's frames:
 //   X = ((f32(u) - cx) d) / fx,  Y = ((f32(v) - cy) d) / fy,  q_r = ((C[r][0] X + C[r][1] Y) + C[r][2] d) + C[r][3]
@@ -48,7 +53,7 @@ D3F_HD inline float depth_value(const float* image, size_t i, float) { return im
 D3F_HD inline float lattice(float origin, float voxel, int i) { return origin + voxel * (float)i; }
 
 // what one frame observes at one voxel: false when the frame skips it; else t, and (uf, vf), the voxel's projection
-// whose rounding names the depth pixel that was read (tsdf_color.hpp reads the colour there)
+// whose rounding names the depth pixel that was read (colour_pixel reads the colour there)
 template <typename DepthT>
 D3F_HD inline bool observe_frame(float x, float y, float z, const float* M, const float* K, const DepthT* image, int H,
                                  int W, float depth_scale, float depth_max, float trunc, float& t, float& uf, float& vf) {
@@ -69,37 +74,54 @@ D3F_HD inline bool observe_frame(float x, float y, float z, const float* M, cons
   return true;
 }
 
-// one frame into one voxel
-template <typename DepthT>
+// the colour frame colour [H, W, kCc] at the projection (uf, vf) of an observed voxel, bilinear over the 2 x 2 pixels
+// around it, each index clamped into the image (the rule is tsdf_color.hpp's): cp [kCc]
+template <int kCc>
+D3F_HD inline void colour_pixel(const float* colour, int H, int W, float uf, float vf, float* cp) {
+  // observed: -0.5 <= uf < W - 0.5 and likewise vf, so the conversions to int are safe
+  const float u0 = floorf(uf), v0 = floorf(vf);
+  const float a = uf - u0, b = vf - v0;
+  const int iu = (int)u0, iv = (int)v0;
+  const size_t c0 = (size_t)(iu < 0 ? 0 : iu), c1 = (size_t)(iu + 1 < W ? iu + 1 : W - 1);
+  const size_t r0 = (size_t)(iv < 0 ? 0 : iv) * (size_t)W, r1 = (size_t)(iv + 1 < H ? iv + 1 : H - 1) * (size_t)W;
+#pragma unroll
+  for (int ch = 0; ch < kCc; ++ch) {
+    const float c00 = colour[(r0 + c0) * kCc + ch], c01 = colour[(r0 + c1) * kCc + ch];
+    const float c10 = colour[(r1 + c0) * kCc + ch], c11 = colour[(r1 + c1) * kCc + ch];
+    cp[ch] = (c00 * (1.0f - a) + c01 * a) * (1.0f - b) + (c10 * (1.0f - a) + c11 * a) * b;
+  }
+}
+
+// one frame into one voxel.  kCc colour channels: colour [H, W, kCc] is the frame's colour image and c [kCc] the
+// voxel's colour, updated with the w from before the increment; kCc = 0: no colour, neither is touched
+template <int kCc, typename DepthT>
 D3F_HD inline void integrate_frame(float x, float y, float z, const float* M, const float* K, const DepthT* image,
-                                   int H, int W, float depth_scale, float depth_max, float trunc, float& D, float& w) {
+                                   const float* colour, int H, int W, float depth_scale, float depth_max, float trunc,
+                                   float& D, float& w, float* c) {
   float t, uf, vf;
   if (!observe_frame(x, y, z, M, K, image, H, W, depth_scale, depth_max, trunc, t, uf, vf)) return;
+  if constexpr (kCc > 0) {
+    float cp[kCc];
+    colour_pixel<kCc>(colour, H, W, uf, vf, cp);
+#pragma unroll
+    for (int ch = 0; ch < kCc; ++ch) c[ch] = (c[ch] * w + cp[ch]) / (w + 1.0f);
+  }
   D = (D * w + t) / (w + 1.0f);
   w = w + 1.0f;
 }
 
-// the frames [f0, f1) of a volume into the voxel at (x, y, z), continuing from the (D, w) given; images [F, H, W],
-// M [F, 12], K [F, 4].  The running mean is sequential over the frames, so the frames [f0, k) from (0, 0) and then
-// [k, f1) from their result give exactly what [f0, f1) gives from (0, 0) (d3f_tsdf_integrate_into).
-template <typename DepthT>
-D3F_HD inline void integrate_voxel_into(float x, float y, float z, int f0, int f1, const float* M, const float* K,
-                                        const DepthT* images, int H, int W, float depth_scale, float depth_max,
-                                        float trunc, float& D, float& w) {
+// the frames [f0, f1) of a volume into the voxel at (x, y, z), continuing from the (D, w, c) given; images [F, H, W],
+// colours [F, H, W, kCc], M [F, 12], K [F, 4].  "From D = 0, w = 0, c = 0" is the caller passing zeros.  The running
+// mean is sequential over the frames, so the frames [f0, k) from zeros and then [k, f1) from their result give exactly
+// what [f0, f1) gives from zeros (the _into entry points)
+template <int kCc, typename DepthT>
+D3F_HD inline void integrate_voxel(float x, float y, float z, int f0, int f1, const float* M, const float* K,
+                                   const DepthT* images, const float* colours, int H, int W, float depth_scale,
+                                   float depth_max, float trunc, float& D, float& w, float* c) {
   const size_t pixels = (size_t)H * (size_t)W;
   for (int f = f0; f < f1; ++f)
-    integrate_frame(x, y, z, M + 12 * (size_t)f, K + 4 * (size_t)f, images + pixels * (size_t)f, H, W, depth_scale,
-                    depth_max, trunc, D, w);
-}
-
-// all frames [f0, f1) of a volume into the voxel at (x, y, z), from D = 0, w = 0
-template <typename DepthT>
-D3F_HD inline void integrate_voxel(float x, float y, float z, int f0, int f1, const float* M, const float* K,
-                                   const DepthT* images, int H, int W, float depth_scale, float depth_max,
-                                   float trunc, float& D, float& w) {
-  D = 0.0f;
-  w = 0.0f;
-  integrate_voxel_into(x, y, z, f0, f1, M, K, images, H, W, depth_scale, depth_max, trunc, D, w);
+    integrate_frame<kCc>(x, y, z, M + 12 * (size_t)f, K + 4 * (size_t)f, images + pixels * (size_t)f,
+                         colours + pixels * (size_t)f * kCc, H, W, depth_scale, depth_max, trunc, D, w, c);
 }
 
 // the volume of global voxel g / of frame f: the last v with start[v] <= i (start rises; empty ranges are skipped)

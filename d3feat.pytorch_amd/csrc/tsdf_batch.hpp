@@ -1,7 +1,8 @@
 // What the tsdf*.hip files share beyond the rules of tsdf.hpp and tsdf_sparse.hpp: the batch of volumes and its
-// frames, the position of a voxel in its lattice, the argument checks (dense and sparse), and the two-level exclusive
-// scan of per-block counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block
-// rank).  Included by .hip files only.
+// frames (Volumes, beside Bricks the two models tsdf_integrate.hip and tsdf_raycast.hip are templated on), the position
+// of a voxel in its lattice, the argument checks (dense and sparse), and the two-level exclusive scan of per-block
+// counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by
+// .hip files only.
 #pragma once
 #include "common.hpp"
 #include "tsdf.hpp"

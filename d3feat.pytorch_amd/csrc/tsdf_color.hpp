@@ -1,5 +1,6 @@
-// Colour in TSDF volumes: fused beside D and w, sampled at points and carried by the ray-caster (tsdf.hip,
-// tsdf_sparse.hip, tsdf_raycast.hip; the d3f_tsdf_*_color entry points and their host twins).  Stated in the terms of tsdf.hpp, tsdf_sparse.hpp and tsdf_raycast.hpp, which it includes:
+// Colour in TSDF volumes: fused beside D and w, sampled at points and carried by the ray-caster (tsdf_integrate.hip,
+// tsdf_raycast.hip; the d3f_tsdf_*_color entry points and their host twins).  Stated in the terms of tsdf.hpp,
+// tsdf_sparse.hpp and tsdf_raycast.hpp, which it includes:
 // everything here is __host__ __device__ and reads no state, all arithmetic is f32 in exactly the order written
 // (-ffp-contract=off, correctly rounded division), and ops.tsdf_numpy(color=) / tsdf_sample_color_numpy /
 // tsdf_raycast_numpy(color=) restate it, so device, host twin and NumPy agree bit for bit.  A NaN is a NaN: which of
@@ -14,8 +15,8 @@
 // intensity_grey (rgbd_odometry.hpp) for Cc = 1 -- level 0 of the tracker's intensity pyramid, so the model holds what
 // the tracker compares.
 //
-// Integration.  On exactly the frames where integrate_frame updates D and w (observe_frame is true), with the w from
-// BEFORE the increment, per channel
+// Integration (the text is tsdf.hpp's: integrate_frame<kCc> and colour_pixel<kCc>).  On exactly the frames where
+// integrate_frame updates D and w (observe_frame is true), with the w from BEFORE the increment, per channel
 //   c = (c w + c_pixel) / (w + 1)
 // then D and w as tsdf.hpp has them.  There is no second weight: w is the weight of the colour too, and D and w are
 // those of the colourless integration bit for bit.
@@ -28,9 +29,10 @@
 //   not, because a voxel is not a pixel: at voxel 0.02 and 16.7 mm pixels the nearest pixel's colour sits up to half
 //   a pixel off the voxel, the offsets do not average out (a mean of 0.1 pixel = 1.7 mm where the two pitches are
 //   6 : 5), and an RGB-D tracker finds that offset between a frame and the render of the model.
-// A non-finite colour value in any of the four taps propagates into the voxel's colour; it is a value, never an index.  Continuing (integrate_voxel_color_into) starts from the stored (D, w, c) as
-// integrate_voxel_into does, so the frames [0, k) and then [k, F) give the colour of one call bit for bit.  A slot of
-// a sparse pool that does not exist, like a voxel of an absent brick, is w = 0 with colour 0.
+// A non-finite colour value in any of the four taps propagates into the voxel's colour; it is a value, never an index.
+// Continuing (the _color_into entry points) starts integrate_voxel from the stored (D, w, c), so the frames [0, k) and
+// then [k, F) give the colour of one call bit for bit.  A slot of a sparse pool that does not exist, like a voxel of
+// an absent brick, is w = 0 with colour 0.
 //
 // color_at(sampler, colour, q, min_weight, out[Cc]): the colour at a point q of the volume's frame.
 //   g_a = (q_a - origin_a) / voxel.  OUTSIDE unless 0 <= g_a <= f32(n_a - 1) on all three axes, compared as floats
@@ -50,59 +52,6 @@
 #include "tsdf_raycast_sparse.hpp"
 
 namespace d3f {
-namespace tsdf {
-
-// one frame into one voxel with kCc colour channels: colour [H, W, kCc] is the frame's image, c [kCc] the voxel's
-template <int kCc, typename DepthT>
-D3F_HD inline void integrate_frame_color(float x, float y, float z, const float* M, const float* K,
-                                         const DepthT* image, const float* colour, int H, int W, float depth_scale,
-                                         float depth_max, float trunc, float& D, float& w, float* c) {
-  float t, uf, vf;
-  if (!observe_frame(x, y, z, M, K, image, H, W, depth_scale, depth_max, trunc, t, uf, vf)) return;
-  // observed: -0.5 <= uf < W - 0.5 and likewise vf, so the conversions to int are safe
-  const float u0 = floorf(uf), v0 = floorf(vf);
-  const float a = uf - u0, b = vf - v0;
-  const int iu = (int)u0, iv = (int)v0;
-  const size_t c0 = (size_t)(iu < 0 ? 0 : iu), c1 = (size_t)(iu + 1 < W ? iu + 1 : W - 1);
-  const size_t r0 = (size_t)(iv < 0 ? 0 : iv) * (size_t)W, r1 = (size_t)(iv + 1 < H ? iv + 1 : H - 1) * (size_t)W;
-#pragma unroll
-  for (int ch = 0; ch < kCc; ++ch) {
-    const float c00 = colour[(r0 + c0) * kCc + ch], c01 = colour[(r0 + c1) * kCc + ch];
-    const float c10 = colour[(r1 + c0) * kCc + ch], c11 = colour[(r1 + c1) * kCc + ch];
-    const float cp = (c00 * (1.0f - a) + c01 * a) * (1.0f - b) + (c10 * (1.0f - a) + c11 * a) * b;
-    c[ch] = (c[ch] * w + cp) / (w + 1.0f);
-  }
-  D = (D * w + t) / (w + 1.0f);
-  w = w + 1.0f;
-}
-
-// the frames [f0, f1) into the voxel at (x, y, z), continuing from the (D, w, c) given; colours [F, H, W, kCc]
-template <int kCc, typename DepthT>
-D3F_HD inline void integrate_voxel_color_into(float x, float y, float z, int f0, int f1, const float* M, const float* K,
-                                              const DepthT* images, const float* colours, int H, int W,
-                                              float depth_scale, float depth_max, float trunc, float& D, float& w,
-                                              float* c) {
-  const size_t pixels = (size_t)H * (size_t)W;
-  for (int f = f0; f < f1; ++f)
-    integrate_frame_color<kCc>(x, y, z, M + 12 * (size_t)f, K + 4 * (size_t)f, images + pixels * (size_t)f,
-                               colours + pixels * (size_t)f * kCc, H, W, depth_scale, depth_max, trunc, D, w, c);
-}
-
-// the same from D = 0, w = 0, c = 0
-template <int kCc, typename DepthT>
-D3F_HD inline void integrate_voxel_color(float x, float y, float z, int f0, int f1, const float* M, const float* K,
-                                         const DepthT* images, const float* colours, int H, int W, float depth_scale,
-                                         float depth_max, float trunc, float& D, float& w, float* c) {
-  D = 0.0f;
-  w = 0.0f;
-#pragma unroll
-  for (int ch = 0; ch < kCc; ++ch) c[ch] = 0.0f;
-  integrate_voxel_color_into<kCc>(x, y, z, f0, f1, M, K, images, colours, H, W, depth_scale, depth_max, trunc, D, w,
-                                  c);
-}
-
-}  // namespace tsdf
-
 namespace raycast {
 
 D3F_HD inline float color_nan() { return tsdf::bits_float(0x7fc00000u); }

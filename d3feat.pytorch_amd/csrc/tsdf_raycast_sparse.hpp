@@ -1,5 +1,5 @@
 // Ray-casting a sparse TSDF volume, growing its bricks and continuing its integration (tsdf_raycast.hip:
-// d3f_tsdf_raycast_sparse and its host twin; tsdf_sparse.hip: d3f_tsdf_sparse_integrate_into).  Stated in the terms of
+// d3f_tsdf_raycast_sparse and its host twin; tsdf_integrate.hip: d3f_tsdf_sparse_integrate_into).  Stated in the terms of
 // tsdf_raycast.hpp and tsdf_sparse.hpp, which it includes: everything here is __host__ __device__ and reads no state,
 // all arithmetic is f32 in the order written there, and ops.tsdf_raycast_sparse_numpy restates it.
 //

@@ -1,22 +1,16 @@
 // Sparse TSDF volumes: bricks of 8 x 8 x 8 voxels allocated only where a depth pixel can reach within the truncation
-// distance (include/d3feat_hip.h: d3f_tsdf_sparse_mark, _index, _integrate, _extract; the rule is
-// csrc/tsdf_sparse.hpp).
+// distance (include/d3feat_hip.h: d3f_tsdf_sparse_mark, _index, _extract; the rule is csrc/tsdf_sparse.hpp).  The
+// integration into the allocated bricks, d3f_tsdf_sparse_integrate, is csrc/tsdf_integrate.hip.
 //   mark       one workgroup per 1024 pixels of one frame: the frame, its volume, K and C are workgroup-uniform and
 //              come through scalar loads; a lane flags the bricks of its pixel's box with plain stores of 1
 //              (idempotent: no atomic decides anything; a flag that is already set is not written again).
 //   index      the flags are the counts of the two-level scan of tsdf_batch.hpp (groups of 1024 lattice bricks), then
 //              one thread per lattice brick writes its rank (or -1), its coordinates at its pool row, and the volume's
 //              first row.
-//   integrate  one workgroup per allocated brick, so the volume, its frame range and the frame matrices are uniform as
-//              in tsdf.hip's integrate_kernel; lanes along ix (a wave is one z plane of the brick), each thread owns
-//              slots t and t + 256 for ALL frames: the pool is read never and written once, contiguously, no atomics.
-//              d3f_tsdf_sparse_integrate_into is the same kernel with one difference: the thread first reads the (D, w)
-//              its slots hold and continues the running mean from them; a volume without a frame is left alone.
 //   extract    tsdf.hip's count -> scan -> emit over blocks of 256 pool slots (two per brick); the +1 neighbour across
 //              a brick face is found through brick_index.  No atomic decides a position.
 // The host twins run the same tsdf_sparse.hpp text on the CPU and make no GPU call.
-#include "tsdf_batch.hpp"
-#include "tsdf_color.hpp"    // includes tsdf_sparse.hpp; the colour fused beside D and w
+#include "tsdf_batch.hpp"    // includes tsdf_sparse.hpp
 
 namespace {
 
@@ -98,95 +92,6 @@ __global__ void __launch_bounds__(kThreads) sparse_index_kernel(const int32_t* _
   const int64_t row = group_offset[l / kScanThreads] + block_offset[l];
   brick_index[l] = (int32_t)(row - first);
   if (row >= 0 && row < L) brick_position(dims + 3 * (size_t)v, l - ls, brick_coord + 3 * row);
-}
-
-// ------------------------------------------------------------------------------------------------------- integrate
-// D and w of slot s of pool row b.  kInto: D and w come in holding the slot's stored values and the frames continue
-// from them (d3f_tsdf_sparse_integrate_into); a slot beyond dims is left as it is
-template <typename DepthT, bool kInto = false, int kCc = 0>
-__host__ __device__ inline void fuse_slot(const Bricks& k, const Frames& fr, int v, int64_t b, int s, float& D,
-                                          float& w, const float* colours = nullptr, float* c = nullptr) {
-  int i[3];
-  if (!kInto) {
-    D = 0.0f;
-    w = 0.0f;
-#pragma unroll
-    for (int ch = 0; ch < kCc; ++ch) c[ch] = 0.0f;
-  }
-  if (!slot_voxel(k.dims + 3 * (size_t)v, k.brick_coord + 3 * (size_t)b, s, i)) return;
-  int f0 = fr.frame_start[v], f1 = fr.frame_start[v + 1];
-  if (f0 < 0) f0 = 0;
-  if (f1 > fr.F) f1 = fr.F;
-  const float voxel = k.voxel[v];
-  const float x = lattice(k.origin[3 * v], voxel, i[0]), y = lattice(k.origin[3 * v + 1], voxel, i[1]);
-  const float z = lattice(k.origin[3 * v + 2], voxel, i[2]);
-  if constexpr (kCc > 0) {
-    if (kInto)
-      integrate_voxel_color_into<kCc>(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, colours, fr.H, fr.W,
-                                      fr.depth_scale, fr.depth_max, fr.trunc[v], D, w, c);
-    else
-      integrate_voxel_color<kCc>(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, colours, fr.H, fr.W,
-                                 fr.depth_scale, fr.depth_max, fr.trunc[v], D, w, c);
-  } else if (kInto) {
-    integrate_voxel_into(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale,
-                         fr.depth_max, fr.trunc[v], D, w);
-  } else {
-    integrate_voxel(x, y, z, f0, f1, fr.M, fr.K, (const DepthT*)fr.images, fr.H, fr.W, fr.depth_scale, fr.depth_max,
-                    fr.trunc[v], D, w);
-  }
-}
-
-// grid (B): the brick is blockIdx.x, so its volume and everything indexed by it are uniform.  kInto: the slot's thread
-// reads its stored (D, w) first and continues from it; the rows of a volume that owns no frame in the call are left alone
-template <typename DepthT, bool kInto = false>
-__global__ void __launch_bounds__(kThreads) sparse_integrate_kernel(Bricks k, Frames fr, float* __restrict__ D_out,
-                                                                    float* __restrict__ w_out) {
-  const int64_t b = (int64_t)blockIdx.x;
-  if (b >= k.B) return;
-  const int v = owner(k.brick_start, k.V, b);
-  if (kInto && fr.frame_start[v + 1] <= fr.frame_start[v]) return;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int s = half * kThreads + (int)threadIdx.x;
-    float D, w;
-    if (kInto) {
-      D = D_out[b * kBrickVoxels + s];
-      w = w_out[b * kBrickVoxels + s];
-    }
-    fuse_slot<DepthT, kInto>(k, fr, v, b, s, D, w);
-    D_out[b * kBrickVoxels + s] = D;
-    w_out[b * kBrickVoxels + s] = w;
-  }
-}
-
-// the same launch with kCc colour channels (tsdf_color.hpp): the thread also owns its slot's row of C_out [B, 512, kCc]
-template <typename DepthT, bool kInto, int kCc>
-__global__ void __launch_bounds__(kThreads) sparse_integrate_color_kernel(Bricks k, Frames fr,
-                                                                          const float* __restrict__ colours,
-                                                                          float* __restrict__ D_out,
-                                                                          float* __restrict__ w_out,
-                                                                          float* __restrict__ C_out) {
-  const int64_t b = (int64_t)blockIdx.x;
-  if (b >= k.B) return;
-  const int v = owner(k.brick_start, k.V, b);
-  if (kInto && fr.frame_start[v + 1] <= fr.frame_start[v]) return;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int s = half * kThreads + (int)threadIdx.x;
-    const int64_t at = b * kBrickVoxels + s;
-    float D, w, c[kCc];
-    if (kInto) {
-      D = D_out[at];
-      w = w_out[at];
-#pragma unroll
-      for (int ch = 0; ch < kCc; ++ch) c[ch] = C_out[at * kCc + ch];
-    }
-    fuse_slot<DepthT, kInto, kCc>(k, fr, v, b, s, D, w, colours, c);
-    D_out[at] = D;
-    w_out[at] = w;
-#pragma unroll
-    for (int ch = 0; ch < kCc; ++ch) C_out[at * kCc + ch] = c[ch];
-  }
 }
 
 // --------------------------------------------------------------------------------------------------------- extract
@@ -298,87 +203,6 @@ void mark_host(const Frames& fr, const Bricks& k, int32_t* flags) {
   }
 }
 
-template <typename DepthT, bool kInto>
-void launch_sparse_integrate(int64_t bricks, const Bricks& k, const Frames& fr, int channels, const float* colours,
-                             float* D, float* w, float* Cp, hipStream_t s) {
-  if (channels == 1)
-    sparse_integrate_color_kernel<DepthT, kInto, 1><<<(unsigned)bricks, kThreads, 0, s>>>(k, fr, colours, D, w, Cp);
-  else if (channels == 3)
-    sparse_integrate_color_kernel<DepthT, kInto, 3><<<(unsigned)bricks, kThreads, 0, s>>>(k, fr, colours, D, w, Cp);
-  else
-    sparse_integrate_kernel<DepthT, kInto><<<(unsigned)bricks, kThreads, 0, s>>>(k, fr, D, w);
-}
-
-// channels 0: no colour; 1 or 3: colours [F, H, W, channels] and Cp [B, 512, channels] are needed
-bool colour_ok(int channels, int F, const float* colours, const float* Cp) {
-  if (channels == 0) return true;
-  return (channels == 1 || channels == 3) && (F == 0 || colours) && Cp;
-}
-
-template <bool kInto>
-int run_sparse_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
-                         const float* intrinsics, const float* volume_to_camera, const float* origin,
-                         const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-                         const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
-                         float* w, void* stream, int channels = 0, const float* colours = nullptr,
-                         float* Cp = nullptr) {
-  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (bricks == 0) return D3F_OK;
-  if (!D || !w || !brick_coord || !colour_ok(channels, F, colours, Cp)) return D3F_EINVAL;
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
-  if (depth_is_f32)
-    launch_sparse_integrate<float, kInto>(bricks, k, fr, channels, colours, D, w, Cp, (hipStream_t)stream);
-  else
-    launch_sparse_integrate<uint16_t, kInto>(bricks, k, fr, channels, colours, D, w, Cp, (hipStream_t)stream);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
-}
-
-template <typename DepthT, bool kInto>
-void fuse_slot_host(const Bricks& k, const Frames& fr, int v, int64_t b, int s, int channels, const float* colours,
-                    float* D, float* w, float* Cp) {
-  const int64_t at = b * kBrickVoxels + s;
-  if (channels == 1)
-    fuse_slot<DepthT, kInto, 1>(k, fr, v, b, s, D[at], w[at], colours, Cp + at);
-  else if (channels == 3)
-    fuse_slot<DepthT, kInto, 3>(k, fr, v, b, s, D[at], w[at], colours, Cp + 3 * at);
-  else
-    fuse_slot<DepthT, kInto>(k, fr, v, b, s, D[at], w[at]);
-}
-
-template <bool kInto>
-int run_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                              int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-                              const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
-                              float* w, int channels = 0, const float* colours = nullptr, float* Cp = nullptr) {
-  if (!batch_ok(V, bricks) || bricks > 0x7fffffff || !origin || !dims || !voxel || !trunc || !brick_start ||
-      !frames_ok(depth, F, H, W, frame_start, intrinsics, volume_to_camera, depth_scale, depth_max))
-    return D3F_EINVAL;
-  if (bricks == 0) return D3F_OK;
-  if (!D || !w || !brick_coord || brick_start[0] != 0 || brick_start[V] != bricks ||
-      !colour_ok(channels, F, colours, Cp))
-    return D3F_EINVAL;
-  for (int v = 0; v < V; ++v)
-    if (brick_start[v + 1] < brick_start[v]) return D3F_EINVAL;
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
-  for (int v = 0; v < V; ++v) {
-    if (kInto && frame_start[v + 1] <= frame_start[v]) continue;      // a volume without a frame keeps its rows
-    for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
-      for (int s = 0; s < kBrickVoxels; ++s) {
-        if (depth_is_f32)
-          fuse_slot_host<float, kInto>(k, fr, v, b, s, channels, colours, D, w, Cp);
-        else
-          fuse_slot_host<uint16_t, kInto>(k, fr, v, b, s, channels, colours, D, w, Cp);
-      }
-  }
-  return D3F_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -468,91 +292,6 @@ int d3f_tsdf_sparse_index_host(const int32_t* flags, const int64_t* lattice_star
   }
   brick_start[V] = row;
   return D3F_OK;
-}
-
-int d3f_tsdf_sparse_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                              int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-                              const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
-                              float* w, void* stream) {
-  return run_sparse_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
-                                     dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
-                                     stream);
-}
-
-int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W,
-                                   const int32_t* frame_start, int V, const float* intrinsics,
-                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
-                                   const float* voxel, const float* trunc, const int64_t* brick_start,
-                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                   float* D, float* w) {
-  return run_sparse_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
-                                          origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
-                                          depth_max, D, w);
-}
-
-int d3f_tsdf_sparse_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W,
-                                   const int32_t* frame_start, int V, const float* intrinsics,
-                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
-                                   const float* voxel, const float* trunc, const int64_t* brick_start,
-                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                   float* D, float* w, void* stream) {
-  return run_sparse_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
-                                    dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
-                                    stream);
-}
-
-int d3f_tsdf_sparse_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W,
-                                        const int32_t* frame_start, int V, const float* intrinsics,
-                                        const float* volume_to_camera, const float* origin, const int32_t* dims,
-                                        const float* voxel, const float* trunc, const int64_t* brick_start,
-                                        const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                        float* D, float* w) {
-  return run_sparse_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
-                                         origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
-                                         depth_max, D, w);
-}
-
-int d3f_tsdf_sparse_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
-    void* stream) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_sparse_integrate<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
-                                     dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
-                                     stream, channels, color, Cp);
-}
-
-int d3f_tsdf_sparse_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_sparse_integrate_host<false>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
-                                          origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
-                                          depth_max, D, w, channels, color, Cp);
-}
-
-int d3f_tsdf_sparse_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
-    void* stream) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_sparse_integrate<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin,
-                                     dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale, depth_max, D, w,
-                                     stream, channels, color, Cp);
-}
-
-int d3f_tsdf_sparse_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp) {
-  if (channels != 1 && channels != 3) return D3F_EINVAL;
-  return run_sparse_integrate_host<true>(depth, depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera,
-                                          origin, dims, voxel, trunc, brick_start, brick_coord, bricks, depth_scale,
-                                          depth_max, D, w, channels, color, Cp);
 }
 
 size_t d3f_tsdf_sparse_extract_ws_bytes(int64_t bricks) {

@@ -3362,33 +3362,48 @@ def _tsdf_into(into, total, device, channels=0, what="voxels"):
     return tuple(into)
 
 
-def _tsdf_integrate(fn, name, device, stream, depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel,
-                    trunc, depth_scale, depth_max, into=None, color=None):
+def _tsdf_integrate(host, device, depth, frame_start, intrinsics, volume_to_camera, volumes, trunc, depth_scale,
+                    depth_max, into, color):
+    """Every integrate form, d3f_tsdf[_sparse]_integrate[_color][_into][_host].  ``volumes``: ``(origin, dims, voxel)``
+    of dense volumes, or a ``SparseVolumes``; what depends on which is the tables in the argument list and the shape
+    of the outputs."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
+    sparse = isinstance(volumes, SparseVolumes)
+    if sparse and V != volumes.volumes:
+        raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, volumes.volumes))
+    origin, dims, voxel = (volumes.origin, volumes.dims, volumes.voxel) if sparse else volumes
     o, n, vx, tr, vol_start = _tsdf_volumes(origin, dims, voxel, V, trunc)
-    total = int(vol_start[-1])
     c = None if color is None else tsdf_color_frames(color, d.shape)
     Cc = 0 if c is None else c.shape[-1]
-    td, tfs, tK, tM, to, tn, tvx, ttr, tvs = _on(device, d, fs, K, M, o, n, vx, tr, vol_start)
-    if into is None:
-        D = torch.empty(total, dtype=torch.float32, device=device)
-        w = torch.empty(total, dtype=torch.float32, device=device)
-        Cv = torch.empty((total, Cc), dtype=torch.float32, device=device) if Cc else None
+    td, tfs, tK, tM, ttr = _on(device, d, fs, K, M, tr)
+    if sparse:
+        _, bs, _, bc, to, tn, tvx = _sparse_tables(volumes, device)
+        B = volumes.bricks
+        shape, what = (B, TSDF_BRICK_VOXELS), "slots of the allocated bricks"
+        head, tail = (V,), (_p(bs), _p(bc) if B else None, B)
     else:
-        D, w, Cv = (_tsdf_into(into, total, device, Cc) + (None,))[:3]
-    if Cc or into is not None:       # d3f_tsdf_integrate[_color][_into][_host]
-        name = name.replace("integrate", "integrate" + ("_color" if Cc else "") + ("" if into is None else "_into"))
-        fn = getattr(_native.lib(), name)
-    rest = (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), _p(tvs), V, total,
-            int(np.diff(vol_start).max()), _p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr), float(depth_scale),
-            float(depth_max), _p(D), _p(w))
-    if Cc:
-        tc = _on(device, c)[0]
-        _native.check(fn(*((_p(td), _p(tc), Cc) + rest + (_p(Cv), stream))), name)
-        return D, w, tvs, Cv
-    _native.check(fn(*((_p(td),) + rest + (stream,))), name)
-    return D, w, tvs
+        to, tn, tvx, tvs = _on(device, o, n, vx, vol_start)
+        shape, what = (int(vol_start[-1]),), "voxels"
+        head, tail = (_p(tvs), V, shape[0], int(np.diff(vol_start).max())), ()
+    cells = int(np.prod(shape))
+    if into is None:
+        D = torch.empty(shape, dtype=torch.float32, device=device)
+        w = torch.empty(shape, dtype=torch.float32, device=device)
+        Cv = torch.empty(shape + (Cc,), dtype=torch.float32, device=device) if Cc else None
+    else:
+        D, w, Cv = (_tsdf_into(into, cells, device, Cc, what) + (None,))[:3]
+    ptr = _p if cells else (lambda t: None)
+    name = ("d3f_tsdf" + ("_sparse" if sparse else "") + "_integrate" + ("_color" if Cc else "") +
+            ("" if into is None else "_into") + ("_host" if host else ""))
+    tc = _on(device, c)[0] if Cc else None
+    args = ((_p(td),) + ((_p(tc), Cc) if Cc else ()) +
+            (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs)) + head +
+            (_p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr)) + tail +
+            (float(depth_scale), float(depth_max), ptr(D), ptr(w)) + ((ptr(Cv),) if Cc else ()) +
+            (() if sparse and host else (None if host else _stream(),)))     # the sparse twins take no stream
+    _native.check(getattr(_native.lib(), name)(*args), name)
+    return (D, w) + (() if sparse else (tvs,)) + ((Cv,) if Cc else ())
 
 
 def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale=1000.0,
@@ -3415,18 +3430,16 @@ def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dim
     call's bit for bit.  A non-finite colour value propagates into the voxels that have it among their four.  ``into=(D, w, Cv)`` continues all three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate"):
-        return _tsdf_integrate(_native.lib().d3f_tsdf_integrate, "d3f_tsdf_integrate", dev, _stream(), depth,
-                               frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                               depth_max, into, color)
+        return _tsdf_integrate(False, dev, depth, frame_start, intrinsics, volume_to_camera, (origin, dims, voxel),
+                               trunc, depth_scale, depth_max, into, color)
 
 
 def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc,
                         depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host / d3f_tsdf_integrate_into_host and their _color
     forms): CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
-    return _tsdf_integrate(_native.lib().d3f_tsdf_integrate_host, "d3f_tsdf_integrate_host", torch.device("cpu"), None,
-                           depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc, depth_scale,
-                           depth_max, into, color)
+    return _tsdf_integrate(True, torch.device("cpu"), depth, frame_start, intrinsics, volume_to_camera,
+                           (origin, dims, voxel), trunc, depth_scale, depth_max, into, color)
 
 
 def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
@@ -3513,9 +3526,9 @@ def _lattice_axes(local, n, o, vx):
 
 
 def _tsdf_fuse_numpy(xyz, d, K, M, f0, f1, trunc, depth_scale, depth_max, start=None, colour=None):
-    """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1);
-    ``start = (D, w)``: integrate_voxel_into, continuing from these values.  ``colour`` f32 [F,H,W,Cc]:
-    integrate_voxel_color of csrc/tsdf_color.hpp, ``start = (D, w, c)``, and (D, w, c [n,Cc]) is returned."""
+    """integrate_voxel of csrc/tsdf.hpp for the f32 lattice points ``xyz = (x, y, z)`` over the frames [f0, f1), from
+    zero; ``start = (D, w)``: continuing from these values.  ``colour`` f32 [F,H,W,Cc]: integrate_voxel<Cc> (the
+    colour rule is csrc/tsdf_color.hpp), ``start = (D, w, c)``, and (D, w, c [n,Cc]) is returned."""
     x, y, z = xyz
     H, W = d.shape[1:]
     f32 = np.float32
@@ -3815,42 +3828,6 @@ def _sparse_tables(sv, device):
     return tls, bs, bi, bc, to, tn, tvx
 
 
-def _tsdf_integrate_sparse(host, device, stream, depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
-                           depth_scale, depth_max, into=None, color=None):
-    d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
-    V = fs.size - 1
-    if V != sv.volumes:
-        raise ValueError("frame_start names %d volumes, the sparse volumes are %d" % (V, sv.volumes))
-    tr = _tsdf_volumes(sv.origin, sv.dims, sv.voxel, V, trunc)[3]
-    c = None if color is None else tsdf_color_frames(color, d.shape)
-    Cc = 0 if c is None else c.shape[-1]
-    td, tfs, tK, tM, ttr = _on(device, d, fs, K, M, tr)
-    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, device)
-    B = sv.bricks
-    name = "d3f_tsdf_sparse_integrate" + ("_color" if Cc else "")
-    if into is None:
-        D = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
-        w = torch.empty((B, TSDF_BRICK_VOXELS), dtype=torch.float32, device=device)
-        Cp = torch.empty((B, TSDF_BRICK_VOXELS, Cc), dtype=torch.float32, device=device) if Cc else None
-    else:
-        D, w, Cp = (_tsdf_into(into, B * TSDF_BRICK_VOXELS, device, Cc, "slots of the allocated bricks") + (None,))[:3]
-        name += "_into"                                            # d3f_tsdf_sparse_integrate[_color]_into[_host]
-    args = (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs), V, _p(tK), _p(tM), _p(to),
-            _p(tn), _p(tvx), _p(ttr), _p(bs), _p(bc) if B else None, B, float(depth_scale), float(depth_max),
-            _p(D) if B else None, _p(w) if B else None)
-    if Cc:
-        tc = _on(device, c)[0]
-        args = (_p(td), _p(tc), Cc) + args + (_p(Cp) if B else None,)
-    else:
-        args = (_p(td),) + args
-    L = _native.lib()
-    if host:
-        _native.check(getattr(L, name + "_host")(*args), name + "_host")
-    else:
-        _native.check(getattr(L, name)(*(args + (stream,))), name)
-    return (D, w, Cp) if Cc else (D, w)
-
-
 def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
                           depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """Fuse depth frames into the allocated bricks of ``sv`` in ONE launch (d3f_tsdf_sparse_integrate): device tensors
@@ -3868,16 +3845,16 @@ def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, 
     holds the dense ``Cv`` of that voxel bit for bit, every other slot 0.  ``into=(D, w, Cp)`` continues all three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate_sparse"):
-        return _tsdf_integrate_sparse(False, dev, _stream(), depth, frame_start, intrinsics, volume_to_camera, sv,
-                                      trunc, depth_scale, depth_max, into, color)
+        return _tsdf_integrate(False, dev, depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale,
+                               depth_max, into, color)
 
 
 def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
                                depth_max=TSDF_DEPTH_MAX, into=None, color=None):
     """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host / d3f_tsdf_sparse_integrate_into_host):
     CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
-    return _tsdf_integrate_sparse(True, torch.device("cpu"), None, depth, frame_start, intrinsics, volume_to_camera,
-                                  sv, trunc, depth_scale, depth_max, into, color)
+    return _tsdf_integrate(True, torch.device("cpu"), depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
+                           depth_scale, depth_max, into, color)
 
 
 def _sparse_pool(D, w, sv, device):

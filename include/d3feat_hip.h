@@ -1035,7 +1035,8 @@ int d3f_pose_graph_edge_host(const double* Pi_host, const double* Pj_host, const
 
 /* ------------------------------------------------------------------------------------------------
  * TSDF fusion of depth frames into a batch of V dense volumes, and the extraction of their zero crossings as point
- * clouds (csrc/tsdf.hpp states the rule in full; the reference has no such step).
+ * clouds (csrc/tsdf.hpp states the rule in full; the reference has no such step).  Bounds and extraction are
+ * csrc/tsdf.hip, the integration csrc/tsdf_integrate.hip.
  * Volume v: lattice dims[v] = (nx, ny, nz), ix fastest; origin[v][3], voxel[v], trunc[v]; its voxels are
  * [vol_start[v], vol_start[v+1]) of D / w (vol_start int64 [V+1] from 0 to total_voxels; every dim >= 1); it owns the
  * frames [frame_start[v], frame_start[v+1]) (an empty range leaves the volume at D = 0, w = 0).
@@ -1079,7 +1080,7 @@ int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, i
                             const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
                             float depth_max, float* D, float* w, void* stream);
 /* d3f_tsdf_integrate_into: the same kernel body, but every voxel's thread first reads the (D, w) stored in the volume
- *   and continues the running mean from it (tsdf.hpp: integrate_voxel_into).  The mean is sequential over frames, so
+ *   and continues the running mean from it (tsdf.hpp: integrate_voxel).  The mean is sequential over frames, so
  *   integrating the frames [0, k) and then [k, F) into the result gives the volume of one call over [0, F) bit for
  *   bit.  A volume that owns no frame in the call keeps its values. */
 int d3f_tsdf_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
@@ -1325,7 +1326,9 @@ int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* 
  * voxel's projection (indices clamped into the image); D and w are the colourless call's bit for bit.
  *
  * d3f_tsdf_integrate_color / _into extend d3f_tsdf_integrate / d3f_tsdf_integrate_into: the same arguments and launch
- * shape plus `color`, `channels` and `Cv` (written once by the voxel's thread; _into continues from the stored rows). */
+ * shape plus `color`, `channels` and `Cv` (written once by the voxel's thread; _into continues from the stored rows).
+ * All sixteen integrate entry points, dense and sparse, are one kernel body and one host function in
+ * csrc/tsdf_integrate.hip; the colourless ones are its channels = 0 form. */
 int d3f_tsdf_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
     const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
     const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,

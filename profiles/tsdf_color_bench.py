@@ -2,9 +2,10 @@
 of 640 x 480 of the analytic room scaled 2.4 times, voxel 0.006 m, about 2 x 10^8 voxels -- painted with the analytic
 texture ``tex`` of tests/rgbd_cases.py:
 
-  * d3f_tsdf_integrate against d3f_tsdf_integrate_color with 1 and 3 channels;
+  * d3f_tsdf_integrate against d3f_tsdf_integrate_color with 1 and 3 channels, and the _into forms of both without
+    colour and with 3 channels;
   * d3f_tsdf_sparse_integrate against d3f_tsdf_sparse_integrate_color with 1 and 3 channels, on the bricks of the same
-    fragment;
+    fragment, and their _into forms likewise;
   * ops.tsdf_raycast of 1 view and of 16 views of 640 x 480, without colour and with a 1- and a 3-channel volume;
   * ops.tsdf_sample_color on the extracted cloud, 1 and 3 channels.
 
@@ -107,14 +108,21 @@ def main():
     rest = (0, F, H, W, p(tfs), p(tvs), 1, total, total, p(tK), p(tM), p(to), p(tn), p(tvx), p(ttr), 1000.0,
             ops.TSDF_DEPTH_MAX, p(D), p(w))
 
-    def dense(c):
+    def dense(c, into=""):
         if c == 0:
-            return lambda: _native.check(L.d3f_tsdf_integrate(*((p(td),) + rest + (stream,))), "d3f_tsdf_integrate")
-        return lambda: _native.check(L.d3f_tsdf_integrate_color(*((p(td), p(tc[c]), c) + rest + (p(Cv[c]), stream))),
-                                     "d3f_tsdf_integrate_color")
+            fn = getattr(L, "d3f_tsdf_integrate" + into)
+            return lambda: _native.check(fn(*((p(td),) + rest + (stream,))), "d3f_tsdf_integrate" + into)
+        fn = getattr(L, "d3f_tsdf_integrate_color" + into)
+        return lambda: _native.check(fn(*((p(td), p(tc[c]), c) + rest + (p(Cv[c]), stream))),
+                                     "d3f_tsdf_integrate_color" + into)
     ms = take_turns({"Cc = %d" % c: dense(c) for c in (0, 1, 3)})
     report(out, "integrate (d3f_tsdf_integrate / d3f_tsdf_integrate_color), one launch", ms, "Cc = 0",
            {"Cc = %d" % c: "writes %.2f GB" % ((8 + 4 * c) * 1e-9 * total) for c in (0, 1, 3)})
+    ms = take_turns({"Cc = %d" % c: dense(c, "_into") for c in (0, 3)})      # continues what the arms above left
+    report(out, "integrate into (d3f_tsdf_integrate_into / d3f_tsdf_integrate_color_into), one launch", ms, "Cc = 0",
+           {"Cc = %d" % c: "reads and writes %.2f GB" % ((8 + 4 * c) * 1e-9 * total) for c in (0, 3)})
+    for c in (0, 1, 3):                                  # the ray-cast and the sampling below read a volume fused once
+        dense(c)()
 
     # ------------------------------------------------------------------------------------------- sparse integrate
     sv = ops.tsdf_allocate(depth, [0, F], TB.K, C, origin, dims, VOXEL, trunc)
@@ -127,17 +135,20 @@ def main():
     srest = (0, F, H, W, p(tfs), 1, p(tK), p(tM), p(so), p(sn), p(svx), p(ttr), p(bs), p(bc), B, 1000.0,
              ops.TSDF_DEPTH_MAX, p(Dp), p(wp))
 
-    def sparse(c):
+    def sparse(c, into=""):
         if c == 0:
-            return lambda: _native.check(L.d3f_tsdf_sparse_integrate(*((p(td),) + srest + (stream,))),
-                                         "d3f_tsdf_sparse_integrate")
-        return lambda: _native.check(L.d3f_tsdf_sparse_integrate_color(*((p(td), p(tc[c]), c) + srest +
-                                                                         (p(Cp[c]), stream))),
-                                     "d3f_tsdf_sparse_integrate_color")
+            fn = getattr(L, "d3f_tsdf_sparse_integrate" + into)
+            return lambda: _native.check(fn(*((p(td),) + srest + (stream,))), "d3f_tsdf_sparse_integrate" + into)
+        fn = getattr(L, "d3f_tsdf_sparse_integrate_color" + into)
+        return lambda: _native.check(fn(*((p(td), p(tc[c]), c) + srest + (p(Cp[c]), stream))),
+                                     "d3f_tsdf_sparse_integrate_color" + into)
     ms = take_turns({"Cc = %d" % c: sparse(c) for c in (0, 1, 3)})
     report(out, "sparse integrate, %d bricks of %d (%.1f %% of the lattice)" % (B, int(sv.lattice_start[-1]),
                                                                               100.0 * B / int(sv.lattice_start[-1])),
            ms, "Cc = 0", {"Cc = %d" % c: "writes %.3f GB" % ((8 + 4 * c) * 1e-9 * slots) for c in (0, 1, 3)})
+    ms = take_turns({"Cc = %d" % c: sparse(c, "_into") for c in (0, 3)})
+    report(out, "sparse integrate into, the same bricks", ms, "Cc = 0",
+           {"Cc = %d" % c: "reads and writes %.3f GB" % ((8 + 4 * c) * 1e-9 * slots) for c in (0, 3)})
 
     # -------------------------------------------------------------------------------------------------- ray-cast
     for views in (1, VIEWS):

@@ -3,8 +3,8 @@
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined d3feat.pytorch_amd/csrc/tsdf.hip \
-//         d3feat.pytorch_amd/csrc/tsdf_raycast.hip tests/raycast_host_twins.cpp -o /tmp/raycast_host_twins \
-//         && /tmp/raycast_host_twins
+//         d3feat.pytorch_amd/csrc/tsdf_integrate.hip d3feat.pytorch_amd/csrc/tsdf_raycast.hip \
+//         tests/raycast_host_twins.cpp -o /tmp/raycast_host_twins && /tmp/raycast_host_twins
 //
 // Two volumes of different dims (13 x 9 x 7 and 5 x 1 x 4, the second without a cell along y) are fused from two frames
 // of 37 x 23 by d3f_tsdf_integrate_host, and again as one frame followed by d3f_tsdf_integrate_into_host; the two must

@@ -1,19 +1,24 @@
-// A stand-alone program for the host twins of the sparse ray-caster and of the continued sparse integration under the
-// host sanitizers (no GPU call is made, and nothing here is loaded into Python).  Build and run from the repository root:
+// A stand-alone program for the host twins of the sparse ray-caster, of the continued sparse integration and of the
+// colour integration (dense and sparse) under the host sanitizers (no GPU call is made, and nothing here is loaded into Python).  Build and run from the repository root:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined d3feat.pytorch_amd/csrc/tsdf.hip \
-//         d3feat.pytorch_amd/csrc/tsdf_sparse.hip d3feat.pytorch_amd/csrc/tsdf_raycast.hip \
+//         d3feat.pytorch_amd/csrc/tsdf_integrate.hip d3feat.pytorch_amd/csrc/tsdf_sparse.hip \
+//         d3feat.pytorch_amd/csrc/tsdf_raycast.hip \
 //         tests/raycast_sparse_host_twins.cpp -o /tmp/raycast_sparse_host_twins && /tmp/raycast_sparse_host_twins
 //
 // Two volumes of different dims (13 x 9 x 7: 2 x 2 x 1 lattice bricks with borders at index 7 | 8 on two axes, and
 // 5 x 1 x 4, without a cell along y) go through d3f_tsdf_sparse_mark_host, _index_host and _integrate_host over two
 // frames of 37 x 23 each, and again as one frame followed by d3f_tsdf_sparse_integrate_into_host; the two pools must
-// agree bit for bit.  d3f_tsdf_raycast_sparse_host then renders six views in the order 1, 0, 1, 0, 0, 0 -- among them a
+// agree bit for bit.  The colour forms follow with 1 and 3 channels, dense (d3f_tsdf_integrate_color_host) and sparse
+// (d3f_tsdf_sparse_integrate_color_host): the whole call against two frames followed by the other two through the
+// _color_into_host forms, bit for bit on D, w and the colour, D and w those of the colourless calls, and the pool's
+// colour that of the dense volume.  d3f_tsdf_raycast_sparse_host then renders six views in the order 1, 0, 1, 0, 0, 0 -- among them a
 // pose holding a NaN, a pose holding an infinity and a camera far outside -- with the skip and the clip on and off, with
 // and without normals, at min_weight 1 and 0, and all must equal d3f_tsdf_raycast_host on the pool scattered into dense
 // volumes, bit for bit; then again with two of the bricks taken out of the tables.
-// Every buffer is sized exactly (the pool to the allocated bricks, brick_coord to them too), so a read or write past an
+// Every buffer is sized exactly (the pool to the allocated bricks, brick_coord to them too, the colour frames and
+// Cv / Cp to their channels), so a read or write past an
 // end is reported.  Exit status 0 and "ok" mean that the sanitizers saw nothing.
 #include <math.h>
 #include <stdint.h>
@@ -87,6 +92,71 @@ int main() {
     return 9;
   if (memcmp(D.data(), D2.data(), D.size() * sizeof(float)) || memcmp(w.data(), w2.data(), w.size() * sizeof(float)))
     return 10;
+
+  // colour, 1 and 3 channels, dense and sparse: the whole call against frames 0 and 2 followed by frames 1 and 3 _into
+  // the result; D and w are those of the colourless calls.  The colour frames and Cv / Cp are sized exactly
+  std::vector<float> Dv(total), wv(total), Dv2(total), wv2(total), Dc(total), wc(total), Dq(D.size()), wq(w.size());
+  if (d3f_tsdf_integrate_host(depth.data(), 1, F, H, W, both, vol_start, V, total, total, K.data(), M.data(), origin, dims,
+                              voxel, trunc, 1000.0f, 6.0f, Dv.data(), wv.data(), nullptr))
+    return 30;
+  for (int Cc = 1; Cc <= 3; Cc += 2) {
+    std::vector<float> colour((size_t)F * H * W * Cc), ca, cb;
+    for (size_t i = 0; i < colour.size(); ++i) colour[i] = 0.5f + 0.4f * sinf(0.37f * (float)i);
+    for (int f = 0; f < F; ++f) {
+      std::vector<float>& c = f % 2 ? cb : ca;
+      c.insert(c.end(), colour.begin() + (size_t)f * H * W * Cc, colour.begin() + (size_t)(f + 1) * H * W * Cc);
+    }
+    std::vector<float> Cv((size_t)total * Cc), Cv2(Cv.size()), Cp((size_t)B * 512 * Cc), Cp2(Cp.size());
+    if (d3f_tsdf_integrate_color_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, vol_start, V, total, total, K.data(),
+                                      M.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dc.data(), wc.data(), Cv.data(),
+                                      nullptr))
+      return 31;
+    if (d3f_tsdf_integrate_color_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total, Ka.data(),
+                                      Ma.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dv2.data(), wv2.data(),
+                                      Cv2.data(), nullptr))
+      return 32;
+    if (d3f_tsdf_integrate_color_into_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total,
+                                           Kb.data(), Mb.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dv2.data(),
+                                           wv2.data(), Cv2.data(), nullptr))
+      return 33;
+    if (memcmp(Dc.data(), Dv.data(), Dv.size() * sizeof(float)) || memcmp(wc.data(), wv.data(), wv.size() * sizeof(float)) ||
+        memcmp(Dc.data(), Dv2.data(), Dv.size() * sizeof(float)) || memcmp(wc.data(), wv2.data(), wv.size() * sizeof(float)) ||
+        memcmp(Cv.data(), Cv2.data(), Cv.size() * sizeof(float)))
+      return 34;
+    if (d3f_tsdf_sparse_integrate_color_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, V, K.data(), M.data(), origin,
+                                             dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, Dq.data(),
+                                             wq.data(), Cp.data()))
+      return 35;
+    if (d3f_tsdf_sparse_integrate_color_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, V, Ka.data(), Ma.data(), origin,
+                                             dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, D2.data(),
+                                             w2.data(), Cp2.data()))
+      return 36;
+    if (d3f_tsdf_sparse_integrate_color_into_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, V, Kb.data(), Mb.data(),
+                                                  origin, dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f,
+                                                  D2.data(), w2.data(), Cp2.data()))
+      return 37;
+    if (memcmp(Dq.data(), D.data(), D.size() * sizeof(float)) || memcmp(wq.data(), w.data(), w.size() * sizeof(float)) ||
+        memcmp(Dq.data(), D2.data(), D.size() * sizeof(float)) || memcmp(wq.data(), w2.data(), w.size() * sizeof(float)) ||
+        memcmp(Cp.data(), Cp2.data(), Cp.size() * sizeof(float)))
+      return 38;
+    // a slot inside the lattice holds the dense colour of its voxel; a slot beyond dims holds 0
+    int seen = 0;
+    for (int v = 0; v < V; ++v)
+      for (int64_t b = brick_start[v]; b < brick_start[v + 1]; ++b)
+        for (int s = 0; s < 512; ++s) {
+          const int ix = coord[3 * b] * 8 + (s & 7), iy = coord[3 * b + 1] * 8 + ((s >> 3) & 7);
+          const int iz = coord[3 * b + 2] * 8 + (s >> 6);
+          const bool in = ix < dims[3 * v] && iy < dims[3 * v + 1] && iz < dims[3 * v + 2];
+          const int64_t at = vol_start[v] + ((int64_t)iz * dims[3 * v + 1] + iy) * dims[3 * v] + ix;
+          for (int ch = 0; ch < Cc; ++ch) {
+            const float c = Cp[(b * 512 + s) * Cc + ch];
+            if (in ? memcmp(&c, &Cv[at * Cc + ch], sizeof c) != 0 : c != 0.0f) return 39;
+          }
+          seen += in && wq[b * 512 + s] > 0.0f;
+        }
+    printf("colour, %d channel(s): %d coloured slots\n", Cc, seen);
+    if (!seen) return 40;
+  }
 
   // the pool scattered into dense volumes: zero outside the allocated bricks
   std::vector<float> Dd(total, 0.0f), wd(total, 0.0f);

@@ -41,6 +41,13 @@ def test_into_rejects_a_wrong_colour_volume():
     CC.check_into_errors(NUMPY)
 
 
+@pytest.mark.parametrize("f32", [False, True], ids=['uint16', 'f32'])
+@pytest.mark.parametrize("channels", [1, 3])
+def test_colour_batch_with_a_frameless_volume_under_into(channels, f32):
+    CC.check_batch_into(HOST, channels, f32)
+    CC.check_batch_into(NUMPY, channels, f32)
+
+
 @pytest.mark.parametrize("name,channels", [(n, 1 + 2 * (i % 2)) for i, n in enumerate(CC.INTEGRATION_CASES)])
 def test_sparse_pool_holds_the_dense_colour(name, channels):
     CC.check_sparse(HOST, name, channels)

@@ -43,6 +43,15 @@ def test_into_rejects_a_wrong_colour_volume():
     CC.check_into_errors(DEVICE)
 
 
+@pytest.mark.parametrize("f32", [False, True], ids=['uint16', 'f32'])
+@pytest.mark.parametrize("channels", [1, 3])
+def test_colour_batch_with_a_frameless_volume_under_into(channels, f32):
+    whole, pool = CC.check_batch_into(DEVICE, channels, f32)
+    assert whole[3].is_cuda and pool[2].is_cuda
+    host = CC.batch_host(channels, f32)
+    assert all(CC.RC.same_bits(a, b) for a, b in zip((whole[0], whole[1], whole[3]), (host[0], host[1], host[3])))
+
+
 @pytest.mark.parametrize("name,channels", [(n, 1 + 2 * (i % 2)) for i, n in enumerate(CC.INTEGRATION_CASES)])
 def test_sparse_pool_holds_the_dense_colour(name, channels):
     sv, D, w, Cp = CC.check_sparse(DEVICE, name, channels)

@@ -1,4 +1,4 @@
-"""GPU: the TSDF kernels (csrc/tsdf.hip) against their host twins bit for bit -- bounds, D, w, points and point_start on
+"""GPU: the TSDF kernels (csrc/tsdf.hip, csrc/tsdf_integrate.hip) against their host twins bit for bit -- bounds, D, w, points and point_start on
 the analytic room of ``tsdf_scene`` and on every small volume -- batches against single volumes and from run to run, the
 capacity rule of the extraction, uint16 against f32 depth, and ``fuse_fragments`` on the device against the CPU path."""
 import numpy as np

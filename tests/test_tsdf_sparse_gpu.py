@@ -1,4 +1,4 @@
-"""GPU: the sparse TSDF kernels (csrc/tsdf_sparse.hip) against their host twins bit for bit -- tables, pool, points and
+"""GPU: the sparse TSDF kernels (csrc/tsdf_sparse.hip, csrc/tsdf_integrate.hip) against their host twins bit for bit -- tables, pool, points and
 point_start on the room of ``tsdf_scene`` (two fragments as one batch) and on every small volume -- batches against
 single volumes and from run to run, uint16 against f32 depth, the capacity rule of the extraction, and
 ``fuse_fragments(sparse=True)`` on the device against the CPU path."""

@@ -15,6 +15,7 @@ import odometry_cases as OC
 import raycast_cases as RCC
 import rgbd_cases as RC
 import tsdf_scene as S
+import tsdf_sparse_cases as SC
 
 arr = RC.arr
 SMALL = sorted(S.small_cases())
@@ -186,6 +187,81 @@ def check_into_errors(be):
     if be.suffix == '':                                                  # the wrong device
         with pytest.raises(ValueError):
             be.integrate(color=color, into=(D, w, Cv.cpu()), **args)
+
+
+# ---------------------------------------------------------- 2b. a batch of volumes, one of them frameless under into=
+BATCH = ('dims_13x9x7', 'partly_outside', 'brick_face_17x9x9')      # 819, 11439 (45 workgroups) and 1377 voxels
+BATCH_FIRST, BATCH_SECOND = ((0, 2, 3, 4), [0, 1, 3, 4]), ((1, 5), [0, 1, 1, 2])     # (frames, frame_start) of the split
+BATCH_OBSERVED, BATCH_TWICE = (702, 542, 813), (689, 467, 809)      # voxels per volume with w > 0; seen by both frames
+
+
+@functools.lru_cache(maxsize=None)
+def batch_inputs(channels, f32):
+    """(integrate arguments, colour, camera_to_volume) of the three volumes ``BATCH``, two frames of 37 x 23 each."""
+    case = SC.batch_of(BATCH)
+    inten = RC.small_intensity(np.asarray(case['depth']).shape)
+    return with_depth(case, f32), (inten if channels == 1 else RC.to_rgb8(inten)), case['camera_to_volume']
+
+
+def batch_frames(args, color, frames, frame_start):
+    ix = list(frames)
+    return dict(args, depth=args['depth'][ix], volume_to_camera=args['volume_to_camera'][ix],
+                frame_start=frame_start), color[ix]
+
+
+@functools.lru_cache(maxsize=None)
+def batch_reference(channels, f32):
+    """(D, w, vol_start, Cv) of the restatement for the whole call; shared."""
+    args, color, _ = batch_inputs(channels, f32)
+    return RCC.freeze(*NUMPY.integrate(color=color, **args))
+
+
+@functools.lru_cache(maxsize=None)
+def batch_host(channels, f32):
+    """The whole call through the host twin; shared."""
+    args, color, _ = batch_inputs(channels, f32)
+    return HOST.integrate(color=color, **args)
+
+
+def check_batch_into(be, channels, f32):
+    """Colour over several volumes (v > 0 in the colour row's index) and a volume without a frame under ``into=``,
+    dense and through the pool: the split call equals the whole call, which equals the restatement."""
+    args, color, C = batch_inputs(channels, f32)
+    whole = be.integrate(color=color, **args)
+    plain = be.integrate(**args)
+    ref = batch_reference(channels, f32)
+    vs = [int(x) for x in arr(whole[2])]
+    assert vs == [0, 819, 12258, 13635] and arr(whole[3]).shape == (vs[-1], channels)
+    assert RC.same_bits(whole[0], plain[0]) and RC.same_bits(whole[1], plain[1]), "colour changed D or w"
+    assert all(RC.same_bits(a, b) for a, b in zip((whole[0], whole[1], whole[3]), (ref[0], ref[1], ref[3])))
+    w = arr(whole[1])
+    assert tuple(int((w[a:b] > 0).sum()) for a, b in zip(vs, vs[1:])) == BATCH_OBSERVED
+    assert tuple(int((w[a:b] == 2).sum()) for a, b in zip(vs, vs[1:])) == BATCH_TWICE
+    a1, c1 = batch_frames(args, color, *BATCH_FIRST)
+    a2, c2 = batch_frames(args, color, *BATCH_SECOND)
+    first = be.integrate(color=c1, **a1)
+    middle = [np.array(arr(t)[vs[1]:vs[2]]) for t in (first[0], first[1], first[3])]
+    again = be.integrate(color=c2, into=(first[0], first[1], first[3]), **a2)
+    for t, m in zip((again[0], again[1], again[3]), middle):
+        assert RC.same_bits(arr(t)[vs[1]:vs[2]], m), "the volume without a frame changed"
+    assert all(RC.same_bits(a, b) for a, b in zip((again[0], again[1], again[3]), (whole[0], whole[1], whole[3])))
+    # the same through the pool
+    frames, vol, rest = sparse_args(dict(args, camera_to_volume=C))
+    sv = be.allocate(*frames, C, *vol)
+    pool = be.sparse(*frames, args['volume_to_camera'], sv, *rest, color=color)
+    p1 = be.sparse(a1['depth'], a1['frame_start'], frames[2], a1['volume_to_camera'], sv, *rest, color=c1)
+    p2 = be.sparse(a2['depth'], a2['frame_start'], frames[2], a2['volume_to_camera'], sv, *rest, color=c2, into=p1)
+    assert arr(pool[2]).shape == (sv.bricks, 512, channels)
+    assert all(RC.same_bits(a, b) for a, b in zip(p2, pool))
+    hs = host_tables(sv)
+    dense = ops.tsdf_densify(np.array(arr(pool[0])), np.array(arr(pool[1])), hs, color=np.array(arr(pool[2])))
+    inside = allocated_voxels(sv)
+    assert inside.any() and not inside.all()
+    assert (np.asarray(arr(sv.brick_coord)) * 8 + 7 >= np.repeat(sv.dims, np.diff(arr(sv.brick_start)), 0)).any(), \
+        "no brick has a slot beyond dims"
+    for got, want in zip((dense[0], dense[1], dense[3]), (ref[0], ref[1], ref[3])):
+        assert RC.same_bits(got[inside], want[inside]) and not got[~inside].any()
+    return whole, pool
 
 
 # ----------------------------------------------------------------------------------------------------- 3. sparse
