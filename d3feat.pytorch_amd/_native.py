@@ -233,6 +233,11 @@ SIGNATURES = {
     "d3f_icp_rigid_plane": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _i, _d, _d, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_icp_plane_fit_host": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "d3f_color_gradients": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_color_gradient_from_moments_host": (_i, [_vp, _d, _vp, _f, _i, _vp]),
+    "d3f_icp_rigid_color_ws_bytes": (_sz, [_i, C.c_int64]),
+    "d3f_icp_rigid_color": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _d, _i, _d, _d,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_pair_information_ws_bytes": (_sz, [_i, C.c_int64]),
     "d3f_pair_information": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _sz,
                                   _vp]),

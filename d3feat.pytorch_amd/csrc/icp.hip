@@ -36,6 +36,13 @@
 // pivots (a product of two f32 values is exact in f64 and nothing is subtracted afterwards, so there is no cancellation
 // to protect).  Setup, prefix, reduction orders and flags are ICP's (the same code: icp_setup_kernel, pair_sums); a
 // finishing launch adds the pair's block sums and writes them.  Three launches whatever the data.
+//
+// Coloured form (d3f_icp_rigid_color; kernels instantiated with kColor; color_icp.hpp has the rule).  Point-to-plane's
+// winner branch with J and r scaled by sqrt(lambda_geometric), plus a second rank-1 update with the colour row
+// J_C = sc [a x d, d], r_C = sc ((I_y - I_x) + (a - c) . d) when the matched fixed point's field (d, I_y: one 16-byte
+// read through the same index) and the moving row's intensity are finite.  31 sums: the 29, n_color and the unweighted
+// sum of squared colour residuals; the fit is kPlane's on the first 29 and reports n_color and color_rmse at the stop.
+#include "color_icp.hpp"
 #include "pair_search.hpp"
 #include "plane.hpp"
 #include "rigid.hpp"
@@ -51,7 +58,12 @@ constexpr int kRowsPerSlice = (kBlock / 64) * (64 / kG);
 constexpr int kSlices = kRows / kRowsPerSlice;
 constexpr int kPoint = 0, kPlane = 1;   // what the fit minimises
 constexpr int kInfo = 2;                // no fit: the raw moments of the accepted rows (d3f_pair_information)
-constexpr int sums_of(int kind) { return kind == kPlane ? d3f::plane::kPlaneSums : kind == kInfo ? D3F_INFO_MOMENTS : 17; }
+constexpr int kColor = 3;               // kPlane's fit over geometric and colour rows (d3f_icp_rigid_color)
+constexpr int sums_of(int kind) {
+  return kind == kPlane ? d3f::plane::kPlaneSums : kind == kInfo ? D3F_INFO_MOMENTS : kind == kColor ? d3f::color::kColorSums : 17;
+}
+// where sum d2 sits: the last sum, but for kColor, whose first 29 sums are kPlane's
+constexpr int d2_of(int kind) { return kind == kColor ? d3f::plane::kPlaneSums - 1 : sums_of(kind) - 1; }
 static_assert(kRows % kRowsPerSlice == 0, "a workgroup serves whole slices");
 
 struct IcpArgs {
@@ -77,6 +89,10 @@ struct IcpArgs {
   long long rows;
   int B, P, Ns, max_iters;
   double* moments;            // [P, D3F_INFO_MOMENTS] (kInfo)
+  const float4* field;        // [Ns] (d, I), input row order (kColor)
+  int32_t* n_color;           // [P] (kColor)
+  double* color_rmse;         // [P] (kColor)
+  double sg, sc;              // sqrt(lambda_geometric), sqrt(1 - lambda_geometric) (kColor)
 };
 
 __device__ __forceinline__ long long first_block(const IcpArgs& A, int p) { return A.row_start[p] / kRows + p; }
@@ -95,7 +111,7 @@ __device__ __forceinline__ void write_pose(double* __restrict__ o, const double*
 }
 
 // kFit: the pair is iterated (kPoint, kPlane); without it (kInfo) the flags, the copy of T and `done` are all there is
-template <bool kFit>
+template <bool kFit, bool kColorOut = false>
 __global__ void icp_setup_kernel(const IcpArgs A) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (A.trace) {
@@ -126,6 +142,10 @@ __global__ void icp_setup_kernel(const IcpArgs A) {
       write_pose(A.T + 16 * (size_t)p, A.T_init + 12 * (size_t)p);
       A.count[p] = 0;
       A.rmse[p] = 0.0;
+      if constexpr (kColorOut) {
+        A.n_color[p] = 0;
+        A.color_rmse[p] = 0.0;
+      }
     }
   }
 }
@@ -193,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
     const uint64_t best =
         nearest_in_cloud<kG>(A.S, ok, x, y, z, T, b, tgt0, tgt_n, per_cloud, cell, reach, sub, A.status + p, mine, win);
     const bool winner = ok && best != ~0ull && mine == best;   // the one lane of the group that holds the winner
-    if constexpr (kKind == kPlane) {
+    if constexpr (kKind == kPlane || kKind == kColor) {
       if (winner) {
         // a = T_k x - py in f64 (NOT the f32-rounded query: at coordinates of 300 that rounding is 3e-5 of residual
         // noise), c = y - py, nrm the matched point's normal; J = [a x nrm, nrm], r = (a - c) . nrm
@@ -203,9 +223,14 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
                              (((T[4] * x + T[5] * y) + T[6] * z) + T[7]) - py[1],
                              (((T[8] * x + T[9] * y) + T[10] * z) + T[11]) - py[2]};
         const double c[3] = {(double)win.x - py[0], (double)win.y - py[1], (double)win.z - py[2]};
-        const double J[6] = {a[1] * nrm[2] - a[2] * nrm[1], a[2] * nrm[0] - a[0] * nrm[2], a[0] * nrm[1] - a[1] * nrm[0],
-                             nrm[0], nrm[1], nrm[2]};
-        const double r = ((a[0] - c[0]) * nrm[0] + (a[1] - c[1]) * nrm[1]) + (a[2] - c[2]) * nrm[2];
+        double J[6] = {a[1] * nrm[2] - a[2] * nrm[1], a[2] * nrm[0] - a[0] * nrm[2], a[0] * nrm[1] - a[1] * nrm[0],
+                       nrm[0], nrm[1], nrm[2]};
+        double r = ((a[0] - c[0]) * nrm[0] + (a[1] - c[1]) * nrm[1]) + (a[2] - c[2]) * nrm[2];
+        if constexpr (kKind == kColor) {   // scaled before any product is formed (sg = 1 changes no bit)
+#pragma unroll
+          for (int i = 0; i < 6; ++i) J[i] *= A.sg;
+          r *= A.sg;
+        }
         acc[0] += 1.0;
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
@@ -213,7 +238,28 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
           for (int j = i; j < 6; ++j) acc[1 + d3f::plane::upper6(i, j)] += J[i] * J[j];
           acc[22 + i] += J[i] * r;
         }
-        acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
+        acc[d2_of(kKind)] += (double)__uint_as_float((uint32_t)(best >> 32));
+        if constexpr (kKind == kColor) {
+          // the colour row: the matched fixed point's (d, I_y) and the moving row's I_x (its stacked row is sa + i)
+          const float4 f = A.field[w];
+          const float ix = A.field[(size_t)(sa + i)].w;
+          if (isfinite(f.x) && isfinite(f.y) && isfinite(f.z) && isfinite(f.w) && isfinite(ix)) {
+            const double d[3] = {(double)f.x, (double)f.y, (double)f.z};
+            const double rc = ((double)f.w - (double)ix) +
+                              (((a[0] - c[0]) * d[0] + (a[1] - c[1]) * d[1]) + (a[2] - c[2]) * d[2]);
+            const double Jc[6] = {A.sc * (a[1] * d[2] - a[2] * d[1]), A.sc * (a[2] * d[0] - a[0] * d[2]),
+                                  A.sc * (a[0] * d[1] - a[1] * d[0]), A.sc * d[0], A.sc * d[1], A.sc * d[2]};
+            const double rs = A.sc * rc;
+#pragma unroll
+            for (int i2 = 0; i2 < 6; ++i2) {
+#pragma unroll
+              for (int j = i2; j < 6; ++j) acc[1 + d3f::plane::upper6(i2, j)] += Jc[i2] * Jc[j];
+              acc[22 + i2] += Jc[i2] * rs;
+            }
+            acc[d3f::plane::kPlaneSums] += 1.0;
+            acc[d3f::plane::kPlaneSums + 1] += rc * rc;
+          }
+        }
       }
     } else if constexpr (kKind == kInfo) {
       if (winner) {
@@ -229,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
             acc[13 + (r * (7 - r)) / 2 + (c - r)] += ys[r] * ys[c];
           }
         }
-        acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
+        acc[d2_of(kKind)] += (double)__uint_as_float((uint32_t)(best >> 32));
       }
     } else if (winner) {
       const double xd[3] = {x - px[0], y - px[1], z - px[2]};
@@ -244,7 +290,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
       for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[7 + 3 * r + c] += xd[r] * yd[c];
-      acc[kSums - 1] += (double)__uint_as_float((uint32_t)(best >> 32));
+      acc[d2_of(kKind)] += (double)__uint_as_float((uint32_t)(best >> 32));
     }
   }
   d3f::wave_sum_f64(acc);
@@ -261,6 +307,13 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(const IcpArgs A) {
   }
 }
 
+// n_color and color_rmse of the pose a coloured pair stops at
+__device__ __forceinline__ void write_color(const IcpArgs& A, int p, const double (&v)[d3f::color::kColorSums]) {
+  const double nc = v[d3f::plane::kPlaneSums];
+  A.n_color[p] = (int)nc;
+  A.color_rmse[p] = nc > 0.0 ? sqrt(v[d3f::plane::kPlaneSums + 1] / nc) : 0.0;
+}
+
 // one wave per pair: the pair's block sums in a fixed order, the stopping rule, the fit
 template <int kKind>
 __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter) {
@@ -272,7 +325,7 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
   pair_sums(A, p, a, lane, v);
   if (lane != 0) return;
   const int sa = A.cloud_start[a], len_a = A.cloud_start[a + 1] - sa, tgt0 = A.cloud_start[b];
-  const double n = v[0], sd2 = v[kSums - 1];
+  const double n = v[0], sd2 = v[d2_of(kKind)];
   const double fitness = len_a > 0 ? n / (double)len_a : 0.0, rmse = n > 0.0 ? sqrt(sd2 / n) : 0.0;
   if (A.trace) {
     double* tr = A.trace + 2 * ((size_t)p * (A.max_iters + 1) + k_iter);
@@ -293,6 +346,7 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
     write_pose(A.T + 16 * (size_t)p, T);
     A.count[p] = (int)n;
     A.rmse[p] = rmse;
+    if constexpr (kKind == kColor) write_color(A, p, v);
     A.done[p] = 1;
     return;
   }
@@ -302,7 +356,7 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
     px[k] = (double)A.points[3 * (size_t)sa + k];
     py[k] = (double)A.points[3 * (size_t)tgt0 + k];
   }
-  if constexpr (kKind == kPlane) {
+  if constexpr (kKind == kPlane || kKind == kColor) {
     double Tk[12], Tn[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Tk[k] = T[k];
@@ -311,6 +365,7 @@ __global__ __launch_bounds__(64) void icp_fit_kernel(const IcpArgs A, int k_iter
       write_pose(A.T + 16 * (size_t)p, T);
       A.count[p] = (int)n;
       A.rmse[p] = rmse;
+      if constexpr (kKind == kColor) write_color(A, p, v);
       A.done[p] = 1;
       return;
     }
@@ -400,7 +455,8 @@ int icp_prepare(int kind, const void* grid_ws, const float* points, int Ns, cons
 }
 
 template <int kKind>
-int icp_run(const void* grid_ws, const float* points, const float* normals, int Ns, const int32_t* cloud_start, int B,
+int icp_run(const void* grid_ws, const float* points, const float* normals, const float* field,
+            double lambda_geometric, int32_t* n_color, double* color_rmse, int Ns, const int32_t* cloud_start, int B,
             float grid_radius, float max_distance, const int32_t* pairs, const int64_t* row_start, int P, int64_t rows,
             const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T, int32_t* count,
             double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes,
@@ -408,12 +464,19 @@ int icp_run(const void* grid_ws, const float* points, const float* normals, int 
   if (max_iters < 0 || max_iters > D3F_ICP_MAX_ITERS || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0) ||
       (P > 0 && (!T || !rmse || !iterations)))
     return D3F_EINVAL;
+  if (kKind == kColor && (!(lambda_geometric >= 0.0 && lambda_geometric <= 1.0) || (P > 0 && (!n_color || !color_rmse))))
+    return D3F_EINVAL;
   IcpArgs a = {};
   long long blocks = 0;
   const int rc = icp_prepare(kKind, grid_ws, points, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
                              rows, T_init, count, status, ws, ws_bytes, a, blocks);
   if (rc != D3F_OK || P == 0) return rc;
   a.normals = normals;
+  a.field = reinterpret_cast<const float4*>(field);
+  a.n_color = n_color;
+  a.color_rmse = color_rmse;
+  a.sg = sqrt(lambda_geometric);
+  a.sc = sqrt(1.0 - lambda_geometric);
   a.T = T;
   a.rmse = rmse;
   a.iterations = iterations;
@@ -426,7 +489,7 @@ int icp_run(const void* grid_ws, const float* points, const float* normals, int 
   long long setup_blocks = ((fill > P ? fill : P) + 255) / 256;
   if (setup_blocks > 4096) setup_blocks = 4096;
   if (setup_blocks < (P + 255) / 256) setup_blocks = (P + 255) / 256;
-  icp_setup_kernel<true><<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
+  icp_setup_kernel<true, kKind == kColor><<<(unsigned)setup_blocks, 256, 0, stream>>>(a);
   D3F_LAUNCH_CHECK();
   for (int k = 0; k <= max_iters; ++k) {
     icp_search_kernel<kKind><<<(unsigned)blocks, kBlock, 0, stream>>>(a);
@@ -477,7 +540,7 @@ int d3f_icp_rigid(const void* grid_ws, const float* points, int Ns, const int32_
                   int64_t rows, const double* T_init, int max_iters, double rel_fitness, double rel_rmse, double* T,
                   int32_t* count, double* rmse, int32_t* iterations, int32_t* status, double* trace, void* ws,
                   size_t ws_bytes, void* stream_) {
-  return icp_run<kPoint>(grid_ws, points, nullptr, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+  return icp_run<kPoint>(grid_ws, points, nullptr, nullptr, 1.0, nullptr, nullptr, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
                          rows, T_init, max_iters, rel_fitness, rel_rmse, T, count, rmse, iterations, status, trace, ws,
                          ws_bytes, stream_);
 }
@@ -488,9 +551,23 @@ int d3f_icp_rigid_plane(const void* grid_ws, const float* points, const float* n
                         double rel_fitness, double rel_rmse, double* T, int32_t* count, double* rmse,
                         int32_t* iterations, int32_t* status, double* trace, void* ws, size_t ws_bytes, void* stream_) {
   if (!normals) return D3F_EINVAL;
-  return icp_run<kPlane>(grid_ws, points, normals, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
+  return icp_run<kPlane>(grid_ws, points, normals, nullptr, 1.0, nullptr, nullptr, Ns, cloud_start, B, grid_radius, max_distance, pairs, row_start, P,
                          rows, T_init, max_iters, rel_fitness, rel_rmse, T, count, rmse, iterations, status, trace, ws,
                          ws_bytes, stream_);
+}
+
+size_t d3f_icp_rigid_color_ws_bytes(int P, int64_t rows) { return icp_layout(nullptr, P, rows, kColor).bytes; }
+
+int d3f_icp_rigid_color(const void* grid_ws, const float* points, const float* normals, const float* field, int Ns,
+                        const int32_t* cloud_start, int B, float grid_radius, float max_distance, const int32_t* pairs,
+                        const int64_t* row_start, int P, int64_t rows, const double* T_init, double lambda_geometric,
+                        int max_iters, double rel_fitness, double rel_rmse, double* T, int32_t* count, double* rmse,
+                        int32_t* iterations, int32_t* status, int32_t* n_color, double* color_rmse, double* trace,
+                        void* ws, size_t ws_bytes, void* stream_) {
+  if (!normals || !field) return D3F_EINVAL;
+  return icp_run<kColor>(grid_ws, points, normals, field, lambda_geometric, n_color, color_rmse, Ns, cloud_start, B,
+                         grid_radius, max_distance, pairs, row_start, P, rows, T_init, max_iters, rel_fitness, rel_rmse,
+                         T, count, rmse, iterations, status, trace, ws, ws_bytes, stream_);
 }
 
 int d3f_icp_fit_host(const double* sums_host, const double* px_host, const double* py_host, double* out_host) {

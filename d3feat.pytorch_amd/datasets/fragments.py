@@ -711,6 +711,51 @@ def write_ply_points(filename, points, colors=None):
         f.write(rows)
 
 
+def read_ply_colors(filename):
+    """f32 [N,3] in [0, 1]: the uchar ``red green blue`` of the ``vertex`` element of a PLY file (what
+    ``write_ply_points(colors=)`` writes; ascii or binary, the vertex element first), in the row order of
+    ``read_ply_points``; None when the file carries no such colours."""
+    from .ThreeDMatch import _PLY_TYPES
+    with open(filename, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise ValueError("%s: not a PLY file" % filename)
+        fmt, n_vertex, props, element = None, None, [], None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: truncated PLY header" % filename)
+            tok = line.decode('ascii', 'replace').split()
+            if not tok or tok[0] in ('comment', 'obj_info'):
+                continue
+            if tok[0] == 'format':
+                fmt = tok[1]
+            elif tok[0] == 'element':
+                element = tok[1]
+                if element == 'vertex':
+                    n_vertex = int(tok[2])
+            elif tok[0] == 'property' and element == 'vertex':
+                if tok[1] == 'list':
+                    raise ValueError("%s: list property in the vertex element" % filename)
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == 'end_header':
+                break
+        if n_vertex is None or fmt is None:
+            raise ValueError("%s: no vertex element" % filename)
+        kinds = dict(props)
+        if any(kinds.get(c) != 'u1' for c in ('red', 'green', 'blue')):
+            return None
+        if fmt == 'ascii':
+            rows = np.loadtxt(f, max_rows=n_vertex, ndmin=2) if n_vertex else np.zeros((0, len(props)))
+            names = [n for n, _ in props]
+            rgb = np.stack([rows[:, names.index(c)] for c in ('red', 'green', 'blue')], axis=1)
+        else:
+            order = {'binary_little_endian': '<', 'binary_big_endian': '>'}[fmt]
+            dtype = np.dtype([(n, order + t) for n, t in props])
+            data = np.frombuffer(f.read(n_vertex * dtype.itemsize), dtype=dtype, count=n_vertex)
+            rgb = np.stack([data['red'], data['green'], data['blue']], axis=1)
+        return rgb.astype(np.float32) / np.float32(255.0)
+
+
 def write_ply_mesh(filename, vertices, faces, normals=None, colors=None):
     """Binary little-endian PLY of a triangle mesh: ``vertex`` with the float properties x, y, z (and nx, ny, nz when
     ``normals`` is given, and uchar red, green, blue when ``colors`` f32 [Nv, 1 or 3] in [0, 1] is) and ``face`` with

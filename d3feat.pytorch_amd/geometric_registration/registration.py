@@ -14,7 +14,9 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``refine_transforms`` / ``icp_numpy``  point-to-point ICP over the whole fragments after RANSAC (``ops.icp_rigid``, all
   pairs of a scene in one call) and its NumPy restatement -- ``estimate_transform`` / ``register_scene`` run it when
   given ``icp=dict(max_distance=...)``; ``estimation='point_to_plane'`` in that dict takes the point-to-plane form with
-  normals from ``ops.estimate_normals`` (NumPy restatement: ``estimate_normals_numpy``);
+  normals from ``ops.estimate_normals`` (NumPy restatement: ``estimate_normals_numpy``), ``estimation='colored'``
+  with ``colors=`` the coloured form (``ops.color_gradients``, ``ops.icp_rigid(color_field=)``; NumPy restatements:
+  ``color_gradients_numpy``, ``icp_numpy(color_field=)``; ``intensity_of`` turns RGB into the intensity they take);
 * ``information_matrices`` / ``information_from_moments`` / ``information_numpy`` / ``writeinfo``  the 6x6 information
   matrix of fragment pairs under given poses (``ops.pair_information``: one search, 20 raw moments per pair) -- the
   matrix ``gt.info`` holds and a pose graph takes per edge -- and the writer of ``gt.info``;
@@ -43,6 +45,9 @@ ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 
 PG_ST_ITER_CAP, PG_ST_NONFINITE, PG_ST_GRAPH, PG_ST_INDEFINITE = 1, 2, 4, 8                         # ops.PG_ST_*
 PG_LAMBDA0, PG_LAMBDA_MIN, PG_LAMBDA_MAX = 1e-4, 1e-12, 1e8    # csrc/posegraph.hpp kLambda0 / kLambdaMin / kLambdaMax
 PLANE_PIVOT = 1e-10            # csrc/plane.hpp kPlanePivot
+GRADIENT_PIVOT = 1e-6          # csrc/color_icp.hpp kGradientPivot
+INTENSITY_SCALE = 2.0 ** 20    # csrc/color_icp.hpp kIntensityScale
+LAMBDA_GEOMETRIC = 0.968       # Open3D's default weight of the geometric term; not tuned here
 
 
 def _compact(mutual, src_pts, tgt_pts):
@@ -191,13 +196,34 @@ def _plane_step(x, ym, nrm, T, py):
     """One point-to-plane fit (include/d3feat_hip.h): moving points x matched to fixed points ym with normals nrm under
     the 4x4 T, about the pivot py -> (T_next, singular).  The pivot test is the kernel's (Cholesky of the normal
     equations); the solution is a least-squares solve of the stacked system."""
+    J, r = _plane_rows(x, ym, nrm, T, py)[:2]
+    return _step_from_rows(J, r, T, py)
+
+
+def _plane_rows(x, ym, nrm, T, py):
+    """The stacked point-to-plane rows ``J [n,6]``, ``r [n]`` of include/d3feat_hip.h, and a, c."""
     R, t = T[:3, :3], T[:3, 3]
     x = x.astype(np.float64)
     a = np.stack([((R[r, 0] * x[:, 0] + R[r, 1] * x[:, 1]) + R[r, 2] * x[:, 2]) + t[r] for r in range(3)], 1) - py
     c = ym.astype(np.float64) - py
     n = nrm.astype(np.float64)
-    J = np.concatenate([np.cross(a, n), n], 1)
-    r = ((a - c) * n).sum(1)
+    return np.concatenate([np.cross(a, n), n], 1), ((a - c) * n).sum(1), a, c
+
+
+def _color_rows(a, c, fy, ix):
+    """The unweighted colour rows of the accepted correspondences (include/d3feat_hip.h): ``fy [n,4]`` the field rows of
+    the matched fixed points, ``ix [n]`` the intensities of the moving points -> ``(J_C [m,6], r_C [m])`` over the m rows
+    where ``fy`` is finite in all four entries and ``ix`` is finite."""
+    ok = np.isfinite(fy).all(1) & np.isfinite(ix)
+    d = fy[ok, :3].astype(np.float64)
+    a, c = a[ok], c[ok]
+    r = (fy[ok, 3].astype(np.float64) - ix[ok].astype(np.float64)) + ((a - c) * d).sum(1)
+    return np.concatenate([np.cross(a, d), d], 1), r
+
+
+def _step_from_rows(J, r, T, py):
+    """The fit of ``_plane_step`` on the stacked rows J, r."""
+    R, t = T[:3, :3], T[:3, 3]
     A = J.T @ J
     floor, U = PLANE_PIVOT * A.diagonal().max(), np.zeros((6, 6))
     for i in range(6):
@@ -217,8 +243,19 @@ def _plane_step(x, ym, nrm, T, py):
     return out, False
 
 
+def _per_cloud(rows, clouds, width, name):
+    """A stacked f32 array [N, width] (or one array per cloud) -> one array per cloud."""
+    if isinstance(rows, (list, tuple)):
+        return [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, width) for r in rows]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, width)
+    ends = np.cumsum([len(c) for c in clouds])
+    if rows.shape[0] != (ends[-1] if len(ends) else 0):
+        raise ValueError("%s must hold one row per stacked point" % name)
+    return [rows[e - len(c):e] for e, c in zip(ends, clouds)]
+
+
 def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6, return_trace=False,
-              normals=None):
+              normals=None, color_field=None, lambda_geometric=LAMBDA_GEOMETRIC):
     """The contract of ``ops.icp_rigid`` in NumPy f64 (include/d3feat_hip.h): the ``device='cpu'`` path of
     ``refine_transforms`` and the oracle of the GPU tests.  ``clouds``: list of [n,3] f32 arrays; pair p = (moving cloud
     a, fixed cloud b), ``T_init[p]`` maps a into b's frame.  The search is ``preprocess.transform_points`` /
@@ -226,7 +263,11 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
     quaternions.  Returns ``(T [P,4,4], count int32 [P], rmse [P], iterations int32 [P], status int32 [P])`` and, with
     ``return_trace``, ``trace [P, max_iters+1, 2]`` = (n_k, sum d2_k), NaN beyond the stop.  ``normals``: None, or
     the f32 normals of the stacked clouds [N,3] (or one array per cloud): the point-to-plane form, whose fit follows
-    ``_plane_step`` and which may end with ``ICP_ST_SINGULAR``."""
+    ``_plane_step`` and which may end with ``ICP_ST_SINGULAR``.  ``color_field``: None, or the f32 field [N,4] of
+    ``color_gradients_numpy`` / ``ops.color_gradients`` (or one array per cloud; requires ``normals``): the COLOURED
+    form -- the point-to-plane rows times ``sqrt(lambda_geometric)`` stacked with the colour rows times
+    ``sqrt(1 - lambda_geometric)`` (rows of weight zero are left out: they add nothing), the same pivot test and solve --
+    and ``n_color int32 [P]``, ``color_rmse [P]`` of the returned poses are appended to the results."""
     from ..datasets.preprocess import nearest_within, transform_points
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     P, K = pairs.shape[0], int(max_iters)
@@ -238,6 +279,15 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
         if normals.shape[0] != (ends[-1] if len(ends) else 0):
             raise ValueError("normals must hold one row per stacked point")
         normals = [normals[e - len(c):e] for e, c in zip(ends, clouds)]
+    colored = color_field is not None
+    if colored:
+        if normals is None:
+            raise ValueError("color_field requires normals")
+        if not 0.0 <= float(lambda_geometric) <= 1.0:
+            raise ValueError("lambda_geometric must be in [0, 1]")
+        field = _per_cloud(color_field, clouds, 4, "color_field")
+        sg, sc = np.sqrt(float(lambda_geometric)), np.sqrt(1.0 - float(lambda_geometric))
+    n_color, color_rmse = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.float64)
     T = _pose44(T_init, P)
     count, iters, status = (np.zeros(P, dtype=np.int32) for _ in range(3))
     rmse = np.zeros(P, dtype=np.float64)
@@ -265,6 +315,13 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
             r = float(np.sqrt(sd2 / n)) if n else 0.0
             trace[p, k] = (n, sd2)
             count[p], rmse[p] = n, r
+            if colored and n:
+                Jg, rg, av, cv = _plane_rows(x[sel], ym, normals[b][nn[sel]], T[p], y[0].astype(np.float64))
+                Jc, rc = _color_rows(av, cv, field[b][nn[sel]], field[a][sel, 3])
+                n_color[p] = len(rc)
+                color_rmse[p] = float(np.sqrt((rc * rc).sum() / len(rc))) if len(rc) else 0.0
+            elif colored:
+                n_color[p], color_rmse[p] = 0, 0.0
             if n < 3:
                 status[p] |= ICP_ST_FEW
                 break
@@ -274,7 +331,13 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
                 break
             px, py = x[0].astype(np.float64), y[0].astype(np.float64)    # pivots: row 0 of either cloud
             if normals is not None:
-                T[p], singular = _plane_step(x[sel], ym, normals[b][nn[sel]], T[p], py)
+                if colored:
+                    Jg, rg = sg * Jg, sg * rg
+                    if sc > 0.0:
+                        Jg, rg = np.concatenate([Jg, sc * Jc]), np.concatenate([rg, sc * rc])
+                    T[p], singular = _step_from_rows(Jg, rg, T[p], py)
+                else:
+                    T[p], singular = _plane_step(x[sel], ym, normals[b][nn[sel]], T[p], py)
                 if singular:
                     status[p] |= ICP_ST_SINGULAR
                     break
@@ -291,7 +354,119 @@ def icp_numpy(clouds, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-
             prev = (fitness, r)
             iters[p] = k + 1
     res = (T, count, rmse, iters, status)
-    return res + (trace,) if return_trace else res
+    res = res + (trace,) if return_trace else res
+    return res + (n_color, color_rmse) if colored else res
+
+
+def intensity_of(colors):
+    """The intensity the coloured ICP takes, f32 [N], from the colours ``fuse_fragments(color=)`` returns (array or
+    tensor; the result is of the same kind): ``[N,1]`` (or ``[N]``) passes as it is; ``[N,3]`` f32 in [0, 1] becomes
+    ``(0.299 R + 0.587 G) + 0.114 B`` in f32, the RGB-D tracker's weights; uint8 is divided by 255 as ``rgbd_pyramid``
+    does.  NaN stays NaN: "no colour"."""
+    tensor = isinstance(colors, torch.Tensor)
+    c = colors if tensor else np.asarray(colors)
+    eight = c.dtype == (torch.uint8 if tensor else np.uint8)
+    c = c.to(torch.float32) if tensor else c.astype(np.float32)
+    n = int(c.shape[0])
+    c = c.reshape(n, -1)
+    if c.shape[1] == 3:
+        w = (torch.tensor if tensor else np.float32)([0.299, 0.587, 0.114])
+        if tensor:
+            w = w.to(c.device)
+        I = (w[0] * c[:, 0] + w[1] * c[:, 1]) + w[2] * c[:, 2]
+    elif c.shape[1] == 1:
+        I = c[:, 0]
+    else:
+        raise ValueError("colors must be [N], [N,1] or [N,3], got %s" % (tuple(colors.shape),))
+    if eight:
+        I = I / 255.0 if tensor else I / np.float32(255.0)
+    return I.contiguous() if tensor else np.ascontiguousarray(I, dtype=np.float32)
+
+
+def color_gradients_numpy(clouds, radius, normals, intensity, min_neighbors=4, return_moments=False, block=1 << 21):
+    """The contract of ``ops.color_gradients`` in NumPy (include/d3feat_hip.h): ``clouds`` a list of [n,3] f32 arrays,
+    each searched on its own; ``normals`` f32 [N,3] and ``intensity`` f32 [N] over the stacked rows (or one array per
+    cloud).  Returns ``(field f32 [N,4] = (d, I), count int32 [N])`` and, with ``return_moments``, ``moments int64
+    [N,13]`` -- the integers the kernel adds, equal to the device's bit for bit; the 2x2 solve is the kernel's closed
+    form in f64.  Brute force within a window of the rows sorted by x, as ``estimate_normals_numpy``."""
+    r32 = np.float32(radius)
+    if not (0.0 < float(r32) < np.inf) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    r2, Q = r32 * r32, normals_scale(radius)
+    normals = _per_cloud(normals, clouds, 3, "normals")
+    intensity = _per_cloud(intensity, clouds, 1, "intensity")
+    fields, counts, moments = [], [], []
+    for cloud, nrm, inten in zip(clouds, normals, intensity):
+        p = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        I = inten.reshape(-1)
+        if nrm.shape[0] != n or I.shape[0] != n:
+            raise ValueError("normals and intensity must hold one row per point")
+        with np.errstate(invalid='ignore'):
+            usable = (I >= np.float32(0)) & (I <= np.float32(1))
+        q = np.where(usable, np.rint(np.where(usable, I, 0).astype(np.float64) * INTENSITY_SCALE), 0).astype(np.int64)
+        order = np.argsort(p[:, 0], kind='stable')
+        ps, qs, us = p[order], q[order], usable[order]
+        m = np.zeros((n, 13), dtype=np.int64)
+        reach = float(r32) * 1.001 + 1e-6
+        step = max(1, int(block) // max(n, 1))
+        for s in range(0, n, step):
+            qp = ps[s:s + step]
+            lo = np.searchsorted(ps[:, 0], float(qp[0, 0]) - reach, 'left')
+            hi = np.searchsorted(ps[:, 0], float(qp[-1, 0]) + reach, 'right')
+            t = ps[lo:hi]
+            d = t[None, :, :] - qp[:, None, :]                         # p_j - p_i: one f32 subtraction
+            e = qp[:, None, :] - t[None, :, :]                         # the search's p_i - p_j
+            d2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+            inside = (d2 < r2) & us[None, lo:hi] & us[s:s + step, None]
+            u = np.where(inside[..., None], np.rint(d.astype(np.float64) * Q).astype(np.int64), 0)
+            ux, uy, uz = u[..., 0], u[..., 1], u[..., 2]
+            c = np.where(inside, qs[None, lo:hi] - qs[s:s + step, None], 0)
+            m[s:s + step] = np.stack([inside.sum(1), ux.sum(1), uy.sum(1), uz.sum(1), (ux * ux).sum(1),
+                                      (ux * uy).sum(1), (ux * uz).sum(1), (uy * uy).sum(1), (uy * uz).sum(1),
+                                      (uz * uz).sum(1), (ux * c).sum(1), (uy * c).sum(1), (uz * c).sum(1)], 1)
+        back = np.empty(n, dtype=np.int64)
+        back[order] = np.arange(n)
+        m = m[back]
+        fields.append(color_field_from_moments(m, Q, nrm, I, min_neighbors))
+        counts.append(m[:, 0].astype(np.int32))
+        moments.append(m)
+    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dtype=dt)
+    res = (cat(fields, (0, 4), np.float32), cat(counts, (0,), np.int32))
+    return res + (cat(moments, (0, 13), np.int64),) if return_moments else res
+
+
+def color_field_from_moments(m, Q, nrm, intensity, min_neighbors=4):
+    """Everything after the moments of ``color_gradients_numpy`` (csrc/color_icp.hpp gradient_from_moments, in the same
+    order of operations): ``m int64 [n,13]``, ``nrm f32 [n,3]``, ``intensity f32 [n]`` -> ``field f32 [n,4]``."""
+    m = np.asarray(m, dtype=np.int64).reshape(-1, 13)
+    nv = np.asarray(nrm, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    I = np.asarray(intensity, dtype=np.float32).reshape(-1)
+    n = m.shape[0]
+    field = np.full((n, 4), np.nan, dtype=np.float32)
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        usable = (I >= np.float32(0)) & (I <= np.float32(1))
+        field[usable, 3] = I[usable]
+        mag = np.abs(nv)
+        ok = usable & (m[:, 0] >= int(min_neighbors)) & (mag.sum(1) > 0.0)
+        use_y = mag[:, 1] < mag[:, 0]
+        use_z = mag[:, 2] < np.where(use_y, mag[:, 1], mag[:, 0])
+        k = np.where(use_z, 2, np.where(use_y, 1, 0))
+        axis = np.eye(3)[k]
+        e1 = np.cross(nv, axis)
+        e1 = e1 / np.sqrt((e1[:, 0] * e1[:, 0] + e1[:, 1] * e1[:, 1]) + e1[:, 2] * e1[:, 2])[:, None]
+        e2 = np.cross(nv, e1)
+        S = m[:, [4, 5, 6, 5, 7, 8, 6, 8, 9]].astype(np.float64).reshape(-1, 3, 3) * (1.0 / (Q * Q))
+        h = m[:, 10:13].astype(np.float64) * (1.0 / (Q * INTENSITY_SCALE))
+        a1, a2 = np.einsum('nij,nj->ni', S, e1), np.einsum('nij,nj->ni', S, e2)
+        g00, g01, g11 = (e1 * a1).sum(1), (e1 * a2).sum(1), (e2 * a2).sum(1)
+        b0, b1 = (e1 * h).sum(1), (e2 * h).sum(1)
+        det, top = g00 * g11 - g01 * g01, np.maximum(g00, g11)
+        ok &= det > GRADIENT_PIVOT * (top * top)
+        c0, c1 = (g11 * b0 - g01 * b1) / det, (g00 * b1 - g01 * b0) / det
+        d = e1 * c0[:, None] + e2 * c1[:, None]
+        field[ok, :3] = d[ok].astype(np.float32)
+    return field
 
 
 def _icp_keywords(icp):
@@ -326,13 +501,18 @@ def _cloud_grid(clouds, radius, dev):
 
 
 def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', estimation='point_to_point',
-                      normal_radius=None, return_information=False, **icp):
+                      normal_radius=None, return_information=False, colors=None, lambda_geometric=LAMBDA_GEOMETRIC,
+                      **icp):
     """ICP refinement of fragment-pair poses, all pairs in ONE ``ops.icp_rigid`` call over one ``ops.CloudGrid`` of the
     fragments.  ``estimation``: ``'point_to_point'``, or ``'point_to_plane'`` -- the cell list is then built at
     ``max(normal_radius, max_distance)`` (``normal_radius`` defaults to ``2 * max_distance``), the normals of all
     fragments are estimated once (``ops.estimate_normals``, viewpoint at each fragment's origin) and the fit minimises
     the point-to-plane residual: a handful of iterations from a good RANSAC pose, but it can stall on a low overlap that
-    is mostly one plane and diverge from a poor start -- an option, not the default.
+    is mostly one plane and diverge from a poor start -- an option, not the default.  ``'colored'`` adds a colour term
+    to that (``ops.color_gradients`` over the same cell list and radius, then the coloured ``ops.icp_rigid``) which
+    holds the slide along a textured plane: ``colors`` is then required, one array / tensor per fragment -- ``[n,3]``
+    RGB or ``[n,1]`` / ``[n]`` intensity, what ``intensity_of`` takes -- registered to the points; ``lambda_geometric``
+    in [0, 1] weighs the geometric term (default: Open3D's 0.968, not tuned here).
     ``clouds``: list of [n,3] arrays / tensors, fragment k at index k;
     ``keys_or_pairs``: ``gt.log`` keys ``'i_j'`` or (i, j) tuples with ``T[p]`` ([P,4,4] / [P,3,4]; array or tensor)
     mapping fragment j into fragment i -- j is the moving cloud, i the fixed one.  ``icp``: ``max_iters``,
@@ -341,9 +521,15 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
     (``icp_numpy``).  A pair that ends with fewer than 3 matches keeps the pose it had then.
     ``return_information=True`` appends ``info [P,6,6]``, the benchmark-form information matrices of the RETURNED poses
     at ``max_distance`` (``information_matrices``): one more call on the cell list that is already built."""
-    if estimation not in ('point_to_point', 'point_to_plane'):
-        raise ValueError("estimation must be 'point_to_point' or 'point_to_plane', got %r" % (estimation,))
-    plane = estimation == 'point_to_plane'
+    if estimation not in ('point_to_point', 'point_to_plane', 'colored'):
+        raise ValueError("estimation must be 'point_to_point', 'point_to_plane' or 'colored', got %r" % (estimation,))
+    colored = estimation == 'colored'
+    plane = estimation == 'point_to_plane' or colored
+    if colored:
+        if colors is None:
+            raise ValueError("estimation='colored' needs colors, one array per fragment")
+        if len(colors) != len(clouds) or any(int(c.shape[0]) != int(p.shape[0]) for c, p in zip(colors, clouds)):
+            raise ValueError("colors must hold one row per point of every fragment")
     if normal_radius is None:
         normal_radius = 2.0 * float(max_distance)
     ji = _moving_fixed_pairs(keys_or_pairs, len(clouds))
@@ -353,7 +539,12 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
         Tn = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T
         if plane:
             icp = dict(icp, normals=estimate_normals_numpy(arrs, normal_radius)[0])
-        Tr, count, rmse, iters, _ = icp_numpy(arrs, ji, Tn, max_distance, **icp)
+        if colored:
+            inten = np.concatenate([intensity_of(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c)
+                                    for c in colors])
+            icp = dict(icp, color_field=color_gradients_numpy(arrs, normal_radius, icp['normals'], inten)[0],
+                       lambda_geometric=lambda_geometric)
+        Tr, count, rmse, iters = icp_numpy(arrs, ji, Tn, max_distance, **icp)[:4]
         res = (Tr, count / np.maximum(lens[ji[:, 0]], 1), rmse, iters)
         return res + (information_from_moments(information_numpy(arrs, ji, Tr, max_distance)[0]),) \
             if return_information else res
@@ -361,8 +552,12 @@ def refine_transforms(clouds, keys_or_pairs, T, max_distance, device='cuda', est
     grid = _cloud_grid(clouds, max(float(normal_radius), float(max_distance)) if plane else max_distance, dev)
     if plane:
         icp = dict(icp, normals=ops.estimate_normals(grid, None, normal_radius)[0])
-    Tr, count, rmse, iters, _ = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
-                                              max_distance, **icp)
+    if colored:
+        inten = torch.cat([torch.as_tensor(intensity_of(c)).to(dev) for c in colors])
+        icp = dict(icp, color_field=ops.color_gradients(grid, None, normal_radius, icp['normals'], inten)[0],
+                   lambda_geometric=lambda_geometric)
+    Tr, count, rmse, iters = ops.icp_rigid(grid, None, ji, torch.as_tensor(T, dtype=torch.float64).to(dev),
+                                           max_distance, **icp)[:4]
     fitness = count.double() / torch.as_tensor(np.maximum(lens[ji[:, 0]], 1), dtype=torch.float64, device=dev)
     if return_information:
         return Tr, fitness, rmse, iters, information_from_moments(ops.pair_information(grid, None, ji, Tr,
@@ -542,6 +737,28 @@ def evaluate_registration(est, gt, info, err2=0.2 ** 2):
     return recall, precision, errs
 
 
+def _scene_colors(colors, frags, rows):
+    """The colours of the fragments ``frags`` (with ``rows`` points each) for ``register_scene``: ``colors`` a folder of
+    ``cloud_bin_<i>.ply`` files or a sequence indexed by fragment number -> one array per fragment, in ``frags``'
+    order."""
+    from ..datasets.fragments import read_ply_colors
+    if colors is None:
+        raise ValueError("estimation='colored' needs colors: a folder of cloud_bin_<i>.ply files or per-fragment arrays")
+    out = []
+    for f, n in zip(frags, rows):
+        if isinstance(colors, (str, os.PathLike)):
+            name = os.path.join(colors, 'cloud_bin_%d.ply' % f)
+            c = read_ply_colors(name) if os.path.exists(name) else None
+        else:
+            c = colors[f] if f < len(colors) else None
+        if c is None:
+            raise ValueError("fragment %d has no colours" % f)
+        if int(c.shape[0]) != n:
+            raise ValueError("fragment %d: %d colours for %d points" % (f, int(c.shape[0]), n))
+        out.append(c)
+    return out
+
+
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
                    pose_graph=None, **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
@@ -549,7 +766,11 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
     ``evaluate_registration(...)`` when ``<gtpath>/gt.info`` exists, else None.  ``icp``: None, or a dict of
     ``refine_transforms`` keywords (at least ``max_distance``): every pose is refined by ICP over the dumped keypoint
-    files (they hold the whole subsampled fragment), all pairs in one call, before it is written and scored.
+    files (they hold the whole subsampled fragment), all pairs in one call, before it is written and scored.  With
+    ``estimation='colored'`` in that dict its ``colors`` names a folder of ``cloud_bin_<i>.ply`` files that hold one
+    coloured vertex per row of fragment i's keypoint file (``fragments.write_ply_points(colors=)``; read with
+    ``fragments.read_ply_colors``), or is a sequence of per-fragment colour arrays indexed by fragment number; a
+    fragment without colours raises ``ValueError``.
     ``pose_graph``: None, or a dict of ``multiway_registration`` keywords (at least ``max_distance``): the information
     matrices of the estimated poses are taken (from the ICP call when ``icp`` is given, else from one
     ``information_matrices`` call over the keypoint files), ``multiway_registration`` gives one pose per fragment, and
@@ -591,8 +812,11 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]
     info = None
     if icp is not None:
+        icp = _icp_keywords(icp)
+        if icp.get('estimation') == 'colored':
+            icp['colors'] = _scene_colors(icp.get('colors'), frags, [int(cache[f][0].shape[0]) for f in frags])
         res = refine_transforms([cache[f][0] for f in frags], ij, T, device=dev,
-                                return_information=pose_graph is not None, **_icp_keywords(icp))
+                                return_information=pose_graph is not None, **icp)
         T, info = res[0], (res[4] if pose_graph is not None else None)
     if pose_graph is None:
         T = T.cpu().numpy()                                      # the scene's only read-back

@@ -2919,6 +2919,15 @@ def icp_plane_bytes(rows, found=None):
             + 12 * (rows if found is None else int(found)))
 
 
+def icp_color_bytes(rows, found=None):
+    """Algorithmic bytes of ONE coloured search of ``rows`` rows: ``icp_plane_bytes`` with 248 bytes of sums (31 f64) per
+    workgroup in place of 232, plus the 16-byte field row of the matched fixed point and the 4-byte intensity of the
+    moving point of every matched row (``found`` of them, by default one per row)."""
+    rows = int(rows)
+    return (icp_plane_bytes(rows, found) + 2 * (248 - 232) * (-(-rows // ICP_BLOCK_ROWS))
+            + 20 * (rows if found is None else int(found)))
+
+
 def pair_information_bytes(rows, found=None):
     """Algorithmic bytes of the ONE search of ``pair_information``: ``icp_rigid_bytes`` with 160 bytes of sums (20 f64)
     per workgroup in place of 136."""
@@ -2967,8 +2976,52 @@ def estimate_normals(grid_or_points, lens, radius, min_neighbors=3, viewpoint=No
     return (normals, count, moments) if return_moments else (normals, count)
 
 
+def color_gradients_bytes(n, neighbors=None):
+    """Algorithmic bytes of the colour gradients of ``n`` points: ``estimate_normals_bytes`` with the point's normal (12)
+    and intensity (4) read, the 4-byte intensity of every neighbour (``neighbors`` of them in all, by default the point
+    itself) and a 16-byte field row written in place of the 12-byte normal."""
+    n = int(n)
+    return estimate_normals_bytes(n, neighbors) + n * (12 + 4 + 4) + 4 * (n if neighbors is None else int(neighbors))
+
+
+def color_gradients(grid_or_points, lens, radius, normals, intensity, min_neighbors=4, return_moments=False):
+    """Colour gradient of every point of the stacked clouds on its tangent plane (d3f_color_gradients) -- what the
+    coloured form of ``icp_rigid`` reads per matched fixed point.
+
+    ``grid_or_points``, ``lens``, ``radius``: as in ``estimate_normals`` (the same neighbourhood: the point's own cloud,
+    itself included).  ``normals`` f32 [N,3] (``estimate_normals``) and ``intensity`` f32 [N] or [N,1] in input row
+    order; an intensity is usable when ``0 <= I <= 1``, anything else (NaN included) means "no colour"
+    (``registration.intensity_of`` makes one from RGB).  The gradient is the least-squares slope of the intensity over
+    the neighbours with a usable intensity, restricted to the tangent plane (rule: include/d3feat_hip.h).  Returns device
+    tensors ``(field [N,4] f32 = (d_x, d_y, d_z, I), count [N] int32)`` and, with ``return_moments``, ``moments [N,13]
+    int64``.  Three NaNs mark an invalid gradient (own intensity not usable, fewer than ``min_neighbors`` usable
+    neighbours, a zero normal, neighbours on one line), a NaN in ``.w`` an unusable intensity.  The moments are integer
+    sums, so the result is bit-identical from run to run, for a cloud alone or stacked, and for any cell size."""
+    if not (0.0 < float(radius) < float("inf")) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    grid = _resolve_grid(grid_or_points, lens, radius, "radius")
+    dev = grid.supports.device
+    N = grid.Ns
+    nrm = _f32(normals, "normals")
+    if tuple(nrm.shape) != (N, 3) or nrm.device != dev:
+        raise ValueError("normals must be [%d,3] on the points' device, got %s" % (N, tuple(nrm.shape)))
+    inten = _f32(intensity, "intensity")
+    if tuple(inten.shape) not in ((N,), (N, 1)) or inten.device != dev:
+        raise ValueError("intensity must be [%d] or [%d,1] on the points' device, got %s" % (N, N, tuple(inten.shape)))
+    field = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    moments = torch.empty((N, 13), dtype=torch.int64, device=dev) if return_moments else None
+    if N:
+        with _region("color_gradients[N=%d]" % N, color_gradients_bytes(N)):
+            _native.check(_native.lib().d3f_color_gradients(
+                _p(grid.ws), _p(grid.supports), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(radius), int(min_neighbors), _p(nrm), _p(inten), _p(field), _p(count), _p(moments),
+                _p(grid.status.word), _stream()), "d3f_color_gradients")
+    return (field, count, moments) if return_moments else (field, count)
+
+
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
-              return_trace=False, rows=None, normals=None):
+              return_trace=False, rows=None, normals=None, color_field=None, lambda_geometric=0.968):
     """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).
 
     ``grid_or_points``, ``lens``, ``pairs``: as in ``nearest_pairs`` -- pair p = (MOVING cloud a, FIXED cloud b) and
@@ -2989,7 +3042,15 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     TransformationEstimationPointToPlane).  Search, count, rmse, stopping rule and trace keep their meaning; a pair
     whose 6x6 normal equations are singular (the overlap is one plane, or has only zero normals) stops at its current
     pose with ``ICP_ST_SINGULAR``.  It converges in a handful of iterations from a good pose and can stall or diverge
-    where point-to-point does not -- on a low overlap that is mostly one plane, or from a poor start."""
+    where point-to-point does not -- on a low overlap that is mostly one plane, or from a poor start.
+
+    ``color_field``: None, or the f32 [N,4] field of ``color_gradients`` (requires ``normals``) -- COLOURED ICP
+    (d3f_icp_rigid_color; Open3D's registration_colored_icp): the point-to-plane rows weighted by
+    ``sqrt(lambda_geometric)`` plus, per matched row whose fixed point has a valid gradient and whose moving point has
+    an intensity, a colour row weighted by ``sqrt(1 - lambda_geometric)``, so that texture holds the pose where a
+    single plane lets it slide.  ``n_color [P] int32`` and ``color_rmse [P] f64`` of the returned pose are then
+    appended to the results (after ``trace``); ``n_color == 0`` means that colour took no part.  ``lambda_geometric=1``
+    gives the point-to-plane results bit for bit.  The default 0.968 is Open3D's; it has not been tuned here."""
     if not 0 <= int(max_iters) <= ICP_MAX_ITERS:
         raise ValueError("max_iters must be in 0..%d" % ICP_MAX_ITERS)
     if not float(rel_fitness) >= 0.0 or not float(rel_rmse) >= 0.0:
@@ -3011,6 +3072,27 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
         if tuple(nrm.shape) != (grid.Ns, 3) or nrm.device != dev:
             raise ValueError("normals must be [%d,3] on the points' device, got %s" % (grid.Ns, tuple(nrm.shape)))
     plane = nrm is not None
+    if color_field is not None:
+        if not plane:
+            raise ValueError("color_field requires normals")
+        if not 0.0 <= float(lambda_geometric) <= 1.0:
+            raise ValueError("lambda_geometric must be in [0, 1]")
+        field = _f32(color_field, "color_field")
+        if tuple(field.shape) != (grid.Ns, 4) or field.device != dev:
+            raise ValueError("color_field must be [%d,4] on the points' device, got %s" % (grid.Ns, tuple(field.shape)))
+        n_color = torch.empty(P, dtype=torch.int32, device=dev)
+        color_rmse = torch.empty(P, dtype=torch.float64, device=dev)
+        nbytes = L.d3f_icp_rigid_color_ws_bytes(P, rows)
+        ws = _ws(nbytes, dev)
+        with _region("icp_rigid_color[P=%d,rows=%d,iters<=%d]" % (P, rows, K), (K + 1) * icp_color_bytes(rows)):
+            _native.check(L.d3f_icp_rigid_color(
+                _p(grid.ws), _p(grid.supports), _p(nrm), _p(field), grid.Ns, _p(grid.cloud_start),
+                int(grid.s_len.numel()), grid.radius, float(max_distance), _p(pr), _p(row_start), P, rows, _p(tf),
+                float(lambda_geometric), K, float(rel_fitness), float(rel_rmse), _p(T), _p(count), _p(rmse),
+                _p(iterations), _p(status), _p(n_color), _p(color_rmse), _p(trace), _p(ws), nbytes, _stream()),
+                "d3f_icp_rigid_color")
+        res = (T, count, rmse, iterations, status)
+        return (res + (trace,) if return_trace else res) + (n_color, color_rmse)
     name = "d3f_icp_rigid_plane" if plane else "d3f_icp_rigid"
     nbytes = getattr(L, name + "_ws_bytes")(P, rows)
     ws = _ws(nbytes, dev)

@@ -916,6 +916,69 @@ int d3f_icp_plane_fit_host(const double* sums_host, const double* py_host, const
                            int* singular_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Coloured ICP: point-to-plane ICP with a colour term, so that a pair whose overlap is mostly one plane -- where the
+ * point-to-plane residual leaves the slide along the plane free -- is held by the texture on that plane (Park, Zhou,
+ * Koltun 2017; Open3D's registration_colored_icp).  csrc/color_icp.hpp states the rule beside the code.
+ *
+ * Intensity: one f32 per point in input row order beside the points.  It is USABLE when 0 <= I <= 1 compared as floats;
+ * any other value, NaN included, means "no colour".  q = (int64) rint((double) I * 2^20).
+ *
+ * d3f_color_gradients.  The cell list (grid_ws, grid_radius), points, Ns, cloud_start, B, radius and the neighbourhood
+ * are those of d3f_estimate_normals: the points j of the SAME cloud, i itself included, with d2 < radius * radius (f32,
+ * strict), the same Q and u = rint((p_j - p_i) Q).  `normals` [Ns,3] f32 (the normal of the query row is read) and
+ * `intensity` [Ns] f32 are inputs.  Only neighbours with a usable intensity count; a point whose OWN intensity is not
+ * usable is not searched (count 0, zero moments).
+ *   moments (int64) [13]: n, sum u (3), sum u u^T (xx xy xz yy yz zz) as for the normals, then sum u_x c, sum u_y c,
+ *        sum u_z c with c = q_j - q_i; |u| <= 2^20 and |c| <= 2^20, a product is below 2^40 and 2^22 neighbours fit.
+ *        All 13 are integers: lanes, groups, bucket order, stacking and cell size cannot change them.
+ *   Everything after the moments is a function of them and of the f32 normal nrm of the row, in f64:
+ *        S = sum u u^T / Q^2 (about the point, not centred); h = sum u c / (Q 2^20);
+ *        e1 = normalise(nrm x axis), axis the unit vector of the component of nrm with the smallest magnitude (lowest
+ *        index on ties); e2 = nrm x e1; E = [e1 e2]; G = E^T S E (2x2), g2 = E^T h;
+ *        d = E G^-1 g2 by the closed form of the 2x2 (so d . nrm = 0 to rounding), rounded to f32: the least-squares
+ *        slope of the intensity over the neighbourhood on the tangent plane, in intensity per unit length.
+ *   invalid: the point's own intensity is not usable, n < min_neighbors (>= 1; 4 is the front ends' default), nrm is
+ *        zero or not finite, or det G <= 1e-6 max(G00, G11)^2 (neighbours on one line).
+ * Outputs in input row order: field [Ns,4] f32 = (d_x, d_y, d_z, I), 16-byte aligned; an invalid gradient is three
+ * NaNs, an unusable intensity a NaN in .w.  Optional (NULL to skip): count [Ns] int32 (= n), moments [Ns,13] int64.
+ * Rows beyond cloud_start[B] get four NaNs, count 0 and zero moments.  A point outside the addressable cell grid is in
+ * no cell list: count 0, D3F_ST_CELL_RANGE in *status.  One launch on `stream`, no host synchronisation, no
+ * allocation, no LDS, no floating-point atomics.
+ * d3f_color_gradient_from_moments_host: host-only twin of everything after the moments (the same inline code): m[13],
+ * Q, nrm[3], the point's own intensity, min_neighbors -> out[4], one row of `field`.
+ *
+ * d3f_icp_rigid_color: d3f_icp_rigid_plane with `field` [Ns,4] f32 (16-byte aligned) and lambda_geometric in [0, 1].
+ * Setup, search, n_k, sum d2, fitness, rmse, the stopping rule, trace, flags, block prefix and every reduction order
+ * are d3f_icp_rigid_plane's.  Per accepted row a, c, J, r are point-to-plane's; J and r are multiplied by
+ * sg = sqrt(lambda_geometric) before any product is formed.  A colour row is added when field[y] of the matched FIXED
+ * point is finite in all four entries (d, I_y) and field[x].w = I_x of the moving point is finite:
+ *   J_C = sc [a x d, d],  r_C = sc ((I_y - I_x) + (a - c) . d),  sc = sqrt(1 - lambda_geometric),
+ * into the same 21 + 6 sums, after the geometric row.
+ *   sums[31] = { the 29 of d3f_icp_rigid_plane over both kinds of rows, n_color,
+ *                sum ((I_y - I_x) + (a - c) . d)^2 (unweighted) }.
+ * Fit: d3f_icp_rigid_plane's on the first 29 (a singular system ends the pair with D3F_ICP_ST_SINGULAR).  Beside the
+ * outputs of d3f_icp_rigid_plane: n_color [P] int32 and color_rmse [P] f64 = sqrt(sums[30] / n_color) (0 without colour
+ * rows) of the RETURNED pose (0 for a pair the setup stopped), so that a caller sees whether colour took part.
+ * lambda_geometric = 1: sg is exactly 1 and the colour rows add +-0 to accumulators that start at +0 -- T, count, rmse,
+ * iterations, status and trace are d3f_icp_rigid_plane's bit for bit.  A field that is NaN everywhere gives
+ * point-to-plane scaled by sg: n_color = 0.  Workspace: d3f_icp_rigid_color_ws_bytes(P, rows).  Launches, determinism
+ * and batch independence as for d3f_icp_rigid.
+ * ---------------------------------------------------------------------------------------------- */
+int d3f_color_gradients(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                        float grid_radius, float radius, int min_neighbors, const float* normals,
+                        const float* intensity, float* field, int32_t* count, int64_t* moments, int32_t* status,
+                        void* stream);
+int d3f_color_gradient_from_moments_host(const int64_t* m_host, double Q, const float* nrm_host, float intensity,
+                                         int min_neighbors, float* out_host);
+size_t d3f_icp_rigid_color_ws_bytes(int P, int64_t rows);
+int d3f_icp_rigid_color(const void* grid_ws, const float* points, const float* normals, const float* field, int Ns,
+                        const int32_t* cloud_start, int B, float grid_radius, float max_distance, const int32_t* pairs,
+                        const int64_t* row_start, int P, int64_t rows, const double* T_init, double lambda_geometric,
+                        int max_iters, double rel_fitness, double rel_rmse, double* T, int32_t* count, double* rmse,
+                        int32_t* iterations, int32_t* status, int32_t* n_color, double* color_rmse, double* trace,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Raw moments of the accepted correspondences of cloud pairs under GIVEN poses -- what the 6x6 information matrix of a
  * pair is made of (the benchmark's gt.info, which registration recall is scored under, and the weight of an edge of a
  * pose graph; Open3D's get_information_matrix_from_point_clouds).  The clouds, the cell list (grid_ws, grid_radius),
