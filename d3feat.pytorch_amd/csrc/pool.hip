@@ -4,6 +4,8 @@
 // and :79-91 (closest_pool: gather column 0).  The reference materialises the gathered [n2,H,d] tensor; here a
 // thread owns one (query, 4 channels) group (one channel when C % 4 != 0); consecutive lanes own consecutive channel
 // groups, so every neighbor row is read as coalesced 16-B loads and the neighbor index is (nearly) wave-uniform.
+// The 4-channel max-pool forward goes further: its rows belong to waves, which read each index row once and keep the
+// gathers of 8 neighbors in flight (max_pool_fwd_v4_kernel).
 // Element indices are 32-bit whenever the matrices have fewer than 2^31 elements: a 64-bit division by a run-time C per
 // thread costs more than the loads of these kernels (closest_pool forward at 38k x 128: 47 -> 15 us).
 #include "common.hpp"
@@ -55,36 +57,134 @@ __global__ void max_pool_fwd_kernel(const float* __restrict__ x, int Ns, int C, 
   if (argmax) argmax[(size_t)n * C + c] = arg;
 }
 
-// 4 channels per thread (C % 4 == 0), 32-bit element indices
-__global__ void max_pool_fwd_v4_kernel(const float* __restrict__ x, int Ns, int C4, const int32_t* __restrict__ idx,
-                                       int Nq, int H, float* __restrict__ out, int32_t* __restrict__ argmax,
-                                       float* __restrict__ clear, const int32_t* __restrict__ width,
-                                       d3f::RowGroups rg) {
+// One gather group of max_pool_fwd_v4_kernel: the 16-byte gathers of G consecutive neighbors (entries j0 .. j0 + G - 1
+// of the index chunk, which the L lanes of a row hold as ea = columns 0 .. L - 1 and eb = columns L .. 2L - 1) issued
+// back to back, then compared in row order as they return.  Every load is unconditional and every update a select (a
+// conditional load or a branch around a compare costs the counted waits: kpconv_dx_gather.hip): a shadow entry loads
+// the row `spare` (the query's first neighbor, which the wave has just read: one fixed row for every shadow of the
+// launch measured 2-7 % slower) and the shadow's zero is selected afterwards.  Entries past the chunk repeat its last
+// one and are not counted.
+template <bool kWave, int G>
+__device__ __forceinline__ void max_pool_gather_group(const float4* __restrict__ x4, int Ns, uint32_t C4, uint32_t c4,
+                                                      int ea, int eb, int spare, int lane0, int L, int j0, int h0,
+                                                      int Hw, float4& best, int4& arg) {
+  int m[G];
+  float4 v[G];
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    const int j = min(j0 + k, 2 * L - 1);
+    const int e = j < L ? ea : eb, src = j < L ? j : j - L;
+    m[k] = kWave ? __builtin_amdgcn_readlane(e, src) : __shfl(e, lane0 + src);
+  }
+#pragma unroll
+  for (int k = 0; k < G; ++k) v[k] = x4[(uint32_t)(m[k] >= 0 && m[k] < Ns ? m[k] : spare) * C4 + c4];
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    const int h = h0 + j0 + k;
+    const bool real = m[k] >= 0 && m[k] < Ns;
+    const uint32_t keep = real ? ~0u : 0u;  // shadow row is zeros (blocks.py:103); a mask, so that the load stays put
+    const auto kept = [keep](float f) { return __uint_as_float(__float_as_uint(f) & keep); };
+    const float4 u = make_float4(kept(v[k].x), kept(v[k].y), kept(v[k].z), kept(v[k].w));
+    const int mm = real ? m[k] : Ns;
+    const bool counted = j0 + k < 2 * L && h < Hw;
+    const bool tx = counted && (u.x > best.x || h == 0), ty = counted && (u.y > best.y || h == 0);
+    const bool tz = counted && (u.z > best.z || h == 0), tw = counted && (u.w > best.w || h == 0);
+    best.x = tx ? u.x : best.x; arg.x = tx ? mm : arg.x;
+    best.y = ty ? u.y : best.y; arg.y = ty ? mm : arg.y;
+    best.z = tz ? u.z : best.z; arg.z = tz ? mm : arg.z;
+    best.w = tw ? u.w : best.w; arg.w = tw ? mm : arg.w;
+  }
+}
+
+// 4 channels per lane (C % 4 == 0), 32-bit element indices.  Rows belong to waves: the L lanes of a row cover its C4
+// channel groups.  kWave = false: C4 divides 64, a wave takes 64 / C4 consecutive rows (L = C4); kWave = true: one row
+// per wave and ceil(C4 / 64) waves per row (L = 64, the lanes past C4 idle).  The lanes of a row read its index row
+// once, 2L columns per pair of coalesced loads, and hand the entries out by shuffle (readlane when the wave has one
+// row); the gathers run 8 neighbors at a time (max_pool_gather_group).  The row's cloud and its group's table width
+// come from one coalesced load of the lengths and one of the widths per wave, issued together with the index row.
+// No lane leaves before the last shuffle: the rows and channel groups past the end are clamped and not stored.
+// 62 / 55 VGPRs; per 3-pair stack 85.8 / 38.6 / 30.2 / 26.4 -> 50.4 / 23.3 / 15.2 / 9.9 us
+// (profiles/maxpool_rows_timeline.txt).
+template <bool kWave>
+__global__ __launch_bounds__(256) void max_pool_fwd_v4_kernel(const float* __restrict__ x, int Ns, int C4,
+                                                              const int32_t* __restrict__ idx, int Nq, int H,
+                                                              float* __restrict__ out, int32_t* __restrict__ argmax,
+                                                              float* __restrict__ clear,
+                                                              const int32_t* __restrict__ width, d3f::RowGroups rg) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (clear) {
     const uint32_t n4 = (uint32_t)Ns * (uint32_t)C4;
     for (uint32_t i = t; i < n4; i += gridDim.x * blockDim.x) ((float4*)clear)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  if (t >= (uint32_t)Nq * (uint32_t)C4) return;
-  const uint32_t n = t / (uint32_t)C4, c4 = t - n * (uint32_t)C4;
+  const int lane = (int)(threadIdx.x & 63u);
+  // workgroups go to the 8 XCDs round robin: XCD k takes the k-th eighth of the rows, so that queries next to each
+  // other, which share most of their neighbors, gather through the same L2 (64.7 -> 50.4 us at 23.8k x 128)
+  const uint32_t per_xcd = gridDim.x >> 3, left = gridDim.x & 7u, xcd = blockIdx.x & 7u;
+  const uint32_t block = xcd * per_xcd + min(xcd, left) + (blockIdx.x >> 3);
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(block * 4u + (threadIdx.x >> 6)));
+  const int L = kWave ? 64 : C4;                                  // lanes per row (kWave = false: a power of two)
+  const int lshift = kWave ? 6 : __builtin_ctz((unsigned)C4);
+  const uint32_t parts = kWave ? ((uint32_t)C4 + 63u) >> 6 : 1u;  // waves per row
+  const uint32_t unit = wave / parts, part = wave - unit * parts;
+  const uint32_t n_first = unit << (6 - lshift);
+  if (n_first >= (uint32_t)Nq) return;                            // the whole wave
+  const int sub = lane >> lshift, sl = lane - (sub << lshift), lane0 = sub << lshift;
+  const uint32_t n_own = n_first + (uint32_t)sub, c_own = part * 64u + (uint32_t)sl;
+  const bool live = n_own < (uint32_t)Nq && c_own < (uint32_t)C4;
+  const uint32_t n = min(n_own, (uint32_t)Nq - 1u), c4 = min(c_own, (uint32_t)C4 - 1u);
   const int32_t* row = idx + (size_t)n * H;
-  int Hw = H;
-  if (width) Hw = min(H, max(1, rg.len ? width[d3f::group_of_row(rg, (int)n)] : *width));
-  float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-  int a0 = Ns, a1 = Ns, a2 = Ns, a3 = Ns;
-  const float4* x4 = (const float4*)x;
-  for (int h = 0; h < Hw; ++h) {
-    const int m = row[h];
-    const bool real = m >= 0 && m < Ns;
-    const float4 v = real ? x4[(size_t)m * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);  // shadow row is zeros (blocks.py:103)
-    const int mm = real ? m : Ns;
-    if (v.x > best.x || h == 0) { best.x = v.x; a0 = mm; }
-    if (v.y > best.y || h == 0) { best.y = v.y; a1 = mm; }
-    if (v.z > best.z || h == 0) { best.z = v.z; a2 = mm; }
-    if (v.w > best.w || h == 0) { best.w = v.w; a3 = mm; }
+  int ea = row[min(sl, H - 1)], eb = row[min(L + sl, H - 1)];     // first chunk of the index row, two entries per lane
+
+  // the reference's table has min(limit, max_count) columns (dataloader.py:64-66): with a wider, static-shape table the
+  // device-resident max_count says how many leading columns it would have kept; stacked pairs: every group of clouds
+  // has the width of the table its own batch would have had
+  int Hw = H, Hmax = H;
+  if (width) {
+    const bool grouped = rg.len && rg.group > 0;
+    const int wd = width[grouped ? min(lane, (rg.B - 1) / rg.group) : 0];
+    int g = 0;
+    if (grouped) {
+      const int len = rg.len[min(lane, rg.B - 1)];
+      int b = 0, end = 0;                                         // locate_batch for every row of the wave at once
+      for (int k = 0; k < rg.B - 1; ++k) {
+        end += __builtin_amdgcn_readlane(len, k);
+        b += (int)n >= end;
+      }
+      g = b / rg.group;
+    }
+    Hw = min(H, max(1, __shfl(wd, g)));
+    Hmax = Hw;
+    if (!kWave)
+      for (int o = 32; o >= L; o >>= 1) Hmax = max(Hmax, __shfl_xor(Hmax, o));
+    Hmax = __builtin_amdgcn_readfirstlane(Hmax);
   }
-  ((float4*)out)[t] = best;
-  if (argmax) ((int4*)argmax)[t] = make_int4(a0, a1, a2, a3);
+
+  float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  int4 arg = make_int4(Ns, Ns, Ns, Ns);
+  if (Ns <= 0) {
+    best = make_float4(0.f, 0.f, 0.f, 0.f);                       // no support row to read: every entry is the shadow
+  } else {
+    const float4* x4 = (const float4*)x;
+    const int spare = min(max(kWave ? __builtin_amdgcn_readlane(ea, 0) : __shfl(ea, lane0), 0), Ns - 1);
+    for (int h0 = 0; h0 < Hmax; h0 += 2 * L) {
+      if (h0 > 0) {                                               // tables wider than 2L columns
+        ea = row[min(h0 + sl, H - 1)];
+        eb = row[min(h0 + L + sl, H - 1)];
+      }
+      const int cnt = min(2 * L, Hmax - h0);
+      int j0 = 0;
+      for (; j0 + 8 <= cnt; j0 += 8)  // (groups of 4 and of 16, 43 and 81 VGPRs: 2-7 % slower on a step's 4 launches)
+        max_pool_gather_group<kWave, 8>(x4, Ns, (uint32_t)C4, c4, ea, eb, spare, lane0, L, j0, h0, Hw, best, arg);
+      if (cnt - j0 > 4)
+        max_pool_gather_group<kWave, 8>(x4, Ns, (uint32_t)C4, c4, ea, eb, spare, lane0, L, j0, h0, Hw, best, arg);
+      else if (cnt - j0 > 0)
+        max_pool_gather_group<kWave, 4>(x4, Ns, (uint32_t)C4, c4, ea, eb, spare, lane0, L, j0, h0, Hw, best, arg);
+    }
+  }
+  if (!live) return;
+  const uint32_t o = n * (uint32_t)C4 + c4;
+  ((float4*)out)[o] = best;
+  if (argmax) ((int4*)argmax)[o] = arg;
 }
 
 __global__ void max_pool_bwd_kernel(const float* __restrict__ go, const int32_t* __restrict__ argmax, int Nq, int C,
@@ -183,9 +283,15 @@ int d3f_max_pool_forward(const float* x, int Ns, int C, const int32_t* idx, int 
   }
   const bool small = (long long)Nq * C < (1ll << 31) && (long long)Ns * C < (1ll << 31);
   const bool aligned = ((uintptr_t)x | (uintptr_t)out | (uintptr_t)argmax_out | (uintptr_t)grad_x_clear) % 16 == 0;
-  if (C % 4 == 0 && small && aligned)
-    max_pool_fwd_v4_kernel<<<d3f::cdiv((long long)Nq * (C / 4), 256), 256, 0, (hipStream_t)stream>>>(
-        x, Ns, C / 4, idx, Nq, H, out, argmax_out, grad_x_clear, width_dev, rg);
+  if (C % 4 == 0 && small && aligned) {
+    const int C4 = C / 4;
+    if (C4 < 64 && 64 % C4 == 0)  // 64 / C4 rows per wave
+      max_pool_fwd_v4_kernel<false><<<d3f::cdiv(d3f::cdiv((long long)Nq * C4, 64), 4), 256, 0, (hipStream_t)stream>>>(
+          x, Ns, C4, idx, Nq, H, out, argmax_out, grad_x_clear, width_dev, rg);
+    else                          // ceil(C4 / 64) waves per row
+      max_pool_fwd_v4_kernel<true><<<d3f::cdiv((long long)Nq * d3f::cdiv(C4, 64), 4), 256, 0, (hipStream_t)stream>>>(
+          x, Ns, C4, idx, Nq, H, out, argmax_out, grad_x_clear, width_dev, rg);
+  }
   else
     max_pool_fwd_kernel<<<d3f::cdiv((long long)Nq * C, 256), 256, 0, (hipStream_t)stream>>>(
         x, Ns, C, idx, Nq, H, out, argmax_out, grad_x_clear, width_dev, rg);
