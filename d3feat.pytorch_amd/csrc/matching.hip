@@ -10,10 +10,11 @@
 //   The target range is split over grid.y so that the launch fills the chip; partial winners are merged with ONE
 //   64-bit atomicMin per row on the key (order-preserving bits of the distance << 32 | column): ties resolve to the
 //   lowest index exactly like np.argmin, in any arrival order.
-//   The reference compares sqrt(2 - 2s): the running minimum is kept on v = 2 - 2s (no sqrt in the inner loop) and the
-//   correctly rounded sqrt is taken only when a candidate beats the incumbent (a handful of times per row), so two
-//   different v that round to the same distance keep the earlier column as numpy does.  A negative v (NaN after the
-//   reference's sqrt) wins like NaN does in np.argmin.
+//   The reference compares sqrt(2 - 2s): the running minimum is kept on v = 2 - 2s (no sqrt in the inner loop); a
+//   candidate whose v is clearly below the incumbent's takes over, and only two v within 2^-20 of each other are
+//   compared on their correctly rounded roots, so two different v that round to the same distance keep the earlier
+//   column as numpy does.  A negative v (NaN after the reference's sqrt) wins like NaN does in np.argmin: the first one.
+//   tests/test_matching_exact_gpu.py holds all of this to np.argmin bit for bit, on inputs whose products are exact.
 // Row AND column arg-min come out of ONE sweep over the S x T tiles (round 4; the reference forms S T^T once,
 // common.py:9-13): the products a wave holds for its 32 rows x 16 columns also give, per column, the best of those rows;
 // the workgroup's 128 rows meet in an LDS table of (distance bits << 32 | row) keys over its column chunk (ds_min_u64),
@@ -31,6 +32,22 @@ __device__ __forceinline__ uint32_t ord_bits(float f) {  // monotone float -> ui
   const uint32_t b = __float_as_uint(f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
+
+// The correctly rounded square root of v = 2 - 2a, the reference's np.sqrt.  __fsqrt_rn is NOT that: the HIP headers map
+// it to the native v_sqrt_f32 (1 ulp), which tells apart products that np.sqrt rounds to ONE distance -- the later,
+// larger product then wins where np.argmin keeps the earlier index.  v_sqrt_f32 is within 1 ulp, so the residuals of its
+// two neighbours decide: the compiler's own expansion of sqrtf, without the denormal scaling and class checks (v is 0
+// or at least 2^-23; +inf, the "no candidate yet" value, comes back as +inf).  sqrtf itself costs 0.497 against 0.470 ms
+// at 19k x 19k x 32 with everything else equal: the root sits on the column side's dependent chain of every 16 columns.
+__device__ __forceinline__ float sqrt_rn(float v) {
+  float s = __builtin_amdgcn_sqrtf(v);
+  const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
+  const float rd = fmaf(-sd, s, v), ru = fmaf(-su, s, v);
+  s = rd <= 0.0f ? sd : s;
+  return ru > 0.0f ? su : s;
+}
+// the reference's distance; a negative v (its NaN) ranks below every distance
+__device__ __forceinline__ float dist_of(float v) { return v < 0.0f ? -INFINITY : sqrt_rn(v); }
 
 __global__ void fill_u64_kernel(unsigned long long* __restrict__ p, int n, unsigned long long v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,20 +93,20 @@ __global__ __launch_bounds__(256) void row_argmin_kernel(const float* __restrict
 #pragma unroll
     for (int u = 0; u < KS; ++u) afrag[rt][u] = *(const float4*)(S + (size_t)r * C + 16 * u + 4 * lk);
   }
-  // per lane and row: incumbent (rounded distance bs, column bj) among THIS lane's columns, and a filter flt = the
+  // per lane and row: incumbent (its v = 2 - 2a in bv, column bj) among THIS lane's columns, and a filter flt = the
   // smallest v any of the 16 lanes of the row has seen in earlier tiles.  A candidate with v >= flt cannot have a
   // smaller distance than the row's incumbent, and (columns ascend from tile to tile) loses a distance tie to it, so
   // it is dropped by one compare; without the shared filter every lane would rediscover its own minimum over 1/16 of
-  // the columns and the update path (a correctly rounded sqrt) would run on most tiles.
+  // the columns and the update path would run on most tiles.
   // The hot compare is on the raw dot product: v = 2 - 2a < flt can only hold when a > thr = (2 - flt)/2 - 1e-6
   // (conservative; the update path re-checks v < flt exactly), one v_cmp per product.
-  float flt[RT][4], thr[RT][4], bs[RT][4];
+  float flt[RT][4], thr[RT][4], bv[RT][4];
   int bj[RT][4];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      flt[rt][r] = INFINITY; thr[rt][r] = -INFINITY; bs[rt][r] = INFINITY; bj[rt][r] = 0x7fffffff;
+      flt[rt][r] = INFINITY; thr[rt][r] = -INFINITY; bv[rt][r] = INFINITY; bj[rt][r] = 0x7fffffff;
     }
 
   float4 bnext[4][KS];
@@ -153,24 +170,26 @@ __global__ __launch_bounds__(256) void row_argmin_kernel(const float* __restrict
             if (acc[rt][r] == m) ri = 16 * rt + r;
             near += !(acc[rt][r] <= mthr) ? 1 : 0;
           }
-        unsigned long long ckey;
-        if (near > 1 || !(m == m)) {   // (rare; NaN products: every candidate is looked at)
+        // The key of the lane's best row, (order-preserving bits of its distance) << 32 | row: for m <= 1, v >= 0 and so
+        // is its root, whose order-preserving bits are its own with the sign bit set.  It is computed before the rare
+        // cases are looked at, so that the root's latency overlaps the bookkeeping below.
+        unsigned long long ckey =
+            ((unsigned long long)(__float_as_uint(sqrt_rn(fmaf(-2.0f, m, 2.0f))) | 0x80000000u) << 32) |
+            (uint32_t)(row0 + ri + 4 * lk);
+        // m > 1: 2 - 2m < 0, and so is every other product above 1, however far below m: they are all NaN to the
+        // reference, which returns the FIRST of them, not the largest.
+        if (near > 1 || !(m <= 1.0f)) {   // (rare; m > 1 or a NaN product: every candidate is looked at)
           ckey = ~0ull;
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-              if (acc[rt][r] > mthr || !(acc[rt][r] == acc[rt][r])) {
-                const float v = 2.0f - 2.0f * acc[rt][r];
-                const float sv = v < 0.0f ? -INFINITY : __fsqrt_rn(v);
+              if (acc[rt][r] > fminf(mthr, 1.0f) || !(acc[rt][r] == acc[rt][r])) {
+                const float sv = dist_of(fmaf(-2.0f, acc[rt][r], 2.0f));
                 const unsigned long long k2 =
                     ((unsigned long long)ord_bits(sv) << 32) | (uint32_t)(row0 + 16 * rt + 4 * lk + r);
                 ckey = k2 < ckey ? k2 : ckey;
               }
-        } else {
-          const float v = 2.0f - 2.0f * m;
-          const float sv = v < 0.0f ? -INFINITY : __fsqrt_rn(v);
-          ckey = ((unsigned long long)ord_bits(sv) << 32) | (uint32_t)(row0 + ri + 4 * lk);
         }
         atomicMin(&colbest[j - cbeg], ckey);   // LDS: the 4 row quads of the wave and the 4 waves meet here
       }
@@ -180,18 +199,37 @@ __global__ __launch_bounds__(256) void row_argmin_kernel(const float* __restrict
 #pragma unroll
         for (int r = 0; r < 4; ++r) any |= acc[rt][r] > thr[rt][r];
       if (any && j < cend) {
+        // v < flt: the candidate is no farther than the lane's incumbent (bv >= flt) and takes over only when its
+        // ROUNDED distance is smaller.  For 0 <= v < bv (1 - 2^-20) the roots are more than sqrt(bv) 2^-21 apart, four
+        // times what the two roundings can move them, so no root is taken; the rest (one distance or two neighbouring
+        // ones: `pending`, rare) is decided on the roots themselves below.
+        unsigned pending = 0;
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = 2.0f - 2.0f * acc[rt][r];
+            const float v = fmaf(-2.0f, acc[rt][r], 2.0f);   // (2a is exact: one rounding, as in 2 - 2a)
             if (v < flt[rt][r]) {
               flt[rt][r] = v;
-              thr[rt][r] = (2.0f - v) * 0.5f - 1e-6f;
-              const float sv = v < 0.0f ? -INFINITY : __fsqrt_rn(v);
-              if (sv < bs[rt][r]) { bs[rt][r] = sv; bj[rt][r] = j; }
+              thr[rt][r] = acc[rt][r] - 1e-6f;   // ((2 - v) / 2 is a up to the rounding of v, 1.2e-7 at most)
+              const float b = bv[rt][r];
+              const bool live = b >= 0.0f;   // (an incumbent with a negative v is the reference's first NaN: it stays)
+              const bool sure = live & ((v < 0.0f) | (v < b * (1.0f - 0x1p-20f)));
+              bv[rt][r] = sure ? v : b;
+              bj[rt][r] = sure ? j : bj[rt][r];
+              pending |= (live & !sure) ? 1u << (4 * rt + r) : 0u;
             }
           }
+        if (pending) {
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (pending >> (4 * rt + r) & 1u) {
+                const float v = fmaf(-2.0f, acc[rt][r], 2.0f);   // (2a is exact: one rounding, as in 2 - 2a)
+                if (dist_of(v) < dist_of(bv[rt][r])) { bv[rt][r] = v; bj[rt][r] = j; }
+              }
+        }
       }
     }
     // every other tile: share the filter among the 16 lanes of each row
@@ -213,7 +251,7 @@ __global__ __launch_bounds__(256) void row_argmin_kernel(const float* __restrict
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      unsigned long long key = ((unsigned long long)ord_bits(bs[rt][r]) << 32) | (uint32_t)bj[rt][r];
+      unsigned long long key = ((unsigned long long)ord_bits(dist_of(bv[rt][r])) << 32) | (uint32_t)bj[rt][r];
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
         const unsigned long long ok = __shfl_xor(key, o, 64);

@@ -1652,7 +1652,11 @@ def test_mutual_nn_at_full_size_on_the_reference_descriptors():
     """BASELINE configs[3]: dense N x N matching at 19k x 19k x 32 on the descriptors the REFERENCE produced for the
     benchmark pair (eval mode).  Row / column argmins and the mutual set are compared with what the reference's
     build_correspondence (common.py:5-21, float32 sqrt(2 - 2 S T^T)) computed; every row that picks another column
-    must be a distance tie at float32 resolution, proven in float64, and their number is bounded."""
+    must be a distance tie at float32 resolution, proven in float64, and their number is bounded.
+    Measured on the MI355X: 410 flipped rows of 19099 and 340 flipped columns of 19070 (|ours ^ ref| = 270 of 1448
+    mutual pairs), the same in every run -- the merges are integer atomicMin -- and the same with the native and the
+    correctly rounded square root.  The caps are twice that: room for a compiler that reorders the float32 sums, none
+    for a wrong rule (tests/test_matching_exact_gpu.py holds the rule itself, bit for bit, on exact inputs)."""
     g = _golden_s1_match()
     n0 = int(g['n0'])
     fe = g['features_eval']
@@ -1661,7 +1665,7 @@ def test_mutual_nn_at_full_size_on_the_reference_descriptors():
     ra, ca, mu = ra.cpu().numpy().astype(np.int64), ca.cpu().numpy().astype(np.int64), mu.cpu().numpy().astype(bool)
     S64, T64 = S.astype(np.float64), T.astype(np.float64)
 
-    def check(ours, ref, A, B, what):
+    def check(ours, ref, A, B, what, cap):
         flip = np.nonzero(ours != ref)[0]
         d_o = np.linalg.norm(A[flip] - B[ours[flip]], axis=1)
         d_r = np.linalg.norm(A[flip] - B[ref[flip]], axis=1)
@@ -1669,10 +1673,10 @@ def test_mutual_nn_at_full_size_on_the_reference_descriptors():
         # candidates closer than that in d^2 are a tie for BOTH implementations
         assert np.all(np.abs(d_o ** 2 - d_r ** 2) < 8e-6), (what, float(np.abs(d_o ** 2 - d_r ** 2).max()))
         # (random-init descriptors are strongly clustered: ~2 % of the rows have a second candidate within that band)
-        assert len(flip) <= 0.05 * len(ours), (what, len(flip), len(ours))
+        assert len(flip) <= cap, (what, len(flip), len(ours))
         return len(flip)
-    f_rows = check(ra, g['row_argmin'], S64, T64, 'row argmin')
-    f_cols = check(ca, g['col_argmin'], T64, S64, 'column argmin')
+    f_rows = check(ra, g['row_argmin'], S64, T64, 'row argmin', 2 * 410)
+    f_cols = check(ca, g['col_argmin'], T64, S64, 'column argmin', 2 * 340)
     ours = set(map(tuple, np.stack([np.nonzero(mu)[0], ra[mu]], 1).tolist()))
     ref = set(map(tuple, g['corr_all'].tolist()))
     assert len(ref) > 1000 and len(ours ^ ref) <= 2 * (f_rows + f_cols), (len(ours), len(ref), f_rows, f_cols)
