@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libd3feat_hip.so")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
-           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
+           "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_extract.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
            "tsdf_mesh_sparse.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -80,6 +80,29 @@ def _tsdf_reader_signatures():
             sigs["d3f_tsdf_raycast" + stem + host] = (_i, [_vp, _vp] + cast + [_vp])
             sigs["d3f_tsdf_raycast" + stem + "_color" + host] = (_i, [_vp, _vp, _vp, _i] + cast + [_vp, _vp])
             sigs["d3f_tsdf_sample_color" + stem + host] = (_i, [_vp, _vp, _i] + model + points + [_vp])
+    return sigs
+
+
+def _tsdf_surface_signatures():
+    """The sixteen entry points that take the surface out of a fused model (csrc/tsdf_extract.hip, csrc/tsdf_mesh.hip,
+    csrc/tsdf_mesh_sparse.hip): d3f_tsdf[_sparse]_{extract,mesh} x {_ws_bytes, _count, the emit form, _host}, each from
+    the same pieces: D and w, the model's tables (the count forms take neither origin nor voxel), min_weight, the
+    capacities and the outputs, the workspace and the stream (the twins take neither)."""
+    dense = ([_vp, _vp, _i, _i64],                             # vol_start, dims, V, total_voxels
+             [_vp, _vp, _vp, _vp, _i, _i64])                   # vol_start, origin, dims, voxel, V, total_voxels
+    rows = [_vp, _vp, _vp, _vp]                                # lattice_start, brick_start, brick_index, brick_coord
+    bricks = (rows + [_vp, _i, _i64, _i64],                    # ..., dims, V, lattice_bricks, bricks
+              rows + [_vp, _vp, _vp, _i, _i64, _i64])          # ..., origin, dims, voxel, V, lattice_bricks, bricks
+    ws = [_vp, _sz, _vp]                                       # ws, ws_bytes, stream
+    sigs = {}
+    for stem, (counted, model) in (("", dense), ("_sparse", bricks)):
+        for what, starts, capacities, rest in (("extract", [_vp], [_i64], [_vp, _vp, _vp]),        # points, point_start, status
+                                               ("mesh", [_vp, _vp], [_i64, _i64], [_vp] * 6)):    # vertices, normals, faces, the starts, status
+            name = "d3f_tsdf" + stem + "_" + what
+            sigs[name + "_ws_bytes"] = (_sz, [_i64])
+            sigs[name + "_count"] = (_i, [_vp, _vp] + counted + [_f] + starts + ws)
+            sigs[name] = (_i, [_vp, _vp] + model + [_f, _i] + capacities + rest + ws)
+            sigs[name + "_host"] = (_i, [_vp, _vp] + model + [_f] + capacities + rest)
     return sigs
 
 
@@ -249,11 +272,6 @@ SIGNATURES = {
     "d3f_pose_graph_edge_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_tsdf_bounds": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
     "d3f_tsdf_bounds_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
-    "d3f_tsdf_extract_ws_bytes": (_sz, [C.c_int64]),
-    "d3f_tsdf_extract_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
-                              _vp]),
-    "d3f_tsdf_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, _vp, _vp, _vp]),
     "d3f_tsdf_sparse_mark": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _vp,
                                   _vp]),
     "d3f_tsdf_sparse_mark_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f,
@@ -261,26 +279,6 @@ SIGNATURES = {
     "d3f_tsdf_sparse_index_ws_bytes": (_sz, [C.c_int64]),
     "d3f_tsdf_sparse_index": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_tsdf_sparse_index_host": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
-    "d3f_tsdf_sparse_extract_ws_bytes": (_sz, [C.c_int64]),
-    "d3f_tsdf_sparse_extract_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _sz,
-                                           _vp]),
-    "d3f_tsdf_sparse_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
-                                     C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_sparse_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
-                                          C.c_int64, _vp, _vp, _vp]),
-    "d3f_tsdf_mesh_ws_bytes": (_sz, [C.c_int64]),
-    "d3f_tsdf_mesh_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
-                           _vp, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
-                                _vp, _vp]),
-    "d3f_tsdf_sparse_mesh_ws_bytes": (_sz, [C.c_int64]),
-    "d3f_tsdf_sparse_mesh_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _vp,
-                                        _sz, _vp]),
-    "d3f_tsdf_sparse_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
-                                  C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
-                                       C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
     "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
@@ -308,6 +306,7 @@ SIGNATURES = {
 
 SIGNATURES.update(_tsdf_integrate_signatures())
 SIGNATURES.update(_tsdf_reader_signatures())
+SIGNATURES.update(_tsdf_surface_signatures())
 
 ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failure"}
 STATUS_BITS = {1: "a query has more in-radius candidates than the kernel can rank (512)",

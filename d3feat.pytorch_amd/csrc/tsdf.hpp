@@ -1,5 +1,6 @@
-// TSDF fusion of depth frames into dense volumes and the extraction of their zero crossings (tsdf.hip: d3f_tsdf_bounds,
-// d3f_tsdf_extract; tsdf_integrate.hip: d3f_tsdf_integrate, dense and sparse; and their host twins).  Everything here
+// TSDF fusion of depth frames into dense volumes and the extraction of their zero crossings (tsdf.hip: d3f_tsdf_bounds;
+// tsdf_integrate.hip: d3f_tsdf_integrate, tsdf_extract.hip: d3f_tsdf_extract, both dense and sparse; and their host
+// twins).  Everything here
 // is __host__ __device__ and reads no state: the kernels and the host twins run this text, and ops.tsdf_numpy /
 // tsdf_extract_numpy restate it.  All arithmetic is f32 in exactly the order written; the library is built with
 // -ffp-contract=off and f32 division is correctly rounded on both sides, so device, host twin and NumPy agree bit for

@@ -1,8 +1,9 @@
 // What the tsdf*.hip files share beyond the rules of tsdf.hpp and tsdf_sparse.hpp: the batch of volumes and its
-// frames (Volumes, beside Bricks the two models tsdf_integrate.hip and tsdf_raycast.hip are templated on), the position
-// of a voxel in its lattice, the argument checks (dense and sparse), and the two-level exclusive scan of per-block
-// counts (count per block of 256 voxels -> scan -> emit at group offset + block offset + in-block rank).  Included by
-// .hip files only.
+// frames (Volumes, beside Bricks the two models tsdf_integrate.hip, tsdf_extract.hip and tsdf_raycast.hip are templated
+// on), the position of a voxel in its lattice, the cells a host twin walks, the argument checks (dense and sparse), the
+// two-level exclusive scan of per-block counts with its workspace, and the two things a workgroup does around it in
+// tsdf_extract.hip, tsdf_mesh.hip and tsdf_mesh_sparse.hip (count per block of 256 cells -> scan -> emit at group offset
+// + block offset + in-block rank): workgroup_sum() and rank_in_wave() / words_below().  Included by .hip files only.
 #pragma once
 #include "common.hpp"
 #include "tsdf.hpp"
@@ -44,6 +45,19 @@ __host__ __device__ inline void locate(const Volumes& b, int v, int64_t local, i
   iy = (int)(row % ny);
   iz = (int)(row / ny);
 }
+
+// the cells (voxels; pool slots) that a host twin walks for volume v, [begin, end), and where the volume or the brick
+// of cell `at` begins
+inline void volume_cells(const Volumes& b, int v, int64_t& begin, int64_t& end) {
+  begin = b.vol_start[v];
+  end = b.vol_start[v + 1];
+}
+inline void volume_cells(const Bricks& k, int v, int64_t& begin, int64_t& end) {
+  begin = k.brick_start[v] * kBrickVoxels;
+  end = k.brick_start[v + 1] * kBrickVoxels;
+}
+inline int64_t cell_first(const Volumes& b, int v, int64_t) { return b.vol_start[v]; }
+inline int64_t cell_first(const Bricks&, int, int64_t at) { return at - at % kBrickVoxels; }
 
 // -------------------------------------------------------------------------------------------------- argument checks
 static inline bool batch_ok(int V, int64_t total) { return V >= 1 && V <= D3F_TSDF_MAX_VOLUMES && total >= 0; }
@@ -179,6 +193,53 @@ static inline int run_block_scan(const BlockScan& s, int64_t blocks, int64_t* gr
   scan_totals_kernel<<<1, kScanThreads, 0, stream>>>(s.group_total, s.groups, s.group_offset, grand_total);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
+}
+
+struct ScanWs : BlockScan {     // one scan over `counts` counts (blocks of cells; lattice bricks) in a workspace
+  size_t bytes;
+  ScanWs(void* ws, int64_t counts) {
+    d3f::Carver c(ws);
+    carve(c, counts);
+    bytes = d3f::align_up(c.off, 256);
+  }
+};
+
+// ------------------------------------------------------------------- a workgroup of kThreads: the count and the rank
+constexpr int kWaves = kThreads / D3F_WAVE;
+
+// the sum of `n` over the workgroup, in thread 0.  One barrier, before the sum: the other waves are not held until
+// thread 0 has added up, so wave_total [kWaves] must not be written again before another barrier
+__device__ inline int workgroup_sum(int n, int* wave_total) {
+  n = d3f::wave_sum_i(n);
+  if (d3f::lane_id() == 0) wave_total[threadIdx.x / D3F_WAVE] = n;
+  __syncthreads();
+  int s = 0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < kWaves; ++k) s += wave_total[k];
+  return s;
+}
+
+// the rank of a thread's first item among the items of its workgroup, in two steps around ONE barrier of the caller's.
+// Before it: the set bits of `mask` (bits 0..2, an item each) in the lower lanes of this wave are returned, and lane 0
+// writes those of the whole wave to totals[word].  After it: words_below() adds the words under `word`.  A wave that
+// ranks several masks gives each its own word (or its own array), in the order of the output.
+__device__ inline int rank_in_wave(int mask, int* totals, int word) {
+  const int lane = d3f::lane_id();
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int before = 0, total = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const unsigned long long m = __ballot((mask >> a) & 1);
+    before += __popcll(m & below);
+    total += __popcll(m);
+  }
+  if (lane == 0) totals[word] = total;
+  return before;
+}
+__device__ inline int words_below(const int* totals, int word) {
+  int s = 0;
+  for (int k = 0; k < word; ++k) s += totals[k];
+  return s;
 }
 
 }  // namespace tsdf

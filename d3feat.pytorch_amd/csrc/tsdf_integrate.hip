@@ -15,7 +15,7 @@
 //             plane of the brick), each thread owns slots t and t + 256.  A slot beyond dims is not in the lattice: it
 //             holds 0, and kInto leaves it as it is.
 // The host twins run the same text on the CPU, cell after cell, and make no GPU call.
-#include "tsdf_batch.hpp"   // Volumes, Frames, locate(), the argument checks
+#include "tsdf_batch.hpp"   // Volumes, Frames, locate(), volume_cells() / cell_first() of the twins, the argument checks
 #include "tsdf_color.hpp"   // includes tsdf_sparse.hpp (Bricks, slot_voxel) and the rule of the colour
 
 namespace {
@@ -54,18 +54,6 @@ __host__ __device__ inline bool cell_voxel(const Volumes& b, int v, int64_t, int
 __host__ __device__ inline bool cell_voxel(const Bricks& k, int v, int64_t first, int64_t off, int i[3]) {
   return slot_voxel(k.dims + 3 * (size_t)v, k.brick_coord + 3 * (size_t)(first / kBrickVoxels), (int)off, i);
 }
-
-// the host twin's cells of volume v, [begin, end), and where the volume or brick of cell `at` begins
-inline void volume_cells(const Volumes& b, int v, int64_t& begin, int64_t& end) {
-  begin = b.vol_start[v];
-  end = b.vol_start[v + 1];
-}
-inline void volume_cells(const Bricks& k, int v, int64_t& begin, int64_t& end) {
-  begin = k.brick_start[v] * kBrickVoxels;
-  end = k.brick_start[v + 1] * kBrickVoxels;
-}
-inline int64_t cell_first(const Volumes& b, int v, int64_t) { return b.vol_start[v]; }
-inline int64_t cell_first(const Bricks&, int, int64_t at) { return at - at % kBrickVoxels; }
 
 // the argument checks, in the three steps of integrate() below.  `largest`: max_volume_voxels of the dense device
 // forms, which sizes their grid (the dense twins, which ignore theirs, pass total_voxels); the bricks of the sparse

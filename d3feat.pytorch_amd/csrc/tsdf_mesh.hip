@@ -1,5 +1,5 @@
 // Triangle meshes with normals from a batch of TSDF volumes (include/d3feat_hip.h: d3f_tsdf_mesh_count, d3f_tsdf_mesh;
-// the rule is csrc/tsdf_mesh.hpp).  The shape of tsdf.hip's extract: one thread per voxel, 256 per workgroup.
+// the rule is csrc/tsdf_mesh.hpp).  The shape of tsdf_extract.hip: one thread per voxel, 256 per workgroup.
 //   count   per block the ACTIVE cells (vertices) and the triangles, in one pass; the ballot of ACTIVE cells is kept,
 //           one bit per voxel (a 64-bit word per wave).
 //   scan    the two-level exclusive scan of tsdf_batch.hpp, over the vertex counts and over the triangle counts.
@@ -12,27 +12,13 @@
 // The host twin runs the same tsdf_mesh.hpp text on the CPU and makes no GPU call.
 #include <vector>
 
-#include "tsdf_batch.hpp"
-#include "tsdf_mesh.hpp"
+#include "tsdf_mesh_batch.hpp"   // includes tsdf_batch.hpp and tsdf_mesh.hpp
 
 namespace {
 
 using namespace d3f::tsdf;
 
-constexpr int kWaves = kThreads / D3F_WAVE;
-
-struct MeshWs {
-  BlockScan vertices, faces;
-  uint64_t* active;        // [blocks * kWaves] ballots of the ACTIVE cells
-  size_t bytes;
-  MeshWs(void* ws, int64_t blocks) {
-    d3f::Carver c(ws);
-    vertices.carve(c, blocks);
-    faces.carve(c, blocks);
-    active = c.take<uint64_t>((size_t)blocks * kWaves);
-    bytes = d3f::align_up(c.off, 256);
-  }
-};
+constexpr int kWords = kWaves;            // ballot words per block: one per wave
 
 // what global voxel g of volume v emits: its neighbourhood, and where it lies
 struct Voxel {
@@ -49,18 +35,6 @@ __host__ __device__ inline Voxel look(const Volumes& b, const float* D, const fl
   locate(b, v, x.local, x.ix, x.iy, x.iz, x.nx, x.ny, nz);
   x.h = hood(D + base, w + base, x.local, b.vol_start[v + 1] - base, x.ix, x.iy, x.iz, x.nx, x.ny, nz, min_weight);
   return x;
-}
-
-// the sum of `n` over the workgroup, in thread 0
-__device__ inline int workgroup_sum(int n, int* wave_total) {
-  n = d3f::wave_sum_i(n);
-  if (d3f::lane_id() == 0) wave_total[threadIdx.x / D3F_WAVE] = n;
-  __syncthreads();
-  int s = 0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < kWaves; ++k) s += wave_total[k];
-  __syncthreads();
-  return s;
 }
 
 __global__ void __launch_bounds__(kThreads) mesh_count_kernel(Volumes b, const float* __restrict__ D,
@@ -81,6 +55,7 @@ __global__ void __launch_bounds__(kThreads) mesh_count_kernel(Volumes b, const f
   const unsigned long long ballot = __ballot(is_active);
   if (d3f::lane_id() == 0) active[(size_t)blockIdx.x * kWaves + threadIdx.x / D3F_WAVE] = ballot;
   const int nv = workgroup_sum(is_active, wave_total);
+  __syncthreads();                                 // wave_total is written again
   const int nf = workgroup_sum(triangles, wave_total);
   if (threadIdx.x == 0) {
     vertex_count[blockIdx.x] = nv;
@@ -98,16 +73,6 @@ __host__ __device__ inline int64_t vertex_position(const Offsets* block_offset, 
   return pos + __builtin_popcountll(active[word] & ((1ull << (g % D3F_WAVE)) - 1ull));
 }
 
-struct MeshOut {
-  float* vertices;          // [vertex_capacity, 3]
-  float* normals;           // [vertex_capacity, 3]
-  int32_t* faces;           // [face_capacity, 3]
-  int64_t* vertex_start;    // [V + 1]
-  int64_t* face_start;      // [V + 1]
-  int32_t* status;
-  int64_t vertex_capacity, face_capacity;
-};
-
 // the vertex of voxel x's ACTIVE cell into row pos, the triangles of its edges into the rows from fpos on; returns the
 // status bits.  vertex_of(global voxel) gives the global row of that voxel's vertex.
 template <typename VertexOf>
@@ -115,40 +80,14 @@ __host__ __device__ inline int emit_voxel(const Volumes& b, const float* D, int 
                                           int64_t pos, int64_t fpos, const MeshOut& out, VertexOf vertex_of) {
   int bits = 0;
   const int64_t base = b.vol_start[v];
-  if (edges) {
-    if (pos < out.vertex_capacity)
-      cell_vertex(D + base, x.local, x.ix, x.iy, x.iz, x.nx, x.ny, edges, b.origin + 3 * v, b.voxel[v],
-                  out.vertices + 3 * pos, out.normals + 3 * pos);
-    else
-      bits |= D3F_TSDF_ST_OVERFLOW;
-  }
+  if (edges && vertex_fits(out, pos, bits))
+    cell_vertex(D + base, x.local, x.ix, x.iy, x.iz, x.nx, x.ny, edges, b.origin + 3 * v, b.voxel[v],
+                out.vertices + 3 * pos, out.normals + 3 * pos);
   if (!quads) return bits;
   const int64_t first = vertex_of(base);          // vertex_start[v]
-  for (int a = 0; a < 3; ++a) {
-    if (!((quads >> a) & 1)) continue;
-    if (fpos >= out.face_capacity) {
-      bits |= D3F_TSDF_ST_FACE_OVERFLOW;
-      fpos += 2;
-      continue;
-    }
-    int32_t q[4], t[6];
-    bool fits = true;      // false: more than 2^31 - 1 vertices in one volume, and no wrapped index is written
-    for (int k = 0; k < 4; ++k) {
-      const int64_t row = vertex_of(base + face_cell(x.local, x.nx, x.ny, a, k)) - first;
-      fits = fits && row <= 0x7fffffff;
-      q[k] = (int32_t)row;
-    }
-    quad_triangles(q, (x.h.neg >> kHoodSelf) & 1u, t);
-    for (int tri = 0; tri < 2; ++tri, ++fpos) {
-      if (fpos >= out.face_capacity)
-        bits |= D3F_TSDF_ST_FACE_OVERFLOW;
-      else if (!fits)
-        bits |= D3F_TSDF_ST_OVERFLOW;
-      else
-        for (int r = 0; r < 3; ++r) out.faces[3 * fpos + r] = t[3 * tri + r];
-    }
-  }
-  return bits;
+  return bits | write_quads(out, quads, (x.h.neg >> kHoodSelf) & 1u, fpos, [&](int a, int n) {
+           return vertex_of(base + face_cell(x.local, x.nx, x.ny, a, n)) - first;
+         });
 }
 
 __global__ void __launch_bounds__(kThreads) mesh_emit_kernel(Volumes b, const float* __restrict__ D,
@@ -158,7 +97,7 @@ __global__ void __launch_bounds__(kThreads) mesh_emit_kernel(Volumes b, const fl
                                                              const int64_t* __restrict__ f_block_offset,
                                                              const int64_t* __restrict__ f_group_offset,
                                                              const uint64_t* __restrict__ active, MeshOut out) {
-  __shared__ int wave_vertices[kWaves], wave_triangles[kWaves];
+  __shared__ int wave_vertices[kWaves], wave_quads[kWaves];
   const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool live = g < b.total;
   Voxel x = {};
@@ -171,25 +110,11 @@ __global__ void __launch_bounds__(kThreads) mesh_emit_kernel(Volumes b, const fl
       quads = face_mask(x.h);
     }
   }
-  const int lane = d3f::lane_id(), wave = (int)threadIdx.x / D3F_WAVE;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const unsigned long long mv = __ballot(edges != 0);
-  int v_before = __popcll(mv & below), f_before = 0, f_total = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const unsigned long long m = __ballot((quads >> a) & 1);
-    f_before += 2 * __popcll(m & below);
-    f_total += 2 * __popcll(m);
-  }
-  if (lane == 0) {
-    wave_vertices[wave] = __popcll(mv);
-    wave_triangles[wave] = f_total;
-  }
+  const int wave = (int)threadIdx.x / D3F_WAVE;
+  int v_before = rank_in_wave(edges != 0, wave_vertices, wave), q_before = rank_in_wave(quads, wave_quads, wave);
   __syncthreads();
-  for (int k = 0; k < wave; ++k) {
-    v_before += wave_vertices[k];
-    f_before += wave_triangles[k];
-  }
+  v_before += words_below(wave_vertices, wave);
+  const int f_before = 2 * (q_before + words_below(wave_quads, wave));
   if (!live) return;
   const int64_t group = blockIdx.x / kScanThreads;
   const int64_t pos = v_group_offset[group] + v_block_offset[blockIdx.x] + v_before;
@@ -220,18 +145,13 @@ bool mesh_args_ok(const float* D, const float* w, const int64_t* vol_start, cons
          vertex_start && face_start;
 }
 
-bool mesh_out_ok(const float* origin, const float* voxel, const MeshOut& out) {
-  return origin && voxel && out.status && out.vertex_capacity >= 0 && out.face_capacity >= 0 &&
-         (out.vertex_capacity == 0 || (out.vertices && out.normals)) && (out.face_capacity == 0 || out.faces);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t d3f_tsdf_mesh_ws_bytes(int64_t total_voxels) {
   if (total_voxels < 0) return 0;
-  return MeshWs(nullptr, voxel_blocks(total_voxels)).bytes + 256;
+  return MeshWs(nullptr, voxel_blocks(total_voxels), kWords).bytes + 256;
 }
 
 int d3f_tsdf_mesh_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
@@ -239,7 +159,7 @@ int d3f_tsdf_mesh_count(const float* D, const float* w, const int64_t* vol_start
                         size_t ws_bytes, void* stream) {
   if (!mesh_args_ok(D, w, vol_start, dims, V, total_voxels, vertex_start, face_start) || !ws) return D3F_EINVAL;
   const int64_t blocks = voxel_blocks(total_voxels);
-  const MeshWs x(ws, blocks);
+  const MeshWs x(ws, blocks, kWords);
   if (ws_bytes < x.bytes) return D3F_EWORKSPACE;
   const Volumes b = {vol_start, nullptr, dims, nullptr, V, total_voxels};
   return run_mesh_count(b, D, w, min_weight, vertex_start, face_start, x, blocks, (hipStream_t)stream);
@@ -255,7 +175,7 @@ int d3f_tsdf_mesh(const float* D, const float* w, const int64_t* vol_start, cons
       !ws)
     return D3F_EINVAL;
   const int64_t blocks = voxel_blocks(total_voxels);
-  const MeshWs x(ws, blocks);
+  const MeshWs x(ws, blocks, kWords);
   if (ws_bytes < x.bytes) return D3F_EWORKSPACE;
   const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
   if (!counted) {

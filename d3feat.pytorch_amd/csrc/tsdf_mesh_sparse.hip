@@ -17,31 +17,17 @@
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   sparse_mesh_count_kernel  VGPRs 34, SGPRs 55, no scratch, LDS 5248 bytes, 8 waves per SIMD
-//   sparse_mesh_emit_kernel   VGPRs 58, SGPRs 79, no scratch, LDS 5280 bytes, 8 waves per SIMD
+//   sparse_mesh_emit_kernel   VGPRs 56, SGPRs 79, no scratch, LDS 5280 bytes, 8 waves per SIMD
 #include <vector>
 
-#include "tsdf_batch.hpp"
+#include "tsdf_mesh_batch.hpp"   // includes tsdf_batch.hpp and tsdf_mesh.hpp
 #include "tsdf_mesh_sparse.hpp"
 
 namespace {
 
 using namespace d3f::tsdf;
 
-constexpr int kWaves = kThreads / D3F_WAVE;
 constexpr int kSlotsPerThread = kBrickVoxels / kThreads;
-
-struct SparseMeshWs {
-  BlockScan vertices, faces;
-  uint64_t* active;        // [B * 8] ballots of the ACTIVE cells
-  size_t bytes;
-  SparseMeshWs(void* ws, int64_t B) {
-    d3f::Carver c(ws);
-    vertices.carve(c, B);
-    faces.carve(c, B);
-    active = c.take<uint64_t>((size_t)B * kBrickWords);
-    bytes = d3f::align_up(c.off, 256);
-  }
-};
 
 struct Halo {
   float value[kHaloVoxels];      // D
@@ -108,21 +94,11 @@ __global__ void __launch_bounds__(kThreads) sparse_mesh_count_kernel(Bricks k, c
     nv += t.edges != 0;
     nf += 2 * popcount3(t.quads);
   }
-  nv = d3f::wave_sum_i(nv);
-  nf = d3f::wave_sum_i(nf);
-  if (d3f::lane_id() == 0) {
-    wave_vertices[wave] = nv;
-    wave_triangles[wave] = nf;
-  }
-  __syncthreads();
+  nv = workgroup_sum(nv, wave_vertices);
+  nf = workgroup_sum(nf, wave_triangles);
   if (threadIdx.x == 0) {
-    int sv = 0, sf = 0;
-    for (int j = 0; j < kWaves; ++j) {
-      sv += wave_vertices[j];
-      sf += wave_triangles[j];
-    }
-    vertex_count[b] = sv;
-    face_count[b] = sf;
+    vertex_count[b] = nv;
+    face_count[b] = nf;
   }
 }
 
@@ -149,59 +125,25 @@ __host__ __device__ inline int64_t vertex_position(const int64_t* block_offset, 
   return pos + __builtin_popcountll(words[s >> 6] & ((1ull << (s & 63)) - 1ull));
 }
 
-struct MeshOut {
-  float* vertices;          // [vertex_capacity, 3]
-  float* normals;           // [vertex_capacity, 3]
-  int32_t* faces;           // [face_capacity, 3]
-  int32_t* status;
-  int64_t vertex_capacity, face_capacity;
-};
-
 // the vertex of slot t's ACTIVE cell into row pos, the triangles of its edges into the rows from fpos on; returns the
 // status bits.  vertex_of(pool row, slot) gives the global row of that cell's vertex; `first` = vertex_start[v].
 template <typename VertexOf>
 __host__ __device__ inline int emit_slot(const Bricks& k, const Halo& halo, int v, int64_t b, const Slot& t, int64_t pos,
                                          int64_t fpos, int64_t first, const MeshOut& out, VertexOf vertex_of) {
   int bits = 0;
-  if (t.edges) {
-    if (pos >= 0 && pos < out.vertex_capacity) {
-      const int32_t* c = k.brick_coord + 3 * (size_t)b;
-      float d[8];
-      halo_corners(halo.value, t.x, t.y, t.z, d);
-      cell_vertex(d, c[0] * 8 + t.x, c[1] * 8 + t.y, c[2] * 8 + t.z, t.edges, k.origin + 3 * (size_t)v, k.voxel[v],
-                  out.vertices + 3 * pos, out.normals + 3 * pos);
-    } else {
-      bits |= D3F_TSDF_ST_OVERFLOW;
-    }
+  if (t.edges && vertex_fits(out, pos, bits)) {
+    const int32_t* c = k.brick_coord + 3 * (size_t)b;
+    float d[8];
+    halo_corners(halo.value, t.x, t.y, t.z, d);
+    cell_vertex(d, c[0] * 8 + t.x, c[1] * 8 + t.y, c[2] * 8 + t.z, t.edges, k.origin + 3 * (size_t)v, k.voxel[v],
+                out.vertices + 3 * pos, out.normals + 3 * pos);
   }
-  for (int a = 0; a < 3; ++a) {
-    if (!((t.quads >> a) & 1)) continue;
-    if (fpos < 0 || fpos >= out.face_capacity) {
-      bits |= D3F_TSDF_ST_FACE_OVERFLOW;
-      fpos += 2;
-      continue;
-    }
-    int32_t q[4], tri[6];
-    bool fits = true;      // false: more than 2^31 - 1 vertices in one volume, and no wrapped index is written
-    for (int n = 0; n < 4; ++n) {
-      int j, slot;
-      face_cell_sparse(t.x, t.y, t.z, a, n, j, slot);
-      const int64_t row = halo.rows[j];                      // there: the cell is COMPLETE, so its lowest voxel is VALID
-      const int64_t at = (row >= 0 ? vertex_of(row, slot) : first) - first;
-      fits = fits && at >= 0 && at <= 0x7fffffff;
-      q[n] = (int32_t)at;
-    }
-    quad_triangles(q, (t.h.neg >> kHoodSelf) & 1u, tri);
-    for (int n = 0; n < 2; ++n, ++fpos) {
-      if (fpos >= out.face_capacity)
-        bits |= D3F_TSDF_ST_FACE_OVERFLOW;
-      else if (!fits)
-        bits |= D3F_TSDF_ST_OVERFLOW;
-      else
-        for (int r = 0; r < 3; ++r) out.faces[3 * fpos + r] = tri[3 * n + r];
-    }
-  }
-  return bits;
+  return bits | write_quads(out, t.quads, (t.h.neg >> kHoodSelf) & 1u, fpos, [&](int a, int n) {
+           int j, slot;
+           face_cell_sparse(t.x, t.y, t.z, a, n, j, slot);
+           const int64_t row = halo.rows[j];                 // there: the cell is COMPLETE, so its lowest voxel is VALID
+           return (row >= 0 ? vertex_of(row, slot) : first) - first;
+         });
 }
 
 __global__ void __launch_bounds__(kThreads) sparse_mesh_emit_kernel(Bricks k, const float* __restrict__ D,
@@ -209,32 +151,19 @@ __global__ void __launch_bounds__(kThreads) sparse_mesh_emit_kernel(Bricks k, co
                                                                     BlockScan vs, BlockScan fs,
                                                                     const uint64_t* __restrict__ active, MeshOut out) {
   __shared__ Halo halo;
-  __shared__ int word_vertices[kBrickWords], word_triangles[kBrickWords];
+  __shared__ int word_vertices[kBrickWords], word_quads[kBrickWords];
   const int64_t b = (int64_t)blockIdx.x;
   if (b >= k.B) return;                                   // uniform: the whole workgroup
   const int v = owner(k.brick_start, k.V, b);
   stage_halo(k, D, w, min_weight, v, b, halo);
-  const int lane = d3f::lane_id(), wave = (int)threadIdx.x / D3F_WAVE;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const int wave = (int)threadIdx.x / D3F_WAVE;
   Slot t[kSlotsPerThread];
-  int v_before[kSlotsPerThread], f_before[kSlotsPerThread];
+  int v_before[kSlotsPerThread], q_before[kSlotsPerThread];
 #pragma unroll
   for (int half = 0; half < kSlotsPerThread; ++half) {
     t[half] = look(halo, half * kThreads + (int)threadIdx.x);
-    const unsigned long long mv = __ballot(t[half].edges != 0);
-    v_before[half] = __popcll(mv & below);
-    f_before[half] = 0;
-    int f_total = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const unsigned long long m = __ballot((t[half].quads >> a) & 1);
-      f_before[half] += 2 * __popcll(m & below);
-      f_total += 2 * __popcll(m);
-    }
-    if (lane == 0) {
-      word_vertices[half * kWaves + wave] = __popcll(mv);
-      word_triangles[half * kWaves + wave] = f_total;
-    }
+    v_before[half] = rank_in_wave(t[half].edges != 0, word_vertices, half * kWaves + wave);
+    q_before[half] = rank_in_wave(t[half].quads, word_quads, half * kWaves + wave);
   }
   __syncthreads();
   const int64_t group = b / kScanThreads;
@@ -247,11 +176,9 @@ __global__ void __launch_bounds__(kThreads) sparse_mesh_emit_kernel(Bricks k, co
 #pragma unroll
   for (int half = 0; half < kSlotsPerThread; ++half) {
     if (!t[half].edges && !t[half].quads) continue;
-    int64_t pos = row_vertex + v_before[half], fpos = row_face + f_before[half];
-    for (int j = 0; j < half * kWaves + wave; ++j) {
-      pos += word_vertices[j];
-      fpos += word_triangles[j];
-    }
+    const int word = half * kWaves + wave;
+    const int64_t pos = row_vertex + v_before[half] + words_below(word_vertices, word);
+    const int64_t fpos = row_face + 2 * (q_before[half] + words_below(word_quads, word));
     bits |= emit_slot(k, halo, v, b, t[half], pos, fpos, first, out, [&](int64_t row, int slot) {
       return vertex_position(vs.block_offset, vs.group_offset, active, row, slot);
     });
@@ -260,7 +187,7 @@ __global__ void __launch_bounds__(kThreads) sparse_mesh_emit_kernel(Bricks k, co
 }
 
 int run_count(const Bricks& k, const float* D, const float* w, float min_weight, int64_t* vertex_start,
-              int64_t* face_start, const SparseMeshWs& x, hipStream_t stream) {
+              int64_t* face_start, const MeshWs& x, hipStream_t stream) {
   sparse_mesh_count_kernel<<<(unsigned)k.B, kThreads, 0, stream>>>(k, D, w, min_weight, x.vertices.block_count,
                                                                   x.faces.block_count, x.active);
   D3F_LAUNCH_CHECK();
@@ -280,18 +207,13 @@ bool tables_ok(const float* D, const float* w, const int64_t* lattice_start, con
   return D && w && lattice_start && brick_start && brick_index && brick_coord && dims && vertex_start && face_start;
 }
 
-bool out_ok(const float* origin, const float* voxel, const MeshOut& out) {
-  return origin && voxel && out.status && out.vertex_capacity >= 0 && out.face_capacity >= 0 &&
-         (out.vertex_capacity == 0 || (out.vertices && out.normals)) && (out.face_capacity == 0 || out.faces);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t d3f_tsdf_sparse_mesh_ws_bytes(int64_t bricks) {
   if (bricks < 0) return 0;
-  return SparseMeshWs(nullptr, bricks).bytes + 256;
+  return MeshWs(nullptr, bricks, kBrickWords).bytes + 256;
 }
 
 int d3f_tsdf_sparse_mesh_count(const float* D, const float* w, const int64_t* lattice_start,
@@ -301,7 +223,7 @@ int d3f_tsdf_sparse_mesh_count(const float* D, const float* w, const int64_t* la
   if (!pool_ok(V, lattice_bricks, bricks) || bricks == 0 ||
       !tables_ok(D, w, lattice_start, brick_start, brick_index, brick_coord, dims, vertex_start, face_start) || !ws)
     return D3F_EINVAL;
-  const SparseMeshWs x(ws, bricks);
+  const MeshWs x(ws, bricks, kBrickWords);
   if (ws_bytes < x.bytes) return D3F_EWORKSPACE;
   const Bricks k = {lattice_start, brick_start, brick_index, brick_coord, nullptr, dims, nullptr, V, lattice_bricks,
                     bricks};
@@ -314,12 +236,12 @@ int d3f_tsdf_sparse_mesh(const float* D, const float* w, const int64_t* lattice_
                          float min_weight, int counted, int64_t vertex_capacity, int64_t face_capacity, float* vertices,
                          float* normals, int32_t* faces, int64_t* vertex_start, int64_t* face_start, int32_t* status,
                          void* ws, size_t ws_bytes, void* stream) {
-  const MeshOut out = {vertices, normals, faces, status, vertex_capacity, face_capacity};
+  const MeshOut out = {vertices, normals, faces, vertex_start, face_start, status, vertex_capacity, face_capacity};
   if (!pool_ok(V, lattice_bricks, bricks) || bricks == 0 ||
       !tables_ok(D, w, lattice_start, brick_start, brick_index, brick_coord, dims, vertex_start, face_start) ||
-      !out_ok(origin, voxel, out) || !ws)
+      !mesh_out_ok(origin, voxel, out) || !ws)
     return D3F_EINVAL;
-  const SparseMeshWs x(ws, bricks);
+  const MeshWs x(ws, bricks, kBrickWords);
   if (ws_bytes < x.bytes) return D3F_EWORKSPACE;
   const Bricks k = {lattice_start, brick_start, brick_index, brick_coord, origin, dims, voxel, V, lattice_bricks,
                     bricks};
@@ -339,9 +261,9 @@ int d3f_tsdf_sparse_mesh_host(const float* D, const float* w, const int64_t* lat
                               float min_weight, int64_t vertex_capacity, int64_t face_capacity, float* vertices,
                               float* normals, int32_t* faces, int64_t* vertex_start, int64_t* face_start,
                               int32_t* status) {
-  const MeshOut out = {vertices, normals, faces, status, vertex_capacity, face_capacity};
+  const MeshOut out = {vertices, normals, faces, vertex_start, face_start, status, vertex_capacity, face_capacity};
   if (!pool_ok(V, lattice_bricks, bricks) || !lattice_start || !brick_start || !brick_index || !dims || !vertex_start ||
-      !face_start || !out_ok(origin, voxel, out) || (bricks > 0 && (!D || !w || !brick_coord)) ||
+      !face_start || !mesh_out_ok(origin, voxel, out) || (bricks > 0 && (!D || !w || !brick_coord)) ||
       !host_tables_ok(lattice_start, brick_start, dims, V, lattice_bricks, bricks) ||
       !host_coords_ok(lattice_start, brick_start, brick_coord, dims, V))
     return D3F_EINVAL;

@@ -1,6 +1,6 @@
 // Sparse TSDF volumes: a dense table over bricks of 8 x 8 x 8 voxels plus a compact pool that holds D and w only for
-// the bricks a depth pixel can reach within the truncation distance (tsdf_sparse.hip: d3f_tsdf_sparse_mark, _index,
-// _extract; tsdf_integrate.hip: _integrate; and their host twins).  Stated in the terms of tsdf.hpp, which it includes: everything here is
+// the bricks a depth pixel can reach within the truncation distance (tsdf_sparse.hip: d3f_tsdf_sparse_mark, _index;
+// tsdf_integrate.hip: _integrate; tsdf_extract.hip: _extract; and their host twins).  Stated in the terms of tsdf.hpp, which it includes: everything here is
 // __host__ __device__ and reads no state, all arithmetic is f32 in exactly the order written (-ffp-contract=off), and
 // ops.tsdf_allocate_numpy / tsdf_sparse_numpy / tsdf_extract_sparse_numpy restate it, so device, host twin and NumPy
 // agree bit for bit -- and, for every voxel that can produce output, with the dense path of tsdf.hpp.

@@ -3524,10 +3524,16 @@ def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin
                            (origin, dims, voxel), trunc, depth_scale, depth_max, into, color)
 
 
-def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
+def _pool_tensors(D, w, device):
+    """D and w as the extract and mesh functions take them -- tensors, arrays or lists, wherever they are -- as flat
+    float32 tensors on ``device``, named as ``_dense_model`` / ``_sparse_model`` want them."""
     D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else
             torch.as_tensor(a, dtype=torch.float32) for a in (D, w))
-    D, w = D.to(device).contiguous().view(-1), w.to(device).contiguous().view(-1)
+    return ("D", D.to(device).contiguous().view(-1)), ("w", w.to(device).contiguous().view(-1))
+
+
+def _tsdf_extract_inputs(D, w, origin, dims, voxel, device):
+    (_, D), (_, w) = _pool_tensors(D, w, device)
     V = int(np.asarray(dims.cpu() if isinstance(dims, torch.Tensor) else dims).reshape(-1, 3).shape[0])
     o, n, vx, _, vol_start = _tsdf_volumes(origin, dims, voxel, V)
     total = int(vol_start[-1])
@@ -3557,45 +3563,15 @@ def tsdf_extract(D, w, vol_start, origin, dims, voxel, min_weight=1.0, capacity=
     run back to back into ``capacity`` rows, points beyond it are dropped and TSDF_ST_OVERFLOW is set in the status word
     (``return_status=True`` appends it as a device int32 [1] tensor; ``point_start`` is complete either way)."""
     dev = _tsdf_device()
-    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, dev)
-    _check_vol_start(vol_start, tvs)
-    L = _native.lib()
-    nbytes = L.d3f_tsdf_extract_ws_bytes(total)
-    ws = _ws(nbytes, dev)
-    point_start = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    counted = 0
-    with _region("tsdf_extract"):
-        if capacity is None:
-            _native.check(L.d3f_tsdf_extract_count(_p(D), _p(w), _p(tvs), _p(tn), V, total, float(min_weight),
-                                                   _p(point_start), _p(ws), nbytes, _stream()),
-                          "d3f_tsdf_extract_count")
-            capacity = int(point_start[V].item())          # the one read-back: the size of the result
-            counted = 1
-        points = torch.empty((int(capacity), 3), dtype=torch.float32, device=dev)
-        _native.check(L.d3f_tsdf_extract(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight),
-                                         counted, int(capacity), _p(points) if capacity else None, _p(point_start),
-                                         _p(status), _p(ws), nbytes, _stream()), "d3f_tsdf_extract")
-    return (points, point_start, status) if return_status else (points, point_start)
+    return _tsdf_extract(False, dev, _dense_model(False, dev, _pool_tensors(D, w, dev), vol_start, origin, dims, voxel),
+                         min_weight, capacity, return_status)
 
 
 def tsdf_extract_host(D, w, vol_start, origin, dims, voxel, min_weight=1.0, capacity=None, return_status=False):
     """The host twin of ``tsdf_extract`` (d3f_tsdf_extract_host): CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
-    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, cpu)
-    _check_vol_start(vol_start, tvs)
-    fn = _native.lib().d3f_tsdf_extract_host
-    point_start = torch.zeros(V + 1, dtype=torch.int64)
-    status = torch.zeros(1, dtype=torch.int32)
-    if capacity is None:
-        scratch = torch.zeros(1, dtype=torch.int32)
-        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), 0, None,
-                         _p(point_start), _p(scratch)), "d3f_tsdf_extract_host")
-        capacity = int(point_start[V])
-    points = torch.empty((int(capacity), 3), dtype=torch.float32)
-    _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), int(capacity),
-                     _p(points) if capacity else None, _p(point_start), _p(status)), "d3f_tsdf_extract_host")
-    return (points, point_start, status) if return_status else (points, point_start)
+    return _tsdf_extract(True, cpu, _dense_model(True, cpu, _pool_tensors(D, w, cpu), vol_start, origin, dims, voxel),
+                         min_weight, capacity, return_status)
 
 
 def _lattice_axes(local, n, o, vx):
@@ -3940,9 +3916,7 @@ def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera,
 
 
 def _sparse_pool(D, w, sv, device):
-    D, w = (torch.from_numpy(np.array(a, dtype=np.float32)) if isinstance(a, np.ndarray) else
-            torch.as_tensor(a, dtype=torch.float32) for a in (D, w))
-    D, w = D.to(device).contiguous().view(-1), w.to(device).contiguous().view(-1)
+    (_, D), (_, w) = _pool_tensors(D, w, device)
     if int(D.numel()) != sv.bricks * TSDF_BRICK_VOXELS or int(w.numel()) != int(D.numel()):
         raise ValueError("D and w must hold the %d x 512 slots of the allocated bricks, got %d and %d"
                          % (sv.bricks, D.numel(), w.numel()))
@@ -3955,52 +3929,15 @@ def tsdf_extract_sparse(D, w, sv, min_weight=1.0, capacity=None, return_status=F
     they are ``tsdf_extract``'s points of the dense volumes, bit for bit.  ``D``, ``w`` as ``tsdf_integrate_sparse``
     returns them; ``capacity``, ``return_status`` and the one read-back as for ``tsdf_extract``."""
     dev = _tsdf_device()
-    D, w = _sparse_pool(D, w, sv, dev)
-    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, dev)
-    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
-    point_start = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    if B == 0:                                                 # nothing allocated: no kernel has anything to do
-        points = torch.empty((int(capacity or 0), 3), dtype=torch.float32, device=dev)
-        return (points, point_start, status) if return_status else (points, point_start)
-    L = _native.lib()
-    nbytes = L.d3f_tsdf_sparse_extract_ws_bytes(B)
-    ws = _ws(nbytes, dev)
-    counted = 0
-    with _region("tsdf_extract_sparse"):
-        if capacity is None:
-            _native.check(L.d3f_tsdf_sparse_extract_count(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(tn), V,
-                                                          lattice, B, float(min_weight), _p(point_start), _p(ws),
-                                                          nbytes, _stream()), "d3f_tsdf_sparse_extract_count")
-            capacity = int(point_start[V].item())          # the one read-back: the size of the result
-            counted = 1
-        points = torch.empty((int(capacity), 3), dtype=torch.float32, device=dev)
-        _native.check(L.d3f_tsdf_sparse_extract(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(to), _p(tn), _p(tvx),
-                                                V, lattice, B, float(min_weight), counted, int(capacity),
-                                                _p(points) if capacity else None, _p(point_start), _p(status), _p(ws),
-                                                nbytes, _stream()), "d3f_tsdf_sparse_extract")
-    return (points, point_start, status) if return_status else (points, point_start)
+    return _tsdf_extract(False, dev, _sparse_model(False, dev, _pool_tensors(D, w, dev), sv), min_weight, capacity,
+                         return_status)
 
 
 def tsdf_extract_sparse_host(D, w, sv, min_weight=1.0, capacity=None, return_status=False):
     """The host twin of ``tsdf_extract_sparse`` (d3f_tsdf_sparse_extract_host): CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
-    D, w = _sparse_pool(D, w, sv, cpu)
-    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, cpu)
-    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
-    fn = _native.lib().d3f_tsdf_sparse_extract_host
-    point_start = torch.zeros(V + 1, dtype=torch.int64)
-    status = torch.zeros(1, dtype=torch.int32)
-    pool = (_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(bc) if B else None, _p(to), _p(tn),
-            _p(tvx), V, lattice, B, float(min_weight))
-    if capacity is None:
-        scratch = torch.zeros(1, dtype=torch.int32)
-        _native.check(fn(*(pool + (0, None, _p(point_start), _p(scratch)))), "d3f_tsdf_sparse_extract_host")
-        capacity = int(point_start[V])
-    points = torch.empty((int(capacity), 3), dtype=torch.float32)
-    _native.check(fn(*(pool + (int(capacity), _p(points) if capacity else None, _p(point_start), _p(status)))),
-                  "d3f_tsdf_sparse_extract_host")
-    return (points, point_start, status) if return_status else (points, point_start)
+    return _tsdf_extract(True, cpu, _sparse_model(True, cpu, _pool_tensors(D, w, cpu), sv), min_weight, capacity,
+                         return_status)
 
 
 def _slot_voxels(coord):
@@ -4230,61 +4167,16 @@ def tsdf_mesh(D, w, vol_start, origin, dims, voxel, min_weight=1.0, vertex_capac
     capacity are dropped and TSDF_ST_OVERFLOW (vertices) / TSDF_ST_FACE_OVERFLOW (faces) is set in the status word
     (``return_status=True`` appends it as a device int32 [1] tensor; both starts are complete either way)."""
     dev = _tsdf_device()
-    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, dev)
-    _check_vol_start(vol_start, tvs)
-    L = _native.lib()
-    nbytes = L.d3f_tsdf_mesh_ws_bytes(total)
-    ws = _ws(nbytes, dev)
-    starts = torch.zeros((2, V + 1), dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    counted = 0
-    with _region("tsdf_mesh"):
-        if vertex_capacity is None or face_capacity is None:
-            _native.check(L.d3f_tsdf_mesh_count(_p(D), _p(w), _p(tvs), _p(tn), V, total, float(min_weight),
-                                                _p(starts[0]), _p(starts[1]), _p(ws), nbytes, _stream()),
-                          "d3f_tsdf_mesh_count")
-            nv, nf = starts[:, V].tolist()                 # the one read-back: the sizes of the result
-            vertex_capacity = nv if vertex_capacity is None else vertex_capacity
-            face_capacity = nf if face_capacity is None else face_capacity
-            counted = 1
-        nv, nf = int(vertex_capacity), int(face_capacity)
-        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        _native.check(L.d3f_tsdf_mesh(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight),
-                                      counted, nv, nf, _p(vertices) if nv else None, _p(normals) if nv else None,
-                                      _p(faces) if nf else None, _p(starts[0]), _p(starts[1]), _p(status), _p(ws),
-                                      nbytes, _stream()), "d3f_tsdf_mesh")
-    out = (vertices, normals, faces, starts[0], starts[1])
-    return out + (status,) if return_status else out
+    return _tsdf_mesh(False, dev, _dense_model(False, dev, _pool_tensors(D, w, dev), vol_start, origin, dims, voxel),
+                      min_weight, vertex_capacity, face_capacity, return_status)
 
 
 def tsdf_mesh_host(D, w, vol_start, origin, dims, voxel, min_weight=1.0, vertex_capacity=None, face_capacity=None,
                    return_status=False):
     """The host twin of ``tsdf_mesh`` (d3f_tsdf_mesh_host): CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
-    D, w, V, total, to, tn, tvx, tvs = _tsdf_extract_inputs(D, w, origin, dims, voxel, cpu)
-    _check_vol_start(vol_start, tvs)
-    fn = _native.lib().d3f_tsdf_mesh_host
-    vertex_start = torch.zeros(V + 1, dtype=torch.int64)
-    face_start = torch.zeros(V + 1, dtype=torch.int64)
-    status = torch.zeros(1, dtype=torch.int32)
-
-    def run(nv, nf, vertices, normals, faces, status):
-        _native.check(fn(_p(D), _p(w), _p(tvs), _p(to), _p(tn), _p(tvx), V, total, float(min_weight), nv, nf,
-                         _p(vertices) if nv else None, _p(normals) if nv else None, _p(faces) if nf else None,
-                         _p(vertex_start), _p(face_start), _p(status)), "d3f_tsdf_mesh_host")
-    if vertex_capacity is None or face_capacity is None:
-        run(0, 0, None, None, None, torch.zeros(1, dtype=torch.int32))          # the totals
-        vertex_capacity = int(vertex_start[V]) if vertex_capacity is None else vertex_capacity
-        face_capacity = int(face_start[V]) if face_capacity is None else face_capacity
-    nv, nf = int(vertex_capacity), int(face_capacity)
-    vertices = torch.empty((nv, 3), dtype=torch.float32)
-    normals = torch.empty((nv, 3), dtype=torch.float32)
-    faces = torch.empty((nf, 3), dtype=torch.int32)
-    run(nv, nf, vertices, normals, faces, status)
-    out = (vertices, normals, faces, vertex_start, face_start)
-    return out + (status,) if return_status else out
+    return _tsdf_mesh(True, cpu, _dense_model(True, cpu, _pool_tensors(D, w, cpu), vol_start, origin, dims, voxel),
+                      min_weight, vertex_capacity, face_capacity, return_status)
 
 
 _MESH_QUAD = ((-1, -1), (0, -1), (0, 0), (-1, 0))       # the cells q0..q3 around an edge, offsets on the axes (b, c)
@@ -4413,69 +4305,15 @@ def tsdf_mesh_sparse(D, w, sv, min_weight=1.0, vertex_capacity=None, face_capaci
     added late by ``tsdf_extend`` hold only the later frames.  ``D``, ``w`` as ``tsdf_integrate_sparse`` returns them;
     the capacities, ``return_status`` and the one read-back as for ``tsdf_mesh``."""
     dev = _tsdf_device()
-    D, w = _sparse_pool(D, w, sv, dev)
-    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, dev)
-    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
-    starts = torch.zeros((2, V + 1), dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    if B == 0:                                                 # nothing allocated: no kernel has anything to do
-        nv, nf = int(vertex_capacity or 0), int(face_capacity or 0)
-        out = (torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nv, 3), dtype=torch.float32, device=dev),
-               torch.empty((nf, 3), dtype=torch.int32, device=dev), starts[0], starts[1])
-        return out + (status,) if return_status else out
-    L = _native.lib()
-    nbytes = L.d3f_tsdf_sparse_mesh_ws_bytes(B)
-    ws = _ws(nbytes, dev)
-    counted = 0
-    with _region("tsdf_mesh_sparse"):
-        if vertex_capacity is None or face_capacity is None:
-            _native.check(L.d3f_tsdf_sparse_mesh_count(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(tn), V, lattice,
-                                                       B, float(min_weight), _p(starts[0]), _p(starts[1]), _p(ws),
-                                                       nbytes, _stream()), "d3f_tsdf_sparse_mesh_count")
-            nv, nf = starts[:, V].tolist()                 # the one read-back: the sizes of the result
-            vertex_capacity = nv if vertex_capacity is None else vertex_capacity
-            face_capacity = nf if face_capacity is None else face_capacity
-            counted = 1
-        nv, nf = int(vertex_capacity), int(face_capacity)
-        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        _native.check(L.d3f_tsdf_sparse_mesh(_p(D), _p(w), _p(tls), _p(bs), _p(bi), _p(bc), _p(to), _p(tn), _p(tvx), V,
-                                             lattice, B, float(min_weight), counted, nv, nf,
-                                             _p(vertices) if nv else None, _p(normals) if nv else None,
-                                             _p(faces) if nf else None, _p(starts[0]), _p(starts[1]), _p(status),
-                                             _p(ws), nbytes, _stream()), "d3f_tsdf_sparse_mesh")
-    out = (vertices, normals, faces, starts[0], starts[1])
-    return out + (status,) if return_status else out
+    return _tsdf_mesh(False, dev, _sparse_model(False, dev, _pool_tensors(D, w, dev), sv), min_weight, vertex_capacity,
+                      face_capacity, return_status)
 
 
 def tsdf_mesh_sparse_host(D, w, sv, min_weight=1.0, vertex_capacity=None, face_capacity=None, return_status=False):
     """The host twin of ``tsdf_mesh_sparse`` (d3f_tsdf_sparse_mesh_host): CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
-    D, w = _sparse_pool(D, w, sv, cpu)
-    tls, bs, bi, bc, to, tn, tvx = _sparse_tables(sv, cpu)
-    V, lattice, B = sv.volumes, int(sv.lattice_start[-1]), sv.bricks
-    fn = _native.lib().d3f_tsdf_sparse_mesh_host
-    vertex_start = torch.zeros(V + 1, dtype=torch.int64)
-    face_start = torch.zeros(V + 1, dtype=torch.int64)
-    status = torch.zeros(1, dtype=torch.int32)
-
-    def run(nv, nf, vertices, normals, faces, status):
-        _native.check(fn(_p(D) if B else None, _p(w) if B else None, _p(tls), _p(bs), _p(bi), _p(bc) if B else None,
-                         _p(to), _p(tn), _p(tvx), V, lattice, B, float(min_weight), nv, nf,
-                         _p(vertices) if nv else None, _p(normals) if nv else None, _p(faces) if nf else None,
-                         _p(vertex_start), _p(face_start), _p(status)), "d3f_tsdf_sparse_mesh_host")
-    if vertex_capacity is None or face_capacity is None:
-        run(0, 0, None, None, None, torch.zeros(1, dtype=torch.int32))          # the totals
-        vertex_capacity = int(vertex_start[V]) if vertex_capacity is None else vertex_capacity
-        face_capacity = int(face_start[V]) if face_capacity is None else face_capacity
-    nv, nf = int(vertex_capacity), int(face_capacity)
-    vertices = torch.empty((nv, 3), dtype=torch.float32)
-    normals = torch.empty((nv, 3), dtype=torch.float32)
-    faces = torch.empty((nf, 3), dtype=torch.int32)
-    run(nv, nf, vertices, normals, faces, status)
-    out = (vertices, normals, faces, vertex_start, face_start)
-    return out + (status,) if return_status else out
+    return _tsdf_mesh(True, cpu, _sparse_model(True, cpu, _pool_tensors(D, w, cpu), sv), min_weight, vertex_capacity,
+                      face_capacity, return_status)
 
 
 def _brick_rows27(sv, v, index, coord, bs):
@@ -4706,7 +4544,10 @@ def _color_volume(Cv, total, what):
 # colour as given, checked to be float32 on the device), ``stem`` of the entry points' names, ``V``, ``cells`` (the voxels
 # or slots that D, w and the colours must hold), ``stored`` (False: an empty pool, whose pointers go in as NULL), the
 # words of the error messages (``holds``, ``limit``), ``color(c)`` -> (the checked colour tensor, Cc) and ``tables()`` ->
-# (the C arguments between the colour and the views / points, the tensors behind them).
+# (the C arguments between the colour and the views / points, the tensors behind them).  ``tables(surface=True)`` gives
+# the pair of argument lists of the extract and mesh entry points instead: those of the emit forms and the twins, which
+# take ``brick_coord`` too (NULL for an empty pool), and those of the count forms, which take no origin and no voxel.
+# The last argument of either is the size that the ``_ws_bytes`` functions take.
 _FusedModel = collections.namedtuple("_FusedModel", "tensors stem V cells stored holds limit color tables")
 
 
@@ -4729,10 +4570,11 @@ def _dense_model(host, device, named, vol_start, origin, dims, voxel):
     o, n, vx, _, vs = _tsdf_volumes(origin, dims, voxel, V)
     total = int(vs[-1])
 
-    def tables():
+    def tables(surface=False):
         held = _on(device, vs, o, n, vx)
         _check_vol_start(vol_start, held[0])
-        return tuple(_p(t) for t in held) + (V, total), held
+        args = tuple(_p(t) for t in held) + (V, total)
+        return ((args, (args[0], args[2], V, total)) if surface else args), held
 
     return _FusedModel(tensors=tensors, stem="", V=V, cells=total, stored=True, holds="the %d voxels of dims" % total,
                        limit=" (at most %d volumes)" % TSDF_MAX_VOLUMES,
@@ -4747,12 +4589,87 @@ def _sparse_model(host, device, named, sv):
         Cp = _sparse_color_pool(c, sv, device)
         return Cp, int(Cp.shape[-1])
 
-    def tables():
-        tls, bs, bi, _, to, tn, tvx = held = _sparse_tables(sv, device)
-        return (_p(tls), _p(bs), _p(bi), _p(to), _p(tn), _p(tvx), sv.volumes, int(sv.lattice_start[-1]), B), held
+    def tables(surface=False):
+        tls, bs, bi, bc, to, tn, tvx = held = _sparse_tables(sv, device)
+        rows, sizes = (_p(tls), _p(bs), _p(bi)), (sv.volumes, int(sv.lattice_start[-1]), B)
+        if surface:
+            rows += (_p(bc) if B else None,)
+        args = rows + (_p(to), _p(tn), _p(tvx)) + sizes
+        return ((args, rows + (_p(tn),) + sizes) if surface else args), held
 
     return _FusedModel(tensors=tensors, stem="_sparse", V=sv.volumes, cells=B * TSDF_BRICK_VOXELS, stored=bool(B),
                        holds="the %d x 512 slots of the allocated bricks" % B, limit="", color=color, tables=tables)
+
+
+def _tsdf_surface(host, device, model, what, min_weight, capacities, outputs, return_status):
+    """Every extract and mesh form, d3f_tsdf[_sparse]_{extract,mesh}{_count, , _host}.  ``model``: ``_dense_model`` /
+    ``_sparse_model`` of (D, w); ``what``: "extract" / "mesh"; ``capacities``: one per kind of row (points; vertices and
+    faces), None for "as many as there are"; ``outputs``: (dtype, index of its capacity) per output of rows [n,3].
+    Returns the outputs, one start [V+1] per capacity and, with ``return_status``, the status word.
+
+    The capacity rule, once: with every capacity given nothing is read back, rows beyond a capacity are dropped and
+    leave a bit in the status.  Otherwise the device forms count and scan first, read the totals (the ONE read-back),
+    and emit into exactly that many rows; a twin is run twice, first into no rows at all."""
+    D, w = model.tensors
+    if int(D.numel()) != model.cells or int(w.numel()) != model.cells:
+        raise ValueError("D and w must hold %s, got %d and %d" % (model.holds, D.numel(), w.numel()))
+    if not model.stem and (model.cells == 0 or model.V > TSDF_MAX_VOLUMES):
+        raise ValueError("between 1 and %d volumes per call" % TSDF_MAX_VOLUMES)
+    (emit_tables, count_tables), _held = model.tables(surface=True)
+    V, name = model.V, "d3f_tsdf%s_%s" % (model.stem, what)
+    starts = torch.zeros((len(capacities), V + 1), dtype=torch.int64, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def rows(capacities):
+        return tuple(torch.empty((int(capacities[j]), 3), dtype=dtype, device=device) for dtype, j in outputs)
+
+    def returned(out):
+        out += tuple(starts)
+        return out + (status,) if return_status else out
+
+    if not host and not model.stored:                          # nothing allocated: no kernel has anything to do
+        return returned(rows([c or 0 for c in capacities]))
+    L = _native.lib()
+    pool = (_p(D), _p(w)) if model.stored else (None, None)
+    known = all(c is not None for c in capacities)
+
+    def emit(fn, head, capacities, out, status, tail):
+        capacities = tuple(int(c) for c in capacities)
+        _native.check(fn(*(pool + emit_tables + head + capacities + tuple(_p(t) if t.numel() else None for t in out) +
+                           tuple(_p(s) for s in starts) + (_p(status),) + tail)), fn.__name__)
+
+    if host:
+        fn = getattr(L, name + "_host")
+        if not known:                                          # the totals
+            emit(fn, (float(min_weight),), [0] * len(capacities), rows([0] * len(capacities)),
+                 torch.zeros(1, dtype=torch.int32), ())
+            capacities = [int(s[V]) if c is None else c for c, s in zip(capacities, starts)]
+        out = rows(capacities)
+        emit(fn, (float(min_weight),), capacities, out, status, ())
+        return returned(out)
+    nbytes = getattr(L, name + "_ws_bytes")(emit_tables[-1])
+    ws = _ws(nbytes, device)
+    tail = (_p(ws), nbytes, _stream())
+    with _region("tsdf_" + what + model.stem):
+        if not known:
+            _native.check(getattr(L, name + "_count")(*(pool + count_tables + (float(min_weight),) +
+                                                        tuple(_p(s) for s in starts) + tail)), name + "_count")
+            totals = starts[:, V].tolist()                     # the one read-back: the sizes of the result
+            capacities = [t if c is None else c for c, t in zip(capacities, totals)]
+        out = rows(capacities)
+        emit(getattr(L, name), (float(min_weight), int(not known)), capacities, out, status, tail)
+    return returned(out)
+
+
+def _tsdf_extract(host, device, model, min_weight, capacity, return_status):
+    """(points f32 [M,3], point_start int64 [V+1]) of ``model``, on ``device``."""
+    return _tsdf_surface(host, device, model, "extract", min_weight, [capacity], ((torch.float32, 0),), return_status)
+
+
+def _tsdf_mesh(host, device, model, min_weight, vertex_capacity, face_capacity, return_status):
+    """(vertices f32 [Nv,3], normals f32 [Nv,3], faces int32 [Nf,3], vertex_start, face_start) of ``model``."""
+    return _tsdf_surface(host, device, model, "mesh", min_weight, [vertex_capacity, face_capacity],
+                         ((torch.float32, 0), (torch.float32, 0), (torch.int32, 1)), return_status)
 
 
 def _tsdf_raycast(host, device, model, trunc, intrinsics, camera_to_volume, height, width, view_volume, step, depth_min,

@@ -1098,8 +1098,8 @@ int d3f_pose_graph_edge_host(const double* Pi_host, const double* Pj_host, const
 
 /* ------------------------------------------------------------------------------------------------
  * TSDF fusion of depth frames into a batch of V dense volumes, and the extraction of their zero crossings as point
- * clouds (csrc/tsdf.hpp states the rule in full; the reference has no such step).  Bounds and extraction are
- * csrc/tsdf.hip, the integration csrc/tsdf_integrate.hip.
+ * clouds (csrc/tsdf.hpp states the rule in full; the reference has no such step).  The bounds are csrc/tsdf.hip,
+ * the integration csrc/tsdf_integrate.hip, the extraction csrc/tsdf_extract.hip.
  * Volume v: lattice dims[v] = (nx, ny, nz), ix fastest; origin[v][3], voxel[v], trunc[v]; its voxels are
  * [vol_start[v], vol_start[v+1]) of D / w (vol_start int64 [V+1] from 0 to total_voxels; every dim >= 1); it owns the
  * frames [frame_start[v], frame_start[v+1]) (an empty range leaves the volume at D = 0, w = 0).

@@ -1,4 +1,4 @@
-"""Times the TSDF fusion of one fragment at the benchmark's own size (datasets/fragments.py, csrc/tsdf.hip): 50 synthetic
+"""Times the TSDF fusion of one fragment at the benchmark's own size (datasets/fragments.py, csrc/tsdf.hip, csrc/tsdf_integrate.hip, csrc/tsdf_extract.hip): 50 synthetic
 depth frames of 640 x 480 of the analytic room of tests/tsdf_scene.py scaled up 2.4 times, voxel 0.006 m, trunc 5 voxels
 -- about 2 x 10^8 voxels.
 

@@ -1,5 +1,5 @@
 """Times the mesh extraction of one fragment-sized TSDF volume against the point extraction of the SAME volume in the same
-run (csrc/tsdf_mesh.hip against csrc/tsdf.hip's extract): the volume of profiles/tsdf_bench.py -- 50 synthetic depth
+run (csrc/tsdf_mesh.hip against csrc/tsdf_extract.hip): the volume of profiles/tsdf_bench.py -- 50 synthetic depth
 frames of 640 x 480 of the analytic room of tests/tsdf_scene.py scaled up 2.4 times, voxel 0.006 m, trunc 5 voxels,
 about 2 x 10^8 voxels -- integrated once on the device.
 

@@ -203,7 +203,7 @@ def main():
 
     say()
     for kernel in ("sparse_mesh_count_kernel", "sparse_mesh_emit_kernel"):
-        res = kernel_resources("tsdf_mesh_sparse.hip", kernel)
+        res = kernel_resources(kernel, "tsdf_mesh_sparse.hip")
         say("%s as compiled for gfx950: %s" % (kernel, ", ".join("%s %d" % kv for kv in res.items()) if res else
                                                 "not measured (no hipcc here)"))
     text = "\n".join(out) + "\n"

@@ -45,10 +45,10 @@ BATCH = 16
 MODEL = dict(frames_per_fragment=50, voxel=0.01)
 
 
-def kernel_resources(kernel):
-    """The compiler's report for the kernel of csrc/tsdf_raycast.hip whose mangled name holds ``kernel``, or None when
-    there is no hipcc."""
-    src = os.path.join(_native.CSRC, "tsdf_raycast.hip")
+def kernel_resources(kernel, source="tsdf_raycast.hip"):
+    """The compiler's report for the kernel of csrc/``source`` whose mangled name holds ``kernel``, or None when there
+    is no hipcc."""
+    src = os.path.join(_native.CSRC, source)
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-pass-failed", "-fPIC",
                "-I" + os.path.join(REPO, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",

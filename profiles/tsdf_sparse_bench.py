@@ -2,8 +2,8 @@
 timer and line format this uses): 50 synthetic depth frames of 640 x 480 of the analytic room of tests/tsdf_scene.py
 scaled up 2.4 times, voxel 0.006 m, trunc 0.03 m.
 
-  * the dense integrate, extract-count and extract-emit launches of csrc/tsdf.hip, unchanged;
-  * the sparse mark, index, integrate, extract-count and extract-emit launches of csrc/tsdf_sparse.hip: device events
+  * the dense integrate, extract-count and extract-emit launches (csrc/tsdf_integrate.hip, csrc/tsdf_extract.hip), unchanged;
+  * the sparse mark, index, integrate, extract-count and extract-emit launches (csrc/tsdf_sparse.hip and the same two files): device events
     around each C-ABI call on tensors that are already on the device, REPEAT times after a warm-up; median, minimum,
     maximum;
   * allocated bricks over lattice bricks, and the bytes of the sparse volume (pool plus tables, ops.tsdf_sparse_bytes)

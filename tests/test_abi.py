@@ -29,6 +29,46 @@ def test_ctypes_table_covers_header():
     assert sorted(_native.SIGNATURES) == _declared()
 
 
+def test_the_generated_surface_prototypes_are_the_sixteen_literal_ones():
+    """_native._tsdf_surface_signatures() builds the extract and mesh prototypes from shared pieces; this is the table
+    they replaced, entry by entry as it was written out."""
+    C = ctypes
+    _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+    literal = {
+        "d3f_tsdf_extract_ws_bytes": (_sz, [C.c_int64]),
+        "d3f_tsdf_extract_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _sz, _vp]),
+        "d3f_tsdf_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz,
+                                  _vp]),
+        "d3f_tsdf_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, _vp, _vp, _vp]),
+        "d3f_tsdf_sparse_extract_ws_bytes": (_sz, [C.c_int64]),
+        "d3f_tsdf_sparse_extract_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp,
+                                               _sz, _vp]),
+        "d3f_tsdf_sparse_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
+                                         C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
+        "d3f_tsdf_sparse_extract_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
+                                              C.c_int64, _vp, _vp, _vp]),
+        "d3f_tsdf_mesh_ws_bytes": (_sz, [C.c_int64]),
+        "d3f_tsdf_mesh_count": (_i, [_vp, _vp, _vp, _vp, _i, C.c_int64, _f, _vp, _vp, _vp, _sz, _vp]),
+        "d3f_tsdf_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, _i, C.c_int64, C.c_int64, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _sz, _vp]),
+        "d3f_tsdf_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _f, C.c_int64, C.c_int64, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
+        "d3f_tsdf_sparse_mesh_ws_bytes": (_sz, [C.c_int64]),
+        "d3f_tsdf_sparse_mesh_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _vp, _vp, _vp,
+                                            _sz, _vp]),
+        "d3f_tsdf_sparse_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f, _i,
+                                      C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+        "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
+                                           C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    }
+    generated = _native._tsdf_surface_signatures()
+    assert sorted(generated) == sorted(literal)
+    for name, prototype in literal.items():
+        assert generated[name] == prototype, name
+        assert _native.SIGNATURES[name] == prototype, name
+    assert "tsdf_extract.hip" in _native.SOURCES
+
+
 def test_no_gpu_calls_needed_for_size_queries():
     lib = _native.lib()
     assert lib.d3f_version().decode().startswith("d3feat-hip")
