@@ -4,8 +4,9 @@
 //
 // Supports are bucketed by a 64-bit cell key (cloud, cx, cy, cz) hashed into a power-of-two table; the cell edge is
 // radius * kCellSlack and cell coordinates are computed in f64, so a 27-cell scan provably covers every support with
-// d2 < radius^2.  A point is accepted only while scanning ITS OWN cell key, so hash collisions neither lose nor duplicate
-// candidates.
+// d2 < radius^2.  Hash collisions neither lose nor duplicate candidates: the searches over cloud pairs
+// (pair_search.hpp) accept a point only while scanning ITS OWN cell key; radius_neighbors.hip scans every distinct bucket of a query once and accepts a point iff it
+// belongs to the query's cloud and d2 < radius^2, without reading the keys (the argument is at the head of that file).
 #pragma once
 #include "common.hpp"
 

@@ -7,11 +7,21 @@
 //
 // Design (CDNA4): supports are bucketed by a 64-bit cell key (batch, cx, cy, cz) hashed into a power-of-two
 // table; the cell edge is radius*(1+1e-4) and cell coordinates are computed in f64 so a 27-cell scan provably
-// covers every accepted support.  A point is accepted only while scanning ITS OWN cell key, so hash collisions
-// neither lose nor duplicate candidates.  One 64-lane wave serves one query: lanes 0..26 look up the 27
-// buckets, a wave prefix sum flattens their ranges so all 64 lanes test candidates, survivors are compacted
-// with ballot/popcount into LDS as (d2 bits << 32 | index) and ranked by a wave-wide bitonic network
-// (register shuffles for <= 64 candidates, LDS otherwise).
+// covers every accepted support.  One 64-lane wave serves one query: lanes 0..26 look up the 27 buckets and
+// keep every DISTINCT bucket once, a wave prefix sum flattens their ranges so all 64 lanes test candidates,
+// survivors are compacted with ballot/popcount into LDS as (d2 bits << 32 | index) and ranked by a wave-wide
+// bitonic network (register shuffles for <= 64 candidates, LDS otherwise).
+//
+// Hash collisions neither lose nor duplicate candidates, without a look at the stored cell keys:
+//  * every bucket the 27 cells hash to is scanned exactly once (two cells of one query that share a bucket are
+//    folded into the lower lane at set-up), so nothing is seen twice;
+//  * a support with d2 < r2 lies in one of the 27 cells (the f64 cell argument above) and in none of the cells
+//    pruned by the box distance, so its bucket is among the scanned ones: nothing is lost;
+//  * whatever else a scanned bucket holds -- supports of a cell outside the 27, of a pruned cell, or of another
+//    cloud -- fails `d2 < r2` by the 1e-4 cell margin the pruning relies on (a thousand times the f32 rounding
+//    of d2), or fails the cloud test: its global index (pts.w) lies outside the support rows of the query's cloud.
+// So a candidate is accepted iff it belongs to the query's cloud and d2 < r2.  The keys grid_scatter_kernel
+// stores are still written: nearest_pairs.hip reads lists built here.
 #include "cell_list.hpp"
 
 namespace {
@@ -53,10 +63,42 @@ constexpr int kUpKeys = 32;   // transposed lists: coarse points ranked per fine
 
 struct WaveScratch {
   uint64_t cand[kCand];
-  uint64_t nkey[32];
-  int pre[32];
-  int st[32];
+  int delta[32];   // per cell lane: first stored position of its bucket - first flat candidate position
+  int mark[64];    // per pass: the cell lane whose range starts at this flat position, else 0
+  uint8_t slot[256];   // set-up: where the cell lanes of one bucket meet (see "every bucket ONCE")
 };
+
+// ---- compare-exchange steps of the in-register bitonic networks (64-bit keys, one key per lane) ----
+
+// lanes that keep the SMALLER key in step (k, j) of a network over lanes masked by kLanes - 1: a compile-time lane mask
+constexpr uint64_t keep_smaller_mask(int k, int j, int lanes) {
+  uint64_t m = 0;
+  for (int l = 0; l < 64; ++l) {
+    const int x = l & (lanes - 1);
+    if (((x & k) == 0) == ((x & j) == 0)) m |= 1ull << l;
+  }
+  return m;
+}
+
+// one compare (v < partner) per step; both halves of the key are selected from (its lane mask) xor (the constant)
+template <int kK, int kJ, int kLanes>
+__device__ __forceinline__ uint64_t compare_exchange(uint64_t v) {
+  const uint64_t o = shfl_xor_u64(v, kJ);
+  const uint64_t keep_own = ~(__ballot(v < o) ^ keep_smaller_mask(kK, kJ, kLanes));   // (equal keys: either is right)
+  return __builtin_amdgcn_inverse_ballot_w64(keep_own) ? v : o;
+}
+template <int kK, int kJ, int kLanes>
+__device__ __forceinline__ uint64_t bitonic_merge(uint64_t v) {
+  v = compare_exchange<kK, kJ, kLanes>(v);
+  if constexpr (kJ > 1) v = bitonic_merge<kK, kJ / 2, kLanes>(v);
+  return v;
+}
+// stages 2 .. kK of the network: sorts every aligned group of kK lanes (ascending where lane & kK == 0)
+template <int kK, int kLanes>
+__device__ __forceinline__ uint64_t bitonic_stages(uint64_t v) {
+  if constexpr (kK > 2) v = bitonic_stages<kK / 2, kLanes>(v);
+  return bitonic_merge<kK, kK / 2, kLanes>(v);
+}
 
 __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     const float* __restrict__ q, int Nq, const int32_t* __restrict__ q_len, const int32_t* __restrict__ s_len, int B,
@@ -67,13 +109,52 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     int max_count_group, float r2_prefix, float prune_r, int flag_empty, const int32_t* __restrict__ done_rows,
     int32_t* __restrict__ tr_counts, uint64_t* __restrict__ tr_keys) {
   __shared__ WaveScratch scratch[kQueryWaves];
+  __shared__ int wg_done, wg_count[kQueryWaves], wg_word[kQueryWaves];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int qi = blockIdx.x * kQueryWaves + wave;
-  if (qi >= Nq) return;  // no workgroup barrier below: waves are independent
+  // The max count is ONE word per group of clouds, and the looks at it and the atomic maxima of all queries are served
+  // one after the other: the pooling searches spend a third to a half of their time there, the more the faster the
+  // queries themselves are (profiles/radius_diet_ab.txt).  So the waves of a workgroup hand in their counts through LDS
+  // and the LAST one to arrive looks once for all of them (every wave hands in on every way out of the kernel; nobody
+  // waits for anybody -- the only barrier is this one at the top, before any wave has left).
+  if (max_count) {
+    if (threadIdx.x == 0) wg_done = 0;
+    __syncthreads();
+  }
+  auto hand_in_count = [&](int count, int word) {
+    if (!max_count || lane != 0) return;
+    wg_count[wave] = count;
+    wg_word[wave] = word;
+    if (__hip_atomic_fetch_add(&wg_done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) != kQueryWaves - 1) return;
+    // (the pre-check reads past the CU's L1, which another CU's atomic never refreshes: with a plain load thousands of
+    // waves kept seeing the initial 0 and queued their atomics on the one word -- 71 us for 8000 queries, 12 us now)
+    auto raise = [&](int w, int c) {
+      if (c > __hip_atomic_load(max_count + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_count + w, c);
+    };
+    const int word0 = wg_word[0];
+    int most = 0;
+    for (int w = 0; w < kQueryWaves; ++w) {
+      if (wg_word[w] == word0) most = max(most, wg_count[w]);
+      else raise(wg_word[w], wg_count[w]);   // (a workgroup across a boundary between two groups of clouds)
+    }
+    raise(word0, most);
+  };
+  if (qi >= Nq) {  // no workgroup barrier below: waves are independent
+    hand_in_count(0, 0);
+    return;
+  }
   // rows another producer has filled already (d3f_upsample_rows_from_pool: the transpose of the pooling search's lists)
-  if (done_rows && done_rows[qi] > 0) return;
+  if (done_rows && done_rows[qi] > 0) {
+    hand_in_count(0, 0);
+    return;
+  }
   WaveScratch& ws = scratch[wave];
-  volatile uint64_t* cand = ws.cand;
+  uint64_t* const cand = ws.cand;   // plain LDS accesses; phases of the wave are ordered by wave_sync()
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
   if (qi >= d3f::batch_offset(q_len, B)) {  // Nq is a row capacity: rows past sum(q_len) get an all-shadow row
     if (out_idx)
       for (int c = lane; c < width; c += 64) out_idx[(size_t)qi * width + c] = Ns;
@@ -81,11 +162,19 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
       for (int c = lane; c < wide_width; c += 64) out_wide[(size_t)qi * wide_width + c] = Ns;
     if (lane == 0 && out_counts) out_counts[qi] = 0;
     if (lane == 0 && out_last_key) out_last_key[qi] = ~0ull;
+    hand_in_count(0, 0);
     return;
   }
 
-  int b, qstart;
-  d3f::locate_batch(q_len, B, qi, b, qstart);
+  // the query's cloud b and the support rows [s_lo, s_lo + s_n) of that cloud (the cloud test of a candidate)
+  int b = 0, s_lo = 0;
+  for (int qs = 0; b < B - 1; ++b) {
+    const int ql = q_len[b], sl = s_len[b];
+    if (qi < qs + ql) break;
+    qs += ql;
+    s_lo += sl;
+  }
+  const uint32_t s_n = (uint32_t)s_len[b];
   const float qx = q[3 * qi + 0], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
   const int cx = cell_coord(qx, inv_cell), cy = cell_coord(qy, inv_cell), cz = cell_coord(qz, inv_cell);
 
@@ -93,7 +182,8 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
   // an accepted support (a point was put into the cell its coordinates fall in, in the same f64 arithmetic): it is not
   // scanned at all -- a sphere of one cell edge meets ~20.6 of the 27 cells on average, one of 0.75 edge (the prefix
   // form's reach) ~12.  The 1e-4 margin is a thousand times the f32 rounding of d2; results are unchanged bit for bit.
-  int len = 0;
+  int len = 0, st = 0;
+  uint32_t bk = ~0u;   // (no bucket: the table has at most 2^31 of them)
   if (lane < 27) {
     const int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
     const double cell = 1.0 / inv_cell;
@@ -103,12 +193,27 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     };
     const double gx = gap(qx, cx + dx), gy = gap(qy, cy + dy), gz = gap(qz, cz + dz);
     const double reach = (double)prune_r * (1.0 + 1e-4);
-    const uint64_t nk = pack_key(b, cx + dx, cy + dy, cz + dz);
-    const uint32_t bk = bucket_of(nk, mask);
-    const int st = start[bk];
+    bk = bucket_of(pack_key(b, cx + dx, cy + dy, cz + dz), mask);
+    st = start[bk];
     len = (gx * gx + gy * gy + gz * gz <= reach * reach) ? end[bk] - st : 0;
-    ws.nkey[lane] = nk;
-    ws.st[lane] = st;
+  }
+  // every bucket ONCE: of the cell lanes that still scan, only the lowest lane of each distinct bucket keeps its range
+  // (see the head of the file: with that, and the cloud test below, the stored cell keys need not be read)
+  // Comparing all pairs of lanes costs more than the key loads it saves, so the lanes first meet in a small LDS table
+  // indexed by the low bits of their bucket: each writes its lane number and reads the slot back.  Of the lanes of one
+  // bucket at most one reads its own number, so every bucket that two lanes share has a lane that "lost" its slot; only
+  // for those (less than one per query on average) the wave compares the bucket against all lanes and keeps the lowest.
+  {
+    const bool live = len > 0;
+    if (live) ws.slot[bk & 255u] = (uint8_t)lane;
+    wave_sync();
+    const bool lost = live && ws.slot[bk & 255u] != (uint8_t)lane;
+    uint64_t fold = 0;
+    for (uint64_t m = __ballot(lost); m; m &= m - 1) {   // wave-uniform
+      const uint64_t same = __ballot(live && bk == (uint32_t)__builtin_amdgcn_readlane((int)bk, __builtin_ctzll(m)));
+      fold |= same & (same - 1);
+    }
+    if (__builtin_amdgcn_inverse_ballot_w64(fold)) len = 0;
   }
   // inclusive prefix over lanes 0..31 (27 cells) by DPP: shifts inside the rows of 16 (out-of-row sources read 0), then
   // row 0's total broadcast into row 1 -- five LDS-crossbar shuffles and their waits gone
@@ -118,47 +223,62 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
   incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);    // row_shr:4
   incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);    // row_shr:8
   incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1 and 3
-  if (lane < 32) ws.pre[lane] = incl - len;  // exclusive prefix; entries 27..31 == total
+  const int pre = incl - len;                  // first flat candidate position of this lane's range
+  if (lane < 32) ws.delta[lane] = st - pre;    // stored position = flat position + delta[cell lane]
   const int P = __builtin_amdgcn_readlane(incl, 31);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // One pass = 64 flat positions p0 + lane.  Which range a position falls in, without a search per candidate: the cell
+  // lanes whose range starts inside the pass leave their lane number at that position (0 elsewhere -- position 0 of the
+  // whole scan is the start of the first range, so "lane 0" and "no mark" never get confused), and an inclusive max-scan
+  // over the wave (DPP, no LDS) with the carry of the pass before spreads it: lane numbers rise with the positions.  The
+  // point is loaded from a clamped address by every lane; whether the position exists is decided on the value.
+  int carry = 0;
+  auto fetch = [&](int p0) -> float4 {
+    ws.mark[lane] = 0;
+    if (len > 0 && (uint32_t)(pre - p0) < 64u) ws.mark[pre - p0] = lane;
+    wave_sync();
+    uint32_t c = (uint32_t)ws.mark[lane];
+    wave_sync();
+    // (unsigned max: 0 is its identity, so the DPP moves fold into the v_max)
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x111, 0xF, 0xF, true));    // row_shr:1
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x112, 0xF, 0xF, true));    // row_shr:2
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x114, 0xF, 0xF, true));    // row_shr:4
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x118, 0xF, 0xF, true));    // row_shr:8
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x142, 0xA, 0xF, false));   // row_bcast:15 into rows 1, 3
+    c = max(c, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x143, 0xC, 0xF, false));   // row_bcast:31 into rows 2, 3
+    c = max(c, (uint32_t)carry);
+    carry = __builtin_amdgcn_readlane((int)c, 63);
+    const int p = p0 + lane, d = ws.delta[c];
+    return pts[p < P ? p + d : 0];
+  };
 
   // prefix mode (r2_prefix > 0, d3f_radius_query_prefix): only the entries within the PREFIX radius are ranked; of the
   // others the nearest is carried along as a running minimum of the same (d2, index) keys
   const bool prefix = r2_prefix > 0.0f;
   uint64_t nearest = ~0ull;
   int T = 0;
+  float4 next = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (P > 0) next = fetch(0);
   for (int p0 = 0; p0 < P; p0 += 64) {
-    const int p = p0 + lane;
-    bool ok = false;
-    uint64_t packed = 0;
-    if (p < P) {
-      int lo = 0;  // largest j with pre[j] <= p
-#pragma unroll
-      for (int step = 16; step > 0; step >>= 1) {
-        const int j = lo + step;
-        if (j < 27 && ws.pre[j] <= p) lo = j;
-      }
-      const int pos = ws.st[lo] + (p - ws.pre[lo]);
-      const float4 sp = pts[pos];
-      if (key[pos] == ws.nkey[lo]) {
-        const float d2 = d3f::sqdist_exact(qx, qy, qz, sp.x, sp.y, sp.z);
-        ok = d2 < r2;
-        packed = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(sp.w);
-        if (prefix) {
-          if (ok && packed < nearest) nearest = packed;
-          ok = d2 < r2_prefix;          // (r2_prefix <= r2: checked by the launcher)
-        }
-      }
+    const float4 sp = next;
+    if (p0 + 64 < P) next = fetch(p0 + 64);   // the next pass's points are in flight during this pass's arithmetic
+    const float d2 = d3f::sqdist_exact(qx, qy, qz, sp.x, sp.y, sp.z);
+    const uint32_t sidx = (uint32_t)__float_as_int(sp.w);
+    const bool mine = p0 + lane < P && sidx - (uint32_t)s_lo < s_n;   // an existing position, a support of cloud b
+    bool ok = mine && d2 < r2;
+    const uint64_t packed = ((uint64_t)__float_as_uint(d2) << 32) | sidx;
+    if (prefix) {
+      if (ok && packed < nearest) nearest = packed;
+      ok = mine && d2 < r2_prefix;          // (r2_prefix <= r2: checked by the launcher)
     }
     const uint64_t m = __ballot(ok);
     if (ok) {
-      const int slot = T + __popcll(m & ((1ull << lane) - 1ull));
+      const int slot = T + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
       if (slot < kCand) cand[slot] = packed;
     }
     T += __popcll(m);
   }
+  wave_sync();
   if (prefix) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -168,19 +288,11 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     if (T == 0 && nearest != ~0ull) {     // nothing within the prefix radius: the row is the one nearest entry
       if (lane == 0) cand[0] = nearest;
       T = 1;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
     }
   }
   if (lane == 0) {
     if (out_counts) out_counts[qi] = T;
-    // (the pre-check reads past the CU's L1, which another CU's atomic never refreshes: with a plain load thousands of
-    // waves kept seeing the initial 0 and queued their atomics on the one word -- 71 us for 8000 queries, 12 us now)
-    if (max_count) {
-      int32_t* mc = max_count + (max_count_group > 0 ? b / max_count_group : 0);   // per group of clouds, or one word
-      if (T > __hip_atomic_load(mc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(mc, T);
-    }
     if (T > kCand) atomicOr(status, D3F_ST_CAND_OVERFLOW);
     // prefix form with a nearest bound: the caller vouched for a support within the bound of every query (the engine:
     // the voxel diagonal).  A row that found none is a broken promise -- e.g. a coarse level that overflowed its
@@ -188,6 +300,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     if (flag_empty && T == 0) atomicOr(status, D3F_ST_NO_NEAREST);
     if (out_wide && T > wide_width) atomicOr(status, D3F_ST_WIDE_OVERFLOW);
   }
+  hand_in_count(T, max_count_group > 0 ? b / max_count_group : 0);   // per group of clouds, or one word
   const int Tc = T < kCand ? T : kCand;
   int32_t* row = out_idx ? out_idx + (size_t)qi * width : nullptr;
   if (tr_counts) {
@@ -208,19 +321,9 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
     // <= 16 (32) keys sit in the first 16 (32) lanes: the network's stages up to that width sort them (the other lane
     // groups hold ~0 only) -- 10 (15) compare-exchange steps instead of 21 for the short rows of the coarse levels and
     // of the prefix form
-    const int kmax = Tc <= 16 ? 16 : (Tc <= 32 ? 32 : 64);
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-      if (k <= kmax) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-          const uint64_t o = shfl_xor_u64(v, j);
-          const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-          const uint64_t mn = v < o ? v : o, mx = v < o ? o : v;
-          v = (lower == up) ? mn : mx;
-        }
-      }
-    }
+    v = bitonic_stages<16, 64>(v);
+    if (Tc > 16) v = bitonic_merge<32, 16, 64>(v);
+    if (Tc > 32) v = bitonic_merge<64, 32, 64>(v);
     if (row) {
       if (lane < width) row[lane] = lane < Tc ? (int32_t)(uint32_t)v : Ns;
       for (int c = 64 + lane; c < width; c += 64) row[c] = Ns;
@@ -243,6 +346,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
   for (int i = Tc + lane; i < n; i += 64) cand[i] = ~0ull;
   for (int k = 2; k <= n; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
+      wave_sync();   // a step reads what other lanes wrote in the step before
       for (int t = lane; t < (n >> 1); t += 64) {
         const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1));
         const int c = a | j;
@@ -255,6 +359,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void radius_query_kernel(
       }
     }
   }
+  wave_sync();
   if (row)
     for (int c = lane; c < width; c += 64) row[c] = c < Tc ? (int32_t)(uint32_t)cand[c] : Ns;
   if (out_wide)
@@ -288,16 +393,7 @@ __global__ __launch_bounds__(256) void up_rank_kernel(int32_t* __restrict__ coun
     if (l32 == 0) counts[f] = 0;
   }
   uint64_t v = l32 < n ? keys[(size_t)f * kUpKeys + l32] : ~0ull;
-#pragma unroll
-  for (int k = 2; k <= 32; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t o = shfl_xor_u64(v, j);
-      const bool up_dir = (l32 & k) == 0, lower = (l32 & j) == 0;
-      const uint64_t mn = v < o ? v : o, mx = v < o ? o : v;
-      v = (lower == up_dir) ? mn : mx;
-    }
-  }
+  v = bitonic_stages<32, 32>(v);   // (lanes taken modulo 32: both half waves sort ascending)
   if (n > 0) {
     int32_t* row = up + (size_t)f * width;
     for (int c = l32; c < width; c += 32) row[c] = c < n ? (int32_t)(uint32_t)v : Nc;
