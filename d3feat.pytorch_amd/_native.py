@@ -14,7 +14,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_extract.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_mesh_sparse.hip"]
+           "tsdf_mesh_sparse.hip", "fpfh.hip"]
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _d = C.c_double
@@ -261,6 +261,10 @@ SIGNATURES = {
     "d3f_icp_rigid_color_ws_bytes": (_sz, [_i, C.c_int64]),
     "d3f_icp_rigid_color": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _d, _i, _d, _d,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_fpfh_ws_bytes": (_sz, [_i]),
+    "d3f_fpfh": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_fpfh_passes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "d3f_fpfh_host": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _vp, _vp]),
     "d3f_pair_information_ws_bytes": (_sz, [_i, C.c_int64]),
     "d3f_pair_information": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _sz,
                                   _vp]),
@@ -309,7 +313,7 @@ SIGNATURES.update(_tsdf_reader_signatures())
 SIGNATURES.update(_tsdf_surface_signatures())
 
 ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failure"}
-STATUS_BITS = {1: "a query has more in-radius candidates than the kernel can rank (512)",
+STATUS_BITS = {1: "a query has more in-radius candidates than the kernel can rank (512; fpfh: 2^18 neighbours of a point)",
                2: "a point lies outside the addressable cell grid",
                4: "voxel hash table full",
                8: "a pyramid level needs more rows than its capacity (raise the capacities)",

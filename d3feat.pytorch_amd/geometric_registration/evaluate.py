@@ -136,6 +136,35 @@ def generate_features(model, scenes, save_path, config, neighborhood_limits, dev
             engine.check_status()
 
 
+def generate_fpfh_features(scenes, save_path, radius, normal_radius=None, seed=0, desc_name='FPFH', device='cuda'):
+    """``generate_features`` without a network: FPFH descriptors (``registration.describe_fpfh``: one cell list, one
+    normals call and one ``ops.fpfh`` call per scene) in the same layout -- per fragment
+    ``descriptors/<scene>/cloud_bin_<i>.<desc_name>.npy`` [N,64] f32 (33 columns scaled to unit rows and zero-padded: the
+    norm and the width the matching kernel reads), ``keypoints/<scene>/cloud_bin_<i>.npy`` [N,3] f32 (the whole
+    fragment, as the ICP path relies on) and
+    ``scores/<scene>/cloud_bin_<i>.npy`` [N,1] f32.  FPFH has no detector: the score is a uniform draw in (0, 1] from
+    ``numpy.random.default_rng(seed)`` for a point with a descriptor and 0 for one without, so the top-k selection of
+    ``register_one_scene`` / ``registration.register_scene`` (with ``desc_name=``) is a reproducible uniform sample of
+    the described points.  ``device='cpu'`` runs the NumPy restatement."""
+    from . import registration as reg
+    rng = np.random.default_rng(seed)
+    for scene, fragments in scenes.items():
+        dpath, kpath, spath = _paths(save_path, scene)
+        for p in (dpath, kpath, spath):
+            os.makedirs(p, exist_ok=True)
+        frags = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 3) for f in fragments]
+        descs, counts = reg.describe_fpfh(frags, radius, normal_radius, device=device)
+        for ids, points in enumerate(frags):
+            desc, count = descs[ids], counts[ids]
+            if isinstance(desc, torch.Tensor):
+                desc, count = desc.cpu().numpy(), count.cpu().numpy()
+            draw = 1.0 - rng.random(points.shape[0])                       # (0, 1]
+            scores = np.where(count > 0, draw, 0.0).astype(np.float32).reshape(-1, 1)
+            np.save(os.path.join(dpath, 'cloud_bin_%d.%s' % (ids, desc_name)), desc.astype(np.float32))
+            np.save(os.path.join(kpath, 'cloud_bin_%d' % ids), points)
+            np.save(os.path.join(spath, 'cloud_bin_%d' % ids), scores)
+
+
 # ----------------------------------------------------------------------------------------------------- registration
 def match_pair(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score, gt_trans,
                num_points=250, distance_threshold=0.10, random_points=False, rng=None):
@@ -159,8 +188,9 @@ def match_pair(source_keypts, source_desc, source_score, target_keypts, target_d
 
 
 def register_one_scene(inlier_ratio_threshold, distance_threshold, save_path, scene, gtpath, num_frag=None,
-                       num_points=250, random_points=False, device='cuda', seed=0):
-    """Recall / mean inlier count / mean inlier ratio of one scene from the dumped files (test.py:20-76)."""
+                       num_points=250, random_points=False, device='cuda', seed=0, desc_name=DESC_NAME):
+    """Recall / mean inlier count / mean inlier ratio of one scene from the dumped files (test.py:20-76).
+    ``desc_name``: the descriptor whose dump is read (``'FPFH'``: ``generate_fpfh_features``)."""
     gt = loadlog(gtpath)
     dpath, kpath, spath = _paths(save_path, scene)
     if num_frag is None:
@@ -172,7 +202,7 @@ def register_one_scene(inlier_ratio_threshold, distance_threshold, save_path, sc
         if i not in cache:
             name = 'cloud_bin_%d' % i
             cache[i] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (
-                get_keypts(kpath, name), get_desc(dpath, name), get_scores(spath, name).reshape(-1)))
+                get_keypts(kpath, name), get_desc(dpath, name, desc_name), get_scores(spath, name).reshape(-1)))
         return cache[i]
     rng = np.random.RandomState(seed)
     counts = []
@@ -195,11 +225,12 @@ def register_one_scene(inlier_ratio_threshold, distance_threshold, save_path, sc
 
 
 def evaluate_scenes(save_path, scenes_gt, inlier_ratio_threshold=0.05, distance_threshold=0.10, num_points=250,
-                    random_points=False, device='cuda'):
+                    random_points=False, device='cuda', desc_name=DESC_NAME):
     """{scene: gt directory} -> ({scene: [recall, inlier num, inlier ratio]}, averages) -- test.py:169-188."""
     out = {}
     for scene, gtpath in scenes_gt.items():
         out[scene] = list(register_one_scene(inlier_ratio_threshold, distance_threshold, save_path, scene, gtpath,
-                                             num_points=num_points, random_points=random_points, device=device))
+                                             num_points=num_points, random_points=random_points, device=device,
+                                             desc_name=desc_name))
     avg = np.mean(np.array(list(out.values()), dtype=np.float64), axis=0)
     return out, {'recall': float(avg[0]), 'inlier_num': float(avg[1]), 'inlier_ratio': float(avg[2])}

@@ -25,7 +25,10 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``multiway_registration`` / ``spanning_tree_poses`` / ``pose_graph_numpy``  one consistent pose per fragment from the
   pair poses and their information matrices: robust pose-graph optimisation (``ops.pose_graph_optimize``, one launch)
   that prunes false loop closures, and its NumPy restatement -- ``register_scene`` runs it when given
-  ``pose_graph=dict(max_distance=...)``.
+  ``pose_graph=dict(max_distance=...)``;
+* ``describe_fpfh`` / ``fpfh_numpy``  FPFH descriptors of fragments (``ops.fpfh``; csrc/fpfh.hpp has the rule) and their
+  NumPy restatement: the training-free descriptor and the baseline column of the registration tables --
+  ``evaluate.generate_fpfh_features`` dumps them and ``register_scene(desc_name='FPFH')`` reads them.
 
 Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
 target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
@@ -469,6 +472,163 @@ def color_field_from_moments(m, Q, nrm, intensity, min_neighbors=4):
     return field
 
 
+# ------------------------------------------------------------------------------------------------- FPFH descriptors
+FPFH_MAX_NEIGHBORS = 1 << 18                     # csrc/fpfh.hpp kMaxNeighbors
+FPFH_WEIGHT_SCALE, FPFH_WEIGHT_CAP = 2.0 ** 32, 2.0 ** 12
+# cos and sin of theta_b = -pi + 2 pi b / 11, b = 1..10: the constants of csrc/fpfh.hpp, b = 11 - k mirrored from b = k
+_FPFH_COS5 = [-0.8412535328311811, -0.4154150130018863, 0.14231483827328512, 0.6548607339452851, 0.9594929736144975]
+_FPFH_SIN5 = [-0.5406408174555978, -0.9096319953545184, -0.9898214418809327, -0.7557495743542583, -0.2817325568414295]
+FPFH_COS = np.array(_FPFH_COS5 + _FPFH_COS5[::-1], dtype=np.float64)
+FPFH_SIN = np.array(_FPFH_SIN5 + [-s for s in _FPFH_SIN5[::-1]], dtype=np.float64)
+
+
+def _fpfh_feature_bin(f):
+    t = np.floor((11.0 * (f + 1.0)) * 0.5)
+    return np.where(t >= 10.0, 10.0, np.where(t >= 0.0, t, 0.0)).astype(np.int64)
+
+
+def fpfh_pair_bins(dp, d2, ni, nj):
+    """The three bins (theta, f2, f3; each 0..10) of pairs (i, j) under the rule of csrc/fpfh.hpp: ``dp`` [m,3] f64 =
+    p_j - p_i, ``d2`` [m] its squared length as the rule sums it (non-zero), ``ni`` / ``nj`` [m,3] f64 normals.
+    Only + - * / sqrt and floor, in the header's order."""
+    px, py, pz = dp[:, 0], dp[:, 1], dp[:, 2]
+    with np.errstate(all='ignore'):
+        dist = np.sqrt(d2)
+        a1 = ((ni[:, 0] * px + ni[:, 1] * py) + ni[:, 2] * pz) / dist
+        a2 = ((nj[:, 0] * px + nj[:, 1] * py) + nj[:, 2] * pz) / dist
+        swap = np.abs(a1) < np.abs(a2)
+        n1 = np.where(swap[:, None], nj, ni)
+        n2 = np.where(swap[:, None], ni, nj)
+        qx, qy, qz = np.where(swap, -px, px), np.where(swap, -py, py), np.where(swap, -pz, pz)
+        f3 = np.where(swap, -a2, a1)
+        vx, vy, vz = qy * n1[:, 2] - qz * n1[:, 1], qz * n1[:, 0] - qx * n1[:, 2], qx * n1[:, 1] - qy * n1[:, 0]
+        vn = np.sqrt((vx * vx + vy * vy) + vz * vz)
+        flat = vn == 0.0
+        vx, vy, vz = vx / vn, vy / vn, vz / vn
+        wx, wy, wz = n1[:, 1] * vz - n1[:, 2] * vy, n1[:, 2] * vx - n1[:, 0] * vz, n1[:, 0] * vy - n1[:, 1] * vx
+        f2 = (vx * n2[:, 0] + vy * n2[:, 1]) + vz * n2[:, 2]
+        y = (wx * n2[:, 0] + wy * n2[:, 1]) + wz * n2[:, 2]
+        x = (n1[:, 0] * n2[:, 0] + n1[:, 1] * n2[:, 1]) + n1[:, 2] * n2[:, 2]
+        reached = (y[:, None] * FPFH_COS[None, :] - x[:, None] * FPFH_SIN[None, :]) >= 0.0
+    theta = np.where(y < 0.0, reached[:, :5].sum(1), 5 + reached[:, 5:].sum(1))
+    theta = np.where((x == 0.0) & (y == 0.0), 5, theta)
+    five = np.int64(5)
+    return (np.where(flat, five, theta).astype(np.int64), np.where(flat, five, _fpfh_feature_bin(f2)),
+            np.where(flat, five, _fpfh_feature_bin(f3)))
+
+
+def _fpfh_blocks(ps, usable, r2f, reach, block):
+    """Blocks of the rows of one cloud sorted by x: (s, lo, accepted [rows, window] bool, d [rows, window, 3] f64 =
+    p_j - p_i, d2 [rows, window] f64) with the window ps[lo:lo + window] -- the neighbourhood test of csrc/fpfh.hpp."""
+    n = ps.shape[0]
+    step = max(1, int(block) // max(n, 1))
+    for s in range(0, n, step):
+        q = ps[s:s + step]
+        lo = np.searchsorted(ps[:, 0], float(q[0, 0]) - reach, 'left')
+        hi = np.searchsorted(ps[:, 0], float(q[-1, 0]) + reach, 'right')
+        t = ps[lo:hi]
+        e = q[:, None, :] - t[None, :, :]                              # the search's p_i - p_j, f32
+        d2f = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+        d = t.astype(np.float64)[None, :, :] - q.astype(np.float64)[:, None, :]
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        ok = (d2f < r2f) & (d2 != 0.0) & usable[s:s + step, None] & usable[None, lo:hi]
+        yield s, lo, ok, d, d2
+
+
+def fpfh_numpy(clouds, radius, normals, return_spfh=False, unit=False, block=1 << 20):
+    """The contract of ``ops.fpfh`` in NumPy (csrc/fpfh.hpp): ``clouds`` a list of [n,3] f32 arrays, each searched on
+    its own, ``normals`` f32 [N,3] over the stacked rows.  Returns ``(desc f32 [N,33], count int32 [N])`` and, with
+    ``return_spfh``, ``spfh int32 [N,33]`` -- equal to the device's and the host twin's bit for bit: the rule uses only
+    correctly rounded f64 operations and integer sums.  ``unit``: rows scaled to unit L2 norm by the rule's fixed-order
+    sum of squares.  Brute force within a window of the rows sorted by x, like
+    ``estimate_normals_numpy``."""
+    r32 = np.float32(radius)
+    if not (0.0 < float(r32) < np.inf):
+        raise ValueError("radius must be positive and finite")
+    r2f, r2 = r32 * r32, float(r32) * float(r32)
+    reach = float(r32) * 1.001 + 1e-6
+    nrm_all = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    descs, counts, spfhs = [], [], []
+    row0 = 0
+    for cloud in clouds:
+        p = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        nrm = nrm_all[row0:row0 + n]
+        if nrm.shape[0] != n:
+            raise ValueError("normals must hold one row per point of every cloud")
+        row0 += n
+        order = np.argsort(p[:, 0], kind='stable')
+        ps, ns = p[order], nrm[order].astype(np.float64)
+        usable = (nrm[order] != 0).any(1)
+        c = np.zeros((n, 33), dtype=np.int64)
+        for s, lo, ok, d, d2 in _fpfh_blocks(ps, usable, r2f, reach, block):
+            qi, tj = np.nonzero(ok)
+            if not qi.size:
+                continue
+            bins = fpfh_pair_bins(d[qi, tj], d2[qi, tj], ns[s + qi], ns[lo + tj])
+            rows = ok.shape[0]
+            for h in range(3):
+                c[s:s + rows, 11 * h:11 * h + 11] = np.bincount(qi * 11 + bins[h], minlength=rows * 11).reshape(rows, 11)
+        cnt = c[:, :11].sum(1)
+        S = np.zeros((n, 33), dtype=np.int64)
+        for s, lo, ok, d, d2 in _fpfh_blocks(ps, usable, r2f, reach, block):
+            nj = np.broadcast_to(cnt[None, lo:lo + ok.shape[1]], ok.shape)
+            with np.errstate(all='ignore'):
+                W = np.rint((FPFH_WEIGHT_SCALE * np.minimum(r2 / d2, FPFH_WEIGHT_CAP)) / nj.astype(np.float64))
+            W = np.where(ok, W, 0.0).astype(np.int64)
+            S[s:s + ok.shape[0]] = W @ c[lo:lo + ok.shape[1]]
+        tot = np.repeat(S.reshape(n, 3, 11).sum(2), 11, axis=1)
+        live = (cnt >= 1) & (cnt <= FPFH_MAX_NEIGHBORS)
+        with np.errstate(all='ignore'):
+            first = np.where(tot == 0, 0.0, (100.0 * S.astype(np.float64)) / tot.astype(np.float64))
+            desc = first + (100.0 * c.astype(np.float64)) / cnt.astype(np.float64)[:, None]
+        desc = np.where(live[:, None], desc, 0.0).astype(np.float32)
+        if unit:
+            wide, q = desc.astype(np.float64), np.zeros(n)
+            for b in range(33):                                        # the rule's order of additions
+                q = q + wide[:, b] * wide[:, b]
+            with np.errstate(all='ignore'):
+                desc = np.where(desc != 0, wide / np.sqrt(q)[:, None], 0.0).astype(np.float32)
+        back = np.empty(n, dtype=np.int64)
+        back[order] = np.arange(n)
+        descs.append(desc[back])
+        counts.append(cnt[back].astype(np.int32))
+        spfhs.append(c[back].astype(np.int32))
+    if row0 != nrm_all.shape[0]:
+        raise ValueError("normals must hold one row per point of every cloud")
+    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dtype=dt)
+    res = (cat(descs, (0, 33), np.float32), cat(counts, (0,), np.int32))
+    return res + (cat(spfhs, (0, 33), np.int32),) if return_spfh else res
+
+
+def describe_fpfh(clouds, radius, normal_radius=None, viewpoint=None, device='cuda'):
+    """FPFH descriptors of fragments, the training-free stand-in for the network: ONE ``ops.CloudGrid`` at
+    ``max(radius, normal_radius)`` over all fragments, one ``ops.estimate_normals`` call (``normal_radius`` defaults to
+    ``0.4 * radius`` -- Open3D's examples use 2 and 5 voxels; ``viewpoint``: the same point in every fragment's own
+    frame, default the origin) and one ``ops.fpfh`` call at ``radius``.  ``clouds``: list of [n,3] arrays / tensors.
+    Returns ``(descriptors, counts)``: per fragment a [n,64] f32 block of zero-padded UNIT rows -- the width and the norm
+    ``ops.mutual_nn`` reads: it ranks by the inner product, which for unit rows is the order of the L2 distance -- and
+    the [n] int32 neighbour counts (0: no descriptor, a row of zeros); device tensors, or NumPy arrays from
+    ``device='cpu'`` (``estimate_normals_numpy``, ``fpfh_numpy``)."""
+    if normal_radius is None:
+        normal_radius = 0.4 * float(radius)
+    if not (0.0 < float(radius) < np.inf) or not (0.0 < float(normal_radius) < np.inf):
+        raise ValueError("radius and normal_radius must be positive and finite")
+    lens = [int(c.shape[0]) for c in clouds]
+    ends = np.cumsum([0] + lens)
+    if str(device).startswith('cpu'):
+        arrs = _host_arrays(clouds)
+        nrm = estimate_normals_numpy(arrs, normal_radius, viewpoint=viewpoint)[0]
+        d33, cnt = fpfh_numpy(arrs, radius, nrm, unit=True)
+        desc = np.zeros((d33.shape[0], 64), dtype=np.float32)
+        desc[:, :33] = d33
+    else:
+        grid = _cloud_grid(clouds, max(float(radius), float(normal_radius)), torch.device(device))
+        nrm = ops.estimate_normals(grid, None, normal_radius, viewpoint=viewpoint)[0]
+        desc, cnt = ops.fpfh(grid, None, radius, nrm, row_width=64, unit=True)
+    return ([desc[ends[k]:ends[k + 1]] for k in range(len(lens))], [cnt[ends[k]:ends[k + 1]] for k in range(len(lens))])
+
+
 def _icp_keywords(icp):
     if not isinstance(icp, dict) or 'max_distance' not in icp:
         raise ValueError("icp must be None or a dict of refine_transforms keywords with at least max_distance")
@@ -760,7 +920,7 @@ def _scene_colors(colors, frags, rows):
 
 
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
-                   pose_graph=None, **ransac):
+                   pose_graph=None, desc_name=ev.DESC_NAME, **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
@@ -775,7 +935,9 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     matrices of the estimated poses are taken (from the ICP call when ``icp`` is given, else from one
     ``information_matrices`` call over the keypoint files), ``multiway_registration`` gives one pose per fragment, and
     the log holds ``inv(P_i) P_j`` for every pair it kept -- the pairs it pruned are left out.  The return value is then
-    ``(the usual result, poses [num_frag,4,4])``.  Still one read-back per scene."""
+    ``(the usual result, poses [num_frag,4,4])``.  Still one read-back per scene.
+    ``desc_name``: the descriptor whose dump is read (``cloud_bin_<i>.<desc_name>.npy``): ``'FPFH'`` for the files of
+    ``evaluate.generate_fpfh_features``."""
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -787,7 +949,7 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
         if i not in cache:
             name = 'cloud_bin_%d' % i
             cache[i] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (
-                ev.get_keypts(kpath, name), ev.get_desc(dpath, name), ev.get_scores(spath, name).reshape(-1)))
+                ev.get_keypts(kpath, name), ev.get_desc(dpath, name, desc_name), ev.get_scores(spath, name).reshape(-1)))
         return cache[i]
     keys = sorted(gt, key=lambda k: tuple(int(x) for x in k.split('_')))
     if not keys:

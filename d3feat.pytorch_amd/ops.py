@@ -3020,6 +3020,102 @@ def color_gradients(grid_or_points, lens, radius, normals, intensity, min_neighb
     return (field, count, moments) if return_moments else (field, count)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# FPFH descriptors (csrc/fpfh.hpp has the rule; Open3D's compute_fpfh_feature)
+# ---------------------------------------------------------------------------------------------------------------
+FPFH_WIDTH = 33          # 3 histograms of 11 bins
+FPFH_ROW = 36            # int32 per row of the SPFH table between the two passes (33 counts, n, two zeros)
+FPFH_WIDTHS = (33, 64)   # row widths d3f_fpfh writes; 64 is zero-padded, the width mutual_nn reads
+
+
+def fpfh_bytes(n, neighbors=None):
+    """Algorithmic bytes of the FPFH descriptors of ``n`` points at row width 33, both passes: each pass reads the point
+    (12), the (start, end) headers of 27 buckets (216) and the stored point and cell key of every candidate the accepted
+    cells hold (24 each; ``neighbors`` of them in all, by default one per point).  The SPFH pass also reads the point's
+    normal (12) and the 12-byte normal of every neighbour and writes a 144-byte table row and the count (4); the FPFH
+    pass reads the point's own table row (144) and that of every neighbour (144 each) and writes the descriptor (132)."""
+    n = int(n)
+    m = n if neighbors is None else int(neighbors)
+    return n * (2 * (12 + 27 * 8) + 12 + 4 + 4 * FPFH_ROW + 4 * FPFH_ROW + 4 * FPFH_WIDTH) + m * (2 * 24 + 12 + 4 * FPFH_ROW)
+
+
+def _fpfh_width(row_width):
+    if int(row_width) not in FPFH_WIDTHS:
+        raise ValueError("row_width must be 33 or 64, got %r" % (row_width,))
+    return int(row_width)
+
+
+def fpfh(grid_or_points, lens, radius, normals, row_width=33, return_spfh=False, unit=False):
+    """FPFH descriptor of every point of the stacked clouds (d3f_fpfh; what Open3D's compute_fpfh_feature computes on the
+    CPU): three 11-bin histograms of the pair features of the point's neighbours within ``radius`` IN ITS OWN CLOUD, each
+    the sum of the point's own histogram and the distance-weighted histograms of its neighbours, scaled to 100.
+
+    ``grid_or_points``, ``lens``, ``radius``: as in ``estimate_normals``.  ``normals`` f32 [N,3] in input row order
+    (``estimate_normals``); a point whose normal is (0, 0, 0) has no descriptor and is nobody's neighbour.  Returns device
+    tensors ``(desc [N,row_width] f32, count [N] int32)`` and, with ``return_spfh``, ``spfh [N,33] int32`` (the
+    neighbour counts per bin).  ``row_width`` 33, or 64 for zero-padded rows: zero columns do not change an L2 distance,
+    so that is what ``mutual_nn`` reads with no copy -- with ``unit=True``, which scales every row to unit L2 norm in
+    the kernel (f64, a fixed order: csrc/fpfh.hpp): ``mutual_nn`` ranks by the inner product of UNIT rows, which for
+    them is the order of the L2 distance.  ``count`` is the number of neighbours; a point with count 0 has
+    no descriptor and a row of zeros.  Every sum over neighbours is an integer (csrc/fpfh.hpp), so the result is
+    bit-identical from run to run, for any row order, for a cloud alone or stacked, and for any cell size.  Two
+    launches, no read-back, capturable in a graph."""
+    if not (0.0 < float(radius) < float("inf")):
+        raise ValueError("radius must be positive and finite")
+    width = _fpfh_width(row_width)
+    grid = _resolve_grid(grid_or_points, lens, radius, "radius")
+    dev = grid.supports.device
+    N = grid.Ns
+    nrm = _f32(normals, "normals")
+    if tuple(nrm.shape) != (N, 3) or nrm.device != dev:
+        raise ValueError("normals must be [%d,3] on the points' device, got %s" % (N, tuple(nrm.shape)))
+    desc = torch.empty((N, width), dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    spfh = torch.empty((N, FPFH_WIDTH), dtype=torch.int32, device=dev) if return_spfh else None
+    if N:
+        L = _native.lib()
+        nbytes = L.d3f_fpfh_ws_bytes(N)
+        ws = _ws(nbytes, dev)
+        with _region("fpfh[N=%d]" % N, fpfh_bytes(N)):
+            _native.check(L.d3f_fpfh(
+                _p(grid.ws), _p(grid.supports), _p(nrm), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(radius), width, int(bool(unit)), _p(desc), _p(count), _p(spfh), _p(grid.status.word), _p(ws), nbytes,
+                _stream()),
+                "d3f_fpfh")
+    return (desc, count, spfh) if return_spfh else (desc, count)
+
+
+def fpfh_host(points, lens, radius, normals, row_width=33, return_spfh=False, unit=False):
+    """The host twin of ``fpfh`` (d3f_fpfh_host): the same inline rule compiled for the CPU, brute force within each
+    cloud, one thread.  ``points`` [N,3], ``lens`` and ``normals`` [N,3] are host arrays (or CPU tensors); returns CPU
+    tensors.  No GPU call."""
+    if not (0.0 < float(radius) < float("inf")):
+        raise ValueError("radius must be positive and finite")
+    width = _fpfh_width(row_width)
+    pts = np.ascontiguousarray(_host_array(points), dtype=np.float32)
+    nrm = np.ascontiguousarray(_host_array(normals), dtype=np.float32)
+    ln = np.asarray(_host_array(lens), dtype=np.int64).reshape(-1)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be [N,3], got %s" % (pts.shape,))
+    N = int(pts.shape[0])
+    if nrm.shape != (N, 3):
+        raise ValueError("normals must be [%d,3], got %s" % (N, nrm.shape))
+    if not 1 <= ln.size <= MAX_CLOUDS or ln.min() < 0 or int(ln.sum()) > N:
+        raise ValueError("lens must be 1..%d non-negative lengths that sum to at most the %d stacked points"
+                         % (MAX_CLOUDS, N))
+    start = np.zeros(ln.size + 1, dtype=np.int32)
+    start[1:] = np.cumsum(ln)
+    desc = np.zeros((N, width), dtype=np.float32)
+    count = np.zeros(N, dtype=np.int32)
+    spfh = np.zeros((N, FPFH_WIDTH), dtype=np.int32) if return_spfh else None
+    _native.check(_native.lib().d3f_fpfh_host(
+        pts.ctypes.data, nrm.ctypes.data, N, start.ctypes.data, int(ln.size), float(radius), width, int(bool(unit)),
+        desc.ctypes.data,
+        count.ctypes.data, spfh.ctypes.data if return_spfh else None), "d3f_fpfh_host")
+    out = (torch.from_numpy(desc), torch.from_numpy(count))
+    return out + (torch.from_numpy(spfh),) if return_spfh else out
+
+
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
               return_trace=False, rows=None, normals=None, color_field=None, lambda_geometric=0.968):
     """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).

@@ -979,6 +979,47 @@ int d3f_icp_rigid_color(const void* grid_ws, const float* points, const float* n
                         void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FPFH descriptors (Rusu, Blodow, Beetz 2009) of every point of the stacked clouds of a cell list: the training-free
+ * descriptor of the registration chain.  Replaces Open3D's compute_fpfh_feature, which the reference's users run on the
+ * CPU.  csrc/fpfh.hpp states the rule beside the code; in short:
+ *   neighbours of point i: the points j != i of the SAME cloud with d2 < radius * radius (f32 without FMA, strict: the
+ *        acceptance of d3f_estimate_normals), a normal that is not (0, 0, 0), and a non-zero f64 distance; a point whose
+ *        own normal is (0, 0, 0) has no descriptor and is nobody's neighbour; n_i = the number of neighbours;
+ *   pair features in f64 with + - * / sqrt only, Open3D's role swap decided by |a1| < |a2|, the angle's bin decided by
+ *        the signs of ten 2x2 determinants against constant (cos, sin) pairs -- no acos, no atan2;
+ *   SPFH: c_i[33] int32 counts (theta, f2, f3; 11 bins each);
+ *   FPFH: W_j = (int64) rint((2^32 min(radius^2 / d2, 2^12)) / n_j), S_i[b] = sum_j W_j c_j[b] in int64,
+ *        desc_i[b] = f32((100 S_i[b]) / tot_h + (100 c_i[b]) / n_i), tot_h the sum of b's histogram of S_i.
+ * Every sum over neighbours is an integer, so the result is bit-identical from run to run, for any row order, for a
+ * cloud alone or stacked, and for any cell size.  The cap 2^12 on the weight (a neighbour closer than radius / 64) and
+ * the omission of atan2 / acos are the two differences from Open3D.
+ *
+ * d3f_fpfh.  The cell list (grid_ws, grid_radius), points, Ns, cloud_start and B are those of d3f_estimate_normals;
+ * radius <= grid_radius; `normals` [Ns,3] f32 in input row order; row_width 33 or 64 (columns 33.. are zeros: the width
+ * d3f_mutual_nn reads); unit != 0 scales every row to unit L2 norm -- unit_i[b] = f32(desc_i[b] / sqrt(q)) in f64, q the
+ * sum of the squares of the 33 f32 entries in the order b = 0..32 -- which d3f_mutual_nn needs: it ranks by the inner
+ * product of unit rows.  Outputs in input row order: desc [Ns,row_width] f32, count [Ns] int32 (= n_i), optional (NULL
+ * to skip) spfh [Ns,33] int32.  A point without a descriptor (n_i = 0: no usable normal, no neighbour, or outside the
+ * addressable cell grid, which also sets D3F_ST_CELL_RANGE in *status) and the rows beyond cloud_start[B] get zeros and
+ * count 0.  A point with more than 2^18 neighbours, beyond which the int64 sums could overflow, sets
+ * D3F_ST_CAND_OVERFLOW in *status and gets zeros.  ws: d3f_fpfh_ws_bytes(Ns) bytes, 16-byte aligned (the SPFH table
+ * between the two passes).  Two launches on `stream`, no host synchronisation, no allocation, no floating-point atomics.
+ * d3f_fpfh_host: the same inline rule on the host over HOST arrays, brute force within each cloud (it knows no cell
+ * grid, so no point is out of range).
+ * ---------------------------------------------------------------------------------------------- */
+size_t d3f_fpfh_ws_bytes(int Ns);
+int d3f_fpfh(const void* grid_ws, const float* points, const float* normals, int Ns, const int32_t* cloud_start, int B,
+             float grid_radius, float radius, int row_width, int unit, float* desc, int32_t* count, int32_t* spfh,
+             int32_t* status, void* ws, size_t ws_bytes, void* stream);
+/* measurement aid (profiles/fpfh_bench.py): d3f_fpfh with passes = 1 the SPFH launch alone, 2 the FPFH launch alone
+ * over the table a previous call left in ws, 3 both (= d3f_fpfh) */
+int d3f_fpfh_passes(const void* grid_ws, const float* points, const float* normals, int Ns, const int32_t* cloud_start,
+                    int B, float grid_radius, float radius, int row_width, int unit, float* desc, int32_t* count,
+                    int32_t* spfh, int32_t* status, void* ws, size_t ws_bytes, int passes, void* stream);
+int d3f_fpfh_host(const float* points, const float* normals, int Ns, const int32_t* cloud_start, int B, float radius,
+                  int row_width, int unit, float* desc, int32_t* count, int32_t* spfh);
+
+/* ------------------------------------------------------------------------------------------------
  * Raw moments of the accepted correspondences of cloud pairs under GIVEN poses -- what the 6x6 information matrix of a
  * pair is made of (the benchmark's gt.info, which registration recall is scored under, and the weight of an edge of a
  * pose graph; Open3D's get_information_matrix_from_point_clouds).  The clouds, the cell list (grid_ws, grid_radius),
