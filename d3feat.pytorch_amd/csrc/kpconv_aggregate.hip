@@ -26,31 +26,6 @@ namespace d3f {
 void* kpconv_timing_open(int which, hipStream_t stream, int Nq, int Ns, int H, int Cin, int Cout, int K);
 void kpconv_timing_close(void* rec, hipStream_t stream);
 
-// kpconv_dx_gather.hip (phase A of the gather kernel: one chunk of <= 64 compacted reverse neighbors)
-template <int CV, int NSTEPS>
-__device__ __forceinline__ void agg_rev_core(int n_c, float qx, float qy, float qz, float inn, __amdgpu_buffer_rsrc_t rs_g,
-                                             unsigned row_bytes, unsigned col_off, float cx, float cy, float cz,
-                                             float inv_extent, int lg, f32x4 (&acc)[CV]) {
-  constexpr int NG = 4 * NSTEPS;
-  typename VecT<CV>::type xv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const unsigned n = (unsigned)__shfl(n_c, 4 * g + lg, 64);
-    xv[g] = buf_load_vec<CV>(rs_g, n * row_bytes + col_off);
-  }
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    float4 sp;
-    sp.x = __shfl(qx, 4 * g + lg, 64);
-    sp.y = __shfl(qy, 4 * g + lg, 64);
-    sp.z = __shfl(qz, 4 * g + lg, 64);
-    sp.w = 0.0f;
-    const float w = kp_influence(sp, cx, cy, cz, inv_extent) * __shfl(inn, 4 * g + lg, 64);
-#pragma unroll
-    for (int r = 0; r < CV; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, vget<CV>(xv[g], r), acc[r], 0, 0, 0);
-  }
-}
-
 // D tile of one row (lane (li, lg): rows k = 4 lg + j, channels li CV + r) -> out[(row K + k) C + cbase + li CV ..]
 template <int CV>
 __device__ __forceinline__ void store_agg_row(float* __restrict__ out_row, int K, int C, int cbase, int li, int lg,
@@ -84,9 +59,8 @@ __global__ __launch_bounds__(256, (NSTEPS >= 4 ? 3 : 4)) void kpconv_agg_fwd_ker
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int q0 = blockIdx.x * 16;
-  const bool klive = li < K;
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_sp = make_rsrc(spack, (unsigned)Ns * 16u);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, (unsigned)Ns * (unsigned)Cin * 4u);
   const int cbase = blockIdx.y * CC;
@@ -101,7 +75,10 @@ __global__ __launch_bounds__(256, (NSTEPS >= 4 ? 3 : 4)) void kpconv_agg_fwd_ker
 
 // transposed direction over the EXACT-form reverse table (reverse_table.hip: row s = its true reverse neighbors,
 // compacted, as float4 {q - s, bits of q}): grid (support tiles of 16, channel chunks of 16 CV)
-template <int CV>
+// HAS_NN false: g is already divided by nn (training hands it over that way) -- no nn resource, gather or wait exists.
+// With nn, a row's gather of it is requested behind the row's gradient-row gathers (dxg_core), so it heads no round
+// trip of its own either: one for kernel points and entries, one per row.
+template <int CV, bool HAS_NN>
 __global__ __launch_bounds__(256) void kpconv_agg_rev_kernel(const float4* __restrict__ rev_rel, int W,
                                                              const float* __restrict__ g, const float* __restrict__ nn,
                                                              const float* __restrict__ kp, int Ns, int Nq, int Cout, int K,
@@ -110,29 +87,25 @@ __global__ __launch_bounds__(256) void kpconv_agg_rev_kernel(const float4* __res
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int s0 = blockIdx.x * 16 + wave * 4;
-  const bool klive = li < K;
   // |(s - q) - kp| = |(q - s) + kp|: the kernel points seen from s itself are negated
-  const float cx = klive ? -kp[3 * li + 0] : kFarKernelPoint, cy = klive ? -kp[3 * li + 1] : kFarKernelPoint,
-              cz = klive ? -kp[3 * li + 2] : kFarKernelPoint;
-  const __amdgpu_buffer_rsrc_t rs_nn = make_rsrc(nn ? nn : g, (unsigned)Nq * 4u);
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
+  const __amdgpu_buffer_rsrc_t rs_nn = make_rsrc(HAS_NN ? nn : g, (unsigned)Nq * 4u);
   const __amdgpu_buffer_rsrc_t rs_g = make_rsrc(g, (unsigned)Nq * (unsigned)Cout * 4u);
   const float inv_extent = 1.0f / extent;
   const unsigned row_bytes = (unsigned)Cout * 4u;
   const int cbase = blockIdx.y * CC;
   const unsigned col_off = (unsigned)(cbase + li * CV) * 4u;
-  // entries + 1/nn of the wave's four rows first: two memory round trips for four rows
+  // entries of the wave's four rows first
   float4 eA[4];
-  float nvA[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int s = s0 + i;
     eA[i] = rev_rel[(size_t)min(s, Ns - 1) * W + min(lane, W - 1)];
     if (!(s < Ns && lane < W)) eA[i].w = __int_as_float(Nq);
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    nvA[i] = __uint_as_float(
-        __builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)min(max(__float_as_int(eA[i].w), 0), Nq) * 4u, 0, 0));
+  const bool klive = li < K;
+  const float cx = klive ? -kx : kFarKernelPoint, cy = klive ? -ky : kFarKernelPoint, cz = klive ? -kz : kFarKernelPoint;
 #pragma unroll 1
   for (int i = 0; i < 4; ++i) {
     const int s = s0 + i;
@@ -141,29 +114,26 @@ __global__ __launch_bounds__(256) void kpconv_agg_rev_kernel(const float4* __res
     for (int r = 0; r < CV; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (s < Ns) {
       float4 e = eA[0];
-      float nv = nvA[0];
       for (int c0 = 0; c0 < W; c0 += 64) {
         if (c0 > 0) {   // rows longer than 64 entries (rare)
           e = rev_rel[(size_t)s * W + min(c0 + lane, W - 1)];
           if (c0 + lane >= W) e.w = __int_as_float(Nq);
-          nv = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)min(max(__float_as_int(e.w), 0), Nq) * 4u, 0, 0));
         }
         const int n = min(max(__float_as_int(e.w), 0), Nq);
         const int cnt = __popcll(__ballot(n < Nq));     // compacted: the live entries are a prefix
         if (cnt == 0) break;
-        const float inn = n < Nq ? (nn ? 1.0f / nv : 1.0f) : 0.0f;
-        const int steps = (cnt + 15) >> 4;
-        if (steps == 1) agg_rev_core<CV, 1>(n, e.x, e.y, e.z, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-        else if (steps == 2) agg_rev_core<CV, 2>(n, e.x, e.y, e.z, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-        else if (steps == 3) agg_rev_core<CV, 3>(n, e.x, e.y, e.z, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-        else agg_rev_core<CV, 4>(n, e.x, e.y, e.z, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
+        if (HAS_NN)
+          dxg_core_n<CV, true>((cnt + 15) >> 4, n, e.x, e.y, e.z, 0.0f, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent,
+                               lg, acc, Nq, rs_nn);
+        else
+          dxg_core_n<CV>((cnt + 15) >> 4, n, e.x, e.y, e.z, n < Nq ? 1.0f : 0.0f, rs_g, row_bytes, col_off, cx, cy, cz,
+                         inv_extent, lg, acc);
         if (cnt < 64) break;
       }
       store_agg_row<CV>(A + (size_t)s * K * Cout, K, Cout, cbase, li, lg, acc);
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { eA[j] = eA[j + 1]; nvA[j] = nvA[j + 1]; }
+    for (int j = 0; j < 3; ++j) eA[j] = eA[j + 1];
   }
 }
 
@@ -224,9 +194,18 @@ int d3f_kpconv_aggregate_transposed(const float* rev_rel, int rev_width, int Ns,
   dim3 grid(d3f::cdiv(Ns, 16), Cout / (16 * CV));
   const float4* rel = (const float4*)rev_rel;
   void* timing = d3f::kpconv_timing_open(6, st, Nq, Ns, rev_width, 0, Cout, K);
-  if (CV == 1) d3f::kpconv_agg_rev_kernel<1><<<grid, 256, 0, st>>>(rel, rev_width, grad_out, nn, kernel_points, Ns, Nq, Cout, K, extent, agg_out);
-  else if (CV == 2) d3f::kpconv_agg_rev_kernel<2><<<grid, 256, 0, st>>>(rel, rev_width, grad_out, nn, kernel_points, Ns, Nq, Cout, K, extent, agg_out);
-  else d3f::kpconv_agg_rev_kernel<4><<<grid, 256, 0, st>>>(rel, rev_width, grad_out, nn, kernel_points, Ns, Nq, Cout, K, extent, agg_out);
+#define D3F_AGGR(CVV, NN) \
+  d3f::kpconv_agg_rev_kernel<CVV, NN><<<grid, 256, 0, st>>>(rel, rev_width, grad_out, nn, kernel_points, Ns, Nq, Cout, K, extent, agg_out)
+  if (nn) {
+    if (CV == 1) D3F_AGGR(1, true);
+    else if (CV == 2) D3F_AGGR(2, true);
+    else D3F_AGGR(4, true);
+  } else {
+    if (CV == 1) D3F_AGGR(1, false);
+    else if (CV == 2) D3F_AGGR(2, false);
+    else D3F_AGGR(4, false);
+  }
+#undef D3F_AGGR
   d3f::kpconv_timing_close(timing, st);
   D3F_LAUNCH_CHECK();
   return D3F_OK;

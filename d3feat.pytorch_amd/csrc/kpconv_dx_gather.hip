@@ -36,50 +36,12 @@ struct RevTest {
                              // layer, radius 2r): only its entries with d2 < r2 belong to the transposed table
 };
 
-// Feature gathers + MFMAs of one prepared chunk: lane l holds entry l of the (compacted) list -- its query index n_c
-// (Nq = none), that query's position RELATIVE TO THE ROW'S SUPPORT (q - s, exact; the centres are then -kp) and 1/nn
-// (0 = none); `NSTEPS` 16-entry MFMA steps cover the live prefix.
-template <int CV, int NSTEPS>
-__device__ __forceinline__ void dxg_core(int n_c, float qx, float qy, float qz, float inn, __amdgpu_buffer_rsrc_t rs_g,
-                                         unsigned row_bytes, unsigned col_off, float cx, float cy, float cz,
-                                         float inv_extent, int lg, f32x4 (&acc)[CV]) {
-  constexpr int NG = 4 * NSTEPS;
-  typename VecT<CV>::type xv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const unsigned n = (unsigned)__shfl(n_c, 4 * g + lg, 64);
-    xv[g] = buf_load_vec<CV>(rs_g, n * row_bytes + col_off);
-  }
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    float4 sp;
-    sp.x = __shfl(qx, 4 * g + lg, 64);
-    sp.y = __shfl(qy, 4 * g + lg, 64);
-    sp.z = __shfl(qz, 4 * g + lg, 64);
-    sp.w = 0.0f;
-    const float w = kp_influence(sp, cx, cy, cz, inv_extent) * __shfl(inn, 4 * g + lg, 64);
-#pragma unroll
-    for (int r = 0; r < CV; ++r)
-      acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, vget<CV>(xv[g], r), acc[r], 0, 0, 0);
-  }
-}
-
-template <int CV>
-__device__ __forceinline__ void dxg_core_n(int steps, int n_c, float qx, float qy, float qz, float inn,
-                                           __amdgpu_buffer_rsrc_t rs_g, unsigned row_bytes, unsigned col_off, float cx,
-                                           float cy, float cz, float inv_extent, int lg, f32x4 (&acc)[CV]) {
-  if (steps == 1) dxg_core<CV, 1>(n_c, qx, qy, qz, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-  else if (steps == 2) dxg_core<CV, 2>(n_c, qx, qy, qz, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-  else if (steps == 3) dxg_core<CV, 3>(n_c, qx, qy, qz, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-  else dxg_core<CV, 4>(n_c, qx, qy, qz, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
-}
-
 // Table form, one 64-entry chunk of the row of support s: membership of every entry FIRST (position + last key of the
 // entry's query: 20 bytes), live entries compacted to the front of the wave through a 64-entry LDS scratch, and only
 // then the Cout-wide gradient rows of the LIVE entries are gathered -- a pooling layer's transpose is the d2 < r2 head
 // of a row of the (radius 2r) upsampling table: 4x fewer gathers and one MFMA step instead of three.
-template <int CV>
-__device__ __forceinline__ void dxg_table_chunk(int n, float qx, float qy, float qz, float nnv, uint64_t lk, bool has_nn,
+template <int CV, bool HAS_NN>
+__device__ __forceinline__ void dxg_table_chunk(int n, float qx, float qy, float qz, float nnv, uint64_t lk,
                                                 const RevTest& rt, int Nq, int last_lane, int32_t* status,
                                                 float4* scr4, float* scr1, __amdgpu_buffer_rsrc_t rs_g,
                                                 unsigned row_bytes, unsigned col_off, float cx, float cy, float cz,
@@ -96,7 +58,7 @@ __device__ __forceinline__ void dxg_table_chunk(int n, float qx, float qy, float
   const int rank = __popcll(m & ((1ull << lane) - 1ull));
   if (member) {
     scr4[rank] = make_float4(qx - rt.sx, qy - rt.sy, qz - rt.sz, __int_as_float(n));
-    scr1[rank] = has_nn ? 1.0f / nnv : 1.0f;
+    scr1[rank] = HAS_NN ? 1.0f / nnv : 1.0f;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -108,7 +70,8 @@ __device__ __forceinline__ void dxg_table_chunk(int n, float qx, float qy, float
   dxg_core_n<CV>((cnt + 15) >> 4, n_c, c.x, c.y, c.z, inn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
 }
 
-template <int CV, int NBW, int WK>
+// HAS_NN false: gout is already divided by nn (training hands it over that way): no 1/nn gather in any table form.
+template <int CV, int NBW, int WK, bool HAS_NN>
 __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
     const float* __restrict__ s_pts, const float* __restrict__ q_pts, const int32_t* __restrict__ rev_ptr,
     const int32_t* __restrict__ rev_ent, const float* __restrict__ gout, const float* __restrict__ nn,
@@ -129,12 +92,12 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int s0 = blockIdx.x * 16;
-  const bool klive = li < K;
   // kernel point li as seen from the row's point s: |(s - q) - kp| = |(q - s) - (-kp)|
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(q_pts, (unsigned)Nq * 12u);
-  const __amdgpu_buffer_rsrc_t rs_nn = make_rsrc(nn ? nn : q_pts, (unsigned)Nq * 4u);
+  // (HAS_NN false: the caller's gradient is already divided by nn -- training -- and no load through rs_nn exists)
+  const __amdgpu_buffer_rsrc_t rs_nn = make_rsrc(HAS_NN ? nn : q_pts, (unsigned)Nq * 4u);
   const __amdgpu_buffer_rsrc_t rs_g = make_rsrc(gout, (unsigned)Nq * (unsigned)Cout * 4u);
   const float inv_extent = 1.0f / extent;
   const int wn = (WK == 1) ? wave : (WK == 2 ? (wave & 1) : 0);
@@ -160,14 +123,14 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
     // ------------------------------------------------------------------ phase A: 4 rows per wave
     if (rev_rel) {
       // exact form (d3f_reverse_table_filter): row s = its true reverse neighbors, compacted, as {q - s, q}: one coalesced
-      // kilobyte per row and a 4-byte gather of 1/nn per entry; the kernel points are seen from s itself (centre = -kp).
+      // kilobyte per row and, with nn, a 4-byte gather per entry, requested behind the row's gradient-row gathers
+      // (dxg_core); the kernel points are seen from s itself (centre = -kp).
       // (A software-pipelined variant -- row i + 1's gradient-row gathers in flight under row i's MFMAs -- halved the
       // cycles per wave but needs 204 instead of 160 VGPRs at 32 channels, one occupancy step: 53.1 vs 50.4 us per
       // launch, profiles/r03_kpconv_phase_clock.txt; the kernel has no saturated unit -- MFMA 0.20, VALU 0.31, LDS 0.35,
       // TA 0.31 busy -- it is bound by how many dependent phases the resident waves overlap.)
       const int W = rev_width;
       float4 eA[4];
-      float nvA[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int s = s0 + wave * 4 + i;
@@ -176,10 +139,6 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         eA[i] = rev_rel[(size_t)min(s, Ns - 1) * W + min(lane, W - 1)];
         if (!(s < Ns && lane < W)) eA[i].w = __int_as_float(Nq);
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        nvA[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-            rs_nn, (unsigned)min(max(__float_as_int(eA[i].w), 0), Nq) * 4u, 0, 0));
       if (clk) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         pc.lap(1);
@@ -192,26 +151,26 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         for (int r = 0; r < CV; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (s < Ns) {
           float4 e = eA[0];
-          float nv = nvA[0];
           for (int c0 = 0; c0 < W; c0 += 64) {
             if (c0 > 0) {   // rows longer than 64 entries (rare)
               e = rev_rel[(size_t)s * W + min(c0 + lane, W - 1)];
               if (c0 + lane >= W) e.w = __int_as_float(Nq);
-              nv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                  rs_nn, (unsigned)min(max(__float_as_int(e.w), 0), Nq) * 4u, 0, 0));
             }
             const int n = min(max(__float_as_int(e.w), 0), Nq);
             const int cnt = __popcll(__ballot(n < Nq));     // compacted: the live entries are a prefix
             if (cnt == 0) break;
-            const float inn = n < Nq ? (nn ? 1.0f / nv : 1.0f) : 0.0f;
-            dxg_core_n<CV>((cnt + 15) >> 4, n, e.x, e.y, e.z, inn, rs_g, row_bytes, col_off, -kx, -ky, -kz, inv_extent,
-                           lg, acc);
+            if (HAS_NN)
+              dxg_core_n<CV, true>((cnt + 15) >> 4, n, e.x, e.y, e.z, 0.0f, rs_g, row_bytes, col_off, -kx, -ky, -kz,
+                                   inv_extent, lg, acc, Nq, rs_nn);
+            else
+              dxg_core_n<CV>((cnt + 15) >> 4, n, e.x, e.y, e.z, n < Nq ? 1.0f : 0.0f, rs_g, row_bytes, col_off, -kx, -ky,
+                             -kz, inv_extent, lg, acc);
             if (cnt < 64) break;
           }
         }
         store_wf_tile<CV>(tile + (wave * 4 + i) * RS, li, lg, acc);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { eA[j] = eA[j + 1]; nvA[j] = nvA[j + 1]; }
+        for (int j = 0; j < 3; ++j) eA[j] = eA[j + 1];
       }
     } else if (last_key) {
       // table form.  The index rows of the wave's four supports (two 64-entry chunks each) are fetched together, then
@@ -223,10 +182,17 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
       for (int i = 0; i < 4; ++i) {
         const int s = s0 + wave * 4 + i;
         const size_t rb = (size_t)min(s, Ns - 1) * W;
-        nA[i] = (s < Ns && lane < W) ? rev_ent[rb + lane] : Nq;
-        nB[i] = (s < Ns && 64 + lane < W) ? rev_ent[rb + 64 + lane] : Nq;
+        // (unconditional loads from clamped addresses, the select on the value: see the exact form above)
+        nA[i] = rev_ent[rb + min(lane, W - 1)];
+        nB[i] = rev_ent[rb + min(64 + lane, W - 1)];
       }
-      float qx[4], qy[4], qz[4], nv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool row = s0 + wave * 4 + i < Ns;
+        if (!(row && lane < W)) nA[i] = Nq;
+        if (!(row && 64 + lane < W)) nB[i] = Nq;
+      }
+      float qx[4], qy[4], qz[4], nv[4] = {1.0f, 1.0f, 1.0f, 1.0f};
       int lklo[4], lkhi[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         qx[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u, 0, 0));
         qy[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u + 4u, 0, 0));
         qz[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u + 8u, 0, 0));
-        nv[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, n * 4u, 0, 0));
+        if (HAS_NN) nv[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, n * 4u, 0, 0));
         const u32x2v k2 = __builtin_amdgcn_raw_buffer_load_b64(rs_lk, n * 8u, 0, 0);
         lklo[i] = (int)k2[0];
         lkhi[i] = (int)k2[1];
@@ -257,9 +223,8 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
           const RevTest rt = {last_key, sx, sy, sz, (unsigned)s, rev_r2};
           int32_t* st = ch == 0 ? status : nullptr;
           const uint64_t lk_i = ((uint64_t)(unsigned)lkhi[0] << 32) | (unsigned)lklo[0];
-          dxg_table_chunk<CV>(nA[0], qx[0], qy[0], qz[0], nv[0], lk_i,
-                              nn != nullptr, rt, Nq, W <= 64 ? W - 1 : -1, st, scr4, scr1, rs_g, row_bytes, col_off,
-                              cx, cy, cz, inv_extent, lane, lg, acc);
+          dxg_table_chunk<CV, HAS_NN>(nA[0], qx[0], qy[0], qz[0], nv[0], lk_i, rt, Nq, W <= 64 ? W - 1 : -1, st, scr4,
+                                      scr1, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lane, lg, acc);
           // rows longer than 64 entries (rare): further chunks on demand (the second one's indices are already here);
           // entries are ranked with the shadow entries last, so the first all-shadow chunk ends the row
           int nb = nB[0];
@@ -270,10 +235,11 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
             const float bx = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u, 0, 0));
             const float by = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u + 4u, 0, 0));
             const float bz = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, n * 12u + 8u, 0, 0));
-            const float bn = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, n * 4u, 0, 0));
+            const float bn =
+                HAS_NN ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, n * 4u, 0, 0)) : 1.0f;
             const u32x2v k2 = __builtin_amdgcn_raw_buffer_load_b64(rs_lk, n * 8u, 0, 0);
             const int last = (W - 1 >= c0 && W - 1 < c0 + 64) ? W - 1 - c0 : -1;
-            dxg_table_chunk<CV>(nb, bx, by, bz, bn, ((uint64_t)k2[1] << 32) | k2[0], nn != nullptr, rt, Nq, last, st,
+            dxg_table_chunk<CV, HAS_NN>(nb, bx, by, bz, bn, ((uint64_t)k2[1] << 32) | k2[0], rt, Nq, last, st,
                                 scr4, scr1, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lane, lg, acc);
           }
         }
@@ -282,7 +248,8 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           nA[j] = nA[j + 1]; nB[j] = nB[j + 1]; qx[j] = qx[j + 1]; qy[j] = qy[j + 1]; qz[j] = qz[j + 1];
-          nv[j] = nv[j + 1]; lklo[j] = lklo[j + 1]; lkhi[j] = lkhi[j + 1];
+          if (HAS_NN) nv[j] = nv[j + 1];
+          lklo[j] = lklo[j + 1]; lkhi[j] = lkhi[j + 1];
         }
       }
     } else
@@ -299,13 +266,15 @@ __global__ __launch_bounds__(256) void kpconv_dx_gather_kernel(
         const float sx = s_pts[3 * (size_t)s + 0], sy = s_pts[3 * (size_t)s + 1], sz = s_pts[3 * (size_t)s + 2];
         for (int c0 = beg; c0 < end; c0 += 64) {
           const int rem = min(end - c0, 64);
-          const int n = lane < rem ? min(max(rev_ent[(size_t)c0 + lane], 0), Nq) : Nq;
+          const int n_raw = rev_ent[(size_t)c0 + min(lane, rem - 1)];   // (clamped address; the select is on the value)
+          const int n = lane < rem ? min(max(n_raw, 0), Nq) : Nq;
           // the lane's own reverse neighbor: position and 1/nn (a shadow lane reads zeros and gets weight 0)
           const float qx = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)n * 12u, 0, 0));
           const float qy = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)n * 12u + 4u, 0, 0));
           const float qz = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)n * 12u + 8u, 0, 0));
-          const float nnv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)n * 4u, 0, 0));
-          const float inn = (lane < rem && n < Nq) ? (nn ? 1.0f / nnv : 1.0f) : 0.0f;
+          const float nnv =
+              HAS_NN ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)n * 4u, 0, 0)) : 1.0f;
+          const float inn = (lane < rem && n < Nq) ? (HAS_NN ? 1.0f / nnv : 1.0f) : 0.0f;
           dxg_core_n<CV>((rem + 15) >> 4, n, qx - sx, qy - sy, qz - sz, inn, rs_g, row_bytes, col_off, -kx, -ky, -kz,
                          inv_extent, lg, acc);
         }
@@ -409,10 +378,14 @@ static int launch_dxg(const float* s_pts, const float* q_pts, const int32_t* rev
   {                                                                                                                 \
     const size_t lds = lds_base + ((WK) > 1 ? sizeof(float) * 16 * (size_t)slab : 0);                               \
     dim3 grid(tiles, Cin / slab);                                                                                   \
-    kpconv_dx_gather_kernel<CV, NBW, WK><<<grid, 256, lds, stream>>>(s_pts, q_pts, rev_ptr, rev_ent, gout, nn, kp, W, \
-                                                                      Ns, Nq, Cin, Cout, K, extent, gx, last_key,    \
-                                                                      rev_width, rev_r2, status, phase_clock_ptr(), \
-                                                                      rev_rel);                                     \
+    if (nn)                                                                                                         \
+      kpconv_dx_gather_kernel<CV, NBW, WK, true><<<grid, 256, lds, stream>>>(                                       \
+          s_pts, q_pts, rev_ptr, rev_ent, gout, nn, kp, W, Ns, Nq, Cin, Cout, K, extent, gx, last_key, rev_width,   \
+          rev_r2, status, phase_clock_ptr(), rev_rel);                                                              \
+    else                                                                                                            \
+      kpconv_dx_gather_kernel<CV, NBW, WK, false><<<grid, 256, lds, stream>>>(                                      \
+          s_pts, q_pts, rev_ptr, rev_ent, gout, nn, kp, W, Ns, Nq, Cin, Cout, K, extent, gx, last_key, rev_width,   \
+          rev_r2, status, phase_clock_ptr(), rev_rel);                                                              \
   }
   void* timing = kpconv_timing_open(3, stream, Nq, Ns, 0, Cin, Cout, K);
   switch (slab) {

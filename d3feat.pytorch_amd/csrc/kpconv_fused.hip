@@ -144,9 +144,8 @@ __global__ __launch_bounds__(256) void kpconv_fwd_fused_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int q0 = blockIdx.x * 16;
-  const bool klive = li < K;
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_sp = make_rsrc(spack, (unsigned)Ns * 16u);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, (unsigned)Ns * (unsigned)Cin * 4u);
   const float inv_extent = 1.0f / extent;
@@ -348,13 +347,7 @@ __global__ __launch_bounds__(256) void kpconv_bwd_dx_kernel(
   const float inv_extent = 1.0f / extent;
   float kpx[4], kpy[4], kpz[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int k = 4 * s + lg;
-    const bool live = k < K;
-    kpx[s] = live ? kp[3 * k + 0] : kFarKernelPoint;
-    kpy[s] = live ? kp[3 * k + 1] : kFarKernelPoint;
-    kpz[s] = live ? kp[3 * k + 2] : kFarKernelPoint;
-  }
+  for (int s = 0; s < 4; ++s) load_kernel_point(kp, K, 4 * s + lg, kpx[s], kpy[s], kpz[s]);
 #pragma unroll 1
   for (int i = iq; i < 4; i += qsplit) {
     const int ql = wave * 4 + i;
@@ -413,9 +406,8 @@ __global__ __launch_bounds__(256) void kpconv_bwd_dw_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int cbase = blockIdx.y * CC, obase = blockIdx.z * SLAB;
-  const bool klive = li < K;
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_sp = make_rsrc(spack, (unsigned)Ns * 16u);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, (unsigned)Ns * (unsigned)Cin * 4u);
   const float inv_extent = 1.0f / extent;

@@ -81,8 +81,8 @@ __global__ __launch_bounds__(256) void kpconv_small_fwd_kernel(const float* __re
   const int li = lane & 15;
   const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
   const bool klive = li < K;
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_s = make_rsrc(s_pts, (unsigned)Ns * 12u);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, (unsigned)Ns * CIN * 4u);
   const float inv_extent = 1.0f / extent;
@@ -142,9 +142,8 @@ __global__ __launch_bounds__(256) void kpconv_small_dw_kernel(const float* __res
   const int lane = threadIdx.x & 63;
   const int li = lane & 15;
   const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-  const bool klive = li < K;
-  const float kx = klive ? kp[3 * li + 0] : kFarKernelPoint, ky = klive ? kp[3 * li + 1] : kFarKernelPoint,
-              kz = klive ? kp[3 * li + 2] : kFarKernelPoint;
+  float kx, ky, kz;
+  load_kernel_point(kp, K, li, kx, ky, kz);
   const __amdgpu_buffer_rsrc_t rs_s = make_rsrc(s_pts, (unsigned)Ns * 12u);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, (unsigned)Ns * CIN * 4u);
   const float inv_extent = 1.0f / extent;

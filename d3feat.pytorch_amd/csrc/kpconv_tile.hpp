@@ -61,6 +61,19 @@ __device__ __forceinline__ float4 buf_load_vec<4>(__amdgpu_buffer_rsrc_t r, unsi
 // clamps to exactly 0 without a select in the inner loop.
 constexpr float kFarKernelPoint = 1e18f;
 
+// The loads are unconditional, from an address clamped into the table (K >= 1), and the select is on the VALUE:
+// `li < K ? kp[3 * li + c] : far` compiles to a branch around each load with a full wait behind it, three dependent
+// memory round trips at the head of the kernel before its other prologue loads are even requested.
+__device__ __forceinline__ void load_kernel_point(const float* __restrict__ kp, int K, int li, float& kx, float& ky,
+                                                  float& kz) {
+  const float* p = kp + 3 * min(li, K - 1);
+  const float x = p[0], y = p[1], z = p[2];
+  const bool klive = li < K;
+  kx = klive ? x : kFarKernelPoint;
+  ky = klive ? y : kFarKernelPoint;
+  kz = klive ? z : kFarKernelPoint;
+}
+
 // influence of the kernel point at (cx,cy,cz) on a neighbor whose position RELATIVE TO THE QUERY is sp
 // (blocks.py:283-336):   w = max(0, 1 - sqrt(|(s - q) - kp|^2)/extent)
 // The caller subtracts the query first, as the reference does: s - q of two neighbouring float32 points is exact
@@ -139,21 +152,30 @@ __device__ __forceinline__ void aggregate_wave_n(const int (&nall)[4], const flo
   }
 }
 
-// (query position, clamped index row) of the wave's four queries
+// (query position, clamped index row) of the wave's four queries: the four index rows, then the four positions, all
+// requested before anything waits -- one memory round trip, and the first gather waits for the first row alone.
+// Every load is unconditional from an address clamped into its tensor (Nq, H >= 1); a dead query or a lane >= H
+// selects the shadow index on the loaded VALUE (a conditional load is a branch with a full wait behind it: four
+// serial round trips here).
 template <int DUMMY = 0>
 __device__ __forceinline__ void load_wave_queries(const float* __restrict__ q_pts, const int32_t* __restrict__ idx,
                                                   int q_first, int Nq, int H, int Ns, int lane, int (&nall)[4],
                                                   float (&qx)[4], float (&qy)[4], float (&qz)[4]) {
+  const int ls = min(lane, H - 1);
+  int raw[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) raw[i] = idx[(size_t)min(q_first + i, Nq - 1) * H + ls];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int q = q_first + i;
-    const bool live = q < Nq;
-    const int n = (live && lane < H) ? idx[(size_t)q * H + lane] : Ns;
-    nall[i] = (int)min((unsigned)n, (unsigned)Ns);  // negative / oversized entries behave like the shadow index
-    const int qs = live ? q : 0;
+    const int qs = q_first + i < Nq ? q_first + i : 0;
     qx[i] = q_pts[3 * (size_t)qs + 0];
     qy[i] = q_pts[3 * (size_t)qs + 1];
     qz[i] = q_pts[3 * (size_t)qs + 2];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int n = (q_first + i < Nq && lane < H) ? raw[i] : Ns;
+    nall[i] = (int)min((unsigned)n, (unsigned)Ns);  // negative / oversized entries behave like the shadow index
   }
 }
 
@@ -197,6 +219,53 @@ __device__ __forceinline__ void aggregate_wave_steps(const float* __restrict__ q
   load_wave_queries(q_pts, idx, q_first, Nq, H, Ns, lane, nall, qx, qy, qz);
   aggregate_wave_n<CV, NSTEPS>(nall, qx, qy, qz, kx, ky, kz, rs_sp, rs_x, (unsigned)Cin * 4u,
                                (unsigned)(cbase + li * CV) * 4u, inv_extent, lg, lane, nn_lds, flush);
+}
+
+// The transposed direction (kpconv_dx_gather.hip phase A, kpconv_aggregate.hip): gradient-row gathers + MFMAs of one
+// prepared chunk of a reverse row.  Lane l holds entry l of the (compacted) list -- its query index n_c (Nq = none),
+// that query's position RELATIVE TO THE ROW'S SUPPORT (q - s, exact; the centres are then -kp) and 1/nn (0 = none);
+// `NSTEPS` 16-entry MFMA steps cover the live prefix.  NN_GATHER: the lane's nn[n_c] is still to be fetched (through
+// `rs_nn`; `inn` is unused) -- requested BEHIND the gradient-row gathers, which need the entry alone, so that it
+// shares their round trip instead of heading one of its own (requested ahead of them, the scheduler lifts the
+// division and its wait among the gathers).
+template <int CV, int NSTEPS, bool NN_GATHER>
+__device__ __forceinline__ void dxg_core(int n_c, float qx, float qy, float qz, float inn, int Nq,
+                                         __amdgpu_buffer_rsrc_t rs_nn, __amdgpu_buffer_rsrc_t rs_g, unsigned row_bytes, unsigned col_off, float cx,
+                                         float cy, float cz, float inv_extent, int lg, f32x4 (&acc)[CV]) {
+  constexpr int NG = 4 * NSTEPS;
+  typename VecT<CV>::type xv[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const unsigned n = (unsigned)__shfl(n_c, 4 * g + lg, 64);
+    xv[g] = buf_load_vec<CV>(rs_g, n * row_bytes + col_off);
+  }
+  if (NN_GATHER) {
+    const float nv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_nn, (unsigned)n_c * 4u, 0, 0));
+    inn = n_c < Nq ? 1.0f / nv : 0.0f;
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    float4 sp;
+    sp.x = __shfl(qx, 4 * g + lg, 64);
+    sp.y = __shfl(qy, 4 * g + lg, 64);
+    sp.z = __shfl(qz, 4 * g + lg, 64);
+    sp.w = 0.0f;
+    const float w = kp_influence(sp, cx, cy, cz, inv_extent) * __shfl(inn, 4 * g + lg, 64);
+#pragma unroll
+    for (int r = 0; r < CV; ++r)
+      acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, vget<CV>(xv[g], r), acc[r], 0, 0, 0);
+  }
+}
+
+template <int CV, bool NN_GATHER = false>
+__device__ __forceinline__ void dxg_core_n(int steps, int n_c, float qx, float qy, float qz, float inn,
+                                           __amdgpu_buffer_rsrc_t rs_g, unsigned row_bytes, unsigned col_off, float cx,
+                                           float cy, float cz, float inv_extent, int lg, f32x4 (&acc)[CV], int Nq = 0,
+                                           __amdgpu_buffer_rsrc_t rs_nn = __amdgpu_buffer_rsrc_t()) {
+  if (steps == 1) dxg_core<CV, 1, NN_GATHER>(n_c, qx, qy, qz, inn, Nq, rs_nn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
+  else if (steps == 2) dxg_core<CV, 2, NN_GATHER>(n_c, qx, qy, qz, inn, Nq, rs_nn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
+  else if (steps == 3) dxg_core<CV, 3, NN_GATHER>(n_c, qx, qy, qz, inn, Nq, rs_nn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
+  else dxg_core<CV, 4, NN_GATHER>(n_c, qx, qy, qz, inn, Nq, rs_nn, rs_g, row_bytes, col_off, cx, cy, cz, inv_extent, lg, acc);
 }
 
 // store one query's D tile (rows k = 4*lg + i, column li -> channels li*CV + r) into a [16][CC] LDS row block.
