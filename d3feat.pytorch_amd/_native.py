@@ -5,6 +5,7 @@ operator raises ``RuntimeError`` (the reference's only error type, cpp_neighbors
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -16,310 +17,120 @@ SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_f
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_extract.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
            "tsdf_mesh_sparse.hip", "fpfh.hip"]
 
-_vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-_d = C.c_double
+# The binding is READ from the header, once, at import: prototypes, struct layouts and integer #defines are stated there
+# alone.  What the closed type map below cannot take raises; nothing in the header is skipped.
+HEADER = os.path.join(_REPO, "include", "d3feat_hip.h")
+_SCALARS = {"void": None, "int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+            "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_POINTEES = set(_SCALARS) | {"char", "uint8_t"}     # what a c_void_p may point to, besides the structs
+_STRUCT = r"typedef\s+struct\s+(%s)\s*\{(.*?)\}\s*\1\s*;"
+
+
+def _code(text):
+    """The header without its comments and its extern "C" guards."""
+    return re.sub(r"#ifdef __cplusplus\n.*?#endif", "", re.sub(r"/\*.*?\*/", " ", text, flags=re.S), flags=re.S)
+
+
+def _declaration(text, structs, where):
+    """'const float* x' -> ('x', c_void_p), 'double R[9]' -> ('R', c_double * 9), 'int' -> ('', c_int)."""
+    m = re.fullmatch(r"\s*(\w+)\s*((?:\*\s*)*)(\w*)\s*(?:\[(\d+)\])?\s*", re.sub(r"\bconst\b", " ", text))
+    base, stars = (m.group(1), m.group(2).count("*")) if m else (None, 0)
+    if stars == 0 and base in _SCALARS:
+        ctype = _SCALARS[base]
+    elif stars == 1 and base == "char":
+        ctype = C.c_char_p
+    elif stars == 1 and base in structs:
+        ctype = C.POINTER(structs[base])
+    elif stars and (base in _POINTEES or base in structs):
+        ctype = C.c_void_p
+    else:
+        raise RuntimeError("d3feat_hip.h: %s: no ctypes type for %r" % (where, " ".join(text.split())))
+    return m.group(3), ctype * int(m.group(4)) if m.group(4) else ctype
+
+
+def parse_struct(text, name):
+    """The _fields_ of `typedef struct name { ... } name;`, one per declarator ('int32_t N, Cin;' holds two)."""
+    m = re.search(_STRUCT % name, _code(text), flags=re.S)
+    if not m:
+        raise RuntimeError("d3feat_hip.h: no struct %s" % name)
+    fields = []
+    for line in filter(str.strip, m.group(2).split(";")):
+        first, *others = re.sub(r"\bconst\b", " ", line).split(",")
+        base = re.match(r"\s*\w*", first).group(0)
+        fields += [_declaration(d, {}, "struct " + name) for d in [first] + [base + " " + d for d in others]]
+    if not all(field for field, _ in fields):
+        raise RuntimeError("d3feat_hip.h: struct %s: a field without a name" % name)
+    return fields
+
+
+def parse_defines(text):
+    """{D3F_X: value} of every #define D3F_X <integer expression>; the expression may name earlier defines."""
+    out = {}
+    for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(D3F_\w+)(.*)$", _code(text), flags=re.M):
+        try:
+            plain = re.sub(r"\bD3F_\w+", lambda m: "(%d)" % out[m.group(0)], expr)
+            value = eval(plain, {"__builtins__": {}}) if re.fullmatch(r"[\s0-9a-fA-FxX()+\-*<>|&~^]+", plain) else None
+        except Exception:       # a define that is not (yet) there, a syntax error
+            value = None
+        if type(value) is int:
+            out[name] = value
+        elif name != "D3F_SPACK_READY":         # a pointer cast, the one define that is no integer: ops.SPACK_READY
+            raise RuntimeError("d3feat_hip.h: #define %s %s: no integer expression" % (name, expr.strip()))
+    return out
+
+
+def parse_prototypes(text, structs):
+    """{name: (restype, [argtypes])}.  Every statement outside the structs has to be one prototype of a d3f_ function,
+    and every `d3f_<name>(` in the header one of them."""
+    code = re.sub(_STRUCT % r"\w+", "", re.sub(r"^[ \t]*#.*$", "", _code(text), flags=re.M), flags=re.S)
+    out = {}
+    for st in filter(str.strip, re.split(r"(?<=;)", code)):        # each statement with its ';'
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(d3f_\w+)\s*\(([^()]*)\)\s*;", st)
+        if not m or m.group(2) in out:
+            raise RuntimeError("d3feat_hip.h: not one whole, new prototype: %r" % " ".join(st.split())[:200])
+        name, params = m.group(2), [] if m.group(3).strip() == "void" else m.group(3).split(",")
+        out[name] = (_declaration(m.group(1), structs, name + ", return type")[1],
+                     [_declaration(p, structs, name)[1] for p in params])
+    if len(re.findall(r"\bd3f_\w+\s*\(", _code(text))) != len(out):
+        raise RuntimeError("d3feat_hip.h: d3f_<name>( occurs outside the %d prototypes" % len(out))
+    return out
+
+
+with open(HEADER) as _f:
+    _TEXT = _f.read()
 
 
 class Tunables(C.Structure):
     """d3f_tunables of include/d3feat_hip.h: the library's knobs (it never reads the environment)."""
-    _fields_ = [("atb_task_us", C.c_int32), ("atb_form", C.c_int32), ("atb_first_form_wgs", C.c_int32),
-                ("match_wgs", C.c_int32), ("agg_through_lds", C.c_int32), ("atb_pipe", C.c_int32), ("xw_rows", C.c_int32), ("xw_split", C.c_int32),
-                ("rowgemm_wide", C.c_int32), ("rowgemm_rt", C.c_int32), ("reserved", C.c_int32 * 6)]
+    _fields_ = parse_struct(_TEXT, "d3f_tunables")
 
 
 class AtbProblem(C.Structure):
     """d3f_atb_problem of include/d3feat_hip.h: one queued weight gradient grad_w [Cout, ldw] = grad_out^T x."""
-    _fields_ = [("x", _vp), ("grad_out", _vp), ("grad_w", _vp), ("N", C.c_int32), ("Cin", C.c_int32),
-                ("Cout", C.c_int32), ("ldw", C.c_int32), ("bias_part", _vp), ("bias_blocks", C.c_int32),
-                ("bias_cols", C.c_int32), ("grad_bias", _vp), ("grad_bias2", _vp)]
+    _fields_ = parse_struct(_TEXT, "d3f_atb_problem")
 
 
 class AugmentJob(C.Structure):
     """d3f_augment_job of include/d3feat_hip.h: one training item of the resident 3DMatch split."""
-    _fields_ = [("src_off", C.c_int64), ("tgt_off", C.c_int64), ("corr_off", C.c_int64), ("src_len", C.c_int32),
-                ("tgt_len", C.c_int32), ("corr_len", C.c_int32), ("reserved", C.c_int32), ("R", C.c_double * 9),
-                ("t", C.c_double * 3), ("key", C.c_uint64), ("out_src", _vp), ("out_tgt", _vp), ("out_corr", _vp),
-                ("out_dist", _vp)]
+    _fields_ = parse_struct(_TEXT, "d3f_augment_job")
 
 
-_i64 = C.c_int64
+STRUCTS = {"d3f_tunables": Tunables, "d3f_atb_problem": AtbProblem, "d3f_augment_job": AugmentJob}
+SIGNATURES = parse_prototypes(_TEXT, STRUCTS)   # name -> (restype, argtypes)
+DEFINES = parse_defines(_TEXT)                  # every integer #define D3F_X; each also a module attribute _native.D3F_X
+globals().update(DEFINES)
+del _f, _TEXT
 
-
-def _tsdf_integrate_signatures():
-    """The sixteen entry points that write a fused model (csrc/tsdf_integrate.hip), each from the same pieces: the depth
-    (the colour forms: the colour frames and the channels too), the frames, the model's tables around K, M, origin,
-    dims, voxel and trunc, the depth range, D and w (the colour forms: the colour volume too), the stream."""
-    frames = [_i, _i, _i, _i, _vp]                             # depth_is_f32, F, H, W, frame_start
-    common = [_vp, _vp, _vp, _vp, _vp, _vp]                    # K, M, origin, dims, voxel, trunc
-    dense = frames + [_vp, _i, _i64, _i64] + common            # vol_start, V, total_voxels, max_volume_voxels
-    bricks = frames + [_i] + common + [_vp, _vp, _i64]         # V; brick_start, brick_coord, bricks
-    sigs = {}
-    for stem, model, host_stream in (("", dense, [_vp]), ("_sparse", bricks, [])):     # the sparse twins take no stream
-        for into in ("", "_into"):
-            for host, stream in (("", [_vp]), ("_host", host_stream)):
-                name = "d3f_tsdf" + stem + "_integrate%s" + into + host
-                sigs[name % ""] = (_i, [_vp] + model + [_f, _f, _vp, _vp] + stream)
-                sigs[name % "_color"] = (_i, [_vp, _vp, _i] + model + [_f, _f, _vp, _vp, _vp] + stream)
-    return sigs
-
-
-def _tsdf_reader_signatures():
-    """The twelve entry points that read a fused model (csrc/tsdf_raycast.hip), each from the same pieces: D and w (the
-    colour forms: Cv and the channels too), the model's tables, the views or the points with their outputs, the colour
-    image, the stream."""
-    dense = [_vp, _vp, _vp, _vp, _i, _i64]                     # vol_start, origin, dims, voxel, V, total_voxels
-    bricks = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64]    # lattice_start, brick_start, brick_index, origin, dims,
-    #                                                            voxel, V, lattice_bricks, bricks
-    views = [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i]   # view_volume, R, H, W, K, C, step, depth_min, depth_max,
-    #                                                            min_weight, clip
-    points = [_vp, _vp, _i64, _f, _vp]                         # points, point_start, N, min_weight, out
-    sigs = {}
-    for stem, model, skip in (("", dense, []), ("_sparse", bricks, [_i])):
-        cast = model + views + skip + [_vp, _vp]               # ..., depth, normals
-        for host in ("", "_host"):
-            sigs["d3f_tsdf_raycast" + stem + host] = (_i, [_vp, _vp] + cast + [_vp])
-            sigs["d3f_tsdf_raycast" + stem + "_color" + host] = (_i, [_vp, _vp, _vp, _i] + cast + [_vp, _vp])
-            sigs["d3f_tsdf_sample_color" + stem + host] = (_i, [_vp, _vp, _i] + model + points + [_vp])
-    return sigs
-
-
-def _tsdf_surface_signatures():
-    """The sixteen entry points that take the surface out of a fused model (csrc/tsdf_extract.hip, csrc/tsdf_mesh.hip,
-    csrc/tsdf_mesh_sparse.hip): d3f_tsdf[_sparse]_{extract,mesh} x {_ws_bytes, _count, the emit form, _host}, each from
-    the same pieces: D and w, the model's tables (the count forms take neither origin nor voxel), min_weight, the
-    capacities and the outputs, the workspace and the stream (the twins take neither)."""
-    dense = ([_vp, _vp, _i, _i64],                             # vol_start, dims, V, total_voxels
-             [_vp, _vp, _vp, _vp, _i, _i64])                   # vol_start, origin, dims, voxel, V, total_voxels
-    rows = [_vp, _vp, _vp, _vp]                                # lattice_start, brick_start, brick_index, brick_coord
-    bricks = (rows + [_vp, _i, _i64, _i64],                    # ..., dims, V, lattice_bricks, bricks
-              rows + [_vp, _vp, _vp, _i, _i64, _i64])          # ..., origin, dims, voxel, V, lattice_bricks, bricks
-    ws = [_vp, _sz, _vp]                                       # ws, ws_bytes, stream
-    sigs = {}
-    for stem, (counted, model) in (("", dense), ("_sparse", bricks)):
-        for what, starts, capacities, rest in (("extract", [_vp], [_i64], [_vp, _vp, _vp]),        # points, point_start, status
-                                               ("mesh", [_vp, _vp], [_i64, _i64], [_vp] * 6)):    # vertices, normals, faces, the starts, status
-            name = "d3f_tsdf" + stem + "_" + what
-            sigs[name + "_ws_bytes"] = (_sz, [_i64])
-            sigs[name + "_count"] = (_i, [_vp, _vp] + counted + [_f] + starts + ws)
-            sigs[name] = (_i, [_vp, _vp] + model + [_f, _i] + capacities + rest + ws)
-            sigs[name + "_host"] = (_i, [_vp, _vp] + model + [_f] + capacities + rest)
-    return sigs
-
-
-# name -> (restype, argtypes); mirrors include/d3feat_hip.h one to one
-SIGNATURES = {
-    "d3f_version": (C.c_char_p, []),
-    "d3f_device_arch_ok": (_i, []),
-    "d3f_device_arch_name": (_i, [C.c_char_p, _i]),
-    "d3f_debug_set_flags": (None, [_i]),
-    "d3f_get_tunables": (None, [C.POINTER(Tunables)]),
-    "d3f_set_tunables": (_i, [C.POINTER(Tunables)]),
-    "d3f_linear_grad_weight_group_ws_bytes": (_sz, [C.POINTER(AtbProblem), _i]),
-    "d3f_linear_grad_weight_group": (_i, [C.POINTER(AtbProblem), _i, _vp, _sz, _vp]),
-    "d3f_debug_set_phase_clock": (None, [_vp]),
-    "d3f_debug_kernel_timing_begin": (_i, [_i, _i]),
-    "d3f_debug_kernel_timing_end": (_i, [_vp, _vp, _i]),
-    "d3f_radius_grid_ws_bytes": (_sz, [_i]),
-    "d3f_radius_grid_build": (_i, [_vp, _i, _vp, _i, _f, _vp, _sz, _vp, _vp]),
-    "d3f_radius_query": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_radius_query_ex": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
-    "d3f_radius_grid_zero_bytes": (_sz, [_i]),
-    "d3f_zero_buffers": (_i, [_vp, _vp, _i, _vp]),
-    "d3f_copy_buffers": (_i, [_vp, _vp, _vp, _vp, _i, C.c_double, _vp]),
-    "d3f_radius_grid_build_prezeroed": (_i, [_vp, _i, _vp, _i, _f, _vp, _sz, _vp, _vp]),
-    "d3f_radius_query_prefix": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
-    "d3f_radius_query_prefix_missing": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
-    "d3f_radius_query_pool_transposed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp,
-                                              _vp]),
-    "d3f_upsample_rows_rank": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "d3f_grid_subsample_ws_bytes": (_sz, [_i, _i]),
-    "d3f_grid_subsample": (_i, [_vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "d3f_grid_subsample_ex": (_i, [_vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz,
-                                   _vp, _vp]),
-    "d3f_kpconv_deform_aggregate": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp,
-                                         _vp]),
-    "d3f_kpconv_deform_grad": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
-    "d3f_bias_act_packs": (_i, [_i]),
-    "d3f_bias_act_forward_pack": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "d3f_batchnorm_ws_bytes": (_sz, [_i, _i]),
-    "d3f_batchnorm_forward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_batchnorm_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_kpconv_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "d3f_kpconv_forward": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp,
-                                _vp, _sz, _vp]),
-    "d3f_kpconv_packs_supports": (_i, [_i, _i, _i, _i, _i]),
-    "d3f_kpconv_saves_wf": (_i, [_i, _i, _i, _i]),
-    "d3f_kpconv_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _i,
-                                 _vp, _vp, _vp, _sz, _vp]),
-    "d3f_kpconv_grad_input_supported": (_i, [_i, _i, _i, _i]),
-    "d3f_kpconv_aggregate": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_kpconv_aggregate_modes": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp]),
-    "d3f_kpconv_grad_input_modes": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _f, _i, _vp, _vp, _vp]),
-    "d3f_kpconv_grad_input": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "d3f_kpconv_aggregate_transposed_supported": (_i, [_i, _i]),
-    "d3f_kpconv_aggregate_transposed": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _vp]),
-    "d3f_reverse_table_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_reverse_table_build": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_kpconv_grad_input_gather_supported": (_i, [_i, _i, _i]),
-    "d3f_kpconv_grad_input_gather": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp,
-                                          _vp, _vp]),
-    "d3f_reverse_table_filter": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
-    "d3f_linear_grad_weight_supported": (_i, [_i, _i, _i]),
-    "d3f_linear_fused_supported": (_i, [_i, _i, _i]),
-    "d3f_linear_bias_act_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
-    "d3f_linear_pair_supported": (_i, [_i, _i, _i, _i]),
-    "d3f_linear_pair_bias_act_forward": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
-    "d3f_linear_grad_input": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "d3f_linear_grad_weight_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_linear_grad_weight": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "d3f_linear_grad_weight_bias": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp]),
-    "d3f_permute_kpconv_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "d3f_gemm_epilogue_supported": (_i, [_i, _i, _i, _i, _i]),
-    "d3f_gemm_epilogue_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_gemm_epilogue": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _i, _vp, _sz,
-                               _vp]),
-    "d3f_bias_act_backward_blocks": (_i, [_i, _i]),
-    "d3f_bias_act_backward_partial": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_bias_sum": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "d3f_max_pool_forward": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "d3f_max_pool_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "d3f_closest_pool_forward": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "d3f_closest_pool_backward": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "d3f_bias_act_forward": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
-    "d3f_bias_act_backward_ws_bytes": (_sz, [_i, _i]),
-    "d3f_bias_act_backward": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "d3f_global_max": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
-    "d3f_global_max_rows": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "d3f_global_max_groups": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
-    "d3f_detection_scores_aux_floats": (_i, [_i]),
-    "d3f_detection_scores_forward": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "d3f_detection_scores_ws_bytes": (_sz, [_i, _i]),
-    "d3f_detection_scores_backward": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_detection_scores_backward_groups": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
-    "d3f_detection_rows_supported": (_i, [_i, _i]),
-    "d3f_detection_rows_ws_bytes": (_sz, [_i]),
-    "d3f_detection_rows_forward": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
-                                        _vp, _vp]),
-    "d3f_detection_rows_forward_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
-                                              _vp]),
-    "d3f_detection_rows_backward": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _sz, _vp]),
-    "d3f_detection_rows_backward_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
-                                               _vp, _sz, _vp]),
-    "d3f_circle_det_loss_forward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp,
-                                               _vp, _vp, _vp, _vp]),
-    "d3f_circle_det_loss_backward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp,
-                                                _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_select_normalize_forward_pairs": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_select_normalize_backward_pairs": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_circle_det_loss_stats_floats": (_sz, [_i]),
-    "d3f_contrastive_det_loss_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                                             _vp]),
-    "d3f_contrastive_det_loss_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              _vp]),
-    "d3f_contrastive_det_loss_forward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _d, _f, _f, _f, _f, _vp, _vp,
-                                                   _vp, _vp, _vp, _vp, _vp]),
-    "d3f_contrastive_det_loss_backward_pairs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp,
-                                                    _vp, _vp, _vp, _vp]),
-    "d3f_circle_det_loss_ws_bytes": (_sz, [_i]),
-    "d3f_circle_det_loss_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                                         _vp]),
-    "d3f_circle_det_loss_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_select_normalize_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_select_normalize_backward": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_mutual_nn_ws_bytes": (_sz, [_i, _i]),
-    "d3f_mutual_nn": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_mutual_nn_batched_ws_bytes": (_sz, [_i, _i]),
-    "d3f_mutual_nn_batched": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_topk_scores": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
-    "d3f_ransac_rigid_ws_bytes": (_sz, [_i, _i]),
-    "d3f_ransac_rigid": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                              _vp, _sz, _vp]),
-    "d3f_ransac_sample_host": (_i, [C.c_uint64, _i, _i, _i, _vp]),
-    "d3f_rigid_fit_host": (_i, [_vp, _vp, _i, _vp]),
-    "d3f_augment_pairs_ws_bytes": (_sz, [_i, _i]),
-    "d3f_augment_pairs": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(AugmentJob), _i, _i, _d, _vp, _sz, _vp]),
-    "d3f_augment_item_host": (_i, [_vp, _vp, C.POINTER(AugmentJob), _i, _d]),
-    "d3f_augment_key_host": (C.c_uint64, [C.c_uint64, _i, C.c_uint32]),
-    "d3f_cloud_grid_build": (_i, [_vp, _i, _vp, _i, _f, _vp, _sz, _vp, _vp]),
-    "d3f_nearest_pairs": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp]),
-    "d3f_nearest_pairs_lanes": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _i,
-                                     _vp]),
-    "d3f_icp_rigid_ws_bytes": (_sz, [_i, C.c_int64]),
-    "d3f_icp_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp,
-                           _vp, _vp, _vp, _sz, _vp]),
-    "d3f_icp_fit_host": (_i, [_vp, _vp, _vp, _vp]),
-    "d3f_estimate_normals": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_normal_from_moments_host": (_i, [_vp, _d, _vp, _vp]),
-    "d3f_icp_rigid_plane_ws_bytes": (_sz, [_i, C.c_int64]),
-    "d3f_icp_rigid_plane": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _i, _d, _d, _vp, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_icp_plane_fit_host": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "d3f_color_gradients": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_color_gradient_from_moments_host": (_i, [_vp, _d, _vp, _f, _i, _vp]),
-    "d3f_icp_rigid_color_ws_bytes": (_sz, [_i, C.c_int64]),
-    "d3f_icp_rigid_color": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _d, _i, _d, _d,
-                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_fpfh_ws_bytes": (_sz, [_i]),
-    "d3f_fpfh": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_fpfh_passes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
-    "d3f_fpfh_host": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _vp, _vp]),
-    "d3f_pair_information_ws_bytes": (_sz, [_i, C.c_int64]),
-    "d3f_pair_information": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _sz,
-                                  _vp]),
-    "d3f_pose_graph_optimize_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_pose_graph_optimize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _d, _d, _vp, _vp, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_pose_graph_optimize_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _d, _d, _vp, _vp, _vp,
-                                      _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_pose_graph_edge_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_tsdf_bounds": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
-    "d3f_tsdf_bounds_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp]),
-    "d3f_tsdf_sparse_mark": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _vp,
-                                  _vp]),
-    "d3f_tsdf_sparse_mark_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f,
-                                       _vp]),
-    "d3f_tsdf_sparse_index_ws_bytes": (_sz, [C.c_int64]),
-    "d3f_tsdf_sparse_index": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_tsdf_sparse_index_host": (_i, [_vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
-    "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
-    "d3f_depth_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
-    "d3f_depth_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
-    "d3f_depth_odometry_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_depth_odometry_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
-    "d3f_depth_odometry_step_host": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp]),
-    "d3f_depth_odometry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                _vp]),
-    "d3f_depth_odometry_host": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "d3f_rgbd_pyramid": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "d3f_rgbd_pyramid_host": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
-    "d3f_rgbd_odometry_ws_bytes": (_sz, [_i, _i, _i]),
-    "d3f_rgbd_odometry_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _sz,
-                                    _vp]),
-    "d3f_rgbd_odometry_step_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp]),
-    "d3f_rgbd_odometry": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                               _vp, _vp, _sz, _vp]),
-    "d3f_rgbd_odometry_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp,
-                                    _vp, _vp]),
-    "d3f_sgd_guarded_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "d3f_sgd_guarded_step_lanes": (_i, [_vp, _i, _vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "d3f_adam_guarded_step": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "d3f_poison_gradient_if_status": (_i, [_vp, _vp, _vp, _vp]),
-}
-
-SIGNATURES.update(_tsdf_integrate_signatures())
-SIGNATURES.update(_tsdf_reader_signatures())
-SIGNATURES.update(_tsdf_surface_signatures())
-
-ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failure"}
-STATUS_BITS = {1: "a query has more in-radius candidates than the kernel can rank (512; fpfh: 2^18 neighbours of a point)",
-               2: "a point lies outside the addressable cell grid",
-               4: "voxel hash table full",
-               8: "a pyramid level needs more rows than its capacity (raise the capacities)",
-               16: "a point has more in-radius neighbors than the reverse (wide) table holds",
-               32: "an upsampling query has no coarse point within the guaranteed nearest bound (a coarse level lost "
-                   "voxels, or the bound passed to query_prefix is wrong)"}
+ERRORS = {DEFINES["D3F_" + name]: text for name, text in (
+    ("EINVAL", "invalid argument"), ("EWORKSPACE", "workspace too small"), ("ELAUNCH", "HIP launch failure"))}
+STATUS_BITS = {DEFINES["D3F_ST_" + name]: text for name, text in (
+    ("CAND_OVERFLOW", "a query has more in-radius candidates than the kernel can rank (512; fpfh: 2^18 neighbours of a point)"),
+    ("CELL_RANGE", "a point lies outside the addressable cell grid"),
+    ("TABLE_FULL", "voxel hash table full"),
+    ("CAPACITY", "a pyramid level needs more rows than its capacity (raise the capacities)"),
+    ("WIDE_OVERFLOW", "a point has more in-radius neighbors than the reverse (wide) table holds"),
+    ("NO_NEAREST", "an upsampling query has no coarse point within the guaranteed nearest bound (a coarse level lost voxels, "
+                   "or the bound passed to query_prefix is wrong)"))}
 
 
 def build(verbose=False, jobs=None, extra_flags=(), out=None, objdir=None):

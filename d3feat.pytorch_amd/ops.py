@@ -11,8 +11,8 @@ import torch
 
 from . import _native
 
-ORDER_REFERENCE = 0   # row order of the reference's std::unordered_map iteration (grid_subsampling.cpp:85)
-ORDER_FIRST_SEEN = 1  # cells in order of their first input point
+ORDER_REFERENCE = _native.D3F_ORDER_REFERENCE    # row order of the reference's std::unordered_map iteration (grid_subsampling.cpp:85)
+ORDER_FIRST_SEEN = _native.D3F_ORDER_FIRST_SEEN  # cells in order of their first input point
 
 
 def _stream():
@@ -2638,7 +2638,7 @@ def mutual_nn_batched(source_desc, target_desc, seg, max_src, max_tgt):
     return ra, ca, mu
 
 
-TOPK_MAX = 6144
+TOPK_MAX = _native.D3F_TOPK_MAX
 
 
 def topk_scores(scores, seg, k):
@@ -2659,10 +2659,11 @@ def topk_scores(scores, seg, k):
 # ---------------------------------------------------------------------------------------------------------------
 # rigid registration (what the reference leaves to Open3D's RANSAC on the CPU)
 # ---------------------------------------------------------------------------------------------------------------
-RANSAC_MAX_HYPOTHESES = 1 << 24
-RANSAC_MAX_COUNT = 65536
-RANSAC_MAX_REFINE = 64
-RANSAC_ST_FEW, RANSAC_ST_NO_HYPOTHESIS, RANSAC_ST_SEGMENT = 1, 2, 4
+RANSAC_MAX_HYPOTHESES = _native.D3F_RANSAC_MAX_HYPOTHESES
+RANSAC_MAX_COUNT = _native.D3F_RANSAC_MAX_COUNT
+RANSAC_MAX_REFINE = _native.D3F_RANSAC_MAX_REFINE
+RANSAC_ST_FEW, RANSAC_ST_NO_HYPOTHESIS = _native.D3F_RANSAC_ST_FEW, _native.D3F_RANSAC_ST_NO_HYPOTHESIS
+RANSAC_ST_SEGMENT = _native.D3F_RANSAC_ST_SEGMENT
 
 
 def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0,
@@ -2706,8 +2707,8 @@ def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, e
 # ---------------------------------------------------------------------------------------------------------------
 # training items from a device-resident split (datasets.ThreeDMatch.ThreeDMatchResident)
 # ---------------------------------------------------------------------------------------------------------------
-AUGMENT_MAX_JOBS = 16
-AUGMENT_MAX_NODE = 1024
+AUGMENT_MAX_JOBS = _native.D3F_AUGMENT_MAX_JOBS
+AUGMENT_MAX_NODE = _native.D3F_AUGMENT_MAX_NODE
 # one item: rows of its clouds in the packed point store, rows of its table in the packed correspondence store, the
 # target's rigid transform (R [3,3], t [3]; float64) and the 64-bit item key
 AugmentJob = collections.namedtuple('AugmentJob', 'src_off src_len tgt_off tgt_len corr_off corr_len R t key')
@@ -2894,13 +2895,15 @@ def nearest_pairs(grid_or_points, lens, pairs, transforms, radius, lanes=0):
 # ---------------------------------------------------------------------------------------------------------------
 # point-to-point ICP over a list of cloud pairs (the refinement after RANSAC; Open3D's registration_icp)
 # ---------------------------------------------------------------------------------------------------------------
-ICP_MAX_ITERS = 1024
-ICP_BLOCK_ROWS = 512
-ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE = 1, 2, 4, 8
-ICP_ST_SINGULAR = 16   # point-to-plane: singular normal equations (one plane's free slide, zero normals)
-PG_ST_ITER_CAP, PG_ST_NONFINITE, PG_ST_GRAPH, PG_ST_INDEFINITE = 1, 2, 4, 8   # pose_graph_optimize (D3F_PG_ST_*)
-PG_MAX_NODES = 128     # nodes of one graph (D3F_PG_MAX_NODES)
-PG_MAX_ITERS = 1024
+ICP_MAX_ITERS = _native.D3F_ICP_MAX_ITERS
+ICP_BLOCK_ROWS = _native.D3F_ICP_BLOCK_ROWS
+ICP_ST_FEW, ICP_ST_CELL_RANGE = _native.D3F_ICP_ST_FEW, _native.D3F_ICP_ST_CELL_RANGE
+ICP_ST_PAIR, ICP_ST_NONFINITE = _native.D3F_ICP_ST_PAIR, _native.D3F_ICP_ST_NONFINITE
+ICP_ST_SINGULAR = _native.D3F_ICP_ST_SINGULAR   # point-to-plane: singular normal equations (one plane's free slide, zero normals)
+PG_ST_ITER_CAP, PG_ST_NONFINITE = _native.D3F_PG_ST_ITER_CAP, _native.D3F_PG_ST_NONFINITE   # pose_graph_optimize
+PG_ST_GRAPH, PG_ST_INDEFINITE = _native.D3F_PG_ST_GRAPH, _native.D3F_PG_ST_INDEFINITE
+PG_MAX_NODES = _native.D3F_PG_MAX_NODES     # nodes of one graph
+PG_MAX_ITERS = _native.D3F_PG_MAX_ITERS
 
 
 def icp_rigid_bytes(rows, found=None):
@@ -3203,7 +3206,7 @@ def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, r
     return res + (trace,) if return_trace else res
 
 
-INFO_MOMENTS = 20   # n, sum x (3), sum x x^T (6), sum y (3), sum y y^T (6), sum d2
+INFO_MOMENTS = _native.D3F_INFO_MOMENTS   # n, sum x (3), sum x x^T (6), sum y (3), sum y y^T (6), sum d2
 
 
 def pair_information(grid_or_points, lens, pairs, T, max_distance, rows=None):
@@ -3380,8 +3383,8 @@ def pose_graph_optimize_host(poses, edges, T, info, uncertain, max_distance, nod
 # TSDF fusion of depth frames into dense volumes, and their zero crossings as point clouds (csrc/tsdf.hpp)
 # ---------------------------------------------------------------------------------------------------------------
 TSDF_DEPTH_MAX = 6.0          # default depth_max in metres: farther pixels are not fused
-TSDF_ST_OVERFLOW = 1          # D3F_TSDF_ST_OVERFLOW
-TSDF_MAX_VOLUMES = 65535
+TSDF_ST_OVERFLOW = _native.D3F_TSDF_ST_OVERFLOW
+TSDF_MAX_VOLUMES = _native.D3F_TSDF_MAX_VOLUMES
 
 
 def _tsdf_depth_array(depth, device_ok=False):
@@ -4236,7 +4239,7 @@ def tsdf_extract_sparse_numpy(D, w, sv, min_weight=1.0):
 # ---------------------------------------------------------------------------------------------------------------
 # triangle meshes with normals from the TSDF volumes: dual contouring of the lattice (csrc/tsdf_mesh.hpp)
 # ---------------------------------------------------------------------------------------------------------------
-TSDF_ST_FACE_OVERFLOW = 2     # D3F_TSDF_ST_FACE_OVERFLOW
+TSDF_ST_FACE_OVERFLOW = _native.D3F_TSDF_ST_FACE_OVERFLOW
 
 
 def tsdf_mesh_bytes(total_voxels, vertices, faces):
@@ -4584,7 +4587,7 @@ def tsdf_mesh_sparse_numpy(D, w, sv, min_weight=1.0, chunk=1 << 10):
 # Ray-casting TSDF volumes, dense and sparse: a volume plus a camera pose gives a depth image (csrc/tsdf_raycast.hpp has
 # the rule; csrc/tsdf_raycast.hip the kernel, for both kinds of model)
 # ---------------------------------------------------------------------------------------------------------------
-RAYCAST_MAX_SAMPLES = 65536   # D3F_RAYCAST_MAX_SAMPLES: samples of one ray at most
+RAYCAST_MAX_SAMPLES = _native.D3F_RAYCAST_MAX_SAMPLES   # samples of one ray at most
 RAYCAST_DEPTH_MIN = 0.1       # default depth_min in metres: where every ray starts
 RAYCAST_MAX_VIEWS = 65535
 
@@ -5320,14 +5323,14 @@ def tsdf_extend_numpy(sv, D, w, depth, frame_start, intrinsics, camera_to_volume
 # Depth odometry: camera poses of a depth sequence by projective point-to-plane ICP over a depth pyramid
 # (csrc/odometry.hpp has the rule; csrc/odometry.hip the kernels, of this section and the next)
 # ---------------------------------------------------------------------------------------------------------------
-ODO_ST_FEW = 1           # D3F_ODO_ST_FEW: the final association has fewer than 6 accepted pixels
-ODO_ST_PAIR = 4          # D3F_ODO_ST_PAIR: a frame index outside [0, F)
-ODO_ST_NONFINITE = 8     # D3F_ODO_ST_NONFINITE: T_init holds a non-finite value
-ODO_ST_SINGULAR = 16     # D3F_ODO_ST_SINGULAR: the last fit at level 0 was singular (e.g. a view of a single plane)
-ODO_MAX_LEVELS = 8
-ODO_MAX_ITERS = 1024
+ODO_ST_FEW = _native.D3F_ODO_ST_FEW               # the final association has fewer than 6 accepted pixels
+ODO_ST_PAIR = _native.D3F_ODO_ST_PAIR             # a frame index outside [0, F)
+ODO_ST_NONFINITE = _native.D3F_ODO_ST_NONFINITE   # T_init holds a non-finite value
+ODO_ST_SINGULAR = _native.D3F_ODO_ST_SINGULAR     # the last fit at level 0 was singular (e.g. a view of a single plane)
+ODO_MAX_LEVELS = _native.D3F_ODO_MAX_LEVELS
+ODO_MAX_ITERS = _native.D3F_ODO_MAX_ITERS
 ODO_MAX_PAIRS = 65535
-ODO_SUMS = 29            # n, the 21 upper entries of sum J J^T, sum J r (6), sum d2
+ODO_SUMS = _native.D3F_ODO_SUMS                   # n, the 21 upper entries of sum J J^T, sum J r (6), sum d2
 ODO_MIN_PIXELS = 6
 ODO_ITERATIONS = (10, 5, 4)
 ODO_MAX_DISTANCE = 0.1
@@ -5879,11 +5882,12 @@ def depth_odometry_numpy(pyr_or_depth, pairs, T_init=None, iterations=ODO_ITERAT
 # RGB-D odometry: the depth odometry with a photometric term (csrc/rgbd_odometry.hpp has the rule; the kernels and
 # the helpers that take ``photo_weight`` are the depth odometry's)
 # ---------------------------------------------------------------------------------------------------------------
-RGBD_SUMS = 31           # the 29 of the depth odometry (both kinds of rows in sum J J^T and sum J r), n_photo, sum r_I^2
+RGBD_SUMS = _native.D3F_RGBD_SUMS   # the 29 of the depth odometry (both kinds of rows in sum J J^T and sum J r), n_photo, sum r_I^2
 ODO_PHOTO_WEIGHT = 0.3   # profiles/rgbd_odometry_weight_sweep.txt: the largest of the swept weights that meets both
 #                          conditions of the sweep (the planar slide recovered, the textured room no worse than twice
 #                          the depth tracker's worst pair)
-_RGBD_KINDS = {'rgb8': 0, 'grey8': 1, 'f32': 2}      # D3F_RGBD_COLOR_*
+_RGBD_KINDS = {'rgb8': _native.D3F_RGBD_COLOR_RGB8, 'grey8': _native.D3F_RGBD_COLOR_GREY8,
+               'f32': _native.D3F_RGBD_COLOR_F32}
 
 
 class RgbdPyramid(DepthPyramid):

@@ -1,7 +1,13 @@
-"""CPU: the C-ABI library loads and exports every symbol include/d3feat_hip.h declares; the ctypes table mirrors it."""
+"""CPU: the C-ABI library loads and exports every symbol include/d3feat_hip.h declares; the ctypes binding is read
+from that header (prototypes, structs, integer defines), strictly, and agrees with what the C compiler makes of it."""
+import ast
 import ctypes
 import os
 import re
+import shutil
+import subprocess
+
+import pytest
 
 import d3feat_pytorch_amd
 from d3feat_pytorch_amd import _native
@@ -30,8 +36,8 @@ def test_ctypes_table_covers_header():
 
 
 def test_the_generated_surface_prototypes_are_the_sixteen_literal_ones():
-    """_native._tsdf_surface_signatures() builds the extract and mesh prototypes from shared pieces; this is the table
-    they replaced, entry by entry as it was written out."""
+    """The extract and mesh prototypes as they were once written out by hand, entry by entry, against what the header
+    yields."""
     C = ctypes
     _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
     literal = {
@@ -61,12 +67,164 @@ def test_the_generated_surface_prototypes_are_the_sixteen_literal_ones():
         "d3f_tsdf_sparse_mesh_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _f,
                                            C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     }
-    generated = _native._tsdf_surface_signatures()
-    assert sorted(generated) == sorted(literal)
     for name, prototype in literal.items():
-        assert generated[name] == prototype, name
         assert _native.SIGNATURES[name] == prototype, name
     assert "tsdf_extract.hip" in _native.SOURCES
+
+
+def test_prototypes_of_every_other_type_class_are_the_literal_ones():
+    """char* both ways, a void return, pointers to the three structs, int64_t / uint64_t / uint32_t / double by value and
+    as return types, void* const*: the hand-written entries of these twelve, as they stood before the table was derived."""
+    C = ctypes
+    _vp, _i, _f, _sz, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double
+    literal = {
+        "d3f_version": (C.c_char_p, []),
+        "d3f_device_arch_name": (_i, [C.c_char_p, _i]),
+        "d3f_debug_set_flags": (None, [_i]),
+        "d3f_get_tunables": (None, [C.POINTER(_native.Tunables)]),
+        "d3f_linear_grad_weight_group": (_i, [C.POINTER(_native.AtbProblem), _i, _vp, _sz, _vp]),
+        "d3f_augment_pairs": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(_native.AugmentJob), _i, _i, _d, _vp, _sz, _vp]),
+        "d3f_augment_key_host": (C.c_uint64, [C.c_uint64, _i, C.c_uint32]),
+        "d3f_ransac_rigid": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _sz, _vp]),
+        "d3f_copy_buffers": (_i, [_vp, _vp, _vp, _vp, _i, C.c_double, _vp]),
+        "d3f_zero_buffers": (_i, [_vp, _vp, _i, _vp]),
+        "d3f_depth_pyramid_pixels": (C.c_int64, [_i, _i, _i]),
+        "d3f_icp_rigid_color": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, C.c_int64, _vp, _d, _i, _d, _d,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    }
+    for name, prototype in literal.items():
+        assert _native.SIGNATURES[name] == prototype, name
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int d3f_f(const float* x, unsigned n);", ("d3f_f", "n")),                     # a parameter type outside the map
+    ("int d3f_f(const struct_t* x);", ("d3f_f", "x")),                              # ... a pointer to something unknown
+    ("short d3f_f(int n);", ("d3f_f", "return type")),                               # a return type outside the map
+    ("int d3f_a(int n)\nint d3f_b(int n);", ("d3f_a",)),                             # no ';': would hide d3f_a or d3f_b
+    ("int d3f_a(int n);\nint d3f_b(int n)\n", ("d3f_b",)),
+    ("int d3f_f(int (*callback)(int));", ("d3f_f",)),                                # not a plain parameter list
+    ("int d3f_f(int n);\nint d3f_f(int n);", ("d3f_f",)),                            # declared twice
+    ("#define D3F_CALL(x) d3f_f(x)\nint d3f_f(int n);", ("d3f_<name>(",)),           # a use no prototype accounts for
+    ("static int helper(int n);", ("helper",)),                                      # a statement that is no d3f_ prototype
+])
+def test_the_parser_raises_on_prototypes_it_cannot_take(text, names):
+    with pytest.raises(RuntimeError) as e:
+        _native.parse_prototypes(text, {})
+    for n in names:
+        assert n in str(e.value), str(e.value)
+
+
+@pytest.mark.parametrize("line", ["#define D3F_N sizeof(int)", "#define D3F_N ((float*)1)", "#define D3F_N 1.5",
+                                  "#define D3F_N D3F_LATER\n#define D3F_LATER 1", "#define D3F_N", "#define D3F_N(x) 1"])
+def test_the_parser_raises_on_a_define_that_is_no_integer(line):
+    with pytest.raises(RuntimeError) as e:
+        _native.parse_defines("#define D3F_ONE 1\n" + line)
+    assert "D3F_N" in str(e.value)
+
+
+def test_the_parser_on_synthetic_text():
+    C = ctypes
+    text = """/* int d3f_commented_out(int n); */
+    #define D3F_A 3 /* three */
+    #define D3F_B (D3F_A << 4)
+    #define D3F_C (-(D3F_B | 0x1))
+    #define D3F_SPACK_READY ((float*)(uintptr_t)1)
+    typedef struct d3f_s {
+      const float* p; /* [n] */
+      int32_t n, m[3], k;
+      double R[9], t[3];
+      uint64_t key;
+      void *a, *b;
+    } d3f_s;
+    const char* d3f_name(void);
+    void d3f_take(const d3f_s* s, void* const* ptrs /* host */, int64_t n, const uint8_t* mask, char* out);
+    """
+    assert _native.parse_defines(text) == {"D3F_A": 3, "D3F_B": 48, "D3F_C": -49}
+    fields = _native.parse_struct(text, "d3f_s")
+    assert fields == [("p", C.c_void_p), ("n", C.c_int32), ("m", C.c_int32 * 3), ("k", C.c_int32), ("R", C.c_double * 9),
+                      ("t", C.c_double * 3), ("key", C.c_uint64), ("a", C.c_void_p), ("b", C.c_void_p)]
+    S = type("S", (C.Structure,), {"_fields_": fields})
+    assert _native.parse_prototypes(text, {"d3f_s": S}) == {
+        "d3f_name": (C.c_char_p, []),
+        "d3f_take": (None, [C.POINTER(S), C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p])}
+    for bad in ("typedef struct d3f_s { long n; } d3f_s;", "typedef struct d3f_s { int32_t; } d3f_s;",
+                "typedef struct d3f_other { int32_t n; } d3f_other;"):
+        with pytest.raises(RuntimeError):
+            _native.parse_struct(bad, "d3f_s")
+
+
+def test_every_define_is_a_module_attribute():
+    """An independent, crude list of the header's defines against what _native carries; ERRORS and STATUS_BITS by name."""
+    src = open(os.path.join(REPO, "include", "d3feat_hip.h")).read()
+    names = re.findall(r"^#define\s+(D3F_\w+)", src, flags=re.M)
+    assert len(names) == len(set(names)) >= 55
+    assert sorted(set(names) - {"D3F_SPACK_READY"}) == sorted(_native.DEFINES)
+    assert not hasattr(_native, "D3F_SPACK_READY")
+    for n, v in _native.DEFINES.items():
+        assert type(v) is int and getattr(_native, n) == v
+    assert (_native.D3F_EINVAL, _native.D3F_EWORKSPACE, _native.D3F_ELAUNCH) == (-1, -2, -3)
+    assert _native.D3F_RANSAC_MAX_HYPOTHESES == 1 << 24 and _native.D3F_PG_MAX_EDGES == 1 << 20
+    assert sorted(_native.ERRORS) == [-3, -2, -1]
+    assert sorted(_native.STATUS_BITS) == [1, 2, 4, 8, 16, 32]
+    assert _native.STATUS_BITS[_native.D3F_ST_TABLE_FULL] == "voxel hash table full"
+
+
+def test_the_c_compiler_agrees_on_structs_and_defines(tmp_path):
+    """Second witness: a C program that includes the header prints sizeof, every field's offsetof and size, and every
+    integer define; the ctypes classes and _native.D3F_* must say the same."""
+    cc = [shutil.which("cc")] if shutil.which("cc") else [shutil.which("hipcc"), "-x", "c++"]
+    if not cc[0]:
+        pytest.skip("no C compiler")
+    lines, expected = [], []
+    for cname, cls in _native.STRUCTS.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        expected.append("%s %d" % (cname, ctypes.sizeof(cls)))
+        for field, ctype in cls._fields_:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (cname, field, cname, field, cname, field))
+            expected.append("%s.%s %d %d" % (cname, field, getattr(cls, field).offset, ctypes.sizeof(ctype)))
+    for name, value in _native.DEFINES.items():
+        lines.append('printf("%s %%lld\\n", (long long)(%s));' % (name, name))
+        expected.append("%s %d" % (name, value))
+    assert len(expected) == 3 + 11 + 12 + 14 + len(_native.DEFINES) and len(_native.DEFINES) >= 54   # fields per struct
+    src = tmp_path / "witness.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "d3feat_hip.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
+                   % "\n  ".join(lines))
+    exe = str(tmp_path / "witness")
+    subprocess.check_call(cc + ["-I", os.path.join(REPO, "include"), str(src), "-o", exe])
+    assert subprocess.check_output([exe]).decode().split("\n")[:-1] == expected
+
+
+STARRED_CALL_SITES = ["d3f_depth_pyramid", "d3f_depth_pyramid_host", "d3f_detection_rows_backward",
+                      "d3f_detection_rows_backward_pairs", "d3f_detection_rows_forward", "d3f_detection_rows_forward_pairs",
+                      "d3f_rgbd_pyramid", "d3f_rgbd_pyramid_host", "d3f_tsdf_sparse_mark", "d3f_tsdf_sparse_mark_host"]
+
+
+def test_every_call_site_passes_as_many_arguments_as_the_header_declares():
+    """<expr>.d3f_<name>(...) anywhere in the package: the argument count is the prototype's.  A call with a starred
+    argument cannot be counted; those are the ten listed above and no others."""
+    counted, starred, wrong = 0, [], []
+    for root, _, files in os.walk(os.path.dirname(_native.__file__)):
+        for f in sorted(files):
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(root, f)
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)
+                        and node.func.attr.startswith("d3f_")):
+                    continue
+                name = node.func.attr
+                if any(isinstance(a, ast.Starred) for a in node.args):
+                    starred.append(name)
+                    continue
+                counted += 1
+                if node.keywords or len(node.args) != len(_native.SIGNATURES[name][1]):
+                    wrong.append("%s:%d %s passes %d of %d" % (os.path.relpath(path, REPO), node.lineno, name,
+                                                              len(node.args), len(_native.SIGNATURES[name][1])))
+    assert not wrong, wrong
+    assert sorted(starred) == STARRED_CALL_SITES
+    assert counted >= 145
 
 
 def test_no_gpu_calls_needed_for_size_queries():
