@@ -103,6 +103,16 @@ __device__ __forceinline__ long sampled_row(const SampledRows& sr, int m2, int N
   if (sr.pair_len) row += batch_offset(sr.pair_len, 2 * (m / sr.M_pair) + (pos ? 1 : 0));
   return row < 0 ? 0 : (row >= N ? N - 1 : row);
 }
+// The SampledRows of an entry point's (idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len), M per pair; false is
+// D3F_EINVAL.  pair_len NULL: the global rows of ONE pair, p_offset optional.  pair_len [2 pairs]: cloud-local rows.
+static inline bool make_sampled_rows(const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M, int pairs,
+                                     const int32_t* p_offset, const int32_t* pair_len, SampledRows& sr) {
+  if (!idx_a || !idx_p || idx_stride < 1 || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH) return false;
+  if (pair_len ? p_offset != nullptr : pairs != 1) return false;
+  if ((long long)pairs * M > (1 << 24)) return false;   // 2 * rows is a grid size, and the detector's partial count
+  sr = {idx_a, idx_p, idx_stride, pairs * M, p_offset, pair_len, M};
+  return true;
+}
 
 // squared distance with the reference's float32 evaluation order and NO fused multiply-add:
 // d2 = dx*dx; d2 += dy*dy; d2 += dz*dz   (nanoflann.hpp:433-441).  NOTE: on AMD the __f*_rn intrinsics are plain

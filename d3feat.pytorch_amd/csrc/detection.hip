@@ -695,19 +695,22 @@ size_t d3f_detection_rows_ws_bytes(int rows) {
 }
 
 static bool det_rows_args_ok(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                             const int32_t* len, int B, int group, const d3f::SampledRows& sr) {
-  if (!feat || !idx || !feat_max || !sr.idx_a || !sr.idx_p || N < 1 || sr.M < 1 || sr.idx_stride < 1 || sr.M_pair < 1)
-    return false;
+                             const int32_t* len, int B, int group, int pairs, const int32_t* pair_len) {
+  if (!feat || !idx || !feat_max || N < 1) return false;
   if (!d3f_detection_rows_supported(C, H)) return false;
   if (len && (B < 1 || B > D3F_MAX_BATCH || group < 0)) return false;   // group 0: one normaliser for the whole batch
-  if (sr.M > (1 << 24)) return false;
+  if (len && pair_len && B != 2 * pairs) return false;                  // the groups are made of the pairs' clouds
   return true;
 }
 
-static int det_rows_forward_impl(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                 int training, const int32_t* width, const int32_t* len, int B, int group,
-                                 const d3f::SampledRows& sr, float* sa, float* sp, float* aux, void* stream_) {
-  if (!det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, sr) || !sa || !sp || (aux && !training))
+int d3f_detection_rows_forward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                               int training, const int32_t* width, const int32_t* len, int B, int group,
+                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M, int pairs,
+                               const int32_t* p_offset, const int32_t* pair_len, float* sa, float* sp, float* aux,
+                               void* stream_) {
+  d3f::SampledRows sr;
+  if (!d3f::make_sampled_rows(idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len, sr) ||
+      !det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, pairs, pair_len) || !sa || !sp || (aux && !training))
     return D3F_EINVAL;
   const d3f::RowGroups rg = {group > 0 ? len : nullptr, B, group};
   hipStream_t stream = (hipStream_t)stream_;
@@ -719,28 +722,15 @@ static int det_rows_forward_impl(const float* feat, int N, int C, const int32_t*
   return D3F_OK;
 }
 
-int d3f_detection_rows_forward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                               int training, const int32_t* width, const int32_t* len, int B, int group,
-                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M,
-                               const int32_t* p_offset, float* sa, float* sp, float* aux, void* stream) {
-  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
-  return det_rows_forward_impl(feat, N, C, idx, H, feat_max, training, width, len, B, group, sr, sa, sp, aux, stream);
-}
-
-int d3f_detection_rows_forward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                     int training, const int32_t* width, const int32_t* len, int B, int group,
-                                     const int64_t* corr, int M, int pairs, float* sa, float* sp, float* aux,
-                                     void* stream) {
-  if (!corr || !len || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH || B != 2 * pairs) return D3F_EINVAL;
-  const d3f::SampledRows sr = {corr, corr + 1, 2, pairs * M, nullptr, len, M};
-  return det_rows_forward_impl(feat, N, C, idx, H, feat_max, training, width, len, B, group, sr, sa, sp, aux, stream);
-}
-
-static int det_rows_backward_impl(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                  const int32_t* len, int B, int group, const d3f::SampledRows& sr, const float* aux,
-                                  const float* g_sa, const float* g_sp, float* grad_x, void* ws, size_t ws_bytes,
-                                  void* stream_) {
-  if (!det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, sr) || !aux || !grad_x || !ws) return D3F_EINVAL;
+int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
+                                int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
+                                size_t ws_bytes, void* stream_) {
+  d3f::SampledRows sr;
+  if (!d3f::make_sampled_rows(idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len, sr) ||
+      !det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, pairs, pair_len) || !aux || !grad_x || !ws)
+    return D3F_EINVAL;
   const int rows = 2 * sr.M;
   if (ws_bytes < d3f_detection_rows_ws_bytes(rows)) return D3F_EWORKSPACE;
   const d3f::RowGroups rg = {group > 0 ? len : nullptr, B, group};
@@ -761,25 +751,6 @@ static int det_rows_backward_impl(const float* feat, int N, int C, const int32_t
                                                              tie_list, grad_x);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
-}
-
-int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
-                                int idx_stride, int M, const int32_t* p_offset, const float* aux, const float* g_sa,
-                                const float* g_sp, float* grad_x, void* ws, size_t ws_bytes, void* stream) {
-  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
-  return det_rows_backward_impl(feat, N, C, idx, H, feat_max, len, B, group, sr, aux, g_sa, g_sp, grad_x, ws, ws_bytes,
-                                stream);
-}
-
-int d3f_detection_rows_backward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                      const int32_t* len, int B, int group, const int64_t* corr, int M, int pairs,
-                                      const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
-                                      size_t ws_bytes, void* stream) {
-  if (!corr || !len || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH || B != 2 * pairs) return D3F_EINVAL;
-  const d3f::SampledRows sr = {corr, corr + 1, 2, pairs * M, nullptr, len, M};
-  return det_rows_backward_impl(feat, N, C, idx, H, feat_max, len, B, group, sr, aux, g_sa, g_sp, grad_x, ws, ws_bytes,
-                                stream);
 }
 
 }  // extern "C"

@@ -2,9 +2,11 @@
 //
 // Replaces reference utils/loss.py: cdist 'euclidean' (:8-44), CircleLoss.forward (:111-141) and
 // DetLoss.forward (:149-158) -- ~40 small PyTorch launches and two host syncs per step in the reference.
-// M (sampled correspondences) is 128 in training / 64 in validation (config.py:78), so the whole problem
-// (M*M = 16k distances) lives in ONE workgroup: distances go to the caller's `dists` buffer (an output of the
-// reference API as well), row/column statistics to LDS, and a single launch produces both losses + metrics.
+// M (sampled correspondences) is 128 in training / 64 in validation (config.py:78).  At M <= 128, C <= 64 the M x M
+// problem of every stacked pair is cut into strips of lines, one workgroup each, and a second tiny launch sums the
+// scalars (the tiled kernels below); larger problems fall back to ONE workgroup of 1024 threads working on the global
+// buffers, a single pair at a time.  Distances go to the caller's `dists` buffer (an output of the reference API as
+// well) in either form.
 //
 // Semantics reproduced literally (including the reference's quirk that masked entries contribute exp(-0) = 1 to
 // the log-sum-exp because their detached weight is clamped to 0):
@@ -90,73 +92,45 @@ __device__ float block_sum(float v, float* sh) {
   return t;
 }
 
-// LDS plan of the cached variants (M <= 128, C <= 64; everything the workgroup touches more than once):
-//   fwd: region0 = descriptors a, p as [M][C+1] each (later reused for the mask bytes), region1 = D as [M][M+1]
-//   bwd: region0 = a, p as [M][C+1] each, region1 = G as [M][M+1]
-// Without CACHE (larger problems) the same code runs on the global buffers.
-__host__ __device__ inline size_t cached_lds_bytes(int M, int C) {
-  return sizeof(float) * ((size_t)2 * M * (C + 1) + (size_t)M * (M + 1));
-}
+// the tiled kernels' domain; beyond it the one-workgroup kernels run on the global buffers
 static bool cache_ok(int M, int C) { return M <= 128 && C <= 64; }
 
 // stats layout (floats): [0,M) lse_pr  [M,2M) lse_nr  [2M,3M) lse_pc  [3M,4M) lse_nc  [4M,5M) cn  [5M,6M) cnarg(int)
-template <bool CACHE>
 __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(
     const float* __restrict__ a, const float* __restrict__ p, int M, int C, const uint8_t* __restrict__ negm,
     const float* __restrict__ sa, const float* __restrict__ sp, LossParams P, float* __restrict__ D,
     float* __restrict__ fp_out, float* __restrict__ avgneg_out, float* __restrict__ scalars,
     float* __restrict__ stats) {
   __shared__ float sh[16];
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
-  const int CS = C + 1, DS = M + 1;
-  float* al = lds;
-  float* pl = lds + (size_t)M * CS;
-  float* Dl = lds + (size_t)2 * M * CS;
-  uint8_t* nl = (uint8_t*)lds;  // overlays al/pl once the distances exist
-  if (CACHE) {
-    for (int t = tid; t < M * C; t += blockDim.x) {
-      al[(t / C) * CS + t % C] = a[t];
-      pl[(t / C) * CS + t % C] = p[t];
-    }
-    __syncthreads();
-  }
   for (int t = tid; t < M * M; t += blockDim.x) {
     const int i = t / M, j = t % M;
     float acc = 0.0f;
     for (int c = 0; c < C; ++c) {
-      const float df = CACHE ? al[i * CS + c] - pl[j * CS + c] : a[(size_t)i * C + c] - p[(size_t)j * C + c];
+      const float df = a[(size_t)i * C + c] - p[(size_t)j * C + c];
       acc += df * df;
     }
-    const float d = sqrtf(acc + 1e-12f);
-    D[t] = d;
-    if (CACHE) Dl[i * DS + j] = d;
+    D[t] = sqrtf(acc + 1e-12f);
   }
   __threadfence_block();
   __syncthreads();
-  if (CACHE) {
-    for (int t = tid; t < M * M; t += blockDim.x) nl[t] = negm[t];
-    __syncthreads();
-  }
-  const float* Dr = CACHE ? Dl : D;
-  const long ld = CACHE ? DS : M;
-  const uint8_t* nr = CACHE ? nl : negm;
+  const long ld = M;   // row stride of D
   for (int i = wave; i < M; i += nw) {
     float lp, ln, sd, cm; int ca;
-    line_stats(Dr, (long)i * ld, 1, nr, (long)i * M, 1, M, i, P, lp, ln, sd, cm, ca);
+    line_stats(D, (long)i * ld, 1, negm, (long)i * M, 1, M, i, P, lp, ln, sd, cm, ca);
     if (lane == 0) {
       stats[i] = lp;
       stats[M + i] = ln;
       stats[4 * M + i] = cm;
       ((int*)stats)[5 * M + i] = ca;
-      const float fp = Dr[(long)i * ld + i];  // max_j D*I = D_ii (D > 0)
+      const float fp = D[(long)i * ld + i];  // max_j D*I = D_ii (D > 0)
       fp_out[i] = fp;
       avgneg_out[i] = (sd - fp) / (float)(M - 1);
     }
   }
   for (int j = wave; j < M; j += nw) {
     float lp, ln, sd, cm; int ca;
-    line_stats(Dr, (long)j, ld, nr, (long)j, M, M, j, P, lp, ln, sd, cm, ca);
+    line_stats(D, (long)j, ld, negm, (long)j, M, M, j, P, lp, ln, sd, cm, ca);
     if (lane == 0) {
       stats[2 * M + j] = lp;
       stats[3 * M + j] = ln;
@@ -188,26 +162,16 @@ __global__ __launch_bounds__(kThreads) void loss_fwd_kernel(
   }
 }
 
-template <bool CACHE>
+// G [M,M] = dL/dD / D: the caller's workspace
 __global__ __launch_bounds__(kThreads) void loss_bwd_kernel(
     const float* __restrict__ a, const float* __restrict__ p, int M, int C, const uint8_t* __restrict__ negm,
     const float* __restrict__ sa, const float* __restrict__ sp, LossParams P, const float* __restrict__ D,
     const float* __restrict__ stats, const float* __restrict__ g_desc, const float* __restrict__ g_det,
     float* __restrict__ G, float* __restrict__ ga, float* __restrict__ gp, float* __restrict__ gsa,
     float* __restrict__ gsp) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
-  const int CS = C + 1, DS = M + 1;
-  float* al = lds;
-  float* pl = lds + (size_t)M * CS;
-  float* Gl = lds + (size_t)2 * M * CS;
   const float gd = g_desc ? *g_desc : 0.0f, gt = g_det ? *g_det : 0.0f;
   const float invM = 1.0f / (float)M;
-  if (CACHE)
-    for (int t = tid; t < M * C; t += blockDim.x) {
-      al[(t / C) * CS + t % C] = a[t];
-      pl[(t / C) * CS + t % C] = p[t];
-    }
   for (int t = tid; t < M * M; t += blockDim.x) {
     const int i = t / M, j = t % M;
     const float d = D[t];
@@ -220,33 +184,22 @@ __global__ __launch_bounds__(kThreads) void loss_bwd_kernel(
     const float w = gt * invM * (sa[i] + sp[i]);
     if (j == i) g += w;
     if (j == ((const int*)stats)[5 * M + i]) g -= w;
-    if (CACHE) Gl[i * DS + j] = g / d;
-    else G[t] = g / d;
+    G[t] = g / d;
   }
   __threadfence_block();
   __syncthreads();
   for (int t = tid; t < M * C; t += blockDim.x) {
     const int i = t / C, c = t % C;
     float acc = 0.0f;
-    if (CACHE) {
-      const float ai = al[i * CS + c];
-      for (int j = 0; j < M; ++j) acc += Gl[i * DS + j] * (ai - pl[j * CS + c]);
-    } else {
-      const float ai = a[t];
-      for (int j = 0; j < M; ++j) acc += G[(size_t)i * M + j] * (ai - p[(size_t)j * C + c]);
-    }
+    const float ai = a[t];
+    for (int j = 0; j < M; ++j) acc += G[(size_t)i * M + j] * (ai - p[(size_t)j * C + c]);
     ga[t] = acc;
   }
   for (int t = tid; t < M * C; t += blockDim.x) {
     const int j = t / C, c = t % C;
     float acc = 0.0f;
-    if (CACHE) {
-      const float pj = pl[j * CS + c];
-      for (int i = 0; i < M; ++i) acc += Gl[i * DS + j] * (pj - al[i * CS + c]);
-    } else {
-      const float pj = p[t];
-      for (int i = 0; i < M; ++i) acc += G[(size_t)i * M + j] * (pj - a[(size_t)i * C + c]);
-    }
+    const float pj = p[t];
+    for (int i = 0; i < M; ++i) acc += G[(size_t)i * M + j] * (pj - a[(size_t)i * C + c]);
     gp[t] = acc;
   }
   for (int i = tid; i < M; i += blockDim.x) {
@@ -288,7 +241,7 @@ __global__ __launch_bounds__(256) void loss_fwd_tile_kernel(const float* __restr
   uint8_t* mr = (uint8_t*)(Dc + (size_t)M * KS);   // [L][M]
   uint8_t* mc = mr + (size_t)L * M;                // [M][L]
   const int l0 = blockIdx.x * L, nl = min(L, M - l0);
-  {  // blockIdx.y = fragment pair of a stacked batch (d3f_circle_det_loss_forward_pairs): its own M x M problem
+  {  // blockIdx.y = fragment pair of a stacked batch: its own M x M problem
     const size_t pr = blockIdx.y;
     a += pr * M * C; p += pr * M * C; negm += pr * M * M; D += pr * M * M;
     fp_out += pr * M; avgneg_out += pr * M; stats += pr * 6 * M;
@@ -740,13 +693,16 @@ extern "C" {
 size_t d3f_circle_det_loss_stats_floats(int M) { return 6 * (size_t)(M > 0 ? M : 1); }
 size_t d3f_circle_det_loss_ws_bytes(int M) { return sizeof(float) * (size_t)(M > 0 ? M : 1) * (size_t)(M > 0 ? M : 1); }
 
-static int loss_forward_impl(const float* anchor, const float* positive, int M, int C, int pairs, const uint8_t* neg_mask,
-                             const float* anc_score, const float* pos_score, LossParams P, float w_desc, float w_det,
-                             float* dists, float* furthest_positive, float* average_negative, float* out_scalars,
-                             float* out_total, float* stats, void* stream) {
+// The one-workgroup kernels (!cache_ok) serve one pair and know neither weights nor a total.
+int d3f_circle_det_loss_forward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                const uint8_t* neg_mask, const float* anc_score, const float* pos_score, float log_scale,
+                                float safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                float* dists, float* furthest_positive, float* average_negative, float* out_scalars,
+                                float* out_total, float* stats, void* stream) {
   if (!anchor || !positive || !neg_mask || !anc_score || !pos_score || !dists || !furthest_positive ||
       !average_negative || !out_scalars || !stats || M < 2 || M > kMaxM || C < 1 || pairs < 1 || pairs > 32)
     return D3F_EINVAL;
+  const LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
   if (cache_ok(M, C)) {
     loss_fwd_tile_kernel<<<dim3(d3f::cdiv(M, kLossStrip), pairs), 256, tiled_lds_bytes(M, C), (hipStream_t)stream>>>(
         anchor, positive, M, C, neg_mask, P, dists, furthest_positive, average_negative, stats);
@@ -754,82 +710,45 @@ static int loss_forward_impl(const float* anchor, const float* positive, int M, 
                                                              average_negative, stats, out_scalars, pairs, w_desc, w_det,
                                                              out_total);
   } else {
-    if (pairs != 1 || out_total) return D3F_EINVAL;   // the one-workgroup form (M > 128) serves a single pair
-    loss_fwd_kernel<false><<<1, kThreads, 0, (hipStream_t)stream>>>(anchor, positive, M, C, neg_mask, anc_score,
-                                                                     pos_score, P, dists, furthest_positive,
-                                                                     average_negative, out_scalars, stats);
+    if (pairs != 1 || out_total || w_desc != 1.0f || w_det != 1.0f) return D3F_EINVAL;
+    loss_fwd_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(anchor, positive, M, C, neg_mask, anc_score, pos_score, P,
+                                                             dists, furthest_positive, average_negative, out_scalars,
+                                                             stats);
   }
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
 
-int d3f_circle_det_loss_forward(const float* anchor, const float* positive, int M, int C, const uint8_t* neg_mask,
-                                const float* anc_score, const float* pos_score, float log_scale, float safe_radius,
-                                float pos_margin, float neg_margin, float* dists, float* furthest_positive,
-                                float* average_negative, float* out_scalars, float* stats, void* stream) {
-  LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
-  return loss_forward_impl(anchor, positive, M, C, 1, neg_mask, anc_score, pos_score, P, 1.0f, 1.0f, dists,
-                           furthest_positive, average_negative, out_scalars, nullptr, stats, stream);
-}
-
-int d3f_circle_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                      const uint8_t* neg_mask, const float* anc_score, const float* pos_score,
-                                      float log_scale, float safe_radius, float pos_margin, float neg_margin,
-                                      float w_desc, float w_det, float* dists, float* furthest_positive,
-                                      float* average_negative, float* out_scalars, float* out_total, float* stats,
-                                      void* stream) {
-  if (!out_total || !cache_ok(M, C)) return D3F_EINVAL;
-  LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
-  return loss_forward_impl(anchor, positive, M, C, pairs, neg_mask, anc_score, pos_score, P, w_desc, w_det, dists,
-                           furthest_positive, average_negative, out_scalars, out_total, stats, stream);
-}
-
-int d3f_circle_det_loss_backward(const float* anchor, const float* positive, int M, int C, const uint8_t* neg_mask,
-                                 const float* anc_score, const float* pos_score, float log_scale, float safe_radius,
-                                 float pos_margin, float neg_margin, const float* dists, const float* stats,
-                                 const float* grad_desc, const float* grad_det, float* grad_anchor,
-                                 float* grad_positive, float* grad_anc_score, float* grad_pos_score, void* ws,
-                                 size_t ws_bytes, void* stream) {
+int d3f_circle_det_loss_backward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                 const uint8_t* neg_mask, const float* anc_score, const float* pos_score, float log_scale,
+                                 float safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                 const float* dists, const float* stats, const float* grad_desc, const float* grad_det,
+                                 float* grad_anchor, float* grad_positive, float* grad_anc_score, float* grad_pos_score,
+                                 void* ws, size_t ws_bytes, void* stream) {
   if (!anchor || !positive || !neg_mask || !anc_score || !pos_score || !dists || !stats || !grad_anchor ||
-      !grad_positive || !ws || M < 2 || M > kMaxM || C < 1)
+      !grad_positive || M < 2 || M > kMaxM || C < 1 || pairs < 1 || pairs > 32)
     return D3F_EINVAL;
-  if (ws_bytes < d3f_circle_det_loss_ws_bytes(M)) return D3F_EWORKSPACE;
-  LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
-  if (cache_ok(M, C))
-    loss_bwd_tile_kernel<<<d3f::cdiv(M, kLossStrip), 256, tiled_lds_bytes(M, C), (hipStream_t)stream>>>(
+  const LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
+  if (cache_ok(M, C)) {
+    loss_bwd_tile_kernel<<<dim3(d3f::cdiv(M, kLossStrip), pairs), 256, tiled_lds_bytes(M, C), (hipStream_t)stream>>>(
         anchor, positive, M, C, neg_mask, anc_score, pos_score, P, dists, stats, grad_desc, grad_det, grad_anchor,
-        grad_positive, grad_anc_score, grad_pos_score, 1.0f, 1.0f);
-  else
-    loss_bwd_kernel<false><<<1, kThreads, 0, (hipStream_t)stream>>>(anchor, positive, M, C, neg_mask, anc_score,
-                                                                     pos_score, P, dists, stats, grad_desc, grad_det,
-                                                                     (float*)ws, grad_anchor, grad_positive,
-                                                                     grad_anc_score, grad_pos_score);
+        grad_positive, grad_anc_score, grad_pos_score, w_desc, w_det);
+  } else {
+    if (pairs != 1 || w_desc != 1.0f || w_det != 1.0f || !ws) return D3F_EINVAL;
+    if (ws_bytes < d3f_circle_det_loss_ws_bytes(M)) return D3F_EWORKSPACE;
+    loss_bwd_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(anchor, positive, M, C, neg_mask, anc_score, pos_score, P,
+                                                             dists, stats, grad_desc, grad_det, (float*)ws, grad_anchor,
+                                                             grad_positive, grad_anc_score, grad_pos_score);
+  }
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
 
-int d3f_circle_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                       const uint8_t* neg_mask, const float* anc_score, const float* pos_score,
-                                       float log_scale, float safe_radius, float pos_margin, float neg_margin,
-                                       float w_desc, float w_det, const float* dists, const float* stats,
-                                       const float* grad_total, float* grad_anchor, float* grad_positive,
-                                       float* grad_anc_score, float* grad_pos_score, void* stream) {
-  if (!anchor || !positive || !neg_mask || !anc_score || !pos_score || !dists || !stats || !grad_total || !grad_anchor ||
-      !grad_positive || M < 2 || C < 1 || pairs < 1 || pairs > 32 || !cache_ok(M, C))
-    return D3F_EINVAL;
-  LossParams P = {log_scale, safe_radius, pos_margin, neg_margin};
-  loss_bwd_tile_kernel<<<dim3(d3f::cdiv(M, kLossStrip), pairs), 256, tiled_lds_bytes(M, C), (hipStream_t)stream>>>(
-      anchor, positive, M, C, neg_mask, anc_score, pos_score, P, dists, stats, grad_total, grad_total, grad_anchor,
-      grad_positive, grad_anc_score, grad_pos_score, w_desc, w_det);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
-}
-
-static int contrastive_forward_impl(const float* anchor, const float* positive, int M, int C, int pairs,
-                                    const double* dist_keypts, const float* anc_score, const float* pos_score,
-                                    double safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
-                                    float* dists, float* furthest_positive, float* average_negative, float* out_scalars,
-                                    float* out_total, float* stats, void* stream) {
+int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                     const double* dist_keypts, const float* anc_score, const float* pos_score,
+                                     double safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                     float* dists, float* furthest_positive, float* average_negative,
+                                     float* out_scalars, float* out_total, float* stats, void* stream) {
   if (!anchor || !positive || !dist_keypts || !anc_score || !pos_score || !dists || !furthest_positive ||
       !average_negative || !out_scalars || !stats || M < 2 || M > kMaxM || C < 1 || C > 256 || pairs < 1 || pairs > 32)
     return D3F_EINVAL;
@@ -843,33 +762,11 @@ static int contrastive_forward_impl(const float* anchor, const float* positive, 
   return D3F_OK;
 }
 
-int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C,
-                                     const double* dist_keypts, const float* anc_score, const float* pos_score,
-                                     double safe_radius, float pos_margin, float neg_margin, float* dists,
-                                     float* furthest_positive, float* average_negative, float* out_scalars,
-                                     float* stats, void* stream) {
-  return contrastive_forward_impl(anchor, positive, M, C, 1, dist_keypts, anc_score, pos_score, safe_radius, pos_margin,
-                                  neg_margin, 1.0f, 1.0f, dists, furthest_positive, average_negative, out_scalars,
-                                  nullptr, stats, stream);
-}
-
-int d3f_contrastive_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                           const double* dist_keypts, const float* anc_score, const float* pos_score,
-                                           double safe_radius, float pos_margin, float neg_margin, float w_desc,
-                                           float w_det, float* dists, float* furthest_positive,
-                                           float* average_negative, float* out_scalars, float* out_total, float* stats,
-                                           void* stream) {
-  if (!out_total) return D3F_EINVAL;
-  return contrastive_forward_impl(anchor, positive, M, C, pairs, dist_keypts, anc_score, pos_score, safe_radius,
-                                  pos_margin, neg_margin, w_desc, w_det, dists, furthest_positive, average_negative,
-                                  out_scalars, out_total, stats, stream);
-}
-
-static int contrastive_backward_impl(const float* anchor, const float* positive, int M, int C, int pairs,
-                                     const float* anc_score, const float* pos_score, float pos_margin, float neg_margin,
-                                     const float* stats, const float* grad_desc, const float* grad_det, float w_desc,
-                                     float w_det, float* grad_anchor, float* grad_positive, float* grad_anc_score,
-                                     float* grad_pos_score, void* stream) {
+int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                      const float* anc_score, const float* pos_score, float pos_margin, float neg_margin,
+                                      float w_desc, float w_det, const float* stats, const float* grad_desc,
+                                      const float* grad_det, float* grad_anchor, float* grad_positive,
+                                      float* grad_anc_score, float* grad_pos_score, void* stream) {
   if (!anchor || !positive || !anc_score || !pos_score || !stats || !grad_anchor || !grad_positive || M < 2 ||
       M > kMaxM || C < 1 || C > 256 || pairs < 1 || pairs > 32)
     return D3F_EINVAL;
@@ -880,41 +777,19 @@ static int contrastive_backward_impl(const float* anchor, const float* positive,
   return D3F_OK;
 }
 
-int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, const float* anc_score,
-                                      const float* pos_score, float pos_margin, float neg_margin, const float* stats,
-                                      const float* grad_desc, const float* grad_det, float* grad_anchor,
-                                      float* grad_positive, float* grad_anc_score, float* grad_pos_score,
-                                      void* stream) {
-  return contrastive_backward_impl(anchor, positive, M, C, 1, anc_score, pos_score, pos_margin, neg_margin, stats,
-                                   grad_desc, grad_det, 1.0f, 1.0f, grad_anchor, grad_positive, grad_anc_score,
-                                   grad_pos_score, stream);
-}
-
-int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                            const float* anc_score, const float* pos_score, float pos_margin,
-                                            float neg_margin, float w_desc, float w_det, const float* stats,
-                                            const float* grad_total, float* grad_anchor, float* grad_positive,
-                                            float* grad_anc_score, float* grad_pos_score, void* stream) {
-  if (!grad_total) return D3F_EINVAL;
-  return contrastive_backward_impl(anchor, positive, M, C, pairs, anc_score, pos_score, pos_margin, neg_margin, stats,
-                                   grad_total, grad_total, w_desc, w_det, grad_anchor, grad_positive, grad_anc_score,
-                                   grad_pos_score, stream);
-}
-
 /* Sampled-correspondence front end of the loss -- replaces F.normalize over all N descriptors
- * (models/architectures.py:318) followed by the four index selections of trainer.py:91-94.
- * idx_a / idx_p: int64 row indices, element m at idx[m * idx_stride] (idx_stride = 2: the two columns of the [M,2]
- * correspondence table read in place); idx_p is offset by *p_offset, a device int32 = points of the first cloud, or
- * NULL.  out_a/out_p [M,C] normalised descriptors, sa/sp [M] scores. */
+ * (models/architectures.py:318) followed by the four index selections of trainer.py:91-94.  The rows are resolved by
+ * d3f::make_sampled_rows (common.hpp); out_a/out_p [pairs*M,C] normalised descriptors, sa/sp [pairs*M] scores. */
 int d3f_select_normalize_forward(const float* x, const float* scores, int N, int C, const int64_t* idx_a,
-                                 const int64_t* idx_p, int idx_stride, int M, const int32_t* p_offset, float* out_a,
-                                 float* out_p, float* sa, float* sp, void* stream) {
-  if (!x || !idx_a || !idx_p || !out_a || !out_p || (scores && (!sa || !sp)) || N < 1 || C < 1 || M < 1 ||
-      idx_stride < 1)
+                                 const int64_t* idx_p, int idx_stride, int M, int pairs, const int32_t* p_offset,
+                                 const int32_t* pair_len, float* out_a, float* out_p, float* sa, float* sp,
+                                 void* stream) {
+  d3f::SampledRows sr;
+  if (!d3f::make_sampled_rows(idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len, sr) || !x || !out_a || !out_p ||
+      (scores && (!sa || !sp)) || N < 1 || C < 1)
     return D3F_EINVAL;
-  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
-  select_normalize_fwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, sr, out_a, out_p,
-                                                                                      sa, sp);
+  select_normalize_fwd_kernel<<<d3f::cdiv(2 * sr.M, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, sr, out_a,
+                                                                                         out_p, sa, sp);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
@@ -923,50 +798,17 @@ int d3f_select_normalize_forward(const float* x, const float* scores, int N, int
  * single fill); g_* may be NULL for outputs that received no gradient.  grad_scores NULL: only grad_x [N,C] is cleared
  * and written (the detector's rows form adds its own part to it, d3f_detection_rows_backward). */
 int d3f_select_normalize_backward(const float* x, int N, int C, const int64_t* idx_a, const int64_t* idx_p,
-                                  int idx_stride, int M, const int32_t* p_offset, const float* g_a, const float* g_p,
-                                  const float* g_sa, const float* g_sp, float* grad_x, float* grad_scores,
-                                  void* stream) {
-  if (!x || !idx_a || !idx_p || !grad_x || N < 1 || C < 1 || M < 1 || idx_stride < 1 ||
-      (grad_scores && grad_scores != grad_x + (size_t)N * C))
+                                  int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                  const float* g_a, const float* g_p, const float* g_sa, const float* g_sp,
+                                  float* grad_x, float* grad_scores, void* stream) {
+  d3f::SampledRows sr;
+  if (!d3f::make_sampled_rows(idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len, sr) || !x || !grad_x || N < 1 ||
+      C < 1 || (grad_scores && grad_scores != grad_x + (size_t)N * C))
     return D3F_EINVAL;
   if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + (grad_scores ? 1 : 0)), (hipStream_t)stream) != hipSuccess)
     return D3F_ELAUNCH;
-  const d3f::SampledRows sr = {idx_a, idx_p, idx_stride, M, p_offset, nullptr, 1};
-  select_normalize_bwd_kernel<<<d3f::cdiv(2 * M, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, sr, g_a, g_p, g_sa, g_sp,
-                                                                                      grad_x, grad_scores);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
-}
-
-/* The same for `pairs` fragment pairs stacked into one batch (clouds 2p, 2p+1 of the stack = pair p; len [2 pairs] the
- * level-0 stack lengths on the device): corr [pairs*M, 2] int64 holds every pair's own table (cloud-local rows, as the
- * dataset yields them, trainer.py:91-94), outputs are [pairs*M, ...]. */
-int d3f_select_normalize_forward_pairs(const float* x, const float* scores, int N, int C, const int64_t* corr, int M,
-                                       int pairs, const int32_t* len, float* out_a, float* out_p, float* sa, float* sp,
-                                       void* stream) {
-  if (!x || !corr || !len || !out_a || !out_p || (scores && (!sa || !sp)) || N < 1 || C < 1 || M < 1 || pairs < 1 ||
-      2 * pairs > D3F_MAX_BATCH)
-    return D3F_EINVAL;
-  const int T = pairs * M;
-  const d3f::SampledRows sr = {corr, corr + 1, 2, T, nullptr, len, M};
-  select_normalize_fwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, scores, N, C, sr, out_a, out_p,
-                                                                                      sa, sp);
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
-}
-
-int d3f_select_normalize_backward_pairs(const float* x, int N, int C, const int64_t* corr, int M, int pairs,
-                                        const int32_t* len, const float* g_a, const float* g_p, const float* g_sa,
-                                        const float* g_sp, float* grad_x, float* grad_scores, void* stream) {
-  if (!x || !corr || !len || !grad_x || N < 1 || C < 1 || M < 1 || pairs < 1 || 2 * pairs > D3F_MAX_BATCH ||
-      (grad_scores && grad_scores != grad_x + (size_t)N * C))
-    return D3F_EINVAL;
-  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)N * (C + (grad_scores ? 1 : 0)), (hipStream_t)stream) != hipSuccess)
-    return D3F_ELAUNCH;
-  const int T = pairs * M;
-  const d3f::SampledRows sr = {corr, corr + 1, 2, T, nullptr, len, M};
-  select_normalize_bwd_kernel<<<d3f::cdiv(2 * T, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, sr, g_a, g_p, g_sa, g_sp,
-                                                                                      grad_x, grad_scores);
+  select_normalize_bwd_kernel<<<d3f::cdiv(2 * sr.M, 4), 256, 0, (hipStream_t)stream>>>(x, N, C, sr, g_a, g_p, g_sa,
+                                                                                         g_sp, grad_x, grad_scores);
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }

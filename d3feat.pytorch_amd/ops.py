@@ -2068,53 +2068,47 @@ class DetectorRows(object):
 # ---------------------------------------------------------------------------------------------------------------
 # circle + detector loss (utils/loss.py:8-44,111-141,149-158)
 # ---------------------------------------------------------------------------------------------------------------
-def _circle_fwd(oa, op, sa, sp, neg_mask, P, M, params, weights):
-    """Forward launches on selected rows oa/op [P*M,C]: (scalars, total or None, dists, fp, an, stats).  ``weights``
-    None: the single-pair kernel (scalars [6], dists [M,M]; scalars[5] = desc + det); otherwise P stacked pairs in two
-    launches (strips of all pairs, finalize), scalars [P,6], dists [P,M,M], total = sum_p (w_desc desc_p + w_det det_p)."""
-    L = _native.lib()
-    C, dev = int(oa.shape[1]), oa.device
+def _loss_outputs(oa, P, M, with_total):
+    """(scalars [P,6], total or None, dists [P,M,M], fp [P*M], an [P*M], stats) for either loss's forward entry."""
+    dev = oa.device
+    return (torch.empty((P, 6), dtype=torch.float32, device=dev),
+            torch.empty((), dtype=torch.float32, device=dev) if with_total else None,
+            torch.empty((P, M, M), dtype=torch.float32, device=dev),
+            torch.empty(P * M, dtype=torch.float32, device=dev), torch.empty(P * M, dtype=torch.float32, device=dev),
+            torch.empty(P * _native.lib().d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev))
+
+
+def _circle_tiled(M, C):
+    """The strips route of d3f_circle_det_loss_*; beyond it one workgroup serves one pair, without weights or total."""
+    return M <= 128 and C <= 64
+
+
+def _circle_fwd(oa, op, sa, sp, neg_mask, P, M, params, weights=(1.0, 1.0), with_total=False):
+    """Forward launches on selected rows oa/op [P*M,C]: (scalars [P,6], total, dists [P,M,M], fp, an, stats) with
+    total = sum_p (w_desc desc_p + w_det det_p), or None."""
+    C = int(oa.shape[1])
     s, sr, pm, nm = params
-    lead = () if weights is None else (P,)
-    dists = torch.empty(lead + (M, M), dtype=torch.float32, device=dev)
-    fp = torch.empty(P * M, dtype=torch.float32, device=dev)
-    an = torch.empty(P * M, dtype=torch.float32, device=dev)
-    scalars = torch.empty(lead + (6,), dtype=torch.float32, device=dev)
-    stats = torch.empty(P * L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
-    if weights is None:
-        total = None
-        _native.check(L.d3f_circle_det_loss_forward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
-                                                    _p(dists), _p(fp), _p(an), _p(scalars), _p(stats), _stream()),
-                      "d3f_circle_det_loss_forward")
-    else:
-        total = torch.empty((), dtype=torch.float32, device=dev)
-        _native.check(L.d3f_circle_det_loss_forward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
-                                                          pm, nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
-                                                          _p(scalars), _p(total), _p(stats), _stream()),
-                      "d3f_circle_det_loss_forward_pairs")
-    return scalars, total, dists, fp, an, stats
+    out = scalars, total, dists, fp, an, stats = _loss_outputs(oa, P, M, with_total)
+    _native.check(_native.lib().d3f_circle_det_loss_forward(
+        _p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm, weights[0], weights[1], _p(dists), _p(fp),
+        _p(an), _p(scalars), _p(total), _p(stats), _stream()), "d3f_circle_det_loss_forward")
+    return out
 
 
 def _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, weights, g_ptrs):
-    """(ga, gp, gsa, gsp) of _circle_fwd.  ``g_ptrs``: device addresses of d / d desc and d / d det (single pair), or of
-    d / d total alone (stacked pairs: the kernel applies ``weights``)."""
+    """(ga, gp, gsa, gsp) of _circle_fwd.  ``g_ptrs``: device addresses of d / d desc and d / d det (the same address
+    twice for d / d total: the kernel applies ``weights``)."""
     L = _native.lib()
     C = int(oa.shape[1])
     s, sr, pm, nm = params
     ga, gp = torch.empty_like(oa), torch.empty_like(op)
     gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
-    if weights is None:
-        nbytes = L.d3f_circle_det_loss_ws_bytes(M)
-        ws = _ws(nbytes, oa.device)
-        _native.check(L.d3f_circle_det_loss_backward(_p(oa), _p(op), M, C, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm,
-                                                     _p(dists), _p(stats), g_ptrs[0], g_ptrs[1], _p(ga), _p(gp),
-                                                     _p(gsa), _p(gsp), _p(ws), nbytes, _stream()),
-                      "d3f_circle_det_loss_backward")
-    else:
-        _native.check(L.d3f_circle_det_loss_backward_pairs(_p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr,
-                                                           pm, nm, weights[0], weights[1], _p(dists), _p(stats),
-                                                           g_ptrs[0], _p(ga), _p(gp), _p(gsa), _p(gsp), _stream()),
-                      "d3f_circle_det_loss_backward_pairs")
+    nbytes = 0 if _circle_tiled(M, C) else L.d3f_circle_det_loss_ws_bytes(M)
+    ws = _ws(nbytes, oa.device) if nbytes else None
+    _native.check(L.d3f_circle_det_loss_backward(
+        _p(oa), _p(op), M, C, P, _p(neg_mask), _p(sa), _p(sp), s, sr, pm, nm, weights[0], weights[1], _p(dists),
+        _p(stats), g_ptrs[0], g_ptrs[1], _p(ga), _p(gp), _p(gsa), _p(gsp), _p(ws), nbytes, _stream()),
+        "d3f_circle_det_loss_backward")
     return ga, gp, gsa, gsp
 
 
@@ -2125,9 +2119,10 @@ class _CircleDetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, positive, neg_mask, anc_score, pos_score, log_scale, safe_radius, pos_margin,
                 neg_margin):
+        M = int(anchor.shape[0])
         ctx.params = (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin))
-        scalars, _, dists, fp, an, stats = _circle_fwd(anchor, positive, anc_score, pos_score, neg_mask, 1,
-                                                       int(anchor.shape[0]), ctx.params, None)
+        scalars, _, dists, fp, an, stats = _circle_fwd(anchor, positive, anc_score, pos_score, neg_mask, 1, M, ctx.params)
+        scalars, dists = scalars.view(6), dists.view(M, M)
         ctx.save_for_backward(anchor, positive, neg_mask, anc_score, pos_score, dists, stats)
         ctx.mark_non_differentiable(dists, fp, an)
         ctx.set_materialize_grads(False)
@@ -2140,7 +2135,7 @@ class _CircleDetFn(torch.autograd.Function):
         anchor, positive, neg_mask, anc_score, pos_score, dists, stats = ctx.saved_tensors
         g = g_scalars.contiguous().float()
         ga, gp, gsa, gsp = _circle_bwd(anchor, positive, anc_score, pos_score, neg_mask, dists, stats, 1,
-                                       int(anchor.shape[0]), ctx.params, None, (g.data_ptr(), g.data_ptr() + 4))
+                                       int(anchor.shape[0]), ctx.params, (1.0, 1.0), (g.data_ptr(), g.data_ptr() + 4))
         return ga, gp, None, gsa, gsp, None, None, None, None
 
 
@@ -2159,63 +2154,72 @@ def circle_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, log_sca
     return _CircleDetFn.apply(anchor, positive, neg_mask, sa, sp, log_scale, safe_radius, pos_margin, neg_margin)
 
 
-def _corr_columns(idx_a, idx_p):
-    """(ptr_a, ptr_p, stride) of the two index vectors.  When they are the two columns of one contiguous [M,2] int64
-    table (``corr[:, 0]``, ``corr[:, 1]``) they are read in place with stride 2; otherwise compacted."""
+def _sampled_rows(idx_a, idx_p, p_offset=None, lens=None):
+    """(saved, stride): the sampled rows of a training step as the select + normalise and detector entries take them
+    ("The sampled rows" in include/d3feat_hip.h).  ``saved`` = (ia, ip, p_offset, lens), what a backward keeps: int64 index
+    vectors read with ``stride``; one pair has global rows, ``p_offset`` (device int32 [1]) or None and ``lens`` None; P
+    stacked pairs have cloud-local rows and ``lens`` device int32 [2P].  The two columns of one contiguous [T,2] int64
+    table (``corr[:, 0]``, ``corr[:, 1]``) are read in place with stride 2; anything else is compacted."""
     if (idx_a.dtype == torch.int64 and idx_p.dtype == torch.int64 and idx_a.dim() == 1 and idx_p.dim() == 1
             and idx_a.stride(0) == 2 and idx_p.stride(0) == 2 and idx_p.data_ptr() == idx_a.data_ptr() + 8
             and idx_a.shape == idx_p.shape):
-        return idx_a, idx_p, 2
+        return (idx_a, idx_p, p_offset, lens), 2
     ia, ip = idx_a.contiguous(), idx_p.contiguous()
     if ia.dtype != torch.int64 or ip.dtype != torch.int64:
         ia, ip = ia.long(), ip.long()
-    return ia, ip, 1
+    return (ia, ip, p_offset, lens), 1
 
 
-def _select_normalize_fwd(x, scores, ia, ip, stride, off):
-    N, C, M = int(x.shape[0]), int(x.shape[1]), int(ia.shape[0])
-    dev = x.device
-    oa = torch.empty((M, C), dtype=torch.float32, device=dev)
-    op = torch.empty((M, C), dtype=torch.float32, device=dev)
-    sa = torch.empty(M, dtype=torch.float32, device=dev)
-    sp = torch.empty(M, dtype=torch.float32, device=dev)
-    _native.check(_native.lib().d3f_select_normalize_forward(_p(x), _p(scores), N, C, _p(ia), _p(ip), stride, M,
-                                                             _p(off), _p(oa), _p(op), _p(sa), _p(sp), _stream()),
-                  "d3f_select_normalize_forward")
+def _select_rows_fwd(x, scores, corr, p_offset, lens, P, M):
+    """The 2 P M sampled rows of corr [P*M,2], gathered and normalised by one launch: (oa, op [P*M,C], sa, sp [P*M], saved,
+    stride), the last two as _sampled_rows gives them.  ``scores`` None: sa / sp are left for the detector's rows form to
+    fill (_det_rows_fwd)."""
+    saved, stride = _sampled_rows(corr[:, 0], corr[:, 1], p_offset, lens)
+    return _select_normalize_fwd(x, scores, saved, stride, P, M) + (saved, stride)
+
+
+def _select_normalize_fwd(x, scores, saved, stride, P, M):
+    N, C, T, dev = int(x.shape[0]), int(x.shape[1]), P * M, x.device
+    ia, ip, p_offset, lens = saved
+    oa = torch.empty((T, C), dtype=torch.float32, device=dev)
+    op = torch.empty((T, C), dtype=torch.float32, device=dev)
+    sa = torch.empty(T, dtype=torch.float32, device=dev)
+    sp = torch.empty(T, dtype=torch.float32, device=dev)
+    _native.check(_native.lib().d3f_select_normalize_forward(
+        _p(x), _p(scores), N, C, _p(ia), _p(ip), stride, M, P, _p(p_offset), _p(lens), _p(oa), _p(op), _p(sa), _p(sp),
+        _stream()), "d3f_select_normalize_forward")
     return oa, op, sa, sp
 
 
-def _grad_rows_buffer(x, with_scores):
-    """(grad_x [N,C], grad_scores [N,1] or None): one allocation, cleared by one fill."""
+def _select_rows_bwd(x, saved, stride, P, M, g_a, g_p, g_sa, g_sp, with_scores=True):
+    """(grad_x [N,C], grad_scores [N,1]) of _select_normalize_fwd: one allocation, cleared by one fill.  ``with_scores``
+    False: (grad_x, None), the score gradients go through _det_rows_bwd instead."""
     N, C = int(x.shape[0]), int(x.shape[1])
-    if not with_scores:
-        return torch.empty((N, C), dtype=torch.float32, device=x.device), None
-    buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
-    return buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
-
-
-def _select_normalize_bwd(x, ia, ip, stride, off, g_a, g_p, g_sa, g_sp, with_scores=True):
-    N, C, M = int(x.shape[0]), int(x.shape[1]), int(ia.shape[0])
-    gx, gs = _grad_rows_buffer(x, with_scores)
+    ia, ip, p_offset, lens = saved
+    if with_scores:
+        buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
+        gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+    else:
+        gx, gs, g_sa, g_sp = torch.empty((N, C), dtype=torch.float32, device=x.device), None, None, None
     cont = [g.contiguous() if g is not None else None for g in (g_a, g_p, g_sa, g_sp)]
-    _native.check(_native.lib().d3f_select_normalize_backward(_p(x), N, C, _p(ia), _p(ip), stride, M, _p(off),
-                                                              _p(cont[0]), _p(cont[1]), _p(cont[2]), _p(cont[3]),
-                                                              _p(gx), _p(gs), _stream()), "d3f_select_normalize_backward")
+    _native.check(_native.lib().d3f_select_normalize_backward(
+        _p(x), N, C, _p(ia), _p(ip), stride, M, P, _p(p_offset), _p(lens), _p(cont[0]), _p(cont[1]), _p(cont[2]),
+        _p(cont[3]), _p(gx), _p(gs), _stream()), "d3f_select_normalize_backward")
     return gx, gs
 
 
 class _SelectNormalizeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scores, idx_a, idx_p, p_offset, stride):
-        ctx.save_for_backward(x, idx_a, idx_p, p_offset if p_offset is not None else idx_a.new_empty(0))
-        ctx.has_off, ctx.stride = p_offset is not None, stride
-        return _select_normalize_fwd(x, scores, idx_a, idx_p, stride, p_offset)
+    def forward(ctx, x, scores, saved, stride):
+        ctx.save_for_backward(x, *saved)
+        ctx.stride = stride
+        return _select_normalize_fwd(x, scores, saved, stride, 1, int(saved[0].shape[0]))
 
     @staticmethod
     def backward(ctx, g_a, g_p, g_sa, g_sp):
-        x, idx_a, idx_p, p_off = ctx.saved_tensors
-        gx, gs = _select_normalize_bwd(x, idx_a, idx_p, ctx.stride, p_off if ctx.has_off else None, g_a, g_p, g_sa, g_sp)
-        return gx, gs, None, None, None, None
+        x, *saved = ctx.saved_tensors
+        gx, gs = _select_rows_bwd(x, saved, ctx.stride, 1, int(saved[0].shape[0]), g_a, g_p, g_sa, g_sp)
+        return gx, gs, None, None
 
 
 def _p_offset(p_offset, device):
@@ -2231,8 +2235,7 @@ def select_normalize(x, scores, idx_a, idx_p, p_offset=None):
     are read in place); p_offset: device int32 scalar."""
     x = _f32(x, "x")
     sc = _f32(scores, "scores").reshape(-1, 1)
-    ia, ip, stride = _corr_columns(idx_a, idx_p)
-    return _SelectNormalizeFn.apply(x, sc, ia, ip, _p_offset(p_offset, x.device), stride)
+    return _SelectNormalizeFn.apply(x, sc, *_sampled_rows(idx_a, idx_p, _p_offset(p_offset, x.device)))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -2245,45 +2248,25 @@ def _dk64(dist_keypts, shape, device):
     return dk
 
 
-def _contrastive_fwd(oa, op, sa, sp, dk, P, M, params, weights):
+def _contrastive_fwd(oa, op, sa, sp, dk, P, M, params, weights=(1.0, 1.0), with_total=False):
     """Forward launches on selected rows oa/op [P*M,C]: (scalars [P,6], total or None, dists, fp, an, stats)."""
-    L = _native.lib()
-    C, dev = int(oa.shape[1]), oa.device
+    C = int(oa.shape[1])
     sr, pm, nm = params
-    dists = torch.empty((P, M, M), dtype=torch.float32, device=dev)
-    fp = torch.empty(P * M, dtype=torch.float32, device=dev)
-    an = torch.empty(P * M, dtype=torch.float32, device=dev)
-    scalars = torch.empty((P, 6), dtype=torch.float32, device=dev)
-    stats = torch.empty(P * L.d3f_circle_det_loss_stats_floats(M), dtype=torch.float32, device=dev)
-    if weights is None:
-        total = None
-        _native.check(L.d3f_contrastive_det_loss_forward(_p(oa), _p(op), M, C, _p(dk), _p(sa), _p(sp), sr, pm, nm,
-                                                         _p(dists), _p(fp), _p(an), _p(scalars), _p(stats), _stream()),
-                      "d3f_contrastive_det_loss_forward")
-    else:
-        total = torch.empty((), dtype=torch.float32, device=dev)
-        _native.check(L.d3f_contrastive_det_loss_forward_pairs(_p(oa), _p(op), M, C, P, _p(dk), _p(sa), _p(sp), sr, pm,
-                                                               nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
-                                                               _p(scalars), _p(total), _p(stats), _stream()),
-                      "d3f_contrastive_det_loss_forward_pairs")
-    return scalars, total, dists, fp, an, stats
+    out = scalars, total, dists, fp, an, stats = _loss_outputs(oa, P, M, with_total)
+    _native.check(_native.lib().d3f_contrastive_det_loss_forward(
+        _p(oa), _p(op), M, C, P, _p(dk), _p(sa), _p(sp), sr, pm, nm, weights[0], weights[1], _p(dists), _p(fp), _p(an),
+        _p(scalars), _p(total), _p(stats), _stream()), "d3f_contrastive_det_loss_forward")
+    return out
 
 
 def _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs):
-    L = _native.lib()
     C = int(oa.shape[1])
     _, pm, nm = params
     ga, gp = torch.empty_like(oa), torch.empty_like(op)
     gsa, gsp = torch.empty_like(sa), torch.empty_like(sp)
-    if weights is None:
-        _native.check(L.d3f_contrastive_det_loss_backward(_p(oa), _p(op), M, C, _p(sa), _p(sp), pm, nm, _p(stats),
-                                                          g_ptrs[0], g_ptrs[1], _p(ga), _p(gp), _p(gsa), _p(gsp),
-                                                          _stream()), "d3f_contrastive_det_loss_backward")
-    else:
-        _native.check(L.d3f_contrastive_det_loss_backward_pairs(_p(oa), _p(op), M, C, P, _p(sa), _p(sp), pm, nm,
-                                                                weights[0], weights[1], _p(stats), g_ptrs[0], _p(ga),
-                                                                _p(gp), _p(gsa), _p(gsp), _stream()),
-                      "d3f_contrastive_det_loss_backward_pairs")
+    _native.check(_native.lib().d3f_contrastive_det_loss_backward(
+        _p(oa), _p(op), M, C, P, _p(sa), _p(sp), pm, nm, weights[0], weights[1], _p(stats), g_ptrs[0], g_ptrs[1],
+        _p(ga), _p(gp), _p(gsa), _p(gsp), _stream()), "d3f_contrastive_det_loss_backward")
     return ga, gp, gsa, gsp
 
 
@@ -2294,7 +2277,7 @@ class _ContrastiveDetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, positive, dk, anc_score, pos_score, params):
         M = int(anchor.shape[0])
-        scalars, _, dists, fp, an, stats = _contrastive_fwd(anchor, positive, anc_score, pos_score, dk, 1, M, params, None)
+        scalars, _, dists, fp, an, stats = _contrastive_fwd(anchor, positive, anc_score, pos_score, dk, 1, M, params)
         scalars, dists = scalars.view(6), dists.view(M, M)
         ctx.save_for_backward(anchor, positive, anc_score, pos_score, stats)
         ctx.params = params
@@ -2309,7 +2292,7 @@ class _ContrastiveDetFn(torch.autograd.Function):
         anchor, positive, anc_score, pos_score, stats = ctx.saved_tensors
         g = g_scalars.contiguous().float()
         ga, gp, gsa, gsp = _contrastive_bwd(anchor, positive, anc_score, pos_score, stats, 1, int(anchor.shape[0]),
-                                            ctx.params, None, (g.data_ptr(), g.data_ptr() + 4))
+                                            ctx.params, (1.0, 1.0), (g.data_ptr(), g.data_ptr() + 4))
         return ga, gp, None, gsa, gsp, None
 
 
@@ -2333,44 +2316,9 @@ def contrastive_det_loss(anchor, positive, dist_keypts, anc_score, pos_score, sa
 # ---------------------------------------------------------------------------------------------------------------
 # the whole loss of one training step (trainer.py:91-98) as ONE autograd node
 # ---------------------------------------------------------------------------------------------------------------
-def _select_rows_fwd(x, scores, corr, p_offset, lens, P, M):
-    """The 2 P M sampled rows, gathered and normalised by one launch: (oa, op, sa, sp, saved, stride).  ``scores``
-    None: sa / sp are left for the detector's rows form to fill (_det_rows_fwd).  ``lens`` None:
-    one pair (corr [M,2], its columns read in place; p_offset); otherwise P stacked pairs (corr [P*M,2] cloud-local,
-    lens int32 [2P]).  ``saved`` (three tensors or None) and ``stride`` (None: stacked) are what _select_rows_bwd needs."""
-    if lens is None:
-        ia, ip, stride = _corr_columns(corr[:, 0], corr[:, 1])
-        return _select_normalize_fwd(x, scores, ia, ip, stride, p_offset) + ((ia, ip, p_offset), stride)
-    N, C, T, dev = int(x.shape[0]), int(x.shape[1]), P * M, x.device
-    oa = torch.empty((T, C), dtype=torch.float32, device=dev)
-    op = torch.empty((T, C), dtype=torch.float32, device=dev)
-    sa = torch.empty(T, dtype=torch.float32, device=dev)
-    sp = torch.empty(T, dtype=torch.float32, device=dev)
-    _native.check(_native.lib().d3f_select_normalize_forward_pairs(_p(x), _p(scores), N, C, _p(corr), M, P, _p(lens),
-                                                                   _p(oa), _p(op), _p(sa), _p(sp), _stream()),
-                  "d3f_select_normalize_forward_pairs")
-    return oa, op, sa, sp, (corr, lens, None), None
-
-
-def _select_rows_bwd(x, saved, stride, P, M, ga, gp, gsa, gsp, with_scores=True):
-    """(grad_x [N,C], grad_scores [N,1]) of _select_rows_fwd; ``with_scores`` False: (grad_x, None), the score
-    gradients go through _det_rows_bwd instead."""
-    s0, s1, s2 = saved
-    if not with_scores:
-        gsa = gsp = None
-    if stride is not None:
-        return _select_normalize_bwd(x, s0, s1, stride, s2, ga, gp, gsa, gsp, with_scores)
-    N, C = int(x.shape[0]), int(x.shape[1])
-    gx, gs = _grad_rows_buffer(x, with_scores)
-    _native.check(_native.lib().d3f_select_normalize_backward_pairs(_p(x), N, C, _p(s0), M, P, _p(s1), _p(ga), _p(gp),
-                                                                    _p(gsa), _p(gsp), _p(gx), _p(gs), _stream()),
-                  "d3f_select_normalize_backward_pairs")
-    return gx, gs
-
-
 def _det_rows_args(x, det, fmax, pair_lens):
-    """Leading arguments of the d3f_detection_rows_* entries and their (len, B, group); the stacked forms hand the
-    pairs' own lengths (group 0: one normaliser for all of them, as the dense form without groups)."""
+    """Leading arguments of the d3f_detection_rows_* entries and their normaliser groups (len, B, group); stacked pairs
+    hand their own lengths (group 0: one normaliser for all of them, as the dense form without groups)."""
     N, C, H = int(x.shape[0]), int(x.shape[1]), int(det.neighbors.shape[1])
     if int(det.neighbors.shape[0]) != N:
         raise ValueError("DetectorRows: the neighbor table must have one row per descriptor")
@@ -2385,50 +2333,39 @@ def _det_rows_args(x, det, fmax, pair_lens):
 
 def _det_rows_fwd(x, det, fmax, saved, stride, P, M, sa, sp, want_aux):
     """Scores of the sampled rows into sa / sp; returns the compact aux [2 P M, 8] (None when no backward follows)."""
-    L = _native.lib()
-    head, groups = _det_rows_args(x, det, fmax, None if stride is not None else saved[1])
+    ia, ip, p_offset, lens = saved
+    head, groups = _det_rows_args(x, det, fmax, lens)
     aux = torch.empty((2 * P * M, 8), dtype=torch.float32, device=x.device) if want_aux else None
-    s0, s1, s2 = saved
     with _region("detection_rows_fwd[T=%d]" % (P * M)):
-        if stride is not None:
-            _native.check(L.d3f_detection_rows_forward(*head, 1 if det.training else 0, _p(det.width), *groups, _p(s0),
-                                                       _p(s1), stride, M, _p(s2), _p(sa), _p(sp), _p(aux), _stream()),
-                          "d3f_detection_rows_forward")
-        else:
-            _native.check(L.d3f_detection_rows_forward_pairs(*head, 1 if det.training else 0, _p(det.width), *groups,
-                                                             _p(s0), M, P, _p(sa), _p(sp), _p(aux), _stream()),
-                          "d3f_detection_rows_forward_pairs")
+        _native.check(_native.lib().d3f_detection_rows_forward(
+            *head, 1 if det.training else 0, _p(det.width), *groups, _p(ia), _p(ip), stride, M, P, _p(p_offset),
+            _p(lens), _p(sa), _p(sp), _p(aux), _stream()), "d3f_detection_rows_forward")
     return aux
 
 
 def _det_rows_bwd(x, det, fmax, saved, stride, P, M, aux, gsa, gsp, gx):
     """Adds the detector's gradient of the sampled rows (and the normaliser's arg-max term) to ``gx``."""
     L = _native.lib()
-    head, groups = _det_rows_args(x, det, fmax, None if stride is not None else saved[1])
+    ia, ip, p_offset, lens = saved
+    head, groups = _det_rows_args(x, det, fmax, lens)
     nws = int(L.d3f_detection_rows_ws_bytes(2 * P * M))
     ws = _ws(nws, x.device)
-    s0, s1, s2 = saved
     with _region("detection_rows_bwd[T=%d]" % (P * M)):
-        if stride is not None:
-            _native.check(L.d3f_detection_rows_backward(*head, *groups, _p(s0), _p(s1), stride, M, _p(s2), _p(aux),
-                                                        _p(gsa), _p(gsp), _p(gx), _p(ws), nws, _stream()),
-                          "d3f_detection_rows_backward")
-        else:
-            _native.check(L.d3f_detection_rows_backward_pairs(*head, *groups, _p(s0), M, P, _p(aux), _p(gsa), _p(gsp),
-                                                              _p(gx), _p(ws), nws, _stream()),
-                          "d3f_detection_rows_backward_pairs")
+        _native.check(L.d3f_detection_rows_backward(
+            *head, *groups, _p(ia), _p(ip), stride, M, P, _p(p_offset), _p(lens), _p(aux), _p(gsa), _p(gsp), _p(gx),
+            _p(ws), nws, _stream()), "d3f_detection_rows_backward")
 
 
 class _TrainLossFn(torch.autograd.Function):
-    """x [N,C] raw descriptors, scores [N,1], corr -> (total, scalars, dists, furthest_positive, average_negative)
-    with total = sum over the pairs of w_desc * desc + w_det * det.  Same kernels as select_normalize + circle_det_loss /
-    contrastive_det_loss; what disappears is the autograd glue between them (index selects and their zero-filled
-    backward, the weighted sum and its backward: ~12 sub-5-us launches per step).
-    ``lens`` None: one pair (corr [M,2], p_offset), scalars [6] (circle) / [1,6] (contrastive); otherwise P pairs
-    stacked into one batch (corr [P*M,2], every pair's own cloud-local table; lens int32 [2P], the level-0 stack lengths
-    on the device), scalars [P,6], dists [P,M,M].  ``aux``: the circle loss's neg_mask (uint8) or the contrastive loss's
-    keypoint distances (f64), [M,M] / [P,M,M]; ``params`` = the loss's scalars, led by log_scale for the circle loss.
-    ``gw``: (w_desc, w_det) on the device, for the one form whose kernel does not apply the weights itself.
+    """x [N,C] raw descriptors, scores [N,1], corr [P*M,2] -> (total, scalars [P,6], dists [P,M,M], furthest_positive
+    [P*M], average_negative [P*M]) with total = sum over the pairs of w_desc * desc + w_det * det.  ``lens`` None: one
+    pair with ``p_offset``; otherwise every pair's own cloud-local table and lens int32 [2P] on the device.
+    Same kernels as select_normalize + circle_det_loss / contrastive_det_loss; what disappears is the autograd glue
+    between them (index selects and their zero-filled backward, the weighted sum and its backward: ~12 sub-5-us launches
+    per step).  ``aux``: the circle loss's neg_mask (uint8) or the contrastive loss's keypoint distances (f64),
+    [M,M] / [P,M,M]; ``params`` = the loss's scalars, led by log_scale for the circle loss.
+    ``gw``: (w_desc, w_det) on the device for the circle loss's one-workgroup route (one pair beyond M = 128 or C = 64),
+    whose kernel knows no weights; None everywhere else.
     ``scores`` may be a ``DetectorRows`` instead of a tensor: the node then scores the sampled rows itself, is
     differentiable with respect to x only and returns the single merged grad_x (one fill, no dense score gradient)."""
 
@@ -2443,16 +2380,15 @@ class _TrainLossFn(torch.autograd.Function):
                                                 det.training and ctx.needs_input_grad[0]))
         else:
             ctx.det = None
-        # the single-pair circle kernel knows no weights: unit weights (config.py:58-59) take its own desc + det
+        # the one-workgroup circle kernel knows no weights: unit weights (config.py:58-59) take its own desc + det
         # (scalars[5]; no launch for the sum), others go through ``gw``; every other form weights inside the kernel
-        plain = circle and lens is None
-        if circle:
-            scalars, total, dists, fp, an, stats = _circle_fwd(oa, op, sa, sp, aux, P, M, params,
-                                                               None if plain else weights)
-        else:
-            scalars, total, dists, fp, an, stats = _contrastive_fwd(oa, op, sa, sp, aux, P, M, params, weights)
+        plain = circle and not _circle_tiled(M, int(x.shape[1]))
         if plain:
-            total = scalars[5] if weights == (1.0, 1.0) else torch.dot(scalars[:2], gw)
+            scalars, _, dists, fp, an, stats = _circle_fwd(oa, op, sa, sp, aux, P, M, params)
+            total = scalars[0, 5] if weights == (1.0, 1.0) else torch.dot(scalars[0, :2], gw)
+        else:
+            scalars, total, dists, fp, an, stats = (_circle_fwd if circle else _contrastive_fwd)(
+                oa, op, sa, sp, aux, P, M, params, weights, True)
         ctx.save_for_backward(x, *saved, oa, op, sa, sp, stats, *((aux, dists, gw) if circle else ()))
         ctx.meta = (stride, circle, plain, P, M, params, weights)
         ctx.mark_non_differentiable(scalars, dists, fp, an)
@@ -2463,27 +2399,27 @@ class _TrainLossFn(torch.autograd.Function):
     def backward(ctx, g_total, g_scalars, g_dists, g_fp, g_an):
         if g_total is None:
             return (None,) * 11
-        x, s0, s1, s2, oa, op, sa, sp, stats = ctx.saved_tensors[:9]
+        x, oa, op, sa, sp, stats = ctx.saved_tensors[:1] + ctx.saved_tensors[5:10]
+        saved = ctx.saved_tensors[1:5]
         stride, circle, plain, P, M, params, weights = ctx.meta
         if plain and weights != (1.0, 1.0):
-            g = (ctx.saved_tensors[11] * g_total).contiguous()
-            g_ptrs = (g.data_ptr(), g.data_ptr() + 4)
+            g = (ctx.saved_tensors[12] * g_total).contiguous()
+            g_ptrs, weights = (g.data_ptr(), g.data_ptr() + 4), (1.0, 1.0)
         else:      # d total / d desc = d total / d det = g_total: both pointers read the same scalar
             g = g_total.contiguous().float().reshape(1)
             g_ptrs = (g.data_ptr(), g.data_ptr())
         if circle:
-            neg_mask, dists = ctx.saved_tensors[9:11]
-            grads = _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, None if plain else weights, g_ptrs)
+            neg_mask, dists = ctx.saved_tensors[10:12]
+            grads = _circle_bwd(oa, op, sa, sp, neg_mask, dists, stats, P, M, params, weights, g_ptrs)
         else:
             grads = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs)
         if ctx.det is None:
-            gx, gs = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads)
-            return (gx, gs) + (None,) * 9
+            return _select_rows_bwd(x, saved, stride, P, M, *grads) + (None,) * 9
         det, fmax, aux8 = ctx.det
         if aux8 is None:
             raise RuntimeError("train loss: the detector's backward is defined for training mode only")
-        gx, _ = _select_rows_bwd(x, (s0, s1, s2), stride, P, M, *grads, with_scores=False)
-        _det_rows_bwd(x, det, fmax, (s0, s1, s2), stride, P, M, aux8, grads[2], grads[3], gx)
+        gx, _ = _select_rows_bwd(x, saved, stride, P, M, *grads, with_scores=False)
+        _det_rows_bwd(x, det, fmax, saved, stride, P, M, aux8, grads[2], grads[3], gx)
         return (gx,) + (None,) * 10
 
 
@@ -2497,19 +2433,40 @@ def _loss_inputs(x, scores):
     return x, _f32(scores, "scores").reshape(-1, 1)
 
 
-def _check_corr(corr):
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
-        raise ValueError("corr must be an int64 [M,2] device tensor")
-    return corr.contiguous()
-
-
-def _check_corr_pairs(corr, lens, P, M):
-    """(corr [P*M,2], lens) of a stacked batch of P pairs with M correspondences each."""
-    if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
-        raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
-    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
-        raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
-    return corr.contiguous().view(P * M, 2), lens.contiguous()
+def _train_loss(x, scores, corr, p_offset, lens, table, limit, circle, params, w_desc, w_det, gw_cache=None):
+    """The four train_* front ends behind their own arguments.  ``lens`` None: one pair, corr int64 [M,2] with
+    ``p_offset``; returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]).  Otherwise P stacked
+    pairs, corr [P,M,2] / [P*M,2] and lens device int32 [2P]; desc, det, accuracy are [P], the two vectors [P,M].
+    ``table(device, M)`` checks and returns the loss's neg_mask / keypoint distances (M None: stacked, its own [P,M,M]
+    gives P and M); ``limit`` = (lowest M, highest M, highest C, message) or None."""
+    x, sc = _loss_inputs(x, scores)
+    if lens is None:
+        if not (corr.is_cuda and corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2):
+            raise ValueError("corr must be an int64 [M,2] device tensor")
+        P, M = 1, int(corr.shape[0])
+        aux = table(x.device, M)
+    else:
+        aux = table(x.device, None)
+        P, M = int(aux.shape[0]), int(aux.shape[1])
+        if not (corr.is_cuda and corr.dtype == torch.int64 and corr.numel() == 2 * P * M and corr.shape[-1] == 2):
+            raise ValueError("corr must be an int64 [P,M,2] device tensor (P = %d, M = %d)" % (P, M))
+        if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.numel() == 2 * P):
+            raise ValueError("lens must hold the 2P level-0 stack lengths as device int32")
+        lens = lens.contiguous()
+    C = int(x.shape[1])
+    if limit is not None and (not limit[0] <= M <= limit[1] or C > limit[2] or P > 32):
+        raise ValueError(limit[3])
+    weights, gw = (float(w_desc), float(w_det)), None
+    if circle and not _circle_tiled(M, C) and weights != (1.0, 1.0):
+        key = (x.device,) + weights
+        if key not in gw_cache:
+            gw_cache[key] = torch.tensor(weights, dtype=torch.float32, device=x.device)
+        gw = gw_cache[key]
+    total, scalars, dists, fp, an = _TrainLossFn.apply(x, sc, corr.contiguous().view(P * M, 2), _p_offset(p_offset, x.device),
+                                                       lens, aux, circle, P, params, weights, gw)
+    if lens is None:
+        return total, scalars[0, 0], scalars[0, 1], scalars[0, 2], fp, an
+    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
 
 
 def train_loss(x, scores, corr, p_offset, dist_keypts, log_scale=10.0, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
@@ -2520,21 +2477,17 @@ def train_loss(x, scores, corr, p_offset, dist_keypts, log_scale=10.0, safe_radi
     gradient.  ``neg_mask``: ``dist_keypts > safe_radius`` as uint8 when the caller already has it (the pipelined step
     evaluates it with the pair's upload, off the training stream).  ``scores``: the [N,1] scores, or a ``DetectorRows``
     (here and in the three sibling forms): the detector then runs on the 2M sampled rows only, inside this node."""
-    x, sc = _loss_inputs(x, scores)
-    corr = _check_corr(corr)
-    if neg_mask is None:
-        neg_mask = _neg_mask_of(dist_keypts, safe_radius)
-    elif not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous()
-              and tuple(neg_mask.shape) == (corr.shape[0], corr.shape[0])):
-        raise ValueError("neg_mask must be a contiguous uint8 [M,M] device tensor (dist_keypts > safe_radius)")
-    key = (x.device, float(w_desc), float(w_det))
-    if key not in _gw_cache:
-        _gw_cache[key] = torch.tensor([float(w_desc), float(w_det)], dtype=torch.float32, device=x.device)
-    total, scalars, dists, fp, an = _TrainLossFn.apply(
-        x, sc, corr, _p_offset(p_offset, x.device), None, neg_mask, True, 1,
-        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)),
-        _gw_cache[key])
-    return total, scalars[0], scalars[1], scalars[2], fp, an
+    def table(device, M):
+        if neg_mask is None:
+            return _neg_mask_of(dist_keypts, safe_radius)
+        if not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous()
+                and tuple(neg_mask.shape) == (M, M)):
+            raise ValueError("neg_mask must be a contiguous uint8 [M,M] device tensor (dist_keypts > safe_radius)")
+        return neg_mask
+
+    return _train_loss(x, scores, corr, p_offset, None, table, None, True,
+                       (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), w_desc, w_det,
+                       _gw_cache)
 
 
 def train_loss_pairs(x, scores, corr, lens, dist_keypts=None, log_scale=10.0, safe_radius=0.1, pos_margin=0.1,
@@ -2547,21 +2500,16 @@ def train_loss_pairs(x, scores, corr, lens, dist_keypts=None, log_scale=10.0, sa
     uint8 [P,M,M] = dist_keypts > safe_radius.  Three launches forward (select + normalise, strips of all pairs,
     finalize), two backward.
     Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
-    x, sc = _loss_inputs(x, scores)
-    if neg_mask is None:
-        neg_mask = _neg_mask_of(dist_keypts, safe_radius)
-    if not (neg_mask.is_cuda and neg_mask.dtype == torch.uint8 and neg_mask.is_contiguous() and neg_mask.dim() == 3
-            and neg_mask.shape[1] == neg_mask.shape[2]):
-        raise ValueError("neg_mask must be a contiguous uint8 [P,M,M] device tensor (dist_keypts > safe_radius)")
-    P, M = int(neg_mask.shape[0]), int(neg_mask.shape[1])
-    corr, lens = _check_corr_pairs(corr, lens, P, M)
-    if M > 128 or int(x.shape[1]) > 64 or P > 32:
-        raise ValueError("stacked loss: M <= 128 correspondences, C <= 64 channels, P <= 32 pairs")
-    total, scalars, dists, fp, an = _TrainLossFn.apply(
-        x, sc, corr, None, lens, neg_mask, True, P,
-        (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)),
-        None)
-    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
+    def table(device, _):
+        mask = _neg_mask_of(dist_keypts, safe_radius) if neg_mask is None else neg_mask
+        if not (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3
+                and mask.shape[1] == mask.shape[2]):
+            raise ValueError("neg_mask must be a contiguous uint8 [P,M,M] device tensor (dist_keypts > safe_radius)")
+        return mask
+
+    return _train_loss(x, scores, corr, None, lens, table,
+                       (0, 128, 64, "stacked loss: M <= 128 correspondences, C <= 64 channels, P <= 32 pairs"), True,
+                       (float(log_scale), float(safe_radius), float(pos_margin), float(neg_margin)), w_desc, w_det)
 
 
 def train_contrastive_loss(x, scores, corr, p_offset, dist_keypts, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
@@ -2570,16 +2518,12 @@ def train_contrastive_loss(x, scores, corr, p_offset, dist_keypts, safe_radius=0
     ``w_desc * ContrastiveLoss(normalize(x)[corr[:,0]], normalize(x)[corr[:,1] + p_offset], dist_keypts) + w_det *
     DetLoss(dists, ...)``.  Returns (total, desc, det, accuracy, furthest_positive [M], average_negative [M]); only
     ``total`` carries gradient."""
-    x, sc = _loss_inputs(x, scores)
-    corr = _check_corr(corr)
-    M = int(corr.shape[0])
-    if not 2 <= M <= 1024 or int(x.shape[1]) > 256:
-        raise ValueError("contrastive loss: 2 <= M <= 1024 correspondences, C <= 256 channels")
-    dk = _dk64(dist_keypts, (1, M, M), x.device) if dist_keypts.dim() == 3 else _dk64(dist_keypts, (M, M), x.device)
-    total, scalars, dists, fp, an = _TrainLossFn.apply(
-        x, sc, corr, _p_offset(p_offset, x.device), None, dk, False, 1,
-        (float(safe_radius), float(pos_margin), float(neg_margin)), (float(w_desc), float(w_det)), None)
-    return total, scalars[0, 0], scalars[0, 1], scalars[0, 2], fp, an
+    def table(device, M):
+        return _dk64(dist_keypts, (1, M, M) if dist_keypts.dim() == 3 else (M, M), device)
+
+    return _train_loss(x, scores, corr, p_offset, None, table,
+                       (2, 1024, 256, "contrastive loss: 2 <= M <= 1024 correspondences, C <= 256 channels"), False,
+                       (float(safe_radius), float(pos_margin), float(neg_margin)), w_desc, w_det)
 
 
 def train_contrastive_loss_pairs(x, scores, corr, lens, dist_keypts, safe_radius=0.1, pos_margin=0.1, neg_margin=1.4,
@@ -2587,18 +2531,14 @@ def train_contrastive_loss_pairs(x, scores, corr, lens, dist_keypts, safe_radius
     """``train_loss_pairs`` with the contrastive loss: P stacked pairs, ``dist_keypts`` [P,M,M] (read as float64),
     total = sum_p (w_desc desc_p + w_det det_p).
     Returns (total, desc [P], det [P], accuracy [P], furthest_positive [P,M], average_negative [P,M])."""
-    x, sc = _loss_inputs(x, scores)
-    if dist_keypts.dim() != 3 or dist_keypts.shape[1] != dist_keypts.shape[2]:
-        raise ValueError("dist_keypts must be [P,M,M]")
-    P, M = int(dist_keypts.shape[0]), int(dist_keypts.shape[1])
-    dk = _dk64(dist_keypts, (P, M, M), x.device)
-    corr, lens = _check_corr_pairs(corr, lens, P, M)
-    if not 2 <= M <= 1024 or int(x.shape[1]) > 256 or P > 32:
-        raise ValueError("stacked contrastive loss: 2 <= M <= 1024, C <= 256 channels, P <= 32 pairs")
-    total, scalars, dists, fp, an = _TrainLossFn.apply(
-        x, sc, corr, None, lens, dk, False, P, (float(safe_radius), float(pos_margin), float(neg_margin)),
-        (float(w_desc), float(w_det)), None)
-    return total, scalars[:, 0], scalars[:, 1], scalars[:, 2], fp.view(P, M), an.view(P, M)
+    def table(device, _):
+        if dist_keypts.dim() != 3 or dist_keypts.shape[1] != dist_keypts.shape[2]:
+            raise ValueError("dist_keypts must be [P,M,M]")
+        return _dk64(dist_keypts, tuple(dist_keypts.shape), device)
+
+    return _train_loss(x, scores, corr, None, lens, table,
+                       (2, 1024, 256, "stacked contrastive loss: 2 <= M <= 1024, C <= 256 channels, P <= 32 pairs"), False,
+                       (float(safe_radius), float(pos_margin), float(neg_margin)), w_desc, w_det)
 
 
 # ---------------------------------------------------------------------------------------------------------------

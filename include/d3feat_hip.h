@@ -530,82 +530,100 @@ int d3f_detection_scores_backward_groups(const float* feat, int N, int C, const 
                                          size_t ws_bytes, void* stream);
 size_t d3f_detection_scores_ws_bytes(int N, int C);
 
-/* The detector on the SAMPLED rows of a training step: the loss reads the scores of the 2M correspondences only
- * (trainer.py:90-97 and :158-165 index scores[corr] before det_loss), so one wave per sampled row runs the body of
+/* ------------------------------------------------------------------------------------------------
+ * The training loss (trainer.py:90-98) in four stages, each one forward and one backward entry: select + normalise the
+ * sampled rows, the detector on those rows, then circle + detector loss or contrastive + detector loss.
+ *
+ * The pair dimension.  Every entry takes `pairs`: the fragment pairs of one training batch (the reference trains on one
+ * pair per step, datasets/dataloader.py:73; stacking P of them into one launch sequence is this build's batching).  M is
+ * the number of sampled correspondences PER PAIR and every per-pair array below gains a leading pair dimension:
+ * anchor/positive/out_a/out_p [pairs*M,C], scores sa/sp [pairs*M], neg_mask / dist_keypts / dists [pairs,M,M],
+ * out_scalars [pairs,6], stats [pairs * d3f_circle_det_loss_stats_floats(M)], aux [2*pairs*M,8] (all anchors, then all
+ * positives).  Every pair is its own M x M problem.  pairs <= 32 (2*pairs <= 64 clouds in the rows stages).
+ *
+ * The sampled rows (select + normalise, detector): idx_a / idx_p int64 [pairs*M], element m at idx[m * idx_stride]
+ * (2 = the columns of a [pairs*M,2] correspondence table, idx_p = idx_a + 1, read in place).
+ *   pair_len NULL: the rows are global rows of x; pairs must be 1; idx_p is offset by *p_offset (device int32: rows of
+ *     the first cloud, trainer.py:91-94) when given.
+ *   pair_len [2*pairs] (device int32, the level-0 stack lengths; clouds 2p, 2p+1 of the stack are pair p): the rows are
+ *     local to the pair's own clouds, as the dataset yields them, and each column is offset by the start of its cloud.
+ *     p_offset must be NULL.
+ * pairs*M <= 2^24.  Rows outside [0, N) are clamped.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Select + normalise -- replaces F.normalize over all N descriptors (models/architectures.py:318) + the four index
+ * selections of trainer.py:91-94 and their backward:
+ *   out[m,:] = x[row[m],:] / max(||x[row[m],:]||, 1e-12),  s[m] = scores[row[m]].
+ * backward: grad_x [N,C] and grad_scores [N] are ONE allocation of N*(C+1) floats (grad_scores == grad_x + N*C),
+ * overwritten; g_* may be NULL.
+ * scores NULL (forward; sa / sp are then not written) and grad_scores NULL (backward; only grad_x [N,C] is cleared and
+ * written): the detector runs on the sampled rows itself (d3f_detection_rows_forward / _backward). */
+int d3f_select_normalize_forward(const float* x, const float* scores, int N, int C, const int64_t* idx_a,
+                                 const int64_t* idx_p, int idx_stride, int M, int pairs, const int32_t* p_offset,
+                                 const int32_t* pair_len, float* out_a, float* out_p, float* sa, float* sp,
+                                 void* stream);
+int d3f_select_normalize_backward(const float* x, int N, int C, const int64_t* idx_a, const int64_t* idx_p,
+                                  int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                  const float* g_a, const float* g_p, const float* g_sa, const float* g_sp,
+                                  float* grad_x, float* grad_scores, void* stream);
+
+/* The detector on the SAMPLED rows: the loss reads the scores of the 2*pairs*M correspondences only (trainer.py:90-97
+ * and :158-165 index scores[corr] before det_loss), so one wave per sampled row runs the body of
  * d3f_detection_scores_forward (the same device function: the scores are bit-identical to the dense ones) and leaves
- * sa [M], sp [M] and a compact aux [2M, 8] (anchors, then positives; NULL when no backward follows or training == 0).
- * Rows are resolved as by d3f_select_normalize_forward[_pairs]; feat_max / width / len + group as for
- * d3f_detection_scores_forward (group 0: one normaliser for the whole batch; the _pairs forms take len [B = 2 pairs] for
- * both the pairs' clouds and the groups).  C in {16, 32, 64} and H <= 64 (d3f_detection_rows_supported); anything else
- * is D3F_EINVAL: the caller keeps the dense path.
- * backward: g_sa / g_sp [M] (either may be NULL = 0) are d loss / d sa, sp.  The gradient of x -- the three per-row terms
+ * sa, sp and a compact aux (NULL when no backward follows or training == 0).
+ * feat_max / width / len [B] + group are the normaliser groups of d3f_detection_scores_forward (group 0: one normaliser
+ * for the whole batch); with pair_len and len both given the groups are made of the pairs' clouds: B == 2*pairs.
+ * C in {16, 32, 64} and H <= 64 (d3f_detection_rows_supported); anything else is D3F_EINVAL: the caller keeps the dense
+ * path.
+ * backward: g_sa / g_sp (either may be NULL = 0) are d loss / d sa, sp.  The gradient of x -- the three per-row terms
  * of d3f_detection_scores_backward and the normaliser's arg-max term -- is ADDED to grad_x [N,C] with float atomics:
- * grad_x is the buffer d3f_select_normalize_backward[_pairs] (grad_scores NULL) has just cleared and written its rows
+ * grad_x is the buffer d3f_select_normalize_backward (grad_scores NULL) has just cleared and written its rows
  * into, so one fill serves both.  The arg-max positions are found by reading feat only; the normaliser's term is summed
  * from one partial per sampled row in a fixed order (the same bits on every replay).
- * ws >= d3f_detection_rows_ws_bytes(2M). */
+ * ws >= d3f_detection_rows_ws_bytes(2*pairs*M). */
 int d3f_detection_rows_supported(int C, int H);
 size_t d3f_detection_rows_ws_bytes(int rows);
 int d3f_detection_rows_forward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
                                int training, const int32_t* width, const int32_t* len, int B, int group,
-                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M,
-                               const int32_t* p_offset, float* sa, float* sp, float* aux, void* stream);
-int d3f_detection_rows_forward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                     int training, const int32_t* width, const int32_t* len, int B, int group,
-                                     const int64_t* corr, int M, int pairs, float* sa, float* sp, float* aux,
-                                     void* stream);
+                               const int64_t* idx_a, const int64_t* idx_p, int idx_stride, int M, int pairs,
+                               const int32_t* p_offset, const int32_t* pair_len, float* sa, float* sp, float* aux,
+                               void* stream);
 int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
                                 const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
-                                int idx_stride, int M, const int32_t* p_offset, const float* aux, const float* g_sa,
-                                const float* g_sp, float* grad_x, void* ws, size_t ws_bytes, void* stream);
-int d3f_detection_rows_backward_pairs(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
-                                      const int32_t* len, int B, int group, const int64_t* corr, int M, int pairs,
-                                      const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
-                                      size_t ws_bytes, void* stream);
+                                int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
+                                size_t ws_bytes, void* stream);
 
-/* ------------------------------------------------------------------------------------------------
- * Descriptor loss -- replaces utils/loss.py: cdist(:8-44, 'euclidean'), CircleLoss.forward(:111-141),
- * DetLoss.forward(:149-158), fused into one single-workgroup launch (M <= 1024 sampled correspondences).
+/* Circle + detector loss -- replaces utils/loss.py: cdist(:8-44, 'euclidean'), CircleLoss.forward(:111-141),
+ * DetLoss.forward(:149-158).  M in 2..1024 sampled correspondences.
  * anchor/positive [M,C]; neg_mask [M,M] uint8 = (dist_keypts > safe_radius), evaluated by the caller in the
  * dtype the dataset supplies (float64 in the reference, loss.py:116); anc_score/pos_score [M].
  * Outputs: dists [M,M], furthest_positive [M], average_negative [M],
  *   out_scalars[0..5] = desc_loss, det_loss, accuracy(%), mean furthest_positive, mean average_negative,
  *                      desc_loss + det_loss;
+ *   out_total [1] (may be NULL) = sum_p (w_desc desc_p + w_det det_p): its gradient is the SUM of the pairs' gradients
+ *                      (the caller's optimizer scale makes the mean);
  *   stats [d3f_circle_det_loss_stats_floats(M)] = row/column log-sum-exps + closest negatives, kept for backward.
- * backward: gradients of  grad_desc*desc_loss + grad_det*det_loss  (device scalars; either may be NULL = 0)
- *   wrt anchor, positive [M,C] and the two score vectors [M] (optional).
- * ---------------------------------------------------------------------------------------------- */
+ * backward: gradients of  sum_p (grad_desc w_desc desc_p + grad_det w_det det_p)  (grad_desc / grad_det device
+ *   scalars; either may be NULL = 0; a caller that differentiates out_total passes its gradient as both)
+ *   wrt anchor, positive and the two score vectors (optional).
+ * Two routes.  M <= 128 and C <= 64 (the training and validation shapes): strips of every pair's matrix, one workgroup
+ *   each, then one tiny launch for the scalars; backward one launch; ws is not used and may be NULL.
+ *   Otherwise ONE workgroup works on the global buffers: pairs must be 1, w_desc = w_det = 1 and out_total NULL
+ *   (D3F_EINVAL else), and the backward needs ws >= d3f_circle_det_loss_ws_bytes(M). */
 size_t d3f_circle_det_loss_stats_floats(int M);
 size_t d3f_circle_det_loss_ws_bytes(int M);
-int d3f_circle_det_loss_forward(const float* anchor, const float* positive, int M, int C, const uint8_t* neg_mask,
-                                const float* anc_score, const float* pos_score, float log_scale, float safe_radius,
-                                float pos_margin, float neg_margin, float* dists, float* furthest_positive,
-                                float* average_negative, float* out_scalars, float* stats, void* stream);
-int d3f_circle_det_loss_backward(const float* anchor, const float* positive, int M, int C, const uint8_t* neg_mask,
-                                 const float* anc_score, const float* pos_score, float log_scale, float safe_radius,
-                                 float pos_margin, float neg_margin, const float* dists, const float* stats,
-                                 const float* grad_desc, const float* grad_det, float* grad_anchor,
-                                 float* grad_positive, float* grad_anc_score, float* grad_pos_score, void* ws,
-                                 size_t ws_bytes, void* stream);
-
-/* `pairs` fragment pairs stacked into one training batch (the reference trains on one pair per step,
- * datasets/dataloader.py:73; stacking P of them into one launch sequence is this build's batching): every array above
- * gains a leading pair dimension (anchor/positive [pairs*M,C], neg_mask [pairs,M,M], scores [pairs*M], dists
- * [pairs,M,M], out_scalars [pairs,6], stats [pairs * d3f_circle_det_loss_stats_floats(M)]); every pair is its own
- * M x M problem.  out_total [1] = sum_p (w_desc desc_p + w_det det_p): its gradient is the SUM of the pairs' gradients
- * (the caller's optimizer scale makes the mean).  M <= 128, C <= 64, pairs <= 32.  backward: grad_total device scalar. */
-int d3f_circle_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                      const uint8_t* neg_mask, const float* anc_score, const float* pos_score,
-                                      float log_scale, float safe_radius, float pos_margin, float neg_margin,
-                                      float w_desc, float w_det, float* dists, float* furthest_positive,
-                                      float* average_negative, float* out_scalars, float* out_total, float* stats,
-                                      void* stream);
-int d3f_circle_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                       const uint8_t* neg_mask, const float* anc_score, const float* pos_score,
-                                       float log_scale, float safe_radius, float pos_margin, float neg_margin,
-                                       float w_desc, float w_det, const float* dists, const float* stats,
-                                       const float* grad_total, float* grad_anchor, float* grad_positive,
-                                       float* grad_anc_score, float* grad_pos_score, void* stream);
+int d3f_circle_det_loss_forward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                const uint8_t* neg_mask, const float* anc_score, const float* pos_score, float log_scale,
+                                float safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                float* dists, float* furthest_positive, float* average_negative, float* out_scalars,
+                                float* out_total, float* stats, void* stream);
+int d3f_circle_det_loss_backward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                 const uint8_t* neg_mask, const float* anc_score, const float* pos_score, float log_scale,
+                                 float safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                 const float* dists, const float* stats, const float* grad_desc, const float* grad_det,
+                                 float* grad_anchor, float* grad_positive, float* grad_anc_score, float* grad_pos_score,
+                                 void* ws, size_t ws_bytes, void* stream);
 
 /* Batch-hard contrastive loss + detector loss -- replaces utils/loss.py: ContrastiveLoss.forward(:54-62) with
  * metric 'euclidean' (what training_3DMatch.py:119-125 builds for desc_loss 'contrastive'), calculate_loss(:65-97) and
@@ -613,58 +631,20 @@ int d3f_circle_det_loss_backward_pairs(const float* anchor, const float* positiv
  *   dists = D + 10*near,  near_ij = (dist_keypts_ij + (i == j ? 10 : 0)) < safe_radius  (f64, like the reference's
  *   NumPy); furthest_positive = dists_ii, closest negative cn_i = min_{j != i} dists_ij (lowest j on ties);
  *   desc = mean_i [max(fp_i - pos_margin, 0) + max(neg_margin - cn_i, 0)], det = mean_i (fp_i - cn_i)(sa_i + sp_i).
- * anchor/positive [M,C] (C <= 256), dist_keypts [M,M] float64, scores [M]; M in 2..1024.  Outputs and out_scalars as
- * d3f_circle_det_loss_forward; stats [d3f_circle_det_loss_stats_floats(M)] hold what the backward reads.
- * backward: gradients of grad_desc*desc + grad_det*det (device scalars; either may be NULL = 0) wrt anchor, positive
- * and (optional) the scores, as torch autograd forms them: half the gradient where a hinge is exactly 0. */
-int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C,
+ * anchor/positive [M,C] (C <= 256), dist_keypts [M,M] float64, scores [M]; M in 2..1024.  Outputs, out_scalars,
+ * out_total, w_desc / w_det and grad_desc / grad_det as d3f_circle_det_loss_forward / _backward; stats
+ * [d3f_circle_det_loss_stats_floats(M)] hold what the backward reads.  The gradients are those torch autograd forms:
+ * half the gradient where a hinge is exactly 0. */
+int d3f_contrastive_det_loss_forward(const float* anchor, const float* positive, int M, int C, int pairs,
                                      const double* dist_keypts, const float* anc_score, const float* pos_score,
-                                     double safe_radius, float pos_margin, float neg_margin, float* dists,
-                                     float* furthest_positive, float* average_negative, float* out_scalars,
-                                     float* stats, void* stream);
-int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, const float* anc_score,
-                                      const float* pos_score, float pos_margin, float neg_margin, const float* stats,
-                                      const float* grad_desc, const float* grad_det, float* grad_anchor,
-                                      float* grad_positive, float* grad_anc_score, float* grad_pos_score,
-                                      void* stream);
-/* stacked pairs, laid out as d3f_circle_det_loss_forward_pairs (dist_keypts [pairs,M,M] float64); pairs <= 32. */
-int d3f_contrastive_det_loss_forward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                           const double* dist_keypts, const float* anc_score, const float* pos_score,
-                                           double safe_radius, float pos_margin, float neg_margin, float w_desc,
-                                           float w_det, float* dists, float* furthest_positive,
-                                           float* average_negative, float* out_scalars, float* out_total, float* stats,
-                                           void* stream);
-int d3f_contrastive_det_loss_backward_pairs(const float* anchor, const float* positive, int M, int C, int pairs,
-                                            const float* anc_score, const float* pos_score, float pos_margin,
-                                            float neg_margin, float w_desc, float w_det, const float* stats,
-                                            const float* grad_total, float* grad_anchor, float* grad_positive,
-                                            float* grad_anc_score, float* grad_pos_score, void* stream);
-
-/* Sampled-correspondence front end of the loss -- replaces F.normalize over all N descriptors
- * (models/architectures.py:318) + the four index selections of trainer.py:91-94 and their backward:
- *   out[m,:] = x[idx[m],:] / max(||x[idx[m],:]||, 1e-12),  s[m] = scores[idx[m]].
- * idx_a / idx_p int64, element m at idx[m * idx_stride] (2 = the columns of the [M,2] correspondence table, read in
- * place); idx_p is offset by *p_offset (device int32: rows of the first cloud) when given.
- * backward: grad_x [N,C] and grad_scores [N] are ONE allocation of N*(C+1) floats (grad_scores == grad_x + N*C),
- * overwritten; g_* may be NULL.
- * scores NULL (forward; sa / sp are then not written) and grad_scores NULL (backward; only grad_x [N,C] is cleared and
- * written): the detector runs on the sampled rows itself (d3f_detection_rows_forward / _backward). */
-int d3f_select_normalize_forward(const float* x, const float* scores, int N, int C, const int64_t* idx_a,
-                                 const int64_t* idx_p, int idx_stride, int M, const int32_t* p_offset, float* out_a,
-                                 float* out_p, float* sa, float* sp, void* stream);
-int d3f_select_normalize_backward(const float* x, int N, int C, const int64_t* idx_a, const int64_t* idx_p,
-                                  int idx_stride, int M, const int32_t* p_offset, const float* g_a, const float* g_p,
-                                  const float* g_sa, const float* g_sp, float* grad_x, float* grad_scores,
-                                  void* stream);
-/* stacked pairs: clouds 2p, 2p+1 of the stack are pair p (len [2 pairs]: level-0 stack lengths on the device); corr
- * [pairs*M,2] int64 holds every pair's own table with cloud-local rows (trainer.py:91-94 adds len(first cloud) to the
- * second column; here each column is offset by the start of its cloud in the stack); outputs [pairs*M, ...]. */
-int d3f_select_normalize_forward_pairs(const float* x, const float* scores, int N, int C, const int64_t* corr, int M,
-                                       int pairs, const int32_t* len, float* out_a, float* out_p, float* sa, float* sp,
-                                       void* stream);
-int d3f_select_normalize_backward_pairs(const float* x, int N, int C, const int64_t* corr, int M, int pairs,
-                                        const int32_t* len, const float* g_a, const float* g_p, const float* g_sa,
-                                        const float* g_sp, float* grad_x, float* grad_scores, void* stream);
+                                     double safe_radius, float pos_margin, float neg_margin, float w_desc, float w_det,
+                                     float* dists, float* furthest_positive, float* average_negative,
+                                     float* out_scalars, float* out_total, float* stats, void* stream);
+int d3f_contrastive_det_loss_backward(const float* anchor, const float* positive, int M, int C, int pairs,
+                                      const float* anc_score, const float* pos_score, float pos_margin, float neg_margin,
+                                      float w_desc, float w_det, const float* stats, const float* grad_desc,
+                                      const float* grad_det, float* grad_anchor, float* grad_positive,
+                                      float* grad_anc_score, float* grad_pos_score, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense matching -- replaces build_correspondence (geometric_registration/common.py:5-21): the

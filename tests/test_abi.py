@@ -197,13 +197,13 @@ def test_the_c_compiler_agrees_on_structs_and_defines(tmp_path):
 
 
 STARRED_CALL_SITES = ["d3f_depth_pyramid", "d3f_depth_pyramid_host", "d3f_detection_rows_backward",
-                      "d3f_detection_rows_backward_pairs", "d3f_detection_rows_forward", "d3f_detection_rows_forward_pairs",
-                      "d3f_rgbd_pyramid", "d3f_rgbd_pyramid_host", "d3f_tsdf_sparse_mark", "d3f_tsdf_sparse_mark_host"]
+                      "d3f_detection_rows_forward", "d3f_rgbd_pyramid", "d3f_rgbd_pyramid_host", "d3f_tsdf_sparse_mark",
+                      "d3f_tsdf_sparse_mark_host"]
 
 
 def test_every_call_site_passes_as_many_arguments_as_the_header_declares():
     """<expr>.d3f_<name>(...) anywhere in the package: the argument count is the prototype's.  A call with a starred
-    argument cannot be counted; those are the ten listed above and no others."""
+    argument cannot be counted; those are the eight listed above and no others."""
     counted, starred, wrong = 0, [], []
     for root, _, files in os.walk(os.path.dirname(_native.__file__)):
         for f in sorted(files):
@@ -224,7 +224,7 @@ def test_every_call_site_passes_as_many_arguments_as_the_header_declares():
                                                               len(node.args), len(_native.SIGNATURES[name][1])))
     assert not wrong, wrong
     assert sorted(starred) == STARRED_CALL_SITES
-    assert counted >= 145
+    assert counted >= 138
 
 
 def test_no_gpu_calls_needed_for_size_queries():

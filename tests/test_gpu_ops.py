@@ -1956,6 +1956,49 @@ def test_train_loss_of_stacked_pairs_equals_the_per_pair_losses():
         assert float((ts.grad - gs).abs().max()) <= 1e-6 * float(gs.abs().max()) + 1e-9
 
 
+def test_one_pair_by_offset_and_by_pair_lengths_gives_the_same_bits():
+    """One pair through ops.train_loss / train_contrastive_loss (global rows: the second column offset by p_offset) and
+    through the stacked forms with P = 1 (cloud-local rows + the two stack lengths): the same entry points resolve the
+    same rows, so every output and gradient has the same bits.  N0 = 37, N1 = 41, C = 16, M = 9: two loss strips of 8
+    (the second partial) and three contrastive blocks of 4 rows.  No row is sampled twice, so the select backward's
+    float atomics never meet.  With ops.DetectorRows (5 neighbours) the forward is still bit-equal; the detector's
+    backward adds neighbours' terms with atomics in free order, so grad_x is held to the bound
+    tests/test_sparse_detector_gpu.py puts on stacked against single pairs."""
+    rng = np.random.default_rng(3741)
+    n0, n1, C, M, H = 37, 41, 16, 9, 5
+    N = n0 + n1
+    x = rng.normal(size=(N, C)).astype(np.float32)
+    sc = rng.random((N, 1)).astype(np.float32)
+    corr = cu(np.stack([rng.permutation(n0)[:M], rng.permutation(n1)[:M]], 1).astype(np.int64))
+    lens = cu(np.array([n0, n1], np.int32))
+    dk = rng.random((M, M)) * 0.3
+    dk = cu(np.minimum(dk, dk.T))
+    idx = np.concatenate([rng.integers(0, n0 + n0 // 3, size=(n0, H)), n0 + rng.integers(0, n1 + n1 // 3, size=(n1, H))])
+    idx[:n0][idx[:n0] >= n0] = N                                # about a quarter shadow entries, none across the clouds
+    idx[idx >= N] = N
+    idx[:, 0] = np.arange(N)
+    det = ops.DetectorRows(cu(idx.astype(np.int32)), training=True, lens=lens)
+    names = ("total", "desc", "det", "accuracy", "furthest_positive", "average_negative")
+    for single, stacked in ((ops.train_loss, ops.train_loss_pairs),
+                            (ops.train_contrastive_loss, ops.train_contrastive_loss_pairs)):
+        for w_desc, w_det in ((1.0, 1.0), (1.0, 0.5)):
+            for rows_form in (False, True):
+                res = []
+                for f, args in ((single, (corr, n0, dk)), (stacked, (corr.view(1, M, 2), lens, dk.view(1, M, M)))):
+                    tx, ts = cu(x).requires_grad_(True), cu(sc).requires_grad_(True)
+                    out = f(tx, det if rows_form else ts, *args, w_desc=w_desc, w_det=w_det)
+                    out[0].backward()
+                    res.append([out[0]] + [o.reshape(-1) for o in out[1:]] + [tx.grad, None if rows_form else ts.grad])
+                for name, u, v in zip(names, res[0], res[1]):
+                    assert torch.equal(u, v), (single.__name__, w_desc, w_det, rows_form, name)
+                if rows_form:
+                    want = res[0][6]
+                    assert float((res[1][6] - want).abs().max()) <= 1e-6 * float(want.abs().max()) + 1e-9
+                else:
+                    assert torch.equal(res[0][6], res[1][6]) and torch.equal(res[0][7], res[1][7])
+                assert float(res[0][6].abs().max()) > 0
+
+
 @pytest.mark.parametrize("ns,nq,cin", [(700, 500, 64), (700, 700, 512), (5000, 5000, 128), (4500, 1200, 32)])
 def test_epilogue_packed_supports_equal_the_packing_launch(ns, nq, cin):
     """ops.bias_act(..., pack_for=(s_pts, clear)) leaves the packed supports of the KPConv it feeds behind

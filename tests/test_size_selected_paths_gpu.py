@@ -2,7 +2,7 @@
 suite never takes -- each against the project's own oracle (oracle/ops_ref.py, utils.loss in f64, torch.optim,
 torch.nn.functional.batch_norm in f64):
 
-A. csrc/loss.hip  loss_fwd_kernel<false> / loss_bwd_kernel<false>: the one-workgroup circle + detector loss that runs
+A. csrc/loss.hip  loss_fwd_kernel / loss_bwd_kernel: the one-workgroup circle + detector loss that runs
    whenever cache_ok(M, C) = (M <= 128 && C <= 64) fails (every other test has M <= 128, C = 32: the tiled kernels).
 B. csrc/loss.hip  contrastive_fwd_kernel / contrastive_bwd_kernel past one 64-channel chunk (acc[1..3], a partly filled
    last chunk) and past two 64-row ballot rounds, one round carrying many hits.
@@ -115,8 +115,8 @@ def _assert_circle(shape, tol, min_gap=None):
 
 @pytest.mark.parametrize("m,c", [(129, 32), (200, 32), (64, 65), (2, 80)])
 def test_circle_det_loss_in_one_workgroup(m, c):
-    """ops.circle_det_loss forward + backward where cache_ok(M, C) fails: loss_fwd_kernel<false> and
-    loss_bwd_kernel<false>, one 1024-thread workgroup on the global buffers (distances in ``dists``, G in the
+    """ops.circle_det_loss forward + backward where cache_ok(M, C) fails: loss_fwd_kernel and
+    loss_bwd_kernel, one 1024-thread workgroup on the global buffers (distances in ``dists``, G in the
     workspace), against ops_ref.circle_loss + ops_ref.det_loss in f64 at test_circle_det_loss's tolerances.
     (129, 32): the first M past the tiled form.  (200, 32): M no multiple of 64, so the last round of line_stats has idle
     lanes.  (64, 65): the smallest C that leaves the tiled form, at a small M.  (2, 80): the smallest legal M -- 1020 of
@@ -125,7 +125,7 @@ def test_circle_det_loss_in_one_workgroup(m, c):
 
 
 def test_circle_det_loss_in_one_workgroup_at_the_largest_m():
-    """(M, C) = (1024, 32), kMaxM: every thread of loss_fwd_kernel<false> / loss_bwd_kernel<false> walks 1024 of the
+    """(M, C) = (1024, 32), kMaxM: every thread of loss_fwd_kernel / loss_bwd_kernel walks 1024 of the
     M * M entries, every wave 64 rows and 64 columns of 1024 entries, every thread of the backward 32 sums of 1024 terms.
     The sums are 8 x longer than at M = 128, so every bound is max(test_circle_det_loss's, 4 x the error of the f32
     oracle against the f64 oracle), see _max_with_factor_4; the test computes them.  Measured f32-vs-f64 oracle errors:
@@ -140,7 +140,7 @@ def test_circle_det_loss_in_one_workgroup_at_the_largest_m():
 
 def test_train_loss_with_weights_at_a_size_that_is_not_tiled():
     """ops.train_loss at M = 200 with (w_desc, w_det) = (1.0, 0.5): the `plain and weights != (1, 1)` route of
-    _TrainLossFn (total = dot(scalars[:2], gw), the backward hands both weighted gradients to loss_bwd_kernel<false>)
+    _TrainLossFn (total = dot(scalars[:2], gw), the backward hands both weighted gradients to loss_bwd_kernel)
     against the eager composition F.normalize + indexing + ops_ref in f64."""
     rng = np.random.default_rng(200)
     M, C, n0, n1 = 200, 32, 700, 650
