@@ -11,7 +11,7 @@
 // Frame f: a depth image H x W (uint16 raw units or f32 metres), intrinsics K = (fx, fy, cx, cy), M [3x4 row-major]
 // mapping the volume's frame into the camera, C [3x4] its inverse (camera into the volume's frame; the bounds only).
 //
-// Integration, per voxel (x, y, z), frames in order, from D = 0, w = 0 or from the stored values (the _into forms):
+// Integration, per voxel (x, y, z), frames in order, from D = 0, w = 0 or from the stored values (into != 0):
 //   p_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3]                      r = 0, 1, 2
 //   skip unless p_z > 0
 //   u = floorf(((fx p_x) / p_z + cx) + 0.5f), v likewise with fy, p_y, cy;  skip unless 0 <= u < W and 0 <= v < H
@@ -114,7 +114,7 @@ D3F_HD inline void integrate_frame(float x, float y, float z, const float* M, co
 // the frames [f0, f1) of a volume into the voxel at (x, y, z), continuing from the (D, w, c) given; images [F, H, W],
 // colours [F, H, W, kCc], M [F, 12], K [F, 4].  "From D = 0, w = 0, c = 0" is the caller passing zeros.  The running
 // mean is sequential over the frames, so the frames [f0, k) from zeros and then [k, f1) from their result give exactly
-// what [f0, f1) gives from zeros (the _into entry points)
+// what [f0, f1) gives from zeros (the entries' into != 0)
 template <int kCc, typename DepthT>
 D3F_HD inline void integrate_voxel(float x, float y, float z, int f0, int f1, const float* M, const float* K,
                                    const DepthT* images, const float* colours, int H, int W, float depth_scale,

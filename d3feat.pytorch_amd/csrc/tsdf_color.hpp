@@ -30,7 +30,7 @@
 //   a pixel off the voxel, the offsets do not average out (a mean of 0.1 pixel = 1.7 mm where the two pitches are
 //   6 : 5), and an RGB-D tracker finds that offset between a frame and the render of the model.
 // A non-finite colour value in any of the four taps propagates into the voxel's colour; it is a value, never an index.
-// Continuing (the _color_into entry points) starts integrate_voxel from the stored (D, w, c), so the frames [0, k) and
+// Continuing (into != 0 with channels > 0) starts integrate_voxel from the stored (D, w, c), so the frames [0, k) and
 // then [k, F) give the colour of one call bit for bit.  A slot of a sparse pool that does not exist, like a voxel of
 // an absent brick, is w = 0 with colour 0.
 //

@@ -1,7 +1,7 @@
 // TSDF integration: depth frames, and colour frames beside them, fused into a batch of dense volumes or into the
-// allocated bricks of sparse ones, from zero or continuing from what is stored (include/d3feat_hip.h: the sixteen
-// d3f_tsdf[_sparse]_integrate[_color][_into][_host]; the rule is integrate_voxel<kCc> of csrc/tsdf.hpp, the colour
-// csrc/tsdf_color.hpp, the bricks csrc/tsdf_sparse.hpp).
+// allocated bricks of sparse ones, from zero or continuing from what is stored (include/d3feat_hip.h: the four
+// d3f_tsdf[_sparse]_integrate[_host], colour by `channels`, continuing by `into`; the rule is integrate_voxel<kCc> of
+// csrc/tsdf.hpp, the colour csrc/tsdf_color.hpp, the bricks csrc/tsdf_sparse.hpp).
 //   One thread owns a cell of D / w / the colour array for ALL frames of its volume: the model is read never (kInto:
 //   once, the cell's stored values, from which the running mean continues) and written once with coalesced stores, no
 //   atomics, deterministic by construction.  The volume is uniform over the workgroup, so its frame range, the frame
@@ -56,7 +56,7 @@ __host__ __device__ inline bool cell_voxel(const Bricks& k, int v, int64_t first
 }
 
 // the argument checks, in the three steps of integrate() below.  `largest`: max_volume_voxels of the dense device
-// forms, which sizes their grid (the dense twins, which ignore theirs, pass total_voxels); the bricks of the sparse
+// form, which sizes its grid (the dense twin, which ignores its own, passes total_voxels); the bricks of the sparse
 inline bool model_ok(const Volumes& b, int64_t largest) {
   return batch_ok(b.V, b.total) && largest >= 0 && largest <= b.total && b.vol_start && b.origin && b.dims && b.voxel;
 }
@@ -88,7 +88,7 @@ inline dim3 launch_grid(const Volumes& b, int64_t largest) {
 inline dim3 launch_grid(const Bricks& k, int64_t) { return dim3((unsigned)k.B); }
 
 // ------------------------------------------------------------------------------------------------------- one cell
-// kInto: the cell's stored (D, w, c) come first and the frames continue from them (the _into entry points); without
+// kInto: the cell's stored (D, w, c) come first and the frames continue from them (the entries' into != 0); without
 // it they start from zero.  kCc > 0: colours [F, H, W, kCc] are fused into the cell's row of C_out (tsdf_color.hpp)
 template <typename DepthT, bool kInto, int kCc, typename Model>
 __host__ __device__ inline void fuse_cell(const Model& m, const Frames& fr, int v, int64_t first, int64_t off,
@@ -170,127 +170,79 @@ bool colour_ok(int channels, int F, const float* colours, const float* C) {
   return (channels == 1 || channels == 3) && (F == 0 || colours) && C;
 }
 
-// every entry point.  `coloured`: a _color form, which rejects channels other than 1 and 3 before anything else; the
-// others pass channels = 0.  An empty model is D3F_OK before D, w or the colour pointers are looked at.
 template <bool kHost, bool kInto, typename Model>
-int integrate(const Model& m, int64_t largest, const Frames& fr, int depth_is_f32, bool coloured, int channels,
-              const float* colours, float* D, float* w, float* C, void* stream) {
-  if (coloured && channels != 1 && channels != 3) return D3F_EINVAL;
+void fuse_depth(const Model& m, int64_t largest, const Frames& fr, int depth_is_f32, int channels,
+                const float* colours, float* D, float* w, float* C, hipStream_t stream) {
+  if (depth_is_f32)
+    fuse_channels<kHost, float, kInto>(m, largest, fr, channels, colours, D, w, C, stream);
+  else
+    fuse_channels<kHost, uint16_t, kInto>(m, largest, fr, channels, colours, D, w, C, stream);
+}
+
+// every entry point.  channels other than 0, 1 and 3 are rejected before anything else; an empty model is D3F_OK before
+// D, w or the colour pointers are looked at; `into` picks kInto, here and nowhere else
+template <bool kHost, typename Model>
+int integrate(const Model& m, int64_t largest, const Frames& fr, int depth_is_f32, int channels, const float* colours,
+              int into, float* D, float* w, float* C, void* stream) {
+  if (channels != 0 && channels != 1 && channels != 3) return D3F_EINVAL;
   if (!model_ok(m, largest) || !fr.trunc ||
       !frames_ok(fr.images, fr.F, fr.H, fr.W, fr.frame_start, fr.K, fr.M, fr.depth_scale, fr.depth_max))
     return D3F_EINVAL;
   if (cell_count(m) == 0 || largest == 0) return D3F_OK;
   if (!D || !w || !layout_ok<kHost>(m, largest) || !colour_ok(channels, fr.F, colours, C)) return D3F_EINVAL;
-  if (depth_is_f32)
-    fuse_channels<kHost, float, kInto>(m, largest, fr, channels, colours, D, w, C, (hipStream_t)stream);
+  if (into)
+    fuse_depth<kHost, true>(m, largest, fr, depth_is_f32, channels, colours, D, w, C, (hipStream_t)stream);
   else
-    fuse_channels<kHost, uint16_t, kInto>(m, largest, fr, channels, colours, D, w, C, (hipStream_t)stream);
+    fuse_depth<kHost, false>(m, largest, fr, depth_is_f32, channels, colours, D, w, C, (hipStream_t)stream);
   if constexpr (!kHost) D3F_LAUNCH_CHECK();
   return D3F_OK;
 }
 
-// the argument lists of the C ABI.  The dense twins take and ignore max_volume_voxels and stream
-template <bool kHost, bool kInto>
-int integrate_dense(const void* depth, bool coloured, const float* color, int channels, int depth_is_f32, int F, int H,
-                    int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
-                    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera,
-                    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
-                    float depth_max, float* D, float* w, float* Cv, void* stream) {
-  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  return integrate<kHost, kInto>(b, kHost ? total_voxels : max_volume_voxels, fr, depth_is_f32, coloured, channels,
-                                 color, D, w, Cv, stream);
-}
-
-template <bool kHost, bool kInto>
-int integrate_sparse(const void* depth, bool coloured, const float* color, int channels, int depth_is_f32, int F, int H,
-                     int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
-                     const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
-                     const int64_t* brick_start, const int32_t* brick_coord, int64_t bricks, float depth_scale,
-                     float depth_max, float* D, float* w, float* Cp, void* stream) {
-  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
-  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
-  return integrate<kHost, kInto>(k, bricks, fr, depth_is_f32, coloured, channels, color, D, w, Cp, stream);
-}
-
 }  // namespace
 
-// the parameters of the entry points as include/d3feat_hip.h declares them, and the same names as arguments
-#define D3F_DENSE_PARAMS                                                                                              \
-  int depth_is_f32, int F, int H, int W, const int32_t *frame_start, const int64_t *vol_start, int V,                 \
-      int64_t total_voxels, int64_t max_volume_voxels, const float *intrinsics, const float *volume_to_camera,        \
-      const float *origin, const int32_t *dims, const float *voxel, const float *trunc, float depth_scale,            \
-      float depth_max, float *D, float *w
-#define D3F_DENSE_ARGS                                                                                                \
-  depth_is_f32, F, H, W, frame_start, vol_start, V, total_voxels, max_volume_voxels, intrinsics, volume_to_camera,    \
-      origin, dims, voxel, trunc, depth_scale, depth_max, D, w
-#define D3F_SPARSE_PARAMS                                                                                             \
-  int depth_is_f32, int F, int H, int W, const int32_t *frame_start, int V, const float *intrinsics,                  \
-      const float *volume_to_camera, const float *origin, const int32_t *dims, const float *voxel,                    \
-      const float *trunc, const int64_t *brick_start, const int32_t *brick_coord, int64_t bricks, float depth_scale,  \
-      float depth_max, float *D, float *w
-#define D3F_SPARSE_ARGS                                                                                               \
-  depth_is_f32, F, H, W, frame_start, V, intrinsics, volume_to_camera, origin, dims, voxel, trunc, brick_start,       \
-      brick_coord, bricks, depth_scale, depth_max, D, w
-
+// the C ABI: a twin's argument list is its device form's; it ignores stream, the dense one max_volume_voxels too
 extern "C" {
 
-int d3f_tsdf_integrate(const void* depth, D3F_DENSE_PARAMS, void* stream) {
-  return integrate_dense<false, false>(depth, false, nullptr, 0, D3F_DENSE_ARGS, nullptr, stream);
-}
-int d3f_tsdf_integrate_host(const void* depth, D3F_DENSE_PARAMS, void*) {
-  return integrate_dense<true, false>(depth, false, nullptr, 0, D3F_DENSE_ARGS, nullptr, nullptr);
-}
-int d3f_tsdf_integrate_into(const void* depth, D3F_DENSE_PARAMS, void* stream) {
-  return integrate_dense<false, true>(depth, false, nullptr, 0, D3F_DENSE_ARGS, nullptr, stream);
-}
-int d3f_tsdf_integrate_into_host(const void* depth, D3F_DENSE_PARAMS, void*) {
-  return integrate_dense<true, true>(depth, false, nullptr, 0, D3F_DENSE_ARGS, nullptr, nullptr);
-}
-int d3f_tsdf_integrate_color(const void* depth, const float* color, int channels, D3F_DENSE_PARAMS, float* Cv,
-                             void* stream) {
-  return integrate_dense<false, false>(depth, true, color, channels, D3F_DENSE_ARGS, Cv, stream);
-}
-int d3f_tsdf_integrate_color_host(const void* depth, const float* color, int channels, D3F_DENSE_PARAMS, float* Cv,
-                                  void*) {
-  return integrate_dense<true, false>(depth, true, color, channels, D3F_DENSE_ARGS, Cv, nullptr);
-}
-int d3f_tsdf_integrate_color_into(const void* depth, const float* color, int channels, D3F_DENSE_PARAMS, float* Cv,
-                                  void* stream) {
-  return integrate_dense<false, true>(depth, true, color, channels, D3F_DENSE_ARGS, Cv, stream);
-}
-int d3f_tsdf_integrate_color_into_host(const void* depth, const float* color, int channels, D3F_DENSE_PARAMS,
-                                       float* Cv, void*) {
-  return integrate_dense<true, true>(depth, true, color, channels, D3F_DENSE_ARGS, Cv, nullptr);
+int d3f_tsdf_integrate(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
+                       const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+                       int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera,
+                       const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+                       float depth_scale, float depth_max, int into, float* D, float* w, float* Cv, void* stream) {
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  return integrate<false>(b, max_volume_voxels, fr, depth_is_f32, channels, color, into, D, w, Cv, stream);
 }
 
-int d3f_tsdf_sparse_integrate(const void* depth, D3F_SPARSE_PARAMS, void* stream) {
-  return integrate_sparse<false, false>(depth, false, nullptr, 0, D3F_SPARSE_ARGS, nullptr, stream);
+int d3f_tsdf_integrate_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
+                            const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t,
+                            const float* intrinsics, const float* volume_to_camera, const float* origin,
+                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
+                            float depth_max, int into, float* D, float* w, float* Cv, void*) {
+  const Volumes b = {vol_start, origin, dims, voxel, V, total_voxels};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  return integrate<true>(b, total_voxels, fr, depth_is_f32, channels, color, into, D, w, Cv, nullptr);
 }
-int d3f_tsdf_sparse_integrate_host(const void* depth, D3F_SPARSE_PARAMS) {
-  return integrate_sparse<true, false>(depth, false, nullptr, 0, D3F_SPARSE_ARGS, nullptr, nullptr);
+
+int d3f_tsdf_sparse_integrate(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+                              int W, const int32_t* frame_start, int V, const float* intrinsics,
+                              const float* volume_to_camera, const float* origin, const int32_t* dims,
+                              const float* voxel, const float* trunc, const int64_t* brick_start,
+                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                              int into, float* D, float* w, float* Cp, void* stream) {
+  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  return integrate<false>(k, bricks, fr, depth_is_f32, channels, color, into, D, w, Cp, stream);
 }
-int d3f_tsdf_sparse_integrate_into(const void* depth, D3F_SPARSE_PARAMS, void* stream) {
-  return integrate_sparse<false, true>(depth, false, nullptr, 0, D3F_SPARSE_ARGS, nullptr, stream);
-}
-int d3f_tsdf_sparse_integrate_into_host(const void* depth, D3F_SPARSE_PARAMS) {
-  return integrate_sparse<true, true>(depth, false, nullptr, 0, D3F_SPARSE_ARGS, nullptr, nullptr);
-}
-int d3f_tsdf_sparse_integrate_color(const void* depth, const float* color, int channels, D3F_SPARSE_PARAMS, float* Cp,
-                                    void* stream) {
-  return integrate_sparse<false, false>(depth, true, color, channels, D3F_SPARSE_ARGS, Cp, stream);
-}
-int d3f_tsdf_sparse_integrate_color_host(const void* depth, const float* color, int channels, D3F_SPARSE_PARAMS,
-                                         float* Cp) {
-  return integrate_sparse<true, false>(depth, true, color, channels, D3F_SPARSE_ARGS, Cp, nullptr);
-}
-int d3f_tsdf_sparse_integrate_color_into(const void* depth, const float* color, int channels, D3F_SPARSE_PARAMS,
-                                         float* Cp, void* stream) {
-  return integrate_sparse<false, true>(depth, true, color, channels, D3F_SPARSE_ARGS, Cp, stream);
-}
-int d3f_tsdf_sparse_integrate_color_into_host(const void* depth, const float* color, int channels, D3F_SPARSE_PARAMS,
-                                              float* Cp) {
-  return integrate_sparse<true, true>(depth, true, color, channels, D3F_SPARSE_ARGS, Cp, nullptr);
+
+int d3f_tsdf_sparse_integrate_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+                                   int W, const int32_t* frame_start, int V, const float* intrinsics,
+                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
+                                   const float* voxel, const float* trunc, const int64_t* brick_start,
+                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                                   int into, float* D, float* w, float* Cp, void*) {
+  const Bricks k = {nullptr, brick_start, nullptr, brick_coord, origin, dims, voxel, V, 0, bricks};
+  const Frames fr = {depth, frame_start, intrinsics, volume_to_camera, trunc, F, H, W, depth_scale, depth_max};
+  return integrate<true>(k, bricks, fr, depth_is_f32, channels, color, into, D, w, Cp, nullptr);
 }
 
 }  // extern "C"

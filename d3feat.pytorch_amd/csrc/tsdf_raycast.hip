@@ -1,5 +1,5 @@
 // Reading a fused TSDF model, dense or sparse (include/d3feat_hip.h: d3f_tsdf_raycast, d3f_tsdf_raycast_sparse,
-// d3f_tsdf_sample_color, d3f_tsdf_sample_color_sparse, each with its _color and _host forms).  The rules are
+// d3f_tsdf_sample_color, d3f_tsdf_sample_color_sparse, each with its _host twin).  The rules are
 // csrc/tsdf_raycast.hpp (the marching loop), csrc/tsdf_raycast_sparse.hpp (the sparse sampler it is instantiated for)
 // and csrc/tsdf_color.hpp (the colour at a point and behind a hit); here is what surrounds them, written once for
 // both kinds of model: make_sampler builds the Lattice of a volume of `Volumes` or the SparseLattice of one of `Bricks`.
@@ -13,7 +13,7 @@
 //   of 2 KB rows; a cell that straddles bricks looks all of them up first; an absent brick costs the table read alone,
 //   and the samples that stay inside it are skipped.  The sample loop leaves as soon as the ray has ended, and the box
 //   clip of the rule keeps it to the stretch of the ray that crosses the lattice.  Every pixel is written once, by its
-//   thread: depth, normals and, in the colour forms, the colour of the hit.
+//   thread: depth, normals and, with channels > 0, the colour of the hit.
 //   Point sampling colours what the extract and mesh kernels emit -- clouds and mesh vertices -- without touching
 //   those kernels.  One thread per point; point i belongs to the volume owner(point_start, V, i), as d3f_tsdf_extract
 //   lays the clouds out.  A thread makes the 8 weight loads and the 8 Cc colour loads of its cell together (the sparse
@@ -133,6 +133,11 @@ struct Views {              // device pointers on the device side, host pointers
   int clip, skip;               // skip: brick skipping, which the dense sampler has none of
 };
 
+Views views(const int32_t* view_volume, const float* K, const float* C, const float* step, int R, int H, int W,
+            float depth_min, float depth_max, float min_weight, int clip, int skip) {
+  return {view_volume, K, C, step, R, H, W, depth_min, depth_max, min_weight, clip, skip};
+}
+
 template <int kCc>
 struct Colour {             // the colour forms: what they read and write on top
   const float* Cv;              // [total, kCc] beside D and w, or the pool [B, 512, kCc]
@@ -228,18 +233,18 @@ int cast_views(const Model& m, const Views& vw, const float* D, const float* w, 
   return D3F_OK;
 }
 
-// every ray-cast entry; `coloured` false is a colourless form, whose Cv, channels and colour image are not looked at.
+// every ray-cast entry; channels = 0 is the colourless form, whose Cv and colour image are not looked at.
 // R = 0 is D3F_OK before the colour pointers are looked at; the twins check the tables before that.
 template <bool kHost, typename Model>
 int raycast(const Model& m, const Views& vw, const float* D, const float* w, const float* Cv, int channels,
-            bool coloured, float* depth, float* normals, float* color, void* stream) {
-  if (!model_ok(m) || !views_ok(vw, depth) || (vw.R > 0 && stored(m) > 0 && !(D && w)) ||
-      (coloured && channels != 1 && channels != 3) || (kHost && !host_model_ok(m)))
+            float* depth, float* normals, float* color, void* stream) {
+  if ((channels != 0 && channels != 1 && channels != 3) || !model_ok(m) || !views_ok(vw, depth) ||
+      (vw.R > 0 && stored(m) > 0 && !(D && w)) || (kHost && !host_model_ok(m)))
     return D3F_EINVAL;
   if (vw.R == 0) return D3F_OK;
-  if (coloured && (!color || (stored(m) > 0 && !Cv))) return D3F_EINVAL;
+  if (channels && (!color || (stored(m) > 0 && !Cv))) return D3F_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
-  if (!coloured) return cast_views<kHost, Model, 0>(m, vw, D, w, nullptr, depth, normals, nullptr, s);
+  if (channels == 0) return cast_views<kHost, Model, 0>(m, vw, D, w, nullptr, depth, normals, nullptr, s);
   if (channels == 1) return cast_views<kHost, Model, 1>(m, vw, D, w, Cv, depth, normals, color, s);
   return cast_views<kHost, Model, 3>(m, vw, D, w, Cv, depth, normals, color, s);
 }
@@ -317,101 +322,53 @@ int sample_color(const Model& m, const Points& p, const float* w, const float* C
 
 extern "C" {
 
-int d3f_tsdf_raycast(const float* D, const float* w, const int64_t* vol_start, const float* origin,
-                     const int32_t* dims, const float* voxel, int V, int64_t total_voxels, const int32_t* view_volume,
-                     int R, int H, int W, const float* intrinsics, const float* camera_to_volume, const float* step,
-                     float depth_min, float depth_max, float min_weight, int clip, float* depth, float* normals,
-                     void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0};
-  return raycast<false>(dense_model(vol_start, origin, dims, voxel, V, total_voxels), vw, D, w, nullptr, 0, false,
-                        depth, normals, nullptr, stream);
+int d3f_tsdf_raycast(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                     const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+                     const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                     const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                     float min_weight, int clip, float* depth, float* normals, float* color, void* stream) {
+  return raycast<false>(
+      dense_model(vol_start, origin, dims, voxel, V, total_voxels),
+      views(view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0), D, w,
+      Cv, channels, depth, normals, color, stream);
 }
 
-int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_start, const float* origin,
-                          const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+int d3f_tsdf_raycast_host(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                          const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                          float min_weight, int clip, float* depth, float* normals, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0};
-  return raycast<true>(dense_model(vol_start, origin, dims, voxel, V, total_voxels), vw, D, w, nullptr, 0, false,
-                       depth, normals, nullptr, stream);
+                          float min_weight, int clip, float* depth, float* normals, float* color, void* stream) {
+  return raycast<true>(
+      dense_model(vol_start, origin, dims, voxel, V, total_voxels),
+      views(view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0), D, w,
+      Cv, channels, depth, normals, color, stream);
 }
 
-int d3f_tsdf_raycast_color(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
-                           const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
-                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                           float min_weight, int clip, float* depth, float* normals, float* color, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0};
-  return raycast<false>(dense_model(vol_start, origin, dims, voxel, V, total_voxels), vw, D, w, Cv, channels, true,
-                        depth, normals, color, stream);
-}
-
-int d3f_tsdf_raycast_color_host(const float* D, const float* w, const float* Cv, int channels,
-                                const int64_t* vol_start, const float* origin, const int32_t* dims, const float* voxel,
-                                int V, int64_t total_voxels, const int32_t* view_volume, int R, int H, int W,
-                                const float* intrinsics, const float* camera_to_volume, const float* step,
-                                float depth_min, float depth_max, float min_weight, int clip, float* depth,
-                                float* normals, float* color, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, 0};
-  return raycast<true>(dense_model(vol_start, origin, dims, voxel, V, total_voxels), vw, D, w, Cv, channels, true,
-                       depth, normals, color, stream);
-}
-
-int d3f_tsdf_raycast_sparse(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
-                            const int32_t* brick_index, const float* origin, const int32_t* dims, const float* voxel,
-                            int V, int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H,
-                            int W, const float* intrinsics, const float* camera_to_volume, const float* step,
+int d3f_tsdf_raycast_sparse(const float* D, const float* w, const float* Cp, int channels,
+                            const int64_t* lattice_start, const int64_t* brick_start, const int32_t* brick_index,
+                            const float* origin, const int32_t* dims, const float* voxel, int V,
+                            int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H, int W,
+                            const float* intrinsics, const float* camera_to_volume, const float* step,
                             float depth_min, float depth_max, float min_weight, int clip, int skip, float* depth,
-                            float* normals, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
-                    skip};
+                            float* normals, float* color, void* stream) {
   return raycast<false>(
-      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks), vw, D, w,
-      nullptr, 0, false, depth, normals, nullptr, stream);
+      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks),
+      views(view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, skip), D,
+      w, Cp, channels, depth, normals, color, stream);
 }
 
-int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* lattice_start,
-                                 const int64_t* brick_start, const int32_t* brick_index, const float* origin,
-                                 const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const float* Cp, int channels,
+                                 const int64_t* lattice_start, const int64_t* brick_start,
+                                 const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                 const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                                 float min_weight, int clip, int skip, float* depth, float* normals, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
-                    skip};
+                                 float min_weight, int clip, int skip, float* depth, float* normals, float* color,
+                                 void* stream) {
   return raycast<true>(
-      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks), vw, D, w,
-      nullptr, 0, false, depth, normals, nullptr, stream);
-}
-
-int d3f_tsdf_raycast_sparse_color(const float* D, const float* w, const float* Cp, int channels,
-                                  const int64_t* lattice_start, const int64_t* brick_start,
-                                  const int32_t* brick_index, const float* origin, const int32_t* dims,
-                                  const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
-                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                                  float min_weight, int clip, int skip, float* depth, float* normals, float* color,
-                                  void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
-                    skip};
-  return raycast<false>(
-      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks), vw, D, w,
-      Cp, channels, true, depth, normals, color, stream);
-}
-
-int d3f_tsdf_raycast_sparse_color_host(const float* D, const float* w, const float* Cp, int channels,
-                                       const int64_t* lattice_start, const int64_t* brick_start,
-                                       const int32_t* brick_index, const float* origin, const int32_t* dims,
-                                       const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
-                                       const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                                       const float* camera_to_volume, const float* step, float depth_min,
-                                       float depth_max, float min_weight, int clip, int skip, float* depth,
-                                       float* normals, float* color, void* stream) {
-  const Views vw = {view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip,
-                    skip};
-  return raycast<true>(
-      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks), vw, D, w,
-      Cp, channels, true, depth, normals, color, stream);
+      sparse_model(lattice_start, brick_start, brick_index, origin, dims, voxel, V, lattice_bricks, bricks),
+      views(view_volume, intrinsics, camera_to_volume, step, R, H, W, depth_min, depth_max, min_weight, clip, skip), D,
+      w, Cp, channels, depth, normals, color, stream);
 }
 
 int d3f_tsdf_sample_color(const float* Cv, const float* w, int channels, const int64_t* vol_start, const float* origin,

@@ -1,7 +1,7 @@
 // Ray-casting a sparse TSDF volume, growing its bricks and continuing its integration (tsdf_raycast.hip:
-// d3f_tsdf_raycast_sparse and its host twin; tsdf_integrate.hip: d3f_tsdf_sparse_integrate_into).  Stated in the terms of
-// tsdf_raycast.hpp and tsdf_sparse.hpp, which it includes: everything here is __host__ __device__ and reads no state,
-// all arithmetic is f32 in the order written there, and ops.tsdf_raycast_sparse_numpy restates it.
+// d3f_tsdf_raycast_sparse and its host twin; tsdf_integrate.hip: d3f_tsdf_sparse_integrate, into != 0).  Stated in the
+// terms of tsdf_raycast.hpp and tsdf_sparse.hpp, which it includes: everything here is __host__ __device__ and reads
+// no state, all arithmetic is f32 in the order written there, and ops.tsdf_raycast_sparse_numpy restates it.
 //
 // The rule is cast_ray of tsdf_raycast.hpp unchanged -- the same text, instantiated for another sampler -- with ONE
 // thing replaced: where the D and w of a cell's corner voxel come from.
@@ -43,10 +43,10 @@
 // late holds only the frames integrated after it appeared.  Where earlier frames saw that space as free (t = 1, which
 // the dense volume would have averaged in) it is not the dense value; where they did not see it at all it is.
 //
-// Continuing an integration (d3f_tsdf_sparse_integrate_into): every existing slot of a row whose volume owns a frame
-// in the call continues integrate_voxel_into from its stored (D, w); the rows of a volume without a frame, and the
-// slots beyond dims, are left alone.  For fixed tables the frames [0, k) and then [k, F) into the result give the pool
-// of one call bit for bit.
+// Continuing an integration (d3f_tsdf_sparse_integrate, into != 0): every existing slot of a row whose volume owns a
+// frame in the call continues integrate_voxel_into from its stored (D, w); the rows of a volume without a frame, and
+// the slots beyond dims, are left alone.  For fixed tables the frames [0, k) and then [k, F) into the result give
+// the pool of one call bit for bit.
 #pragma once
 #include "tsdf_raycast.hpp"
 #include "tsdf_sparse.hpp"

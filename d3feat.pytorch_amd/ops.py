@@ -3485,9 +3485,9 @@ def _tsdf_into(into, total, device, channels=0, what="voxels"):
 
 def _tsdf_integrate(host, device, depth, frame_start, intrinsics, volume_to_camera, volumes, trunc, depth_scale,
                     depth_max, into, color):
-    """Every integrate form, d3f_tsdf[_sparse]_integrate[_color][_into][_host].  ``volumes``: ``(origin, dims, voxel)``
-    of dense volumes, or a ``SparseVolumes``; what depends on which is the tables in the argument list and the shape
-    of the outputs."""
+    """Every integrate form: d3f_tsdf[_sparse]_integrate[_host], its ``channels`` and its ``into``.  ``volumes``:
+    ``(origin, dims, voxel)`` of dense volumes, or a ``SparseVolumes``; what depends on which is the tables in the
+    argument list and the shape of the outputs."""
     d, fs, K, M = _tsdf_frames(depth, frame_start, intrinsics, volume_to_camera)
     V = fs.size - 1
     sparse = isinstance(volumes, SparseVolumes)
@@ -3515,14 +3515,12 @@ def _tsdf_integrate(host, device, depth, frame_start, intrinsics, volume_to_came
     else:
         D, w, Cv = (_tsdf_into(into, cells, device, Cc, what) + (None,))[:3]
     ptr = _p if cells else (lambda t: None)
-    name = ("d3f_tsdf" + ("_sparse" if sparse else "") + "_integrate" + ("_color" if Cc else "") +
-            ("" if into is None else "_into") + ("_host" if host else ""))
-    tc = _on(device, c)[0] if Cc else None
-    args = ((_p(td),) + ((_p(tc), Cc) if Cc else ()) +
-            (int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs)) + head +
+    name = "d3f_tsdf" + ("_sparse" if sparse else "") + "_integrate" + ("_host" if host else "")
+    tc = _on(device, c)[0] if Cc else None                     # Cc = 0: null colour pointers, which are not looked at
+    args = ((_p(td), _p(tc), Cc, int(d.dtype != np.uint16), d.shape[0], d.shape[1], d.shape[2], _p(tfs)) + head +
             (_p(tK), _p(tM), _p(to), _p(tn), _p(tvx), _p(ttr)) + tail +
-            (float(depth_scale), float(depth_max), ptr(D), ptr(w)) + ((ptr(Cv),) if Cc else ()) +
-            (() if sparse and host else (None if host else _stream(),)))     # the sparse twins take no stream
+            (float(depth_scale), float(depth_max), int(into is not None), ptr(D), ptr(w), ptr(Cv),
+             None if host else _stream()))
     _native.check(getattr(_native.lib(), name)(*args), name)
     return (D, w) + (() if sparse else (tvs,)) + ((Cv,) if Cc else ())
 
@@ -3539,16 +3537,16 @@ def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dim
     a voxel for all frames: written once, no atomics, bit-identical from run to run and to the host twin.
 
     ``into=(D, w)``: device tensors of an earlier call over the same ``origin`` / ``dims`` / ``voxel`` / ``trunc``; the
-    frames are integrated into them IN PLACE (d3f_tsdf_integrate_into) and the same tensors are returned.  The running
-    mean is sequential over frames, so the frames [0, k) and then [k, F) ``into`` the result give the volume of one call
-    over [0, F) bit for bit.  A volume that owns no frame in the call keeps its values.
+    frames are integrated into them IN PLACE (d3f_tsdf_integrate, into = 1) and the same tensors are returned.  The
+    running mean is sequential over frames, so the frames [0, k) and then [k, F) ``into`` the result give the volume of
+    one call over [0, F) bit for bit.  A volume that owns no frame in the call keeps its values.
 
     ``color=frames`` (what ``tsdf_color_frames`` takes: uint8 RGB gives 3 channels, uint8 grey or f32 [F,H,W] one)
-    fuses the colour beside D and w (d3f_tsdf_integrate_color; the rule is csrc/tsdf_color.hpp) and returns ``(D, w,
-    vol_start, Cv f32 [total, Cc])``.  There is ONE weight: on exactly the frames that update a voxel's D and w, with
-    the w from before the increment, ``c = (c w + c_pixel) / (w + 1)`` per channel, ``c_pixel`` read bilinearly over the
-    2 x 2 pixels around the voxel's projection (the depth is read at the nearest of them); D and w are the colourless
-    call's bit for bit.  A non-finite colour value propagates into the voxels that have it among their four.  ``into=(D, w, Cv)`` continues all three."""
+    fuses the colour beside D and w (d3f_tsdf_integrate, channels = Cc; the rule is csrc/tsdf_color.hpp) and returns
+    ``(D, w, vol_start, Cv f32 [total, Cc])``.  There is ONE weight: on exactly the frames that update a voxel's D and
+    w, with the w from before the increment, ``c = (c w + c_pixel) / (w + 1)`` per channel, ``c_pixel`` read bilinearly
+    over the 2 x 2 pixels around the voxel's projection (the depth is read at the nearest of them); D and w are the
+    colourless call's bit for bit.  A non-finite colour value propagates into the voxels that have it among their four.  ``into=(D, w, Cv)`` continues all three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate"):
         return _tsdf_integrate(False, dev, depth, frame_start, intrinsics, volume_to_camera, (origin, dims, voxel),
@@ -3557,8 +3555,8 @@ def tsdf_integrate(depth, frame_start, intrinsics, volume_to_camera, origin, dim
 
 def tsdf_integrate_host(depth, frame_start, intrinsics, volume_to_camera, origin, dims, voxel, trunc,
                         depth_scale=1000.0, depth_max=TSDF_DEPTH_MAX, into=None, color=None):
-    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host / d3f_tsdf_integrate_into_host and their _color
-    forms): CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
+    """The host twin of ``tsdf_integrate`` (d3f_tsdf_integrate_host): CPU tensors out (``into``: CPU tensors, written
+    in place), no GPU call."""
     return _tsdf_integrate(True, torch.device("cpu"), depth, frame_start, intrinsics, volume_to_camera,
                            (origin, dims, voxel), trunc, depth_scale, depth_max, into, color)
 
@@ -3933,13 +3931,14 @@ def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, 
     bit; a slot beyond ``dims`` holds 0.  The frame arguments and ``trunc`` are those of ``tsdf_integrate``.
 
     ``into=(D, w)``: the device pool of an earlier call over the same ``sv`` and ``trunc``; the frames are integrated
-    into it IN PLACE (d3f_tsdf_sparse_integrate_into; csrc/tsdf_raycast_sparse.hpp) and the same tensors are returned.
-    The frames [0, k) and then [k, F) ``into`` the result give the pool of one call over [0, F) bit for bit; the rows of
-    a volume that owns no frame in the call keep their values.
+    into it IN PLACE (d3f_tsdf_sparse_integrate, into = 1; csrc/tsdf_raycast_sparse.hpp) and the same tensors are
+    returned.  The frames [0, k) and then [k, F) ``into`` the result give the pool of one call over [0, F) bit for bit;
+    the rows of a volume that owns no frame in the call keep their values.
 
     ``color=frames`` as for ``tsdf_integrate``: the colour pool ``Cp f32 [B,512,Cc]`` is fused beside D and w
-    (d3f_tsdf_sparse_integrate_color; csrc/tsdf_color.hpp) and ``(D, w, Cp)`` is returned; every slot inside the lattice
-    holds the dense ``Cv`` of that voxel bit for bit, every other slot 0.  ``into=(D, w, Cp)`` continues all three."""
+    (d3f_tsdf_sparse_integrate, channels = Cc; csrc/tsdf_color.hpp) and ``(D, w, Cp)`` is returned; every slot inside
+    the lattice holds the dense ``Cv`` of that voxel bit for bit, every other slot 0.  ``into=(D, w, Cp)`` continues all
+    three."""
     dev = _tsdf_device()
     with _region("tsdf_integrate_sparse"):
         return _tsdf_integrate(False, dev, depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale,
@@ -3948,7 +3947,7 @@ def tsdf_integrate_sparse(depth, frame_start, intrinsics, volume_to_camera, sv, 
 
 def tsdf_integrate_sparse_host(depth, frame_start, intrinsics, volume_to_camera, sv, trunc, depth_scale=1000.0,
                                depth_max=TSDF_DEPTH_MAX, into=None, color=None):
-    """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host / d3f_tsdf_sparse_integrate_into_host):
+    """The host twin of ``tsdf_integrate_sparse`` (d3f_tsdf_sparse_integrate_host):
     CPU tensors out (``into``: CPU tensors, written in place), no GPU call."""
     return _tsdf_integrate(True, torch.device("cpu"), depth, frame_start, intrinsics, volume_to_camera, sv, trunc,
                            depth_scale, depth_max, into, color)
@@ -4732,12 +4731,12 @@ def _tsdf_raycast(host, device, model, trunc, intrinsics, camera_to_volume, heig
         tables, _held = model.tables()
         tvv, tK, tC, tst = _on(device, vv, K, C, st)
         ptr = _p if model.stored else (lambda t: None)
-        name = "d3f_tsdf_raycast" + model.stem + ("_color" if Cc else "") + ("_host" if host else "")
-        args = ((ptr(D), ptr(w)) + ((ptr(Cv), Cc) if Cc else ()) + tables +
+        name = "d3f_tsdf_raycast" + model.stem + ("_host" if host else "")
+        args = ((ptr(D), ptr(w), ptr(Cv), Cc) + tables +         # Cc = 0: null colour pointers, which are not looked at
                 (_p(tvv), R, H, W, _p(tK), _p(tC), _p(tst), float(depth_min), float(depth_max), float(min_weight),
-                 int(bool(clip))) + (() if skip is None else (int(bool(skip)),)) + (_p(depth), _p(nrm)) +
-                ((_p(col),) if Cc else ()))
-        _native.check(getattr(_native.lib(), name)(*(args + (None if host else _stream(),))), name)
+                 int(bool(clip))) + (() if skip is None else (int(bool(skip)),)) +
+                (_p(depth), _p(nrm), _p(col), None if host else _stream()))
+        _native.check(getattr(_native.lib(), name)(*args), name)
     out = (depth,) + ((nrm,) if normals else ()) + ((col,) if Cc else ())
     return out if len(out) > 1 else depth
 
@@ -4766,7 +4765,7 @@ def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera
     tensors without a launch.
 
     ``color=Cv`` (the colour volume [total, Cc] of ``tsdf_integrate(color=)``, a device tensor) appends the colour
-    image f32 [R,H,W,Cc] to whatever is returned (d3f_tsdf_raycast_color; csrc/tsdf_color.hpp): at a hit the
+    image f32 [R,H,W,Cc] to whatever is returned (d3f_tsdf_raycast, channels = Cc; csrc/tsdf_color.hpp): at a hit the
     trilinear mean of the colours of the hit cell's corners with ``w >= min_weight``, renormalised over those corners
     (so a hit in a partly observed cell still has a colour); NaN in every channel where depth is 0 -- NaN, not 0, so
     the render goes into ``rgbd_pyramid`` as f32 intensity and the tracker's finiteness test drops those pixels.
@@ -4781,7 +4780,7 @@ def tsdf_raycast(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera
 def tsdf_raycast_host(D, w, vol_start, origin, dims, voxel, trunc, intrinsics, camera_to_volume, height, width,
                       view_volume=None, step=None, depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX,
                       min_weight=1.0, normals=False, clip=True, color=None):
-    """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host / d3f_tsdf_raycast_color_host): CPU tensors (or arrays)
+    """The host twin of ``tsdf_raycast`` (d3f_tsdf_raycast_host): CPU tensors (or arrays)
     in, CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
     model = _dense_model(True, cpu, (("D", D), ("w", w), ("color", color)), vol_start, origin, dims, voxel)
@@ -5087,8 +5086,8 @@ def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, w
     ``tsdf_raycast_sparse_numpy``.  R = 0 returns empty tensors without a launch; B = 0 gives images of zeros.
 
     ``color=Cp`` (the colour pool [B,512,Cc] of ``tsdf_integrate_sparse(color=)``) appends the colour image f32
-    [R,H,W,Cc] (d3f_tsdf_raycast_sparse_color), NaN where depth is 0: ``tsdf_raycast(color=)`` of the densified pool bit
-    for bit, a corner in an absent brick being w = 0 with colour 0."""
+    [R,H,W,Cc] (d3f_tsdf_raycast_sparse, channels = Cc), NaN where depth is 0: ``tsdf_raycast(color=)`` of the densified
+    pool bit for bit, a corner in an absent brick being w = 0 with colour 0."""
     dev = _tsdf_device()
     with _region("tsdf_raycast_sparse"):
         model = _sparse_model(False, dev, (("D", D), ("w", w), ("color", color)), sv)
@@ -5099,7 +5098,7 @@ def tsdf_raycast_sparse(D, w, sv, trunc, intrinsics, camera_to_volume, height, w
 def tsdf_raycast_sparse_host(D, w, sv, trunc, intrinsics, camera_to_volume, height, width, view_volume=None, step=None,
                              depth_min=RAYCAST_DEPTH_MIN, depth_max=TSDF_DEPTH_MAX, min_weight=1.0, normals=False,
                              clip=True, skip=True, color=None):
-    """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host / _color_host): CPU tensors (or arrays)
+    """The host twin of ``tsdf_raycast_sparse`` (d3f_tsdf_raycast_sparse_host): CPU tensors (or arrays)
     in, CPU tensors out, no GPU call."""
     cpu = torch.device("cpu")
     model = _sparse_model(True, cpu, (("D", D), ("w", w), ("color", color)), sv)

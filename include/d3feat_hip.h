@@ -1136,6 +1136,21 @@ int d3f_pose_graph_edge_host(const double* Pi_host, const double* Pj_host, const
  *   max_volume_voxels: a host bound on the voxels of one volume (the launch is blocks of the largest volume x V, the
  *   volume being the grid's second index: uniform, so its frames' matrices come through scalar loads); voxels of a
  *   volume beyond it are not written.
+ * The rules of the eight entries d3f_tsdf[_sparse]_integrate[_host] and d3f_tsdf_raycast[_sparse][_host]:
+ *   channels is 0, 1 or 3; anything else is D3F_EINVAL, before anything else is looked at.  channels = 0 is the
+ *     colourless form: color, Cv / Cp and the ray-cast's color image are not looked at and may be null.  With 1 or 3
+ *     ("Colour in TSDF volumes" below) integrate needs Cv / Cp, and color when F > 0; a ray-cast with R > 0 needs the
+ *     color image, and Cv / Cp when something is stored (total_voxels > 0, bricks > 0).
+ *   into != 0 continues the running mean from the stored D, w (and Cv / Cp when channels > 0), which every cell's
+ *     thread reads first; into = 0 starts from zero.  The mean is sequential over frames, so the frames [0, k) and
+ *     then, into the result, [k, F) give the volume of one call over [0, F) bit for bit (sparse: for fixed tables).  A
+ *     volume that owns no frame in an into call keeps its values, and so do a brick's slots beyond dims.
+ *   A twin's parameter list is its device form's: it takes host pointers, makes no GPU call and ignores stream, the
+ *     dense integrate twin max_volume_voxels too.
+ *   An empty model (total_voxels = 0, max_volume_voxels = 0, bricks = 0) is D3F_OK before D, w and the colour pointers
+ *     are looked at; R = 0 is D3F_OK before the colour pointers are looked at.
+ *   Dense and sparse, all of integrate is one kernel body and one host function in csrc/tsdf_integrate.hip, all of
+ *   ray-cast one of each in csrc/tsdf_raycast.hip.
  * d3f_tsdf_extract: count per block of voxels, exclusive scan, emit at block offset + in-block rank: points
  *   [capacity, 3] in the order volume, lattice index of the lower voxel, axis; point_start int64 [V+1].  A point at
  *   or beyond `capacity` is not written and ORs D3F_TSDF_ST_OVERFLOW into *status (int32, zeroed by the caller);
@@ -1153,30 +1168,16 @@ int d3f_tsdf_bounds(const void* depth, int depth_is_f32, int F, int H, int W, co
 int d3f_tsdf_bounds_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start, int V,
                          const float* intrinsics, const float* camera_to_volume, float depth_scale, float depth_max,
                          float* bounds, void* stream);
-int d3f_tsdf_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                       const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                       const float* intrinsics, const float* volume_to_camera, const float* origin,
-                       const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max,
-                       float* D, float* w, void* stream);
-int d3f_tsdf_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                            const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                            const float* intrinsics, const float* volume_to_camera, const float* origin,
-                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
-                            float depth_max, float* D, float* w, void* stream);
-/* d3f_tsdf_integrate_into: the same kernel body, but every voxel's thread first reads the (D, w) stored in the volume
- *   and continues the running mean from it (tsdf.hpp: integrate_voxel).  The mean is sequential over frames, so
- *   integrating the frames [0, k) and then [k, F) into the result gives the volume of one call over [0, F) bit for
- *   bit.  A volume that owns no frame in the call keeps its values. */
-int d3f_tsdf_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                            const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                            const float* intrinsics, const float* volume_to_camera, const float* origin,
-                            const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
-                            float depth_max, float* D, float* w, void* stream);
-int d3f_tsdf_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                                 const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-                                 const float* intrinsics, const float* volume_to_camera, const float* origin,
-                                 const int32_t* dims, const float* voxel, const float* trunc, float depth_scale,
-                                 float depth_max, float* D, float* w, void* stream);
+int d3f_tsdf_integrate(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
+                       const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+                       int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera,
+                       const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+                       float depth_scale, float depth_max, int into, float* D, float* w, float* Cv, void* stream);
+int d3f_tsdf_integrate_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
+                            const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
+                            int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera,
+                            const float* origin, const int32_t* dims, const float* voxel, const float* trunc,
+                            float depth_scale, float depth_max, int into, float* D, float* w, float* Cv, void* stream);
 size_t d3f_tsdf_extract_ws_bytes(int64_t total_voxels);
 int d3f_tsdf_extract_count(const float* D, const float* w, const int64_t* vol_start, const int32_t* dims, int V,
                            int64_t total_voxels, float min_weight, int64_t* point_start, void* ws, size_t ws_bytes,
@@ -1206,7 +1207,8 @@ int d3f_tsdf_extract_host(const float* D, const float* w, const int64_t* vol_sta
  *   (brick_start[V] = the number of allocated bricks, the one value a caller reads back) and brick_coord, which must
  *   hold lattice_bricks rows (the bound known before the read-back); the rows from brick_start[V] on are not written.
  * d3f_tsdf_sparse_integrate: one workgroup per pool row, written once by the threads that own its slots for all frames
- *   of the row's volume: no atomics, nothing read back; every slot is d3f_tsdf_integrate's voxel bit for bit.
+ *   of the row's volume: no atomics, nothing read back; every slot is d3f_tsdf_integrate's voxel bit for bit.  color,
+ *   channels and into follow the rules stated there; a slot beyond dims holds colour 0 beside D = 0, w = 0.
  * d3f_tsdf_sparse_extract: count per block of 256 slots, exclusive scan, emit, as d3f_tsdf_extract; the +1 neighbour
  *   across a brick face is found through brick_index, an absent brick being an invalid neighbour.  points
  *   [capacity, 3] in the order volume, brick in lattice order, slot, axis: d3f_tsdf_extract's rows bit for bit, as a
@@ -1231,33 +1233,18 @@ int d3f_tsdf_sparse_index(const int32_t* flags, const int64_t* lattice_start, co
 int d3f_tsdf_sparse_index_host(const int32_t* flags, const int64_t* lattice_start, const int32_t* dims, int V,
                                int64_t lattice_bricks, int32_t* brick_index, int32_t* brick_coord,
                                int64_t* brick_start);
-int d3f_tsdf_sparse_integrate(const void* depth, int depth_is_f32, int F, int H, int W, const int32_t* frame_start,
-                              int V, const float* intrinsics, const float* volume_to_camera, const float* origin,
-                              const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D,
-                              float* w, void* stream);
-int d3f_tsdf_sparse_integrate_host(const void* depth, int depth_is_f32, int F, int H, int W,
-                                   const int32_t* frame_start, int V, const float* intrinsics,
+int d3f_tsdf_sparse_integrate(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+                              int W, const int32_t* frame_start, int V, const float* intrinsics,
+                              const float* volume_to_camera, const float* origin, const int32_t* dims,
+                              const float* voxel, const float* trunc, const int64_t* brick_start,
+                              const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
+                              int into, float* D, float* w, float* Cp, void* stream);
+int d3f_tsdf_sparse_integrate_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
+                                   int W, const int32_t* frame_start, int V, const float* intrinsics,
                                    const float* volume_to_camera, const float* origin, const int32_t* dims,
                                    const float* voxel, const float* trunc, const int64_t* brick_start,
                                    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                   float* D, float* w);
-/* d3f_tsdf_sparse_integrate_into: the same kernel body, but every slot's thread first reads the (D, w) stored in the
- *   pool and continues the running mean from it (csrc/tsdf_raycast_sparse.hpp).  For fixed tables the frames [0, k) and
- *   then [k, F) into the result give the pool of one call over [0, F) bit for bit.  The rows of a volume that owns no
- *   frame in the call, and the slots beyond dims, keep their values. */
-int d3f_tsdf_sparse_integrate_into(const void* depth, int depth_is_f32, int F, int H, int W,
-                                   const int32_t* frame_start, int V, const float* intrinsics,
-                                   const float* volume_to_camera, const float* origin, const int32_t* dims,
-                                   const float* voxel, const float* trunc, const int64_t* brick_start,
-                                   const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                   float* D, float* w, void* stream);
-int d3f_tsdf_sparse_integrate_into_host(const void* depth, int depth_is_f32, int F, int H, int W,
-                                        const int32_t* frame_start, int V, const float* intrinsics,
-                                        const float* volume_to_camera, const float* origin, const int32_t* dims,
-                                        const float* voxel, const float* trunc, const int64_t* brick_start,
-                                        const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max,
-                                        float* D, float* w);
+                                   int into, float* D, float* w, float* Cp, void* stream);
 size_t d3f_tsdf_sparse_extract_ws_bytes(int64_t bricks);
 int d3f_tsdf_sparse_extract_count(const float* D, const float* w, const int64_t* lattice_start,
                                   const int64_t* brick_start, const int32_t* brick_index, const int32_t* brick_coord,
@@ -1362,23 +1349,25 @@ int d3f_tsdf_sparse_mesh_host(const float* D, const float* w, const int64_t* lat
  * when all 8 corners of its cell have w >= min_weight; a valid positive sample followed by a valid non-positive one is
  * a hit at the interpolated zero, a valid negative sample not preceded by a valid positive one ends the ray without
  * one.  depth f32 [R, H, W] in metres, 0 without a hit; normals (may be null) f32 [R, H, W, 3] in the camera frame,
- * towards positive D, zeros where there is no hit or a gradient sample is invalid.  clip != 0 cuts every ray's sample
- * range to the lattice's box (widened: the result is the same bit for bit; clip = 0 is the switch that proves it).
- * A step that is not > 0 or gives more than D3F_RAYCAST_MAX_SAMPLES samples casts nothing.  0 <= R <= 65535, H W <=
- * 2^30, 0 <= depth_min <= depth_max.  One thread per ray, a wave per 8 x 8 pixels, all views in one launch; no atomics,
- * nothing read back, a view's image bit-identical alone, in any batch and from run to run, and to the host twin.
+ * towards positive D, zeros where there is no hit or a gradient sample is invalid; Cv, channels and the color image
+ * [R, H, W, channels] by the rules stated with d3f_tsdf_integrate and "Colour in TSDF volumes" below.  clip != 0 cuts
+ * every ray's sample range to the lattice's box (widened: the result is the same bit for bit; clip = 0 is the switch
+ * that proves it).  A step that is not > 0 or gives more than D3F_RAYCAST_MAX_SAMPLES samples casts nothing.
+ * 0 <= R <= 65535, H W <= 2^30, 0 <= depth_min <= depth_max.  One thread per ray, a wave per 8 x 8 pixels, all views in
+ * one launch; no atomics, nothing read back, a view's image bit-identical alone, in any batch and from run to run, and
+ * to the host twin.
  * ---------------------------------------------------------------------------------------------- */
 #define D3F_RAYCAST_MAX_SAMPLES 65536
-int d3f_tsdf_raycast(const float* D, const float* w, const int64_t* vol_start, const float* origin,
-                     const int32_t* dims, const float* voxel, int V, int64_t total_voxels, const int32_t* view_volume,
-                     int R, int H, int W, const float* intrinsics, const float* camera_to_volume, const float* step,
-                     float depth_min, float depth_max, float min_weight, int clip, float* depth, float* normals,
-                     void* stream);
-int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_start, const float* origin,
-                          const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+int d3f_tsdf_raycast(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                     const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
+                     const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
+                     const float* camera_to_volume, const float* step, float depth_min, float depth_max,
+                     float min_weight, int clip, float* depth, float* normals, float* color, void* stream);
+int d3f_tsdf_raycast_host(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
+                          const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                          float min_weight, int clip, float* depth, float* normals, void* stream);
+                          float min_weight, int clip, float* depth, float* normals, float* color, void* stream);
 /* d3f_tsdf_raycast_sparse: the same render of V SPARSE volumes (the tables and the pool of the sparse section above;
  *   csrc/tsdf_raycast_sparse.hpp states the rule): cast_ray unchanged, a corner voxel's D and w read from its brick's
  *   pool row, D = 0, w = 0 where the brick is absent -- by definition d3f_tsdf_raycast of the densified pool, bit for
@@ -1387,104 +1376,36 @@ int d3f_tsdf_raycast_host(const float* D, const float* w, const int64_t* vol_sta
  *   result is the same bit for bit, skip = 0 is the switch that proves it).  Every index read from the tables is
  *   bounded before use: tables that do not fit give an unspecified image, and nothing outside brick_index
  *   [lattice_bricks] and the pool is read.  The other arguments, limits and guarantees are d3f_tsdf_raycast's. */
-int d3f_tsdf_raycast_sparse(const float* D, const float* w, const int64_t* lattice_start, const int64_t* brick_start,
-                            const int32_t* brick_index, const float* origin, const int32_t* dims, const float* voxel,
-                            int V, int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H,
-                            int W, const float* intrinsics, const float* camera_to_volume, const float* step,
+int d3f_tsdf_raycast_sparse(const float* D, const float* w, const float* Cp, int channels,
+                            const int64_t* lattice_start, const int64_t* brick_start, const int32_t* brick_index,
+                            const float* origin, const int32_t* dims, const float* voxel, int V,
+                            int64_t lattice_bricks, int64_t bricks, const int32_t* view_volume, int R, int H, int W,
+                            const float* intrinsics, const float* camera_to_volume, const float* step,
                             float depth_min, float depth_max, float min_weight, int clip, int skip, float* depth,
-                            float* normals, void* stream);
-int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const int64_t* lattice_start,
-                                 const int64_t* brick_start, const int32_t* brick_index, const float* origin,
-                                 const int32_t* dims, const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
+                            float* normals, float* color, void* stream);
+int d3f_tsdf_raycast_sparse_host(const float* D, const float* w, const float* Cp, int channels,
+                                 const int64_t* lattice_start, const int64_t* brick_start,
+                                 const int32_t* brick_index, const float* origin, const int32_t* dims,
+                                 const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                                 float min_weight, int clip, int skip, float* depth, float* normals, void* stream);
+                                 float min_weight, int clip, int skip, float* depth, float* normals, float* color,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Colour in TSDF volumes (csrc/tsdf_color.hpp states the rule in full, in the terms of csrc/tsdf.hpp,
  * csrc/tsdf_sparse.hpp and csrc/tsdf_raycast.hpp; the reference has no such step).  A colour volume Cv is f32
  * [total_voxels, channels], channel last, beside D and w; a sparse pool Cp is f32 [bricks, 512, channels]; channels is
- * 1 (intensity) or 3 (R, G, B), anything else is D3F_EINVAL.  Colour frames are f32 [F, H, W, channels], registered to
- * the depth pixel by pixel.  There is one weight: on exactly the frames that update D and w, with the w from before
- * the increment, c = (c w + c_pixel) / (w + 1) per channel, c_pixel read bilinearly over the 2 x 2 pixels around the
- * voxel's projection (indices clamped into the image); D and w are the colourless call's bit for bit.
- *
- * d3f_tsdf_integrate_color / _into extend d3f_tsdf_integrate / d3f_tsdf_integrate_into: the same arguments and launch
- * shape plus `color`, `channels` and `Cv` (written once by the voxel's thread; _into continues from the stored rows).
- * All sixteen integrate entry points, dense and sparse, are one kernel body and one host function in
- * csrc/tsdf_integrate.hip; the colourless ones are its channels = 0 form. */
-int d3f_tsdf_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H, int W,
-    const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels, int64_t max_volume_voxels,
-    const float* intrinsics, const float* volume_to_camera, const float* origin, const int32_t* dims,
-    const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w, float* Cv,
-    void* stream);
-int d3f_tsdf_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
-    int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
-    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
-    float* Cv, void* stream);
-int d3f_tsdf_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F, int H,
-    int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
-    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
-    float* Cv, void* stream);
-int d3f_tsdf_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32, int F,
-    int H, int W, const int32_t* frame_start, const int64_t* vol_start, int V, int64_t total_voxels,
-    int64_t max_volume_voxels, const float* intrinsics, const float* volume_to_camera, const float* origin,
-    const int32_t* dims, const float* voxel, const float* trunc, float depth_scale, float depth_max, float* D, float* w,
-    float* Cv, void* stream);
-/* d3f_tsdf_sparse_integrate_color / _into extend d3f_tsdf_sparse_integrate / d3f_tsdf_sparse_integrate_into: one
- * workgroup per brick as there; a slot that does not exist holds colour 0 beside D = 0, w = 0. */
-int d3f_tsdf_sparse_integrate_color(const void* depth, const float* color, int channels, int depth_is_f32, int F,
-    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
-    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
-    void* stream);
-int d3f_tsdf_sparse_integrate_color_host(const void* depth, const float* color, int channels, int depth_is_f32, int F,
-    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
-    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp);
-int d3f_tsdf_sparse_integrate_color_into(const void* depth, const float* color, int channels, int depth_is_f32, int F,
-    int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
-    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp,
-    void* stream);
-int d3f_tsdf_sparse_integrate_color_into_host(const void* depth, const float* color, int channels, int depth_is_f32,
-    int F, int H, int W, const int32_t* frame_start, int V, const float* intrinsics, const float* volume_to_camera,
-    const float* origin, const int32_t* dims, const float* voxel, const float* trunc, const int64_t* brick_start,
-    const int32_t* brick_coord, int64_t bricks, float depth_scale, float depth_max, float* D, float* w, float* Cp);
-/* d3f_tsdf_raycast_color / d3f_tsdf_raycast_sparse_color extend d3f_tsdf_raycast / d3f_tsdf_raycast_sparse: depth and
- * normals are theirs bit for bit; color f32 [R, H, W, channels] holds, at a hit, color_at of the hit point -- the
- * trilinear mean of the cell's corners with w >= min_weight, renormalised over those corners -- and NaN in every
- * channel without a hit (NaN, not 0: the render goes into the intensity pyramid as it is and the RGB-D tracker's
- * finiteness test drops those pixels). */
-int d3f_tsdf_raycast_color(const float* D, const float* w, const float* Cv, int channels, const int64_t* vol_start,
-                           const float* origin, const int32_t* dims, const float* voxel, int V, int64_t total_voxels,
-                           const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                           const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                           float min_weight, int clip, float* depth, float* normals, float* color, void* stream);
-int d3f_tsdf_raycast_color_host(const float* D, const float* w, const float* Cv, int channels,
-                                const int64_t* vol_start, const float* origin, const int32_t* dims, const float* voxel,
-                                int V, int64_t total_voxels, const int32_t* view_volume, int R, int H, int W,
-                                const float* intrinsics, const float* camera_to_volume, const float* step,
-                                float depth_min, float depth_max, float min_weight, int clip, float* depth,
-                                float* normals, float* color, void* stream);
-int d3f_tsdf_raycast_sparse_color(const float* D, const float* w, const float* Cp, int channels,
-                                  const int64_t* lattice_start, const int64_t* brick_start,
-                                  const int32_t* brick_index, const float* origin, const int32_t* dims,
-                                  const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
-                                  const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                                  const float* camera_to_volume, const float* step, float depth_min, float depth_max,
-                                  float min_weight, int clip, int skip, float* depth, float* normals, float* color,
-                                  void* stream);
-int d3f_tsdf_raycast_sparse_color_host(const float* D, const float* w, const float* Cp, int channels,
-                                       const int64_t* lattice_start, const int64_t* brick_start,
-                                       const int32_t* brick_index, const float* origin, const int32_t* dims,
-                                       const float* voxel, int V, int64_t lattice_bricks, int64_t bricks,
-                                       const int32_t* view_volume, int R, int H, int W, const float* intrinsics,
-                                       const float* camera_to_volume, const float* step, float depth_min,
-                                       float depth_max, float min_weight, int clip, int skip, float* depth,
-                                       float* normals, float* color, void* stream);
+ * 1 (intensity) or 3 (R, G, B) -- in the integrate and ray-cast entries above also 0, for no colour at all -- and
+ * anything else is D3F_EINVAL.  Colour frames are f32 [F, H, W, channels], registered to the depth pixel by pixel.
+ * Integrate: there is one weight: on exactly the frames that update D and w, with the w from before the increment,
+ * c = (c w + c_pixel) / (w + 1) per channel, c_pixel read bilinearly over the 2 x 2 pixels around the voxel's
+ * projection (indices clamped into the image); D and w are the channels = 0 call's bit for bit.
+ * Ray-cast: depth and normals are the channels = 0 call's bit for bit; color f32 [R, H, W, channels] holds, at a hit,
+ * color_at of the hit point -- the trilinear mean of the cell's corners with w >= min_weight, renormalised over those
+ * corners -- and NaN in every channel without a hit (NaN, not 0: the render goes into the intensity pyramid as it is
+ * and the RGB-D tracker's finiteness test drops those pixels).
+ * ---------------------------------------------------------------------------------------------- */
 /* d3f_tsdf_sample_color / d3f_tsdf_sample_color_sparse: color_at at N arbitrary points, one thread per point -- what
  * colours the clouds of d3f_tsdf_extract / d3f_tsdf_sparse_extract and the vertices of d3f_tsdf_mesh /
  * d3f_tsdf_sparse_mesh, whose kernels and output orders they leave alone.  points f32 [N, 3] in the frame of the

@@ -117,9 +117,9 @@ def main():
                                         ops.TSDF_DEPTH_MAX, p(tb), stream), "d3f_tsdf_bounds")
 
     def run_integrate():
-        _native.check(L.d3f_tsdf_integrate(p(td), 0, FRAMES, HEIGHT, WIDTH, p(tfs), p(tvs), 1, total, total, p(tK), p(tM), p(to),
-                                           p(tn), p(tvx), p(ttr), 1000.0, ops.TSDF_DEPTH_MAX, p(D), p(w), stream),
-                      "d3f_tsdf_integrate")
+        _native.check(L.d3f_tsdf_integrate(p(td), None, 0, 0, FRAMES, HEIGHT, WIDTH, p(tfs), p(tvs), 1, total, total,
+                                           p(tK), p(tM), p(to), p(tn), p(tvx), p(ttr), 1000.0, ops.TSDF_DEPTH_MAX, 0,
+                                           p(D), p(w), None, stream), "d3f_tsdf_integrate")
 
     nbytes = L.d3f_tsdf_extract_ws_bytes(total)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)

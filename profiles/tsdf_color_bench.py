@@ -2,10 +2,9 @@
 of 640 x 480 of the analytic room scaled 2.4 times, voxel 0.006 m, about 2 x 10^8 voxels -- painted with the analytic
 texture ``tex`` of tests/rgbd_cases.py:
 
-  * d3f_tsdf_integrate against d3f_tsdf_integrate_color with 1 and 3 channels, and the _into forms of both without
-    colour and with 3 channels;
-  * d3f_tsdf_sparse_integrate against d3f_tsdf_sparse_integrate_color with 1 and 3 channels, on the bricks of the same
-    fragment, and their _into forms likewise;
+  * d3f_tsdf_integrate with channels = 0 against 1 and 3 channels, and with into = 1 without colour and with 3
+    channels;
+  * d3f_tsdf_sparse_integrate likewise, on the bricks of the same fragment;
   * ops.tsdf_raycast of 1 view and of 16 views of 640 x 480, without colour and with a 1- and a 3-channel volume;
   * ops.tsdf_sample_color on the extracted cloud, 1 and 3 channels.
 
@@ -105,21 +104,18 @@ def main():
     out.append("")
 
     # ------------------------------------------------------------------------------------------------ integrate
+    tc[0], Cv[0] = None, None                            # channels = 0: no colour frames, no colour volume
     rest = (0, F, H, W, p(tfs), p(tvs), 1, total, total, p(tK), p(tM), p(to), p(tn), p(tvx), p(ttr), 1000.0,
-            ops.TSDF_DEPTH_MAX, p(D), p(w))
+            ops.TSDF_DEPTH_MAX)
 
-    def dense(c, into=""):
-        if c == 0:
-            fn = getattr(L, "d3f_tsdf_integrate" + into)
-            return lambda: _native.check(fn(*((p(td),) + rest + (stream,))), "d3f_tsdf_integrate" + into)
-        fn = getattr(L, "d3f_tsdf_integrate_color" + into)
-        return lambda: _native.check(fn(*((p(td), p(tc[c]), c) + rest + (p(Cv[c]), stream))),
-                                     "d3f_tsdf_integrate_color" + into)
+    def dense(c, into=0):
+        args = (p(td), p(tc[c]), c) + rest + (into, p(D), p(w), p(Cv[c]), stream)
+        return lambda: _native.check(L.d3f_tsdf_integrate(*args), "d3f_tsdf_integrate")
     ms = take_turns({"Cc = %d" % c: dense(c) for c in (0, 1, 3)})
-    report(out, "integrate (d3f_tsdf_integrate / d3f_tsdf_integrate_color), one launch", ms, "Cc = 0",
+    report(out, "integrate (d3f_tsdf_integrate), one launch", ms, "Cc = 0",
            {"Cc = %d" % c: "writes %.2f GB" % ((8 + 4 * c) * 1e-9 * total) for c in (0, 1, 3)})
-    ms = take_turns({"Cc = %d" % c: dense(c, "_into") for c in (0, 3)})      # continues what the arms above left
-    report(out, "integrate into (d3f_tsdf_integrate_into / d3f_tsdf_integrate_color_into), one launch", ms, "Cc = 0",
+    ms = take_turns({"Cc = %d" % c: dense(c, 1) for c in (0, 3)})            # continues what the arms above left
+    report(out, "integrate into (d3f_tsdf_integrate, into = 1), one launch", ms, "Cc = 0",
            {"Cc = %d" % c: "reads and writes %.2f GB" % ((8 + 4 * c) * 1e-9 * total) for c in (0, 3)})
     for c in (0, 1, 3):                                  # the ray-cast and the sampling below read a volume fused once
         dense(c)()
@@ -132,21 +128,18 @@ def main():
     Dp = torch.empty(slots, dtype=torch.float32, device=dev)
     wp = torch.empty(slots, dtype=torch.float32, device=dev)
     Cp = {c: torch.empty((slots, c), dtype=torch.float32, device=dev) for c in (1, 3)}
+    Cp[0] = None
     srest = (0, F, H, W, p(tfs), 1, p(tK), p(tM), p(so), p(sn), p(svx), p(ttr), p(bs), p(bc), B, 1000.0,
-             ops.TSDF_DEPTH_MAX, p(Dp), p(wp))
+             ops.TSDF_DEPTH_MAX)
 
-    def sparse(c, into=""):
-        if c == 0:
-            fn = getattr(L, "d3f_tsdf_sparse_integrate" + into)
-            return lambda: _native.check(fn(*((p(td),) + srest + (stream,))), "d3f_tsdf_sparse_integrate" + into)
-        fn = getattr(L, "d3f_tsdf_sparse_integrate_color" + into)
-        return lambda: _native.check(fn(*((p(td), p(tc[c]), c) + srest + (p(Cp[c]), stream))),
-                                     "d3f_tsdf_sparse_integrate_color" + into)
+    def sparse(c, into=0):
+        args = (p(td), p(tc[c]), c) + srest + (into, p(Dp), p(wp), p(Cp[c]), stream)
+        return lambda: _native.check(L.d3f_tsdf_sparse_integrate(*args), "d3f_tsdf_sparse_integrate")
     ms = take_turns({"Cc = %d" % c: sparse(c) for c in (0, 1, 3)})
     report(out, "sparse integrate, %d bricks of %d (%.1f %% of the lattice)" % (B, int(sv.lattice_start[-1]),
                                                                               100.0 * B / int(sv.lattice_start[-1])),
            ms, "Cc = 0", {"Cc = %d" % c: "writes %.3f GB" % ((8 + 4 * c) * 1e-9 * slots) for c in (0, 1, 3)})
-    ms = take_turns({"Cc = %d" % c: sparse(c, "_into") for c in (0, 3)})
+    ms = take_turns({"Cc = %d" % c: sparse(c, 1) for c in (0, 3)})
     report(out, "sparse integrate into, the same bricks", ms, "Cc = 0",
            {"Cc = %d" % c: "reads and writes %.3f GB" % ((8 + 4 * c) * 1e-9 * slots) for c in (0, 3)})
 

@@ -102,9 +102,9 @@ def main():
 
     def cast(R, clip):
         def run():
-            _native.check(L.d3f_tsdf_raycast(p(D), p(w), p(tvs), p(to), p(tn), p(tvx), 1, total, p(tvv), R, H, W, p(tK),
-                                             p(tC), p(tst), ops.RAYCAST_DEPTH_MIN, ops.TSDF_DEPTH_MAX, 1.0, clip,
-                                             p(images[(R, clip)]), None, stream), "d3f_tsdf_raycast")
+            _native.check(L.d3f_tsdf_raycast(p(D), p(w), None, 0, p(tvs), p(to), p(tn), p(tvx), 1, total, p(tvv), R, H,
+                                             W, p(tK), p(tC), p(tst), ops.RAYCAST_DEPTH_MIN, ops.TSDF_DEPTH_MAX, 1.0,
+                                             clip, p(images[(R, clip)]), None, None, stream), "d3f_tsdf_raycast")
         return run
 
     arms = {"1 view, clip on": cast(1, 1), "1 view, clip off": cast(1, 0), "%d views, clip on" % BATCH: cast(BATCH, 1),

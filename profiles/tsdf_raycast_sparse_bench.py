@@ -141,15 +141,16 @@ def main():
 
     def cast(R, kind):
         def sparse():
-            _native.check(L.d3f_tsdf_raycast_sparse(p(Ds), p(ws), p(tls), p(bs), p(bi), p(to), p(tn), p(tvx), 1, lattice,
-                                                    B, p(tvv), R, H, W, p(tK), p(tC), p(tst), ops.RAYCAST_DEPTH_MIN,
-                                                    ops.TSDF_DEPTH_MAX, 1.0, 1, int(kind == "skip on"),
-                                                    p(images[(R, kind)]), None, stream), "d3f_tsdf_raycast_sparse")
+            _native.check(L.d3f_tsdf_raycast_sparse(p(Ds), p(ws), None, 0, p(tls), p(bs), p(bi), p(to), p(tn), p(tvx),
+                                                    1, lattice, B, p(tvv), R, H, W, p(tK), p(tC), p(tst),
+                                                    ops.RAYCAST_DEPTH_MIN, ops.TSDF_DEPTH_MAX, 1.0, 1,
+                                                    int(kind == "skip on"), p(images[(R, kind)]), None, None, stream),
+                          "d3f_tsdf_raycast_sparse")
 
         def dense():
-            _native.check(L.d3f_tsdf_raycast(p(D), p(w), p(tvs), p(to), p(tn), p(tvx), 1, total, p(tvv), R, H, W, p(tK),
-                                             p(tC), p(tst), ops.RAYCAST_DEPTH_MIN, ops.TSDF_DEPTH_MAX, 1.0, 1,
-                                             p(images[(R, kind)]), None, stream), "d3f_tsdf_raycast")
+            _native.check(L.d3f_tsdf_raycast(p(D), p(w), None, 0, p(tvs), p(to), p(tn), p(tvx), 1, total, p(tvv), R, H,
+                                             W, p(tK), p(tC), p(tst), ops.RAYCAST_DEPTH_MIN, ops.TSDF_DEPTH_MAX, 1.0, 1,
+                                             p(images[(R, kind)]), None, None, stream), "d3f_tsdf_raycast")
         return dense if kind == "dense" else sparse
 
     names = {(R, kind): "%d view%s, %s" % (R, "" if R == 1 else "s", "dense volume" if kind == "dense" else

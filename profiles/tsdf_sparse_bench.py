@@ -85,9 +85,9 @@ def main():
     ws_ = torch.empty((bricks, 512), dtype=torch.float32, device=dev)
 
     def run_sparse_integrate():
-        check(L.d3f_tsdf_sparse_integrate(p(td), 0, F, H, W, p(tfs), 1, p(tK), p(tM), p(to), p(tn), p(tvx), p(ttr),
-                                          p(brick_start), p(sv.brick_coord), bricks, 1000.0, dmax, p(Ds), p(ws_),
-                                          stream), "d3f_tsdf_sparse_integrate")
+        check(L.d3f_tsdf_sparse_integrate(p(td), None, 0, 0, F, H, W, p(tfs), 1, p(tK), p(tM), p(to), p(tn), p(tvx),
+                                          p(ttr), p(brick_start), p(sv.brick_coord), bricks, 1000.0, dmax, 0, p(Ds),
+                                          p(ws_), None, stream), "d3f_tsdf_sparse_integrate")
 
     sparse_bytes_ws = L.d3f_tsdf_sparse_extract_ws_bytes(bricks)
     sparse_ws = torch.empty(sparse_bytes_ws, dtype=torch.uint8, device=dev)
@@ -122,8 +122,9 @@ def main():
     w = torch.empty(total, dtype=torch.float32, device=dev)
 
     def run_integrate():
-        check(L.d3f_tsdf_integrate(p(td), 0, F, H, W, p(tfs), p(tvs), 1, total, total, p(tK), p(tM), p(to), p(tn), p(tvx),
-                                   p(ttr), 1000.0, dmax, p(D), p(w), stream), "d3f_tsdf_integrate")
+        check(L.d3f_tsdf_integrate(p(td), None, 0, 0, F, H, W, p(tfs), p(tvs), 1, total, total, p(tK), p(tM), p(to),
+                                   p(tn), p(tvx), p(ttr), 1000.0, dmax, 0, p(D), p(w), None, stream),
+              "d3f_tsdf_integrate")
 
     nbytes = L.d3f_tsdf_extract_ws_bytes(total)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)

@@ -7,7 +7,7 @@
 //         tests/raycast_host_twins.cpp -o /tmp/raycast_host_twins && /tmp/raycast_host_twins
 //
 // Two volumes of different dims (13 x 9 x 7 and 5 x 1 x 4, the second without a cell along y) are fused from two frames
-// of 37 x 23 by d3f_tsdf_integrate_host, and again as one frame followed by d3f_tsdf_integrate_into_host; the two must
+// of 37 x 23 by d3f_tsdf_integrate_host, and again as one frame followed by the same entry with into = 1; the two must
 // agree bit for bit.  d3f_tsdf_raycast_host then renders six views in the order 1, 0, 1, 0, 0, 0 -- among them a pose
 // holding a NaN, a pose holding an infinity and a camera far outside -- with and without normals and with the clip on
 // and off, which must agree bit for bit.  Every buffer is sized exactly, so a read or write past an end is reported.
@@ -43,8 +43,9 @@ int main() {
   const float step[2] = {0.05f, 0.05f};
   const int32_t both[3] = {0, 2, 4}, first[3] = {0, 1, 2};
   std::vector<float> D(total), w(total), D2(total), w2(total);
-  if (d3f_tsdf_integrate_host(depth.data(), 1, F, H, W, both, vol_start, V, total, total, K.data(), M.data(), origin,
-                              dims, voxel, trunc, 1000.0f, 6.0f, D.data(), w.data(), nullptr))
+  if (d3f_tsdf_integrate_host(depth.data(), nullptr, 0, 1, F, H, W, both, vol_start, V, total, total, K.data(),
+                              M.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 0, D.data(), w.data(), nullptr,
+                              nullptr))
     return 2;
   // frames 0 and 2 first, then frames 1 and 3 into the result
   std::vector<float> da, db, Ka, Kb, Ma, Mb;
@@ -54,16 +55,18 @@ int main() {
     k.insert(k.end(), K.begin() + 4 * f, K.begin() + 4 * (f + 1));
     m.insert(m.end(), M.begin() + 12 * f, M.begin() + 12 * (f + 1));
   }
-  if (d3f_tsdf_integrate_host(da.data(), 1, 2, H, W, first, vol_start, V, total, total, Ka.data(), Ma.data(), origin, dims,
-                              voxel, trunc, 1000.0f, 6.0f, D2.data(), w2.data(), nullptr))
+  if (d3f_tsdf_integrate_host(da.data(), nullptr, 0, 1, 2, H, W, first, vol_start, V, total, total, Ka.data(),
+                              Ma.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 0, D2.data(), w2.data(), nullptr,
+                              nullptr))
     return 3;
-  if (d3f_tsdf_integrate_into_host(db.data(), 1, 2, H, W, first, vol_start, V, total, total, Kb.data(), Mb.data(), origin,
-                                   dims, voxel, trunc, 1000.0f, 6.0f, D2.data(), w2.data(), nullptr))
+  if (d3f_tsdf_integrate_host(db.data(), nullptr, 0, 1, 2, H, W, first, vol_start, V, total, total, Kb.data(),
+                              Mb.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 1, D2.data(), w2.data(), nullptr,
+                              nullptr))
     return 4;
   if (memcmp(D.data(), D2.data(), total * sizeof(float)) || memcmp(w.data(), w2.data(), total * sizeof(float))) return 5;
   const int32_t none[3] = {0, 0, 0};                                         // no volume owns a frame: nothing changes
-  if (d3f_tsdf_integrate_into_host(db.data(), 1, 2, H, W, none, vol_start, V, total, total, Kb.data(), Mb.data(), origin,
-                                   dims, voxel, trunc, 1000.0f, 6.0f, D2.data(), w2.data(), nullptr))
+  if (d3f_tsdf_integrate_host(db.data(), nullptr, 0, 1, 2, H, W, none, vol_start, V, total, total, Kb.data(), Mb.data(),
+                              origin, dims, voxel, trunc, 1000.0f, 6.0f, 1, D2.data(), w2.data(), nullptr, nullptr))
     return 6;
   if (memcmp(D.data(), D2.data(), total * sizeof(float))) return 7;
 
@@ -81,15 +84,17 @@ int main() {
   std::vector<float> image((size_t)R * H * W), normals((size_t)R * H * W * 3), image2(image.size()), normals2(normals.size());
   for (int clip = 0; clip < 2; ++clip) {
     std::vector<float>&im = clip ? image : image2, &nr = clip ? normals : normals2;
-    if (d3f_tsdf_raycast_host(D.data(), w.data(), vol_start, origin, dims, voxel, V, total, view_volume, R, H, W, Kv.data(),
-                              C.data(), step, 0.1f, 6.0f, 1.0f, clip, im.data(), nr.data(), nullptr))
+    if (d3f_tsdf_raycast_host(D.data(), w.data(), nullptr, 0, vol_start, origin, dims, voxel, V, total, view_volume, R,
+                              H, W, Kv.data(), C.data(), step, 0.1f, 6.0f, 1.0f, clip, im.data(), nr.data(), nullptr,
+                              nullptr))
       return 8;
   }
   if (memcmp(image.data(), image2.data(), image.size() * sizeof(float)) ||
       memcmp(normals.data(), normals2.data(), normals.size() * sizeof(float)))
     return 9;
-  if (d3f_tsdf_raycast_host(D.data(), w.data(), vol_start, origin, dims, voxel, V, total, view_volume, R, H, W, Kv.data(),
-                            C.data(), step, 0.1f, 6.0f, 1.0f, 1, image2.data(), nullptr, nullptr))
+  if (d3f_tsdf_raycast_host(D.data(), w.data(), nullptr, 0, vol_start, origin, dims, voxel, V, total, view_volume, R, H,
+                            W, Kv.data(), C.data(), step, 0.1f, 6.0f, 1.0f, 1, image2.data(), nullptr, nullptr,
+                            nullptr))
     return 10;
   if (memcmp(image.data(), image2.data(), image.size() * sizeof(float))) return 11;
   int hits[R] = {0, 0, 0, 0, 0, 0};
@@ -101,12 +106,13 @@ int main() {
     }
   printf("hits per view: %d %d %d %d %d %d\n", hits[0], hits[1], hits[2], hits[3], hits[4], hits[5]);
   if (hits[0] || hits[2] || hits[3] || hits[4] || hits[5] || !hits[1]) return 13;   // only view 1 sees a surface
-  if (d3f_tsdf_raycast_host(D.data(), w.data(), vol_start, origin, dims, voxel, V, total, view_volume, 0, H, W, nullptr,
-                            nullptr, step, 0.1f, 6.0f, 1.0f, 1, nullptr, nullptr, nullptr))
+  if (d3f_tsdf_raycast_host(D.data(), w.data(), nullptr, 0, vol_start, origin, dims, voxel, V, total, view_volume, 0, H,
+                            W, nullptr, nullptr, step, 0.1f, 6.0f, 1.0f, 1, nullptr, nullptr, nullptr, nullptr))
     return 14;
   const float bad_step[2] = {0.0f, 1e-9f};                                    // casts nothing: zeros, no long loop
-  if (d3f_tsdf_raycast_host(D.data(), w.data(), vol_start, origin, dims, voxel, V, total, view_volume, R, H, W, Kv.data(),
-                            C.data(), bad_step, 0.1f, 6.0f, 1.0f, 1, image2.data(), nullptr, nullptr))
+  if (d3f_tsdf_raycast_host(D.data(), w.data(), nullptr, 0, vol_start, origin, dims, voxel, V, total, view_volume, R, H,
+                            W, Kv.data(), C.data(), bad_step, 0.1f, 6.0f, 1.0f, 1, image2.data(), nullptr, nullptr,
+                            nullptr))
     return 15;
   for (float d : image2)
     if (d != 0.0f) return 16;

@@ -9,10 +9,10 @@
 //
 // Two volumes of different dims (13 x 9 x 7: 2 x 2 x 1 lattice bricks with borders at index 7 | 8 on two axes, and
 // 5 x 1 x 4, without a cell along y) go through d3f_tsdf_sparse_mark_host, _index_host and _integrate_host over two
-// frames of 37 x 23 each, and again as one frame followed by d3f_tsdf_sparse_integrate_into_host; the two pools must
-// agree bit for bit.  The colour forms follow with 1 and 3 channels, dense (d3f_tsdf_integrate_color_host) and sparse
-// (d3f_tsdf_sparse_integrate_color_host): the whole call against two frames followed by the other two through the
-// _color_into_host forms, bit for bit on D, w and the colour, D and w those of the colourless calls, and the pool's
+// frames of 37 x 23 each, and again as one frame followed by the same entry with into = 1; the two pools must
+// agree bit for bit.  The colour forms follow with channels = 1 and 3, dense (d3f_tsdf_integrate_host) and sparse
+// (d3f_tsdf_sparse_integrate_host): the whole call against two frames followed by the other two with into = 1,
+// bit for bit on D, w and the colour, D and w those of the channels = 0 calls, and the pool's
 // colour that of the dense volume.  d3f_tsdf_raycast_sparse_host then renders six views in the order 1, 0, 1, 0, 0, 0 -- among them a
 // pose holding a NaN, a pose holding an infinity and a camera far outside -- with the skip and the clip on and off, with
 // and without normals, at min_weight 1 and 0, and all must equal d3f_tsdf_raycast_host on the pool scattered into dense
@@ -67,8 +67,9 @@ int main() {
   if (B < 1 || B > L) return 4;
   std::vector<int32_t> coord(coord_all.begin(), coord_all.begin() + 3 * B);        // exactly B rows
   std::vector<float> D((size_t)B * 512), w((size_t)B * 512), D2(D.size()), w2(w.size());
-  if (d3f_tsdf_sparse_integrate_host(depth.data(), 1, F, H, W, both, V, K.data(), M.data(), origin, dims, voxel, trunc,
-                                     brick_start, coord.data(), B, 1000.0f, 6.0f, D.data(), w.data()))
+  if (d3f_tsdf_sparse_integrate_host(depth.data(), nullptr, 0, 1, F, H, W, both, V, K.data(), M.data(), origin, dims,
+                                     voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 0, D.data(), w.data(),
+                                     nullptr, nullptr))
     return 5;
   // frames 0 and 2 first, then frames 1 and 3 into the result
   std::vector<float> da, db, Ka, Kb, Ma, Mb;
@@ -78,26 +79,30 @@ int main() {
     k.insert(k.end(), K.begin() + 4 * f, K.begin() + 4 * (f + 1));
     m.insert(m.end(), M.begin() + 12 * f, M.begin() + 12 * (f + 1));
   }
-  if (d3f_tsdf_sparse_integrate_host(da.data(), 1, 2, H, W, first, V, Ka.data(), Ma.data(), origin, dims, voxel, trunc,
-                                     brick_start, coord.data(), B, 1000.0f, 6.0f, D2.data(), w2.data()))
+  if (d3f_tsdf_sparse_integrate_host(da.data(), nullptr, 0, 1, 2, H, W, first, V, Ka.data(), Ma.data(), origin, dims,
+                                     voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 0, D2.data(), w2.data(),
+                                     nullptr, nullptr))
     return 6;
-  if (d3f_tsdf_sparse_integrate_into_host(db.data(), 1, 2, H, W, first, V, Kb.data(), Mb.data(), origin, dims, voxel,
-                                          trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, D2.data(), w2.data()))
+  if (d3f_tsdf_sparse_integrate_host(db.data(), nullptr, 0, 1, 2, H, W, first, V, Kb.data(), Mb.data(), origin, dims,
+                                     voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 1, D2.data(), w2.data(),
+                                     nullptr, nullptr))
     return 7;
   if (memcmp(D.data(), D2.data(), D.size() * sizeof(float)) || memcmp(w.data(), w2.data(), w.size() * sizeof(float)))
     return 8;
   const int32_t none[3] = {0, 0, 0};                                         // no volume owns a frame: nothing changes
-  if (d3f_tsdf_sparse_integrate_into_host(db.data(), 1, 2, H, W, none, V, Kb.data(), Mb.data(), origin, dims, voxel,
-                                          trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, D2.data(), w2.data()))
+  if (d3f_tsdf_sparse_integrate_host(db.data(), nullptr, 0, 1, 2, H, W, none, V, Kb.data(), Mb.data(), origin, dims,
+                                     voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 1, D2.data(), w2.data(),
+                                     nullptr, nullptr))
     return 9;
   if (memcmp(D.data(), D2.data(), D.size() * sizeof(float)) || memcmp(w.data(), w2.data(), w.size() * sizeof(float)))
     return 10;
 
-  // colour, 1 and 3 channels, dense and sparse: the whole call against frames 0 and 2 followed by frames 1 and 3 _into
+  // colour, 1 and 3 channels, dense and sparse: the whole call against frames 0 and 2 followed by frames 1 and 3 into
   // the result; D and w are those of the colourless calls.  The colour frames and Cv / Cp are sized exactly
   std::vector<float> Dv(total), wv(total), Dv2(total), wv2(total), Dc(total), wc(total), Dq(D.size()), wq(w.size());
-  if (d3f_tsdf_integrate_host(depth.data(), 1, F, H, W, both, vol_start, V, total, total, K.data(), M.data(), origin, dims,
-                              voxel, trunc, 1000.0f, 6.0f, Dv.data(), wv.data(), nullptr))
+  if (d3f_tsdf_integrate_host(depth.data(), nullptr, 0, 1, F, H, W, both, vol_start, V, total, total, K.data(),
+                              M.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 0, Dv.data(), wv.data(), nullptr,
+                              nullptr))
     return 30;
   for (int Cc = 1; Cc <= 3; Cc += 2) {
     std::vector<float> colour((size_t)F * H * W * Cc), ca, cb;
@@ -107,33 +112,33 @@ int main() {
       c.insert(c.end(), colour.begin() + (size_t)f * H * W * Cc, colour.begin() + (size_t)(f + 1) * H * W * Cc);
     }
     std::vector<float> Cv((size_t)total * Cc), Cv2(Cv.size()), Cp((size_t)B * 512 * Cc), Cp2(Cp.size());
-    if (d3f_tsdf_integrate_color_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, vol_start, V, total, total, K.data(),
-                                      M.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dc.data(), wc.data(), Cv.data(),
-                                      nullptr))
+    if (d3f_tsdf_integrate_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, vol_start, V, total, total, K.data(),
+                                M.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 0, Dc.data(), wc.data(), Cv.data(),
+                                nullptr))
       return 31;
-    if (d3f_tsdf_integrate_color_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total, Ka.data(),
-                                      Ma.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dv2.data(), wv2.data(),
-                                      Cv2.data(), nullptr))
+    if (d3f_tsdf_integrate_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total, Ka.data(),
+                                Ma.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 0, Dv2.data(), wv2.data(),
+                                Cv2.data(), nullptr))
       return 32;
-    if (d3f_tsdf_integrate_color_into_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total,
-                                           Kb.data(), Mb.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, Dv2.data(),
-                                           wv2.data(), Cv2.data(), nullptr))
+    if (d3f_tsdf_integrate_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, vol_start, V, total, total, Kb.data(),
+                                Mb.data(), origin, dims, voxel, trunc, 1000.0f, 6.0f, 1, Dv2.data(), wv2.data(),
+                                Cv2.data(), nullptr))
       return 33;
     if (memcmp(Dc.data(), Dv.data(), Dv.size() * sizeof(float)) || memcmp(wc.data(), wv.data(), wv.size() * sizeof(float)) ||
         memcmp(Dc.data(), Dv2.data(), Dv.size() * sizeof(float)) || memcmp(wc.data(), wv2.data(), wv.size() * sizeof(float)) ||
         memcmp(Cv.data(), Cv2.data(), Cv.size() * sizeof(float)))
       return 34;
-    if (d3f_tsdf_sparse_integrate_color_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, V, K.data(), M.data(), origin,
-                                             dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, Dq.data(),
-                                             wq.data(), Cp.data()))
+    if (d3f_tsdf_sparse_integrate_host(depth.data(), colour.data(), Cc, 1, F, H, W, both, V, K.data(), M.data(), origin,
+                                       dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 0, Dq.data(),
+                                       wq.data(), Cp.data(), nullptr))
       return 35;
-    if (d3f_tsdf_sparse_integrate_color_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, V, Ka.data(), Ma.data(), origin,
-                                             dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, D2.data(),
-                                             w2.data(), Cp2.data()))
+    if (d3f_tsdf_sparse_integrate_host(da.data(), ca.data(), Cc, 1, 2, H, W, first, V, Ka.data(), Ma.data(), origin,
+                                       dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 0, D2.data(),
+                                       w2.data(), Cp2.data(), nullptr))
       return 36;
-    if (d3f_tsdf_sparse_integrate_color_into_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, V, Kb.data(), Mb.data(),
-                                                  origin, dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f,
-                                                  D2.data(), w2.data(), Cp2.data()))
+    if (d3f_tsdf_sparse_integrate_host(db.data(), cb.data(), Cc, 1, 2, H, W, first, V, Kb.data(), Mb.data(), origin,
+                                       dims, voxel, trunc, brick_start, coord.data(), B, 1000.0f, 6.0f, 1, D2.data(),
+                                       w2.data(), Cp2.data(), nullptr))
       return 37;
     if (memcmp(Dq.data(), D.data(), D.size() * sizeof(float)) || memcmp(wq.data(), w.data(), w.size() * sizeof(float)) ||
         memcmp(Dq.data(), D2.data(), D.size() * sizeof(float)) || memcmp(wq.data(), w2.data(), w.size() * sizeof(float)) ||
@@ -194,21 +199,23 @@ int main() {
         for (int iy = 0; iy < 9; ++iy)
           for (int ix = 8; ix < 13; ++ix) Dd[((size_t)iz * 9 + iy) * 13 + ix] = wd[((size_t)iz * 9 + iy) * 13 + ix] = 0.0f;
     }
-    if (d3f_tsdf_raycast_host(Dd.data(), wd.data(), vol_start, origin, dims, voxel, V, total, view_volume, R, H, W,
-                              Kv.data(), C.data(), step, 0.1f, 6.0f, min_weight, 1, image.data(), normals.data(), nullptr))
+    if (d3f_tsdf_raycast_host(Dd.data(), wd.data(), nullptr, 0, vol_start, origin, dims, voxel, V, total, view_volume,
+                              R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f, min_weight, 1, image.data(),
+                              normals.data(), nullptr, nullptr))
       return 11;
     for (int mode = 0; mode < 4; ++mode) {
-      if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), lattice_start, brick_start, index.data(), origin, dims, voxel, V,
-                                       L, B, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f, min_weight,
-                                       mode & 1, mode >> 1, image2.data(), normals2.data(), nullptr))
+      if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), nullptr, 0, lattice_start, brick_start, index.data(), origin,
+                                       dims, voxel, V, L, B, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f,
+                                       6.0f, min_weight, mode & 1, mode >> 1, image2.data(), normals2.data(), nullptr,
+                                       nullptr))
         return 12;
       if (memcmp(image.data(), image2.data(), image.size() * sizeof(float)) ||
           memcmp(normals.data(), normals2.data(), normals.size() * sizeof(float)))
         return 13 + mode;
     }
-    if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), lattice_start, brick_start, index.data(), origin, dims, voxel, V,
-                                     L, B, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f, min_weight, 1, 1,
-                                     image2.data(), nullptr, nullptr))
+    if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), nullptr, 0, lattice_start, brick_start, index.data(), origin,
+                                     dims, voxel, V, L, B, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f,
+                                     min_weight, 1, 1, image2.data(), nullptr, nullptr, nullptr))
       return 17;
     if (memcmp(image.data(), image2.data(), image.size() * sizeof(float))) return 18;
     if (!mw && !pass) {
@@ -219,16 +226,16 @@ int main() {
       if (hits[0] || hits[2] || hits[3] || hits[4] || hits[5] || !hits[1]) return 19;   // only view 1 sees a surface
     }
   }
-  if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), lattice_start, brick_start, index.data(), origin, dims, voxel, V, L,
-                                   B, view_volume, 0, H, W, nullptr, nullptr, step, 0.1f, 6.0f, 1.0f, 1, 1, nullptr,
-                                   nullptr, nullptr))
+  if (d3f_tsdf_raycast_sparse_host(D.data(), w.data(), nullptr, 0, lattice_start, brick_start, index.data(), origin,
+                                   dims, voxel, V, L, B, view_volume, 0, H, W, nullptr, nullptr, step, 0.1f, 6.0f, 1.0f,
+                                   1, 1, nullptr, nullptr, nullptr, nullptr))
     return 20;
   // no brick at all: a pool of no rows is never read
   const int64_t empty_start[3] = {0, 0, 0};
   std::vector<int32_t> absent(L, -1);
-  if (d3f_tsdf_raycast_sparse_host(nullptr, nullptr, lattice_start, empty_start, absent.data(), origin, dims, voxel, V, L,
-                                   0, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f, 1.0f, 1, 1,
-                                   image2.data(), normals2.data(), nullptr))
+  if (d3f_tsdf_raycast_sparse_host(nullptr, nullptr, nullptr, 0, lattice_start, empty_start, absent.data(), origin,
+                                   dims, voxel, V, L, 0, view_volume, R, H, W, Kv.data(), C.data(), step, 0.1f, 6.0f,
+                                   1.0f, 1, 1, image2.data(), normals2.data(), nullptr, nullptr))
     return 21;
   for (float d : image2)
     if (d != 0.0f) return 22;

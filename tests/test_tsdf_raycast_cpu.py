@@ -14,6 +14,7 @@ from d3feat_pytorch_amd.datasets import fragments as fr
 import odometry_cases as OC
 import raycast_cases as RC
 import tsdf_scene as S
+from tsdf_entry_cases import REMOVED_ENTRIES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -290,7 +291,10 @@ def test_the_new_entries_of_the_header_are_bound():
     src = open(os.path.join(REPO, "include", "d3feat_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     lib = _native.lib()
-    for name in ("d3f_tsdf_raycast", "d3f_tsdf_raycast_host", "d3f_tsdf_integrate_into", "d3f_tsdf_integrate_into_host"):
+    for name in ("d3f_tsdf_raycast", "d3f_tsdf_raycast_host", "d3f_tsdf_integrate", "d3f_tsdf_integrate_host"):
         assert re.search(r"\b%s\s*\(" % name, src) and name in _native.SIGNATURES and hasattr(lib, name)
+    assert len(REMOVED_ENTRIES) == 16                      # folded into the entries above: `channels` and `into`
+    for name in REMOVED_ENTRIES:
+        assert not re.search(r"\b%s\s*\(" % name, src) and name not in _native.SIGNATURES and not hasattr(lib, name)
     assert "tsdf_raycast.hip" in _native.SOURCES
     assert re.search(r"#define D3F_RAYCAST_MAX_SAMPLES %d\b" % ops.RAYCAST_MAX_SAMPLES, src)

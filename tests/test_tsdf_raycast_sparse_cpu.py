@@ -16,6 +16,7 @@ import raycast_cases as RC
 import raycast_sparse_cases as C
 import tsdf_scene as S
 import tsdf_sparse_cases as SC
+from tsdf_entry_cases import REMOVED_ENTRIES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 same_bits, host = SC.same_bits, SC.host
@@ -248,7 +249,10 @@ def test_the_new_entries_of_the_header_are_bound():
     src = open(os.path.join(REPO, "include", "d3feat_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     lib = _native.lib()
-    for name in ("d3f_tsdf_raycast_sparse", "d3f_tsdf_raycast_sparse_host", "d3f_tsdf_sparse_integrate_into",
-                 "d3f_tsdf_sparse_integrate_into_host"):
+    for name in ("d3f_tsdf_raycast_sparse", "d3f_tsdf_raycast_sparse_host", "d3f_tsdf_sparse_integrate",
+                 "d3f_tsdf_sparse_integrate_host"):
         assert re.search(r"\b%s\s*\(" % name, src) and name in _native.SIGNATURES and hasattr(lib, name)
+    assert len(REMOVED_ENTRIES) == 16                      # folded into the entries above: `channels` and `into`
+    for name in REMOVED_ENTRIES:
+        assert not re.search(r"\b%s\s*\(" % name, src) and name not in _native.SIGNATURES and not hasattr(lib, name)
     assert fr.DEFAULT_MODEL['sparse'] is False
