@@ -25,7 +25,9 @@ def default_config(**overrides):
         dist_type='euclidean', desc_loss='circle', pos_margin=0.1, neg_margin=1.4, m=0.1, log_scale=10,
         safe_radius=0.1, det_loss='score', desc_loss_weight=1.0, det_loss_weight=1.0,
         optimizer='SGD', lr=0.01, weight_decay=1e-6, momentum=0.98, scheduler='ExpLR', scheduler_gamma=0.1 ** (1 / 80),
-        num_node=128, downsample=0.03, batch_size=1)
+        num_node=128, downsample=0.03, batch_size=1,
+        # train without float atomics: bit-equal replays of a step, at a measured price (README, ops.set_deterministic)
+        deterministic=False)
     cfg.architecture = d3feat_architecture(cfg.num_layers)
     for k, v in overrides.items():
         setattr(cfg, k, v)

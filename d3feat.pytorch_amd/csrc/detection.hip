@@ -566,6 +566,174 @@ __global__ __launch_bounds__(256) void det_rows_tie_apply_kernel(const float* __
     if (feat[i] == mx) atomicAdd(&grad[i], tie_term);
 }
 
+// ---- order-fixed backward of the loss node's sampled rows (the deterministic mode) -------------------------------------
+// select_normalize_bwd_kernel (loss.hip) and det_rows_bwd_kernel / det_rows_tie_apply_kernel add into ONE dense gradient
+// with float atomics: a point sampled twice, a point that is a neighbor of several sampled rows with the same winning
+// channel, an arg-max position that is also a target -- the sum then depends on arrival order.  Here every contribution is
+// first STORED as a record {key, value}, the keys are sorted (by the caller, between the two entries) and one thread per
+// destination element adds that element's records in key order.  Row m2 (anchors, then positives) owns R = C + 3 + H
+// record slots, in this order:
+//     slot c < C      the normalisation's term for element (row, c)         (as select_normalize_bwd_kernel)
+//     slot C, C + 1   the detector's own c* term, then its c' term          (as det_rows_bwd_kernel, lane 0)
+//     slot C + 2 + h  the -du/num term for (neighbor h of the row, c*)      (as det_rows_bwd_kernel, lane h)
+//     slot C + 2 + H  the score gradient of the row (only without the rows-form detector: element N C + row)
+// record r = m2 R + slot has key = element * (2 M R) + r, or kNoRecord where the atomic form adds nothing.  So an element of
+// the gradient is, left to right in float32:  0, then its records of ascending sampled row m2, inside a row in slot order
+// (normalise, c*, c', neighbors by slot), and LAST the group's arg-max (tie) term when the element is an arg-max position.
+constexpr long long kNoRecord = 0x7fffffffffffffffll;
+
+__global__ __launch_bounds__(256) void loss_rows_records_kernel(const float* __restrict__ feat, int N, int C,
+                                                                const int32_t* __restrict__ idx, int H,
+                                                                const float* __restrict__ fmax, d3f::RowGroups rg,
+                                                                d3f::SampledRows sr, const float* __restrict__ aux,
+                                                                const float* __restrict__ g_a,
+                                                                const float* __restrict__ g_p,
+                                                                const float* __restrict__ g_sa,
+                                                                const float* __restrict__ g_sp, int with_scores,
+                                                                long long* __restrict__ rec_key,
+                                                                float* __restrict__ rec_val, float* __restrict__ part,
+                                                                int32_t* __restrict__ pgroup) {
+  const int lane = threadIdx.x & 63;
+  const int m2 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m2 >= 2 * sr.M) return;
+  const int R = C + 3 + H;
+  const long long nrec = 2ll * sr.M * R, first = (long long)m2 * R;
+  long long* key = rec_key + first;
+  float* val = rec_val + first;
+  const bool pos = m2 >= sr.M;
+  const int m = pos ? m2 - sr.M : m2;
+  const long row = d3f::sampled_row(sr, m2, N);
+  // the normalisation: grad_x[row, :] += g/n - y (y.g)/n, the arithmetic of select_normalize_bwd_kernel
+  const float* g = pos ? g_p : g_a;
+  if (g) g += (size_t)m * C;
+  float ss = 0.0f, dot = 0.0f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = feat[row * C + c];
+    ss += v * v;
+    dot += v * (g ? g[c] : 0.0f);
+  }
+  ss = d3f::wave_sum(ss);
+  dot = d3f::wave_sum(dot);
+  const float nrm = sqrtf(ss);
+  for (int c = lane; c < C; c += 64) {
+    const float v = feat[row * C + c];
+    const float gv = !g ? 0.0f : (nrm > 1e-12f ? (g[c] - v * dot / ss) / nrm : g[c] / 1e-12f);
+    key[c] = g ? (row * C + c) * nrec + first + c : kNoRecord;
+    val[c] = gv;
+  }
+  const float* gs = pos ? g_sp : g_sa;
+  const float ds = gs ? gs[m] : 0.0f;
+  if (lane == 0) {   // the dense score gradient (no rows-form detector)
+    const bool on = with_scores && gs;
+    key[C + 2 + H] = on ? ((long long)N * C + row) * nrec + first + C + 2 + H : kNoRecord;
+    val[C + 2 + H] = on ? ds : 0.0f;
+  }
+  // the detector on this row: the arithmetic of det_rows_bwd_kernel
+  long long k_star = kNoRecord, k_prime = kNoRecord, k_nb = kNoRecord;
+  float v_star = 0.0f, v_prime = 0.0f, v_nb = 0.0f, s = 0.0f;
+  int gi = 0;
+  if (aux) {
+    const int n = (int)row;
+    gi = d3f::group_of_row(rg, n);
+    const float denom = fmaxf(fmax[gi], 0.0f) + 1e-6f;
+    if (ds != 0.0f) {
+      const float4 a0 = *(const float4*)(aux + (size_t)m2 * 8);      // f*, alpha*, beta*, u*
+      const float4 a1 = *(const float4*)(aux + (size_t)m2 * 8 + 4);  // dmax, num, c*, c'
+      const int cstar = __float_as_int(a1.z), cprime = __float_as_int(a1.w);
+      const float sig = a0.w > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-a0.w));
+      const float du = ds * a0.z * sig;
+      const bool ok = (unsigned)cstar < (unsigned)C && (unsigned)cprime < (unsigned)C;
+      if (ok && lane < H) {
+        const int nb = idx[(size_t)n * H + lane];
+        if (nb >= 0 && nb < N) {
+          const float gn = -du / a1.y;
+          k_nb = ((long long)nb * C + cstar) * nrec + first + C + 2 + lane;
+          v_nb = gn / denom;
+          s = gn * (feat[(size_t)nb * C + cstar] / denom);
+        }
+      }
+      if (ok && lane == 0) {
+        const float inv = 1.0f / (1e-6f + a1.x);
+        const float v1 = du + ds * a0.y * inv, v2 = -ds * a0.y * a0.x * inv * inv;
+        k_star = ((long long)n * C + cstar) * nrec + first + C;
+        k_prime = ((long long)n * C + cprime) * nrec + first + C + 1;
+        v_star = v1 / denom;
+        v_prime = v2 / denom;
+        s += v1 * a0.x + v2 * a1.x;
+      }
+    }
+    s = d3f::wave_sum(s);
+  }
+  if (lane < H) {
+    key[C + 2 + lane] = k_nb;
+    val[C + 2 + lane] = v_nb;
+  }
+  if (lane == 0) {
+    key[C] = k_star;
+    val[C] = v_star;
+    key[C + 1] = k_prime;
+    val[C + 1] = v_prime;
+    if (aux) {
+      part[m2] = s;
+      pgroup[m2] = gi;
+    }
+  }
+}
+
+// one thread per SORTED record: the first record of an element adds that element's run up, left to right
+__global__ __launch_bounds__(256) void loss_rows_segsum_kernel(const long long* __restrict__ skey, long long n,
+                                                               long long nrec, const float* __restrict__ rec_val,
+                                                               float* __restrict__ grad, long long n_elem) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long long k = skey[i];
+  if (k < 0 || k == kNoRecord) return;
+  const long long e = k / nrec;
+  if (e >= n_elem || (i > 0 && skey[i - 1] / nrec == e)) return;
+  float acc = 0.0f;
+  for (long long j = i; j < n; ++j) {
+    const long long kj = skey[j];
+    if (kj == kNoRecord || kj / nrec != e) break;
+    acc += rec_val[kj % nrec];
+  }
+  grad[e] = acc;
+}
+
+// det_rows_tie_apply_kernel with plain adds: the listed positions of a group are distinct elements and the dense scan
+// visits every element once, so each element has ONE writer here, behind the segmented sums on the stream
+__global__ __launch_bounds__(256) void det_rows_tie_apply_ordered_kernel(const float* __restrict__ feat, int cap_rows,
+                                                                         int C, const float* __restrict__ fmax,
+                                                                         d3f::RowGroups rg, const float* __restrict__ part,
+                                                                         const int32_t* __restrict__ pgroup, int rows,
+                                                                         const int32_t* __restrict__ tie_count,
+                                                                         const unsigned long long* __restrict__ tie_list,
+                                                                         float* __restrict__ grad,
+                                                                         float* __restrict__ tie_term_out) {
+  const int g = blockIdx.y;
+  const int cnt = tie_count[g];
+  __shared__ float S;
+  if (threadIdx.x < 64) {
+    float s = 0.0f;
+    for (int m2 = threadIdx.x; m2 < rows; m2 += 64)
+      if (pgroup[m2] == g) s += part[m2];
+    s = d3f::wave_sum(s);
+    if (threadIdx.x == 0) S = s;
+  }
+  __syncthreads();
+  const float mx = fmaxf(fmax[g], 0.0f), denom = mx + 1e-6f;
+  const float ties = (float)cnt + (mx == 0.0f ? 1.0f : 0.0f);
+  const float tie_term = (-S / denom) / fmaxf(ties, 1.0f);
+  if (tie_term_out && threadIdx.x == 0) tie_term_out[g] = tie_term;
+  if (cnt <= DET_TIE_CAP) {
+    for (int t = threadIdx.x; t < cnt; t += blockDim.x) grad[tie_list[(size_t)g * DET_TIE_CAP + t]] += tie_term;
+    return;
+  }
+  size_t beg, end;
+  group_range(rg, cap_rows, C, beg, end);
+  for (size_t i = beg + threadIdx.x; i < end; i += blockDim.x)
+    if (feat[i] == mx) grad[i] += tie_term;
+}
+
 }  // namespace
 
 extern "C" {
@@ -749,6 +917,76 @@ int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* 
   det_rows_tie_scan_kernel<<<dim3(blocks, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, tie_count, tie_list);
   det_rows_tie_apply_kernel<<<dim3(1, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, part, pgroup, rows, tie_count,
                                                              tie_list, grad_x);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+/* ---- the same two backward passes without float atomics (see loss_rows_records_kernel) ---- */
+int d3f_loss_rows_record_width(int C, int H) { return (C < 1 || H < 0) ? 0 : C + 3 + H; }
+
+static bool loss_rows_keys_fit(int N, int C, long long nrec) {
+  return nrec >= 1 && ((double)N * (C + 1) + 1.0) * (double)nrec < 9.0e18;
+}
+
+int d3f_loss_rows_backward_records(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                   const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
+                                   int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                   const float* aux, const float* g_a, const float* g_p, const float* g_sa,
+                                   const float* g_sp, int with_scores, int64_t* rec_key, float* rec_val, void* ws,
+                                   size_t ws_bytes, void* stream_) {
+  d3f::SampledRows sr;
+  if (!d3f::make_sampled_rows(idx_a, idx_p, idx_stride, M, pairs, p_offset, pair_len, sr) || !feat || N < 1 || C < 1 ||
+      H < 0 || H > 64 || !rec_key || !rec_val || !ws || (aux && with_scores))
+    return D3F_EINVAL;
+  if (aux ? !det_rows_args_ok(feat, N, C, idx, H, feat_max, len, B, group, pairs, pair_len) : H != 0) return D3F_EINVAL;
+  const int rows = 2 * sr.M;
+  if (ws_bytes < d3f_detection_rows_ws_bytes(rows)) return D3F_EWORKSPACE;
+  if (!loss_rows_keys_fit(N, C, (long long)rows * (C + 3 + H))) return D3F_EINVAL;
+  const d3f::RowGroups rg = {(aux && group > 0) ? len : nullptr, B, group};
+  d3f::Carver cv(ws);
+  float* part = cv.take<float>(rows);
+  int32_t* pgroup = cv.take<int32_t>(rows);
+  loss_rows_records_kernel<<<d3f::cdiv(rows, 4), 256, 0, (hipStream_t)stream_>>>(
+      feat, N, C, idx, H, feat_max, rg, sr, aux, g_a, g_p, g_sa, g_sp, with_scores, (long long*)rec_key, rec_val, part,
+      pgroup);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_loss_rows_backward_apply(const float* feat, int N, int C, int H, const float* feat_max, const int32_t* len, int B,
+                                 int group, int rows, int with_detector, int with_scores, const int64_t* sorted_key,
+                                 const float* rec_val, float* grad_x, float* tie_term_out, void* ws, size_t ws_bytes,
+                                 void* stream_) {
+  if (!feat || N < 1 || C < 1 || H < 0 || H > 64 || rows < 2 || rows > (1 << 25) || !sorted_key || !rec_val || !grad_x ||
+      !ws || (with_detector && with_scores))
+    return D3F_EINVAL;
+  if (with_detector && (!feat_max || !d3f_detection_rows_supported(C, H) ||
+                        (len && (B < 1 || B > D3F_MAX_BATCH || group < 0))))
+    return D3F_EINVAL;
+  if (ws_bytes < d3f_detection_rows_ws_bytes(rows)) return D3F_EWORKSPACE;
+  const long long nrec = (long long)rows * (C + 3 + H);
+  if (!loss_rows_keys_fit(N, C, nrec)) return D3F_EINVAL;
+  hipStream_t stream = (hipStream_t)stream_;
+  const long long n_elem = (long long)N * (C + (with_scores ? 1 : 0));
+  d3f::Carver cv(ws);
+  float* part = cv.take<float>(rows);
+  int32_t* pgroup = cv.take<int32_t>(rows);
+  int32_t* tie_count = cv.take<int32_t>(D3F_MAX_BATCH);
+  unsigned long long* tie_list = cv.take<unsigned long long>((size_t)D3F_MAX_BATCH * DET_TIE_CAP);
+  if (d3f::zero_async(grad_x, sizeof(float) * (size_t)n_elem, stream) != hipSuccess) return D3F_ELAUNCH;
+  loss_rows_segsum_kernel<<<d3f::cdiv(nrec, 256), 256, 0, stream>>>((const long long*)sorted_key, nrec, nrec, rec_val,
+                                                                     grad_x, n_elem);
+  if (with_detector) {
+    const d3f::RowGroups rg = {group > 0 ? len : nullptr, B, group};
+    const int G = rg.len ? d3f::cdiv(B, group) : 1;
+    if (d3f::zero_async(tie_count, sizeof(int32_t) * (size_t)G, stream) != hipSuccess) return D3F_ELAUNCH;
+    int blocks = d3f::cdiv((long long)N * C, 256 * 16 * (long long)G);
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    det_rows_tie_scan_kernel<<<dim3(blocks, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, tie_count, tie_list);
+    det_rows_tie_apply_ordered_kernel<<<dim3(1, G), 256, 0, stream>>>(feat, N, C, feat_max, rg, part, pgroup, rows,
+                                                                       tie_count, tie_list, grad_x, tie_term_out);
+  }
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }

@@ -330,6 +330,48 @@ int d3f_bias_act_backward(const float* grad_out, const float* out, float slope, 
                                 ws_bytes, stream, false);
 }
 
+/* The two-pass form at EVERY row count (the deterministic mode): below 4096 rows d3f_bias_act_backward flushes its
+ * per-block column sums with float atomics; here they go to ws [blocks, C] and bias_sum_kernel adds them up in block
+ * order.  grad_bias / grad_bias2 are overwritten (no pre-cleared accumulators needed). */
+static int ordered_rows_per_block(int N, int C) {
+  const int cblocks = d3f::cdiv(C, 64);
+  int rows = 256;
+  while (rows > 16 && (long long)d3f::cdiv(N, rows) * cblocks < 1024) rows >>= 1;
+  return rows;
+}
+
+size_t d3f_bias_act_backward_ordered_ws_bytes(int N, int C) {
+  if (N < 1 || C < 1) return 256;
+  if (N >= 4096) return d3f_bias_act_backward_ws_bytes(N, C);
+  return d3f::align_up(sizeof(float) * (size_t)d3f::cdiv(N, ordered_rows_per_block(N, C)) * (size_t)C, 256);
+}
+
+int d3f_bias_act_backward_ordered(const float* grad_out, const float* out, float slope, int N, int C, float* grad_x,
+                                  float* grad_bias, float* grad_bias2, const float* row_div, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (!grad_out || !out || N < 0 || C < 1 || (!grad_x && !grad_bias) || (grad_bias2 && !grad_bias)) return D3F_EINVAL;
+  if (!grad_bias || N >= 4096) {   // nothing to sum, or the many-row two-pass form that is the default anyway
+    if (grad_bias && (!ws || ws_bytes < d3f_bias_act_backward_ws_bytes(N, C))) return D3F_EWORKSPACE;
+    return bias_act_backward_impl(grad_out, out, slope, N, C, grad_x, grad_bias, grad_bias2, 1, row_div, ws, ws_bytes,
+                                  stream, false);
+  }
+  if (N == 0) {
+    if (d3f::zero_async(grad_bias, sizeof(float) * (size_t)C, (hipStream_t)stream) != hipSuccess) return D3F_ELAUNCH;
+    if (grad_bias2 && d3f::zero_async(grad_bias2, sizeof(float) * (size_t)C, (hipStream_t)stream) != hipSuccess)
+      return D3F_ELAUNCH;
+    return D3F_OK;
+  }
+  if (!ws || ws_bytes < d3f_bias_act_backward_ordered_ws_bytes(N, C)) return D3F_EWORKSPACE;
+  const int rows = ordered_rows_per_block(N, C);
+  dim3 grid(d3f::cdiv(N, rows), d3f::cdiv(C, 64));
+  bias_act_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(grad_out, out, slope, N, C, rows, grad_x, grad_bias,
+                                                             grad_bias2, row_div, (float*)ws);
+  bias_sum_kernel<<<d3f::cdiv(C, 64), 1024, 0, (hipStream_t)stream>>>((const float*)ws, (int)grid.x, C, grad_bias,
+                                                                     grad_bias2);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
 static int bias_act_backward_impl(const float* grad_out, const float* out, float slope, int N, int C, float* grad_x,
                                   float* grad_bias, float* grad_bias2, int bias_prezeroed, const float* row_div,
                                   void* ws, size_t ws_bytes, void* stream, bool partial_only) {

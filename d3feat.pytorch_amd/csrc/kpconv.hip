@@ -137,6 +137,72 @@ __global__ __launch_bounds__(256) void kpconv_dx_kernel(const float* __restrict_
   }
 }
 
+// The same sum as a gather over the table's transpose (the deterministic mode): one wave per SUPPORT row s, lanes <->
+// input channels, the edges (q, s) of the row in the transpose's own order -- CSR (rev_ptr / rev_ent: ascending q, an edge
+// listed twice counts twice, as in the scatter) or the exact form (rev_rel [Ns, W] float4 {q - s, bits of q}, ranked, rows
+// end at the first index >= Nq).  grad_x[s, c] = sum over the edges of (sum_k w[q,s,k] gW[q,k,c]), every row written once.
+template <int CPL>
+__global__ __launch_bounds__(256) void kpconv_dx_rev_kernel(const float* __restrict__ q_pts,
+                                                            const float* __restrict__ s_pts,
+                                                            const int32_t* __restrict__ rev_ptr,
+                                                            const int32_t* __restrict__ rev_ent,
+                                                            const float4* __restrict__ rev_rel, int rev_width,
+                                                            const float* __restrict__ kp, int Nq, int Ns, int Cin, int K,
+                                                            float extent, const float* __restrict__ gW,
+                                                            float* __restrict__ grad_x, float gauss_denom, int mode) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= Ns) return;
+  const int kk = lane & 15;
+  const bool klive = kk < K;
+  const float kx = klive ? kp[3 * kk + 0] : 0.0f, ky = klive ? kp[3 * kk + 1] : 0.0f, kz = klive ? kp[3 * kk + 2] : 0.0f;
+  const float sx = s_pts[3 * (size_t)s + 0], sy = s_pts[3 * (size_t)s + 1], sz = s_pts[3 * (size_t)s + 2];
+  const int beg = rev_rel ? 0 : rev_ptr[s];
+  const int n = rev_rel ? rev_width : rev_ptr[s + 1] - beg;
+  float acc[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) acc[j] = 0.0f;
+  for (int i = 0; i < n; ++i) {
+    int q;
+    float rx, ry, rz;   // s - q, what the forward pass subtracts the kernel points from
+    if (rev_rel) {
+      const float4 v = rev_rel[(size_t)s * rev_width + i];
+      q = __float_as_int(v.w);
+      if ((unsigned)q >= (unsigned)Nq) break;
+      rx = -v.x; ry = -v.y; rz = -v.z;
+    } else {
+      q = rev_ent[beg + i];
+      if ((unsigned)q >= (unsigned)Nq) continue;
+      rx = sx - q_pts[3 * (size_t)q + 0]; ry = sy - q_pts[3 * (size_t)q + 1]; rz = sz - q_pts[3 * (size_t)q + 2];
+    }
+    const float dx = rx - kx, dy = ry - ky, dz = rz - kz;
+    const float d2 = dx * dx + dy * dy + dz * dz;
+    const float w = influence_weight(d2, klive, kk, extent, gauss_denom, mode);
+    const float* gq = gW + (size_t)q * K * Cin;
+    float e[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) e[j] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const float wk = __shfl(w, k, 64);
+      if (k < K) {
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+          const int c = lane + 64 * j;
+          e[j] = fmaf(wk, c < Cin ? gq[(size_t)k * Cin + c] : 0.0f, e[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) acc[j] += e[j];
+  }
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const int c = lane + 64 * j;
+    if (c < Cin) grad_x[(size_t)s * Cin + c] = acc[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // f32 MFMA GEMM with generic strides:  C[i,j] (+)= rscale[i] * sum_k A(i,k) * B(k,j)
 //   A(i,k) at A[i*sai + k*sak], B(k,j) at B[k*sbk + j*sbj], C row-major [M,N].
@@ -499,6 +565,33 @@ int d3f_kpconv_grad_input_modes(const float* q_pts, int Nq, const float* s_pts, 
   else if (cpl <= 4) D3F_DX(4);
   else D3F_DX(8);
 #undef D3F_DX
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+// grad_x [Ns, Cin] (OVERWRITTEN) of any channel count and mode as a gather over the table's transpose: no atomics
+int d3f_kpconv_grad_input_modes_gather(const float* q_pts, int Nq, const float* s_pts, int Ns, const int32_t* rev_ptr,
+                                       const int32_t* rev_ent, const float* rev_rel, int rev_width, int Cin,
+                                       const float* kernel_points, int K, float extent, int mode, const float* gwf,
+                                       float* grad_x, void* stream_) {
+  if (!q_pts || !s_pts || !kernel_points || !gwf || !grad_x || Nq < 0 || Ns < 0 || Cin < 1 || Cin > 512 || K < 1 ||
+      K > 16 || !(extent > 0.0f) || !mode_ok(mode))
+    return D3F_EINVAL;
+  if (rev_rel ? (rev_ptr || rev_ent || rev_width < 1 || ((uintptr_t)rev_rel & 15u)) : (!rev_ptr || !rev_ent))
+    return D3F_EINVAL;
+  if (Ns == 0) return D3F_OK;
+  const int grid = cdiv(Ns, 4);
+  const int cpl = cdiv(Cin, 64);
+  const float gd = gauss_denominator(extent);
+#define D3F_DXR(CPL)                                                                                                \
+  kpconv_dx_rev_kernel<CPL><<<grid, 256, 0, (hipStream_t)stream_>>>(q_pts, s_pts, rev_ptr, rev_ent,                 \
+                                                                    (const float4*)rev_rel, rev_width, kernel_points, \
+                                                                    Nq, Ns, Cin, K, extent, gwf, grad_x, gd, mode)
+  if (cpl <= 1) D3F_DXR(1);
+  else if (cpl <= 2) D3F_DXR(2);
+  else if (cpl <= 4) D3F_DXR(4);
+  else D3F_DXR(8);
+#undef D3F_DXR
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }

@@ -266,6 +266,138 @@ __global__ void closest_pool_bwd32_kernel(const float* __restrict__ go, uint32_t
   if (m >= 0 && m < Ns && v != 0.0f) atomicAdd(&gx[(uint32_t)m * C + c], v);
 }
 
+// ---- gather forms of the two backward passes (the deterministic mode) -------------------------------------------------
+// The scatters above add in arrival order.  These walk the CSR transpose of the table (reverse_table.hip: rev_ent[rev_ptr[s]
+// .. rev_ptr[s+1]) = the query rows that list support s, ASCENDING) and write every row of grad_x exactly once: no clear
+// launch, no atomic, the same bits on every replay.  A thread owns one float4 (or one float) of one support row, so the
+// threads of a row read the same entries (one broadcast request) and 16 contiguous bytes of each listed query row; four
+// entries are fetched before the first is added.
+//   max_pool      gx[s, c] = base[s, c] + go[q1, c] + go[q2, c] + ...   q1 < q2 < ... in rev(s) with argmax[q, c] == s
+//   closest_pool  gx[s, c] = go[n1, c] + go[n2, c] + ...                n1 < n2 < ... with idx[n, 0] == s (rev of column 0)
+// added left to right in float32; base (optional, may be gx itself) is a gradient an older consumer left for the same
+// tensor and comes FIRST.  A query that lists s twice is one term; rows nobody lists and shadow entries give base / 0.
+template <typename I>
+__global__ __launch_bounds__(256) void max_pool_bwd_gather_kernel(const float* __restrict__ go,
+                                                                  const int32_t* __restrict__ argmax,
+                                                                  const int32_t* __restrict__ ptr,
+                                                                  const int32_t* __restrict__ ent, I total, I C, int Nq,
+                                                                  const float* base, float* gx) {
+  const I t = (I)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const I s = t / C, c = t - s * C;
+  float acc = base ? base[t] : 0.0f;
+  int prev = -1;
+  for (int i = ptr[s], e = ptr[s + 1]; i < e; ++i) {
+    const int q = ent[i];
+    if (q == prev || (unsigned)q >= (unsigned)Nq) continue;
+    prev = q;
+    const I o = (I)q * C + c;
+    if (argmax[o] == (int)s) acc += go[o];
+  }
+  gx[t] = acc;
+}
+
+__global__ __launch_bounds__(256) void max_pool_bwd_gather_v4_kernel(const float4* __restrict__ go,
+                                                                     const int4* __restrict__ argmax,
+                                                                     const int32_t* __restrict__ ptr,
+                                                                     const int32_t* __restrict__ ent, uint32_t total4,
+                                                                     uint32_t C4, int Nq, const float4* base, float4* gx) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total4) return;
+  const uint32_t s = t / C4, c4 = t - s * C4;
+  const int si = (int)s;
+  float4 acc = base ? base[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+  int prev = -1;
+  int i = ptr[s];
+  const int e = ptr[s + 1];
+  for (; i + 4 <= e; i += 4) {
+    int q[4];
+    bool live[4];
+    int4 a[4];
+    float4 g[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = ent[i + j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) live[j] = q[j] != (j ? q[j - 1] : prev) && (unsigned)q[j] < (unsigned)Nq;
+    prev = q[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {   // (a dead entry re-reads row 0: entries exist only when Nq > 0)
+      const uint32_t o = (uint32_t)(live[j] ? q[j] : 0) * C4 + c4;
+      a[j] = argmax[o];
+      g[j] = go[o];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (live[j] && a[j].x == si) acc.x += g[j].x;
+      if (live[j] && a[j].y == si) acc.y += g[j].y;
+      if (live[j] && a[j].z == si) acc.z += g[j].z;
+      if (live[j] && a[j].w == si) acc.w += g[j].w;
+    }
+  }
+  for (; i < e; ++i) {
+    const int q = ent[i];
+    if (q == prev || (unsigned)q >= (unsigned)Nq) continue;
+    prev = q;
+    const uint32_t o = (uint32_t)q * C4 + c4;
+    const int4 a = argmax[o];
+    const float4 g = go[o];
+    if (a.x == si) acc.x += g.x;
+    if (a.y == si) acc.y += g.y;
+    if (a.z == si) acc.z += g.z;
+    if (a.w == si) acc.w += g.w;
+  }
+  gx[t] = acc;
+}
+
+template <typename I>
+__global__ __launch_bounds__(256) void closest_pool_bwd_gather_kernel(const float* __restrict__ go, I ld,
+                                                                      const int32_t* __restrict__ ptr,
+                                                                      const int32_t* __restrict__ ent, I total, I C,
+                                                                      int Nq, float* __restrict__ gx) {
+  const I t = (I)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const I s = t / C, c = t - s * C;
+  float acc = 0.0f;
+  for (int i = ptr[s], e = ptr[s + 1]; i < e; ++i) {
+    const int n = ent[i];
+    if ((unsigned)n < (unsigned)Nq) acc += go[(I)n * ld + c];
+  }
+  gx[t] = acc;
+}
+
+// ld4 = row stride of go in float4
+__global__ __launch_bounds__(256) void closest_pool_bwd_gather_v4_kernel(const float4* __restrict__ go, uint32_t ld4,
+                                                                         const int32_t* __restrict__ ptr,
+                                                                         const int32_t* __restrict__ ent, uint32_t total4,
+                                                                         uint32_t C4, int Nq, float4* __restrict__ gx) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total4) return;
+  const uint32_t s = t / C4, c4 = t - s * C4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int i = ptr[s];
+  const int e = ptr[s + 1];
+  for (; i + 4 <= e; i += 4) {
+    int n[4];
+    float4 g[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) n[j] = ent[i + j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g[j] = go[(uint32_t)((unsigned)n[j] < (unsigned)Nq ? n[j] : 0) * ld4 + c4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((unsigned)n[j] < (unsigned)Nq) {
+        acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; acc.w += g[j].w;
+      }
+  }
+  for (; i < e; ++i) {
+    const int n = ent[i];
+    if ((unsigned)n >= (unsigned)Nq) continue;
+    const float4 g = go[(uint32_t)n * ld4 + c4];
+    acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
+  }
+  gx[t] = acc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -349,6 +481,54 @@ int d3f_closest_pool_backward(const float* grad_out, int ld, const int32_t* idx,
   else
     closest_pool_bwd_kernel<<<d3f::cdiv((long long)Nq * C, 256), 256, 0, (hipStream_t)stream>>>(grad_out, ld, idx, Nq,
                                                                                                 H, C, Ns, grad_x);
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_max_pool_backward_gather(const float* grad_out, const int32_t* argmax, int Nq, int C, int Ns,
+                                 const int32_t* rev_ptr, const int32_t* rev_ent, const float* grad_base, float* grad_x,
+                                 void* stream) {
+  if (((!grad_out || !argmax) && Nq > 0) || !rev_ptr || !rev_ent || !grad_x || Nq < 0 || C < 1 || Ns < 0)
+    return D3F_EINVAL;   // (no query rows: nothing is read through grad_out / argmax, every row is grad_base or 0)
+  if (Ns == 0) return D3F_OK;
+  const long long total = (long long)Ns * C;
+  const bool small = (long long)Nq * C < (1ll << 31) && total < (1ll << 31);
+  const bool aligned = ((uintptr_t)grad_out | (uintptr_t)argmax | (uintptr_t)grad_base | (uintptr_t)grad_x) % 16 == 0;
+  if (small && aligned && C % 4 == 0)
+    max_pool_bwd_gather_v4_kernel<<<d3f::cdiv(total / 4, 256), 256, 0, (hipStream_t)stream>>>(
+        (const float4*)grad_out, (const int4*)argmax, rev_ptr, rev_ent, (uint32_t)(total / 4), (uint32_t)(C / 4), Nq,
+        (const float4*)grad_base, (float4*)grad_x);
+  else if (small)
+    max_pool_bwd_gather_kernel<uint32_t><<<d3f::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(
+        grad_out, argmax, rev_ptr, rev_ent, (uint32_t)total, (uint32_t)C, Nq, grad_base, grad_x);
+  else if (total < 256ll * 0x7fffffffll)
+    max_pool_bwd_gather_kernel<size_t><<<d3f::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(
+        grad_out, argmax, rev_ptr, rev_ent, (size_t)total, (size_t)C, Nq, grad_base, grad_x);
+  else
+    return D3F_EINVAL;
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
+int d3f_closest_pool_backward_gather(const float* grad_out, int ld, int Nq, int C, int Ns, const int32_t* rev_ptr,
+                                     const int32_t* rev_ent, float* grad_x, void* stream) {
+  if ((!grad_out && Nq > 0) || !rev_ptr || !rev_ent || !grad_x || Nq < 0 || C < 1 || Ns < 0 || ld < C) return D3F_EINVAL;
+  if (Ns == 0) return D3F_OK;
+  const long long total = (long long)Ns * C;
+  const bool small = (long long)Nq * ld < (1ll << 31) && total < (1ll << 31);
+  const bool aligned = ((uintptr_t)grad_out | (uintptr_t)grad_x) % 16 == 0;
+  if (small && aligned && C % 4 == 0 && ld % 4 == 0)
+    closest_pool_bwd_gather_v4_kernel<<<d3f::cdiv(total / 4, 256), 256, 0, (hipStream_t)stream>>>(
+        (const float4*)grad_out, (uint32_t)(ld / 4), rev_ptr, rev_ent, (uint32_t)(total / 4), (uint32_t)(C / 4), Nq,
+        (float4*)grad_x);
+  else if (small)
+    closest_pool_bwd_gather_kernel<uint32_t><<<d3f::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(
+        grad_out, (uint32_t)ld, rev_ptr, rev_ent, (uint32_t)total, (uint32_t)C, Nq, grad_x);
+  else if (total < 256ll * 0x7fffffffll)
+    closest_pool_bwd_gather_kernel<size_t><<<d3f::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(
+        grad_out, (size_t)ld, rev_ptr, rev_ent, (size_t)total, (size_t)C, Nq, grad_x);
+  else
+    return D3F_EINVAL;
   D3F_LAUNCH_CHECK();
   return D3F_OK;
 }

@@ -387,7 +387,9 @@ def build_pyramid(points, lengths, config, neighborhood_limits, index_dtype=torc
                     lst[li] = lst[li][:, :w].contiguous()
     if reverse_tables and not search_form and index_dtype == torch.int32:
         # reference-width (trimmed) tables: CSR transposes of the tables KPConv runs on (conv + pooling), attached to the
-        # tables themselves (ops.build_reverse_table), so the batch dict keeps the reference's keys
+        # tables themselves (ops.build_reverse_table), so the batch dict keeps the reference's keys.  Under the
+        # deterministic mode ops.wants_reverse_table holds for every level, here and in the static builders above: the
+        # few-point levels get their transposes too
         level = 0
         for li, e in enumerate(walk.layers):
             if e['conv_r'] is not None and ops.wants_reverse_table(pts[level].shape[0]):

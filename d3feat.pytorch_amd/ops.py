@@ -486,8 +486,83 @@ UPSAMPLES_FROM_POOL = True
 
 
 def wants_reverse_table(Ns):
-    """Whether a table over ``Ns`` supports is worth transposing (what the pyramid builders ask)."""
+    """Whether a table over ``Ns`` supports is worth transposing (what the pyramid builders ask).  Under the deterministic
+    mode every table is: the few-point levels' grad-input is a gather too."""
+    if _DETERMINISTIC:
+        return int(Ns) > 0
     return int(Ns) >= DX_GATHER_MIN_ROWS
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# deterministic mode: a training step without float atomics (DESIGN section 5)
+# ---------------------------------------------------------------------------------------------------------------
+# Process-wide, off by default, and no environment variable.  An autograd node reads it when its FORWARD runs and keeps the
+# choice on ``ctx``: its backward follows its forward, and a captured graph keeps the mode it was captured in.  Under it
+# every float-atomic scatter of the step is replaced by an order-fixed form (the table in DESIGN section 5); an operator
+# that has none raises instead of running.
+_DETERMINISTIC = False
+# how many launches of the scatter (atomic) forms a step has two forms for (pool backward, few-point KPConv grad-input,
+# the loss node's sparse backward) / of the order-fixed replacements the dispatch made: tests assert on these that a mode
+# did or did not reach a form
+DISPATCH_COUNTS = {'scatter': 0, 'ordered': 0}
+
+
+def set_deterministic(flag):
+    """Switch the deterministic mode on or off for the process; returns the previous setting."""
+    global _DETERMINISTIC
+    old, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    return old
+
+
+def is_deterministic():
+    return _DETERMINISTIC
+
+
+class deterministic_mode(object):
+    """``with ops.deterministic_mode(True): ...`` -- the mode for the nodes whose forward runs inside (and for the pyramid
+    built inside); restores the previous setting on exit.  The setting is the process's, not a thread's: scopes on different
+    threads must not overlap (the training engines enter theirs one at a time)."""
+
+    def __init__(self, flag=True):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.old = set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        set_deterministic(self.old)
+        return False
+
+
+def _no_deterministic_form(op, why="its backward adds with float atomics"):
+    """What torch does for an operator without a deterministic implementation."""
+    raise RuntimeError("%s does not have a deterministic implementation (%s), but the deterministic mode is on "
+                       "(ops.set_deterministic(True)).  Turn the mode off for this operation, or use an operator that has "
+                       "an order-fixed form." % (op, why))
+
+
+def _count(kind):
+    DISPATCH_COUNTS[kind] += 1
+
+
+def _csr_of(idx, Ns):
+    """CSR transpose of a table for the gather-form pool backward: (ptr, ent), NOT attached to the table (a pooling table
+    carries its KPConv transpose there).  Built where the node's forward runs: in a captured step the table's contents
+    change from replay to replay, the build is part of the graph."""
+    Nq, H = int(idx.shape[0]), int(idx.shape[1])
+    if Nq * H == 0:     # no entry: every row of the transpose is empty
+        return (torch.zeros(int(Ns) + 1, dtype=torch.int32, device=idx.device),
+                torch.zeros(1, dtype=torch.int32, device=idx.device))
+    ptr = torch.empty(int(Ns) + 1, dtype=torch.int32, device=idx.device)
+    ent = torch.empty(max(Nq * H, 1), dtype=torch.int32, device=idx.device)
+    L = _native.lib()
+    nbytes = L.d3f_reverse_table_ws_bytes(Nq, H, int(Ns))
+    ws = _ws(nbytes, idx.device)
+    with _region("reverse_table[Nq=%d,H=%d,Ns=%d]" % (Nq, H, Ns), 12 * Nq * H + 8 * Ns):
+        _native.check(L.d3f_reverse_table_build(_p(idx), Nq, H, int(Ns), _p(ptr), _p(ent), _p(ws), nbytes, _stream()),
+                      "d3f_reverse_table_build")
+    return ptr, ent
 
 
 
@@ -667,6 +742,7 @@ class _KPConvFn(torch.autograd.Function):
             gwf = _kpconv_gw(gon, weights, Nq, K, Cin, Cout)
             nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
             ws = _ws(nbytes, x.device)
+            _count('scatter')
             with _region("kpconv_dx_scatter[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * K * Cin + 4 * Nq * H * (1 + Cin)):
                 _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
                                                       _p(kernel_points), K, ctx.extent, _p(gwf), _p(keep), pre, _p(gx),
@@ -757,7 +833,17 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
         L = _native.lib()
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
         K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
-        if rev is not None and not (Ns >= DX_GATHER_MIN_ROWS and L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K)):
+        det = ctx.det = _DETERMINISTIC
+        if det and ctx.needs_input_grad[3]:
+            # the gather form at EVERY row count; a table that came without a transpose gets its CSR form here
+            if not L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K):
+                _no_deterministic_form("KPConv grad-input for %d -> %d channels" % (Cin, Cout),
+                                       "the gather form does not cover these channel counts")
+            if rev is None:
+                ptr, ent = _csr_of(idx, Ns)
+                rev = ReverseTable(ent, Nq, H, Ns, ptr=ptr)
+        elif rev is not None and not (Ns >= DX_GATHER_MIN_ROWS and
+                                      L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K)):
             rev = None
         ctx.rev = rev
         dev = x.device
@@ -815,7 +901,7 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
         atb = (ctx.needs_input_grad[5] and Nq >= _SPLITK_MIN_ROWS
                and bool(L.d3f_linear_grad_weight_supported(Nq, Cout, K * Cin))
                and not (K * Cin * Cout >= _DW_LIBRARY_MIN_OUT and Nq <= _DW_LIBRARY_MAX_ROWS))
-        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, Nq, Cout, gon, gb, None, pre, nn, atb)
+        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, Nq, Cout, gon, gb, None, pre, nn, atb, ctx.det)
         gx = gw = None
         if ctx.needs_input_grad[5]:
             gw = _grad_target(ctx.gw_slot, weights)
@@ -853,6 +939,7 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
             gwf = _kpconv_gw(gon, weights, Nq, K, Cin, Cout)
             nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
             ws = _ws(nbytes, x.device)
+            _count('scatter')
             with _region("kpconv_dx_scatter[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * K * Cin + 4 * Nq * H * (1 + Cin)):
                 _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
                                                       _p(kernel_points), K, ctx.extent, _p(gwf), _p(ctx.keep), pre,
@@ -876,7 +963,15 @@ def kpconv_bias_act(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent
     q_pts, s_pts, x = _f32(q_pts, "q_pts"), _f32(s_pts, "s_pts"), _f32(x, "x")
     Nq, H = int(q_pts.shape[0]), int(neighb_inds.shape[1])
     K, Cin = int(weights.shape[0]), int(weights.shape[1])
-    if _takes_gemm_path(Nq, Cin) and s_pts.shape[0] > 0 and \
+    gemm_path = _takes_gemm_path(Nq, Cin)
+    if _DETERMINISTIC and torch.is_grad_enabled() and Nq > 0:
+        # deterministic mode: the aggregation + GEMM node at every row count (its grad-input is the gather form); the
+        # channel counts the gather kernel does not cover go through ops.kpconv's order-fixed node below
+        gemm_path = not x.requires_grad or bool(
+            _native.lib().d3f_kpconv_grad_input_gather_supported(Cin, int(weights.shape[2]), K))
+    elif _DETERMINISTIC and not torch.is_grad_enabled() and x.requires_grad:
+        x = x.detach()      # (no graph is recorded: the node must not ask for a grad-input form it will never run)
+    if gemm_path and s_pts.shape[0] > 0 and \
             _native.lib().d3f_kpconv_grad_input_supported(Cin, K, H, int(s_pts.shape[0])):
         idx = _i32(neighb_inds, "neighb_inds")
         kp, w = _f32(kernel_points, "kernel_points"), _f32(weights, "weights")
@@ -946,6 +1041,62 @@ class _KPConvModesFn(torch.autograd.Function):
         return None, None, None, gx, None, gw, None, None
 
 
+class _KPConvOrderedFn(torch.autograd.Function):
+    """KPConv of ANY channel count and mode under the deterministic mode: the general path's aggregation kernel (a gather,
+    one wave per query) -> wf, nn; the contraction with the kernel weights by GEMMs; grad_W = wf^T (g / nn) on the
+    weight-gradient routes of the other nodes; grad_x as a GATHER over the table's transpose
+    (d3f_kpconv_grad_input_modes_gather) in place of the scatters of _KPConvFn / _KPConvModesFn.  ``rev``: the table's
+    ReverseTable in CSR or exact form; None: its CSR transpose is built here."""
+
+    @staticmethod
+    def forward(ctx, q_pts, s_pts, idx, x, kp, weights, extent, mode, rev):
+        L = _native.lib()
+        Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
+        K, Cin, Cout = (int(v) for v in weights.shape)
+        wf = torch.empty((Nq, K * Cin), dtype=torch.float32, device=x.device)
+        nn_ = torch.empty((Nq,), dtype=torch.float32, device=x.device)
+        with _region("kpconv_ordered_fwd[Nq=%d,Cin=%d,H=%d,mode=%d]" % (Nq, Cin, H, mode), 4 * Nq * H * (4 + Cin)):
+            _native.check(L.d3f_kpconv_aggregate_modes(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin, _p(kp), K,
+                                                       extent, mode, _p(wf), _p(nn_), _stream()),
+                          "d3f_kpconv_aggregate_modes")
+        out = torch.mm(wf, weights.reshape(K * Cin, Cout)) / nn_[:, None]
+        if ctx.needs_input_grad[3]:
+            if rev is not None and rev.ptr is None and rev.rel is None:
+                rev = None      # (a search-form transpose: not one of the kernel's two forms)
+            if rev is None:
+                ptr, ent = _csr_of(idx, Ns)
+                rev = ReverseTable(ent, Nq, H, Ns, ptr=ptr)
+        ctx.rev = rev
+        ctx.save_for_backward(q_pts, s_pts, kp, weights, wf, nn_)
+        ctx.extent, ctx.mode, ctx.gw_slot = extent, mode, _grad_slot(weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q_pts, s_pts, kp, weights, wf, nn_ = ctx.saved_tensors
+        L = _native.lib()
+        Nq, Ns = int(q_pts.shape[0]), int(s_pts.shape[0])
+        K, Cin, Cout = (int(v) for v in weights.shape)
+        g = grad_out.contiguous() / nn_[:, None]
+        gx = gw = None
+        if ctx.needs_input_grad[5]:
+            gw = _grad_target(ctx.gw_slot, weights)
+            atb = Nq >= _SPLITK_MIN_ROWS and bool(L.d3f_linear_grad_weight_supported(Nq, Cout, K * Cin))
+            _weight_grad(g, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), atb, label="kpconv_dw_atb",
+                         gemm_label="kpconv_dw_gemm[Nq=%d,Cin=%d,Cout=%d]" % (Nq, Cin, Cout))
+        if ctx.needs_input_grad[3]:
+            rev = ctx.rev
+            gwf = torch.mm(g, weights.reshape(K * Cin, Cout).t()).contiguous()
+            gx = torch.empty((Ns, Cin), dtype=torch.float32, device=g.device)
+            _count('ordered')
+            with _region("kpconv_ordered_dx[Ns=%d,Cin=%d,mode=%d]" % (Ns, Cin, ctx.mode), 8 * Nq * K * Cin):
+                _native.check(L.d3f_kpconv_grad_input_modes_gather(
+                    _p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent) if rev.ptr is not None else None,
+                    _p(rev.rel), rev.width, Cin, _p(kp), K, ctx.extent, ctx.mode, _p(gwf), _p(gx), _stream()),
+                    "d3f_kpconv_grad_input_modes_gather")
+        return None, None, None, gx, None, _adoptable(gw, ctx.gw_slot), None, None, None
+
+
 def kpconv(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent, influence='linear', aggregation='sum',
            rev=None):
     """Rigid KPConv.  Shapes as KPConv.forward (blocks.py:237); 'linear' / 'sum' (the D3Feat configuration) runs on
@@ -958,6 +1109,21 @@ def kpconv(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent, influen
     if x.shape[0] != s_pts.shape[0] or x.shape[1] != w.shape[1] or idx.shape[0] != q_pts.shape[0]:
         raise RuntimeError("KPConv: inconsistent shapes q%s s%s idx%s x%s W%s" % (
             tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape)))
+    if _DETERMINISTIC and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
+        # a training call under the deterministic mode: every mode and channel count through the order-fixed node
+        # (_KPConvFn's kernels combine channel chunks, waves and weight-gradient partials with float atomics, _KPConvFn /
+        # _KPConvModesFn scatter their grad-input)
+        if q_pts.shape[0] == 0 or s_pts.shape[0] == 0:
+            return x.new_zeros((q_pts.shape[0], w.shape[2])) + 0.0 * (x.sum() + w.sum())
+        # ... but the input layer (features without gradient) on the input-layer kernels: their forward has no atomic and,
+        # where they save the weighted features (16-slot rows: Cout % 16 == 0), grad_W is the A^T B kernel over them
+        # (asked at K = 1, where the 16-slot rows cannot be mistaken for K * Cin)
+        if mode == 0 and not x.requires_grad and SAVE_WEIGHTED_FEATURES and \
+                _native.lib().d3f_kpconv_saves_wf(int(w.shape[1]), int(w.shape[2]), 1, int(idx.shape[1])) == 16 * int(w.shape[1]):
+            return _KPConvFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), None, None)
+        if x.requires_grad:
+            rev = reverse_table_of(neighb_inds, int(q_pts.shape[0]), int(idx.shape[1]), int(s_pts.shape[0]), rev)
+        return _KPConvOrderedFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), mode, rev if x.requires_grad else None)
     if mode != 0:
         if q_pts.shape[0] == 0 or s_pts.shape[0] == 0:
             return x.new_zeros((q_pts.shape[0], w.shape[2])) + 0.0 * (x.sum() + w.sum())
@@ -1029,6 +1195,8 @@ def kpconv_deformable(q_pts, s_pts, neighb_inds, x, kernel_points, weights, exte
         raise RuntimeError("deformable KPConv: inconsistent shapes q%s s%s idx%s x%s W%s offsets%s" % (
             tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape),
             tuple(offsets.shape)))
+    if _DETERMINISTIC and torch.is_grad_enabled() and x.requires_grad:
+        _no_deterministic_form("kpconv_deformable")
     deformed = offsets + kp                                              # blocks.py:287
     extent = float(extent)
     extent_sq = float(np.float32(extent ** 2))                           # the float32 scalar of `sq_distances < ext**2`
@@ -1355,9 +1523,10 @@ def linear_pair_bias_act(x1, w1, b1a, b1b, x2, w2, b2a, b2b, slope=0.1, grad_dep
 # The bias gradient's second pass rides in the weight gradient's second-stage launch (csrc/linear.hip,
 # atb_reduce_bias_kernel) whenever both are two-pass forms: N >= 4096 rows for the epilogue's backward and the A^T B
 # kernel for grad_W -- the nodes pass ``fold`` = "this node's weight gradient takes the A^T B path".
-def _epilogue_backward(go, out, slope, N, C, gm, first, second, pre, row_div, fold):
+def _epilogue_backward(go, out, slope, N, C, gm, first, second, pre, row_div, fold, det=False):
     """grad through act(. + biases): masked gradient into ``gm`` (None: not wanted) and the bias gradient(s).  With
-    ``fold`` only the first pass runs; returns (partials, blocks) for d3f_linear_grad_weight_bias, else (None, 0)."""
+    ``fold`` only the first pass runs; returns (partials, blocks) for d3f_linear_grad_weight_bias, else (None, 0).
+    ``det``: the node ran its forward under the deterministic mode -- the two-pass form at every row count."""
     L = _native.lib()
     wsb, nws = _bias_bwd_ws(N, C, go.device) if first is not None else (None, 0)
     nblk = int(L.d3f_bias_act_backward_blocks(N, C)) if (fold and first is not None and wsb is not None) else 0
@@ -1365,10 +1534,24 @@ def _epilogue_backward(go, out, slope, N, C, gm, first, second, pre, row_div, fo
         _native.check(L.d3f_bias_act_backward_partial(_p(go), _p(out), float(slope), N, C, _p(gm), _p(row_div), _p(wsb),
                                                       nws, _stream()), "d3f_bias_act_backward_partial")
         return wsb, nblk
+    if det and first is not None:
+        _bias_act_backward_ordered(go, out, slope, N, C, gm, first, second, row_div)
+        return None, 0
     _native.check(L.d3f_bias_act_backward(_p(go), _p(out), float(slope), N, C, _p(gm), _p(first), _p(second),
                                           pre if first is not None else 0, _p(row_div), _p(wsb), nws, _stream()),
                   "d3f_bias_act_backward")
     return None, 0
+
+
+def _bias_act_backward_ordered(go, out, slope, N, C, gm, first, second, row_div):
+    """d3f_bias_act_backward without its float atomics (deterministic mode): column sums per row block, added in block
+    order; ``first`` / ``second`` are overwritten."""
+    L = _native.lib()
+    nws = int(L.d3f_bias_act_backward_ordered_ws_bytes(N, C))
+    ws = _ws(nws, go.device)
+    _count('ordered')
+    _native.check(L.d3f_bias_act_backward_ordered(_p(go), _p(out), float(slope), N, C, _p(gm), _p(first), _p(second),
+                                                  _p(row_div), _p(ws), nws, _stream()), "d3f_bias_act_backward_ordered")
 
 
 class WeightGradGroup(object):
@@ -1518,6 +1701,7 @@ class _LinearLibBiasActFn(torch.autograd.Function):
         ctx.gbuf, ctx.slope = gbuf, float(slope)
         ctx.has = (b1 is not None, add is not None, b2 is not None)
         ctx.gw_slot = _grad_slot(weight)
+        ctx.det = _DETERMINISTIC
         raw = torch.mm(x, weight.t())
         out = torch.empty_like(raw)
         if pack is not None:
@@ -1559,7 +1743,7 @@ class _LinearLibBiasActFn(torch.autograd.Function):
         else:
             gm = go if identity else torch.empty_like(go)
             bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, None if identity else gm, first,
-                                                        second, pre, None, atb)
+                                                        second, pre, None, atb, ctx.det)
         gx = _add_deposited(ctx.holder, gm, weight) if ctx.needs_input_grad[0] else None
         if gx is not None and ctx.dep is not None and ctx.dep.deposit(gx):
             gx = None
@@ -1600,6 +1784,9 @@ class _UpsampleLinearFn(torch.autograd.Function):
         ctx.gbuf, ctx.gt_buf, ctx.slope = gbuf, gt_buf, float(slope)
         ctx.has = (b1 is not None, b2 is not None)
         ctx.gw_slot = _grad_slot(weight)
+        # deterministic mode: the pooled gradient is a gather over the transpose of the table's column 0
+        ctx.det = _DETERMINISTIC
+        ctx.csr = _csr_of(idx[:, :1].contiguous(), Nc) if ctx.det else None
         return out
 
     @staticmethod
@@ -1616,14 +1803,19 @@ class _UpsampleLinearFn(torch.autograd.Function):
         gm = torch.empty_like(go)
         atb = (ctx.needs_input_grad[3] and N >= _SPLITK_MIN_ROWS
                and bool(L.d3f_linear_grad_weight_supported(N, Cs, Cout)))
-        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, gm, first, second, pre, None, atb)
+        bias_part, bias_blocks = _epilogue_backward(go, out, ctx.slope, N, Cout, gm, first, second, pre, None, atb,
+                                                    ctx.det)
         # pooled gradient of the coarse product: g_t[m] = sum_{n: idx[n,0] = m} gm[n]
         gt, ctx.gt_buf = ctx.gt_buf, None
         pre_t = 1 if gt is not None else 0
         if gt is None:
             gt = torch.empty((Nc, Cout), dtype=torch.float32, device=go.device)
-        _native.check(L.d3f_closest_pool_backward(_p(gm), Cout, _p(idx), N, H, Cout, Nc, _p(gt), pre_t, _stream()),
-                      "d3f_closest_pool_backward")
+        if ctx.det:
+            _closest_pool_backward_gather(gm, Cout, N, Cout, Nc, ctx.csr, gt)
+        else:
+            _count('scatter')
+            _native.check(L.d3f_closest_pool_backward(_p(gm), Cout, _p(idx), N, H, Cout, Nc, _p(gt), pre_t, _stream()),
+                          "d3f_closest_pool_backward")
         w1, w2 = weight[:, :Cc], weight[:, Cc:]
         gxc = torch.mm(gt, w1) if ctx.needs_input_grad[0] else None
         gskip = torch.mm(gm, w2) if ctx.needs_input_grad[2] else None
@@ -1703,7 +1895,8 @@ class _MaxPoolFn(torch.autograd.Function):
         Nq, H = int(idx.shape[0]), int(idx.shape[1])
         out = torch.empty((Nq, C), dtype=torch.float32, device=x.device)
         arg = torch.empty((Nq, C), dtype=torch.int32, device=x.device)
-        gx_buf = torch.empty_like(x) if ctx.needs_input_grad[0] else None  # cleared by the forward launch
+        # cleared by the forward launch (the deterministic mode's gather writes every row: nothing to clear)
+        gx_buf = torch.empty_like(x) if (ctx.needs_input_grad[0] and not _DETERMINISTIC) else None
         with _region("max_pool_fwd[Nq=%d,C=%d]" % (Nq, C), 4 * Nq * H + 4 * Nq * H * C + 4 * Nq * C):
             _native.check(_native.lib().d3f_max_pool_forward(_p(x), Ns, C, _p(idx), Nq, H, _p(out), _p(arg),
                                                              _p(gx_buf), _p(width), _p(g_len),
@@ -1712,6 +1905,9 @@ class _MaxPoolFn(torch.autograd.Function):
         ctx.save_for_backward(arg)
         ctx.shape = (Ns, C)
         ctx.gx_buf = gx_buf
+        # deterministic mode: the backward gathers over the CSR transpose of the pooling table
+        ctx.det = _DETERMINISTIC
+        ctx.csr = _csr_of(idx, Ns) if (ctx.det and ctx.needs_input_grad[0]) else None
         return out
 
     @staticmethod
@@ -1723,10 +1919,29 @@ class _MaxPoolFn(torch.autograd.Function):
         pre = 1 if gx is not None else 0
         # a gradient an older consumer of x already produced (the decoder, for a skip tensor): scatter on top of it
         c = ctx.incoming.collect() if ctx.incoming is not None else None
+        if ctx.det:
+            # order per element: the incoming gradient FIRST, then the queries that list the row, ascending
+            base = None
+            if c is not None and tuple(c.shape) == (Ns, C):
+                base, c = c.contiguous().float(), None
+            if gx is None:
+                gx = torch.empty((Ns, C), dtype=torch.float32, device=go.device)
+            ptr, ent = ctx.csr
+            _count('ordered')
+            with _region("max_pool_bwd_gather[Ns=%d,C=%d]" % (Ns, C), 8 * int(arg.shape[0]) * C + 4 * Ns * C):
+                _native.check(_native.lib().d3f_max_pool_backward_gather(_p(go), _p(arg), int(arg.shape[0]), C, Ns,
+                                                                         _p(ptr), _p(ent), _p(base), _p(gx), _stream()),
+                              "d3f_max_pool_backward_gather")
+            if c is not None:
+                gx.add_(c)
+            if ctx.dep is not None and ctx.dep.deposit(gx):
+                gx = None
+            return gx, None, None, None, None, None
         if c is not None and c.is_contiguous() and c.dtype == torch.float32 and tuple(c.shape) == (Ns, C):
             gx, pre, c = c, 1, None
         if gx is None:
             gx = torch.empty((Ns, C), dtype=torch.float32, device=go.device)
+        _count('scatter')
         _native.check(_native.lib().d3f_max_pool_backward(_p(go), _p(arg), int(arg.shape[0]), C, Ns, _p(gx), pre,
                                                           _stream()), "d3f_max_pool_backward")
         if c is not None:
@@ -1771,12 +1986,16 @@ class _ClosestPoolFn(torch.autograd.Function):
         Nq, H = int(idx.shape[0]), int(idx.shape[1])
         Cs = int(skip.shape[1]) if skip is not None else 0
         out = torch.empty((Nq, C + Cs), dtype=torch.float32, device=x.device)
-        gx_buf = torch.empty_like(x) if ctx.needs_input_grad[0] else None  # cleared by the forward launch
+        # cleared by the forward launch (the deterministic mode's gather writes every row: nothing to clear)
+        gx_buf = torch.empty_like(x) if (ctx.needs_input_grad[0] and not _DETERMINISTIC) else None
         _native.check(_native.lib().d3f_closest_pool_forward(_p(x), Ns, C, _p(idx), Nq, H, _p(skip), Cs, _p(out),
                                                              _p(gx_buf), _stream()), "d3f_closest_pool_forward")
         ctx.save_for_backward(idx)
         ctx.shape = (Ns, C, Cs)
         ctx.gx_buf = gx_buf
+        # deterministic mode: the backward gathers over the CSR transpose of the table's column 0
+        ctx.det = _DETERMINISTIC
+        ctx.csr = _csr_of(idx[:, :1].contiguous(), Ns) if (ctx.det and ctx.needs_input_grad[0]) else None
         return out
 
     @staticmethod
@@ -1794,11 +2013,26 @@ class _ClosestPoolFn(torch.autograd.Function):
             pre = 1 if gx is not None else 0
             if gx is None:
                 gx = torch.empty((Ns, C), dtype=torch.float32, device=go.device)
-            _native.check(_native.lib().d3f_closest_pool_backward(_p(go), ld, _p(idx), int(idx.shape[0]),
-                                                                  int(idx.shape[1]), C, Ns, _p(gx), pre, _stream()),
-                          "d3f_closest_pool_backward")
+            if ctx.det:
+                _closest_pool_backward_gather(go, ld, int(idx.shape[0]), C, Ns, ctx.csr, gx)
+            else:
+                _count('scatter')
+                _native.check(_native.lib().d3f_closest_pool_backward(_p(go), ld, _p(idx), int(idx.shape[0]),
+                                                                      int(idx.shape[1]), C, Ns, _p(gx), pre, _stream()),
+                              "d3f_closest_pool_backward")
         g_skip = go[:, C:] if (Cs and ctx.needs_input_grad[2]) else None
         return gx, None, g_skip
+
+
+def _closest_pool_backward_gather(go, ld, Nq, C, Ns, csr, gx):
+    """gx [Ns, C] = per coarse row the sum of the ``go`` rows (stride ``ld``) of the fine rows that point to it, ascending:
+    the gather form of d3f_closest_pool_backward (deterministic mode)."""
+    ptr, ent = csr
+    _count('ordered')
+    with _region("closest_pool_bwd_gather[Ns=%d,C=%d]" % (Ns, C), 4 * Nq * C + 4 * Ns * C):
+        _native.check(_native.lib().d3f_closest_pool_backward_gather(_p(go), int(ld), int(Nq), int(C), int(Ns), _p(ptr),
+                                                                     _p(ent), _p(gx), _stream()),
+                      "d3f_closest_pool_backward_gather")
 
 
 def closest_pool(x, inds, skip=None):
@@ -1831,6 +2065,7 @@ class _BiasActFn(torch.autograd.Function):
                                      b2 is not None and ctx.needs_input_grad[3], C, x.device)
         ctx.gbuf, ctx.slope = gbuf, float(slope)
         ctx.has = (b1 is not None, add is not None, b2 is not None)
+        ctx.det = _DETERMINISTIC
         if pack is not None:
             s_pts, want_clear = pack
             spack = torch.empty(16 * N, dtype=torch.uint8, device=x.device)
@@ -1871,9 +2106,12 @@ class _BiasActFn(torch.autograd.Function):
             if need_gx and not identity:
                 gx = torch.empty_like(go)
             wsb, nws = _bias_bwd_ws(N, C, go.device) if first is not None else (None, 0)
-            _native.check(_native.lib().d3f_bias_act_backward(_p(go), _p(out), ctx.slope, N, C, _p(gx), _p(first),
-                                                              _p(second), pre if first is not None else 0, None,
-                                                              _p(wsb), nws, _stream()), "d3f_bias_act_backward")
+            if ctx.det and first is not None:
+                _bias_act_backward_ordered(go, out, ctx.slope, N, C, gx, first, second, None)
+            else:
+                _native.check(_native.lib().d3f_bias_act_backward(_p(go), _p(out), ctx.slope, N, C, _p(gx), _p(first),
+                                                                  _p(second), pre if first is not None else 0, None,
+                                                                  _p(wsb), nws, _stream()), "d3f_bias_act_backward")
             if identity:
                 gx = go
         return (gx if ctx.needs_input_grad[0] else None, g1, gx if ctx.has[1] and ctx.needs_input_grad[2] else None,
@@ -2042,6 +2280,9 @@ def detection_scores(features, neighbors, training=True, lens=None, width=None, 
     stacks several reference batches of that many clouds (8 pairs: 2); the normaliser (architectures.py:342 takes the
     maximum of ONE pair) and ``width`` are then per group, in forward and backward."""
     _check_groups(width, (lens, group) if group else None, "detection_scores")
+    if _DETERMINISTIC and training and torch.is_grad_enabled() and features.requires_grad:
+        # (the training step scores the sampled rows inside the loss node, ops.DetectorRows, which has an ordered form)
+        _no_deterministic_form("detection_scores (the dense detector's backward)")
     return _DetScoreFn.apply(_f32(features, "features"), _i32(neighbors, "neighbors"), bool(training), lens, width,
                              int(group))
 
@@ -2208,17 +2449,70 @@ def _select_rows_bwd(x, saved, stride, P, M, g_a, g_p, g_sa, g_sp, with_scores=T
     return gx, gs
 
 
+_LOSS_RECORDS = None     # tests: a dict here receives the records of the next ordered loss backward (its ``debug``)
+
+
+def _loss_rows_bwd_ordered(x, saved, stride, P, M, g_a, g_p, g_sa, g_sp, with_scores=True, det=None, debug=None):
+    """_select_rows_bwd (and, with ``det`` = (DetectorRows, fmax, aux), _det_rows_bwd on top of it) without float atomics,
+    for the deterministic mode: every contribution is stored as a record, the record keys are sorted, and each element of
+    the gradient is the float32 sum of its records in key order -- ascending sampled row (anchors, then positives), inside a
+    row the normalisation's term, the detector's c* and c' terms, the neighbors by slot -- with the group's arg-max term
+    last (d3f_loss_rows_backward_records / _apply).  Returns (grad_x [N,C], grad_scores [N,1] or None).  ``debug``: a dict
+    that receives the records (key, val), their width and the arg-max terms (tests restate the sums from them)."""
+    L = _native.lib()
+    N, C = int(x.shape[0]), int(x.shape[1])
+    ia, ip, p_offset, lens = saved
+    rows = 2 * P * M
+    if debug is None:
+        debug = _LOSS_RECORDS
+    if det is not None:
+        rows_det, fmax, aux = det
+        head, groups = _det_rows_args(x, rows_det, fmax, lens)
+        H, with_scores = int(rows_det.neighbors.shape[1]), False
+        n_groups = int(fmax.numel())
+    else:
+        head, groups, fmax, aux, H, n_groups = (_p(x), N, C, None, 0, None), (None, 0, 0), None, None, 0, 1
+    R = int(L.d3f_loss_rows_record_width(C, H))
+    key = torch.empty(rows * R, dtype=torch.int64, device=x.device)
+    val = torch.empty(rows * R, dtype=torch.float32, device=x.device)
+    nws = int(L.d3f_detection_rows_ws_bytes(rows))
+    ws = _ws(nws, x.device)     # (part / pgroup of the first call are read by the second: ONE buffer)
+    cont = [g.contiguous() if g is not None else None for g in (g_a, g_p, g_sa, g_sp)]
+    if with_scores:
+        buf = torch.empty(N * (C + 1), dtype=torch.float32, device=x.device)
+        gx, gs = buf[:N * C].view(N, C), buf[N * C:].view(N, 1)
+    else:
+        gx, gs = torch.empty((N, C), dtype=torch.float32, device=x.device), None
+    tie = torch.zeros(n_groups, dtype=torch.float32, device=x.device) if debug is not None else None
+    _count('ordered')
+    with _region("loss_rows_bwd_ordered[T=%d]" % (P * M)):
+        feat, _, _, nb, _, fm = head
+        g_len, g_b, g_group = groups
+        _native.check(L.d3f_loss_rows_backward_records(
+            feat, N, C, nb, H, fm, g_len, g_b, g_group, _p(ia), _p(ip), stride, M, P, _p(p_offset), _p(lens), _p(aux),
+            _p(cont[0]), _p(cont[1]), _p(cont[2]), _p(cont[3]), 1 if with_scores else 0, _p(key), _p(val), _p(ws), nws,
+            _stream()), "d3f_loss_rows_backward_records")
+        skey = torch.sort(key)[0]       # (keys are unique: element * records + record index)
+        _native.check(L.d3f_loss_rows_backward_apply(
+            feat, N, C, H, fm, g_len, g_b, g_group, rows, 1 if det is not None else 0, 1 if with_scores else 0, _p(skey),
+            _p(val), _p(gx), _p(tie), _p(ws), nws, _stream()), "d3f_loss_rows_backward_apply")
+    if debug is not None:
+        debug.update(key=key, val=val, width=R, tie_terms=tie, sorted_key=skey)
+    return gx, gs
+
+
 class _SelectNormalizeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scores, saved, stride):
         ctx.save_for_backward(x, *saved)
-        ctx.stride = stride
+        ctx.stride, ctx.ordered = stride, _DETERMINISTIC
         return _select_normalize_fwd(x, scores, saved, stride, 1, int(saved[0].shape[0]))
 
     @staticmethod
     def backward(ctx, g_a, g_p, g_sa, g_sp):
         x, *saved = ctx.saved_tensors
-        gx, gs = _select_rows_bwd(x, saved, ctx.stride, 1, int(saved[0].shape[0]), g_a, g_p, g_sa, g_sp)
+        bwd = _loss_rows_bwd_ordered if ctx.ordered else _select_rows_bwd
+        gx, gs = bwd(x, saved, ctx.stride, 1, int(saved[0].shape[0]), g_a, g_p, g_sa, g_sp)
         return gx, gs, None, None
 
 
@@ -2391,6 +2685,7 @@ class _TrainLossFn(torch.autograd.Function):
                 oa, op, sa, sp, aux, P, M, params, weights, True)
         ctx.save_for_backward(x, *saved, oa, op, sa, sp, stats, *((aux, dists, gw) if circle else ()))
         ctx.meta = (stride, circle, plain, P, M, params, weights)
+        ctx.ordered = _DETERMINISTIC
         ctx.mark_non_differentiable(scalars, dists, fp, an)
         ctx.set_materialize_grads(False)   # (else four zero-fill launches per step for the by-products' gradients)
         return total, scalars, dists, fp, an
@@ -2414,10 +2709,15 @@ class _TrainLossFn(torch.autograd.Function):
         else:
             grads = _contrastive_bwd(oa, op, sa, sp, stats, P, M, params, weights, g_ptrs)
         if ctx.det is None:
-            return _select_rows_bwd(x, saved, stride, P, M, *grads) + (None,) * 9
+            return (_loss_rows_bwd_ordered if ctx.ordered else _select_rows_bwd)(x, saved, stride, P, M, *grads) + \
+                (None,) * 9
         det, fmax, aux8 = ctx.det
         if aux8 is None:
             raise RuntimeError("train loss: the detector's backward is defined for training mode only")
+        if ctx.ordered:     # normalisation + detector + arg-max terms in ONE order-fixed sum per element
+            gx, _ = _loss_rows_bwd_ordered(x, saved, stride, P, M, *grads, with_scores=False, det=ctx.det)
+            return (gx,) + (None,) * 10
+        _count('scatter')
         gx, _ = _select_rows_bwd(x, saved, stride, P, M, *grads, with_scores=False)
         _det_rows_bwd(x, det, fmax, saved, stride, P, M, aux8, grads[2], grads[3], gx)
         return (gx,) + (None,) * 10

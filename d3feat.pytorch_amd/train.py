@@ -11,6 +11,7 @@ Differences that are the point of this build:
     NaN/Inf guard is decided from the REDUCED gradients so every rank takes the same decision without a host sync.
 One process per GPU; `torch.distributed` backend "nccl" is RCCL on ROCm.
 """
+import contextlib
 import os
 
 import torch
@@ -535,8 +536,12 @@ class TrainStep:
 
     stack = 1
 
-    def __init__(self, config, neighborhood_limits, device, world_size=1, seed=0, model=None):
+    def __init__(self, config, neighborhood_limits, device, world_size=1, seed=0, model=None, deterministic=None):
+        """``deterministic`` (default: ``config.deterministic``, else False): the engine builds its pyramids and runs /
+        records its steps under ops.deterministic_mode -- no float atomic in the step, the same bits in every gradient,
+        loss and updated parameter from run to run (eager steps, and replays of graphs captured by this engine)."""
         self.config, self.limits, self.device, self.world = config, [int(x) for x in neighborhood_limits], device, world_size
+        self.deterministic = bool(getattr(config, 'deterministic', False) if deterministic is None else deterministic)
         if model is None:
             import numpy as np
             np.random.seed(seed)
@@ -613,9 +618,16 @@ class TrainStep:
     # (or D3FEAT_DENSE_DETECTOR=1 in the environment): all N scores and their dense backward, as before (A/B experiments)
     SPARSE_DETECTOR = os.environ.get('D3FEAT_DENSE_DETECTOR', '0') in ('', '0')
 
+    def _mode(self):
+        """The deterministic mode around everything this engine builds, runs or records (the pyramid builders ask
+        ops.wants_reverse_table, the autograd nodes read the mode in their forward); an engine that does not ask for it
+        leaves the process-wide setting alone."""
+        return ops.deterministic_mode(True) if getattr(self, 'deterministic', False) else contextlib.nullcontext()
+
     def build_batch(self, item):
-        batch = dl.collate_fn_descriptor([item], self.config, self.limits, device=self.device, exact_width=False,
-                                         reverse_tables=self.reverse_tables, keep_status=True)
+        with self._mode():
+            batch = dl.collate_fn_descriptor([item], self.config, self.limits, device=self.device, exact_width=False,
+                                             reverse_tables=self.reverse_tables, keep_status=True)
         # flags the searches raised after the level-size read-back (candidate overflow, ...): checked at the caller's
         # next check_status() instead of being dropped
         pend = getattr(self, '_eager_status', None)
@@ -688,12 +700,17 @@ class TrainStep:
         return m.detection_scores(batch, x)
 
     def forward_loss(self, batch):
-        x = self.model.forward_descriptors(batch)
-        return self._loss_from_raw(x, self._scores_for_loss(batch, x), batch)
+        with self._mode():
+            x = self.model.forward_descriptors(batch)
+            return self._loss_from_raw(x, self._scores_for_loss(batch, x), batch)
 
     def _forward_loss_cut(self, batch):
         """forward_loss with the autograd graph cut at the input of encoder block CUT: everything downstream (coarse
         encoder, decoder, loss) hangs off detached leaves.  Returns the loss tuple and [(tensor, leaf), ...]."""
+        with self._mode():
+            return self._forward_loss_cut_body(batch)
+
+    def _forward_loss_cut_body(self, batch):
         m = self.model
         x = batch['features'].detach()
         skips, cuts = [], []
@@ -1049,11 +1066,12 @@ class TrainStep:
             st.status = ops.DeviceStatus(self.device)
         # (the word describes THIS pair -- what an earlier one caused is kept by the optimizer, state[2:4] --: it is cleared
         # by the build's first launch, together with the cell lists' counters)
-        batch = dl.build_pyramid_static(st.pts, st.lens, self.config, self.limits, self.caps,
-                                        reverse_tables=self.reverse_tables, status=st.status,
-                                        conv_widths=not self.reverse_tables,   # (the eval-mode gate's input: inference)
-                                        group=2 if self.stack > 1 else getattr(self, 'group', 0),
-                                        engine_upsamples=self.engine_upsamples, clear_status=True)
+        with self._mode():
+            batch = dl.build_pyramid_static(st.pts, st.lens, self.config, self.limits, self.caps,
+                                            reverse_tables=self.reverse_tables, status=st.status,
+                                            conv_widths=not self.reverse_tables,   # (the eval-mode gate's input: inference)
+                                            group=2 if self.stack > 1 else getattr(self, 'group', 0),
+                                            engine_upsamples=self.engine_upsamples, clear_status=True)
         batch.pop('_status')
         if st.batch is None or adopt:
             st.batch = batch

@@ -130,8 +130,11 @@ class Trainer(object):
         limits = _get(args, 'neighborhood_limits', None)
         if limits is None:
             limits = self.train_loader.limits
+        # args.deterministic (default off): the step without float atomics -- the same bits in every gradient, loss and
+        # parameter when a run is repeated, on the eager and the graph-replayed step (TrainStep, ops.set_deterministic)
+        self.deterministic = bool(_get(args, 'deterministic', False))
         self.engine = TrainStep(args, limits, self.device, world_size=self.world, seed=_get(args, 'seed', 0),
-                                model=_get(args, 'model', None))
+                                model=_get(args, 'model', None), deterministic=self.deterministic)
         self.model = self.engine.model
         self.optimizer = self.engine.opt
         self.scheduler = ExponentialLR(self.optimizer, gamma=args.scheduler_gamma)

@@ -401,6 +401,19 @@ int d3f_closest_pool_forward(const float* x, int Ns, int C, const int32_t* idx, 
                              int Cs, float* out, float* grad_x_clear, void* stream);
 int d3f_closest_pool_backward(const float* grad_out, int ld, const int32_t* idx, int Nq, int H, int C, int Ns,
                               float* grad_x, int grad_x_precleared, void* stream);
+/* Gather forms for the deterministic mode: no float atomic, every row of grad_x [Ns,C] written once (no clearing), the
+ * same bits on every call.  rev_ptr [Ns+1] / rev_ent = the CSR transpose d3f_reverse_table_build gives (queries per
+ * support, ascending); every sum runs left to right in float32 over ascending query rows.
+ * d3f_max_pool_backward_gather replaces the scatter of d3f_max_pool_backward: rev of the pooling table idx [Nq,H];
+ *   grad_x[s,c] = grad_base[s,c] + sum of grad_out[q,c] over the q that list s with argmax[q,c] == s.  grad_base (optional,
+ *   [Ns,C], may be grad_x itself): a gradient an older consumer left for the same tensor; it is the FIRST term.
+ * d3f_closest_pool_backward_gather replaces the scatter of d3f_closest_pool_backward: rev of COLUMN 0 of the upsampling
+ *   table as a [Nq,1] table; grad_x[s,c] = sum of grad_out[n*ld + c] over the n with idx[n,0] == s. */
+int d3f_max_pool_backward_gather(const float* grad_out, const int32_t* argmax, int Nq, int C, int Ns,
+                                 const int32_t* rev_ptr, const int32_t* rev_ent, const float* grad_base, float* grad_x,
+                                 void* stream);
+int d3f_closest_pool_backward_gather(const float* grad_out, int ld, int Nq, int C, int Ns, const int32_t* rev_ptr,
+                                     const int32_t* rev_ent, float* grad_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Block epilogue -- replaces BatchNormBlock's bias add (models/blocks.py:473, use_bn=False), nn.LeakyReLU(0.1)
@@ -441,6 +454,13 @@ int d3f_bias_act_backward_blocks(int N, int C);
 int d3f_bias_act_backward_partial(const float* grad_out, const float* out, float slope, int N, int C, float* grad_x,
                                   const float* row_div, void* ws, size_t ws_bytes, void* stream);
 int d3f_bias_sum(const float* part, int blocks, int C, float* grad_bias, float* grad_bias2, void* stream);
+/* The two-pass form at EVERY row count, for the deterministic mode: replaces the float atomics with which
+ * d3f_bias_act_backward flushes its per-block column sums below 4096 rows.  The sums go to ws [blocks, C] and are added
+ * up in block order; grad_bias / grad_bias2 are OVERWRITTEN.  ws >= d3f_bias_act_backward_ordered_ws_bytes(N, C). */
+size_t d3f_bias_act_backward_ordered_ws_bytes(int N, int C);
+int d3f_bias_act_backward_ordered(const float* grad_out, const float* out, float slope, int N, int C, float* grad_x,
+                                  float* grad_bias, float* grad_bias2, const float* row_div, void* ws, size_t ws_bytes,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Deformable KPConv -- replaces the deformable=True branch of KPConv.forward (models/blocks.py:243-257,286-324,365-366).
@@ -593,6 +613,32 @@ int d3f_detection_rows_backward(const float* feat, int N, int C, const int32_t* 
                                 int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
                                 const float* aux, const float* g_sa, const float* g_sp, float* grad_x, void* ws,
                                 size_t ws_bytes, void* stream);
+/* Order-fixed backward of the loss node's sampled rows, for the deterministic mode: replaces the float-atomic scatters of
+ * d3f_select_normalize_backward (into grad_x and grad_scores) and of d3f_detection_rows_backward (c*, c', neighbor and
+ * arg-max terms) into the one dense gradient.  Two entries with a key sort by the caller between them:
+ *   _records  stores every contribution of sampled row m2 (anchors, then positives) as rec_key / rec_val
+ *             [2*pairs*M, R], R = d3f_loss_rows_record_width(C, H) = C + 3 + H slots per row: slot c < C the
+ *             normalisation's term of (row, c); C and C + 1 the detector's c* and c' terms; C + 2 + h the term of neighbor
+ *             slot h; C + 2 + H the row's score gradient.  Record r = m2 * R + slot has rec_key = element * (rows * R) + r
+ *             (element of grad_x, or N*C + row of grad_scores), INT64_MAX where the atomic forms add nothing.
+ *             aux / idx / feat_max NULL and H = 0: no rows-form detector (g_sa / g_sp are then score gradients, kept with
+ *             with_scores = 1).
+ *   _apply    takes the keys SORTED ascending: clears grad_x [N, C] (+ [N] scores behind it with with_scores), gives every
+ *             element the float32 sum of its records in key order -- ascending m2, inside a row normalise, c*, c',
+ *             neighbors by slot -- and, with_detector, adds each group's arg-max term LAST.  tie_term_out (optional, one
+ *             float per group) receives that term.
+ * ws is the SAME buffer in both calls (>= d3f_detection_rows_ws_bytes(2*pairs*M)); rows = 2*pairs*M. */
+int d3f_loss_rows_record_width(int C, int H);
+int d3f_loss_rows_backward_records(const float* feat, int N, int C, const int32_t* idx, int H, const float* feat_max,
+                                   const int32_t* len, int B, int group, const int64_t* idx_a, const int64_t* idx_p,
+                                   int idx_stride, int M, int pairs, const int32_t* p_offset, const int32_t* pair_len,
+                                   const float* aux, const float* g_a, const float* g_p, const float* g_sa,
+                                   const float* g_sp, int with_scores, int64_t* rec_key, float* rec_val, void* ws,
+                                   size_t ws_bytes, void* stream);
+int d3f_loss_rows_backward_apply(const float* feat, int N, int C, int H, const float* feat_max, const int32_t* len, int B,
+                                 int group, int rows, int with_detector, int with_scores, const int64_t* sorted_key,
+                                 const float* rec_val, float* grad_x, float* tie_term_out, void* ws, size_t ws_bytes,
+                                 void* stream);
 
 /* Circle + detector loss -- replaces utils/loss.py: cdist(:8-44, 'euclidean'), CircleLoss.forward(:111-141),
  * DetLoss.forward(:149-158).  M in 2..1024 sampled correspondences.
@@ -1563,6 +1609,14 @@ int d3f_kpconv_aggregate_modes(const float* q_pts, int Nq, const float* s_pts, i
 int d3f_kpconv_grad_input_modes(const float* q_pts, int Nq, const float* s_pts, int Ns, const int32_t* idx, int H,
                                 int Cin, const float* kernel_points, int K, float extent, int mode, const float* gwf,
                                 float* grad_x, void* stream);
+/* For the deterministic mode: replaces the float-atomic scatter of d3f_kpconv_grad_input_modes (and, with mode 0, of the
+ * general path of d3f_kpconv_backward) by a gather over the table's transpose -- CSR (rev_ptr [Ns+1] + rev_ent, rev_rel
+ * NULL) or the exact form (rev_rel [Ns, rev_width, 4]) of d3f_kpconv_grad_input_gather.  One wave per support row adds
+ * the row's edges in the transpose's order; grad_x [Ns, Cin] is overwritten.  Any Cin <= 512, K <= 16, every mode. */
+int d3f_kpconv_grad_input_modes_gather(const float* q_pts, int Nq, const float* s_pts, int Ns, const int32_t* rev_ptr,
+                                       const int32_t* rev_ent, const float* rev_rel, int rev_width, int Cin,
+                                       const float* kernel_points, int K, float extent, int mode, const float* gwf,
+                                       float* grad_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer step with the reference's non-finite-gradient guard -- replaces trainer.py:104-111 (per-parameter
