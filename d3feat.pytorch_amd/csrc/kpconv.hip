@@ -27,8 +27,7 @@ __global__ __launch_bounds__(256) void kpconv_wf_kernel(const float* __restrict_
                                                         const float* __restrict__ x,
                                                         const float* __restrict__ kp, int Nq, int Ns, int H, int Cin,
                                                         int K, float extent, float* __restrict__ wf,
-                                                        float* __restrict__ nn, float gauss_denom = 1.0f,
-                                                        int mode = 0) {
+                                                        float* __restrict__ nn, float gauss_denom, int mode) {
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= Nq) return;
@@ -93,8 +92,7 @@ __global__ __launch_bounds__(256) void kpconv_dx_kernel(const float* __restrict_
                                                         const int32_t* __restrict__ idx,
                                                         const float* __restrict__ kp, int Nq, int Ns, int H, int Cin,
                                                         int K, float extent, const float* __restrict__ gW,
-                                                        float* __restrict__ grad_x, float gauss_denom = 1.0f,
-                                                        int mode = 0) {
+                                                        float* __restrict__ grad_x, float gauss_denom, int mode) {
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= Nq) return;
@@ -298,6 +296,23 @@ int launch_wf(const float* q_pts, const float* s_pts, const int32_t* idx, const 
   return D3F_OK;
 }
 
+// grad_x [Ns, Cin] (cleared by the caller) += the scatter of gW [Nq, K*Cin]; Cin <= 512 (the entry points check it)
+int launch_dx(const float* q_pts, const float* s_pts, const int32_t* idx, const float* kp, int Nq, int Ns, int H, int Cin,
+              int K, float extent, const float* gW, float* grad_x, hipStream_t stream, int mode) {
+  const int grid = cdiv(Nq, 4);
+  const int cpl = cdiv(Cin, 64);
+  const float gd = gauss_denominator(extent);
+#define D3F_DX(CPL) \
+  kpconv_dx_kernel<CPL><<<grid, 256, 0, stream>>>(q_pts, s_pts, idx, kp, Nq, Ns, H, Cin, K, extent, gW, grad_x, gd, mode)
+  if (cpl <= 1) D3F_DX(1);
+  else if (cpl <= 2) D3F_DX(2);
+  else if (cpl <= 4) D3F_DX(4);
+  else D3F_DX(8);
+#undef D3F_DX
+  D3F_LAUNCH_CHECK();
+  return D3F_OK;
+}
+
 // kpconv_fused.hip
 bool kpconv_fused_supported(int Cin, int Cout, int K, int H, int Ns);
 size_t kpconv_fused_ws_bytes(int Ns);
@@ -471,16 +486,7 @@ int d3f_kpconv_backward(const float* q_pts, int Nq, const float* s_pts, int Ns, 
     // gW [Nq, KC] = (grad_out / nn) [Nq, Cout] @ W^T [Cout, KC]
     rc = launch_gemm(grad_out, Cout, 1, weights, 1, Cout, gW, Nq, KC, Cout, nn, 1, 1, stream);
     if (rc) return rc;
-    const int grid = cdiv(Nq, 4);
-    const int cpl = cdiv(Cin, 64);
-#define D3F_DX(CPL) \
-  kpconv_dx_kernel<CPL><<<grid, 256, 0, stream>>>(q_pts, s_pts, idx, kernel_points, Nq, Ns, H, Cin, K, extent, gW, grad_x)
-    if (cpl <= 1) D3F_DX(1);
-    else if (cpl <= 2) D3F_DX(2);
-    else if (cpl <= 4) D3F_DX(4);
-    else D3F_DX(8);
-#undef D3F_DX
-    D3F_LAUNCH_CHECK();
+    return launch_dx(q_pts, s_pts, idx, kernel_points, Nq, Ns, H, Cin, K, extent, gW, grad_x, stream, 0);
   }
   return D3F_OK;
 }
@@ -529,15 +535,19 @@ int d3f_kpconv_grad_input(const float* q_pts, int Nq, const float* s_pts, int Ns
 }
 
 // ---- non-default influence / aggregation modes (blocks.py:327-352): general path only ---------------------------
-// mode = influence (0 'linear', 1 'constant', 2 'gaussian') | 4 when aggregation_mode == 'closest'.
-static bool mode_ok(int mode) { return mode >= 0 && mode < 8 && (mode & 3) != 3; }
+// mode: kpconv_modes.hpp.  What the three entries ask of the arguments they share; a table entry adds idx / H / Ns >= 1.
+static bool modes_args_ok(const void* q_pts, int Nq, const void* s_pts, int Ns, int Cin, const void* kp, int K,
+                          float extent, int mode) {
+  return q_pts && s_pts && kp && Nq >= 0 && Ns >= 0 && Cin >= 1 && Cin <= 512 && K >= 1 && K <= 16 && extent > 0.0f &&
+         kpconv_mode_ok(mode);
+}
 
 // wf [Nq, K*Cin] = sum_h w_mode[n,h,k] x[idx[n,h], :],  nn [Nq] = max(1, #neighbors with a positive feature sum)
 int d3f_kpconv_aggregate_modes(const float* q_pts, int Nq, const float* s_pts, int Ns, const int32_t* idx, int H,
                                const float* x, int Cin, const float* kernel_points, int K, float extent, int mode,
                                float* wf_out, float* nn_out, void* stream_) {
-  if (!q_pts || !s_pts || !idx || !x || !kernel_points || !wf_out || !nn_out || Nq < 0 || Ns < 1 || H < 1 ||
-      Cin < 1 || Cin > 512 || K < 1 || K > 16 || !(extent > 0.0f) || !mode_ok(mode))
+  if (!modes_args_ok(q_pts, Nq, s_pts, Ns, Cin, kernel_points, K, extent, mode) || !idx || H < 1 || Ns < 1 || !x ||
+      !wf_out || !nn_out)
     return D3F_EINVAL;
   if (Nq == 0) return D3F_OK;
   return launch_wf<true>(q_pts, s_pts, idx, x, kernel_points, Nq, Ns, H, Cin, K, extent, wf_out, nn_out,
@@ -548,25 +558,13 @@ int d3f_kpconv_aggregate_modes(const float* q_pts, int Nq, const float* s_pts, i
 int d3f_kpconv_grad_input_modes(const float* q_pts, int Nq, const float* s_pts, int Ns, const int32_t* idx, int H,
                                 int Cin, const float* kernel_points, int K, float extent, int mode, const float* gwf,
                                 float* grad_x, void* stream_) {
-  if (!q_pts || !s_pts || !idx || !kernel_points || !gwf || !grad_x || Nq < 0 || Ns < 1 || H < 1 || Cin < 1 ||
-      Cin > 512 || K < 1 || K > 16 || !(extent > 0.0f) || !mode_ok(mode))
+  if (!modes_args_ok(q_pts, Nq, s_pts, Ns, Cin, kernel_points, K, extent, mode) || !idx || H < 1 || Ns < 1 || !gwf ||
+      !grad_x)
     return D3F_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   if (d3f::zero_async(grad_x, sizeof(float) * (size_t)Ns * Cin, stream) != hipSuccess) return D3F_ELAUNCH;
   if (Nq == 0) return D3F_OK;
-  const int grid = cdiv(Nq, 4);
-  const int cpl = cdiv(Cin, 64);
-  const float gd = gauss_denominator(extent);
-#define D3F_DX(CPL)                                                                                                 \
-  kpconv_dx_kernel<CPL><<<grid, 256, 0, stream>>>(q_pts, s_pts, idx, kernel_points, Nq, Ns, H, Cin, K, extent, gwf, \
-                                                  grad_x, gd, mode)
-  if (cpl <= 1) D3F_DX(1);
-  else if (cpl <= 2) D3F_DX(2);
-  else if (cpl <= 4) D3F_DX(4);
-  else D3F_DX(8);
-#undef D3F_DX
-  D3F_LAUNCH_CHECK();
-  return D3F_OK;
+  return launch_dx(q_pts, s_pts, idx, kernel_points, Nq, Ns, H, Cin, K, extent, gwf, grad_x, stream, mode);
 }
 
 // grad_x [Ns, Cin] (OVERWRITTEN) of any channel count and mode as a gather over the table's transpose: no atomics
@@ -574,9 +572,7 @@ int d3f_kpconv_grad_input_modes_gather(const float* q_pts, int Nq, const float* 
                                        const int32_t* rev_ent, const float* rev_rel, int rev_width, int Cin,
                                        const float* kernel_points, int K, float extent, int mode, const float* gwf,
                                        float* grad_x, void* stream_) {
-  if (!q_pts || !s_pts || !kernel_points || !gwf || !grad_x || Nq < 0 || Ns < 0 || Cin < 1 || Cin > 512 || K < 1 ||
-      K > 16 || !(extent > 0.0f) || !mode_ok(mode))
-    return D3F_EINVAL;
+  if (!modes_args_ok(q_pts, Nq, s_pts, Ns, Cin, kernel_points, K, extent, mode) || !gwf || !grad_x) return D3F_EINVAL;
   if (rev_rel ? (rev_ptr || rev_ent || rev_width < 1 || ((uintptr_t)rev_rel & 15u)) : (!rev_ptr || !rev_ent))
     return D3F_EINVAL;
   if (Ns == 0) return D3F_OK;

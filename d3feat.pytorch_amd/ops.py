@@ -634,10 +634,74 @@ def _takes_gemm_path(Nq, Cin):
     return 0 < Nq < _GEMM_DX_MAX_ROWS or (Nq > 0 and Cin >= _GEMM_PATH_MIN_CIN)
 
 
-def _kpconv_gw(gon, weights, Nq, K, Cin, Cout):
-    """gW [Nq, K Cin] = (g / nn) [Nq, Cout] @ W^T, W viewed [K Cin, Cout]: the per-query gradient of the weighted features
-    the scatter-form grad-input kernel distributes (few-point layers)."""
-    return torch.mm(gon, weights.view(K * Cin, Cout).t())
+def _csr_table(idx, Ns):
+    """The CSR transpose of a table that came without a usable one, for the gather forms of the deterministic mode."""
+    ptr, ent = _csr_of(idx, Ns)
+    return ReverseTable(ent, int(idx.shape[0]), int(idx.shape[1]), Ns, ptr=ptr)
+
+
+def _gather_table(rev, idx, Ns, K, Cin, Cout, always=False):
+    """The reverse table the fused-path nodes' grad-input gathers over, None for the scatter form: the table's transpose
+    from DX_GATHER_MIN_ROWS support rows up, for the channel counts the gather kernel covers.  ``always`` (a training call
+    under the deterministic mode): at every row count, the CSR form built here when none came; other channel counts raise."""
+    covered = _native.lib().d3f_kpconv_grad_input_gather_supported(Cin, Cout, K)
+    if always:
+        if not covered:
+            _no_deterministic_form("KPConv grad-input for %d -> %d channels" % (Cin, Cout),
+                                   "the gather form does not cover these channel counts")
+        return rev if rev is not None else _csr_table(idx, Ns)
+    return rev if (rev is not None and Ns >= DX_GATHER_MIN_ROWS and covered) else None
+
+
+def _packed_supports(x, Ns, ready, packs, want_keep, need_clear):
+    """(keep, gx_buf, clear): the packed supports a forward launch leaves for the backward pass, the scatter target it
+    clears on the side (``need_clear``; the gather form writes every row: nothing to clear) and what the launch takes as
+    its grad_x_clear argument.  The epilogue that produced x may have packed the supports already (``ready``, a
+    PackedSupports): no packing launch then.  ``packs``: the launch works on packed supports at all; ``want_keep``: when
+    the node allocates them itself."""
+    keep = gx_buf = None
+    use_ready = packs and ready is not None and (not need_clear or ready.gx_buf is not None)
+    if use_ready:
+        keep, gx_buf = ready.spack, (ready.gx_buf if need_clear else None)
+    elif want_keep and packs:
+        keep = torch.empty(16 * Ns, dtype=torch.uint8, device=x.device)
+        if need_clear:
+            gx_buf = torch.empty_like(x)
+    return keep, gx_buf, SPACK_READY if use_ready else _p(gx_buf)
+
+
+def _scatter_target(ctx, x):
+    """(gx, pre): the buffer the node's forward cleared on the side (pre = 1); a second backward gets a fresh one."""
+    gx, ctx.gx_buf = ctx.gx_buf, None
+    return (gx, 1) if gx is not None else (torch.empty_like(x), 0)
+
+
+def _kpconv_dx_gather(q_pts, s_pts, H, rev, kernel_points, weights, extent, nn, g, gx):
+    """grad_x as a gather over the reverse table: aggregate g / nn around every support, then contract with W^T -- one
+    launch instead of the gW GEMM + atomic scatter.  ``nn`` None: ``g`` is already divided."""
+    Nq, Ns = int(q_pts.shape[0]), int(s_pts.shape[0])
+    K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
+    with _region("kpconv_dx_gather[Ns=%d,Cin=%d,Cout=%d]" % (Ns, Cin, Cout), kpconv_bwd_bytes(Nq, Ns, H, K, Cin, Cout)):
+        _native.check(_native.lib().d3f_kpconv_grad_input_gather(
+            _p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent), _p(rev.last_key), rev.width, rev.radius, _p(rev.rel),
+            _p(kernel_points), K, _p(weights), Cin, Cout, extent, _p(nn), _p(g), _p(gx),
+            _p(rev.status.word) if rev.status is not None else None, _stream()), "d3f_kpconv_grad_input_gather")
+
+
+def _kpconv_dx_scatter(q_pts, s_pts, idx, x, kernel_points, weights, extent, gon, keep, pre, gx):
+    """grad_x of the few-point layers: gW [Nq, K Cin] = (g / nn) [Nq, Cout] @ W^T (W viewed [K Cin, Cout]) over all
+    queries is one library GEMM; the kernel only scatters it (float atomics)."""
+    L = _native.lib()
+    Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
+    K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
+    gwf = torch.mm(gon, weights.view(K * Cin, Cout).t())
+    nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
+    ws = _ws(nbytes, x.device)
+    _count('scatter')
+    with _region("kpconv_dx_scatter[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * K * Cin + 4 * Nq * H * (1 + Cin)):
+        _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin, _p(kernel_points), K,
+                                              extent, _p(gwf), _p(keep), pre, _p(gx), _p(ws), nbytes, _stream()),
+                      "d3f_kpconv_grad_input")
 
 
 class _KPConvFn(torch.autograd.Function):
@@ -646,9 +710,7 @@ class _KPConvFn(torch.autograd.Function):
         L = _native.lib()
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
         K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
-        if rev is not None and not (Ns >= DX_GATHER_MIN_ROWS and L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K)):
-            rev = None
-        ctx.rev = rev
+        ctx.rev = rev = _gather_table(rev, idx, Ns, K, Cin, Cout)
         out = torch.empty((Nq, Cout), dtype=torch.float32, device=x.device)
         nn = torch.empty(Nq, dtype=torch.float32, device=x.device)
         nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, Cout)
@@ -660,23 +722,15 @@ class _KPConvFn(torch.autograd.Function):
         if SAVE_WEIGHTED_FEATURES and ctx.needs_input_grad[5] and Nq > 0 and wf_row:
             wf = torch.empty((Nq, wf_row), dtype=torch.float32, device=x.device)
         # training: the packed supports are kept for the backward pass and its scatter target is cleared on the side
-        keep = gx_buf = None
         packs = Nq > 0 and Ns > 0 and L.d3f_kpconv_packs_supports(Cin, Cout, K, H, Ns)
-        need_clear = ctx.needs_input_grad[3] and rev is None   # (the gather form writes every row: nothing to clear)
-        # the epilogue that produced x may have packed the supports already (PackedSupports): no packing launch then
-        use_ready = packs and ready is not None and (not need_clear or ready.gx_buf is not None)
-        if use_ready:
-            keep, gx_buf = ready.spack, (ready.gx_buf if need_clear else None)
-        elif (ctx.needs_input_grad[3] or ctx.needs_input_grad[5]) and packs:
-            keep = torch.empty(16 * Ns, dtype=torch.uint8, device=x.device)
-            if need_clear:
-                gx_buf = torch.empty_like(x)
+        keep, gx_buf, clear = _packed_supports(x, Ns, ready, packs, ctx.needs_input_grad[3] or ctx.needs_input_grad[5],
+                                               ctx.needs_input_grad[3] and rev is None)
         with _region("kpconv_fwd[Nq=%d,Cin=%d,Cout=%d,H=%d]" % (Nq, Cin, Cout, H),
                      kpconv_fwd_bytes(Nq, Ns, H, K, Cin, Cout)):
             _native.check(L.d3f_kpconv_forward(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
                                                _p(kernel_points), K, _p(weights), Cout, float(extent), _p(out),
-                                               _p(nn), _p(wf), _p(keep), SPACK_READY if use_ready else _p(gx_buf),
-                                               _p(ws), nbytes, _stream()), "d3f_kpconv_forward")
+                                               _p(nn), _p(wf), _p(keep), clear, _p(ws), nbytes, _stream()),
+                          "d3f_kpconv_forward")
         ctx.keep, ctx.gx_buf = keep, gx_buf
         ctx.gw_slot = _grad_slot(weights)
         ctx.has_wf = wf is not None
@@ -695,58 +749,37 @@ class _KPConvFn(torch.autograd.Function):
         keep, pre = ctx.keep, 0
         gx = None
         if need_x:
-            gx, ctx.gx_buf = ctx.gx_buf, None  # cleared by the forward; a second backward gets a fresh buffer
-            pre = 1 if gx is not None else 0
-            if gx is None:
-                gx = torch.empty_like(x)
+            gx, pre = _scatter_target(ctx, x)
         gw = _grad_target(ctx.gw_slot, weights) if need_w else None
         go = grad_out.contiguous().float() if (need_x or need_w) else None
         gw_native, gx_native = gw, gx
+        # grad_W = wf^T (g / nn) over the saved weighted features: from _SPLITK_MIN_ROWS rows the reduction-parallel kernel
+        # (tall-skinny upper levels; shapes it does not take stay with d3f_kpconv_backward), below an ordinary GEMM with a
+        # short reduction -- a library call (few points, wide layers: bottom of the U-Net)
+        wf_dw = need_w and wf is not None and wf.shape[1] == K * Cin
+        big_dw = wf_dw and Nq >= _SPLITK_MIN_ROWS and L.d3f_linear_grad_weight_supported(Nq, Cout, K * Cin)
         gon = None
-        big_dw = (need_w and wf is not None and Nq >= _SPLITK_MIN_ROWS and wf.shape[1] == K * Cin
-                  and L.d3f_linear_grad_weight_supported(Nq, Cout, K * Cin))
-        if big_dw:
-            # g / nn ONCE (one small elementwise launch) for both consumers: inside the A^T B kernel the division sat in
-            # every lane of every column block behind a dependent 4-byte load (round 4, bench per-launch table:
-            # 23.9k x 480 x 32 in 63 us against 24 us without it), and the gather kernel divided once per edge
-            gon = go / nn.unsqueeze(1)
+
+        def g_over_nn():
+            # g / nn ONCE (one small elementwise launch), where its first consumer runs: inside the A^T B kernel the
+            # division sat in every lane of every column block behind a dependent 4-byte load (round 4, bench per-launch
+            # table: 23.9k x 480 x 32 in 63 us against 24 us without it), and the gather kernel divided once per edge
+            nonlocal gon
+            if gon is None:
+                gon = go / nn.unsqueeze(1)
+            return gon
         if need_x and ctx.rev is not None and Nq > 0:
-            # gather over the reverse table: aggregate grad_out/nn around every support, then contract with W^T
-            rev = ctx.rev
-            with _region("kpconv_dx_gather[Ns=%d,Cin=%d,Cout=%d]" % (Ns, Cin, Cout),
-                         kpconv_bwd_bytes(Nq, Ns, H, K, Cin, Cout)):
-                _native.check(L.d3f_kpconv_grad_input_gather(_p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent),
-                                                             _p(rev.last_key), rev.width, rev.radius, _p(rev.rel),
-                                                             _p(kernel_points), K, _p(weights), Cin, Cout, ctx.extent,
-                                                             _p(nn) if gon is None else None,
-                                                             _p(go) if gon is None else _p(gon), _p(gx),
-                                                             _p(rev.status.word) if rev.status is not None else None,
-                                                             _stream()),
-                              "d3f_kpconv_grad_input_gather")
+            # (the gather divides by nn itself unless the A^T B kernel wants g / nn anyway)
+            _kpconv_dx_gather(q_pts, s_pts, H, ctx.rev, kernel_points, weights, ctx.extent, None if big_dw else nn,
+                              g_over_nn() if big_dw else go, gx)
             gx_native = None
-        if big_dw:
-            # x := g / nn [Nq, Cout], grad_out := wf [Nq, K Cin]: grad_W [K Cin, Cout] = wf^T (g / nn)
-            _weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), True, label="kpconv_dw_atb")
-            gw_native = None
-        if need_w and wf is not None and Nq < _SPLITK_MIN_ROWS and wf.shape[1] == K * Cin:
-            # few points, wide layers (bottom of the U-Net): grad_W = wf^T (g/nn) is an ordinary GEMM with a short
-            # reduction -- a library call; the reduction-parallel kernel is for the tall-skinny upper levels
-            gon = go / nn.unsqueeze(1)
-            _weight_grad(gon, wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), False,
+        if big_dw or (wf_dw and Nq < _SPLITK_MIN_ROWS):
+            # x := g / nn [Nq, Cout], grad_out := wf [Nq, K Cin]
+            _weight_grad(g_over_nn(), wf, Nq, Cout, K * Cin, gw.view(K * Cin, Cout), big_dw, label="kpconv_dw_atb",
                          gemm_label="kpconv_dw_gemm[Nq=%d,Cin=%d,Cout=%d]" % (Nq, Cin, Cout))
             gw_native = None
         if gx_native is not None and 0 < Nq < _GEMM_DX_MAX_ROWS and L.d3f_kpconv_grad_input_supported(Cin, K, H, Ns):
-            # same layers: gW = (g/nn) W^T over all queries is one library GEMM; the kernel only scatters
-            if gon is None:
-                gon = go / nn.unsqueeze(1)
-            gwf = _kpconv_gw(gon, weights, Nq, K, Cin, Cout)
-            nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
-            ws = _ws(nbytes, x.device)
-            _count('scatter')
-            with _region("kpconv_dx_scatter[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * K * Cin + 4 * Nq * H * (1 + Cin)):
-                _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
-                                                      _p(kernel_points), K, ctx.extent, _p(gwf), _p(keep), pre, _p(gx),
-                                                      _p(ws), nbytes, _stream()), "d3f_kpconv_grad_input")
+            _kpconv_dx_scatter(q_pts, s_pts, idx, x, kernel_points, weights, ctx.extent, g_over_nn(), keep, pre, gx)
             gx_native = None
         if gx_native is not None or gw_native is not None:
             nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, Cout)
@@ -834,37 +867,20 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
         K, Cin, Cout = int(weights.shape[0]), int(weights.shape[1]), int(weights.shape[2])
         det = ctx.det = _DETERMINISTIC
-        if det and ctx.needs_input_grad[3]:
-            # the gather form at EVERY row count; a table that came without a transpose gets its CSR form here
-            if not L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K):
-                _no_deterministic_form("KPConv grad-input for %d -> %d channels" % (Cin, Cout),
-                                       "the gather form does not cover these channel counts")
-            if rev is None:
-                ptr, ent = _csr_of(idx, Ns)
-                rev = ReverseTable(ent, Nq, H, Ns, ptr=ptr)
-        elif rev is not None and not (Ns >= DX_GATHER_MIN_ROWS and
-                                      L.d3f_kpconv_grad_input_gather_supported(Cin, Cout, K)):
-            rev = None
-        ctx.rev = rev
+        # (under the mode: the gather form at EVERY row count)
+        ctx.rev = rev = _gather_table(rev, idx, Ns, K, Cin, Cout, always=det and ctx.needs_input_grad[3])
         dev = x.device
         wf = torch.empty((Nq, K * Cin), dtype=torch.float32, device=dev)
         nn = torch.empty(Nq, dtype=torch.float32, device=dev)
         nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
         ws = _ws(nbytes, dev)
-        keep = gx_buf = None
+        # (the aggregation kernel always works on packed supports; they are kept only for the scatter kernel)
         need_clear = ctx.needs_input_grad[3] and rev is None
-        # the epilogue that produced x may have packed the supports already (PackedSupports): no packing launch then
-        use_ready = ready is not None and (not need_clear or ready.gx_buf is not None)
-        if use_ready:
-            keep, gx_buf = ready.spack, (ready.gx_buf if need_clear else None)
-        elif need_clear:
-            keep = torch.empty(16 * Ns, dtype=torch.uint8, device=dev)
-            gx_buf = torch.empty_like(x)
+        keep, gx_buf, clear = _packed_supports(x, Ns, ready, True, need_clear, need_clear)
         with _region("kpconv_aggregate[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * H * (4 + Cin) + 4 * Nq * K * Cin):
             _native.check(L.d3f_kpconv_aggregate(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
-                                                 _p(kernel_points), K, float(extent), _p(wf), _p(nn), _p(keep),
-                                                 SPACK_READY if use_ready else _p(gx_buf), _p(ws), nbytes, _stream()),
-                          "d3f_kpconv_aggregate")
+                                                 _p(kernel_points), K, float(extent), _p(wf), _p(nn), _p(keep), clear,
+                                                 _p(ws), nbytes, _stream()), "d3f_kpconv_aggregate")
         ctx.keep, ctx.gx_buf = keep, gx_buf
         want_b = bias is not None and ctx.needs_input_grad[6]
         gbuf, _ = _bias_grad_buffer(want_b, False, Cout, dev)
@@ -920,30 +936,11 @@ class _KPConvGemmBiasActFn(torch.autograd.Function):
                               "d3f_kpconv_aggregate_transposed")
             gx = torch.mm(agg, _permuted_weights(weights))
         elif ctx.needs_input_grad[3] and rev is not None:
-            # gather form: one launch instead of the gW GEMM + atomic scatter (gon is already / nn)
             gx = torch.empty_like(x)
-            with _region("kpconv_dx_gather[Ns=%d,Cin=%d,Cout=%d]" % (Ns, Cin, Cout),
-                         kpconv_bwd_bytes(Nq, Ns, H, K, Cin, Cout)):
-                _native.check(L.d3f_kpconv_grad_input_gather(_p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent),
-                                                             _p(rev.last_key), rev.width, rev.radius, _p(rev.rel),
-                                                             _p(kernel_points), K, _p(weights), Cin, Cout, ctx.extent,
-                                                             None, _p(gon), _p(gx),
-                                                             _p(rev.status.word) if rev.status is not None else None,
-                                                             _stream()),
-                              "d3f_kpconv_grad_input_gather")
+            _kpconv_dx_gather(q_pts, s_pts, H, rev, kernel_points, weights, ctx.extent, None, gon, gx)
         elif ctx.needs_input_grad[3]:
-            gx, ctx.gx_buf = ctx.gx_buf, None
-            pre = 1 if gx is not None else 0
-            if gx is None:
-                gx = torch.empty_like(x)
-            gwf = _kpconv_gw(gon, weights, Nq, K, Cin, Cout)
-            nbytes = L.d3f_kpconv_ws_bytes(Nq, Ns, H, K, Cin, 64)
-            ws = _ws(nbytes, x.device)
-            _count('scatter')
-            with _region("kpconv_dx_scatter[Nq=%d,Cin=%d,H=%d]" % (Nq, Cin, H), 4 * Nq * K * Cin + 4 * Nq * H * (1 + Cin)):
-                _native.check(L.d3f_kpconv_grad_input(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin,
-                                                      _p(kernel_points), K, ctx.extent, _p(gwf), _p(ctx.keep), pre,
-                                                      _p(gx), _p(ws), nbytes, _stream()), "d3f_kpconv_grad_input")
+            gx, pre = _scatter_target(ctx, x)
+            _kpconv_dx_scatter(q_pts, s_pts, idx, x, kernel_points, weights, ctx.extent, gon, ctx.keep, pre, gx)
         return None, None, None, gx, None, _adoptable(gw, ctx.gw_slot), gb, None, None, None, None
 
 
@@ -951,6 +948,22 @@ def _ready_supports(x, s_pts):
     """The PackedSupports the producer of ``x`` left on it, if they belong to exactly this (s_pts, x)."""
     ready = getattr(x, '_d3f_spack', None)
     return ready if (ready is not None and ready.fits(s_pts, x)) else None
+
+
+def _kpconv_operands(q_pts, s_pts, neighb_inds, x, kernel_points, weights, offsets=None):
+    """(q_pts, s_pts, idx, x, kp, w) as the kernels take them (contiguous float32 / int32 device tensors), their shapes
+    checked against each other -- and ``offsets`` [Nq, K, 3] of a deformable KPConv against them."""
+    q_pts, s_pts, x = _f32(q_pts, "q_pts"), _f32(s_pts, "s_pts"), _f32(x, "x")
+    idx = _i32(neighb_inds, "neighb_inds")
+    kp, w = _f32(kernel_points, "kernel_points"), _f32(weights, "weights")
+    ok = x.shape[0] == s_pts.shape[0] and x.shape[1] == w.shape[1] and idx.shape[0] == q_pts.shape[0]
+    if offsets is not None:
+        ok = ok and tuple(offsets.shape) == (q_pts.shape[0], w.shape[0], 3)
+    if not ok:
+        text = "KPConv: inconsistent shapes q%s s%s idx%s x%s W%s" % tuple(
+            tuple(t.shape) for t in (q_pts, s_pts, idx, x, w))
+        raise RuntimeError(text if offsets is None else "deformable %s offsets%s" % (text, tuple(offsets.shape)))
+    return q_pts, s_pts, idx, x, kp, w
 
 
 def kpconv_bias_act(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent, bias, slope=0.1, influence='linear',
@@ -966,18 +979,14 @@ def kpconv_bias_act(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent
     gemm_path = _takes_gemm_path(Nq, Cin)
     if _DETERMINISTIC and torch.is_grad_enabled() and Nq > 0:
         # deterministic mode: the aggregation + GEMM node at every row count (its grad-input is the gather form); the
-        # channel counts the gather kernel does not cover go through ops.kpconv's order-fixed node below
+        # channel counts the gather kernel does not cover go through the general-path node's gather form (ops.kpconv below)
         gemm_path = not x.requires_grad or bool(
             _native.lib().d3f_kpconv_grad_input_gather_supported(Cin, int(weights.shape[2]), K))
     elif _DETERMINISTIC and not torch.is_grad_enabled() and x.requires_grad:
         x = x.detach()      # (no graph is recorded: the node must not ask for a grad-input form it will never run)
     if gemm_path and s_pts.shape[0] > 0 and \
             _native.lib().d3f_kpconv_grad_input_supported(Cin, K, H, int(s_pts.shape[0])):
-        idx = _i32(neighb_inds, "neighb_inds")
-        kp, w = _f32(kernel_points, "kernel_points"), _f32(weights, "weights")
-        if x.shape[0] != s_pts.shape[0] or x.shape[1] != w.shape[1] or idx.shape[0] != q_pts.shape[0]:
-            raise RuntimeError("KPConv: inconsistent shapes q%s s%s idx%s x%s W%s" % (
-                tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape)))
+        q_pts, s_pts, idx, x, kp, w = _kpconv_operands(q_pts, s_pts, neighb_inds, x, kernel_points, weights)
         b = _opt_f32(bias, "bias")
         rev = reverse_table_of(neighb_inds, Nq, H, int(s_pts.shape[0]), rev) if x.requires_grad else None
         return _KPConvGemmBiasActFn.apply(q_pts, s_pts, idx, x, kp, w, b, float(extent), float(slope), rev,
@@ -998,24 +1007,28 @@ def kpconv_mode(influence='linear', aggregation='sum'):
     return KP_INFLUENCES[influence] | KP_AGGREGATIONS[aggregation]
 
 
-class _KPConvModesFn(torch.autograd.Function):
-    """KPConv with a non-default influence / aggregation mode (blocks.py:327-352): mode-aware aggregation and
-    grad-input kernels of the general path, contraction with the kernel weights by library GEMMs."""
+class _KPConvGeneralFn(torch.autograd.Function):
+    """KPConv of ANY channel count and influence / aggregation mode (blocks.py:327-352) on the general path: the
+    mode-aware aggregation kernel (a gather, one wave per query) -> wf, nn; the contraction with the kernel weights by
+    library GEMMs; grad_W = wf^T (g / nn) on the weight-gradient routes of the other nodes; grad_x from
+    gW = (g / nn) W^T, as a float-atomic scatter over the table (``rev`` None: the non-default modes) or as a GATHER over
+    its transpose (``rev``: the ReverseTable in CSR or exact form; every training call under the deterministic mode, in
+    place of the scatters of this node and of _KPConvFn)."""
 
     @staticmethod
-    def forward(ctx, q_pts, s_pts, idx, x, kp, weights, extent, mode):
-        L = _native.lib()
+    def forward(ctx, q_pts, s_pts, idx, x, kp, weights, extent, mode, rev):
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
         K, Cin, Cout = (int(v) for v in weights.shape)
         wf = torch.empty((Nq, K * Cin), dtype=torch.float32, device=x.device)
         nn_ = torch.empty((Nq,), dtype=torch.float32, device=x.device)
-        with _region("kpconv_modes_fwd[Nq=%d,Cin=%d,H=%d,mode=%d]" % (Nq, Cin, H, mode), 4 * Nq * H * (4 + Cin)):
-            _native.check(L.d3f_kpconv_aggregate_modes(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin, _p(kp), K,
-                                                       extent, mode, _p(wf), _p(nn_), _stream()),
-                          "d3f_kpconv_aggregate_modes")
+        with _region("kpconv_%s_fwd[Nq=%d,Cin=%d,H=%d,mode=%d]" % ("modes" if rev is None else "ordered", Nq, Cin, H, mode),
+                     4 * Nq * H * (4 + Cin)):
+            _native.check(_native.lib().d3f_kpconv_aggregate_modes(
+                _p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin, _p(kp), K, extent, mode, _p(wf), _p(nn_),
+                _stream()), "d3f_kpconv_aggregate_modes")
         out = torch.mm(wf, weights.reshape(K * Cin, Cout)) / nn_[:, None]
         ctx.save_for_backward(q_pts, s_pts, idx, kp, weights, wf, nn_)
-        ctx.extent, ctx.mode, ctx.gw_slot = extent, mode, _grad_slot(weights)
+        ctx.extent, ctx.mode, ctx.rev, ctx.gw_slot = extent, mode, rev, _grad_slot(weights)
         return out
 
     @staticmethod
@@ -1023,59 +1036,6 @@ class _KPConvModesFn(torch.autograd.Function):
         q_pts, s_pts, idx, kp, weights, wf, nn_ = ctx.saved_tensors
         L = _native.lib()
         Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
-        K, Cin, Cout = (int(v) for v in weights.shape)
-        g = grad_out.contiguous() / nn_[:, None]
-        gx = gw = None
-        if ctx.needs_input_grad[5]:
-            gw = torch.mm(wf.t(), g).reshape(K, Cin, Cout)
-            if ctx.gw_slot is not None:
-                ctx.gw_slot.copy_(gw)
-                gw = _adoptable(ctx.gw_slot)
-        if ctx.needs_input_grad[3]:
-            gwf = torch.mm(g, weights.reshape(K * Cin, Cout).t()).contiguous()
-            gx = torch.empty((Ns, Cin), dtype=torch.float32, device=g.device)
-            with _region("kpconv_modes_dx[Nq=%d,Cin=%d,H=%d,mode=%d]" % (Nq, Cin, H, ctx.mode), 8 * Nq * H * Cin):
-                _native.check(L.d3f_kpconv_grad_input_modes(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, Cin, _p(kp), K,
-                                                            ctx.extent, ctx.mode, _p(gwf), _p(gx), _stream()),
-                              "d3f_kpconv_grad_input_modes")
-        return None, None, None, gx, None, gw, None, None
-
-
-class _KPConvOrderedFn(torch.autograd.Function):
-    """KPConv of ANY channel count and mode under the deterministic mode: the general path's aggregation kernel (a gather,
-    one wave per query) -> wf, nn; the contraction with the kernel weights by GEMMs; grad_W = wf^T (g / nn) on the
-    weight-gradient routes of the other nodes; grad_x as a GATHER over the table's transpose
-    (d3f_kpconv_grad_input_modes_gather) in place of the scatters of _KPConvFn / _KPConvModesFn.  ``rev``: the table's
-    ReverseTable in CSR or exact form; None: its CSR transpose is built here."""
-
-    @staticmethod
-    def forward(ctx, q_pts, s_pts, idx, x, kp, weights, extent, mode, rev):
-        L = _native.lib()
-        Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
-        K, Cin, Cout = (int(v) for v in weights.shape)
-        wf = torch.empty((Nq, K * Cin), dtype=torch.float32, device=x.device)
-        nn_ = torch.empty((Nq,), dtype=torch.float32, device=x.device)
-        with _region("kpconv_ordered_fwd[Nq=%d,Cin=%d,H=%d,mode=%d]" % (Nq, Cin, H, mode), 4 * Nq * H * (4 + Cin)):
-            _native.check(L.d3f_kpconv_aggregate_modes(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, _p(x), Cin, _p(kp), K,
-                                                       extent, mode, _p(wf), _p(nn_), _stream()),
-                          "d3f_kpconv_aggregate_modes")
-        out = torch.mm(wf, weights.reshape(K * Cin, Cout)) / nn_[:, None]
-        if ctx.needs_input_grad[3]:
-            if rev is not None and rev.ptr is None and rev.rel is None:
-                rev = None      # (a search-form transpose: not one of the kernel's two forms)
-            if rev is None:
-                ptr, ent = _csr_of(idx, Ns)
-                rev = ReverseTable(ent, Nq, H, Ns, ptr=ptr)
-        ctx.rev = rev
-        ctx.save_for_backward(q_pts, s_pts, kp, weights, wf, nn_)
-        ctx.extent, ctx.mode, ctx.gw_slot = extent, mode, _grad_slot(weights)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        q_pts, s_pts, kp, weights, wf, nn_ = ctx.saved_tensors
-        L = _native.lib()
-        Nq, Ns = int(q_pts.shape[0]), int(s_pts.shape[0])
         K, Cin, Cout = (int(v) for v in weights.shape)
         g = grad_out.contiguous() / nn_[:, None]
         gx = gw = None
@@ -1088,12 +1048,18 @@ class _KPConvOrderedFn(torch.autograd.Function):
             rev = ctx.rev
             gwf = torch.mm(g, weights.reshape(K * Cin, Cout).t()).contiguous()
             gx = torch.empty((Ns, Cin), dtype=torch.float32, device=g.device)
-            _count('ordered')
-            with _region("kpconv_ordered_dx[Ns=%d,Cin=%d,mode=%d]" % (Ns, Cin, ctx.mode), 8 * Nq * K * Cin):
-                _native.check(L.d3f_kpconv_grad_input_modes_gather(
-                    _p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent) if rev.ptr is not None else None,
-                    _p(rev.rel), rev.width, Cin, _p(kp), K, ctx.extent, ctx.mode, _p(gwf), _p(gx), _stream()),
-                    "d3f_kpconv_grad_input_modes_gather")
+            if rev is None:
+                with _region("kpconv_modes_dx[Nq=%d,Cin=%d,H=%d,mode=%d]" % (Nq, Cin, H, ctx.mode), 8 * Nq * H * Cin):
+                    _native.check(L.d3f_kpconv_grad_input_modes(_p(q_pts), Nq, _p(s_pts), Ns, _p(idx), H, Cin, _p(kp), K,
+                                                                ctx.extent, ctx.mode, _p(gwf), _p(gx), _stream()),
+                                  "d3f_kpconv_grad_input_modes")
+            else:
+                _count('ordered')
+                with _region("kpconv_ordered_dx[Ns=%d,Cin=%d,mode=%d]" % (Ns, Cin, ctx.mode), 8 * Nq * K * Cin):
+                    _native.check(L.d3f_kpconv_grad_input_modes_gather(
+                        _p(q_pts), Nq, _p(s_pts), Ns, _p(rev.ptr), _p(rev.ent) if rev.ptr is not None else None,
+                        _p(rev.rel), rev.width, Cin, _p(kp), K, ctx.extent, ctx.mode, _p(gwf), _p(gx), _stream()),
+                        "d3f_kpconv_grad_input_modes_gather")
         return None, None, None, gx, None, _adoptable(gw, ctx.gw_slot), None, None, None
 
 
@@ -1103,36 +1069,29 @@ def kpconv(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent, influen
     the fused kernels, the other modes of blocks.py:327-352 on the general path.  ``rev``: the table's ReverseTable
     (build_reverse_table; found on the table itself when its builder attached it): grad_x is then a gather."""
     mode = kpconv_mode(influence, aggregation)
-    q_pts, s_pts, x = _f32(q_pts, "q_pts"), _f32(s_pts, "s_pts"), _f32(x, "x")
-    idx = _i32(neighb_inds, "neighb_inds")
-    kp, w = _f32(kernel_points, "kernel_points"), _f32(weights, "weights")
-    if x.shape[0] != s_pts.shape[0] or x.shape[1] != w.shape[1] or idx.shape[0] != q_pts.shape[0]:
-        raise RuntimeError("KPConv: inconsistent shapes q%s s%s idx%s x%s W%s" % (
-            tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape)))
-    if _DETERMINISTIC and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
-        # a training call under the deterministic mode: every mode and channel count through the order-fixed node
-        # (_KPConvFn's kernels combine channel chunks, waves and weight-gradient partials with float atomics, _KPConvFn /
-        # _KPConvModesFn scatter their grad-input)
-        if q_pts.shape[0] == 0 or s_pts.shape[0] == 0:
-            return x.new_zeros((q_pts.shape[0], w.shape[2])) + 0.0 * (x.sum() + w.sum())
-        # ... but the input layer (features without gradient) on the input-layer kernels: their forward has no atomic and,
-        # where they save the weighted features (16-slot rows: Cout % 16 == 0), grad_W is the A^T B kernel over them
-        # (asked at K = 1, where the 16-slot rows cannot be mistaken for K * Cin)
-        if mode == 0 and not x.requires_grad and SAVE_WEIGHTED_FEATURES and \
-                _native.lib().d3f_kpconv_saves_wf(int(w.shape[1]), int(w.shape[2]), 1, int(idx.shape[1])) == 16 * int(w.shape[1]):
-            return _KPConvFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), None, None)
-        if x.requires_grad:
-            rev = reverse_table_of(neighb_inds, int(q_pts.shape[0]), int(idx.shape[1]), int(s_pts.shape[0]), rev)
-        return _KPConvOrderedFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), mode, rev if x.requires_grad else None)
-    if mode != 0:
-        if q_pts.shape[0] == 0 or s_pts.shape[0] == 0:
-            return x.new_zeros((q_pts.shape[0], w.shape[2])) + 0.0 * (x.sum() + w.sum())
-        return _KPConvModesFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), mode)
-    if x.requires_grad:
-        rev = reverse_table_of(neighb_inds, int(q_pts.shape[0]), int(idx.shape[1]), int(s_pts.shape[0]), rev)
+    q_pts, s_pts, idx, x, kp, w = _kpconv_operands(q_pts, s_pts, neighb_inds, x, kernel_points, weights)
+    Nq, Ns, H = int(q_pts.shape[0]), int(s_pts.shape[0]), int(idx.shape[1])
+    # a training call under the deterministic mode: every mode and channel count through the general node's gather form
+    # (_KPConvFn's kernels combine channel chunks, waves and weight-gradient partials with float atomics, and both nodes'
+    # other grad-input forms scatter)
+    ordered = _DETERMINISTIC and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
+    if (ordered or mode != 0) and (Nq == 0 or Ns == 0):
+        return x.new_zeros((Nq, w.shape[2])) + 0.0 * (x.sum() + w.sum())
+    # ... but the input layer (features without gradient) on the input-layer kernels: their forward has no atomic and,
+    # where they save the weighted features (16-slot rows: Cout % 16 == 0), grad_W is the A^T B kernel over them
+    # (asked at K = 1, where the 16-slot rows cannot be mistaken for K * Cin)
+    if ordered and mode == 0 and not x.requires_grad and SAVE_WEIGHTED_FEATURES and \
+            _native.lib().d3f_kpconv_saves_wf(int(w.shape[1]), int(w.shape[2]), 1, H) == 16 * int(w.shape[1]):
+        return _KPConvFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), None, None)
+    if x.requires_grad and (ordered or mode == 0):
+        rev = reverse_table_of(neighb_inds, Nq, H, Ns, rev)
     else:
         rev = None
-    return _KPConvFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), rev, _ready_supports(x, s_pts))
+    if not ordered and mode == 0:
+        return _KPConvFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), rev, _ready_supports(x, s_pts))
+    if ordered and x.requires_grad and (rev is None or (rev.ptr is None and rev.rel is None)):
+        rev = _csr_table(idx, Ns)       # (no transpose, or a search-form one: not one of the gather kernel's two forms)
+    return _KPConvGeneralFn.apply(q_pts, s_pts, idx, x, kp, w, float(extent), mode, rev)
 
 
 class _KPConvDeformAggFn(torch.autograd.Function):
@@ -1186,15 +1145,9 @@ def kpconv_deformable(q_pts, s_pts, neighb_inds, x, kernel_points, weights, exte
     the last two are what the reference keeps on the module for its fitting / repulsive regulariser
     (architectures.py:22-55); min_d2 carries its gradient to the offsets."""
     mode = kpconv_mode(influence, aggregation)
-    q_pts, s_pts, x = _f32(q_pts, "q_pts"), _f32(s_pts, "s_pts"), _f32(x, "x")
-    idx = _i32(neighb_inds, "neighb_inds")
-    kp, w = _f32(kernel_points, "kernel_points"), _f32(weights, "weights")
+    q_pts, s_pts, idx, x, kp, w = _kpconv_operands(q_pts, s_pts, neighb_inds, x, kernel_points, weights, offsets)
     K, Cin, Cout = (int(v) for v in w.shape)
     Nq = int(q_pts.shape[0])
-    if x.shape[0] != s_pts.shape[0] or x.shape[1] != Cin or idx.shape[0] != Nq or tuple(offsets.shape) != (Nq, K, 3):
-        raise RuntimeError("deformable KPConv: inconsistent shapes q%s s%s idx%s x%s W%s offsets%s" % (
-            tuple(q_pts.shape), tuple(s_pts.shape), tuple(idx.shape), tuple(x.shape), tuple(w.shape),
-            tuple(offsets.shape)))
     if _DETERMINISTIC and torch.is_grad_enabled() and x.requires_grad:
         _no_deterministic_form("kpconv_deformable")
     deformed = offsets + kp                                              # blocks.py:287

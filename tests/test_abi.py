@@ -236,6 +236,26 @@ def test_no_gpu_calls_needed_for_size_queries():
     assert lib.d3f_circle_det_loss_stats_floats(128) == 6 * 128
 
 
+def test_general_path_kpconv_entries_reject_bad_arguments_on_the_host():
+    """d3f_kpconv_aggregate_modes / _grad_input_modes / _grad_input_modes_gather: a mode outside the table of
+    kpconv_modes.hpp, K > 16, Cin > 512 or extent = 0 is D3F_EINVAL before anything touches a device (the addresses are
+    never read); the gather entry also wants exactly one of the two forms of the transpose."""
+    lib = _native.lib()
+    p, nq, ns, h = 0x10000, 5, 4, 3         # (16-byte aligned, as the exact-form table has to be)
+
+    def gather(mode=0, K=15, Cin=8, extent=0.1, csr=p, rel=None):
+        return lib.d3f_kpconv_grad_input_modes_gather(p, nq, p, ns, csr, csr, rel, 7, Cin, p, K, extent, mode, p, p, None)
+
+    def table_entries(mode=0, K=15, Cin=8, extent=0.1):
+        return (lib.d3f_kpconv_aggregate_modes(p, nq, p, ns, p, h, p, Cin, p, K, extent, mode, p, p, None),
+                lib.d3f_kpconv_grad_input_modes(p, nq, p, ns, p, h, Cin, p, K, extent, mode, p, p, None))
+    # (every call below has exactly one bad argument, so none of them gets as far as a launch)
+    for kw in [dict(mode=m) for m in (-1, 3, 7 + 1)] + [dict(K=17), dict(Cin=513), dict(extent=0.0)]:
+        assert table_entries(**kw) + (gather(**kw),) == (_native.D3F_EINVAL,) * 3, kw
+    assert gather(rel=p) == _native.D3F_EINVAL               # both forms of the transpose
+    assert gather(csr=None) == _native.D3F_EINVAL            # neither
+
+
 def test_tunables_struct_round_trips_and_rejects_nonsense():
     """d3f_get_tunables / d3f_set_tunables: the library's only knobs (it reads no environment); defaults are all zero."""
     lib = _native.lib()

@@ -192,19 +192,14 @@ def test_pool_nodes_follow_the_mode_of_their_forward():
 
 
 # ------------------------------------------------------------------------------------------------ 2. KPConv grad-input
-@pytest.mark.parametrize("ns", [37, 159])
-@pytest.mark.parametrize("ch", [64, 512])
-@pytest.mark.parametrize("block", [True, False])
-def test_kpconv_grad_input_is_a_gather_at_few_rows(ns, ch, block):
-    """Below ops.DX_GATHER_MIN_ROWS the default grad-input is the float-atomic scatter; under the mode the block's node
-    (aggregation + GEMM, d3f_kpconv_grad_input_gather) and ops.kpconv's order-fixed node both gather.  Against float64."""
+def _check_grad_input_is_a_gather(ns, ch, block, mode=('linear', 'sum')):
     rng = np.random.default_rng([ns, ch])
     h = 12
     q, s, idx, x, kp, w = _kpconv_case(rng, ns, ns, h, ch, ch)
     bias = rng.normal(size=ch).astype(np.float32) * 0.1
     d = lambda a: torch.from_numpy(a).double()
     tx, tw = d(x).requires_grad_(True), d(w).requires_grad_(True)
-    ref = ops_ref.kpconv(d(q), d(s), torch.from_numpy(idx), tx, d(kp), tw, SPARSE_EXTENT)
+    ref = ops_ref.kpconv(d(q), d(s), torch.from_numpy(idx), tx, d(kp), tw, SPARSE_EXTENT, *mode)
     if block:
         ref = torch.nn.functional.leaky_relu(ref + d(bias), 0.1)
     go = rng.normal(size=tuple(ref.shape)).astype(np.float32)
@@ -225,7 +220,7 @@ def test_kpconv_grad_input_is_a_gather_at_few_rows(ns, ch, block):
                 if block:
                     out = ops.kpconv_bias_act(cu(q), cu(s), tab, gx, cu(kp), gw, SPARSE_EXTENT, cu(bias))
                 else:
-                    out = ops.kpconv(cu(q), cu(s), tab, gx, cu(kp), gw, SPARSE_EXTENT)
+                    out = ops.kpconv(cu(q), cu(s), tab, gx, cu(kp), gw, SPARSE_EXTENT, *mode)
             out.backward(cu(go))
         finally:
             ops.set_profiler(None)
@@ -240,6 +235,23 @@ def test_kpconv_grad_input_is_a_gather_at_few_rows(ns, ch, block):
     assert rel_err(grads[0][1].cpu().numpy(), tw.grad.numpy()) < BWD_TOL
     assert np.array_equal(bits(grads[0][0]), bits(grads[1][0]))
     assert np.array_equal(bits(grads[0][1]), bits(grads[1][1]))
+
+
+@pytest.mark.parametrize("ns", [37, 159])
+@pytest.mark.parametrize("ch", [64, 512])
+@pytest.mark.parametrize("block", [True, False])
+def test_kpconv_grad_input_is_a_gather_at_few_rows(ns, ch, block):
+    """Below ops.DX_GATHER_MIN_ROWS the default grad-input is the float-atomic scatter; under the mode the block's node
+    (aggregation + GEMM, d3f_kpconv_grad_input_gather) and ops.kpconv's order-fixed node both gather.  Against float64."""
+    _check_grad_input_is_a_gather(ns, ch, block)
+
+
+@pytest.mark.parametrize("mode", [("gaussian", "closest"), ("constant", "sum")], ids="-".join)
+def test_kpconv_grad_input_is_a_gather_at_a_non_default_mode(mode):
+    """The block=False arm of the test above (ops.kpconv's general-path node, gather form) at the other influence /
+    aggregation modes, against ops_ref.kpconv in float64 with the same bounds (tests/test_kpconv_cases_cpu.py holds the
+    float32 oracle to them on these inputs)."""
+    _check_grad_input_is_a_gather(37, 64, False, mode)
 
 
 # ------------------------------------------------------------------------------------------------ 3. sparse loss backward

@@ -835,12 +835,10 @@ def test_split_backward_matches_single_backward(golden_s0):
     assert float((c.flat.data - d.flat.data).abs().max()) < 1e-4 * float(d.flat.data.abs().max())
 
 
-def test_weight_gradients_land_in_the_flat_buffer_without_copies(golden_s0):
-    """FlatParams hands every weight matrix / KPConv kernel its place in the flat gradient buffer; the backward
-    kernels write there and autograd adopts the view (no clone, no concatenation); values equal a plain backward."""
+def _slot_backward_and_plain_backward(g, cfg):
+    """(TrainStep, flat gradient of a backward into the reserved slots, the same backward with ordinary gradient tensors);
+    asserts that every weight's gradient was adopted in its slot."""
     from d3feat_pytorch_amd.train import TrainStep
-    g = golden_s0
-    cfg = cfgmod.default_config(first_features_dim=16, num_node=64)
     limits = [int(x) for x in g['limits']]
     item = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in _item(g))
     np.random.seed(0)
@@ -862,7 +860,37 @@ def test_weight_gradients_land_in_the_flat_buffer_without_copies(golden_s0):
     t.flat.zero_grad()
     t.forward_loss(batch)[0].backward()
     ref = torch.cat([p.grad.reshape(-1) for p in t.flat.params])
+    return t, flat, ref
+
+
+def test_weight_gradients_land_in_the_flat_buffer_without_copies(golden_s0):
+    """FlatParams hands every weight matrix / KPConv kernel its place in the flat gradient buffer; the backward
+    kernels write there and autograd adopts the view (no clone, no concatenation); values equal a plain backward."""
+    _, flat, ref = _slot_backward_and_plain_backward(
+        golden_s0, cfgmod.default_config(first_features_dim=16, num_node=64))
     assert float((flat - ref).abs().max()) < 1e-6 * float(ref.abs().max())
+
+
+def test_weight_gradients_land_in_the_flat_buffer_at_a_non_default_mode(golden_s0):
+    """The same with KP_influence 'gaussian' / aggregation_mode 'closest': every KPConv is the general-path node, whose
+    weight gradient goes to its slot like every other node's.  Bounds, both relative to the largest entry of the plain
+    backward's gradient: 1e-6 (the bound of the test above) for the parameters from the last KPConv kernel on, in the
+    model's order -- the backward pass forms their gradients before it reaches a KPConv grad-input; 2e-5 (the drift
+    test_bench_paths... allows between two replays of a step with float atomics) for the parameters before it: their
+    gradients come through at least one grad-input, which this node scatters with float atomics in both runs."""
+    t, flat, ref = _slot_backward_and_plain_backward(
+        golden_s0, cfgmod.default_config(first_features_dim=16, num_node=64, KP_influence='gaussian',
+                                         aggregation_mode='closest'))
+    names = [n for n, p in t.model.named_parameters() if p.requires_grad]
+    assert len(names) == len(t.flat.params)
+    last_kp = max(i for i, n in enumerate(names) if n.endswith('KPConv.weights'))
+    scale, off = float(ref.abs().max()), 0
+    for i, (n, p) in enumerate(zip(names, t.flat.params)):
+        diff = float((flat[off:off + p.numel()] - ref[off:off + p.numel()]).abs().max())
+        bound = 2e-5 if i < last_kp else 1e-6
+        print("%-50s %.3e of the largest entry (bound %.0e)" % (n, diff / scale, bound))
+        assert diff < bound * scale, (n, diff / scale, bound)
+        off += p.numel()
 
 
 def test_trainer_epochs_schedule_under_graph_and_snapshot_resume(golden_s0, tmp_path):

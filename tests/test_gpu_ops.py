@@ -1559,6 +1559,49 @@ def test_kpconv_modes_match_reference_vectors(influence, aggregation):
         assert err <= 1e-4 * max(1.0, float(v.abs().max())), (name, err)
 
 
+@pytest.mark.parametrize("influence,aggregation", [("gaussian", "closest"), ("constant", "sum")])
+def test_kpconv_modes_weight_gradient_routes(influence, aggregation):
+    """The general-path node's weight gradient on the routes every node takes: 4100 rows are the first past
+    ops._SPLITK_MIN_ROWS and 16 / 15 * 16 / 16 the smallest channel counts the A^T B kernel takes, so outside a
+    weight_grad_group it is that kernel and inside one it joins the stage's grouped launch.  Against the float64 oracle."""
+    import os
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'kpconv_modes.npz'))
+    K = g['weights'].shape[0]
+    gen = torch.Generator().manual_seed(12)
+    nq, ns, H, ci, co = 4100, 600, 8, 16, 16
+    assert nq >= ops._SPLITK_MIN_ROWS and _native.lib().d3f_linear_grad_weight_supported(nq, co, K * ci)
+    s_pts = torch.rand((ns, 3), generator=gen)
+    q_pts = torch.rand((nq, 3), generator=gen)
+    d2 = ((q_pts[:, None] - s_pts[None]) ** 2).sum(-1)
+    dist, order = torch.sort(d2, dim=1)
+    inds = torch.where(dist[:, :H] < 0.2 ** 2, order[:, :H], torch.full_like(order[:, :H], ns))
+    kp = torch.from_numpy(g['kernel_points']) * 0.8
+    w = torch.randn((K, ci, co), generator=gen) * 0.1
+    xx = torch.randn((ns, ci), generator=gen)
+    go = torch.randn((nq, co), generator=gen)
+    a = [t.double().requires_grad_(True) for t in (xx, w)]
+    ops_ref.kpconv(q_pts.double(), s_pts.double(), inds, a[0], kp.double(), a[1], 0.1, influence, aggregation).backward(
+        go.double())
+
+    class Prof:
+        records = []
+    for grouped in (False, True):
+        b = [t.clone().to(DEV).requires_grad_(True) for t in (xx, w)]
+        got = ops.kpconv(q_pts.to(DEV), s_pts.to(DEV), inds.to(DEV), b[0], kp.to(DEV), b[1], 0.1, influence, aggregation)
+        Prof.records = []
+        ops.set_profiler(Prof)
+        try:
+            with ops.weight_grad_group() if grouped else _nullcontext() as group:
+                got.backward(go.to(DEV))
+                assert not grouped or len(group.problems) == 1
+        finally:
+            ops.set_profiler(None)
+        torch.cuda.synchronize()
+        assert grouped or any(r[0].startswith("kpconv_dw_atb") for r in Prof.records), [r[0] for r in Prof.records]
+        assert rel_err(b[0].grad.cpu().numpy(), a[0].grad.numpy()) < BWD_TOL, grouped
+        assert rel_err(b[1].grad.cpu().numpy(), a[1].grad.numpy()) < BWD_TOL, grouped
+
+
 def test_guarded_sgd_step_matches_torch_sgd_and_skips_on_nonfinite():
     """d3f_sgd_guarded_step vs torch.optim.SGD(momentum, weight_decay) (training_3DMatch.py:62-76) + the guard of
     trainer.py:104-111; device-resident hyper-parameters incl. the gradient scale of the data-parallel mean."""
