@@ -79,14 +79,14 @@ D3F_HD inline void normal_from_moments(const int64_t (&m)[10], double Q, double 
 // entry (i, j), i <= j, of the packed upper triangle of a 6x6, row by row
 D3F_HD constexpr int upper6(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
 
-// T_k [12] row-major 3x4 -> T_next [12]; false (T_next = T_k) when the system is singular
-D3F_HD inline bool plane_step(const double sums[kPlaneSums], const double py[3], const double Tk[12], double Tn[12]) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) Tn[k] = Tk[k];
+// v = -A^-1 b for the symmetric 6x6 A given by its packed upper triangle (upper6) and the right-hand side b, by
+// Cholesky; false (v untouched) when a pivot is <= kPlanePivot * max_i A_ii or not a number.  The point-to-plane step
+// below and the fast-global-registration step (fgr.hpp) share it.
+D3F_HD inline bool solve6(const double A[21], const double b[6], double v[6]) {
   double L[21], top = 0.0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    const double d = sums[1 + upper6(i, i)];
+    const double d = A[upper6(i, i)];
     top = d > top ? d : top;
   }
   const double floor_ = kPlanePivot * top;
@@ -94,7 +94,7 @@ D3F_HD inline bool plane_step(const double sums[kPlaneSums], const double py[3],
   // A = U^T U with U upper triangular, kept in the packed layout of the sums
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    double d = sums[1 + upper6(i, i)];
+    double d = A[upper6(i, i)];
 #pragma unroll
     for (int k = 0; k < i; ++k) d -= L[upper6(k, i)] * L[upper6(k, i)];
     if (!(d > floor_)) ok = false;   // (NaN too)
@@ -102,17 +102,17 @@ D3F_HD inline bool plane_step(const double sums[kPlaneSums], const double py[3],
     L[upper6(i, i)] = root;
 #pragma unroll
     for (int j = i + 1; j < 6; ++j) {
-      double s = sums[1 + upper6(i, j)];
+      double s = A[upper6(i, j)];
 #pragma unroll
       for (int k = 0; k < i; ++k) s -= L[upper6(k, i)] * L[upper6(k, j)];
       L[upper6(i, j)] = s / root;
     }
   }
   if (!ok) return false;
-  double y[6], v[6];
+  double y[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {   // U^T y = -b
-    double s = -sums[22 + i];
+    double s = -b[i];
 #pragma unroll
     for (int k = 0; k < i; ++k) s -= L[upper6(k, i)] * y[k];
     y[i] = s / L[upper6(i, i)];
@@ -124,6 +124,15 @@ D3F_HD inline bool plane_step(const double sums[kPlaneSums], const double py[3],
     for (int k = i + 1; k < 6; ++k) s -= L[upper6(i, k)] * v[k];
     v[i] = s / L[upper6(i, i)];
   }
+  return true;
+}
+
+// T_k [12] row-major 3x4 -> T_next [12]; false (T_next = T_k) when the system is singular
+D3F_HD inline bool plane_step(const double sums[kPlaneSums], const double py[3], const double Tk[12], double Tn[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Tn[k] = Tk[k];
+  double v[6];
+  if (!solve6(sums + 1, sums + 22, v)) return false;
   const double ca = cos(v[0]), sa = sin(v[0]), cb = cos(v[1]), sb = sin(v[1]), cg = cos(v[2]), sg = sin(v[2]);
   const double D[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
                        sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,

@@ -2,11 +2,15 @@
 
 The reference stops at the feature-match recall (``evaluate.register_one_scene``) and leaves pose estimation to Open3D
 on the CPU.  Here it runs on the device: top-k keypoints by score, mutual nearest neighbours (``ops.mutual_nn``), then
-RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid`` call (two launches).
+RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid`` call (two launches) -- or, with
+``estimator='fgr'``, fast global registration of the same matches in one ``ops.fgr_rigid`` call (one launch).
 
 * ``estimate_transform``             one pair: keypoints / descriptors / scores -> (T, inliers, num_matches);
 * ``estimate_transforms_from_match`` the batched inference path: ``infer.InferStep.match(item, feats, scores,
   num_points=k)`` output -> one transform per pair of the stacked item;
+* ``fgr_numpy`` / ``fgr_multiplicities`` / ``fgr_draw``  the NumPy restatement of ``ops.fgr_rigid`` (csrc/fgr.hpp has
+  the rule: tuple test, graduated non-convexity, Gauss-Newton on SE(3)) and of its tuple test and sampler;
+  ``FGR_DEFAULTS`` are the parameters ``estimator='fgr'`` starts from;
 * ``loadinfo`` / ``transformation_error`` / ``evaluate_registration``  the benchmark's ``gt.info`` files and its
   registration recall / precision (error p <= 0.2^2 under the 6x6 information matrix, pairs with j - i > 1);
 * ``register_scene``                  every pair listed in ``gt.log`` from the dumped files, estimates written in the
@@ -44,6 +48,11 @@ from . import evaluate as ev
 from .common import select_keypoints
 
 RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio=0.9, refine_iters=3, seed=0)
+FGR_DEFAULTS = dict(distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4, tuple_scale=0.95,
+                    tuple_trials=None, max_tuples=1000, seed=0)
+FGR_ST_FEW, FGR_ST_SINGULAR, FGR_ST_SEGMENT, FGR_ST_NONFINITE = 1, 2, 4, 8                          # ops.FGR_ST_*
+FGR_MAX_TRIALS = 1 << 22       # ops.FGR_MAX_TRIALS
+RANSAC_MIN_CROSS2 = 1e-12      # csrc/rigid.hpp kMinCross2
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 1, 2, 4, 8, 16      # ops.ICP_ST_*
 PG_ST_ITER_CAP, PG_ST_NONFINITE, PG_ST_GRAPH, PG_ST_INDEFINITE = 1, 2, 4, 8                         # ops.PG_ST_*
 PG_LAMBDA0, PG_LAMBDA_MIN, PG_LAMBDA_MAX = 1e-4, 1e-12, 1e8    # csrc/posegraph.hpp kLambda0 / kLambdaMin / kLambdaMax
@@ -86,27 +95,32 @@ def _pair_points(source_keypts, source_desc, source_score, target_keypts, target
 
 
 def estimate_transform(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
-                       num_points=5000, icp=None, **ransac):
+                       num_points=5000, icp=None, estimator='ransac', fgr=None, **ransac):
     """One fragment pair (device tensors): top-k keypoints by score, mutual nearest neighbours, RANSAC.  Returns device
     tensors ``(T [4,4] f64, inliers, num_matches)``; T maps the target into the source frame.  ``ransac``: keywords of
-    ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS).  ``icp``: None, or a dict of ``refine_transforms`` keywords (at
-    least ``max_distance``): the RANSAC pose is then refined by ICP over ALL points of the two fragments."""
+    ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS).  ``estimator='fgr'`` hands the same matches to ``ops.fgr_rigid``
+    instead, with ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); no ``ransac`` keyword is taken then.
+    ``icp``: None, or a dict of ``refine_transforms`` keywords (at least ``max_distance``): the estimated pose is then
+    refined by ICP over ALL points of the two fragments."""
+    _check_estimator(estimator, fgr, ransac)
     mutual, sp, tp = _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
                                   num_points)
     src, tgt, seg, n = _compact(mutual.view(1, -1), sp.unsqueeze(0), tp.unsqueeze(0))
-    T, inl = _ransac(src, tgt, seg, ransac)[:2]
+    T, inl = _estimate(estimator, fgr, src, tgt, seg, ransac)
     if icp is not None:
         T = refine_transforms([source_keypts, target_keypts], [(0, 1)], T, device=source_keypts.device,
                               **_icp_keywords(icp))[0]
     return T[0], inl[0], n[0]
 
 
-def estimate_transforms_from_match(points, seg, row, mutual, sel, **ransac):
+def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ransac', fgr=None, **ransac):
     """The batched path: ``row, mutual, sel = InferStep.match(item, feats, scores, num_points=k)`` with ``points`` the
     item's stacked level-0 points [rows,3] and ``seg`` = ``InferStep.segments(item)`` [2P,2] (clouds 2p, 2p+1 are the
     source and target of pair p).  The mutual rows of every pair are compacted on the device and ONE ``ransac_rigid``
-    call estimates all P transforms.  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
-    P, k = int(row.shape[0]), int(row.shape[1])
+    call estimates all P transforms (``estimator='fgr'``, ``fgr=dict(...)``: one ``fgr_rigid`` call, as in
+    ``estimate_transform``).  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
+    _check_estimator(estimator, fgr, ransac)
+    P, k =int(row.shape[0]), int(row.shape[1])
     pts = points if points.dtype == torch.float32 else points.float()
     off = seg[:, 0].long()
     live = (sel >= 0)
@@ -117,8 +131,203 @@ def estimate_transforms_from_match(points, seg, row, mutual, sel, **ransac):
     tgt_rows = off[1::2].view(P, 1) + torch.gather(sel[1::2].long(), 1, tslot).clamp(min=0)
     m = mutual.bool() & live[0::2]
     src, tgt, sg, n = _compact(m, pts[src_rows.reshape(-1)].view(P, k, 3), pts[tgt_rows.reshape(-1)].view(P, k, 3))
-    T, inl = _ransac(src, tgt, sg, ransac)[:2]
+    T, inl = _estimate(estimator, fgr, src, tgt, sg, ransac)
     return T, inl, n
+
+
+# ------------------------------------------------------------------------------------------------- fast global registration
+def _splitmix64(x):
+    x = np.asarray(x, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def fgr_draw(seed, p, h, count):
+    """[..., 3] indices that trial h of pair p draws from ``count`` correspondences: the hash of csrc/rigid.hpp."""
+    key = _splitmix64(_splitmix64(np.uint64(int(seed) & 0xffffffffffffffff)) ^ np.uint64(p))
+    h = np.asarray(h, dtype=np.uint64)
+    out = []
+    for k in range(3):
+        z = _splitmix64(key ^ ((h << np.uint64(2)) | np.uint64(k)))
+        with np.errstate(over='ignore'):
+            out.append(((z >> np.uint64(32)) * np.uint64(count)) >> np.uint64(32))
+    return np.stack(out, axis=-1).astype(np.int64)
+
+
+def _fgr_triples_ok(s, g, scale):
+    """[H,3,3] f64 source / target triples -> [H] bool: rigid::triple_ok in its own order of operations."""
+    def cross2(p):
+        u, v = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+        x = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+        y = u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2]
+        z = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+        return (x * x + y * y) + z * z
+
+    def dist2(a, b):
+        d = a - b
+        return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    with np.errstate(invalid='ignore'):
+        ok = ~(cross2(s) < RANSAC_MIN_CROSS2) & ~(cross2(g) < RANSAC_MIN_CROSS2)
+        r2 = scale * scale
+        for i, j in ((0, 1), (1, 2), (2, 0)):
+            la2, lb2 = dist2(s[:, i], s[:, j]), dist2(g[:, i], g[:, j])
+            lo, hi = np.where(la2 < lb2, la2, lb2), np.where(la2 < lb2, lb2, la2)
+            ok &= lo >= r2 * hi
+    return ok
+
+
+def fgr_multiplicities(src, tgt, seed, p, tuple_scale=0.95, tuple_trials=None, max_tuples=1000, chunk=1 << 16):
+    """The tuple test of csrc/fgr.hpp on one pair's [n,3] f32 correspondences -> ``(m int32 [n], tuples)``."""
+    n = int(src.shape[0])
+    trials = min(100 * n, FGR_MAX_TRIALS) if tuple_trials is None else int(tuple_trials)
+    if trials == 0:
+        return np.ones(n, dtype=np.int32), 0
+    m, taken = np.zeros(n, dtype=np.int64), 0
+    s64, g64 = src.astype(np.float64), tgt.astype(np.float64)
+    for base in range(0, trials, chunk):
+        idx = fgr_draw(seed, p, np.arange(base, min(base + chunk, trials)), n)
+        ok = (idx[:, 0] != idx[:, 1]) & (idx[:, 0] != idx[:, 2]) & (idx[:, 1] != idx[:, 2])
+        ok &= _fgr_triples_ok(s64[idx], g64[idx], float(tuple_scale))
+        good = idx[ok]
+        if max_tuples > 0:
+            good = good[:max_tuples - taken]
+        m += np.bincount(good.reshape(-1), minlength=n)
+        taken += len(good)
+        if max_tuples > 0 and taken >= max_tuples:
+            break
+    return m.astype(np.int32), taken
+
+
+def _inliers_f32(T, src, tgt, tau):
+    """rigid::inlier_f32 over [n,3] f32 rows under the f32 image of T.  A f32 fmaf is taken as the f32 rounding of the
+    f64 ``a * b + c`` (the product is exact in f64): equal to the true fmaf except on double-rounding ties."""
+    f32, f64 = np.float32, np.float64
+    rt = T[:3].astype(f32)
+    fma = lambda a, b, c: (f64(a) * b.astype(f64) + c.astype(f64)).astype(f32)
+    x, y, z = tgt[:, 0], tgt[:, 1], tgt[:, 2]
+    e = []
+    for a in range(3):
+        inner = fma(rt[a, 2], z, np.full(len(tgt), rt[a, 3], dtype=f32))
+        e.append(fma(rt[a, 0], x, fma(rt[a, 1], y, inner)) - src[:, a])
+    d2 = (e[2].astype(f64) * e[2].astype(f64)
+          + ((e[1].astype(f64) * e[1].astype(f64) + (e[0] * e[0]).astype(f64)).astype(f32)).astype(f64)).astype(f32)
+    return int((d2 < f32(tau) * f32(tau)).sum())
+
+
+def fgr_numpy(src, tgt, seg, distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4,
+              tuple_scale=0.95, tuple_trials=None, max_tuples=1000, seed=0, first_pair=0, return_debug=False):
+    """The rule of ``ops.fgr_rigid`` (csrc/fgr.hpp) restated in NumPy f64 -- the independent witness of the device code
+    and its host twin, not a transliteration: explicit 3x6 Jacobians, ``np.sum`` / ``einsum`` in their own order, a
+    general linear solve behind the kernel's pivot test.  ``src`` / ``tgt`` [rows,3] f32 and ``seg`` [P,2] are host
+    arrays.  Returns arrays ``(T [P,4,4], inliers [P], tuples [P], weight_sum [P], status [P])`` and, with
+    ``return_debug``, ``(multiplicity int32 [rows], trace [P, iterations, 8])`` as ``ops.fgr_rigid`` does."""
+    src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    tgt = np.ascontiguousarray(tgt, dtype=np.float32).reshape(-1, 3)
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1, 2)
+    P, rows, K = seg.shape[0], src.shape[0], int(iterations)
+    T = np.tile(np.eye(4), (P, 1, 1))
+    inl, tup, st = (np.zeros(P, dtype=np.int32) for _ in range(3))
+    wsum = np.zeros(P)
+    mult = np.zeros(rows, dtype=np.int32)
+    trace = np.full((P, K, 8), np.nan)
+    delta2 = float(distance_threshold) * float(distance_threshold)
+    for p, (off, n) in enumerate(seg):
+        if off < 0 or n < 0 or n > ops.RANSAC_MAX_COUNT or off + n > rows:
+            st[p] = FGR_ST_SEGMENT
+            continue
+        if n < 3:
+            st[p] = FGR_ST_FEW
+            continue
+        a32, b32 = src[off:off + n], tgt[off:off + n]
+        m, tup[p] = fgr_multiplicities(a32, b32, seed, first_pair + p, tuple_scale, tuple_trials, int(max_tuples))
+        mult[off:off + n] = m
+        live = m > 0
+        if live.sum() < 3:
+            st[p] |= FGR_ST_FEW
+            continue
+        a, b, w0 = a32[live].astype(np.float64), b32[live].astype(np.float64), m[live].astype(np.float64)
+        with np.errstate(all='ignore'):
+            ca, cb = a.mean(0), b.mean(0)
+            a, b = a - ca, b - cb
+            mu = max(float((a * a).sum(1).max()), float((b * b).sum(1).max()))
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            st[p] |= FGR_ST_NONFINITE
+            continue
+        R, t = np.eye(3), np.zeros(3)
+        for it in range(K):
+            if it % int(anneal_every) == 0 and mu > delta2:
+                mu = max(mu / float(division_factor), delta2)
+            with np.errstate(all='ignore'):
+                q = b @ R.T + t
+                r = a - q
+                w = w0 * (mu / ((r * r).sum(1) + mu)) ** 2
+                J = np.zeros((len(q), 3, 6))
+                J[:, 0, 1], J[:, 0, 2] = -q[:, 2], q[:, 1]                 # [q]x
+                J[:, 1, 0], J[:, 1, 2] = q[:, 2], -q[:, 0]
+                J[:, 2, 0], J[:, 2, 1] = -q[:, 1], q[:, 0]
+                J[:, 0, 3] = J[:, 1, 4] = J[:, 2, 5] = -1.0
+                A = np.einsum('n,nij,nik->jk', w, J, J)
+                g = np.einsum('n,nij,ni->j', w, J, r)
+            if not (np.isfinite(A).all() and np.isfinite(g).all() and np.isfinite(w.sum())):
+                st[p] |= FGR_ST_NONFINITE
+                break
+            wsum[p] = w.sum()
+            floor, U, singular = PLANE_PIVOT * A.diagonal().max(), np.zeros((6, 6)), False
+            for i in range(6):
+                d = A[i, i] - (U[:i, i] ** 2).sum()
+                if not d > floor:
+                    singular = True
+                    break
+                U[i, i] = np.sqrt(d)
+                U[i, i + 1:] = (A[i, i + 1:] - U[:i, i] @ U[:i, i + 1:]) / U[i, i]
+            step = np.zeros(6) if singular else np.linalg.solve(A, -g)
+            trace[p, it] = np.concatenate([[mu, wsum[p]], step])
+            if singular:
+                st[p] |= FGR_ST_SINGULAR
+                break
+            E = _rodrigues(step[:3])
+            R, t = E @ R, E @ t + step[3:]
+        if st[p] & FGR_ST_NONFINITE:
+            wsum[p] = 0.0
+            continue
+        T[p, :3, :3], T[p, :3, 3] = R, ca + t - R @ cb
+        inl[p] = _inliers_f32(T[p], a32, b32, distance_threshold)
+    res = (T, inl, tup, wsum, st)
+    return res + (mult, trace) if return_debug else res
+
+
+def _rodrigues(w):
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:
+        return np.eye(3) + K
+    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
+
+
+def _fgr(src, tgt, seg, params):
+    p = dict(FGR_DEFAULTS)
+    p.update(params or {})
+    return ops.fgr_rigid(src, tgt, seg, **p)
+
+
+def _check_estimator(estimator, fgr, ransac):
+    """The ``estimator=`` / ``fgr=`` / ``**ransac`` keywords of the three entry points, checked before any work."""
+    if estimator not in ('ransac', 'fgr'):
+        raise ValueError("estimator must be 'ransac' or 'fgr', got %r" % (estimator,))
+    if estimator == 'ransac' and fgr is not None:
+        raise ValueError("fgr= is only taken with estimator='fgr'")
+    if estimator == 'fgr' and ransac:
+        raise ValueError("estimator='fgr' takes its parameters in fgr=, not %s" % sorted(ransac))
+    if fgr is not None and not isinstance(fgr, dict):
+        raise ValueError("fgr must be None or a dict of ops.fgr_rigid keywords")
+
+
+def _estimate(estimator, fgr, src, tgt, seg, ransac):
+    """(T, inliers) of the compacted matches by the chosen estimator."""
+    return (_fgr(src, tgt, seg, fgr) if estimator == 'fgr' else _ransac(src, tgt, seg, ransac))[:2]
 
 
 # ------------------------------------------------------------------------------------------------- ICP refinement
@@ -920,7 +1129,7 @@ def _scene_colors(colors, frags, rows):
 
 
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
-                   pose_graph=None, desc_name=ev.DESC_NAME, **ransac):
+                   pose_graph=None, desc_name=ev.DESC_NAME, estimator='ransac', fgr=None, **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
@@ -937,7 +1146,10 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     the log holds ``inv(P_i) P_j`` for every pair it kept -- the pairs it pruned are left out.  The return value is then
     ``(the usual result, poses [num_frag,4,4])``.  Still one read-back per scene.
     ``desc_name``: the descriptor whose dump is read (``cloud_bin_<i>.<desc_name>.npy``): ``'FPFH'`` for the files of
-    ``evaluate.generate_fpfh_features``."""
+    ``evaluate.generate_fpfh_features``.
+    ``estimator``: ``'ransac'`` (the default) or ``'fgr'``: one batched ``ops.fgr_rigid`` call on the same matches, with
+    ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); everything after the pose estimate is the same."""
+    _check_estimator(estimator, fgr, ransac)
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -968,7 +1180,7 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
         sps.append(sp)
         tps.append(tp)
     src, tgt, seg, _ = _compact(torch.stack(muts), torch.stack(sps), torch.stack(tps))
-    T = _ransac(src, tgt, seg, ransac)[0]
+    T = _estimate(estimator, fgr, src, tgt, seg, ransac)[0]
     frags = sorted(cache)
     slot = {f: n for n, f in enumerate(frags)}
     ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]

@@ -2897,6 +2897,101 @@ def ransac_rigid(src, tgt, seg, num_hypotheses=50000, distance_threshold=0.05, e
     return res + (hc, hr) if return_hypotheses else res
 
 
+# fast global registration: the RANSAC-free estimator on the same correspondences (csrc/fgr.hpp has the rule)
+FGR_MAX_PAIRS = _native.D3F_FGR_MAX_PAIRS
+FGR_MAX_ITERS = _native.D3F_FGR_MAX_ITERS
+FGR_MAX_TRIALS = _native.D3F_FGR_MAX_TRIALS
+FGR_ST_FEW, FGR_ST_SINGULAR = _native.D3F_FGR_ST_FEW, _native.D3F_FGR_ST_SINGULAR
+FGR_ST_SEGMENT, FGR_ST_NONFINITE = _native.D3F_FGR_ST_SEGMENT, _native.D3F_FGR_ST_NONFINITE
+
+
+def _fgr_scalars(P, distance_threshold, iterations, division_factor, anneal_every, tuple_scale, tuple_trials,
+                 max_tuples, seed, first_pair):
+    """The checked scalar arguments of d3f_fgr_rigid / d3f_fgr_rigid_host, in the header's order."""
+    if not 1 <= P <= FGR_MAX_PAIRS:
+        raise ValueError("seg must hold 1..%d pairs" % FGR_MAX_PAIRS)
+    if not 1 <= int(iterations) <= FGR_MAX_ITERS:
+        raise ValueError("iterations must be in 1..%d" % FGR_MAX_ITERS)
+    if not (0.0 < float(distance_threshold) < float("inf")):
+        raise ValueError("distance_threshold must be positive and finite")
+    if not (1.0 < float(division_factor) < float("inf")) or int(anneal_every) < 1:
+        raise ValueError("division_factor must be > 1 and anneal_every at least 1")
+    if not (0.0 < float(tuple_scale) <= 1.0):
+        raise ValueError("tuple_scale must be in (0, 1]")
+    trials = -1 if tuple_trials is None else int(tuple_trials)
+    if not -1 <= trials <= FGR_MAX_TRIALS or int(max_tuples) < 0 or int(first_pair) < 0:
+        raise ValueError("tuple_trials must be None or in 0..%d, max_tuples and first_pair non-negative" % FGR_MAX_TRIALS)
+    return (int(first_pair), float(distance_threshold), int(iterations), float(division_factor), int(anneal_every),
+            float(tuple_scale), trials, int(max_tuples), int(seed) & 0xffffffffffffffff)
+
+
+def fgr_rigid(src, tgt, seg, distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4,
+              tuple_scale=0.95, tuple_trials=None, max_tuples=1000, seed=0, first_pair=0, return_debug=False):
+    """Fast global registration of P correspondence sets in one launch (d3f_fgr_rigid; csrc/fgr.hpp has the rule).
+
+    ``src`` / ``tgt`` / ``seg`` as in ``ransac_rigid`` (the segments must not overlap).  Returns device tensors
+    ``(T [P,4,4] f64, inliers [P], tuples [P], weight_sum [P] f64, status [P])``: T maps the TARGET onto the SOURCE and
+    is the identity where ``status`` has FGR_ST_FEW, FGR_ST_SEGMENT or FGR_ST_NONFINITE; ``inliers`` counts ALL
+    correspondences within ``distance_threshold`` under T, the number ``ransac_rigid`` reports.  ``tuple_trials``: None
+    = min(100 count, FGR_MAX_TRIALS) per pair, 0 = no tuple test (then the result does not depend on ``seed``).
+    ``return_debug=True`` appends ``multiplicity [rows] int32`` (0 for rows of no segment) and ``trace [P, iterations,
+    8] f64`` = (mu, weight_sum, omega, v) per iteration, NaN for iterations that did not run."""
+    s, t = _f32(src, "src"), _f32(tgt, "tgt")
+    if s.dim() != 2 or s.shape[1] != 3 or tuple(t.shape) != tuple(s.shape):
+        raise ValueError("src and tgt must be [rows,3] tensors of the same shape")
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 2
+            and seg.shape[1] == 2 and seg.shape[0] >= 1 and seg.is_contiguous()):
+        raise ValueError("seg must be a contiguous device int32 [P,2] tensor")
+    P, rows = int(seg.shape[0]), int(s.shape[0])
+    scalars = _fgr_scalars(P, distance_threshold, iterations, division_factor, anneal_every, tuple_scale, tuple_trials,
+                           max_tuples, seed, first_pair)
+    dev = s.device
+    T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+    inl, tup, st = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    wsum = torch.empty(P, dtype=torch.float64, device=dev)
+    mult = torch.zeros(rows, dtype=torch.int32, device=dev) if return_debug else None
+    trace = torch.full((P, int(iterations), 8), float("nan"), dtype=torch.float64, device=dev) if return_debug else None
+    nbytes = _native.lib().d3f_fgr_rigid_ws_bytes(rows)
+    ws = _ws(nbytes, dev)
+    _native.check(_native.lib().d3f_fgr_rigid(
+        _p(s), _p(t), rows, _p(seg), P, scalars[0], scalars[1], scalars[2], scalars[3], scalars[4], scalars[5],
+        scalars[6], scalars[7], scalars[8], _p(T), _p(inl), _p(tup), _p(wsum), _p(st), _p(mult), _p(trace), _p(ws),
+        nbytes, _stream()), "d3f_fgr_rigid")
+    res = (T, inl, tup, wsum, st)
+    return res + (mult, trace) if return_debug else res
+
+
+def fgr_rigid_host(src, tgt, seg, distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4,
+                   tuple_scale=0.95, tuple_trials=None, max_tuples=1000, seed=0, first_pair=0, return_debug=False):
+    """The host twin of ``fgr_rigid`` (d3f_fgr_rigid_host): the same rule compiled for the CPU, one thread, the same
+    summation order.  ``src`` / ``tgt`` / ``seg`` are host arrays (or CPU tensors); returns CPU tensors.  No GPU
+    call."""
+    s, t, g = _host_array(src), _host_array(tgt), _host_array(seg)
+    if s.dtype != np.float32 or t.dtype != np.float32:
+        raise ValueError("src and tgt must be float32")
+    s, t = np.ascontiguousarray(s), np.ascontiguousarray(t)
+    if s.ndim != 2 or s.shape[1] != 3 or t.shape != s.shape:
+        raise ValueError("src and tgt must be [rows,3] arrays of the same shape")
+    if g.dtype != np.int32 or g.ndim != 2 or g.shape[1] != 2 or g.shape[0] < 1:
+        raise ValueError("seg must be an int32 [P,2] array")
+    g = np.ascontiguousarray(g)
+    P, rows, K = int(g.shape[0]), int(s.shape[0]), int(iterations)
+    scalars = _fgr_scalars(P, distance_threshold, iterations, division_factor, anneal_every, tuple_scale, tuple_trials,
+                           max_tuples, seed, first_pair)
+    T = np.zeros((P, 4, 4), dtype=np.float64)
+    inl, tup, st = (np.zeros(P, dtype=np.int32) for _ in range(3))
+    wsum = np.zeros(P, dtype=np.float64)
+    mult = np.zeros(rows, dtype=np.int32) if return_debug else None
+    trace = np.full((P, K, 8), np.nan, dtype=np.float64) if return_debug else None
+    _native.check(_native.lib().d3f_fgr_rigid_host(
+        s.ctypes.data if rows else None, t.ctypes.data if rows else None, rows, g.ctypes.data, P, scalars[0], scalars[1],
+        scalars[2], scalars[3], scalars[4], scalars[5], scalars[6], scalars[7], scalars[8], T.ctypes.data,
+        inl.ctypes.data, tup.ctypes.data, wsum.ctypes.data, st.ctypes.data,
+        mult.ctypes.data if return_debug else None, trace.ctypes.data if return_debug else None), "d3f_fgr_rigid_host")
+    res = tuple(torch.from_numpy(x) for x in (T, inl, tup, wsum, st))
+    return res + (torch.from_numpy(mult), torch.from_numpy(trace)) if return_debug else res
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # training items from a device-resident split (datasets.ThreeDMatch.ThreeDMatchResident)
 # ---------------------------------------------------------------------------------------------------------------

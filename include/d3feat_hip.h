@@ -763,6 +763,57 @@ int d3f_ransac_sample_host(uint64_t seed, int p, int h, int count, int32_t* out_
 int d3f_rigid_fit_host(const double* src_host, const double* tgt_host, int n, double* out_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fast global registration -- replaces Open3D's registration_fgr_based_on_correspondence (Zhou, Park, Koltun, ECCV
+ * 2016: tuple constraint, graduated non-convexity over a scaled Geman-McClure penalty), the RANSAC-free estimator the
+ * reference's evaluation would hand the same correspondences to; like RANSAC the reference leaves it to Open3D on the
+ * CPU.  Inputs and convention are d3f_ransac_rigid's: src / tgt [rows,3] f32, seg [P,2] int32 ON THE DEVICE =
+ * (offset, count) per pair, T [P,4,4] f64 mapping TARGET onto SOURCE (src ~ R tgt + t).  The segments of different
+ * pairs must not overlap (every row has one multiplicity slot).  The rule is written in full in csrc/fgr.hpp:
+ *   tuple test   trial h of pair p draws 3 indices by the hash of (seed, first_pair + p, h, k) of csrc/rigid.hpp and
+ *                passes when they are distinct, both triangles are non-degenerate and every edge satisfies
+ *                min(la, lb) >= tuple_scale * max(la, lb); the first max_tuples passing trials in order of h (0: all)
+ *                add 1 to the multiplicity m_i of their correspondences.  tuple_trials < 0: min(100 count,
+ *                D3F_FGR_MAX_TRIALS) trials (Open3D's rule); 0: no test, every m_i = 1.
+ *   objective    sum_i m_i rho_mu(|a_i - T b_i|), minimised by `iterations` line-process / Gauss-Newton steps on SE(3)
+ *                about the centroids of the live (m_i > 0) rows, mu annealed from the squared extent of the pair to
+ *                distance_threshold^2: divided by division_factor before every anneal_every-th iteration and clamped
+ *                there.  mu is a squared distance in metres; there is no scene rescaling and no early exit.
+ * One launch of P workgroups, f64 sums in a fixed order, no floating-point atomic, no host synchronisation
+ * (graph-capturable); a pair's outputs are the same bits alone (with first_pair = its index) or in any batch.
+ * Outputs per pair: T; inliers [P] = correspondences (all of them, whatever m_i) within distance_threshold under the
+ * f32 image of T, the count d3f_ransac_rigid reports; tuples [P] = counted triples; weight_sum [P] f64 = sum of the
+ * line-process weights of the last iteration; status [P] (D3F_FGR_ST_* bits; FEW, SEGMENT or NONFINITE: T is the
+ * identity and inliers 0; SINGULAR: the pose of the iterations before stays).  Optional (NULL to skip), for tests:
+ * multiplicity [rows] int32 (rows of no segment are not written) and trace [P, iterations, 8] f64 = (mu, weight_sum,
+ * omega (3), v (3)) per iteration (iterations that did not run are not written).
+ * Workspace: d3f_fgr_rigid_ws_bytes(rows) -- the multiplicities, 4 bytes per row.
+ * Limits: 1 <= P <= D3F_FGR_MAX_PAIRS, 1 <= iterations <= D3F_FGR_MAX_ITERS, anneal_every >= 1, division_factor > 1,
+ * 0 < tuple_scale <= 1, tuple_trials <= D3F_FGR_MAX_TRIALS, max_tuples >= 0, distance_threshold > 0, count <=
+ * D3F_RANSAC_MAX_COUNT (a longer or out-of-range segment sets D3F_FGR_ST_SEGMENT); src / tgt may be NULL when rows = 0.
+ * d3f_fgr_rigid_host: the host twin -- the same rule (csrc/fgr.hpp) on one CPU thread with the same summation order;
+ * every pointer is a host pointer, no workspace, no GPU call.  It differs from the device only where the device's
+ * sin / cos differ from the host's.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_FGR_MAX_PAIRS (1 << 20)
+#define D3F_FGR_MAX_ITERS 1024
+#define D3F_FGR_MAX_TRIALS (1 << 22)
+#define D3F_FGR_ST_FEW 1        /* fewer than 3 correspondences, or fewer than 3 left by the tuple test */
+#define D3F_FGR_ST_SINGULAR 2   /* the 6x6 system lost a pivot: the pair stopped at the pose it had */
+#define D3F_FGR_ST_SEGMENT 4    /* segment outside [0, rows) or longer than D3F_RANSAC_MAX_COUNT */
+#define D3F_FGR_ST_NONFINITE 8  /* a coordinate or a sum is not finite */
+size_t d3f_fgr_rigid_ws_bytes(int rows);
+int d3f_fgr_rigid(const float* src, const float* tgt, int rows, const int32_t* seg, int P, int first_pair,
+                  double distance_threshold, int iterations, double division_factor, int anneal_every,
+                  double tuple_scale, int tuple_trials, int max_tuples, uint64_t seed, double* T, int32_t* inliers,
+                  int32_t* tuples, double* weight_sum, int32_t* status, int32_t* multiplicity, double* trace, void* ws,
+                  size_t ws_bytes, void* stream);
+int d3f_fgr_rigid_host(const float* src_host, const float* tgt_host, int rows, const int32_t* seg_host, int P,
+                       int first_pair, double distance_threshold, int iterations, double division_factor,
+                       int anneal_every, double tuple_scale, int tuple_trials, int max_tuples, uint64_t seed,
+                       double* T_host, int32_t* inliers_host, int32_t* tuples_host, double* weight_sum_host,
+                       int32_t* status_host, int32_t* multiplicity_host, double* trace_host);
+
+/* ------------------------------------------------------------------------------------------------
  * Training items from a device-resident 3DMatch split -- replaces the per-item host work of the reference's
  * ThreeDMatchDataset.__getitem__ (ThreeDMatch.py:93-149: float64 copies, rotation, two noise draws, a choice over the
  * correspondences, cdist) and the upload that follows it.  The split is stored once on the device as `points`
