@@ -180,8 +180,7 @@ __global__ __launch_bounds__(kBlock) void normals_kernel(const NormalArgs A) {
   }
 }
 
-// Q = 2^floor(log2(2^20 / radius)), in double (ilogb is exact)
-double quantum_scale(float radius) { return ldexp(1.0, ilogb(1048576.0 / (double)radius)); }
+using d3f::plane::quantum_scale;
 
 }  // namespace
 

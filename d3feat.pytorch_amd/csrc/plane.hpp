@@ -27,6 +27,9 @@ constexpr int kJacobiSweeps3 = 6;
 constexpr double kPlanePivot = 1e-10;
 constexpr int kPlaneSums = 29;
 
+// Q = 2^floor(log2(2^20 / radius)) of the integer moments, on the host in double (ilogb is exact)
+inline double quantum_scale(float radius) { return ldexp(1.0, ilogb(1048576.0 / (double)radius)); }
+
 // one Jacobi rotation in the (p, q) plane of a symmetric 3x3 (r the third index): app, aqq, apq the 2x2 block, arp, arq
 // the third row's entries, v?p / v?q the two columns of the accumulated eigenvectors
 D3F_HD inline void jacobi3(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,

@@ -136,7 +136,8 @@ def generate_features(model, scenes, save_path, config, neighborhood_limits, dev
             engine.check_status()
 
 
-def generate_fpfh_features(scenes, save_path, radius, normal_radius=None, seed=0, desc_name='FPFH', device='cuda'):
+def generate_fpfh_features(scenes, save_path, radius, normal_radius=None, seed=0, desc_name='FPFH', device='cuda',
+                           detector=None, iss=None):
     """``generate_features`` without a network: FPFH descriptors (``registration.describe_fpfh``: one cell list, one
     normals call and one ``ops.fpfh`` call per scene) in the same layout -- per fragment
     ``descriptors/<scene>/cloud_bin_<i>.<desc_name>.npy`` [N,64] f32 (33 columns scaled to unit rows and zero-padded: the
@@ -145,8 +146,17 @@ def generate_fpfh_features(scenes, save_path, radius, normal_radius=None, seed=0
     ``scores/<scene>/cloud_bin_<i>.npy`` [N,1] f32.  FPFH has no detector: the score is a uniform draw in (0, 1] from
     ``numpy.random.default_rng(seed)`` for a point with a descriptor and 0 for one without, so the top-k selection of
     ``register_one_scene`` / ``registration.register_scene`` (with ``desc_name=``) is a reproducible uniform sample of
-    the described points.  ``device='cpu'`` runs the NumPy restatement."""
+    the described points.  ``device='cpu'`` runs the NumPy restatement.
+
+    ``detector='iss'`` with ``iss=dict(salient_radius=..., non_max_radius=...)`` (further keywords of
+    ``registration.detect_iss``: the gammas, ``min_neighbors``) pairs FPFH with the ISS detector, as the published FPFH
+    baselines do: the score is the ISS saliency for a point that survives the suppression AND has a descriptor, and 0
+    for every other point; ``seed`` is not used.  Anything else than None / ``'iss'`` raises ``ValueError``."""
     from . import registration as reg
+    if detector not in (None, 'iss') or (detector is None) != (iss is None):
+        raise ValueError("detector must be None, or 'iss' with iss=dict(salient_radius=..., non_max_radius=...)")
+    if detector == 'iss' and not (isinstance(iss, dict) and {'salient_radius', 'non_max_radius'} <= set(iss)):
+        raise ValueError("iss must be a dict of detect_iss keywords with at least salient_radius and non_max_radius")
     rng = np.random.default_rng(seed)
     for scene, fragments in scenes.items():
         dpath, kpath, spath = _paths(save_path, scene)
@@ -154,11 +164,20 @@ def generate_fpfh_features(scenes, save_path, radius, normal_radius=None, seed=0
             os.makedirs(p, exist_ok=True)
         frags = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 3) for f in fragments]
         descs, counts = reg.describe_fpfh(frags, radius, normal_radius, device=device)
+        if detector == 'iss':
+            saliency, kept = reg.detect_iss(frags, device=device, **iss)
         for ids, points in enumerate(frags):
             desc, count = descs[ids], counts[ids]
             if isinstance(desc, torch.Tensor):
                 desc, count = desc.cpu().numpy(), count.cpu().numpy()
-            draw = 1.0 - rng.random(points.shape[0])                       # (0, 1]
+            if detector == 'iss':
+                sal, rows = saliency[ids], kept[ids]
+                if isinstance(sal, torch.Tensor):
+                    sal, rows = sal.cpu().numpy(), rows.cpu().numpy()
+                draw = np.zeros(points.shape[0], dtype=np.float32)
+                draw[rows] = sal[rows]
+            else:
+                draw = 1.0 - rng.random(points.shape[0])                   # (0, 1]
             scores = np.where(count > 0, draw, 0.0).astype(np.float32).reshape(-1, 1)
             np.save(os.path.join(dpath, 'cloud_bin_%d.%s' % (ids, desc_name)), desc.astype(np.float32))
             np.save(os.path.join(kpath, 'cloud_bin_%d' % ids), points)
@@ -234,3 +253,48 @@ def evaluate_scenes(save_path, scenes_gt, inlier_ratio_threshold=0.05, distance_
                                              desc_name=desc_name))
     avg = np.mean(np.array(list(out.values()), dtype=np.float64), axis=0)
     return out, {'recall': float(avg[0]), 'inlier_num': float(avg[1]), 'inlier_ratio': float(avg[2])}
+
+
+# ---------------------------------------------------------------------------------------------------- repeatability
+def repeatability_scene(save_path, scene, gtpath, num_points=(4, 8, 16, 32, 64, 128, 256, 512), distance=0.1,
+                        nms_radius=None, device='cuda'):
+    """Keypoint repeatability of one scene from the dumped keypoints and scores of any ``generate_*`` and the scene's
+    ``gt.log`` (``registration.keypoint_repeatability`` has the convention).  For every k of ``num_points`` each
+    fragment's keypoints are its ``select_keypoints`` top-k among the rows with a POSITIVE score -- a zero score is never
+    a keypoint, so a fragment with fewer such rows gives what it has.  ``nms_radius``: the scores first go through
+    ``registration.suppress_non_maxima`` at that radius (a suppressed row's score becomes 0).  One
+    ``keypoint_repeatability`` call per k.  Returns ``({k: relative repeatability}, {k: int64 [num_frag] keypoints per
+    fragment})``."""
+    from . import registration as reg
+    gt = loadlog(gtpath)
+    _, kpath, spath = _paths(save_path, scene)
+    num_frag = len([f for f in os.listdir(kpath) if f.endswith('.npy')])
+    names = ['cloud_bin_%d' % i for i in range(num_frag)]
+    keypts = [np.ascontiguousarray(get_keypts(kpath, n), dtype=np.float32).reshape(-1, 3) for n in names]
+    scores = [np.ascontiguousarray(get_scores(spath, n), dtype=np.float32).reshape(-1) for n in names]
+    if nms_radius is not None:
+        masks = reg.suppress_non_maxima(keypts, scores, nms_radius, device=device)
+        scores = [np.where(m.cpu().numpy() if isinstance(m, torch.Tensor) else m, s, np.float32(0.0))
+                  for m, s in zip(masks, scores)]
+    keys = sorted(gt, key=lambda k: tuple(int(x) for x in k.split('_')))
+    if not keys:
+        raise ValueError("no fragment pair is listed in %s" % os.path.join(gtpath, 'gt.log'))
+    T = np.stack([gt[k] for k in keys])
+    with np.errstate(invalid='ignore'):
+        positive = [np.nonzero(s > 0)[0] for s in scores]
+    rep, counts = {}, {}
+    for k in num_points:
+        sets = [p[rows[select_keypoints(torch.from_numpy(s[rows]), k).numpy()]]
+                for p, s, rows in zip(keypts, scores, positive)]
+        rep[int(k)] = reg.keypoint_repeatability(sets, keys, T, distance=distance, device=device)[4]
+        counts[int(k)] = np.asarray([len(s) for s in sets], dtype=np.int64)
+    return rep, counts
+
+
+def repeatability_scenes(save_path, scenes_gt, num_points=(4, 8, 16, 32, 64, 128, 256, 512), distance=0.1,
+                         nms_radius=None, device='cuda'):
+    """{scene: gt directory} -> ({scene: {k: relative repeatability}}, {k: the mean over the scenes}), averaged over
+    scenes the way ``evaluate_scenes`` averages recall."""
+    out = {scene: repeatability_scene(save_path, scene, gtpath, num_points, distance, nms_radius, device)[0]
+           for scene, gtpath in scenes_gt.items()}
+    return out, {int(k): float(np.mean([r[int(k)] for r in out.values()])) for k in num_points}

@@ -32,7 +32,10 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
   ``pose_graph=dict(max_distance=...)``;
 * ``describe_fpfh`` / ``fpfh_numpy``  FPFH descriptors of fragments (``ops.fpfh``; csrc/fpfh.hpp has the rule) and their
   NumPy restatement: the training-free descriptor and the baseline column of the registration tables --
-  ``evaluate.generate_fpfh_features`` dumps them and ``register_scene(desc_name='FPFH')`` reads them.
+  ``evaluate.generate_fpfh_features`` dumps them and ``register_scene(desc_name='FPFH')`` reads them;
+* ``detect_iss`` / ``suppress_non_maxima`` / ``iss_numpy`` / ``radius_nms_numpy``  ISS keypoints of fragments
+  (``ops.iss_keypoints``; csrc/iss.hpp has the rule), radius non-maximum suppression of any score (``ops.radius_nms``)
+  and their NumPy restatements; ``keypoint_repeatability`` the detector's metric over the pairs of a ``gt.log``.
 
 Every transform maps the TARGET fragment into the SOURCE frame (src ~ R tgt + t), like ``gt.log``.  In ICP's terms the
 target fragment j of a key ``i_j`` is the MOVING cloud and the source fragment i the FIXED one: ``ops.icp_rigid`` takes
@@ -836,6 +839,169 @@ def describe_fpfh(clouds, radius, normal_radius=None, viewpoint=None, device='cu
         nrm = ops.estimate_normals(grid, None, normal_radius, viewpoint=viewpoint)[0]
         desc, cnt = ops.fpfh(grid, None, radius, nrm, row_width=64, unit=True)
     return ([desc[ends[k]:ends[k + 1]] for k in range(len(lens))], [cnt[ends[k]:ends[k + 1]] for k in range(len(lens))])
+
+
+# ------------------------------------------------------------------------- ISS keypoints, suppression, repeatability
+def iss_eigenvalues_numpy(moments, Q):
+    """f64 [n,3] eigenvalues, descending, of the covariance of the integer ``moments`` [n,10] at scale ``Q``
+    (include/d3feat_hip.h) by ``numpy.linalg.eigvalsh``; a row with n < 1 gives zeros."""
+    m = np.asarray(moments, dtype=np.int64).reshape(-1, 10)
+    e = np.zeros((m.shape[0], 3))
+    live = np.nonzero(m[:, 0] >= 1)[0]
+    if live.size:
+        k = m[live, 0].astype(np.float64)
+        sm = m[live, 1:4].astype(np.float64)
+        S = m[live][:, [4, 5, 6, 5, 7, 8, 6, 8, 9]].astype(np.float64).reshape(-1, 3, 3)
+        C = (S - sm[:, :, None] * sm[:, None, :] / k[:, None, None]) / k[:, None, None] / (float(Q) * float(Q))
+        e[live] = np.linalg.eigvalsh(C)[:, ::-1]
+    return e
+
+
+def iss_saliency_numpy(moments, Q, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """Everything after the moments of ``ops.iss_saliency`` in NumPy (csrc/iss.hpp): f32 [n] saliency from the int64
+    ``moments`` [n,10]; the eigenvalues come from ``eigvalsh`` and agree with the kernel's Jacobi solver to rounding."""
+    m = np.asarray(moments, dtype=np.int64).reshape(-1, 10)
+    e = iss_eigenvalues_numpy(m, Q)
+    gate = ((m[:, 0] >= int(min_neighbors)) & (e[:, 0] > 0) & (e[:, 1] < float(gamma_21) * e[:, 0])
+            & (e[:, 2] < float(gamma_32) * e[:, 1]))
+    s = np.where(gate, e[:, 2], 0.0).astype(np.float32)
+    return np.where(s > 0, s, np.float32(0.0)).astype(np.float32)
+
+
+def radius_nms_numpy(clouds, scores, radius, min_neighbors=1, block=1 << 21):
+    """The contract of ``ops.radius_nms`` in NumPy, exactly: ``clouds`` a list of [n,3] f32 arrays, ``scores`` the
+    stacked f32 scores [N] / [N,1] (or one array per cloud).  Returns ``(keep bool [N], count int32 [N])`` over the
+    stacked rows.  Brute force within a window of the rows sorted by x, as ``estimate_normals_numpy``."""
+    r32 = np.float32(radius)
+    if not (0.0 < float(r32) < np.inf) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    score_of = _per_cloud(scores, clouds, 1, "scores")
+    r2 = r32 * r32
+    keeps, counts = [], []
+    for cloud, sc in zip(clouds, score_of):
+        p = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        sc = sc.reshape(-1)
+        n = p.shape[0]
+        order = np.argsort(p[:, 0], kind='stable')
+        ps, ss = p[order], sc[order]
+        keep, cnt = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int32)
+        with np.errstate(invalid='ignore'):
+            walking = np.nonzero(ss > 0)[0]                               # (a NaN is not > 0)
+        reach = float(r32) * 1.001 + 1e-6
+        step = max(1, int(block) // max(n, 1))
+        for s in range(0, walking.size, step):
+            rows = walking[s:s + step]
+            q = ps[rows]
+            lo = np.searchsorted(ps[:, 0], float(q[0, 0]) - reach, 'left')
+            hi = np.searchsorted(ps[:, 0], float(q[-1, 0]) + reach, 'right')
+            t, ts = ps[lo:hi], ss[lo:hi]
+            e = q[:, None, :] - t[None, :, :]                              # the search's p_i - p_j
+            d2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+            inside = d2 < r2
+            with np.errstate(invalid='ignore'):
+                beaten = (inside & (ts[None, :] > ss[rows][:, None])).any(1)
+            cnt[rows] = inside.sum(1)
+            keep[rows] = ~beaten & (cnt[rows] >= int(min_neighbors))
+        back = np.empty(n, dtype=np.int64)
+        back[order] = np.arange(n)
+        keeps.append(keep[back])
+        counts.append(cnt[back])
+    cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dtype=dt)
+    return cat(keeps, bool), cat(counts, np.int32)
+
+
+def iss_numpy(clouds, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """The contract of ``ops.iss_keypoints`` in NumPy: ``(saliency f32 [N], keep bool [N], count_salient int32 [N],
+    count_nms int32 [N])`` over the stacked rows of ``clouds``.  The moments are ``estimate_normals_numpy``'s -- the
+    integers the kernel adds --, the eigenvalues ``numpy.linalg.eigvalsh``'s (they agree with the kernel's Jacobi solver
+    to rounding, so a point whose gate ratio sits within rounding of its threshold may differ), the suppression exact."""
+    for g in (gamma_21, gamma_32):
+        if not (0.0 < float(g) <= 1.0):
+            raise ValueError("gamma_21 and gamma_32 must lie in (0, 1], got %r" % (g,))
+    arrs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds]
+    _, count, moments = estimate_normals_numpy(arrs, salient_radius, min_neighbors=min_neighbors, return_moments=True)
+    saliency = iss_saliency_numpy(moments, normals_scale(salient_radius), gamma_21, gamma_32, min_neighbors)
+    keep, count_nms = radius_nms_numpy(arrs, saliency, non_max_radius, min_neighbors)
+    return saliency, keep, count, count_nms
+
+
+def _split(rows, lens):
+    ends = np.cumsum([0] + list(lens))
+    return [rows[ends[k]:ends[k + 1]] for k in range(len(lens))]
+
+
+def detect_iss(clouds, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, device='cuda'):
+    """ISS keypoints of the fragments of a scene: ONE ``ops.CloudGrid`` at the larger of the two radii over all
+    fragments and one ``ops.iss_keypoints`` call.  ``clouds``: list of [n,3] arrays / tensors.  Returns ``(saliency,
+    rows)``: per fragment the [n] f32 saliency (0: not salient) and the ascending row indices (int64) of the points that
+    survive the suppression; device tensors, or NumPy arrays from ``device='cpu'`` (``iss_numpy``)."""
+    lens = [int(c.shape[0]) for c in clouds]
+    if str(device).startswith('cpu'):
+        saliency, keep = iss_numpy(_host_arrays(clouds), salient_radius, non_max_radius, gamma_21, gamma_32,
+                                   min_neighbors)[:2]
+        return _split(saliency, lens), [np.nonzero(k)[0] for k in _split(keep, lens)]
+    grid = _cloud_grid(clouds, max(float(salient_radius), float(non_max_radius)), torch.device(device))
+    saliency, keep = ops.iss_keypoints(grid, None, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)[:2]
+    return _split(saliency, lens), [torch.nonzero(k).view(-1) for k in _split(keep, lens)]
+
+
+def suppress_non_maxima(clouds, scores, radius, min_neighbors=1, device='cuda'):
+    """Radius non-maximum suppression of ANY per-point score over the fragments of a scene -- what a caller wraps around
+    the learned detector's scores before ``select_keypoints``, whose plain top-k clusters.  ``scores``: one [n] / [n,1]
+    array or tensor per fragment.  One ``ops.CloudGrid`` at ``radius`` and one ``ops.radius_nms`` call; returns the
+    per-fragment keep masks (bool; device tensors, or NumPy arrays from ``device='cpu'``: ``radius_nms_numpy``)."""
+    lens = [int(c.shape[0]) for c in clouds]
+    if len(scores) != len(clouds) or any(int(np.prod(s.shape)) != n for s, n in zip(scores, lens)):
+        raise ValueError("scores must hold one value per point of every fragment")
+    if str(device).startswith('cpu'):
+        flat = [np.asarray(s.detach().cpu().numpy() if isinstance(s, torch.Tensor) else s, dtype=np.float32).reshape(-1)
+                for s in scores]
+        return _split(radius_nms_numpy(_host_arrays(clouds), flat, radius, min_neighbors)[0], lens)
+    dev = torch.device(device)
+    grid = _cloud_grid(clouds, float(radius), dev)
+    flat = [torch.as_tensor(s, dtype=torch.float32).reshape(-1).to(dev) for s in scores]
+    score = torch.cat(flat) if flat else torch.zeros(0, dtype=torch.float32, device=dev)
+    return _split(ops.radius_nms(grid, None, radius, score, min_neighbors)[0], lens)
+
+
+def keypoint_repeatability(keypoints, keys_or_pairs, T, distance=0.1, device='cuda'):
+    """Repeatability of a detector over the fragment pairs of a scene.  ``keypoints``: one [k_i,3] array / tensor per
+    fragment, in the fragment's own frame (k_i may be 0); ``keys_or_pairs``: ``gt.log`` keys ``'i_j'`` or (i, j) tuples;
+    ``T[e]`` the 4x4 ground truth that maps fragment j into fragment i.  For every pair, in BOTH directions, the number
+    of keypoints of one fragment that have a keypoint of the other closer than ``distance`` after the ground-truth
+    motion (strictly, ``ops.nearest_pairs``' rule; j's keypoints are moved by T[e], i's by its inverse).
+
+    Returns ``(hits_ji, n_j, hits_ij, n_i, repeatability)``: int64 arrays over the pairs -- keypoints of j repeated in
+    i, keypoints of j, and the other direction -- and the scene's relative repeatability ``sum hits / sum n`` over both
+    directions.  A fragment without keypoints contributes 0 / 0 and so drops out of the sums; with no keypoint at all
+    the repeatability is NaN.  One ``ops.CloudGrid`` over all keypoint sets and one ``ops.nearest_pairs`` call over the
+    2P directed pairs, of which only the per-pair count is read; ``device='cpu'``: ``preprocess.nearest_pairs_numpy``.
+
+    The evaluation script of the D3Feat paper was not at hand.  The convention taken here: both directions, and ALL
+    keypoints of a fragment in the denominator, not only those that fall into the pair's overlap -- so the number is
+    bounded by the overlap ratio and is comparable between detectors on the same pairs, not with the paper's table."""
+    from ..datasets import preprocess as pp
+    ji = _moving_fixed_pairs(keys_or_pairs, len(keypoints))                # rows (j, i): j moves into i under T
+    P = ji.shape[0]
+    Tji = _pose44(T, P) if P else np.zeros((0, 4, 4))
+    if not (0.0 < float(distance) < np.inf):
+        raise ValueError("distance must be positive and finite")
+    pairs = np.concatenate([ji, ji[:, ::-1]])                              # then i moves into j under T^-1
+    Ts = np.concatenate([Tji, np.linalg.inv(Tji) if P else Tji])
+    lens = np.asarray([int(k.shape[0]) for k in keypoints], dtype=np.int64)
+    if P == 0 or int(lens.sum()) == 0:
+        count = np.zeros(2 * P, dtype=np.int64)
+    elif str(device).startswith('cpu'):
+        count = pp.nearest_pairs_numpy(_host_arrays([k.reshape(-1, 3) for k in keypoints]), pairs, Ts,
+                                       distance)[1].astype(np.int64)
+    else:
+        grid = _cloud_grid(keypoints, float(distance), torch.device(device))
+        count = ops.nearest_pairs(grid, None, pairs, Ts, distance)[1].cpu().numpy().astype(np.int64)
+    hits_ji, hits_ij = count[:P], count[P:]
+    n_j, n_i = lens[ji[:, 0]] if P else lens[:0], lens[ji[:, 1]] if P else lens[:0]
+    total = int(n_j.sum() + n_i.sum())
+    rep = float(hits_ji.sum() + hits_ij.sum()) / total if total else float('nan')
+    return hits_ji, n_j, hits_ij, n_i, rep
 
 
 def _icp_keywords(icp):

@@ -3407,6 +3407,157 @@ def fpfh_host(points, lens, radius, normals, row_width=33, return_spfh=False, un
     return out + (torch.from_numpy(spfh),) if return_spfh else out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# ISS keypoints and radius non-maximum suppression (csrc/iss.hpp has the rule; Open3D's compute_iss_keypoints)
+# ---------------------------------------------------------------------------------------------------------------
+def iss_saliency_bytes(n, neighbors=None):
+    """Algorithmic bytes of the ISS saliency of ``n`` points: ``estimate_normals_bytes`` with a 4-byte saliency written
+    in place of the 12-byte normal."""
+    return estimate_normals_bytes(n, neighbors) - 8 * int(n)
+
+
+def radius_nms_bytes(n, walking=None, neighbors=None):
+    """Algorithmic bytes of the suppression of ``n`` rows of which ``walking`` (default all) have a positive score: every
+    row reads its score (4) and writes keep and count (5); a walking row reads its point (12), the (start, end) headers
+    of 27 buckets (216), and the stored point, cell key and score of every candidate (28 each; ``neighbors`` of them in
+    all, by default the row itself)."""
+    n = int(n)
+    w = n if walking is None else int(walking)
+    return n * (4 + 5) + w * (12 + 27 * 8) + 28 * (w if neighbors is None else int(neighbors))
+
+
+def _iss_checks(radius, min_neighbors, gammas=()):
+    if not (0.0 < float(radius) < float("inf")) or int(min_neighbors) < 1:
+        raise ValueError("radius must be positive and finite, min_neighbors at least 1")
+    for g in gammas:
+        if not (0.0 < float(g) <= 1.0):
+            raise ValueError("gamma_21 and gamma_32 must lie in (0, 1], got %r" % (g,))
+
+
+def _score_rows(score, N, dev):
+    s = _f32(score, "score")
+    if tuple(s.shape) not in ((N,), (N, 1)) or s.device != dev:
+        raise ValueError("score must be [%d] or [%d,1] on the points' device, got %s" % (N, N, tuple(s.shape)))
+    return s
+
+
+def iss_saliency(grid_or_points, lens, radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, return_moments=False):
+    """ISS saliency of every point of the stacked clouds (d3f_iss_saliency): with e1 >= e2 >= e3 the eigenvalues of the
+    covariance of the point's neighbours within ``radius`` IN ITS OWN CLOUD (itself included; the neighbourhood and the
+    integer moments of ``estimate_normals``), a point is salient when it has at least ``min_neighbors`` neighbours,
+    ``e2 < gamma_21 e1`` and ``e3 < gamma_32 e2``; its saliency is e3 (f32, squared length units), 0 when not salient.
+    The defaults are Open3D's.
+
+    ``grid_or_points``, ``lens``, ``radius``: as in ``estimate_normals``.  Returns device tensors ``(saliency [N] f32,
+    count [N] int32)`` in input row order and, with ``return_moments``, ``moments [N,10] int64``.  The result is
+    bit-identical from run to run, for any row order, for a cloud alone or stacked, and for any cell size."""
+    _iss_checks(radius, min_neighbors, (gamma_21, gamma_32))
+    grid = _resolve_grid(grid_or_points, lens, radius, "radius")
+    dev = grid.supports.device
+    N = grid.Ns
+    saliency = torch.empty(N, dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    moments = torch.empty((N, 10), dtype=torch.int64, device=dev) if return_moments else None
+    if N:
+        with _region("iss_saliency[N=%d]" % N, iss_saliency_bytes(N)):
+            _native.check(_native.lib().d3f_iss_saliency(
+                _p(grid.ws), _p(grid.supports), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(radius), float(gamma_21), float(gamma_32), int(min_neighbors), _p(saliency), _p(count),
+                _p(moments), _p(grid.status.word), _stream()), "d3f_iss_saliency")
+    return (saliency, count, moments) if return_moments else (saliency, count)
+
+
+def radius_nms(grid_or_points, lens, radius, score, min_neighbors=1):
+    """Radius non-maximum suppression of any per-point score (d3f_radius_nms): row i is kept when ``score[i] > 0`` (a NaN
+    is not), no neighbour within ``radius`` IN ITS OWN CLOUD has a strictly larger score -- equal scores both survive,
+    so the row order does not matter -- and the neighbourhood, i included, holds at least ``min_neighbors`` points.
+
+    ``grid_or_points``, ``lens``, ``radius``: as in ``estimate_normals``; ``score`` f32 [N] or [N,1] in input row order.
+    Returns device tensors ``(keep [N] bool, count [N] int32)``: ``count`` is the size of the neighbourhood of a row
+    with a positive score and 0 for every other row (those are not searched).  One launch, no read-back."""
+    _iss_checks(radius, min_neighbors)
+    grid = _resolve_grid(grid_or_points, lens, radius, "radius")
+    dev = grid.supports.device
+    N = grid.Ns
+    s = _score_rows(score, N, dev)
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    if N:
+        with _region("radius_nms[N=%d]" % N, radius_nms_bytes(N)):
+            _native.check(_native.lib().d3f_radius_nms(
+                _p(grid.ws), _p(grid.supports), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(radius), _p(s), int(min_neighbors), _p(keep), _p(count), _p(grid.status.word), _stream()),
+                "d3f_radius_nms")
+    return keep.view(torch.bool), count
+
+
+def iss_keypoints(grid_or_points, lens, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975,
+                  min_neighbors=5):
+    """ISS keypoints of the stacked clouds (d3f_iss_keypoints): ``iss_saliency`` at ``salient_radius``, then
+    ``radius_nms`` of that saliency at ``non_max_radius`` with the same ``min_neighbors``, over ONE cell list whose
+    radius covers both.  Returns device tensors ``(saliency [N] f32, keep [N] bool, count_salient [N] int32, count_nms
+    [N] int32)``, bit for bit what the two calls return.  Two launches, no read-back, capturable in a graph."""
+    _iss_checks(salient_radius, min_neighbors, (gamma_21, gamma_32))
+    _iss_checks(non_max_radius, min_neighbors)
+    grid = _resolve_grid(grid_or_points, lens, max(float(salient_radius), float(non_max_radius)), "radius")
+    dev = grid.supports.device
+    N = grid.Ns
+    saliency = torch.empty(N, dtype=torch.float32, device=dev)
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    count_salient = torch.empty(N, dtype=torch.int32, device=dev)
+    count_nms = torch.empty(N, dtype=torch.int32, device=dev)
+    if N:
+        with _region("iss_keypoints[N=%d]" % N, iss_saliency_bytes(N) + radius_nms_bytes(N)):
+            _native.check(_native.lib().d3f_iss_keypoints(
+                _p(grid.ws), _p(grid.supports), N, _p(grid.cloud_start), int(grid.s_len.numel()), grid.radius,
+                float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors),
+                _p(saliency), _p(keep), _p(count_salient), _p(count_nms), _p(grid.status.word), _stream()),
+                "d3f_iss_keypoints")
+    return saliency, keep.view(torch.bool), count_salient, count_nms
+
+
+def iss_saliency_from_moments_host(moments, Q, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """The host twin of everything after the moments of ``iss_saliency`` (d3f_iss_saliency_from_moments_host, the same
+    inline code compiled for the CPU): ``moments`` int64 [n,10] host rows, ``Q`` their scale
+    (``registration.normals_scale(radius)``) -> f32 [n] CPU tensor.  No GPU call."""
+    _iss_checks(1.0, min_neighbors, (gamma_21, gamma_32))
+    m = np.ascontiguousarray(_host_array(moments), dtype=np.int64)
+    if m.ndim != 2 or m.shape[1] != 10 or not float(Q) > 0.0:
+        raise ValueError("moments must be [n,10] and Q positive, got %s and %r" % (m.shape, Q))
+    out = np.zeros(m.shape[0], dtype=np.float32)
+    fn = _native.lib().d3f_iss_saliency_from_moments_host
+    for k in range(m.shape[0]):
+        _native.check(fn(m[k].ctypes.data, float(Q), float(gamma_21), float(gamma_32), int(min_neighbors),
+                         out[k:].ctypes.data), "d3f_iss_saliency_from_moments_host")
+    return torch.from_numpy(out)
+
+
+def radius_nms_host(points, lens, radius, score, min_neighbors=1):
+    """The host twin of ``radius_nms`` (d3f_radius_nms_host): the same rule compiled for the CPU, brute force within
+    each cloud, one thread.  ``points`` [N,3], ``lens`` and ``score`` [N] or [N,1] are host arrays (or CPU tensors);
+    returns CPU tensors ``(keep bool [N], count int32 [N])``.  No GPU call."""
+    _iss_checks(radius, min_neighbors)
+    pts = np.ascontiguousarray(_host_array(points), dtype=np.float32)
+    ln = np.asarray(_host_array(lens), dtype=np.int64).reshape(-1)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be [N,3], got %s" % (pts.shape,))
+    N = int(pts.shape[0])
+    sc = np.ascontiguousarray(_host_array(score), dtype=np.float32)
+    if sc.shape not in ((N,), (N, 1)):
+        raise ValueError("score must be [%d] or [%d,1], got %s" % (N, N, sc.shape))
+    if not 1 <= ln.size <= MAX_CLOUDS or ln.min() < 0 or int(ln.sum()) > N:
+        raise ValueError("lens must be 1..%d non-negative lengths that sum to at most the %d stacked points"
+                         % (MAX_CLOUDS, N))
+    start = np.zeros(ln.size + 1, dtype=np.int32)
+    start[1:] = np.cumsum(ln)
+    keep = np.zeros(N, dtype=np.uint8)
+    count = np.zeros(N, dtype=np.int32)
+    _native.check(_native.lib().d3f_radius_nms_host(
+        pts.ctypes.data, sc.ctypes.data, N, start.ctypes.data, int(ln.size), float(radius), int(min_neighbors),
+        keep.ctypes.data, count.ctypes.data), "d3f_radius_nms_host")
+    return torch.from_numpy(keep.astype(np.bool_)), torch.from_numpy(count)
+
+
 def icp_rigid(grid_or_points, lens, pairs, T_init, max_distance, max_iters=30, rel_fitness=1e-6, rel_rmse=1e-6,
               return_trace=False, rows=None, normals=None, color_field=None, lambda_geometric=0.968):
     """Point-to-point ICP of P cloud pairs, all advancing together on the device (d3f_icp_rigid).

@@ -1097,6 +1097,59 @@ int d3f_fpfh_host(const float* points, const float* normals, int Ns, const int32
                   int row_width, int unit, float* desc, int32_t* count, int32_t* spfh);
 
 /* ------------------------------------------------------------------------------------------------
+ * ISS keypoints (Zhong 2009; Open3D's compute_iss_keypoints) of every point of the stacked clouds of a cell list, and
+ * radius non-maximum suppression of ANY per-point score over the same list: the detector of the training-free chain and
+ * the suppression a caller wraps around the learned detector's scores.  csrc/iss.hpp states the rule beside the code.
+ *
+ * d3f_iss_saliency.  The cell list (grid_ws, grid_radius), points, Ns, cloud_start, B and the neighbourhood at `radius`
+ * (the salient radius) are those of d3f_estimate_normals bit for bit: the points j of the SAME cloud, i itself included,
+ * with d2 < radius * radius (f32 without FMA, f32 product, strict), the same Q and the same ten int64 moments.
+ *   C = (S - s s^T / n) / n / Q^2 in f64, formed as for the normals, and diagonalised by the same fixed number of cyclic
+ *        Jacobi sweeps (csrc/plane.hpp) without eigenvectors; e1 >= e2 >= e3 its sorted diagonal;
+ *   salient: n >= min_neighbors (>= 1), e1 > 0, e2 < gamma_21 e1, e3 < gamma_32 e2 (products in f64, no division;
+ *        0 < gamma <= 1; Open3D's defaults are 0.975, 0.975 and 5);
+ *   saliency = (float)e3 in squared length units when salient and that float is > 0, else 0.0f.
+ * Outputs in input row order: saliency [Ns] f32, count [Ns] int32 (= n), optional (NULL to skip) moments [Ns,10] int64.
+ * Rows beyond cloud_start[B] get zeros.  A point outside the addressable cell grid is in no cell list: zeros, and
+ * D3F_ST_CELL_RANGE in *status.  The moments are integers, so the result does not depend on the order of the rows, on
+ * the clouds stacked beside a cloud or on the cell size, and is bit-identical from run to run.
+ * d3f_iss_saliency_from_moments_host: host-only twin of everything after the moments (the same inline code): m[10], Q,
+ * the gammas and min_neighbors -> *out.
+ *
+ * d3f_radius_nms.  `score` [Ns] f32 in input row order, any values; `radius` (the non-maximum radius) <= grid_radius;
+ * min_neighbors >= 1.  Row i is KEPT when
+ *   score[i] > 0 (a NaN is not),
+ *   no neighbour j (the acceptance above, at `radius`) has score[j] > score[i] -- strictly: equal scores both survive,
+ *        so the result does not depend on the row order (Open3D's IsLocalMaxima); a NaN neighbour beats nobody,
+ *   and the neighbourhood holds at least min_neighbors points, i included.
+ * Outputs: keep [Ns] uint8 (0 / 1) and count [Ns] int32, the size of the neighbourhood.  A row whose score is not > 0,
+ * a row outside the addressable grid (D3F_ST_CELL_RANGE) and the rows beyond cloud_start[B] are not searched: keep 0,
+ * count 0.  Every other row is searched to the end, beaten or not, so count is its whole neighbourhood and both outputs
+ * are a pure function of (points, score, radius, min_neighbors).  No arithmetic beyond the distance test.
+ * d3f_radius_nms_host: the same rule on the host over HOST arrays, brute force within each cloud, one thread (it knows
+ * no cell grid, so no point is out of range).
+ *
+ * d3f_iss_keypoints: d3f_iss_saliency at salient_radius, then d3f_radius_nms of that saliency at non_max_radius with the
+ * same min_neighbors, on one stream over one cell list (grid_radius covers both radii).  Outputs those of the two.
+ * Every entry: one launch per pass on `stream`, no workspace, no host synchronisation, no allocation, no LDS, no
+ * floating-point atomics; capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+int d3f_iss_saliency(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                     float grid_radius, float radius, double gamma_21, double gamma_32, int min_neighbors,
+                     float* saliency, int32_t* count, int64_t* moments, int32_t* status, void* stream);
+int d3f_radius_nms(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                   float grid_radius, float radius, const float* score, int min_neighbors, uint8_t* keep,
+                   int32_t* count, int32_t* status, void* stream);
+int d3f_iss_keypoints(const void* grid_ws, const float* points, int Ns, const int32_t* cloud_start, int B,
+                      float grid_radius, float salient_radius, float non_max_radius, double gamma_21, double gamma_32,
+                      int min_neighbors, float* saliency, uint8_t* keep, int32_t* count_salient, int32_t* count_nms,
+                      int32_t* status, void* stream);
+int d3f_iss_saliency_from_moments_host(const int64_t* m_host, double Q, double gamma_21, double gamma_32,
+                                       int min_neighbors, float* out_host);
+int d3f_radius_nms_host(const float* points, const float* score, int Ns, const int32_t* cloud_start, int B,
+                        float radius, int min_neighbors, uint8_t* keep, int32_t* count);
+
+/* ------------------------------------------------------------------------------------------------
  * Raw moments of the accepted correspondences of cloud pairs under GIVEN poses -- what the 6x6 information matrix of a
  * pair is made of (the benchmark's gt.info, which registration recall is scored under, and the weight of an edge of a
  * pose graph; Open3D's get_information_matrix_from_point_clouds).  The clouds, the cell list (grid_ws, grid_radius),
