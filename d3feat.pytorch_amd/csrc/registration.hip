@@ -15,9 +15,11 @@
 // 2. refine_kernel: one workgroup per pair.  Maximum of the pair's slab slots, re-derivation of the winner from the hash
 //    (nothing per hypothesis is stored), then refine_iters x { inliers under the current (R, t) -> f64 centroids and
 //    cross-covariance over them (per-thread strided partial sums, then a fixed LDS tree: the same order on every run)
-//    -> Horn fit }, then a final recount.  A refit needs >= 3 inliers, else the current transform is kept.
+//    -> Horn fit }, then a final recount.  A refit needs >= 3 inliers, else the current transform is kept.  The loop
+//    is rigid::refine of rigid_refine.hpp, which sc2.hip runs too.
 #include "common.hpp"
 #include "rigid.hpp"
+#include "rigid_refine.hpp"
 
 namespace {
 
@@ -57,12 +59,9 @@ __device__ __forceinline__ bool hypothesis(const float* __restrict__ src, const 
   return true;
 }
 
-__device__ __forceinline__ void to_f32(const double R[9], const double t[3], float rt[12]) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) rt[i] = (float)R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) rt[9 + i] = (float)t[i];
-}
+using d3f::rigid::kRed;
+using d3f::rigid::to_f32;
+static_assert(kThreads == d3f::rigid::kRefineThreads, "the refinement's tree is written for this workgroup");
 
 __global__ __launch_bounds__(kThreads) void score_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
                                                          int rows, const int32_t* __restrict__ seg, int first_pair,
@@ -140,27 +139,6 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const float* __restrict
   }
 }
 
-constexpr int kRed = 16;   // doubles per thread in the refinement's LDS tree
-
-// sums v[0..n) over the workgroup in a fixed tree order; every thread gets the totals
-template <int N>
-__device__ __forceinline__ void block_sum(double (*red)[kRed], double v[N]) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) red[tid][k] = v[k];
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) red[tid][k] += red[tid + s][k];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = red[0][k];
-}
-
 __global__ __launch_bounds__(kThreads) void refine_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
                                                           int rows, const int32_t* __restrict__ seg, int first_pair,
                                                           float tau2, float edge_ratio, uint64_t seed, int refine_iters,
@@ -192,45 +170,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(const float* __restric
     h = (int)~(uint32_t)(best & 0xffffffffull);
     pre = (int)(best >> 32) - 1;
     hypothesis(src, tgt, off, count, d3f::rigid::pair_key(seed, first_pair + p), h, edge_ratio, R, t);
-    for (int it = 0; it <= refine_iters; ++it) {
-      float rt[12];
-      to_f32(R, t, rt);
-      // inlier count and f64 centroid sums over this thread's rows (ascending)
-      double v[kRed];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) v[k] = 0.0;
-      for (int i = tid; i < count; i += kThreads) {
-        const size_t r = 3 * (size_t)(off + i);
-        const float sx = src[r], sy = src[r + 1], sz = src[r + 2], gx = tgt[r], gy = tgt[r + 1], gz = tgt[r + 2];
-        if (d3f::rigid::inlier_f32(rt, gx, gy, gz, sx, sy, sz, tau2)) {
-          v[0] += 1.0;
-          v[1] += sx; v[2] += sy; v[3] += sz;
-          v[4] += gx; v[5] += gy; v[6] += gz;
-        }
-      }
-      block_sum<7>(red, v);
-      const int n_in = (int)v[0];
-      fin = n_in;
-      if (it == refine_iters || n_in < 3) break;
-      const double cs[3] = {v[1] / n_in, v[2] / n_in, v[3] / n_in}, ct[3] = {v[4] / n_in, v[5] / n_in, v[6] / n_in};
-      double S[kRed];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) S[k] = 0.0;
-      for (int i = tid; i < count; i += kThreads) {
-        const size_t r = 3 * (size_t)(off + i);
-        const float sx = src[r], sy = src[r + 1], sz = src[r + 2], gx = tgt[r], gy = tgt[r + 1], gz = tgt[r + 2];
-        if (d3f::rigid::inlier_f32(rt, gx, gy, gz, sx, sy, sz, tau2)) {
-          const double ds[3] = {sx - cs[0], sy - cs[1], sz - cs[2]}, dg[3] = {gx - ct[0], gy - ct[1], gz - ct[2]};
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) S[3 * a + b] += dg[a] * ds[b];
-        }
-      }
-      block_sum<9>(red, S);
-      d3f::rigid::rotation_from_covariance(S, R);
-      d3f::rigid::translation(R, cs, ct, t);
-    }
+    fin = d3f::rigid::refine(src, tgt, off, count, tau2, refine_iters, red, R, t);
   }
   if (tid == 0) {
     double* o = T + 16 * (size_t)p;

@@ -3,7 +3,8 @@
 The reference stops at the feature-match recall (``evaluate.register_one_scene``) and leaves pose estimation to Open3D
 on the CPU.  Here it runs on the device: top-k keypoints by score, mutual nearest neighbours (``ops.mutual_nn``), then
 RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid`` call (two launches) -- or, with
-``estimator='fgr'``, fast global registration of the same matches in one ``ops.fgr_rigid`` call (one launch).
+``estimator='fgr'``, fast global registration of the same matches in one ``ops.fgr_rigid`` call (one launch), or, with
+``estimator='sc2'``, the spatial-compatibility estimator in one ``ops.sc2_rigid`` call (four launches, no sampling).
 
 * ``estimate_transform``             one pair: keypoints / descriptors / scores -> (T, inliers, num_matches);
 * ``estimate_transforms_from_match`` the batched inference path: ``infer.InferStep.match(item, feats, scores,
@@ -11,6 +12,9 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``fgr_numpy`` / ``fgr_multiplicities`` / ``fgr_draw``  the NumPy restatement of ``ops.fgr_rigid`` (csrc/fgr.hpp has
   the rule: tuple test, graduated non-convexity, Gauss-Newton on SE(3)) and of its tuple test and sampler;
   ``FGR_DEFAULTS`` are the parameters ``estimator='fgr'`` starts from;
+* ``sc2_numpy`` / ``sc2_compatibility`` / ``sc2_pack_rows``  the NumPy restatement of ``ops.sc2_rigid`` (csrc/sc2.hpp
+  has the rule: compatibility bits, degree seeds, second-order consensus sets) and of its bit matrix; ``SC2_DEFAULTS``
+  are the parameters ``estimator='sc2'`` starts from;
 * ``loadinfo`` / ``transformation_error`` / ``evaluate_registration``  the benchmark's ``gt.info`` files and its
   registration recall / precision (error p <= 0.2^2 under the 6x6 information matrix, pairs with j - i > 1);
 * ``register_scene``                  every pair listed in ``gt.log`` from the dumped files, estimates written in the
@@ -54,6 +58,9 @@ RANSAC_DEFAULTS = dict(num_hypotheses=50000, distance_threshold=0.05, edge_ratio
 FGR_DEFAULTS = dict(distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4, tuple_scale=0.95,
                     tuple_trials=None, max_tuples=1000, seed=0)
 FGR_ST_FEW, FGR_ST_SINGULAR, FGR_ST_SEGMENT, FGR_ST_NONFINITE = 1, 2, 4, 8                          # ops.FGR_ST_*
+SC2_DEFAULTS = dict(distance_threshold=0.05, compat_threshold=0.1, num_seeds=256, set_size=20, refine_iters=3)
+SC2_ST_FEW, SC2_ST_NO_HYPOTHESIS, SC2_ST_SEGMENT = 1, 2, 4                                          # ops.SC2_ST_*
+SC2_MAX_COUNT = 8192           # ops.SC2_MAX_COUNT
 FGR_MAX_TRIALS = 1 << 22       # ops.FGR_MAX_TRIALS
 RANSAC_MIN_CROSS2 = 1e-12      # csrc/rigid.hpp kMinCross2
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 1, 2, 4, 8, 16      # ops.ICP_ST_*
@@ -98,31 +105,33 @@ def _pair_points(source_keypts, source_desc, source_score, target_keypts, target
 
 
 def estimate_transform(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
-                       num_points=5000, icp=None, estimator='ransac', fgr=None, **ransac):
+                       num_points=5000, icp=None, estimator='ransac', fgr=None, sc2=None, **ransac):
     """One fragment pair (device tensors): top-k keypoints by score, mutual nearest neighbours, RANSAC.  Returns device
     tensors ``(T [4,4] f64, inliers, num_matches)``; T maps the target into the source frame.  ``ransac``: keywords of
     ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS).  ``estimator='fgr'`` hands the same matches to ``ops.fgr_rigid``
     instead, with ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); no ``ransac`` keyword is taken then.
+    ``estimator='sc2'`` hands them to ``ops.sc2_rigid``, with ``sc2`` a dict of its keywords (defaults: SC2_DEFAULTS;
+    ``max_count`` is filled in from ``num_points``).
     ``icp``: None, or a dict of ``refine_transforms`` keywords (at least ``max_distance``): the estimated pose is then
     refined by ICP over ALL points of the two fragments."""
-    _check_estimator(estimator, fgr, ransac)
+    _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
     mutual, sp, tp = _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
                                   num_points)
     src, tgt, seg, n = _compact(mutual.view(1, -1), sp.unsqueeze(0), tp.unsqueeze(0))
-    T, inl = _estimate(estimator, fgr, src, tgt, seg, ransac)
+    T, inl = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, seg, ransac, int(mutual.numel()))
     if icp is not None:
         T = refine_transforms([source_keypts, target_keypts], [(0, 1)], T, device=source_keypts.device,
                               **_icp_keywords(icp))[0]
     return T[0], inl[0], n[0]
 
 
-def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ransac', fgr=None, **ransac):
+def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ransac', fgr=None, sc2=None, **ransac):
     """The batched path: ``row, mutual, sel = InferStep.match(item, feats, scores, num_points=k)`` with ``points`` the
     item's stacked level-0 points [rows,3] and ``seg`` = ``InferStep.segments(item)`` [2P,2] (clouds 2p, 2p+1 are the
     source and target of pair p).  The mutual rows of every pair are compacted on the device and ONE ``ransac_rigid``
-    call estimates all P transforms (``estimator='fgr'``, ``fgr=dict(...)``: one ``fgr_rigid`` call, as in
-    ``estimate_transform``).  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
-    _check_estimator(estimator, fgr, ransac)
+    call estimates all P transforms (``estimator='fgr'``, ``fgr=dict(...)``: one ``fgr_rigid`` call; ``estimator='sc2'``,
+    ``sc2=dict(...)``: one ``sc2_rigid`` call with ``max_count`` = k; as in ``estimate_transform``).  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
+    _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
     P, k =int(row.shape[0]), int(row.shape[1])
     pts = points if points.dtype == torch.float32 else points.float()
     off = seg[:, 0].long()
@@ -134,7 +143,7 @@ def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ran
     tgt_rows = off[1::2].view(P, 1) + torch.gather(sel[1::2].long(), 1, tslot).clamp(min=0)
     m = mutual.bool() & live[0::2]
     src, tgt, sg, n = _compact(m, pts[src_rows.reshape(-1)].view(P, k, 3), pts[tgt_rows.reshape(-1)].view(P, k, 3))
-    T, inl = _estimate(estimator, fgr, src, tgt, sg, ransac)
+    T, inl = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, sg, ransac, k)
     return T, inl, n
 
 
@@ -205,7 +214,12 @@ def fgr_multiplicities(src, tgt, seed, p, tuple_scale=0.95, tuple_trials=None, m
 
 
 def _inliers_f32(T, src, tgt, tau):
-    """rigid::inlier_f32 over [n,3] f32 rows under the f32 image of T.  A f32 fmaf is taken as the f32 rounding of the
+    """The count of ``_inlier_mask_f32``."""
+    return int(_inlier_mask_f32(T, src, tgt, tau).sum())
+
+
+def _inlier_mask_f32(T, src, tgt, tau):
+    """rigid::inlier_f32 over [n,3] f32 rows under the f32 image of T -> [n] bool.  A f32 fmaf is taken as the f32 rounding of the
     f64 ``a * b + c`` (the product is exact in f64): equal to the true fmaf except on double-rounding ties."""
     f32, f64 = np.float32, np.float64
     rt = T[:3].astype(f32)
@@ -217,7 +231,7 @@ def _inliers_f32(T, src, tgt, tau):
         e.append(fma(rt[a, 0], x, fma(rt[a, 1], y, inner)) - src[:, a])
     d2 = (e[2].astype(f64) * e[2].astype(f64)
           + ((e[1].astype(f64) * e[1].astype(f64) + (e[0] * e[0]).astype(f64)).astype(f32)).astype(f64)).astype(f32)
-    return int((d2 < f32(tau) * f32(tau)).sum())
+    return d2 < f32(tau) * f32(tau)
 
 
 def fgr_numpy(src, tgt, seg, distance_threshold=0.05, iterations=128, division_factor=1.4, anneal_every=4,
@@ -310,27 +324,155 @@ def _rodrigues(w):
     return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
 
 
-def _fgr(src, tgt, seg, params):
+# ------------------------------------------------------------------------------------------------- spatial compatibility
+def sc2_compatibility(src, tgt, compat_threshold=0.1):
+    """Rule 1 of csrc/sc2.hpp on one pair's [n,3] f32 correspondences -> C [n,n] bool: only + - * in f64, in the
+    header's order, so the bits are the kernel's."""
+    a, b = np.asarray(src, dtype=np.float32).astype(np.float64), np.asarray(tgt, dtype=np.float32).astype(np.float64)
+
+    def d2(p):
+        d = p[:, None, :] - p[None, :, :]
+        return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    with np.errstate(all='ignore'):
+        A, B = d2(a), d2(b)
+        s = (A + B) - float(compat_threshold) * float(compat_threshold)
+        C = (s < 0.0) | (s * s < 4.0 * (A * B))
+    np.fill_diagonal(C, False)
+    return C
+
+
+def sc2_pack_rows(C, W):
+    """[n,n] bool -> uint64 [n,W]: bit l of word w is column 64 w + l."""
+    n = C.shape[0]
+    wide = np.zeros((n, 64 * W), dtype=bool)
+    wide[:, :n] = C
+    return np.ascontiguousarray(np.packbits(wide, axis=1, bitorder='little')).view('<u8').astype(np.uint64).reshape(n, W)
+
+
+def _kabsch(s, g):
+    """[n,3] f64 source / target -> (R, t) with src ~ R tgt + t (SVD, reflection fix)."""
+    cs, ct = s.mean(0), g.mean(0)
+    U, _, Vt = np.linalg.svd((g - ct).T @ (s - cs))
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T)) or 1.0])
+    R = Vt.T @ D @ U.T
+    return R, cs - R @ ct
+
+
+def sc2_numpy(src, tgt, seg, distance_threshold=0.05, compat_threshold=0.1, num_seeds=256, set_size=20, refine_iters=3,
+              max_count=None, return_debug=False):
+    """The rule of ``ops.sc2_rigid`` (csrc/sc2.hpp) restated in NumPy -- the independent witness of the device code and
+    its host twin: bit-packed rows and ``np.bitwise_count`` for everything integer (equal bit for bit), an SVD fit in
+    place of Horn's quaternions and ``np.mean`` sums for everything f64 (equal to rounding).  ``src`` / ``tgt`` [rows,3]
+    f32 and ``seg`` [P,2] are host arrays.  Returns arrays ``(T [P,4,4], inliers [P], best_seed [P], best_count [P],
+    status [P])`` and, with ``return_debug``, ``(degree [rows], seed_rows [P,S], consensus [P,S,set_size], hyp_count
+    [P,S], hyp_rt [P,S,12] f32, matrix int64 [P,max_count,W])`` as ``ops.sc2_rigid`` does."""
+    src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    tgt = np.ascontiguousarray(tgt, dtype=np.float32).reshape(-1, 3)
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1, 2)
+    P, rows, S, K = seg.shape[0], src.shape[0], int(num_seeds), int(set_size)
+    mc = max(1, min(rows, SC2_MAX_COUNT)) if max_count is None else int(max_count)
+    W = (mc + 63) // 64
+    T = np.tile(np.eye(4), (P, 1, 1))
+    inl, bc, st = (np.zeros(P, dtype=np.int32) for _ in range(3))
+    bs = np.full(P, -1, dtype=np.int32)
+    degree = np.zeros(rows, dtype=np.int32)
+    seed_rows = np.full((P, S), -1, dtype=np.int32)
+    consensus = np.full((P, S, K), -1, dtype=np.int32)
+    hyp_count = np.full((P, S), -1, dtype=np.int32)
+    hyp_rt = np.zeros((P, S, 12), dtype=np.float32)
+    matrix = np.zeros((P, mc, W), dtype=np.uint64)
+    for p, (off, n) in enumerate(seg):
+        if off < 0 or n < 0 or n > mc or off + n > rows:
+            st[p] = SC2_ST_SEGMENT
+            continue
+        if n < 3:
+            st[p] = SC2_ST_FEW
+        a32, b32 = src[off:off + n], tgt[off:off + n]
+        M = sc2_pack_rows(sc2_compatibility(a32, b32, compat_threshold), W)
+        matrix[p, :n] = M
+        deg = np.bitwise_count(M).sum(axis=1).astype(np.int64)
+        degree[off:off + n] = deg
+        order = np.lexsort((np.arange(n), -deg))[:min(S, n)]              # descending degree, ties to the lower row
+        seed_rows[p, :len(order)] = order
+        a64, b64 = a32.astype(np.float64), b32.astype(np.float64)
+        best, best_T = (-1, 0), None
+        for rank, i in enumerate(order):
+            cand = np.nonzero((M[i, np.arange(n) >> 6] >> (np.arange(n) & 63).astype(np.uint64)) & np.uint64(1))[0]
+            s2 = np.bitwise_count(M[i][None, :] & M[cand]).sum(axis=1).astype(np.int64)
+            pick = cand[np.argsort(-s2, kind='stable')][:K - 1]           # descending s_ij, ties to the lower j
+            rows_of_set = np.concatenate([[i], pick])
+            consensus[p, rank, :len(rows_of_set)] = rows_of_set
+            if deg[i] < 2:
+                continue
+            Th = np.eye(4)
+            Th[:3, :3], Th[:3, 3] = _kabsch(a64[rows_of_set], b64[rows_of_set])
+            c = _inliers_f32(Th, a32, b32, distance_threshold)
+            hyp_count[p, rank] = c
+            hyp_rt[p, rank] = np.concatenate([Th[:3, :3].reshape(-1), Th[:3, 3]]).astype(np.float32)
+            if c > best[0]:                                                # first maximum: ties to the lowest rank
+                best, best_T = (c, rank), Th
+        if st[p]:
+            continue
+        if best_T is None:
+            st[p] = SC2_ST_NO_HYPOTHESIS
+            continue
+        bs[p], bc[p] = order[best[1]], best[0]
+        Tc = best_T
+        for it in range(int(refine_iters) + 1):
+            mask = _inlier_mask_f32(Tc, a32, b32, distance_threshold)
+            inl[p] = int(mask.sum())
+            if it == int(refine_iters) or inl[p] < 3:
+                break
+            Tc = np.eye(4)
+            Tc[:3, :3], Tc[:3, 3] = _kabsch(a64[mask], b64[mask])
+        T[p] = Tc
+    res = (T, inl, bs, bc, st)
+    return res + (degree, seed_rows, consensus, hyp_count, hyp_rt, matrix.view(np.int64)) if return_debug else res
+
+
+def _fgr(src, tgt, seg, params, hint):
     p = dict(FGR_DEFAULTS)
     p.update(params or {})
     return ops.fgr_rigid(src, tgt, seg, **p)
 
 
-def _check_estimator(estimator, fgr, ransac):
-    """The ``estimator=`` / ``fgr=`` / ``**ransac`` keywords of the three entry points, checked before any work."""
-    if estimator not in ('ransac', 'fgr'):
-        raise ValueError("estimator must be 'ransac' or 'fgr', got %r" % (estimator,))
-    if estimator == 'ransac' and fgr is not None:
-        raise ValueError("fgr= is only taken with estimator='fgr'")
-    if estimator == 'fgr' and ransac:
-        raise ValueError("estimator='fgr' takes its parameters in fgr=, not %s" % sorted(ransac))
-    if fgr is not None and not isinstance(fgr, dict):
-        raise ValueError("fgr must be None or a dict of ops.fgr_rigid keywords")
+def _sc2(src, tgt, seg, params, hint):
+    p = dict(SC2_DEFAULTS)
+    p.update(params or {})
+    p.setdefault('max_count', hint)
+    return ops.sc2_rigid(src, tgt, seg, **p)
 
 
-def _estimate(estimator, fgr, src, tgt, seg, ransac):
-    """(T, inliers) of the compacted matches by the chosen estimator."""
-    return (_fgr(src, tgt, seg, fgr) if estimator == 'fgr' else _ransac(src, tgt, seg, ransac))[:2]
+def _ransac_entry(src, tgt, seg, params, hint):
+    return _ransac(src, tgt, seg, params)
+
+
+# estimator name -> (the keyword that carries its parameters, None: the entry point's own **keywords; its call).  A call
+# takes (src, tgt, seg, parameters, the longest segment the compaction can produce) and returns (T, inliers, ...).
+_ESTIMATORS = {'ransac': (None, _ransac_entry), 'fgr': ('fgr', _fgr), 'sc2': ('sc2', _sc2)}
+
+
+def _check_estimator(estimator, given, ransac):
+    """The ``estimator=`` / ``fgr=`` / ``sc2=`` / ``**ransac`` keywords of the three entry points, checked before any
+    work.  ``given``: {keyword: value} of the estimators' own dicts."""
+    if estimator not in _ESTIMATORS:
+        raise ValueError("estimator must be one of %s, got %r" % (sorted(_ESTIMATORS), estimator))
+    own = _ESTIMATORS[estimator][0]
+    for name, value in given.items():
+        if value is None:
+            continue
+        if name != own:
+            raise ValueError("%s= is only taken with estimator=%r" % (name, name))
+        if not isinstance(value, dict):
+            raise ValueError("%s must be None or a dict of ops.%s_rigid keywords" % (name, name))
+    if own is not None and ransac:
+        raise ValueError("estimator=%r takes its parameters in %s=, not %s" % (estimator, own, sorted(ransac)))
+
+
+def _estimate(estimator, given, src, tgt, seg, ransac, hint):
+    """(T, inliers) of the compacted matches by the chosen estimator; ``hint``: no segment is longer than this."""
+    own, call = _ESTIMATORS[estimator]
+    return call(src, tgt, seg, ransac if own is None else given[own], hint)[:2]
 
 
 # ------------------------------------------------------------------------------------------------- ICP refinement
@@ -1295,7 +1437,7 @@ def _scene_colors(colors, frags, rows):
 
 
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
-                   pose_graph=None, desc_name=ev.DESC_NAME, estimator='ransac', fgr=None, **ransac):
+                   pose_graph=None, desc_name=ev.DESC_NAME, estimator='ransac', fgr=None, sc2=None, **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
@@ -1314,8 +1456,10 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     ``desc_name``: the descriptor whose dump is read (``cloud_bin_<i>.<desc_name>.npy``): ``'FPFH'`` for the files of
     ``evaluate.generate_fpfh_features``.
     ``estimator``: ``'ransac'`` (the default) or ``'fgr'``: one batched ``ops.fgr_rigid`` call on the same matches, with
-    ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); everything after the pose estimate is the same."""
-    _check_estimator(estimator, fgr, ransac)
+    ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); or ``'sc2'``: one batched ``ops.sc2_rigid`` call, with
+    ``sc2`` a dict of its keywords (defaults: SC2_DEFAULTS, ``max_count`` = ``num_points``); everything after the pose
+    estimate is the same."""
+    _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -1346,7 +1490,7 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
         sps.append(sp)
         tps.append(tp)
     src, tgt, seg, _ = _compact(torch.stack(muts), torch.stack(sps), torch.stack(tps))
-    T = _estimate(estimator, fgr, src, tgt, seg, ransac)[0]
+    T = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, seg, ransac, k)[0]
     frags = sorted(cache)
     slot = {f: n for n, f in enumerate(frags)}
     ij = [tuple(slot[int(x)] for x in key.split('_')) for key in keys]

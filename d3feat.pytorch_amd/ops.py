@@ -2992,6 +2992,126 @@ def fgr_rigid_host(src, tgt, seg, distance_threshold=0.05, iterations=128, divis
     return res + (torch.from_numpy(mult), torch.from_numpy(trace)) if return_debug else res
 
 
+# spatial compatibility of second order: the estimator without sampling (csrc/sc2.hpp has the rule)
+SC2_MAX_COUNT = _native.D3F_SC2_MAX_COUNT
+SC2_MAX_SET = _native.D3F_SC2_MAX_SET
+SC2_MAX_SEEDS = _native.D3F_SC2_MAX_SEEDS
+SC2_ST_FEW, SC2_ST_NO_HYPOTHESIS = _native.D3F_SC2_ST_FEW, _native.D3F_SC2_ST_NO_HYPOTHESIS
+SC2_ST_SEGMENT = _native.D3F_SC2_ST_SEGMENT
+
+
+def _sc2_scalars(P, rows, max_count, distance_threshold, compat_threshold, num_seeds, set_size, refine_iters):
+    """The checked scalar arguments of d3f_sc2_rigid / d3f_sc2_rigid_host, in the header's order."""
+    if not 1 <= P <= 65535:
+        raise ValueError("seg must hold 1..65535 pairs")
+    mc = max(1, min(rows, SC2_MAX_COUNT)) if max_count is None else int(max_count)
+    if not 1 <= mc <= SC2_MAX_COUNT:
+        raise ValueError("max_count must be in 1..%d" % SC2_MAX_COUNT)
+    if not (0.0 < float(distance_threshold) < float("inf")) or not (0.0 < float(compat_threshold) < float("inf")):
+        raise ValueError("distance_threshold and compat_threshold must be positive and finite")
+    if not 1 <= int(num_seeds) <= SC2_MAX_SEEDS:
+        raise ValueError("num_seeds must be in 1..%d" % SC2_MAX_SEEDS)
+    if not 3 <= int(set_size) <= SC2_MAX_SET:
+        raise ValueError("set_size must be in 3..%d" % SC2_MAX_SET)
+    if not 0 <= int(refine_iters) <= RANSAC_MAX_REFINE:
+        raise ValueError("refine_iters must be in 0..%d" % RANSAC_MAX_REFINE)
+    return mc, float(distance_threshold), float(compat_threshold), int(num_seeds), int(set_size), int(refine_iters)
+
+
+def sc2_rigid(src, tgt, seg, distance_threshold=0.05, compat_threshold=0.1, num_seeds=256, set_size=20, refine_iters=3,
+              max_count=None, max_bytes=2 << 30, return_debug=False, _poison_ws=False):
+    """Spatial-compatibility (SC2) pose estimation of P correspondence sets in four launches (d3f_sc2_rigid; csrc/sc2.hpp
+    has the rule): no sampling, no seed.
+
+    ``src`` / ``tgt`` / ``seg`` as in ``ransac_rigid`` (the segments must not overlap).  Returns device tensors ``(T
+    [P,4,4] f64, inliers [P], best_seed [P], best_count [P], status [P])``: T maps the TARGET onto the SOURCE and is the
+    identity where ``status`` is non-zero (SC2_ST_* bits); ``best_seed`` is the winning seed's row inside its pair.
+    ``max_count``: the longest segment the call takes (None: min(rows, SC2_MAX_COUNT)); the bit matrices cost
+    ``max_count * ceil(max_count / 64) * 8`` bytes per pair.  When the workspace of all P pairs exceeds ``max_bytes`` the
+    pairs are processed in slices of ``seg`` (device slices, no read-back) and the outputs concatenated: the same bits as
+    one call.  One pair that alone exceeds ``max_bytes`` raises ``ValueError``.
+    ``return_debug=True`` appends ``degree [rows] int32`` (0 for rows of no segment), ``seed_rows [P,num_seeds]``,
+    ``consensus [P,num_seeds,set_size]``, ``hyp_count [P,num_seeds]``, ``hyp_rt [P,num_seeds,12] f32`` and the bit
+    matrices ``int64 [P, max_count, W]`` -- a view of the workspace (of the slices' workspaces, concatenated, when the
+    call was sliced)."""
+    s, t = _f32(src, "src"), _f32(tgt, "tgt")
+    if s.dim() != 2 or s.shape[1] != 3 or tuple(t.shape) != tuple(s.shape):
+        raise ValueError("src and tgt must be [rows,3] tensors of the same shape")
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 2
+            and seg.shape[1] == 2 and seg.shape[0] >= 1 and seg.is_contiguous()):
+        raise ValueError("seg must be a contiguous device int32 [P,2] tensor")
+    P, rows = int(seg.shape[0]), int(s.shape[0])
+    mc, dt, ct, S, K, iters = _sc2_scalars(P, rows, max_count, distance_threshold, compat_threshold, num_seeds, set_size,
+                                           refine_iters)
+    L = _native.lib()
+    if L.d3f_sc2_rigid_ws_bytes(1, mc, S) > int(max_bytes):
+        raise ValueError("one pair needs %d bytes of workspace at max_count=%d, more than max_bytes=%d"
+                         % (L.d3f_sc2_rigid_ws_bytes(1, mc, S), mc, int(max_bytes)))
+    step = P
+    while L.d3f_sc2_rigid_ws_bytes(step, mc, S) > int(max_bytes):      # the parts are aligned: no closed form
+        step = (step + 1) // 2
+    dev, W = s.device, (mc + 63) // 64
+    T = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+    out = [torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4)]
+    deg = sr = cons = hc = hr = None
+    mats = []
+    if return_debug:
+        deg = torch.zeros(rows, dtype=torch.int32, device=dev)
+        sr = torch.empty((P, S), dtype=torch.int32, device=dev)
+        cons = torch.empty((P, S, K), dtype=torch.int32, device=dev)
+        hc = torch.empty((P, S), dtype=torch.int32, device=dev)
+        hr = torch.empty((P, S, 12), dtype=torch.float32, device=dev)
+    for a in range(0, P, step):
+        b = min(a + step, P)
+        nbytes = L.d3f_sc2_rigid_ws_bytes(b - a, mc, S)
+        ws = _ws(nbytes, dev)
+        if _poison_ws:
+            ws.fill_(0xFF)
+        _native.check(L.d3f_sc2_rigid(
+            _p(s), _p(t), rows, _p(seg[a:b]), b - a, mc, dt, ct, S, K, iters, _p(T[a:b]), _p(out[0][a:b]),
+            _p(out[1][a:b]), _p(out[2][a:b]), _p(out[3][a:b]), _p(deg), _p(sr[a:b]) if return_debug else None,
+            _p(cons[a:b]) if return_debug else None, _p(hc[a:b]) if return_debug else None,
+            _p(hr[a:b]) if return_debug else None, _p(ws), nbytes, _stream()), "d3f_sc2_rigid")
+        if return_debug:
+            mats.append(ws[:8 * (b - a) * mc * W].view(torch.int64).view(b - a, mc, W))
+    res = (T,) + tuple(out)
+    if return_debug:
+        res = res + (deg, sr, cons, hc, hr, mats[0] if len(mats) == 1 else torch.cat(mats))
+    return res
+
+
+def sc2_rigid_host(src, tgt, seg, distance_threshold=0.05, compat_threshold=0.1, num_seeds=256, set_size=20,
+                   refine_iters=3, max_count=None, return_debug=False):
+    """The host twin of ``sc2_rigid`` (d3f_sc2_rigid_host): the same rule compiled for the CPU, one thread.  ``src`` /
+    ``tgt`` / ``seg`` are host arrays (or CPU tensors); returns CPU tensors, with ``return_debug`` the same extra
+    outputs as ``sc2_rigid``.  No GPU call."""
+    s, t, g = _host_array(src), _host_array(tgt), _host_array(seg)
+    if s.dtype != np.float32 or t.dtype != np.float32:
+        raise ValueError("src and tgt must be float32")
+    s, t = np.ascontiguousarray(s), np.ascontiguousarray(t)
+    if s.ndim != 2 or s.shape[1] != 3 or t.shape != s.shape:
+        raise ValueError("src and tgt must be [rows,3] arrays of the same shape")
+    if g.dtype != np.int32 or g.ndim != 2 or g.shape[1] != 2 or g.shape[0] < 1:
+        raise ValueError("seg must be an int32 [P,2] array")
+    g = np.ascontiguousarray(g)
+    P, rows = int(g.shape[0]), int(s.shape[0])
+    mc, dt, ct, S, K, iters = _sc2_scalars(P, rows, max_count, distance_threshold, compat_threshold, num_seeds, set_size,
+                                           refine_iters)
+    T = np.zeros((P, 4, 4), dtype=np.float64)
+    out = [np.zeros(P, dtype=np.int32) for _ in range(4)]
+    dbg = []
+    if return_debug:
+        dbg = [np.zeros(rows, dtype=np.int32), np.zeros((P, S), dtype=np.int32), np.zeros((P, S, K), dtype=np.int32),
+               np.zeros((P, S), dtype=np.int32), np.zeros((P, S, 12), dtype=np.float32),
+               np.zeros((P, mc, (mc + 63) // 64), dtype=np.int64)]
+    ptr = [x.ctypes.data for x in dbg] if return_debug else [None] * 6
+    _native.check(_native.lib().d3f_sc2_rigid_host(
+        s.ctypes.data if rows else None, t.ctypes.data if rows else None, rows, g.ctypes.data, P, mc, dt, ct, S, K, iters,
+        T.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, ptr[0], ptr[1],
+        ptr[2], ptr[3], ptr[4], ptr[5]), "d3f_sc2_rigid_host")
+    return tuple(torch.from_numpy(x) for x in [T] + out + dbg)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # training items from a device-resident split (datasets.ThreeDMatch.ThreeDMatchResident)
 # ---------------------------------------------------------------------------------------------------------------

@@ -814,6 +814,67 @@ int d3f_fgr_rigid_host(const float* src_host, const float* tgt_host, int rows, c
                        int32_t* status_host, int32_t* multiplicity_host, double* trace_host);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spatial-compatibility pose estimation (second order; after SC^2-PCR, Chen et al., CVPR 2022) -- the estimator for
+ * correspondence sets with a few per cent of inliers, without sampling and without a seed.  Inputs and convention are
+ * d3f_ransac_rigid's: src / tgt [rows,3] f32, seg [P,2] int32 ON THE DEVICE = (offset, count) per pair (the segments do
+ * not overlap), T [P,4,4] f64 mapping TARGET onto SOURCE (src ~ R tgt + t).  The rule is written in full in
+ * csrc/sc2.hpp; with a_i / b_i the pair's source / target row i as exact f64 images and n its count:
+ *   compatibility  i != j: A = |a_i - a_j|^2, B = |b_i - b_j|^2 summed as ((dx dx + dy dy) + dz dz), s = (A + B) -
+ *                  compat_threshold^2, C_ij = (s < 0) || (s s < 4 (A B)); C_ii = 0.  No square root, no libm: the bits
+ *                  are the same on device, host and in NumPy.  A non-finite coordinate leaves its row and column empty.
+ *   seeds          degree d_i = popcount(row i); seed rank = rows by descending d_i, ties to the lower i; the first
+ *                  min(num_seeds, n) ranks are seeds; a seed with d_i < 2 gives no hypothesis.
+ *   consensus set  seed i, then the min(set_size - 1, d_i) rows j with C_ij = 1 by descending s_ij = popcount(row_i &
+ *                  row_j), ties to the lower j, in that order.
+ *   hypothesis     the f64 Horn fit (csrc/rigid.hpp) over the set in that order; its f32 image is scored over ALL n
+ *                  rows as d3f_ransac_rigid scores, at (float)distance_threshold squared in f32.
+ *   winner         the largest count, ties to the lowest seed rank; then d3f_ransac_rigid's refinement, refine_iters
+ *                  times (csrc/rigid_refine.hpp), and a final recount.
+ * Differences from the paper: seeds come from the integer degree (the paper: leading eigenvector and non-maximum
+ * suppression); one selection stage and an unweighted fit (the paper: two stages, spectral weights); no sampling
+ * anywhere; the authors' code was not at hand to compare with.
+ * Four launches of static shape, no atomics, no host synchronisation (graph-capturable); a pair's outputs are the same
+ * bits alone or in any batch.
+ * Outputs per pair: T; inliers [P] (final count); best_seed [P] (the winning seed's row inside the pair, -1 if none);
+ * best_count [P] (its count before refinement); status [P] (D3F_SC2_ST_* bits; any bit set: T is the identity and
+ * inliers 0).  Optional (NULL to skip), for tests: degree [rows] int32 (rows of no segment are not written); seed_rows
+ * [P,num_seeds] (the row of each rank, -1 beyond min(num_seeds, n)); consensus [P,num_seeds,set_size] (rows in set
+ * order, -1 padded; written for every seed, also one with d_i < 2); hyp_count [P,num_seeds] (-1 when there is no
+ * hypothesis); hyp_rt [P,num_seeds,12] f32 (R row-major, then t; zeros when there is no hypothesis).
+ * Workspace: d3f_sc2_rigid_ws_bytes(P, max_count, num_seeds), five parts, each aligned to 256 bytes, in this order:
+ *   bit matrix  uint64 [P, max_count, W], W = ceil(max_count / 64): pair p's matrix at word p * max_count * W, row i
+ *               at i * W, bit l of word w = column 64 w + l; rows and bits >= n are 0;
+ *   degrees     int32 [P, max_count];   seed table  int32 [P, num_seeds];
+ *   keys        uint64 [P, num_seeds] = ((count + 1) << 32) | ~rank, 0 without a hypothesis;
+ *   poses       f64 [P, num_seeds, 12] (written where there is a hypothesis).
+ * The workspace need NOT be cleared by the caller: every word a launch reads was written by an earlier launch of the
+ * same call.  The matrix is max_count * W * 8 bytes per pair: 3.2 MB at 5000.
+ * Limits: 1 <= max_count <= D3F_SC2_MAX_COUNT, 3 <= set_size <= D3F_SC2_MAX_SET, 1 <= num_seeds <= D3F_SC2_MAX_SEEDS,
+ * 1 <= P <= 65535, 0 <= refine_iters <= D3F_RANSAC_MAX_REFINE, both thresholds positive and finite; a segment out of
+ * range or with count > max_count sets D3F_SC2_ST_SEGMENT; src / tgt may be NULL when rows = 0.
+ * d3f_sc2_rigid_host: the host twin -- the same rule on one CPU thread, the same summation order in the refinement;
+ * every pointer is a host pointer, no workspace, no GPU call.  In place of the workspace it takes matrix_host, optional
+ * (NULL to skip): uint64 [P, max_count, W], the bit matrices.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_SC2_MAX_COUNT 8192
+#define D3F_SC2_MAX_SET 64
+#define D3F_SC2_MAX_SEEDS 4096
+#define D3F_SC2_ST_FEW 1           /* fewer than 3 correspondences */
+#define D3F_SC2_ST_NO_HYPOTHESIS 2 /* no seed has two compatible correspondences */
+#define D3F_SC2_ST_SEGMENT 4       /* segment outside [0, rows) or longer than max_count */
+size_t d3f_sc2_rigid_ws_bytes(int P, int max_count, int num_seeds);
+int d3f_sc2_rigid(const float* src, const float* tgt, int rows, const int32_t* seg, int P, int max_count,
+                  double distance_threshold, double compat_threshold, int num_seeds, int set_size, int refine_iters,
+                  double* T, int32_t* inliers, int32_t* best_seed, int32_t* best_count, int32_t* status, int32_t* degree,
+                  int32_t* seed_rows, int32_t* consensus, int32_t* hyp_count, float* hyp_rt, void* ws, size_t ws_bytes,
+                  void* stream);
+int d3f_sc2_rigid_host(const float* src_host, const float* tgt_host, int rows, const int32_t* seg_host, int P,
+                       int max_count, double distance_threshold, double compat_threshold, int num_seeds, int set_size,
+                       int refine_iters, double* T_host, int32_t* inliers_host, int32_t* best_seed_host,
+                       int32_t* best_count_host, int32_t* status_host, int32_t* degree_host, int32_t* seed_rows_host,
+                       int32_t* consensus_host, int32_t* hyp_count_host, float* hyp_rt_host, uint64_t* matrix_host);
+
+/* ------------------------------------------------------------------------------------------------
  * Training items from a device-resident 3DMatch split -- replaces the per-item host work of the reference's
  * ThreeDMatchDataset.__getitem__ (ThreeDMatch.py:93-149: float64 copies, rotation, two noise draws, a choice over the
  * correspondences, cdist) and the upload that follows it.  The split is stored once on the device as `points`
