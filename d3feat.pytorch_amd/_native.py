@@ -15,7 +15,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 SOURCES = ["radius_neighbors.hip", "grid_subsample.hip", "kpconv.hip", "kpconv_fused.hip", "kpconv_aggregate.hip", "kpconv_small.hip", "kpconv_deform.hip", "pool.hip", "detection.hip", "loss.hip",
            "reverse_table.hip", "kpconv_dx_gather.hip", "matching.hip", "elementwise.hip", "batchnorm.hip", "linear.hip", "gemm_epilogue.hip", "optimizer.hip", "misc.hip",
            "registration.hip", "nearest_pairs.hip", "icp.hip", "normals.hip", "augment.hip", "posegraph.hip", "tsdf.hip", "tsdf_integrate.hip", "tsdf_extract.hip", "tsdf_mesh.hip", "tsdf_sparse.hip", "odometry.hip", "tsdf_raycast.hip",
-           "tsdf_mesh_sparse.hip", "fpfh.hip", "fgr.hip", "iss.hip", "sc2.hip"]
+           "tsdf_mesh_sparse.hip", "fpfh.hip", "fgr.hip", "iss.hip", "sc2.hip", "knn_match.hip"]
 
 # The binding is READ from the header, once, at import: prototypes, struct layouts and integer #defines are stated there
 # alone.  What the closed type map below cannot take raises; nothing in the header is skipped.

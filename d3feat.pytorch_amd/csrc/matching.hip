@@ -20,34 +20,13 @@
 // the workgroup's 128 rows meet in an LDS table of (distance bits << 32 | row) keys over its column chunk (ds_min_u64),
 // and after the sweep every column of the chunk costs one global 64-bit atomicMin.  The dot product of a (row, column)
 // pair is the same bit pattern whichever side asks for it, so both arg-mins see identical distances.
-#include "common.hpp"
+#include "knn_match.hpp"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kColsPerTile = 64;
-
-__device__ __forceinline__ uint32_t ord_bits(float f) {  // monotone float -> uint32
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// The correctly rounded square root of v = 2 - 2a, the reference's np.sqrt.  __fsqrt_rn is NOT that: the HIP headers map
-// it to the native v_sqrt_f32 (1 ulp), which tells apart products that np.sqrt rounds to ONE distance -- the later,
-// larger product then wins where np.argmin keeps the earlier index.  v_sqrt_f32 is within 1 ulp, so the residuals of its
-// two neighbours decide: the compiler's own expansion of sqrtf, without the denormal scaling and class checks (v is 0
-// or at least 2^-23; +inf, the "no candidate yet" value, comes back as +inf).  sqrtf itself costs 0.497 against 0.470 ms
-// at 19k x 19k x 32 with everything else equal: the root sits on the column side's dependent chain of every 16 columns.
-__device__ __forceinline__ float sqrt_rn(float v) {
-  float s = __builtin_amdgcn_sqrtf(v);
-  const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
-  const float rd = fmaf(-sd, s, v), ru = fmaf(-su, s, v);
-  s = rd <= 0.0f ? sd : s;
-  return ru > 0.0f ? su : s;
-}
-// the reference's distance; a negative v (its NaN) ranks below every distance
-__device__ __forceinline__ float dist_of(float v) { return v < 0.0f ? -INFINITY : sqrt_rn(v); }
+using namespace d3f::match;   // kColsPerTile, ord_bits, sqrt_rn, dist_of, chunking: shared with knn_match.hip
 
 __global__ void fill_u64_kernel(unsigned long long* __restrict__ p, int n, unsigned long long v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -282,20 +261,6 @@ __global__ void unpack_mutual_kernel(const unsigned long long* __restrict__ best
     row_arg[i] = j;
     if (mutual) mutual[i] = (j >= 0 && j < Nt && (int32_t)(best_col[j] & 0xffffffffull) == i) ? 1 : 0;
   }
-}
-
-// workgroups along the target range: ~2048 in all (8 per CU), column chunks of whole tiles that fit the LDS table
-static void chunking(int gx, int Nt, int& chunks, int& cpc) {
-  const int target = d3f::tunables().match_wgs > 0 ? d3f::tunables().match_wgs : 2048;
-  chunks = target / (gx > 0 ? gx : 1);
-  const int max_chunks = d3f::cdiv(Nt, 4 * kColsPerTile);
-  if (chunks > max_chunks) chunks = max_chunks;
-  const int min_chunks = d3f::cdiv(Nt, 4096);   // 32 KB of keys per workgroup at most
-  if (chunks < min_chunks) chunks = min_chunks;
-  if (chunks < 1) chunks = 1;
-  cpc = d3f::cdiv(Nt, chunks);
-  cpc = d3f::cdiv(cpc, kColsPerTile) * kColsPerTile;
-  chunks = d3f::cdiv(Nt, cpc);
 }
 
 template <int C>

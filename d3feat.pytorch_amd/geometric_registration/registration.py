@@ -15,6 +15,10 @@ RANSAC over the mutual matches of ALL pairs of a scene in one ``ops.ransac_rigid
 * ``sc2_numpy`` / ``sc2_compatibility`` / ``sc2_pack_rows``  the NumPy restatement of ``ops.sc2_rigid`` (csrc/sc2.hpp
   has the rule: compatibility bits, degree seeds, second-order consensus sets) and of its bit matrix; ``SC2_DEFAULTS``
   are the parameters ``estimator='sc2'`` starts from;
+* ``knn_match_numpy``  the NumPy restatement of ``ops.knn_match`` (csrc/knn_match.hpp has the rule: the k nearest
+  target descriptors by rounded f32 distance, then index); ``matches=dict(k=K)`` / ``matches=dict(ratio=r)`` on
+  ``estimate_transform`` / ``register_scene`` hand the estimator every keypoint's K nearest neighbours, or its nearest
+  one where Lowe's ratio test holds, instead of the mutual ones;
 * ``loadinfo`` / ``transformation_error`` / ``evaluate_registration``  the benchmark's ``gt.info`` files and its
   registration recall / precision (error p <= 0.2^2 under the 6x6 information matrix, pairs with j - i > 1);
 * ``register_scene``                  every pair listed in ``gt.log`` from the dumped files, estimates written in the
@@ -61,6 +65,8 @@ FGR_ST_FEW, FGR_ST_SINGULAR, FGR_ST_SEGMENT, FGR_ST_NONFINITE = 1, 2, 4, 8      
 SC2_DEFAULTS = dict(distance_threshold=0.05, compat_threshold=0.1, num_seeds=256, set_size=20, refine_iters=3)
 SC2_ST_FEW, SC2_ST_NO_HYPOTHESIS, SC2_ST_SEGMENT = 1, 2, 4                                          # ops.SC2_ST_*
 SC2_MAX_COUNT = 8192           # ops.SC2_MAX_COUNT
+RANSAC_MAX_COUNT = 65536       # ops.RANSAC_MAX_COUNT
+KNN_MAX = 8                    # ops.KNN_MAX
 FGR_MAX_TRIALS = 1 << 22       # ops.FGR_MAX_TRIALS
 RANSAC_MIN_CROSS2 = 1e-12      # csrc/rigid.hpp kMinCross2
 ICP_ST_FEW, ICP_ST_CELL_RANGE, ICP_ST_PAIR, ICP_ST_NONFINITE, ICP_ST_SINGULAR = 1, 2, 4, 8, 16      # ops.ICP_ST_*
@@ -94,29 +100,109 @@ def _ransac(src, tgt, seg, params):
     return ops.ransac_rigid(src, tgt, seg, **p)
 
 
-def _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score, num_points):
-    """[k] mutual flags and the [k,3] source keypoints with their matched target keypoints (match_pair's selection)."""
+def knn_match_numpy(S, T, k, block=1024):
+    """The rule of ``ops.knn_match`` (csrc/knn_match.hpp) in NumPy: (idx int32 [Ns,k], dist f32 [Ns,k]), ascending
+    (float32 distance, column) with NaN distances first; slots beyond Nt hold -1 / +inf.  Never holds more than ``block``
+    rows of the matrix.  The products are the float32 images of the float64 ones: THE products where they are exact
+    (tests/knn_cases.py), else within a rounding of the kernel's."""
+    S, T, k = np.ascontiguousarray(S, np.float32), np.ascontiguousarray(T, np.float32), int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError("k must be in 1..%d" % KNN_MAX)
+    idx = np.full((len(S), k), -1, np.int32)
+    dist = np.full((len(S), k), np.inf, np.float32)
+    m, T64 = min(k, len(T)), T.astype(np.float64).T
+    for b in range(0, len(S), int(block)):
+        a = (S[b:b + block].astype(np.float64) @ T64).astype(np.float32)
+        with np.errstate(invalid='ignore'):
+            d = np.sqrt(np.float32(2) - np.float32(2) * a)
+        key = np.where(np.isnan(d), -np.inf, d)
+        order = np.argsort(key, axis=1, kind='stable')[:, :m]
+        idx[b:b + block, :m] = order
+        dist[b:b + block, :m] = np.take_along_axis(d, order, 1)
+    return idx, dist
+
+
+def _check_matches(matches, estimator, num_points):
+    """The ``matches=`` keyword, checked before any work: None for the mutual rule (``None`` / ``'mutual'``), else
+    ``(K, ratio, mutual)`` -- ``dict(k=K)``: ratio None; ``dict(ratio=r)``: K = 1; ``dict(k=K, mutual=True)``: the K
+    nearest, mutual ones only."""
+    if matches is None or matches == 'mutual':
+        return None
+    if not isinstance(matches, dict) or not matches:
+        raise ValueError("matches must be None, 'mutual', dict(k=K), dict(k=K, mutual=True) or dict(ratio=r), got %r"
+                         % (matches,))
+    unknown = sorted(set(matches) - {'k', 'ratio', 'mutual'})
+    if unknown:
+        raise ValueError("matches takes the keys 'k', 'ratio' and 'mutual', not %s" % unknown)
+    K, ratio, mutual = matches.get('k', 1), matches.get('ratio'), matches.get('mutual', False)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= KNN_MAX:
+        raise ValueError("matches: k must be an integer in 1..%d, got %r" % (KNN_MAX, K))
+    if not isinstance(mutual, bool):
+        raise ValueError("matches: mutual must be True or False, got %r" % (mutual,))
+    if ratio is not None:
+        if K > 1:
+            raise ValueError("matches takes k > 1 or ratio, not both")
+        if mutual:
+            raise ValueError("matches: mutual is taken with k, not with ratio")
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.floating)) or not 0.0 < ratio <= 1.0:
+            raise ValueError("matches: ratio must be in (0, 1], got %r" % (ratio,))
+        ratio = float(ratio)
+    limit = _MATCH_LIMITS[estimator]
+    if limit is not None and int(num_points) * int(K) > limit:
+        raise ValueError("num_points * k = %d * %d = %d correspondences per pair, estimator=%r takes %d at most"
+                         % (int(num_points), K, int(num_points) * int(K), estimator, limit))
+    return int(K), ratio, mutual
+
+
+def _knn_flags(idx, dist, ratio):
+    """The kept slots of a ``knn_match`` result, flat in slot order i K + s: every filled slot, or (``ratio``, from a
+    k = 2 result) the nearest neighbour of the rows that pass Lowe's test in f32 -- false on NaN and without a second."""
+    if ratio is None:
+        return (idx >= 0).reshape(-1), idx.reshape(-1)
+    r = torch.tensor(ratio, dtype=torch.float32, device=dist.device)
+    return (idx[:, 1] >= 0) & (dist[:, 0] < r * dist[:, 1]), idx[:, 0]
+
+
+def _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score, num_points,
+                 matches=None):
+    """[k] mutual flags and the [k,3] source keypoints with their matched target keypoints (match_pair's selection).
+    ``matches`` = (K, ratio, mutual) of ``_check_matches``: [k K] flags and points, correspondence (i, s) at slot
+    i K + s."""
     si = select_keypoints(source_score.reshape(-1), num_points)
     ti = select_keypoints(target_score.reshape(-1), num_points)
     sd = torch.nan_to_num(source_desc[si]).contiguous()
     td = torch.nan_to_num(target_desc[ti]).contiguous()
+    if matches is not None:
+        K, ratio, mutual = matches
+        idx, dist = ops.knn_match(sd, td, 2 if ratio is not None else K)
+        keep, col = _knn_flags(idx, dist, ratio)
+        if mutual:                           # slot (i, s) stays when source i is the nearest of its s-th target
+            back = ops.mutual_nn(sd, td)[1][col.clamp(min=0).long()]
+            keep = keep & (back == torch.arange(int(sd.shape[0]), device=back.device).repeat_interleave(K))
+        return keep, source_keypts[si].repeat_interleave(K, dim=0), target_keypts[ti][col.clamp(min=0).long()]
     row, _, mutual = ops.mutual_nn(sd, td)
     return mutual, source_keypts[si], target_keypts[ti][row.long()]
 
 
 def estimate_transform(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
-                       num_points=5000, icp=None, estimator='ransac', fgr=None, sc2=None, **ransac):
+                       num_points=5000, icp=None, estimator='ransac', fgr=None, sc2=None, matches=None, **ransac):
     """One fragment pair (device tensors): top-k keypoints by score, mutual nearest neighbours, RANSAC.  Returns device
     tensors ``(T [4,4] f64, inliers, num_matches)``; T maps the target into the source frame.  ``ransac``: keywords of
     ``ops.ransac_rigid`` (defaults: RANSAC_DEFAULTS).  ``estimator='fgr'`` hands the same matches to ``ops.fgr_rigid``
     instead, with ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); no ``ransac`` keyword is taken then.
     ``estimator='sc2'`` hands them to ``ops.sc2_rigid``, with ``sc2`` a dict of its keywords (defaults: SC2_DEFAULTS;
     ``max_count`` is filled in from ``num_points``).
+    ``matches``: None (or ``'mutual'``): the mutual nearest neighbours; ``dict(k=K)``, 1 <= K <= 8: every selected source
+    keypoint with each of its K nearest target keypoints (``ops.knn_match``), K = 1 the plain nearest neighbour;
+    ``dict(ratio=r)``, 0 < r <= 1: its nearest neighbour where Lowe's test ``dist_1 < r dist_2`` holds;
+    ``dict(k=K, mutual=True)``: of the K nearest only those whose own nearest source keypoint it is (one more
+    ``ops.mutual_nn`` call).  ``num_points * K`` beyond what the estimator takes raises ``ValueError``.
     ``icp``: None, or a dict of ``refine_transforms`` keywords (at least ``max_distance``): the estimated pose is then
     refined by ICP over ALL points of the two fragments."""
     _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
+    matches = _check_matches(matches, estimator, num_points)
     mutual, sp, tp = _pair_points(source_keypts, source_desc, source_score, target_keypts, target_desc, target_score,
-                                  num_points)
+                                  num_points, matches)
     src, tgt, seg, n = _compact(mutual.view(1, -1), sp.unsqueeze(0), tp.unsqueeze(0))
     T, inl = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, seg, ransac, int(mutual.numel()))
     if icp is not None:
@@ -130,8 +216,15 @@ def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ran
     item's stacked level-0 points [rows,3] and ``seg`` = ``InferStep.segments(item)`` [2P,2] (clouds 2p, 2p+1 are the
     source and target of pair p).  The mutual rows of every pair are compacted on the device and ONE ``ransac_rigid``
     call estimates all P transforms (``estimator='fgr'``, ``fgr=dict(...)``: one ``fgr_rigid`` call; ``estimator='sc2'``,
-    ``sc2=dict(...)``: one ``sc2_rigid`` call with ``max_count`` = k; as in ``estimate_transform``).  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``."""
+    ``sc2=dict(...)``: one ``sc2_rigid`` call with ``max_count`` = k; as in ``estimate_transform``).  Returns device tensors ``(T [P,4,4] f64, inliers [P], num_matches [P])``.
+    ``row`` / ``mutual`` may also be [P,k,K]: K candidate targets per source keypoint and the flags of the ones to keep
+    (``idx, dist, sel = InferStep.match_knn(...)``, ``mutual`` = ``idx >= 0`` or any filter of one's own); correspondence
+    (i, s) of a pair then sits at slot i K + s and the estimator is told ``max_count`` = k K."""
     _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
+    if row.dim() == 3:
+        if tuple(mutual.shape) != tuple(row.shape):
+            raise ValueError("row and mutual must have one shape, got %s and %s" % (tuple(row.shape), tuple(mutual.shape)))
+        return _transforms_from_knn(points, seg, row, mutual, sel, estimator, fgr, sc2, ransac)
     P, k =int(row.shape[0]), int(row.shape[1])
     pts = points if points.dtype == torch.float32 else points.float()
     off = seg[:, 0].long()
@@ -144,6 +237,28 @@ def estimate_transforms_from_match(points, seg, row, mutual, sel, estimator='ran
     m = mutual.bool() & live[0::2]
     src, tgt, sg, n = _compact(m, pts[src_rows.reshape(-1)].view(P, k, 3), pts[tgt_rows.reshape(-1)].view(P, k, 3))
     T, inl = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, sg, ransac, k)
+    return T, inl, n
+
+
+def _transforms_from_knn(points, seg, idx, keep, sel, estimator, fgr, sc2, ransac):
+    """``estimate_transforms_from_match`` on [P,k,K] tables."""
+    P, k, K = (int(n) for n in idx.shape)
+    limit = _MATCH_LIMITS[estimator]
+    if limit is not None and k * K > limit:
+        raise ValueError("num_points * k = %d * %d = %d correspondences per pair, estimator=%r takes %d at most"
+                         % (k, K, k * K, estimator, limit))
+    pts = points if points.dtype == torch.float32 else points.float()
+    off = seg[:, 0].long()
+    live = (sel >= 0)
+    n_live = live.sum(dim=1)
+    src_rows = off[0::2].view(P, 1) + sel[0::2].clamp(min=0).long()                          # [P,k]
+    tslot = ((k - n_live[1::2]).view(P, 1, 1) + idx.long().clamp(min=0)).clamp(max=k - 1)    # [P,k,K]
+    tsel = torch.gather(sel[1::2].long(), 1, tslot.view(P, k * K)).clamp(min=0)
+    tgt_rows = off[1::2].view(P, 1) + tsel                                                   # [P,k K]
+    m = (keep.bool() & (idx >= 0) & live[0::2].view(P, k, 1)).view(P, k * K)
+    sp = pts[src_rows.reshape(-1)].view(P, k, 1, 3).expand(P, k, K, 3).reshape(P, k * K, 3)
+    src, tgt, sg, n = _compact(m, sp, pts[tgt_rows.reshape(-1)].view(P, k * K, 3))
+    T, inl = _estimate(estimator, dict(fgr=fgr, sc2=sc2), src, tgt, sg, ransac, k * K)
     return T, inl, n
 
 
@@ -450,6 +565,8 @@ def _ransac_entry(src, tgt, seg, params, hint):
 # estimator name -> (the keyword that carries its parameters, None: the entry point's own **keywords; its call).  A call
 # takes (src, tgt, seg, parameters, the longest segment the compaction can produce) and returns (T, inliers, ...).
 _ESTIMATORS = {'ransac': (None, _ransac_entry), 'fgr': ('fgr', _fgr), 'sc2': ('sc2', _sc2)}
+# estimator name -> the longest correspondence set it takes (None: as long as the buffers are)
+_MATCH_LIMITS = {'ransac': RANSAC_MAX_COUNT, 'fgr': None, 'sc2': SC2_MAX_COUNT}
 
 
 def _check_estimator(estimator, given, ransac):
@@ -1437,7 +1554,8 @@ def _scene_colors(colors, frags, rows):
 
 
 def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num_frag=None, out_log=None, icp=None,
-                   pose_graph=None, desc_name=ev.DESC_NAME, estimator='ransac', fgr=None, sc2=None, **ransac):
+                   pose_graph=None, desc_name=ev.DESC_NAME, estimator='ransac', fgr=None, sc2=None, matches=None,
+                   **ransac):
     """Estimates the transform of every pair listed in ``<gtpath>/gt.log`` from the dumped keypoints / descriptors /
     scores (``evaluate``'s layout) with ONE batched ``ransac_rigid`` call, writes them with ``evaluate.writelog`` to
     ``out_log`` (a directory; default ``<save_path>/registration/<scene>``) and returns
@@ -1458,8 +1576,11 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     ``estimator``: ``'ransac'`` (the default) or ``'fgr'``: one batched ``ops.fgr_rigid`` call on the same matches, with
     ``fgr`` a dict of its keywords (defaults: FGR_DEFAULTS); or ``'sc2'``: one batched ``ops.sc2_rigid`` call, with
     ``sc2`` a dict of its keywords (defaults: SC2_DEFAULTS, ``max_count`` = ``num_points``); everything after the pose
-    estimate is the same."""
+    estimate is the same.
+    ``matches``: as in ``estimate_transform``: ``dict(k=K)`` / ``dict(ratio=r)`` replace the mutual rule by the K nearest
+    neighbours / the ratio test (``ops.knn_match``), with K ``num_points`` slots per pair."""
     _check_estimator(estimator, dict(fgr=fgr, sc2=sc2), ransac)
+    matches = _check_matches(matches, estimator, num_points)
     gt = ev.loadlog(gtpath)
     dpath, kpath, spath = ev._paths(save_path, scene)
     if num_frag is None:
@@ -1476,11 +1597,11 @@ def register_scene(save_path, scene, gtpath, num_points=5000, device='cuda', num
     keys = sorted(gt, key=lambda k: tuple(int(x) for x in k.split('_')))
     if not keys:
         raise ValueError("no fragment pair is listed in %s" % os.path.join(gtpath, 'gt.log'))
-    k = int(num_points)
+    k = int(num_points) * (matches[0] if matches is not None else 1)     # slots per pair
     muts, sps, tps = [], [], []
     for key in keys:
         i, j = (int(x) for x in key.split('_'))
-        mutual, sp, tp = _pair_points(*load(i), *load(j), k)
+        mutual, sp, tp = _pair_points(*load(i), *load(j), int(num_points), matches)
         pad = k - int(mutual.shape[0])          # fragments with fewer than k points: pad with non-mutual rows
         if pad:
             mutual = torch.cat([mutual, mutual.new_zeros(pad)])

@@ -115,3 +115,22 @@ class InferStep(TrainStep):
         row, col, mutual = ops.mutual_nn_batched(desc, desc, pair, k, k)
         return row.view(2 * P, k)[0::2], mutual.view(2 * P, k)[0::2], sel
 
+    def match_knn(self, item, feats, scores, num_points, k):
+        """The ``k`` nearest target keypoints of every source keypoint of every pair (``ops.knn_match_batched``; the
+        rule is csrc/knn_match.hpp's) on the ``num_points`` top-scoring keypoints of each cloud.  Returns (idx, dist,
+        sel): [P, num_points, k] tables over the selected source rows -- pair-local target slots as in ``match``, -1 /
+        +inf where a cloud has fewer keypoints or targets -- plus the selection itself.
+        ``registration.estimate_transforms_from_match(points, seg, idx, idx >= 0, sel)`` takes them."""
+        from . import ops
+        seg = self.segments(item)
+        P = seg.shape[0] // 2
+        kp = int(num_points)
+        sel = ops.topk_scores(scores, seg, kp)                                      # [2P, kp] cloud-local, -1 padded
+        rows = (sel.clamp(min=0) + seg[:, :1]).long().reshape(-1)
+        desc = feats.index_select(0, rows)                                           # [2P*kp, C]
+        n_live = (sel >= 0).sum(dim=1).to(torch.int32)
+        base = torch.arange(2 * P, device=self.device, dtype=torch.int32) * kp + (kp - n_live)  # live ones are the tail
+        pair = torch.stack([base[0::2], n_live[0::2], base[1::2], n_live[1::2]], dim=1).contiguous()
+        idx, dist = ops.knn_match_batched(desc, desc, pair, kp, kp, k)
+        return idx.view(2 * P, kp, -1)[0::2], dist.view(2 * P, kp, -1)[0::2], sel
+

@@ -2831,6 +2831,48 @@ def mutual_nn_batched(source_desc, target_desc, seg, max_src, max_tgt):
     return ra, ca, mu
 
 
+KNN_MAX = _native.D3F_KNN_MAX
+
+
+def _knn_k(k):
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError("k must be in 1..%d" % KNN_MAX)
+    return int(k)
+
+
+def knn_match(source_desc, target_desc, k):
+    """(idx int32 [Ns,k], dist f32 [Ns,k]): the k nearest target descriptors of every source descriptor by the rule of
+    csrc/knn_match.hpp -- ascending (float32 distance sqrt(2 - 2 S T^T), target index), a NaN distance first like
+    ``np.argmin``; slots beyond Nt hold -1 / +inf.  ``idx[:, 0]`` is ``mutual_nn``'s row arg-min."""
+    s, t = _f32(source_desc, "source_desc"), _f32(target_desc, "target_desc")
+    Ns, Nt, C, k = int(s.shape[0]), int(t.shape[0]), int(s.shape[1]), _knn_k(k)
+    idx = torch.empty((Ns, k), dtype=torch.int32, device=s.device)
+    dist = torch.empty((Ns, k), dtype=torch.float32, device=s.device)
+    nbytes = _native.lib().d3f_knn_match_ws_bytes(Ns, Nt, k)
+    ws = _ws(nbytes, s.device)
+    _native.check(_native.lib().d3f_knn_match(_p(s), Ns, _p(t), Nt, C, k, _p(idx), _p(dist), _p(ws), nbytes, _stream()),
+                  "d3f_knn_match")
+    return idx, dist
+
+
+def knn_match_batched(source_desc, target_desc, seg, max_src, max_tgt, k):
+    """P ``knn_match`` problems by one pair of launches; ``seg`` / ``max_src`` / ``max_tgt`` as in ``mutual_nn_batched``.
+    Returns (idx [src rows,k], dist [src rows,k]) indexed by stacked source row, holding pair-local indices; rows outside
+    every segment and the rows of a pair with an empty target hold -1 / +inf."""
+    s, t = _f32(source_desc, "source_desc"), _f32(target_desc, "target_desc")
+    if not (seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 2 and seg.shape[1] == 4 and seg.is_contiguous()):
+        raise ValueError("seg must be a contiguous device int32 [P,4] tensor")
+    Ns, Nt, C, P, k = int(s.shape[0]), int(t.shape[0]), int(s.shape[1]), int(seg.shape[0]), _knn_k(k)
+    idx = torch.full((Ns, k), -1, dtype=torch.int32, device=s.device)
+    dist = torch.full((Ns, k), float('inf'), dtype=torch.float32, device=s.device)
+    nbytes = _native.lib().d3f_knn_match_batched_ws_bytes(Ns, P, int(max_src), int(max_tgt), k)
+    ws = _ws(nbytes, s.device)
+    _native.check(_native.lib().d3f_knn_match_batched(_p(s), Ns, _p(t), Nt, _p(seg), P, int(max_src), int(max_tgt), C, k,
+                                                      _p(idx), _p(dist), _p(ws), nbytes, _stream()),
+                  "d3f_knn_match_batched")
+    return idx, dist
+
+
 TOPK_MAX = _native.D3F_TOPK_MAX
 
 

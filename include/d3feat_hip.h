@@ -715,6 +715,27 @@ int d3f_mutual_nn_batched(const float* src_desc, int src_rows, const float* tgt_
                           int32_t* mutual, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * k-nearest descriptor matching -- the k best target rows of every source row, for the estimators that take plain,
+ * top-k or ratio-tested nearest neighbours instead of mutual ones.  csrc/knn_match.hpp has the rule: the distance is
+ * the reference's sqrt(2 - 2 S T^T) in f32, correctly rounded; neighbours ascend by (distance, target index), a NaN
+ * distance (2 - 2a < 0) first, like np.argmin; slot 0 is d3f_mutual_nn's row_argmin.  idx [Ns,k] int32, dist [Ns,k]
+ * f32 (NaN where the reference's distance is); slots beyond Nt hold -1 / +inf.  1 <= k <= D3F_KNN_MAX, C in
+ * {16, 32, 64, 128}.  The sweep of d3f_mutual_nn without its column side; a lane keeps its best k per row in
+ * registers, the column chunks (d3f_tunables.match_wgs) meet in the workspace: two launches, no atomics, the same
+ * result from run to run and for any chunking.
+ * The batched form has d3f_mutual_nn_batched's conventions: seg [P,4], outputs indexed by stacked source row, PAIR-LOCAL
+ * indices; the rows of a pair with an empty target get -1 / +inf, rows outside every segment are untouched.
+ * ---------------------------------------------------------------------------------------------- */
+#define D3F_KNN_MAX 8
+size_t d3f_knn_match_ws_bytes(int Ns, int Nt, int k);
+int d3f_knn_match(const float* src_desc, int Ns, const float* tgt_desc, int Nt, int C, int k, int32_t* idx, float* dist,
+                  void* ws, size_t ws_bytes, void* stream);
+size_t d3f_knn_match_batched_ws_bytes(int src_rows, int P, int max_src, int max_tgt, int k);
+int d3f_knn_match_batched(const float* src_desc, int src_rows, const float* tgt_desc, int tgt_rows, const int32_t* seg,
+                          int P, int max_src, int max_tgt, int C, int k, int32_t* idx, float* dist, void* ws,
+                          size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Keypoint selection -- replaces np.argsort(scores)[-k:] (test.py:56-57, geometric_registration/evaluate): the k
  * highest-scoring rows of every cloud of a stacked batch, in ascending (score, index) order like a stable argsort's
  * tail.  scores [rows]; seg [P,2] int32 on the device = {offset, length} per cloud; out [P,k] int32 CLOUD-LOCAL row
